@@ -36,6 +36,10 @@ concurrently replayed graph, from the committed rocprofv3 trace of this bench
 every field that comes from a counter file says so (`counters_from`: another box, a
 separate pass; the driver's box cannot re-collect them in a 0.08 s timed region); `cpu_baseline` times the CPU oracle (a port -- the
 reference has no CPU path) on a bounded sample of the same frames.
+
+`--dump-outputs DIR` writes, after the timed steps, rank 0's detections of the last timed step
+(what YoloEngine.results hands a caller, per slot) as DIR/<name>.npy: the inputs are seeded,
+so two builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -117,7 +121,52 @@ def parse_args():
     ap.add_argument("--model", choices=["yolov8n", "shufflenet"], default="yolov8n")
     ap.add_argument("--net", type=int, default=640, help="network input size (a multiple of 32)")
     ap.add_argument("--int8", action="store_true", help="int8 weight blob (per-output-channel scales)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's detections of the last timed step as DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.frames_per_step < 1:
+        ap.error("--steps and --frames-per-step must be >= 1, --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000     # --dump-outputs: under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, per_slot, frame_index, max_det):
+    """Write what the timed path handed its caller in the last timed step: per slot, the detections of that slot's frame
+    (YoloEngine.results), as fixed-shape arrays zero-padded past `num_dets`.  float32 for what the engine computes in
+    fp32 or as integers, float64 for the pose (rvec / tvec / quat are doubles in the C ABI).  `frame_index` is the global
+    synthetic frame number of each row.  When every slot would not fit in DUMP_LIMIT_BYTES, a fixed seeded sample of
+    slots is written (rows in slot order; `slot` says which)."""
+    B = len(per_slot)
+    row_bytes = max_det * (4 + 1 + 1 + 8 + 1 + 1 + 1 + 1) * 4 + max_det * (3 + 3 + 4) * 8 + 3 * 4
+    keep = np.arange(B)
+    if B * row_bytes > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(B, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+    n = len(keep)
+    arr = dict(slot=keep.astype(np.float32), frame_index=np.asarray(frame_index, np.float32)[keep],
+               num_dets=np.zeros(n, np.float32), boxes_xyxy=np.zeros((n, max_det, 4), np.float32),
+               scores=np.zeros((n, max_det), np.float32), class_id=np.zeros((n, max_det), np.float32),
+               image_points=np.zeros((n, max_det, 4, 2), np.float32), armor_size=np.zeros((n, max_det), np.float32),
+               valid=np.zeros((n, max_det), np.float32), n_lights=np.zeros((n, max_det), np.float32),
+               pnp_ok=np.zeros((n, max_det), np.float32), rvec=np.zeros((n, max_det, 3), np.float64),
+               tvec=np.zeros((n, max_det, 3), np.float64), quat_xyzw=np.zeros((n, max_det, 4), np.float64))
+    for r, s in enumerate(keep):
+        armors = per_slot[s]
+        arr["num_dets"][r] = len(armors)
+        for j, a in enumerate(armors):
+            arr["boxes_xyxy"][r, j] = a.bbox_xyxy
+            arr["scores"][r, j] = a.confidence
+            arr["class_id"][r, j] = int(a.armor_class)
+            arr["image_points"][r, j] = a.image_points()
+            arr["armor_size"][r, j] = int(a.size)
+            arr["valid"][r, j] = a.valid
+            arr["n_lights"][r, j] = a.n_lights
+            arr["pnp_ok"][r, j] = a.pnp_ok
+            arr["rvec"][r, j], arr["tvec"][r, j], arr["quat_xyzw"][r, j] = a.rvec, a.tvec, a.quat_xyzw
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arr.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def make_blob(args):
@@ -292,7 +341,10 @@ def main():
     dt = time.perf_counter() - t0
     R.barrier()
     dt_max = R.max_over_ranks(dt)
-    n_dets = sum(len(eng.results(s)) for s in range(B))
+    last_step = [eng.results(s) for s in range(B)]    # what the caller of the timed path receives from its last step
+    n_dets = sum(len(r) for r in last_step)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_step, my, eng.max_det)
 
     # ---- the timed configuration, under an assertion: first and last slot of the last batched step must equal a
     # single-slot step of the same engine on the same frame, bit for bit (every tile choice is bitwise neutral)

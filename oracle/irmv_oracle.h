@@ -8,8 +8,8 @@
  * PARITY UNPINNED: the reference (illini-robomaster/irmv_detection) asserts no
  * numerical output anywhere in its tests (test/yolo_test.cpp:36,106 check only a
  * box count and a latency), ships no model file, and delegates all arithmetic to
- * TensorRT / NPP / OpenCV, none of which is present in /root/reference or in this
- * image.  The reference cannot be compiled here (needs NvInfer.h, npp.h, OpenCV,
+ * TensorRT / NPP / OpenCV, none of which ships with the reference or with this
+ * build's toolchain.  The reference cannot be compiled here (needs NvInfer.h, npp.h, OpenCV,
  * ROS2 ament).  This oracle is therefore a restatement of the *published*
  * algorithms at the reference's call sites, cross-checked against torch-CPU,
  * numpy and scipy in tests/ ("Oracle").

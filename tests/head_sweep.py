@@ -2,7 +2,7 @@
 
 Test infrastructure (imports the oracle): used by tests/test_gpu_engine.py::test_head_error_over_unchosen_frames and by
 `scripts/probe.py headerr`.  The reference pins nothing here (its tests assert a box count and a latency,
-/root/reference/test/yolo_test.cpp:36,106; the network is an FP16 TensorRT plan, src/yolo_engine.cpp:105), so the stated
+reference test/yolo_test.cpp:36,106; the network is an FP16 TensorRT plan, src/yolo_engine.cpp:105), so the stated
 tolerance of this build is the contract, and this sweep is what it is stated ON.
 """
 from __future__ import annotations
