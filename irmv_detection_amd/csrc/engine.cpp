@@ -1407,27 +1407,36 @@ extern "C" void *irmv_engine_src_device_buffer(irmv_engine *e, int slot)
 // tile choices already measured in this process, keyed by layer shape and batch (engines are created
 // repeatedly in tests and by multi-slot nodes; the kernels and the device do not change in between)
 // Process-wide and shared by every engine on every thread: all accesses hold g_tune_mu.
+struct TuneEntry { int mt, nt, flags, ipw; };   // a choice as the IRMV_TUNE_CACHE file holds it (flags: tile_flags)
+static bool operator==(const TuneEntry &x, const TuneEntry &y) { return x.mt == y.mt && x.nt == y.nt && x.flags == y.flags && x.ipw == y.ipw; }
 static std::mutex g_tune_mu;
-static std::map<std::string, ConvCfg> g_tune_cache;
-static bool g_tune_file_loaded = false;
+static std::map<std::string, TuneEntry> g_tune_cache;
+static std::set<std::string> g_tune_files;   // IRMV_TUNE_CACHE paths already read
+
+// A tile's family and options as one word (the cache file's third column): LDS family, deep prefetch, direct kernel in the
+// LDS family's K order, pointwise kernel, two- / four-step staging, LDS family chunk-major over 2 / 4 images, 8-wave
+// workgroup, resident weights (ipw = images per workgroup, any value), their ping-pong form
+enum : int { T_LDS = 1, T_DEEP = 2, T_CT = 4, T_PW = 8, T_PF2 = 16, T_PF4 = 32, T_CM2 = 64, T_CM4 = 128, T_W8 = 256, T_WR = 512, T_PP = 1024 };
+static int tile_flags(const ConvCfg &c)
+{
+    return (c.lds ? T_LDS : 0) | (c.deep ? T_DEEP : 0) | (c.ct ? T_CT : 0) | (c.pw ? T_PW : 0) | (c.pf2 ? T_PF2 : 0) | (c.pf4 ? T_PF4 : 0) |
+           (c.cm == 2 ? T_CM2 : 0) | (c.cm == 4 ? T_CM4 : 0) | (c.w8 ? T_W8 : 0) | (c.wr ? T_WR : 0) | (c.pp ? T_PP : 0);
+}
+static TuneEntry tune_entry(const ConvCfg &c) { return {c.mt, c.nt, tile_flags(c), c.ipw}; }
 
 // IRMV_TUNE_CACHE=<file>: persist the measured choices so that a profiled run (rocprofv3 --pmc ...)
-// replays exactly the tiles of the benchmarked run without the tuning launches in its trace.
+// replays exactly the tiles of the benchmarked run without the tuning launches in its trace.  A path is read the first
+// time an engine sees it; its entries replace the process's own for the same key.
 static void tune_cache_load()
 {
-    std::lock_guard<std::mutex> lk(g_tune_mu);
-    if (g_tune_file_loaded) return;
-    g_tune_file_loaded = true;
     const char *path = getenv("IRMV_TUNE_CACHE");
     if (!path) return;
+    std::lock_guard<std::mutex> lk(g_tune_mu);
+    if (!g_tune_files.insert(path).second) return;
     std::ifstream f(path);
     std::string key;
-    int mt, nt, lds, ipw;
-    while (f >> key >> mt >> nt >> lds >> ipw) {
-        ConvCfg c{};
-        c.mt = mt; c.nt = nt; c.lds = (lds & 1) != 0; c.deep = (lds & 2) != 0; c.ct = (lds & 4) != 0; c.pw = (lds & 8) != 0; c.pf2 = (lds & 16) != 0; c.pf4 = (lds & 32) != 0; c.cm = (lds & 64) ? 2 : ((lds & 128) ? 4 : 0); c.w8 = (lds & 256) != 0; c.wr = (lds & 512) != 0; c.pp = (lds & 1024) != 0; c.ipw = ipw;   // bit 0 LDS family, 1 deep prefetch, 2 direct kernel in the LDS family's K order, 3 pointwise kernel, 4 two-step staging, 5 four-step staging, 6 / 7 LDS family chunk-major over 2 / 4 images, 8 LDS family 8-wave workgroup, 9 LDS family with resident weights (ipw = images per workgroup, any value), 10 its ping-pong form
-        g_tune_cache[key] = c;
-    }
+    TuneEntry t;
+    while (f >> key >> t.mt >> t.nt >> t.flags >> t.ipw) g_tune_cache[key] = t;
 }
 
 static void tune_cache_save()
@@ -1436,8 +1445,7 @@ static void tune_cache_save()
     if (!path) return;
     std::lock_guard<std::mutex> lk(g_tune_mu);
     std::ofstream f(path);
-    for (auto &kv : g_tune_cache)
-        f << kv.first << ' ' << kv.second.mt << ' ' << kv.second.nt << ' ' << ((kv.second.lds ? 1 : 0) | (kv.second.deep ? 2 : 0) | (kv.second.ct ? 4 : 0) | (kv.second.pw ? 8 : 0) | (kv.second.pf2 ? 16 : 0) | (kv.second.pf4 ? 32 : 0) | (kv.second.cm == 2 ? 64 : 0) | (kv.second.cm == 4 ? 128 : 0) | (kv.second.w8 ? 256 : 0) | (kv.second.wr ? 512 : 0) | (kv.second.pp ? 1024 : 0)) << ' ' << kv.second.ipw << '\n';
+    for (auto &kv : g_tune_cache) f << kv.first << ' ' << kv.second.mt << ' ' << kv.second.nt << ' ' << kv.second.flags << ' ' << kv.second.ipw << '\n';
 }
 
 static int lds_index(int nt) { return nt == 8 ? 3 : (nt == 4 ? 2 : (nt == 2 ? 1 : 0)); }
@@ -1474,266 +1482,211 @@ static void cfg_name(const ConvCfg &c, char *buf, int n)
 // changes a single output bit (tests/test_gpu_engine.py::test_tile_choice_is_bitwise_neutral).
 static void fill_conv_args(const irmv_engine *e, const Op &op, int first, int count, ConvArgs &a, bool fused = false);
 
-// A candidate of the autotuner: the layer's own configuration with a tile shape and family, every launch-time option off
-// (the candidates below switch on the one or two they are about).
-static ConvCfg tile_cfg(const ConvCfg &base, int mt, int nt, bool lds, int ipw)
+// A candidate of the autotuner: the layer's own configuration with a tile shape, family and options (tile_flags' word).
+static ConvCfg tile_cfg(const ConvCfg &base, int mt, int nt, int flags, int ipw)
 {
     ConvCfg c = base;
-    c.mt = mt; c.nt = nt; c.lds = lds; c.ipw = ipw;
-    c.deep = false; c.ct = false; c.pw = false; c.pf2 = false; c.pf4 = false; c.cm = 0; c.w8 = false; c.wr = false; c.pp = false;
+    c.mt = mt; c.nt = nt; c.ipw = ipw;
+    c.lds = flags & T_LDS; c.deep = flags & T_DEEP; c.ct = flags & T_CT; c.pw = flags & T_PW; c.pf2 = flags & T_PF2; c.pf4 = flags & T_PF4;
+    c.cm = (flags & T_CM2) ? 2 : ((flags & T_CM4) ? 4 : 0); c.w8 = flags & T_W8; c.wr = flags & T_WR; c.pp = flags & T_PP;
     return c;
+}
+
+// The environment switches of the tuner, read once per engine: each takes effect for every engine created after it is set.
+struct TuneSwitches {
+    bool untuned, verbose, warn;        // IRMV_AUTOTUNE=0, IRMV_AUTOTUNE_VERBOSE, IRMV_TUNE_WARN
+    const char *force_s2, *force_wres;  // IRMV_FORCE_S2=lds|ct|deep, IRMV_FORCE_WRES=<n> (parity tests)
+    bool force_pw, force_pwn, force_cm, force_w8, force_nt8, force_pf4;
+    bool no_pw, no_pwn, no_pf2, no_pf4, no_cm, no_w8, no_nt8, no_wres, no_deep;
+};
+
+static TuneSwitches tune_switches()
+{
+    auto on = [](const char *name) { return getenv(name) != nullptr; };
+    const char *at = getenv("IRMV_AUTOTUNE"), *nd = getenv("IRMV_NO_DEEP");
+    TuneSwitches s;
+    s.untuned = at && at[0] == '0'; s.verbose = on("IRMV_AUTOTUNE_VERBOSE"); s.warn = on("IRMV_TUNE_WARN");
+    s.force_s2 = getenv("IRMV_FORCE_S2"); s.force_wres = getenv("IRMV_FORCE_WRES");
+    s.force_pw = on("IRMV_FORCE_PW"); s.force_pwn = on("IRMV_FORCE_PWN"); s.force_cm = on("IRMV_FORCE_CM");
+    s.force_w8 = on("IRMV_FORCE_W8"); s.force_nt8 = on("IRMV_FORCE_NT8"); s.force_pf4 = on("IRMV_FORCE_PF4");
+    s.no_pw = on("IRMV_NO_PW"); s.no_pwn = on("IRMV_NO_PWN"); s.no_pf2 = on("IRMV_NO_PF2"); s.no_pf4 = on("IRMV_NO_PF4");
+    s.no_cm = on("IRMV_NO_CM"); s.no_w8 = on("IRMV_NO_W8"); s.no_nt8 = on("IRMV_NO_NT8"); s.no_wres = on("IRMV_NO_WRES");
+    s.no_deep = nd && nd[0] == '1';
+    return s;
+}
+
+// forced: an IRMV_FORCE_* switch puts the layer on this candidate (parity tests) -- the last forced one that runs is the choice
+struct TuneCand { ConvCfg c; bool forced; };
+
+// Every candidate of one conv layer at one batch, in the order the tuner times them (IRMV_AUTOTUNE=0 takes the first that
+// runs; a cached choice is replayed only if it is one of them).  Launches nothing: a candidate is listed if the family offers
+// the tile for this layer and its LDS geometry fits; run_conv still has the last word.  lds_ok: the layer's kernel family;
+// want_fuse: the fused 1x1 epilogue, which needs an LDS-family tile that owns all 64 channels (nt = 4).
+static std::vector<TuneCand> tune_candidates(const Op &op, const ConvArgs &a, int count, bool want_fuse, bool lds_ok, const TuneSwitches &sw, int num_cus)
+{
+    std::vector<TuneCand> v;
+    // IRMV_FORCE_S2=lds|ct|deep (parity test): the stride-2 layers of the LDS family on ONE of their three bit-identical
+    // implementations -- the LDS kernel, the direct kernel walking K chunk-major, its deep-prefetch form
+    const bool s2 = sw.force_s2 && lds_ok && op.cfg.stride == 2;
+    auto add = [&](const ConvCfg &c, bool forced = false) {
+        if (op.cout_pad % (16 * c.nt) != 0) return;
+        if (s2 && !forced && strcmp(c.lds ? "lds" : (c.deep ? "deep" : "ct"), sw.force_s2) != 0) return;
+        if (c.wr ? !(op.w_lds[2] && conv_wres_bytes(a, c.stride, c.pp) > 0)
+                 : c.lds && !(op.w_lds[lds_index(c.nt)] && conv_lds_bytes(a, c.stride, c.mt, c.nt, nullptr, c.w8) > 0)) return;
+        v.push_back({c, forced});
+    };
+    const int ipw_max = lds_ok ? std::min(4, count) : 1;
+    for (int mt = 1; mt <= 4; mt *= 2)
+        for (int nt = 1; nt <= 4; nt *= 2)
+            for (int ipw = 1; ipw <= ipw_max; ipw *= 2)
+                if (!want_fuse || nt == 4) add(tile_cfg(op.cfg, mt, nt, lds_ok ? T_LDS : 0, ipw));
+    // LDS family, smallest pixel tile, staging two steps ahead (layers whose step is shorter than a memory round trip)
+    if (lds_ok && !want_fuse && !sw.no_pf2)
+        for (int nt = 1; nt <= 4; nt *= 2)
+            for (int ipw = 1; ipw <= ipw_max; ipw *= 2) add(tile_cfg(op.cfg, 1, nt, T_LDS | T_PF2, ipw));
+    // ... and four steps ahead: layers of four or more chunks on maps small enough for four register sets (a lone frame's
+    // 20 x 20 layers: every step of a workgroup in flight at once)
+    if (lds_ok && !want_fuse && !sw.no_pf4 && op.cin >= 128 && op.w_lds[0]) add(tile_cfg(op.cfg, 1, 1, T_LDS | T_PF4, 1), sw.force_pf4);
+    // LDS family, chunk-major over the workgroup's images: a chunk's weights staged once for all of them
+    if (lds_ok && !sw.no_cm)
+        for (int mt = 1; mt <= 2; mt *= 2)
+            for (int ipw = 2; ipw <= std::min(mt == 1 ? 4 : 2, count); ipw *= 2)
+                if (!(want_fuse && mt == 1 && ipw == 2)) add(tile_cfg(op.cfg, mt, 4, T_LDS | (ipw == 2 ? T_CM2 : T_CM4), ipw), sw.force_cm);   // (no instantiation with the fused 1x1)
+    // LDS family, stride 2: one 8-wave workgroup per CU on a block twice as tall (mt = 2 fits LDS, weights staged for
+    // twice the pixels)
+    if (lds_ok && op.cfg.stride == 2 && !want_fuse && !sw.no_w8)
+        for (int mt = 1; mt <= 2; mt *= 2)
+            for (int ipw = 1; ipw <= ipw_max; ipw *= 2)
+                for (int cmv = 0; cmv < 2; cmv++)
+                    if (!cmv || (mt == 2 && ipw == 2) || (mt == 1 && ipw == 4)) add(tile_cfg(op.cfg, mt, 4, T_LDS | T_W8 | (cmv ? (ipw == 2 ? T_CM2 : T_CM4) : 0), ipw), sw.force_w8);
+    // ... and with all of 128 output channels per workgroup (nt = 8, mt = 1): these layers are bound by what a CU can stage
+    // from L2 (12 B/clk), and the stride-2 patch -- four input pixels per output pixel -- is then fetched once per 128
+    // channels instead of once per 64; chunk-major over two images halves the weight staging on top
+    if (lds_ok && op.cfg.stride == 2 && !want_fuse && !sw.no_w8 && !sw.no_nt8)
+        for (int ipw = 1; ipw <= ipw_max; ipw *= 2)
+            for (int cmv = 0; cmv < 2; cmv++)
+                if (!cmv || ipw == 2) add(tile_cfg(op.cfg, 1, 8, T_LDS | T_W8 | (cmv ? T_CM2 : 0), ipw), sw.force_nt8);
+    // LDS family, Cin = Cout = 64, stride 1: resident weights (one 8-wave workgroup per CU walks ipw images at its tile
+    // position; lockstep, or as two ping-pong groups of four waves).  ipw: the smallest that lets the chip hold the
+    // grid in one round, and half of it.
+    if (lds_ok && count >= 2 && !sw.no_wres)
+        for (int ppv = 0; ppv < 2; ppv++) {
+            const int wgt = conv_wres_tiles(a, op.cfg.stride, ppv != 0);
+            if (wgt <= 0) continue;
+            int ipw1 = 1;
+            while (ipw1 < count && (long)wgt * ((count + ipw1 - 1) / ipw1) > num_cus) ipw1++;
+            const int cand[3] = {ipw1, (ipw1 + 1) / 2, std::min(count, 2 * ipw1)};
+            for (int k = 0; k < 3; k++)
+                if (k == 0 || (cand[k] != cand[0] && (k == 1 || cand[2] != cand[1]))) add(tile_cfg(op.cfg, 2, 4, T_LDS | T_WR | (ppv ? T_PP : 0), cand[k]));
+        }
+    // parity tests: IRMV_FORCE_WRES=<n> puts every eligible layer on the resident-weights kernel with n images per
+    // workgroup -- the ping-pong form (listed last, so it wins) where the map tiles into its blocks (n < 0: never), else the
+    // lockstep form
+    if (sw.force_wres && lds_ok && count >= 2) {
+        const int n = atoi(sw.force_wres);
+        for (int ppv = 0; ppv <= (n > 0 ? 1 : 0); ppv++) add(tile_cfg(op.cfg, 2, 4, T_LDS | T_WR | (ppv ? T_PP : 0), std::max(1, std::min(count, n < 0 ? -n : n))), true);
+    }
+    // 1x1 layers: the persistent pointwise kernel (same operands, same k order as the direct kernel)
+    if (conv_pw_eligible(op.cfg, a) && !sw.no_pw) {
+        add(tile_cfg(op.cfg, 2, 4, T_PW, 1), sw.force_pw);
+        // ... and its multi-block form: one workgroup runs a pixel tile against 2 / 4 output-channel blocks (input read once)
+        for (int nbw = 2; nbw <= 4 && !sw.no_pwn; nbw *= 2)
+            if (conv_pw_lds_bytes(a, nbw)) add(tile_cfg(op.cfg, 2, 4, T_PW, nbw), sw.force_pwn);   // (forced: the widest form offered)
+    }
+    // A layer of the LDS family may also run on the direct kernel walking K in that family's order on its weights (ct):
+    // bit-identical, so the family rule still holds.  Offered where the direct kernel has a chance: stride 2.
+    if (lds_ok && !want_fuse && op.w_lds[0] && op.cfg.stride == 2 && !op.cfg.cin16)
+        for (int mt = 1; mt <= 4; mt *= 2)
+            for (int nt = 1; nt <= 4; nt *= 2) add(tile_cfg(op.cfg, mt, nt, T_CT, 1));
+    // single-frame steps: the latency variants of the direct kernel (deep prefetch ring), same rule.
+    // Batched steps: offered to the 1x1 layers only (4..16 k-steps: the ring then holds the wave's whole K range).
+    if ((count == 1 || op.cfg.ks == 1) && !want_fuse && !sw.no_deep && !op.cfg.cin16 && !op.cfg.out_f32 && op.cfg.act == 1 && (!lds_ok || op.w_lds[0])) {
+        const int tiles[4][2] = {{1, 1}, {2, 1}, {1, 2}, {1, 4}};
+        for (auto &t : tiles) add(tile_cfg(op.cfg, t[0], t[1], T_DEEP | (lds_ok ? T_CT : 0), 1));
+    }
+    return v;
 }
 
 static int autotune_convs(irmv_engine *e)
 {
-    const char *env = getenv("IRMV_AUTOTUNE");
-    const bool no_tuning = env && env[0] == '0';   // no timing launches: every layer takes the first legal tile of ITS family (same K order as a tuned engine: bit-identical)
+    const TuneSwitches sw = tune_switches();
     tune_cache_load();
     hipEvent_t ea, eb;
     HIP_TRY(hipEventCreate(&ea));
     HIP_TRY(hipEventCreate(&eb));
     const int counts[2] = {stream_share(e, e->cfg.num_slots), 1};   // the batch one graph actually runs; single frame
-    const bool verbose = getenv("IRMV_AUTOTUNE_VERBOSE") != nullptr;
-    const bool only_direct = false;   // (IRMV_CONV_FAMILY=direct, which changed the K order of the 3x3 layers, was removed in round 4)
     for (Op &op : e->ops) {
         if (op.kind != OP_CONV) continue;
         for (int pass = 0; pass < (counts[0] > 1 ? 2 : 1); pass++) {
+            const int count = counts[pass];
             ConvArgs a;
             const bool fuse_k16 = op.fuse_next >= 0 && op.cfg.cin16;   // the keypoint final in the direct kernel's epilogue: any pixel tile (nt = 1 is the layer's only one)
             bool want_fuse = op.fuse_next >= 0 && !fuse_k16;
-            fill_conv_args(e, op, 0, counts[pass], a, want_fuse || fuse_k16);
+            fill_conv_args(e, op, 0, count, a, want_fuse || fuse_k16);
             if (want_fuse) {   // the fused epilogue needs an LDS-family tile that owns all 64 channels (nt = 4)
                 bool f_ok = false;
-                for (int mt = 1; mt <= 4 && !f_ok; mt *= 2) f_ok = !only_direct && op.w_lds[2] && conv_lds_bytes(a, op.cfg.stride, mt, 4, nullptr) > 0;
+                for (int mt = 1; mt <= 4 && !f_ok; mt *= 2) f_ok = op.w_lds[2] && conv_lds_bytes(a, op.cfg.stride, mt, 4, nullptr) > 0;
                 if (!f_ok) {
                     op.fuse_next = -1;
                     want_fuse = false;
-                    fill_conv_args(e, op, 0, counts[pass], a, false);
+                    fill_conv_args(e, op, 0, count, a, false);
                 }
             }
-            float best = 1e30f;
-            ConvCfg best_cfg = pass == 0 ? op.cfg : op.cfg_one;
             // Kernel family by a rule that does not depend on the batch (the two families walk K in
             // different orders): LDS-staged whenever some tile of it fits this layer, else direct.
             bool lds_ok = false;
-            if (!only_direct && op.cfg.ks == 3 && op.cfg.act == 1 && !op.cfg.out_f32)
+            if (op.cfg.ks == 3 && op.cfg.act == 1 && !op.cfg.out_f32)
                 for (int mt = 1; mt <= 4 && !lds_ok; mt *= 2)
-                    for (int nt = 1; nt <= 4 && !lds_ok; nt *= 2) {
-                        int pr = 0;
-                        const int li = nt == 4 ? 2 : (nt == 2 ? 1 : 0);
-                        lds_ok = op.w_lds[li] && conv_lds_bytes(a, op.cfg.stride, mt, nt, &pr) > 0;
-                    }
-            // IRMV_FORCE_S2=lds|ct|deep (parity test): the stride-2 layers of the LDS family on ONE of their three bit-identical
-            // implementations -- the LDS kernel, the direct kernel walking K chunk-major, its deep-prefetch form
-            const char *force_s2 = getenv("IRMV_FORCE_S2");
+                    for (int nt = 1; nt <= 4 && !lds_ok; nt *= 2) lds_ok = op.w_lds[lds_index(nt)] && conv_lds_bytes(a, op.cfg.stride, mt, nt, nullptr) > 0;
             char key[160];
             snprintf(key, sizeof key, "gfx950.t5|%d.%d.%d.%d.%d.%d|%dx%d>%dx%d|c%d.%d.%d.%d>%d|ld%d.%d.%d|n%d|%d", op.cfg.ks, op.cfg.stride,   // ".t5": the table format / flag set of round 5 -- entries of another round's file never match, so they are re-tuned, not reinterpreted
                      (int)op.cfg.cin16, op.cfg.act, (int)op.cfg.out_f32, (int)lds_ok, a.Hin, a.Win, a.Hout, a.Wout, a.s0.C, a.s1.C, a.s0.shift,
-                     a.s1.shift, a.cout_pad, a.s0.ld, a.s1.ld, a.out_ld, counts[pass], (a.res ? 1 : 0) + 2 * a.n2);
-            // A cached choice (this process, or the IRMV_TUNE_CACHE file) is replayed only if it is a legal tile of THIS
-            // layer at THIS batch: tile shape offered by the family, channel split divides cout, images per workgroup within
-            // the batch, LDS geometry fits, and the fused epilogue's constraints.  Anything else is re-tuned.
+                     a.s1.shift, a.cout_pad, a.s0.ld, a.s1.ld, a.out_ld, count, (a.res ? 1 : 0) + 2 * a.n2);
+            const std::vector<TuneCand> cands = tune_candidates(op, a, count, want_fuse, lds_ok, sw, e->num_cus);
+            // a forced layer neither replays a cached choice nor leaves its own for a later engine; nor does an untuned one
+            const bool forced = (sw.force_s2 && lds_ok && op.cfg.stride == 2) || std::any_of(cands.begin(), cands.end(), [](const TuneCand &k) { return k.forced; });
+            ConvCfg best_cfg = pass == 0 ? op.cfg : op.cfg_one;
             bool have_hit = false;
-            {
+            if (!forced && !sw.untuned && !sw.verbose) {   // a cached choice (this process, or an IRMV_TUNE_CACHE file) is replayed if it is a candidate
                 std::lock_guard<std::mutex> lk(g_tune_mu);
                 auto hit = g_tune_cache.find(key);
-                if (hit != g_tune_cache.end() && !verbose && !no_tuning && !(force_s2 && lds_ok && op.cfg.stride == 2)) {
-                    const ConvCfg &h = hit->second;
-                    const bool pow2 = (h.mt == 1 || h.mt == 2 || h.mt == 4) && (h.nt == 1 || h.nt == 2 || h.nt == 4 || (h.nt == 8 && h.w8 && h.mt == 1)) && (h.ipw == 1 || h.ipw == 2 || h.ipw == 4 || (h.wr && h.ipw >= 1));
-                    // family: LDS-staged, or (single-frame steps only) its chunk-major stand-in on the direct kernel; never both flags
-                    const bool fam_ok = lds_ok ? ((h.lds && !h.ct && !h.deep) || (!h.lds && h.ct && !want_fuse && (!h.deep || counts[pass] == 1)))
-                                               : (!h.lds && !h.ct && (!h.deep || counts[pass] == 1 || op.cfg.ks == 1));
-                    bool ok = pow2 && op.cout_pad % (16 * h.nt) == 0 && h.ipw <= counts[pass] && fam_ok && (!want_fuse || h.nt == 4);
-                    if (h.pw) ok = !h.lds && !h.ct && !h.deep && (h.ipw == 1 || ((h.ipw == 2 || h.ipw == 4) && conv_pw_lds_bytes(a, h.ipw) > 0 && !getenv("IRMV_NO_PWN"))) &&
-                                   conv_pw_eligible(op.cfg, a) && !getenv("IRMV_NO_PW");   // one tile shape; ipw = output-channel blocks per workgroup
-                    if (h.pw && ok && getenv("IRMV_FORCE_PWN") && h.ipw == 1 && (conv_pw_lds_bytes(a, 2) > 0 || conv_pw_lds_bytes(a, 4) > 0)) ok = false;   // (parity tests)
-                    if (!h.pw && getenv("IRMV_FORCE_PW") && conv_pw_eligible(op.cfg, a)) ok = false;                                  // (parity tests)
-                    if (ok && h.lds && !h.wr) {
-                        const int li = lds_index(h.nt);
-                        ok = op.w_lds[li] && conv_lds_bytes(a, op.cfg.stride, h.mt, h.nt, nullptr, h.w8) > 0;
-                    }
-                    if (ok && h.wr) ok = !getenv("IRMV_NO_WRES") && h.lds && !h.pf2 && !h.cm && !h.w8 && h.mt == 2 && h.nt == 4 && op.w_lds[2] && conv_wres_bytes(a, op.cfg.stride, h.pp) > 0;
-                    if (ok && getenv("IRMV_FORCE_WRES") && lds_ok && op.w_lds[2] && counts[pass] >= 2 && conv_wres_bytes(a, op.cfg.stride, false) > 0) ok = false;   // parity tests: always the forced form
-                    if (ok && !h.lds && !h.pw) ok = h.ipw == 1;
-                    if (ok && h.deep) ok = (h.mt == 1 || (h.mt == 2 && h.nt == 1)) && !op.cfg.cin16 && !op.cfg.out_f32 && op.cfg.act == 1;
-                    if (ok && h.ct) ok = op.w_lds[0] != nullptr;
-                    if (ok && h.pf2) ok = h.lds && h.mt == 1 && !want_fuse;
-                    if (ok && h.pf4) ok = !getenv("IRMV_NO_PF4") && h.lds && !h.pf2 && !h.cm && !h.w8 && !h.wr && h.mt == 1 && h.nt == 1 && h.ipw == 1 && op.cin >= 128 && !want_fuse;   // (the only form the tuner generates, times and the bitwise tests cover)
-                    if (ok && h.cm && h.nt != 8) ok = !getenv("IRMV_NO_CM") && h.lds && !h.pf2 && h.cm == h.ipw && h.nt == 4 && ((h.mt == 1 && (!want_fuse || h.cm == 4)) || (h.mt == 2 && h.cm == 2));
-                    if (ok && h.w8 && h.nt == 4) ok = !getenv("IRMV_NO_W8") && h.lds && op.cfg.stride == 2 && !want_fuse && !h.pf2 && (h.mt == 1 || h.mt == 2) &&
-                                                     (h.cm == 0 || (h.cm == h.ipw && ((h.mt == 2 && h.cm == 2) || (h.mt == 1 && h.cm == 4))));
-                    if (ok && h.w8 && h.nt == 8) ok = !getenv("IRMV_NO_W8") && !getenv("IRMV_NO_NT8") && h.lds && op.cfg.stride == 2 && !want_fuse && !h.pf2 && h.mt == 1 && op.w_lds[3] &&
-                                                     (h.cm == 0 || (h.cm == 2 && h.ipw == 2));
-                    if (ok && h.w8 && h.nt != 4 && h.nt != 8) ok = false;
-                    if (ok && h.cm && h.nt == 8 && !h.w8) ok = false;
-                    if (ok && !h.w8 && getenv("IRMV_FORCE_W8") && lds_ok && op.cfg.stride == 2) ok = false;
-                    if (ok && !h.pf4 && getenv("IRMV_FORCE_PF4") && lds_ok && op.cin >= 128 && !want_fuse) ok = false;   // parity tests: re-tune so that the forced tile is tried
-                    if (ok && h.nt != 8 && getenv("IRMV_FORCE_NT8") && lds_ok && op.cfg.stride == 2 && op.w_lds[3] && !want_fuse) ok = false;   // parity tests: the 128-channel workgroup wherever it exists
-                    if (ok && !h.cm && getenv("IRMV_FORCE_CM") && lds_ok && counts[pass] >= 2) ok = false;   // parity tests: the chunk-major tiles wherever one exists
-                    if (ok) {
-                        best_cfg = op.cfg;
-                        best_cfg.mt = h.mt; best_cfg.nt = h.nt; best_cfg.lds = h.lds; best_cfg.ipw = h.ipw; best_cfg.deep = h.deep; best_cfg.ct = h.ct; best_cfg.pw = h.pw; best_cfg.pf2 = h.pf2; best_cfg.pf4 = h.pf4; best_cfg.cm = h.cm; best_cfg.w8 = h.w8; best_cfg.wr = h.wr; best_cfg.pp = h.pp;
-                        best = 0.f;
-                        have_hit = true;
-                    } else if (getenv("IRMV_AUTOTUNE_VERBOSE") || getenv("IRMV_TUNE_WARN"))
-                        fprintf(stderr, "[autotune] cached tile for %s rejected (mt %d nt %d lds %d ipw %d): re-tuning\n", key, h.mt, h.nt, (int)h.lds, h.ipw);
+                if (hit != g_tune_cache.end()) {
+                    const TuneEntry &h = hit->second;
+                    auto it = std::find_if(cands.begin(), cands.end(), [&](const TuneCand &k) { return tune_entry(k.c) == h; });
+                    if (it != cands.end()) { best_cfg = it->c; have_hit = true; }
+                    else if (sw.warn) fprintf(stderr, "[autotune] cached tile for %s rejected (mt %d nt %d lds %d ipw %d): re-tuning\n", key, h.mt, h.nt, h.flags & 1, h.ipw);
                 }
             }
-            if (!have_hit)
-            {
-                auto time_cfg = [&](const ConvCfg &c) -> int {
-                    if (no_tuning && best < 1e29f) return IRMV_OK;   // IRMV_AUTOTUNE=0: the first candidate that runs is the choice
-                    if (force_s2 && lds_ok && op.cfg.stride == 2) {
-                        const char *kind = c.lds ? "lds" : (c.deep ? "deep" : "ct");
-                        if (strcmp(kind, force_s2) != 0) return IRMV_OK;
-                    }
-                    bool ok = true;
-                    for (int i = 0; i < 2 && ok; i++) ok = run_conv(op, c, a, counts[pass], e->stream);
-                    if (!ok) return IRMV_OK;
-                    if (no_tuning) { best = 0.f; best_cfg = c; return IRMV_OK; }
-                    float ms = 1e30f;   // best of 3 bursts of 4
-                    for (int rep = 0; rep < 3; rep++) {
-                        HIP_TRY(hipEventRecord(ea, e->stream));
-                        for (int i = 0; i < 4; i++) run_conv(op, c, a, counts[pass], e->stream);
-                        HIP_TRY(hipEventRecord(eb, e->stream));
-                        HIP_TRY(hipEventSynchronize(eb));
-                        float t = 0.f;
-                        HIP_TRY(hipEventElapsedTime(&t, ea, eb));
-                        ms = t < ms ? t : ms;
-                    }
-                    if (verbose) {
-                        char nm[48];
-                        cfg_name(c, nm, sizeof nm);
-                        fprintf(stderr, "[autotune] %-22s count=%-2d %-28s %8.2f us\n", op.layer.c_str(), counts[pass], nm, ms / 4 * 1e3);
-                    }
-                    if (ms < best) { best = ms; best_cfg = c; }
-                    return IRMV_OK;
-                };
-                const int fam = lds_ok ? 1 : 0;
-                for (int mt = 1; mt <= 4; mt *= 2)
-                    for (int nt = 1; nt <= 4; nt *= 2)
-                        for (int ipw = 1; ipw <= (fam == 1 ? std::min(4, counts[pass]) : 1); ipw *= 2) {
-                            if (op.cout_pad % (16 * nt) != 0) continue;
-                            if (want_fuse && nt != 4) continue;
-                            ConvCfg c = tile_cfg(op.cfg, mt, nt, fam == 1, ipw);
-                            TRY(time_cfg(c));
-                        }
-                // LDS family, smallest pixel tile, staging two steps ahead (layers whose step is shorter than a memory round trip)
-                if (fam == 1 && !want_fuse && !getenv("IRMV_NO_PF2"))
-                    for (int nt = 1; nt <= 4; nt *= 2)
-                        for (int ipw = 1; ipw <= std::min(4, counts[pass]); ipw *= 2) {
-                            if (op.cout_pad % (16 * nt) != 0) continue;
-                            ConvCfg c = tile_cfg(op.cfg, 1, nt, true, ipw);
-                            c.pf2 = true;
-                            TRY(time_cfg(c));
-                        }
-                // ... and four steps ahead: layers of four or more chunks on maps small enough for four register sets (a lone frame's
-                // 20 x 20 layers: every step of a workgroup in flight at once)
-                if (fam == 1 && !want_fuse && !getenv("IRMV_NO_PF4") && op.cin >= 128 && op.w_lds[0]) {
-                    ConvCfg c = tile_cfg(op.cfg, 1, 1, true, 1);
-                    c.pf4 = true;
-                    TRY(time_cfg(c));
-                    if (getenv("IRMV_FORCE_PF4") && run_conv(op, c, a, counts[pass], e->stream)) { best = 0.f; best_cfg = c; }   // parity tests: wherever it exists
+            float best = 1e30f;
+            for (size_t i = 0; i < cands.size() && !have_hit; i++) {
+                const ConvCfg &c = cands[i].c;
+                if (cands[i].forced) {
+                    if (run_conv(op, c, a, count, e->stream)) { best = 0.f; best_cfg = c; }
+                    continue;
                 }
-                // LDS family, chunk-major over the workgroup's images: a chunk's weights staged once for all of them
-                if (fam == 1 && op.cout_pad % 64 == 0 && !getenv("IRMV_NO_CM"))
-                    for (int mt = 1; mt <= 2; mt *= 2)
-                        for (int ipw = 2; ipw <= std::min(mt == 1 ? 4 : 2, counts[pass]); ipw *= 2) {
-                            if (want_fuse && mt == 1 && ipw == 2) continue;   // (no instantiation with the fused 1x1)
-                            ConvCfg c = tile_cfg(op.cfg, mt, 4, true, ipw);
-                            c.cm = ipw;
-                            TRY(time_cfg(c));
-                            if (getenv("IRMV_FORCE_CM") && run_conv(op, c, a, counts[pass], e->stream)) { best = 0.f; best_cfg = c; }   // parity tests
-                        }
-                // LDS family, stride 2: one 8-wave workgroup per CU on a block twice as tall (mt = 2 fits LDS, weights staged for
-                // twice the pixels)
-                if (fam == 1 && op.cfg.stride == 2 && !want_fuse && op.cout_pad % 64 == 0 && !getenv("IRMV_NO_W8"))
-                    for (int mt = 1; mt <= 2; mt *= 2)
-                        for (int ipw = 1; ipw <= std::min(4, counts[pass]); ipw *= 2)
-                            for (int cmv = 0; cmv < 2; cmv++) {
-                                if (cmv && !((mt == 2 && ipw == 2) || (mt == 1 && ipw == 4))) continue;
-                                ConvCfg c = tile_cfg(op.cfg, mt, 4, true, ipw);
-                                c.w8 = true; c.cm = cmv ? ipw : 0;
-                                TRY(time_cfg(c));
-                                if (getenv("IRMV_FORCE_W8") && run_conv(op, c, a, counts[pass], e->stream)) { best = 0.f; best_cfg = c; }   // parity tests
-                            }
-                // ... and with all of 128 output channels per workgroup (nt = 8, mt = 1): these layers are bound by what a CU can stage
-                // from L2 (12 B/clk), and the stride-2 patch -- four input pixels per output pixel -- is then fetched once per 128
-                // channels instead of once per 64; chunk-major over two images halves the weight staging on top
-                if (fam == 1 && op.cfg.stride == 2 && !want_fuse && op.cout_pad % 128 == 0 && op.w_lds[3] && !getenv("IRMV_NO_W8") && !getenv("IRMV_NO_NT8"))
-                    for (int ipw = 1; ipw <= std::min(4, counts[pass]); ipw *= 2)
-                        for (int cmv = 0; cmv < 2; cmv++) {
-                            if (cmv && ipw != 2) continue;
-                            ConvCfg c = tile_cfg(op.cfg, 1, 8, true, ipw);
-                            c.w8 = true; c.cm = cmv ? 2 : 0;
-                            TRY(time_cfg(c));
-                            if (getenv("IRMV_FORCE_NT8") && run_conv(op, c, a, counts[pass], e->stream)) { best = 0.f; best_cfg = c; }   // parity tests
-                        }
-                // LDS family, Cin = Cout = 64, stride 1: resident weights (one 8-wave workgroup per CU walks ipw images at its tile
-                // position; lockstep, or as two ping-pong groups of four waves).  ipw: the smallest that lets the chip hold the
-                // grid in one round, and half of it.
-                if (fam == 1 && counts[pass] >= 2 && op.w_lds[2] && !getenv("IRMV_NO_WRES"))
-                    for (int ppv = 0; ppv < 2; ppv++) {
-                        const int wgt = conv_wres_tiles(a, op.cfg.stride, ppv != 0);
-                        if (wgt <= 0) continue;
-                        int ipw1 = 1;
-                        while (ipw1 < counts[pass] && (long)wgt * ((counts[pass] + ipw1 - 1) / ipw1) > e->num_cus) ipw1++;
-                        const int cand[3] = {ipw1, (ipw1 + 1) / 2, std::min(counts[pass], 2 * ipw1)};
-                        for (int k = 0; k < 3; k++) {
-                            if (k > 0 && (cand[k] == cand[0] || (k == 2 && cand[2] == cand[1]))) continue;
-                            ConvCfg c = tile_cfg(op.cfg, 2, 4, true, cand[k]);
-                            c.wr = true; c.pp = ppv != 0;
-                            TRY(time_cfg(c));
-                        }
-                    }
-                // parity tests: IRMV_FORCE_WRES=<n> puts every eligible layer on the resident-weights kernel with n images per
-                // workgroup -- the ping-pong form where the map tiles into its blocks (n < 0: never), else the lockstep form
-                if (const char *fw = getenv("IRMV_FORCE_WRES"); fw && fam == 1 && counts[pass] >= 2 && op.w_lds[2]) {
-                    const int v = atoi(fw);
-                    for (int ppv = v > 0 ? 1 : 0; ppv >= 0; ppv--) {
-                        ConvCfg c = tile_cfg(op.cfg, 2, 4, true, std::max(1, std::min(counts[pass], v < 0 ? -v : v)));
-                        c.wr = true; c.pp = ppv != 0;
-                        if (conv_wres_bytes(a, op.cfg.stride, c.pp) > 0 && run_conv(op, c, a, counts[pass], e->stream)) { best = 0.f; best_cfg = c; break; }
-                    }
+                if (sw.untuned && best < 1e29f) continue;   // IRMV_AUTOTUNE=0: the first candidate that runs is the choice
+                bool ok = true;
+                for (int r = 0; r < 2 && ok; r++) ok = run_conv(op, c, a, count, e->stream);
+                if (!ok) continue;
+                if (sw.untuned) { best = 0.f; best_cfg = c; continue; }
+                float ms = 1e30f;   // best of 3 bursts of 4
+                for (int rep = 0; rep < 3; rep++) {
+                    HIP_TRY(hipEventRecord(ea, e->stream));
+                    for (int r = 0; r < 4; r++) run_conv(op, c, a, count, e->stream);
+                    HIP_TRY(hipEventRecord(eb, e->stream));
+                    HIP_TRY(hipEventSynchronize(eb));
+                    float t = 0.f;
+                    HIP_TRY(hipEventElapsedTime(&t, ea, eb));
+                    ms = t < ms ? t : ms;
                 }
-                // 1x1 layers: the persistent pointwise kernel (same operands, same k order as the direct kernel)
-                if (conv_pw_eligible(op.cfg, a) && !getenv("IRMV_NO_PW")) {
-                    ConvCfg c = tile_cfg(op.cfg, 2, 4, false, 1);
-                    c.pw = true;
-                    TRY(time_cfg(c));
-                    if (getenv("IRMV_FORCE_PW") && run_conv(op, c, a, counts[pass], e->stream)) { best = 0.f; best_cfg = c; }   // parity tests
-                    // ... and its multi-block form: one workgroup runs a pixel tile against 2 / 4 output-channel blocks (input read once)
-                    for (int nbw = 2; nbw <= 4 && !getenv("IRMV_NO_PWN"); nbw *= 2) {
-                        if (!conv_pw_lds_bytes(a, nbw)) continue;
-                        c.ipw = nbw;
-                        TRY(time_cfg(c));
-                        if (getenv("IRMV_FORCE_PWN") && run_conv(op, c, a, counts[pass], e->stream)) { best = 0.f; best_cfg = c; }   // parity tests: the widest form offered
-                    }
+                if (sw.verbose) {
+                    char nm[48];
+                    cfg_name(c, nm, sizeof nm);
+                    fprintf(stderr, "[autotune] %-22s count=%-2d %-28s %8.2f us\n", op.layer.c_str(), count, nm, ms / 4 * 1e3);
                 }
-                // A layer of the LDS family may also run on the direct kernel walking K in that family's order on its weights (ct):
-                // bit-identical, so the family rule above still holds.  Offered where the direct kernel has a chance: stride 2.
-                if (lds_ok && !want_fuse && op.w_lds[0] && op.cfg.stride == 2 && !op.cfg.cin16)
-                    for (int mt = 1; mt <= 4; mt *= 2)
-                        for (int nt = 1; nt <= 4; nt *= 2) {
-                            if (op.cout_pad % (16 * nt) != 0) continue;
-                            ConvCfg c = tile_cfg(op.cfg, mt, nt, false, 1);
-                            c.ct = true;
-                            TRY(time_cfg(c));
-                        }
-                // single-frame steps: the latency variants of the direct kernel (deep prefetch ring), same rule.
-                static const bool no_deep = [] { const char *v = getenv("IRMV_NO_DEEP"); return v && v[0] == '1'; }();
-                // Batched steps: offered to the 1x1 layers only (4..16 k-steps: the ring then holds the wave's whole K range).
-                if ((counts[pass] == 1 || op.cfg.ks == 1) && !want_fuse && !no_deep && !op.cfg.cin16 && !op.cfg.out_f32 && op.cfg.act == 1 && (!lds_ok || op.w_lds[0])) {
-                    const int tiles[4][2] = {{1, 1}, {2, 1}, {1, 2}, {1, 4}};
-                    for (auto &t : tiles) {
-                        if (op.cout_pad % (16 * t[1]) != 0) continue;
-                        ConvCfg c = tile_cfg(op.cfg, t[0], t[1], false, 1);
-                        c.deep = true; c.ct = lds_ok;
-                        TRY(time_cfg(c));
-                    }
-                }
+                if (ms < best) { best = ms; best_cfg = c; }
             }
-            if (!no_tuning && !(force_s2 && lds_ok && op.cfg.stride == 2)) { std::lock_guard<std::mutex> lk(g_tune_mu); g_tune_cache[key] = best_cfg; }   // (forced / untuned choices are not what a later engine should replay)
+            if (!forced && !sw.untuned) { std::lock_guard<std::mutex> lk(g_tune_mu); g_tune_cache[key] = tune_entry(best_cfg); }
             if (pass == 0) { op.cfg = best_cfg; cfg_name(op.cfg, op.kname, sizeof op.kname); }
             else { op.cfg_one = best_cfg; cfg_name(op.cfg_one, op.kname_one, sizeof op.kname_one); }
             if (counts[0] == 1) { op.cfg_one = op.cfg; cfg_name(op.cfg_one, op.kname_one, sizeof op.kname_one); }

@@ -168,7 +168,7 @@ def cmd_s2(ARGS):
     res = {}
     for kind in ("lds", "ct", "deep"):
         os.environ["IRMV_FORCE_S2"] = kind
-        # IRMV_FORCE_S2 is read once per process (static): run each kind in a child
+        # each kind in a child process of its own
         import subprocess
         code = f"""
     import os, sys
