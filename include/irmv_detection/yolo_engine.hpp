@@ -63,12 +63,18 @@ public:
   // The reference's constructor (yolo_engine.hpp:28-30).  Extension arguments: `device` (HIP ordinal, -1 = default_device()),
   // `warm_up_now` (false: the owner calls warm_up() itself, e.g. after building several engines) and `net_size`
   // (-1 = default_net_size()).  The model file decides the architecture (YOLOv8n or its ShuffleNetV2-backbone variant).
+  // `src_format` (IRMV_SRC_*): what get_src_image_buffer() takes -- the reference's RGB8 frame (IRMV_SRC_HWC8), or the camera's
+  // raw 8-bit Bayer frame of src_image_bytes() = width * height bytes (IRMV_SRC_BAYER_*8), demosaiced on the GPU with the Q8
+  // white-balance gains `bayer_gain_q8` (R, G, B; 256 = 1.0).  get_rotated_image() is a CV_8UC3 frame either way.
   YoloEngine(const std::string & onnx_file_path, cv::Size src_image_size, bool enable_profiling = false, int device = -1,
-             bool warm_up_now = true, int net_size = -1)
+             bool warm_up_now = true, int net_size = -1, int src_format = IRMV_SRC_HWC8,
+             std::array<uint16_t, 3> bayer_gain_q8 = {256, 256, 256})
   : src_image_size_(src_image_size), enable_profiling_(enable_profiling)
   {
     irmv_engine_cfg cfg;
     irmv_engine_cfg_default(&cfg);
+    cfg.src_format = src_format;
+    for (int i = 0; i < 3; i++) cfg.bayer_gain_q8[i] = bayer_gain_q8[static_cast<size_t>(i)];
     cfg.net_size = net_size > 0 ? net_size : default_net_size();
     cfg.device = device >= 0 ? device : default_device();
     cfg.src_width = src_image_size.width;
@@ -194,6 +200,8 @@ public:
   }
 
   uint8_t * get_src_image_buffer() const { return src_image_buffer_; }
+  // bytes a producer writes into get_src_image_buffer() per frame: width * height * 3 (HWC8) or width * height (Bayer)
+  size_t src_image_bytes() const { return irmv_engine_src_bytes(engine_); }
 
 private:
   static void draw_rect(cv::Mat & img, int x1, int y1, int x2, int y2, int c0, int c1, int c2)

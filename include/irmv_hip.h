@@ -41,6 +41,22 @@ extern "C" {
 #define IRMV_POINTS_KEYPOINT_HEAD 1
 #define IRMV_POINTS_CLASSICAL 2 /* gray -> threshold -> contours -> minAreaRect -> lights, on the GPU */
 
+/* Format of the frames a producer writes into the source slots (irmv_engine_cfg.src_format).
+ *   IRMV_SRC_HWC8: H x W x 3 bytes per slot, interleaved pixels in the model's channel order (swap_rb = 0) -- the reference's
+ *                  CAMERA_MEDIA_TYPE_RGB8 frame after the camera SDK's CPU ISP.
+ *   IRMV_SRC_BAYER_*8: H x W bytes per slot, the sensor's raw 8-bit colour-filter-array frame; the name gives the colours of
+ *                  the 2 x 2 cell at (0,0) (0,1) / (1,0) (1,1).  H and W must be even.  The first kernel of every step
+ *                  demosaics it on the GPU into the R, G, B frame an IRMV_SRC_HWC8 engine would have been handed: integer
+ *                  bilinear interpolation (round half up, reflect-101 borders), then the white-balance gains
+ *                  out = min(255, (v * gain + 128) >> 8) per channel (bayer_gain_q8, Q8, 256 = 1.0).  swap_rb, rotate180,
+ *                  resize_mode and everything downstream then act on that frame exactly as on an HWC8 one.
+ *                  irmv_detection_amd/bayer.py is the bit-exact host reference. */
+#define IRMV_SRC_HWC8 0
+#define IRMV_SRC_BAYER_RGGB8 1
+#define IRMV_SRC_BAYER_BGGR8 2
+#define IRMV_SRC_BAYER_GRBG8 3
+#define IRMV_SRC_BAYER_GBRG8 4
+
 #define IRMV_NUM_CLASSES 14   /* ArmorClass B1..RS; 14 = UNKNOWN (include/irmv_detection/armor.hpp:7) */
 #define IRMV_MAX_DET_CAP 256
 #define IRMV_CAND_CAP 8192    /* most candidates the NMS walk can take (upper bound of pre_nms_cap) */
@@ -90,6 +106,11 @@ typedef struct irmv_engine_cfg {
     double armor_max_small_center_distance; /* 3.2 */
     double armor_min_large_center_distance; /* 3.2 */
     double armor_max_large_center_distance; /* 5.5 */
+    /* Appended fields.  irmv_engine_create also accepts struct_size = offsetof(irmv_engine_cfg, src_format) (callers built
+     * against the header without them) and then uses IRMV_SRC_HWC8 and gains of 256. */
+    int32_t src_format;        /* IRMV_SRC_* (default IRMV_SRC_HWC8) */
+    uint16_t bayer_gain_q8[3]; /* R, G, B white-balance gains of a Bayer engine, Q8 in [0, 1023]; 256 = identity (default) */
+    uint16_t reserved1;
 } irmv_engine_cfg;
 
 /* One detection: YoloEngine::bbox (yolo_engine.hpp:19-26) in source-frame
@@ -163,14 +184,16 @@ int irmv_numa_bind_thread(int node);                 /* sched_setaffinity(callin
 int irmv_numa_page_node(const void *p);              /* node holding the page of p (move_pages query); < 0 unknown */
 int irmv_numa_parse_cpulist(const char *s, int *cpus, int cap);   /* "0-3,8" -> {0,1,2,3,8}; returns the count (test aid) */
 
-/* Pinned host frame slot (src_height*src_width*3 bytes, HWC u8), valid for the
- * engine's lifetime; producer threads write straight into it -- the counterpart
- * of YoloEngine::get_src_image_buffer() (yolo_engine.hpp:35) and of the
- * TripleBuffer hand-off (include/irmv_detection/triple_buffer.hpp:24-40). */
+/* Pinned host frame slot, valid for the engine's lifetime; producer threads write straight into it -- the counterpart
+ * of YoloEngine::get_src_image_buffer() (yolo_engine.hpp:35) and of the TripleBuffer hand-off
+ * (include/irmv_detection/triple_buffer.hpp:24-40).  It holds irmv_engine_src_bytes() bytes: src_height*src_width*3
+ * (HWC u8) for IRMV_SRC_HWC8, src_height*src_width (the raw CFA frame, row-major) for the Bayer formats. */
 uint8_t *irmv_engine_src_buffer(irmv_engine *e, int slot);
-/* Device-side staging of the same slot (for producers that already hold the
- * frame in HBM, and for HBM-resident benchmarking). */
+/* Device-side staging of the same slot, in the same format (for producers that already hold the frame in HBM -- a Bayer
+ * producer writes the raw frame here and submits without IRMV_SUBMIT_H2D -- and for HBM-resident benchmarking). */
 void *irmv_engine_src_device_buffer(irmv_engine *e, int slot);
+int irmv_engine_src_format(const irmv_engine *e);      /* IRMV_SRC_* of this engine; -1 for a null engine */
+size_t irmv_engine_src_bytes(const irmv_engine *e);    /* bytes of one source slot (host and device); 0 for a null engine */
 
 #define IRMV_SUBMIT_H2D 1u          /* copy the pinned slots -> HBM first */
 #define IRMV_SUBMIT_ASYNC_UPLOAD 2u /* ... on the engine's upload stream, event-chained to the compute stream: this
@@ -202,7 +225,9 @@ int irmv_engine_detect(irmv_engine *e, int slot, irmv_det *out, int cap, int *n)
 double irmv_engine_last_detect_ms(const irmv_engine *e);
 
 /* 180-degree rotated frame of a slot (what get_rotated_image() aliases after the
- * in-place mirror, src/yolo_engine.cpp:77-78,182-184), rotated on the GPU. */
+ * in-place mirror, src/yolo_engine.cpp:77-78,182-184), rotated on the GPU.  dst_hwc
+ * receives src_height*src_width*3 bytes in every format: a Bayer engine uploads the
+ * raw slot, demosaics it and returns the rotated R, G, B frame. */
 int irmv_engine_rotated_image(irmv_engine *e, int slot, uint8_t *dst_hwc);
 
 /* IrmDetector::extract_armors(get_rotated_image(), bboxes) (src/irm_detector.cpp:183,292-355) on the GPU:

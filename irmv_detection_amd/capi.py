@@ -16,6 +16,8 @@ ARMOR_SMALL, ARMOR_LARGE = 0, 1
 SUBMIT_H2D = 1
 SUBMIT_ASYNC_UPLOAD = 2
 POINTS_AUTO, POINTS_KEYPOINT_HEAD, POINTS_CLASSICAL = 0, 1, 2
+SRC_HWC8, SRC_BAYER_RGGB8, SRC_BAYER_BGGR8, SRC_BAYER_GRBG8, SRC_BAYER_GBRG8 = 0, 1, 2, 3, 4
+BAYER_FORMATS = {"RGGB": SRC_BAYER_RGGB8, "BGGR": SRC_BAYER_BGGR8, "GRBG": SRC_BAYER_GRBG8, "GBRG": SRC_BAYER_GBRG8}
 NUM_CLASSES = 14
 MAX_DET_CAP = 256
 CAND_CAP = 8192
@@ -42,6 +44,7 @@ class EngineCfg(C.Structure):
         ("light_min_ratio", C.c_float), ("light_max_ratio", C.c_float), ("light_max_angle", C.c_float), ("reserved0", C.c_float),
         ("armor_min_small_center_distance", C.c_double), ("armor_max_small_center_distance", C.c_double),
         ("armor_min_large_center_distance", C.c_double), ("armor_max_large_center_distance", C.c_double),
+        ("src_format", C.c_int32), ("bayer_gain_q8", C.c_uint16 * 3), ("reserved1", C.c_uint16),
     ]
 
 
@@ -90,6 +93,8 @@ SYMBOLS = [
     ("irmv_numa_parse_cpulist", C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.c_int]),
     ("irmv_engine_src_buffer", C.POINTER(C.c_uint8), [_P, C.c_int]),
     ("irmv_engine_src_device_buffer", C.c_void_p, [_P, C.c_int]),
+    ("irmv_engine_src_format", C.c_int, [_P]),
+    ("irmv_engine_src_bytes", C.c_size_t, [_P]),
     ("irmv_engine_submit", C.c_int, [_P, C.c_int, C.c_int, C.c_uint32]),
     ("irmv_engine_wait", C.c_int, [_P]),
     ("irmv_engine_wait_slots", C.c_int, [_P, C.c_int, C.c_int]),

@@ -149,7 +149,7 @@ struct Tensor {
 
 struct SegRef { int t = -1, coff = 0, C = 0, shift = 0; };
 
-enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3 };
+enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_DEMOSAIC };
 
 struct Op {
     OpKind kind;
@@ -218,7 +218,8 @@ struct irmv_engine {
     bool split_scan = true;   // scan + box decode as a multi-workgroup kernel in front of nms_pnp (IRMV_SPLIT_SCAN=0: inside it)
     int *cand_counts = nullptr;
     int lvl_hw[3] = {0, 0, 0}, lvl_base[3] = {0, 0, 0};
-    size_t frame_bytes = 0;
+    size_t frame_bytes = 0;       // one HWC source frame (src_dev, rot_dev)
+    size_t src_bytes = 0;         // one source slot as the producer writes it (src_host, and raw_dev or src_dev): frame_bytes, or W*H for a Bayer engine
     hipStream_t stream = nullptr;                 // stream 0: single-slot detect(), read-backs, profile
     hipStream_t extra_streams[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // streams 1..num_streams-1
     int num_streams = 1;
@@ -237,6 +238,8 @@ struct irmv_engine {
     uint8_t *src_host_dev = nullptr;   // the same memory through the device's mapping (the upload kernel reads it: launch_upload_frames)
     int upload_kernel_blocks = 256;    // 0: synchronous single-frame uploads ride the copy engine like every other upload (IRMV_UPLOAD_KERNEL=0)
     uint8_t *src_dev = nullptr;   // [S][frame]
+    uint8_t *raw_dev = nullptr;   // Bayer engines: [S][W*H] raw frames, demosaiced into src_dev by the first op of a step (OP_DEMOSAIC)
+    BayerArgs bayer{};            // (pointers, slot strides, pattern phase and gains of that op; raw / dst set per launch)
     uint8_t *rot_dev = nullptr;   // [frame]
     AxisTap *tap_x = nullptr, *tap_y = nullptr;
     std::vector<Tensor> tensors;
@@ -814,6 +817,8 @@ static int build_engine(irmv_engine *e)
     { const char *gu = getenv("IRMV_GRAPH_UPLOAD"); e->graph_upload = !(gu && gu[0] == '0'); }
     e->slot_owner.assign(S, nullptr);
     e->frame_bytes = (size_t)c.src_width * c.src_height * 3;
+    const bool bayer = c.src_format != IRMV_SRC_HWC8;
+    e->src_bytes = bayer ? (size_t)c.src_width * c.src_height : e->frame_bytes;
     {
         // NUMA-local frame slots (SURVEY section 7 "hard parts": on a full node the copy engines read 8 x 14 k FPS x 3.93 MB =
         // 440 GB/s of host memory): the creating thread runs on the CPUs of the GPU's own socket and prefers its memory while
@@ -823,9 +828,9 @@ static int build_engine(irmv_engine *e)
         const bool want = e->numa_node >= 0 && !(nv && nv[0] == '0');
         numa::ScopedNode scope(want ? e->numa_node : -1);
         const bool user = want && scope.policy();
-        HIP_TRY(hipHostMalloc((void **)&e->src_host, e->frame_bytes * S, user ? (hipHostMallocDefault | hipHostMallocNumaUser) : hipHostMallocDefault));
-        log_range(e, "pinned src_host", e->src_host, e->frame_bytes * S);
-        memset(e->src_host, 0, e->frame_bytes * S);   // first touch, by the bound thread
+        HIP_TRY(hipHostMalloc((void **)&e->src_host, e->src_bytes * S, user ? (hipHostMallocDefault | hipHostMallocNumaUser) : hipHostMallocDefault));
+        log_range(e, "pinned src_host", e->src_host, e->src_bytes * S);
+        memset(e->src_host, 0, e->src_bytes * S);   // first touch, by the bound thread
         if (hipHostGetDevicePointer((void **)&e->src_host_dev, e->src_host, 0) != hipSuccess) { e->src_host_dev = nullptr; (void)hipGetLastError(); }
         if (const char *uk = getenv("IRMV_UPLOAD_KERNEL")) e->upload_kernel_blocks = atoi(uk);
         e->numa_placed = user && scope.bound();
@@ -833,6 +838,17 @@ static int build_engine(irmv_engine *e)
     TRY(dev_alloc(e, (void **)&e->src_dev, e->frame_bytes * S));
     HIP_TRY(hipMemset(e->src_dev, 0, e->frame_bytes * S));
     TRY(dev_alloc(e, (void **)&e->rot_dev, e->frame_bytes));
+    if (bayer) {
+        TRY(dev_alloc(e, (void **)&e->raw_dev, e->src_bytes * S));
+        HIP_TRY(hipMemset(e->raw_dev, 0, e->src_bytes * S));
+        // phase of the R sites: IRMV_SRC_BAYER_{RGGB, BGGR, GRBG, GBRG}8 -> R at (0,0), (1,1), (0,1), (1,0)
+        static const int ry[4] = {0, 1, 0, 1}, rx[4] = {0, 1, 1, 0};
+        BayerArgs &b = e->bayer;
+        b.raw_slot_bytes = e->src_bytes; b.dst_slot_bytes = e->frame_bytes;
+        b.W = c.src_width; b.H = c.src_height;
+        b.ry = ry[c.src_format - 1]; b.rx = rx[c.src_format - 1];
+        for (int i = 0; i < 3; i++) b.gain[i] = c.bayer_gain_q8[i];
+    }
 
     // ---- preprocess geometry (parse_output inverse mapping) ----
     int nw = net, nh = net, px = 0, py = 0;
@@ -903,6 +919,12 @@ static int build_engine(irmv_engine *e)
     TRY(new_tensor(e, "19", s32, s32, 128, false, &a19));
     TRY(new_tensor(e, "21", s32, s32, 256, false, &a21));
 
+    if (bayer) {   // raw slot -> src_dev: the first op of every step (not of run_post, not of a read-back's materialisation)
+        Op op; op.kind = OP_DEMOSAIC; op.layer = "demosaic"; snprintf(op.kname, sizeof op.kname, "bayer_demosaic");
+        op.bytes = (double)e->src_bytes + (double)e->frame_bytes;
+        e->ops.push_back(op);
+    }
+    const size_t conv0_op = e->ops.size() + 1;   // (OP_PRE, then OP_CONV0)
     { Op op; op.kind = OP_PRE; op.layer = "preprocess"; snprintf(op.kname, sizeof op.kname, "preprocess");
       op.bytes = (double)e->frame_bytes + (double)net * net * 8; e->ops.push_back(op); }
     {
@@ -936,10 +958,10 @@ static int build_engine(irmv_engine *e)
         if (!(m1.cfg.cin16 && m1.ksteps == 5 && m1.pair && m1.cout_pad == 32 && m1.out_coff == 0)) e->fused_front = false;
         if (e->fused_front) {
             Op op; op.kind = OP_FRONT; op.layer = "preprocess+model.0+model.1"; snprintf(op.kname, sizeof op.kname, "front_fused");
-            op.flops = e->ops[1].flops + m1.flops;
+            op.flops = e->ops[conv0_op].flops + m1.flops;
             op.bytes = (double)e->frame_bytes + (double)s4 * s4 * 32 * 2;
             op.w_packed = m1.w_packed; op.bias = m1.bias; op.out_t = m1.out_t;
-            for (Op &o : e->ops) o.fused_away = true;   // preprocess, model.0.conv, model.1.conv
+            for (Op &o : e->ops) o.fused_away = o.kind != OP_DEMOSAIC;   // preprocess, model.0.conv, model.1.conv
             e->lazy_tensors.insert("input"); e->lazy_tensors.insert("0");
             e->ops.push_back(op);
         }
@@ -1293,6 +1315,8 @@ extern "C" void irmv_engine_cfg_default(irmv_engine_cfg *cfg)
     cfg->light_min_ratio = 0.1f; cfg->light_max_ratio = 0.4f; cfg->light_max_angle = 40.0f;
     cfg->armor_min_small_center_distance = 0.8; cfg->armor_max_small_center_distance = 3.2;
     cfg->armor_min_large_center_distance = 3.2; cfg->armor_max_large_center_distance = 5.5;
+    cfg->src_format = IRMV_SRC_HWC8;
+    cfg->bayer_gain_q8[0] = cfg->bayer_gain_q8[1] = cfg->bayer_gain_q8[2] = 256;
 }
 
 // Which launch form serves detect() on this box: both timed on slot 0 (whatever its pinned slot holds: zeros at creation), the
@@ -1320,10 +1344,26 @@ static int choose_sync_launch(irmv_engine *e)
     return IRMV_OK;
 }
 
-extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg, irmv_engine **out)
+// struct_size of irmv_engine_cfg before src_format and the gains were appended
+constexpr size_t kCfgSizeV1 = offsetof(irmv_engine_cfg, src_format);
+
+extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **out)
 {
-    if (!cfg || !out) return fail(IRMV_ERR_ARG, "cfg/out is null");
-    if (cfg->struct_size != sizeof(irmv_engine_cfg)) return fail(IRMV_ERR_ARG, "irmv_engine_cfg size mismatch");
+    if (!cfg_in || !out) return fail(IRMV_ERR_ARG, "cfg/out is null");
+    if (cfg_in->struct_size != sizeof(irmv_engine_cfg) && cfg_in->struct_size != kCfgSizeV1) return fail(IRMV_ERR_ARG, "irmv_engine_cfg size mismatch");
+    irmv_engine_cfg full;   // an older caller's prefix, the appended fields at their defaults
+    if (cfg_in->struct_size == kCfgSizeV1) {
+        irmv_engine_cfg_default(&full);
+        memcpy(&full, cfg_in, kCfgSizeV1);
+        full.struct_size = sizeof full;
+    }
+    const irmv_engine_cfg *cfg = cfg_in->struct_size == kCfgSizeV1 ? &full : cfg_in;
+    if (cfg->src_format < IRMV_SRC_HWC8 || cfg->src_format > IRMV_SRC_BAYER_GBRG8) return fail(IRMV_ERR_ARG, "unknown src_format (IRMV_SRC_*)");
+    if (cfg->src_format != IRMV_SRC_HWC8) {
+        if (cfg->src_width % 2 || cfg->src_height % 2) return fail(IRMV_ERR_ARG, "a Bayer src_format (IRMV_SRC_BAYER_*8) needs an even src_width and src_height");
+        for (int i = 0; i < 3; i++)
+            if (cfg->bayer_gain_q8[i] > 1023) return fail(IRMV_ERR_ARG, "bayer_gain_q8 must be in [0, 1023] (Q8, 256 = 1.0)");
+    }
     if (cfg->net_size < 64 || cfg->net_size % 32 != 0 || cfg->net_size > 2048) return fail(IRMV_ERR_ARG, "net_size must be a multiple of 32 in [64, 2048]");
     if (cfg->src_width < 2 || cfg->src_height < 2 || cfg->src_width > 4096) return fail(IRMV_ERR_ARG, "src size out of range (width <= 4096)");
     if (cfg->num_slots < 1 || cfg->num_slots > 256) return fail(IRMV_ERR_ARG, "num_slots must be 1..256");
@@ -1393,16 +1433,21 @@ extern "C" int irmv_numa_parse_cpulist(const char *s, int *cpus, int cap)
 }
 extern "C" int irmv_engine_head_channels(const irmv_engine *e) { return e ? e->no : 0; }
 
+// the device memory an upload of the source slots writes: the raw slots of a Bayer engine, else the HWC frames themselves
+static uint8_t *upload_dev(const irmv_engine *e) { return e->raw_dev ? e->raw_dev : e->src_dev; }
+
 extern "C" uint8_t *irmv_engine_src_buffer(irmv_engine *e, int slot)
 {
     if (!e || slot < 0 || slot >= e->cfg.num_slots) return nullptr;
-    return e->src_host + (size_t)slot * e->frame_bytes;
+    return e->src_host + (size_t)slot * e->src_bytes;
 }
 extern "C" void *irmv_engine_src_device_buffer(irmv_engine *e, int slot)
 {
     if (!e || slot < 0 || slot >= e->cfg.num_slots) return nullptr;
-    return e->src_dev + (size_t)slot * e->frame_bytes;
+    return upload_dev(e) + (size_t)slot * e->src_bytes;
 }
+extern "C" int irmv_engine_src_format(const irmv_engine *e) { return e ? e->cfg.src_format : -1; }
+extern "C" size_t irmv_engine_src_bytes(const irmv_engine *e) { return e ? e->src_bytes : 0; }
 
 // tile choices already measured in this process, keyed by layer shape and batch (engines are created
 // repeatedly in tests and by multi-slot nodes; the kernels and the device do not change in between)
@@ -2008,6 +2053,13 @@ static int enqueue_step(irmv_engine *e, int first, int count, uint32_t flags, bo
         const int reps = (ev && !once) ? (int)(flags & 0xffu) : 1;
         for (int rep = 0; rep < (reps > 0 ? reps : 1); rep++)
         switch (op.kind) {
+        case OP_DEMOSAIC: {
+            BayerArgs a = e->bayer;
+            a.raw = e->raw_dev + (size_t)first * e->src_bytes;
+            a.dst = e->src_dev + (size_t)first * e->frame_bytes;
+            launch_demosaic(a, count, s);
+            break;
+        }
         case OP_PRE: {
             PreArgs a;
             a.src = e->src_dev + (size_t)first * e->frame_bytes;
@@ -2156,8 +2208,26 @@ static int enqueue_step(irmv_engine *e, int first, int count, uint32_t flags, bo
 // Frame upload and result download: plain async copies, pinned memory both ways, on the streams submit_group() picks.
 static int copy_in(irmv_engine *e, int first, int count, hipStream_t st)
 {
-    HIP_TRY(hipMemcpyAsync(e->src_dev + (size_t)first * e->frame_bytes, e->src_host + (size_t)first * e->frame_bytes,
-                           e->frame_bytes * count, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(upload_dev(e) + (size_t)first * e->src_bytes, e->src_host + (size_t)first * e->src_bytes,
+                           e->src_bytes * count, hipMemcpyHostToDevice, st));
+    return IRMV_OK;
+}
+
+// One or two frames travel from the pinned slots as a KERNEL (k_pre.hip upload_frame_kernel), larger groups on the copy engine.
+static bool upload_as_kernel(const irmv_engine *e, int first, int count)
+{
+    const size_t off = (size_t)first * e->src_bytes, bytes = e->src_bytes * count;
+    return count <= 2 && e->upload_kernel_blocks > 0 && e->src_host_dev && off % 16 == 0 && bytes % 16 == 0;
+}
+
+// The synchronous upload of slots [first, first + count) on stream st.  (A Bayer engine's single-frame upload stays a kernel
+// of its own in front of the demosaic: the demosaic reading the pinned slot itself was built and measured slower, DESIGN.md
+// section 9.)
+static int upload_sync(irmv_engine *e, int first, int count, hipStream_t st)
+{
+    if (!upload_as_kernel(e, first, count)) return copy_in(e, first, count, st);
+    const size_t off = (size_t)first * e->src_bytes;
+    launch_upload_frames(e->src_host_dev + off, upload_dev(e) + off, e->src_bytes * count, e->upload_kernel_blocks, st);
     return IRMV_OK;
 }
 
@@ -2187,13 +2257,8 @@ static int get_graph(irmv_engine *e, int first, int count, uint32_t flags, bool 
     hipGraph_t g = nullptr;
     HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     int rc = IRMV_OK;
-    if (flags & 0x10000000u) {   // the frames' upload as the graph's first node (synchronous single-stream submits): one or two frames as a kernel
-        const size_t off = (size_t)first * e->frame_bytes, bytes = e->frame_bytes * count;
-        if (count <= 2 && e->upload_kernel_blocks > 0 && e->src_host_dev && off % 16 == 0 && bytes % 16 == 0)
-            launch_upload_frames(e->src_host_dev + off, e->src_dev + off, bytes, e->upload_kernel_blocks, e->stream);
-        else
-            rc = copy_in(e, first, count, e->stream);
-    }
+    if (flags & 0x10000000u)   // the frames' upload as the graph's first node (synchronous single-stream submits): one or two frames as a kernel
+        rc = upload_sync(e, first, count, e->stream);
     if (!rc) rc = enqueue_step(e, first, count, (flags & ~0x10000000u) | 0x40000000u, post_only, nullptr);
     hipError_t ce = hipStreamEndCapture(e->stream, &g);
     if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
@@ -2267,12 +2332,8 @@ static int submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_
             HIP_TRY(hipEventRecord(g->h2d, up));
             HIP_TRY(hipStreamWaitEvent(st, g->h2d, 0));
         } else if (!graph_up) {
-            // (an eager step, or IRMV_GRAPH_UPLOAD=0)  One or two frames travel as a KERNEL (k_pre.hip upload_frame_kernel), larger groups on the copy engine.
-            const size_t off = (size_t)f * e->frame_bytes, bytes = e->frame_bytes * c;
-            if (c <= 2 && e->upload_kernel_blocks > 0 && e->src_host_dev && off % 16 == 0 && bytes % 16 == 0)
-                launch_upload_frames(e->src_host_dev + off, e->src_dev + off, bytes, e->upload_kernel_blocks, st);
-            else
-                TRY(copy_in(e, f, c, st));
+            // (an eager step, or IRMV_GRAPH_UPLOAD=0)
+            TRY(upload_sync(e, f, c, st));
         }
     }
     if (eager) {
@@ -2429,13 +2490,27 @@ extern "C" int irmv_engine_detect(irmv_engine *e, int slot, irmv_det *out, int c
 
 extern "C" double irmv_engine_last_detect_ms(const irmv_engine *e) { return e ? e->last_detect_ms : 0.0; }
 
+// The slot's pinned frame -> its HWC device frame (src_dev) on stream st, outside a step: an HWC engine copies it there, a
+// Bayer engine copies the raw frame to its device raw slot and demosaics it.
+static int load_frame(irmv_engine *e, int slot, hipStream_t st)
+{
+    TRY(copy_in(e, slot, 1, st));
+    if (e->raw_dev) {
+        BayerArgs a = e->bayer;
+        a.raw = e->raw_dev + (size_t)slot * e->src_bytes;
+        a.dst = e->src_dev + (size_t)slot * e->frame_bytes;
+        launch_demosaic(a, 1, st);
+        HIP_TRY(hipGetLastError());
+    }
+    return IRMV_OK;
+}
+
 extern "C" int irmv_engine_rotated_image(irmv_engine *e, int slot, uint8_t *dst)
 {
     TRY(check_range(e, slot, 1));
     if (!dst) return fail(IRMV_ERR_ARG, "dst is null");
     HIP_TRY(hipSetDevice(e->cfg.device));
-    HIP_TRY(hipMemcpyAsync(e->src_dev + (size_t)slot * e->frame_bytes, e->src_host + (size_t)slot * e->frame_bytes,
-                           e->frame_bytes, hipMemcpyHostToDevice, e->stream));
+    TRY(load_frame(e, slot, e->stream));
     launch_rotate180(e->src_dev + (size_t)slot * e->frame_bytes, e->rot_dev, e->cfg.src_width, e->cfg.src_height, e->stream);
     HIP_TRY(hipMemcpyAsync(dst, e->rot_dev, e->frame_bytes, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -2450,8 +2525,7 @@ extern "C" int irmv_engine_extract_armors(irmv_engine *e, int slot, const float 
     HIP_TRY(hipSetDevice(e->cfg.device));
     TRY(irmv_engine_wait(e));
     hipStream_t st = e->stream;
-    HIP_TRY(hipMemcpyAsync(e->src_dev + (size_t)slot * e->frame_bytes, e->src_host + (size_t)slot * e->frame_bytes, e->frame_bytes,
-                           hipMemcpyHostToDevice, st));
+    TRY(load_frame(e, slot, st));
     HIP_TRY(hipMemcpyAsync(e->light_boxes, xyxy, (size_t)n * 16, hipMemcpyHostToDevice, st));
     LightArgs a = light_args(e, slot);
     a.dets = e->light_dets_dev;

@@ -128,6 +128,20 @@ void launch_preprocess(const PreArgs &a, int batch, hipStream_t s);
 void launch_rotate180(const uint8_t *src, uint8_t *dst, int sw, int sh, hipStream_t s);
 void launch_upload_frames(const uint8_t *src_host_mapped, uint8_t *dst, size_t bytes, int blocks, hipStream_t s);   // bytes % 16 == 0, both pointers 16-byte aligned
 
+// ---- raw Bayer input (k_bayer.hip) ---------------------------------------------------
+// uint8 [B][H][W] CFA frames -> HWC [B][H][W][3] (R, G, B): integer bilinear demosaic with reflect-101 borders, then the
+// Q8 white-balance gains (irmv_detection_amd/bayer.py is the bit-exact host reference).  Any alignment of `raw` and `dst`.
+constexpr int kBayerBandRows = 8;   // output rows per workgroup (+ one halo row above and below, staged in LDS)
+struct BayerArgs {
+    const uint8_t *raw;       // [B][H][W]
+    uint8_t *dst;             // [B][H][W][3]
+    size_t raw_slot_bytes, dst_slot_bytes;
+    int W, H;                 // both even
+    int ry, rx;               // row / column parity of the R sites (B at the opposite parities)
+    uint32_t gain[3];         // Q8, 256 = identity
+};
+void launch_demosaic(const BayerArgs &a, int batch, hipStream_t s);
+
 // model.0.conv: 3x3 s2, 3(+1 pad) -> 16, SiLU
 struct Conv0Args {
     const half_t *x;      // [B][net][net][4]

@@ -87,6 +87,9 @@ class YoloEngine:
     `weights_device_ptr` + `weights_bytes` after an RCCL broadcast), `num_slots`
     (the reference node builds 3 engines, one per TripleBuffer slot), `slot` (the
     slot `detect()` works on), NMS thresholds, resize mode, PnP constants.
+    `src_format`: what a source slot holds -- capi.SRC_HWC8 (H x W x 3, default) or a raw 8-bit Bayer frame
+    (capi.SRC_BAYER_*8, or the pattern name "RGGB" / "BGGR" / "GRBG" / "GBRG"), demosaiced on the GPU with the Q8
+    white-balance `bayer_gains` (R, G, B; 256 = 1.0); irmv_detection_amd.bayer.demosaic is its host reference.
     """
 
     def __init__(self, onnx_file_path: Optional[str], src_image_size: Tuple[int, int] = (1280, 1024),
@@ -99,7 +102,8 @@ class YoloEngine:
                  dist_coeffs: Sequence[float] = DEFAULT_DIST_COEFFS, armor_size: int = capi.ARMOR_SMALL,
                  num_streams: int = 0, point_source: int = capi.POINTS_AUTO, binary_threshold: int = 150,
                  light_min_ratio: float = 0.1, light_max_ratio: float = 0.4, light_max_angle: float = 40.0,
-                 armor_center_distances: Sequence[float] = (0.8, 3.2, 3.2, 5.5), warmup: int = 0):
+                 armor_center_distances: Sequence[float] = (0.8, 3.2, 3.2, 5.5), warmup: int = 0,
+                 src_format=capi.SRC_HWC8, bayer_gains: Sequence[int] = (256, 256, 256)):
         L = capi.load()
         cfg = capi.EngineCfg()
         L.irmv_engine_cfg_default(C.byref(cfg))
@@ -114,6 +118,8 @@ class YoloEngine:
         cfg.light_min_ratio, cfg.light_max_ratio, cfg.light_max_angle = light_min_ratio, light_max_ratio, light_max_angle
         (cfg.armor_min_small_center_distance, cfg.armor_max_small_center_distance,
          cfg.armor_min_large_center_distance, cfg.armor_max_large_center_distance) = armor_center_distances
+        cfg.src_format = capi.BAYER_FORMATS[src_format.upper()] if isinstance(src_format, str) else int(src_format)
+        cfg.bayer_gain_q8 = (C.c_uint16 * 3)(*[int(g) for g in bayer_gains])
         cfg.camera_matrix = (C.c_double * 9)(*camera_matrix)
         cfg.dist_coeffs = (C.c_double * 5)(*(list(dist_coeffs) + [0.0] * 5)[:5])
         self._blob_keepalive = None
@@ -133,6 +139,7 @@ class YoloEngine:
             self._h = None
             capi.check(rc)
         self.src_image_size = (cfg.src_width, cfg.src_height)
+        self.src_format = cfg.src_format
         self.net_size = net_size
         self.num_slots = num_slots
         self.slot = slot
@@ -167,13 +174,13 @@ class YoloEngine:
 
     # ---- reference API -----------------------------------------------------------
     def get_src_image_buffer(self, slot: Optional[int] = None) -> np.ndarray:
-        """uint8 [H, W, 3] view of the pinned frame slot (yolo_engine.hpp:35)."""
+        """uint8 view of the pinned frame slot (yolo_engine.hpp:35): [H, W, 3], or [H, W] (the raw frame) for a Bayer engine."""
         slot = self.slot if slot is None else slot
         p = self._L.irmv_engine_src_buffer(self._h, slot)
         if not p:
             raise IrmvError(capi.ERR_ARG, "bad slot")
         w, h = self.src_image_size
-        return np.ctypeslib.as_array(p, shape=(h, w, 3))
+        return np.ctypeslib.as_array(p, shape=(h, w, 3) if self.src_format == capi.SRC_HWC8 else (h, w))
 
     def src_page_node(self, slot: int = 0) -> int:
         """NUMA node that holds the first page of the pinned frame slot (move_pages query); < 0: unknown."""
@@ -194,7 +201,7 @@ class YoloEngine:
         return float(self._L.irmv_engine_last_detect_ms(self._h))
 
     def get_rotated_image(self, slot: Optional[int] = None) -> np.ndarray:
-        """The 180-degree rotated frame (yolo_engine.hpp:34)."""
+        """The 180-degree rotated frame (yolo_engine.hpp:34); HWC in every source format (a Bayer engine's demosaiced frame)."""
         slot = self.slot if slot is None else slot
         w, h = self.src_image_size
         out = np.empty((h, w, 3), np.uint8)
