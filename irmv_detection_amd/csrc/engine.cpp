@@ -168,9 +168,7 @@ struct Op {
     double w_bytes = 0;           // the weights' share of `bytes`: read once per LAUNCH, not once per frame (irmv_engine_profile)
     double out_bytes = 0;         // the output's share (a conv that carries a fused 1x1 writes that layer's output instead of its own)
     bool pair = false;
-    int lane = 0;      // 0 = trunk; 1..3 = Detect branch (box / cls / kpt): which grouped launch a head conv may join
-    int level = -1;    // Detect level of a head op: it may start as soon as P(level) exists
-    int signal = -1;   // >= 0: this op produces P(signal); side lanes wait on its event
+    int level = -1;    // Detect level of a head op (-1: trunk)
     char kname[48] = {0};
     int sub[4] = {-1, -1, -1, -1};   // OP_C2F2 / OP_C2F32: indices of the layer ops whose weights it uses
     int mode = 0;                    // OP_C2F32: 0 whole block, 1 cv1 + first bottleneck, 2 last bottleneck + cv2
@@ -182,13 +180,26 @@ struct Op {
     int kpt3 = -1;             // a keypoint-branch conv: index of the OP_KPT3 launch (k_kpt.hip) that computes its level's branch in every step; OP_KPT3 itself: 1
 };
 
+// What a step launches depends only on its kind and the engine, so each kind's launch list is decided at creation (build_step_plans).
+// BATCH: count > 1 slots; ONE: one slot; MATERIALIZE: the layers fused kernels keep on chip (read-backs); POST: run_post's kernels.
+enum StepKind { STEP_BATCH, STEP_ONE, STEP_MATERIALIZE, STEP_POST };
+
+struct Launch {
+    int op = -1, group = -1;  // index into irmv_engine::ops; >= 0: the head group (head_groups) launched at its first member's place
+    bool cfg_one = false;     // OP_CONV: runs op.cfg_one, not op.cfg
+    bool fused = false;       // OP_CONV: carries its fuse_next 1x1 in the epilogue
+    unsigned scan = 0;        // bit k: member k of the group (a lone conv: bit 0) appends scan candidates from its epilogue
+    bool keys_only = false;   // OP_NMS: decodes the boxes of its key lists itself
+    bool once = false;        // not repeated under irmv_engine_profile (appends to, consumes or rewrites per-frame lists)
+    std::string name, layer;  // irmv_engine_profile's row
+    double flops = 0, bytes = 0, launch_bytes = 0;   // per frame; launch_bytes (the weights): once per launch
+};
+
 struct GraphKey {
     int first, count;
-    uint32_t flags;
-    bool operator<(const GraphKey &o) const
-    {
-        return std::tie(first, count, flags) < std::tie(o.first, o.count, o.flags);
-    }
+    StepKind kind;
+    bool upload;   // the frames' upload is the graph's first node
+    bool operator<(const GraphKey &o) const { return std::tie(first, count, kind, upload) < std::tie(o.first, o.count, o.kind, o.upload); }
 };
 
 // Events of one submitted slot group [first, first + count): h2d = its frames are in HBM (async upload only);
@@ -214,7 +225,6 @@ struct irmv_engine {
     std::vector<HeadGroup> head_groups;
     bool post_keys_only = false;   // IRMV_POST_KEYS_ONLY=1 (tests): run_post's NMS ignores scan_decode_kernel's boxes and decodes its own, as a whole step's does
     bool emit_scan = false;   // candidates are emitted by the class-branch conv epilogues (needs split_scan's counters and all three levels fused)
-    int emit_level_abase[3] = {0, 0, 0};
     bool split_scan = true;   // scan + box decode as a multi-workgroup kernel in front of nms_pnp (IRMV_SPLIT_SCAN=0: inside it)
     int *cand_counts = nullptr;
     int lvl_hw[3] = {0, 0, 0}, lvl_base[3] = {0, 0, 0};
@@ -234,7 +244,6 @@ struct irmv_engine {
     uint8_t *src_host = nullptr;  // pinned [S][frame]
     int sync_launch = 0;               // how a synchronous single-frame step (detect()) reaches the GPU: 0 = one hipGraph replay (upload = its first node), 1 = launched
                                        // kernel by kernel behind the upload; chosen by timing at creation (choose_sync_launch), IRMV_SYNC_LAUNCH=graph|eager forces
-    hipStream_t enq_stream = nullptr;  // (set around an eager step: the stream enqueue_step launches on instead of `stream`)
     uint8_t *src_host_dev = nullptr;   // the same memory through the device's mapping (the upload kernel reads it: launch_upload_frames)
     int upload_kernel_blocks = 256;    // 0: synchronous single-frame uploads ride the copy engine like every other upload (IRMV_UPLOAD_KERNEL=0)
     uint8_t *src_dev = nullptr;   // [S][frame]
@@ -245,6 +254,7 @@ struct irmv_engine {
     std::vector<Tensor> tensors;
     std::map<std::string, int> tensor_idx;
     std::vector<Op> ops;
+    std::vector<Launch> plans[STEP_POST + 1];   // per StepKind: the launches of such a step, in order (build_step_plans)
     std::vector<void *> dev_allocs;
     int head_t[3] = {-1, -1, -1};
     float *head_all = nullptr;
@@ -524,7 +534,6 @@ static int add_dw(irmv_engine *e, const std::string &layer, SegRef in, int Hin, 
         HIP_TRY(hipMemcpy(op.bias, bs.data(), bs.size() * 4, hipMemcpyHostToDevice));
     }
     snprintf(op.kname, sizeof op.kname, "dwconv3x3s%d", l->stride);
-    snprintf(op.kname_one, sizeof op.kname_one, "dwconv3x3s%d", l->stride);
     op.flops = 2.0 * op.Hout * op.Wout * (double)l->cout * 9;
     op.bytes = 2.0 * ((double)Hin * Win + (double)op.Hout * op.Wout) * l->cout + 2.0 * 9 * l->cout;
     e->ops.push_back(op);
@@ -544,7 +553,6 @@ static int add_shuffle(irmv_engine *e, const std::string &name, SegRef a, SegRef
     op.cin = op.cout = 2 * a.C;
     op.out_t = out_t;
     snprintf(op.kname, sizeof op.kname, "shuffle_cat");
-    snprintf(op.kname_one, sizeof op.kname_one, "shuffle_cat");
     op.bytes = 2.0 * 2.0 * (double)H * W * 2 * a.C;
     e->ops.push_back(op);
     return IRMV_OK;
@@ -658,7 +666,6 @@ static int fuse_bneck64(irmv_engine *e, const std::string &prefix, int n, bool s
         op.shortcut = shortcut;
         op.layer = prefix + ".m." + std::to_string(i) + (with_cv2 ? " + cv2 (one launch)" : " (one launch)");
         snprintf(op.kname, sizeof op.kname, with_cv2 ? "bneck64_b" : "bneck64_a");
-        snprintf(op.kname_one, sizeof op.kname_one, "%s", op.kname);
         op.sub[0] = i_m1; op.sub[1] = i_m2; op.sub[2] = with_cv2 ? last : -1;
         op.Hin = op.Hout = bH; op.Win = op.Wout = bW;
         op.out_t = with_cv2 ? out_t : cat;
@@ -698,11 +705,10 @@ static int fuse_kpt3(irmv_engine *e, int level)
     op.kind = OP_KPT3;
     op.layer = "model.22.cv4." + std::to_string(level) + " (one launch)";
     snprintf(op.kname, sizeof op.kname, "kpt3_c%d", o0.cin);
-    snprintf(op.kname_one, sizeof op.kname_one, "%s", op.kname);
     op.sub[0] = i0; op.sub[1] = i1; op.sub[2] = i2;
     op.Hin = op.Hout = o0.Hin; op.Win = op.Wout = o0.Win;
     op.cin = o0.cin;
-    op.lane = o0.lane; op.level = level;
+    op.level = level;
     op.flops = o0.flops + o1.flops + o2.flops;
     op.w_bytes = o0.w_bytes + o1.w_bytes + o2.w_bytes;
     op.out_bytes = o2.out_bytes;
@@ -796,6 +802,7 @@ static bool front_fits(const std::vector<AxisTap> &tx, const std::vector<AxisTap
 static int autotune_convs(irmv_engine *e);
 static void finalize_head_fusion(irmv_engine *e);
 static int build_head_groups(irmv_engine *e);
+static void build_step_plans(irmv_engine *e);
 
 static int build_engine(irmv_engine *e)
 {
@@ -925,7 +932,7 @@ static int build_engine(irmv_engine *e)
         e->ops.push_back(op);
     }
     const size_t conv0_op = e->ops.size() + 1;   // (OP_PRE, then OP_CONV0)
-    { Op op; op.kind = OP_PRE; op.layer = "preprocess"; snprintf(op.kname, sizeof op.kname, "preprocess");
+    { Op op; op.kind = OP_PRE; op.layer = "preprocess"; snprintf(op.kname, sizeof op.kname, "preprocess"); op.out_t = x0;
       op.bytes = (double)e->frame_bytes + (double)net * net * 8; e->ops.push_back(op); }
     {
         const LayerW *l = find_layer(e, "model.0.conv");
@@ -948,6 +955,7 @@ static int build_engine(irmv_engine *e)
         HIP_TRY(hipMemcpy(e->conv0_w, w.data(), w.size() * 2, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(e->conv0_b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
         Op op; op.kind = OP_CONV0; op.layer = "model.0.conv"; snprintf(op.kname, sizeof op.kname, "conv0_mfma");
+        op.s0.t = x0; op.out_t = a0;
         op.flops = 2.0 * s2 * s2 * 16 * 27;
         op.bytes = (double)net * net * 8 + (double)s2 * s2 * 32 + 27 * 16 * 2;
         e->ops.push_back(op);
@@ -1006,18 +1014,15 @@ static int build_engine(irmv_engine *e)
     TRY(add_c2f(e, "model.8", SegRef{a7, 0, 256, 0}, SegRef{}, s32, s32, 256, 1, true, a8));
     }
     TRY(add_conv(e, "model.9.cv1", SegRef{p5, 0, 256, 0}, SegRef{}, s32, s32, s9, 0));
-    { Op op; op.kind = OP_POOL; op.layer = "model.9.m"; snprintf(op.kname, sizeof op.kname, "sppf_pool");
+    { Op op; op.kind = OP_POOL; op.layer = "model.9.m"; snprintf(op.kname, sizeof op.kname, "sppf_pool"); op.out_t = s9;
       op.bytes = (double)s32 * s32 * 128 * 2 * 4; e->ops.push_back(op); }
     TRY(add_conv(e, "model.9.cv2", SegRef{s9, 0, 512, 0}, SegRef{}, s32, s32, a9, 0));
     TRY(add_c2f(e, "model.12", SegRef{a9, 0, 256, 1}, SegRef{p4, 0, 128, 0}, s16, s16, 128, 1, false, a12));
     TRY(add_c2f(e, "model.15", SegRef{a12, 0, 128, 1}, SegRef{p3, 0, 64, 0}, s8, s8, 64, 1, false, a15));
-    e->ops.back().signal = 0;
     TRY(add_conv(e, "model.16.conv", SegRef{a15, 0, 64, 0}, SegRef{}, s8, s8, a16, 0));
     TRY(add_c2f(e, "model.18", SegRef{a16, 0, 64, 0}, SegRef{a12, 0, 128, 0}, s16, s16, 128, 1, false, a18));
-    e->ops.back().signal = 1;
     TRY(add_conv(e, "model.19.conv", SegRef{a18, 0, 128, 0}, SegRef{}, s16, s16, a19, 0));
     TRY(add_c2f(e, "model.21", SegRef{a19, 0, 128, 0}, SegRef{a9, 0, 256, 0}, s32, s32, 256, 1, false, a21));
-    e->ops.back().signal = 2;
 
     // Detect head: per level one fp32 record of kHeadRec per anchor: box 64 | cls 16 | kpt 16
     const int P[3] = {a15, a18, a21}, PC[3] = {64, 128, 256}, PS[3] = {s8, s16, s32};
@@ -1084,7 +1089,7 @@ static int build_engine(irmv_engine *e)
             Op &mo = e->ops.back();
             const double real = nbr == 3 ? 144.0 : 128.0;
             mo.flops *= real / cm;                      // algorithmic work: the zero-padded channels do not count
-            mo.lane = 1; mo.level = i;
+            mo.level = i;
         }
     }
     for (int b = 0; b < nbr; b++)
@@ -1101,7 +1106,7 @@ static int build_engine(irmv_engine *e)
                 TRY(add_conv(e, pre + ".1", SegRef{t1, 0, mid[b], 0}, SegRef{}, PS[i], PS[i], t2, 0));
             }
             TRY(add_conv(e, pre + ".2", SegRef{t2, 0, mid[b], 0}, SegRef{}, PS[i], PS[i], e->head_t[i], off[b]));
-            for (size_t k = e->ops.size() - (e->merge_head0 ? 2 : 3); k < e->ops.size(); k++) { e->ops[k].lane = 1 + b; e->ops[k].level = i; }
+            for (size_t k = e->ops.size() - (e->merge_head0 ? 2 : 3); k < e->ops.size(); k++) e->ops[k].level = i;
             {   // the branch's final 1x1 can ride in the epilogue of its second 3x3 (k_conv.hip, N2 > 0)
                 const int i1 = (int)e->ops.size() - 2, i2 = i1 + 1;
                 const Op &o1 = e->ops[i1], &o2 = e->ops[i2];
@@ -1147,7 +1152,6 @@ static int build_engine(irmv_engine *e)
     // class-logit scan + box decode of the candidate anchors: kScanBlocks workgroups per frame (k_post.hip)
     if (e->split_scan) {
         Op op; op.kind = OP_SCAN; op.layer = "scan_decode"; snprintf(op.kname, sizeof op.kname, "scan_decode");
-        snprintf(op.kname_one, sizeof op.kname_one, "scan_decode");
         op.bytes = (double)e->A * 64.0; e->ops.push_back(op);
     }
     // [decode +] sort + NMS + keypoints + PnP: one kernel, one workgroup per frame (k_post.hip)
@@ -1395,6 +1399,7 @@ extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **o
     finalize_head_fusion(e.get());
     rc = build_head_groups(e.get());
     if (rc) return rc;
+    build_step_plans(e.get());
     rc = choose_sync_launch(e.get());
     if (rc) return rc;
     *out = e.release();
@@ -1744,22 +1749,13 @@ static int autotune_convs(irmv_engine *e)
     return IRMV_OK;
 }
 
+// a class-branch conv that carries its final 1x1: with emit_scan, its epilogue appends the level's scan candidates
+static bool is_cls_final_carrier(const Op &op) { return op.fuse_next >= 0 && op.level >= 0 && op.layer.rfind("model.22.cv3.", 0) == 0; }
+
 // A 3x3 conv carries its branch's final 1x1 only if BOTH of its tile choices can (LDS family, nt = 4); then the 1x1
 // op drops out of the step and the tensor between the two is no longer written.
 static void finalize_head_fusion(irmv_engine *e)
 {
-    struct Tail {
-        irmv_engine *e;
-        ~Tail()
-        {
-            // candidate emission from the conv epilogues: only if the class branch of EVERY level ends in a fused 1x1
-            int fused = 0;
-            for (const Op &op : e->ops)
-                if (op.kind == OP_CONV && op.fuse_next >= 0 && op.layer.rfind("model.22.cv3.", 0) == 0) fused++;
-            const char *ev = getenv("IRMV_EMIT_SCAN");
-            e->emit_scan = e->split_scan && fused == 3 && !(ev && ev[0] == '0');
-        }
-    } tail{e};
     for (Op &op : e->ops) {
         if (op.fuse_next < 0) continue;
         const bool k16 = op.cfg.cin16 && !op.cfg.lds && !op.cfg_one.lds && !op.cfg.deep && !op.cfg_one.deep && op.cfg.nt == 1 && op.cfg_one.nt == 1 && e->ops[op.fuse_next].w_k16;
@@ -1771,6 +1767,11 @@ static void finalize_head_fusion(irmv_engine *e)
         snprintf(op.kname + l, sizeof op.kname - l, "+1x1");
         snprintf(op.kname_one + l1, sizeof op.kname_one - l1, "+1x1");
     }
+    // candidate emission from the conv epilogues: only if the class branch of EVERY level ends in a fused 1x1
+    int fused = 0;
+    for (const Op &op : e->ops) fused += is_cls_final_carrier(op);
+    const char *ev = getenv("IRMV_EMIT_SCAN");
+    e->emit_scan = e->split_scan && fused == 3 && !(ev && ev[0] == '0');
 }
 
 // ---- grouped Detect-branch launches (single-frame engines) ---------------------------
@@ -1782,10 +1783,8 @@ static void scan_args_for(const irmv_engine *e, const Op &op, const PostArgs &pa
     a.scan_abase = op.level == 0 ? 0 : (op.level == 1 ? w0 * w0 : w0 * w0 + (w0 / 2) * (w0 / 2));
 }
 
-static bool is_cls_final_carrier(const Op &op) { return op.fuse_next >= 0 && op.level >= 0 && op.layer.rfind("model.22.cv3.", 0) == 0; }
-
-// one launch for all members of group g on slot `first`; pa == nullptr: no candidate emission (timing, profile repeats)
-static bool launch_head_group(const irmv_engine *e, const irmv_engine::HeadGroup &g, int first, const PostArgs *pa, hipStream_t s)
+// one launch for all members of group g on slot `first`; member k appends candidates to pa's key lists if bit k of `scan` is set
+static bool launch_head_group(const irmv_engine *e, const irmv_engine::HeadGroup &g, int first, const PostArgs *pa, unsigned scan, hipStream_t s)
 {
     ConvArgs a[kMultiMax];
     const half_t *wl[kMultiMax];
@@ -1793,7 +1792,7 @@ static bool launch_head_group(const irmv_engine *e, const irmv_engine::HeadGroup
     for (int k = 0; k < n; k++) {
         const Op &op = e->ops[g.members[k]];
         fill_conv_args(e, op, first, 1, a[k], true);
-        if (pa && e->emit_scan && is_cls_final_carrier(op)) scan_args_for(e, op, *pa, a[k]);
+        if (scan >> k & 1u) scan_args_for(e, op, *pa, a[k]);
         wl[k] = op.w_lds[g.nt == 4 ? 2 : (g.nt == 2 ? 1 : 0)];
         if (g.family == 0 && !wl[k]) return false;
     }
@@ -1857,7 +1856,7 @@ static int build_head_groups(irmv_engine *e)
                 if (!fam) continue;
             }
             if (getenv("IRMV_GROUP_VERBOSE")) { fprintf(stderr, "[irmv group] timing %s nt %d ...\n", label, nt); fflush(stderr); }
-            const float ms = time_of([&] { return launch_head_group(e, g, 0, nullptr, e->stream); });
+            const float ms = time_of([&] { return launch_head_group(e, g, 0, nullptr, 0u, e->stream); });
             if (getenv("IRMV_GROUP_VERBOSE")) { fprintf(stderr, "[irmv group] ... %.2f us\n", ms * 1e3f); fflush(stderr); }
             if (ms > 0.f && (best_ms < 0.f || ms < best_ms)) { best_ms = ms; best = g; }
         }
@@ -1898,9 +1897,62 @@ static int build_head_groups(irmv_engine *e)
     return IRMV_OK;
 }
 
+// ---- step plans ------------------------------------------------------------------
+// The one place that decides which ops of e->ops a step of each kind launches, and how.
+static void build_step_plans(irmv_engine *e)
+{
+    for (int k = STEP_BATCH; k <= STEP_POST; k++) {
+        const bool one = k == STEP_ONE, mat = k == STEP_MATERIALIZE, post = k == STEP_POST, step = !mat && !post;
+        auto emits = [&](const Op &op) { return step && e->emit_scan && is_cls_final_carrier(op); };
+        for (int i = 0; i < (int)e->ops.size(); i++) {
+            const Op &op = e->ops[i];
+            if (post && op.kind != OP_NMS && op.kind != OP_LIGHT && op.kind != OP_SCAN) continue;
+            if (op.kind == OP_SCAN && e->emit_scan && !post) continue;   // the class-branch convs have already filled the key lists
+            const bool grouped = one && op.kind == OP_CONV && op.group >= 0;
+            if (grouped && e->head_groups[op.group].members[0] != i) continue;   // rides in its group's launch
+            // single-frame steps: the 64-channel Bottlenecks ride in their OP_BNECK launch; every other kind runs the layers
+            const bool bneck = one && e->bneck64;
+            if (op.kind == OP_BNECK ? !bneck : (op.bneck >= 0 && bneck)) continue;
+            // every step runs a level's keypoint branch as its OP_KPT3 launch (where the engine has one)
+            if (op.kind == OP_KPT3 ? !step : (op.kpt3 >= 0 && step)) continue;
+            // a step skips the layers a fused kernel covers; a read-back runs only those (and the unfused form of a conv that
+            // normally carries a 1x1 in its epilogue)
+            if (mat ? !(op.fused_away || op.fuse_next >= 0 || ((op.bneck >= 0 || op.kpt3 >= 0) && op.kind == OP_CONV)) : op.fused_away) continue;
+            Launch l; l.op = i;
+            // every kernel is idempotent and can be repeated inside its profile bracket -- except the light extraction and, with
+            // the split scan, the scan / NMS pair (the scan appends to the frame's candidate list, the NMS kernel consumes and resets it)
+            l.once = op.kind == OP_LIGHT || (e->split_scan && (op.kind == OP_SCAN || op.kind == OP_NMS));
+            l.keys_only = op.kind == OP_NMS && ((e->emit_scan && !post) || (post && e->post_keys_only));
+            l.layer = op.layer;
+            if (grouped) {   // one launch for the whole group
+                const irmv_engine::HeadGroup &g = e->head_groups[op.group];
+                l.group = op.group;
+                l.name = g.name;
+                l.layer += " ... (" + std::to_string(g.members.size()) + " convs)";
+                for (size_t m = 0; m < g.members.size(); m++) {
+                    const Op &mo = e->ops[g.members[m]];
+                    if (emits(mo)) l.scan |= 1u << m;
+                    l.flops += mo.flops + (mo.fuse_next >= 0 ? e->ops[mo.fuse_next].flops : 0.0);
+                    l.bytes += mo.bytes;
+                }
+            } else {
+                l.cfg_one = op.kind == OP_CONV && (one || mat) && stream_share(e, e->cfg.num_slots) > 1;   // (a read-back runs one slot)
+                l.fused = !mat && op.fuse_next >= 0;
+                l.scan = emits(op) ? 1u : 0u;
+                l.name = l.cfg_one ? op.kname_one : op.kname;
+                const Op *nx = l.fused ? &e->ops[op.fuse_next] : nullptr;   // the fused 1x1's output is what reaches memory, its weights ride along
+                l.flops = op.flops + (nx ? nx->flops : 0.0);
+                l.launch_bytes = op.w_bytes + (nx ? nx->w_bytes : 0.0);
+                l.bytes = op.bytes + (nx ? nx->out_bytes - op.out_bytes + nx->w_bytes : 0.0) - l.launch_bytes;
+            }
+            e->plans[k].push_back(l);
+        }
+    }
+}
+
 // ---- step execution ------------------------------------------------------------
-struct EvRec { hipEvent_t a = nullptr, b = nullptr; int op = -1; };
-constexpr uint32_t kProfileRepeat = 4;   // launches per event bracket in irmv_engine_profile
+struct EvRec { hipEvent_t a = nullptr, b = nullptr; };
+constexpr int kProfileRepeat = 4;   // launches per event bracket in irmv_engine_profile
 
 static void fill_conv_args(const irmv_engine *e, const Op &op, int first, int count, ConvArgs &a, bool fused)
 {
@@ -1975,6 +2027,13 @@ static LightArgs light_args(const irmv_engine *e, int first)
     return a;
 }
 
+static BayerArgs bayer_args(const irmv_engine *e, int first)   // a Bayer engine's demosaic of its raw slots from `first` on
+{
+    BayerArgs a = e->bayer;
+    a.raw = e->raw_dev + (size_t)first * e->src_bytes; a.dst = e->src_dev + (size_t)first * e->frame_bytes;
+    return a;
+}
+
 static PostArgs post_args(const irmv_engine *e, int first)
 {
     PostArgs p = e->post;
@@ -1991,7 +2050,6 @@ static PostArgs post_args(const irmv_engine *e, int first)
     return p;
 }
 
-// Enqueue one step on the engine stream.  ev != nullptr: bracket every kernel with events.
 // one fused C2f block (OP_C2F32).  (A 16 x 16 tile on an 8-wave workgroup -- a third less halo work, one workgroup per CU --
 // was built and measured in round 3: 5 - 30 % slower than the 8 x 16 tile in an eager replay, a tie in the benchmarked one;
 // dropped.)
@@ -2018,52 +2076,28 @@ static bool launch_c2f32_op(const irmv_engine *e, const Op &op, int first, int c
     return launch_c2f32(op.mode, op.shortcut, a, count, s);
 }
 
-static int enqueue_step(irmv_engine *e, int first, int count, uint32_t flags, bool post_only, std::vector<EvRec> *ev)
+// Enqueue a step of kind `kind` on slots [first, first + count), stream s: the launches of e->plans[kind], in order.
+// ev != nullptr (irmv_engine_profile): one event pair per launch, around `reps` repetitions of it (one if it is `once`).
+static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipStream_t s, int reps, std::vector<EvRec> *ev)
 {
     const int net = e->cfg.net_size;
-    const bool capturing = (flags & 0x40000000u) != 0;
-    const bool materialize = (flags & 0x20000000u) != 0;
     const PostArgs pa = post_args(e, first);
-    (void)capturing;   // a step is one line of launches (the Detect branches forked onto side streams inside the captured graph
-                       // measured 11 % slower: DESIGN.md section 6a; the option was removed in round 3)
-    for (const Op &op : e->ops) {
-        if (post_only && op.kind != OP_NMS && op.kind != OP_LIGHT && op.kind != OP_SCAN) continue;
-        if (op.kind == OP_SCAN && e->emit_scan && !post_only) continue;   // the class-branch convs have already filled the key lists
-        const bool grouped = op.kind == OP_CONV && op.group >= 0 && count == 1 && !materialize && !post_only;
-        if (grouped && e->head_groups[op.group].members[0] != (int)(&op - e->ops.data())) continue;   // rides in its group's launch
-        // a step skips the layers a fused kernel covers; a read-back runs only those (and the unfused form of a conv that
-        // normally carries a 1x1 in its epilogue)
-        // single-frame steps: the 64-channel Bottlenecks ride in their OP_BNECK launch; every other step runs the layers
-        const bool one_frame = count == 1 && !materialize && !post_only && e->bneck64;
-        if (op.kind == OP_BNECK ? !one_frame : (op.bneck >= 0 && one_frame)) continue;
-        const bool fused_kpt = !materialize && !post_only;   // every step runs a level's keypoint branch as its OP_KPT3 launch (where the engine has one)
-        if (op.kind == OP_KPT3 ? !fused_kpt : (op.kpt3 >= 0 && fused_kpt)) continue;
-        if (materialize ? !(op.fused_away || op.fuse_next >= 0 || ((op.bneck >= 0 || op.kpt3 >= 0) && op.kind == OP_CONV)) : op.fused_away) continue;
-        hipStream_t s = e->enq_stream ? e->enq_stream : e->stream;
+    for (const Launch &l : e->plans[kind]) {
+        const Op &op = e->ops[l.op];
         EvRec r{};
-        r.op = (int)(&op - e->ops.data());
         if (ev) {
             HIP_TRY(hipEventCreate(&r.a));
             HIP_TRY(hipEventCreate(&r.b));
             HIP_TRY(hipEventRecord(r.a, s));
         }
-        // every kernel is idempotent and can be repeated inside its event bracket -- except the light extraction and, with the
-        // split scan, the scan / NMS pair (the scan appends to the frame's candidate list, the NMS kernel consumes and resets it)
-        const bool once = op.kind == OP_LIGHT || (e->split_scan && (op.kind == OP_SCAN || op.kind == OP_NMS));
-        const int reps = (ev && !once) ? (int)(flags & 0xffu) : 1;
-        for (int rep = 0; rep < (reps > 0 ? reps : 1); rep++)
+        const int n = l.once ? 1 : reps;
+        for (int rep = 0; rep < n; rep++)
         switch (op.kind) {
-        case OP_DEMOSAIC: {
-            BayerArgs a = e->bayer;
-            a.raw = e->raw_dev + (size_t)first * e->src_bytes;
-            a.dst = e->src_dev + (size_t)first * e->frame_bytes;
-            launch_demosaic(a, count, s);
-            break;
-        }
+        case OP_DEMOSAIC: launch_demosaic(bayer_args(e, first), count, s); break;
         case OP_PRE: {
             PreArgs a;
             a.src = e->src_dev + (size_t)first * e->frame_bytes;
-            a.dst = static_cast<half_t *>(e->tensors[e->tensor_idx.at("input")].slot(first));
+            a.dst = static_cast<half_t *>(e->tensors[op.out_t].slot(first));
             a.tx = e->tap_x; a.ty = e->tap_y;
             a.sw = e->cfg.src_width; a.sh = e->cfg.src_height; a.net = net; a.swap_rb = e->cfg.swap_rb;
             a.src_slot_bytes = e->frame_bytes;
@@ -2100,10 +2134,7 @@ static int enqueue_step(irmv_engine *e, int first, int count, uint32_t flags, bo
             launch_c2f2(a, count, s);
             break;
         }
-        case OP_C2F32: {
-            if (!launch_c2f32_op(e, op, first, count, s)) return fail(IRMV_ERR_ARG, "no fused C2f kernel for " + op.layer);
-            break;
-        }
+        case OP_C2F32: if (!launch_c2f32_op(e, op, first, count, s)) return fail(IRMV_ERR_ARG, "no fused C2f kernel for " + op.layer); break;
         case OP_BNECK: {
             const Op &m1 = e->ops[op.sub[0]], &m2 = e->ops[op.sub[1]];
             const Tensor &ct = e->tensors[op.res_t];
@@ -2162,38 +2193,31 @@ static int enqueue_step(irmv_engine *e, int first, int count, uint32_t flags, bo
         }
         case OP_CONV0: {
             Conv0Args a;
-            a.x = static_cast<const half_t *>(e->tensors[e->tensor_idx.at("input")].slot(first));
-            a.y = static_cast<half_t *>(e->tensors[e->tensor_idx.at("0")].slot(first));
+            a.x = static_cast<const half_t *>(e->tensors[op.s0.t].slot(first));
+            a.y = static_cast<half_t *>(e->tensors[op.out_t].slot(first));
             a.w = e->conv0_w; a.b = e->conv0_b; a.net = net; a.batch = count;
             launch_conv0(a, s);
             break;
         }
         case OP_CONV: {
-            if (grouped) {   // (a profiled launch is repeated: only its last repetition appends candidates)
-                if (!launch_head_group(e, e->head_groups[op.group], first, rep == (reps > 0 ? reps : 1) - 1 ? &pa : nullptr, s))
-                    return fail(IRMV_ERR_ARG, std::string("grouped launch refused: ") + e->head_groups[op.group].name);
+            const unsigned scan = rep == n - 1 ? l.scan : 0u;   // (a profiled launch is repeated: only its last repetition appends candidates)
+            if (l.group >= 0) {
+                if (!launch_head_group(e, e->head_groups[l.group], first, &pa, scan, s)) return fail(IRMV_ERR_ARG, "grouped launch refused: " + l.name);
                 break;
             }
             ConvArgs a;
-            fill_conv_args(e, op, first, count, a, !materialize);
-            if (e->emit_scan && !materialize && !post_only && is_cls_final_carrier(op) && rep == (reps > 0 ? reps : 1) - 1)
-                scan_args_for(e, op, pa, a);   // (a profiled launch is repeated: only its last repetition appends)
-            const ConvCfg &cc = (count == 1 && stream_share(e, e->cfg.num_slots) > 1) ? op.cfg_one : op.cfg;
-            if (!run_conv(op, cc, a, count, s)) return fail(IRMV_ERR_ARG, std::string("no conv kernel for ") + op.kname + " (" + op.layer + ")");
+            fill_conv_args(e, op, first, count, a, l.fused);
+            if (scan) scan_args_for(e, op, pa, a);
+            if (!run_conv(op, l.cfg_one ? op.cfg_one : op.cfg, a, count, s)) return fail(IRMV_ERR_ARG, std::string("no conv kernel for ") + op.kname + " (" + op.layer + ")");
             break;
         }
         case OP_POOL: {
-            const Tensor &t = e->tensors[e->tensor_idx.at("9.cat")];
+            const Tensor &t = e->tensors[op.out_t];
             launch_sppf_pool(static_cast<half_t *>(t.slot(first)), count, t.H, t.W, t.C / 4, s);
             break;
         }
         case OP_SCAN: launch_scan_decode(pa, count, s); break;
-        case OP_NMS: {
-            PostArgs pn = pa;
-            pn.keys_only = ((e->emit_scan && !post_only) || (post_only && e->post_keys_only)) ? 1 : 0;
-            launch_nms_pnp(pn, count, s);
-            break;
-        }
+        case OP_NMS: { PostArgs pn = pa; pn.keys_only = l.keys_only ? 1 : 0; launch_nms_pnp(pn, count, s); break; }
         case OP_LIGHT: launch_light_extract(light_args(e, first), e->cfg.max_det, count, s); break;
         }
         HIP_TRY(hipGetLastError());
@@ -2249,17 +2273,17 @@ static int check_range(const irmv_engine *e, int first, int count)
     return IRMV_OK;
 }
 
-static int get_graph(irmv_engine *e, int first, int count, uint32_t flags, bool post_only, hipGraphExec_t *out)
+static int get_graph(irmv_engine *e, StepKind kind, int first, int count, bool upload, hipGraphExec_t *out)
 {
-    const GraphKey key{first, count, flags | (post_only ? 0x80000000u : 0u)};
+    const GraphKey key{first, count, kind, upload};
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) { *out = it->second; return IRMV_OK; }
     hipGraph_t g = nullptr;
     HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     int rc = IRMV_OK;
-    if (flags & 0x10000000u)   // the frames' upload as the graph's first node (synchronous single-stream submits): one or two frames as a kernel
+    if (upload)   // the frames' upload as the graph's first node (synchronous single-stream submits): one or two frames as a kernel
         rc = upload_sync(e, first, count, e->stream);
-    if (!rc) rc = enqueue_step(e, first, count, (flags & ~0x10000000u) | 0x40000000u, post_only, nullptr);
+    if (!rc) rc = enqueue_step(e, kind, first, count, e->stream, 1, nullptr);
     hipError_t ce = hipStreamEndCapture(e->stream, &g);
     if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
     if (ce != hipSuccess) return fail(IRMV_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
@@ -2309,8 +2333,9 @@ static int submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_
     // front the host stays far ahead of the GPU: 0.339 -> 0.331 ms per 1280 x 1024 frame).  Every other step is a graph replay.
     const bool eager = e->sync_launch == 1 && c == 1 && (flags & IRMV_SUBMIT_H2D) && !async_up;
     const bool graph_up = (flags & IRMV_SUBMIT_H2D) && !async_up && e->graph_upload && !eager;
+    const StepKind kind = c == 1 ? STEP_ONE : STEP_BATCH;
     hipGraphExec_t ge = nullptr;
-    if (!eager) TRY(get_graph(e, f, c, graph_up ? 0x10000000u : 0u, false, &ge));
+    if (!eager) TRY(get_graph(e, kind, f, c, graph_up, &ge));
     SlotGroup *g;
     TRY(group_of(e, f, c, &g));
     hipStream_t up = async_up ? e->h2d_stream : st;
@@ -2336,14 +2361,8 @@ static int submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_
             TRY(upload_sync(e, f, c, st));
         }
     }
-    if (eager) {
-        e->enq_stream = st;
-        const int rc = enqueue_step(e, f, c, 0, false, nullptr);
-        e->enq_stream = nullptr;
-        if (rc) return rc;
-    } else {
-        HIP_TRY(hipGraphLaunch(ge, st));
-    }
+    if (eager) TRY(enqueue_step(e, kind, f, c, st, 1, nullptr));
+    else HIP_TRY(hipGraphLaunch(ge, st));
     TRY(copy_out(e, f, c, st));
     HIP_TRY(hipEventRecord(g->out, st));
     g->in_flight = true;
@@ -2395,7 +2414,7 @@ extern "C" int irmv_engine_run_post(irmv_engine *e, int first, int count)
     HIP_TRY(hipSetDevice(e->cfg.device));
     TRY(irmv_engine_wait(e));
     hipGraphExec_t ge;
-    TRY(get_graph(e, first, count, 0, true, &ge));
+    TRY(get_graph(e, STEP_POST, first, count, false, &ge));
     HIP_TRY(hipGraphLaunch(ge, e->stream));
     TRY(copy_out(e, first, count));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -2496,10 +2515,7 @@ static int load_frame(irmv_engine *e, int slot, hipStream_t st)
 {
     TRY(copy_in(e, slot, 1, st));
     if (e->raw_dev) {
-        BayerArgs a = e->bayer;
-        a.raw = e->raw_dev + (size_t)slot * e->src_bytes;
-        a.dst = e->src_dev + (size_t)slot * e->frame_bytes;
-        launch_demosaic(a, 1, st);
+        launch_demosaic(bayer_args(e, slot), 1, st);
         HIP_TRY(hipGetLastError());
     }
     return IRMV_OK;
@@ -2613,7 +2629,7 @@ static int materialize_fused(irmv_engine *e, int slot)
     if (e->lazy_tensors.empty()) return IRMV_OK;
     HIP_TRY(hipSetDevice(e->cfg.device));
     TRY(irmv_engine_wait(e));
-    TRY(enqueue_step(e, slot, 1, 0x20000000u, false, nullptr));
+    TRY(enqueue_step(e, STEP_MATERIALIZE, slot, 1, e->stream, 1, nullptr));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return IRMV_OK;
 }
@@ -2706,52 +2722,33 @@ extern "C" int irmv_engine_profile(irmv_engine *e, int first, int count, irmv_ke
     if (!n) return fail(IRMV_ERR_ARG, "n is null");
     HIP_TRY(hipSetDevice(e->cfg.device));
     // Eager replay of the step's launches on the engine stream, every kernel bracketed by an event
-    // pair.  The kernels are idempotent and are launched kRep times inside their bracket: an event pair around ONE launch also times ~4 us of
+    // pair.  The kernels are idempotent and are launched kProfileRepeat times inside their bracket: an event pair around ONE launch also times ~4 us of
     // command-processor hand-over, which would read as kernel time on these 5-80 us kernels.
     // (Event-record nodes inside a captured graph cannot be read back with hipEventElapsedTime on
     // ROCm 7.2: "invalid resource handle".)
     TRY(irmv_engine_wait(e));
-    std::vector<EvRec> ev;
-    TRY(enqueue_step(e, first, count, kProfileRepeat, false, &ev));
+    const StepKind kind = count == 1 ? STEP_ONE : STEP_BATCH;
+    std::vector<EvRec> ev;   // (one per launch of the plan, in its order)
+    TRY(enqueue_step(e, kind, first, count, e->stream, kProfileRepeat, &ev));
     TRY(copy_out(e, first, count));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    int k = 0;
     for (size_t i = 0; i < ev.size(); i++) {
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, ev[i].a, ev[i].b));
         (void)hipEventDestroy(ev[i].a);
         (void)hipEventDestroy(ev[i].b);
-        const Op &op = e->ops[ev[i].op];
-        if (!(op.kind == OP_LIGHT || (e->split_scan && (op.kind == OP_SCAN || op.kind == OP_NMS)))) ms /= (float)kProfileRepeat;
-        if (k < cap && stats) {
-            irmv_kernel_stat &st = stats[k];
+        const Launch &l = e->plans[kind][i];
+        if ((int)i < cap && stats) {
+            irmv_kernel_stat &st = stats[i];
             memset(&st, 0, sizeof st);
-            if (op.kind == OP_CONV && op.group >= 0 && count == 1) {   // one launch for the whole group
-                const irmv_engine::HeadGroup &g = e->head_groups[op.group];
-                snprintf(st.name, sizeof st.name, "%s", g.name);
-                snprintf(st.layer, sizeof st.layer, "%s ... (%zu convs)", op.layer.c_str(), g.members.size());
-                for (int mi : g.members) {
-                    const Op &mo = e->ops[mi];
-                    st.flops += mo.flops + (mo.fuse_next >= 0 ? e->ops[mo.fuse_next].flops : 0.0);
-                    st.bytes += mo.bytes;
-                }
-            } else {
-            snprintf(st.name, sizeof st.name, "%s", (count == 1 && stream_share(e, e->cfg.num_slots) > 1 && op.kind == OP_CONV) ? op.kname_one : op.kname);
-            snprintf(st.layer, sizeof st.layer, "%s", op.layer.c_str());
-            st.flops = (op.flops + (op.fuse_next >= 0 ? e->ops[op.fuse_next].flops : 0.0)) * count;
-            double b = op.bytes, w = op.w_bytes;
-            if (op.fuse_next >= 0) {   // the fused 1x1's output is what reaches memory, its weights ride along
-                const Op &nx = e->ops[op.fuse_next];
-                b += nx.out_bytes - op.out_bytes + nx.w_bytes;
-                w += nx.w_bytes;
-            }
-            st.bytes = (b - w) * count + w;   // activations per frame, weights once per launch
-            }
-            st.ms = ms;
+            snprintf(st.name, sizeof st.name, "%s", l.name.c_str());
+            snprintf(st.layer, sizeof st.layer, "%s", l.layer.c_str());
+            st.flops = l.flops * count;
+            st.bytes = l.bytes * count + l.launch_bytes;
+            st.ms = l.once ? ms : ms / (float)kProfileRepeat;
         }
-        k++;
     }
-    *n = k;
+    *n = (int)ev.size();
     return IRMV_OK;
 }
 
