@@ -9,8 +9,8 @@
  * sizes, POD structs.  The header-only C++ facade in include/irmv_detection/
  * wraps these entry points 1:1 behind the reference's own class names.
  *
- * Every entry returns IRMV_OK (0) or a negative error code; irmv_last_error()
- * returns a thread-local message.  (The reference checks no CUDA/NPP/TensorRT
+ * Every entry returns IRMV_OK (0) or a negative error code (one test hook also
+ * IRMV_DECLINED); irmv_last_error() returns a thread-local message.  (The reference checks no CUDA/NPP/TensorRT
  * return code at all -- src/yolo_engine.cpp passim.)
  *
  * There is no CPU fallback anywhere behind this ABI: without a HIP device every
@@ -255,6 +255,54 @@ int irmv_engine_read_tap(irmv_engine *e, int slot, const char *name, float *nhwc
 int irmv_engine_read_raw(irmv_engine *e, int slot, irmv_raw_dets *out);
 int irmv_engine_num_anchors(const irmv_engine *e);
 int irmv_engine_head_channels(const irmv_engine *e);
+
+/* ---- per-layer conv test hooks (tests/test_gpu_conv_candidates.py) ------
+ * Every conv layer of the engine, every tile candidate its autotuner timed, run one at a time on a slot range. */
+typedef struct irmv_conv_seg {
+    char tensor[32];            /* irmv_engine_read_tap name; "" = none */
+    int32_t coff, C, shift;     /* channel offset and count in that tensor; shift 1: read as its nearest 2x upsample */
+} irmv_conv_seg;
+
+typedef struct irmv_conv_op {
+    int32_t op;                 /* the engine's op index: the `op` argument of the calls below */
+    char layer[32];             /* weight layer, as the blob names it */
+    int32_t ks, stride, act, out_f32, cin, cout, cout_pad;
+    int32_t Hin, Win, Hout, Wout;
+    irmv_conv_seg s0, s1;       /* input = concat(s0, s1) along channels */
+    irmv_conv_seg res;          /* residual added after the activation (C = cout); tensor "" = none */
+    char out_tensor[32];        /* output channels [out_coff, out_coff + cout_pad) of this tensor */
+    int32_t out_coff;
+    int32_t out_lazy;           /* a step does not write out_tensor (a fused kernel keeps it on chip) */
+    int32_t fused;              /* a step runs this conv with its branch's final 1x1 in the epilogue ... */
+    int32_t tune_fused;         /* ... and the autotuner listed candidates for that epilogue */
+    char fuse_layer[32];        /* that 1x1: its layer, output tensor, channel offset and cout (fused or tune_fused) */
+    char fuse_tensor[32];
+    int32_t fuse_coff, fuse_cout, fuse_cout_pad;
+    int32_t reserved;
+    char kname[48], kname_one[48];   /* the tiles chosen for the stream share and for one slot */
+} irmv_conv_op;
+
+typedef struct irmv_conv_cand {
+    char name[48];              /* kernel name, as irmv_engine_profile names it */
+    int32_t mt, nt, flags, ipw; /* the tile as the tune cache stores it */
+    int32_t forced, reserved;   /* forced: an IRMV_FORCE_* switch put the layer on it */
+} irmv_conv_cand;
+
+#define IRMV_DECLINED 1         /* irmv_engine_run_conv_candidate: no kernel instantiation runs that candidate */
+
+/* One record per conv op, in step order; *n = their number (records beyond cap are not written). */
+int irmv_engine_conv_ops(irmv_engine *e, irmv_conv_op *ops, int cap, int *n);
+/* The candidate list the autotuner timed for conv op `op` at tune_count (the stream share of num_slots, or 1). */
+int irmv_engine_conv_candidates(irmv_engine *e, int op, int tune_count, irmv_conv_cand *cands, int cap, int *n);
+#define IRMV_RUN_POISON 1u       /* first fill the output channels the run must write (cout of them; for a run that carries
+                                     the fused 1x1, that 1x1's head slice) on its slots with all-ones bytes, a NaN */
+#define IRMV_RUN_POISON_ONLY 2u  /* ... and launch nothing (shows that a run which writes nothing is seen) */
+/* Run candidate `cand` of that list (-1: the engine's own choice for tune_count) on slots [first, first + count) and
+ * synchronize.  IRMV_DECLINED if no kernel runs it; IRMV_ERR_ARG for an op whose output overlaps one of its inputs. */
+int irmv_engine_run_conv_candidate(irmv_engine *e, int op, int tune_count, int cand, int first_slot, int count, uint32_t flags);
+/* The raw storage (fp16 bits at the activation scale, or fp32) of a tensor's slots [first, first + count); bytes must
+ * equal its size.  Unlike irmv_engine_read_tap it never recomputes a tensor a step keeps on chip. */
+int irmv_engine_read_tensor(irmv_engine *e, const char *name, int first_slot, int count, void *dst, size_t bytes);
 
 /* Run one step eagerly with a HIP event pair around every kernel launch. */
 int irmv_engine_profile(irmv_engine *e, int first_slot, int count, irmv_kernel_stat *stats, int cap, int *n);

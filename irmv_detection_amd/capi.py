@@ -71,6 +71,32 @@ class KernelStat(C.Structure):
                 ("bytes", C.c_double), ("ms", C.c_float), ("reserved", C.c_int32)]
 
 
+class ConvSeg(C.Structure):
+    _fields_ = [("tensor", C.c_char * 32), ("coff", C.c_int32), ("C", C.c_int32), ("shift", C.c_int32)]
+
+
+class ConvOp(C.Structure):
+    _fields_ = [("op", C.c_int32), ("layer", C.c_char * 32),
+                ("ks", C.c_int32), ("stride", C.c_int32), ("act", C.c_int32), ("out_f32", C.c_int32),
+                ("cin", C.c_int32), ("cout", C.c_int32), ("cout_pad", C.c_int32),
+                ("Hin", C.c_int32), ("Win", C.c_int32), ("Hout", C.c_int32), ("Wout", C.c_int32),
+                ("s0", ConvSeg), ("s1", ConvSeg), ("res", ConvSeg),
+                ("out_tensor", C.c_char * 32), ("out_coff", C.c_int32), ("out_lazy", C.c_int32),
+                ("fused", C.c_int32), ("tune_fused", C.c_int32),
+                ("fuse_layer", C.c_char * 32), ("fuse_tensor", C.c_char * 32),
+                ("fuse_coff", C.c_int32), ("fuse_cout", C.c_int32), ("fuse_cout_pad", C.c_int32), ("reserved", C.c_int32),
+                ("kname", C.c_char * 48), ("kname_one", C.c_char * 48)]
+
+
+class ConvCand(C.Structure):
+    _fields_ = [("name", C.c_char * 48), ("mt", C.c_int32), ("nt", C.c_int32), ("flags", C.c_int32), ("ipw", C.c_int32),
+                ("forced", C.c_int32), ("reserved", C.c_int32)]
+
+
+DECLINED = 1    # irmv_engine_run_conv_candidate: no kernel runs that candidate
+RUN_POISON, RUN_POISON_ONLY = 1, 2   # ... its flags: NaN over the output it must write first (and launch nothing)
+
+
 # every symbol include/irmv_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -115,6 +141,10 @@ SYMBOLS = [
     ("irmv_engine_read_raw", C.c_int, [_P, C.c_int, C.POINTER(RawDets)]),
     ("irmv_engine_num_anchors", C.c_int, [_P]),
     ("irmv_engine_head_channels", C.c_int, [_P]),
+    ("irmv_engine_conv_ops", C.c_int, [_P, C.POINTER(ConvOp), C.c_int, C.POINTER(C.c_int)]),
+    ("irmv_engine_conv_candidates", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(ConvCand), C.c_int, C.POINTER(C.c_int)]),
+    ("irmv_engine_run_conv_candidate", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]),
+    ("irmv_engine_read_tensor", C.c_int, [_P, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     ("irmv_engine_profile", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_pnp_create", C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_P)]),
     ("irmv_pnp_destroy", None, [_P]),

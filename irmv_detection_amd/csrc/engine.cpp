@@ -149,6 +149,15 @@ struct Tensor {
 
 struct SegRef { int t = -1, coff = 0, C = 0, shift = 0; };
 
+// The environment switches of the tuner, read once per engine: each takes effect for every engine created after it is set.
+struct TuneSwitches {
+    bool untuned, verbose, warn;        // IRMV_AUTOTUNE=0, IRMV_AUTOTUNE_VERBOSE, IRMV_TUNE_WARN
+    bool has_s2, has_wres;              // IRMV_FORCE_S2=lds|ct|deep, IRMV_FORCE_WRES=<n> (parity tests) are set ...
+    std::string force_s2, force_wres;   // ... to these values (copies: an engine's hooks read them after the environment may have changed)
+    bool force_pw, force_pwn, force_cm, force_w8, force_nt8, force_pf4;
+    bool no_pw, no_pwn, no_pf2, no_pf4, no_cm, no_w8, no_nt8, no_wres, no_deep;
+};
+
 enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_DEMOSAIC };
 
 struct Op {
@@ -178,6 +187,7 @@ struct Op {
     int group = -1;            // single-frame steps: index into irmv_engine::head_groups of the one launch this conv rides in
     int bneck = -1;            // single-frame steps: index of the OP_BNECK launch (k_bneck.hip) that computes this conv; OP_BNECK itself: 1 = kept
     int kpt3 = -1;             // a keypoint-branch conv: index of the OP_KPT3 launch (k_kpt.hip) that computes its level's branch in every step; OP_KPT3 itself: 1
+    int tune_fuse[2] = {-1, -1};   // OP_CONV: fuse_next as the autotuner's two passes (stream share, one slot) found it (test hooks rebuild their candidate lists)
 };
 
 // What a step launches depends only on its kind and the engine, so each kind's launch list is decided at creation (build_step_plans).
@@ -289,6 +299,7 @@ struct irmv_engine {
     bool bneck64 = true;       // single-frame steps run the 64-channel Bottlenecks of the C2f blocks (and their cv2) as one launch each (IRMV_BNECK64=0: off)
     bool merge_head0 = false;
     bool kpt3 = true;          // the keypoint branch of a Detect level as one launch (engines that do not merge the first-stage Detect convs; IRMV_KPT3=0: off)
+    TuneSwitches tune_sw{};    // the tuner's switches as autotune_convs read them (the conv test hooks list the same candidates)
 
     ~irmv_engine();
 };
@@ -1542,21 +1553,15 @@ static ConvCfg tile_cfg(const ConvCfg &base, int mt, int nt, int flags, int ipw)
     return c;
 }
 
-// The environment switches of the tuner, read once per engine: each takes effect for every engine created after it is set.
-struct TuneSwitches {
-    bool untuned, verbose, warn;        // IRMV_AUTOTUNE=0, IRMV_AUTOTUNE_VERBOSE, IRMV_TUNE_WARN
-    const char *force_s2, *force_wres;  // IRMV_FORCE_S2=lds|ct|deep, IRMV_FORCE_WRES=<n> (parity tests)
-    bool force_pw, force_pwn, force_cm, force_w8, force_nt8, force_pf4;
-    bool no_pw, no_pwn, no_pf2, no_pf4, no_cm, no_w8, no_nt8, no_wres, no_deep;
-};
-
 static TuneSwitches tune_switches()
 {
     auto on = [](const char *name) { return getenv(name) != nullptr; };
     const char *at = getenv("IRMV_AUTOTUNE"), *nd = getenv("IRMV_NO_DEEP");
     TuneSwitches s;
     s.untuned = at && at[0] == '0'; s.verbose = on("IRMV_AUTOTUNE_VERBOSE"); s.warn = on("IRMV_TUNE_WARN");
-    s.force_s2 = getenv("IRMV_FORCE_S2"); s.force_wres = getenv("IRMV_FORCE_WRES");
+    const char *s2 = getenv("IRMV_FORCE_S2"), *wres = getenv("IRMV_FORCE_WRES");
+    s.has_s2 = s2 != nullptr; s.force_s2 = s2 ? s2 : "";
+    s.has_wres = wres != nullptr; s.force_wres = wres ? wres : "";
     s.force_pw = on("IRMV_FORCE_PW"); s.force_pwn = on("IRMV_FORCE_PWN"); s.force_cm = on("IRMV_FORCE_CM");
     s.force_w8 = on("IRMV_FORCE_W8"); s.force_nt8 = on("IRMV_FORCE_NT8"); s.force_pf4 = on("IRMV_FORCE_PF4");
     s.no_pw = on("IRMV_NO_PW"); s.no_pwn = on("IRMV_NO_PWN"); s.no_pf2 = on("IRMV_NO_PF2"); s.no_pf4 = on("IRMV_NO_PF4");
@@ -1577,10 +1582,10 @@ static std::vector<TuneCand> tune_candidates(const Op &op, const ConvArgs &a, in
     std::vector<TuneCand> v;
     // IRMV_FORCE_S2=lds|ct|deep (parity test): the stride-2 layers of the LDS family on ONE of their three bit-identical
     // implementations -- the LDS kernel, the direct kernel walking K chunk-major, its deep-prefetch form
-    const bool s2 = sw.force_s2 && lds_ok && op.cfg.stride == 2;
+    const bool s2 = sw.has_s2 && lds_ok && op.cfg.stride == 2;
     auto add = [&](const ConvCfg &c, bool forced = false) {
         if (op.cout_pad % (16 * c.nt) != 0) return;
-        if (s2 && !forced && strcmp(c.lds ? "lds" : (c.deep ? "deep" : "ct"), sw.force_s2) != 0) return;
+        if (s2 && !forced && sw.force_s2 != (c.lds ? "lds" : (c.deep ? "deep" : "ct"))) return;
         if (c.wr ? !(op.w_lds[2] && conv_wres_bytes(a, c.stride, c.pp) > 0)
                  : c.lds && !(op.w_lds[lds_index(c.nt)] && conv_lds_bytes(a, c.stride, c.mt, c.nt, nullptr, c.w8) > 0)) return;
         v.push_back({c, forced});
@@ -1632,8 +1637,8 @@ static std::vector<TuneCand> tune_candidates(const Op &op, const ConvArgs &a, in
     // parity tests: IRMV_FORCE_WRES=<n> puts every eligible layer on the resident-weights kernel with n images per
     // workgroup -- the ping-pong form (listed last, so it wins) where the map tiles into its blocks (n < 0: never), else the
     // lockstep form
-    if (sw.force_wres && lds_ok && count >= 2) {
-        const int n = atoi(sw.force_wres);
+    if (sw.has_wres && lds_ok && count >= 2) {
+        const int n = atoi(sw.force_wres.c_str());
         for (int ppv = 0; ppv <= (n > 0 ? 1 : 0); ppv++) add(tile_cfg(op.cfg, 2, 4, T_LDS | T_WR | (ppv ? T_PP : 0), std::max(1, std::min(count, n < 0 ? -n : n))), true);
     }
     // 1x1 layers: the persistent pointwise kernel (same operands, same k order as the direct kernel)
@@ -1657,9 +1662,36 @@ static std::vector<TuneCand> tune_candidates(const Op &op, const ConvArgs &a, in
     return v;
 }
 
+// How the tuner sees a conv op on slots [first, first + count): its arguments, whether it is tuned for its branch's final
+// 1x1 in the epilogue (op.fuse_next), and its kernel family.  autotune_convs and the conv test hooks both use it.
+struct ConvView { ConvArgs a; bool want_fuse, lds_ok; };
+static ConvView conv_view(const irmv_engine *e, const Op &op, int first, int count)
+{
+    ConvView v;
+    const bool fuse_k16 = op.fuse_next >= 0 && op.cfg.cin16;   // the keypoint final in the direct kernel's epilogue: any pixel tile (nt = 1 is the layer's only one)
+    v.want_fuse = op.fuse_next >= 0 && !fuse_k16;
+    fill_conv_args(e, op, first, count, v.a, v.want_fuse || fuse_k16);
+    if (v.want_fuse) {   // the fused epilogue needs an LDS-family tile that owns all 64 channels (nt = 4)
+        bool f_ok = false;
+        for (int mt = 1; mt <= 4 && !f_ok; mt *= 2) f_ok = op.w_lds[2] && conv_lds_bytes(v.a, op.cfg.stride, mt, 4, nullptr) > 0;
+        if (!f_ok) {
+            v.want_fuse = false;
+            fill_conv_args(e, op, first, count, v.a, false);
+        }
+    }
+    // Kernel family by a rule that does not depend on the batch (the two families walk K in
+    // different orders): LDS-staged whenever some tile of it fits this layer, else direct.
+    v.lds_ok = false;
+    if (op.cfg.ks == 3 && op.cfg.act == 1 && !op.cfg.out_f32)
+        for (int mt = 1; mt <= 4 && !v.lds_ok; mt *= 2)
+            for (int nt = 1; nt <= 4 && !v.lds_ok; nt *= 2) v.lds_ok = op.w_lds[lds_index(nt)] && conv_lds_bytes(v.a, op.cfg.stride, mt, nt, nullptr) > 0;
+    return v;
+}
+
 static int autotune_convs(irmv_engine *e)
 {
     const TuneSwitches sw = tune_switches();
+    e->tune_sw = sw;
     tune_cache_load();
     hipEvent_t ea, eb;
     HIP_TRY(hipEventCreate(&ea));
@@ -1669,32 +1701,18 @@ static int autotune_convs(irmv_engine *e)
         if (op.kind != OP_CONV) continue;
         for (int pass = 0; pass < (counts[0] > 1 ? 2 : 1); pass++) {
             const int count = counts[pass];
-            ConvArgs a;
-            const bool fuse_k16 = op.fuse_next >= 0 && op.cfg.cin16;   // the keypoint final in the direct kernel's epilogue: any pixel tile (nt = 1 is the layer's only one)
-            bool want_fuse = op.fuse_next >= 0 && !fuse_k16;
-            fill_conv_args(e, op, 0, count, a, want_fuse || fuse_k16);
-            if (want_fuse) {   // the fused epilogue needs an LDS-family tile that owns all 64 channels (nt = 4)
-                bool f_ok = false;
-                for (int mt = 1; mt <= 4 && !f_ok; mt *= 2) f_ok = op.w_lds[2] && conv_lds_bytes(a, op.cfg.stride, mt, 4, nullptr) > 0;
-                if (!f_ok) {
-                    op.fuse_next = -1;
-                    want_fuse = false;
-                    fill_conv_args(e, op, 0, count, a, false);
-                }
-            }
-            // Kernel family by a rule that does not depend on the batch (the two families walk K in
-            // different orders): LDS-staged whenever some tile of it fits this layer, else direct.
-            bool lds_ok = false;
-            if (op.cfg.ks == 3 && op.cfg.act == 1 && !op.cfg.out_f32)
-                for (int mt = 1; mt <= 4 && !lds_ok; mt *= 2)
-                    for (int nt = 1; nt <= 4 && !lds_ok; nt *= 2) lds_ok = op.w_lds[lds_index(nt)] && conv_lds_bytes(a, op.cfg.stride, mt, nt, nullptr) > 0;
+            op.tune_fuse[pass] = op.fuse_next;
+            const ConvView v = conv_view(e, op, 0, count);
+            if (!v.want_fuse && !op.cfg.cin16) op.fuse_next = -1;   // no tile can carry the 1x1: the layers stay apart
+            const ConvArgs &a = v.a;
+            const bool want_fuse = v.want_fuse, lds_ok = v.lds_ok;
             char key[160];
             snprintf(key, sizeof key, "gfx950.t5|%d.%d.%d.%d.%d.%d|%dx%d>%dx%d|c%d.%d.%d.%d>%d|ld%d.%d.%d|n%d|%d", op.cfg.ks, op.cfg.stride,   // ".t5": the table format / flag set of round 5 -- entries of another round's file never match, so they are re-tuned, not reinterpreted
                      (int)op.cfg.cin16, op.cfg.act, (int)op.cfg.out_f32, (int)lds_ok, a.Hin, a.Win, a.Hout, a.Wout, a.s0.C, a.s1.C, a.s0.shift,
                      a.s1.shift, a.cout_pad, a.s0.ld, a.s1.ld, a.out_ld, count, (a.res ? 1 : 0) + 2 * a.n2);
             const std::vector<TuneCand> cands = tune_candidates(op, a, count, want_fuse, lds_ok, sw, e->num_cus);
             // a forced layer neither replays a cached choice nor leaves its own for a later engine; nor does an untuned one
-            const bool forced = (sw.force_s2 && lds_ok && op.cfg.stride == 2) || std::any_of(cands.begin(), cands.end(), [](const TuneCand &k) { return k.forced; });
+            const bool forced = (sw.has_s2 && lds_ok && op.cfg.stride == 2) || std::any_of(cands.begin(), cands.end(), [](const TuneCand &k) { return k.forced; });
             ConvCfg best_cfg = pass == 0 ? op.cfg : op.cfg_one;
             bool have_hit = false;
             if (!forced && !sw.untuned && !sw.verbose) {   // a cached choice (this process, or an IRMV_TUNE_CACHE file) is replayed if it is a candidate
@@ -2695,6 +2713,152 @@ extern "C" int irmv_engine_read_tap(irmv_engine *e, int slot, const char *name, 
     std::vector<float> v;
     TRY(read_tensor_f32(e, t, slot, v));
     memcpy(nhwc, v.data(), v.size() * 4);
+    return IRMV_OK;
+}
+
+// ---- per-layer conv test hooks (tests/test_gpu_conv_candidates.py) ---------------------
+extern "C" int irmv_engine_read_tensor(irmv_engine *e, const char *name, int first, int count, void *dst, size_t bytes)
+{
+    TRY(check_range(e, first, count));
+    if (!name) return fail(IRMV_ERR_ARG, "name is null");
+    auto it = e->tensor_idx.find(name);
+    if (it == e->tensor_idx.end()) return fail(IRMV_ERR_ARG, std::string("no tensor named ") + name);
+    const Tensor &t = e->tensors[it->second];
+    const size_t need = t.slot_elems * t.esize() * count;
+    if (!dst || bytes != need) return fail(IRMV_ERR_ARG, "read_tensor: buffer size does not match the slot range");
+    TRY(irmv_engine_wait(e));
+    HIP_TRY(hipMemcpy(dst, t.slot(first), need, hipMemcpyDeviceToHost));
+    return IRMV_OK;
+}
+
+static int conv_op_at(const irmv_engine *e, int op)
+{
+    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
+    if (op < 0 || op >= (int)e->ops.size() || e->ops[op].kind != OP_CONV) return fail(IRMV_ERR_ARG, "not a conv op");
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_conv_ops(irmv_engine *e, irmv_conv_op *ops, int cap, int *n)
+{
+    if (!e || !n) return fail(IRMV_ERR_ARG, "engine / n is null");
+    auto name = [](char *dst, size_t cap_, const std::string &s) { snprintf(dst, cap_, "%s", s.c_str()); };
+    auto seg = [&](irmv_conv_seg &d, const SegRef &s) {
+        memset(&d, 0, sizeof d);
+        if (s.t < 0 || s.C == 0) return;
+        name(d.tensor, sizeof d.tensor, e->tensors[s.t].name);
+        d.coff = s.coff; d.C = s.C; d.shift = s.shift;
+    };
+    int k = 0;
+    for (size_t i = 0; i < e->ops.size(); i++) {
+        const Op &op = e->ops[i];
+        if (op.kind != OP_CONV) continue;
+        if (ops && k < cap) {
+            irmv_conv_op &r = ops[k];
+            memset(&r, 0, sizeof r);
+            r.op = (int32_t)i;
+            name(r.layer, sizeof r.layer, op.layer);
+            r.ks = op.cfg.ks; r.stride = op.cfg.stride; r.act = op.cfg.act; r.out_f32 = op.cfg.out_f32;
+            r.cin = op.cin; r.cout = op.cout; r.cout_pad = op.cout_pad;
+            r.Hin = op.Hin; r.Win = op.Win; r.Hout = op.Hout; r.Wout = op.Wout;
+            seg(r.s0, op.s0);
+            seg(r.s1, op.s1);
+            if (op.res_t >= 0) seg(r.res, SegRef{op.res_t, op.res_coff, op.cout, 0});
+            const Tensor &ot = e->tensors[op.out_t];
+            name(r.out_tensor, sizeof r.out_tensor, ot.name);
+            r.out_coff = op.out_coff;
+            r.out_lazy = e->lazy_tensors.count(ot.name) ? 1 : 0;
+            r.fused = op.fuse_next >= 0;
+            r.tune_fused = op.tune_fuse[0] >= 0 || op.tune_fuse[1] >= 0;
+            const int f = op.fuse_next >= 0 ? op.fuse_next : std::max(op.tune_fuse[0], op.tune_fuse[1]);
+            if (f >= 0) {
+                const Op &o2 = e->ops[f];
+                name(r.fuse_layer, sizeof r.fuse_layer, o2.layer);
+                name(r.fuse_tensor, sizeof r.fuse_tensor, e->tensors[o2.out_t].name);
+                r.fuse_coff = o2.out_coff; r.fuse_cout = o2.cout; r.fuse_cout_pad = o2.cout_pad;
+            }
+            name(r.kname, sizeof r.kname, op.kname);
+            name(r.kname_one, sizeof r.kname_one, op.kname_one);
+        }
+        k++;
+    }
+    *n = k;
+    return IRMV_OK;
+}
+
+// The op as the tuner saw it at tune_count (which of its two passes, and the fused 1x1 that pass was tuned for);
+// cands: that pass's candidate list, exactly as autotune_convs built it.
+static int conv_tune_pass(const irmv_engine *e, int op, int tune_count, Op &o, std::vector<TuneCand> &cands)
+{
+    TRY(conv_op_at(e, op));
+    const int share = stream_share(e, e->cfg.num_slots);
+    if (tune_count != share && tune_count != 1) return fail(IRMV_ERR_ARG, "tune_count is neither the stream share nor 1");
+    o = e->ops[op];
+    o.fuse_next = o.tune_fuse[tune_count == share ? 0 : 1];
+    const ConvView v = conv_view(e, o, 0, tune_count);
+    cands = tune_candidates(o, v.a, tune_count, v.want_fuse, v.lds_ok, e->tune_sw, e->num_cus);
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_conv_candidates(irmv_engine *e, int op, int tune_count, irmv_conv_cand *out, int cap, int *n)
+{
+    if (!n) return fail(IRMV_ERR_ARG, "n is null");
+    Op o;
+    std::vector<TuneCand> cands;
+    TRY(conv_tune_pass(e, op, tune_count, o, cands));
+    for (size_t i = 0; i < cands.size() && out && (int)i < cap; i++) {
+        irmv_conv_cand &r = out[i];
+        memset(&r, 0, sizeof r);
+        cfg_name(cands[i].c, r.name, sizeof r.name);
+        const TuneEntry t = tune_entry(cands[i].c);
+        r.mt = t.mt; r.nt = t.nt; r.flags = t.flags; r.ipw = t.ipw;
+        r.forced = cands[i].forced;
+    }
+    *n = (int)cands.size();
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_run_conv_candidate(irmv_engine *e, int op, int tune_count, int cand, int first, int count, uint32_t flags)
+{
+    TRY(check_range(e, first, count));
+    Op o;
+    std::vector<TuneCand> cands;
+    TRY(conv_tune_pass(e, op, tune_count, o, cands));
+    if (cand < -1 || cand >= (int)cands.size()) return fail(IRMV_ERR_ARG, "no such candidate");
+    const Op &real = e->ops[op];
+    // re-running a conv must not change its own inputs: refuse an output range that overlaps one of them
+    auto overlaps = [](int t, int lo, int hi, int t2, int lo2, int hi2) { return t >= 0 && t == t2 && lo < hi2 && lo2 < hi; };
+    const int o0 = real.out_coff, o1 = real.out_coff + real.cout_pad;
+    if (overlaps(real.out_t, o0, o1, real.s0.t, real.s0.coff, real.s0.coff + real.s0.C) ||
+        overlaps(real.out_t, o0, o1, real.s1.t, real.s1.coff, real.s1.coff + real.s1.C) ||
+        overlaps(real.out_t, o0, o1, real.res_t, real.res_coff, real.res_coff + real.cout_pad))
+        return fail(IRMV_ERR_ARG, "conv op writes one of its own inputs");
+    TRY(irmv_engine_wait(e));
+    ConvCfg c;
+    if (cand >= 0) c = cands[cand].c;
+    else {   // the engine's own choice for tune_count, with the epilogue a step runs it with
+        o = real;
+        c = tune_count == stream_share(e, e->cfg.num_slots) ? real.cfg : real.cfg_one;
+    }
+    const ConvView v = conv_view(e, o, first, count);
+    if (flags & (IRMV_RUN_POISON | IRMV_RUN_POISON_ONLY)) {
+        // all-ones bytes (a NaN in fp16 and in fp32) over the real output channels of the slots the run must write: the
+        // fused 1x1's slice of the head when the run carries it (the 3x3's own output then never leaves the registers)
+        const Op &w = v.a.n2 > 0 ? e->ops[o.fuse_next] : real;
+        const Tensor &t = e->tensors[w.out_t];
+        if (w.out_coff + w.cout > t.C) return fail(IRMV_ERR_ARG, "output channels out of range");
+        HIP_TRY(hipMemset2DAsync(static_cast<char *>(t.slot(first)) + (size_t)w.out_coff * t.esize(), (size_t)t.C * t.esize(), 0xff,
+                                 (size_t)w.cout * t.esize(), (size_t)count * t.H * t.W, e->stream));
+        if (flags & IRMV_RUN_POISON_ONLY) {
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            return IRMV_OK;
+        }
+    }
+    if (!run_conv(o, c, v.a, count, e->stream)) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        return IRMV_DECLINED;
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return IRMV_OK;
 }
 

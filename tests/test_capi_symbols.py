@@ -32,14 +32,19 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
 
 def test_struct_layouts_match_the_header(tmp_path):
     src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "irmv_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu\\n",'
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "irmv_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu'
+                   ' %zu %zu %zu %zu %zu %zu %zu\\n",'
                    'sizeof(irmv_engine_cfg), sizeof(irmv_det), sizeof(irmv_raw_dets), sizeof(irmv_kernel_stat),'
-                   'offsetof(irmv_engine_cfg, camera_matrix), offsetof(irmv_engine_cfg, weights_path), offsetof(irmv_det, rvec));return 0;}\n')
+                   'offsetof(irmv_engine_cfg, camera_matrix), offsetof(irmv_engine_cfg, weights_path), offsetof(irmv_det, rvec),'
+                   'sizeof(irmv_conv_seg), sizeof(irmv_conv_op), sizeof(irmv_conv_cand), offsetof(irmv_conv_op, res),'
+                   'offsetof(irmv_conv_op, fuse_layer), offsetof(irmv_conv_op, kname_one), offsetof(irmv_conv_cand, forced));return 0;}\n')
     exe = tmp_path / "sz"
     subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
     got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
     exp = [C.sizeof(capi.EngineCfg), C.sizeof(capi.Det), C.sizeof(capi.RawDets), C.sizeof(capi.KernelStat),
-           capi.EngineCfg.camera_matrix.offset, capi.EngineCfg.weights_path.offset, capi.Det.rvec.offset]
+           capi.EngineCfg.camera_matrix.offset, capi.EngineCfg.weights_path.offset, capi.Det.rvec.offset,
+           C.sizeof(capi.ConvSeg), C.sizeof(capi.ConvOp), C.sizeof(capi.ConvCand), capi.ConvOp.res.offset,
+           capi.ConvOp.fuse_layer.offset, capi.ConvOp.kname_one.offset, capi.ConvCand.forced.offset]
     assert got == exp
 
 
