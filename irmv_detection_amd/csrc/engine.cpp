@@ -1509,32 +1509,9 @@ static void tune_cache_save()
     for (auto &kv : g_tune_cache) f << kv.first << ' ' << kv.second.mt << ' ' << kv.second.nt << ' ' << kv.second.flags << ' ' << kv.second.ipw << '\n';
 }
 
-static int lds_index(int nt) { return nt == 8 ? 3 : (nt == 4 ? 2 : (nt == 2 ? 1 : 0)); }
+static ConvWeights conv_weights(const Op &op) { return {op.w_packed, {op.w_lds[0], op.w_lds[1], op.w_lds[2], op.w_lds[3]}, op.w_k16}; }
 
-static bool run_conv(const Op &op, const ConvCfg &c, const ConvArgs &a, int count, hipStream_t s)
-{
-    const int li = lds_index(c.nt);
-    if (op.w_k16) return launch_conv_k16(a, s);   // the keypoint finals: one kernel, whatever the tile table says (same bits as their fused form)
-    if (c.pw) return launch_conv_pw(c, a, s);
-    if (c.wr) return c.lds && op.w_lds[2] && launch_conv_wres(c.ipw, a, op.w_lds[2], count, s, c.pp);
-    if (c.lds) return op.w_lds[li] && launch_conv_lds(c.stride, c.mt, c.nt, c.ipw, a, op.w_lds[li], count, s, c.pf4 ? 2 : (c.pf2 ? 1 : 0), c.cm, c.w8);
-    if (c.ct) {   // direct kernel in the LDS family's K order, on that family's nt = 1 weight packing
-        if (!op.w_lds[0] || a.n2 > 0) return false;
-        ConvArgs a2 = a;
-        a2.w = op.w_lds[0];
-        return launch_conv(c, a2, s);
-    }
-    return launch_conv(c, a, s);
-}
-
-static void cfg_name(const ConvCfg &c, char *buf, int n)
-{
-    if (c.pw) snprintf(buf, n, c.ipw > 1 ? "conv1x1s1_pw_n%d" : "conv1x1s1_pw", c.ipw);
-    else if (c.wr) snprintf(buf, n, "conv3x3s1_wres%s_i%d", c.pp ? "_pp" : "", c.ipw);
-    else if (c.lds && c.ipw > 1) snprintf(buf, n, "conv3x3s%d_lds_mt%d_nt%d_i%d%s%s", c.stride, c.mt, c.nt, c.ipw, c.cm ? "_cm" : (c.pf4 ? "_p4" : (c.pf2 ? "_p2" : "")), c.w8 ? "_w8" : "");
-    else if (c.lds) snprintf(buf, n, "conv3x3s%d_lds_mt%d_nt%d%s%s", c.stride, c.mt, c.nt, c.pf4 ? "_p4" : (c.pf2 ? "_p2" : ""), c.w8 ? "_w8" : "");
-    else conv_cfg_name(c, buf, n);
-}
+static bool run_conv(const Op &op, const ConvCfg &c, const ConvArgs &a, int count, hipStream_t s) { return launch_conv(c, a, conv_weights(op), count, s); }
 
 // ---- per-layer tile autotuner ---------------------------------------------------
 // Every conv layer is timed at its real shape with each (MT, NT) tile the kernel
@@ -1574,21 +1551,19 @@ static TuneSwitches tune_switches()
 struct TuneCand { ConvCfg c; bool forced; };
 
 // Every candidate of one conv layer at one batch, in the order the tuner times them (IRMV_AUTOTUNE=0 takes the first that
-// runs; a cached choice is replayed only if it is one of them).  Launches nothing: a candidate is listed if the family offers
-// the tile for this layer and its LDS geometry fits; run_conv still has the last word.  lds_ok: the layer's kernel family;
-// want_fuse: the fused 1x1 epilogue, which needs an LDS-family tile that owns all 64 channels (nt = 4).
+// runs; a cached choice is replayed only if it is one of them).  Launches nothing: a candidate is listed if resolve_conv
+// finds a kernel for it on this layer, the one that run_conv launches.  lds_ok: the layer's kernel family; want_fuse: the
+// fused 1x1 epilogue, which needs an LDS-family tile that owns all 64 channels (nt = 4).
 static std::vector<TuneCand> tune_candidates(const Op &op, const ConvArgs &a, int count, bool want_fuse, bool lds_ok, const TuneSwitches &sw, int num_cus)
 {
     std::vector<TuneCand> v;
     // IRMV_FORCE_S2=lds|ct|deep (parity test): the stride-2 layers of the LDS family on ONE of their three bit-identical
     // implementations -- the LDS kernel, the direct kernel walking K chunk-major, its deep-prefetch form
     const bool s2 = sw.has_s2 && lds_ok && op.cfg.stride == 2;
+    const ConvWeights w = conv_weights(op);
     auto add = [&](const ConvCfg &c, bool forced = false) {
-        if (op.cout_pad % (16 * c.nt) != 0) return;
         if (s2 && !forced && sw.force_s2 != (c.lds ? "lds" : (c.deep ? "deep" : "ct"))) return;
-        if (c.wr ? !(op.w_lds[2] && conv_wres_bytes(a, c.stride, c.pp) > 0)
-                 : c.lds && !(op.w_lds[lds_index(c.nt)] && conv_lds_bytes(a, c.stride, c.mt, c.nt, nullptr, c.w8) > 0)) return;
-        v.push_back({c, forced});
+        if (resolve_conv(c, a, w, count)) v.push_back({c, forced});
     };
     const int ipw_max = lds_ok ? std::min(4, count) : 1;
     for (int mt = 1; mt <= 4; mt *= 2)
@@ -1601,26 +1576,26 @@ static std::vector<TuneCand> tune_candidates(const Op &op, const ConvArgs &a, in
             for (int ipw = 1; ipw <= ipw_max; ipw *= 2) add(tile_cfg(op.cfg, 1, nt, T_LDS | T_PF2, ipw));
     // ... and four steps ahead: layers of four or more chunks on maps small enough for four register sets (a lone frame's
     // 20 x 20 layers: every step of a workgroup in flight at once)
-    if (lds_ok && !want_fuse && !sw.no_pf4 && op.cin >= 128 && op.w_lds[0]) add(tile_cfg(op.cfg, 1, 1, T_LDS | T_PF4, 1), sw.force_pf4);
+    if (lds_ok && !want_fuse && !sw.no_pf4 && op.cin >= 128) add(tile_cfg(op.cfg, 1, 1, T_LDS | T_PF4, 1), sw.force_pf4);
     // LDS family, chunk-major over the workgroup's images: a chunk's weights staged once for all of them
     if (lds_ok && !sw.no_cm)
         for (int mt = 1; mt <= 2; mt *= 2)
             for (int ipw = 2; ipw <= std::min(mt == 1 ? 4 : 2, count); ipw *= 2)
-                if (!(want_fuse && mt == 1 && ipw == 2)) add(tile_cfg(op.cfg, mt, 4, T_LDS | (ipw == 2 ? T_CM2 : T_CM4), ipw), sw.force_cm);   // (no instantiation with the fused 1x1)
+                add(tile_cfg(op.cfg, mt, 4, T_LDS | (ipw == 2 ? T_CM2 : T_CM4), ipw), sw.force_cm);
     // LDS family, stride 2: one 8-wave workgroup per CU on a block twice as tall (mt = 2 fits LDS, weights staged for
     // twice the pixels)
     if (lds_ok && op.cfg.stride == 2 && !want_fuse && !sw.no_w8)
         for (int mt = 1; mt <= 2; mt *= 2)
             for (int ipw = 1; ipw <= ipw_max; ipw *= 2)
                 for (int cmv = 0; cmv < 2; cmv++)
-                    if (!cmv || (mt == 2 && ipw == 2) || (mt == 1 && ipw == 4)) add(tile_cfg(op.cfg, mt, 4, T_LDS | T_W8 | (cmv ? (ipw == 2 ? T_CM2 : T_CM4) : 0), ipw), sw.force_w8);
+                    add(tile_cfg(op.cfg, mt, 4, T_LDS | T_W8 | (cmv ? (ipw == 2 ? T_CM2 : T_CM4) : 0), ipw), sw.force_w8);
     // ... and with all of 128 output channels per workgroup (nt = 8, mt = 1): these layers are bound by what a CU can stage
     // from L2 (12 B/clk), and the stride-2 patch -- four input pixels per output pixel -- is then fetched once per 128
     // channels instead of once per 64; chunk-major over two images halves the weight staging on top
     if (lds_ok && op.cfg.stride == 2 && !want_fuse && !sw.no_w8 && !sw.no_nt8)
         for (int ipw = 1; ipw <= ipw_max; ipw *= 2)
             for (int cmv = 0; cmv < 2; cmv++)
-                if (!cmv || ipw == 2) add(tile_cfg(op.cfg, 1, 8, T_LDS | T_W8 | (cmv ? T_CM2 : 0), ipw), sw.force_nt8);
+                add(tile_cfg(op.cfg, 1, 8, T_LDS | T_W8 | (cmv ? T_CM2 : 0), ipw), sw.force_nt8);
     // LDS family, Cin = Cout = 64, stride 1: resident weights (one 8-wave workgroup per CU walks ipw images at its tile
     // position; lockstep, or as two ping-pong groups of four waves).  ipw: the smallest that lets the chip hold the
     // grid in one round, and half of it.
@@ -1646,16 +1621,16 @@ static std::vector<TuneCand> tune_candidates(const Op &op, const ConvArgs &a, in
         add(tile_cfg(op.cfg, 2, 4, T_PW, 1), sw.force_pw);
         // ... and its multi-block form: one workgroup runs a pixel tile against 2 / 4 output-channel blocks (input read once)
         for (int nbw = 2; nbw <= 4 && !sw.no_pwn; nbw *= 2)
-            if (conv_pw_lds_bytes(a, nbw)) add(tile_cfg(op.cfg, 2, 4, T_PW, nbw), sw.force_pwn);   // (forced: the widest form offered)
+            add(tile_cfg(op.cfg, 2, 4, T_PW, nbw), sw.force_pwn);   // (forced: the widest form offered)
     }
     // A layer of the LDS family may also run on the direct kernel walking K in that family's order on its weights (ct):
     // bit-identical, so the family rule still holds.  Offered where the direct kernel has a chance: stride 2.
-    if (lds_ok && !want_fuse && op.w_lds[0] && op.cfg.stride == 2 && !op.cfg.cin16)
+    if (lds_ok && !want_fuse && op.cfg.stride == 2 && !op.cfg.cin16)
         for (int mt = 1; mt <= 4; mt *= 2)
             for (int nt = 1; nt <= 4; nt *= 2) add(tile_cfg(op.cfg, mt, nt, T_CT, 1));
     // single-frame steps: the latency variants of the direct kernel (deep prefetch ring), same rule.
     // Batched steps: offered to the 1x1 layers only (4..16 k-steps: the ring then holds the wave's whole K range).
-    if ((count == 1 || op.cfg.ks == 1) && !want_fuse && !sw.no_deep && !op.cfg.cin16 && !op.cfg.out_f32 && op.cfg.act == 1 && (!lds_ok || op.w_lds[0])) {
+    if ((count == 1 || op.cfg.ks == 1) && !want_fuse && !sw.no_deep && !op.cfg.cin16 && !op.cfg.out_f32 && op.cfg.act == 1) {
         const int tiles[4][2] = {{1, 1}, {2, 1}, {1, 2}, {1, 4}};
         for (auto &t : tiles) add(tile_cfg(op.cfg, t[0], t[1], T_DEEP | (lds_ok ? T_CT : 0), 1));
     }
@@ -1668,12 +1643,13 @@ struct ConvView { ConvArgs a; bool want_fuse, lds_ok; };
 static ConvView conv_view(const irmv_engine *e, const Op &op, int first, int count)
 {
     ConvView v;
+    const ConvWeights w = conv_weights(op);
     const bool fuse_k16 = op.fuse_next >= 0 && op.cfg.cin16;   // the keypoint final in the direct kernel's epilogue: any pixel tile (nt = 1 is the layer's only one)
     v.want_fuse = op.fuse_next >= 0 && !fuse_k16;
     fill_conv_args(e, op, first, count, v.a, v.want_fuse || fuse_k16);
     if (v.want_fuse) {   // the fused epilogue needs an LDS-family tile that owns all 64 channels (nt = 4)
         bool f_ok = false;
-        for (int mt = 1; mt <= 4 && !f_ok; mt *= 2) f_ok = op.w_lds[2] && conv_lds_bytes(v.a, op.cfg.stride, mt, 4, nullptr) > 0;
+        for (int mt = 1; mt <= 4 && !f_ok; mt *= 2) f_ok = conv_lds_fits(v.a, w, op.cfg.stride, mt, 4);
         if (!f_ok) {
             v.want_fuse = false;
             fill_conv_args(e, op, first, count, v.a, false);
@@ -1684,7 +1660,7 @@ static ConvView conv_view(const irmv_engine *e, const Op &op, int first, int cou
     v.lds_ok = false;
     if (op.cfg.ks == 3 && op.cfg.act == 1 && !op.cfg.out_f32)
         for (int mt = 1; mt <= 4 && !v.lds_ok; mt *= 2)
-            for (int nt = 1; nt <= 4 && !v.lds_ok; nt *= 2) v.lds_ok = op.w_lds[lds_index(nt)] && conv_lds_bytes(v.a, op.cfg.stride, mt, nt, nullptr) > 0;
+            for (int nt = 1; nt <= 4 && !v.lds_ok; nt *= 2) v.lds_ok = conv_lds_fits(v.a, w, op.cfg.stride, mt, nt);
     return v;
 }
 
@@ -1749,15 +1725,15 @@ static int autotune_convs(irmv_engine *e)
                 }
                 if (sw.verbose) {
                     char nm[48];
-                    cfg_name(c, nm, sizeof nm);
+                    conv_cfg_name(c, nm, sizeof nm);
                     fprintf(stderr, "[autotune] %-22s count=%-2d %-28s %8.2f us\n", op.layer.c_str(), count, nm, ms / 4 * 1e3);
                 }
                 if (ms < best) { best = ms; best_cfg = c; }
             }
             if (!forced && !sw.untuned) { std::lock_guard<std::mutex> lk(g_tune_mu); g_tune_cache[key] = tune_entry(best_cfg); }
-            if (pass == 0) { op.cfg = best_cfg; cfg_name(op.cfg, op.kname, sizeof op.kname); }
-            else { op.cfg_one = best_cfg; cfg_name(op.cfg_one, op.kname_one, sizeof op.kname_one); }
-            if (counts[0] == 1) { op.cfg_one = op.cfg; cfg_name(op.cfg_one, op.kname_one, sizeof op.kname_one); }
+            if (pass == 0) { op.cfg = best_cfg; conv_cfg_name(op.cfg, op.kname, sizeof op.kname); }
+            else { op.cfg_one = best_cfg; conv_cfg_name(op.cfg_one, op.kname_one, sizeof op.kname_one); }
+            if (counts[0] == 1) { op.cfg_one = op.cfg; conv_cfg_name(op.cfg_one, op.kname_one, sizeof op.kname_one); }
         }
     }
     (void)hipEventDestroy(ea);
@@ -1805,16 +1781,15 @@ static void scan_args_for(const irmv_engine *e, const Op &op, const PostArgs &pa
 static bool launch_head_group(const irmv_engine *e, const irmv_engine::HeadGroup &g, int first, const PostArgs *pa, unsigned scan, hipStream_t s)
 {
     ConvArgs a[kMultiMax];
-    const half_t *wl[kMultiMax];
+    ConvWeights w[kMultiMax];
     const int n = (int)g.members.size();
     for (int k = 0; k < n; k++) {
         const Op &op = e->ops[g.members[k]];
         fill_conv_args(e, op, first, 1, a[k], true);
         if (scan >> k & 1u) scan_args_for(e, op, *pa, a[k]);
-        wl[k] = op.w_lds[g.nt == 4 ? 2 : (g.nt == 2 ? 1 : 0)];
-        if (g.family == 0 && !wl[k]) return false;
+        w[k] = conv_weights(op);
     }
-    return g.family == 0 ? launch_conv_lds_multi(g.nt, a, wl, n, 1, s) : launch_conv_direct_multi(g.cfg, a, n, s);
+    return g.family == 0 ? launch_conv_lds_multi(g.nt, a, w, n, 1, s) : launch_conv_direct_multi(g.cfg, a, n, s);
 }
 
 static int build_head_groups(irmv_engine *e)
@@ -1907,7 +1882,7 @@ static int build_head_groups(irmv_engine *e)
     if (kpt) {
         const size_t before = e->head_groups.size();
         try_group(g3, 1, {1}, "head_kpt1");
-        bool k16 = false;   // (finals on the 16x16x16 MFMA are fused into the convs in front of them, or run launch_conv_k16: the grouped direct kernel would give other bits)
+        bool k16 = false;   // (finals on the 16x16x16 MFMA are fused into the convs in front of them, or run their own kernel: the grouped direct kernel would give other bits)
         for (int i : g4) k16 = k16 || i < 0 || e->ops[i].w_k16 != nullptr;
         if (e->head_groups.size() > before && !k16) try_group(g4, 1, {1}, "head_kpt2");
     }
@@ -2015,7 +1990,7 @@ static void fill_conv_args(const irmv_engine *e, const Op &op, int first, int co
         a.out2_ld = t2.C;
         a.n2 = o2.cout_pad / 16;
     }
-    if (op.w_k16) a.w2 = op.w_k16;   // a Cin = 16 final as its own launch (launch_conv_k16)
+    if (op.w_k16) a.w2 = op.w_k16;   // a Cin = 16 final as its own launch (k_conv.hip conv1x1_k16_f32_kernel)
 }
 
 static LightArgs light_args(const irmv_engine *e, int first)
@@ -2808,7 +2783,7 @@ extern "C" int irmv_engine_conv_candidates(irmv_engine *e, int op, int tune_coun
     for (size_t i = 0; i < cands.size() && out && (int)i < cap; i++) {
         irmv_conv_cand &r = out[i];
         memset(&r, 0, sizeof r);
-        cfg_name(cands[i].c, r.name, sizeof r.name);
+        conv_cfg_name(cands[i].c, r.name, sizeof r.name);
         const TuneEntry t = tune_entry(cands[i].c);
         r.mt = t.mt; r.nt = t.nt; r.flags = t.flags; r.ipw = t.ipw;
         r.forced = cands[i].forced;

@@ -334,25 +334,24 @@ struct ConvCfg {
     bool wr;     // LDS family, Cin = Cout = 64, stride 1: the layer's weights stay resident in the LDS of one 8-wave workgroup that walks ipw images
     bool pp;     // ... as two ping-pong groups of four waves (one in its MFMA phase while the other stores, stages and loads)
 };
-// returns false if no instantiation exists for cfg
-bool launch_conv(const ConvCfg &cfg, const ConvArgs &a, hipStream_t s);
+// A conv op's weight packings: the direct family's fragments, the LDS family's per-nt packings (nt = 1 / 2 / 4 / 8, nullptr
+// where the layer has none: [n-block][chunk 32][tap][tile][lane][8]), and a Cin = 16 final's weights in the A layout of the
+// 16x16x16 MFMA (nullptr: not such a final)
+struct ConvWeights { const half_t *w_packed; const half_t *w_lds[4]; const half_t *w_k16; };
+// The one answer to "which kernel runs cfg on this layer" (k_conv.hip's variant tables): false = no such variant.  Launches
+// nothing; out (optional) receives the launcher, its weights, geometry and dynamic LDS (unspecified on false).
+struct ConvLaunch;
+bool resolve_conv(const ConvCfg &cfg, const ConvArgs &a, const ConvWeights &w, int batch, ConvLaunch *out = nullptr);
+bool launch_conv(const ConvCfg &cfg, const ConvArgs &a, const ConvWeights &w, int batch, hipStream_t s);   // false: no such variant
 const char *conv_cfg_name(const ConvCfg &cfg, char *buf, int n);
-bool conv_pw_eligible(const ConvCfg &cfg, const ConvArgs &a);
+bool conv_pw_eligible(const ConvCfg &cfg, const ConvArgs &a);   // the 1x1 layers the pointwise family serves
+bool conv_lds_fits(const ConvArgs &a, const ConvWeights &w, int stride, int mt, int nt);   // LDS family: packing present, (mt, nt) tile fits
+int conv_wres_tiles(const ConvArgs &a, int stride, bool pp);    // weights-resident variant: tile positions per image (0 = not eligible)
 // n independent layers (n <= kMultiMax) as ONE launch with a common tile: LDS family, stride 1, mt = 1, nt in {1, 2, 4}
 // (fused 1x1s allowed at nt = 4, per member); direct family: the two shapes of the keypoint branch (3x3 Cin = 16 SiLU,
 // 1x1 fp32 bias-only; mt = nt = 1).  false: some member has no such tile.
-bool launch_conv_lds_multi(int nt, const ConvArgs *a, const half_t *const *wl, int n, int batch, hipStream_t s);
+bool launch_conv_lds_multi(int nt, const ConvArgs *a, const ConvWeights *w, int n, int batch, hipStream_t s);
 bool launch_conv_direct_multi(const ConvCfg &cfg, const ConvArgs *a, int n, hipStream_t s);
-bool launch_conv_k16(const ConvArgs &a, hipStream_t s);   // 1x1, Cin = 16 -> <= 16 channels, bias only, fp32 out: a.w2 = weights in the 16x16x16 MFMA's A layout
-bool launch_conv_pw(const ConvCfg &cfg, const ConvArgs &a, hipStream_t s);   // cfg.ipw = NBW: 64-channel output blocks per workgroup (1: the single-block kernel)
-size_t conv_pw_lds_bytes(const ConvArgs &a, int nbw);                        // NBW = 2 / 4: LDS of the multi-block form, 0 = not offered
-// LDS-staged 3x3 family (k_conv.hip): wl = weights packed [n-block][chunk 32][tap][tile][lane][8] for this nt
-size_t conv_lds_bytes(const ConvArgs &a, int stride, int mt, int nt, int *patch_rows_max, bool w8 = false);
-// weights-resident variant: bytes of LDS (0 = not eligible), tile positions per image and workgroup column, launcher
-size_t conv_wres_bytes(const ConvArgs &a, int stride, bool pp);
-int conv_wres_tiles(const ConvArgs &a, int stride, bool pp);
-bool launch_conv_wres(int ipw, const ConvArgs &a, const half_t *wl, int batch, hipStream_t s, bool pp);
-bool launch_conv_lds(int stride, int mt, int nt, int ipw, const ConvArgs &a, const half_t *wl, int batch, hipStream_t s, int pf2 = 0, int cm = 0, bool w8 = false);   // a.n2 > 0: fused 1x1 (needs stride 1, nt 4, cout 64); pf2: staging two steps ahead (mt = 1)
 
 // SPPF pooling chain: slice 0 (C ch) of [B][H][W][4C] -> slices 1..3 (5x5, 9x9, 13x13 max)
 void launch_sppf_pool(half_t *buf, int batch, int H, int W, int C, hipStream_t s);

@@ -15,7 +15,10 @@
 // into the operand addressing (two K segments, one at half resolution).
 #include "irmv_common.hpp"
 
+#include <algorithm>
 #include <cstdio>
+#include <cstring>
+#include <iterator>
 #include <mutex>
 #include <type_traits>
 
@@ -279,77 +282,70 @@ __global__ __launch_bounds__(256) void conv_mfma_multi(DirectMultiArgs m)
     conv_mfma_body<KS, STRIDE, MT, NT, CIN16, ACT, OUT_F32>(m.a[k], id % gx, id / gx, gx, gy);
 }
 
+// Block scheme and tile grid of the LDS family for one layer and tile shape (lds_geom below); bytes: the dynamic LDS of a
+// launch of any family (0: the tile does not fit).
+struct LdsGeom { bool tile2d; int tiles_x, tiles_y, twc_log2, patch_bytes; size_t bytes; };
+
+// One launch as resolve_conv decided it: every launcher instance of the tables below takes this.
+using ConvLauncher = void (*)(const ConvLaunch &, hipStream_t);
+struct ConvLaunch {
+    ConvLauncher launch;
+    ConvArgs a;          // direct family: a.w = w; the keypoint finals: a.w2 = w
+    const half_t *w;     // the weight packing the kernel reads
+    int batch, ipw;      // LDS family: images, and images per workgroup
+    LdsGeom g;
+};
+
 template <int KS, int STRIDE, int MT, int NT, bool CIN16, int ACT, bool OUT_F32, bool CT = false, bool DEEP = false>
-static void launch_inst(const ConvArgs &a, hipStream_t s)
+static void launch_inst(const ConvLaunch &l, hipStream_t s)
 {
+    const ConvArgs &a = l.a;
     const int tiles = (a.M + 15) / 16;
     const int bx = (tiles + 4 * MT - 1) / (4 * MT);
     const int by = a.cout_pad / (16 * NT);
     hipLaunchKernelGGL((conv_mfma_kernel<KS, STRIDE, MT, NT, CIN16, ACT, OUT_F32, CT, DEEP>), dim3(bx, by), dim3(256), 0, s, a);
 }
 
-template <int KS, int STRIDE, bool CIN16, int ACT, bool OUT_F32>
-static bool launch_tile(int mt, int nt, const ConvArgs &a, hipStream_t s)
+// The direct kernel's variants: one row per layer shape, its (mt, nt) tiles indexed [log2 mt][log2 nt] (nullptr: none).
+// Key fields are ints so that a key compares bytewise.
+struct DirectKey { int ks, stride, cin16, act, out_f32, ct, deep; };
+struct DirectVariant { DirectKey key; ConvLauncher tile[3][3]; };
+
+template <int KS, int ST, bool C16, int ACT, bool F32, bool CT = false, bool DEEP = false>
+constexpr DirectVariant direct_variant()
 {
-#define IRMV_TILE(MT_, NT_)                                                   \
-    if (mt == MT_ && nt == NT_) {                                             \
-        launch_inst<KS, STRIDE, MT_, NT_, CIN16, ACT, OUT_F32>(a, s);         \
-        return true;                                                          \
+    DirectVariant v{{KS, ST, C16, ACT, F32, CT, DEEP}, {}};
+    v.tile[0][0] = launch_inst<KS, ST, 1, 1, C16, ACT, F32, CT, DEEP>;
+    v.tile[1][0] = launch_inst<KS, ST, 2, 1, C16, ACT, F32, CT, DEEP>;
+    v.tile[0][1] = launch_inst<KS, ST, 1, 2, C16, ACT, F32, CT, DEEP>;
+    v.tile[0][2] = launch_inst<KS, ST, 1, 4, C16, ACT, F32, CT, DEEP>;
+    if constexpr (!DEEP) {   // the latency variants (deep prefetch) have the four small tiles above only
+        v.tile[2][0] = launch_inst<KS, ST, 4, 1, C16, ACT, F32, CT, DEEP>;
+        v.tile[1][1] = launch_inst<KS, ST, 2, 2, C16, ACT, F32, CT, DEEP>;
+        v.tile[2][1] = launch_inst<KS, ST, 4, 2, C16, ACT, F32, CT, DEEP>;
+        v.tile[1][2] = launch_inst<KS, ST, 2, 4, C16, ACT, F32, CT, DEEP>;
+        v.tile[2][2] = launch_inst<KS, ST, 4, 4, C16, ACT, F32, CT, DEEP>;
     }
-    IRMV_TILE(1, 1) IRMV_TILE(2, 1) IRMV_TILE(4, 1)
-    IRMV_TILE(1, 2) IRMV_TILE(2, 2) IRMV_TILE(4, 2)
-    IRMV_TILE(1, 4) IRMV_TILE(2, 4) IRMV_TILE(4, 4)
-#undef IRMV_TILE
-    return false;
+    return v;
 }
 
-// latency variants (deep prefetch): small tiles only
-template <int KS, int STRIDE, int ACT, bool OUT_F32, bool CT>
-static bool launch_deep(int mt, int nt, const ConvArgs &a, hipStream_t s)
-{
-#define IRMV_DEEP(MT_, NT_)                                                            \
-    if (mt == MT_ && nt == NT_) {                                                      \
-        launch_inst<KS, STRIDE, MT_, NT_, false, ACT, OUT_F32, CT, true>(a, s);        \
-        return true;                                                                   \
-    }
-    IRMV_DEEP(1, 1) IRMV_DEEP(2, 1) IRMV_DEEP(1, 2) IRMV_DEEP(1, 4)
-#undef IRMV_DEEP
-    return false;
-}
-
-bool launch_conv(const ConvCfg &c, const ConvArgs &a, hipStream_t s)
-{
-    if (a.cout_pad % (16 * c.nt) != 0) return false;
-    if (c.deep) {
-        // a.w must be the packing that matches the K order: direct packing, or (chunk-major) the LDS family's nt = 1 packing
-        if (c.ks == 3 && c.stride == 1 && c.act == 1 && !c.out_f32 && !c.cin16) return c.ct ? launch_deep<3, 1, 1, false, true>(c.mt, c.nt, a, s) : launch_deep<3, 1, 1, false, false>(c.mt, c.nt, a, s);
-        if (c.ks == 3 && c.stride == 2 && c.act == 1 && !c.out_f32 && !c.cin16) return c.ct ? launch_deep<3, 2, 1, false, true>(c.mt, c.nt, a, s) : launch_deep<3, 2, 1, false, false>(c.mt, c.nt, a, s);
-        if (c.ks == 1 && c.stride == 1 && c.act == 1 && !c.out_f32 && !c.ct) return launch_deep<1, 1, 1, false, false>(c.mt, c.nt, a, s);
-        return false;
-    }
-    if (c.ct) {   // chunk-major order on the standard prefetch ring: stride-2 3x3 layers of the LDS family
-        if (!(c.ks == 3 && c.stride == 2 && c.act == 1 && !c.out_f32 && !c.cin16)) return false;
-#define IRMV_CT(MT_, NT_)                                                        \
-        if (c.mt == MT_ && c.nt == NT_) {                                        \
-            launch_inst<3, 2, MT_, NT_, false, 1, false, true, false>(a, s);     \
-            return true;                                                         \
-        }
-        IRMV_CT(1, 1) IRMV_CT(2, 1) IRMV_CT(4, 1) IRMV_CT(1, 2) IRMV_CT(2, 2) IRMV_CT(4, 2) IRMV_CT(1, 4) IRMV_CT(2, 4) IRMV_CT(4, 4)
-#undef IRMV_CT
-        return false;
-    }
-#define IRMV_CASE(KS_, ST_, C16_, ACT_, F32_)                                                             \
-    if (c.ks == KS_ && c.stride == ST_ && c.cin16 == C16_ && c.act == ACT_ && c.out_f32 == F32_)          \
-        return launch_tile<KS_, ST_, C16_, ACT_, F32_>(c.mt, c.nt, a, s);
-    IRMV_CASE(3, 1, false, 1, false)   // 3x3 stride 1, SiLU, fp16 out
-    IRMV_CASE(3, 1, true, 1, false)
-    IRMV_CASE(3, 2, false, 1, false)   // 3x3 stride 2
-    IRMV_CASE(3, 2, true, 1, false)
-    IRMV_CASE(1, 1, false, 1, false)   // 1x1 SiLU
-    IRMV_CASE(1, 1, false, 0, true)    // 1x1 head finals: bias only, fp32 out
-#undef IRMV_CASE
-    return false;
-}
+static constexpr DirectVariant k_direct[] = {
+    // direct_variant<ks, stride, cin16, act, out_f32, ct, deep>
+    direct_variant<3, 1, false, 1, false>(),                 // 3x3 stride 1, SiLU, fp16 out
+    direct_variant<3, 1, true, 1, false>(),
+    direct_variant<3, 2, false, 1, false>(),                 // 3x3 stride 2
+    direct_variant<3, 2, true, 1, false>(),
+    direct_variant<1, 1, false, 1, false>(),                 // 1x1 SiLU
+    direct_variant<1, 1, false, 0, true>(),                  // 1x1 head finals: bias only, fp32 out
+    // ct: chunk-major order on the standard prefetch ring, the LDS family's nt = 1 packing (its stride-2 3x3 layers)
+    direct_variant<3, 2, false, 1, false, true, false>(),
+    // deep: latency variants; a.w the packing that matches the K order (direct, or with ct the LDS family's nt = 1)
+    direct_variant<3, 1, false, 1, false, false, true>(),
+    direct_variant<3, 1, false, 1, false, true, true>(),
+    direct_variant<3, 2, false, 1, false, false, true>(),
+    direct_variant<3, 2, false, 1, false, true, true>(),
+    direct_variant<1, 1, false, 1, false, false, true>(),
+};
 
 // The keypoint branch's final 1x1 (16 -> nk <= 16, bias only, fp32 out) as its own launch: ONE v_mfma_f32_16x16x16_f16 per 16
 // pixels -- the instruction, operands and rounding of the fused form above (conv_mfma_body, K16_FUSE), so that the fused
@@ -369,16 +365,28 @@ __global__ __launch_bounds__(256) void conv1x1_k16_f32_kernel(ConvArgs a)
         (f32x4){c[0] * kActUnscale + b[0], c[1] * kActUnscale + b[1], c[2] * kActUnscale + b[2], c[3] * kActUnscale + b[3]};
 }
 
-bool launch_conv_k16(const ConvArgs &a, hipStream_t s)
+static void launch_k16(const ConvLaunch &l, hipStream_t s)
 {
-    if (a.Cin != 16 || a.cout_pad != 16 || !a.w2 || a.s1.C != 0 || a.s0.shift != 0) return false;
-    hipLaunchKernelGGL(conv1x1_k16_f32_kernel, dim3(((a.M + 15) / 16 + 3) / 4), dim3(256), 0, s, a);
-    return true;
+    hipLaunchKernelGGL(conv1x1_k16_f32_kernel, dim3(((l.a.M + 15) / 16 + 3) / 4), dim3(256), 0, s, l.a);
 }
+
+// the grouped direct kernel: the two shapes of the keypoint branch, mt = nt = 1
+template <int KS, int ST, bool C16, int ACT, bool F32>
+static void launch_direct_multi_inst(const DirectMultiArgs &m, int total, hipStream_t s)
+{
+    hipLaunchKernelGGL((conv_mfma_multi<KS, ST, 1, 1, C16, ACT, F32>), dim3(total), dim3(256), 0, s, m);
+}
+static constexpr struct { DirectKey key; void (*launch)(const DirectMultiArgs &, int, hipStream_t); } k_direct_multi[] = {
+    {{3, 1, true, 1, false, false, false}, launch_direct_multi_inst<3, 1, true, 1, false>},   // 3x3, Cin = 16, SiLU
+    {{1, 1, false, 0, true, false, false}, launch_direct_multi_inst<1, 1, false, 0, true>},   // 1x1 finals: bias only, fp32 out
+};
 
 bool launch_conv_direct_multi(const ConvCfg &c, const ConvArgs *a, int n, hipStream_t s)
 {
     if (n < 1 || n > kMultiMax || c.mt != 1 || c.nt != 1 || c.deep || c.ct || c.lds || c.pw) return false;
+    const DirectKey key{c.ks, c.stride, c.cin16, c.act, c.out_f32, 0, 0};
+    const auto *v = std::find_if(std::begin(k_direct_multi), std::end(k_direct_multi), [&](const auto &r) { return !memcmp(&r.key, &key, sizeof key); });
+    if (v == std::end(k_direct_multi)) return false;
     DirectMultiArgs m{};
     m.n = n;
     int total = 0;
@@ -391,22 +399,8 @@ bool launch_conv_direct_multi(const ConvCfg &c, const ConvArgs *a, int n, hipStr
         total += m.gx[k] * m.gy[k];
     }
     m.start[n] = total;
-    if (c.ks == 3 && c.stride == 1 && c.cin16 && c.act == 1 && !c.out_f32) {
-        hipLaunchKernelGGL((conv_mfma_multi<3, 1, 1, 1, true, 1, false>), dim3(total), dim3(256), 0, s, m);
-        return true;
-    }
-    if (c.ks == 1 && c.stride == 1 && !c.cin16 && c.act == 0 && c.out_f32) {
-        hipLaunchKernelGGL((conv_mfma_multi<1, 1, 1, 1, false, 0, true>), dim3(total), dim3(256), 0, s, m);
-        return true;
-    }
-    return false;
-}
-
-const char *conv_cfg_name(const ConvCfg &c, char *buf, int n)
-{
-    snprintf(buf, n, "conv%dx%ds%d_mt%d_nt%d%s%s%s%s", c.ks, c.ks, c.stride, c.mt, c.nt, c.cin16 ? "_c16" : "",
-             c.out_f32 ? "_f32" : "", c.deep ? "_deep" : "", c.ct ? "_ct" : "");
-    return buf;
+    v->launch(m, total, s);
+    return true;
 }
 
 // ---------------------------------------------------------------------------
@@ -721,77 +715,80 @@ __global__ __launch_bounds__(512) void conv1x1_pwn_kernel(ConvArgs a, int wg_per
     if (ub < u1) run_tile(std::integral_constant<int, 1>{}, std::false_type{}, ub);
 }
 
-// eligible: 1x1, SiLU, fp16 out, pair-packed, 64 | cout, K a multiple of 32 with 4..16 k-steps, first segment a multiple of 32
+// eligible: 1x1, SiLU, fp16 out, pair-packed, 64 | cout, K a multiple of 32, first segment a multiple of 32 (and a k-step
+// count k_pw below lists)
 bool conv_pw_eligible(const ConvCfg &c, const ConvArgs &a)
 {
     return c.ks == 1 && c.stride == 1 && c.act == 1 && !c.out_f32 && !c.cin16 && a.pair && a.cout_pad % 64 == 0 && a.Cin % 32 == 0 && a.s0.C % 32 == 0 &&
-           (a.ksteps == 4 || a.ksteps == 6 || a.ksteps == 8 || a.ksteps == 12 || a.ksteps == 16) && a.res == nullptr && a.n2 == 0;
+           a.res == nullptr && a.n2 == 0;
 }
 
-// LDS of the multi-block form: NBW weight slabs + NBW x 64 biases; 0 = this (KS, NBW) is not offered
-size_t conv_pw_lds_bytes(const ConvArgs &a, int nbw)
+template <int KS>
+static void launch_pw_inst(const ConvLaunch &l, hipStream_t s)
 {
-    if (!(nbw == 2 || nbw == 4) || a.cout_pad % (64 * nbw) != 0) return 0;
-    const int ks = a.ksteps;
-    if (!(ks == 4 || ks == 6 || ks == 8 || ks == 12 || ks == 16) || nbw * ks > 32) return 0;   // <= 128 KiB of weights, <= 16 staging pieces per thread
-    return (size_t)nbw * 4 * ks * 1024 + (size_t)nbw * 64 * 4;
-}
-
-bool launch_conv_pw(const ConvCfg &c, const ConvArgs &a, hipStream_t s)
-{
-    if (!conv_pw_eligible(c, a)) return false;
+    static unsigned long long attr_done = 0;
+    once_per_device(attr_done, [] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_pw_kernel<KS>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    });
+    const ConvArgs &a = l.a;
     const int tiles_total = (a.M + 31) / 32, nblocks = a.cout_pad / 64;
-    if (c.ipw > 1) {   // several output-channel blocks per workgroup (c.ipw = NBW): the input is read nblocks / NBW times
-        const int nbw = c.ipw;
-        const size_t lds = conv_pw_lds_bytes(a, nbw);
-        if (!lds) return false;
-        const int groups = nblocks / nbw;
-        const int units = (a.M + 15) / 16;
-#define IRMV_PWN(KS_, NBW_)                                                                                          \
-        if (a.ksteps == KS_ && nbw == NBW_) {                                                                          \
-            static unsigned long long attr_done = 0;                                                                   \
-            /* per DEVICE (engines on several GPUs are created from concurrent threads): workgroups a CU holds (registers   \
-               and LDS) and the device's CU count size the grid to one round.  Element `dev` is written once, inside the    \
-               critical section of once_per_device, before any launch on that device leaves it. */                        \
-            static int per_cu[64], cus[64];                                                                            \
-            int dev = 0;                                                                                               \
-            (void)hipGetDevice(&dev);                                                                                  \
-            dev &= 63;                                                                                                 \
-            once_per_device(attr_done, [lds, dev] {                                                                    \
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_pwn_kernel<KS_, NBW_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                int nb = 0, nc = 0;                                                                                    \
-                per_cu[dev] = 1; cus[dev] = 256;                                                                       \
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(conv1x1_pwn_kernel<KS_, NBW_>), 512, lds) == hipSuccess && nb >= 1) per_cu[dev] = nb > 2 ? 2 : nb; \
-                if (hipDeviceGetAttribute(&nc, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && nc > 0) cus[dev] = nc; \
-            });                                                                                                        \
-            int wg = (cus[dev] * per_cu[dev] + groups - 1) / groups;     /* the chip in one round ... */               \
-            if (wg > (units + 7) / 8) wg = (units + 7) / 8;              /* ... but a 16-pixel unit per wave at least (20 x 20 maps: more  \
-                                                                            workgroups beat longer pipelines: 2 / 3 units per wave +7 / +25 %) */ \
-            if (wg < 1) wg = 1;                                                                                        \
-            hipLaunchKernelGGL((conv1x1_pwn_kernel<KS_, NBW_>), dim3(wg, groups), dim3(512), lds, s, a, wg);           \
-            return true;                                                                                               \
-        }
-        IRMV_PWN(4, 2) IRMV_PWN(6, 2) IRMV_PWN(8, 2) IRMV_PWN(12, 2) IRMV_PWN(16, 2) IRMV_PWN(4, 4) IRMV_PWN(6, 4) IRMV_PWN(8, 4)
-#undef IRMV_PWN
-        return false;
-    }
     // ~2 workgroups per CU in total, never more workgroups than there are 4-tile rounds
     int wg = (tiles_total + 3) / 4;
     const int cap = (512 + nblocks - 1) / nblocks;
     if (wg > cap) wg = cap;
     if (wg < 1) wg = 1;
-#define IRMV_PW(KS_)                                                                                               \
-    if (a.ksteps == KS_) {                                                                                          \
-        static unsigned long long attr_done = 0;                                                                    \
-        once_per_device(attr_done, [] {                                                                             \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_pw_kernel<KS_>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); \
-        });                                                                                                         \
-        hipLaunchKernelGGL((conv1x1_pw_kernel<KS_>), dim3(wg, nblocks), dim3(256), (size_t)4 * KS_ * 1024, s, a, tiles_total, wg);            \
-        return true;                                                                                                \
-    }
-    IRMV_PW(4) IRMV_PW(6) IRMV_PW(8) IRMV_PW(12) IRMV_PW(16)
-#undef IRMV_PW
-    return false;
+    hipLaunchKernelGGL((conv1x1_pw_kernel<KS>), dim3(wg, nblocks), dim3(256), l.g.bytes, s, a, tiles_total, wg);
+}
+
+// several output-channel blocks per workgroup (NBW): the input is read nblocks / NBW times
+template <int KS, int NBW>
+static void launch_pwn_inst(const ConvLaunch &l, hipStream_t s)
+{
+    static unsigned long long attr_done = 0;
+    // per DEVICE (engines on several GPUs are created from concurrent threads): workgroups a CU holds (registers and LDS)
+    // and the device's CU count size the grid to one round.  Element `dev` is written once, inside the critical section of
+    // once_per_device, before any launch on that device leaves it.
+    static int per_cu[64], cus[64];
+    const ConvArgs &a = l.a;
+    const size_t lds = l.g.bytes;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    dev &= 63;
+    once_per_device(attr_done, [lds, dev] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_pwn_kernel<KS, NBW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        int nb = 0, nc = 0;
+        per_cu[dev] = 1; cus[dev] = 256;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(conv1x1_pwn_kernel<KS, NBW>), 512, lds) == hipSuccess && nb >= 1) per_cu[dev] = nb > 2 ? 2 : nb;
+        if (hipDeviceGetAttribute(&nc, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && nc > 0) cus[dev] = nc;
+    });
+    const int groups = a.cout_pad / 64 / NBW;
+    const int units = (a.M + 15) / 16;
+    int wg = (cus[dev] * per_cu[dev] + groups - 1) / groups;     // the chip in one round ...
+    if (wg > (units + 7) / 8) wg = (units + 7) / 8;              // ... but a 16-pixel unit per wave at least (20 x 20 maps: more
+                                                                 // workgroups beat longer pipelines: 2 / 3 units per wave +7 / +25 %)
+    if (wg < 1) wg = 1;
+    hipLaunchKernelGGL((conv1x1_pwn_kernel<KS, NBW>), dim3(wg, groups), dim3(512), lds, s, a, wg);
+}
+
+// The pointwise family's variants: (k-steps, output-channel blocks per workgroup; 1 = the single-block kernel).  The
+// multi-block form keeps NBW x KS <= 32: <= 128 KiB of weights, <= 16 staging pieces per thread.
+static constexpr struct { int ksteps, nbw; ConvLauncher launch; } k_pw[] = {
+    {4, 1, launch_pw_inst<4>}, {6, 1, launch_pw_inst<6>}, {8, 1, launch_pw_inst<8>}, {12, 1, launch_pw_inst<12>}, {16, 1, launch_pw_inst<16>},
+    {4, 2, launch_pwn_inst<4, 2>}, {6, 2, launch_pwn_inst<6, 2>}, {8, 2, launch_pwn_inst<8, 2>}, {12, 2, launch_pwn_inst<12, 2>}, {16, 2, launch_pwn_inst<16, 2>},
+    {4, 4, launch_pwn_inst<4, 4>}, {6, 4, launch_pwn_inst<6, 4>}, {8, 4, launch_pwn_inst<8, 4>},
+};
+
+// cfg.ipw = NBW; g.bytes = the weight slabs (+ the multi-block form's NBW x 64 biases)
+static ConvLauncher pick_pw(const ConvCfg &c, const ConvArgs &a, LdsGeom &g)
+{
+    const int nbw = c.ipw > 1 ? c.ipw : 1;
+    if (!conv_pw_eligible(c, a) || a.cout_pad % (64 * nbw) != 0) return nullptr;
+    for (const auto &v : k_pw)
+        if (v.ksteps == a.ksteps && v.nbw == nbw) {
+            g.bytes = (size_t)nbw * 4 * a.ksteps * 1024 + (nbw > 1 ? (size_t)nbw * 64 * 4 : 0);
+            return v.launch;
+        }
+    return nullptr;
 }
 
 // 16-byte patch pieces a thread stages per chunk (registers are reserved for all of them): a stride-1 2-D block is at
@@ -815,7 +812,7 @@ __device__ __forceinline__ void conv3x3_lds_body(const ConvArgs &a, const half_t
     // PF: register staging of the (image, chunk) steps this many ahead of the MFMAs: 0 one step, 1 two, 2 four
     constexpr bool PF2 = PF != 0;
     constexpr int NPF = PF == 2 ? 4 : (PF == 1 ? 2 : 1);
-    constexpr int NTH = 64 * NWV;   // NWV waves stacked along pixels (4; 8 for the stride-2 layers' large block, see launch_conv_lds)
+    constexpr int NTH = 64 * NWV;   // NWV waves stacked along pixels (4; 8 for the stride-2 layers' large block, see k_lds)
     // PP (ping-pong, with WR): the workgroup's waves form TWO groups of NWP = NWV / 2 waves.  Each group owns a pixel tile
     // and a patch buffer of its own; they share the resident weights and run half a step apart -- while one group is in
     // its MFMA phase the other runs its epilogue, writes its next patch to LDS and issues the loads of the one after --
@@ -879,7 +876,7 @@ __device__ __forceinline__ void conv3x3_lds_body(const ConvArgs &a, const half_t
     }
     // WR > 0 (weights resident): the layer has exactly WR chunks; the weights of ALL of them are staged once per workgroup
     // and stay, the patch holds all WR chunk planes of an image, and a step is a whole image (one pair of barriers per
-    // image instead of one per chunk, no weight traffic after the first step) -- see launch_conv_wres.
+    // image instead of one per chunk, no weight traffic after the first step) -- see wres_geom.
     constexpr int NPL = WR > 0 ? WR : 1;               // chunk planes of the patch / chunk slabs of the weights in LDS
     static_assert(WR == 0 || (!PF2 && CM == 0), "resident weights: image-major steps, one step of staging lead");
     constexpr int NPB = PP ? 2 * NPL : NPL;            // patch planes in LDS (one set per ping-pong group)
@@ -1393,8 +1390,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IRMV_LDS_WA
 
 // Geometry of the LDS kernel for one layer and tile shape.  The 2-D block scheme is used when the
 // block tiles the image exactly (no masked lanes); otherwise the row-run scheme.  bytes == 0: not eligible.
-struct LdsGeom { bool tile2d; int tiles_x, tiles_y, twc_log2, patch_bytes; size_t bytes; };
-
 static LdsGeom lds_geom(const ConvArgs &a, int stride, int mt, int nt, int nwv = 4, int wr = 0, bool pp = false, int pf = 0)
 {   // nwv: the waves that share one patch (ping-pong: half the workgroup's)
     LdsGeom g{false, 0, 0, 0, 0, 0};
@@ -1428,31 +1423,34 @@ static LdsGeom lds_geom(const ConvArgs &a, int stride, int mt, int nt, int nwv =
     return g;
 }
 
-size_t conv_lds_bytes(const ConvArgs &a, int stride, int mt, int nt, int *patch_rows_max, bool w8)
+// the LDS family's packing for a tile of nt 16-channel tiles
+static const half_t *lds_weights(const ConvWeights &w, int nt) { return w.w_lds[nt == 8 ? 3 : (nt == 4 ? 2 : (nt == 2 ? 1 : 0))]; }
+
+bool conv_lds_fits(const ConvArgs &a, const ConvWeights &w, int stride, int mt, int nt)
 {
-    const LdsGeom g = lds_geom(a, stride, mt, nt, w8 ? 8 : 4);
-    if (patch_rows_max) *patch_rows_max = g.patch_bytes;
-    return g.bytes;
+    return lds_weights(w, nt) && lds_geom(a, stride, mt, nt).bytes > 0;
 }
 
 template <int STRIDE, int MT, int NT, bool TILE2D, int N2, int PF = 0, int CM = 0, int NWV = 4, int WR = 0, bool PP = false>
-static void launch_lds_inst(const ConvArgs &a, const half_t *wl, int batch, int ipw, const LdsGeom &g, hipStream_t s)
+static void launch_lds_inst(const ConvLaunch &l, hipStream_t s)
 {
     static unsigned long long attr_done = 0;   // per instantiation: devices whose dynamic-LDS limit has been raised
     once_per_device(attr_done, [] {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_lds_kernel<STRIDE, MT, NT, TILE2D, N2, PF, CM, NWV, WR, PP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
-    const int groups = (batch + ipw - 1) / ipw;
+    const LdsGeom &g = l.g;
+    const int groups = (l.batch + l.ipw - 1) / l.ipw;
     const int wg_tiles = PP ? (g.tiles_x * g.tiles_y + 1) / 2 : g.tiles_x * g.tiles_y;   // ping-pong: two tile positions per workgroup
-    const int nblocks = a.cout_pad / (16 * NT);
-    hipLaunchKernelGGL((conv3x3_lds_kernel<STRIDE, MT, NT, TILE2D, N2, PF, CM, NWV, WR, PP>), dim3(wg_tiles * groups * nblocks), dim3(64 * NWV), g.bytes, s, a,
-                       wl, g.tiles_x, g.tiles_y, g.twc_log2, g.patch_bytes, ipw, batch, nblocks, xcd_image_order() | (wres_stagger() << 1));
+    const int nblocks = l.a.cout_pad / (16 * NT);
+    hipLaunchKernelGGL((conv3x3_lds_kernel<STRIDE, MT, NT, TILE2D, N2, PF, CM, NWV, WR, PP>), dim3(wg_tiles * groups * nblocks), dim3(64 * NWV), g.bytes, s, l.a,
+                       l.w, g.tiles_x, g.tiles_y, g.twc_log2, g.patch_bytes, l.ipw, l.batch, nblocks, xcd_image_order() | (wres_stagger() << 1));
 }
 
 // Weights-resident variant: Cin = 64 -> 64 channels, stride 1.  ONE 8-wave workgroup per CU keeps the
 // layer's whole 72 KiB of weights in LDS and walks `ipw` images at its tile position (any ipw >= 1: the grid is sized so
 // that the chip holds it in one round); per image it stages the 64-channel patch once and runs all 18 k-steps between
-// one pair of barriers.  Same K order as the chunked kernel (chunk, tap) -> bit-identical.
+// one pair of barriers.  Same K order as the chunked kernel (chunk, tap) -> bit-identical.  pp: two ping-pong groups of
+// four waves, each on its own (4 mt rows x 16)-pixel block.
 static LdsGeom wres_geom(const ConvArgs &a, int stride, bool pp)
 {
     if (stride != 1 || a.Cin != 64 || a.cout_pad != 64 || !a.pair || (a.n2 > 0 && a.res) || !(a.n2 == 0 || a.n2 == 1 || a.n2 == 4)) return LdsGeom{false, 0, 0, 0, 0, 0};
@@ -1460,7 +1458,6 @@ static LdsGeom wres_geom(const ConvArgs &a, int stride, bool pp)
     if (pp && !g.tile2d) g.bytes = 0;   // ping-pong groups: 2-D blocks only
     return g;
 }
-size_t conv_wres_bytes(const ConvArgs &a, int stride, bool pp) { return wres_geom(a, stride, pp).bytes; }
 int conv_wres_tiles(const ConvArgs &a, int stride, bool pp)
 {
     const LdsGeom g = wres_geom(a, stride, pp);
@@ -1468,141 +1465,151 @@ int conv_wres_tiles(const ConvArgs &a, int stride, bool pp)
     return pp ? (g.tiles_x * g.tiles_y + 1) / 2 : g.tiles_x * g.tiles_y;
 }
 
-bool launch_conv_wres(int ipw, const ConvArgs &a, const half_t *wl, int batch, hipStream_t s, bool pp)
+// The LDS family's variants: one row per kernel instantiation key, its launchers for the row-run and the 2-D block
+// scheme as launch[tile2d] (nullptr: none).  Key fields are ints so that a key compares bytewise.
+//   n2: the fused trailing 1x1's 16-row tiles (the workgroup must own all 64 channels: stride 1, nt 4)
+//   pf: staging two (1) or four (2) steps ahead, the small pixel tiles (mt = 1), plain epilogue; four: nt = 1 on maps
+//       small enough for lds_pmax(.., pf = 2) pieces per thread
+//   cm: chunk-major order over the workgroup's cm = ipw images (16 cm mt nt accumulator registers)
+//   nwv = 8: stride-2 layers, ONE 8-wave workgroup per CU on a block of 128 mt pixels; nt = 8: 128
+//       output channels per workgroup, the patch staged once per 128 channels (mt = 1: 16 pixels x 128 channels per wave)
+//   wr: weights resident (wres_geom), pp: as two ping-pong groups
+struct LdsKey { int stride, mt, nt, n2, pf, cm, nwv, wr, pp; };
+struct LdsVariant { LdsKey key; ConvLauncher launch[2]; };
+
+template <int ST, int MT, int NT, int N2 = 0, int PF = 0, int CM = 0, int NWV = 4, int WR = 0, bool PP = false>
+constexpr LdsVariant lds_variant()
 {
-    if (ipw < 1) ipw = 1;
-    if (pp) {   // ping-pong: two groups of four waves, each on its own (4 mt rows x 16)-pixel block
-        const LdsGeom gp = wres_geom(a, 1, true);
-        if (!gp.bytes) return false;
-#define IRMV_WRES_PP(N2_)                                                                                   \
-        if (a.n2 == N2_) { launch_lds_inst<1, 2, 4, true, N2_, false, 0, 8, 2, true>(a, wl, batch, ipw, gp, s); return true; }
-        IRMV_WRES_PP(0) IRMV_WRES_PP(1) IRMV_WRES_PP(4)
-#undef IRMV_WRES_PP
-        return false;
-    }
-    const LdsGeom g = wres_geom(a, 1, false);
-    if (!g.bytes) return false;
-#define IRMV_WRES(N2_)                                                                                      \
-    if (a.n2 == N2_) {                                                                                      \
-        if (g.tile2d) launch_lds_inst<1, 2, 4, true, N2_, false, 0, 8, 2>(a, wl, batch, ipw, g, s);          \
-        else launch_lds_inst<1, 2, 4, false, N2_, false, 0, 8, 2>(a, wl, batch, ipw, g, s);                  \
-        return true;                                                                                        \
-    }
-    IRMV_WRES(0) IRMV_WRES(1) IRMV_WRES(4)
-#undef IRMV_WRES
-    return false;
+    LdsVariant v{{ST, MT, NT, N2, PF, CM, NWV, WR, PP}, {nullptr, launch_lds_inst<ST, MT, NT, true, N2, PF, CM, NWV, WR, PP>}};
+    if constexpr (!PP) v.launch[0] = launch_lds_inst<ST, MT, NT, false, N2, PF, CM, NWV, WR, PP>;   // ping-pong: 2-D blocks only
+    return v;
 }
 
-bool launch_conv_lds(int stride, int mt, int nt, int ipw, const ConvArgs &a, const half_t *wl, int batch, hipStream_t s, int pf2, int cm, bool w8)
+static constexpr LdsVariant k_lds[] = {
+    // lds_variant<stride, mt, nt, n2, pf, cm, nwv, wr, pp>
+    lds_variant<1, 1, 1>(), lds_variant<1, 2, 1>(), lds_variant<1, 4, 1>(),
+    lds_variant<1, 1, 2>(), lds_variant<1, 2, 2>(), lds_variant<1, 4, 2>(),
+    lds_variant<1, 1, 4>(), lds_variant<1, 2, 4>(), lds_variant<1, 4, 4>(),
+    lds_variant<2, 1, 1>(), lds_variant<2, 2, 1>(), lds_variant<2, 4, 1>(),
+    lds_variant<2, 1, 2>(), lds_variant<2, 2, 2>(), lds_variant<2, 4, 2>(),
+    lds_variant<2, 1, 4>(), lds_variant<2, 2, 4>(), lds_variant<2, 4, 4>(),
+    // fused 1x1
+    lds_variant<1, 1, 4, 1>(), lds_variant<1, 2, 4, 1>(), lds_variant<1, 4, 4, 1>(),
+    lds_variant<1, 1, 4, 4>(), lds_variant<1, 2, 4, 4>(), lds_variant<1, 4, 4, 4>(),
+    // staging two / four steps ahead
+    lds_variant<1, 1, 1, 0, 1>(), lds_variant<1, 1, 2, 0, 1>(), lds_variant<1, 1, 4, 0, 1>(),
+    lds_variant<2, 1, 1, 0, 1>(), lds_variant<2, 1, 2, 0, 1>(), lds_variant<2, 1, 4, 0, 1>(),
+    lds_variant<1, 1, 1, 0, 2>(), lds_variant<2, 1, 1, 0, 2>(),
+    // chunk-major
+    lds_variant<1, 1, 4, 0, 0, 4>(), lds_variant<1, 1, 4, 0, 0, 2>(), lds_variant<1, 2, 4, 0, 0, 2>(),
+    lds_variant<2, 1, 4, 0, 0, 4>(), lds_variant<2, 1, 4, 0, 0, 2>(), lds_variant<2, 2, 4, 0, 0, 2>(),
+    lds_variant<1, 1, 4, 1, 0, 4>(), lds_variant<1, 2, 4, 1, 0, 2>(), lds_variant<1, 1, 4, 4, 0, 4>(), lds_variant<1, 2, 4, 4, 0, 2>(),
+    // 8-wave workgroups, stride 2
+    lds_variant<2, 2, 4, 0, 0, 0, 8>(), lds_variant<2, 2, 4, 0, 0, 2, 8>(), lds_variant<2, 1, 4, 0, 0, 0, 8>(), lds_variant<2, 1, 4, 0, 0, 4, 8>(),
+    lds_variant<2, 1, 8, 0, 0, 0, 8>(), lds_variant<2, 1, 8, 0, 0, 2, 8>(),
+    // weights resident: lockstep, ping-pong
+    lds_variant<1, 2, 4, 0, 0, 0, 8, 2>(), lds_variant<1, 2, 4, 1, 0, 0, 8, 2>(), lds_variant<1, 2, 4, 4, 0, 0, 8, 2>(),
+    lds_variant<1, 2, 4, 0, 0, 0, 8, 2, true>(), lds_variant<1, 2, 4, 1, 0, 0, 8, 2, true>(), lds_variant<1, 2, 4, 4, 0, 0, 8, 2, true>(),
+};
+
+static ConvLauncher pick_lds(const ConvCfg &c, const ConvArgs &a, int ipw, LdsGeom &g)
 {
-    if (ipw < 1) ipw = 1;
-    if (w8) {   // stride-2 layers: ONE 8-wave workgroup per CU on a block of 128 mt pixels -- see DESIGN section 4
-        if (stride != 2 || !(nt == 4 || nt == 8) || a.n2 > 0 || pf2 || (cm && cm != ipw)) return false;
-        const LdsGeom g8 = lds_geom(a, stride, mt, nt, 8);
-        if (!g8.bytes) return false;
-        if (nt == 8) {   // 128 output channels per workgroup: the patch is staged once per 128 channels (mt = 1: 16 pixels x 128 channels per wave)
-#define IRMV_LDS_W8N8(CM_)                                                                                  \
-            if (mt == 1 && cm == CM_) {                                                                     \
-                if (g8.tile2d) launch_lds_inst<2, 1, 8, true, 0, false, CM_, 8>(a, wl, batch, ipw, g8, s);  \
-                else launch_lds_inst<2, 1, 8, false, 0, false, CM_, 8>(a, wl, batch, ipw, g8, s);           \
-                return true;                                                                                \
-            }
-            IRMV_LDS_W8N8(0) IRMV_LDS_W8N8(2)
-#undef IRMV_LDS_W8N8
-            return false;
-        }
-#define IRMV_LDS_W8(MT_, CM_)                                                                            \
-        if (mt == MT_ && cm == CM_) {                                                                    \
-            if (g8.tile2d) launch_lds_inst<2, MT_, 4, true, 0, false, CM_, 8>(a, wl, batch, ipw, g8, s); \
-            else launch_lds_inst<2, MT_, 4, false, 0, false, CM_, 8>(a, wl, batch, ipw, g8, s);          \
-            return true;                                                                                 \
-        }
-        IRMV_LDS_W8(2, 0) IRMV_LDS_W8(2, 2) IRMV_LDS_W8(1, 0) IRMV_LDS_W8(1, 4)
-#undef IRMV_LDS_W8
-        return false;
-    }
-    const LdsGeom g = lds_geom(a, stride, mt, nt);
-    if (!g.bytes) return false;
-    if (cm) {   // chunk-major order over the workgroup's cm = ipw images (16 cm mt nt accumulator registers)
-        if (cm != ipw || pf2) return false;
-        if (a.n2 > 0 && (stride != 1 || nt != 4 || a.cout_pad != 64 || !a.pair || a.res)) return false;
-#define IRMV_LDS_CM(ST_, MT_, NT_, CM_, N2_)                                                               \
-        if (stride == ST_ && mt == MT_ && nt == NT_ && cm == CM_ && a.n2 == N2_) {                         \
-            if (g.tile2d) launch_lds_inst<ST_, MT_, NT_, true, N2_, false, CM_>(a, wl, batch, ipw, g, s);  \
-            else launch_lds_inst<ST_, MT_, NT_, false, N2_, false, CM_>(a, wl, batch, ipw, g, s);          \
-            return true;                                                                                   \
-        }
-        IRMV_LDS_CM(1, 1, 4, 4, 0) IRMV_LDS_CM(1, 1, 4, 2, 0) IRMV_LDS_CM(1, 2, 4, 2, 0)
-        IRMV_LDS_CM(2, 1, 4, 4, 0) IRMV_LDS_CM(2, 1, 4, 2, 0) IRMV_LDS_CM(2, 2, 4, 2, 0)
-        IRMV_LDS_CM(1, 1, 4, 4, 1) IRMV_LDS_CM(1, 2, 4, 2, 1) IRMV_LDS_CM(1, 1, 4, 4, 4) IRMV_LDS_CM(1, 2, 4, 2, 4)
-#undef IRMV_LDS_CM
-        return false;
-    }
-    if (pf2) {   // two- (1) or four- (2) steps-ahead staging: the small pixel tiles (MT = 1), plain epilogue
-        if (mt != 1 || a.n2 > 0) return false;
-        if (pf2 == 2) {   // four register sets: one 16-channel tile, maps small enough for lds_pmax(.., pf = 2) pieces per thread
-            const LdsGeom g4 = lds_geom(a, stride, 1, nt, 4, 0, false, 2);
-            if (nt != 1 || !g4.bytes) return false;
-            if (stride == 1) {
-                if (g4.tile2d) launch_lds_inst<1, 1, 1, true, 0, 2>(a, wl, batch, ipw, g4, s);
-                else launch_lds_inst<1, 1, 1, false, 0, 2>(a, wl, batch, ipw, g4, s);
-            } else {
-                if (g4.tile2d) launch_lds_inst<2, 1, 1, true, 0, 2>(a, wl, batch, ipw, g4, s);
-                else launch_lds_inst<2, 1, 1, false, 0, 2>(a, wl, batch, ipw, g4, s);
-            }
-            return true;
-        }
-#define IRMV_LDS_P(ST_, NT_)                                                                     \
-        if (stride == ST_ && nt == NT_) {                                                        \
-            if (g.tile2d) launch_lds_inst<ST_, 1, NT_, true, 0, 1>(a, wl, batch, ipw, g, s);  \
-            else launch_lds_inst<ST_, 1, NT_, false, 0, 1>(a, wl, batch, ipw, g, s);          \
-            return true;                                                                         \
-        }
-        IRMV_LDS_P(1, 1) IRMV_LDS_P(1, 2) IRMV_LDS_P(1, 4) IRMV_LDS_P(2, 1) IRMV_LDS_P(2, 2) IRMV_LDS_P(2, 4)
-#undef IRMV_LDS_P
-        return false;
-    }
-    if (a.n2 > 0) {   // fused trailing 1x1: the workgroup must own all 64 channels of every pixel
-        if (stride != 1 || nt != 4 || a.cout_pad != 64 || !a.pair || a.res) return false;
-#define IRMV_LDS_F(MT_, N2_)                                                                   \
-        if (mt == MT_ && a.n2 == N2_) {                                                        \
-            if (g.tile2d) launch_lds_inst<1, MT_, 4, true, N2_>(a, wl, batch, ipw, g, s);      \
-            else launch_lds_inst<1, MT_, 4, false, N2_>(a, wl, batch, ipw, g, s);              \
-            return true;                                                                       \
-        }
-        IRMV_LDS_F(1, 1) IRMV_LDS_F(2, 1) IRMV_LDS_F(4, 1) IRMV_LDS_F(1, 4) IRMV_LDS_F(2, 4) IRMV_LDS_F(4, 4)
-#undef IRMV_LDS_F
-        return false;
-    }
-#define IRMV_LDS(ST_, MT_, NT_)                                                                \
-    if (stride == ST_ && mt == MT_ && nt == NT_) {                                             \
-        if (g.tile2d) launch_lds_inst<ST_, MT_, NT_, true, 0>(a, wl, batch, ipw, g, s);                \
-        else launch_lds_inst<ST_, MT_, NT_, false, 0>(a, wl, batch, ipw, g, s);                        \
-        return true;                                                                           \
-    }
-    IRMV_LDS(1, 1, 1) IRMV_LDS(1, 2, 1) IRMV_LDS(1, 4, 1)
-    IRMV_LDS(1, 1, 2) IRMV_LDS(1, 2, 2) IRMV_LDS(1, 4, 2) IRMV_LDS(1, 1, 4) IRMV_LDS(1, 2, 4) IRMV_LDS(1, 4, 4)
-    IRMV_LDS(2, 1, 1) IRMV_LDS(2, 2, 1) IRMV_LDS(2, 4, 1)
-    IRMV_LDS(2, 1, 2) IRMV_LDS(2, 2, 2) IRMV_LDS(2, 4, 2) IRMV_LDS(2, 1, 4) IRMV_LDS(2, 2, 4) IRMV_LDS(2, 4, 4)
-#undef IRMV_LDS
-    return false;
+    const int pf = c.pf4 ? 2 : (c.pf2 ? 1 : 0), nwv = c.w8 || c.wr ? 8 : 4;
+    if (c.cm && c.cm != ipw) return nullptr;
+    if (a.n2 > 0 && (a.cout_pad != 64 || !a.pair || a.res)) return nullptr;   // the fused 1x1 reads all 64 channels of a pixel
+    g = c.wr ? wres_geom(a, c.stride, c.pp) : lds_geom(a, c.stride, c.mt, c.nt, nwv, 0, false, pf);
+    if (!g.bytes) return nullptr;
+    const LdsKey key{c.stride, c.mt, c.nt, a.n2, pf, c.cm, nwv, c.wr ? 2 : 0, c.pp};
+    for (const LdsVariant &v : k_lds)
+        if (!memcmp(&v.key, &key, sizeof key)) return v.launch[g.tile2d];
+    return nullptr;
 }
 
-bool launch_conv_lds_multi(int nt, const ConvArgs *a, const half_t *const *wl, int n, int batch, hipStream_t s)
+static ConvLauncher pick_direct(const ConvCfg &c)
+{
+    const int mi = c.mt == 1 ? 0 : (c.mt == 2 ? 1 : 2), ni = c.nt == 1 ? 0 : (c.nt == 2 ? 1 : 2);
+    if (c.mt != 1 << mi || c.nt != 1 << ni) return nullptr;
+    const DirectKey key{c.ks, c.stride, c.cin16, c.act, c.out_f32, c.ct, c.deep};
+    for (const DirectVariant &v : k_direct)
+        if (!memcmp(&v.key, &key, sizeof key)) return v.tile[mi][ni];
+    return nullptr;
+}
+
+// Family order: the keypoint finals' kernel, pointwise, LDS-staged (weights resident among them), the direct kernel in
+// the LDS family's K order (ct), the direct kernel.
+bool resolve_conv(const ConvCfg &c, const ConvArgs &a, const ConvWeights &w, int batch, ConvLaunch *out)
+{
+    if (a.cout_pad % (16 * c.nt) != 0) return false;
+    ConvLaunch local;
+    ConvLaunch &l = out ? *out : local;   // (the eager launch path resolves every launch: no second copy of the arguments)
+    l.launch = nullptr; l.a = a; l.w = w.w_packed; l.batch = batch; l.ipw = c.ipw < 1 ? 1 : c.ipw; l.g = LdsGeom{false, 0, 0, 0, 0, 0};
+    // A Cin = 16 final runs its one kernel whatever the tile says (the bits of its fused form), so every candidate of such a
+    // layer launches it under a direct tile's name.  (Follow-up: a family of its own, with one candidate.)
+    if (w.w_k16) {
+        if (a.Cin == 16 && a.cout_pad == 16 && a.s1.C == 0 && a.s0.shift == 0) l.launch = launch_k16;
+        l.w = l.a.w2 = w.w_k16;
+    } else if (c.pw) {
+        l.launch = pick_pw(c, a, l.g);
+    } else if (c.lds) {
+        l.w = lds_weights(w, c.nt);
+        if (l.w) l.launch = pick_lds(c, a, l.ipw, l.g);
+    } else if (!c.wr) {
+        if (c.ct) l.w = a.n2 > 0 ? nullptr : w.w_lds[0];   // ct: the LDS family's nt = 1 packing
+        if (l.w) l.launch = pick_direct(c);
+        l.a.w = l.w;
+    }
+    return l.launch != nullptr;
+}
+
+bool launch_conv(const ConvCfg &c, const ConvArgs &a, const ConvWeights &w, int batch, hipStream_t s)
+{
+    ConvLaunch l;
+    if (!resolve_conv(c, a, w, batch, &l)) return false;
+    l.launch(l, s);
+    return true;
+}
+
+const char *conv_cfg_name(const ConvCfg &c, char *buf, int n)
+{
+    if (c.pw) snprintf(buf, n, c.ipw > 1 ? "conv1x1s1_pw_n%d" : "conv1x1s1_pw", c.ipw);
+    else if (c.wr) snprintf(buf, n, "conv3x3s1_wres%s_i%d", c.pp ? "_pp" : "", c.ipw);
+    else if (c.lds && c.ipw > 1) snprintf(buf, n, "conv3x3s%d_lds_mt%d_nt%d_i%d%s%s", c.stride, c.mt, c.nt, c.ipw, c.cm ? "_cm" : (c.pf4 ? "_p4" : (c.pf2 ? "_p2" : "")), c.w8 ? "_w8" : "");
+    else if (c.lds) snprintf(buf, n, "conv3x3s%d_lds_mt%d_nt%d%s%s", c.stride, c.mt, c.nt, c.pf4 ? "_p4" : (c.pf2 ? "_p2" : ""), c.w8 ? "_w8" : "");
+    else snprintf(buf, n, "conv%dx%ds%d_mt%d_nt%d%s%s%s%s", c.ks, c.ks, c.stride, c.mt, c.nt, c.cin16 ? "_c16" : "",
+                  c.out_f32 ? "_f32" : "", c.deep ? "_deep" : "", c.ct ? "_ct" : "");
+    return buf;
+}
+
+template <int NT>
+static void launch_lds_multi_inst(const LdsMultiArgs &m, int total, size_t bytes, hipStream_t s)
+{
+    static unsigned long long attr_done = 0;
+    once_per_device(attr_done, [] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_lds_multi<1, 1, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    });
+    hipLaunchKernelGGL((conv3x3_lds_multi<1, 1, NT>), dim3(total), dim3(256), bytes, s, m);
+}
+static constexpr struct { int nt; void (*launch)(const LdsMultiArgs &, int, size_t, hipStream_t); } k_lds_multi[] = {
+    {1, launch_lds_multi_inst<1>}, {2, launch_lds_multi_inst<2>}, {4, launch_lds_multi_inst<4>},
+};
+
+bool launch_conv_lds_multi(int nt, const ConvArgs *a, const ConvWeights *w, int n, int batch, hipStream_t s)
 {   // (round 4: deeper staging -- two and four steps ahead -- was built for this launch and measured on the first-stage
     // group of a lone frame: 14.4 us one step ahead, 18.3 / 17.5 us two / four ahead at nt = 2.  The launch is 1.9 GFLOP on
     // 500 workgroups, not a chain of round trips; removed again.)
-    if (n < 1 || n > kMultiMax || !(nt == 1 || nt == 2 || nt == 4)) return false;
+    const auto *v = std::find_if(std::begin(k_lds_multi), std::end(k_lds_multi), [&](const auto &r) { return r.nt == nt; });
+    if (n < 1 || n > kMultiMax || v == std::end(k_lds_multi)) return false;
     LdsMultiArgs m{};
     m.n = n;
     int total = 0;
     size_t bytes = 0;
     for (int k = 0; k < n; k++) {
         const LdsGeom g = lds_geom(a[k], 1, 1, nt);
-        if (!g.bytes) return false;
+        const half_t *wl = lds_weights(w[k], nt);
+        if (!wl || !g.bytes) return false;
         if (a[k].n2 > 0 && (nt != 4 || a[k].cout_pad != 64 || !a[k].pair || a[k].res || !(a[k].n2 == 1 || a[k].n2 == 4))) return false;
         LdsMember &l = m.m[k];
-        l.a = a[k]; l.wl = wl[k];
+        l.a = a[k]; l.wl = wl;
         l.tiles_x = g.tiles_x; l.tiles_y = g.tiles_y; l.twc_log2 = g.twc_log2; l.patch_bytes = g.patch_bytes; l.batch = batch; l.tile2d = g.tile2d ? 1 : 0;
         l.gx = g.tiles_x * g.tiles_y * batch;       // one image per workgroup
         l.gy = a[k].cout_pad / (16 * nt);
@@ -1611,18 +1618,8 @@ bool launch_conv_lds_multi(int nt, const ConvArgs *a, const half_t *const *wl, i
         bytes = bytes > g.bytes ? bytes : g.bytes;
     }
     m.start[n] = total;
-#define IRMV_LDS_M(NT_)                                                                                                  \
-    if (nt == NT_) {                                                                                                      \
-        static unsigned long long attr_done = 0;                                                                          \
-        once_per_device(attr_done, [] {                                                                                   \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_lds_multi<1, 1, NT_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        });                                                                                                               \
-        hipLaunchKernelGGL((conv3x3_lds_multi<1, 1, NT_>), dim3(total), dim3(256), bytes, s, m);                          \
-        return true;                                                                                                      \
-    }
-    IRMV_LDS_M(1) IRMV_LDS_M(2) IRMV_LDS_M(4)
-#undef IRMV_LDS_M
-    return false;
+    v->launch(m, total, bytes, s);
+    return true;
 }
 
 // SPPF (SURVEY.md Appendix A "Blocks"): p1 = maxpool5(a), p2 = maxpool5(p1),

@@ -35,13 +35,17 @@ int main(int argc, char **argv)
     a.M = B * S * S; a.Cin = Cin; a.bias = d_b; a.out = d_out; a.out_ld = Cout; a.cout_pad = Cout; a.ksteps = 9 * Cin / 32; a.pair = 1;
     hipStream_t st; CK(hipStreamCreate(&st));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    irmv::ConvCfg cfg{};   // the LDS family, stride 1, SiLU, fp16 out
+    cfg.ks = 3; cfg.stride = 1; cfg.act = 1; cfg.lds = true; cfg.mt = mt; cfg.nt = nt; cfg.ipw = ipw;
+    irmv::ConvWeights w{};
+    w.w_lds[nt == 4 ? 2 : nt - 1] = d_w;
     for (int i = 0; i < 5; i++)
-        if (!irmv::launch_conv_lds(1, mt, nt, ipw, a, d_w, B, st, false)) { fprintf(stderr, "not eligible\n"); return 2; }
+        if (!irmv::launch_conv(cfg, a, w, B, st)) { fprintf(stderr, "not eligible\n"); return 2; }
     CK(hipStreamSynchronize(st));
     const int reps = 50;
     CK(hipEventRecord(e0, st));
     for (int i = 0; i < reps; i++) {
-        irmv::launch_conv_lds(1, mt, nt, ipw, a, d_w, B, st, false);
+        irmv::launch_conv(cfg, a, w, B, st);
     }
     CK(hipEventRecord(e1, st));
     CK(hipStreamSynchronize(st));

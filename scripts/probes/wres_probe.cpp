@@ -53,9 +53,13 @@ int main(int argc, char **argv)
         printf("S=%d B=%d %-28s %8.2f us  %7.1f TFLOP/s\n", S, B, name, us, fl / us * 1e-6);
         return 0;
     };
+    irmv::ConvCfg cfg{};   // the LDS family, stride 1, SiLU, fp16 out, nt = 4
+    cfg.ks = 3; cfg.stride = 1; cfg.act = 1; cfg.lds = true; cfg.mt = rmt; cfg.nt = nt; cfg.ipw = ripw; cfg.cm = rcm;
+    irmv::ConvWeights w{};
+    w.w_lds[2] = d_w;
     char nm[64];
     snprintf(nm, sizeof nm, "ref mt%d nt4 i%d cm%d", rmt, ripw, rcm);
-    if (time_it([&] { return irmv::launch_conv_lds(1, rmt, nt, ripw, a, d_w, B, st, false, rcm); }, nm)) return 1;
+    if (time_it([&] { return irmv::launch_conv(cfg, a, w, B, st); }, nm)) return 1;
     std::vector<irmv::half_t> h_ref(n_out), h_out(n_out);
     CK(hipMemcpy(h_ref.data(), d_ref, n_out * 2, hipMemcpyDeviceToHost));
     a.out = d_out;
@@ -67,7 +71,9 @@ int main(int argc, char **argv)
         for (int pp = 0; pp < 2; pp++) {
             CK(hipMemset(d_out, 0xff, n_out * 2));
             snprintf(nm, sizeof nm, "wres%s i%d", pp ? "_pp" : "", ipw);
-            if (time_it([&] { return irmv::launch_conv_wres(ipw, a, d_w, B, st, pp != 0); }, nm)) return 1;
+            irmv::ConvCfg wr = cfg;   // weights resident: mt 2, nt 4, ipw images per workgroup
+            wr.mt = 2; wr.cm = 0; wr.ipw = ipw; wr.wr = true; wr.pp = pp != 0;
+            if (time_it([&] { return irmv::launch_conv(wr, a, w, B, st); }, nm)) return 1;
             CK(hipMemcpy(h_out.data(), d_out, n_out * 2, hipMemcpyDeviceToHost));
             size_t bad = 0;
             for (size_t i = 0; i < n_out; i++) bad += memcmp(&h_ref[i], &h_out[i], 2) != 0;
