@@ -66,9 +66,11 @@ public:
   // `src_format` (IRMV_SRC_*): what get_src_image_buffer() takes -- the reference's RGB8 frame (IRMV_SRC_HWC8), or the camera's
   // raw 8-bit Bayer frame of src_image_bytes() = width * height bytes (IRMV_SRC_BAYER_*8), demosaiced on the GPU with the Q8
   // white-balance gains `bayer_gain_q8` (R, G, B; 256 = 1.0).  get_rotated_image() is a CV_8UC3 frame either way.
+  // `net_height` (-1 = square): the network input is net_size wide and net_height tall, e.g. 640 x 512 for the 1280 x 1024
+  // camera (include/irmv_hip.h, irmv_engine_cfg::net_height); net_input_size() returns what the engine runs.
   YoloEngine(const std::string & onnx_file_path, cv::Size src_image_size, bool enable_profiling = false, int device = -1,
              bool warm_up_now = true, int net_size = -1, int src_format = IRMV_SRC_HWC8,
-             std::array<uint16_t, 3> bayer_gain_q8 = {256, 256, 256})
+             std::array<uint16_t, 3> bayer_gain_q8 = {256, 256, 256}, int net_height = -1)
   : src_image_size_(src_image_size), enable_profiling_(enable_profiling)
   {
     irmv_engine_cfg cfg;
@@ -76,6 +78,7 @@ public:
     cfg.src_format = src_format;
     for (int i = 0; i < 3; i++) cfg.bayer_gain_q8[i] = bayer_gain_q8[static_cast<size_t>(i)];
     cfg.net_size = net_size > 0 ? net_size : default_net_size();
+    cfg.net_height = net_height > 0 ? net_height : 0;
     cfg.device = device >= 0 ? device : default_device();
     cfg.src_width = src_image_size.width;
     cfg.src_height = src_image_size.height;
@@ -91,6 +94,14 @@ public:
     rotated_ = cv::Mat(src_image_size.height, src_image_size.width, CV_8UC3);
     dets_.resize(static_cast<size_t>(irmv_engine_max_det(engine_)));
     if (warm_up_now) warm_up();
+  }
+
+  // width x height of the network input
+  cv::Size net_input_size() const
+  {
+    int w = 0, h = 0;
+    irmv_engine_net_dims(engine_, &w, &h);
+    return cv::Size(w, h);
   }
 
   void warm_up()

@@ -71,7 +71,7 @@ typedef struct irmv_engine_cfg {
     int32_t device;            /* HIP device ordinal */
     int32_t src_width;         /* camera frame, e.g. 1280 (cv::Size src_image_size) */
     int32_t src_height;        /* e.g. 1024 */
-    int32_t net_size;          /* 640 (src/yolo_engine.cpp:98-99,189) */
+    int32_t net_size;          /* network input width; also its height when net_height is 0: 640 (src/yolo_engine.cpp:98-99,189) */
     int32_t resize_mode;       /* IRMV_RESIZE_* */
     int32_t rotate180;         /* 1 = reference (nppiMirror both axes, :182-184) */
     int32_t swap_rb;           /* 0 = reference: producer deposits model channel order */
@@ -111,6 +111,17 @@ typedef struct irmv_engine_cfg {
     int32_t src_format;        /* IRMV_SRC_* (default IRMV_SRC_HWC8) */
     uint16_t bayer_gain_q8[3]; /* R, G, B white-balance gains of a Bayer engine, Q8 in [0, 1023]; 256 = identity (default) */
     uint16_t reserved1;
+    /* Appended after those.  irmv_engine_create also accepts struct_size = offsetof(irmv_engine_cfg, reserved2) (= the sizeof
+     * of the header before this field; bytes from net_height on are then not read) and uses net_height = 0.
+     * Rectangular network input: net_size is the width W, net_height the height H, both multiples of 32 in [64, 2048];
+     * 0 = square (H = net_size, default).  The input is [3][H][W]; the head has A = sum over s in {8, 16, 32} of
+     * (H / s)(W / s) anchors (640 x 512: 6720).  Geometry per axis, sw x sh the source frame:
+     *   IRMV_RESIZE_STRETCH:   scale_x = sw / W, scale_y = sh / H (1280 x 1024 -> 640 x 512: 2 : 1 on both axes, no distortion)
+     *   IRMV_RESIZE_LETTERBOX: r = min(W / sw, H / sh), nw = min(W, floor(sw r + 0.5)), nh = min(H, floor(sh r + 0.5)),
+     *                          px = (W - nw) / 2, py = (H - nh) / 2; the rest is grey padding (none for 1280 x 1024 -> 640 x 512)
+     * For W == H this is exactly the square arithmetic. */
+    int32_t net_height;
+    int32_t reserved2;
 } irmv_engine_cfg;
 
 /* One detection: YoloEngine::bbox (yolo_engine.hpp:19-26) in source-frame
@@ -243,18 +254,22 @@ int irmv_engine_set_extract_params(irmv_engine *e, int binary_threshold, float l
 int irmv_engine_point_source(const irmv_engine *e);
 
 /* ---- stage-wise read-backs used by the parity tests -------------------- */
-int irmv_engine_read_input(irmv_engine *e, int slot, float *chw);             /* [3][net][net], as the reference's input_buffer_ */
-int irmv_engine_read_head(irmv_engine *e, int slot, float *head);             /* [anchors][64+nc+nk] */
+int irmv_engine_read_input(irmv_engine *e, int slot, float *chw);             /* [3][net_h][net_w], as the reference's input_buffer_ */
+int irmv_engine_read_head(irmv_engine *e, int slot, float *head);             /* [A][64+nc+nk], A = irmv_engine_num_anchors(): levels
+                                                                                 s = 8, 16, 32 in turn, each (net_h/s) x (net_w/s) row-major */
 int irmv_engine_write_head(irmv_engine *e, int slot, const float *head);      /* inject a head tensor ... */
 int irmv_engine_run_post(irmv_engine *e, int first_slot, int count);          /* ... and run decode->NMS->PnP only */
 /* fault injection for the robustness test: overwrite every slot's candidate counter (the one piece of state a step leaves for
  * the next kernel of the same step) with `value`.  The next step must stay inside its buffers and reset the counter; the
  * step after it must be correct again.  IRMV_ERR_ARG for an engine that keeps no counters (IRMV_SPLIT_SCAN=0). */
 int irmv_engine_debug_poke_candidate_counts(irmv_engine *e, int value);
-int irmv_engine_read_tap(irmv_engine *e, int slot, const char *name, float *nhwc, int shape[3]);
+int irmv_engine_read_tap(irmv_engine *e, int slot, const char *name, float *nhwc, int shape[3]);   /* shape = {H, W, C}: a tensor of
+                                                                                 level s is (net_h/s) x (net_w/s) */
 int irmv_engine_read_raw(irmv_engine *e, int slot, irmv_raw_dets *out);
 int irmv_engine_num_anchors(const irmv_engine *e);
 int irmv_engine_head_channels(const irmv_engine *e);
+/* The network input of this engine: *width = net_size, *height = net_height (net_size for a square engine). */
+int irmv_engine_net_dims(const irmv_engine *e, int *width, int *height);
 
 /* ---- per-layer conv test hooks (tests/test_gpu_conv_candidates.py) ------
  * Every conv layer of the engine, every tile candidate its autotuner timed, run one at a time on a slot range. */
@@ -267,7 +282,7 @@ typedef struct irmv_conv_op {
     int32_t op;                 /* the engine's op index: the `op` argument of the calls below */
     char layer[32];             /* weight layer, as the blob names it */
     int32_t ks, stride, act, out_f32, cin, cout, cout_pad;
-    int32_t Hin, Win, Hout, Wout;
+    int32_t Hin, Win, Hout, Wout;   /* rows x columns at the conv's input and output: (net_h/s) x (net_w/s) at stride s */
     irmv_conv_seg s0, s1;       /* input = concat(s0, s1) along channels */
     irmv_conv_seg res;          /* residual added after the activation (C = cout); tensor "" = none */
     char out_tensor[32];        /* output channels [out_coff, out_coff + cout_pad) of this tensor */

@@ -45,6 +45,7 @@ class EngineCfg(C.Structure):
         ("armor_min_small_center_distance", C.c_double), ("armor_max_small_center_distance", C.c_double),
         ("armor_min_large_center_distance", C.c_double), ("armor_max_large_center_distance", C.c_double),
         ("src_format", C.c_int32), ("bayer_gain_q8", C.c_uint16 * 3), ("reserved1", C.c_uint16),
+        ("net_height", C.c_int32), ("reserved2", C.c_int32),   # net_height 0: square net_size x net_size input
     ]
 
 
@@ -141,6 +142,7 @@ SYMBOLS = [
     ("irmv_engine_read_raw", C.c_int, [_P, C.c_int, C.POINTER(RawDets)]),
     ("irmv_engine_num_anchors", C.c_int, [_P]),
     ("irmv_engine_head_channels", C.c_int, [_P]),
+    ("irmv_engine_net_dims", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("irmv_engine_conv_ops", C.c_int, [_P, C.POINTER(ConvOp), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_engine_conv_candidates", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(ConvCand), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_engine_run_conv_candidate", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]),

@@ -778,17 +778,17 @@ static void axis_taps(std::vector<AxisTap> &out, int dn_total, int sn, int dn, i
 // The fused front kernel (k_front.hip) stages each tile's source region in LDS as 4-byte pixels, read in groups of
 // 4 pixels = three aligned dwords: the width must be a multiple of 4 and the largest region must fit kFrontStageMax
 // bytes of LDS.  Same box arithmetic as the kernel.
-static bool front_fits(const std::vector<AxisTap> &tx, const std::vector<AxisTap> &ty, int net, int sw, int *tiles_x, int *tiles_y, int *stage_bytes)
+static bool front_fits(const std::vector<AxisTap> &tx, const std::vector<AxisTap> &ty, int sw, int *tiles_x, int *tiles_y, int *stage_bytes)
 {
-    const int W1 = net / 4;
+    const int W1 = (int)tx.size() / 4, H1 = (int)ty.size() / 4;
     *tiles_x = (W1 + kFrontTileX - 1) / kFrontTileX;
-    *tiles_y = (W1 + kFrontTileY - 1) / kFrontTileY;
+    *tiles_y = (H1 + kFrontTileY - 1) / kFrontTileY;
     *stage_bytes = front_min_stage_bytes();
     if (sw % 4 != 0) return false;   // 4-pixel groups = 12 source bytes read as three aligned dwords
     auto span = [&](const std::vector<AxisTap> &t, int g0, int n, int *lo, int *hi) {
         *lo = 0x7fffffff; *hi = -1;
         for (int i = g0; i < g0 + n; i++) {
-            if (i < 0 || i >= net || t[i].i0 < 0) continue;
+            if (i < 0 || i >= (int)t.size() || t[i].i0 < 0) continue;
             *lo = std::min({*lo, t[i].i0, t[i].i1});
             *hi = std::max({*hi, t[i].i0, t[i].i1});
         }
@@ -818,7 +818,7 @@ static void build_step_plans(irmv_engine *e);
 static int build_engine(irmv_engine *e)
 {
     const irmv_engine_cfg &c = e->cfg;
-    const int net = c.net_size, S = c.num_slots;
+    const int net_w = c.net_size, net_h = c.net_height > 0 ? c.net_height : c.net_size, S = c.num_slots;
     HIP_TRY(hipSetDevice(c.device));
     HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     // default: batched engines replay concurrent sub-batches of ~64 frames, two to four of them; a stream per slot
@@ -869,22 +869,23 @@ static int build_engine(irmv_engine *e)
     }
 
     // ---- preprocess geometry (parse_output inverse mapping) ----
-    int nw = net, nh = net, px = 0, py = 0;
+    // letterbox into net_w x net_h: r = min(W / sw, H / sh), the scaled frame rounded and centred (W == H: the square case)
+    int nw = net_w, nh = net_h, px = 0, py = 0;
     if (c.resize_mode == IRMV_RESIZE_LETTERBOX) {
-        const double r = std::min((double)net / c.src_width, (double)net / c.src_height);
-        nw = std::min(net, (int)std::floor(c.src_width * r + 0.5));
-        nh = std::min(net, (int)std::floor(c.src_height * r + 0.5));
-        px = (net - nw) / 2;
-        py = (net - nh) / 2;
+        const double r = std::min((double)net_w / c.src_width, (double)net_h / c.src_height);
+        nw = std::min(net_w, (int)std::floor(c.src_width * r + 0.5));
+        nh = std::min(net_h, (int)std::floor(c.src_height * r + 0.5));
+        px = (net_w - nw) / 2;
+        py = (net_h - nh) / 2;
     }
     std::vector<AxisTap> tx, ty;
-    axis_taps(tx, net, c.src_width, nw, px, c.rotate180 != 0);
-    axis_taps(ty, net, c.src_height, nh, py, c.rotate180 != 0);
-    TRY(dev_alloc(e, (void **)&e->tap_x, net * sizeof(AxisTap)));
-    TRY(dev_alloc(e, (void **)&e->tap_y, net * sizeof(AxisTap)));
-    HIP_TRY(hipMemcpy(e->tap_x, tx.data(), net * sizeof(AxisTap), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->tap_y, ty.data(), net * sizeof(AxisTap), hipMemcpyHostToDevice));
-    e->fused_front = front_fits(tx, ty, net, c.src_width, &e->front_tiles_x, &e->front_tiles_y, &e->front_stage_bytes);
+    axis_taps(tx, net_w, c.src_width, nw, px, c.rotate180 != 0);
+    axis_taps(ty, net_h, c.src_height, nh, py, c.rotate180 != 0);
+    TRY(dev_alloc(e, (void **)&e->tap_x, net_w * sizeof(AxisTap)));
+    TRY(dev_alloc(e, (void **)&e->tap_y, net_h * sizeof(AxisTap)));
+    HIP_TRY(hipMemcpy(e->tap_x, tx.data(), net_w * sizeof(AxisTap), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->tap_y, ty.data(), net_h * sizeof(AxisTap), hipMemcpyHostToDevice));
+    e->fused_front = front_fits(tx, ty, c.src_width, &e->front_tiles_x, &e->front_tiles_y, &e->front_stage_bytes);
     e->front_v[0] = px; e->front_v[1] = px + nw; e->front_v[2] = py; e->front_v[3] = py + nh;
     {   // columns at exactly 2 : 1 (1280 -> 640): the taps of column px + k are the aligned source pair (m, m + 1) with
         // m = m0 + step k even, both weights 1/2; step = 2, or -2 under rotate180 (the pair is then listed as (m + 1, m):
@@ -903,7 +904,7 @@ static int build_engine(irmv_engine *e)
         if (const char *f = getenv("IRMV_FRONT_TILE8")) if (f[0] == '0') tall = false;
         if (tall) {
             e->front_tile_y = kFrontTileYDirect;
-            e->front_tiles_y = (net / 4 + kFrontTileYDirect - 1) / kFrontTileYDirect;
+            e->front_tiles_y = (net_h / 4 + kFrontTileYDirect - 1) / kFrontTileYDirect;
             e->front_stage_bytes = front_min_stage_bytes(kFrontTileYDirect);
         }
         e->front_fx_i0 = fx ? m0 : 0;
@@ -913,29 +914,31 @@ static int build_engine(irmv_engine *e)
     if (e->fused_front && !front_prepare()) e->fused_front = false;
 
     // ---- graph ----
-    const int s2 = net / 2, s4 = net / 4, s8 = net / 8, s16 = net / 16, s32 = net / 32;
+    // level sizes: h<s> x w<s> = net_h / s x net_w / s
+    const int h2 = net_h / 2, h4 = net_h / 4, h8 = net_h / 8, h16 = net_h / 16, h32 = net_h / 32;
+    const int w2 = net_w / 2, w4 = net_w / 4, w8 = net_w / 8, w16 = net_w / 16, w32 = net_w / 32;
     int x0, a0, a1, a2, a3, a4, a5, a6, a7, a8, s9, a9, a12, a15, a16, a18, a19, a21;
-    TRY(new_tensor(e, "input", net, net, 4, false, &x0));
-    TRY(new_tensor(e, "0", s2, s2, 16, false, &a0));
-    TRY(new_tensor(e, "1", s4, s4, 32, false, &a1));
+    TRY(new_tensor(e, "input", net_h, net_w, 4, false, &x0));
+    TRY(new_tensor(e, "0", h2, w2, 16, false, &a0));
+    TRY(new_tensor(e, "1", h4, w4, 32, false, &a1));
     const bool shuffle = e->backbone == 1;   // ShuffleNetV2 stages: blocks 2..8, P3 / P4 / P5 = tensors "3" / "6" / "8"
-    if (shuffle) TRY(new_tensor(e, "2", s8, s8, 64, false, &a2));
-    else TRY(new_tensor(e, "2", s4, s4, 32, false, &a2));
-    TRY(new_tensor(e, "3", s8, s8, 64, false, &a3));
-    if (shuffle) TRY(new_tensor(e, "4", s16, s16, 128, false, &a4));
-    else TRY(new_tensor(e, "4", s8, s8, 64, false, &a4));
-    TRY(new_tensor(e, "5", s16, s16, 128, false, &a5));
-    TRY(new_tensor(e, "6", s16, s16, 128, false, &a6));
-    TRY(new_tensor(e, "7", s32, s32, 256, false, &a7));
-    TRY(new_tensor(e, "8", s32, s32, 256, false, &a8));
-    TRY(new_tensor(e, "9.cat", s32, s32, 512, false, &s9));
-    TRY(new_tensor(e, "9", s32, s32, 256, false, &a9));
-    TRY(new_tensor(e, "12", s16, s16, 128, false, &a12));
-    TRY(new_tensor(e, "15", s8, s8, 64, false, &a15));
-    TRY(new_tensor(e, "16", s16, s16, 64, false, &a16));
-    TRY(new_tensor(e, "18", s16, s16, 128, false, &a18));
-    TRY(new_tensor(e, "19", s32, s32, 128, false, &a19));
-    TRY(new_tensor(e, "21", s32, s32, 256, false, &a21));
+    if (shuffle) TRY(new_tensor(e, "2", h8, w8, 64, false, &a2));
+    else TRY(new_tensor(e, "2", h4, w4, 32, false, &a2));
+    TRY(new_tensor(e, "3", h8, w8, 64, false, &a3));
+    if (shuffle) TRY(new_tensor(e, "4", h16, w16, 128, false, &a4));
+    else TRY(new_tensor(e, "4", h8, w8, 64, false, &a4));
+    TRY(new_tensor(e, "5", h16, w16, 128, false, &a5));
+    TRY(new_tensor(e, "6", h16, w16, 128, false, &a6));
+    TRY(new_tensor(e, "7", h32, w32, 256, false, &a7));
+    TRY(new_tensor(e, "8", h32, w32, 256, false, &a8));
+    TRY(new_tensor(e, "9.cat", h32, w32, 512, false, &s9));
+    TRY(new_tensor(e, "9", h32, w32, 256, false, &a9));
+    TRY(new_tensor(e, "12", h16, w16, 128, false, &a12));
+    TRY(new_tensor(e, "15", h8, w8, 64, false, &a15));
+    TRY(new_tensor(e, "16", h16, w16, 64, false, &a16));
+    TRY(new_tensor(e, "18", h16, w16, 128, false, &a18));
+    TRY(new_tensor(e, "19", h32, w32, 128, false, &a19));
+    TRY(new_tensor(e, "21", h32, w32, 256, false, &a21));
 
     if (bayer) {   // raw slot -> src_dev: the first op of every step (not of run_post, not of a read-back's materialisation)
         Op op; op.kind = OP_DEMOSAIC; op.layer = "demosaic"; snprintf(op.kname, sizeof op.kname, "bayer_demosaic");
@@ -944,7 +947,7 @@ static int build_engine(irmv_engine *e)
     }
     const size_t conv0_op = e->ops.size() + 1;   // (OP_PRE, then OP_CONV0)
     { Op op; op.kind = OP_PRE; op.layer = "preprocess"; snprintf(op.kname, sizeof op.kname, "preprocess"); op.out_t = x0;
-      op.bytes = (double)e->frame_bytes + (double)net * net * 8; e->ops.push_back(op); }
+      op.bytes = (double)e->frame_bytes + (double)net_h * net_w * 8; e->ops.push_back(op); }
     {
         const LayerW *l = find_layer(e, "model.0.conv");
         if (!l || l->cin != 3 || l->cout != 16 || l->k != 3 || l->stride != 2)
@@ -967,18 +970,18 @@ static int build_engine(irmv_engine *e)
         HIP_TRY(hipMemcpy(e->conv0_b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
         Op op; op.kind = OP_CONV0; op.layer = "model.0.conv"; snprintf(op.kname, sizeof op.kname, "conv0_mfma");
         op.s0.t = x0; op.out_t = a0;
-        op.flops = 2.0 * s2 * s2 * 16 * 27;
-        op.bytes = (double)net * net * 8 + (double)s2 * s2 * 32 + 27 * 16 * 2;
+        op.flops = 2.0 * h2 * w2 * 16 * 27;
+        op.bytes = (double)net_h * net_w * 8 + (double)h2 * w2 * 32 + 27 * 16 * 2;
         e->ops.push_back(op);
     }
-    TRY(add_conv(e, "model.1.conv", SegRef{a0, 0, 16, 0}, SegRef{}, s2, s2, a1, 0));
+    TRY(add_conv(e, "model.1.conv", SegRef{a0, 0, 16, 0}, SegRef{}, h2, w2, a1, 0));
     {
         const Op &m1 = e->ops.back();
         if (!(m1.cfg.cin16 && m1.ksteps == 5 && m1.pair && m1.cout_pad == 32 && m1.out_coff == 0)) e->fused_front = false;
         if (e->fused_front) {
             Op op; op.kind = OP_FRONT; op.layer = "preprocess+model.0+model.1"; snprintf(op.kname, sizeof op.kname, "front_fused");
             op.flops = e->ops[conv0_op].flops + m1.flops;
-            op.bytes = (double)e->frame_bytes + (double)s4 * s4 * 32 * 2;
+            op.bytes = (double)e->frame_bytes + (double)h4 * w4 * 32 * 2;
             op.w_packed = m1.w_packed; op.bias = m1.bias; op.out_t = m1.out_t;
             for (Op &o : e->ops) o.fused_away = o.kind != OP_DEMOSAIC;   // preprocess, model.0.conv, model.1.conv
             e->lazy_tensors.insert("input"); e->lazy_tensors.insert("0");
@@ -987,16 +990,16 @@ static int build_engine(irmv_engine *e)
     }
     int p3 = a4, p4 = a6, p5 = a8;   // the tensors the neck reads
     if (shuffle) {
-        TRY(add_shuffle_down(e, "model.2", a1, 32, s4, s4, 64, a2));
-        TRY(add_shuffle_unit(e, "model.3", a2, 64, s8, s8, a3));
-        TRY(add_shuffle_down(e, "model.4", a3, 64, s8, s8, 128, a4));
-        TRY(add_shuffle_unit(e, "model.5", a4, 128, s16, s16, a5));
-        TRY(add_shuffle_unit(e, "model.6", a5, 128, s16, s16, a6));
-        TRY(add_shuffle_down(e, "model.7", a6, 128, s16, s16, 256, a7));
-        TRY(add_shuffle_unit(e, "model.8", a7, 256, s32, s32, a8));
+        TRY(add_shuffle_down(e, "model.2", a1, 32, h4, w4, 64, a2));
+        TRY(add_shuffle_unit(e, "model.3", a2, 64, h8, w8, a3));
+        TRY(add_shuffle_down(e, "model.4", a3, 64, h8, w8, 128, a4));
+        TRY(add_shuffle_unit(e, "model.5", a4, 128, h16, w16, a5));
+        TRY(add_shuffle_unit(e, "model.6", a5, 128, h16, w16, a6));
+        TRY(add_shuffle_down(e, "model.7", a6, 128, h16, w16, 256, a7));
+        TRY(add_shuffle_unit(e, "model.8", a7, 256, h32, w32, a8));
         p3 = a3;
     } else {
-    TRY(add_c2f(e, "model.2", SegRef{a1, 0, 32, 0}, SegRef{}, s4, s4, 32, 1, true, a2));
+    TRY(add_c2f(e, "model.2", SegRef{a1, 0, 32, 0}, SegRef{}, h4, w4, 32, 1, true, a2));
     {
         // model.2 as one kernel (k_c2f.hip) when its four layers have the shapes that kernel is written for
         const int n = (int)e->ops.size();
@@ -1010,36 +1013,36 @@ static int build_engine(irmv_engine *e)
         if (ok) {
             Op op; op.kind = OP_C2F2; op.layer = "model.2 (cv1+m.0+cv2)"; snprintf(op.kname, sizeof op.kname, "c2f2_fused");
             op.flops = c1.flops + m1.flops + m2.flops + c2.flops;
-            op.bytes = 2.0 * (double)s4 * s4 * 32 * 2;
+            op.bytes = 2.0 * (double)h4 * w4 * 32 * 2;
             for (int i = 0; i < 4; i++) { op.sub[i] = n - 4 + i; e->ops[n - 4 + i].fused_away = true; }
             op.s0 = c1.s0; op.out_t = c2.out_t;
             e->lazy_tensors.insert("model.2.cat"); e->lazy_tensors.insert("model.2.tmp");
             e->ops.push_back(op);
         }
     }
-    TRY(add_conv(e, "model.3.conv", SegRef{a2, 0, 32, 0}, SegRef{}, s4, s4, a3, 0));
-    TRY(add_c2f(e, "model.4", SegRef{a3, 0, 64, 0}, SegRef{}, s8, s8, 64, 2, true, a4));
-    TRY(add_conv(e, "model.5.conv", SegRef{a4, 0, 64, 0}, SegRef{}, s8, s8, a5, 0));
-    TRY(add_c2f(e, "model.6", SegRef{a5, 0, 128, 0}, SegRef{}, s16, s16, 128, 2, true, a6));
-    TRY(add_conv(e, "model.7.conv", SegRef{a6, 0, 128, 0}, SegRef{}, s16, s16, a7, 0));
-    TRY(add_c2f(e, "model.8", SegRef{a7, 0, 256, 0}, SegRef{}, s32, s32, 256, 1, true, a8));
+    TRY(add_conv(e, "model.3.conv", SegRef{a2, 0, 32, 0}, SegRef{}, h4, w4, a3, 0));
+    TRY(add_c2f(e, "model.4", SegRef{a3, 0, 64, 0}, SegRef{}, h8, w8, 64, 2, true, a4));
+    TRY(add_conv(e, "model.5.conv", SegRef{a4, 0, 64, 0}, SegRef{}, h8, w8, a5, 0));
+    TRY(add_c2f(e, "model.6", SegRef{a5, 0, 128, 0}, SegRef{}, h16, w16, 128, 2, true, a6));
+    TRY(add_conv(e, "model.7.conv", SegRef{a6, 0, 128, 0}, SegRef{}, h16, w16, a7, 0));
+    TRY(add_c2f(e, "model.8", SegRef{a7, 0, 256, 0}, SegRef{}, h32, w32, 256, 1, true, a8));
     }
-    TRY(add_conv(e, "model.9.cv1", SegRef{p5, 0, 256, 0}, SegRef{}, s32, s32, s9, 0));
+    TRY(add_conv(e, "model.9.cv1", SegRef{p5, 0, 256, 0}, SegRef{}, h32, w32, s9, 0));
     { Op op; op.kind = OP_POOL; op.layer = "model.9.m"; snprintf(op.kname, sizeof op.kname, "sppf_pool"); op.out_t = s9;
-      op.bytes = (double)s32 * s32 * 128 * 2 * 4; e->ops.push_back(op); }
-    TRY(add_conv(e, "model.9.cv2", SegRef{s9, 0, 512, 0}, SegRef{}, s32, s32, a9, 0));
-    TRY(add_c2f(e, "model.12", SegRef{a9, 0, 256, 1}, SegRef{p4, 0, 128, 0}, s16, s16, 128, 1, false, a12));
-    TRY(add_c2f(e, "model.15", SegRef{a12, 0, 128, 1}, SegRef{p3, 0, 64, 0}, s8, s8, 64, 1, false, a15));
-    TRY(add_conv(e, "model.16.conv", SegRef{a15, 0, 64, 0}, SegRef{}, s8, s8, a16, 0));
-    TRY(add_c2f(e, "model.18", SegRef{a16, 0, 64, 0}, SegRef{a12, 0, 128, 0}, s16, s16, 128, 1, false, a18));
-    TRY(add_conv(e, "model.19.conv", SegRef{a18, 0, 128, 0}, SegRef{}, s16, s16, a19, 0));
-    TRY(add_c2f(e, "model.21", SegRef{a19, 0, 128, 0}, SegRef{a9, 0, 256, 0}, s32, s32, 256, 1, false, a21));
+      op.bytes = (double)h32 * w32 * 128 * 2 * 4; e->ops.push_back(op); }
+    TRY(add_conv(e, "model.9.cv2", SegRef{s9, 0, 512, 0}, SegRef{}, h32, w32, a9, 0));
+    TRY(add_c2f(e, "model.12", SegRef{a9, 0, 256, 1}, SegRef{p4, 0, 128, 0}, h16, w16, 128, 1, false, a12));
+    TRY(add_c2f(e, "model.15", SegRef{a12, 0, 128, 1}, SegRef{p3, 0, 64, 0}, h8, w8, 64, 1, false, a15));
+    TRY(add_conv(e, "model.16.conv", SegRef{a15, 0, 64, 0}, SegRef{}, h8, w8, a16, 0));
+    TRY(add_c2f(e, "model.18", SegRef{a16, 0, 64, 0}, SegRef{a12, 0, 128, 0}, h16, w16, 128, 1, false, a18));
+    TRY(add_conv(e, "model.19.conv", SegRef{a18, 0, 128, 0}, SegRef{}, h16, w16, a19, 0));
+    TRY(add_c2f(e, "model.21", SegRef{a19, 0, 128, 0}, SegRef{a9, 0, 256, 0}, h32, w32, 256, 1, false, a21));
 
     // Detect head: per level one fp32 record of kHeadRec per anchor: box 64 | cls 16 | kpt 16
-    const int P[3] = {a15, a18, a21}, PC[3] = {64, 128, 256}, PS[3] = {s8, s16, s32};
+    const int P[3] = {a15, a18, a21}, PC[3] = {64, 128, 256}, PH[3] = {h8, h16, h32}, PW[3] = {w8, w16, w32};
     int base = 0;
     for (int i = 0; i < 3; i++) {
-        e->lvl_hw[i] = PS[i] * PS[i];
+        e->lvl_hw[i] = PH[i] * PW[i];
         e->lvl_base[i] = base;
         base += e->lvl_hw[i];
     }
@@ -1049,8 +1052,8 @@ static int build_engine(irmv_engine *e)
     for (int i = 0; i < 3; i++) {   // per-level views [slot][H*W][kHeadRec] into the one head allocation
         Tensor t;
         t.name = "head." + std::to_string(i);
-        t.H = PS[i]; t.W = PS[i]; t.C = kHeadRec; t.f32 = true;
-        t.slot_elems = (size_t)PS[i] * PS[i] * kHeadRec;
+        t.H = PH[i]; t.W = PW[i]; t.C = kHeadRec; t.f32 = true;
+        t.slot_elems = (size_t)PH[i] * PW[i] * kHeadRec;
         t.base = e->head_all + (size_t)e->lvl_base[i] * S * kHeadRec;
         e->head_t[i] = (int)e->tensors.size();
         e->tensor_idx[t.name] = e->head_t[i];
@@ -1095,8 +1098,8 @@ static int build_engine(irmv_engine *e)
             m.cin = PC[i]; m.cout = cm; m.k = 3; m.stride = 1; m.act = 1;
             m.w = e->merged_w.back().data(); m.b = e->merged_b.back().data();
             e->layers.push_back(m);
-            TRY(new_tensor(e, "22.s0." + std::to_string(i), PS[i], PS[i], cm, false, &t_s0[i]));
-            TRY(add_conv(e, m.name, SegRef{P[i], 0, PC[i], 0}, SegRef{}, PS[i], PS[i], t_s0[i], 0));
+            TRY(new_tensor(e, "22.s0." + std::to_string(i), PH[i], PW[i], cm, false, &t_s0[i]));
+            TRY(add_conv(e, m.name, SegRef{P[i], 0, PC[i], 0}, SegRef{}, PH[i], PW[i], t_s0[i], 0));
             Op &mo = e->ops.back();
             const double real = nbr == 3 ? 144.0 : 128.0;
             mo.flops *= real / cm;                      // algorithmic work: the zero-padded channels do not count
@@ -1108,15 +1111,15 @@ static int build_engine(irmv_engine *e)
             const std::string pre = std::string("model.22.") + br[b] + "." + std::to_string(i);
             const std::string tn = std::string("22.") + br[b] + "." + std::to_string(i);
             int t1 = -1, t2;
-            TRY(new_tensor(e, tn + ".1", PS[i], PS[i], mid[b], false, &t2));
+            TRY(new_tensor(e, tn + ".1", PH[i], PW[i], mid[b], false, &t2));
             if (e->merge_head0) {
-                TRY(add_conv(e, pre + ".1", SegRef{t_s0[i], coff0[b], mid[b], 0}, SegRef{}, PS[i], PS[i], t2, 0));
+                TRY(add_conv(e, pre + ".1", SegRef{t_s0[i], coff0[b], mid[b], 0}, SegRef{}, PH[i], PW[i], t2, 0));
             } else {
-                TRY(new_tensor(e, tn + ".0", PS[i], PS[i], mid[b], false, &t1));
-                TRY(add_conv(e, pre + ".0", SegRef{P[i], 0, PC[i], 0}, SegRef{}, PS[i], PS[i], t1, 0));
-                TRY(add_conv(e, pre + ".1", SegRef{t1, 0, mid[b], 0}, SegRef{}, PS[i], PS[i], t2, 0));
+                TRY(new_tensor(e, tn + ".0", PH[i], PW[i], mid[b], false, &t1));
+                TRY(add_conv(e, pre + ".0", SegRef{P[i], 0, PC[i], 0}, SegRef{}, PH[i], PW[i], t1, 0));
+                TRY(add_conv(e, pre + ".1", SegRef{t1, 0, mid[b], 0}, SegRef{}, PH[i], PW[i], t2, 0));
             }
-            TRY(add_conv(e, pre + ".2", SegRef{t2, 0, mid[b], 0}, SegRef{}, PS[i], PS[i], e->head_t[i], off[b]));
+            TRY(add_conv(e, pre + ".2", SegRef{t2, 0, mid[b], 0}, SegRef{}, PH[i], PW[i], e->head_t[i], off[b]));
             for (size_t k = e->ops.size() - (e->merge_head0 ? 2 : 3); k < e->ops.size(); k++) e->ops[k].level = i;
             {   // the branch's final 1x1 can ride in the epilogue of its second 3x3 (k_conv.hip, N2 > 0)
                 const int i1 = (int)e->ops.size() - 2, i2 = i1 + 1;
@@ -1187,7 +1190,7 @@ static int build_engine(irmv_engine *e)
     log_range(e, "pinned light_dets", e->light_dets_host, (size_t)c.max_det * sizeof(DevDet));
 
     PostArgs &p = e->post;
-    p.net = net; p.A = e->A; p.nc = e->nc; p.nk = e->nk;
+    p.net_w = net_w; p.net_h = net_h; p.A = e->A; p.nc = e->nc; p.nk = e->nk;
     p.logit_thr = (float)std::log((double)c.score_thr / (1.0 - (double)c.score_thr));
     p.iou_thr = c.iou_thr;
     p.max_det = c.max_det;
@@ -1197,8 +1200,8 @@ static int build_engine(irmv_engine *e)
     { const char *pf = getenv("IRMV_NMS_PREFILTER"); p.prefilter = (pf && pf[0] == '0') ? 0 : 1;
       if (const char *pe = getenv("IRMV_NMS_PRE")) { int hi = 0, lo = 0; if (sscanf(pe, "%d,%d", &hi, &lo) == 2 && hi >= 64 && hi <= 512 && lo >= 32 && lo < hi) p.prefilter = hi | (lo << 16); } }   // experiment: size of the head of the list   // =0: crowded frames sort and mask every candidate (round-3 behaviour; bit-identical)
     if (c.resize_mode == IRMV_RESIZE_STRETCH) {
-        p.scale_x = (float)c.src_width / (float)net;   // src/yolo_engine.cpp:155-156
-        p.scale_y = (float)c.src_height / (float)net;
+        p.scale_x = (float)c.src_width / (float)net_w;   // src/yolo_engine.cpp:155-156
+        p.scale_y = (float)c.src_height / (float)net_h;
         p.off_x = p.off_y = 0.f;
     } else {
         p.scale_x = (float)c.src_width / (float)nw;
@@ -1361,18 +1364,22 @@ static int choose_sync_launch(irmv_engine *e)
 
 // struct_size of irmv_engine_cfg before src_format and the gains were appended
 constexpr size_t kCfgSizeV1 = offsetof(irmv_engine_cfg, src_format);
+// ... and before net_height: that header's sizeof.  net_height sits in its tail padding, so those bytes are never read.
+constexpr size_t kCfgSizeV2 = offsetof(irmv_engine_cfg, reserved2);
+static_assert(offsetof(irmv_engine_cfg, net_height) < kCfgSizeV2 && kCfgSizeV2 < sizeof(irmv_engine_cfg), "three distinct cfg sizes");
 
 extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **out)
 {
     if (!cfg_in || !out) return fail(IRMV_ERR_ARG, "cfg/out is null");
-    if (cfg_in->struct_size != sizeof(irmv_engine_cfg) && cfg_in->struct_size != kCfgSizeV1) return fail(IRMV_ERR_ARG, "irmv_engine_cfg size mismatch");
+    const size_t sz = cfg_in->struct_size;
+    if (sz != sizeof(irmv_engine_cfg) && sz != kCfgSizeV1 && sz != kCfgSizeV2) return fail(IRMV_ERR_ARG, "irmv_engine_cfg size mismatch");
     irmv_engine_cfg full;   // an older caller's prefix, the appended fields at their defaults
-    if (cfg_in->struct_size == kCfgSizeV1) {
+    if (sz != sizeof(irmv_engine_cfg)) {
         irmv_engine_cfg_default(&full);
-        memcpy(&full, cfg_in, kCfgSizeV1);
+        memcpy(&full, cfg_in, sz == kCfgSizeV1 ? kCfgSizeV1 : offsetof(irmv_engine_cfg, net_height));
         full.struct_size = sizeof full;
     }
-    const irmv_engine_cfg *cfg = cfg_in->struct_size == kCfgSizeV1 ? &full : cfg_in;
+    const irmv_engine_cfg *cfg = sz != sizeof(irmv_engine_cfg) ? &full : cfg_in;
     if (cfg->src_format < IRMV_SRC_HWC8 || cfg->src_format > IRMV_SRC_BAYER_GBRG8) return fail(IRMV_ERR_ARG, "unknown src_format (IRMV_SRC_*)");
     if (cfg->src_format != IRMV_SRC_HWC8) {
         if (cfg->src_width % 2 || cfg->src_height % 2) return fail(IRMV_ERR_ARG, "a Bayer src_format (IRMV_SRC_BAYER_*8) needs an even src_width and src_height");
@@ -1380,6 +1387,8 @@ extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **o
             if (cfg->bayer_gain_q8[i] > 1023) return fail(IRMV_ERR_ARG, "bayer_gain_q8 must be in [0, 1023] (Q8, 256 = 1.0)");
     }
     if (cfg->net_size < 64 || cfg->net_size % 32 != 0 || cfg->net_size > 2048) return fail(IRMV_ERR_ARG, "net_size must be a multiple of 32 in [64, 2048]");
+    if (cfg->net_height != 0 && (cfg->net_height < 64 || cfg->net_height % 32 != 0 || cfg->net_height > 2048))
+        return fail(IRMV_ERR_ARG, "net_height must be 0 (square) or a multiple of 32 in [64, 2048]");
     if (cfg->src_width < 2 || cfg->src_height < 2 || cfg->src_width > 4096) return fail(IRMV_ERR_ARG, "src size out of range (width <= 4096)");
     if (cfg->num_slots < 1 || cfg->num_slots > 256) return fail(IRMV_ERR_ARG, "num_slots must be 1..256");
     if (cfg->max_det < 1 || cfg->max_det > IRMV_MAX_DET_CAP) return fail(IRMV_ERR_ARG, "max_det must be 1..256");
@@ -1392,6 +1401,7 @@ extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **o
     if (cfg->device < 0 || cfg->device >= ndev) return fail(IRMV_ERR_HIP, "no such HIP device");
     std::unique_ptr<irmv_engine> e(new irmv_engine);
     e->cfg = *cfg;
+    if (e->cfg.net_height == 0) e->cfg.net_height = e->cfg.net_size;   // from here on: net_size = width, net_height = height
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0) e->num_cus = cus;
@@ -1424,6 +1434,12 @@ extern "C" int irmv_engine_num_slots(const irmv_engine *e) { return e ? e->cfg.n
 extern "C" int irmv_engine_max_det(const irmv_engine *e) { return e ? e->cfg.max_det : 0; }
 extern "C" int irmv_engine_num_streams(const irmv_engine *e) { return e ? e->num_streams : 0; }
 extern "C" int irmv_engine_num_anchors(const irmv_engine *e) { return e ? e->A : 0; }
+extern "C" int irmv_engine_net_dims(const irmv_engine *e, int *width, int *height)
+{
+    if (!e || !width || !height) return fail(IRMV_ERR_ARG, "engine/width/height is null");
+    *width = e->cfg.net_size; *height = e->cfg.net_height;
+    return IRMV_OK;
+}
 extern "C" int irmv_engine_numa_node(const irmv_engine *e) { return e ? e->numa_node : -1; }
 extern "C" int irmv_engine_numa_placed(const irmv_engine *e) { return e && e->numa_placed ? 1 : 0; }
 
@@ -1773,8 +1789,7 @@ static void scan_args_for(const irmv_engine *e, const Op &op, const PostArgs &pa
 {
     a.scan_keys = pa.keys; a.scan_counts = pa.counts; a.scan_thr = pa.logit_thr; a.scan_nc = pa.nc;
     a.scan_key_cap = pa.key_cap;
-    const int w0 = e->cfg.net_size / 8;
-    a.scan_abase = op.level == 0 ? 0 : (op.level == 1 ? w0 * w0 : w0 * w0 + (w0 / 2) * (w0 / 2));
+    a.scan_abase = e->lvl_base[op.level];
 }
 
 // one launch for all members of group g on slot `first`; member k appends candidates to pa's key lists if bit k of `scan` is set
@@ -2073,7 +2088,7 @@ static bool launch_c2f32_op(const irmv_engine *e, const Op &op, int first, int c
 // ev != nullptr (irmv_engine_profile): one event pair per launch, around `reps` repetitions of it (one if it is `once`).
 static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipStream_t s, int reps, std::vector<EvRec> *ev)
 {
-    const int net = e->cfg.net_size;
+    const int net_w = e->cfg.net_size, net_h = e->cfg.net_height;
     const PostArgs pa = post_args(e, first);
     for (const Launch &l : e->plans[kind]) {
         const Op &op = e->ops[l.op];
@@ -2092,7 +2107,7 @@ static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hip
             a.src = e->src_dev + (size_t)first * e->frame_bytes;
             a.dst = static_cast<half_t *>(e->tensors[op.out_t].slot(first));
             a.tx = e->tap_x; a.ty = e->tap_y;
-            a.sw = e->cfg.src_width; a.sh = e->cfg.src_height; a.net = net; a.swap_rb = e->cfg.swap_rb;
+            a.sw = e->cfg.src_width; a.sh = e->cfg.src_height; a.net_w = net_w; a.net_h = net_h; a.swap_rb = e->cfg.swap_rb;
             a.src_slot_bytes = e->frame_bytes;
             launch_preprocess(a, count, s);
             break;
@@ -2103,7 +2118,7 @@ static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hip
             a.src_slot_bytes = e->frame_bytes;
             a.tx = e->tap_x; a.ty = e->tap_y;
             a.vx0 = e->front_v[0]; a.vx1 = e->front_v[1]; a.vy0 = e->front_v[2]; a.vy1 = e->front_v[3];
-            a.sw = e->cfg.src_width; a.sh = e->cfg.src_height; a.net = net; a.swap_rb = e->cfg.swap_rb;
+            a.sw = e->cfg.src_width; a.sh = e->cfg.src_height; a.net_w = net_w; a.net_h = net_h; a.swap_rb = e->cfg.swap_rb;
             a.fastx = e->front_fastx; a.fx_i0 = e->front_fx_i0; a.fx_step = e->front_fx_step;
             a.w0 = e->conv0_w; a.b0 = e->conv0_b;
             a.w1 = op.w_packed; a.b1 = op.bias;
@@ -2120,7 +2135,8 @@ static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hip
             const Tensor &xt = e->tensors[op.s0.t], &ot = e->tensors[op.out_t];
             a.x = static_cast<const half_t *>(xt.slot(first)); a.x_ld = xt.C;
             a.out = static_cast<half_t *>(ot.slot(first)); a.out_ld = ot.C;
-            a.S = xt.H; a.tiles = (xt.H + kC2fTile - 1) / kC2fTile;
+            a.H = xt.H; a.W = xt.W;
+            a.tiles_x = (xt.W + kC2fTile - 1) / kC2fTile; a.tiles_y = (xt.H + kC2fTile - 1) / kC2fTile;
             const Op &c1 = e->ops[op.sub[0]], &m1 = e->ops[op.sub[1]], &m2 = e->ops[op.sub[2]], &c2 = e->ops[op.sub[3]];
             a.w_cv1 = c1.w_packed; a.w_m1 = m1.w_packed; a.w_m2 = m2.w_packed; a.w_cv2 = c2.w_packed;
             a.b_cv1 = c1.bias; a.b_m1 = m1.bias; a.b_m2 = m2.bias; a.b_cv2 = c2.bias;
@@ -2188,7 +2204,7 @@ static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hip
             Conv0Args a;
             a.x = static_cast<const half_t *>(e->tensors[op.s0.t].slot(first));
             a.y = static_cast<half_t *>(e->tensors[op.out_t].slot(first));
-            a.w = e->conv0_w; a.b = e->conv0_b; a.net = net; a.batch = count;
+            a.w = e->conv0_w; a.b = e->conv0_b; a.net_w = net_w; a.net_h = net_h; a.batch = count;
             launch_conv0(a, s);
             break;
         }
@@ -2633,7 +2649,7 @@ extern "C" int irmv_engine_read_input(irmv_engine *e, int slot, float *chw)
     TRY(materialize_fused(e, slot));
     std::vector<float> v;
     TRY(read_tensor_f32(e, e->tensors[e->tensor_idx.at("input")], slot, v));
-    const size_t n = (size_t)e->cfg.net_size * e->cfg.net_size;
+    const size_t n = (size_t)e->cfg.net_size * e->cfg.net_height;
     for (size_t p = 0; p < n; p++)
         for (int c = 0; c < 3; c++) chw[c * n + p] = v[p * 4 + c];
     return IRMV_OK;

@@ -119,9 +119,9 @@ struct AxisTap { int32_t i0, i1, w1, pad; };
 
 struct PreArgs {
     const uint8_t *src;   // [B][sh][sw][3]
-    half_t *dst;          // [B][net][net][4]
-    const AxisTap *tx, *ty;
-    int sw, sh, net, swap_rb;
+    half_t *dst;          // [B][net_h][net_w][4]
+    const AxisTap *tx, *ty;   // [net_w], [net_h]
+    int sw, sh, net_w, net_h, swap_rb;
     size_t src_slot_bytes;
 };
 void launch_preprocess(const PreArgs &a, int batch, hipStream_t s);
@@ -144,11 +144,11 @@ void launch_demosaic(const BayerArgs &a, int batch, hipStream_t s);
 
 // model.0.conv: 3x3 s2, 3(+1 pad) -> 16, SiLU
 struct Conv0Args {
-    const half_t *x;      // [B][net][net][4]
-    half_t *y;            // [B][net/2][net/2][16]
+    const half_t *x;      // [B][net_h][net_w][4]
+    half_t *y;            // [B][net_h/2][net_w/2][16]
     const half_t *w;      // packed MFMA A fragments [2 k-steps][64 lanes][8]; k = kh*16 + slot*4 + c
     const float *b;       // [16]
-    int net, batch;
+    int net_w, net_h, batch;
 };
 void launch_conv0(const Conv0Args &a, hipStream_t s);
 
@@ -161,13 +161,13 @@ struct FrontArgs {
     size_t src_slot_bytes;
     const AxisTap *tx, *ty;
     int vx0, vx1, vy0, vy1;   // net-input columns / rows with a source tap: [v0, v1) (the rest is letterbox padding)
-    int sw, sh, net, swap_rb;
+    int sw, sh, net_w, net_h, swap_rb;
     int fastx, fx_i0, fx_step;   // columns at exactly 2 : 1: column vx0 + k blends the source pair (m, m + 1), m = fx_i0 + fx_step k (fx_step = +-2), weights 1/2; fastx bit 1: tiles without padding read the source straight into registers
     const half_t *w0;     // model.0.conv fragments (Conv0Args::w)
     const float *b0;
     const half_t *w1;     // model.1.conv, direct-family packing (Cin = 16: 5 k-steps x 2 paired tiles)
     const float *b1;
-    half_t *out;          // [B][net/4][net/4][out_ld]
+    half_t *out;          // [B][net_h/4][net_w/4][out_ld]
     int out_ld;
     int tiles_x, tiles_y;
     int tile_y;           // kFrontTileY, or kFrontTileYDirect (needs fastx bit 1)
@@ -180,11 +180,11 @@ bool launch_front(const FrontArgs &a, int batch, hipStream_t s);
 // fused model.2 (C2f: cv1, one shortcut Bottleneck of two 3x3 16 -> 16 convs, cv2) (k_c2f.hip)
 constexpr int kC2fTile = 16;
 struct C2fArgs {
-    const half_t *x;      // block input [B][S][S][x_ld], 32 channels used
+    const half_t *x;      // block input [B][H][W][x_ld], 32 channels used
     int x_ld;
-    half_t *out;          // block output [B][S][S][out_ld], 32 channels
+    half_t *out;          // block output [B][H][W][out_ld], 32 channels
     int out_ld;
-    int S, tiles;         // spatial size, tiles per side
+    int H, W, tiles_x, tiles_y;   // spatial size, tiles per row / column
     const half_t *w_cv1, *w_m1, *w_m2, *w_cv2;   // direct-family packings of the four layers
     const float *b_cv1, *b_m1, *b_m2, *b_cv2;
 };
@@ -386,7 +386,7 @@ struct PostArgs {
     int key_cap;              // = A * nc: the list can never overflow
     DevDet *dets;             // [B][max_det]
     DevFrameOut *fout;        // [B]
-    int net, A, nc, nk;
+    int net_w, net_h, A, nc, nk;   // net input width x height; A = sum over s in {8, 16, 32} of (net_h / s) (net_w / s)
     float logit_thr, iou_thr;
     int max_det, pre_nms_cap;
     // parse_output mapping net -> source frame: x_src = (x - off_x) * scale_x

@@ -64,10 +64,10 @@ __global__ __launch_bounds__(256) void c2f2_kernel(C2fArgs a, int batch, int xcd
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, r = lane & 15;
     int tile_id, b;
-    tile_image(blockIdx.x, a.tiles * a.tiles, batch, xcd, tile_id, b);
-    const int tyi = tile_id / a.tiles, txi = tile_id - tyi * a.tiles;
+    tile_image(blockIdx.x, a.tiles_x * a.tiles_y, batch, xcd, tile_id, b);
+    const int tyi = tile_id / a.tiles_x, txi = tile_id - tyi * a.tiles_x;
     const int oy0 = tyi * T, ox0 = txi * T;
-    const int S = a.S;
+    const int H = a.H, W = a.W;
     const half8 zero8 = (half8){0, 0, 0, 0, 0, 0, 0, 0};
 
     // ---- weights (16 fragments) into registers, each a phase or more before its first use: cv1 and m.0.cv1 now (the loads
@@ -100,13 +100,13 @@ __global__ __launch_bounds__(256) void c2f2_kernel(C2fArgs a, int batch, int xcd
         constexpr int NROWT = XW / 4, NCOLT = (XN / 16 - XW + 3) / 4;      // per wave: 5 row tiles, then 1 or 2 column tiles (XN / 16 - XW = 5 of them)
         static_assert(XW % 4 == 0 && XW - 16 == 4 && NCOLT == 2, "20 row tiles + 5 column tiles");
         const char *xbase = reinterpret_cast<const char *>(a.x);
-        const uint32_t img = (uint32_t)b * (uint32_t)(S * S);
+        const uint32_t img = (uint32_t)b * (uint32_t)(H * W);
         auto px_off = [&](int gy, int gx) -> uint32_t {                    // byte offset of the (clamped) pixel, this lane's 8 channels
-            const int gyc = gy < 0 ? 0 : (gy >= S ? S - 1 : gy), gxc = gx < 0 ? 0 : (gx >= S ? S - 1 : gx);
-            return ((img + (uint32_t)(gyc * S + gxc)) * (uint32_t)a.x_ld + 8u * g) * 2u;
+            const int gyc = gy < 0 ? 0 : (gy >= H ? H - 1 : gy), gxc = gx < 0 ? 0 : (gx >= W ? W - 1 : gx);
+            return ((img + (uint32_t)(gyc * W + gxc)) * (uint32_t)a.x_ld + 8u * g) * 2u;
         };
         const int gx_r = ox0 - 2 + r;
-        const bool in_x = (unsigned)gx_r < (unsigned)S;
+        const bool in_x = (unsigned)gx_r < (unsigned)W;
         int ly_c[NCOLT], lx_c[NCOLT];
         bool has_c[NCOLT];
 #pragma unroll
@@ -137,13 +137,13 @@ __global__ __launch_bounds__(256) void c2f2_kernel(C2fArgs a, int batch, int xcd
 #pragma unroll
         for (int i = 0; i < NROWT; i++) {
             const int t = wave + 4 * i, gy = oy0 - 2 + t;                    // wave-uniform
-            run_tile(Bq[i], t, r, in_x && (unsigned)gy < (unsigned)S);
+            run_tile(Bq[i], t, r, in_x && (unsigned)gy < (unsigned)H);
         }
 #pragma unroll
         for (int k = 0; k < NCOLT; k++) {
             if (!has_c[k]) break;
             const int gy = oy0 - 2 + ly_c[k], gx = ox0 - 2 + lx_c[k];
-            run_tile(Bq[NROWT + k], ly_c[k], lx_c[k], (unsigned)gy < (unsigned)S && (unsigned)gx < (unsigned)S);
+            run_tile(Bq[NROWT + k], ly_c[k], lx_c[k], (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W);
         }
     }
     __syncthreads();
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void c2f2_kernel(C2fArgs a, int batch, int xcd
             if (mv) {
                 const int gy = oy0 - 1 + ly, gx = ox0 - 1 + lx;
                 half4 o = (half4){0, 0, 0, 0};
-                if ((unsigned)gy < (unsigned)S && (unsigned)gx < (unsigned)S) o = silu_pack4(acc[0], acc[1], acc[2], acc[3]);
+                if ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) o = silu_pack4(acc[0], acc[1], acc[2], acc[3]);
                 *reinterpret_cast<half4 *>(s_t + m * HP + g * 8) = o;
             }
         }
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void c2f2_kernel(C2fArgs a, int batch, int xcd
         float bias[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) bias[i] = s_bias[32 + g * 8 + i];
-        half_t *out = a.out + (size_t)b * S * S * a.out_ld;
+        half_t *out = a.out + (size_t)b * H * W * a.out_ld;
         for (int t = wave; t < T * T / 16; t += 4) {
             const int m = t * 16 + r;
             const int ly = m / T, lx = m - ly * T;
@@ -238,9 +238,9 @@ __global__ __launch_bounds__(256) void c2f2_kernel(C2fArgs a, int batch, int xcd
             acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(Wc2[0][1], B1, acc0, 0, 0, 0);
             acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(Wc2[1][1], B1, acc1, 0, 0, 0);
             const int gy = oy0 + ly, gx = ox0 + lx;
-            if (gy < S && gx < S) {
+            if (gy < H && gx < W) {
                 const half8 o = silu_pack8(acc0[0], acc0[1], acc0[2], acc0[3], acc1[0], acc1[1], acc1[2], acc1[3]);
-                *reinterpret_cast<half8 *>(out + ((size_t)gy * S + gx) * a.out_ld + g * 8) = o;
+                *reinterpret_cast<half8 *>(out + ((size_t)gy * W + gx) * a.out_ld + g * 8) = o;
             }
         }
     }
@@ -250,7 +250,7 @@ static int c2f_xcd_order() { return xcd_image_order(); }
 
 void launch_c2f2(const C2fArgs &a, int batch, hipStream_t s)
 {
-    hipLaunchKernelGGL(c2f2_kernel, dim3(a.tiles * a.tiles * batch), dim3(256), 0, s, a, batch, c2f_xcd_order());
+    hipLaunchKernelGGL(c2f2_kernel, dim3(a.tiles_x * a.tiles_y * batch), dim3(256), 0, s, a, batch, c2f_xcd_order());
 }
 
 

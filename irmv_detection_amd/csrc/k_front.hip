@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TY == 4 ? 5
     tile_image(blockIdx.x, a.tiles_x * a.tiles_y, batch, xcd, tile_id, b);
     const int tyi = tile_id / a.tiles_x, txi = tile_id - tyi * a.tiles_x;
     const int oy0 = tyi * TY, ox0 = txi * TX;
-    const int net = a.net, W0 = net >> 1, W1 = net >> 2;
+    const int net_w = a.net_w, net_h = a.net_h, W0 = net_w >> 1, H0 = net_h >> 1, W1 = net_w >> 2, H1 = net_h >> 2;
     const int gy0 = 4 * oy0 - 3, gx0 = 4 * ox0 - 3;   // net-input coordinates of s_in[0][0]
 
     // both biases -> LDS (visible after the staging barrier): fetched from global memory where they are used (start of
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TY == 4 ? 5
     // registers and blends two adjacent net-input pixels from them.  Same integers as A2's 2 : 1 path (sum of the pair,
     // vertical blend, one rounding shift), so the same bits.  Tiles that contain padding or out-of-image pixels (EDGE) load
     // from clamped addresses and select the constant afterwards.
-    const bool tile_inside = gx0 >= max(a.vx0, 0) && gx0 + INW <= min(a.vx1, net) && gy0 >= max(a.vy0, 0) && gy0 + INH <= min(a.vy1, net);
+    const bool tile_inside = gx0 >= max(a.vx0, 0) && gx0 + INW <= min(a.vx1, net_w) && gy0 >= max(a.vy0, 0) && gy0 + INH <= min(a.vy1, net_h);
     const bool direct = (a.fastx & 2) != 0;
     if (direct) {
         constexpr int NPAIR = (INW + 1) / 2, NIT = INH * NPAIR;                    // 34 pairs x 19 (35) rows = 646 (1190) items
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TY == 4 ? 5
                     half4 o = (half4){v0, v1, v2, (half_t)0.0f};
                     if (EDGE) {   // outside the net input: the convolution's zero padding; inside without a source: the letterbox grey
                         const int gx = gx0 + lx;
-                        const bool in_net = (unsigned)gy < (unsigned)net && (unsigned)gx < (unsigned)net;
+                        const bool in_net = (unsigned)gy < (unsigned)net_h && (unsigned)gx < (unsigned)net_w;
                         const bool has_src = gy >= a.vy0 && gy < a.vy1 && gx >= a.vx0 && gx < a.vx1;
                         o = !in_net ? (half4){0, 0, 0, 0} : (has_src ? o : (half4){padv, padv, padv, (half_t)0.0f});
                     }
@@ -204,8 +204,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TY == 4 ? 5
         // branch's block behind a wait -- for every load issued so far -- in front of the source loads)
         const bool tap_x = tid < INW;
         const int tap_i = tap_x ? gx0 + tid : gy0 + (tid - INW);
-        const bool tap_ok = tid < INW + INH && (unsigned)tap_i < (unsigned)net;
-        AxisTap my_tap = (tap_x ? a.tx : a.ty)[min(max(tap_i, 0), net - 1)];
+        const int tap_n = tap_x ? net_w : net_h;
+        const bool tap_ok = tid < INW + INH && (unsigned)tap_i < (unsigned)tap_n;
+        AxisTap my_tap = (tap_x ? a.tx : a.ty)[min(max(tap_i, 0), tap_n - 1)];
     
         FSTAMP(1);
         // ---- A1: source region -> LDS as 4-byte pixels (12 source bytes -> one 16-byte LDS store) ----
@@ -314,7 +315,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TY == 4 ? 5
                 // pixel tid + 256 k sits 3 rows and 55 columns (256 = 3 INW + 55) past pixel tid + 256 (k - 1)
                 static_assert(INW == 67 && INH * INW <= 5 * 256, "the walk below is written for the 19 x 67 tile");
                 int ly = tid / INW, lx = tid - ly * INW;
-                const bool inside = gx0 >= max(a.vx0, 0) && gx0 + INW <= min(a.vx1, net) && gy0 >= max(a.vy0, 0) && gy0 + INH <= min(a.vy1, net);
+                const bool inside = gx0 >= max(a.vx0, 0) && gx0 + INW <= min(a.vx1, net_w) && gy0 >= max(a.vy0, 0) && gy0 + INH <= min(a.vy1, net_h);
                 if (inside) {   // (three tiles in four) every pixel of the tile has both taps: nothing to test per pixel
     #pragma unroll
                     for (int k = 0; k < 5; k++) {
@@ -328,7 +329,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TY == 4 ? 5
                         if (k < 4 || tid < INH * INW - 4 * 256) {
                             const int gx = gx0 + lx;
                             half4 o = (half4){0, 0, 0, 0};
-                            if ((unsigned)(gy0 + ly) < (unsigned)net && (unsigned)gx < (unsigned)net) {
+                            if ((unsigned)(gy0 + ly) < (unsigned)net_h && (unsigned)gx < (unsigned)net_w) {
                                 const uint32_t ty = s_ty[ly];
                                 o = (ty == 0xffffffffu || gx < a.vx0 || gx >= a.vx1) ? (half4){padv, padv, padv, (half_t)0.0f} : blend(ly, lx, ty);
                             }
@@ -344,7 +345,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TY == 4 ? 5
                 const int ly = pp / INW, lx = pp - ly * INW;
                 const int p = ly * INP + lx;
                 half4 o = (half4){0, 0, 0, 0};
-                if ( (unsigned)(gy0 + ly) < (unsigned)net && (unsigned)(gx0 + lx) < (unsigned)net) {
+                if ( (unsigned)(gy0 + ly) < (unsigned)net_h && (unsigned)(gx0 + lx) < (unsigned)net_w) {
                     const uint32_t ty = s_ty[ly], tx = s_tx[lx];
                     if (ty == 0xffffffffu || tx == 0xffffffffu) {
                         o = (half4){padv, padv, padv, (half_t)0.0f};
@@ -394,7 +395,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TY == 4 ? 5
         // that a wave spends (ablation: the reads alone were 57 of the kernel's 182 us per 64 frames), so the wave's
         // tiles go in batches: every fragment read of a batch is issued first, then its MFMAs, then its epilogues.
         const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-        const bool c0_inside = 2 * oy0 - 1 >= 0 && 2 * oy0 - 1 + C0H <= W0 && 2 * ox0 - 1 >= 0 && 2 * ox0 - 1 + C0W <= W0;   // no model.1 padding in this tile
+        const bool c0_inside = 2 * oy0 - 1 >= 0 && 2 * oy0 - 1 + C0H <= H0 && 2 * ox0 - 1 >= 0 && 2 * ox0 - 1 + C0W <= W0;   // no model.1 padding in this tile
         constexpr int NROWT = 2 * C0H, NCOLT = (C0H + 15) / 16, NTILES = NROWT + NCOLT;
         constexpr int KT = (NTILES + 3) / 4;   // tiles per wave (the last one may not exist for the upper waves)
         static_assert(C0W == 33 && NROWT % 4 == 2 && NCOLT <= 2, "row tiles end with waves 0, 1 of the last k; waves 2, 3 take the column tiles");
@@ -445,7 +446,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TY == 4 ? 5
                 const int ly = colt ? ly_c : row0 + 2 * (k0 + k);
                 const int cy = 2 * oy0 - 1 + ly, cx = colt ? 2 * ox0 - 1 + (C0W - 1) : cx_row;
                 half4 o = z4;
-                if (c0_inside || ((unsigned)cy < (unsigned)W0 && (unsigned)cx < (unsigned)W0)) {
+                if (c0_inside || ((unsigned)cy < (unsigned)H0 && (unsigned)cx < (unsigned)W0)) {
                     // model.0 reads the UNSCALED image: one fma brings the accumulator to the activation scale (bias0 = log2 e * b)
                     o = silu_pack4(__builtin_fmaf(acc[k][0], kActScale, bias0[0]), __builtin_fmaf(acc[k][1], kActScale, bias0[1]),
                                    __builtin_fmaf(acc[k][2], kActScale, bias0[2]), __builtin_fmaf(acc[k][3], kActScale, bias0[3]));
@@ -494,7 +495,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TY == 4 ? 5
 #pragma unroll
             for (int mt = 0; mt < MTC; mt++) {
                 const int oy = oy0 + MTC * wave + mt;
-                if (oy >= W1) continue;
+                if (oy >= H1) continue;
                 float vals[8];
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
@@ -502,7 +503,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TY == 4 ? 5
                     vals[4 + i] = acc[mt][1][i];
                 }
                 const half8 o = silu_pack8(vals[0], vals[1], vals[2], vals[3], vals[4], vals[5], vals[6], vals[7]);
-                *reinterpret_cast<half8 *>(a.out + ((size_t)(b * W1 + oy) * W1 + ox) * a.out_ld + g * 8) = o;
+                *reinterpret_cast<half8 *>(a.out + ((size_t)(b * H1 + oy) * W1 + ox) * a.out_ld + g * 8) = o;
             }
         }
     }

@@ -60,7 +60,7 @@ __device__ __forceinline__ int anchor_of(uint32_t id, int nc, int A)
 }
 
 // anchor -> grid position, stride, and the (level base, level size, index in level) that locate its head record
-__device__ __forceinline__ void anchor_geom(int a, int net, int &ix, int &iy, int &stride, int &lbase, int &lhw, int &rin)
+__device__ __forceinline__ void anchor_geom(int a, int net_w, int net_h, int &ix, int &iy, int &stride, int &lbase, int &lhw, int &rin)
 {
     int base = 0;
     ix = iy = 0;
@@ -70,7 +70,7 @@ __device__ __forceinline__ void anchor_geom(int a, int net, int &ix, int &iy, in
     rin = 0;
 #pragma unroll
     for (int l = 0; l < 3; l++) {
-        const int s = 8 << l, w = net / s, cnt = w * w;
+        const int s = 8 << l, w = net_w / s, cnt = w * (net_h / s);
         if (stride == 0 && a < base + cnt) {
             const int r = a - base;
             iy = r / w;
@@ -143,7 +143,7 @@ __device__ __forceinline__ void decode_boxes(const PostArgs &a, int b, const uns
         const bool live = ai < n_anch;                 // quad-uniform
         const int an = live ? (alist ? (int)alist[ai] : ai) : 0;   // no list (more anchors than it can index): every anchor
         int ix, iy, s, lbase, lhw, rin;
-        anchor_geom(an, a.net, ix, iy, s, lbase, lhw, rin);
+        anchor_geom(an, a.net_w, a.net_h, ix, iy, s, lbase, lhw, rin);
         const float *rec = head_rec(a.head_all, a.slots_total, a.first + b, lbase, lhw, rin);
         float l[16];
 #pragma unroll
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256) void scan_decode_kernel(PostArgs a, int per)
     constexpr int U = kScanU;
     if (tid == 0) s_n = 0;
     __syncthreads();
-    const int w0 = a.net >> 3, A0 = w0 * w0, A1 = A0 + (w0 >> 1) * (w0 >> 1);   // level boundaries
+    const int w0 = a.net_w >> 3, h0 = a.net_h >> 3, A0 = w0 * h0, A1 = A0 + (w0 >> 1) * (h0 >> 1);   // level boundaries
     unsigned long long *gk = a.keys + (size_t)b * a.key_cap;
     const int t_end = min((int)(blockIdx.x + 1) * per, quads);
     for (int t0 = blockIdx.x * per; t0 < t_end; t0 += 256 * U) {
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void scan_decode_kernel(PostArgs a, int per)
                 const float dl = __shfl(d, base), dt = __shfl(d, base + 1), dr = __shfl(d, base + 2), db = __shfl(d, base + 3);
                 if (q == 0) {
                     int ix, iy, s, lbase, lhw, rin;
-                    anchor_geom(an, a.net, ix, iy, s, lbase, lhw, rin);
+                    anchor_geom(an, a.net_w, a.net_h, ix, iy, s, lbase, lhw, rin);
                     const float ax = (float)ix + 0.5f, ay = (float)iy + 0.5f, sf = (float)s;
                     f32x4 box;
                     box[0] = (ax - dl) * sf;
@@ -425,7 +425,7 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
         int lbase = 0;
 #pragma unroll 1
         for (int l = 0; l < 3; l++) {
-            const int lw = a.net / (8 << l), lhw = lw * lw;
+            const int lhw = (a.net_w / (8 << l)) * (a.net_h / (8 << l));
             const float *lrec = a.head_all + ((size_t)lbase * a.slots_total + (size_t)(a.first + b) * lhw) * kHeadRec;
             const int quads = lhw * 4;
             for (int q0 = 0; q0 < quads; q0 += 1024 * U) {
@@ -473,7 +473,7 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
                 const uint32_t id = 0xffffffffu - (uint32_t)(key & 0xffffffffu);
                 an_[u] = live_[u] ? anchor_of(id, a.nc, a.A) : 0;
                 int ix, iy, st, lbase, lhw, rin;
-                anchor_geom(an_[u], a.net, ix, iy, st, lbase, lhw, rin);
+                anchor_geom(an_[u], a.net_w, a.net_h, ix, iy, st, lbase, lhw, rin);
                 const float *rec = head_rec(a.head_all, a.slots_total, a.first + b, lbase, lhw, rin);
 #pragma unroll
                 for (int i = 0; i < 4; i++) v[u][i] = reinterpret_cast<const f32x4 *>(rec + 16 * q)[i];
@@ -488,7 +488,7 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
                 const float dl = __shfl(d, base), dt = __shfl(d, base + 1), dr = __shfl(d, base + 2), db = __shfl(d, base + 3);
                 if (live_[u] && q == 0) {
                     int ix, iy, st, lbase, lhw, rin;
-                    anchor_geom(an_[u], a.net, ix, iy, st, lbase, lhw, rin);
+                    anchor_geom(an_[u], a.net_w, a.net_h, ix, iy, st, lbase, lhw, rin);
                     const float ax = (float)ix + 0.5f, ay = (float)iy + 0.5f, sf = (float)st;
                     f32x4 box;
                     box[0] = (ax - dl) * sf;
@@ -709,7 +709,7 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
                 id_[u] = 0xffffffffu - (uint32_t)(key & 0xffffffffu);
                 an_[u] = live ? anchor_of(id_[u], a.nc, a.A) : 0;
                 int ix, iy, st, lbase, lhw, rin;
-                anchor_geom(an_[u], a.net, ix, iy, st, lbase, lhw, rin);
+                anchor_geom(an_[u], a.net_w, a.net_h, ix, iy, st, lbase, lhw, rin);
                 const float *rec = head_rec(a.head_all, a.slots_total, a.first + b, lbase, lhw, rin);
 #pragma unroll
                 for (int i = 0; i < 4; i++) v[u][i] = reinterpret_cast<const f32x4 *>(rec + 16 * q)[i];
@@ -728,7 +728,7 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
                 if (r < n_stored) {
                     if (q == 0) {
                         int ix, iy, st, lbase, lhw, rin;
-                        anchor_geom(an_[u], a.net, ix, iy, st, lbase, lhw, rin);
+                        anchor_geom(an_[u], a.net_w, a.net_h, ix, iy, st, lbase, lhw, rin);
                         const float ax = (float)ix + 0.5f, ay = (float)iy + 0.5f, sf = (float)st;
                         f32x4 box;
                         box[0] = (ax - dl) * sf;
@@ -1230,7 +1230,7 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
                 kpv[4] = k1[0]; kpv[5] = k1[1]; kpv[6] = k1[2]; kpv[7] = k1[3];
             } else {
                 int ix, iy, s, lbase, lhw, rin;
-                anchor_geom(an, a.net, ix, iy, s, lbase, lhw, rin);
+                anchor_geom(an, a.net_w, a.net_h, ix, iy, s, lbase, lhw, rin);
                 const float *kp = head_rec(a.head_all, a.slots_total, a.first + b, lbase, lhw, rin) + kKptOff;
 #pragma unroll
                 for (int q = 0; q < 8; q++) kpv[q] = q < a.nk ? kp[q] : 0.f;
@@ -1247,7 +1247,7 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
             const unsigned long long key = kept_key[j];
             const float logit = unorderable((uint32_t)(key >> 32));
             int ix, iy, s, lbase, lhw, rin;
-            anchor_geom(an, a.net, ix, iy, s, lbase, lhw, rin);
+            anchor_geom(an, a.net_w, a.net_h, ix, iy, s, lbase, lhw, rin);
             const float axm = ((float)ix + 0.5f) - 0.5f, aym = ((float)iy + 0.5f) - 0.5f, sf = (float)s;
             if (w) {
                 d->score = 1.0f / (1.0f + irmv_expf(-logit));

@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a)
     const AxisTap ty = a.ty[dy];
     const int row_bytes = a.sw * 3;
     const uint8_t *src = a.src + (size_t)b * a.src_slot_bytes;
-    half_t *dst = a.dst + ((size_t)b * a.net + dy) * a.net * 4;
+    half_t *dst = a.dst + ((size_t)b * a.net_h + dy) * a.net_w * 4;
     const half_t padv = (half_t)(114.0f / 255.0f);
 
     if (ty.i0 >= 0) {
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a)
     __syncthreads();
 
     const uint32_t wy = (uint32_t)ty.w1;
-    for (int dx = threadIdx.x; dx < a.net; dx += blockDim.x) {
+    for (int dx = threadIdx.x; dx < a.net_w; dx += blockDim.x) {
         const AxisTap tx = a.tx[dx];
         half4 o;
         if (ty.i0 < 0 || tx.i0 < 0) {
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a)
 
 void launch_preprocess(const PreArgs &a, int batch, hipStream_t s)
 {
-    hipLaunchKernelGGL(preprocess_kernel, dim3(a.net, batch), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(preprocess_kernel, dim3(a.net_h, batch), dim3(256), 0, s, a);
 }
 
 // dst(x, y) = src(sw-1-x, sh-1-y): the frame get_rotated_image() exposes.
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void conv0_kernel(Conv0Args a)
     constexpr int MT = 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane >> 4, r = lane & 15;
-    const int Ho = a.net >> 1, HWo = Ho * Ho;
+    const int Ho = a.net_h >> 1, Wo = a.net_w >> 1, HWo = Ho * Wo;
     const int M = a.batch * HWo;
     const int tile0 = (blockIdx.x * 4 + wave) * MT;
     const half8 *wp = reinterpret_cast<const half8 *>(a.w) + lane;
@@ -131,8 +131,8 @@ __global__ __launch_bounds__(256) void conv0_kernel(Conv0Args a)
         const int m = (tile0 + mt) * 16 + r;
         const bool mv = m < M;
         const int mm = mv ? m : 0;
-        const int b = mm / HWo, rem = mm - b * HWo, oy = rem / Ho, ox = rem - oy * Ho;
-        const half_t *xb = a.x + (size_t)b * a.net * a.net * 4;
+        const int b = mm / HWo, rem = mm - b * HWo, oy = rem / Wo, ox = rem - oy * Wo;
+        const half_t *xb = a.x + (size_t)b * a.net_h * a.net_w * 4;
         const int ix0 = ox * 2 - 1 + 2 * (g & 1);       // first pixel of this lane's tap pair
         half8 bf[2];
 #pragma unroll
@@ -140,9 +140,9 @@ __global__ __launch_bounds__(256) void conv0_kernel(Conv0Args a)
             const int kh = 2 * s + (g >> 1);
             const int iy = oy * 2 - 1 + kh;
             half4 lo = z4, hi = z4;
-            if (mv && kh < 3 && (unsigned)iy < (unsigned)a.net) {
-                const half_t *row = xb + (size_t)iy * a.net * 4;
-                if ((unsigned)ix0 < (unsigned)a.net) lo = *reinterpret_cast<const half4 *>(row + (size_t)ix0 * 4);
+            if (mv && kh < 3 && (unsigned)iy < (unsigned)a.net_h) {
+                const half_t *row = xb + (size_t)iy * a.net_w * 4;
+                if ((unsigned)ix0 < (unsigned)a.net_w) lo = *reinterpret_cast<const half4 *>(row + (size_t)ix0 * 4);
                 if ((g & 1) == 0) hi = *reinterpret_cast<const half4 *>(row + (size_t)(ix0 + 1) * 4);   // kw = 1; slot 3 is padding
             }
             bf[s] = (half8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
@@ -161,8 +161,7 @@ __global__ __launch_bounds__(256) void conv0_kernel(Conv0Args a)
 
 void launch_conv0(const Conv0Args &a, hipStream_t s)
 {
-    const int Ho = a.net >> 1;
-    const int tiles = (a.batch * Ho * Ho + 15) / 16;
+    const int tiles = (a.batch * (a.net_h >> 1) * (a.net_w >> 1) + 15) / 16;
     hipLaunchKernelGGL(conv0_kernel, dim3((tiles + 15) / 16), dim3(256), 0, s, a);
 }
 

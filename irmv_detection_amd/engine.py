@@ -90,6 +90,8 @@ class YoloEngine:
     `src_format`: what a source slot holds -- capi.SRC_HWC8 (H x W x 3, default) or a raw 8-bit Bayer frame
     (capi.SRC_BAYER_*8, or the pattern name "RGGB" / "BGGR" / "GRBG" / "GBRG"), demosaiced on the GPU with the Q8
     white-balance `bayer_gains` (R, G, B; 256 = 1.0); irmv_detection_amd.bayer.demosaic is its host reference.
+    `net_size` x `net_height`: the network input's width x height (`net_height=None`: square, net_size x net_size; e.g.
+    640 x 512 for a 1280 x 1024 camera); `net_width` / `net_height` hold the engine's dimensions.
     """
 
     def __init__(self, onnx_file_path: Optional[str], src_image_size: Tuple[int, int] = (1280, 1024),
@@ -103,13 +105,14 @@ class YoloEngine:
                  num_streams: int = 0, point_source: int = capi.POINTS_AUTO, binary_threshold: int = 150,
                  light_min_ratio: float = 0.1, light_max_ratio: float = 0.4, light_max_angle: float = 40.0,
                  armor_center_distances: Sequence[float] = (0.8, 3.2, 3.2, 5.5), warmup: int = 0,
-                 src_format=capi.SRC_HWC8, bayer_gains: Sequence[int] = (256, 256, 256)):
+                 src_format=capi.SRC_HWC8, bayer_gains: Sequence[int] = (256, 256, 256), net_height: Optional[int] = None):
         L = capi.load()
         cfg = capi.EngineCfg()
         L.irmv_engine_cfg_default(C.byref(cfg))
         cfg.device = device
         cfg.src_width, cfg.src_height = int(src_image_size[0]), int(src_image_size[1])
         cfg.net_size = net_size
+        cfg.net_height = 0 if net_height is None else int(net_height)
         cfg.resize_mode, cfg.rotate180, cfg.swap_rb = resize_mode, int(rotate180), int(swap_rb)
         cfg.score_thr, cfg.iou_thr, cfg.max_det, cfg.pre_nms_cap = score_thr, iou_thr, max_det, pre_nms_cap
         cfg.num_slots, cfg.armor_size = num_slots, armor_size
@@ -140,7 +143,12 @@ class YoloEngine:
             capi.check(rc)
         self.src_image_size = (cfg.src_width, cfg.src_height)
         self.src_format = cfg.src_format
-        self.net_size = net_size
+        self.net_size = net_size                 # the width (and, square, the height)
+        self.net_width, self.net_height = net_size, net_height or net_size
+        if hasattr(L, "irmv_engine_net_dims"):                        # (absent only in an older build loaded through IRMV_LIB_PATH)
+            w, h = C.c_int(0), C.c_int(0)
+            capi.check(L.irmv_engine_net_dims(self._h, C.byref(w), C.byref(h)))
+            self.net_width, self.net_height = w.value, h.value
         self.num_slots = num_slots
         self.slot = slot
         self.max_det = max_det
@@ -300,7 +308,7 @@ class YoloEngine:
 
     # ---- stage read-backs for parity tests -----------------------------------------
     def read_input(self, slot: int = 0) -> np.ndarray:
-        out = np.empty((3, self.net_size, self.net_size), np.float32)
+        out = np.empty((3, self.net_height, self.net_width), np.float32)
         capi.check(self._L.irmv_engine_read_input(self._h, slot, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 

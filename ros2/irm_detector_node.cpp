@@ -30,6 +30,8 @@ public:
     p.armor_min_large_center_distance = node_->declare_parameter("armor.min_large_center_distance", 3.2);
     p.armor_max_large_center_distance = node_->declare_parameter("armor.max_large_center_distance", 5.5);
     p.device = int(node_->declare_parameter("device", 0));
+    const auto ns = node_->declare_parameter("net_input_size", std::vector<int64_t>{0, 0});   // {width, height}; {0, 0}: square default
+    if (ns.size() == 2) p.net_input_size = cv::Size(int(ns[0]), int(ns[1]));
     const std::string model = node_->declare_parameter("model_path", std::string("models/yolov7.onnx"));
     const auto k = node_->declare_parameter("camera_matrix", std::vector<double>{957.669211, 0, 345.943891, 0, 969.127115, 284.057302, 0, 0, 1});
     const auto d = node_->declare_parameter("distortion", std::vector<double>{-0.405274, 0.126058, -0.026939, -0.006503, 0.0});
