@@ -319,6 +319,30 @@ int irmv_engine_run_conv_candidate(irmv_engine *e, int op, int tune_count, int c
  * equal its size.  Unlike irmv_engine_read_tap it never recomputes a tensor a step keeps on chip. */
 int irmv_engine_read_tensor(irmv_engine *e, const char *name, int first_slot, int count, void *dst, size_t bytes);
 
+/* ---- per-op test hooks (tests/test_gpu_graph_ops.py) ------------------------
+ * Every op of the engine's graph, of any kind; the non-conv layer ops run one at a time on a slot range. */
+typedef struct irmv_graph_op {
+    int32_t op;                 /* the engine's op index (the `op` of irmv_engine_run_op and of the conv hooks above) */
+    char kind[16];              /* conv conv0 pool dw shuffle front c2f2 c2f32 bneck kpt3 pre demosaic scan nms light */
+    char layer[48];             /* weight layer, or the op's own name (model.9.m, model.N.shuffle, preprocess, ...) */
+    char kname[48];             /* kernel, as irmv_engine_profile names it */
+    irmv_conv_seg s0, s1;       /* inputs (tensor "" = none; the pool's: channels [0, C) of its own tensor) */
+    char out_tensor[32];        /* the op writes channels [out_coff, out_coff + out_C) of this tensor; "" = no activation tensor */
+    int32_t out_coff, out_C;
+    int32_t fused_away;         /* a step runs a fused kernel in its place (read-backs still run it) */
+    int32_t reserved;
+} irmv_graph_op;
+
+/* One record per op of the graph, in step order; *n = their number (records beyond cap are not written). */
+int irmv_engine_ops(irmv_engine *e, irmv_graph_op *ops, int cap, int *n);
+/* Run the engine's own kernel of a conv0, pool, dw or shuffle op on slots [first, first + count), as a step of that
+ * count launches it, and synchronize.  flags: IRMV_RUN_POISON / IRMV_RUN_POISON_ONLY over the op's output channels on
+ * those slots (the pool: channels [C, 4C) of its tensor; [0, C) is its input).  IRMV_ERR_ARG for any other kind. */
+int irmv_engine_run_op(irmv_engine *e, int op, int first_slot, int count, uint32_t flags);
+/* Host only: the channel slab of the SPPF LDS kernel for a launch of `batch` frames of [H][W][4C] (8, 16 or 32), or 0
+ * for the global-memory kernel -- the rule the step's launch follows.  IRMV_ERR_ARG for a shape no engine has. */
+int irmv_sppf_slab(int batch, int H, int W, int C);
+
 /* Run one step eagerly with a HIP event pair around every kernel launch. */
 int irmv_engine_profile(irmv_engine *e, int first_slot, int count, irmv_kernel_stat *stats, int cap, int *n);
 

@@ -94,6 +94,12 @@ class ConvCand(C.Structure):
                 ("forced", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GraphOp(C.Structure):
+    _fields_ = [("op", C.c_int32), ("kind", C.c_char * 16), ("layer", C.c_char * 48), ("kname", C.c_char * 48),
+                ("s0", ConvSeg), ("s1", ConvSeg), ("out_tensor", C.c_char * 32), ("out_coff", C.c_int32), ("out_C", C.c_int32),
+                ("fused_away", C.c_int32), ("reserved", C.c_int32)]
+
+
 DECLINED = 1    # irmv_engine_run_conv_candidate: no kernel runs that candidate
 RUN_POISON, RUN_POISON_ONLY = 1, 2   # ... its flags: NaN over the output it must write first (and launch nothing)
 
@@ -147,6 +153,9 @@ SYMBOLS = [
     ("irmv_engine_conv_candidates", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(ConvCand), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_engine_run_conv_candidate", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]),
     ("irmv_engine_read_tensor", C.c_int, [_P, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    ("irmv_engine_ops", C.c_int, [_P, C.POINTER(GraphOp), C.c_int, C.POINTER(C.c_int)]),
+    ("irmv_engine_run_op", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint32]),
+    ("irmv_sppf_slab", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     ("irmv_engine_profile", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_pnp_create", C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_P)]),
     ("irmv_pnp_destroy", None, [_P]),

@@ -2084,6 +2084,49 @@ static bool launch_c2f32_op(const irmv_engine *e, const Op &op, int first, int c
     return launch_c2f32(op.mode, op.shortcut, a, count, s);
 }
 
+// The kernels of the graph's non-conv layer ops (depthwise, shuffle, model.0.conv, SPPF) on slots [first, first + count):
+// what a step launches for them, and what irmv_engine_run_op runs.
+static void launch_graph_op(irmv_engine *e, const Op &op, int first, int count, hipStream_t s)
+{
+    switch (op.kind) {
+    case OP_DW: {
+        DwArgs a;
+        const Tensor &xt = e->tensors[op.s0.t], &ot = e->tensors[op.out_t];
+        a.x = static_cast<const half_t *>(xt.slot(first)) + op.s0.coff; a.x_ld = xt.C;
+        a.y = static_cast<half_t *>(ot.slot(first)) + op.out_coff; a.y_ld = ot.C;
+        a.w = op.w_packed; a.b = op.bias;
+        a.Hin = op.Hin; a.Win = op.Win; a.Hout = op.Hout; a.Wout = op.Wout; a.C = op.cout; a.stride = op.cfg.stride;
+        launch_dwconv3x3(a, count, s);
+        break;
+    }
+    case OP_SHUF: {
+        ShufArgs a;
+        const Tensor &at = e->tensors[op.s0.t], &bt = e->tensors[op.s1.t], &ot = e->tensors[op.out_t];
+        a.a = static_cast<const half_t *>(at.slot(first)) + op.s0.coff; a.a_ld = at.C;
+        a.b = static_cast<const half_t *>(bt.slot(first)) + op.s1.coff; a.b_ld = bt.C;
+        a.out = static_cast<half_t *>(ot.slot(first)); a.out_ld = ot.C;
+        a.bc = op.s0.C;
+        a.pixels = (size_t)count * op.Hin * op.Win;
+        launch_shuffle_cat(a, s);
+        break;
+    }
+    case OP_CONV0: {
+        Conv0Args a;
+        a.x = static_cast<const half_t *>(e->tensors[op.s0.t].slot(first));
+        a.y = static_cast<half_t *>(e->tensors[op.out_t].slot(first));
+        a.w = e->conv0_w; a.b = e->conv0_b; a.net_w = e->cfg.net_size; a.net_h = e->cfg.net_height; a.batch = count;
+        launch_conv0(a, s);
+        break;
+    }
+    case OP_POOL: {
+        const Tensor &t = e->tensors[op.out_t];
+        launch_sppf_pool(static_cast<half_t *>(t.slot(first)), count, t.H, t.W, t.C / 4, s);
+        break;
+    }
+    default: break;
+    }
+}
+
 // Enqueue a step of kind `kind` on slots [first, first + count), stream s: the launches of e->plans[kind], in order.
 // ev != nullptr (irmv_engine_profile): one event pair per launch, around `reps` repetitions of it (one if it is `once`).
 static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipStream_t s, int reps, std::vector<EvRec> *ev)
@@ -2179,35 +2222,7 @@ static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hip
             if (!launch_kpt3(a, op.cin, count, s)) return fail(IRMV_ERR_ARG, "no fused keypoint-branch kernel for " + op.layer);
             break;
         }
-        case OP_DW: {
-            DwArgs a;
-            const Tensor &xt = e->tensors[op.s0.t], &ot = e->tensors[op.out_t];
-            a.x = static_cast<const half_t *>(xt.slot(first)) + op.s0.coff; a.x_ld = xt.C;
-            a.y = static_cast<half_t *>(ot.slot(first)) + op.out_coff; a.y_ld = ot.C;
-            a.w = op.w_packed; a.b = op.bias;
-            a.Hin = op.Hin; a.Win = op.Win; a.Hout = op.Hout; a.Wout = op.Wout; a.C = op.cout; a.stride = op.cfg.stride;
-            launch_dwconv3x3(a, count, s);
-            break;
-        }
-        case OP_SHUF: {
-            ShufArgs a;
-            const Tensor &at = e->tensors[op.s0.t], &bt = e->tensors[op.s1.t], &ot = e->tensors[op.out_t];
-            a.a = static_cast<const half_t *>(at.slot(first)) + op.s0.coff; a.a_ld = at.C;
-            a.b = static_cast<const half_t *>(bt.slot(first)) + op.s1.coff; a.b_ld = bt.C;
-            a.out = static_cast<half_t *>(ot.slot(first)); a.out_ld = ot.C;
-            a.bc = op.s0.C;
-            a.pixels = (size_t)count * op.Hin * op.Win;
-            launch_shuffle_cat(a, s);
-            break;
-        }
-        case OP_CONV0: {
-            Conv0Args a;
-            a.x = static_cast<const half_t *>(e->tensors[op.s0.t].slot(first));
-            a.y = static_cast<half_t *>(e->tensors[op.out_t].slot(first));
-            a.w = e->conv0_w; a.b = e->conv0_b; a.net_w = net_w; a.net_h = net_h; a.batch = count;
-            launch_conv0(a, s);
-            break;
-        }
+        case OP_DW: case OP_SHUF: case OP_CONV0: case OP_POOL: launch_graph_op(e, op, first, count, s); break;
         case OP_CONV: {
             const unsigned scan = rep == n - 1 ? l.scan : 0u;   // (a profiled launch is repeated: only its last repetition appends candidates)
             if (l.group >= 0) {
@@ -2218,11 +2233,6 @@ static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hip
             fill_conv_args(e, op, first, count, a, l.fused);
             if (scan) scan_args_for(e, op, pa, a);
             if (!run_conv(op, l.cfg_one ? op.cfg_one : op.cfg, a, count, s)) return fail(IRMV_ERR_ARG, std::string("no conv kernel for ") + op.kname + " (" + op.layer + ")");
-            break;
-        }
-        case OP_POOL: {
-            const Tensor &t = e->tensors[op.out_t];
-            launch_sppf_pool(static_cast<half_t *>(t.slot(first)), count, t.H, t.W, t.C / 4, s);
             break;
         }
         case OP_SCAN: launch_scan_decode(pa, count, s); break;
@@ -2851,6 +2861,107 @@ extern "C" int irmv_engine_run_conv_candidate(irmv_engine *e, int op, int tune_c
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(e->stream));
     return IRMV_OK;
+}
+
+// ---- per-op test hooks (tests/test_gpu_graph_ops.py) ---------------------------------
+static const char *op_kind_name(OpKind k)
+{
+    switch (k) {
+    case OP_PRE: return "pre";
+    case OP_CONV0: return "conv0";
+    case OP_CONV: return "conv";
+    case OP_POOL: return "pool";
+    case OP_NMS: return "nms";
+    case OP_LIGHT: return "light";
+    case OP_FRONT: return "front";
+    case OP_C2F2: return "c2f2";
+    case OP_C2F32: return "c2f32";
+    case OP_DW: return "dw";
+    case OP_SHUF: return "shuffle";
+    case OP_SCAN: return "scan";
+    case OP_BNECK: return "bneck";
+    case OP_KPT3: return "kpt3";
+    case OP_DEMOSAIC: return "demosaic";
+    }
+    return "?";
+}
+
+// The activation channels op writes: [*coff, *coff + *C) of tensor *t (-1: none).  The pool writes slices 1..3 of its
+// tensor (slice 0 is its input); the ops that write a whole tensor (preprocess, model.0.conv, shuffle, fused kernels
+// standing for a layer) record no channel count of their own.
+static void op_output(const irmv_engine *e, const Op &op, int *t, int *coff, int *C)
+{
+    *t = op.out_t; *coff = 0; *C = 0;
+    if (op.out_t < 0) return;
+    const Tensor &ot = e->tensors[op.out_t];
+    if (op.kind == OP_POOL) { *coff = ot.C / 4; *C = ot.C - ot.C / 4; return; }
+    *coff = op.out_coff;
+    *C = op.cout > 0 ? op.cout : ot.C - op.out_coff;
+}
+
+extern "C" int irmv_engine_ops(irmv_engine *e, irmv_graph_op *ops, int cap, int *n)
+{
+    if (!e || !n) return fail(IRMV_ERR_ARG, "engine / n is null");
+    auto name = [](char *dst, size_t cap_, const std::string &s) { snprintf(dst, cap_, "%s", s.c_str()); };
+    auto seg = [&](irmv_conv_seg &d, const SegRef &s) {
+        memset(&d, 0, sizeof d);
+        if (s.t < 0) return;
+        name(d.tensor, sizeof d.tensor, e->tensors[s.t].name);
+        d.coff = s.coff; d.C = s.C > 0 ? s.C : e->tensors[s.t].C - s.coff; d.shift = s.shift;
+    };
+    for (size_t i = 0; ops && i < e->ops.size() && (int)i < cap; i++) {
+        const Op &op = e->ops[i];
+        irmv_graph_op &r = ops[i];
+        memset(&r, 0, sizeof r);
+        r.op = (int32_t)i;
+        name(r.kind, sizeof r.kind, op_kind_name(op.kind));
+        name(r.layer, sizeof r.layer, op.layer);
+        name(r.kname, sizeof r.kname, op.kname);
+        seg(r.s0, op.kind == OP_POOL ? SegRef{op.out_t, 0, e->tensors[op.out_t].C / 4, 0} : op.s0);
+        seg(r.s1, op.s1);
+        int t, coff, C;
+        op_output(e, op, &t, &coff, &C);
+        if (t >= 0) {
+            name(r.out_tensor, sizeof r.out_tensor, e->tensors[t].name);
+            r.out_coff = coff; r.out_C = C;
+        }
+        r.fused_away = op.fused_away ? 1 : 0;
+    }
+    *n = (int)e->ops.size();
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_run_op(irmv_engine *e, int op, int first, int count, uint32_t flags)
+{
+    TRY(check_range(e, first, count));
+    if (op < 0 || op >= (int)e->ops.size()) return fail(IRMV_ERR_ARG, "no such op");
+    const Op &o = e->ops[op];
+    if (o.kind != OP_CONV0 && o.kind != OP_POOL && o.kind != OP_DW && o.kind != OP_SHUF)
+        return fail(IRMV_ERR_ARG, std::string("run_op runs conv0, pool, dw and shuffle ops, not ") + op_kind_name(o.kind));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));
+    if (flags & (IRMV_RUN_POISON | IRMV_RUN_POISON_ONLY)) {   // all-ones bytes (an fp16 NaN) over what the run must write
+        int t, coff, C;
+        op_output(e, o, &t, &coff, &C);
+        const Tensor &ot = e->tensors[t];
+        if (coff + C > ot.C) return fail(IRMV_ERR_ARG, "output channels out of range");
+        HIP_TRY(hipMemset2DAsync(static_cast<char *>(ot.slot(first)) + (size_t)coff * ot.esize(), (size_t)ot.C * ot.esize(), 0xff,
+                                 (size_t)C * ot.esize(), (size_t)count * ot.H * ot.W, e->stream));
+        if (flags & IRMV_RUN_POISON_ONLY) {
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            return IRMV_OK;
+        }
+    }
+    launch_graph_op(e, o, first, count, e->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return IRMV_OK;
+}
+
+extern "C" int irmv_sppf_slab(int batch, int H, int W, int C)
+{
+    if (batch < 1 || H < 1 || W < 1 || C < 8 || C % 8 != 0) return fail(IRMV_ERR_ARG, "sppf_slab: bad shape");
+    return sppf_slab(batch, H, W, C);
 }
 
 extern "C" int irmv_engine_read_raw(irmv_engine *e, int slot, irmv_raw_dets *out)

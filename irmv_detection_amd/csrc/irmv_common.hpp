@@ -355,6 +355,8 @@ bool launch_conv_direct_multi(const ConvCfg &cfg, const ConvArgs *a, int n, hipS
 
 // SPPF pooling chain: slice 0 (C ch) of [B][H][W][4C] -> slices 1..3 (5x5, 9x9, 13x13 max)
 void launch_sppf_pool(half_t *buf, int batch, int H, int W, int C, hipStream_t s);
+// ... the channel slab of its LDS kernel for that launch (8, 16 or 32), or 0: the global-memory kernel (host only)
+int sppf_slab(int batch, int H, int W, int C);
 
 // ---- post-processing -----------------------------------------------------------
 struct DevDet {           // device/pinned result record
@@ -403,7 +405,8 @@ struct PostArgs {
                               // for another step to find non-zero); every reader clamps it to key_cap
 };
 void launch_nms_pnp(const PostArgs &a, int batch, hipStream_t s);
-constexpr int kScanBlocks = 16;   // workgroups per frame of scan_decode_kernel
+constexpr int kScanBlocks = 16;   // workgroups per frame of scan_decode_kernel (more where a 16th of the keys would not fit kScanLdsMax)
+constexpr size_t kScanLdsMax = 159 * 1024;   // its dynamic LDS: 160 KiB per workgroup on gfx950, less its static variables
 void launch_scan_decode(const PostArgs &a, int batch, hipStream_t s);
 // ---- classical light extraction (k_light.hip) -------------
 constexpr int kLightLdsPoints = 256;         // contours up to this many points are sorted / hulled in LDS

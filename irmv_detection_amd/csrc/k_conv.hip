@@ -1758,7 +1758,7 @@ __global__ __launch_bounds__(256) void sppf_pool_kernel(half_t *buf, int batch, 
     *reinterpret_cast<half8 *>(o + 3 * C) = m13;
 }
 
-void launch_sppf_pool(half_t *buf, int batch, int H, int W, int C, hipStream_t s)
+int sppf_slab(int batch, int H, int W, int C)
 {
     // Channel slab of a workgroup: its four [H*W][CW] fp16 images must fit in LDS.  A slab is read as CW * 2 contiguous
     // bytes per pixel out of a 4 C * 2-byte row, so wide slabs use the memory system better (8 channels = 16 of every
@@ -1769,6 +1769,12 @@ void launch_sppf_pool(half_t *buf, int batch, int H, int W, int C, hipStream_t s
         if (fits(c) && (long)batch * (C / c) >= 768) cw = c;
     for (int c = 8; c <= 32 && !cw; c <<= 1)   // few frames: the narrowest slab = the most workgroups
         if (fits(c)) cw = c;
+    return cw;
+}
+
+void launch_sppf_pool(half_t *buf, int batch, int H, int W, int C, hipStream_t s)
+{
+    const int cw = sppf_slab(batch, H, W, C);
     if (cw) {
         const size_t lds = (size_t)4 * H * W * cw * 2;
         static unsigned long long attr_done = 0;

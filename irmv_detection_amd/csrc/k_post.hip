@@ -174,7 +174,15 @@ __device__ __forceinline__ void decode_boxes(const PostArgs &a, int b, const uns
 // decoded here, four lanes per anchor, exactly as decode_boxes does.
 // ---------------------------------------------------------------------------
 constexpr int kScanU = 2;   // loads in flight per lane: one memory round trip per U * 64 anchors
-static int scan_quads_per_block(int A) { return ((A * 4 + kScanBlocks - 1) / kScanBlocks + 256 * kScanU - 1) / (256 * kScanU) * (256 * kScanU); }
+// A workgroup's range of (anchor, side) quads: a kScanBlocks-th of the frame, unless its keys would not fit in LDS (nets of more
+// than 22 528 anchors, beyond 1024 x 1024, whose launch was refused): then ranges that do, and as many more workgroups.
+static int scan_quads_per_block(int A, int nc)
+{
+    constexpr int step = 256 * kScanU;
+    const int per = ((A * 4 + kScanBlocks - 1) / kScanBlocks + step - 1) / step * step;
+    const int cap = (int)(kScanLdsMax / (nc * sizeof(unsigned long long))) * 4 / step * step;
+    return per < cap ? per : cap;
+}
 
 // The workgroup's keys are collected in LDS (sized for every (anchor, class) pair of its range: it cannot overflow) and
 // leave with ONE global atomic per workgroup: one atomic per candidate on the frame's counter serialises in L2 (measured:
@@ -258,8 +266,9 @@ __global__ __launch_bounds__(256) void scan_decode_kernel(PostArgs a, int per)
 
 void launch_scan_decode(const PostArgs &a, int batch, hipStream_t s)
 {
-    const int per = scan_quads_per_block(a.A);
+    const int per = scan_quads_per_block(a.A, a.nc);
     const size_t lds = (size_t)(per / 4) * a.nc * sizeof(unsigned long long);
+    const int blocks = std::max(kScanBlocks, (a.A * 4 + per - 1) / per);
     static std::mutex mu;
     static size_t raised[64] = {0};
     int dev = 0;
@@ -271,7 +280,7 @@ void launch_scan_decode(const PostArgs &a, int batch, hipStream_t s)
             raised[dev & 63] = lds;
         }
     }
-    hipLaunchKernelGGL(scan_decode_kernel, dim3(kScanBlocks, batch), dim3(256), lds, s, a, per);
+    hipLaunchKernelGGL(scan_decode_kernel, dim3(blocks, batch), dim3(256), lds, s, a, per);
 }
 
 // "IoU(a, b) > thr" as inter > thr * union (same expression as the oracle's iou_gt)

@@ -48,6 +48,36 @@ def test_struct_layouts_match_the_header(tmp_path):
     assert got == exp
 
 
+def test_graph_op_record_matches_the_header(tmp_path):
+    """irmv_graph_op (irmv_engine_ops) against its ctypes mirror, field by field."""
+    fields = [f for f, _ in capi.GraphOp._fields_]
+    src = tmp_path / "go.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "irmv_hip.h"\nint main(void){printf("%zu", sizeof(irmv_graph_op));' +
+                   "".join(f'printf(" %zu", offsetof(irmv_graph_op, {f}));' for f in fields) + "return 0;}\n")
+    exe = tmp_path / "go"
+    subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+    assert got == [C.sizeof(capi.GraphOp)] + [getattr(capi.GraphOp, f).offset for f in fields]
+
+
+def test_sppf_slab_rule(lib):
+    """The SPPF launch's slab rule (host only, no GPU needed): the widest slab whose four [H*W][CW] fp16 images fit in
+    150 KiB of LDS and that still gives >= 768 workgroups, else the narrowest that fits; 0 = the global-memory kernel."""
+    P5 = 128                                                   # model.9.m: 128 channels per slice
+    assert lib.irmv_sppf_slab(1, 20, 20, P5) == 8             # 640 net, one frame
+    assert lib.irmv_sppf_slab(1, 2, 2, P5) == 8               # 64 net
+    assert lib.irmv_sppf_slab(192, 2, 2, P5) == 32            # 192 * 128 / 32 = 768 workgroups
+    assert lib.irmv_sppf_slab(191, 2, 2, P5) == 16
+    assert lib.irmv_sppf_slab(96, 2, 2, P5) == 16             # 96 * 128 / 16 = 768
+    assert lib.irmv_sppf_slab(95, 2, 2, P5) == 8
+    assert lib.irmv_sppf_slab(1, 48, 48, P5) == 8             # 1536 net: 4 * 2304 * 8 * 2 = 147456 B fit
+    assert lib.irmv_sppf_slab(1, 49, 49, P5) == 0             # 1568 net: 153664 B > 150 KiB
+    assert lib.irmv_sppf_slab(1, 64, 64, P5) == 0             # 2048 net
+    assert lib.irmv_sppf_slab(1, 38, 64, P5) == 0             # 2048 x 1216: 2432 pixels
+    assert lib.irmv_sppf_slab(1, 64, 2, P5) == 8 and lib.irmv_sppf_slab(1, 2, 64, P5) == 8
+    assert lib.irmv_sppf_slab(0, 2, 2, P5) == capi.ERR_ARG and lib.irmv_sppf_slab(1, 2, 2, 12) == capi.ERR_ARG
+
+
 def test_defaults_are_the_reference_constants(lib):
     cfg = capi.EngineCfg()
     lib.irmv_engine_cfg_default(C.byref(cfg))

@@ -7,7 +7,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_ref
-from irmv_detection_amd import capi, weights
+from irmv_detection_amd import arch, capi, weights
 from oracle import oracle
 
 
@@ -95,3 +95,86 @@ def test_decode_is_read_tap_arithmetic():
     raw = h.view(np.uint16)
     assert np.array_equal(conv_ref.decode(raw, "input"), h.astype(np.float32))
     assert np.array_equal(conv_ref.decode(raw, "9"), h.astype(np.float32) * np.float32(0.693147180559945309))
+
+
+# ---- the other ops that write activation tensors (tests/test_gpu_graph_ops.py) -----------------------------------------
+@pytest.fixture(scope="module")
+def slayers():
+    return {sp.name: (sp, w, b) for sp, w, b in weights.parse_blob(weights.synthetic_blob(0, backbone=arch.BACKBONE_SHUFFLE))[1]}
+
+
+MAPS = [(1, 1), (2, 2), (3, 3), (13, 11), (64, 2), (2, 64), (7, 5)]
+
+
+S2_MAPS = [(2, 2), (4, 4), (6, 6), (26, 22), (4, 128), (128, 4)]     # the engine's stride-2 inputs are even; outputs odd too
+
+
+@pytest.mark.parametrize("name,H,W", [("model.3.b2.dw", H, W) for H, W in MAPS] + [("model.2.b1.dw", H, W) for H, W in S2_MAPS] +
+                         [("model.7.b2.dw", 26, 22), ("model.8.b2.dw", 13, 11)])
+def test_dwconv_matches_torch(slayers, name, H, W):
+    """Depthwise 3x3 against F.conv2d(groups=C), stride 1 (model.3 / model.8) and 2 (model.2 / model.7), onto odd outputs
+    too (26 x 22 -> 13 x 11)."""
+    sp, w, b = slayers[name]
+    assert sp.groups == sp.cout and w.shape == (sp.cout, 3, 3, 1)
+    rng = np.random.default_rng(H * 100 + W)
+    x = (rng.standard_normal((H, W, sp.cout)) * 2).astype(np.float32)
+    y, acc = conv_ref.dwconv(x, w, b, sp.stride)
+    xt = torch.from_numpy(x.astype(np.float64)).permute(2, 0, 1)[None]
+    wt = torch.from_numpy(w.astype(np.float64)).permute(0, 3, 1, 2)
+    yt = F.conv2d(xt, wt, torch.from_numpy(b.astype(np.float64)), stride=sp.stride, padding=1, groups=sp.cout)[0].permute(1, 2, 0).numpy()
+    assert y.shape == yt.shape == (H // sp.stride, W // sp.stride, sp.cout)
+    assert np.abs(y - yt).max() <= 1e-12 * max(1.0, acc.max())
+    assert (acc >= np.abs(y) - 1e-12).all()
+    # acc is |b| + sum |w| |x| over the taps inside the map: the same op on |x|, |w|, |b|
+    acc_t = F.conv2d(xt.abs(), wt.abs(), torch.from_numpy(np.abs(b).astype(np.float64)), stride=sp.stride, padding=1, groups=sp.cout)
+    assert np.allclose(acc, acc_t[0].permute(1, 2, 0).numpy(), rtol=1e-12, atol=0)
+
+
+@pytest.mark.parametrize("H,W", MAPS + [(20, 20), (20, 16), (49, 49)])
+def test_sppf_matches_chained_max_pools(H, W):
+    rng = np.random.default_rng(H * 1000 + W)
+    a = rng.standard_normal((H, W, 24)).astype(np.float16)      # fp16 values with ties and both zero signs
+    a[rng.random(a.shape) < 0.05] = np.float16(-0.0)
+    p5, p9, p13 = conv_ref.sppf(a)
+    t = torch.from_numpy(a.astype(np.float64)).permute(2, 0, 1)[None]
+    want = []
+    for _ in range(3):
+        t = F.max_pool2d(t, 5, 1, 2)
+        want.append(t[0].permute(1, 2, 0).numpy())
+    for got, exp in zip((p5, p9, p13), want):
+        assert got.shape == (H, W, 24) and np.array_equal(got, exp)
+    # every pool value is one of its window's own values: exact in fp16
+    assert np.array_equal(p13.astype(np.float16).astype(np.float64), p13)
+    if H >= 13 and W >= 13:      # a pixel whose 13x13 window is whole and whose 5x5 is not its own maximum
+        assert (p13 > p9).any() and (p9 > p5).any()
+
+
+@pytest.mark.parametrize("H,W", [(1, 1), (13, 11), (2, 64)])
+def test_shuffle_matches_cat_view_transpose(H, W):
+    rng = np.random.default_rng(H + W)
+    ta = rng.standard_normal((H, W, 96)).astype(np.float16)
+    tb = rng.standard_normal((H, W, 160)).astype(np.float16)
+    a, b = ta[..., 32:96], tb[..., 64:128]                     # slices at offsets, as the op records name them
+    out = conv_ref.shuffle(a, b)
+    x = torch.cat([torch.from_numpy(a.astype(np.float32)), torch.from_numpy(b.astype(np.float32))], dim=-1)   # [H, W, 2 bc]
+    x = x.permute(2, 0, 1)[None]
+    n, c, h, w = x.shape
+    want = x.view(n, 2, c // 2, h, w).transpose(1, 2).reshape(n, c, h, w)[0].permute(1, 2, 0).numpy().astype(np.float16)
+    assert out.dtype == np.float16 and np.array_equal(out.view(np.uint16), want.view(np.uint16))
+
+
+@pytest.mark.parametrize("H,W", [(2, 2), (4, 6), (26, 22), (128, 4), (4, 128)])
+def test_conv0_ignores_the_fourth_input_channel(layers, H, W):
+    """model.0.conv (3x3 stride 2, 3 -> 16, SiLU) on the engine's 4-channel input: the fourth channel, whatever it holds,
+    is no input of the layer.  (The net input is even in both directions; 26 x 22 gives odd outputs.)"""
+    sp, w, b = layers["model.0.conv"]
+    assert (sp.cin, sp.cout, sp.k, sp.stride, sp.act) == (3, 16, 3, 2, 1)
+    rng = np.random.default_rng(H * 7 + W)
+    x4 = rng.random((H, W, 4)).astype(np.float32)
+    x4[..., 3] = 1e6
+    y, acc = conv_ref.conv0(x4, w, b)
+    assert y.shape == (H // 2, W // 2, 16)
+    yt = _torch(x4[..., :3], w, b, 2, 1)
+    assert np.abs(y - yt).max() <= 1e-12 * max(1.0, acc.max())
+    x4[..., 3] = 0
+    assert np.array_equal(conv_ref.conv0(x4, w, b)[0], y)

@@ -38,7 +38,7 @@ wherever it is large against 2^-11 |y| (an error of one fp16 step of the bias pa
 end bounds of tests/test_gpu_engine.py (EMU_TOL = 6e-2 on the taps, HEAD_TOL = 4e-2 on the head) accept such an
 engine: test_per_layer_check_sees_what_the_end_to_end_bounds_miss below.
 
-The 256-slot engine is the slow case (test_slow_...; leave it out with -k "not slow").
+The 256-slot and 2048-net engines are the slow cases (test_slow_...; leave them out with -k "not slow").
 """
 import ctypes as C
 import time
@@ -299,6 +299,7 @@ CONFIGS = [   # (id, net, slots, backbone / dtype)
     ("224x5", 224, 5, "c2f"),
     ("1024x2", 1024, 2, "c2f"),
     ("shufflenet-int8-416x4", 416, 4, "shuffle-int8"),
+    ("64x3", 64, 3, "c2f"),                # the smallest net: P5 2 x 2, P4 4 x 4 -- every pixel a border pixel
 ]
 
 
@@ -310,7 +311,7 @@ def test_every_conv_candidate_is_bitwise_the_choice_and_within_the_bound(blob, c
     with YoloEngine(None, (1280, 1024), weights_blob=b, net_size=net, num_slots=slots) as e:
         load_frames(e, slots)
         res = sweep(e, b, lines.append)
-        if net in (96, 224, 1024):
+        if net in (64, 96, 224, 1024):
             _post_exact(e, net)
     with capsys.disabled():
         print("\n".join(lines))
@@ -328,6 +329,19 @@ def test_slow_every_conv_candidate_on_a_256_slot_engine(blob, capsys):
     with capsys.disabled():
         print("\n".join(lines))
     _report("320x256", res, t0, capsys)
+
+
+def test_slow_every_conv_candidate_on_a_2048_engine(blob, capsys):
+    """The largest net irmv_engine_create accepts: 256 x 256 at stride 8, 86016 anchors; decode / NMS bit-exact too."""
+    t0 = time.time()
+    lines = []
+    with YoloEngine(None, (1280, 1024), weights_blob=blob, net_size=2048, num_slots=1) as e:
+        load_frames(e, 1)
+        res = sweep(e, blob, lines.append)
+        _post_exact(e, 2048)
+    with capsys.disabled():
+        print("\n".join(lines))
+    _report("2048x1", res, t0, capsys)
 
 
 def test_per_layer_check_sees_what_the_end_to_end_bounds_miss(blob, onet, frame0, capsys):

@@ -92,6 +92,8 @@ CONFIGS = [   # (id, W, H, slots, kind)
     ("shufflenet-int8-416x352x4", 416, 352, 4, "shuffle-int8"),
     ("320x640x2", 320, 640, 2, "c2f"),
     ("224x96x2", 224, 96, 2, "c2f"),          # odd tilings: 28 x 12 at stride 8, 14 x 6, 7 x 3
+    ("2048x64x1", 2048, 64, 1, "c2f"),        # extreme aspect ratios: P5 2 x 64 and 64 x 2
+    ("64x2048x1", 64, 2048, 1, "c2f"),
 ]
 
 
@@ -145,7 +147,7 @@ def _crowded_head(rng, A, hot):
     return head
 
 
-@pytest.mark.parametrize("W,H", [(640, 512), (416, 352)])
+@pytest.mark.parametrize("W,H", [(640, 512), (416, 352), (1568, 1568), (2048, 2048), (2048, 1216)])   # up to 86016 anchors
 def test_post_exact_on_engine_and_synthetic_heads(blob, W, H):
     with _engine(blob, W, H, num_slots=2) as e:
         for fi in (0, 1, 2):
