@@ -339,6 +339,39 @@ int irmv_engine_ops(irmv_engine *e, irmv_graph_op *ops, int cap, int *n);
  * count launches it, and synchronize.  flags: IRMV_RUN_POISON / IRMV_RUN_POISON_ONLY over the op's output channels on
  * those slots (the pool: channels [C, 4C) of its tensor; [0, C) is its input).  IRMV_ERR_ARG for any other kind. */
 int irmv_engine_run_op(irmv_engine *e, int op, int first_slot, int count, uint32_t flags);
+/* ---- light-extraction test hook (tests/test_gpu_light_shapes.py) ----------------
+ * What light_extract_kernel saw in one box, stage by stage. */
+#define IRMV_LIGHT_MAX_CONTOURS 1024   /* contours per box; more: armor_valid = -1 */
+#define IRMV_LIGHT_POINTS_CAP 4096     /* contour points per box; more: armor_valid = -1 */
+typedef struct irmv_light_rec {
+    float corners[8];           /* the minimum-area rectangle's four corners, box coordinates, before Light sorts them by y */
+    float top[2], bottom[2], center[2];   /* frame coordinates when ok, box coordinates otherwise */
+    double length;
+    int32_t measured;           /* 0: the contour has fewer than 5 points (or the box got no answer): nothing else is set */
+    int32_t ok;                 /* passed is_light() */
+    int32_t hull_edges;         /* edges of the convex hull; 0: one or two distinct points, or all collinear */
+    int32_t in_lds;             /* measured in LDS (up to lds_points points) or in global memory */
+} irmv_light_rec;
+typedef struct irmv_light_trace {
+    int32_t n_contours;         /* contours kept, at most max_contours */
+    int32_t n_found;            /* as the scan counted them; max_contours + 1 = more than that */
+    int32_t n_points;           /* points of the kept contours, counted past points_cap */
+    int32_t too_large;          /* 1: the box gets armor_valid = -1 */
+    int32_t pool_fit, in_lds;   /* the label image got its slice of the pool; it lived in LDS */
+    int32_t rx, ry, rw, rh;     /* the box as the kernel cut it out of the frame */
+    int32_t max_contours, points_cap, lds_image, lds_points;   /* the kernel's limits: contours, points, LDS label image bytes, LDS contour points */
+    uint64_t label_pool, pool_offset;   /* bytes of the pool; bytes handed to the boxes before this one */
+    int32_t starts[IRMV_LIGHT_MAX_CONTOURS + 1];   /* contour i: points [starts[i], starts[i + 1]), discovery order */
+    int16_t points[IRMV_LIGHT_POINTS_CAP][2];      /* (x, y) in box coordinates, as the border following emitted them */
+    int32_t reserved;
+    irmv_light_rec recs[IRMV_LIGHT_MAX_CONTOURS];  /* per contour, discovery order */
+} irmv_light_trace;
+/* irmv_engine_extract_armors with a record of the kernel's stages: the same launch on the same scratch, plus trace[n].
+ * out receives exactly what irmv_engine_extract_armors gives. */
+int irmv_engine_light_trace(irmv_engine *e, int slot, const float *xyxy, int n, irmv_light_trace *trace, irmv_det *out);
+/* Host only: out = {max_contours, points_cap, lds_image, lds_points} without an engine. */
+int irmv_light_limits(int32_t out[4]);
+
 /* Host only: the channel slab of the SPPF LDS kernel for a launch of `batch` frames of [H][W][4C] (8, 16 or 32), or 0
  * for the global-memory kernel -- the rule the step's launch follows.  IRMV_ERR_ARG for a shape no engine has. */
 int irmv_sppf_slab(int batch, int H, int W, int C);

@@ -100,6 +100,23 @@ class GraphOp(C.Structure):
                 ("fused_away", C.c_int32), ("reserved", C.c_int32)]
 
 
+LIGHT_MAX_CONTOURS, LIGHT_POINTS_CAP = 1024, 4096   # array bounds of irmv_light_trace (the kernel's limits: light_limits())
+
+
+class LightRec(C.Structure):
+    _fields_ = [("corners", C.c_float * 8), ("top", C.c_float * 2), ("bottom", C.c_float * 2), ("center", C.c_float * 2),
+                ("length", C.c_double), ("measured", C.c_int32), ("ok", C.c_int32), ("hull_edges", C.c_int32), ("in_lds", C.c_int32)]
+
+
+class LightTrace(C.Structure):
+    _fields_ = [("n_contours", C.c_int32), ("n_found", C.c_int32), ("n_points", C.c_int32), ("too_large", C.c_int32),
+                ("pool_fit", C.c_int32), ("in_lds", C.c_int32), ("rx", C.c_int32), ("ry", C.c_int32), ("rw", C.c_int32), ("rh", C.c_int32),
+                ("max_contours", C.c_int32), ("points_cap", C.c_int32), ("lds_image", C.c_int32), ("lds_points", C.c_int32),
+                ("label_pool", C.c_uint64), ("pool_offset", C.c_uint64),
+                ("starts", C.c_int32 * (LIGHT_MAX_CONTOURS + 1)), ("points", C.c_int16 * 2 * LIGHT_POINTS_CAP), ("reserved", C.c_int32),
+                ("recs", LightRec * LIGHT_MAX_CONTOURS)]
+
+
 DECLINED = 1    # irmv_engine_run_conv_candidate: no kernel runs that candidate
 RUN_POISON, RUN_POISON_ONLY = 1, 2   # ... its flags: NaN over the output it must write first (and launch nothing)
 
@@ -139,6 +156,8 @@ SYMBOLS = [
     ("irmv_engine_last_detect_ms", C.c_double, [_P]),
     ("irmv_engine_rotated_image", C.c_int, [_P, C.c_int, C.POINTER(C.c_uint8)]),
     ("irmv_engine_extract_armors", C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(Det)]),
+    ("irmv_engine_light_trace", C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(LightTrace), C.POINTER(Det)]),
+    ("irmv_light_limits", C.c_int, [C.POINTER(C.c_int32)]),
     ("irmv_engine_read_input", C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
     ("irmv_engine_read_head", C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
     ("irmv_engine_write_head", C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
@@ -204,6 +223,14 @@ def device_count() -> int:
 
 def device_synchronize(device: int = 0) -> None:
     check(load().irmv_device_synchronize(device))
+
+
+def light_limits() -> dict:
+    """The light extraction's limits as the kernel is compiled (host only): contours and contour points per box (more
+    = no answer), bytes of a label image that stays in LDS, points of a contour that is measured in LDS."""
+    v = (C.c_int32 * 4)()
+    check(load().irmv_light_limits(v))
+    return dict(max_contours=v[0], points_cap=v[1], lds_image=v[2], lds_points=v[3])
 
 
 def numa_parse_cpulist(text: str):

@@ -37,8 +37,6 @@
 
 using namespace irmv;
 
-constexpr int kLightPointsCap = 4096;       // contour points per detection
-
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg)
 {
@@ -281,6 +279,7 @@ struct irmv_engine {
     short *light_points = nullptr, *light_hulls = nullptr;
     float *light_boxes = nullptr;      // explicit boxes of irmv_engine_extract_armors
     DevDet *light_dets_dev = nullptr, *light_dets_host = nullptr;
+    LightTrace *light_trace_dev = nullptr;   // [max_det], allocated by the first irmv_engine_light_trace
     float *boxes = nullptr;
     unsigned long long *keys = nullptr;
     DevDet *dets_dev = nullptr, *dets_host = nullptr, *dets_host_dev = nullptr;       // *_host_dev: device view of the pinned buffer
@@ -2552,7 +2551,14 @@ extern "C" int irmv_engine_rotated_image(irmv_engine *e, int slot, uint8_t *dst)
     return IRMV_OK;
 }
 
-extern "C" int irmv_engine_extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, irmv_det *out)
+static_assert(sizeof(irmv_light_rec) == sizeof(LightTraceRec) && sizeof(irmv_light_trace) == sizeof(LightTrace) &&
+                  offsetof(irmv_light_trace, starts) == offsetof(LightTrace, starts) && offsetof(irmv_light_trace, points) == offsetof(LightTrace, points) &&
+                  offsetof(irmv_light_trace, recs) == offsetof(LightTrace, recs) && offsetof(irmv_light_rec, length) == offsetof(LightTraceRec, length) &&
+                  IRMV_LIGHT_MAX_CONTOURS == kLightMaxContours && IRMV_LIGHT_POINTS_CAP == kLightPointsCap,
+              "irmv_light_trace is LightTrace");
+
+// irmv_engine_extract_armors; trace != nullptr: irmv_engine_light_trace (the kernel also records its stages)
+static int extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, irmv_light_trace *trace, irmv_det *out)
 {
     TRY(check_range(e, slot, 1));
     if (n < 0 || n > e->cfg.max_det || (n > 0 && (!xyxy || !out))) return fail(IRMV_ERR_ARG, "n must be 0..max_det with xyxy/out set");
@@ -2560,6 +2566,8 @@ extern "C" int irmv_engine_extract_armors(irmv_engine *e, int slot, const float 
     HIP_TRY(hipSetDevice(e->cfg.device));
     TRY(irmv_engine_wait(e));
     hipStream_t st = e->stream;
+    if (trace && !e->light_trace_dev) TRY(dev_alloc(e, (void **)&e->light_trace_dev, (size_t)e->cfg.max_det * sizeof(LightTrace)));
+    if (trace) HIP_TRY(hipMemsetAsync(e->light_trace_dev, 0, (size_t)n * sizeof(LightTrace), st));
     TRY(load_frame(e, slot, st));
     HIP_TRY(hipMemcpyAsync(e->light_boxes, xyxy, (size_t)n * 16, hipMemcpyHostToDevice, st));
     LightArgs a = light_args(e, slot);
@@ -2570,8 +2578,10 @@ extern "C" int irmv_engine_extract_armors(irmv_engine *e, int slot, const float 
     a.num_dets = nullptr;
     a.n_boxes = n;
     a.boxes = e->light_boxes;
+    a.trace = trace ? e->light_trace_dev : nullptr;
     launch_light_extract(a, n, 1, st);
     HIP_TRY(hipGetLastError());
+    if (trace) HIP_TRY(hipMemcpyAsync(trace, e->light_trace_dev, (size_t)n * sizeof(LightTrace), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(e->light_dets_host, e->light_dets_dev, (size_t)n * sizeof(DevDet), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (int i = 0; i < n; i++) {
@@ -2589,6 +2599,24 @@ extern "C" int irmv_engine_extract_armors(irmv_engine *e, int slot, const float 
         o.armor_size = d.armor_size;
         o.n_lights = d.n_lights;
     }
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, irmv_det *out)
+{
+    return extract_armors(e, slot, xyxy, n, nullptr, out);
+}
+
+extern "C" int irmv_engine_light_trace(irmv_engine *e, int slot, const float *xyxy, int n, irmv_light_trace *trace, irmv_det *out)
+{
+    if (n > 0 && !trace) return fail(IRMV_ERR_ARG, "trace is null");
+    return extract_armors(e, slot, xyxy, n, trace, out);
+}
+
+extern "C" int irmv_light_limits(int32_t out[4])
+{
+    if (!out) return fail(IRMV_ERR_ARG, "out is null");
+    out[0] = kLightMaxContours; out[1] = kLightPointsCap; out[2] = kLightLdsImage; out[3] = kLightLdsPoints;
     return IRMV_OK;
 }
 

@@ -412,6 +412,26 @@ void launch_scan_decode(const PostArgs &a, int batch, hipStream_t s);
 constexpr int kLightLdsPoints = 256;         // contours up to this many points are sorted / hulled in LDS
 constexpr int kLightLdsImage = 40 * 1024;   // padded label images up to this many bytes live in LDS
 constexpr int kLightMaxContours = 1024;   // contours per ROI; more -> armor_valid = -1 (no answer), never a truncated one
+constexpr int kLightPointsCap = 4096;     // contour points per detection; more -> no answer as well
+
+// What light_extract_kernel saw in one box, stage by stage (test hook irmv_engine_light_trace; the layout of
+// irmv_light_rec / irmv_light_trace in include/irmv_hip.h).  Production launches carry no trace.
+struct LightTraceRec {
+    float corners[8];                        // minAreaRect corners c[0..7], ROI coordinates, before the sort by y
+    float top[2], bottom[2], center[2];      // frame coordinates if ok, else ROI coordinates
+    double length;
+    int32_t measured, ok, hull_edges, in_lds;   // hull_edges: 0 for the degenerate cases (one or two distinct points, collinear)
+};
+struct LightTrace {
+    int32_t n_contours, n_found, n_points, too_large;   // kept (<= cap); as the scan counted them (cap + 1 = more); points counted past the cap
+    int32_t pool_fit, in_lds, rx, ry, rw, rh;
+    int32_t max_contours, points_cap, lds_image, lds_points;
+    uint64_t label_pool, pool_offset;
+    int32_t starts[kLightMaxContours + 1];
+    int16_t points[kLightPointsCap][2];      // as trace_border emitted them, contours in discovery order
+    int32_t pad_;
+    LightTraceRec recs[kLightMaxContours];   // per contour, discovery order; measured = 0: fewer than 5 points (or no answer)
+};
 
 struct LightArgs {
     const uint8_t *frames;   // [B][rows][cols][3] device frames (un-rotated; rotation folded into the fetch)
@@ -432,6 +452,7 @@ struct LightArgs {
     double min_small_cd, max_small_cd, min_large_cd, max_large_cd;
     const PnpConst *pnp;
     int pnp_armor_size;
+    LightTrace *trace;       // [n_boxes] or nullptr (every launch of a step): see LightTrace
 };
 void launch_light_extract(const LightArgs &a, int n_boxes_max, int batch, hipStream_t s);
 

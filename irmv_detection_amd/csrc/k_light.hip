@@ -115,7 +115,8 @@ __device__ __forceinline__ int cross_i(const S *o, const S *a, const S *b)
 // Same arithmetic as oracle/orc_light.c: the sort is a rank sort and every hull edge's bounding rectangle is measured
 // by its own lane, but each number is produced by the same operations, and the winner is the first minimal edge.
 template <typename S>
-__device__ void contour_to_light(S *p, int n, S *scratch, const LightArgs &a, float min_x, float min_y, int lane, LightRec &L)
+__device__ void contour_to_light(S *p, int n, S *scratch, const LightArgs &a, float min_x, float min_y, int lane, LightRec &L,
+                                 LightTraceRec *tr)
 {
     L.ok = 0;
     // 1. sort by (x, y): rank of a point = points with a smaller key, plus equal keys before it
@@ -209,6 +210,10 @@ __device__ void contour_to_light(S *p, int n, S *scratch, const LightArgs &a, fl
         }
     }
     if (lane != 0) return;
+    if (tr) {
+        for (int i = 0; i < 8; i++) tr->corners[i] = c[i];
+        tr->hull_edges = special ? 0 : h;
+    }
     // Light(box): corners sorted by y, top / bottom mid-points, length, width, tilt (armor.hpp:14-27)
     float q[4][2];
     for (int i = 0; i < 4; i++) { q[i][0] = c[2 * i]; q[i][1] = c[2 * i + 1]; }
@@ -241,7 +246,8 @@ __device__ void contour_to_light(S *p, int n, S *scratch, const LightArgs &a, fl
 // events) and a few scalar bit operations reproduce every decision of the scan; only accepted starts are walked
 // (lane 0 follows the border), after which the labels to the right are re-read because they now carry marks.
 template <typename P>
-__device__ void scan_external(P *img, int step, int rw, int rh, int lane, short *pts, int points_cap, int *s_start, int *s_nfound, int *s_toolarge)
+__device__ void scan_external(P *img, int step, int rw, int rh, int lane, short *pts, int points_cap, int *s_start, int *s_nfound, int *s_nfound_raw,
+                              int *s_toolarge)
 {
     int nfound = 0, npts = 0;
     for (int y = 1; y <= rh; y++) {
@@ -308,6 +314,7 @@ __device__ void scan_external(P *img, int step, int rw, int rh, int lane, short 
         const int nf = nfound < kLightMaxContours ? nfound : kLightMaxContours;
         s_start[nf] = npts;
         *s_nfound = nf;
+        *s_nfound_raw = nfound;
         if (nfound > kLightMaxContours || npts > points_cap) *s_toolarge = 1;
     }
 }
@@ -331,7 +338,7 @@ __device__ __forceinline__ unsigned long long label_bytes(const Roi &r)
 
 __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
 {
-    __shared__ int s_nfound, s_toolarge;
+    __shared__ int s_nfound, s_toolarge, s_nfound_raw;
     __shared__ unsigned long long s_prefix;
     __shared__ int s_start[kLightMaxContours + 1];
     __shared__ short s_cpts[4][2 * kLightLdsPoints * 3 + 4];   // per wave: a contour's points + 2n points of sort / hull scratch
@@ -348,7 +355,7 @@ __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
     const int rx = R.rx, ry = R.ry, rw = R.rw, rh = R.rh, step = rw + 2;
     // label image carved from the frame's pool in detection order (deterministic: a full pool drops the
     // lowest-score boxes): offset = sum of the needs of the detections before this one
-    if (tid == 0) { s_prefix = 0ull; s_nfound = 0; s_nlights = 0; }
+    if (tid == 0) { s_prefix = 0ull; s_nfound = 0; s_nfound_raw = 0; s_nlights = 0; }
     __syncthreads();
     unsigned long long mine = 0;
     for (int i = tid; i < j; i += blockDim.x) {
@@ -401,10 +408,26 @@ __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
     // wave-uniform.  A border is followed by lane 0; its marks change labels to the right, so the rest of the chunk is
     // re-examined afterwards.  Same decisions in the same order as the one-pixel-at-a-time scan of oracle/orc_light.c.
     if (!skip && tid < 64) {
-        if (in_lds) scan_external((lds_i8 *)s_img, step, rw, rh, tid, pts, a.points_cap, s_start, &s_nfound, &s_toolarge);
-        else scan_external((glb_i8 *)img, step, rw, rh, tid, pts, a.points_cap, s_start, &s_nfound, &s_toolarge);
+        if (in_lds) scan_external((lds_i8 *)s_img, step, rw, rh, tid, pts, a.points_cap, s_start, &s_nfound, &s_nfound_raw, &s_toolarge);
+        else scan_external((glb_i8 *)img, step, rw, rh, tid, pts, a.points_cap, s_start, &s_nfound, &s_nfound_raw, &s_toolarge);
     }
     __syncthreads();
+    if (a.trace) {
+        // the scan's own counts and the points in the order they were emitted, before step 3 sorts long contours in place
+        LightTrace &T = a.trace[j];
+        const int nkept = s_nfound, npts = skip ? 0 : s_start[nkept];
+        if (tid == 0) {
+            T.n_contours = nkept; T.n_found = s_nfound_raw; T.n_points = npts; T.too_large = s_toolarge;
+            T.pool_fit = fits ? 1 : 0; T.in_lds = in_lds ? 1 : 0;
+            T.rx = rx; T.ry = ry; T.rw = rw; T.rh = rh;
+            T.max_contours = kLightMaxContours; T.points_cap = a.points_cap; T.lds_image = kLightLdsImage; T.lds_points = kLightLdsPoints;
+            T.label_pool = a.label_pool; T.pool_offset = s_prefix;
+        }
+        for (int i = tid; i <= nkept && !skip; i += blockDim.x) T.starts[i] = s_start[i];
+        const int ncopy = min(npts, min(a.points_cap, kLightPointsCap));
+        for (int i = tid; i < 2 * ncopy; i += blockDim.x) (&T.points[0][0])[i] = pts[i];
+        __syncthreads();
+    }
     // 3. a wave per contour: minAreaRect -> Light -> gating.  Contours are visited in discovery order, so the two lights
     // OpenCV's order (last found first) puts in front are the last two a wave keeps; the waves' pairs are merged below.
     const int nfound = s_nfound;
@@ -419,6 +442,7 @@ __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
             const int n = s_start[c + 1] - s_start[c];
             if (n < 5) continue;
             LightRec L;
+            LightTraceRec *tr = a.trace ? &a.trace[j].recs[c] : nullptr;
             if (n <= kLightLdsPoints) {
                 // the sort / hull walks are chains of dependent accesses: contours of ordinary size are measured in LDS
                 using lds_i16 = __attribute__((address_space(3))) short;
@@ -426,10 +450,15 @@ __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
                 const short *gp = pts + 2 * (size_t)s_start[c];
                 for (int i = lane; i < 2 * n; i += 64) lp[i] = gp[i];
                 wave_lds_sync();
-                contour_to_light(lp, n, lp + 2 * kLightLdsPoints, a, min_x, min_y, lane, L);
+                contour_to_light(lp, n, lp + 2 * kLightLdsPoints, a, min_x, min_y, lane, L, tr);
                 wave_lds_sync();
             } else {
-                contour_to_light(pts + 2 * (size_t)s_start[c], n, hulls + (size_t)s_start[c] * 2 * 2, a, min_x, min_y, lane, L);
+                contour_to_light(pts + 2 * (size_t)s_start[c], n, hulls + (size_t)s_start[c] * 2 * 2, a, min_x, min_y, lane, L, tr);
+            }
+            if (tr && lane == 0) {
+                for (int i = 0; i < 2; i++) { tr->top[i] = L.top[i]; tr->bottom[i] = L.bottom[i]; tr->center[i] = L.center[i]; }
+                tr->length = L.length;
+                tr->measured = 1; tr->ok = L.ok; tr->in_lds = n <= kLightLdsPoints ? 1 : 0;
             }
             if (lane == 0 && L.ok) { r1 = r0; c1 = c0; r0 = L; c0 = c; cnt++; }
         }

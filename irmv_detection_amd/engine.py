@@ -233,6 +233,24 @@ class YoloEngine:
             res.append(a)
         return res
 
+    def light_trace(self, bboxes, slot: Optional[int] = None):
+        """extract_armors plus what the kernel saw on the way (test hook irmv_engine_light_trace): -> (raw capi.Det array,
+        capi.LightTrace array), one entry per box."""
+        slot = self.slot if slot is None else slot
+        xy = np.ascontiguousarray(bboxes, np.float32).reshape(-1, 4)
+        out = (capi.Det * max(len(xy), 1))()
+        trace = (capi.LightTrace * max(len(xy), 1))()
+        capi.check(self._L.irmv_engine_light_trace(self._h, slot, xy.ctypes.data_as(C.POINTER(C.c_float)), len(xy), trace, out))
+        return out, trace
+
+    def extract_armors_raw(self, bboxes, slot: Optional[int] = None):
+        """extract_armors as the raw capi.Det records (for byte comparisons)."""
+        slot = self.slot if slot is None else slot
+        xy = np.ascontiguousarray(bboxes, np.float32).reshape(-1, 4)
+        out = (capi.Det * max(len(xy), 1))()
+        capi.check(self._L.irmv_engine_extract_armors(self._h, slot, xy.ctypes.data_as(C.POINTER(C.c_float)), len(xy), out))
+        return out
+
     # 5 x 7 bitmap glyphs of the ArmorClass names (B1..B5, BO, BS, R1..R5, RO, RS, UNKNOWN): the same table as the C++ facade
     # (include/irmv_detection/yolo_engine.hpp), drawn at scale 3 = the size of FONT_HERSHEY_SIMPLEX at scale 1
     _GLYPHS = {"B": (0x1e, 0x11, 0x11, 0x1e, 0x11, 0x11, 0x1e), "R": (0x1e, 0x11, 0x11, 0x1e, 0x14, 0x12, 0x11),

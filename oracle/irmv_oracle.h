@@ -127,6 +127,20 @@ void orc_light_params_default(orc_light_params *P);
 /* external contours (RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) of a binary w x h image, OpenCV order */
 int orc_find_external_contours(const uint8_t *bin, int w, int h, short *pts, int pts_cap, int *offsets, int max_contours);
 void orc_min_area_rect(const short *pts, int n, float corners[8]);
+/* ... with the hull it was taken over (hull_out: room for 2n + 2 points), its size and the chosen edge; each may be NULL */
+void orc_min_area_rect_ex(const short *pts, int n, float corners[8], short *hull_out, int *h_out, int *best_edge);
+/* the stages orc_extract_armor is made of, one call each */
+typedef struct orc_light_rec {
+    float corners[8];                      /* minAreaRect corners, ROI coordinates, before Light sorts them by y */
+    float top[2], bottom[2], center[2];    /* frame coordinates if ok, else ROI coordinates */
+    double length, width, tilt, ratio;
+    int ok, hull_edges;                    /* hull_edges: 0 for one or two distinct points and for collinear contours */
+} orc_light_rec;
+int orc_light_roi(int cols, int rows, const float xyxy[4], int roi[4], float min_xy[2]);
+void orc_light_binary(const uint8_t *img, int cols, const int roi[4], int binary_threshold, uint8_t *bin);
+void orc_contour_light(const short *pts, int n, const orc_light_params *P, float min_x, float min_y, orc_light_rec *L);
+int orc_armor_from_lights(const orc_light_rec *a, const orc_light_rec *b, const orc_light_params *P, int *size, float pts[8],
+                          float center[2], double *cd_out);
 /* IrmDetector::extract_armors for ONE bbox on the (rotated) u8 HWC frame; pts = LB, LT, RT, RB */
 int orc_extract_armor(const uint8_t *img, int cols, int rows, const float xyxy[4], const orc_light_params *P,
                       int *size, float pts[8], float center[2], int *n_lights_out);

@@ -25,6 +25,12 @@ class LightParams(C.Structure):
                 ("armor_max_large_center_distance", C.c_double)]
 
 
+class LightRec(C.Structure):
+    _fields_ = [("corners", C.c_float * 8), ("top", C.c_float * 2), ("bottom", C.c_float * 2), ("center", C.c_float * 2),
+                ("length", C.c_double), ("width", C.c_double), ("tilt", C.c_double), ("ratio", C.c_double),
+                ("ok", C.c_int), ("hull_edges", C.c_int)]
+
+
 def build(force: bool = False) -> str:
     srcs = [os.path.join(_HERE, f) for f in ("orc_net.c", "orc_post.c", "orc_light.c", "irmv_oracle.h", "Makefile")]
     stale = (not os.path.exists(_LIB_PATH)) or any(
@@ -82,6 +88,14 @@ def lib():
         L.orc_find_external_contours.argtypes = [u8p, C.c_int, C.c_int, C.POINTER(C.c_short), C.c_int, i32p, C.c_int]
         L.orc_min_area_rect.argtypes = [C.POINTER(C.c_short), C.c_int, f32p]
         L.orc_extract_armor.argtypes = [u8p, C.c_int, C.c_int, f32p, C.POINTER(LightParams), i32p, f32p, f32p, i32p]
+        L.orc_min_area_rect_ex.argtypes = [C.POINTER(C.c_short), C.c_int, f32p, C.POINTER(C.c_short), i32p, i32p]
+        L.orc_min_area_rect_ex.restype = None
+        L.orc_light_roi.argtypes = [C.c_int, C.c_int, f32p, i32p, f32p]
+        L.orc_light_binary.argtypes = [u8p, C.c_int, i32p, C.c_int, u8p]
+        L.orc_light_binary.restype = None
+        L.orc_contour_light.argtypes = [C.POINTER(C.c_short), C.c_int, C.POINTER(LightParams), C.c_float, C.c_float, C.POINTER(LightRec)]
+        L.orc_contour_light.restype = None
+        L.orc_armor_from_lights.argtypes = [C.POINTER(LightRec), C.POINTER(LightRec), C.POINTER(LightParams), i32p, f32p, f32p, f64p]
         _lib = L
     return _lib
 
@@ -271,14 +285,68 @@ def light_params(**kw) -> "LightParams":
 
 
 def find_external_contours(binary: np.ndarray):
-    """-> list of int16 [n, 2] (x, y) arrays, OpenCV order (last found first)"""
+    """-> list of int16 [n, 2] (x, y) arrays, OpenCV order (last found first).  No cap: every contour, every point."""
     b = np.ascontiguousarray(binary, np.uint8)
     h, w = b.shape
-    cap = 8 * (w + h) * 8 + 4096
+    cap, max_c = 4 * w * h + 64, w * h // 2 + 2      # a border pixel is emitted at most four times; isolated pixels at most every other one
     pts = np.zeros((cap, 2), np.int16)
-    off = np.zeros(4097, np.int32)
-    n = lib().orc_find_external_contours(_p(b, C.c_uint8), w, h, _p(pts, C.c_short), cap, _p(off, C.c_int), 4096)
+    off = np.zeros(max_c + 1, np.int32)
+    n = lib().orc_find_external_contours(_p(b, C.c_uint8), w, h, _p(pts, C.c_short), cap, _p(off, C.c_int), max_c)
     return [pts[off[i]:off[i + 1]].copy() for i in range(n)]
+
+
+def scan_external(binary: np.ndarray):
+    """The same contours as the raster scan finds them: -> (starts int32 [n + 1], points int16 [total, 2]), contours in
+    DISCOVERY order (the reverse of OpenCV's), total = the true point count."""
+    cs = find_external_contours(binary)[::-1]
+    starts = np.zeros(len(cs) + 1, np.int32)
+    starts[1:] = np.cumsum([len(c) for c in cs])
+    return starts, (np.concatenate(cs) if cs else np.zeros((0, 2), np.int16))
+
+
+def light_roi(cols: int, rows: int, xyxy):
+    """-> (ok, (rx, ry, rw, rh), (min_x, min_y) float32): the ROI extract_armors cuts for a bbox"""
+    box = np.ascontiguousarray(xyxy, np.float32).reshape(4)
+    roi, mn = np.zeros(4, np.int32), np.zeros(2, np.float32)
+    ok = lib().orc_light_roi(cols, rows, _p(box, C.c_float), _p(roi, C.c_int), _p(mn, C.c_float))
+    return bool(ok), tuple(int(v) for v in roi), mn
+
+
+def light_binary(img: np.ndarray, roi, binary_threshold: int) -> np.ndarray:
+    """gray + threshold of a ROI (rx, ry, rw, rh) of the HWC u8 frame -> uint8 [rh, rw] of 255 / 0"""
+    img = np.ascontiguousarray(img, np.uint8)
+    r = np.ascontiguousarray(roi, np.int32)
+    out = np.zeros((int(r[3]), int(r[2])), np.uint8)
+    lib().orc_light_binary(_p(img, C.c_uint8), img.shape[1], _p(r, C.c_int), int(binary_threshold), _p(out, C.c_uint8))
+    return out
+
+
+def contour_light(pts: np.ndarray, params=None, min_xy=(0.0, 0.0)) -> "LightRec":
+    """One contour -> minAreaRect -> Light -> is_light(): the record orc_extract_armor gates on"""
+    p = np.ascontiguousarray(pts, np.int16).reshape(-1, 2)
+    P = params or light_params()
+    L = LightRec()
+    lib().orc_contour_light(_p(p, C.c_short), len(p), C.byref(P), C.c_float(min_xy[0]), C.c_float(min_xy[1]), C.byref(L))
+    return L
+
+
+def armor_from_lights(a: "LightRec", b: "LightRec", params=None):
+    """Armor(a, b) + the centre-distance gate; a, b in OpenCV's contour order"""
+    P = params or light_params()
+    size, cd = C.c_int(0), C.c_double(0)
+    pts, center = np.zeros(8, np.float32), np.zeros(2, np.float32)
+    ok = lib().orc_armor_from_lights(C.byref(a), C.byref(b), C.byref(P), C.byref(size), _p(pts, C.c_float), _p(center, C.c_float),
+                                     C.byref(cd))
+    return dict(ok=bool(ok), size=size.value, pts=pts.reshape(4, 2), center=center, cd=cd.value)
+
+
+def min_area_rect_ex(pts: np.ndarray):
+    """-> (corners float32 [4, 2], hull int16 [h, 2] in the order the edges are tried, chosen edge or -1)"""
+    p = np.ascontiguousarray(pts, np.int16).reshape(-1, 2)
+    out, hull = np.zeros(8, np.float32), np.zeros((2 * len(p) + 2, 2), np.int16)
+    h, bi = C.c_int(0), C.c_int(-1)
+    lib().orc_min_area_rect_ex(_p(p, C.c_short), len(p), _p(out, C.c_float), _p(hull, C.c_short), C.byref(h), C.byref(bi))
+    return out.reshape(4, 2), hull[:h.value].copy(), bi.value
 
 
 def min_area_rect(pts: np.ndarray) -> np.ndarray:

@@ -172,11 +172,13 @@ static int convex_hull(const short *pts, int n, short *hull)
 }
 
 /* Minimum-area enclosing rectangle of a point set: corners[8] (4 points, float).  For every hull edge
- * the rectangle aligned with it; the first edge with the smallest area wins. */
-void orc_min_area_rect(const short *pts, int n, float corners[8])
+ * the rectangle aligned with it; the first edge with the smallest area wins.  hull_out (room for 2n + 2 points), h_out,
+ * best_edge may be NULL; *h_out = distinct hull vertices (1, 2 or >= 3), *best_edge = -1 when there is no edge to choose. */
+void orc_min_area_rect_ex(const short *pts, int n, float corners[8], short *hull_out, int *h_out, int *best_edge)
 {
     short *hull = malloc(sizeof(short) * 2 * (size_t)(2 * n + 2));
     const int h = convex_hull(pts, n, hull);
+    int bi = -1;
     if (h == 1) {
         for (int i = 0; i < 4; i++) { corners[2 * i] = hull[0]; corners[2 * i + 1] = hull[1]; }
     } else if (h == 2) {
@@ -201,6 +203,7 @@ void orc_min_area_rect(const short *pts, int n, float corners[8])
             const double area = (smax - smin) * (tmax - tmin);
             if (area < best) {
                 best = area;
+                bi = i;
                 const double sx[4] = { smin, smax, smax, smin }, tx[4] = { tmin, tmin, tmax, tmax };
                 for (int c = 0; c < 4; c++) {
                     bc[2 * c] = a[0] + sx[c] * ux - tx[c] * uy;
@@ -210,13 +213,16 @@ void orc_min_area_rect(const short *pts, int n, float corners[8])
         }
         for (int c = 0; c < 8; c++) corners[c] = (float)bc[c];
     }
+    if (hull_out) memcpy(hull_out, hull, sizeof(short) * 2 * (size_t)h);
+    if (h_out) *h_out = h;
+    if (best_edge) *best_edge = bi;
     free(hull);
 }
 
-/* ---- Light / Armor (reference include/irmv_detection/armor.hpp) ---------------------------- */
-typedef struct { float top[2], bottom[2], center[2]; double length, width, tilt; } light_t;
+void orc_min_area_rect(const short *pts, int n, float corners[8]) { orc_min_area_rect_ex(pts, n, corners, NULL, NULL, NULL); }
 
-static void make_light(const float c[8], light_t *L)
+/* ---- Light / Armor (reference include/irmv_detection/armor.hpp) ---------------------------- */
+static void make_light(const float c[8], orc_light_rec *L)
 {
     float p[4][2];
     for (int i = 0; i < 4; i++) { p[i][0] = c[2 * i]; p[i][1] = c[2 * i + 1]; }
@@ -235,48 +241,32 @@ static void make_light(const float c[8], light_t *L)
     L->tilt = atan2(fabs(dx), fabs(dy)) / 3.14159265358979323846 * 180.0;
 }
 
-/* One bbox -> at most one armor.  out: valid, size (0 small / 1 large), pts[8] = LB, LT, RT, RB
- * (src/pnp_solver.cpp:41-44), center[2].  Returns 1 if an armor was produced. */
-int orc_extract_armor(const uint8_t *img, int cols, int rows, const float xyxy[4], const orc_light_params *P,
-                      int *size, float pts[8], float center[2], int *n_lights_out)
+/* One contour (>= 5 points in extract_armors) -> minAreaRect -> Light -> is_light().  top / bottom / center are in
+ * ROI coordinates unless the light passes the gate: then (min_x, min_y) is added, as extract_armors does. */
+void orc_contour_light(const short *pts, int n, const orc_light_params *P, float min_x, float min_y, orc_light_rec *L)
 {
-    float min_x = xyxy[0] > 0.0f ? xyxy[0] : 0.0f, min_y = xyxy[1] > 0.0f ? xyxy[1] : 0.0f;
-    float max_x = xyxy[2] < (float)cols ? xyxy[2] : (float)cols, max_y = xyxy[3] < (float)rows ? xyxy[3] : (float)rows;
-    if (n_lights_out) *n_lights_out = 0;
-    if (min_x >= max_x || min_y >= max_y) return 0;
-    const int rx = (int)min_x, ry = (int)min_y, rw = (int)(max_x - min_x), rh = (int)(max_y - min_y);   /* cv::Rect(float...) truncates */
-    if (rw <= 0 || rh <= 0) return 0;   /* (the reference would hand an empty Mat to cvtColor and throw) */
-    uint8_t *bin = malloc((size_t)rw * rh);
-    for (int y = 0; y < rh; y++)
-        for (int x = 0; x < rw; x++)
-            bin[(size_t)y * rw + x] = gray_of(img + ((size_t)(ry + y) * cols + rx + x) * 3) > P->binary_threshold ? 255 : 0;
-    const int pts_cap = 4 * rw * rh + 64, max_c = rw * rh / 2 + 2;   /* no cap, as in OpenCV: every border pixel is emitted at most 4 times */
-    short *cp = malloc(sizeof(short) * 2 * (size_t)pts_cap);
-    int *off = malloc(sizeof(int) * (max_c + 1));
-    const int nc = orc_find_external_contours(bin, rw, rh, cp, pts_cap, off, max_c);
-    light_t lights[2];
-    int nl = 0, total_lights = 0;
-    for (int i = 0; i < nc; i++) {
-        const int n = off[i + 1] - off[i];
-        if (n < 5) continue;
-        float c[8];
-        orc_min_area_rect(cp + 2 * off[i], n, c);
-        light_t L;
-        make_light(c, &L);
-        const double ratio = L.width / L.length;
-        if (!(P->light_min_ratio < ratio && ratio < P->light_max_ratio && L.tilt < P->light_max_angle)) continue;
-        L.center[0] += min_x; L.center[1] += min_y; L.top[0] += min_x; L.top[1] += min_y; L.bottom[0] += min_x; L.bottom[1] += min_y;
-        if (nl < 2) lights[nl++] = L;
-        total_lights++;
-    }
-    free(bin); free(cp); free(off);
-    if (n_lights_out) *n_lights_out = total_lights;
-    if (total_lights < 2) return 0;
-    const light_t *l = lights[0].center[0] < lights[1].center[0] ? &lights[0] : &lights[1];
-    const light_t *r = l == &lights[0] ? &lights[1] : &lights[0];
-    const double avg = (lights[0].length + lights[1].length) / 2;
+    int h = 0;
+    memset(L, 0, sizeof *L);
+    orc_min_area_rect_ex(pts, n, L->corners, NULL, &h, NULL);
+    L->hull_edges = h >= 3 ? h : 0;
+    make_light(L->corners, L);
+    L->ratio = L->width / L->length;
+    L->ok = (P->light_min_ratio < L->ratio && L->ratio < P->light_max_ratio && L->tilt < P->light_max_angle) ? 1 : 0;
+    if (!L->ok) return;
+    L->center[0] += min_x; L->center[1] += min_y; L->top[0] += min_x; L->top[1] += min_y; L->bottom[0] += min_x; L->bottom[1] += min_y;
+}
+
+/* Armor(l1, l2) + the centre-distance gate (armor.hpp:58-68, src/irm_detector.cpp:336-348); a, b in OpenCV's contour order.
+ * *cd_out = centre distance / mean length.  Returns 1 if the pair is an armor. */
+int orc_armor_from_lights(const orc_light_rec *a, const orc_light_rec *b, const orc_light_params *P, int *size, float pts[8],
+                          float center[2], double *cd_out)
+{
+    const orc_light_rec *l = a->center[0] < b->center[0] ? a : b;
+    const orc_light_rec *r = l == a ? b : a;
+    const double avg = (a->length + b->length) / 2;
     const double cdx = (double)l->center[0] - r->center[0], cdy = (double)l->center[1] - r->center[1];
     const double cd = sqrt(cdx * cdx + cdy * cdy) / avg;
+    if (cd_out) *cd_out = cd;
     const int large = cd > P->armor_min_large_center_distance;
     if (!large && (P->armor_min_small_center_distance > cd || P->armor_max_small_center_distance < cd)) return 0;
     if (large && (P->armor_min_large_center_distance > cd || P->armor_max_large_center_distance < cd)) return 0;
@@ -285,6 +275,61 @@ int orc_extract_armor(const uint8_t *img, int cols, int rows, const float xyxy[4
     pts[4] = r->top[0]; pts[5] = r->top[1]; pts[6] = r->bottom[0]; pts[7] = r->bottom[1];
     center[0] = (l->center[0] + r->center[0]) / 2; center[1] = (l->center[1] + r->center[1]) / 2;
     return 1;
+}
+
+/* The ROI of a bbox as extract_armors cuts it (src/irm_detector.cpp:299-307): roi = {rx, ry, rw, rh}, min_xy the float
+ * offset added to the lights.  Returns 0 for a box that leaves nothing. */
+int orc_light_roi(int cols, int rows, const float xyxy[4], int roi[4], float min_xy[2])
+{
+    float min_x = xyxy[0] > 0.0f ? xyxy[0] : 0.0f, min_y = xyxy[1] > 0.0f ? xyxy[1] : 0.0f;
+    float max_x = xyxy[2] < (float)cols ? xyxy[2] : (float)cols, max_y = xyxy[3] < (float)rows ? xyxy[3] : (float)rows;
+    roi[0] = roi[1] = roi[2] = roi[3] = 0;
+    min_xy[0] = min_x; min_xy[1] = min_y;
+    if (min_x >= max_x || min_y >= max_y) return 0;
+    roi[0] = (int)min_x; roi[1] = (int)min_y; roi[2] = (int)(max_x - min_x); roi[3] = (int)(max_y - min_y);   /* cv::Rect(float...) truncates */
+    return roi[2] > 0 && roi[3] > 0;   /* (the reference would hand an empty Mat to cvtColor and throw) */
+}
+
+/* gray + threshold of that ROI: bin[rh][rw] = 255 / 0 */
+void orc_light_binary(const uint8_t *img, int cols, const int roi[4], int binary_threshold, uint8_t *bin)
+{
+    const int rx = roi[0], ry = roi[1], rw = roi[2], rh = roi[3];
+    for (int y = 0; y < rh; y++)
+        for (int x = 0; x < rw; x++)
+            bin[(size_t)y * rw + x] = gray_of(img + ((size_t)(ry + y) * cols + rx + x) * 3) > binary_threshold ? 255 : 0;
+}
+
+/* One bbox -> at most one armor.  out: valid, size (0 small / 1 large), pts[8] = LB, LT, RT, RB
+ * (src/pnp_solver.cpp:41-44), center[2].  Returns 1 if an armor was produced. */
+int orc_extract_armor(const uint8_t *img, int cols, int rows, const float xyxy[4], const orc_light_params *P,
+                      int *size, float pts[8], float center[2], int *n_lights_out)
+{
+    int roi[4];
+    float mn[2];
+    if (n_lights_out) *n_lights_out = 0;
+    if (!orc_light_roi(cols, rows, xyxy, roi, mn)) return 0;
+    const int rw = roi[2], rh = roi[3];
+    uint8_t *bin = malloc((size_t)rw * rh);
+    orc_light_binary(img, cols, roi, P->binary_threshold, bin);
+    const int pts_cap = 4 * rw * rh + 64, max_c = rw * rh / 2 + 2;   /* no cap, as in OpenCV: every border pixel is emitted at most 4 times */
+    short *cp = malloc(sizeof(short) * 2 * (size_t)pts_cap);
+    int *off = malloc(sizeof(int) * (max_c + 1));
+    const int nc = orc_find_external_contours(bin, rw, rh, cp, pts_cap, off, max_c);
+    orc_light_rec lights[2];
+    int nl = 0, total_lights = 0;
+    for (int i = 0; i < nc; i++) {
+        const int n = off[i + 1] - off[i];
+        if (n < 5) continue;
+        orc_light_rec L;
+        orc_contour_light(cp + 2 * off[i], n, P, mn[0], mn[1], &L);
+        if (!L.ok) continue;
+        if (nl < 2) lights[nl++] = L;
+        total_lights++;
+    }
+    free(bin); free(cp); free(off);
+    if (n_lights_out) *n_lights_out = total_lights;
+    if (total_lights < 2) return 0;
+    return orc_armor_from_lights(&lights[0], &lights[1], P, size, pts, center, NULL);
 }
 
 void orc_light_params_default(orc_light_params *P)

@@ -23,7 +23,7 @@ def lib():
 def test_every_declared_symbol_is_exported_and_bound(lib):
     text = open(HEADER).read()
     declared = set(re.findall(r"\b(irmv_[a-z0-9_]+)\s*\(", text))
-    assert len(declared) >= 28
+    assert len(declared) >= 30
     bound = {name for name, _, _ in capi.SYMBOLS}
     assert declared == bound, declared ^ bound
     for name in declared:
@@ -58,6 +58,24 @@ def test_graph_op_record_matches_the_header(tmp_path):
     subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
     got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
     assert got == [C.sizeof(capi.GraphOp)] + [getattr(capi.GraphOp, f).offset for f in fields]
+
+
+def test_light_trace_record_matches_the_header(tmp_path, lib):
+    """irmv_light_trace / irmv_light_rec (irmv_engine_light_trace) against their ctypes mirrors, field by field, and the
+    limits the library was compiled with against the header's array bounds."""
+    parts = ['printf("%zu %zu", sizeof(irmv_light_trace), sizeof(irmv_light_rec));']
+    parts += [f'printf(" %zu", offsetof(irmv_light_trace, {f}));' for f, _ in capi.LightTrace._fields_]
+    parts += [f'printf(" %zu", offsetof(irmv_light_rec, {f}));' for f, _ in capi.LightRec._fields_]
+    src = tmp_path / "lt.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "irmv_hip.h"\nint main(void){' + "".join(parts) + "return 0;}\n")
+    exe = tmp_path / "lt"
+    subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+    assert got == ([C.sizeof(capi.LightTrace), C.sizeof(capi.LightRec)] + [getattr(capi.LightTrace, f).offset for f, _ in capi.LightTrace._fields_] +
+                   [getattr(capi.LightRec, f).offset for f, _ in capi.LightRec._fields_])
+    L = capi.light_limits()
+    assert (L["max_contours"], L["points_cap"]) == (capi.LIGHT_MAX_CONTOURS, capi.LIGHT_POINTS_CAP)
+    assert L["lds_image"] > 0 and L["lds_points"] > 0
 
 
 def test_sppf_slab_rule(lib):
