@@ -263,6 +263,10 @@ int irmv_engine_run_post(irmv_engine *e, int first_slot, int count);          /*
  * the next kernel of the same step) with `value`.  The next step must stay inside its buffers and reset the counter; the
  * step after it must be correct again.  IRMV_ERR_ARG for an engine that keeps no counters (IRMV_SPLIT_SCAN=0). */
 int irmv_engine_debug_poke_candidate_counts(irmv_engine *e, int value);
+/* Read-only (tests): the slot's candidate-anchor bitmap of the sparse head, one bit per anchor, ceil(num_anchors / 32) words
+   (all zero between steps).  *sparse = 1 if this engine's steps store candidate head rows only (IRMV_SPARSE_HEAD=0, or a
+   configuration without candidate emission: 0, and no words are kept: *n = 0).  words may be NULL to query *n. */
+int irmv_engine_debug_read_cand_bits(irmv_engine *e, int slot, uint32_t *words, int cap, int *n, int *sparse);
 int irmv_engine_read_tap(irmv_engine *e, int slot, const char *name, float *nhwc, int shape[3]);   /* shape = {H, W, C}: a tensor of
                                                                                  level s is (net_h/s) x (net_w/s) */
 int irmv_engine_read_raw(irmv_engine *e, int slot, irmv_raw_dets *out);

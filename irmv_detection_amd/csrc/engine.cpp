@@ -198,6 +198,7 @@ struct Launch {
     bool fused = false;       // OP_CONV: carries its fuse_next 1x1 in the epilogue
     unsigned scan = 0;        // bit k: member k of the group (a lone conv: bit 0) appends scan candidates from its epilogue
     bool keys_only = false;   // OP_NMS: decodes the boxes of its key lists itself
+    bool sparse = false;      // a Detect box carrier or OP_KPT3 behind its level's class carrier: stores the candidate anchors' head rows only
     bool once = false;        // not repeated under irmv_engine_profile (appends to, consumes or rewrites per-frame lists)
     std::string name, layer;  // irmv_engine_profile's row
     double flops = 0, bytes = 0, launch_bytes = 0;   // per frame; launch_bytes (the weights): once per launch
@@ -235,6 +236,14 @@ struct irmv_engine {
     bool emit_scan = false;   // candidates are emitted by the class-branch conv epilogues (needs split_scan's counters and all three levels fused)
     bool split_scan = true;   // scan + box decode as a multi-workgroup kernel in front of nms_pnp (IRMV_SPLIT_SCAN=0: inside it)
     int *cand_counts = nullptr;
+    // Sparse head: a step stores the head rows of candidate anchors only (the one reader, nms_pnp_kernel, reads no others).
+    // The class carriers set a bit per candidate anchor, box carriers and OP_KPT3 store where it is set, nms_pnp_kernel clears
+    // it again.  Needs emit_scan; IRMV_SPARSE_HEAD=0: every row is stored.  head_stale[slot]: the slot's head in memory is
+    // the sparse one of its last step -- whatever reads it runs the read-back step first (ensure_dense_head).
+    bool sparse_head = false;
+    unsigned int *cand_bits = nullptr;   // [S][cand_words], zero between steps
+    int cand_words = 0;
+    std::vector<char> head_stale;
     int lvl_hw[3] = {0, 0, 0}, lvl_base[3] = {0, 0, 0};
     size_t frame_bytes = 0;       // one HWC source frame (src_dev, rot_dev)
     size_t src_bytes = 0;         // one source slot as the producer writes it (src_host, and raw_dev or src_dev): frame_bytes, or W*H for a Bayer engine
@@ -1144,7 +1153,12 @@ static int build_engine(irmv_engine *e)
     if (e->split_scan) {
         TRY(dev_alloc(e, (void **)&e->cand_counts, (size_t)S * sizeof(int)));
         HIP_TRY(hipMemset(e->cand_counts, 0, (size_t)S * sizeof(int)));
+        // ... and the candidate-anchor bitmap of the sparse head, kept the same way
+        e->cand_words = (e->A + 31) / 32;
+        TRY(dev_alloc(e, (void **)&e->cand_bits, (size_t)S * e->cand_words * sizeof(unsigned int)));
+        HIP_TRY(hipMemset(e->cand_bits, 0, (size_t)S * e->cand_words * sizeof(unsigned int)));
     }
+    e->head_stale.assign((size_t)S, 0);
     TRY(dev_alloc(e, (void **)&e->dets_dev, (size_t)S * c.max_det * sizeof(DevDet)));
     TRY(dev_alloc(e, (void **)&e->fout_dev, (size_t)S * sizeof(DevFrameOut)));
     HIP_TRY(hipMemset(e->dets_dev, 0, (size_t)S * c.max_det * sizeof(DevDet)));
@@ -1781,6 +1795,8 @@ static void finalize_head_fusion(irmv_engine *e)
     for (const Op &op : e->ops) fused += is_cls_final_carrier(op);
     const char *ev = getenv("IRMV_EMIT_SCAN");
     e->emit_scan = e->split_scan && fused == 3 && !(ev && ev[0] == '0');
+    const char *sh = getenv("IRMV_SPARSE_HEAD");
+    e->sparse_head = e->emit_scan && e->cand_bits && !(sh && sh[0] == '0');
 }
 
 // ---- grouped Detect-branch launches (single-frame engines) ---------------------------
@@ -1789,6 +1805,7 @@ static void scan_args_for(const irmv_engine *e, const Op &op, const PostArgs &pa
     a.scan_keys = pa.keys; a.scan_counts = pa.counts; a.scan_thr = pa.logit_thr; a.scan_nc = pa.nc;
     a.scan_key_cap = pa.key_cap;
     a.scan_abase = e->lvl_base[op.level];
+    a.cand_bits = pa.cand_bits; a.cand_words = pa.cand_words;   // (sparse head: the class channels stay on chip)
 }
 
 // one launch for all members of group g on slot `first`; member k appends candidates to pa's key lists if bit k of `scan` is set
@@ -1905,6 +1922,44 @@ static int build_head_groups(irmv_engine *e)
 }
 
 // ---- step plans ------------------------------------------------------------------
+// a box-branch conv that carries its final 1x1 (the 64 DFL channels of the head rows)
+static bool is_box_final_carrier(const Op &op) { return op.fuse_next >= 0 && op.level >= 0 && op.layer.rfind("model.22.cv2.", 0) == 0; }
+
+// Sparse head: the launches that write head rows store only those of candidate anchors, so within a step every class carrier
+// (it finds the candidates) has to run in front of them.  A step is a linear chain; the op list has the box branches first.
+// The box carriers move behind the last class carrier -- they read their own branch's first conv only and nothing in between
+// reads the head, so no bit changes -- and then they and the keypoint launches are marked.  Launches this does not reach
+// keep every row: a grouped launch (single-frame engines: box and class finals of all levels in ONE launch, no order to
+// be had) and the keypoint branch as layers.  The head bytes of a marked launch, and of every emitting class carrier, no longer
+// count as written: what is left is 96 floats per candidate anchor.
+static void sparse_head_plan(const irmv_engine *e, std::vector<Launch> &plan)
+{
+    int last_cls = -1;
+    bool lvl_cls[3] = {false, false, false};
+    for (size_t i = 0; i < plan.size(); i++)
+        if (plan[i].scan && plan[i].group < 0) { last_cls = (int)i; lvl_cls[e->ops[plan[i].op].level] = true; }
+    std::vector<Launch> out, moved;
+    for (size_t i = 0; i < plan.size(); i++) {
+        Launch &l = plan[i];
+        const Op &op = e->ops[l.op];
+        if (l.scan) {   // class carrier(s): the 1x1's output stays on chip
+            if (l.group < 0) l.bytes -= e->ops[op.fuse_next].out_bytes;
+            else for (size_t m = 0; m < e->head_groups[l.group].members.size(); m++)
+                if (l.scan >> m & 1u) l.bytes -= e->ops[e->ops[e->head_groups[l.group].members[m]].fuse_next].out_bytes;
+        }
+        const bool cls_first = op.level >= 0 && op.level < 3 && lvl_cls[op.level];
+        const bool box = l.group < 0 && l.fused && op.kind == OP_CONV && is_box_final_carrier(op) && cls_first;
+        const bool kpt = op.kind == OP_KPT3 && cls_first && (int)i > last_cls;
+        if (box || kpt) {
+            l.sparse = true;
+            l.bytes -= box ? e->ops[op.fuse_next].out_bytes : op.out_bytes;
+        }
+        if (box && (int)i < last_cls) moved.push_back(l); else out.push_back(l);
+        if ((int)i == last_cls) { out.insert(out.end(), moved.begin(), moved.end()); moved.clear(); }
+    }
+    plan.swap(out);
+}
+
 // The one place that decides which ops of e->ops a step of each kind launches, and how.
 static void build_step_plans(irmv_engine *e)
 {
@@ -1954,6 +2009,7 @@ static void build_step_plans(irmv_engine *e)
             }
             e->plans[k].push_back(l);
         }
+        if (step && e->sparse_head) sparse_head_plan(e, e->plans[k]);
     }
 }
 
@@ -2054,6 +2110,8 @@ static PostArgs post_args(const irmv_engine *e, int first)
     p.fout = (e->zero_copy_results ? e->fout_host_dev : e->fout_dev) + first;
     if (p.dbg) p.dbg += (size_t)first * 16;
     p.counts = e->split_scan ? e->cand_counts + first : nullptr;
+    p.cand_bits = e->sparse_head ? e->cand_bits + (size_t)first * e->cand_words : nullptr;
+    p.cand_words = e->cand_words;
     return p;
 }
 
@@ -2218,19 +2276,25 @@ static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hip
             a.w2 = o1.w_packed; a.b2 = o1.bias;
             a.w3 = o2.w_k16; a.b3 = o2.bias;
             a.out = static_cast<float *>(ht.slot(first)) + o2.out_coff; a.out_ld = ht.C;
+            if (l.sparse) { a.cand_bits = pa.cand_bits; a.cand_words = pa.cand_words; a.abase = e->lvl_base[op.level]; }
             if (!launch_kpt3(a, op.cin, count, s)) return fail(IRMV_ERR_ARG, "no fused keypoint-branch kernel for " + op.layer);
             break;
         }
         case OP_DW: case OP_SHUF: case OP_CONV0: case OP_POOL: launch_graph_op(e, op, first, count, s); break;
         case OP_CONV: {
-            const unsigned scan = rep == n - 1 ? l.scan : 0u;   // (a profiled launch is repeated: only its last repetition appends candidates)
+            unsigned scan = rep == n - 1 ? l.scan : 0u;   // (a profiled launch is repeated: only its last repetition appends candidates)
+            // ... with the sparse head the other repetitions still run the step's kernel -- no class store --, behind a threshold
+            // no logit passes: no key, no bit
+            PostArgs pr = pa;
+            if (!scan && l.scan && e->sparse_head) { scan = l.scan; pr.logit_thr = INFINITY; }
             if (l.group >= 0) {
-                if (!launch_head_group(e, e->head_groups[l.group], first, &pa, scan, s)) return fail(IRMV_ERR_ARG, "grouped launch refused: " + l.name);
+                if (!launch_head_group(e, e->head_groups[l.group], first, &pr, scan, s)) return fail(IRMV_ERR_ARG, "grouped launch refused: " + l.name);
                 break;
             }
             ConvArgs a;
             fill_conv_args(e, op, first, count, a, l.fused);
-            if (scan) scan_args_for(e, op, pa, a);
+            if (scan) scan_args_for(e, op, pr, a);
+            if (l.sparse) { a.cand_bits = pa.cand_bits; a.cand_words = pa.cand_words; a.scan_abase = e->lvl_base[op.level]; }
             if (!run_conv(op, l.cfg_one ? op.cfg_one : op.cfg, a, count, s)) return fail(IRMV_ERR_ARG, std::string("no conv kernel for ") + op.kname + " (" + op.layer + ")");
             break;
         }
@@ -2381,6 +2445,7 @@ static int submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_
     }
     if (eager) TRY(enqueue_step(e, kind, f, c, st, 1, nullptr));
     else HIP_TRY(hipGraphLaunch(ge, st));
+    if (e->sparse_head) std::fill(e->head_stale.begin() + f, e->head_stale.begin() + f + c, 1);
     TRY(copy_out(e, f, c, st));
     HIP_TRY(hipEventRecord(g->out, st));
     g->in_flight = true;
@@ -2426,11 +2491,28 @@ extern "C" int irmv_engine_debug_poke_candidate_counts(irmv_engine *e, int value
     return IRMV_OK;
 }
 
+extern "C" int irmv_engine_debug_read_cand_bits(irmv_engine *e, int slot, uint32_t *words, int cap, int *n, int *sparse)
+{
+    TRY(check_range(e, slot, 1));
+    if (!n || !sparse) return fail(IRMV_ERR_ARG, "n / sparse is null");
+    *sparse = e->sparse_head ? 1 : 0;
+    *n = e->sparse_head ? e->cand_words : 0;
+    if (!words || *n == 0) return IRMV_OK;
+    if (cap < *n) return fail(IRMV_ERR_ARG, "read_cand_bits: buffer too small");
+    TRY(irmv_engine_wait(e));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(hipMemcpy(words, e->cand_bits + (size_t)slot * e->cand_words, (size_t)e->cand_words * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    return IRMV_OK;
+}
+
+static int ensure_dense_head(irmv_engine *e, int slot);
+
 extern "C" int irmv_engine_run_post(irmv_engine *e, int first, int count)
 {
     TRY(check_range(e, first, count));
     HIP_TRY(hipSetDevice(e->cfg.device));
     TRY(irmv_engine_wait(e));
+    for (int s = first; s < first + count; s++) TRY(ensure_dense_head(e, s));   // (scan_decode_kernel reads every anchor's class logits)
     hipGraphExec_t ge;
     TRY(get_graph(e, STEP_POST, first, count, false, &ge));
     HIP_TRY(hipGraphLaunch(ge, e->stream));
@@ -2678,6 +2760,17 @@ static int materialize_fused(irmv_engine *e, int slot)
     TRY(irmv_engine_wait(e));
     TRY(enqueue_step(e, STEP_MATERIALIZE, slot, 1, e->stream, 1, nullptr));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    e->head_stale[slot] = 0;   // (the finals and the keypoint layers have written every head row)
+    return IRMV_OK;
+}
+
+// The head of a slot whose last step stored candidate rows only (sparse_head): the read-back step runs the branches' finals
+// and the keypoint layers as layers, which write every row -- the same bits the carriers compute.  A head written through
+// irmv_engine_write_head since that step is not stale and stays as written.
+static int ensure_dense_head(irmv_engine *e, int slot)
+{
+    if (!e->head_stale[slot]) return IRMV_OK;
+    TRY(materialize_fused(e, slot));
     return IRMV_OK;
 }
 
@@ -2696,6 +2789,7 @@ extern "C" int irmv_engine_read_input(irmv_engine *e, int slot, float *chw)
 extern "C" int irmv_engine_read_head(irmv_engine *e, int slot, float *head)
 {
     TRY(check_range(e, slot, 1));
+    TRY(ensure_dense_head(e, slot));
     for (int l = 0; l < 3; l++) {
         std::vector<float> v;
         TRY(read_tensor_f32(e, e->tensors[e->head_t[l]], slot, v));
@@ -2726,6 +2820,7 @@ extern "C" int irmv_engine_write_head(irmv_engine *e, int slot, const float *hea
         }
         HIP_TRY(hipMemcpy(e->tensors[e->head_t[l]].slot(slot), v.data(), v.size() * 4, hipMemcpyHostToDevice));
     }
+    e->head_stale[slot] = 0;
     return IRMV_OK;
 }
 
@@ -2739,6 +2834,7 @@ extern "C" int irmv_engine_read_tap(irmv_engine *e, int slot, const char *name, 
     shape[0] = t.H; shape[1] = t.W; shape[2] = t.C;
     if (!nhwc) return IRMV_OK;
     if (e->lazy_tensors.count(t.name)) TRY(materialize_fused(e, slot));
+    for (int l = 0; l < 3; l++) if (it->second == e->head_t[l]) TRY(ensure_dense_head(e, slot));
     std::vector<float> v;
     TRY(read_tensor_f32(e, t, slot, v));
     memcpy(nhwc, v.data(), v.size() * 4);
@@ -2756,6 +2852,8 @@ extern "C" int irmv_engine_read_tensor(irmv_engine *e, const char *name, int fir
     const size_t need = t.slot_elems * t.esize() * count;
     if (!dst || bytes != need) return fail(IRMV_ERR_ARG, "read_tensor: buffer size does not match the slot range");
     TRY(irmv_engine_wait(e));
+    for (int l = 0; l < 3; l++)
+        if (it->second == e->head_t[l]) for (int s = first; s < first + count; s++) TRY(ensure_dense_head(e, s));
     HIP_TRY(hipMemcpy(dst, t.slot(first), need, hipMemcpyDeviceToHost));
     return IRMV_OK;
 }
@@ -3024,6 +3122,7 @@ extern "C" int irmv_engine_profile(irmv_engine *e, int first, int count, irmv_ke
     const StepKind kind = count == 1 ? STEP_ONE : STEP_BATCH;
     std::vector<EvRec> ev;   // (one per launch of the plan, in its order)
     TRY(enqueue_step(e, kind, first, count, e->stream, kProfileRepeat, &ev));
+    if (e->sparse_head) std::fill(e->head_stale.begin() + first, e->head_stale.begin() + first + count, 1);
     TRY(copy_out(e, first, count));
     HIP_TRY(hipStreamSynchronize(e->stream));
     for (size_t i = 0; i < ev.size(); i++) {

@@ -269,6 +269,8 @@ struct Kpt3Args {
     const float *b3;      // (not scaled: the final has no activation)
     float *out;           // head records [B][H * W][out_ld], offset to the keypoint channels
     int out_ld;
+    const unsigned int *cand_bits;   // sparse head: [B][cand_words] candidate-anchor bitmap, rows of other anchors are not stored; nullptr = all rows
+    int cand_words, abase;           // abase: first anchor index of this level
 };
 bool kpt3_eligible(int cin);
 bool launch_kpt3(const Kpt3Args &a, int cin, int batch, hipStream_t s);
@@ -301,6 +303,12 @@ struct ConvArgs {
     int *scan_counts;                // [B]
     float scan_thr;
     int scan_nc, scan_abase, scan_key_cap;   // classes; first anchor index of this level; list capacity (= A * nc)
+    // Sparse head (LDS 3x3 kernel, N2 > 0): the frame's candidate-anchor bitmap, one bit per anchor.  nullptr = every head row
+    // is stored.  With scan_keys (class carrier): a candidate's anchor bit is set next to its key and the class channels are
+    // not stored at all (the score travels in the key).  Without (box carrier, launched behind its level's class carrier):
+    // a row is stored only where the anchor's bit is set; scan_abase is then the level's anchor base here too.
+    unsigned int *cand_bits;         // [B][cand_words]
+    int cand_words;
 };
 
 // several independent layers in one launch (k_conv.hip conv3x3_lds_multi / conv_mfma_multi)
@@ -403,6 +411,8 @@ struct PostArgs {
     int *counts;              // [B] candidates appended by scan_decode_kernel; nullptr: nms_pnp_kernel scans the head itself.
                               // Zero at engine creation; nms_pnp_kernel reads its frame's count and resets it (no memset node, nothing
                               // for another step to find non-zero); every reader clamps it to key_cap
+    unsigned int *cand_bits;  // [B][cand_words] candidate-anchor bitmap of the sparse head (ConvArgs::cand_bits), or nullptr: nms_pnp_kernel
+    int cand_words;           // clears its frame's words where it resets the count
 };
 void launch_nms_pnp(const PostArgs &a, int batch, hipStream_t s);
 constexpr int kScanBlocks = 16;   // workgroups per frame of scan_decode_kernel (more where a 16th of the keys would not fit kScanLdsMax)

@@ -1043,6 +1043,17 @@ __device__ __forceinline__ void conv3x3_lds_body(const ConvArgs &a, const half_t
             // epilogue arithmetic on whatever their accumulators hold and only their STORES are skipped.
             if (N2 > 0 || mv[mt]) {
                 const size_t m = (size_t)im * HWo + mloc[mt];
+                // sparse head (ConvArgs::cand_bits): does this lane's pixel store its head row?  The bitmap word is requested
+                // here, ahead of the activation arithmetic, by every lane (no branch around the load: a dense launch reads a
+                // word of the 1x1's bias instead and ignores it)
+                bool st2 = mv[mt];
+                if constexpr (N2 > 0) {
+                    const bool gate = a.cand_bits != nullptr && a.scan_keys == nullptr;
+                    const int an = a.scan_abase + mloc[mt];
+                    const unsigned int *cb = gate ? a.cand_bits : reinterpret_cast<const unsigned int *>(a.bias2);   // (uniform base, 32-bit lane offset)
+                    const unsigned int cw = cb[gate ? (unsigned int)(im * a.cand_words + (an >> 5)) : 0u];
+                    st2 = mv[mt] && (a.cand_bits == nullptr || (gate && ((cw >> (an & 31)) & 1u)));
+                }
                 if constexpr (NT % 2 == 0) {   // pair-packed (host guarantees): 8 contiguous channels per lane
                     half8 ov[NT / 2];
 #pragma unroll
@@ -1075,7 +1086,7 @@ __device__ __forceinline__ void conv3x3_lds_body(const ConvArgs &a, const half_t
                             const int co = t2 * 16 + g * 4;
                             const f32x4 b2 = *reinterpret_cast<const f32x4 *>(s_bias2 + co);
                             const f32x4 v2 = (f32x4){c2[0] * kActUnscale + b2[0], c2[1] * kActUnscale + b2[1], c2[2] * kActUnscale + b2[2], c2[3] * kActUnscale + b2[3]};   // (the 1x1's inputs carry the activation scale)
-                            if (mv[mt]) *reinterpret_cast<f32x4 *>(a.out2 + m * a.out2_ld + co) = v2;
+                            if (st2) *reinterpret_cast<f32x4 *>(a.out2 + m * a.out2_ld + co) = v2;
                             if (a.scan_keys) {
                                 // class logits: lane (g, r) holds classes co .. co + 3 of its pixel -- the values the head record just
                                 // received.  Candidates (rare) go to the frame's key list here, so no kernel re-reads the head for them
@@ -1085,6 +1096,7 @@ __device__ __forceinline__ void conv3x3_lds_body(const ConvArgs &a, const half_t
                                 for (int i = 0; i < 4; i++) hit = hit || (mv[mt] && co + i < a.scan_nc && v2[i] > a.scan_thr);
                                 if (hit) {
                                     const int an = a.scan_abase + mloc[mt];
+                                    if (a.cand_bits) atomicOr(&a.cand_bits[(size_t)im * a.cand_words + (an >> 5)], 1u << (an & 31));
 #pragma unroll
                                     for (int i = 0; i < 4; i++) {
                                         if (co + i < a.scan_nc && v2[i] > a.scan_thr) {

@@ -144,6 +144,17 @@ __global__ __launch_bounds__(KNT) __attribute__((amdgpu_waves_per_eu(3))) void k
     };
 
     for (int im = 0; im < nimg; im++) {
+        // sparse head (Kpt3Args::cand_bits): the bitmap words of this lane's three pixels, requested in front of everything this
+        // image still loads (the memory counter is in order) and by every lane (a dense launch reads a bias word and ignores it)
+        unsigned int cw[3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            const int gy = oy0 + bly, gx = ox0 + i * 4 + blx;
+            const int an = a.abase + ((gy < H && gx < W) ? gy * W + gx : 0);
+            const unsigned int *cb = a.cand_bits ? a.cand_bits : reinterpret_cast<const unsigned int *>(a.b3);   // (uniform base, 32-bit lane offset)
+            const unsigned int w = cb[a.cand_bits ? (unsigned int)((img0 + im) * a.cand_words + (an >> 5)) : 0u];
+            cw[i] = a.cand_bits ? (w >> (an & 31)) & 1u : 1u;
+        }
         // ---- stage 1: 3x3, Cin -> 16, SiLU, on the 12 x 12 region: pixel tiles 3 wave .. 3 wave + 2 ----
         f32x4 acc[3] = {b1, b1, b1};
 #pragma unroll
@@ -201,7 +212,7 @@ __global__ __launch_bounds__(KNT) __attribute__((amdgpu_waves_per_eu(3))) void k
             const f32x4 c2 = __builtin_amdgcn_mfma_f32_16x16x16f16(w3f, o, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
             const f32x4 v2 = (f32x4){c2[0] * kActUnscale + b3[0], c2[1] * kActUnscale + b3[1], c2[2] * kActUnscale + b3[2], c2[3] * kActUnscale + b3[3]};
             const int gy = oy0 + ly, gx = ox0 + lx;
-            if (valid && gy < H && gx < W) *reinterpret_cast<f32x4 *>(a.out + ((size_t)((img0 + im) * H + gy) * W + gx) * a.out_ld + g * 4) = v2;
+            if (valid && gy < H && gx < W && cw[i]) *reinterpret_cast<f32x4 *>(a.out + ((size_t)((img0 + im) * H + gy) * W + gx) * a.out_ld + g * 4) = v2;
         }
     }
 }

@@ -426,6 +426,8 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
         }
         __syncthreads();                                           // every lane has read the count
         if (tid == 0) { s_ncand = n; a.counts[b] = 0; }            // the next step of this slot starts from zero
+        if (a.cand_bits)                                           // ... and so does its candidate-anchor bitmap (sparse head)
+            for (int i = tid; i < a.cand_words; i += blockDim.x) a.cand_bits[(size_t)b * a.cand_words + i] = 0u;
     } else {
     // ---- 0. decode.  Scan: class logits of every anchor -> candidate keys + the list of anchors that have one.  Level
     // by level (records of a level are contiguous), four lanes per anchor; the loads of U rounds are issued together.

@@ -370,6 +370,17 @@ class YoloEngine:
         """Fault injection (tests): overwrite every slot's candidate counter."""
         capi.check(self._L.irmv_engine_debug_poke_candidate_counts(self._h, int(value)))
 
+    def debug_cand_bits(self, slot: int = 0):
+        """(sparse, words): whether this engine's steps store candidate head rows only, and the slot's candidate-anchor
+        bitmap (uint32 words, empty where the engine keeps none)."""
+        n, sparse = C.c_int(0), C.c_int(0)
+        capi.check(self._L.irmv_engine_debug_read_cand_bits(self._h, slot, None, 0, C.byref(n), C.byref(sparse)))
+        words = np.zeros(n.value, np.uint32)
+        if n.value:
+            capi.check(self._L.irmv_engine_debug_read_cand_bits(self._h, slot, words.ctypes.data_as(C.POINTER(C.c_uint32)), n.value,
+                                                                 C.byref(n), C.byref(sparse)))
+        return bool(sparse.value), words
+
     def profile(self, first_slot: int = 0, count: Optional[int] = None) -> List[dict]:
         count = self.num_slots - first_slot if count is None else count
         stats = (capi.KernelStat * 256)()
