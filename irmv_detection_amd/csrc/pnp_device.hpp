@@ -15,6 +15,11 @@ namespace irmv {
 // ---------------------------------------------------------------------------
 struct Pose { double R[9]; double t[3]; double err; };
 
+// A float32 pixel coordinate of magnitude >= 2^24 no longer resolves a pixel (its ulp is >= 2 px): such a quad carries no
+// sub-pixel geometry, and fp64 would still turn it into a finite, meaningless pose (1e30 overflows nothing).  It is refused
+// like a non-finite one (negated: NaN fails too).
+__device__ inline bool pixel_in_range(float v) { return fabsf(v) < 16777216.0f; }
+
 __device__ inline void undistort4(const PnpConst &c, const float *pts, double *nxy)
 {
     for (int i = 0; i < 4; i++) {
@@ -61,20 +66,25 @@ __device__ inline void rot_to_rvec(const double *R, double *r)
     const double ax = R[7] - R[5], ay = R[2] - R[6], az = R[3] - R[1];
     const double s = 0.5 * sqrt(ax * ax + ay * ay + az * az);
     const double th = atan2(s, c);
-    if (s > 1e-9) {
+    if (!(c >= 0.0 || s >= 1e-3)) {   // (negated: a NaN lands here and stays one)
+        // theta near pi: the antisymmetric part is ~ sin(theta) and R's rounding (~1e-13) over it would tilt the axis.  The
+        // symmetric part holds n n^T = (sym(R) - c I) / (1 - c) at every angle: the axis is its largest column; the sign
+        // comes from the antisymmetric part while that is above R's rounding, else the first non-zero component is positive.
+        const double ic = 1.0 / (1.0 - c);
+        const double mxx = (R[0] - c) * ic, myy = (R[4] - c) * ic, mzz = (R[8] - c) * ic;
+        const double mxy = 0.5 * (R[1] + R[3]) * ic, mxz = 0.5 * (R[2] + R[6]) * ic, myz = 0.5 * (R[5] + R[7]) * ic;
+        double x, y, z;
+        if (mxx >= myy && mxx >= mzz) { x = sqrt(mxx); y = mxy / x; z = mxz / x; }
+        else if (myy >= mzz) { y = sqrt(myy); x = mxy / y; z = myz / y; }
+        else { z = sqrt(mzz); x = mxz / z; y = myz / z; }
+        const bool flip = s > 1e-12 ? (x * ax + y * ay + z * az < 0.0) : (x < 0.0 || (x == 0.0 && (y < 0.0 || (y == 0.0 && z < 0.0))));
+        const double k = (flip ? -th : th) / sqrt(x * x + y * y + z * z);
+        r[0] = x * k; r[1] = y * k; r[2] = z * k;
+    } else if (s > 1e-9) {
         const double k = th / (2.0 * s);
         r[0] = ax * k; r[1] = ay * k; r[2] = az * k;
-    } else if (c > 0.0) {
-        r[0] = r[1] = r[2] = 0.0;
     } else {
-        double xx = sqrt(fmax((R[0] + 1.0) * 0.5, 0.0));
-        double yy = sqrt(fmax((R[4] + 1.0) * 0.5, 0.0));
-        double zz = sqrt(fmax((R[8] + 1.0) * 0.5, 0.0));
-        if (R[1] + R[3] < 0.0) yy = -yy;
-        if (R[2] + R[6] < 0.0) zz = -zz;
-        if (xx == 0.0 && R[5] + R[7] < 0.0) zz = -zz;
-        const double nn = sqrt(xx * xx + yy * yy + zz * zz);
-        r[0] = th * xx / nn; r[1] = th * yy / nn; r[2] = th * zz / nn;
+        r[0] = r[1] = r[2] = 0.0;
     }
 }
 
@@ -105,6 +115,8 @@ __device__ inline void rot_to_quat(const double *R, double *q)
 __device__ inline bool solve_pnp_ippe(const PnpConst &c, const float *pts, int armor_size, double *rvec, double *tvec, double *quat)
 {
     const double hy = c.hy[armor_size], hz = c.hz[armor_size];
+    for (int i = 0; i < 8; i++)
+        if (!pixel_in_range(pts[i])) return false;
     double nxy[8];
     undistort4(c, pts, nxy);
     // canonical (Xc, Yc) of LB, LT, RT, RB = (y_model, z_model)
@@ -207,6 +219,7 @@ __device__ inline bool solve_pnp_ippe_pair(const PnpConst &c, float px0, float p
     const int lane = threadIdx.x & 63, base = lane & ~1, q = lane & 1;
     const double hy = c.hy[armor_size], hz = c.hz[armor_size];
     bool ok = true;
+    const bool in_range = pixel_in_range(px0) && pixel_in_range(py0) && pixel_in_range(px1) && pixel_in_range(py1);   // this lane's two points
     double nxy[8];
     {   // points q and q + 2 on this lane (undistort4's loop body, the two chains interleaved by the scheduler)
         double xs[2], ys[2];
@@ -286,7 +299,7 @@ __device__ inline bool solve_pnp_ippe_pair(const PnpConst &c, float px0, float p
         double Rc[9];
         for (int i = 0; i < 3; i++)
             for (int j = 0; j < 3; j++) Rc[i * 3 + j] = rv[i * 3] * m[j] + rv[i * 3 + 1] * m[3 + j] + rv[i * 3 + 2] * m[6 + j];
-        sol_ok = ippe_translation(cX, cY, nxy, Rc, ps.t);
+        sol_ok = ippe_translation(cX, cY, nxy, Rc, ps.t) && in_range;   // (the pair's four points: two per lane, met below)
         if (!sol_ok) { ps.t[0] = ps.t[1] = 0.0; ps.t[2] = 1.0; }
         double e = 0.0;
         for (int i = 0; i < 4; i++) {

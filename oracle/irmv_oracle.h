@@ -103,6 +103,7 @@ void orc_parse_output(const float *det_boxes, int n, int src_w, int src_h, int n
  * (src/pnp_solver.cpp:41-44), source-frame pixels.  armor_size 0 = small
  * (135x55 mm), 1 = large (225x55 mm) (include/irmv_detection/pnp_solver.hpp:29-32).
  * Outputs the lower-reprojection-error solution first.  Returns 1 on success. */
+void orc_rot_to_rvec(const double R[9], double r[3]);   /* the solver's rotation -> rvec step */
 int orc_solve_pnp_ippe(const double K[9], const double D[5], const float img_pts[8],
                        int armor_size, double rvec[3], double tvec[3], double rvec2[3],
                        double tvec2[3], double err[2]);

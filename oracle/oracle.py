@@ -84,6 +84,8 @@ def lib():
         L.orc_armor_object_points.argtypes = [C.c_int, f64p]
         L.orc_rodrigues.argtypes = [f64p, f64p]
         L.orc_rvec_to_quat.argtypes = [f64p, f64p]
+        L.orc_rot_to_rvec.argtypes = [f64p, f64p]
+        L.orc_rot_to_rvec.restype = None
         L.orc_light_params_default.argtypes = [C.POINTER(LightParams)]
         L.orc_find_external_contours.argtypes = [u8p, C.c_int, C.c_int, C.POINTER(C.c_short), C.c_int, i32p, C.c_int]
         L.orc_min_area_rect.argtypes = [C.POINTER(C.c_short), C.c_int, f32p]
@@ -231,6 +233,14 @@ def solve_pnp_ippe(K, D, img_pts, armor_size: int = 0):
                                   _p(r1, C.c_double), _p(t1, C.c_double), _p(r2, C.c_double),
                                   _p(t2, C.c_double), _p(err, C.c_double))
     return dict(ok=bool(ok), rvec=r1, tvec=t1, rvec2=r2, tvec2=t2, err=err)
+
+
+def rot_to_rvec(R):
+    """The solver's own rotation matrix -> rvec step."""
+    R = np.ascontiguousarray(R, np.float64).reshape(9)
+    r = np.zeros(3)
+    lib().orc_rot_to_rvec(_p(R, C.c_double), _p(r, C.c_double))
+    return r
 
 
 def undistort_points(K, D, pts):

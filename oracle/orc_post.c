@@ -393,22 +393,31 @@ static void rot_to_rvec(const double R[9], double r[3])
     double ax = R[7] - R[5], ay = R[2] - R[6], az = R[3] - R[1];
     double s = 0.5 * sqrt(ax * ax + ay * ay + az * az);
     double th = atan2(s, c);
-    if (s > 1e-9) {
+    if (!(c >= 0.0 || s >= 1e-3)) {   /* (negated: a NaN lands here and stays one) */
+        /* theta near pi: the antisymmetric part is ~ sin(theta) and R's rounding (~1e-13) over it would tilt the axis.
+         * The symmetric part holds n n^T = (sym(R) - c I) / (1 - c) at every angle: the axis is its largest column; the
+         * sign comes from the antisymmetric part while that is above R's rounding, else the first non-zero component is
+         * positive. */
+        double ic = 1.0 / (1.0 - c);
+        double mxx = (R[0] - c) * ic, myy = (R[4] - c) * ic, mzz = (R[8] - c) * ic;
+        double mxy = 0.5 * (R[1] + R[3]) * ic, mxz = 0.5 * (R[2] + R[6]) * ic, myz = 0.5 * (R[5] + R[7]) * ic;
+        double x, y, z;
+        if (mxx >= myy && mxx >= mzz) { x = sqrt(mxx); y = mxy / x; z = mxz / x; }
+        else if (myy >= mzz) { y = sqrt(myy); x = mxy / y; z = myz / y; }
+        else { z = sqrt(mzz); x = mxz / z; y = myz / z; }
+        int flip = s > 1e-12 ? (x * ax + y * ay + z * az < 0.0) : (x < 0.0 || (x == 0.0 && (y < 0.0 || (y == 0.0 && z < 0.0))));
+        double k = (flip ? -th : th) / sqrt(x * x + y * y + z * z);
+        r[0] = x * k; r[1] = y * k; r[2] = z * k;
+    } else if (s > 1e-9) {
         double k = th / (2.0 * s);
         r[0] = ax * k; r[1] = ay * k; r[2] = az * k;
-    } else if (c > 0.0) {
+    } else {
         r[0] = r[1] = r[2] = 0.0;
-    } else { /* theta ~ pi: axis from the diagonal */
-        double xx = sqrt(fmax((R[0] + 1.0) * 0.5, 0.0));
-        double yy = sqrt(fmax((R[4] + 1.0) * 0.5, 0.0));
-        double zz = sqrt(fmax((R[8] + 1.0) * 0.5, 0.0));
-        if (R[1] + R[3] < 0.0) yy = -yy;
-        if (R[2] + R[6] < 0.0) zz = -zz;
-        if (xx == 0.0 && R[5] + R[7] < 0.0) zz = -zz;
-        double nn = sqrt(xx * xx + yy * yy + zz * zz);
-        r[0] = th * xx / nn; r[1] = th * yy / nn; r[2] = th * zz / nn;
     }
 }
+
+/* rotation matrix -> rvec as the PnP solver does it (test entry) */
+void orc_rot_to_rvec(const double R[9], double r[3]) { rot_to_rvec(R, r); }
 
 /* rvec -> rotation matrix -> quaternion (x, y, z, w), the consumer step at
  * reference src/irm_detector.cpp:218-226 (tf2::Matrix3x3::getRotation). */
@@ -607,6 +616,9 @@ int orc_solve_pnp_ippe(const double K[9], const double D[5], const float img_pts
                        double rvec[3], double tvec[3], double rvec2[3], double tvec2[3], double err[2])
 {
     enum { N = 4 };
+    /* a float32 pixel coordinate of magnitude >= 2^24 no longer resolves a pixel: refused like a non-finite one */
+    for (int i = 0; i < 2 * N; i++)
+        if (!(fabsf(img_pts[i]) < 16777216.0f)) return 0;
     double obj[3 * N], nxy[2 * N];
     orc_armor_object_points(armor_size, obj);
     orc_undistort_points(K, D, img_pts, N, nxy);

@@ -444,7 +444,7 @@ def test_fused_pnp_matches_oracle(eng, frame0):
             assert np.abs(o["rvec"] - a.rvec).max() <= 1e-6 and np.abs(o["tvec"] - a.tvec).max() <= 1e-6
             q = oracle.rvec_to_quat(a.rvec)
             assert min(np.abs(q - a.quat_xyzw).max(), np.abs(q + a.quat_xyzw).max()) <= 1e-6
-    assert n_ok > 0
+    assert n_ok >= 0.98 * len(armors)      # nothing is skipped but a failed solve: at most 2 %
 
 
 def test_batched_step_equals_per_slot_detect(eng):
@@ -531,12 +531,16 @@ def test_pnp_batch_random_quads_vs_oracle():
     base = np.array([[-40, 15], [-40, -15], [40, -15], [40, 15]], np.float32)
     pts = (base[None] * rng.uniform(0.5, 3, (256, 1, 1)) + rng.uniform(150, 500, (256, 1, 2)) + rng.normal(0, 3, (256, 4, 2))).astype(np.float32)
     ok, r, t = solver.solve_batch(pts.reshape(256, 8))
+    skipped = 0
     for i in range(256):
         o = oracle.solve_pnp_ippe(K_REF, D_REF, pts[i], 0)
         assert bool(ok[i]) == o["ok"]
         if o["ok"] and abs(o["err"][0] - o["err"][1]) > 1e-7:
             assert np.abs(r[i] - o["rvec"]).max() <= 1e-6 and np.abs(t[i] - o["tvec"]).max() <= 1e-6
+        else:
+            skipped += 1
     solver.close()
+    assert skipped <= 0.02 * 256, skipped      # failed or ambiguous quads (tests/pnp_ref.py: AMBIGUOUS) are not compared: at most 2 %
 
 
 def test_tile_choice_is_bitwise_neutral(blob, frame0):
