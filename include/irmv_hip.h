@@ -383,6 +383,20 @@ int irmv_sppf_slab(int batch, int H, int W, int C);
 /* Run one step eagerly with a HIP event pair around every kernel launch. */
 int irmv_engine_profile(irmv_engine *e, int first_slot, int count, irmv_kernel_stat *stats, int cap, int *n);
 
+/* ---- LDS residue test hooks (tests/test_gpu_lds_residue.py) ----------------
+ * LDS keeps its contents from one kernel to the next: a kernel that reads a word it has not written gets the previous
+ * workgroup's data.  These two choose and measure that residue on the calling thread's current device; no production
+ * path uses them. */
+#define IRMV_DEBUG_LDS_WORDS 40960      /* words of one workgroup's allocation: 160 KiB, the most a workgroup may have */
+/* Launch several workgroups per CU that each claim IRMV_DEBUG_LDS_WORDS words of LDS and write pattern32 to every one,
+ * then synchronize the device. */
+int irmv_debug_lds_fill(uint32_t pattern32);
+/* The same geometry, writing no LDS: out[4 w] = the number of words of workgroup w that hold pattern32, out[4 w + 1] = the
+ * value it found in word `word` (an unwritten word flowing into an output: the bug class the residue test looks for),
+ * out[4 w + 2], out[4 w + 3] = the HW_ID and XCC_ID registers of the CU it ran on.  *n = workgroups launched; out holds
+ * 4 * cap words (IRMV_ERR_ARG if cap is smaller than that number; out NULL queries *n alone). */
+int irmv_debug_lds_probe(uint32_t pattern32, uint32_t word, uint32_t *out, int cap, int *n);
+
 /* ---- PnPSolver (include/irmv_detection/pnp_solver.hpp:15-23) ------------ */
 typedef struct irmv_pnp irmv_pnp;
 int irmv_pnp_create(int device, const double camera_matrix[9], const double dist_coeffs[5], irmv_pnp **out);

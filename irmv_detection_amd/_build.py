@@ -27,6 +27,7 @@ SOURCES = [
     ("k_post.hip", ["-ffp-contract=off"]),
     ("k_light.hip", ["-ffp-contract=off"]),
     ("k_shuffle.hip", []),
+    ("k_debug.hip", []),
     ("engine.cpp", ["-x", "hip"]),
 ]
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs.  Left to itself the compiler gives kernels without a waves_per_eu

@@ -177,6 +177,8 @@ SYMBOLS = [
     ("irmv_engine_run_op", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint32]),
     ("irmv_sppf_slab", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     ("irmv_engine_profile", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]),
+    ("irmv_debug_lds_fill", C.c_int, [C.c_uint32]),
+    ("irmv_debug_lds_probe", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_pnp_create", C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_P)]),
     ("irmv_pnp_destroy", None, [_P]),
     ("irmv_pnp_solve", C.c_int, [_P, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_double),
@@ -224,6 +226,25 @@ def device_count() -> int:
 
 def device_synchronize(device: int = 0) -> None:
     check(load().irmv_device_synchronize(device))
+
+
+DEBUG_LDS_WORDS = 40960   # IRMV_DEBUG_LDS_WORDS
+
+
+def debug_lds_fill(pattern32: int) -> None:
+    """Test hook: leave pattern32 in every LDS word of every CU of the current device (several 160 KiB workgroups per CU)."""
+    check(load().irmv_debug_lds_fill(pattern32))
+
+
+def debug_lds_probe(pattern32: int, word: int = 0):
+    """Test hook: -> uint32 [workgroups][4]: words that hold pattern32, the value found in `word`, HW_ID, XCC_ID.  The probe
+    writes no LDS."""
+    import numpy as np
+    n = C.c_int(0)
+    check(load().irmv_debug_lds_probe(pattern32, word, None, 0, C.byref(n)))
+    out = np.zeros((n.value, 4), np.uint32)
+    check(load().irmv_debug_lds_probe(pattern32, word, out.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n)))
+    return out
 
 
 def light_limits() -> dict:

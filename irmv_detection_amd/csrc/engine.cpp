@@ -2702,6 +2702,57 @@ extern "C" int irmv_light_limits(int32_t out[4])
     return IRMV_OK;
 }
 
+static int debug_lds_geometry(int *workgroups)
+{
+    int dev = 0, cus = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    *workgroups = debug_lds_workgroups(cus);
+    return IRMV_OK;
+}
+
+extern "C" int irmv_debug_lds_fill(uint32_t pattern32)
+{
+    int wgs = 0;
+    if (int rc = debug_lds_geometry(&wgs)) return rc;
+    uint32_t *d = nullptr, bad = 0;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMalloc(&d, sizeof(uint32_t)));
+    hipError_t e = hipMemset(d, 0, sizeof(uint32_t));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = launch_lds_fill(pattern32, d, wgs, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(&bad, d, sizeof(uint32_t), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIP_TRY(e);
+    if (bad) return fail(IRMV_ERR_HIP, "irmv_debug_lds_fill: a workgroup read back something else than it wrote");
+    return IRMV_OK;
+}
+
+extern "C" int irmv_debug_lds_probe(uint32_t pattern32, uint32_t word, uint32_t *out, int cap, int *n)
+{
+    static_assert(IRMV_DEBUG_LDS_WORDS == kDebugLdsWords, "header and kernel disagree");
+    if (!n) return fail(IRMV_ERR_ARG, "n is null");
+    int wgs = 0;
+    if (int rc = debug_lds_geometry(&wgs)) return rc;
+    *n = wgs;
+    if (!out) return IRMV_OK;
+    if (cap < wgs) return fail(IRMV_ERR_ARG, "cap is smaller than the number of workgroups");
+    if (word >= (uint32_t)kDebugLdsWords) return fail(IRMV_ERR_ARG, "word is outside the workgroup's allocation");
+    uint32_t *d = nullptr;
+    const size_t bytes = (size_t)wgs * 4 * sizeof(uint32_t);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMalloc(&d, bytes));
+    hipError_t e = hipMemset(d, 0, bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = launch_lds_probe(pattern32, word, d, wgs, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIP_TRY(e);
+    return IRMV_OK;
+}
+
 extern "C" int irmv_engine_point_source(const irmv_engine *e)
 {
     if (!e) return -1;

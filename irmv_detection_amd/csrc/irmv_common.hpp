@@ -466,6 +466,12 @@ struct LightArgs {
 };
 void launch_light_extract(const LightArgs &a, int n_boxes_max, int batch, hipStream_t s);
 
+// ---- LDS fill / probe (k_debug.hip; test hooks irmv_debug_lds_fill / irmv_debug_lds_probe) ----------------------------
+constexpr int kDebugLdsWords = 160 * 1024 / 4;   // the largest LDS allocation of one workgroup on gfx950
+int debug_lds_workgroups(int cus);               // several per CU
+hipError_t launch_lds_fill(uint32_t pattern, uint32_t *check, int workgroups, hipStream_t s);   // check: one zeroed word, counts read-back mismatches
+hipError_t launch_lds_probe(uint32_t pattern, uint32_t word, uint32_t *out, int workgroups, hipStream_t s);   // out: [workgroups][4], zeroed
+
 void launch_pnp_only(const PnpConst &c, const float *pts, int n, int armor_size, double *rvec, double *tvec,
                      int32_t *ok, hipStream_t s);
 
