@@ -376,6 +376,42 @@ int irmv_engine_light_trace(irmv_engine *e, int slot, const float *xyxy, int n, 
 /* Host only: out = {max_contours, points_cap, lds_image, lds_points} without an engine. */
 int irmv_light_limits(int32_t out[4]);
 
+/* ---- the front's plan (tests/test_input_geometry.py) -----------------------------------------------------------------
+ * Host only: every geometry decision between a source frame and model.1's output that irmv_engine_create derives from the
+ * configuration -- the letterbox box, whether the fused front kernel (front_fused) runs and on which of its paths.  It is
+ * the function the engine itself builds from -- box, fastx, tile_y, the tile counts, stage_bytes, fx_i0 / fx_step and
+ * upload_kernel are the values the engine launches with; the engine's environment switches (IRMV_FUSED_FRONT, IRMV_FRONT_*)
+ * come on top.  pair_cases and the four tile class counts are NOT consumed by the engine: they restate on the host what
+ * front_kernel derives per tile from those values (its tile_inside test and the column pairing mq / de of a direct tile),
+ * so that a test can say which of the kernel's paths a configuration reaches.  Runs the same checks of the geometry fields as irmv_engine_create (IRMV_ERR_ARG) and touches no GPU. */
+#define IRMV_MAX_FRAME_BYTES 4294967296ull   /* 3 * src_width * src_height: kernels hold byte offsets into a frame in 32 bits */
+enum {
+    IRMV_FRONT_FUSED = 0,        /* the fused kernel runs */
+    IRMV_FRONT_WIDTH_MOD4 = 1,   /* src_width is not a multiple of 4 (the source is read in groups of 4 pixels) */
+    IRMV_FRONT_TAP_RANGE = 2,    /* a tile's source region has a pitch or a row count over 1023 (taps are packed in 10 bits) */
+    IRMV_FRONT_STAGE_LIMIT = 3   /* a tile's source region is over the LDS stage limit */
+};
+typedef struct irmv_front_plan_t {
+    int32_t fused;           /* 1: preprocess + model.0 + model.1 run as front_fused; 0: as three kernels, `reason` says why */
+    int32_t reason;          /* IRMV_FRONT_* */
+    int32_t fastx;           /* bit 0: every column tap is an aligned source pair at 1/2 : 1/2 (exactly 2 : 1); bit 1: direct tiles */
+    int32_t tile_y;          /* model.1 output rows of a tile: 4, or 8 when every tile is direct */
+    int32_t tiles_x, tiles_y;
+    int32_t stage_bytes;     /* dynamic LDS of the fused kernel */
+    int32_t box[4];          /* net-input columns [box[0], box[1]) and rows [box[2], box[3]) that have a source; the rest is padding */
+    int32_t fx_i0, fx_step;  /* fastx: source pair of column box[0], and the pair's step per column (+2, or -2 under rotate180) */
+    int32_t pair_cases;      /* direct tiles: which column pairings the tile columns hit.  bit 0: step +2, pair % 4 == 0;
+                                bit 1: step +2, pair % 4 == 2; bit 2: step -2, pair % 4 == 0; bit 3: step -2, pair % 4 == 2 */
+    int32_t tiles_inside;    /* tiles whose net-input pixels, halo included, all have a source ... */
+    int32_t tiles_x_edge;    /* ... all rows, not all columns (padding or the net input's edge in x only) */
+    int32_t tiles_y_edge;    /* ... all columns, not all rows */
+    int32_t tiles_corner;    /* ... neither */
+    int32_t max_pitch, max_rows;   /* the largest staged source region of a tile, in pixels (0 where src_width % 4 != 0) */
+    int32_t upload_kernel;   /* 1: a single frame's upload may ride the upload kernel (slot bases and sizes are multiples of 16) */
+    int32_t reserved[3];
+} irmv_front_plan_t;
+int irmv_front_plan(const irmv_engine_cfg *cfg, irmv_front_plan_t *out);
+
 /* Host only: the channel slab of the SPPF LDS kernel for a launch of `batch` frames of [H][W][4C] (8, 16 or 32), or 0
  * for the global-memory kernel -- the rule the step's launch follows.  IRMV_ERR_ARG for a shape no engine has. */
 int irmv_sppf_slab(int batch, int H, int W, int C);

@@ -103,6 +103,19 @@ class GraphOp(C.Structure):
 LIGHT_MAX_CONTOURS, LIGHT_POINTS_CAP = 1024, 4096   # array bounds of irmv_light_trace (the kernel's limits: light_limits())
 
 
+FRONT_FUSED, FRONT_WIDTH_MOD4, FRONT_TAP_RANGE, FRONT_STAGE_LIMIT = 0, 1, 2, 3
+MAX_FRAME_BYTES = 1 << 32
+
+
+class FrontPlan(C.Structure):
+    """irmv_front_plan_t (include/irmv_hip.h)."""
+    _fields_ = [("fused", C.c_int32), ("reason", C.c_int32), ("fastx", C.c_int32), ("tile_y", C.c_int32),
+                ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("stage_bytes", C.c_int32), ("box", C.c_int32 * 4),
+                ("fx_i0", C.c_int32), ("fx_step", C.c_int32), ("pair_cases", C.c_int32),
+                ("tiles_inside", C.c_int32), ("tiles_x_edge", C.c_int32), ("tiles_y_edge", C.c_int32), ("tiles_corner", C.c_int32),
+                ("max_pitch", C.c_int32), ("max_rows", C.c_int32), ("upload_kernel", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class LightRec(C.Structure):
     _fields_ = [("corners", C.c_float * 8), ("top", C.c_float * 2), ("bottom", C.c_float * 2), ("center", C.c_float * 2),
                 ("length", C.c_double), ("measured", C.c_int32), ("ok", C.c_int32), ("hull_edges", C.c_int32), ("in_lds", C.c_int32)]
@@ -176,6 +189,7 @@ SYMBOLS = [
     ("irmv_engine_ops", C.c_int, [_P, C.POINTER(GraphOp), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_engine_run_op", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint32]),
     ("irmv_sppf_slab", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("irmv_front_plan", C.c_int, [C.POINTER(EngineCfg), C.POINTER(FrontPlan)]),
     ("irmv_engine_profile", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_debug_lds_fill", C.c_int, [C.c_uint32]),
     ("irmv_debug_lds_probe", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int)]),
@@ -253,6 +267,24 @@ def light_limits() -> dict:
     v = (C.c_int32 * 4)()
     check(load().irmv_light_limits(v))
     return dict(max_contours=v[0], points_cap=v[1], lds_image=v[2], lds_points=v[3])
+
+
+def front_plan(src_size, net_size, net_height=None, resize_mode=RESIZE_STRETCH, rotate180=True, src_format=SRC_HWC8) -> dict:
+    """The front's plan for a configuration (host only, irmv_front_plan): what irmv_engine_create decides from the same
+    fields.  Raises IrmvError where the engine's validation refuses them."""
+    L = load()
+    cfg = EngineCfg()
+    L.irmv_engine_cfg_default(C.byref(cfg))
+    cfg.src_width, cfg.src_height = int(src_size[0]), int(src_size[1])
+    cfg.net_size, cfg.net_height = int(net_size), 0 if net_height is None else int(net_height)
+    cfg.resize_mode, cfg.rotate180 = int(resize_mode), int(bool(rotate180))
+    cfg.src_format = BAYER_FORMATS[src_format.upper()] if isinstance(src_format, str) else int(src_format)
+    p = FrontPlan()
+    check(L.irmv_front_plan(C.byref(cfg), C.byref(p)))
+    d = {f: getattr(p, f) for f, _ in FrontPlan._fields_ if f not in ("box", "reserved")}
+    d["box"] = tuple(p.box)
+    d["fused"], d["upload_kernel"] = bool(p.fused), bool(p.upload_kernel)
+    return d
 
 
 def numa_parse_cpulist(text: str):

@@ -786,13 +786,15 @@ static void axis_taps(std::vector<AxisTap> &out, int dn_total, int sn, int dn, i
 // The fused front kernel (k_front.hip) stages each tile's source region in LDS as 4-byte pixels, read in groups of
 // 4 pixels = three aligned dwords: the width must be a multiple of 4 and the largest region must fit kFrontStageMax
 // bytes of LDS.  Same box arithmetic as the kernel.
-static bool front_fits(const std::vector<AxisTap> &tx, const std::vector<AxisTap> &ty, int sw, int *tiles_x, int *tiles_y, int *stage_bytes)
+static int front_fits(const std::vector<AxisTap> &tx, const std::vector<AxisTap> &ty, int sw, int *tiles_x, int *tiles_y, int *stage_bytes,
+                      int *pitch_out, int *rows_out)   // IRMV_FRONT_FUSED, or the reason it does not fit
 {
     const int W1 = (int)tx.size() / 4, H1 = (int)ty.size() / 4;
     *tiles_x = (W1 + kFrontTileX - 1) / kFrontTileX;
     *tiles_y = (H1 + kFrontTileY - 1) / kFrontTileY;
     *stage_bytes = front_min_stage_bytes();
-    if (sw % 4 != 0) return false;   // 4-pixel groups = 12 source bytes read as three aligned dwords
+    *pitch_out = *rows_out = 0;
+    if (sw % 4 != 0) return IRMV_FRONT_WIDTH_MOD4;   // 4-pixel groups = 12 source bytes read as three aligned dwords
     auto span = [&](const std::vector<AxisTap> &t, int g0, int n, int *lo, int *hi) {
         *lo = 0x7fffffff; *hi = -1;
         for (int i = g0; i < g0 + n; i++) {
@@ -812,10 +814,90 @@ static bool front_fits(const std::vector<AxisTap> &tx, const std::vector<AxisTap
         span(ty, 4 * i * kFrontTileY - 3, 4 * kFrontTileY + 3, &lo, &hi);
         if (hi >= 0) max_rows = std::max(max_rows, hi - lo + 1);
     }
-    if (max_pitch > 1023 || max_rows > 1023) return false;   // region-relative taps are packed in 10 bits
+    *pitch_out = max_pitch; *rows_out = max_rows;
+    if (max_pitch > 1023 || max_rows > 1023) return IRMV_FRONT_TAP_RANGE;   // region-relative taps are packed in 10 bits
     const size_t need = (size_t)max_pitch * max_rows * 4;
     *stage_bytes = std::max((int)std::min<size_t>((need + 255) & ~(size_t)255, 1u << 30), front_min_stage_bytes());
-    return need <= (size_t)kFrontStageMax;
+    return need <= (size_t)kFrontStageMax ? IRMV_FRONT_FUSED : IRMV_FRONT_STAGE_LIMIT;
+}
+
+// The upload kernel moves 16-byte words: the slots' first byte and their size must be multiples of 16.
+static bool upload_aligned(size_t src_bytes, int first, int count)
+{
+    const size_t off = (size_t)first * src_bytes, bytes = src_bytes * count;
+    return off % 16 == 0 && bytes % 16 == 0;
+}
+
+// Size of the resized frame inside the net input.  Letterbox into net_w x net_h: r = min(W / sw, H / sh), the scaled frame
+// rounded (W == H: the square case); a stretch fills the net input.
+static void scaled_size(const irmv_engine_cfg &c, int *nw, int *nh)
+{
+    const int net_w = c.net_size, net_h = c.net_height > 0 ? c.net_height : c.net_size;
+    *nw = net_w; *nh = net_h;
+    if (c.resize_mode != IRMV_RESIZE_LETTERBOX) return;
+    const double r = std::min((double)net_w / c.src_width, (double)net_h / c.src_height);
+    *nw = std::min(net_w, (int)std::floor(c.src_width * r + 0.5));
+    *nh = std::min(net_h, (int)std::floor(c.src_height * r + 0.5));
+}
+
+// Every geometry decision of the network's front, from the configuration alone (no GPU): the letterbox box, the tap
+// tables, whether the fused front kernel fits, its 2 : 1 column / direct / tall-tile path, and whether a single frame's
+// upload can ride the upload kernel.  build_engine takes its geometry from here and irmv_front_plan exports it, so the
+// exported plan is what runs.  `sw`: the engine's environment switches (IRMV_FRONT_FASTX / _DIRECT / _TILE8); all on
+// for the exported plan.
+struct FrontSwitches { bool fastx = true, direct = true, tall = true; };
+
+static void front_plan(const irmv_engine_cfg &c, const FrontSwitches &sw, irmv_front_plan_t *p, std::vector<AxisTap> &tx, std::vector<AxisTap> &ty)
+{
+    const int net_w = c.net_size, net_h = c.net_height > 0 ? c.net_height : c.net_size;
+    memset(p, 0, sizeof *p);
+    // ---- preprocess geometry (parse_output inverse mapping): the scaled frame, centred ----
+    int nw, nh;
+    scaled_size(c, &nw, &nh);
+    const int px = (net_w - nw) / 2, py = (net_h - nh) / 2;
+    axis_taps(tx, net_w, c.src_width, nw, px, c.rotate180 != 0);
+    axis_taps(ty, net_h, c.src_height, nh, py, c.rotate180 != 0);
+    p->reason = front_fits(tx, ty, c.src_width, &p->tiles_x, &p->tiles_y, &p->stage_bytes, &p->max_pitch, &p->max_rows);
+    p->fused = p->reason == IRMV_FRONT_FUSED;
+    p->tile_y = kFrontTileY;
+    p->box[0] = px; p->box[1] = px + nw; p->box[2] = py; p->box[3] = py + nh;
+    {   // columns at exactly 2 : 1 (1280 -> 640): the taps of column px + k are the aligned source pair (m, m + 1) with
+        // m = m0 + step k even, both weights 1/2; step = 2, or -2 under rotate180 (the pair is then listed as (m + 1, m):
+        // with equal weights the blend does not care)
+        const int step = c.rotate180 ? -2 : 2;
+        const int m0 = nw > 0 ? std::min(tx[px].i0, tx[px].i1) : -1;
+        bool fx = nw > 0 && m0 >= 0 && (m0 & 1) == 0;
+        for (int d = px; d < px + nw && fx; d++)
+            fx = std::min(tx[d].i0, tx[d].i1) == m0 + step * (d - px) && std::max(tx[d].i0, tx[d].i1) == m0 + step * (d - px) + 1 && tx[d].w1 == 1024;
+        if (!sw.fastx) fx = false;
+        const bool direct = fx && sw.direct;   // tiles without a padding pixel skip the LDS staging of the source (k_front.hip); bit 1 of FrontArgs::fastx
+        p->fastx = fx ? (direct ? 3 : 1) : 0;
+        // all tiles direct: nothing is staged, and the tile can be twice as tall (k_front.hip)
+        if (fx && direct && p->fused && sw.tall) {
+            p->tile_y = kFrontTileYDirect;
+            p->tiles_y = (net_h / 4 + kFrontTileYDirect - 1) / kFrontTileYDirect;
+            p->stage_bytes = front_min_stage_bytes(kFrontTileYDirect);
+        }
+        p->fx_i0 = fx ? m0 : 0;
+        p->fx_step = step;
+    }
+    // the kernel's tile classes (k_front.hip tile_inside): a tile is inside on an axis when every net-input pixel it
+    // reads on that axis, halo included, has a source
+    const int inw = 4 * kFrontTileX + 3, inh = 4 * p->tile_y + 3;
+    for (int j = 0; j < p->tiles_y; j++)
+        for (int i = 0; i < p->tiles_x; i++) {
+            const int gx0 = 4 * i * kFrontTileX - 3, gy0 = 4 * j * p->tile_y - 3;
+            const bool in_x = gx0 >= std::max(p->box[0], 0) && gx0 + inw <= std::min(p->box[1], net_w);
+            const bool in_y = gy0 >= std::max(p->box[2], 0) && gy0 + inh <= std::min(p->box[3], net_h);
+            (in_x ? (in_y ? p->tiles_inside : p->tiles_y_edge) : (in_y ? p->tiles_x_edge : p->tiles_corner))++;
+            if (j == 0 && (p->fastx & 2)) {   // the direct tiles' column pairing (k_front.hip mq, de, dg0): step sign x (mq & 3)
+                const int mq = p->fx_i0 + p->fx_step * (gx0 - p->box[0]);
+                p->pair_cases |= 1 << ((p->fx_step > 0 ? 0 : 2) + ((mq & 3) == 0 ? 0 : 1));
+            }
+        }
+    // a single frame travels from its pinned slot as a kernel (upload_as_kernel) where the slot is aligned: slot 1 stands for all
+    const size_t src_bytes = (size_t)c.src_width * c.src_height * (c.src_format != IRMV_SRC_HWC8 ? 1 : 3);
+    p->upload_kernel = upload_aligned(src_bytes, 1, 1);
 }
 
 static int autotune_convs(irmv_engine *e);
@@ -876,48 +958,26 @@ static int build_engine(irmv_engine *e)
         for (int i = 0; i < 3; i++) b.gain[i] = c.bayer_gain_q8[i];
     }
 
-    // ---- preprocess geometry (parse_output inverse mapping) ----
-    // letterbox into net_w x net_h: r = min(W / sw, H / sh), the scaled frame rounded and centred (W == H: the square case)
-    int nw = net_w, nh = net_h, px = 0, py = 0;
-    if (c.resize_mode == IRMV_RESIZE_LETTERBOX) {
-        const double r = std::min((double)net_w / c.src_width, (double)net_h / c.src_height);
-        nw = std::min(net_w, (int)std::floor(c.src_width * r + 0.5));
-        nh = std::min(net_h, (int)std::floor(c.src_height * r + 0.5));
-        px = (net_w - nw) / 2;
-        py = (net_h - nh) / 2;
-    }
+    // ---- preprocess and front geometry: front_plan, under this process's environment switches ----
     std::vector<AxisTap> tx, ty;
-    axis_taps(tx, net_w, c.src_width, nw, px, c.rotate180 != 0);
-    axis_taps(ty, net_h, c.src_height, nh, py, c.rotate180 != 0);
+    irmv_front_plan_t plan;
+    {
+        FrontSwitches sw;
+        if (const char *f = getenv("IRMV_FRONT_FASTX")) if (f[0] == '0') sw.fastx = false;
+        if (const char *f = getenv("IRMV_FRONT_DIRECT")) if (f[0] == '0') sw.direct = false;
+        if (const char *f = getenv("IRMV_FRONT_TILE8")) if (f[0] == '0') sw.tall = false;   // keeps the 4-row tile
+        front_plan(c, sw, &plan, tx, ty);
+    }
+    const int px = plan.box[0], py = plan.box[2], nw = plan.box[1] - px, nh = plan.box[3] - py;
     TRY(dev_alloc(e, (void **)&e->tap_x, net_w * sizeof(AxisTap)));
     TRY(dev_alloc(e, (void **)&e->tap_y, net_h * sizeof(AxisTap)));
     HIP_TRY(hipMemcpy(e->tap_x, tx.data(), net_w * sizeof(AxisTap), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(e->tap_y, ty.data(), net_h * sizeof(AxisTap), hipMemcpyHostToDevice));
-    e->fused_front = front_fits(tx, ty, c.src_width, &e->front_tiles_x, &e->front_tiles_y, &e->front_stage_bytes);
-    e->front_v[0] = px; e->front_v[1] = px + nw; e->front_v[2] = py; e->front_v[3] = py + nh;
-    {   // columns at exactly 2 : 1 (1280 -> 640): the taps of column px + k are the aligned source pair (m, m + 1) with
-        // m = m0 + step k even, both weights 1/2; step = 2, or -2 under rotate180 (the pair is then listed as (m + 1, m):
-        // with equal weights the blend does not care)
-        const int step = c.rotate180 ? -2 : 2;
-        const int m0 = nw > 0 ? std::min(tx[px].i0, tx[px].i1) : -1;
-        bool fx = nw > 0 && m0 >= 0 && (m0 & 1) == 0;
-        for (int d = px; d < px + nw && fx; d++)
-            fx = std::min(tx[d].i0, tx[d].i1) == m0 + step * (d - px) && std::max(tx[d].i0, tx[d].i1) == m0 + step * (d - px) + 1 && tx[d].w1 == 1024;
-        if (const char *f = getenv("IRMV_FRONT_FASTX")) if (f[0] == '0') fx = false;
-        bool direct = fx;   // tiles without a padding pixel skip the LDS staging of the source (k_front.hip); bit 1 of FrontArgs::fastx
-        if (const char *f = getenv("IRMV_FRONT_DIRECT")) if (f[0] == '0') direct = false;
-        e->front_fastx = fx ? (direct ? 3 : 1) : 0;
-        // all tiles direct: nothing is staged, and the tile can be twice as tall (k_front.hip); IRMV_FRONT_TILE8=0 keeps the 4-row tile
-        bool tall = fx && direct && e->fused_front;
-        if (const char *f = getenv("IRMV_FRONT_TILE8")) if (f[0] == '0') tall = false;
-        if (tall) {
-            e->front_tile_y = kFrontTileYDirect;
-            e->front_tiles_y = (net_h / 4 + kFrontTileYDirect - 1) / kFrontTileYDirect;
-            e->front_stage_bytes = front_min_stage_bytes(kFrontTileYDirect);
-        }
-        e->front_fx_i0 = fx ? m0 : 0;
-        e->front_fx_step = step;
-    }
+    e->fused_front = plan.fused != 0;
+    e->front_tiles_x = plan.tiles_x; e->front_tiles_y = plan.tiles_y; e->front_stage_bytes = plan.stage_bytes;
+    e->front_tile_y = plan.tile_y;
+    for (int i = 0; i < 4; i++) e->front_v[i] = plan.box[i];
+    e->front_fastx = plan.fastx; e->front_fx_i0 = plan.fx_i0; e->front_fx_step = plan.fx_step;
     if (const char *ff = getenv("IRMV_FUSED_FRONT")) if (ff[0] == '0') e->fused_front = false;
     if (e->fused_front && !front_prepare()) e->fused_front = false;
 
@@ -1381,18 +1441,20 @@ constexpr size_t kCfgSizeV1 = offsetof(irmv_engine_cfg, src_format);
 constexpr size_t kCfgSizeV2 = offsetof(irmv_engine_cfg, reserved2);
 static_assert(offsetof(irmv_engine_cfg, net_height) < kCfgSizeV2 && kCfgSizeV2 < sizeof(irmv_engine_cfg), "three distinct cfg sizes");
 
-extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **out)
+// The caller's configuration at this library's size (an older caller's prefix, the appended fields at their defaults),
+// and the checks of everything the front's geometry follows from.  No GPU call.
+static int resolve_cfg(const irmv_engine_cfg *cfg_in, irmv_engine_cfg *full)
 {
-    if (!cfg_in || !out) return fail(IRMV_ERR_ARG, "cfg/out is null");
     const size_t sz = cfg_in->struct_size;
     if (sz != sizeof(irmv_engine_cfg) && sz != kCfgSizeV1 && sz != kCfgSizeV2) return fail(IRMV_ERR_ARG, "irmv_engine_cfg size mismatch");
-    irmv_engine_cfg full;   // an older caller's prefix, the appended fields at their defaults
     if (sz != sizeof(irmv_engine_cfg)) {
-        irmv_engine_cfg_default(&full);
-        memcpy(&full, cfg_in, sz == kCfgSizeV1 ? kCfgSizeV1 : offsetof(irmv_engine_cfg, net_height));
-        full.struct_size = sizeof full;
+        irmv_engine_cfg_default(full);
+        memcpy(full, cfg_in, sz == kCfgSizeV1 ? kCfgSizeV1 : offsetof(irmv_engine_cfg, net_height));
+        full->struct_size = sizeof *full;
+    } else {
+        *full = *cfg_in;
     }
-    const irmv_engine_cfg *cfg = sz != sizeof(irmv_engine_cfg) ? &full : cfg_in;
+    const irmv_engine_cfg *cfg = full;
     if (cfg->src_format < IRMV_SRC_HWC8 || cfg->src_format > IRMV_SRC_BAYER_GBRG8) return fail(IRMV_ERR_ARG, "unknown src_format (IRMV_SRC_*)");
     if (cfg->src_format != IRMV_SRC_HWC8) {
         if (cfg->src_width % 2 || cfg->src_height % 2) return fail(IRMV_ERR_ARG, "a Bayer src_format (IRMV_SRC_BAYER_*8) needs an even src_width and src_height");
@@ -1403,6 +1465,35 @@ extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **o
     if (cfg->net_height != 0 && (cfg->net_height < 64 || cfg->net_height % 32 != 0 || cfg->net_height > 2048))
         return fail(IRMV_ERR_ARG, "net_height must be 0 (square) or a multiple of 32 in [64, 2048]");
     if (cfg->src_width < 2 || cfg->src_height < 2 || cfg->src_width > 4096) return fail(IRMV_ERR_ARG, "src size out of range (width <= 4096)");
+    // The narrowest offset arithmetic of the kernels that read a source frame is the fused front's direct tiles (k_front.hip):
+    // row * 3 src_width + 3 x + 11 as ONE unsigned 32-bit byte offset into the frame.  (preprocess_kernel, rotate180_kernel
+    // and the light extraction index with size_t; the demosaic's int counts bytes of one band of rows.)
+    if ((uint64_t)cfg->src_width * (uint64_t)cfg->src_height * 3u > IRMV_MAX_FRAME_BYTES)
+        return fail(IRMV_ERR_ARG, "src frame too large: 3 * src_width * src_height must not exceed 4294967296 bytes (32-bit byte offsets into a frame)");
+    {   // a source so oblong that the short side of its letterboxed frame rounds to nothing: no box, no scale back to the source
+        int nw, nh;
+        scaled_size(*cfg, &nw, &nh);
+        if (nw < 1 || nh < 1) return fail(IRMV_ERR_ARG, "letterbox: the scaled frame has no row or no column; use IRMV_RESIZE_STRETCH");
+    }
+    return IRMV_OK;
+}
+
+extern "C" int irmv_front_plan(const irmv_engine_cfg *cfg_in, irmv_front_plan_t *out)
+{
+    if (!cfg_in || !out) return fail(IRMV_ERR_ARG, "cfg/out is null");
+    irmv_engine_cfg full;
+    if (int rc = resolve_cfg(cfg_in, &full)) return rc;
+    std::vector<AxisTap> tx, ty;
+    front_plan(full, FrontSwitches{}, out, tx, ty);
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **out)
+{
+    if (!cfg_in || !out) return fail(IRMV_ERR_ARG, "cfg/out is null");
+    irmv_engine_cfg full;
+    if (int rc = resolve_cfg(cfg_in, &full)) return rc;
+    const irmv_engine_cfg *cfg = &full;
     if (cfg->num_slots < 1 || cfg->num_slots > 256) return fail(IRMV_ERR_ARG, "num_slots must be 1..256");
     if (cfg->max_det < 1 || cfg->max_det > IRMV_MAX_DET_CAP) return fail(IRMV_ERR_ARG, "max_det must be 1..256");
     if (cfg->pre_nms_cap < 1 || cfg->pre_nms_cap > IRMV_CAND_CAP) return fail(IRMV_ERR_ARG, "pre_nms_cap must be 1..8192");
@@ -2322,8 +2413,7 @@ static int copy_in(irmv_engine *e, int first, int count, hipStream_t st)
 // One or two frames travel from the pinned slots as a KERNEL (k_pre.hip upload_frame_kernel), larger groups on the copy engine.
 static bool upload_as_kernel(const irmv_engine *e, int first, int count)
 {
-    const size_t off = (size_t)first * e->src_bytes, bytes = e->src_bytes * count;
-    return count <= 2 && e->upload_kernel_blocks > 0 && e->src_host_dev && off % 16 == 0 && bytes % 16 == 0;
+    return count <= 2 && e->upload_kernel_blocks > 0 && e->src_host_dev && upload_aligned(e->src_bytes, first, count);
 }
 
 // The synchronous upload of slots [first, first + count) on stream st.  (A Bayer engine's single-frame upload stays a kernel

@@ -24,6 +24,11 @@ For every engine: distinct synthetic frames, one step, then
                      may pick different ones; no later layer can tell them apart, so the sign of a zero is not checked
                      (the same holds for the pool's comparison with the step).
 
+Two kinds that are covered elsewhere have a sweep of their own over source geometries, tests/test_gpu_input_geometry.py:
+
+  * front: bitwise against preprocess + model.0.conv + model.1.conv on every path of the front kernel and every tile class;
+  * pre: bitwise against the oracle's preprocess on the same zoo.
+
 The engines reach all four SPPF variants (irmv_sppf_slab: LDS slabs of 8, 16 and 32 channels, and the global-memory
 kernel of P5 maps above 2400 pixels), P5 maps from 2 x 2 to 64 x 64, 64 x 2 and 2 x 64, and every depthwise (stride 1
 and 2) and shuffle op of the ShuffleNet backbone, fp16 and int8, on maps down to 13 x 11.  The 1568 and 2048 engines
@@ -46,10 +51,11 @@ pytestmark = pytest.mark.gpu
 CHECKED = ("conv0", "pool", "dw", "shuffle")
 COVERED = {   # the other kinds that write activation tensors, and where they are checked
     "conv": "the sweep of tests/test_gpu_conv_candidates.py",
-    "front": "bitwise against its layers in the sweep", "c2f2": "bitwise against its layers in the sweep",
+    "front": "bitwise against its layers in the sweep, and on the zoo of tests/test_gpu_input_geometry.py", "c2f2": "bitwise against its layers in the sweep",
     "c2f32": "bitwise against its layers in the sweep", "bneck": "bitwise against its layers in the sweep",
     "kpt3": "bitwise against its layers in the sweep",
-    "pre": "the preprocess bit-exact tests of tests/test_gpu_engine.py and tests/test_gpu_rect.py",
+    "pre": "the preprocess bit-exact tests of tests/test_gpu_engine.py and tests/test_gpu_rect.py, and bitwise against the oracle "
+           "on the zoo of tests/test_gpu_input_geometry.py",
 }
 P5_C = 128   # model.9.m: channels per slice of 9.cat
 
