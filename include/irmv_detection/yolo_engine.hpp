@@ -68,15 +68,18 @@ public:
   // white-balance gains `bayer_gain_q8` (R, G, B; 256 = 1.0).  get_rotated_image() is a CV_8UC3 frame either way.
   // `net_height` (-1 = square): the network input is net_size wide and net_height tall, e.g. 640 x 512 for the 1280 x 1024
   // camera (include/irmv_hip.h, irmv_engine_cfg::net_height); net_input_size() returns what the engine runs.
+  // `bayer_demosaic` (IRMV_DEMOSAIC_*): the interpolation of a Bayer engine, bilinear or the 5 x 5 Malvar-He-Cutler filters.
   YoloEngine(const std::string & onnx_file_path, cv::Size src_image_size, bool enable_profiling = false, int device = -1,
              bool warm_up_now = true, int net_size = -1, int src_format = IRMV_SRC_HWC8,
-             std::array<uint16_t, 3> bayer_gain_q8 = {256, 256, 256}, int net_height = -1)
+             std::array<uint16_t, 3> bayer_gain_q8 = {256, 256, 256}, int net_height = -1,
+             int bayer_demosaic = IRMV_DEMOSAIC_BILINEAR)
   : src_image_size_(src_image_size), enable_profiling_(enable_profiling)
   {
     irmv_engine_cfg cfg;
     irmv_engine_cfg_default(&cfg);
     cfg.src_format = src_format;
     for (int i = 0; i < 3; i++) cfg.bayer_gain_q8[i] = bayer_gain_q8[static_cast<size_t>(i)];
+    cfg.bayer_demosaic = static_cast<uint16_t>(bayer_demosaic);
     cfg.net_size = net_size > 0 ? net_size : default_net_size();
     cfg.net_height = net_height > 0 ? net_height : 0;
     cfg.device = device >= 0 ? device : default_device();
@@ -120,6 +123,16 @@ public:
     const double cd[4] = {min_small_cd, max_small_cd, min_large_cd, max_large_cd};
     if (irmv_engine_set_extract_params(engine_, binary_threshold, light_min_ratio, light_max_ratio, light_max_angle, cd) != IRMV_OK)
       throw std::runtime_error(std::string("YoloEngine::set_extract_params: ") + irmv_last_error());
+  }
+
+  // The camera ISP's white balance and tone curve of a Bayer engine, retuned while it lives: Q8 gains (R, G, B; 256 = 1.0) and
+  // a [3][256] byte LUT (rows R, G, B; nullptr = identity), out = lut[c][min(255, (v * gain[c] + 128) >> 8)].  Waits for the
+  // steps in flight; every later detect() / get_rotated_image() uses the new values (irmv_engine_set_bayer_isp).
+  void set_bayer_isp(std::array<uint16_t, 3> gain_q8, const uint8_t * lut = nullptr)
+  {
+    if (irmv_engine_set_bayer_isp(engine_, gain_q8.data(), lut) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::set_bayer_isp: ") + irmv_last_error());
+    rotated_valid_ = false;
   }
 
   ~YoloEngine() { irmv_engine_destroy(engine_); }

@@ -47,8 +47,10 @@ extern "C" {
  *   IRMV_SRC_BAYER_*8: H x W bytes per slot, the sensor's raw 8-bit colour-filter-array frame; the name gives the colours of
  *                  the 2 x 2 cell at (0,0) (0,1) / (1,0) (1,1).  H and W must be even.  The first kernel of every step
  *                  demosaics it on the GPU into the R, G, B frame an IRMV_SRC_HWC8 engine would have been handed: integer
- *                  bilinear interpolation (round half up, reflect-101 borders), then the white-balance gains
- *                  out = min(255, (v * gain + 128) >> 8) per channel (bayer_gain_q8, Q8, 256 = 1.0).  swap_rb, rotate180,
+ *                  bilinear interpolation (round half up, reflect-101 borders) or, with bayer_demosaic =
+ *                  IRMV_DEMOSAIC_MHC, the 5 x 5 Malvar-He-Cutler filters, then the white-balance gains
+ *                  out = min(255, (v * gain + 128) >> 8) per channel (bayer_gain_q8, Q8, 256 = 1.0) and, once
+ *                  irmv_engine_set_bayer_isp has been called, a per-channel tone LUT.  swap_rb, rotate180,
  *                  resize_mode and everything downstream then act on that frame exactly as on an HWC8 one.
  *                  irmv_detection_amd/bayer.py is the bit-exact host reference. */
 #define IRMV_SRC_HWC8 0
@@ -56,6 +58,20 @@ extern "C" {
 #define IRMV_SRC_BAYER_BGGR8 2
 #define IRMV_SRC_BAYER_GRBG8 3
 #define IRMV_SRC_BAYER_GBRG8 4
+
+/* Interpolation of a Bayer engine (irmv_engine_cfg.bayer_demosaic).
+ *   IRMV_DEMOSAIC_BILINEAR: the 3 x 3 integer bilinear interpolation above (default).
+ *   IRMV_DEMOSAIC_MHC: Malvar-He-Cutler in integers.  Reflect-101 borders at radius 2 (-1 -> 1, -2 -> 2, W -> W-2,
+ *                  W+1 -> W-3); a site's own colour is its raw value; the other two are clamp((s + 8) >> 4, 0, 255) of a
+ *                  signed sum s in sixteenths (arithmetic shift = floor).  C the centre, S1 / S2 the four axis neighbours at
+ *                  distance 1 / 2, X the four diagonals:
+ *                    G at an R or B site                                  8 C + 4 S1 - 2 S2
+ *                    at a G site, the colour sampled in this site's row     10 C + 8 (W1 + E1) - 2 X - 2 (W2 + E2) + (N2 + S2)
+ *                    at a G site, the colour sampled in this site's column  10 C + 8 (N1 + S1) - 2 X - 2 (N2 + S2) + (W2 + E2)
+ *                    B at an R site, R at a B site                        12 C + 4 X - 3 S2
+ *                  Needs src_width >= 4 and src_height >= 4.  Gains and LUT apply afterwards, as one table look-up. */
+#define IRMV_DEMOSAIC_BILINEAR 0
+#define IRMV_DEMOSAIC_MHC 1
 
 #define IRMV_NUM_CLASSES 14   /* ArmorClass B1..RS; 14 = UNKNOWN (include/irmv_detection/armor.hpp:7) */
 #define IRMV_MAX_DET_CAP 256
@@ -110,7 +126,7 @@ typedef struct irmv_engine_cfg {
      * against the header without them) and then uses IRMV_SRC_HWC8 and gains of 256. */
     int32_t src_format;        /* IRMV_SRC_* (default IRMV_SRC_HWC8) */
     uint16_t bayer_gain_q8[3]; /* R, G, B white-balance gains of a Bayer engine, Q8 in [0, 1023]; 256 = identity (default) */
-    uint16_t reserved1;
+    uint16_t bayer_demosaic;   /* IRMV_DEMOSAIC_* of a Bayer engine (default IRMV_DEMOSAIC_BILINEAR; callers with an older struct_size get it) */
     /* Appended after those.  irmv_engine_create also accepts struct_size = offsetof(irmv_engine_cfg, reserved2) (= the sizeof
      * of the header before this field; bytes from net_height on are then not read) and uses net_height = 0.
      * Rectangular network input: net_size is the width W, net_height the height H, both multiples of 32 in [64, 2048];
@@ -240,6 +256,19 @@ double irmv_engine_last_detect_ms(const irmv_engine *e);
  * receives src_height*src_width*3 bytes in every format: a Bayer engine uploads the
  * raw slot, demosaics it and returns the rotated R, G, B frame. */
 int irmv_engine_rotated_image(irmv_engine *e, int slot, uint8_t *dst_hwc);
+
+/* The gains and tone curve of a Bayer engine, changeable while it lives (the camera SDK's ISP retuned per venue):
+ *   out = lut[c][min(255, (v * gain_q8[c] + 128) >> 8)]   per channel c = R, G, B,
+ * v the interpolated value.  gain_q8: Q8 in [0, 1023]; lut: [3][256] bytes, rows R, G, B, NULL = identity (then exactly the
+ * arithmetic of bayer_gain_q8).  The engine folds both into one [3][256] byte table in device memory that the demosaic
+ * kernel stages in LDS.  The call blocks until every step in flight on every stream of the engine has finished, then
+ * writes the table: every later submit, detect, irmv_engine_rotated_image and irmv_engine_extract_armors uses it.  An engine
+ * on which it was never called (and whose bayer_demosaic is bilinear) keeps the kernel that takes the gains as arguments;
+ * the first call drops the captured graphs that hold that kernel, and they are captured again with the table kernel.
+ * IRMV_ERR_ARG: null engine, an IRMV_SRC_HWC8 engine, null gain_q8, a gain above 1023. */
+int irmv_engine_set_bayer_isp(irmv_engine *e, const uint16_t gain_q8[3], const uint8_t *lut);
+/* The current gains and LUT (either pointer may be NULL); the LUT of an engine that has none set is the identity. */
+int irmv_engine_get_bayer_isp(const irmv_engine *e, uint16_t gain_q8[3], uint8_t *lut);
 
 /* IrmDetector::extract_armors(get_rotated_image(), bboxes) (src/irm_detector.cpp:183,292-355) on the GPU:
  * for each of the n boxes (xyxy, rotated-frame pixels) on the slot's current frame -> out[i].kpts (LB, LT, RT,

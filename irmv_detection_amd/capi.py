@@ -18,6 +18,8 @@ SUBMIT_ASYNC_UPLOAD = 2
 POINTS_AUTO, POINTS_KEYPOINT_HEAD, POINTS_CLASSICAL = 0, 1, 2
 SRC_HWC8, SRC_BAYER_RGGB8, SRC_BAYER_BGGR8, SRC_BAYER_GRBG8, SRC_BAYER_GBRG8 = 0, 1, 2, 3, 4
 BAYER_FORMATS = {"RGGB": SRC_BAYER_RGGB8, "BGGR": SRC_BAYER_BGGR8, "GRBG": SRC_BAYER_GRBG8, "GBRG": SRC_BAYER_GBRG8}
+DEMOSAIC_BILINEAR, DEMOSAIC_MHC = 0, 1
+DEMOSAIC_ALGOS = {"bilinear": DEMOSAIC_BILINEAR, "mhc": DEMOSAIC_MHC}
 NUM_CLASSES = 14
 MAX_DET_CAP = 256
 CAND_CAP = 8192
@@ -44,7 +46,7 @@ class EngineCfg(C.Structure):
         ("light_min_ratio", C.c_float), ("light_max_ratio", C.c_float), ("light_max_angle", C.c_float), ("reserved0", C.c_float),
         ("armor_min_small_center_distance", C.c_double), ("armor_max_small_center_distance", C.c_double),
         ("armor_min_large_center_distance", C.c_double), ("armor_max_large_center_distance", C.c_double),
-        ("src_format", C.c_int32), ("bayer_gain_q8", C.c_uint16 * 3), ("reserved1", C.c_uint16),
+        ("src_format", C.c_int32), ("bayer_gain_q8", C.c_uint16 * 3), ("bayer_demosaic", C.c_uint16),
         ("net_height", C.c_int32), ("reserved2", C.c_int32),   # net_height 0: square net_size x net_size input
     ]
 
@@ -169,6 +171,8 @@ SYMBOLS = [
     ("irmv_engine_last_detect_ms", C.c_double, [_P]),
     ("irmv_engine_rotated_image", C.c_int, [_P, C.c_int, C.POINTER(C.c_uint8)]),
     ("irmv_engine_extract_armors", C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(Det)]),
+    ("irmv_engine_set_bayer_isp", C.c_int, [_P, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]),
+    ("irmv_engine_get_bayer_isp", C.c_int, [_P, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]),
     ("irmv_engine_light_trace", C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(LightTrace), C.POINTER(Det)]),
     ("irmv_light_limits", C.c_int, [C.POINTER(C.c_int32)]),
     ("irmv_engine_read_input", C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),

@@ -266,6 +266,13 @@ struct irmv_engine {
     uint8_t *src_dev = nullptr;   // [S][frame]
     uint8_t *raw_dev = nullptr;   // Bayer engines: [S][W*H] raw frames, demosaiced into src_dev by the first op of a step (OP_DEMOSAIC)
     BayerArgs bayer{};            // (pointers, slot strides, pattern phase and gains of that op; raw / dst set per launch)
+    // The ISP table of a Bayer engine (irmv_engine_set_bayer_isp): gains and tone LUT folded into T[c][v], [3][256] bytes in
+    // device memory, read by the table kernels when they run -- a captured graph holds the pointer, never the values.
+    // bayer_table: the demosaic is a table kernel (an MHC engine from creation on, a bilinear one from its first set).
+    uint8_t *isp_table_dev = nullptr;
+    bool bayer_table = false, bayer_mhc = false;
+    uint16_t isp_gain[3] = {256, 256, 256};
+    uint8_t isp_lut[kBayerTableBytes] = {0};
     uint8_t *rot_dev = nullptr;   // [frame]
     AxisTap *tap_x = nullptr, *tap_y = nullptr;
     std::vector<Tensor> tensors;
@@ -905,6 +912,20 @@ static void finalize_head_fusion(irmv_engine *e);
 static int build_head_groups(irmv_engine *e);
 static void build_step_plans(irmv_engine *e);
 
+// T[c][v] = lut[c][min(255, (v gain[c] + 128) >> 8)] from the engine's current gains and LUT -> isp_table_dev.  The caller has
+// made sure that nothing of this engine is in flight.
+static int write_isp_table(irmv_engine *e)
+{
+    uint8_t t[kBayerTableBytes];
+    for (int c = 0; c < 3; c++)
+        for (uint32_t v = 0; v < 256; v++) t[c * 256 + v] = e->isp_lut[c * 256 + std::min(255u, (v * e->isp_gain[c] + 128u) >> 8)];
+    HIP_TRY(hipMemcpy(e->isp_table_dev, t, sizeof t, hipMemcpyHostToDevice));
+    return IRMV_OK;
+}
+
+// profile / op name of a Bayer engine's demosaic as it runs now
+static const char *demosaic_kname(const irmv_engine *e) { return e->bayer_mhc ? "bayer_demosaic_mhc" : (e->bayer_table ? "bayer_demosaic_lut" : "bayer_demosaic"); }
+
 static int build_engine(irmv_engine *e)
 {
     const irmv_engine_cfg &c = e->cfg;
@@ -956,6 +977,11 @@ static int build_engine(irmv_engine *e)
         b.W = c.src_width; b.H = c.src_height;
         b.ry = ry[c.src_format - 1]; b.rx = rx[c.src_format - 1];
         for (int i = 0; i < 3; i++) b.gain[i] = c.bayer_gain_q8[i];
+        for (int i = 0; i < 3; i++) e->isp_gain[i] = c.bayer_gain_q8[i];
+        for (int i = 0; i < kBayerTableBytes; i++) e->isp_lut[i] = (uint8_t)(i & 255);
+        TRY(dev_alloc(e, (void **)&e->isp_table_dev, kBayerTableBytes));
+        e->bayer_mhc = c.bayer_demosaic == IRMV_DEMOSAIC_MHC;
+        if (e->bayer_mhc) { e->bayer_table = true; TRY(write_isp_table(e)); }
     }
 
     // ---- preprocess and front geometry: front_plan, under this process's environment switches ----
@@ -1009,7 +1035,7 @@ static int build_engine(irmv_engine *e)
     TRY(new_tensor(e, "21", h32, w32, 256, false, &a21));
 
     if (bayer) {   // raw slot -> src_dev: the first op of every step (not of run_post, not of a read-back's materialisation)
-        Op op; op.kind = OP_DEMOSAIC; op.layer = "demosaic"; snprintf(op.kname, sizeof op.kname, "bayer_demosaic");
+        Op op; op.kind = OP_DEMOSAIC; op.layer = "demosaic"; snprintf(op.kname, sizeof op.kname, "%s", demosaic_kname(e));
         op.bytes = (double)e->src_bytes + (double)e->frame_bytes;
         e->ops.push_back(op);
     }
@@ -1451,11 +1477,17 @@ static int resolve_cfg(const irmv_engine_cfg *cfg_in, irmv_engine_cfg *full)
         irmv_engine_cfg_default(full);
         memcpy(full, cfg_in, sz == kCfgSizeV1 ? kCfgSizeV1 : offsetof(irmv_engine_cfg, net_height));
         full->struct_size = sizeof *full;
+        full->bayer_demosaic = IRMV_DEMOSAIC_BILINEAR;   // (the older headers had a reserved field there)
     } else {
         *full = *cfg_in;
     }
     const irmv_engine_cfg *cfg = full;
     if (cfg->src_format < IRMV_SRC_HWC8 || cfg->src_format > IRMV_SRC_BAYER_GBRG8) return fail(IRMV_ERR_ARG, "unknown src_format (IRMV_SRC_*)");
+    if (cfg->bayer_demosaic > IRMV_DEMOSAIC_MHC) return fail(IRMV_ERR_ARG, "unknown bayer_demosaic (IRMV_DEMOSAIC_*)");
+    if (cfg->bayer_demosaic == IRMV_DEMOSAIC_MHC) {
+        if (cfg->src_format == IRMV_SRC_HWC8) return fail(IRMV_ERR_ARG, "bayer_demosaic = IRMV_DEMOSAIC_MHC needs a Bayer src_format (IRMV_SRC_BAYER_*8)");
+        if (cfg->src_width < 4 || cfg->src_height < 4) return fail(IRMV_ERR_ARG, "bayer_demosaic = IRMV_DEMOSAIC_MHC needs src_width >= 4 and src_height >= 4 (reflect-101 at radius 2)");
+    }
     if (cfg->src_format != IRMV_SRC_HWC8) {
         if (cfg->src_width % 2 || cfg->src_height % 2) return fail(IRMV_ERR_ARG, "a Bayer src_format (IRMV_SRC_BAYER_*8) needs an even src_width and src_height");
         for (int i = 0; i < 3; i++)
@@ -2188,6 +2220,12 @@ static BayerArgs bayer_args(const irmv_engine *e, int first)   // a Bayer engine
     return a;
 }
 
+static void launch_bayer(const irmv_engine *e, int first, int count, hipStream_t s)
+{
+    if (e->bayer_table) launch_demosaic_table(bayer_args(e, first), e->isp_table_dev, e->bayer_mhc, count, s);
+    else launch_demosaic(bayer_args(e, first), count, s);
+}
+
 static PostArgs post_args(const irmv_engine *e, int first)
 {
     PostArgs p = e->post;
@@ -2292,7 +2330,7 @@ static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hip
         const int n = l.once ? 1 : reps;
         for (int rep = 0; rep < n; rep++)
         switch (op.kind) {
-        case OP_DEMOSAIC: launch_demosaic(bayer_args(e, first), count, s); break;
+        case OP_DEMOSAIC: launch_bayer(e, first, count, s); break;
         case OP_PRE: {
             PreArgs a;
             a.src = e->src_dev + (size_t)first * e->frame_bytes;
@@ -2705,7 +2743,7 @@ static int load_frame(irmv_engine *e, int slot, hipStream_t st)
 {
     TRY(copy_in(e, slot, 1, st));
     if (e->raw_dev) {
-        launch_demosaic(bayer_args(e, slot), 1, st);
+        launch_bayer(e, slot, 1, st);
         HIP_TRY(hipGetLastError());
     }
     return IRMV_OK;
@@ -2871,6 +2909,47 @@ extern "C" int irmv_engine_set_extract_params(irmv_engine *e, int binary_thresho
         for (auto &g : e->graphs) (void)hipGraphExecDestroy(g.second);
         e->graphs.clear();
     }
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_set_bayer_isp(irmv_engine *e, const uint16_t gain_q8[3], const uint8_t *lut)
+{
+    if (!e || !gain_q8) return fail(IRMV_ERR_ARG, "engine / gain_q8 is null");
+    if (!e->raw_dev) return fail(IRMV_ERR_ARG, "irmv_engine_set_bayer_isp: not a Bayer engine (src_format is IRMV_SRC_HWC8)");
+    for (int i = 0; i < 3; i++)
+        if (gain_q8[i] > 1023) return fail(IRMV_ERR_ARG, "gain_q8 must be in [0, 1023] (Q8, 256 = 1.0)");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));   // every stream of the engine: no step in flight reads the table, no graph is running
+    for (int i = 0; i < 3; i++) e->isp_gain[i] = e->cfg.bayer_gain_q8[i] = gain_q8[i];
+    for (int i = 0; i < kBayerTableBytes; i++) e->isp_lut[i] = lut ? lut[i] : (uint8_t)(i & 255);
+    TRY(write_isp_table(e));
+    if (!e->bayer_table) {
+        // From the argument-gain kernel to the table kernel: the captured steps hold the old kernel node, so they are dropped
+        // and captured again on their next use (run_post's graphs have no demosaic node and stay).  Later sets only rewrite
+        // the table, which the kernels read from device memory when they run.
+        e->bayer_table = true;
+        for (auto it = e->graphs.begin(); it != e->graphs.end();) {
+            if (it->first.kind == STEP_POST) { ++it; continue; }
+            (void)hipGraphExecDestroy(it->second);
+            it = e->graphs.erase(it);
+        }
+        for (size_t i = 0; i < e->ops.size(); i++) {
+            if (e->ops[i].kind != OP_DEMOSAIC) continue;
+            snprintf(e->ops[i].kname, sizeof e->ops[i].kname, "%s", demosaic_kname(e));
+            for (auto &plan : e->plans)
+                for (Launch &l : plan)
+                    if (l.op == (int)i) l.name = e->ops[i].kname;
+        }
+    }
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_get_bayer_isp(const irmv_engine *e, uint16_t gain_q8[3], uint8_t *lut)
+{
+    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
+    if (!e->raw_dev) return fail(IRMV_ERR_ARG, "irmv_engine_get_bayer_isp: not a Bayer engine (src_format is IRMV_SRC_HWC8)");
+    if (gain_q8) for (int i = 0; i < 3; i++) gain_q8[i] = e->isp_gain[i];
+    if (lut) memcpy(lut, e->isp_lut, kBayerTableBytes);
     return IRMV_OK;
 }
 

@@ -131,7 +131,10 @@ void launch_upload_frames(const uint8_t *src_host_mapped, uint8_t *dst, size_t b
 // ---- raw Bayer input (k_bayer.hip) ---------------------------------------------------
 // uint8 [B][H][W] CFA frames -> HWC [B][H][W][3] (R, G, B): integer bilinear demosaic with reflect-101 borders, then the
 // Q8 white-balance gains (irmv_detection_amd/bayer.py is the bit-exact host reference).  Any alignment of `raw` and `dst`.
-constexpr int kBayerBandRows = 8;   // output rows per workgroup (+ one halo row above and below, staged in LDS)
+// With `table` set the last step per channel is table[c][v] instead (gains and tone LUT folded on the host,
+// irmv_engine_set_bayer_isp), and `mhc` selects the 5 x 5 Malvar-He-Cutler interpolation (always in the table form).
+constexpr int kBayerBandRows = 8;   // output rows per workgroup (+ one halo row above and below, two for MHC, staged in LDS)
+constexpr int kBayerTableBytes = 3 * 256;
 struct BayerArgs {
     const uint8_t *raw;       // [B][H][W]
     uint8_t *dst;             // [B][H][W][3]
@@ -141,6 +144,7 @@ struct BayerArgs {
     uint32_t gain[3];         // Q8, 256 = identity
 };
 void launch_demosaic(const BayerArgs &a, int batch, hipStream_t s);
+void launch_demosaic_table(const BayerArgs &a, const uint8_t *table, bool mhc, int batch, hipStream_t s);   // table: [3][256] device bytes, 16-byte aligned; mhc: W, H >= 4
 
 // model.0.conv: 3x3 s2, 3(+1 pad) -> 16, SiLU
 struct Conv0Args {

@@ -90,6 +90,8 @@ class YoloEngine:
     `src_format`: what a source slot holds -- capi.SRC_HWC8 (H x W x 3, default) or a raw 8-bit Bayer frame
     (capi.SRC_BAYER_*8, or the pattern name "RGGB" / "BGGR" / "GRBG" / "GBRG"), demosaiced on the GPU with the Q8
     white-balance `bayer_gains` (R, G, B; 256 = 1.0); irmv_detection_amd.bayer.demosaic is its host reference.
+    `bayer_demosaic`: "bilinear" (default) or "mhc", the 5 x 5 Malvar-He-Cutler filters (capi.DEMOSAIC_*).  `set_bayer_isp`
+    changes the gains and a per-channel tone LUT on the living engine; `bayer_isp` reads them back.
     `net_size` x `net_height`: the network input's width x height (`net_height=None`: square, net_size x net_size; e.g.
     640 x 512 for a 1280 x 1024 camera); `net_width` / `net_height` hold the engine's dimensions.
     """
@@ -105,7 +107,8 @@ class YoloEngine:
                  num_streams: int = 0, point_source: int = capi.POINTS_AUTO, binary_threshold: int = 150,
                  light_min_ratio: float = 0.1, light_max_ratio: float = 0.4, light_max_angle: float = 40.0,
                  armor_center_distances: Sequence[float] = (0.8, 3.2, 3.2, 5.5), warmup: int = 0,
-                 src_format=capi.SRC_HWC8, bayer_gains: Sequence[int] = (256, 256, 256), net_height: Optional[int] = None):
+                 src_format=capi.SRC_HWC8, bayer_gains: Sequence[int] = (256, 256, 256), net_height: Optional[int] = None,
+                 bayer_demosaic="bilinear"):
         L = capi.load()
         cfg = capi.EngineCfg()
         L.irmv_engine_cfg_default(C.byref(cfg))
@@ -123,6 +126,7 @@ class YoloEngine:
          cfg.armor_min_large_center_distance, cfg.armor_max_large_center_distance) = armor_center_distances
         cfg.src_format = capi.BAYER_FORMATS[src_format.upper()] if isinstance(src_format, str) else int(src_format)
         cfg.bayer_gain_q8 = (C.c_uint16 * 3)(*[int(g) for g in bayer_gains])
+        cfg.bayer_demosaic = capi.DEMOSAIC_ALGOS[bayer_demosaic.lower()] if isinstance(bayer_demosaic, str) else int(bayer_demosaic)
         cfg.camera_matrix = (C.c_double * 9)(*camera_matrix)
         cfg.dist_coeffs = (C.c_double * 5)(*(list(dist_coeffs) + [0.0] * 5)[:5])
         self._blob_keepalive = None
@@ -143,6 +147,7 @@ class YoloEngine:
             capi.check(rc)
         self.src_image_size = (cfg.src_width, cfg.src_height)
         self.src_format = cfg.src_format
+        self.bayer_demosaic = "mhc" if cfg.bayer_demosaic == capi.DEMOSAIC_MHC else "bilinear"
         self.net_size = net_size                 # the width (and, square, the height)
         self.net_width, self.net_height = net_size, net_height or net_size
         if hasattr(L, "irmv_engine_net_dims"):                        # (absent only in an older build loaded through IRMV_LIB_PATH)
@@ -215,6 +220,28 @@ class YoloEngine:
         out = np.empty((h, w, 3), np.uint8)
         capi.check(self._L.irmv_engine_rotated_image(self._h, slot, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
+
+    def set_bayer_isp(self, gains: Sequence[int], lut=None) -> None:
+        """Gains (R, G, B; Q8, 256 = 1.0) and tone LUT (uint8 [3][256], rows R, G, B, or [256] for all three; None = identity)
+        of a Bayer engine, from the next submit on: out = lut[c][min(255, (v * gain[c] + 128) >> 8)].  Blocks until every
+        step in flight has finished (irmv_engine_set_bayer_isp)."""
+        g = (C.c_uint16 * 3)(*[int(v) for v in gains])
+        p = None
+        if lut is not None:
+            t = np.asarray(lut)
+            if t.dtype != np.uint8 or t.shape not in ((256,), (3, 256)):
+                raise ValueError("lut must be a uint8 [256] or [3][256] array")
+            t = np.ascontiguousarray(np.broadcast_to(t, (3, 256)))
+            p = t.ctypes.data_as(C.POINTER(C.c_uint8))
+        capi.check(self._L.irmv_engine_set_bayer_isp(self._h, g, p))
+
+    @property
+    def bayer_isp(self):
+        """(gains, lut) as the engine holds them: three Q8 gains and the uint8 [3][256] LUT (identity where none is set)."""
+        g = (C.c_uint16 * 3)()
+        lut = np.empty((3, 256), np.uint8)
+        capi.check(self._L.irmv_engine_get_bayer_isp(self._h, g, lut.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return tuple(g), lut
 
     def extract_armors(self, bboxes, slot: Optional[int] = None) -> List[Armor]:
         """IrmDetector::extract_armors(get_rotated_image(), bboxes) (src/irm_detector.cpp:292-355) on the GPU,
