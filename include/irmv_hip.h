@@ -296,6 +296,10 @@ int irmv_engine_debug_poke_candidate_counts(irmv_engine *e, int value);
    (all zero between steps).  *sparse = 1 if this engine's steps store candidate head rows only (IRMV_SPARSE_HEAD=0, or a
    configuration without candidate emission: 0, and no words are kept: *n = 0).  words may be NULL to query *n. */
 int irmv_engine_debug_read_cand_bits(irmv_engine *e, int slot, uint32_t *words, int cap, int *n, int *sparse);
+/* Read-only (tests): the slot's head records as they lie in memory, with NO read-back step in front (read_head, read_tap and
+   read_tensor first bring a sparse head to the dense state): [num_anchors][96] floats, box 64 | classes at 64 | keypoints at
+   80; `bytes` must be num_anchors * 96 * 4.  After a step of a sparse engine only the rows the step stored are the step's. */
+int irmv_engine_debug_read_head_rows(irmv_engine *e, int slot, float *rec, size_t bytes);
 int irmv_engine_read_tap(irmv_engine *e, int slot, const char *name, float *nhwc, int shape[3]);   /* shape = {H, W, C}: a tensor of
                                                                                  level s is (net_h/s) x (net_w/s) */
 int irmv_engine_read_raw(irmv_engine *e, int slot, irmv_raw_dets *out);

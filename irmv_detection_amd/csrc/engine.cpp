@@ -3078,6 +3078,22 @@ extern "C" int irmv_engine_read_tensor(irmv_engine *e, const char *name, int fir
     return IRMV_OK;
 }
 
+extern "C" int irmv_engine_debug_read_head_rows(irmv_engine *e, int slot, float *rec, size_t bytes)
+{
+    TRY(check_range(e, slot, 1));
+    if (!rec || bytes != (size_t)e->A * kHeadRec * sizeof(float)) return fail(IRMV_ERR_ARG, "debug_read_head_rows: the buffer must hold num_anchors x 96 floats");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));
+    char *dst = reinterpret_cast<char *>(rec);
+    for (int l = 0; l < 3; l++) {   // (no ensure_dense_head: the rows as the last step or write_head left them)
+        const Tensor &t = e->tensors[e->head_t[l]];
+        const size_t n = t.slot_elems * t.esize();
+        HIP_TRY(hipMemcpy(dst, t.slot(slot), n, hipMemcpyDeviceToHost));
+        dst += n;
+    }
+    return IRMV_OK;
+}
+
 static int conv_op_at(const irmv_engine *e, int op)
 {
     if (!e) return fail(IRMV_ERR_ARG, "engine is null");

@@ -408,6 +408,13 @@ class YoloEngine:
                                                                  C.byref(n), C.byref(sparse)))
         return bool(sparse.value), words
 
+    def debug_head_rows(self, slot: int = 0) -> np.ndarray:
+        """The slot's head records as they lie in memory, no read-back step in front: [num_anchors, 96] float32, box 64 |
+        classes at 64 | keypoints at 80 (after a step of a sparse engine only the candidate anchors' rows are the step's)."""
+        out = np.empty((self.num_anchors, 96), np.float32)
+        capi.check(self._L.irmv_engine_debug_read_head_rows(self._h, slot, out.ctypes.data_as(C.POINTER(C.c_float)), out.nbytes))
+        return out
+
     def profile(self, first_slot: int = 0, count: Optional[int] = None) -> List[dict]:
         count = self.num_slots - first_slot if count is None else count
         stats = (capi.KernelStat * 256)()
