@@ -86,6 +86,8 @@ public:
     int device = -1;                                     // HIP device; -1: IRMV_DEVICE or 0
     cv::Size net_input_size{0, 0};                       // network input width x height; 0: the engine's default (square);
                                                          // height 0: square of the width (1280 x 1024 camera: 640 x 512)
+    cv::Size window_size{0, 0};                          // tracking window of the three engines (YoloEngine's `window`); 0: none.  No policy here:
+                                                         // the caller moves each engine's window (engine(id).set_window_center(...))
   };
 
   // What one frame produced, beyond the message: kept for debug publishers and tests.
@@ -104,7 +106,8 @@ public:
   {
     for (auto & e : yolo_engines_) {
       e = std::make_unique<YoloEngine>(model_path, p.image_input_size, p.profiling, p.device, false, p.net_input_size.width > 0 ? p.net_input_size.width : -1,
-                                       IRMV_SRC_HWC8, std::array<uint16_t, 3>{256, 256, 256}, p.net_input_size.height > 0 ? p.net_input_size.height : -1);
+                                       IRMV_SRC_HWC8, std::array<uint16_t, 3>{256, 256, 256}, p.net_input_size.height > 0 ? p.net_input_size.height : -1,
+                                       IRMV_DEMOSAIC_BILINEAR, p.window_size);
       push_params(*e);
     }
     yolo_engines_[0]->warm_up();   // the tile choices are shared by the three engines: one warm-up tunes for all

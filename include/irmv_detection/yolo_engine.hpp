@@ -16,12 +16,15 @@
 //    src/yolo_engine.cpp:38-39, but the file looked for is "<stem>.irmw".
 #pragma once
 
+#include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <iostream>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "irmv_detection/armor.hpp"
@@ -69,11 +72,15 @@ public:
   // `net_height` (-1 = square): the network input is net_size wide and net_height tall, e.g. 640 x 512 for the 1280 x 1024
   // camera (include/irmv_hip.h, irmv_engine_cfg::net_height); net_input_size() returns what the engine runs.
   // `bayer_demosaic` (IRMV_DEMOSAIC_*): the interpolation of a Bayer engine, bilinear or the 5 x 5 Malvar-He-Cutler filters.
+  // `window` ({} = none): a tracking window -- detect() runs on a window.width x window.height crop of the frame at the
+  // sensor's resolution (include/irmv_hip.h, irmv_engine_cfg::win_width).  src_image_size stays the full frame the producer
+  // writes and bboxes come back in its coordinates; set_window() / set_window_center() move the window between detect()
+  // calls; get_rotated_image() is then the rotated window.
   YoloEngine(const std::string & onnx_file_path, cv::Size src_image_size, bool enable_profiling = false, int device = -1,
              bool warm_up_now = true, int net_size = -1, int src_format = IRMV_SRC_HWC8,
              std::array<uint16_t, 3> bayer_gain_q8 = {256, 256, 256}, int net_height = -1,
-             int bayer_demosaic = IRMV_DEMOSAIC_BILINEAR)
-  : src_image_size_(src_image_size), enable_profiling_(enable_profiling)
+             int bayer_demosaic = IRMV_DEMOSAIC_BILINEAR, cv::Size window = {})
+  : src_image_size_(src_image_size), window_size_(window), enable_profiling_(enable_profiling)
   {
     irmv_engine_cfg cfg;
     irmv_engine_cfg_default(&cfg);
@@ -85,6 +92,8 @@ public:
     cfg.device = device >= 0 ? device : default_device();
     cfg.src_width = src_image_size.width;
     cfg.src_height = src_image_size.height;
+    cfg.win_width = window.width;
+    cfg.win_height = window.height;
     cfg.num_slots = 1;  // one engine per TripleBuffer slot, like the reference node
     cfg.weights_path = onnx_file_path.c_str();
     const int rc = irmv_engine_create(&cfg, &engine_);
@@ -94,7 +103,7 @@ public:
     }
     if (rc != IRMV_OK) throw std::runtime_error(std::string("YoloEngine: ") + irmv_last_error());
     src_image_buffer_ = irmv_engine_src_buffer(engine_, 0);
-    rotated_ = cv::Mat(src_image_size.height, src_image_size.width, CV_8UC3);
+    rotated_ = has_window() ? cv::Mat(window.height, window.width, CV_8UC3) : cv::Mat(src_image_size.height, src_image_size.width, CV_8UC3);
     dets_.resize(static_cast<size_t>(irmv_engine_max_det(engine_)));
     if (warm_up_now) warm_up();
   }
@@ -133,6 +142,32 @@ public:
     if (irmv_engine_set_bayer_isp(engine_, gain_q8.data(), lut) != IRMV_OK)
       throw std::runtime_error(std::string("YoloEngine::set_bayer_isp: ") + irmv_last_error());
     rotated_valid_ = false;
+  }
+
+  // ---- tracking window ----
+  bool has_window() const { return window_size_.width > 0 && window_size_.height > 0; }
+  // The window's top-left corner in the coordinates bboxes come back in (the rotated frame); from the next detect() on.
+  void set_window(cv::Point top_left)
+  {
+    if (irmv_engine_set_window(engine_, 0, top_left.x, top_left.y) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::set_window: ") + irmv_last_error());
+    rotated_valid_ = false;
+  }
+  // Centre the window on a point -- the last detection's box centre --, clamped into the frame.  Returns the corner it set.
+  cv::Point set_window_center(cv::Point2f center)
+  {
+    const int x0 = std::clamp(static_cast<int>(std::floor(center.x - window_size_.width / 2.0 + 0.5)), 0, src_image_size_.width - window_size_.width);
+    const int y0 = std::clamp(static_cast<int>(std::floor(center.y - window_size_.height / 2.0 + 0.5)), 0, src_image_size_.height - window_size_.height);
+    set_window(cv::Point(x0, y0));
+    return cv::Point(x0, y0);
+  }
+  // The current window as (top-left corner, size)
+  std::pair<cv::Point, cv::Size> window() const
+  {
+    int x0 = 0, y0 = 0, w = 0, h = 0;
+    if (irmv_engine_get_window(engine_, 0, &x0, &y0, &w, &h) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::window: ") + irmv_last_error());
+    return {cv::Point(x0, y0), cv::Size(w, h)};
   }
 
   ~YoloEngine() { irmv_engine_destroy(engine_); }
@@ -280,6 +315,7 @@ private:
 
   irmv_engine * engine_ = nullptr;
   cv::Size src_image_size_;
+  cv::Size window_size_;
   bool enable_profiling_ = false;
   uint8_t * src_image_buffer_ = nullptr;
   mutable cv::Mat rotated_;

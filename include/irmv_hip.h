@@ -138,6 +138,20 @@ typedef struct irmv_engine_cfg {
      * For W == H this is exactly the square arithmetic. */
     int32_t net_height;
     int32_t reserved2;
+    /* Appended after those, into what was the struct's tail padding: sizeof(irmv_engine_cfg) is what it was without them, so a
+     * caller built against that header passes the same struct_size and whatever its padding bytes hold -- zeros, since every
+     * caller fills the struct with irmv_engine_cfg_default first (which clears all of it).  Anything else there is refused as
+     * a bad window, never run.  The two older struct sizes get 0, 0.
+     * Tracking window: run the step on a win_width x win_height crop of the camera frame, at the sensor's resolution.  Both 0
+     * (default): no window.  Otherwise 1 <= win_width <= src_width and 1 <= win_height <= src_height.  src_width x src_height
+     * stays the full frame -- what a producer writes, what irmv_engine_src_bytes / _src_buffer / _src_device_buffer describe
+     * and IRMV_MAX_FRAME_BYTES bounds -- and the first kernel of every step (the second of a Bayer engine, behind the
+     * demosaic of the whole frame) cuts the slot's window out of it.  Everything downstream sees win_width x win_height where
+     * it saw src_width x src_height: the resize or letterbox into the net input, irmv_front_plan (src_width % 4 now asks it of
+     * win_width), the light extraction, irmv_engine_rotated_image.  Where the window lies is per-slot state, moved with
+     * irmv_engine_set_window without re-capturing anything; at creation every slot's window is centred.  Detections come
+     * back in full-frame coordinates; PnP sees the window's pixels with the principal point moved by the corner. */
+    int16_t win_width, win_height;
 } irmv_engine_cfg;
 
 /* One detection: YoloEngine::bbox (yolo_engine.hpp:19-26) in source-frame
@@ -219,6 +233,25 @@ uint8_t *irmv_engine_src_buffer(irmv_engine *e, int slot);
 /* Device-side staging of the same slot, in the same format (for producers that already hold the frame in HBM -- a Bayer
  * producer writes the raw frame here and submits without IRMV_SUBMIT_H2D -- and for HBM-resident benchmarking). */
 void *irmv_engine_src_device_buffer(irmv_engine *e, int slot);
+/* ---- tracking window (irmv_engine_cfg.win_width / win_height) ----
+ * (x0, y0): the window's top-left corner in the coordinates detections come back in -- the rotated frame when rotate180 = 1,
+ * the frame a tracker sees.  The call waits until the slot's last submitted step is done, then writes the slot's corner and
+ * shifted camera into device memory; it takes effect from the slot's next submit, and no captured graph changes.  Results
+ * read later with irmv_engine_results still carry the corner their step was submitted with.
+ * IRMV_ERR_ARG: null engine, an engine without a window, a slot out of range, a window not inside the frame. */
+int irmv_engine_set_window(irmv_engine *e, int slot, int x0, int y0);
+/* The slot's current corner and the window's size (any pointer may be NULL). */
+int irmv_engine_get_window(const irmv_engine *e, int slot, int *x0, int *y0, int *w, int *h);
+/* Host only: where a window at (x0, y0) lies -- the function the engine itself builds from.  cfg must have a window. */
+typedef struct irmv_window_map_t {
+    int32_t bx0, by0;        /* the corner in buffer coordinates: rotate180 ? src_width - x0 - win_width : x0, likewise y */
+    uint64_t band_offset;    /* the full-width rows the window covers, as bytes of an HWC frame: by0 * src_width * 3 ... */
+    uint64_t band_bytes;     /* ... and win_height * src_width * 3 (what a band upload moves) */
+    double cx, cy;           /* the principal point of the window's pixels: camera_matrix[2] - x0, camera_matrix[5] - y0 */
+    int32_t reserved[4];
+} irmv_window_map_t;
+int irmv_window_map(const irmv_engine_cfg *cfg, int x0, int y0, irmv_window_map_t *out);
+
 int irmv_engine_src_format(const irmv_engine *e);      /* IRMV_SRC_* of this engine; -1 for a null engine */
 size_t irmv_engine_src_bytes(const irmv_engine *e);    /* bytes of one source slot (host and device); 0 for a null engine */
 
@@ -254,7 +287,8 @@ double irmv_engine_last_detect_ms(const irmv_engine *e);
 /* 180-degree rotated frame of a slot (what get_rotated_image() aliases after the
  * in-place mirror, src/yolo_engine.cpp:77-78,182-184), rotated on the GPU.  dst_hwc
  * receives src_height*src_width*3 bytes in every format: a Bayer engine uploads the
- * raw slot, demosaics it and returns the rotated R, G, B frame. */
+ * raw slot, demosaics it and returns the rotated R, G, B frame.  A window engine
+ * returns the rotated window: win_height*win_width*3 bytes. */
 int irmv_engine_rotated_image(irmv_engine *e, int slot, uint8_t *dst_hwc);
 
 /* The gains and tone curve of a Bayer engine, changeable while it lives (the camera SDK's ISP retuned per venue):
@@ -272,7 +306,8 @@ int irmv_engine_get_bayer_isp(const irmv_engine *e, uint16_t gain_q8[3], uint8_t
 
 /* IrmDetector::extract_armors(get_rotated_image(), bboxes) (src/irm_detector.cpp:183,292-355) on the GPU:
  * for each of the n boxes (xyxy, rotated-frame pixels) on the slot's current frame -> out[i].kpts (LB, LT, RT,
- * RB), armor_valid, armor_size, n_lights, and the PnP pose.  Works for any model / point_source. */
+ * RB), armor_valid, armor_size, n_lights, and the PnP pose.  Works for any model / point_source.  A window engine takes the
+ * boxes and returns kpts in the full frame's coordinates and looks at the slot's current window. */
 int irmv_engine_extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, irmv_det *out);
 /* The node's live parameters of that extraction (IrmDetector::param_event_callback, src/irm_detector.cpp:372-403):
  * binary_threshold, light.{min_ratio,max_ratio,max_angle}, armor.{min_small,max_small,min_large,max_large}_center_distance.
@@ -360,7 +395,7 @@ int irmv_engine_read_tensor(irmv_engine *e, const char *name, int first_slot, in
  * Every op of the engine's graph, of any kind; the non-conv layer ops run one at a time on a slot range. */
 typedef struct irmv_graph_op {
     int32_t op;                 /* the engine's op index (the `op` of irmv_engine_run_op and of the conv hooks above) */
-    char kind[16];              /* conv conv0 pool dw shuffle front c2f2 c2f32 bneck kpt3 pre demosaic scan nms light */
+    char kind[16];              /* conv conv0 pool dw shuffle front c2f2 c2f32 bneck kpt3 pre demosaic crop scan nms light */
     char layer[48];             /* weight layer, or the op's own name (model.9.m, model.N.shuffle, preprocess, ...) */
     char kname[48];             /* kernel, as irmv_engine_profile names it */
     irmv_conv_seg s0, s1;       /* inputs (tensor "" = none; the pool's: channels [0, C) of its own tensor) */

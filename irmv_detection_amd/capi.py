@@ -48,6 +48,7 @@ class EngineCfg(C.Structure):
         ("armor_min_large_center_distance", C.c_double), ("armor_max_large_center_distance", C.c_double),
         ("src_format", C.c_int32), ("bayer_gain_q8", C.c_uint16 * 3), ("bayer_demosaic", C.c_uint16),
         ("net_height", C.c_int32), ("reserved2", C.c_int32),   # net_height 0: square net_size x net_size input
+        ("win_width", C.c_int16), ("win_height", C.c_int16),   # tracking window; 0, 0: none (the struct's former tail padding)
     ]
 
 
@@ -118,6 +119,12 @@ class FrontPlan(C.Structure):
                 ("max_pitch", C.c_int32), ("max_rows", C.c_int32), ("upload_kernel", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class WindowMap(C.Structure):
+    """irmv_window_map_t (include/irmv_hip.h)."""
+    _fields_ = [("bx0", C.c_int32), ("by0", C.c_int32), ("band_offset", C.c_uint64), ("band_bytes", C.c_uint64),
+                ("cx", C.c_double), ("cy", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
 class LightRec(C.Structure):
     _fields_ = [("corners", C.c_float * 8), ("top", C.c_float * 2), ("bottom", C.c_float * 2), ("center", C.c_float * 2),
                 ("length", C.c_double), ("measured", C.c_int32), ("ok", C.c_int32), ("hull_edges", C.c_int32), ("in_lds", C.c_int32)]
@@ -158,6 +165,9 @@ SYMBOLS = [
     ("irmv_numa_parse_cpulist", C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.c_int]),
     ("irmv_engine_src_buffer", C.POINTER(C.c_uint8), [_P, C.c_int]),
     ("irmv_engine_src_device_buffer", C.c_void_p, [_P, C.c_int]),
+    ("irmv_engine_set_window", C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    ("irmv_engine_get_window", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("irmv_window_map", C.c_int, [C.POINTER(EngineCfg), C.c_int, C.c_int, C.POINTER(WindowMap)]),
     ("irmv_engine_src_format", C.c_int, [_P]),
     ("irmv_engine_src_bytes", C.c_size_t, [_P]),
     ("irmv_engine_submit", C.c_int, [_P, C.c_int, C.c_int, C.c_uint32]),
@@ -274,16 +284,35 @@ def light_limits() -> dict:
     return dict(max_contours=v[0], points_cap=v[1], lds_image=v[2], lds_points=v[3])
 
 
-def front_plan(src_size, net_size, net_height=None, resize_mode=RESIZE_STRETCH, rotate180=True, src_format=SRC_HWC8) -> dict:
-    """The front's plan for a configuration (host only, irmv_front_plan): what irmv_engine_create decides from the same
-    fields.  Raises IrmvError where the engine's validation refuses them."""
-    L = load()
+def _geometry_cfg(src_size, net_size, net_height, resize_mode, rotate180, src_format, window) -> EngineCfg:
     cfg = EngineCfg()
-    L.irmv_engine_cfg_default(C.byref(cfg))
+    load().irmv_engine_cfg_default(C.byref(cfg))
     cfg.src_width, cfg.src_height = int(src_size[0]), int(src_size[1])
     cfg.net_size, cfg.net_height = int(net_size), 0 if net_height is None else int(net_height)
     cfg.resize_mode, cfg.rotate180 = int(resize_mode), int(bool(rotate180))
     cfg.src_format = BAYER_FORMATS[src_format.upper()] if isinstance(src_format, str) else int(src_format)
+    if window is not None:
+        cfg.win_width, cfg.win_height = int(window[0]), int(window[1])
+    return cfg
+
+
+def window_map(src_size, window, x0, y0, rotate180=True, camera_matrix=None, net_size=640, net_height=None) -> dict:
+    """Where a window at (x0, y0) lies (host only, irmv_window_map): the corner in buffer coordinates, the band of
+    full-width rows it covers and the shifted principal point, as the engine computes them."""
+    cfg = _geometry_cfg(src_size, net_size, net_height, RESIZE_STRETCH, rotate180, SRC_HWC8, window)
+    if camera_matrix is not None:
+        for i, v in enumerate(camera_matrix):
+            cfg.camera_matrix[i] = float(v)
+    m = WindowMap()
+    check(load().irmv_window_map(C.byref(cfg), int(x0), int(y0), C.byref(m)))
+    return dict(bx0=m.bx0, by0=m.by0, band_offset=m.band_offset, band_bytes=m.band_bytes, cx=m.cx, cy=m.cy)
+
+
+def front_plan(src_size, net_size, net_height=None, resize_mode=RESIZE_STRETCH, rotate180=True, src_format=SRC_HWC8, window=None) -> dict:
+    """The front's plan for a configuration (host only, irmv_front_plan): what irmv_engine_create decides from the same
+    fields.  Raises IrmvError where the engine's validation refuses them.  window = (w, h): the plan of a window engine."""
+    L = load()
+    cfg = _geometry_cfg(src_size, net_size, net_height, resize_mode, rotate180, src_format, window)
     p = FrontPlan()
     check(L.irmv_front_plan(C.byref(cfg), C.byref(p)))
     d = {f: getattr(p, f) for f, _ in FrontPlan._fields_ if f not in ("box", "reserved")}

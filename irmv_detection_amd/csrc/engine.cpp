@@ -156,7 +156,7 @@ struct TuneSwitches {
     bool no_pw, no_pwn, no_pf2, no_pf4, no_cm, no_w8, no_nt8, no_wres, no_deep;
 };
 
-enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_DEMOSAIC };
+enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_DEMOSAIC, OP_CROP };
 
 struct Op {
     OpKind kind;
@@ -274,6 +274,19 @@ struct irmv_engine {
     uint16_t isp_gain[3] = {256, 256, 256};
     uint8_t isp_lut[kBayerTableBytes] = {0};
     uint8_t *rot_dev = nullptr;   // [frame]
+    // Tracking window (irmv_engine_cfg.win_width / win_height): cfg.src_width x cfg.src_height is then the WINDOW -- what every
+    // kernel behind the crop sees as its source frame -- and full_w x full_h the frame the producer writes.  OP_CROP cuts the
+    // window at win_dev[slot] out of the slot's full frame (full_dev, or the pinned slot itself) into its src_dev frame.
+    // Without a window full_w x full_h equals the cfg's source size and none of the rest exists.
+    bool window = false;
+    int full_w = 0, full_h = 0;
+    size_t full_bytes = 0;            // one full HWC frame (full_dev)
+    uint8_t *full_dev = nullptr;      // [S][full frame]: what an HWC window engine's uploads and a Bayer one's demosaic write
+    int2 *win_dev = nullptr;          // [S] the windows' corners in buffer coordinates, read by window_crop_kernel when it runs
+    std::vector<int2> win_org;        // [S] the corners as set, in result coordinates (the rotated frame under rotate180)
+    std::vector<int2> sub_org;        // [S] ... as they were at the slot's last submit: what its results are shifted by
+    bool window_upload = true;        // synchronous steps of one or two slots crop straight out of the pinned slot (IRMV_WINDOW_UPLOAD=0: upload, then crop)
+    PnpConst pnp_base{};              // the camera as configured; pnp_dev[slot] = pnp_base with the principal point moved by the slot's corner
     AxisTap *tap_x = nullptr, *tap_y = nullptr;
     std::vector<Tensor> tensors;
     std::map<std::string, int> tensor_idx;
@@ -908,6 +921,7 @@ static void front_plan(const irmv_engine_cfg &c, const FrontSwitches &sw, irmv_f
 }
 
 static int autotune_convs(irmv_engine *e);
+static int write_window(irmv_engine *e, int slot);
 static void finalize_head_fusion(irmv_engine *e);
 static int build_head_groups(irmv_engine *e);
 static void build_step_plans(irmv_engine *e);
@@ -947,7 +961,8 @@ static int build_engine(irmv_engine *e)
     e->slot_owner.assign(S, nullptr);
     e->frame_bytes = (size_t)c.src_width * c.src_height * 3;
     const bool bayer = c.src_format != IRMV_SRC_HWC8;
-    e->src_bytes = bayer ? (size_t)c.src_width * c.src_height : e->frame_bytes;
+    e->full_bytes = (size_t)e->full_w * e->full_h * 3;   // (= frame_bytes without a window)
+    e->src_bytes = bayer ? (size_t)e->full_w * e->full_h : e->full_bytes;
     {
         // NUMA-local frame slots (SURVEY section 7 "hard parts": on a full node the copy engines read 8 x 14 k FPS x 3.93 MB =
         // 440 GB/s of host memory): the creating thread runs on the CPUs of the GPU's own socket and prefers its memory while
@@ -967,14 +982,20 @@ static int build_engine(irmv_engine *e)
     TRY(dev_alloc(e, (void **)&e->src_dev, e->frame_bytes * S));
     HIP_TRY(hipMemset(e->src_dev, 0, e->frame_bytes * S));
     TRY(dev_alloc(e, (void **)&e->rot_dev, e->frame_bytes));
+    if (e->window) {
+        TRY(dev_alloc(e, (void **)&e->full_dev, e->full_bytes * S));
+        HIP_TRY(hipMemset(e->full_dev, 0, e->full_bytes * S));
+        TRY(dev_alloc(e, (void **)&e->win_dev, sizeof(int2) * S));
+        { const char *wu = getenv("IRMV_WINDOW_UPLOAD"); e->window_upload = !(wu && wu[0] == '0'); }
+    }
     if (bayer) {
         TRY(dev_alloc(e, (void **)&e->raw_dev, e->src_bytes * S));
         HIP_TRY(hipMemset(e->raw_dev, 0, e->src_bytes * S));
         // phase of the R sites: IRMV_SRC_BAYER_{RGGB, BGGR, GRBG, GBRG}8 -> R at (0,0), (1,1), (0,1), (1,0)
         static const int ry[4] = {0, 1, 0, 1}, rx[4] = {0, 1, 1, 0};
         BayerArgs &b = e->bayer;
-        b.raw_slot_bytes = e->src_bytes; b.dst_slot_bytes = e->frame_bytes;
-        b.W = c.src_width; b.H = c.src_height;
+        b.raw_slot_bytes = e->src_bytes; b.dst_slot_bytes = e->full_bytes;
+        b.W = e->full_w; b.H = e->full_h;
         b.ry = ry[c.src_format - 1]; b.rx = rx[c.src_format - 1];
         for (int i = 0; i < 3; i++) b.gain[i] = c.bayer_gain_q8[i];
         for (int i = 0; i < 3; i++) e->isp_gain[i] = c.bayer_gain_q8[i];
@@ -1036,7 +1057,12 @@ static int build_engine(irmv_engine *e)
 
     if (bayer) {   // raw slot -> src_dev: the first op of every step (not of run_post, not of a read-back's materialisation)
         Op op; op.kind = OP_DEMOSAIC; op.layer = "demosaic"; snprintf(op.kname, sizeof op.kname, "%s", demosaic_kname(e));
-        op.bytes = (double)e->src_bytes + (double)e->frame_bytes;
+        op.bytes = (double)e->src_bytes + (double)e->full_bytes;
+        e->ops.push_back(op);
+    }
+    if (e->window) {   // the slot's window -> src_dev: behind the demosaic, in front of everything else (like it, not part of run_post or a read-back)
+        Op op; op.kind = OP_CROP; op.layer = "window_crop"; snprintf(op.kname, sizeof op.kname, "window_crop");
+        op.bytes = 2.0 * (double)e->frame_bytes;
         e->ops.push_back(op);
     }
     const size_t conv0_op = e->ops.size() + 1;   // (OP_PRE, then OP_CONV0)
@@ -1077,7 +1103,7 @@ static int build_engine(irmv_engine *e)
             op.flops = e->ops[conv0_op].flops + m1.flops;
             op.bytes = (double)e->frame_bytes + (double)h4 * w4 * 32 * 2;
             op.w_packed = m1.w_packed; op.bias = m1.bias; op.out_t = m1.out_t;
-            for (Op &o : e->ops) o.fused_away = o.kind != OP_DEMOSAIC;   // preprocess, model.0.conv, model.1.conv
+            for (Op &o : e->ops) o.fused_away = o.kind != OP_DEMOSAIC && o.kind != OP_CROP;   // preprocess, model.0.conv, model.1.conv
             e->lazy_tensors.insert("input"); e->lazy_tensors.insert("0");
             e->ops.push_back(op);
         }
@@ -1316,9 +1342,16 @@ static int build_engine(irmv_engine *e)
     pc.p2 = c.dist_coeffs[3]; pc.k3 = c.dist_coeffs[4];
     pc.hy[0] = 135.0 / 2.0 / 1000.0; pc.hy[1] = 225.0 / 2.0 / 1000.0;   // src/pnp_solver.cpp:18-21
     pc.hz[0] = pc.hz[1] = 55.0 / 2.0 / 1000.0;
-    TRY(dev_alloc(e, (void **)&e->pnp_dev, sizeof(PnpConst)));
+    e->pnp_base = pc;
+    TRY(dev_alloc(e, (void **)&e->pnp_dev, sizeof(PnpConst) * (e->window ? S : 1)));
     HIP_TRY(hipMemcpy(e->pnp_dev, &pc, sizeof pc, hipMemcpyHostToDevice));
     p.pnp = e->pnp_dev;
+    p.pnp_stride = e->window ? 1 : 0;
+    if (e->window) {   // every slot's window starts centred
+        e->win_org.assign(S, int2{(e->full_w - c.src_width) / 2, (e->full_h - c.src_height) / 2});
+        e->sub_org = e->win_org;
+        for (int s = 0; s < S; s++) TRY(write_window(e, s));
+    }
     p.dbg = nullptr;
     if (getenv("IRMV_NMS_STAMPS")) {
         TRY(dev_alloc(e, (void **)&e->dbg_dev, (size_t)S * 16 * sizeof(long long)));
@@ -1466,6 +1499,18 @@ constexpr size_t kCfgSizeV1 = offsetof(irmv_engine_cfg, src_format);
 // ... and before net_height: that header's sizeof.  net_height sits in its tail padding, so those bytes are never read.
 constexpr size_t kCfgSizeV2 = offsetof(irmv_engine_cfg, reserved2);
 static_assert(offsetof(irmv_engine_cfg, net_height) < kCfgSizeV2 && kCfgSizeV2 < sizeof(irmv_engine_cfg), "three distinct cfg sizes");
+// The tracking window's two fields lie in what was the tail padding of the struct: its size is the one it had before them.
+static_assert(offsetof(irmv_engine_cfg, win_width) == offsetof(irmv_engine_cfg, reserved2) + 4 && offsetof(irmv_engine_cfg, win_height) + 2 == sizeof(irmv_engine_cfg),
+              "win_width / win_height fill the tail of irmv_engine_cfg");
+
+// What everything behind the crop is built from: the configuration whose source frame is the window (itself without one).
+static irmv_engine_cfg window_view(const irmv_engine_cfg &c)
+{
+    irmv_engine_cfg v = c;
+    if (c.win_width > 0 && c.win_height > 0) { v.src_width = c.win_width; v.src_height = c.win_height; }
+    v.win_width = v.win_height = 0;
+    return v;
+}
 
 // The caller's configuration at this library's size (an older caller's prefix, the appended fields at their defaults),
 // and the checks of everything the front's geometry follows from.  No GPU call.
@@ -1473,7 +1518,7 @@ static int resolve_cfg(const irmv_engine_cfg *cfg_in, irmv_engine_cfg *full)
 {
     const size_t sz = cfg_in->struct_size;
     if (sz != sizeof(irmv_engine_cfg) && sz != kCfgSizeV1 && sz != kCfgSizeV2) return fail(IRMV_ERR_ARG, "irmv_engine_cfg size mismatch");
-    if (sz != sizeof(irmv_engine_cfg)) {
+    if (sz != sizeof(irmv_engine_cfg)) {   // (the defaults include: no window)
         irmv_engine_cfg_default(full);
         memcpy(full, cfg_in, sz == kCfgSizeV1 ? kCfgSizeV1 : offsetof(irmv_engine_cfg, net_height));
         full->struct_size = sizeof *full;
@@ -1502,9 +1547,14 @@ static int resolve_cfg(const irmv_engine_cfg *cfg_in, irmv_engine_cfg *full)
     // and the light extraction index with size_t; the demosaic's int counts bytes of one band of rows.)
     if ((uint64_t)cfg->src_width * (uint64_t)cfg->src_height * 3u > IRMV_MAX_FRAME_BYTES)
         return fail(IRMV_ERR_ARG, "src frame too large: 3 * src_width * src_height must not exceed 4294967296 bytes (32-bit byte offsets into a frame)");
+    // The tracking window: both 0 = none.  src_width x src_height stays the full frame (what the checks above bound); the
+    // letterbox below, like everything behind the crop, sees the window.
+    if (cfg->win_width < 0 || cfg->win_width > cfg->src_width) return fail(IRMV_ERR_ARG, "win_width must be 0 (no window) or in [1, src_width]");
+    if (cfg->win_height < 0 || cfg->win_height > cfg->src_height) return fail(IRMV_ERR_ARG, "win_height must be 0 (no window) or in [1, src_height]");
+    if ((cfg->win_width == 0) != (cfg->win_height == 0)) return fail(IRMV_ERR_ARG, "win_width and win_height must both be 0 (no window) or both be set");
     {   // a source so oblong that the short side of its letterboxed frame rounds to nothing: no box, no scale back to the source
         int nw, nh;
-        scaled_size(*cfg, &nw, &nh);
+        scaled_size(window_view(*cfg), &nw, &nh);
         if (nw < 1 || nh < 1) return fail(IRMV_ERR_ARG, "letterbox: the scaled frame has no row or no column; use IRMV_RESIZE_STRETCH");
     }
     return IRMV_OK;
@@ -1516,7 +1566,7 @@ extern "C" int irmv_front_plan(const irmv_engine_cfg *cfg_in, irmv_front_plan_t 
     irmv_engine_cfg full;
     if (int rc = resolve_cfg(cfg_in, &full)) return rc;
     std::vector<AxisTap> tx, ty;
-    front_plan(full, FrontSwitches{}, out, tx, ty);
+    front_plan(window_view(full), FrontSwitches{}, out, tx, ty);
     return IRMV_OK;
 }
 
@@ -1536,7 +1586,9 @@ extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **o
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (cfg->device < 0 || cfg->device >= ndev) return fail(IRMV_ERR_HIP, "no such HIP device");
     std::unique_ptr<irmv_engine> e(new irmv_engine);
-    e->cfg = *cfg;
+    e->cfg = window_view(*cfg);   // from here on: src_width x src_height = the window, where there is one
+    e->window = cfg->win_width > 0;
+    e->full_w = cfg->src_width; e->full_h = cfg->src_height;
     if (e->cfg.net_height == 0) e->cfg.net_height = e->cfg.net_size;   // from here on: net_size = width, net_height = height
     {
         int cus = 0;
@@ -1602,7 +1654,8 @@ extern "C" int irmv_numa_parse_cpulist(const char *s, int *cpus, int cap)
 extern "C" int irmv_engine_head_channels(const irmv_engine *e) { return e ? e->no : 0; }
 
 // the device memory an upload of the source slots writes: the raw slots of a Bayer engine, else the HWC frames themselves
-static uint8_t *upload_dev(const irmv_engine *e) { return e->raw_dev ? e->raw_dev : e->src_dev; }
+// (a window engine's full frames)
+static uint8_t *upload_dev(const irmv_engine *e) { return e->raw_dev ? e->raw_dev : (e->window ? e->full_dev : e->src_dev); }
 
 extern "C" uint8_t *irmv_engine_src_buffer(irmv_engine *e, int slot)
 {
@@ -1616,6 +1669,70 @@ extern "C" void *irmv_engine_src_device_buffer(irmv_engine *e, int slot)
 }
 extern "C" int irmv_engine_src_format(const irmv_engine *e) { return e ? e->cfg.src_format : -1; }
 extern "C" size_t irmv_engine_src_bytes(const irmv_engine *e) { return e ? e->src_bytes : 0; }
+
+// ---- tracking window ----------------------------------------------------------------
+// A window at (x0, y0) in result coordinates: where it lies in the buffer, the band of full-width rows it covers, and the
+// principal point its pixels are seen with.  The one place this arithmetic lives (irmv_window_map exports it).
+static int window_map(int full_w, int full_h, int win_w, int win_h, int rotate180, const double K[9], int x0, int y0, irmv_window_map_t *m)
+{
+    if (x0 < 0 || y0 < 0 || x0 > full_w - win_w || y0 > full_h - win_h) return fail(IRMV_ERR_ARG, "the window does not lie inside the frame");
+    memset(m, 0, sizeof *m);
+    m->bx0 = rotate180 ? full_w - x0 - win_w : x0;
+    m->by0 = rotate180 ? full_h - y0 - win_h : y0;
+    m->band_offset = (uint64_t)m->by0 * (uint64_t)full_w * 3u;
+    m->band_bytes = (uint64_t)win_h * (uint64_t)full_w * 3u;
+    m->cx = K[2] - (double)x0;
+    m->cy = K[5] - (double)y0;
+    return IRMV_OK;
+}
+
+extern "C" int irmv_window_map(const irmv_engine_cfg *cfg_in, int x0, int y0, irmv_window_map_t *out)
+{
+    if (!cfg_in || !out) return fail(IRMV_ERR_ARG, "cfg/out is null");
+    irmv_engine_cfg full;
+    if (int rc = resolve_cfg(cfg_in, &full)) return rc;
+    if (full.win_width == 0) return fail(IRMV_ERR_ARG, "irmv_window_map: the configuration has no window (win_width, win_height)");
+    return window_map(full.src_width, full.src_height, full.win_width, full.win_height, full.rotate180, full.camera_matrix, x0, y0, out);
+}
+
+// The slot's entries of the two device tables from e->win_org[slot].  The caller has made sure no step of the slot is in flight.
+static int write_window(irmv_engine *e, int slot)
+{
+    irmv_window_map_t m;
+    TRY(window_map(e->full_w, e->full_h, e->cfg.src_width, e->cfg.src_height, e->cfg.rotate180, e->cfg.camera_matrix, e->win_org[slot].x, e->win_org[slot].y, &m));
+    const int2 b{m.bx0, m.by0};
+    PnpConst pc = e->pnp_base;
+    pc.cx = m.cx; pc.cy = m.cy;
+    HIP_TRY(hipMemcpy(e->win_dev + slot, &b, sizeof b, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->pnp_dev + slot, &pc, sizeof pc, hipMemcpyHostToDevice));
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_wait_slots(irmv_engine *e, int first, int count);
+extern "C" int irmv_engine_set_window(irmv_engine *e, int slot, int x0, int y0)
+{
+    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
+    if (!e->window) return fail(IRMV_ERR_ARG, "irmv_engine_set_window: the engine has no window (win_width, win_height)");
+    if (slot < 0 || slot >= e->cfg.num_slots) return fail(IRMV_ERR_ARG, "slot out of range");
+    irmv_window_map_t m;
+    TRY(window_map(e->full_w, e->full_h, e->cfg.src_width, e->cfg.src_height, e->cfg.rotate180, e->cfg.camera_matrix, x0, y0, &m));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait_slots(e, slot, 1));   // the slot's last step has read both tables
+    e->win_org[slot] = int2{x0, y0};
+    return write_window(e, slot);
+}
+
+extern "C" int irmv_engine_get_window(const irmv_engine *e, int slot, int *x0, int *y0, int *w, int *h)
+{
+    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
+    if (!e->window) return fail(IRMV_ERR_ARG, "irmv_engine_get_window: the engine has no window (win_width, win_height)");
+    if (slot < 0 || slot >= e->cfg.num_slots) return fail(IRMV_ERR_ARG, "slot out of range");
+    if (x0) *x0 = e->win_org[slot].x;
+    if (y0) *y0 = e->win_org[slot].y;
+    if (w) *w = e->cfg.src_width;
+    if (h) *h = e->cfg.src_height;
+    return IRMV_OK;
+}
 
 // tile choices already measured in this process, keyed by layer shape and batch (engines are created
 // repeatedly in tests and by multi-slot nodes; the kernels and the device do not change in between)
@@ -2209,6 +2326,7 @@ static LightArgs light_args(const irmv_engine *e, int first)
     a.min_small_cd = c.armor_min_small_center_distance; a.max_small_cd = c.armor_max_small_center_distance;
     a.min_large_cd = c.armor_min_large_center_distance; a.max_large_cd = c.armor_max_large_center_distance;
     a.pnp = e->pnp_dev;
+    a.first = first; a.pnp_stride = e->post.pnp_stride;
     a.pnp_armor_size = c.armor_size;
     return a;
 }
@@ -2216,7 +2334,7 @@ static LightArgs light_args(const irmv_engine *e, int first)
 static BayerArgs bayer_args(const irmv_engine *e, int first)   // a Bayer engine's demosaic of its raw slots from `first` on
 {
     BayerArgs a = e->bayer;
-    a.raw = e->raw_dev + (size_t)first * e->src_bytes; a.dst = e->src_dev + (size_t)first * e->frame_bytes;
+    a.raw = e->raw_dev + (size_t)first * e->src_bytes; a.dst = (e->window ? e->full_dev : e->src_dev) + (size_t)first * e->full_bytes;
     return a;
 }
 
@@ -2224,6 +2342,17 @@ static void launch_bayer(const irmv_engine *e, int first, int count, hipStream_t
 {
     if (e->bayer_table) launch_demosaic_table(bayer_args(e, first), e->isp_table_dev, e->bayer_mhc, count, s);
     else launch_demosaic(bayer_args(e, first), count, s);
+}
+
+// The crop of slots [first, first + count): out of their device frames, or (pinned) out of the pinned slots themselves.
+static void launch_crop(const irmv_engine *e, int first, int count, bool pinned, hipStream_t s)
+{
+    CropArgs a{};
+    a.src = pinned ? e->src_host_dev : e->full_dev; a.src_slot_bytes = e->full_bytes;
+    a.dst = e->src_dev; a.dst_slot_bytes = e->frame_bytes;
+    a.win = e->win_dev; a.first = first;
+    a.full_w = e->full_w; a.full_h = e->full_h; a.win_w = e->cfg.src_width; a.win_h = e->cfg.src_height;
+    launch_window_crop(a, count, s);
 }
 
 static PostArgs post_args(const irmv_engine *e, int first)
@@ -2315,7 +2444,7 @@ static void launch_graph_op(irmv_engine *e, const Op &op, int first, int count, 
 
 // Enqueue a step of kind `kind` on slots [first, first + count), stream s: the launches of e->plans[kind], in order.
 // ev != nullptr (irmv_engine_profile): one event pair per launch, around `reps` repetitions of it (one if it is `once`).
-static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipStream_t s, int reps, std::vector<EvRec> *ev)
+static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipStream_t s, int reps, std::vector<EvRec> *ev, bool crop_pinned = false)
 {
     const int net_w = e->cfg.net_size, net_h = e->cfg.net_height;
     const PostArgs pa = post_args(e, first);
@@ -2331,6 +2460,7 @@ static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hip
         for (int rep = 0; rep < n; rep++)
         switch (op.kind) {
         case OP_DEMOSAIC: launch_bayer(e, first, count, s); break;
+        case OP_CROP: launch_crop(e, first, count, crop_pinned, s); break;
         case OP_PRE: {
             PreArgs a;
             a.src = e->src_dev + (size_t)first * e->frame_bytes;
@@ -2441,8 +2571,20 @@ static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hip
 }
 
 // Frame upload and result download: plain async copies, pinned memory both ways, on the streams submit_group() picks.
-static int copy_in(irmv_engine *e, int first, int count, hipStream_t st)
+// bands (never inside a stream capture, whose copy parameters are baked): an HWC window engine moves, for groups of up to 8
+// slots, only the band of full-width rows each slot's window covers -- one 1-D copy per slot, to the same offset of its device frame.
+constexpr int kBandUploadMaxSlots = 8;
+static int copy_in(irmv_engine *e, int first, int count, hipStream_t st, bool bands = false)
 {
+    if (bands && e->window && !e->raw_dev && count <= kBandUploadMaxSlots) {
+        const size_t pitch = (size_t)e->full_w * 3, len = (size_t)e->cfg.src_height * pitch;
+        for (int s = first; s < first + count; s++) {
+            const int by0 = e->cfg.rotate180 ? e->full_h - e->win_org[s].y - e->cfg.src_height : e->win_org[s].y;
+            const size_t off = (size_t)s * e->src_bytes + (size_t)by0 * pitch;
+            HIP_TRY(hipMemcpyAsync(e->full_dev + off, e->src_host + off, len, hipMemcpyHostToDevice, st));
+        }
+        return IRMV_OK;
+    }
     HIP_TRY(hipMemcpyAsync(upload_dev(e) + (size_t)first * e->src_bytes, e->src_host + (size_t)first * e->src_bytes,
                            e->src_bytes * count, hipMemcpyHostToDevice, st));
     return IRMV_OK;
@@ -2457,9 +2599,17 @@ static bool upload_as_kernel(const irmv_engine *e, int first, int count)
 // The synchronous upload of slots [first, first + count) on stream st.  (A Bayer engine's single-frame upload stays a kernel
 // of its own in front of the demosaic: the demosaic reading the pinned slot itself was built and measured slower, DESIGN.md
 // section 9.)
-static int upload_sync(irmv_engine *e, int first, int count, hipStream_t st)
+// An HWC window engine's synchronous step of one or two slots uploads nothing: its crop reads the window out of the pinned
+// slots (crop_from_pinned), so only the window crosses PCIe.  `captured`: the copy becomes a graph node (whole frames).
+static bool crop_from_pinned(const irmv_engine *e, int count)
 {
-    if (!upload_as_kernel(e, first, count)) return copy_in(e, first, count, st);
+    return e->window && !e->raw_dev && e->window_upload && count <= 2 && e->upload_kernel_blocks > 0 && e->src_host_dev;
+}
+
+static int upload_sync(irmv_engine *e, int first, int count, hipStream_t st, bool captured)
+{
+    if (crop_from_pinned(e, count)) return IRMV_OK;
+    if (!upload_as_kernel(e, first, count)) return copy_in(e, first, count, st, !captured);
     const size_t off = (size_t)first * e->src_bytes;
     launch_upload_frames(e->src_host_dev + off, upload_dev(e) + off, e->src_bytes * count, e->upload_kernel_blocks, st);
     return IRMV_OK;
@@ -2492,8 +2642,8 @@ static int get_graph(irmv_engine *e, StepKind kind, int first, int count, bool u
     HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     int rc = IRMV_OK;
     if (upload)   // the frames' upload as the graph's first node (synchronous single-stream submits): one or two frames as a kernel
-        rc = upload_sync(e, first, count, e->stream);
-    if (!rc) rc = enqueue_step(e, kind, first, count, e->stream, 1, nullptr);
+        rc = upload_sync(e, first, count, e->stream, true);
+    if (!rc) rc = enqueue_step(e, kind, first, count, e->stream, 1, nullptr, upload && crop_from_pinned(e, count));
     hipError_t ce = hipStreamEndCapture(e->stream, &g);
     if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
     if (ce != hipSuccess) return fail(IRMV_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
@@ -2542,7 +2692,8 @@ static int submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_
     // replay spends ~10 us of host work before its first packet reaches the GPU, a direct launch ~4; with the 70 us upload in
     // front the host stays far ahead of the GPU: 0.339 -> 0.331 ms per 1280 x 1024 frame).  Every other step is a graph replay.
     const bool eager = e->sync_launch == 1 && c == 1 && (flags & IRMV_SUBMIT_H2D) && !async_up;
-    const bool graph_up = (flags & IRMV_SUBMIT_H2D) && !async_up && e->graph_upload && !eager;
+    const bool pinned = (flags & IRMV_SUBMIT_H2D) && !async_up && crop_from_pinned(e, c);   // (no upload at all: nothing to keep out of the graph)
+    const bool graph_up = (flags & IRMV_SUBMIT_H2D) && !async_up && (e->graph_upload || pinned) && !eager;
     const StepKind kind = c == 1 ? STEP_ONE : STEP_BATCH;
     hipGraphExec_t ge = nullptr;
     if (!eager) TRY(get_graph(e, kind, f, c, graph_up, &ge));
@@ -2563,17 +2714,18 @@ static int submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_
     if (flags & IRMV_SUBMIT_H2D) {
         if (async_up) {
             if (g->in_flight) HIP_TRY(hipStreamWaitEvent(up, g->out, 0));   // previous step has consumed the device frames
-            TRY(copy_in(e, f, c, up));
+            TRY(copy_in(e, f, c, up, true));
             HIP_TRY(hipEventRecord(g->h2d, up));
             HIP_TRY(hipStreamWaitEvent(st, g->h2d, 0));
         } else if (!graph_up) {
             // (an eager step, or IRMV_GRAPH_UPLOAD=0)
-            TRY(upload_sync(e, f, c, st));
+            TRY(upload_sync(e, f, c, st, false));
         }
     }
-    if (eager) TRY(enqueue_step(e, kind, f, c, st, 1, nullptr));
+    if (eager) TRY(enqueue_step(e, kind, f, c, st, 1, nullptr, pinned));
     else HIP_TRY(hipGraphLaunch(ge, st));
     if (e->sparse_head) std::fill(e->head_stale.begin() + f, e->head_stale.begin() + f + c, 1);
+    if (e->window) std::copy(e->win_org.begin() + f, e->win_org.begin() + f + c, e->sub_org.begin() + f);   // what these results are shifted by
     TRY(copy_out(e, f, c, st));
     HIP_TRY(hipEventRecord(g->out, st));
     g->in_flight = true;
@@ -2703,6 +2855,8 @@ extern "C" int irmv_engine_results(irmv_engine *e, int slot, irmv_det *out, int 
     const DevFrameOut &fo = e->fout_host[slot];
     const int k = std::min(fo.num_dets, cap);
     const DevDet *d = e->dets_host + (size_t)slot * e->cfg.max_det;
+    // device records are window-local: the corner the slot was submitted with brings them to full-frame coordinates
+    const float ox = e->window ? (float)e->sub_org[slot].x : 0.f, oy = e->window ? (float)e->sub_org[slot].y : 0.f;
     for (int i = 0; i < k; i++) {
         irmv_det &o = out[i];
         memcpy(o.xyxy, d[i].xyxy, 16);
@@ -2719,6 +2873,10 @@ extern "C" int irmv_engine_results(irmv_engine *e, int slot, irmv_det *out, int 
         o.armor_size = d[i].armor_size;
         o.n_lights = d[i].n_lights;
         o.reserved = 0;
+        if (e->window) {
+            for (int j = 0; j < 4; j++) o.xyxy[j] += (j & 1) ? oy : ox;
+            for (int j = 0; j < 8; j++) o.kpts[j] += (j & 1) ? oy : ox;
+        }
     }
     *n = k;
     return IRMV_OK;
@@ -2738,12 +2896,16 @@ extern "C" int irmv_engine_detect(irmv_engine *e, int slot, irmv_det *out, int c
 extern "C" double irmv_engine_last_detect_ms(const irmv_engine *e) { return e ? e->last_detect_ms : 0.0; }
 
 // The slot's pinned frame -> its HWC device frame (src_dev) on stream st, outside a step: an HWC engine copies it there, a
-// Bayer engine copies the raw frame to its device raw slot and demosaics it.
+// Bayer engine copies the raw frame to its device raw slot and demosaics it; a window engine then cuts the slot's window out.
 static int load_frame(irmv_engine *e, int slot, hipStream_t st)
 {
-    TRY(copy_in(e, slot, 1, st));
+    TRY(copy_in(e, slot, 1, st, true));
     if (e->raw_dev) {
         launch_bayer(e, slot, 1, st);
+        HIP_TRY(hipGetLastError());
+    }
+    if (e->window) {
+        launch_crop(e, slot, 1, false, st);
         HIP_TRY(hipGetLastError());
     }
     return IRMV_OK;
@@ -2779,7 +2941,17 @@ static int extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, ir
     if (trace && !e->light_trace_dev) TRY(dev_alloc(e, (void **)&e->light_trace_dev, (size_t)e->cfg.max_det * sizeof(LightTrace)));
     if (trace) HIP_TRY(hipMemsetAsync(e->light_trace_dev, 0, (size_t)n * sizeof(LightTrace), st));
     TRY(load_frame(e, slot, st));
-    HIP_TRY(hipMemcpyAsync(e->light_boxes, xyxy, (size_t)n * 16, hipMemcpyHostToDevice, st));
+    // a window engine takes the boxes in full result coordinates: window-local for the kernel, the corner back onto its points
+    const float ox = e->window ? (float)e->win_org[slot].x : 0.f, oy = e->window ? (float)e->win_org[slot].y : 0.f;
+    std::vector<float> local;
+    if (e->window) {
+        local.assign(xyxy, xyxy + (size_t)n * 4);
+        for (size_t j = 0; j < local.size(); j++) local[j] -= (j & 1) ? oy : ox;
+        HIP_TRY(hipMemcpyAsync(e->light_boxes, local.data(), (size_t)n * 16, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));   // (`local` is pageable memory of this call)
+    } else {
+        HIP_TRY(hipMemcpyAsync(e->light_boxes, xyxy, (size_t)n * 16, hipMemcpyHostToDevice, st));
+    }
     LightArgs a = light_args(e, slot);
     a.dets = e->light_dets_dev;
     a.labels = e->light_labels;
@@ -2802,6 +2974,8 @@ static int extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, ir
         o.class_id = IRMV_NUM_CLASSES;
         o.pnp_ok = d.pnp_ok;
         memcpy(o.kpts, d.kpts, 32);
+        if (e->window)
+            for (int j = 0; j < 8; j++) o.kpts[j] += (j & 1) ? oy : ox;
         memcpy(o.rvec, d.rvec, 24);
         memcpy(o.tvec, d.tvec, 24);
         memcpy(o.quat, d.quat, 32);
@@ -3244,6 +3418,7 @@ static const char *op_kind_name(OpKind k)
     case OP_BNECK: return "bneck";
     case OP_KPT3: return "kpt3";
     case OP_DEMOSAIC: return "demosaic";
+    case OP_CROP: return "crop";
     }
     return "?";
 }
@@ -3357,7 +3532,8 @@ extern "C" int irmv_engine_profile(irmv_engine *e, int first, int count, irmv_ke
     TRY(irmv_engine_wait(e));
     const StepKind kind = count == 1 ? STEP_ONE : STEP_BATCH;
     std::vector<EvRec> ev;   // (one per launch of the plan, in its order)
-    TRY(enqueue_step(e, kind, first, count, e->stream, kProfileRepeat, &ev));
+    TRY(enqueue_step(e, kind, first, count, e->stream, kProfileRepeat, &ev));   // (a window engine crops out of its device frames, as a submit without IRMV_SUBMIT_H2D does)
+    if (e->window) std::copy(e->win_org.begin() + first, e->win_org.begin() + first + count, e->sub_org.begin() + first);
     if (e->sparse_head) std::fill(e->head_stale.begin() + first, e->head_stale.begin() + first + count, 1);
     TRY(copy_out(e, first, count));
     HIP_TRY(hipStreamSynchronize(e->stream));

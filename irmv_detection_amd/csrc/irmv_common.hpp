@@ -146,6 +146,17 @@ struct BayerArgs {
 void launch_demosaic(const BayerArgs &a, int batch, hipStream_t s);
 void launch_demosaic_table(const BayerArgs &a, const uint8_t *table, bool mhc, int batch, hipStream_t s);   // table: [3][256] device bytes, 16-byte aligned; mhc: W, H >= 4
 
+// tracking window (k_window.hip): frame b's win_w x win_h window at win[first + b] of its full HWC frame -> its compact frame
+struct CropArgs {
+    const uint8_t *src;       // [num_slots][full_h][full_w][3]: the device frames, or the pinned slots through their device mapping
+    uint8_t *dst;             // [num_slots][win_h][win_w][3]
+    size_t src_slot_bytes, dst_slot_bytes;
+    const int2 *win;          // [num_slots] top-left corner (x, y) in buffer coordinates; read when the kernel runs
+    int first;
+    int full_w, full_h, win_w, win_h;
+};
+void launch_window_crop(const CropArgs &a, int batch, hipStream_t s);
+
 // model.0.conv: 3x3 s2, 3(+1 pad) -> 16, SiLU
 struct Conv0Args {
     const half_t *x;      // [B][net_h][net_w][4]
@@ -417,6 +428,7 @@ struct PostArgs {
                               // for another step to find non-zero); every reader clamps it to key_cap
     unsigned int *cand_bits;  // [B][cand_words] candidate-anchor bitmap of the sparse head (ConvArgs::cand_bits), or nullptr: nms_pnp_kernel
     int cand_words;           // clears its frame's words where it resets the count
+    int pnp_stride;           // frame b solves with pnp[(first + b) * pnp_stride]: 0 = one record for every slot, 1 = one per slot (window engines)
 };
 void launch_nms_pnp(const PostArgs &a, int batch, hipStream_t s);
 constexpr int kScanBlocks = 16;   // workgroups per frame of scan_decode_kernel (more where a 16th of the keys would not fit kScanLdsMax)
@@ -467,6 +479,7 @@ struct LightArgs {
     const PnpConst *pnp;
     int pnp_armor_size;
     LightTrace *trace;       // [n_boxes] or nullptr (every launch of a step): see LightTrace
+    int first, pnp_stride;   // frame b solves with pnp[(first + b) * pnp_stride] (PostArgs::pnp_stride)
 };
 void launch_light_extract(const LightArgs &a, int n_boxes_max, int batch, hipStream_t s);
 

@@ -504,7 +504,7 @@ __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
         d->quat[0] = d->quat[1] = d->quat[2] = 0.0; d->quat[3] = 1.0;
         d->pnp_ok = 0;
         // the reference always solves with the SMALL model (src/pnp_solver.cpp:47-48)
-        if (valid) d->pnp_ok = solve_pnp_ippe(*a.pnp, d->kpts, a.pnp_armor_size, d->rvec, d->tvec, d->quat) ? 1 : 0;
+        if (valid) d->pnp_ok = solve_pnp_ippe(a.pnp[(size_t)(a.first + b) * a.pnp_stride], d->kpts, a.pnp_armor_size, d->rvec, d->tvec, d->quat) ? 1 : 0;
     }
 }
 

@@ -1293,7 +1293,7 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
             IRMV_STAMP(11);
             double rvec[3] = {0.0, 0.0, 0.0}, tvec[3] = {0.0, 0.0, 0.0}, quat[4] = {0.0, 0.0, 0.0, 1.0};
             int pnp_ok = 0;
-            if (a.nk >= 8) pnp_ok = solve_pnp_ippe_pair(*a.pnp, px0, py0, px1, py1, a.armor_size, rvec, tvec, quat) ? 1 : 0;
+            if (a.nk >= 8) pnp_ok = solve_pnp_ippe_pair(a.pnp[(size_t)(a.first + b) * a.pnp_stride], px0, py0, px1, py1, a.armor_size, rvec, tvec, quat) ? 1 : 0;
             IRMV_STAMP(12);
             if (w) {
 #pragma unroll

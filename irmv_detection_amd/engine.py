@@ -94,6 +94,9 @@ class YoloEngine:
     changes the gains and a per-channel tone LUT on the living engine; `bayer_isp` reads them back.
     `net_size` x `net_height`: the network input's width x height (`net_height=None`: square, net_size x net_size; e.g.
     640 x 512 for a 1280 x 1024 camera); `net_width` / `net_height` hold the engine's dimensions.
+    `window` = (w, h): a tracking window -- every step runs on a w x h crop of the frame at the sensor's resolution;
+    `src_image_size` stays the full frame the producer writes, detections come back in full-frame coordinates, and
+    `set_window` / `set_window_center` move a slot's window between steps (irmv_detection_amd.window is the host reference).
     """
 
     def __init__(self, onnx_file_path: Optional[str], src_image_size: Tuple[int, int] = (1280, 1024),
@@ -108,7 +111,7 @@ class YoloEngine:
                  light_min_ratio: float = 0.1, light_max_ratio: float = 0.4, light_max_angle: float = 40.0,
                  armor_center_distances: Sequence[float] = (0.8, 3.2, 3.2, 5.5), warmup: int = 0,
                  src_format=capi.SRC_HWC8, bayer_gains: Sequence[int] = (256, 256, 256), net_height: Optional[int] = None,
-                 bayer_demosaic="bilinear"):
+                 bayer_demosaic="bilinear", window: Optional[Tuple[int, int]] = None):
         L = capi.load()
         cfg = capi.EngineCfg()
         L.irmv_engine_cfg_default(C.byref(cfg))
@@ -127,6 +130,8 @@ class YoloEngine:
         cfg.src_format = capi.BAYER_FORMATS[src_format.upper()] if isinstance(src_format, str) else int(src_format)
         cfg.bayer_gain_q8 = (C.c_uint16 * 3)(*[int(g) for g in bayer_gains])
         cfg.bayer_demosaic = capi.DEMOSAIC_ALGOS[bayer_demosaic.lower()] if isinstance(bayer_demosaic, str) else int(bayer_demosaic)
+        if window is not None:
+            cfg.win_width, cfg.win_height = int(window[0]), int(window[1])
         cfg.camera_matrix = (C.c_double * 9)(*camera_matrix)
         cfg.dist_coeffs = (C.c_double * 5)(*(list(dist_coeffs) + [0.0] * 5)[:5])
         self._blob_keepalive = None
@@ -147,6 +152,7 @@ class YoloEngine:
             capi.check(rc)
         self.src_image_size = (cfg.src_width, cfg.src_height)
         self.src_format = cfg.src_format
+        self.window_size = (cfg.win_width, cfg.win_height) if cfg.win_width else None
         self.bayer_demosaic = "mhc" if cfg.bayer_demosaic == capi.DEMOSAIC_MHC else "bilinear"
         self.net_size = net_size                 # the width (and, square, the height)
         self.net_width, self.net_height = net_size, net_height or net_size
@@ -214,12 +220,37 @@ class YoloEngine:
         return float(self._L.irmv_engine_last_detect_ms(self._h))
 
     def get_rotated_image(self, slot: Optional[int] = None) -> np.ndarray:
-        """The 180-degree rotated frame (yolo_engine.hpp:34); HWC in every source format (a Bayer engine's demosaiced frame)."""
+        """The 180-degree rotated frame (yolo_engine.hpp:34); HWC in every source format (a Bayer engine's demosaiced frame).
+        A window engine returns the slot's rotated window, [win_h, win_w, 3]."""
         slot = self.slot if slot is None else slot
-        w, h = self.src_image_size
+        w, h = self.window_size or self.src_image_size
         out = np.empty((h, w, 3), np.uint8)
         capi.check(self._L.irmv_engine_rotated_image(self._h, slot, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
+
+    def set_window(self, x0: int, y0: int, slot: Optional[int] = None) -> None:
+        """Move the slot's window: (x0, y0) is its top-left corner in the coordinates detections come back in (the rotated
+        frame under rotate180).  Waits for the slot's last submitted step; takes effect from its next one."""
+        slot = self.slot if slot is None else slot
+        capi.check(self._L.irmv_engine_set_window(self._h, slot, int(x0), int(y0)))
+
+    def set_window_center(self, cx: float, cy: float, slot: Optional[int] = None) -> Tuple[int, int]:
+        """Centre the slot's window on (cx, cy) -- e.g. the last detection's box centre --, clamped into the frame.
+        Returns the corner it set."""
+        if self.window_size is None:
+            raise IrmvError(capi.ERR_ARG, "the engine has no window")
+        (w, h), (fw, fh) = self.window_size, self.src_image_size
+        x0 = min(max(int(np.floor(cx - w / 2.0 + 0.5)), 0), fw - w)
+        y0 = min(max(int(np.floor(cy - h / 2.0 + 0.5)), 0), fh - h)
+        self.set_window(x0, y0, slot)
+        return x0, y0
+
+    def window(self, slot: Optional[int] = None) -> Tuple[int, int, int, int]:
+        """(x0, y0, w, h) of the slot's current window."""
+        slot = self.slot if slot is None else slot
+        v = [C.c_int(0) for _ in range(4)]
+        capi.check(self._L.irmv_engine_get_window(self._h, slot, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def set_bayer_isp(self, gains: Sequence[int], lut=None) -> None:
         """Gains (R, G, B; Q8, 256 = 1.0) and tone LUT (uint8 [3][256], rows R, G, B, or [256] for all three; None = identity)
