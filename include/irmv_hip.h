@@ -335,6 +335,10 @@ int irmv_engine_debug_read_cand_bits(irmv_engine *e, int slot, uint32_t *words, 
    read_tensor first bring a sparse head to the dense state): [num_anchors][96] floats, box 64 | classes at 64 | keypoints at
    80; `bytes` must be num_anchors * 96 * 4.  After a step of a sparse engine only the rows the step stored are the step's. */
 int irmv_engine_debug_read_head_rows(irmv_engine *e, int slot, float *rec, size_t bytes);
+/* Read-only (tests): irmv_engine_read_head without the read-back step: [num_anchors][64 + nc + nk] floats as the last step or
+   write_head left them.  Runs no kernel and does not change what a later read_head does.  The same memory as
+   irmv_engine_debug_read_head_rows shows; the two differ in layout only (read_head's columns here, the 96-float records there). */
+int irmv_engine_debug_read_head_raw(irmv_engine *e, int slot, float *head);
 int irmv_engine_read_tap(irmv_engine *e, int slot, const char *name, float *nhwc, int shape[3]);   /* shape = {H, W, C}: a tensor of
                                                                                  level s is (net_h/s) x (net_w/s) */
 int irmv_engine_read_raw(irmv_engine *e, int slot, irmv_raw_dets *out);

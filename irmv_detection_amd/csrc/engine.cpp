@@ -185,6 +185,7 @@ struct Op {
     int group = -1;            // single-frame steps: index into irmv_engine::head_groups of the one launch this conv rides in
     int bneck = -1;            // single-frame steps: index of the OP_BNECK launch (k_bneck.hip) that computes this conv; OP_BNECK itself: 1 = kept
     int kpt3 = -1;             // a keypoint-branch conv: index of the OP_KPT3 launch (k_kpt.hip) that computes its level's branch in every step; OP_KPT3 itself: 1
+    bool gated_first = false;  // a Detect box branch's first conv that some step runs behind the tile gate (sparse branch): its tensor is lazy, the read-back step runs it densely
     int tune_fuse[2] = {-1, -1};   // OP_CONV: fuse_next as the autotuner's two passes (stream share, one slot) found it (test hooks rebuild their candidate lists)
 };
 
@@ -199,6 +200,7 @@ struct Launch {
     unsigned scan = 0;        // bit k: member k of the group (a lone conv: bit 0) appends scan candidates from its epilogue
     bool keys_only = false;   // OP_NMS: decodes the boxes of its key lists itself
     bool sparse = false;      // a Detect box carrier or OP_KPT3 behind its level's class carrier: stores the candidate anchors' head rows only
+    int gate = 0;             // sparse branch, ConvArgs::tile_gate / Kpt3Args::tile_gate: 0 = off, 1 = halo 0 (writes head rows), 2 = halo 1 (box branch's first conv)
     bool once = false;        // not repeated under irmv_engine_profile (appends to, consumes or rewrites per-frame lists)
     std::string name, layer;  // irmv_engine_profile's row
     double flops = 0, bytes = 0, launch_bytes = 0;   // per frame; launch_bytes (the weights): once per launch
@@ -244,6 +246,11 @@ struct irmv_engine {
     unsigned int *cand_bits = nullptr;   // [S][cand_words], zero between steps
     int cand_words = 0;
     std::vector<char> head_stale;
+    // Sparse branch (IRMV_SPARSE_BRANCH=0: off; only with sparse_head): the launches behind the class carriers also skip the
+    // COMPUTATION of (tile, image) pairs without a candidate anchor (Launch::gate).  The box branch's gated first conv leaves its
+    // tensor stale outside active tiles: branch_stale[slot], until the read-back step has run it densely.
+    bool sparse_branch = false;
+    std::vector<char> branch_stale;
     int lvl_hw[3] = {0, 0, 0}, lvl_base[3] = {0, 0, 0};
     size_t frame_bytes = 0;       // one HWC source frame (src_dev, rot_dev)
     size_t src_bytes = 0;         // one source slot as the producer writes it (src_host, and raw_dev or src_dev): frame_bytes, or W*H for a Bayer engine
@@ -1271,6 +1278,7 @@ static int build_engine(irmv_engine *e)
         HIP_TRY(hipMemset(e->cand_bits, 0, (size_t)S * e->cand_words * sizeof(unsigned int)));
     }
     e->head_stale.assign((size_t)S, 0);
+    e->branch_stale.assign((size_t)S, 0);
     TRY(dev_alloc(e, (void **)&e->dets_dev, (size_t)S * c.max_det * sizeof(DevDet)));
     TRY(dev_alloc(e, (void **)&e->fout_dev, (size_t)S * sizeof(DevFrameOut)));
     HIP_TRY(hipMemset(e->dets_dev, 0, (size_t)S * c.max_det * sizeof(DevDet)));
@@ -2037,6 +2045,8 @@ static void finalize_head_fusion(irmv_engine *e)
     e->emit_scan = e->split_scan && fused == 3 && !(ev && ev[0] == '0');
     const char *sh = getenv("IRMV_SPARSE_HEAD");
     e->sparse_head = e->emit_scan && e->cand_bits && !(sh && sh[0] == '0');
+    const char *sb = getenv("IRMV_SPARSE_BRANCH");
+    e->sparse_branch = e->sparse_head && !(sb && sb[0] == '0');
 }
 
 // ---- grouped Detect-branch launches (single-frame engines) ---------------------------
@@ -2172,29 +2182,64 @@ static bool is_box_final_carrier(const Op &op) { return op.fuse_next >= 0 && op.
 // keep every row: a grouped launch (single-frame engines: box and class finals of all levels in ONE launch, no order to
 // be had) and the keypoint branch as layers.  The head bytes of a marked launch, and of every emitting class carrier, no longer
 // count as written: what is left is 96 floats per candidate anchor.
-static void sparse_head_plan(const irmv_engine *e, std::vector<Launch> &plan)
+//
+// Sparse branch (e->sparse_branch): the marked launches also carry the tile gate -- a (tile, image) pair without a candidate
+// anchor stores nothing, so the resident-weight kernels and the keypoint kernel do not compute it (halo 0).  The box branch's
+// first conv feeds nothing but its carrier's 3x3: where it runs a resident-weight kernel it moves behind the last class carrier
+// too (it reads the level input only) and is gated with a halo of one pixel; its tensor becomes a lazy one (Op::gated_first).
+// flops / bytes stay the dense figures: upper bounds for a gated launch.
+static void sparse_head_plan(irmv_engine *e, std::vector<Launch> &plan)
 {
     int last_cls = -1;
     bool lvl_cls[3] = {false, false, false};
     for (size_t i = 0; i < plan.size(); i++)
         if (plan[i].scan && plan[i].group < 0) { last_cls = (int)i; lvl_cls[e->ops[plan[i].op].level] = true; }
+    auto box_carrier = [&](const Launch &l) {
+        const Op &op = e->ops[l.op];
+        return l.group < 0 && l.fused && op.kind == OP_CONV && is_box_final_carrier(op) && op.level < 3 && lvl_cls[op.level];
+    };
+    std::vector<char> first_conv(plan.size(), 0);   // resident-weight launches whose output tensor is read by a box carrier of this plan and by no other op
+    if (e->sparse_branch)
+        for (size_t i = 0; i < plan.size(); i++) {
+            const Launch &f = plan[i];
+            const Op &fo = e->ops[f.op];
+            if (f.group >= 0 || f.fused || f.scan || fo.kind != OP_CONV || !(f.cfg_one ? fo.cfg_one : fo.cfg).wr || fo.res_t >= 0) continue;
+            int carrier = -1;
+            for (size_t j = i + 1; j < plan.size(); j++) {
+                const Op &co = e->ops[plan[j].op];
+                if (box_carrier(plan[j]) && co.level == fo.level && co.s0.t == fo.out_t && co.s1.C == 0 && co.s0.coff == fo.out_coff && co.Hin == fo.Hout && co.Win == fo.Wout) carrier = plan[j].op;
+            }
+            bool other = false;   // any other reader of the tensor (or a second writer) would see it stale outside active tiles
+            for (int k = 0; k < (int)e->ops.size(); k++) {
+                const Op &o = e->ops[k];
+                if (k == carrier || k == f.op) continue;
+                other = other || o.s0.t == fo.out_t || o.s1.t == fo.out_t || o.res_t == fo.out_t || o.out_t == fo.out_t;
+            }
+            first_conv[i] = carrier >= 0 && !other;
+        }
     std::vector<Launch> out, moved;
     for (size_t i = 0; i < plan.size(); i++) {
         Launch &l = plan[i];
-        const Op &op = e->ops[l.op];
+        Op &op = e->ops[l.op];
         if (l.scan) {   // class carrier(s): the 1x1's output stays on chip
             if (l.group < 0) l.bytes -= e->ops[op.fuse_next].out_bytes;
             else for (size_t m = 0; m < e->head_groups[l.group].members.size(); m++)
                 if (l.scan >> m & 1u) l.bytes -= e->ops[e->ops[e->head_groups[l.group].members[m]].fuse_next].out_bytes;
         }
         const bool cls_first = op.level >= 0 && op.level < 3 && lvl_cls[op.level];
-        const bool box = l.group < 0 && l.fused && op.kind == OP_CONV && is_box_final_carrier(op) && cls_first;
+        const bool box = box_carrier(l);
         const bool kpt = op.kind == OP_KPT3 && cls_first && (int)i > last_cls;
         if (box || kpt) {
             l.sparse = true;
             l.bytes -= box ? e->ops[op.fuse_next].out_bytes : op.out_bytes;
+            if (e->sparse_branch) l.gate = 1;
         }
-        if (box && (int)i < last_cls) moved.push_back(l); else out.push_back(l);
+        if (first_conv[i]) {
+            l.gate = 2;
+            op.gated_first = true;
+            e->lazy_tensors.insert(e->tensors[op.out_t].name);
+        }
+        if ((box || first_conv[i]) && (int)i < last_cls) moved.push_back(l); else out.push_back(l);
         if ((int)i == last_cls) { out.insert(out.end(), moved.begin(), moved.end()); moved.clear(); }
     }
     plan.swap(out);
@@ -2219,7 +2264,8 @@ static void build_step_plans(irmv_engine *e)
             if (op.kind == OP_KPT3 ? !step : (op.kpt3 >= 0 && step)) continue;
             // a step skips the layers a fused kernel covers; a read-back runs only those (and the unfused form of a conv that
             // normally carries a 1x1 in its epilogue)
-            if (mat ? !(op.fused_away || op.fuse_next >= 0 || ((op.bneck >= 0 || op.kpt3 >= 0) && op.kind == OP_CONV)) : op.fused_away) continue;
+            // (... and a box branch's first conv that the steps -- their plans are built first -- run behind the tile gate)
+            if (mat ? !(op.fused_away || op.fuse_next >= 0 || op.gated_first || ((op.bneck >= 0 || op.kpt3 >= 0) && op.kind == OP_CONV)) : op.fused_away) continue;
             Launch l; l.op = i;
             // every kernel is idempotent and can be repeated inside its profile bracket -- except the light extraction and, with
             // the split scan, the scan / NMS pair (the scan appends to the frame's candidate list, the NMS kernel consumes and resets it)
@@ -2535,7 +2581,7 @@ static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hip
             a.w2 = o1.w_packed; a.b2 = o1.bias;
             a.w3 = o2.w_k16; a.b3 = o2.bias;
             a.out = static_cast<float *>(ht.slot(first)) + o2.out_coff; a.out_ld = ht.C;
-            if (l.sparse) { a.cand_bits = pa.cand_bits; a.cand_words = pa.cand_words; a.abase = e->lvl_base[op.level]; }
+            if (l.sparse) { a.cand_bits = pa.cand_bits; a.cand_words = pa.cand_words; a.abase = e->lvl_base[op.level]; a.tile_gate = l.gate; }
             if (!launch_kpt3(a, op.cin, count, s)) return fail(IRMV_ERR_ARG, "no fused keypoint-branch kernel for " + op.layer);
             break;
         }
@@ -2553,7 +2599,7 @@ static int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hip
             ConvArgs a;
             fill_conv_args(e, op, first, count, a, l.fused);
             if (scan) scan_args_for(e, op, pr, a);
-            if (l.sparse) { a.cand_bits = pa.cand_bits; a.cand_words = pa.cand_words; a.scan_abase = e->lvl_base[op.level]; }
+            if (l.sparse || l.gate) { a.cand_bits = pa.cand_bits; a.cand_words = pa.cand_words; a.scan_abase = e->lvl_base[op.level]; a.tile_gate = l.gate; }
             if (!run_conv(op, l.cfg_one ? op.cfg_one : op.cfg, a, count, s)) return fail(IRMV_ERR_ARG, std::string("no conv kernel for ") + op.kname + " (" + op.layer + ")");
             break;
         }
@@ -2725,6 +2771,7 @@ static int submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_
     if (eager) TRY(enqueue_step(e, kind, f, c, st, 1, nullptr, pinned));
     else HIP_TRY(hipGraphLaunch(ge, st));
     if (e->sparse_head) std::fill(e->head_stale.begin() + f, e->head_stale.begin() + f + c, 1);
+    if (e->sparse_branch) std::fill(e->branch_stale.begin() + f, e->branch_stale.begin() + f + c, 1);
     if (e->window) std::copy(e->win_org.begin() + f, e->win_org.begin() + f + c, e->sub_org.begin() + f);   // what these results are shifted by
     TRY(copy_out(e, f, c, st));
     HIP_TRY(hipEventRecord(g->out, st));
@@ -3155,6 +3202,7 @@ static int materialize_fused(irmv_engine *e, int slot)
     TRY(enqueue_step(e, STEP_MATERIALIZE, slot, 1, e->stream, 1, nullptr));
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->head_stale[slot] = 0;   // (the finals and the keypoint layers have written every head row)
+    e->branch_stale[slot] = 0; // (... and the box branches' gated first convs their whole tensors)
     return IRMV_OK;
 }
 
@@ -3180,10 +3228,9 @@ extern "C" int irmv_engine_read_input(irmv_engine *e, int slot, float *chw)
     return IRMV_OK;
 }
 
-extern "C" int irmv_engine_read_head(irmv_engine *e, int slot, float *head)
+// the slot's head records as they lie in memory, in read_head's layout: [num_anchors][64 + nc + nk]
+static int copy_head(irmv_engine *e, int slot, float *head)
 {
-    TRY(check_range(e, slot, 1));
-    TRY(ensure_dense_head(e, slot));
     for (int l = 0; l < 3; l++) {
         std::vector<float> v;
         TRY(read_tensor_f32(e, e->tensors[e->head_t[l]], slot, v));
@@ -3196,6 +3243,24 @@ extern "C" int irmv_engine_read_head(irmv_engine *e, int slot, float *head)
         }
     }
     return IRMV_OK;
+}
+
+extern "C" int irmv_engine_read_head(irmv_engine *e, int slot, float *head)
+{
+    TRY(check_range(e, slot, 1));
+    TRY(ensure_dense_head(e, slot));
+    return copy_head(e, slot, head);
+}
+
+// (tests) read_head without the read-back step in front: the rows as the last step or write_head left them -- after a sparse
+// step only the candidate anchors' box and keypoint channels are that step's.  Runs no kernel and leaves head_stale alone.
+extern "C" int irmv_engine_debug_read_head_raw(irmv_engine *e, int slot, float *head)
+{
+    TRY(check_range(e, slot, 1));
+    if (!head) return fail(IRMV_ERR_ARG, "debug_read_head_raw: head is null");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));
+    return copy_head(e, slot, head);
 }
 
 extern "C" int irmv_engine_write_head(irmv_engine *e, int slot, const float *head)
@@ -3227,7 +3292,11 @@ extern "C" int irmv_engine_read_tap(irmv_engine *e, int slot, const char *name, 
     const Tensor &t = e->tensors[it->second];
     shape[0] = t.H; shape[1] = t.W; shape[2] = t.C;
     if (!nhwc) return IRMV_OK;
-    if (e->lazy_tensors.count(t.name)) TRY(materialize_fused(e, slot));
+    // (a box branch's gated first conv is lazy only while its slot is stale: a read of it after the read-back step, or before any
+    //  step, runs nothing and so leaves a head written through write_head alone)
+    bool gated_out = false;
+    for (const Op &op : e->ops) gated_out = gated_out || (op.gated_first && op.out_t == it->second);
+    if (e->lazy_tensors.count(t.name) && (!gated_out || e->branch_stale[slot])) TRY(materialize_fused(e, slot));
     for (int l = 0; l < 3; l++) if (it->second == e->head_t[l]) TRY(ensure_dense_head(e, slot));
     std::vector<float> v;
     TRY(read_tensor_f32(e, t, slot, v));
@@ -3248,6 +3317,9 @@ extern "C" int irmv_engine_read_tensor(irmv_engine *e, const char *name, int fir
     TRY(irmv_engine_wait(e));
     for (int l = 0; l < 3; l++)
         if (it->second == e->head_t[l]) for (int s = first; s < first + count; s++) TRY(ensure_dense_head(e, s));
+    for (const Op &op : e->ops)   // a box branch's first conv behind the tile gate: stale outside the last step's active tiles
+        if (op.gated_first && op.out_t == it->second)
+            for (int s = first; s < first + count; s++) if (e->branch_stale[s]) TRY(materialize_fused(e, s));
     HIP_TRY(hipMemcpy(dst, t.slot(first), need, hipMemcpyDeviceToHost));
     return IRMV_OK;
 }
@@ -3535,6 +3607,7 @@ extern "C" int irmv_engine_profile(irmv_engine *e, int first, int count, irmv_ke
     TRY(enqueue_step(e, kind, first, count, e->stream, kProfileRepeat, &ev));   // (a window engine crops out of its device frames, as a submit without IRMV_SUBMIT_H2D does)
     if (e->window) std::copy(e->win_org.begin() + first, e->win_org.begin() + first + count, e->sub_org.begin() + first);
     if (e->sparse_head) std::fill(e->head_stale.begin() + first, e->head_stale.begin() + first + count, 1);
+    if (e->sparse_branch) std::fill(e->branch_stale.begin() + first, e->branch_stale.begin() + first + count, 1);
     TRY(copy_out(e, first, count));
     HIP_TRY(hipStreamSynchronize(e->stream));
     for (size_t i = 0; i < ev.size(); i++) {

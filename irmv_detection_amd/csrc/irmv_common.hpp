@@ -286,6 +286,7 @@ struct Kpt3Args {
     int out_ld;
     const unsigned int *cand_bits;   // sparse head: [B][cand_words] candidate-anchor bitmap, rows of other anchors are not stored; nullptr = all rows
     int cand_words, abase;           // abase: first anchor index of this level
+    int tile_gate;                   // sparse branch (with cand_bits): != 0 = a (tile, image) pair without a candidate anchor in the tile is not computed
 };
 bool kpt3_eligible(int cin);
 bool launch_kpt3(const Kpt3Args &a, int cin, int batch, hipStream_t s);
@@ -324,6 +325,13 @@ struct ConvArgs {
     // a row is stored only where the anchor's bit is set; scan_abase is then the level's anchor base here too.
     unsigned int *cand_bits;         // [B][cand_words]
     int cand_words;
+    // Sparse branch (tile gate; the resident-weight 3x3 kernels, every other family ignores it and computes everything): a
+    // (tile, image) pair is computed only if some anchor of the level has its bit set inside the tile's output pixels grown by
+    // `halo` pixels on every side.  0 = off, 1 = halo 0 (box carriers: their output is head rows), 2 = halo 1 (the box branch's
+    // first conv: the carrier's 3x3 at a candidate pixel reads its 3x3 neighbourhood).  Needs cand_bits, cand_words and
+    // scan_abase (the level's anchor base), also on a conv without a fused 1x1; the launch must stand behind the level's class
+    // carrier.  What is stored never depends on it: rows are gated per anchor as above, a skipped tile only leaves memory as it was.
+    int tile_gate;
 };
 
 // several independent layers in one launch (k_conv.hip conv3x3_lds_multi / conv_mfma_multi)

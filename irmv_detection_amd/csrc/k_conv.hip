@@ -841,6 +841,63 @@ __device__ __forceinline__ void conv3x3_lds_body(const ConvArgs &a, const half_t
     const int img = grp * ipw, nimg = min(ipw, batch - img);
     const int nblk = by;
     const int HWo = a.Hout * a.Wout;
+    bool gated = false;
+    unsigned int l_mask = 0u;      // gated: the listed images the loader has not fetched yet
+    int l_pos = 0;                 // dense: the loader's next image
+    int n_mine = nimg, n_max = nimg;
+    if constexpr (WR > 0) {
+        // ---- tile gate (ConvArgs::tile_gate, sparse branch): the images of this group's tile position that are worth a step ----
+        // An image is listed if some anchor of the level has its bit set in the tile's output pixels grown by the halo: a 2-D block
+        // is one anchor segment per row, a row run ONE segment (the run, grown by a row and a pixel each way).  Every wave scans
+        // for itself -- lane = (segment, bitmap word the segment can touch), one load per image, sixteen images in flight -- and
+        // the ballots leave a wave-uniform mask: no LDS, no barrier, nothing to be read before it is written.  The ping-pong
+        // form scans the other group's tile too: both groups must agree on the number of barriers.  More than 32 images per
+        // workgroup: no gate, everything is computed.
+        auto gate_images = [&](int t) -> unsigned int {
+            const int h = a.tile_gate - 1;
+            int nseg, lo0, len, pitch;   // segment k: anchors [lo0 + k pitch, + len) of the level
+            if constexpr (TILE2D) {
+                const int TWc = 1 << twc_log2, RH = NWP * MT * (16 >> twc_log2);
+                const int tyi = t / tiles_x, txi = t - tyi * tiles_x;
+                const int ya = max(tyi * RH - h, 0), yb = min(tyi * RH + RH + h, a.Hout);
+                const int xa = max(txi * TWc - h, 0), xb = min(txi * TWc + TWc + h, a.Wout);
+                nseg = yb - ya; lo0 = ya * a.Wout + xa; len = xb - xa; pitch = a.Wout;
+            } else {
+                constexpr int TPX = 16 * NWP * MT;
+                const int lo = max(t * TPX - h * (a.Wout + 1), 0), hi = min(min(t * TPX + TPX, HWo) + h * (a.Wout + 1), HWo);
+                nseg = 1; lo0 = lo; len = hi - lo; pitch = 0;
+            }
+            const int wps = (len + 62) >> 5, items = nseg * wps;   // wps: the most words a segment of len bits touches
+            unsigned int m = 0u;
+            for (int j0 = 0; j0 < items; j0 += 64) {
+                const int it = j0 + lane, sg = it / wps, bl = a.scan_abase + lo0 + sg * pitch, wd = (bl >> 5) + (it - sg * wps);
+                const int s0 = max(bl - wd * 32, 0), s1 = min(bl + len - wd * 32, 32);
+                const bool item = it < items && s1 > s0;
+                const unsigned int bm = item ? (0xffffffffu >> (32 - (s1 - s0))) << s0 : 0u;
+                for (int i0 = 0; i0 < nimg; i0 += 16) {
+                    unsigned int cw[16];
+#pragma unroll
+                    for (int i = 0; i < 16; i++) cw[i] = i0 + i < nimg ? a.cand_bits[(unsigned int)((img + i0 + i) * a.cand_words + (item ? wd : 0))] : 0u;
+#pragma unroll
+                    for (int i = 0; i < 16; i++) m |= __ballot((cw[i] & bm) != 0u) != 0ull ? 1u << ((i0 + i) & 31) : 0u;
+                }
+            }
+            return (unsigned int)__builtin_amdgcn_readfirstlane((int)m);
+        };
+        gated = a.tile_gate != 0 && a.cand_bits != nullptr && nimg <= 32;
+        if (gated) {
+            // (readfirstlane: the group index comes from the thread index, so nothing selected by it is provably wave-uniform --
+            // the image loops below must run on scalars)
+            l_mask = (unsigned int)__builtin_amdgcn_readfirstlane((int)(active ? gate_images(tile) : 0u));
+            n_mine = n_max = __builtin_popcount(l_mask);
+            if constexpr (PP) {
+                const int other = 2 * (bx - grp * wg_tiles) + 1 - sub;
+                const unsigned int o_mask = gate_images(other < tiles_x * tiles_y ? other : 0);
+                n_max = __builtin_amdgcn_readfirstlane(other < tiles_x * tiles_y ? max(n_mine, __builtin_popcount(o_mask)) : n_mine);
+            }
+            if (n_max == 0) return;    // (the whole workgroup, before its first barrier)
+        }
+    }
     int PW, PR, iy_base, ix_base;
     int poff[MT], mloc[MT];
     bool mv[MT];
@@ -1226,6 +1283,12 @@ __device__ __forceinline__ void conv3x3_lds_body(const ConvArgs &a, const half_t
         }
     };
     if constexpr (WR > 0) {
+        auto next_image = [&]() {
+            if (!gated) return l_pos++;
+            const int i = __builtin_ctz(l_mask);
+            l_mask &= l_mask - 1u;
+            return i;
+        };
         // ---- weights resident: stage all WR chunk slabs once, then one step per image ----
         {
             constexpr int WALL = WR * 9 * NT * 64, WPA = (WALL + NTH - 1) / NTH;   // half8 pieces, per thread
@@ -1260,8 +1323,10 @@ __device__ __forceinline__ void conv3x3_lds_body(const ConvArgs &a, const half_t
                     if (use_p[i]) *reinterpret_cast<half8 *>(s_patch + (size_t)c * a_patch_bytes + dst_p[i]) = rq[c][i];
         };
         if constexpr (PP) {
-            // group 1 runs one barrier (= half a step) behind group 0; both execute 2 nimg + 2 barriers
-            issue_wr(0);
+            // group 1 runs one barrier (= half a step) behind group 0; both execute 2 n_max + 2 barriers.  A group whose list is
+            // the shorter one (tile gate), like the second group of an odd tile count, keeps only the barriers' count behind it.
+            int cur = 0, pend = 0;     // the image in the patch, the image in the staging registers
+            if (n_mine > 0) { cur = next_image(); issue_wr(cur); }
             if (sub == 1) {
                 // group 0 passes this barrier through its __syncthreads below and then reads weight / bias / fused-1x1
                 // pieces that THIS group's threads wrote to LDS above: their ds_writes must have landed before the
@@ -1269,16 +1334,19 @@ __device__ __forceinline__ void conv3x3_lds_body(const ConvArgs &a, const half_t
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_s_barrier();
             }
-            write_wr();
-            if (nimg > 1) issue_wr(1);
+            if (n_mine > 0) write_wr();
+            if (n_mine > 1) { pend = next_image(); issue_wr(pend); }
             __syncthreads();
-            for (int s = 0; s < nimg; s++) {
-                ksteps_wr();                                                          // MFMA phase (the other group: load phase)
+            for (int s = 0; s < n_max; s++) {
+                if (s < n_mine) ksteps_wr();                                          // MFMA phase (the other group: load phase)
                 __syncthreads();
-                store_tile(img + s, I0{});                                            // load phase (the other group: MFMA phase)
-                if (s + 1 < nimg) {
-                    write_wr();
-                    if (s + 2 < nimg) issue_wr(s + 2);
+                if (s < n_mine) {
+                    store_tile(img + cur, I0{});                                      // load phase (the other group: MFMA phase)
+                    if (s + 1 < n_mine) {
+                        write_wr();
+                        cur = pend;
+                        if (s + 2 < n_mine) { pend = next_image(); issue_wr(pend); }
+                    }
                 }
                 __syncthreads();
             }
@@ -1288,22 +1356,25 @@ __device__ __forceinline__ void conv3x3_lds_body(const ConvArgs &a, const half_t
         // Lockstep form (maps that do not tile into the ping-pong blocks).  Left alone, the two waves of a SIMD reach their
         // MFMA phase, their fragment reads and their SiLU epilogue together: the matrix pipe idles through both epilogues.
         // STAGGER (round 5; MI355X_MICROARCH.md "Two waves per SIMD", item 9): the second-dispatched half of the workgroup
-        // (waves NWV / 2 ..) defers the epilogue of image s to the start of step s + 1, behind the barrier that releases
+        // (waves NWV / 2 ..) defers the epilogue of list entry s to the start of step s + 1, behind the barrier that releases
         // patch s + 1 -- its vector work then runs beside the first half's MFMAs, and the first half's epilogue beside the
         // tail of its MFMAs.  The sums stay in their accumulator registers across the barriers; same operations on the
-        // same operands, only later: bit-identical.  Barriers per image unchanged (two).
+        // same operands, only later: bit-identical.  Barriers per listed image unchanged (two).
         const bool late = stagger && wave >= NWV / 2;
-        issue_wr(0);
-        for (int s = 0; s < nimg; s++) {
+        int cur = next_image(), prev = cur;   // (n_mine >= 1: a gated workgroup with an empty list has returned)
+        issue_wr(cur);
+        for (int s = 0; s < n_mine; s++) {
             write_wr();
             __syncthreads();
-            if (late && s > 0) store_tile(img + s - 1, I0{});
-            if (s + 1 < nimg) issue_wr(s + 1);
+            if (late && s > 0) store_tile(img + prev, I0{});
+            int nxt = cur;
+            if (s + 1 < n_mine) { nxt = next_image(); issue_wr(nxt); }
             ksteps_wr();
             __syncthreads();
-            if (!late) store_tile(img + s, I0{});
+            if (!late) store_tile(img + cur, I0{});
+            prev = cur; cur = nxt;
         }
-        if (late) store_tile(img + nimg - 1, I0{});
+        if (late) store_tile(img + prev, I0{});
     } else if constexpr (CM > 0) {
         static_assert(!PF2 && CM <= 4, "chunk-major order: one step of staging lead, at most four images");
         auto each_image = [&](auto f) {

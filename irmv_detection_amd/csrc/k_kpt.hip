@@ -91,12 +91,33 @@ __global__ __launch_bounds__(KNT) __attribute__((amdgpu_waves_per_eu(3))) void k
     const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t *>(a.w1), 0, KSTEPS * 1024, 0x00020000);
     auto load_w = [&](int k) { return __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rs_w, lane * 16, k * 1024, 0)); };   // nt = 1 packing: [chunk][tap][lane]
     u32x4 v[KNP];
-    int l_im = 0, l_s = 0;   // loader position: the (image, slab) step the next issue_slab fetches
+    // Tile gate (Kpt3Args::tile_gate, sparse branch): the workgroup's images that have a candidate anchor inside this 10 x 10
+    // tile -- every other (tile, image) pair would store no row, so it is not computed either.  Every wave scans for itself
+    // (no LDS, no barrier): lane = (tile row, one of the two bitmap words the row's ten bits can touch), one load per image,
+    // all of them in flight at once.  A dense launch walks every image.
+    unsigned int amask = nimg >= 32 ? 0xffffffffu : (1u << nimg) - 1u;
+    if (a.tile_gate && a.cand_bits) {
+        const int rows = min(KT, H - oy0), cols = min(KT, W - ox0);
+        const int row = lane >> 1, bl = a.abase + (oy0 + row) * W + ox0, wd = (bl >> 5) + (lane & 1);
+        const int s0 = max(bl - wd * 32, 0), s1 = min(bl + cols - wd * 32, 32);
+        const bool item = row < rows && s1 > s0;
+        const unsigned int bm = item ? (0xffffffffu >> (32 - (s1 - s0))) << s0 : 0u;
+        unsigned int cwd[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) cwd[i] = i < nimg ? a.cand_bits[(unsigned int)((img0 + i) * a.cand_words + (item ? wd : 0))] : 0u;
+        amask = 0u;
+#pragma unroll
+        for (int i = 0; i < 8; i++) amask |= __ballot((cwd[i] & bm) != 0u) != 0ull ? 1u << i : 0u;
+        amask = __builtin_amdgcn_readfirstlane(amask);
+        if (amask == 0u) return;   // (before the first barrier, and wave-uniform over the workgroup: every wave read the same words)
+    }
+    int l_im = __builtin_ctz(amask), l_s = 0;   // loader position: the (image, slab) step the next issue_slab fetches
+    unsigned int l_rest = amask & (amask - 1u); // ... and the active images behind it
     auto issue_slab = [&]() {   // unconditional (a branch around loads makes every later wait a full drain): past the end the last slab again
         const int off = __builtin_amdgcn_readfirstlane(l_im * img_stride + l_s * 128);   // (wave-uniform, but not provably so: left alone every load sits in a waterfall loop)
 #pragma unroll
         for (int i = 0; i < KNP; i++) v[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, src[i], off, 0));
-        if (!(l_im == nimg - 1 && l_s == STEPS - 1)) { if (++l_s == STEPS) { l_s = 0; l_im++; } }
+        if (!(l_rest == 0u && l_s == STEPS - 1)) { if (++l_s == STEPS) { l_s = 0; l_im = __builtin_ctz(l_rest); l_rest &= l_rest - 1u; } }
     };
     auto write_slab = [&]() {
 #pragma unroll
@@ -143,7 +164,8 @@ __global__ __launch_bounds__(KNT) __attribute__((amdgpu_waves_per_eu(3))) void k
         for (int i = 0; i < 3; i++) B[i] = *reinterpret_cast<const half8 *>(s_in + (kh == 1 ? baseO : baseE) + off + i * 256);
     };
 
-    for (int im = 0; im < nimg; im++) {
+    for (unsigned int c_rest = amask; c_rest; c_rest &= c_rest - 1u) {
+        const int im = __builtin_ctz(c_rest);
         // sparse head (Kpt3Args::cand_bits): the bitmap words of this lane's three pixels, requested in front of everything this
         // image still loads (the memory counter is in order) and by every lane (a dense launch reads a bias word and ignores it)
         unsigned int cw[3];

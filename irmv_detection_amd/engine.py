@@ -446,6 +446,13 @@ class YoloEngine:
         capi.check(self._L.irmv_engine_debug_read_head_rows(self._h, slot, out.ctypes.data_as(C.POINTER(C.c_float)), out.nbytes))
         return out
 
+    def debug_read_head_raw(self, slot: int = 0) -> np.ndarray:
+        """read_head's array without the read-back step in front: the rows as the last step or write_head left them (after a
+        sparse step only the candidate anchors' box and keypoint channels are that step's)."""
+        out = np.empty((self.num_anchors, self.head_channels), np.float32)
+        capi.check(self._L.irmv_engine_debug_read_head_raw(self._h, slot, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
     def profile(self, first_slot: int = 0, count: Optional[int] = None) -> List[dict]:
         count = self.num_slots - first_slot if count is None else count
         stats = (capi.KernelStat * 256)()
