@@ -30,6 +30,11 @@ SOURCES = [
     ("k_shuffle.hip", []),
     ("k_debug.hip", []),
     ("engine.cpp", ["-x", "hip"]),
+    ("engine_graph.cpp", ["-x", "hip"]),
+    ("engine_tune.cpp", ["-x", "hip"]),
+    ("engine_plan.cpp", ["-x", "hip"]),
+    ("engine_step.cpp", ["-x", "hip"]),
+    ("engine_hooks.cpp", ["-x", "hip"]),
 ]
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs.  Left to itself the compiler gives kernels without a waves_per_eu
 # bound (fused C2f blocks, direct convs) AGPR accumulators and copies every one of them out with a v_accvgpr_read before the
@@ -44,7 +49,7 @@ def source_hash() -> str:
     their numbers when it differs from the tree it runs in -- a hash of the BINARY would not survive a rebuild elsewhere."""
     import hashlib
     h = hashlib.sha256()
-    names = sorted(set([s for s, _ in SOURCES] + ["irmv_common.hpp", "pnp_device.hpp", "numa.hpp"]))
+    names = sorted(set([s for s, _ in SOURCES] + ["irmv_common.hpp", "pnp_device.hpp", "numa.hpp", "engine_internal.hpp"]))
     for n in names:
         pth = os.path.join(CSRC, n)
         if os.path.exists(pth):
@@ -91,7 +96,7 @@ def build_comm(force: bool = False, verbose: bool = False) -> str:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(LIB_DIR, exist_ok=True)
-    headers = [os.path.join(CSRC, "irmv_common.hpp"), os.path.join(CSRC, "pnp_device.hpp"), os.path.join(CSRC, "numa.hpp"), os.path.join(INCLUDE, "irmv_hip.h"), __file__]
+    headers = [os.path.join(CSRC, "irmv_common.hpp"), os.path.join(CSRC, "pnp_device.hpp"), os.path.join(CSRC, "numa.hpp"), os.path.join(CSRC, "engine_internal.hpp"), os.path.join(INCLUDE, "irmv_hip.h"), __file__]
     objs = []
     cc = hipcc()
     for src, extra in SOURCES:

@@ -15,7 +15,7 @@ strides 8 / 16 / 32), so P3 / P4 / P5 keep their shapes.  Architecture [external
 
 This module is only a *table of conv layers* in canonical order.  It is the
 contract between the weight-blob writer (weights.py), the HIP engine
-(csrc/engine.cpp, which re-derives the same table and refuses a blob that does
+(csrc/engine_graph.cpp, which re-derives the same table and refuses a blob that does
 not match it) and the test-side restatements.
 """
 from __future__ import annotations

@@ -1,0 +1,619 @@
+// Everything that looks into an engine from outside a step: read-backs, the debug_* calls, the LDS fill / probe, the conv and
+// op test hooks, the light trace and the profiler.
+#include "engine_internal.hpp"
+
+static float half_bits_to_float(uint16_t h)
+{
+    const uint32_t sign = ((uint32_t)h & 0x8000u) << 16;
+    uint32_t exp = (h >> 10) & 0x1fu, man = h & 0x3ffu, x;
+    if (exp == 0) {
+        if (man == 0) x = sign;
+        else {
+            int e = -1;
+            do { e++; man <<= 1; } while (!(man & 0x400u));
+            x = sign | ((uint32_t)(112 - e) << 23) | ((man & 0x3ffu) << 13);
+        }
+    } else if (exp == 31) x = sign | 0x7f800000u | (man << 13);
+    else x = sign | ((exp + 112u) << 23) | (man << 13);
+    float f;
+    memcpy(&f, &x, 4);
+    return f;
+}
+
+extern "C" int irmv_engine_debug_poke_candidate_counts(irmv_engine *e, int value)
+{
+    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
+    if (!e->cand_counts) return fail(IRMV_ERR_ARG, "this engine keeps no candidate counters");
+    TRY(irmv_engine_wait(e));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    std::vector<int> v((size_t)e->cfg.num_slots, value);
+    HIP_TRY(hipMemcpy(e->cand_counts, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_debug_read_cand_bits(irmv_engine *e, int slot, uint32_t *words, int cap, int *n, int *sparse)
+{
+    TRY(check_range(e, slot, 1));
+    if (!n || !sparse) return fail(IRMV_ERR_ARG, "n / sparse is null");
+    *sparse = e->sparse_head ? 1 : 0;
+    *n = e->sparse_head ? e->cand_words : 0;
+    if (!words || *n == 0) return IRMV_OK;
+    if (cap < *n) return fail(IRMV_ERR_ARG, "read_cand_bits: buffer too small");
+    TRY(irmv_engine_wait(e));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(hipMemcpy(words, e->cand_bits + (size_t)slot * e->cand_words, (size_t)e->cand_words * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_rotated_image(irmv_engine *e, int slot, uint8_t *dst)
+{
+    TRY(check_range(e, slot, 1));
+    if (!dst) return fail(IRMV_ERR_ARG, "dst is null");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(load_frame(e, slot, e->stream));
+    launch_rotate180(e->src_dev + (size_t)slot * e->frame_bytes, e->rot_dev, e->cfg.src_width, e->cfg.src_height, e->stream);
+    HIP_TRY(hipMemcpyAsync(dst, e->rot_dev, e->frame_bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return IRMV_OK;
+}
+
+static_assert(sizeof(irmv_light_rec) == sizeof(LightTraceRec) && sizeof(irmv_light_trace) == sizeof(LightTrace) &&
+                  offsetof(irmv_light_trace, starts) == offsetof(LightTrace, starts) && offsetof(irmv_light_trace, points) == offsetof(LightTrace, points) &&
+                  offsetof(irmv_light_trace, recs) == offsetof(LightTrace, recs) && offsetof(irmv_light_rec, length) == offsetof(LightTraceRec, length) &&
+                  IRMV_LIGHT_MAX_CONTOURS == kLightMaxContours && IRMV_LIGHT_POINTS_CAP == kLightPointsCap,
+              "irmv_light_trace is LightTrace");
+
+// irmv_engine_extract_armors; trace != nullptr: irmv_engine_light_trace (the kernel also records its stages)
+static int extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, irmv_light_trace *trace, irmv_det *out)
+{
+    TRY(check_range(e, slot, 1));
+    if (n < 0 || n > e->cfg.max_det || (n > 0 && (!xyxy || !out))) return fail(IRMV_ERR_ARG, "n must be 0..max_det with xyxy/out set");
+    if (n == 0) return IRMV_OK;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));
+    hipStream_t st = e->stream;
+    if (trace && !e->light_trace_dev) TRY(dev_alloc(e, (void **)&e->light_trace_dev, (size_t)e->cfg.max_det * sizeof(LightTrace)));
+    if (trace) HIP_TRY(hipMemsetAsync(e->light_trace_dev, 0, (size_t)n * sizeof(LightTrace), st));
+    TRY(load_frame(e, slot, st));
+    // a window engine takes the boxes in full result coordinates: window-local for the kernel, the corner back onto its points
+    const float ox = e->window ? (float)e->win_org[slot].x : 0.f, oy = e->window ? (float)e->win_org[slot].y : 0.f;
+    std::vector<float> local;
+    if (e->window) {
+        local.assign(xyxy, xyxy + (size_t)n * 4);
+        for (size_t j = 0; j < local.size(); j++) local[j] -= (j & 1) ? oy : ox;
+        HIP_TRY(hipMemcpyAsync(e->light_boxes, local.data(), (size_t)n * 16, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));   // (`local` is pageable memory of this call)
+    } else {
+        HIP_TRY(hipMemcpyAsync(e->light_boxes, xyxy, (size_t)n * 16, hipMemcpyHostToDevice, st));
+    }
+    LightArgs a = light_args(e, slot);
+    a.dets = e->light_dets_dev;
+    a.labels = e->light_labels;
+    a.points = e->light_points;
+    a.hulls = e->light_hulls;
+    a.num_dets = nullptr;
+    a.n_boxes = n;
+    a.boxes = e->light_boxes;
+    a.trace = trace ? e->light_trace_dev : nullptr;
+    launch_light_extract(a, n, 1, st);
+    HIP_TRY(hipGetLastError());
+    if (trace) HIP_TRY(hipMemcpyAsync(trace, e->light_trace_dev, (size_t)n * sizeof(LightTrace), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(e->light_dets_host, e->light_dets_dev, (size_t)n * sizeof(DevDet), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i = 0; i < n; i++) {
+        const DevDet &d = e->light_dets_host[i];
+        irmv_det &o = out[i];
+        memset(&o, 0, sizeof o);
+        memcpy(o.xyxy, xyxy + 4 * i, 16);
+        o.class_id = IRMV_NUM_CLASSES;
+        det_pose(e, d, ox, oy, o);
+    }
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, irmv_det *out)
+{
+    return extract_armors(e, slot, xyxy, n, nullptr, out);
+}
+
+extern "C" int irmv_engine_light_trace(irmv_engine *e, int slot, const float *xyxy, int n, irmv_light_trace *trace, irmv_det *out)
+{
+    if (n > 0 && !trace) return fail(IRMV_ERR_ARG, "trace is null");
+    return extract_armors(e, slot, xyxy, n, trace, out);
+}
+
+extern "C" int irmv_light_limits(int32_t out[4])
+{
+    if (!out) return fail(IRMV_ERR_ARG, "out is null");
+    out[0] = kLightMaxContours; out[1] = kLightPointsCap; out[2] = kLightLdsImage; out[3] = kLightLdsPoints;
+    return IRMV_OK;
+}
+
+static int debug_lds_geometry(int *workgroups)
+{
+    int dev = 0, cus = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    *workgroups = debug_lds_workgroups(cus);
+    return IRMV_OK;
+}
+
+// Run one of the two LDS kernels over `wgs` workgroups on a quiet device: a zeroed device buffer of `bytes` for it to write, copied to `out`.
+template <class F> static int debug_lds_run(size_t bytes, void *out, F &&launch)
+{
+    void *d = nullptr;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMalloc(&d, bytes));
+    hipError_t e = hipMemset(d, 0, bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = launch(static_cast<uint32_t *>(d));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIP_TRY(e);
+    return IRMV_OK;
+}
+
+extern "C" int irmv_debug_lds_fill(uint32_t pattern32)
+{
+    int wgs = 0;
+    if (int rc = debug_lds_geometry(&wgs)) return rc;
+    uint32_t bad = 0;
+    TRY(debug_lds_run(sizeof bad, &bad, [&](uint32_t *d) { return launch_lds_fill(pattern32, d, wgs, nullptr); }));
+    if (bad) return fail(IRMV_ERR_HIP, "irmv_debug_lds_fill: a workgroup read back something else than it wrote");
+    return IRMV_OK;
+}
+
+extern "C" int irmv_debug_lds_probe(uint32_t pattern32, uint32_t word, uint32_t *out, int cap, int *n)
+{
+    static_assert(IRMV_DEBUG_LDS_WORDS == kDebugLdsWords, "header and kernel disagree");
+    if (!n) return fail(IRMV_ERR_ARG, "n is null");
+    int wgs = 0;
+    if (int rc = debug_lds_geometry(&wgs)) return rc;
+    *n = wgs;
+    if (!out) return IRMV_OK;
+    if (cap < wgs) return fail(IRMV_ERR_ARG, "cap is smaller than the number of workgroups");
+    if (word >= (uint32_t)kDebugLdsWords) return fail(IRMV_ERR_ARG, "word is outside the workgroup's allocation");
+    return debug_lds_run((size_t)wgs * 4 * sizeof(uint32_t), out, [&](uint32_t *d) { return launch_lds_probe(pattern32, word, d, wgs, nullptr); });
+}
+
+// ---- read-backs --------------------------------------------------------------------
+static int read_tensor_f32(irmv_engine *e, const Tensor &t, int slot, std::vector<float> &out)
+{
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));
+    out.resize(t.slot_elems);
+    if (t.f32) {
+        HIP_TRY(hipMemcpy(out.data(), t.slot(slot), t.slot_elems * 4, hipMemcpyDeviceToHost));
+    } else {
+        std::vector<uint16_t> h(t.slot_elems);
+        HIP_TRY(hipMemcpy(h.data(), t.slot(slot), t.slot_elems * 2, hipMemcpyDeviceToHost));
+        // activation tensors hold log2 e * a (irmv_common.hpp, "activation scale"); the network input does not
+        const float unscale = t.name == "input" ? 1.0f : kActUnscale;
+        for (size_t i = 0; i < t.slot_elems; i++) out[i] = half_bits_to_float(h[i]) * unscale;
+    }
+    return IRMV_OK;
+}
+
+// A step never writes the tensors inside a fused kernel ("input", "0", "model.2.cat", "model.2.tmp"): a read-back of one of
+// them first runs the stand-alone layers the fused kernels cover, on the slot's current device frame.
+static int materialize_fused(irmv_engine *e, int slot)
+{
+    if (e->lazy_tensors.empty()) return IRMV_OK;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));
+    TRY(enqueue_step(e, STEP_MATERIALIZE, slot, 1, e->stream, 1, nullptr));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->head_stale[slot] = 0;   // (the finals and the keypoint layers have written every head row)
+    e->branch_stale[slot] = 0; // (... and the box branches' gated first convs their whole tensors)
+    return IRMV_OK;
+}
+
+// The head of a slot whose last step stored candidate rows only (sparse_head): the read-back step runs the branches' finals
+// and the keypoint layers as layers, which write every row -- the same bits the carriers compute.  A head written through
+// irmv_engine_write_head since that step is not stale and stays as written.
+int irmv::ensure_dense_head(irmv_engine *e, int slot)
+{
+    return e->head_stale[slot] ? materialize_fused(e, slot) : IRMV_OK;
+}
+
+extern "C" int irmv_engine_read_input(irmv_engine *e, int slot, float *chw)
+{
+    TRY(check_range(e, slot, 1));
+    TRY(materialize_fused(e, slot));
+    std::vector<float> v;
+    TRY(read_tensor_f32(e, e->tensors[e->tensor_idx.at("input")], slot, v));
+    const size_t n = (size_t)e->cfg.net_size * e->cfg.net_height;
+    for (size_t p = 0; p < n; p++)
+        for (int c = 0; c < 3; c++) chw[c * n + p] = v[p * 4 + c];
+    return IRMV_OK;
+}
+
+// the slot's head records as they lie in memory, in read_head's layout: [num_anchors][64 + nc + nk]
+static int copy_head(irmv_engine *e, int slot, float *head)
+{
+    for (int l = 0; l < 3; l++) {
+        std::vector<float> v;
+        TRY(read_tensor_f32(e, e->tensors[e->head_t[l]], slot, v));
+        for (int p = 0; p < e->lvl_hw[l]; p++) {
+            float *o = head + (size_t)(e->lvl_base[l] + p) * e->no;
+            const float *r = v.data() + (size_t)p * kHeadRec;
+            memcpy(o, r, 64 * 4);
+            memcpy(o + 64, r + kClsOff, (size_t)e->nc * 4);
+            if (e->nk) memcpy(o + 64 + e->nc, r + kKptOff, (size_t)e->nk * 4);
+        }
+    }
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_read_head(irmv_engine *e, int slot, float *head)
+{
+    TRY(check_range(e, slot, 1));
+    TRY(ensure_dense_head(e, slot));
+    return copy_head(e, slot, head);
+}
+
+// (tests) read_head without the read-back step in front: the rows as the last step or write_head left them -- after a sparse
+// step only the candidate anchors' box and keypoint channels are that step's.  Runs no kernel and leaves head_stale alone.
+extern "C" int irmv_engine_debug_read_head_raw(irmv_engine *e, int slot, float *head)
+{
+    TRY(check_range(e, slot, 1));
+    if (!head) return fail(IRMV_ERR_ARG, "debug_read_head_raw: head is null");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));
+    return copy_head(e, slot, head);
+}
+
+extern "C" int irmv_engine_write_head(irmv_engine *e, int slot, const float *head)
+{
+    TRY(check_range(e, slot, 1));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));
+    for (int l = 0; l < 3; l++) {
+        std::vector<float> v((size_t)e->lvl_hw[l] * kHeadRec, 0.f);
+        for (int p = 0; p < e->lvl_hw[l]; p++) {
+            const float *o = head + (size_t)(e->lvl_base[l] + p) * e->no;
+            float *r = v.data() + (size_t)p * kHeadRec;
+            memcpy(r, o, 64 * 4);
+            memcpy(r + kClsOff, o + 64, (size_t)e->nc * 4);
+            if (e->nk) memcpy(r + kKptOff, o + 64 + e->nc, (size_t)e->nk * 4);
+        }
+        HIP_TRY(hipMemcpy(e->tensors[e->head_t[l]].slot(slot), v.data(), v.size() * 4, hipMemcpyHostToDevice));
+    }
+    e->head_stale[slot] = 0;
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_read_tap(irmv_engine *e, int slot, const char *name, float *nhwc, int shape[3])
+{
+    TRY(check_range(e, slot, 1));
+    if (!name || !shape) return fail(IRMV_ERR_ARG, "name/shape is null");
+    auto it = e->tensor_idx.find(name);
+    if (it == e->tensor_idx.end()) return fail(IRMV_ERR_ARG, std::string("no tensor named ") + name);
+    const Tensor &t = e->tensors[it->second];
+    shape[0] = t.H; shape[1] = t.W; shape[2] = t.C;
+    if (!nhwc) return IRMV_OK;
+    // (a box branch's gated first conv is lazy only while its slot is stale: a read of it after the read-back step, or before any
+    //  step, runs nothing and so leaves a head written through write_head alone)
+    bool gated_out = false;
+    for (const Op &op : e->ops) gated_out = gated_out || (op.gated_first && op.out_t == it->second);
+    if (e->lazy_tensors.count(t.name) && (!gated_out || e->branch_stale[slot])) TRY(materialize_fused(e, slot));
+    for (int l = 0; l < 3; l++) if (it->second == e->head_t[l]) TRY(ensure_dense_head(e, slot));
+    std::vector<float> v;
+    TRY(read_tensor_f32(e, t, slot, v));
+    memcpy(nhwc, v.data(), v.size() * 4);
+    return IRMV_OK;
+}
+
+// ---- per-layer conv test hooks (tests/test_gpu_conv_candidates.py) ---------------------
+extern "C" int irmv_engine_read_tensor(irmv_engine *e, const char *name, int first, int count, void *dst, size_t bytes)
+{
+    TRY(check_range(e, first, count));
+    if (!name) return fail(IRMV_ERR_ARG, "name is null");
+    auto it = e->tensor_idx.find(name);
+    if (it == e->tensor_idx.end()) return fail(IRMV_ERR_ARG, std::string("no tensor named ") + name);
+    const Tensor &t = e->tensors[it->second];
+    const size_t need = t.slot_elems * t.esize() * count;
+    if (!dst || bytes != need) return fail(IRMV_ERR_ARG, "read_tensor: buffer size does not match the slot range");
+    TRY(irmv_engine_wait(e));
+    for (int l = 0; l < 3; l++)
+        if (it->second == e->head_t[l]) for (int s = first; s < first + count; s++) TRY(ensure_dense_head(e, s));
+    for (const Op &op : e->ops)   // a box branch's first conv behind the tile gate: stale outside the last step's active tiles
+        if (op.gated_first && op.out_t == it->second)
+            for (int s = first; s < first + count; s++) if (e->branch_stale[s]) TRY(materialize_fused(e, s));
+    HIP_TRY(hipMemcpy(dst, t.slot(first), need, hipMemcpyDeviceToHost));
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_debug_read_head_rows(irmv_engine *e, int slot, float *rec, size_t bytes)
+{
+    TRY(check_range(e, slot, 1));
+    if (!rec || bytes != (size_t)e->A * kHeadRec * sizeof(float)) return fail(IRMV_ERR_ARG, "debug_read_head_rows: the buffer must hold num_anchors x 96 floats");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));
+    char *dst = reinterpret_cast<char *>(rec);
+    for (int l = 0; l < 3; l++) {   // (no ensure_dense_head: the rows as the last step or write_head left them)
+        const Tensor &t = e->tensors[e->head_t[l]];
+        const size_t n = t.slot_elems * t.esize();
+        HIP_TRY(hipMemcpy(dst, t.slot(slot), n, hipMemcpyDeviceToHost));
+        dst += n;
+    }
+    return IRMV_OK;
+}
+
+static int conv_op_at(const irmv_engine *e, int op)
+{
+    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
+    if (op < 0 || op >= (int)e->ops.size() || e->ops[op].kind != OP_CONV) return fail(IRMV_ERR_ARG, "not a conv op");
+    return IRMV_OK;
+}
+
+template <size_t N> static void put_name(char (&dst)[N], const std::string &s) { snprintf(dst, N, "%s", s.c_str()); }
+
+// A segment as the listing calls report it.  whole: a segment without a channel count of its own stands for the rest of its
+// tensor (irmv_engine_ops); otherwise it is no segment (irmv_engine_conv_ops).
+static void put_seg(const irmv_engine *e, irmv_conv_seg &d, const SegRef &s, bool whole)
+{
+    memset(&d, 0, sizeof d);
+    if (s.t < 0 || (s.C == 0 && !whole)) return;
+    put_name(d.tensor, e->tensors[s.t].name);
+    d.coff = s.coff; d.C = s.C > 0 ? s.C : e->tensors[s.t].C - s.coff; d.shift = s.shift;
+}
+
+// IRMV_RUN_POISON / _POISON_ONLY of a hook's run: all-ones bytes (a NaN in fp16 and in fp32) over channels [coff, coff + C) of
+// tensor t on slots [first, first + count), what the run must write.
+constexpr uint32_t kRunPoisons = IRMV_RUN_POISON | IRMV_RUN_POISON_ONLY;
+static int poison_output(irmv_engine *e, const Tensor &t, int coff, int C, int first, int count)
+{
+    if (coff + C > t.C) return fail(IRMV_ERR_ARG, "output channels out of range");
+    HIP_TRY(hipMemset2DAsync(static_cast<char *>(t.slot(first)) + (size_t)coff * t.esize(), (size_t)t.C * t.esize(), 0xff, (size_t)C * t.esize(), (size_t)count * t.H * t.W, e->stream));
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_conv_ops(irmv_engine *e, irmv_conv_op *ops, int cap, int *n)
+{
+    if (!e || !n) return fail(IRMV_ERR_ARG, "engine / n is null");
+    int k = 0;
+    for (size_t i = 0; i < e->ops.size(); i++) {
+        const Op &op = e->ops[i];
+        if (op.kind != OP_CONV) continue;
+        if (ops && k < cap) {
+            irmv_conv_op &r = ops[k];
+            memset(&r, 0, sizeof r);
+            r.op = (int32_t)i;
+            put_name(r.layer, op.layer);
+            r.ks = op.cfg.ks; r.stride = op.cfg.stride; r.act = op.cfg.act; r.out_f32 = op.cfg.out_f32;
+            r.cin = op.cin; r.cout = op.cout; r.cout_pad = op.cout_pad;
+            r.Hin = op.Hin; r.Win = op.Win; r.Hout = op.Hout; r.Wout = op.Wout;
+            put_seg(e, r.s0, op.s0, false);
+            put_seg(e, r.s1, op.s1, false);
+            if (op.res_t >= 0) put_seg(e, r.res, SegRef{op.res_t, op.res_coff, op.cout, 0}, false);
+            const Tensor &ot = e->tensors[op.out_t];
+            put_name(r.out_tensor, ot.name);
+            r.out_coff = op.out_coff;
+            r.out_lazy = e->lazy_tensors.count(ot.name) ? 1 : 0;
+            r.fused = op.fuse_next >= 0;
+            r.tune_fused = op.tune_fuse[0] >= 0 || op.tune_fuse[1] >= 0;
+            const int f = op.fuse_next >= 0 ? op.fuse_next : std::max(op.tune_fuse[0], op.tune_fuse[1]);
+            if (f >= 0) {
+                const Op &o2 = e->ops[f];
+                put_name(r.fuse_layer, o2.layer);
+                put_name(r.fuse_tensor, e->tensors[o2.out_t].name);
+                r.fuse_coff = o2.out_coff; r.fuse_cout = o2.cout; r.fuse_cout_pad = o2.cout_pad;
+            }
+            put_name(r.kname, op.kname);
+            put_name(r.kname_one, op.kname_one);
+        }
+        k++;
+    }
+    *n = k;
+    return IRMV_OK;
+}
+
+// The op as the tuner saw it at tune_count (which of its two passes, and the fused 1x1 that pass was tuned for);
+// cands: that pass's candidate list, exactly as autotune_convs built it.
+static int conv_tune_pass(const irmv_engine *e, int op, int tune_count, Op &o, std::vector<TuneCand> &cands)
+{
+    TRY(conv_op_at(e, op));
+    const int share = stream_share(e, e->cfg.num_slots);
+    if (tune_count != share && tune_count != 1) return fail(IRMV_ERR_ARG, "tune_count is neither the stream share nor 1");
+    o = e->ops[op];
+    o.fuse_next = o.tune_fuse[tune_count == share ? 0 : 1];
+    const ConvView v = conv_view(e, o, 0, tune_count);
+    cands = tune_candidates(o, v.a, tune_count, v.want_fuse, v.lds_ok, e->sw.tune, e->num_cus);
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_conv_candidates(irmv_engine *e, int op, int tune_count, irmv_conv_cand *out, int cap, int *n)
+{
+    if (!n) return fail(IRMV_ERR_ARG, "n is null");
+    Op o;
+    std::vector<TuneCand> cands;
+    TRY(conv_tune_pass(e, op, tune_count, o, cands));
+    for (size_t i = 0; i < cands.size() && out && (int)i < cap; i++) {
+        irmv_conv_cand &r = out[i];
+        memset(&r, 0, sizeof r);
+        conv_cfg_name(cands[i].c, r.name, sizeof r.name);
+        const TuneEntry t = tune_entry(cands[i].c);
+        r.mt = t.mt; r.nt = t.nt; r.flags = t.flags; r.ipw = t.ipw;
+        r.forced = cands[i].forced;
+    }
+    *n = (int)cands.size();
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_run_conv_candidate(irmv_engine *e, int op, int tune_count, int cand, int first, int count, uint32_t flags)
+{
+    TRY(check_range(e, first, count));
+    Op o;
+    std::vector<TuneCand> cands;
+    TRY(conv_tune_pass(e, op, tune_count, o, cands));
+    if (cand < -1 || cand >= (int)cands.size()) return fail(IRMV_ERR_ARG, "no such candidate");
+    const Op &real = e->ops[op];
+    // re-running a conv must not change its own inputs: refuse an output range that overlaps one of them
+    auto overlaps = [](int t, int lo, int hi, int t2, int lo2, int hi2) { return t >= 0 && t == t2 && lo < hi2 && lo2 < hi; };
+    const int o0 = real.out_coff, o1 = real.out_coff + real.cout_pad;
+    if (overlaps(real.out_t, o0, o1, real.s0.t, real.s0.coff, real.s0.coff + real.s0.C) ||
+        overlaps(real.out_t, o0, o1, real.s1.t, real.s1.coff, real.s1.coff + real.s1.C) ||
+        overlaps(real.out_t, o0, o1, real.res_t, real.res_coff, real.res_coff + real.cout_pad))
+        return fail(IRMV_ERR_ARG, "conv op writes one of its own inputs");
+    TRY(irmv_engine_wait(e));
+    ConvCfg c;
+    if (cand >= 0) c = cands[cand].c;
+    else {   // the engine's own choice for tune_count, with the epilogue a step runs it with
+        o = real;
+        c = tune_count == stream_share(e, e->cfg.num_slots) ? real.cfg : real.cfg_one;
+    }
+    const ConvView v = conv_view(e, o, first, count);
+    if (flags & kRunPoisons) {
+        // the real output channels: the fused 1x1's slice of the head when the run carries it (the 3x3's own output then never
+        // leaves the registers)
+        const Op &w = v.a.n2 > 0 ? e->ops[o.fuse_next] : real;
+        TRY(poison_output(e, e->tensors[w.out_t], w.out_coff, w.cout, first, count));
+    }
+    if (flags & IRMV_RUN_POISON_ONLY) { HIP_TRY(hipStreamSynchronize(e->stream)); return IRMV_OK; }
+    if (!run_conv(o, c, v.a, count, e->stream)) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        return IRMV_DECLINED;
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return IRMV_OK;
+}
+
+// ---- per-op test hooks (tests/test_gpu_graph_ops.py) ---------------------------------
+static const char *op_kind_name(OpKind k)   // (in OpKind's order)
+{
+    static const char *const names[] = {"pre", "conv0", "conv", "pool", "nms", "light", "front", "c2f2", "c2f32", "dw", "shuffle", "scan", "bneck", "kpt3", "demosaic", "crop"};
+    static_assert(sizeof names / sizeof *names == OP_CROP + 1, "a name per OpKind");
+    return (unsigned)k <= OP_CROP ? names[k] : "?";
+}
+
+// The activation channels op writes: [*coff, *coff + *C) of tensor *t (-1: none).  The pool writes slices 1..3 of its
+// tensor (slice 0 is its input); the ops that write a whole tensor (preprocess, model.0.conv, shuffle, fused kernels
+// standing for a layer) record no channel count of their own.
+static void op_output(const irmv_engine *e, const Op &op, int *t, int *coff, int *C)
+{
+    *t = op.out_t; *coff = 0; *C = 0;
+    if (op.out_t < 0) return;
+    const Tensor &ot = e->tensors[op.out_t];
+    if (op.kind == OP_POOL) { *coff = ot.C / 4; *C = ot.C - ot.C / 4; return; }
+    *coff = op.out_coff;
+    *C = op.cout > 0 ? op.cout : ot.C - op.out_coff;
+}
+
+extern "C" int irmv_engine_ops(irmv_engine *e, irmv_graph_op *ops, int cap, int *n)
+{
+    if (!e || !n) return fail(IRMV_ERR_ARG, "engine / n is null");
+    for (size_t i = 0; ops && i < e->ops.size() && (int)i < cap; i++) {
+        const Op &op = e->ops[i];
+        irmv_graph_op &r = ops[i];
+        memset(&r, 0, sizeof r);
+        r.op = (int32_t)i;
+        put_name(r.kind, op_kind_name(op.kind));
+        put_name(r.layer, op.layer);
+        put_name(r.kname, op.kname);
+        put_seg(e, r.s0, op.kind == OP_POOL ? SegRef{op.out_t, 0, e->tensors[op.out_t].C / 4, 0} : op.s0, true);
+        put_seg(e, r.s1, op.s1, true);
+        int t, coff, C;
+        op_output(e, op, &t, &coff, &C);
+        if (t >= 0) {
+            put_name(r.out_tensor, e->tensors[t].name);
+            r.out_coff = coff; r.out_C = C;
+        }
+        r.fused_away = op.fused_away ? 1 : 0;
+    }
+    *n = (int)e->ops.size();
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_run_op(irmv_engine *e, int op, int first, int count, uint32_t flags)
+{
+    TRY(check_range(e, first, count));
+    if (op < 0 || op >= (int)e->ops.size()) return fail(IRMV_ERR_ARG, "no such op");
+    const Op &o = e->ops[op];
+    if (o.kind != OP_CONV0 && o.kind != OP_POOL && o.kind != OP_DW && o.kind != OP_SHUF)
+        return fail(IRMV_ERR_ARG, std::string("run_op runs conv0, pool, dw and shuffle ops, not ") + op_kind_name(o.kind));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));
+    if (flags & kRunPoisons) {
+        int t, coff, C;
+        op_output(e, o, &t, &coff, &C);
+        TRY(poison_output(e, e->tensors[t], coff, C, first, count));
+    }
+    if (flags & IRMV_RUN_POISON_ONLY) { HIP_TRY(hipStreamSynchronize(e->stream)); return IRMV_OK; }
+    Launch l;   // (a plain launch of the op: no group, no fusion, no gate)
+    l.op = op;
+    TRY(launch_op(e, l, first, count, post_args(e, first), 0u, false, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return IRMV_OK;
+}
+
+extern "C" int irmv_sppf_slab(int batch, int H, int W, int C)
+{
+    if (batch < 1 || H < 1 || W < 1 || C < 8 || C % 8 != 0) return fail(IRMV_ERR_ARG, "sppf_slab: bad shape");
+    return sppf_slab(batch, H, W, C);
+}
+
+extern "C" int irmv_engine_read_raw(irmv_engine *e, int slot, irmv_raw_dets *out)
+{
+    TRY(check_range(e, slot, 1));
+    if (!out) return fail(IRMV_ERR_ARG, "out is null");
+    const DevFrameOut &fo = e->fout_host[slot];
+    const DevDet *d = e->dets_host + (size_t)slot * e->cfg.max_det;
+    out->num_dets = fo.num_dets;
+    out->n_candidates = fo.n_candidates;
+    for (int i = 0; i < e->cfg.max_det; i++) {
+        if (out->det_boxes) memcpy(out->det_boxes + 4 * i, d[i].box_net, 16);
+        if (out->det_scores) out->det_scores[i] = d[i].score;
+        if (out->det_classes) out->det_classes[i] = d[i].cls;
+        if (out->det_anchors) out->det_anchors[i] = d[i].anchor;
+        if (out->det_kpts) memcpy(out->det_kpts + 8 * i, d[i].kpts_net, 32);
+    }
+    return IRMV_OK;
+}
+
+// The events of a profiled step -- launch i of the plan runs between ev[2 i] and ev[2 i + 1] --, destroyed however
+// irmv_engine_profile returns.
+struct ProfileEvents {
+    std::vector<hipEvent_t> ev;
+    ~ProfileEvents() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); }
+};
+
+extern "C" int irmv_engine_profile(irmv_engine *e, int first, int count, irmv_kernel_stat *stats, int cap, int *n)
+{
+    TRY(check_range(e, first, count));
+    if (!n) return fail(IRMV_ERR_ARG, "n is null");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    // Eager replay of the step's launches on the engine stream, every kernel bracketed by an event
+    // pair.  The kernels are idempotent and are launched kProfileRepeat times inside their bracket: an event pair around ONE launch also times ~4 us of
+    // command-processor hand-over, which would read as kernel time on these 5-80 us kernels.
+    // (Event-record nodes inside a captured graph cannot be read back with hipEventElapsedTime on
+    // ROCm 7.2: "invalid resource handle".)
+    TRY(irmv_engine_wait(e));
+    const StepKind kind = count == 1 ? STEP_ONE : STEP_BATCH;
+    const std::vector<Launch> &plan = e->plans[kind];
+    ProfileEvents pe;
+    pe.ev.resize(2 * plan.size(), nullptr);
+    for (hipEvent_t &x : pe.ev) HIP_TRY(hipEventCreate(&x));
+    TRY(enqueue_step(e, kind, first, count, e->stream, kProfileRepeat, &pe.ev));   // (a window engine crops out of its device frames, as a submit without IRMV_SUBMIT_H2D does)
+    mark_stepped(e, first, count);
+    TRY(copy_out(e, first, count));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (size_t i = 0; i < plan.size(); i++) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, pe.ev[2 * i], pe.ev[2 * i + 1]));
+        const Launch &l = plan[i];
+        if ((int)i < cap && stats) {
+            irmv_kernel_stat &st = stats[i];
+            memset(&st, 0, sizeof st);
+            put_name(st.name, l.name);
+            put_name(st.layer, l.layer);
+            st.flops = l.flops * count;
+            st.bytes = l.bytes * count + l.launch_bytes;
+            st.ms = l.once ? ms : ms / (float)kProfileRepeat;
+        }
+    }
+    *n = (int)plan.size();
+    return IRMV_OK;
+}

@@ -1,0 +1,339 @@
+// Private to the engine's host files (engine*.cpp); include/ never sees it.  What every part needs -- the error helpers, the
+// engine object and its pieces, the environment switches -- and the functions that cross the files' boundaries:
+//   engine.cpp        error / version / device ABI, configuration and front geometry, create / destroy / getters, NUMA and
+//                     window ABI, extract-parameter and Bayer-ISP setters, the PnP object
+//   engine_graph.cpp  .irmw blob, tensors, weight packing, the op list (build_engine)
+//   engine_tune.cpp   everything decided by timing at creation: conv tiles and their cache, head groups, the synchronous launch form
+//   engine_plan.cpp   head fusion, the sparse head's reordering, the launch list of each step kind
+//   engine_step.cpp   kernel arguments, the per-op launcher, steps, copies, graph capture, submit / wait / results
+//   engine_hooks.cpp  read-backs, debug_*, LDS fill / probe, conv and op test hooks, the profiler, the light trace
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <map>
+#include <mutex>
+#include <set>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/irmv_hip.h"
+#include "irmv_common.hpp"
+#include "numa.hpp"
+
+using namespace irmv;
+
+namespace irmv { int fail(int code, const std::string &msg); }   // sets the calling thread's irmv_last_error text; returns code
+#define HIP_TRY(expr)                                                                                 \
+    do {                                                                                              \
+        hipError_t _e = (expr);                                                                       \
+        if (_e != hipSuccess)                                                                         \
+            return fail(IRMV_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));             \
+    } while (0)
+
+#define TRY(x)            \
+    do {                  \
+        int _rc = (x);    \
+        if (_rc) return _rc; \
+    } while (0)
+
+struct LayerW {
+    std::string name;
+    int cin, cout, k, stride, act;
+    int groups;         // > 1: depthwise (groups == cout, cin == 1)
+    const uint16_t *w;  // OHWI fp16 bits (points into the blob copy)
+    const float *b;
+};
+
+struct Tensor {
+    std::string name;
+    void *base = nullptr;
+    size_t slot_elems = 0;
+    int H = 0, W = 0, C = 0;
+    bool f32 = false;
+    size_t esize() const { return f32 ? 4 : 2; }
+    void *slot(int s) const { return static_cast<char *>(base) + (size_t)s * slot_elems * esize(); }
+};
+
+struct SegRef { int t = -1, coff = 0, C = 0, shift = 0; };
+
+// The front's switches (front_plan): IRMV_FRONT_FASTX / _DIRECT / _TILE8 =0 clear them (the last keeps the 4-row tile); all
+// on for the plan irmv_front_plan exports.
+struct FrontSwitches { bool fastx = true, direct = true, tall = true; };
+
+// The tuner's switches: autotune_convs reads them, and the conv test hooks list the same candidates from them.
+struct TuneSwitches {
+    bool untuned, verbose, warn;        // IRMV_AUTOTUNE=0, IRMV_AUTOTUNE_VERBOSE, IRMV_TUNE_WARN
+    bool has_s2, has_wres;              // IRMV_FORCE_S2=lds|ct|deep, IRMV_FORCE_WRES=<n> (parity tests) are set ...
+    std::string force_s2, force_wres;   // ... to these values (copies: an engine's hooks read them after the environment may have changed)
+    bool force_pw, force_pwn, force_cm, force_w8, force_nt8, force_pf4;
+    bool no_pw, no_pwn, no_pf2, no_pf4, no_cm, no_w8, no_nt8, no_wres, no_deep;
+};
+
+// Every IRMV_* environment switch the engine reads, read once at the top of irmv_engine_create (engine.cpp read_switches):
+// each takes effect for every engine created after it is set.  (IRMV_LOG_ALLOC and IRMV_TUNE_CACHE are per process, not per
+// engine, and are not here.)
+struct EngineSwitches {
+    TuneSwitches tune{};
+    FrontSwitches front;
+    bool fused_front = true, fused_c2f = true;   // IRMV_FUSED_FRONT=0: preprocess, model.0.conv and model.1.conv run as layers; IRMV_FUSED_C2F=0: no fused C2f kernel (model.2's, the 32-channel blocks')
+    bool bneck64 = true;           // single-frame steps run the 64-channel Bottlenecks of the C2f blocks (and their cv2) as one launch each (IRMV_BNECK64=0: off)
+    bool kpt3 = true;              // the keypoint branch of a Detect level as one launch (engines that do not merge the first-stage Detect convs; IRMV_KPT3=0: off)
+    bool fused_head = true;        // IRMV_FUSED_HEAD=0: no Detect final 1x1 rides in the epilogue of the conv in front of it
+    int merge_head0 = -1;          // IRMV_MERGE_HEAD0=0: never merge the first-stage Detect convs of a level, =1: always; else: engines that never batch
+    bool group_head = true;        // IRMV_GROUP_HEAD=0: no grouped Detect-branch launches
+    bool group_verbose = false;    // IRMV_GROUP_VERBOSE: the head groups' timings on stderr
+    bool group_force = false;      // IRMV_GROUP_FORCE=1 (parity test): group even where the one launch timed slower
+    bool has_streams = false; int streams = 0;   // IRMV_STREAMS=<n> is set, to this number of compute streams
+    bool numa = true;              // IRMV_NUMA=0: plain hipHostMallocDefault wherever the creating thread happens to run
+    bool inline_copies = false;    // IRMV_INLINE_COPIES=1: round-1 behaviour, copies on the compute stream
+    bool graph_upload = true;      // uploads that ride the compute stream are a node of the step's graph (IRMV_GRAPH_UPLOAD=0: a separate launch in front of it; measured
+                                   // again in round 5 with the upload kernel: 0.3365 - 0.3438 ms against 0.335 - 0.336 as the first node: no hiding of the graph's launch cost)
+    int upload_kernel_blocks = 256;   // 0: synchronous single-frame uploads ride the copy engine like every other upload (IRMV_UPLOAD_KERNEL=0)
+    bool window_upload = true;     // synchronous steps of one or two slots crop straight out of the pinned slot (IRMV_WINDOW_UPLOAD=0: upload, then crop)
+    int sync_launch = -1;          // IRMV_SYNC_LAUNCH=graph|eager forces detect()'s launch form (0 | 1); anything else, e.g. "auto": choose_sync_launch times it
+    bool split_scan = true;        // scan + box decode as a multi-workgroup kernel in front of nms_pnp (IRMV_SPLIT_SCAN=0: inside it)
+    bool emit_scan = true, sparse_head = true, sparse_branch = true;   // IRMV_EMIT_SCAN=0: the class-branch conv epilogues emit no candidates; IRMV_SPARSE_HEAD=0: every head row is stored;
+                                   // IRMV_SPARSE_BRANCH=0: no tile gate behind the class carriers
+    bool zero_copy_results = true; // IRMV_ZERO_COPY_RESULTS=0: device records + a D2H copy in keypoint mode too
+    bool post_keys_only = false;   // IRMV_POST_KEYS_ONLY=1 (tests): run_post's NMS ignores scan_decode_kernel's boxes and decodes its own, as a whole step's does
+    bool nms_classwalk = true;     // IRMV_NMS_CLASSWALK=0
+    int nms_prefilter = 1;         // PostArgs::prefilter.  IRMV_NMS_PREFILTER=0: crowded frames sort and mask every candidate (round-3 behaviour; bit-identical);
+                                   // IRMV_NMS_PRE=<hi>,<lo> (experiment: size of the head of the list): hi | lo << 16
+    bool nms_stamps = false; int nms_stamps_slots = 0;   // IRMV_NMS_STAMPS=<n>: the NMS kernel stamps its phases, the destructor prints the first n slots' (at least four)
+};
+
+enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_DEMOSAIC, OP_CROP };
+
+struct Op {
+    OpKind kind;
+    std::string layer;
+    ConvCfg cfg{};      // tile shape for full batched steps (count == num_slots)
+    ConvCfg cfg_one{};  // tile shape for single-frame steps (latency mode)
+    char kname_one[48] = {0};
+    SegRef s0, s1;
+    int Hin = 0, Win = 0, Hout = 0, Wout = 0, cin = 0, cout = 0, cout_pad = 0, ksteps = 0;
+    int out_t = -1, out_coff = 0, res_t = -1, res_coff = 0;
+    half_t *w_packed = nullptr;
+    half_t *w_k16 = nullptr;   // 1x1 layers with Cin = 16 and fp32 output (the keypoint branch's finals): the weights in the A layout of v_mfma_f32_16x16x16_f16 [64 lanes][4]
+    half_t *w_lds[4] = {nullptr, nullptr, nullptr, nullptr};   // LDS-kernel layout for nt = 1 / 2 / 4 / 8 (eligible 3x3 layers only; nt = 8: stride-2 layers with >= 128 output channels)
+    float *bias = nullptr;
+    double flops = 0, bytes = 0;  // per frame (bytes: activations in + out, plus the weights)
+    double w_bytes = 0;           // the weights' share of `bytes`: read once per LAUNCH, not once per frame (irmv_engine_profile)
+    double out_bytes = 0;         // the output's share (a conv that carries a fused 1x1 writes that layer's output instead of its own)
+    bool pair = false;
+    int level = -1;    // Detect level of a head op (-1: trunk)
+    char kname[48] = {0};
+    int sub[4] = {-1, -1, -1, -1};   // OP_C2F2 / OP_C2F32: indices of the layer ops whose weights it uses
+    int mode = 0;                    // OP_C2F32: 0 whole block, 1 cv1 + first bottleneck, 2 last bottleneck + cv2
+    bool shortcut = false;
+    int fuse_next = -1;        // LDS 3x3 conv: index of the 1x1 op computed in its epilogue (Detect-head finals), -1 = none
+    bool fused_away = false;   // preprocess / model.0 / model.1 when the fused front kernel runs them (kept for read-backs)
+    int group = -1;            // single-frame steps: index into irmv_engine::head_groups of the one launch this conv rides in
+    int bneck = -1;            // single-frame steps: index of the OP_BNECK launch (k_bneck.hip) that computes this conv; OP_BNECK itself: 1 = kept
+    int kpt3 = -1;             // a keypoint-branch conv: index of the OP_KPT3 launch (k_kpt.hip) that computes its level's branch in every step; OP_KPT3 itself: 1
+    bool gated_first = false;  // a Detect box branch's first conv that some step runs behind the tile gate (sparse branch): its tensor is lazy, the read-back step runs it densely
+    int tune_fuse[2] = {-1, -1};   // OP_CONV: fuse_next as the autotuner's two passes (stream share, one slot) found it (test hooks rebuild their candidate lists)
+};
+
+// What a step launches depends only on its kind and the engine, so each kind's launch list is decided at creation (build_step_plans).
+// BATCH: count > 1 slots; ONE: one slot; MATERIALIZE: the layers fused kernels keep on chip (read-backs); POST: run_post's kernels.
+enum StepKind { STEP_BATCH, STEP_ONE, STEP_MATERIALIZE, STEP_POST };
+
+struct Launch {
+    int op = -1, group = -1;  // index into irmv_engine::ops; >= 0: the head group (head_groups) launched at its first member's place
+    bool cfg_one = false;     // OP_CONV: runs op.cfg_one, not op.cfg
+    bool fused = false;       // OP_CONV: carries its fuse_next 1x1 in the epilogue
+    unsigned scan = 0;        // bit k: member k of the group (a lone conv: bit 0) appends scan candidates from its epilogue
+    bool keys_only = false;   // OP_NMS: decodes the boxes of its key lists itself
+    bool sparse = false;      // a Detect box carrier or OP_KPT3 behind its level's class carrier: stores the candidate anchors' head rows only
+    int gate = 0;             // sparse branch, ConvArgs::tile_gate / Kpt3Args::tile_gate: 0 = off, 1 = halo 0 (writes head rows), 2 = halo 1 (box branch's first conv)
+    bool once = false;        // not repeated under irmv_engine_profile (appends to, consumes or rewrites per-frame lists)
+    std::string name, layer;  // irmv_engine_profile's row
+    double flops = 0, bytes = 0, launch_bytes = 0;   // per frame; launch_bytes (the weights): once per launch
+};
+
+struct GraphKey {
+    int first, count;
+    StepKind kind;
+    bool upload;   // the frames' upload is the graph's first node
+    bool operator<(const GraphKey &o) const { return std::tie(first, count, kind, upload) < std::tie(o.first, o.count, o.kind, o.upload); }
+};
+
+// Events of one submitted slot group [first, first + count): h2d = its frames are in HBM (async upload only);
+// out = its kernels have run and its results are host-visible (so its device frames may be overwritten too).
+struct SlotGroup {
+    int first = 0, count = 0;
+    hipEvent_t h2d = nullptr, out = nullptr;
+    hipStream_t compute = nullptr;   // compute stream of the last submit
+    bool in_flight = false;          // submitted and not yet known complete
+    bool async_up = false;           // the last submit uploaded on the side stream (event h2d is valid)
+};
+
+struct irmv_engine {
+    irmv_engine_cfg cfg{};
+    int nc = 0, nk = 0, A = 0, no = 0;
+    int backbone = 0;   // 0: C2f stages (YOLOv8n), 1: ShuffleNetV2 stages (blob header)
+    int num_cus = 256;  // compute units of the device (persistent kernels size their grids by it)
+    int numa_node = -1;     // host NUMA node closest to the device (hipDeviceAttributeHostNumaId); -1: unknown
+    bool numa_placed = false;   // the pinned frame slots were allocated and first touched under that node's CPU set and memory policy
+    // Single-frame engines: the independent Detect-branch convs of the three levels as one launch per stage (k_conv.hip
+    // conv3x3_lds_multi / conv_mfma_multi).  family 0: LDS 3x3 with tile (mt 1, nt); 1: direct kernel with cfg.
+    struct HeadGroup { std::vector<int> members; int family = 0, nt = 1; ConvCfg cfg{}; char name[48] = {0}; };
+    std::vector<HeadGroup> head_groups;
+    bool emit_scan = false;   // candidates are emitted by the class-branch conv epilogues (needs split_scan's counters and all three levels fused)
+    int *cand_counts = nullptr;
+    // Sparse head: a step stores the head rows of candidate anchors only (the one reader, nms_pnp_kernel, reads no others).
+    // The class carriers set a bit per candidate anchor, box carriers and OP_KPT3 store where it is set, nms_pnp_kernel clears
+    // it again.  Needs emit_scan; IRMV_SPARSE_HEAD=0: every row is stored.  head_stale[slot]: the slot's head in memory is
+    // the sparse one of its last step -- whatever reads it runs the read-back step first (ensure_dense_head).
+    bool sparse_head = false;
+    unsigned int *cand_bits = nullptr;   // [S][cand_words], zero between steps
+    int cand_words = 0;
+    std::vector<char> head_stale;
+    // Sparse branch (IRMV_SPARSE_BRANCH=0: off; only with sparse_head): the launches behind the class carriers also skip the
+    // COMPUTATION of (tile, image) pairs without a candidate anchor (Launch::gate).  The box branch's gated first conv leaves its
+    // tensor stale outside active tiles: branch_stale[slot], until the read-back step has run it densely.
+    bool sparse_branch = false;
+    std::vector<char> branch_stale;
+    int lvl_hw[3] = {0, 0, 0}, lvl_base[3] = {0, 0, 0};
+    size_t frame_bytes = 0;       // one HWC source frame (src_dev, rot_dev)
+    size_t src_bytes = 0;         // one source slot as the producer writes it (src_host, and raw_dev or src_dev): frame_bytes, or W*H for a Bayer engine
+    hipStream_t stream = nullptr;                 // stream 0: single-slot detect(), read-backs, profile
+    hipStream_t extra_streams[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // streams 1..num_streams-1
+    int num_streams = 1;
+    // frame hand-off: uploads can ride a stream of their own, chained to the compute streams by the
+    // events of the submitted slot group
+    hipStream_t h2d_stream = nullptr;
+    std::map<std::pair<int, int>, SlotGroup> groups;   // (first, count) -> events of that group's last submit
+    std::vector<SlotGroup *> slot_owner;               // per slot: the group whose submit touched it last
+    uint8_t *src_host = nullptr;  // pinned [S][frame]
+    int sync_launch = 0;               // how a synchronous single-frame step (detect()) reaches the GPU: 0 = one hipGraph replay (upload = its first node), 1 = launched
+                                       // kernel by kernel behind the upload; chosen by timing at creation (choose_sync_launch), IRMV_SYNC_LAUNCH=graph|eager forces
+    uint8_t *src_host_dev = nullptr;   // the same memory through the device's mapping (the upload kernel reads it: launch_upload_frames)
+    uint8_t *src_dev = nullptr;   // [S][frame]
+    uint8_t *raw_dev = nullptr;   // Bayer engines: [S][W*H] raw frames, demosaiced into src_dev by the first op of a step (OP_DEMOSAIC)
+    BayerArgs bayer{};            // (pointers, slot strides, pattern phase and gains of that op; raw / dst set per launch)
+    // The ISP table of a Bayer engine (irmv_engine_set_bayer_isp): gains and tone LUT folded into T[c][v], [3][256] bytes in
+    // device memory, read by the table kernels when they run -- a captured graph holds the pointer, never the values.
+    // bayer_table: the demosaic is a table kernel (an MHC engine from creation on, a bilinear one from its first set).
+    uint8_t *isp_table_dev = nullptr;
+    bool bayer_table = false, bayer_mhc = false;
+    uint16_t isp_gain[3] = {256, 256, 256};
+    uint8_t isp_lut[kBayerTableBytes] = {0};
+    uint8_t *rot_dev = nullptr;   // [frame]
+    // Tracking window (irmv_engine_cfg.win_width / win_height): cfg.src_width x cfg.src_height is then the WINDOW -- what every
+    // kernel behind the crop sees as its source frame -- and full_w x full_h the frame the producer writes.  OP_CROP cuts the
+    // window at win_dev[slot] out of the slot's full frame (full_dev, or the pinned slot itself) into its src_dev frame.
+    // Without a window full_w x full_h equals the cfg's source size and none of the rest exists.
+    bool window = false;
+    int full_w = 0, full_h = 0;
+    size_t full_bytes = 0;            // one full HWC frame (full_dev)
+    uint8_t *full_dev = nullptr;      // [S][full frame]: what an HWC window engine's uploads and a Bayer one's demosaic write
+    int2 *win_dev = nullptr;          // [S] the windows' corners in buffer coordinates, read by window_crop_kernel when it runs
+    std::vector<int2> win_org;        // [S] the corners as set, in result coordinates (the rotated frame under rotate180)
+    std::vector<int2> sub_org;        // [S] ... as they were at the slot's last submit: what its results are shifted by
+    PnpConst pnp_base{};              // the camera as configured; pnp_dev[slot] = pnp_base with the principal point moved by the slot's corner
+    AxisTap *tap_x = nullptr, *tap_y = nullptr;
+    std::vector<Tensor> tensors;
+    std::map<std::string, int> tensor_idx;
+    std::vector<Op> ops;
+    std::vector<Launch> plans[STEP_POST + 1];   // per StepKind: the launches of such a step, in order (build_step_plans)
+    std::vector<void *> dev_allocs;
+    int head_t[3] = {-1, -1, -1};
+    float *head_all = nullptr;
+    PnpConst *pnp_dev = nullptr;
+    long long *dbg_dev = nullptr;
+    std::set<std::string> lazy_tensors;   // tensors a step does not write because a fused kernel keeps them on chip
+    bool fused_front = false;          // OP_FRONT replaces preprocess + model.0.conv + model.1.conv in a step
+    irmv_front_plan_t front{};         // the front's geometry as front_plan decided it: tile grid, stage bytes, box = the valid (non-padding) net-input column / row ranges,
+                                       // fastx / fx_i0 / fx_step: every x tap is (i0 + 2 k, i0 + 2 k + 1; 1/2): the front kernel's 2 : 1 column path
+    bool classical = false;            // four points from the classical light extraction instead of a keypoint head
+    signed char *light_labels = nullptr;   // label pool: light_pool bytes per slot
+    size_t light_pool = 0;
+    short *light_points = nullptr, *light_hulls = nullptr;
+    float *light_boxes = nullptr;      // explicit boxes of irmv_engine_extract_armors
+    DevDet *light_dets_dev = nullptr, *light_dets_host = nullptr;
+    LightTrace *light_trace_dev = nullptr;   // [max_det], allocated by the first irmv_engine_light_trace
+    float *boxes = nullptr;
+    unsigned long long *keys = nullptr;
+    DevDet *dets_dev = nullptr, *dets_host = nullptr, *dets_host_dev = nullptr;       // *_host_dev: device view of the pinned buffer
+    DevFrameOut *fout_dev = nullptr, *fout_host = nullptr, *fout_host_dev = nullptr;
+    bool zero_copy_results = false;   // the NMS kernel writes its results straight into pinned host memory (no D2H copy)
+    half_t *conv0_w = nullptr;
+    float *conv0_b = nullptr;
+    PostArgs post{};
+    std::map<GraphKey, hipGraphExec_t> graphs;
+    double last_detect_ms = 0;
+    std::vector<uint8_t> blob;
+    std::vector<LayerW> layers;
+    std::vector<std::vector<uint16_t>> dequant;   // int8 blobs: per layer fp16(q * scale), what LayerW::w points to
+    std::vector<std::vector<uint16_t>> merged_w;  // Detect first-stage convs of a level concatenated along cout (single-frame engines)
+    std::vector<std::vector<float>> merged_b;
+    bool merge_head0 = false;
+    EngineSwitches sw{};       // the environment as irmv_engine_create found it
+
+    ~irmv_engine();
+};
+
+constexpr int kProfileRepeat = 4;   // launches per event bracket in irmv_engine_profile
+
+struct TuneEntry { int mt, nt, flags, ipw; };   // a choice as the IRMV_TUNE_CACHE file holds it (flags: tile_flags)
+// forced: an IRMV_FORCE_* switch puts the layer on this candidate (parity tests) -- the last forced one that runs is the choice
+struct TuneCand { ConvCfg c; bool forced; };
+// How the tuner sees a conv op on slots [first, first + count): its arguments, whether it is tuned for its branch's final
+// 1x1 in the epilogue (op.fuse_next), and its kernel family.  autotune_convs and the conv test hooks both use it.
+struct ConvView { ConvArgs a; bool want_fuse, lds_ok; };
+
+// slots handled by one stream of a multi-slot submit
+inline int stream_share(const irmv_engine *e, int count) { return (count + e->num_streams - 1) / e->num_streams; }
+// the device memory an upload of the source slots writes: the raw slots of a Bayer engine, else the HWC frames themselves
+// (a window engine's full frames)
+inline uint8_t *upload_dev(const irmv_engine *e) { return e->raw_dev ? e->raw_dev : (e->window ? e->full_dev : e->src_dev); }
+// profile / op name of a Bayer engine's demosaic as it runs now
+inline const char *demosaic_kname(const irmv_engine *e) { return e->bayer_mhc ? "bayer_demosaic_mhc" : (e->bayer_table ? "bayer_demosaic_lut" : "bayer_demosaic"); }
+inline ConvWeights conv_weights(const Op &op) { return {op.w_packed, {op.w_lds[0], op.w_lds[1], op.w_lds[2], op.w_lds[3]}, op.w_k16}; }
+inline bool run_conv(const Op &op, const ConvCfg &c, const ConvArgs &a, int count, hipStream_t s) { return launch_conv(c, a, conv_weights(op), count, s); }
+
+namespace irmv {
+// engine.cpp
+void log_range(const irmv_engine *e, const char *what, const void *p, size_t bytes);
+bool upload_aligned(size_t src_bytes, int first, int count);
+void front_plan(const irmv_engine_cfg &c, const FrontSwitches &sw, irmv_front_plan_t *p, std::vector<AxisTap> &tx, std::vector<AxisTap> &ty);
+int write_window(irmv_engine *e, int slot);
+int write_isp_table(irmv_engine *e);
+// engine_graph.cpp
+int dev_alloc(irmv_engine *e, void **p, size_t bytes);
+int load_blob(irmv_engine *e);
+int build_engine(irmv_engine *e);
+// engine_tune.cpp
+TuneEntry tune_entry(const ConvCfg &c);
+std::vector<TuneCand> tune_candidates(const Op &op, const ConvArgs &a, int count, bool want_fuse, bool lds_ok, const TuneSwitches &sw, int num_cus);
+ConvView conv_view(const irmv_engine *e, const Op &op, int first, int count);
+int autotune_convs(irmv_engine *e);
+int build_head_groups(irmv_engine *e);
+int choose_sync_launch(irmv_engine *e);
+// engine_plan.cpp
+void finalize_head_fusion(irmv_engine *e);
+void build_step_plans(irmv_engine *e);
+// engine_step.cpp
+void fill_conv_args(const irmv_engine *e, const Op &op, int first, int count, ConvArgs &a, bool fused = false);
+LightArgs light_args(const irmv_engine *e, int first);
+PostArgs post_args(const irmv_engine *e, int first);
+bool launch_head_group(const irmv_engine *e, const irmv_engine::HeadGroup &g, int first, const PostArgs *pa, unsigned scan, hipStream_t s);
+int launch_op(irmv_engine *e, const Launch &l, int first, int count, const PostArgs &pa, unsigned scan, bool crop_pinned, hipStream_t s);
+int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipStream_t s, int reps, const std::vector<hipEvent_t> *ev, bool crop_pinned = false);
+void mark_stepped(irmv_engine *e, int first, int count);
+int copy_out(irmv_engine *e, int first, int count, hipStream_t st = nullptr);
+int check_range(const irmv_engine *e, int first, int count);
+int load_frame(irmv_engine *e, int slot, hipStream_t st);
+void det_pose(const irmv_engine *e, const DevDet &d, float ox, float oy, irmv_det &o);
+// engine_hooks.cpp
+int ensure_dense_head(irmv_engine *e, int slot);
+}

@@ -1,0 +1,157 @@
+// What a step launches: the Detect finals' fusion as the tuner left it, the sparse head's reordering, and the launch list of
+// each step kind.
+#include "engine_internal.hpp"
+
+// a class-branch conv that carries its final 1x1: with emit_scan, its epilogue appends the level's scan candidates
+static bool is_cls_final_carrier(const Op &op) { return op.fuse_next >= 0 && op.level >= 0 && op.layer.rfind("model.22.cv3.", 0) == 0; }
+
+// A 3x3 conv carries its branch's final 1x1 only if BOTH of its tile choices can (LDS family, nt = 4); then the 1x1
+// op drops out of the step and the tensor between the two is no longer written.
+void irmv::finalize_head_fusion(irmv_engine *e)
+{
+    for (Op &op : e->ops) {
+        if (op.fuse_next < 0) continue;
+        const bool k16 = op.cfg.cin16 && !op.cfg.lds && !op.cfg_one.lds && !op.cfg.deep && !op.cfg_one.deep && op.cfg.nt == 1 && op.cfg_one.nt == 1 && e->ops[op.fuse_next].w_k16;
+        const bool ok = k16 || (op.cfg.lds && op.cfg.nt == 4 && op.cfg_one.lds && op.cfg_one.nt == 4);
+        if (!ok) { op.fuse_next = -1; continue; }
+        e->ops[op.fuse_next].fused_away = true;
+        e->lazy_tensors.insert(e->tensors[op.out_t].name);
+        const size_t l = strlen(op.kname), l1 = strlen(op.kname_one);
+        snprintf(op.kname + l, sizeof op.kname - l, "+1x1");
+        snprintf(op.kname_one + l1, sizeof op.kname_one - l1, "+1x1");
+    }
+    // candidate emission from the conv epilogues: only if the class branch of EVERY level ends in a fused 1x1
+    int fused = 0;
+    for (const Op &op : e->ops) fused += is_cls_final_carrier(op);
+    e->emit_scan = e->sw.split_scan && fused == 3 && e->sw.emit_scan;
+    e->sparse_head = e->emit_scan && e->cand_bits && e->sw.sparse_head;
+    e->sparse_branch = e->sparse_head && e->sw.sparse_branch;
+}
+
+// ---- step plans ------------------------------------------------------------------
+// a box-branch conv that carries its final 1x1 (the 64 DFL channels of the head rows)
+static bool is_box_final_carrier(const Op &op) { return op.fuse_next >= 0 && op.level >= 0 && op.layer.rfind("model.22.cv2.", 0) == 0; }
+
+// Sparse head: the launches that write head rows store only those of candidate anchors, so within a step every class carrier
+// (it finds the candidates) has to run in front of them.  A step is a linear chain; the op list has the box branches first.
+// The box carriers move behind the last class carrier -- they read their own branch's first conv only and nothing in between
+// reads the head, so no bit changes -- and then they and the keypoint launches are marked.  Launches this does not reach
+// keep every row: a grouped launch (single-frame engines: box and class finals of all levels in ONE launch, no order to
+// be had) and the keypoint branch as layers.  The head bytes of a marked launch, and of every emitting class carrier, no longer
+// count as written: what is left is 96 floats per candidate anchor.
+//
+// Sparse branch (e->sparse_branch): the marked launches also carry the tile gate -- a (tile, image) pair without a candidate
+// anchor stores nothing, so the resident-weight kernels and the keypoint kernel do not compute it (halo 0).  The box branch's
+// first conv feeds nothing but its carrier's 3x3: where it runs a resident-weight kernel it moves behind the last class carrier
+// too (it reads the level input only) and is gated with a halo of one pixel; its tensor becomes a lazy one (Op::gated_first).
+// flops / bytes stay the dense figures: upper bounds for a gated launch.
+static void sparse_head_plan(irmv_engine *e, std::vector<Launch> &plan)
+{
+    int last_cls = -1;
+    bool lvl_cls[3] = {false, false, false};
+    for (size_t i = 0; i < plan.size(); i++)
+        if (plan[i].scan && plan[i].group < 0) { last_cls = (int)i; lvl_cls[e->ops[plan[i].op].level] = true; }
+    auto box_carrier = [&](const Launch &l) {
+        const Op &op = e->ops[l.op];
+        return l.group < 0 && l.fused && op.kind == OP_CONV && is_box_final_carrier(op) && op.level < 3 && lvl_cls[op.level];
+    };
+    std::vector<char> first_conv(plan.size(), 0);   // resident-weight launches whose output tensor is read by a box carrier of this plan and by no other op
+    if (e->sparse_branch)
+        for (size_t i = 0; i < plan.size(); i++) {
+            const Launch &f = plan[i];
+            const Op &fo = e->ops[f.op];
+            if (f.group >= 0 || f.fused || f.scan || fo.kind != OP_CONV || !(f.cfg_one ? fo.cfg_one : fo.cfg).wr || fo.res_t >= 0) continue;
+            int carrier = -1;
+            for (size_t j = i + 1; j < plan.size(); j++) {
+                const Op &co = e->ops[plan[j].op];
+                if (box_carrier(plan[j]) && co.level == fo.level && co.s0.t == fo.out_t && co.s1.C == 0 && co.s0.coff == fo.out_coff && co.Hin == fo.Hout && co.Win == fo.Wout) carrier = plan[j].op;
+            }
+            bool other = false;   // any other reader of the tensor (or a second writer) would see it stale outside active tiles
+            for (int k = 0; k < (int)e->ops.size(); k++) {
+                const Op &o = e->ops[k];
+                if (k == carrier || k == f.op) continue;
+                other = other || o.s0.t == fo.out_t || o.s1.t == fo.out_t || o.res_t == fo.out_t || o.out_t == fo.out_t;
+            }
+            first_conv[i] = carrier >= 0 && !other;
+        }
+    std::vector<Launch> out, moved;
+    for (size_t i = 0; i < plan.size(); i++) {
+        Launch &l = plan[i];
+        Op &op = e->ops[l.op];
+        if (l.scan) {   // class carrier(s): the 1x1's output stays on chip
+            if (l.group < 0) l.bytes -= e->ops[op.fuse_next].out_bytes;
+            else for (size_t m = 0; m < e->head_groups[l.group].members.size(); m++)
+                if (l.scan >> m & 1u) l.bytes -= e->ops[e->ops[e->head_groups[l.group].members[m]].fuse_next].out_bytes;
+        }
+        const bool cls_first = op.level >= 0 && op.level < 3 && lvl_cls[op.level];
+        const bool box = box_carrier(l);
+        const bool kpt = op.kind == OP_KPT3 && cls_first && (int)i > last_cls;
+        if (box || kpt) {
+            l.sparse = true;
+            l.bytes -= box ? e->ops[op.fuse_next].out_bytes : op.out_bytes;
+            if (e->sparse_branch) l.gate = 1;
+        }
+        if (first_conv[i]) {
+            l.gate = 2;
+            op.gated_first = true;
+            e->lazy_tensors.insert(e->tensors[op.out_t].name);
+        }
+        if ((box || first_conv[i]) && (int)i < last_cls) moved.push_back(l); else out.push_back(l);
+        if ((int)i == last_cls) { out.insert(out.end(), moved.begin(), moved.end()); moved.clear(); }
+    }
+    plan.swap(out);
+}
+
+// The one place that decides which ops of e->ops a step of each kind launches, and how.
+void irmv::build_step_plans(irmv_engine *e)
+{
+    for (int k = STEP_BATCH; k <= STEP_POST; k++) {
+        const bool one = k == STEP_ONE, mat = k == STEP_MATERIALIZE, post = k == STEP_POST, step = !mat && !post;
+        auto emits = [&](const Op &op) { return step && e->emit_scan && is_cls_final_carrier(op); };
+        for (int i = 0; i < (int)e->ops.size(); i++) {
+            const Op &op = e->ops[i];
+            if (post && op.kind != OP_NMS && op.kind != OP_LIGHT && op.kind != OP_SCAN) continue;
+            if (op.kind == OP_SCAN && e->emit_scan && !post) continue;   // the class-branch convs have already filled the key lists
+            const bool grouped = one && op.kind == OP_CONV && op.group >= 0;
+            if (grouped && e->head_groups[op.group].members[0] != i) continue;   // rides in its group's launch
+            // single-frame steps: the 64-channel Bottlenecks ride in their OP_BNECK launch; every other kind runs the layers
+            const bool bneck = one && e->sw.bneck64;
+            if (op.kind == OP_BNECK ? !bneck : (op.bneck >= 0 && bneck)) continue;
+            // every step runs a level's keypoint branch as its OP_KPT3 launch (where the engine has one)
+            if (op.kind == OP_KPT3 ? !step : (op.kpt3 >= 0 && step)) continue;
+            // a step skips the layers a fused kernel covers; a read-back runs only those (and the unfused form of a conv that
+            // normally carries a 1x1 in its epilogue)
+            // (... and a box branch's first conv that the steps -- their plans are built first -- run behind the tile gate)
+            if (mat ? !(op.fused_away || op.fuse_next >= 0 || op.gated_first || ((op.bneck >= 0 || op.kpt3 >= 0) && op.kind == OP_CONV)) : op.fused_away) continue;
+            Launch l; l.op = i;
+            // every kernel is idempotent and can be repeated inside its profile bracket -- except the light extraction and, with
+            // the split scan, the scan / NMS pair (the scan appends to the frame's candidate list, the NMS kernel consumes and resets it)
+            l.once = op.kind == OP_LIGHT || (e->sw.split_scan && (op.kind == OP_SCAN || op.kind == OP_NMS));
+            l.keys_only = op.kind == OP_NMS && ((e->emit_scan && !post) || (post && e->sw.post_keys_only));
+            l.layer = op.layer;
+            if (grouped) {   // one launch for the whole group
+                const irmv_engine::HeadGroup &g = e->head_groups[op.group];
+                l.group = op.group;
+                l.name = g.name;
+                l.layer += " ... (" + std::to_string(g.members.size()) + " convs)";
+                for (size_t m = 0; m < g.members.size(); m++) {
+                    const Op &mo = e->ops[g.members[m]];
+                    if (emits(mo)) l.scan |= 1u << m;
+                    l.flops += mo.flops + (mo.fuse_next >= 0 ? e->ops[mo.fuse_next].flops : 0.0);
+                    l.bytes += mo.bytes;
+                }
+            } else {
+                l.cfg_one = op.kind == OP_CONV && (one || mat) && stream_share(e, e->cfg.num_slots) > 1;   // (a read-back runs one slot)
+                l.fused = !mat && op.fuse_next >= 0;
+                l.scan = emits(op) ? 1u : 0u;
+                l.name = l.cfg_one ? op.kname_one : op.kname;
+                const Op *nx = l.fused ? &e->ops[op.fuse_next] : nullptr;   // the fused 1x1's output is what reaches memory, its weights ride along
+                l.flops = op.flops + (nx ? nx->flops : 0.0);
+                l.launch_bytes = op.w_bytes + (nx ? nx->w_bytes : 0.0);
+                l.bytes = op.bytes + (nx ? nx->out_bytes - op.out_bytes + nx->w_bytes : 0.0) - l.launch_bytes;
+            }
+            e->plans[k].push_back(l);
+        }
+        if (step && e->sparse_head) sparse_head_plan(e, e->plans[k]);
+    }
+}

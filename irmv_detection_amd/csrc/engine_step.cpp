@@ -1,0 +1,668 @@
+// Running a step: the kernel arguments of every op kind, the one launcher, frame and result copies, graph capture, and the
+// submit / wait / results ABI.
+#include "engine_internal.hpp"
+
+// ---- kernel arguments: one builder per op kind, on slots [first, first + count) -----------
+void irmv::fill_conv_args(const irmv_engine *e, const Op &op, int first, int count, ConvArgs &a, bool fused)
+{
+    a = ConvArgs{};
+    auto seg = [&](const SegRef &s) {
+        ConvSeg cs{nullptr, 0, 0, 0};
+        if (s.t < 0 || s.C == 0) return cs;
+        const Tensor &t = e->tensors[s.t];
+        cs.p = static_cast<const half_t *>(t.slot(first)) + s.coff;
+        cs.ld = t.C;
+        cs.C = s.C;
+        cs.shift = s.shift;
+        return cs;
+    };
+    a.s0 = seg(op.s0);
+    a.s1 = seg(op.s1);
+    a.Hin = op.Hin; a.Win = op.Win; a.Hout = op.Hout; a.Wout = op.Wout;
+    a.M = count * op.Hout * op.Wout;
+    a.Cin = op.cin;
+    a.w = op.w_packed;
+    a.bias = op.bias;
+    const Tensor &ot = e->tensors[op.out_t];
+    a.out = static_cast<char *>(ot.slot(first)) + (size_t)op.out_coff * ot.esize();
+    a.out_ld = ot.C;
+    a.res = nullptr;
+    a.res_ld = 0;
+    if (op.res_t >= 0) {
+        const Tensor &rt = e->tensors[op.res_t];
+        a.res = static_cast<const half_t *>(rt.slot(first)) + op.res_coff;
+        a.res_ld = rt.C;
+    }
+    a.cout_pad = op.cout_pad;
+    a.ksteps = op.ksteps;
+    a.pair = op.pair ? 1 : 0;
+    a.w2 = nullptr; a.bias2 = nullptr; a.out2 = nullptr; a.out2_ld = 0; a.n2 = 0;
+    if (fused && op.fuse_next >= 0) {
+        const Op &o2 = e->ops[op.fuse_next];
+        const Tensor &t2 = e->tensors[o2.out_t];
+        a.w2 = op.cfg.cin16 ? o2.w_k16 : o2.w_packed;
+        a.bias2 = o2.bias;
+        a.out2 = static_cast<float *>(t2.slot(first)) + o2.out_coff;
+        a.out2_ld = t2.C;
+        a.n2 = o2.cout_pad / 16;
+    }
+    if (op.w_k16) a.w2 = op.w_k16;   // a Cin = 16 final as its own launch (k_conv.hip conv1x1_k16_f32_kernel)
+}
+
+LightArgs irmv::light_args(const irmv_engine *e, int first)
+{
+    LightArgs a{};
+    const irmv_engine_cfg &c = e->cfg;
+    a.frames = e->src_dev + (size_t)first * e->frame_bytes;
+    a.frame_bytes = e->frame_bytes;
+    a.cols = c.src_width; a.rows = c.src_height; a.rotate180 = c.rotate180;
+    a.dets = e->dets_dev + (size_t)first * c.max_det;
+    a.max_det = c.max_det;
+    a.num_dets = reinterpret_cast<const int *>(e->fout_dev + first);
+    a.num_dets_stride = (int)(sizeof(DevFrameOut) / sizeof(int));
+    a.n_boxes = 0;
+    a.boxes = nullptr;
+    a.labels = e->light_labels + (size_t)first * e->light_pool;
+    a.label_pool = e->light_pool;
+    a.points = e->light_points + (size_t)first * c.max_det * kLightPointsCap * 2;
+    a.points_cap = kLightPointsCap;
+    a.hulls = e->light_hulls + (size_t)first * c.max_det * kLightPointsCap * 4;
+    a.binary_threshold = c.binary_threshold;
+    a.light_min_ratio = c.light_min_ratio; a.light_max_ratio = c.light_max_ratio; a.light_max_angle = c.light_max_angle;
+    a.min_small_cd = c.armor_min_small_center_distance; a.max_small_cd = c.armor_max_small_center_distance;
+    a.min_large_cd = c.armor_min_large_center_distance; a.max_large_cd = c.armor_max_large_center_distance;
+    a.pnp = e->pnp_dev;
+    a.first = first; a.pnp_stride = e->post.pnp_stride;
+    a.pnp_armor_size = c.armor_size;
+    return a;
+}
+
+static BayerArgs bayer_args(const irmv_engine *e, int first)   // a Bayer engine's demosaic of its raw slots from `first` on
+{
+    BayerArgs a = e->bayer;
+    a.raw = e->raw_dev + (size_t)first * e->src_bytes; a.dst = (e->window ? e->full_dev : e->src_dev) + (size_t)first * e->full_bytes;
+    return a;
+}
+
+static void launch_bayer(const irmv_engine *e, int first, int count, hipStream_t s)
+{
+    if (e->bayer_table) launch_demosaic_table(bayer_args(e, first), e->isp_table_dev, e->bayer_mhc, count, s);
+    else launch_demosaic(bayer_args(e, first), count, s);
+}
+
+PostArgs irmv::post_args(const irmv_engine *e, int first)
+{
+    PostArgs p = e->post;
+    p.head_all = e->head_all;
+    p.slots_total = e->cfg.num_slots;
+    p.first = first;
+    p.boxes = e->boxes + (size_t)first * e->A * 4;
+    p.keys = e->keys + (size_t)first * e->A * e->nc;
+    p.key_cap = e->A * e->nc;
+    p.dets = (e->zero_copy_results ? e->dets_host_dev : e->dets_dev) + (size_t)first * e->cfg.max_det;
+    p.fout = (e->zero_copy_results ? e->fout_host_dev : e->fout_dev) + first;
+    if (p.dbg) p.dbg += (size_t)first * 16;
+    p.counts = e->sw.split_scan ? e->cand_counts + first : nullptr;
+    p.cand_bits = e->sparse_head ? e->cand_bits + (size_t)first * e->cand_words : nullptr;
+    p.cand_words = e->cand_words;
+    return p;
+}
+
+// The crop of slots [first, first + count): out of their device frames, or (pinned) out of the pinned slots themselves.
+static CropArgs crop_args(const irmv_engine *e, int first, bool pinned)
+{
+    CropArgs a{};
+    a.src = pinned ? e->src_host_dev : e->full_dev; a.src_slot_bytes = e->full_bytes;
+    a.dst = e->src_dev; a.dst_slot_bytes = e->frame_bytes;
+    a.win = e->win_dev; a.first = first;
+    a.full_w = e->full_w; a.full_h = e->full_h; a.win_w = e->cfg.src_width; a.win_h = e->cfg.src_height;
+    return a;
+}
+
+static void launch_crop(const irmv_engine *e, int first, int count, bool pinned, hipStream_t s) { launch_window_crop(crop_args(e, first, pinned), count, s); }
+
+static PreArgs pre_args(const irmv_engine *e, const Op &op, int first)
+{
+    PreArgs a;
+    a.src = e->src_dev + (size_t)first * e->frame_bytes;
+    a.dst = static_cast<half_t *>(e->tensors[op.out_t].slot(first));
+    a.tx = e->tap_x; a.ty = e->tap_y;
+    a.sw = e->cfg.src_width; a.sh = e->cfg.src_height; a.net_w = e->cfg.net_size; a.net_h = e->cfg.net_height; a.swap_rb = e->cfg.swap_rb;
+    a.src_slot_bytes = e->frame_bytes;
+    return a;
+}
+
+static FrontArgs front_args(const irmv_engine *e, const Op &op, int first)
+{
+    FrontArgs a;
+    a.src = e->src_dev + (size_t)first * e->frame_bytes;
+    a.src_slot_bytes = e->frame_bytes;
+    a.tx = e->tap_x; a.ty = e->tap_y;
+    a.vx0 = e->front.box[0]; a.vx1 = e->front.box[1]; a.vy0 = e->front.box[2]; a.vy1 = e->front.box[3];
+    a.sw = e->cfg.src_width; a.sh = e->cfg.src_height; a.net_w = e->cfg.net_size; a.net_h = e->cfg.net_height; a.swap_rb = e->cfg.swap_rb;
+    a.fastx = e->front.fastx; a.fx_i0 = e->front.fx_i0; a.fx_step = e->front.fx_step;
+    a.w0 = e->conv0_w; a.b0 = e->conv0_b;
+    a.w1 = op.w_packed; a.b1 = op.bias;
+    const Tensor &ot = e->tensors[op.out_t];
+    a.out = static_cast<half_t *>(ot.slot(first));
+    a.out_ld = ot.C;
+    a.tiles_x = e->front.tiles_x; a.tiles_y = e->front.tiles_y; a.tile_y = e->front.tile_y; a.stage_bytes = e->front.stage_bytes;
+    return a;
+}
+
+static C2fArgs c2f2_args(const irmv_engine *e, const Op &op, int first)
+{
+    C2fArgs a;
+    const Tensor &xt = e->tensors[op.s0.t], &ot = e->tensors[op.out_t];
+    a.x = static_cast<const half_t *>(xt.slot(first)); a.x_ld = xt.C;
+    a.out = static_cast<half_t *>(ot.slot(first)); a.out_ld = ot.C;
+    a.H = xt.H; a.W = xt.W;
+    a.tiles_x = (xt.W + kC2fTile - 1) / kC2fTile; a.tiles_y = (xt.H + kC2fTile - 1) / kC2fTile;
+    const Op &c1 = e->ops[op.sub[0]], &m1 = e->ops[op.sub[1]], &m2 = e->ops[op.sub[2]], &c2 = e->ops[op.sub[3]];
+    a.w_cv1 = c1.w_packed; a.w_m1 = m1.w_packed; a.w_m2 = m2.w_packed; a.w_cv2 = c2.w_packed;
+    a.b_cv1 = c1.bias; a.b_m1 = m1.bias; a.b_m2 = m2.bias; a.b_cv2 = c2.bias;
+    return a;
+}
+
+// one fused C2f block (OP_C2F32).  (A 16 x 16 tile on an 8-wave workgroup -- a third less halo work, one workgroup per CU --
+// was built and measured in round 3: 5 - 30 % slower than the 8 x 16 tile in an eager replay, a tie in the benchmarked one;
+// dropped.)
+static C2f32Args c2f32_args(const irmv_engine *e, const Op &op, int first, int count)
+{
+    C2f32Args a{};
+    const Tensor &ct = e->tensors[op.res_t];
+    const Tensor &ot = e->tensors[op.out_t];
+    if (op.sub[0] >= 0) {
+        ConvArgs ca;
+        fill_conv_args(e, e->ops[op.sub[0]], first, count, ca, false);
+        a.s0 = ca.s0; a.s1 = ca.s1; a.cin1 = ca.Cin;
+        a.w_cv1 = e->ops[op.sub[0]].w_packed; a.b_cv1 = e->ops[op.sub[0]].bias;
+    } else {
+        a.cin1 = 32;
+    }
+    a.cat = static_cast<half_t *>(ct.slot(first)); a.cat_ld = ct.C; a.prev_coff = 64;
+    a.out = static_cast<half_t *>(ot.slot(first)); a.out_ld = ot.C;
+    a.H = op.Hin; a.W = op.Win;
+    a.tiles_x = (op.Win + kC2f32TileW - 1) / kC2f32TileW; a.tiles_y = (op.Hin + kC2f32TileH - 1) / kC2f32TileH;
+    a.w_m1 = e->ops[op.sub[1]].w_packed; a.b_m1 = e->ops[op.sub[1]].bias;
+    a.w_m2 = e->ops[op.sub[2]].w_packed; a.b_m2 = e->ops[op.sub[2]].bias;
+    if (op.sub[3] >= 0) { a.w_cv2 = e->ops[op.sub[3]].w_packed; a.b_cv2 = e->ops[op.sub[3]].bias; }
+    return a;
+}
+
+static BneckArgs bneck_args(const irmv_engine *e, const Op &op, int first)
+{
+    const Op &m1 = e->ops[op.sub[0]], &m2 = e->ops[op.sub[1]];
+    const Tensor &ct = e->tensors[op.res_t];
+    BneckArgs a{};
+    a.yin = static_cast<const half_t *>(ct.slot(first)) + m1.s0.coff; a.yin_ld = ct.C;
+    a.ynext = static_cast<half_t *>(ct.slot(first)) + m2.out_coff; a.ynext_ld = ct.C;
+    a.cat = static_cast<const half_t *>(ct.slot(first)); a.cat_ld = ct.C;
+    a.H = op.Hin; a.W = op.Win;
+    a.tiles_x = (op.Win + kBneckTile - 1) / kBneckTile; a.tiles_y = (op.Hin + kBneckTile - 1) / kBneckTile;
+    a.w_m1 = m1.w_lds[0]; a.b_m1 = m1.bias; a.w_m2 = m2.w_lds[0]; a.b_m2 = m2.bias;
+    if (op.sub[2] >= 0) {
+        const Op &c2 = e->ops[op.sub[2]];
+        const Tensor &ot = e->tensors[c2.out_t];
+        a.out = static_cast<half_t *>(ot.slot(first)) + c2.out_coff; a.out_ld = ot.C;
+        a.w_cv2 = c2.w_packed; a.b_cv2 = c2.bias;
+    }
+    return a;
+}
+
+static Kpt3Args kpt3_args(const irmv_engine *e, const Op &op, const Launch &l, int first, const PostArgs &pa)
+{
+    const Op &o0 = e->ops[op.sub[0]], &o1 = e->ops[op.sub[1]], &o2 = e->ops[op.sub[2]];
+    const Tensor &xt = e->tensors[o0.s0.t], &ht = e->tensors[o2.out_t];
+    Kpt3Args a{};
+    a.x = static_cast<const half_t *>(xt.slot(first)) + o0.s0.coff; a.x_ld = xt.C;
+    a.H = op.Hin; a.W = op.Win;
+    a.tiles_x = (op.Win + kKpt3Tile - 1) / kKpt3Tile; a.tiles_y = (op.Hin + kKpt3Tile - 1) / kKpt3Tile;
+    a.w1 = o0.w_lds[0]; a.b1 = o0.bias;
+    a.w2 = o1.w_packed; a.b2 = o1.bias;
+    a.w3 = o2.w_k16; a.b3 = o2.bias;
+    a.out = static_cast<float *>(ht.slot(first)) + o2.out_coff; a.out_ld = ht.C;
+    if (l.sparse) { a.cand_bits = pa.cand_bits; a.cand_words = pa.cand_words; a.abase = e->lvl_base[op.level]; a.tile_gate = l.gate; }
+    return a;
+}
+
+static DwArgs dw_args(const irmv_engine *e, const Op &op, int first)
+{
+    DwArgs a;
+    const Tensor &xt = e->tensors[op.s0.t], &ot = e->tensors[op.out_t];
+    a.x = static_cast<const half_t *>(xt.slot(first)) + op.s0.coff; a.x_ld = xt.C;
+    a.y = static_cast<half_t *>(ot.slot(first)) + op.out_coff; a.y_ld = ot.C;
+    a.w = op.w_packed; a.b = op.bias;
+    a.Hin = op.Hin; a.Win = op.Win; a.Hout = op.Hout; a.Wout = op.Wout; a.C = op.cout; a.stride = op.cfg.stride;
+    return a;
+}
+
+static ShufArgs shuf_args(const irmv_engine *e, const Op &op, int first, int count)
+{
+    ShufArgs a;
+    const Tensor &at = e->tensors[op.s0.t], &bt = e->tensors[op.s1.t], &ot = e->tensors[op.out_t];
+    a.a = static_cast<const half_t *>(at.slot(first)) + op.s0.coff; a.a_ld = at.C;
+    a.b = static_cast<const half_t *>(bt.slot(first)) + op.s1.coff; a.b_ld = bt.C;
+    a.out = static_cast<half_t *>(ot.slot(first)); a.out_ld = ot.C;
+    a.bc = op.s0.C;
+    a.pixels = (size_t)count * op.Hin * op.Win;
+    return a;
+}
+
+static Conv0Args conv0_args(const irmv_engine *e, const Op &op, int first, int count)
+{
+    Conv0Args a;
+    a.x = static_cast<const half_t *>(e->tensors[op.s0.t].slot(first));
+    a.y = static_cast<half_t *>(e->tensors[op.out_t].slot(first));
+    a.w = e->conv0_w; a.b = e->conv0_b; a.net_w = e->cfg.net_size; a.net_h = e->cfg.net_height; a.batch = count;
+    return a;
+}
+
+// ---- grouped Detect-branch launches (single-frame engines) ---------------------------
+
+static void scan_args_for(const irmv_engine *e, const Op &op, const PostArgs &pa, ConvArgs &a)
+{
+    a.scan_keys = pa.keys; a.scan_counts = pa.counts; a.scan_thr = pa.logit_thr; a.scan_nc = pa.nc;
+    a.scan_key_cap = pa.key_cap;
+    a.scan_abase = e->lvl_base[op.level];
+    a.cand_bits = pa.cand_bits; a.cand_words = pa.cand_words;   // (sparse head: the class channels stay on chip)
+}
+
+// one launch for all members of group g on slot `first`; member k appends candidates to pa's key lists if bit k of `scan` is set
+bool irmv::launch_head_group(const irmv_engine *e, const irmv_engine::HeadGroup &g, int first, const PostArgs *pa, unsigned scan, hipStream_t s)
+{
+    ConvArgs a[kMultiMax];
+    ConvWeights w[kMultiMax];
+    const int n = (int)g.members.size();
+    for (int k = 0; k < n; k++) {
+        const Op &op = e->ops[g.members[k]];
+        fill_conv_args(e, op, first, 1, a[k], true);
+        if (scan >> k & 1u) scan_args_for(e, op, *pa, a[k]);
+        w[k] = conv_weights(op);
+    }
+    return g.family == 0 ? launch_conv_lds_multi(g.nt, a, w, n, 1, s) : launch_conv_direct_multi(g.cfg, a, n, s);
+}
+
+// ---- step execution ------------------------------------------------------------
+// The one place an op reaches the GPU: the kernel of l.op's kind on slots [first, first + count), stream s, as launch l of a
+// plan says (irmv_engine_run_op: a plain Launch of the op).  scan: the members of l that append scan candidates to pa's key
+// lists (bit k: member k of a group, bit 0: a lone conv); crop_pinned: OP_CROP reads the pinned slots.
+int irmv::launch_op(irmv_engine *e, const Launch &l, int first, int count, const PostArgs &pa, unsigned scan, bool crop_pinned, hipStream_t s)
+{
+    const Op &op = e->ops[l.op];
+    switch (op.kind) {
+    case OP_DEMOSAIC: launch_bayer(e, first, count, s); break;
+    case OP_CROP: launch_crop(e, first, count, crop_pinned, s); break;
+    case OP_PRE: launch_preprocess(pre_args(e, op, first), count, s); break;
+    case OP_FRONT: if (!launch_front(front_args(e, op, first), count, s)) return fail(IRMV_ERR_HIP, "fused front kernel: LDS request refused"); break;
+    case OP_C2F2: launch_c2f2(c2f2_args(e, op, first), count, s); break;
+    case OP_C2F32: if (!launch_c2f32(op.mode, op.shortcut, c2f32_args(e, op, first, count), count, s)) return fail(IRMV_ERR_ARG, "no fused C2f kernel for " + op.layer); break;
+    case OP_BNECK:   // (cv2's k-steps where the launch carries it)
+        if (!launch_bneck64(op.mode, op.sub[2] >= 0 ? e->ops[op.sub[2]].ksteps : 6, op.shortcut, bneck_args(e, op, first), count, s)) return fail(IRMV_ERR_ARG, "no fused bottleneck kernel for " + op.layer);
+        break;
+    case OP_KPT3: if (!launch_kpt3(kpt3_args(e, op, l, first, pa), op.cin, count, s)) return fail(IRMV_ERR_ARG, "no fused keypoint-branch kernel for " + op.layer); break;
+    case OP_DW: launch_dwconv3x3(dw_args(e, op, first), count, s); break;
+    case OP_SHUF: launch_shuffle_cat(shuf_args(e, op, first, count), s); break;
+    case OP_CONV0: launch_conv0(conv0_args(e, op, first, count), s); break;
+    case OP_POOL: { const Tensor &t = e->tensors[op.out_t]; launch_sppf_pool(static_cast<half_t *>(t.slot(first)), count, t.H, t.W, t.C / 4, s); break; }
+    case OP_CONV: {
+        if (l.group >= 0) {
+            if (!launch_head_group(e, e->head_groups[l.group], first, &pa, scan, s)) return fail(IRMV_ERR_ARG, "grouped launch refused: " + l.name);
+            break;
+        }
+        ConvArgs a;
+        fill_conv_args(e, op, first, count, a, l.fused);
+        if (scan) scan_args_for(e, op, pa, a);
+        if (l.sparse || l.gate) { a.cand_bits = pa.cand_bits; a.cand_words = pa.cand_words; a.scan_abase = e->lvl_base[op.level]; a.tile_gate = l.gate; }
+        if (!run_conv(op, l.cfg_one ? op.cfg_one : op.cfg, a, count, s)) return fail(IRMV_ERR_ARG, std::string("no conv kernel for ") + op.kname + " (" + op.layer + ")");
+        break;
+    }
+    case OP_SCAN: launch_scan_decode(pa, count, s); break;
+    case OP_NMS: { PostArgs pn = pa; pn.keys_only = l.keys_only ? 1 : 0; launch_nms_pnp(pn, count, s); break; }
+    case OP_LIGHT: launch_light_extract(light_args(e, first), e->cfg.max_det, count, s); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return IRMV_OK;
+}
+
+// Enqueue a step of kind `kind` on slots [first, first + count), stream s: the launches of e->plans[kind], in order.
+// ev != nullptr (irmv_engine_profile's events): launch i of the plan is repeated `reps` times (once if it is `once`) between
+// (*ev)[2 i] and (*ev)[2 i + 1].
+int irmv::enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipStream_t s, int reps, const std::vector<hipEvent_t> *ev, bool crop_pinned)
+{
+    const std::vector<Launch> &plan = e->plans[kind];
+    const PostArgs pa = post_args(e, first);
+    PostArgs mute = pa;   // (a threshold no logit passes: no key, no bit)
+    mute.logit_thr = INFINITY;
+    for (size_t i = 0; i < plan.size(); i++) {
+        const Launch &l = plan[i];
+        if (ev) HIP_TRY(hipEventRecord((*ev)[2 * i], s));
+        const int n = l.once ? 1 : reps;
+        for (int rep = 0; rep < n; rep++) {
+            // a profiled launch is repeated: only its last repetition appends candidates.  With the sparse head the other
+            // repetitions still run the step's kernel -- no class store --, behind the mute threshold.
+            const bool last = rep == n - 1, muted = !last && l.scan && e->sparse_head;
+            TRY(launch_op(e, l, first, count, muted ? mute : pa, last || muted ? l.scan : 0u, crop_pinned, s));
+        }
+        if (ev) HIP_TRY(hipEventRecord((*ev)[2 * i + 1], s));
+    }
+    return IRMV_OK;
+}
+
+// Slots [first, first + count) have just been stepped: their heads hold the rows, and their gated tensors the tiles, of that
+// step's candidates only (sparse head / branch), and their results are shifted by the windows' corners as they are now.
+void irmv::mark_stepped(irmv_engine *e, int first, int count)
+{
+    if (e->sparse_head) std::fill(e->head_stale.begin() + first, e->head_stale.begin() + first + count, 1);
+    if (e->sparse_branch) std::fill(e->branch_stale.begin() + first, e->branch_stale.begin() + first + count, 1);
+    if (e->window) std::copy(e->win_org.begin() + first, e->win_org.begin() + first + count, e->sub_org.begin() + first);
+}
+
+// Frame upload and result download: plain async copies, pinned memory both ways, on the streams submit_group() picks.
+// bands (never inside a stream capture, whose copy parameters are baked): an HWC window engine moves, for groups of up to 8
+// slots, only the band of full-width rows each slot's window covers -- one 1-D copy per slot, to the same offset of its device frame.
+constexpr int kBandUploadMaxSlots = 8;
+static int copy_in(irmv_engine *e, int first, int count, hipStream_t st, bool bands = false)
+{
+    if (bands && e->window && !e->raw_dev && count <= kBandUploadMaxSlots) {
+        const size_t pitch = (size_t)e->full_w * 3, len = (size_t)e->cfg.src_height * pitch;
+        for (int s = first; s < first + count; s++) {
+            const int by0 = e->cfg.rotate180 ? e->full_h - e->win_org[s].y - e->cfg.src_height : e->win_org[s].y;
+            const size_t off = (size_t)s * e->src_bytes + (size_t)by0 * pitch;
+            HIP_TRY(hipMemcpyAsync(e->full_dev + off, e->src_host + off, len, hipMemcpyHostToDevice, st));
+        }
+        return IRMV_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(upload_dev(e) + (size_t)first * e->src_bytes, e->src_host + (size_t)first * e->src_bytes,
+                           e->src_bytes * count, hipMemcpyHostToDevice, st));
+    return IRMV_OK;
+}
+
+// One or two frames travel from the pinned slots as a KERNEL (k_pre.hip upload_frame_kernel), larger groups on the copy engine.
+static bool upload_as_kernel(const irmv_engine *e, int first, int count)
+{
+    return count <= 2 && e->sw.upload_kernel_blocks > 0 && e->src_host_dev && upload_aligned(e->src_bytes, first, count);
+}
+
+// The synchronous upload of slots [first, first + count) on stream st.  (A Bayer engine's single-frame upload stays a kernel
+// of its own in front of the demosaic: the demosaic reading the pinned slot itself was built and measured slower, DESIGN.md
+// section 9.)
+// An HWC window engine's synchronous step of one or two slots uploads nothing: its crop reads the window out of the pinned
+// slots (crop_from_pinned), so only the window crosses PCIe.  `captured`: the copy becomes a graph node (whole frames).
+static bool crop_from_pinned(const irmv_engine *e, int count)
+{
+    return e->window && !e->raw_dev && e->sw.window_upload && count <= 2 && e->sw.upload_kernel_blocks > 0 && e->src_host_dev;
+}
+
+static int upload_sync(irmv_engine *e, int first, int count, hipStream_t st, bool captured)
+{
+    if (crop_from_pinned(e, count)) return IRMV_OK;
+    if (!upload_as_kernel(e, first, count)) return copy_in(e, first, count, st, !captured);
+    const size_t off = (size_t)first * e->src_bytes;
+    launch_upload_frames(e->src_host_dev + off, upload_dev(e) + off, e->src_bytes * count, e->sw.upload_kernel_blocks, st);
+    return IRMV_OK;
+}
+
+int irmv::copy_out(irmv_engine *e, int first, int count, hipStream_t st)
+{
+    if (!st) st = e->stream;
+    if (e->zero_copy_results) return IRMV_OK;   // the kernel has already written the pinned records
+    HIP_TRY(hipMemcpyAsync(e->dets_host + (size_t)first * e->cfg.max_det, e->dets_dev + (size_t)first * e->cfg.max_det,
+                           (size_t)count * e->cfg.max_det * sizeof(DevDet), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(e->fout_host + first, e->fout_dev + first, (size_t)count * sizeof(DevFrameOut),
+                           hipMemcpyDeviceToHost, st));
+    return IRMV_OK;
+}
+
+int irmv::check_range(const irmv_engine *e, int first, int count)
+{
+    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
+    if (first < 0 || count < 1 || first + count > e->cfg.num_slots) return fail(IRMV_ERR_ARG, "slot range out of bounds");
+    return IRMV_OK;
+}
+
+static int get_graph(irmv_engine *e, StepKind kind, int first, int count, bool upload, hipGraphExec_t *out)
+{
+    const GraphKey key{first, count, kind, upload};
+    auto it = e->graphs.find(key);
+    if (it != e->graphs.end()) { *out = it->second; return IRMV_OK; }
+    hipGraph_t g = nullptr;
+    HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
+    int rc = IRMV_OK;
+    if (upload)   // the frames' upload as the graph's first node (synchronous single-stream submits): one or two frames as a kernel
+        rc = upload_sync(e, first, count, e->stream, true);
+    if (!rc) rc = enqueue_step(e, kind, first, count, e->stream, 1, nullptr, upload && crop_from_pinned(e, count));
+    hipError_t ce = hipStreamEndCapture(e->stream, &g);
+    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+    if (ce != hipSuccess) return fail(IRMV_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
+    hipGraphExec_t ge = nullptr;
+    HIP_TRY(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+    (void)hipGraphDestroy(g);
+    e->graphs[key] = ge;
+    *out = ge;
+    return IRMV_OK;
+}
+
+static int group_of(irmv_engine *e, int first, int count, SlotGroup **out)
+{
+    const auto key = std::make_pair(first, count);
+    auto it = e->groups.find(key);
+    if (it == e->groups.end()) {
+        SlotGroup g;
+        g.first = first; g.count = count;
+        HIP_TRY(hipEventCreateWithFlags(&g.h2d, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&g.out, hipEventDisableTiming));
+        it = e->groups.emplace(key, g).first;
+    }
+    *out = &it->second;   // std::map nodes never move
+    return IRMV_OK;
+}
+
+// One slot group: [upload] -> ONE hipGraph -> download of the results, in order on compute stream `st`.
+//
+// IRMV_SUBMIT_ASYNC_UPLOAD moves the upload to the engine's upload stream (the dGPU form of the
+// reference's TripleBuffer, include/irmv_detection/triple_buffer.hpp:24-40, whose slots ARE the engines' input memory):
+//
+//   upload stream    [wait: this group's previous step is done with its device frames]  H2D frames  -> ev h2d
+//   compute stream   [wait: ev h2d]  hipGraph, D2H results                                           -> ev out
+//
+// so group B's frames cross PCIe while group A's kernels run.  The price is one cross-stream event hop per group
+// (measured on this stack: scripts/probes/stream_probe.cpp), which is why a lone synchronous detect() -- nothing to
+// overlap with -- keeps everything on one stream, and why the (tiny) download never leaves the compute stream.
+static int submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_t st)
+{
+    const bool async_up = (flags & IRMV_SUBMIT_H2D) && (flags & IRMV_SUBMIT_ASYNC_UPLOAD) && !e->sw.inline_copies;
+    // An upload that rides the compute stream anyway (the synchronous detect()) is captured INTO the step's graph: one
+    // submission instead of two, and the copy -> first kernel hand-over is the graph's own (IRMV_GRAPH_UPLOAD=0: a separate
+    // hipMemcpyAsync in front of the graph, as before; same bits)
+    // A synchronous single-frame step (the reference's detect(), src/yolo_engine.cpp:153-177) has two launch forms with the same
+    // kernels and the same bits: ONE hipGraph replay, or its 41 launches issued one by one behind the upload (round 5: a graph
+    // replay spends ~10 us of host work before its first packet reaches the GPU, a direct launch ~4; with the 70 us upload in
+    // front the host stays far ahead of the GPU: 0.339 -> 0.331 ms per 1280 x 1024 frame).  Every other step is a graph replay.
+    const bool eager = e->sync_launch == 1 && c == 1 && (flags & IRMV_SUBMIT_H2D) && !async_up;
+    const bool pinned = (flags & IRMV_SUBMIT_H2D) && !async_up && crop_from_pinned(e, c);   // (no upload at all: nothing to keep out of the graph)
+    const bool graph_up = (flags & IRMV_SUBMIT_H2D) && !async_up && (e->sw.graph_upload || pinned) && !eager;
+    const StepKind kind = c == 1 ? STEP_ONE : STEP_BATCH;
+    hipGraphExec_t ge = nullptr;
+    if (!eager) TRY(get_graph(e, kind, f, c, graph_up, &ge));
+    SlotGroup *g;
+    TRY(group_of(e, f, c, &g));
+    hipStream_t up = async_up ? e->h2d_stream : st;
+    // slots last used through a different grouping: order behind that group's completion
+    SlotGroup *seen[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int s = f; s < f + c; s++) {
+        SlotGroup *o = e->slot_owner[s];
+        e->slot_owner[s] = g;
+        if (!o || o == g || !o->in_flight || o == seen[0] || o == seen[1] || o == seen[2] || o == seen[3]) continue;
+        seen[3] = seen[2]; seen[2] = seen[1]; seen[1] = seen[0]; seen[0] = o;
+        if (o->compute != st) HIP_TRY(hipStreamWaitEvent(st, o->out, 0));
+        if (up != st) HIP_TRY(hipStreamWaitEvent(up, o->out, 0));
+    }
+    if (g->in_flight && g->compute != st) HIP_TRY(hipStreamWaitEvent(st, g->out, 0));   // the group moved to another compute stream
+    if (flags & IRMV_SUBMIT_H2D) {
+        if (async_up) {
+            if (g->in_flight) HIP_TRY(hipStreamWaitEvent(up, g->out, 0));   // previous step has consumed the device frames
+            TRY(copy_in(e, f, c, up, true));
+            HIP_TRY(hipEventRecord(g->h2d, up));
+            HIP_TRY(hipStreamWaitEvent(st, g->h2d, 0));
+        } else if (!graph_up) {
+            // (an eager step, or IRMV_GRAPH_UPLOAD=0)
+            TRY(upload_sync(e, f, c, st, false));
+        }
+    }
+    if (eager) TRY(enqueue_step(e, kind, f, c, st, 1, nullptr, pinned));
+    else HIP_TRY(hipGraphLaunch(ge, st));
+    mark_stepped(e, f, c);
+    TRY(copy_out(e, f, c, st));
+    HIP_TRY(hipEventRecord(g->out, st));
+    g->in_flight = true;
+    g->async_up = async_up;
+    g->compute = st;
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_submit(irmv_engine *e, int first, int count, uint32_t flags)
+{
+    TRY(check_range(e, first, count));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    // A multi-slot step is cut into num_streams independent sub-batches, one captured graph each, on
+    // separate streams: while one sub-batch sits in a launch gap or a kernel tail the other keeps the
+    // CUs busy (two sub-batches measured +30 % frames/s over one stream at 32 frames).
+    int share = count > 1 ? stream_share(e, count) : count;
+    // Single-slot steps ride the compute stream of their slot (slot mod num_streams): a single frame fills a fraction of
+    // the chip, so the steps of two slots in flight (the TripleBuffer's depth) overlap instead of queueing behind each other.
+    int si = count == 1 ? first % e->num_streams : 0;
+    // A submit of exactly ONE stream's share of the engine's slots, aligned to it, is that share's sub-batch of a whole-engine
+    // step: the same captured graph on the same stream.  A caller that feeds the shares separately decides itself how far
+    // apart the streams run (two shares started together execute the same kernel at the same time all the way down).
+    const int full_share = stream_share(e, e->cfg.num_slots);
+    if (count > 1 && count == full_share && first % full_share == 0 && first / full_share < e->num_streams) { share = count; si = first / full_share; }
+    for (int f = first; f < first + count; f += share, si++) {
+        const int c = std::min(share, first + count - f);
+        hipStream_t st = si == 0 ? e->stream : e->extra_streams[si - 1];
+        TRY(submit_group(e, f, c, flags, st));
+    }
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_run_post(irmv_engine *e, int first, int count)
+{
+    TRY(check_range(e, first, count));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));
+    for (int s = first; s < first + count; s++) TRY(ensure_dense_head(e, s));   // (scan_decode_kernel reads every anchor's class logits)
+    hipGraphExec_t ge;
+    TRY(get_graph(e, STEP_POST, first, count, false, &ge));
+    HIP_TRY(hipGraphLaunch(ge, e->stream));
+    TRY(copy_out(e, first, count));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_wait(irmv_engine *e)
+{
+    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(hipStreamSynchronize(e->h2d_stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (int i = 1; i < e->num_streams; i++) HIP_TRY(hipStreamSynchronize(e->extra_streams[i - 1]));
+    for (auto &kv : e->groups) kv.second.in_flight = false;
+    return IRMV_OK;
+}
+
+// Block until the last submit of slots [first, first + count) has got as far as `upload` says: their pinned slots have been read
+// by its upload, or its results are host-visible.
+static int wait_owners(irmv_engine *e, int first, int count, bool upload)
+{
+    TRY(check_range(e, first, count));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    SlotGroup *last = nullptr;
+    for (int s = first; s < first + count; s++) {
+        SlotGroup *o = e->slot_owner[s];
+        if (!o || o == last || !o->in_flight) continue;
+        // an upload on the side stream has its own event; an inline upload is ordered in front of the kernels, so the
+        // group's completion event covers it
+        HIP_TRY(hipEventSynchronize(upload && o->async_up ? o->h2d : o->out));
+        // the whole group is done only if this call covers it; otherwise it merely stays marked in flight (harmless)
+        if (!upload && o->first >= first && o->first + o->count <= first + count) o->in_flight = false;
+        last = o;
+    }
+    return IRMV_OK;
+}
+
+// From then on a producer may overwrite the pinned slots (the moment the TripleBuffer's consumer can give the buffer back),
+// while the kernels still run.
+extern "C" int irmv_engine_wait_upload(irmv_engine *e, int first, int count) { return wait_owners(e, first, count, true); }
+
+// Other slots may stay in flight (the consumer side of the TripleBuffer: take the newest finished slot while the next one runs).
+extern "C" int irmv_engine_wait_slots(irmv_engine *e, int first, int count) { return wait_owners(e, first, count, false); }
+
+// The pose part of a result record: keypoints (a window engine's shifted by the corner ox, oy), PnP, and the classical
+// extraction's fields.
+void irmv::det_pose(const irmv_engine *e, const DevDet &d, float ox, float oy, irmv_det &o)
+{
+    o.pnp_ok = d.pnp_ok;
+    memcpy(o.kpts, d.kpts, 32);
+    if (e->window)
+        for (int j = 0; j < 8; j++) o.kpts[j] += (j & 1) ? oy : ox;
+    memcpy(o.rvec, d.rvec, 24);
+    memcpy(o.tvec, d.tvec, 24);
+    memcpy(o.quat, d.quat, 32);
+    o.armor_valid = d.armor_valid;
+    o.armor_size = d.armor_size;
+    o.n_lights = d.n_lights;
+}
+
+extern "C" int irmv_engine_results(irmv_engine *e, int slot, irmv_det *out, int cap, int *n)
+{
+    TRY(check_range(e, slot, 1));
+    if (!n || (cap > 0 && !out)) return fail(IRMV_ERR_ARG, "out/n is null");
+    const DevFrameOut &fo = e->fout_host[slot];
+    const int k = std::min(fo.num_dets, cap);
+    const DevDet *d = e->dets_host + (size_t)slot * e->cfg.max_det;
+    // device records are window-local: the corner the slot was submitted with brings them to full-frame coordinates
+    const float ox = e->window ? (float)e->sub_org[slot].x : 0.f, oy = e->window ? (float)e->sub_org[slot].y : 0.f;
+    for (int i = 0; i < k; i++) {
+        irmv_det &o = out[i];
+        memcpy(o.xyxy, d[i].xyxy, 16);
+        o.score = d[i].score;
+        // magic_enum::enum_cast<ArmorClass>(label).value_or(UNKNOWN), src/yolo_engine.cpp:216
+        o.class_id = (d[i].cls >= 0 && d[i].cls < IRMV_NUM_CLASSES) ? d[i].cls : IRMV_NUM_CLASSES;
+        o.anchor = d[i].anchor;
+        det_pose(e, d[i], ox, oy, o);
+        o.reserved = 0;
+        if (e->window)
+            for (int j = 0; j < 4; j++) o.xyxy[j] += (j & 1) ? oy : ox;
+    }
+    *n = k;
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_detect(irmv_engine *e, int slot, irmv_det *out, int cap, int *n)
+{
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    // a synchronous single-slot call has nothing to overlap with: upload, graph and download ride ONE stream
+    TRY(irmv_engine_submit(e, slot, 1, IRMV_SUBMIT_H2D));
+    TRY(irmv_engine_wait_slots(e, slot, 1));
+    const int rc = irmv_engine_results(e, slot, out, cap, n);
+    e->last_detect_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+    return rc;
+}
+
+extern "C" double irmv_engine_last_detect_ms(const irmv_engine *e) { return e ? e->last_detect_ms : 0.0; }
+
+// The slot's pinned frame -> its HWC device frame (src_dev) on stream st, outside a step: an HWC engine copies it there, a
+// Bayer engine copies the raw frame to its device raw slot and demosaics it; a window engine then cuts the slot's window out.
+int irmv::load_frame(irmv_engine *e, int slot, hipStream_t st)
+{
+    TRY(copy_in(e, slot, 1, st, true));
+    if (e->raw_dev) {
+        launch_bayer(e, slot, 1, st);
+        HIP_TRY(hipGetLastError());
+    }
+    if (e->window) {
+        launch_crop(e, slot, 1, false, st);
+        HIP_TRY(hipGetLastError());
+    }
+    return IRMV_OK;
+}

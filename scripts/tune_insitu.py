@@ -26,7 +26,7 @@ def run(table):
     raise RuntimeError(p.stderr[-300:])
 
 
-# flags: 1 lds, 64 cm2, 128 cm4, 256 w8   (engine.cpp tune_cache_save)
+# flags: 1 lds, 64 cm2, 128 cm4, 256 w8   (engine_tune.cpp tune_cache_save)
 ALTS = [("w8 mt2 nt4 i4", "2 4 257 4"), ("w8 mt2 nt4 cm2", "2 4 321 2"), ("w8 mt1 nt4 cm4", "1 4 385 4"), ("w8 mt1 nt4 i4", "1 4 257 4"),
         ("nt8 i1", "1 8 257 1"), ("nt8 i2", "1 8 257 2"), ("nt8 cm2", "1 8 321 2"), ("mt1 nt4 cm4 (4 waves)", "1 4 129 4"), ("mt2 nt4 cm2 (4 waves)", "2 4 65 2")]
 base = [run(lines) for _ in range(rounds)]

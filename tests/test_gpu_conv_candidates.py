@@ -1,6 +1,6 @@
 """Every conv layer on its own, every autotuner candidate included, against a per-layer fp64 reference.
 
-The conv autotuner (engine.cpp autotune_convs) times every candidate tune_candidates() lists for a layer and keeps the
+The conv autotuner (engine_tune.cpp autotune_convs) times every candidate tune_candidates() lists for a layer and keeps the
 fastest, on the claim that all of them compute the same bits.  Here every candidate of every conv op is run through the
 C ABI's test hooks (irmv_engine_conv_candidates / irmv_engine_run_conv_candidate) on every slot range production can run
 it on: the tune count itself, the other stream shares (first > 0, the remainder share), a partial count, and for the
@@ -97,7 +97,7 @@ def read(e, name, first, count):
 
 def layer_table(blob):
     """weight layer name -> (w fp16 OHWI, b fp32) as the engine computes with, including the merged first-stage Detect
-    convs of single-frame engines (engine.cpp: cv2 / cv3 / cv4 .0 concatenated along cout, cv4 padded to 32 channels)."""
+    convs of single-frame engines (engine_graph.cpp: cv2 / cv3 / cv4 .0 concatenated along cout, cv4 padded to 32 channels)."""
     hdr, layers = weights.parse_blob(blob)
     t = {sp.name: (w, b) for sp, w, b in layers}
     for i in range(3):
