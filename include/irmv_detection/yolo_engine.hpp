@@ -75,7 +75,8 @@ public:
   // `window` ({} = none): a tracking window -- detect() runs on a window.width x window.height crop of the frame at the
   // sensor's resolution (include/irmv_hip.h, irmv_engine_cfg::win_width).  src_image_size stays the full frame the producer
   // writes and bboxes come back in its coordinates; set_window() / set_window_center() move the window between detect()
-  // calls; get_rotated_image() is then the rotated window.
+  // calls; get_rotated_image() is then the rotated window.  set_view(View::Frame) runs detect() on the whole frame instead
+  // (the search after a lost target), set_view(View::Window) goes back; get_rotated_image() follows the view.
   YoloEngine(const std::string & onnx_file_path, cv::Size src_image_size, bool enable_profiling = false, int device = -1,
              bool warm_up_now = true, int net_size = -1, int src_format = IRMV_SRC_HWC8,
              std::array<uint16_t, 3> bayer_gain_q8 = {256, 256, 256}, int net_height = -1,
@@ -168,6 +169,27 @@ public:
     if (irmv_engine_get_window(engine_, 0, &x0, &y0, &w, &h) != IRMV_OK)
       throw std::runtime_error(std::string("YoloEngine::window: ") + irmv_last_error());
     return {cv::Point(x0, y0), cv::Size(w, h)};
+  }
+
+  // ---- search view (window engines): detect() on the window, or on the whole frame after the target is lost ----
+  enum class View { Window, Frame };
+  // From the next detect() on.  Frame: what an engine without a window on the same frame computes -- no crop, no offset, the
+  // configured camera; the frame already in the pinned buffer can be run again without touching it.  The first Frame of an
+  // engine builds that view (call it once at start-up); switching back and forth afterwards re-captures nothing.
+  void set_view(View v)
+  {
+    if (irmv_engine_set_view(engine_, 0, v == View::Frame ? IRMV_VIEW_FRAME : IRMV_VIEW_WINDOW) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::set_view: ") + irmv_last_error());
+    const cv::Size sz = v == View::Frame ? src_image_size_ : window_size_;
+    if (rotated_.cols != sz.width || rotated_.rows != sz.height) rotated_ = cv::Mat(sz.height, sz.width, CV_8UC3);   // get_rotated_image(): the view's frame
+    rotated_valid_ = false;
+  }
+  View view() const
+  {
+    int v = IRMV_VIEW_WINDOW;
+    if (irmv_engine_get_view(engine_, 0, &v, nullptr, nullptr) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::view: ") + irmv_last_error());
+    return v == IRMV_VIEW_FRAME ? View::Frame : View::Window;
   }
 
   ~YoloEngine() { irmv_engine_destroy(engine_); }

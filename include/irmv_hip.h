@@ -252,6 +252,33 @@ typedef struct irmv_window_map_t {
 } irmv_window_map_t;
 int irmv_window_map(const irmv_engine_cfg *cfg, int x0, int y0, irmv_window_map_t *out);
 
+/* ---- search view: a window engine runs a slot's step on the whole frame on demand ----
+ * Per-slot state, like the window's corner.  A slot in IRMV_VIEW_FRAME behaves as a slot of an engine WITHOUT a window on the
+ * same src_width x src_height frame, net, weights, camera and switches: no crop; the front reads the full frame where the
+ * uploads or the demosaic put it, with the plan irmv_front_plan gives for win_* = 0 (so the two views may differ in whether
+ * the front runs fused, and on which of its paths); results are scaled by the full frame's factors and carry no offset; PnP
+ * sees the configured camera.  Uploads follow the view at submit time: in the frame view whole frames move, never a band and
+ * never the crop out of the pinned slot; a submit without IRMV_SUBMIT_H2D reads the device frame as it is.  Everything that acts
+ * on "the slot's frame" -- the read-backs, irmv_engine_run_post, irmv_engine_profile, irmv_engine_extract_armors,
+ * irmv_engine_light_trace, irmv_engine_rotated_image -- acts on the slot's current view.
+ * irmv_engine_set_view waits for the slot's last submitted step and takes effect from the slot's next submit; results read
+ * later still carry the view (and, in the window view, the corner) their step was submitted with.  Switching back and forth
+ * re-captures nothing: each (slots, step kind, view) graph is captured once.  All slots of one irmv_engine_submit must be in
+ * one view (IRMV_ERR_ARG otherwise, before anything is enqueued).  irmv_engine_set_window stays allowed in the frame view: it
+ * records the corner, which is in force again when the slot returns to the window view.
+ * The first IRMV_VIEW_FRAME of an engine builds the frame view (tap tables, launch lists, the larger scratch of the classical
+ * extraction and of irmv_engine_rotated_image) after waiting for every step in flight, as irmv_engine_set_bayer_isp does: call
+ * it once at start-up to pay that there.  An engine on which it is never called allocates and runs what it always did.
+ * IRMV_ERR_ARG: null engine, an engine without a window, a slot out of range, an unknown view, a frame view whose letterboxed
+ * frame would have no row or no column (the rule of irmv_engine_create); the engine stays usable. */
+#define IRMV_VIEW_WINDOW 0   /* the slot's step runs on its window (what every window engine does until told otherwise) */
+#define IRMV_VIEW_FRAME  1   /* ... on the whole src_width x src_height frame, into the same net input */
+int irmv_engine_set_view(irmv_engine *e, int slot, int view);
+/* The slot's view and the size of the source frame its steps see: the window's, or the full frame's (any pointer may be NULL). */
+int irmv_engine_get_view(const irmv_engine *e, int slot, int *view, int *src_w, int *src_h);
+/* Read-only (tests): the hipGraphExec objects the engine holds. */
+int irmv_engine_debug_graph_count(const irmv_engine *e);
+
 int irmv_engine_src_format(const irmv_engine *e);      /* IRMV_SRC_* of this engine; -1 for a null engine */
 size_t irmv_engine_src_bytes(const irmv_engine *e);    /* bytes of one source slot (host and device); 0 for a null engine */
 
@@ -288,7 +315,8 @@ double irmv_engine_last_detect_ms(const irmv_engine *e);
  * in-place mirror, src/yolo_engine.cpp:77-78,182-184), rotated on the GPU.  dst_hwc
  * receives src_height*src_width*3 bytes in every format: a Bayer engine uploads the
  * raw slot, demosaics it and returns the rotated R, G, B frame.  A window engine
- * returns the rotated window: win_height*win_width*3 bytes. */
+ * returns the rotated window: win_height*win_width*3 bytes -- or, for a slot in
+ * IRMV_VIEW_FRAME, the rotated full frame: src_height*src_width*3 bytes. */
 int irmv_engine_rotated_image(irmv_engine *e, int slot, uint8_t *dst_hwc);
 
 /* The gains and tone curve of a Bayer engine, changeable while it lives (the camera SDK's ISP retuned per venue):
@@ -307,7 +335,8 @@ int irmv_engine_get_bayer_isp(const irmv_engine *e, uint16_t gain_q8[3], uint8_t
 /* IrmDetector::extract_armors(get_rotated_image(), bboxes) (src/irm_detector.cpp:183,292-355) on the GPU:
  * for each of the n boxes (xyxy, rotated-frame pixels) on the slot's current frame -> out[i].kpts (LB, LT, RT,
  * RB), armor_valid, armor_size, n_lights, and the PnP pose.  Works for any model / point_source.  A window engine takes the
- * boxes and returns kpts in the full frame's coordinates and looks at the slot's current window. */
+ * boxes and returns kpts in the full frame's coordinates and looks at the slot's current window (IRMV_VIEW_FRAME: at the
+ * whole frame). */
 int irmv_engine_extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, irmv_det *out);
 /* The node's live parameters of that extraction (IrmDetector::param_event_callback, src/irm_detector.cpp:372-403):
  * binary_threshold, light.{min_ratio,max_ratio,max_angle}, armor.{min_small,max_small,min_large,max_large}_center_distance.

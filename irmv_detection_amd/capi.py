@@ -20,6 +20,8 @@ SRC_HWC8, SRC_BAYER_RGGB8, SRC_BAYER_BGGR8, SRC_BAYER_GRBG8, SRC_BAYER_GBRG8 = 0
 BAYER_FORMATS = {"RGGB": SRC_BAYER_RGGB8, "BGGR": SRC_BAYER_BGGR8, "GRBG": SRC_BAYER_GRBG8, "GBRG": SRC_BAYER_GBRG8}
 DEMOSAIC_BILINEAR, DEMOSAIC_MHC = 0, 1
 DEMOSAIC_ALGOS = {"bilinear": DEMOSAIC_BILINEAR, "mhc": DEMOSAIC_MHC}
+VIEW_WINDOW, VIEW_FRAME = 0, 1
+VIEWS = {"window": VIEW_WINDOW, "frame": VIEW_FRAME}
 NUM_CLASSES = 14
 MAX_DET_CAP = 256
 CAND_CAP = 8192
@@ -168,6 +170,9 @@ SYMBOLS = [
     ("irmv_engine_set_window", C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     ("irmv_engine_get_window", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("irmv_window_map", C.c_int, [C.POINTER(EngineCfg), C.c_int, C.c_int, C.POINTER(WindowMap)]),
+    ("irmv_engine_set_view", C.c_int, [_P, C.c_int, C.c_int]),
+    ("irmv_engine_get_view", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("irmv_engine_debug_graph_count", C.c_int, [_P]),
     ("irmv_engine_src_format", C.c_int, [_P]),
     ("irmv_engine_src_bytes", C.c_size_t, [_P]),
     ("irmv_engine_submit", C.c_int, [_P, C.c_int, C.c_int, C.c_uint32]),

@@ -323,6 +323,15 @@ static irmv_engine_cfg window_view(const irmv_engine_cfg &c)
     return v;
 }
 
+// a source so oblong that the short side of its letterboxed frame rounds to nothing: no box, no scale back to the source
+int irmv::check_letterbox(const irmv_engine_cfg &c)
+{
+    int nw, nh;
+    scaled_size(c, &nw, &nh);
+    if (nw < 1 || nh < 1) return fail(IRMV_ERR_ARG, "letterbox: the scaled frame has no row or no column; use IRMV_RESIZE_STRETCH");
+    return IRMV_OK;
+}
+
 // The caller's configuration at this library's size (an older caller's prefix, the appended fields at their defaults),
 // and the checks of everything the front's geometry follows from.  No GPU call.
 static int resolve_cfg(const irmv_engine_cfg *cfg_in, irmv_engine_cfg *full)
@@ -363,12 +372,7 @@ static int resolve_cfg(const irmv_engine_cfg *cfg_in, irmv_engine_cfg *full)
     if (cfg->win_width < 0 || cfg->win_width > cfg->src_width) return fail(IRMV_ERR_ARG, "win_width must be 0 (no window) or in [1, src_width]");
     if (cfg->win_height < 0 || cfg->win_height > cfg->src_height) return fail(IRMV_ERR_ARG, "win_height must be 0 (no window) or in [1, src_height]");
     if ((cfg->win_width == 0) != (cfg->win_height == 0)) return fail(IRMV_ERR_ARG, "win_width and win_height must both be 0 (no window) or both be set");
-    {   // a source so oblong that the short side of its letterboxed frame rounds to nothing: no box, no scale back to the source
-        int nw, nh;
-        scaled_size(window_view(*cfg), &nw, &nh);
-        if (nw < 1 || nh < 1) return fail(IRMV_ERR_ARG, "letterbox: the scaled frame has no row or no column; use IRMV_RESIZE_STRETCH");
-    }
-    return IRMV_OK;
+    return check_letterbox(window_view(*cfg));
 }
 
 extern "C" int irmv_front_plan(const irmv_engine_cfg *cfg_in, irmv_front_plan_t *out)
@@ -417,7 +421,7 @@ extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **o
     TRY(autotune_convs(e.get()));
     finalize_head_fusion(e.get());
     TRY(build_head_groups(e.get()));
-    build_step_plans(e.get());
+    build_step_plans(e.get(), e->views[IRMV_VIEW_WINDOW]);
     TRY(choose_sync_launch(e.get()));
     *out = e.release();
     return IRMV_OK;
@@ -499,14 +503,16 @@ extern "C" int irmv_window_map(const irmv_engine_cfg *cfg_in, int x0, int y0, ir
     return window_map(full.src_width, full.src_height, full.win_width, full.win_height, full.rotate180, full.camera_matrix, x0, y0, out);
 }
 
-// The slot's entries of the two device tables from e->win_org[slot].  The caller has made sure no step of the slot is in flight.
+// The slot's entries of the two device tables from e->win_org[slot] and its view: the corner always, the camera with the
+// principal point moved by it in the window view and as configured in the frame view.  The caller has made sure no step of
+// the slot is in flight.
 int irmv::write_window(irmv_engine *e, int slot)
 {
     irmv_window_map_t m;
     TRY(window_map(e->full_w, e->full_h, e->cfg.src_width, e->cfg.src_height, e->cfg.rotate180, e->cfg.camera_matrix, e->win_org[slot].x, e->win_org[slot].y, &m));
     const int2 b{m.bx0, m.by0};
     PnpConst pc = e->pnp_base;
-    pc.cx = m.cx; pc.cy = m.cy;
+    if (e->slot_view[slot] == IRMV_VIEW_WINDOW) { pc.cx = m.cx; pc.cy = m.cy; }
     HIP_TRY(hipMemcpy(e->win_dev + slot, &b, sizeof b, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(e->pnp_dev + slot, &pc, sizeof pc, hipMemcpyHostToDevice));
     return IRMV_OK;
@@ -536,6 +542,41 @@ extern "C" int irmv_engine_get_window(const irmv_engine *e, int slot, int *x0, i
     if (h) *h = e->cfg.src_height;
     return IRMV_OK;
 }
+
+// ---- search view --------------------------------------------------------------------
+extern "C" int irmv_engine_set_view(irmv_engine *e, int slot, int view)
+{
+    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
+    if (!e->window) return fail(IRMV_ERR_ARG, "irmv_engine_set_view: the engine has no window (win_width, win_height)");
+    if (slot < 0 || slot >= e->cfg.num_slots) return fail(IRMV_ERR_ARG, "slot out of range");
+    if (view != IRMV_VIEW_WINDOW && view != IRMV_VIEW_FRAME) return fail(IRMV_ERR_ARG, "unknown view (IRMV_VIEW_*)");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    if (view == IRMV_VIEW_FRAME && !e->views[IRMV_VIEW_FRAME].built) {
+        irmv_engine_cfg full = e->cfg;
+        full.src_width = e->full_w; full.src_height = e->full_h;
+        TRY(check_letterbox(full));
+        TRY(irmv_engine_wait(e));   // every stream of the engine: the build appends to what steps read
+        TRY(build_frame_view(e));
+    }
+    TRY(irmv_engine_wait_slots(e, slot, 1));   // the slot's last step has read its camera record
+    if (e->slot_view[slot] == view) return IRMV_OK;
+    e->slot_view[slot] = view;
+    return write_window(e, slot);
+}
+
+extern "C" int irmv_engine_get_view(const irmv_engine *e, int slot, int *view, int *src_w, int *src_h)
+{
+    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
+    if (!e->window) return fail(IRMV_ERR_ARG, "irmv_engine_get_view: the engine has no window (win_width, win_height)");
+    if (slot < 0 || slot >= e->cfg.num_slots) return fail(IRMV_ERR_ARG, "slot out of range");
+    const View &v = view_of(e, slot);
+    if (view) *view = e->slot_view[slot];
+    if (src_w) *src_w = v.src_w;
+    if (src_h) *src_h = v.src_h;
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_debug_graph_count(const irmv_engine *e) { return e ? (int)e->graphs.size() : 0; }
 
 // ---- extract parameters and Bayer ISP ------------------------------------------------
 // T[c][v] = lut[c][min(255, (v gain[c] + 128) >> 8)] from the engine's current gains and LUT -> isp_table_dev.  The caller has
@@ -604,9 +645,10 @@ extern "C" int irmv_engine_set_bayer_isp(irmv_engine *e, const uint16_t gain_q8[
         for (size_t i = 0; i < e->ops.size(); i++) {
             if (e->ops[i].kind != OP_DEMOSAIC) continue;
             snprintf(e->ops[i].kname, sizeof e->ops[i].kname, "%s", demosaic_kname(e));
-            for (auto &plan : e->plans)
-                for (Launch &l : plan)
-                    if (l.op == (int)i) l.name = e->ops[i].kname;
+            for (View &v : e->views)
+                for (auto &plan : v.plans)
+                    for (Launch &l : plan)
+                        if (l.op == (int)i) l.name = e->ops[i].kname;
         }
     }
     return IRMV_OK;

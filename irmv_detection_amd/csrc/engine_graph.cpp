@@ -463,7 +463,13 @@ static int create_streams_and_frames(irmv_engine *e)
     }
     TRY(dev_alloc(e, (void **)&e->src_dev, e->frame_bytes * S));
     HIP_TRY(hipMemset(e->src_dev, 0, e->frame_bytes * S));
-    TRY(dev_alloc(e, (void **)&e->rot_dev, e->frame_bytes));
+    View &v0 = e->views[IRMV_VIEW_WINDOW];
+    v0.built = true; v0.crop = e->window;
+    v0.src_w = c.src_width; v0.src_h = c.src_height;
+    v0.frames = e->src_dev; v0.frame_bytes = e->frame_bytes;
+    TRY(dev_alloc(e, (void **)&v0.rot_dev, e->frame_bytes));
+    e->slot_view.assign(S, IRMV_VIEW_WINDOW);
+    e->sub_view = e->slot_view;
     if (e->window) {
         TRY(dev_alloc(e, (void **)&e->full_dev, e->full_bytes * S));
         HIP_TRY(hipMemset(e->full_dev, 0, e->full_bytes * S));
@@ -488,20 +494,79 @@ static int create_streams_and_frames(irmv_engine *e)
     return IRMV_OK;
 }
 
-// preprocess and front geometry: front_plan, under the engine's environment switches
-static int build_front_geometry(irmv_engine *e)
+// preprocess, front and post geometry of a view whose source frame is src_w x src_h: front_plan, under the engine's
+// environment switches, and the scale that takes net-input pixels back to that frame
+int irmv::build_view_geometry(irmv_engine *e, View &v, int src_w, int src_h)
 {
     const int net_w = e->cfg.net_size, net_h = e->cfg.net_height;
+    irmv_engine_cfg c = e->cfg;
+    c.src_width = src_w; c.src_height = src_h;
     std::vector<AxisTap> tx, ty;
-    irmv_front_plan_t &plan = e->front;
-    front_plan(e->cfg, e->sw.front, &plan, tx, ty);
-    TRY(dev_alloc(e, (void **)&e->tap_x, net_w * sizeof(AxisTap)));
-    TRY(dev_alloc(e, (void **)&e->tap_y, net_h * sizeof(AxisTap)));
-    HIP_TRY(hipMemcpy(e->tap_x, tx.data(), net_w * sizeof(AxisTap), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->tap_y, ty.data(), net_h * sizeof(AxisTap), hipMemcpyHostToDevice));
-    e->fused_front = plan.fused != 0;
-    if (!e->sw.fused_front) e->fused_front = false;
-    if (e->fused_front && !front_prepare()) e->fused_front = false;
+    irmv_front_plan_t &plan = v.front;
+    front_plan(c, e->sw.front, &plan, tx, ty);
+    TRY(dev_alloc(e, (void **)&v.tap_x, net_w * sizeof(AxisTap)));
+    TRY(dev_alloc(e, (void **)&v.tap_y, net_h * sizeof(AxisTap)));
+    HIP_TRY(hipMemcpy(v.tap_x, tx.data(), net_w * sizeof(AxisTap), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(v.tap_y, ty.data(), net_h * sizeof(AxisTap), hipMemcpyHostToDevice));
+    v.fused_front = plan.fused != 0;
+    if (!e->sw.fused_front) v.fused_front = false;
+    if (v.fused_front && !front_prepare()) v.fused_front = false;
+    const int px = plan.box[0], py = plan.box[2], nw = plan.box[1] - px, nh = plan.box[3] - py;   // the letterbox box
+    if (c.resize_mode == IRMV_RESIZE_STRETCH) {
+        v.scale_x = (float)src_w / (float)net_w;   // src/yolo_engine.cpp:155-156
+        v.scale_y = (float)src_h / (float)net_h;
+        v.off_x = v.off_y = 0.f;
+    } else {
+        v.scale_x = (float)src_w / (float)nw;
+        v.scale_y = (float)src_h / (float)nh;
+        v.off_x = (float)px;
+        v.off_y = (float)py;
+    }
+    return IRMV_OK;
+}
+
+// model.1.conv has the shape the fused front kernel is written for
+static bool front_takes_model1(const Op &m1) { return m1.cfg.cin16 && m1.ksteps == 5 && m1.pair && m1.cout_pad == 32 && m1.out_coff == 0; }
+
+// the op that stands for preprocess + model.0.conv + model.1.conv in the steps of a view whose front is fused
+static void add_front_op(irmv_engine *e, double frame_bytes)
+{
+    const Op &m1 = e->ops[e->front_ops[2]];
+    const Tensor &ot = e->tensors[m1.out_t];
+    Op op; op.kind = OP_FRONT; op.layer = "preprocess+model.0+model.1"; snprintf(op.kname, sizeof op.kname, "front_fused");
+    op.flops = e->ops[e->front_ops[1]].flops + m1.flops;
+    op.bytes = frame_bytes + (double)ot.H * ot.W * 32 * 2;
+    op.w_packed = m1.w_packed; op.bias = m1.bias; op.out_t = m1.out_t;
+    e->lazy_tensors.insert("input"); e->lazy_tensors.insert("0");
+    e->front_op = (int)e->ops.size();
+    e->ops.push_back(op);
+}
+
+// scratch of the classical extraction that grows with the view's frame: per slot a padded label image
+static int alloc_view_light(irmv_engine *e, View &v)
+{
+    const size_t SL = e->classical ? (size_t)e->cfg.num_slots : 1;   // keypoint mode keeps one slot's worth for irmv_engine_extract_armors
+    v.light_pool = std::max<size_t>((size_t)8 * v.src_w * v.src_h, (size_t)(v.src_w + 2) * (v.src_h + 2) + 16);
+    return dev_alloc(e, (void **)&v.light_labels, SL * v.light_pool);
+}
+
+// The frame view of a window engine (irmv_engine_set_view): the full frame's geometry and tap tables, the larger label pool
+// and rotated-image buffer, and the launch lists.  Nothing of the engine is in flight.
+int irmv::build_frame_view(irmv_engine *e)
+{
+    View &v = e->views[IRMV_VIEW_FRAME];
+    if (v.built) return IRMV_OK;
+    v.crop = false;
+    v.src_w = e->full_w; v.src_h = e->full_h;
+    v.frames = e->full_dev; v.frame_bytes = e->full_bytes;
+    TRY(build_view_geometry(e, v, e->full_w, e->full_h));
+    if (!front_takes_model1(e->ops[e->front_ops[2]])) v.fused_front = false;
+    if (v.fused_front && e->front_op < 0) add_front_op(e, (double)e->frame_bytes);   // (its bytes count view 0's frame; build_step_plans adds the difference)
+    TRY(alloc_view_light(e, v));
+    TRY(dev_alloc(e, (void **)&v.rot_dev, v.frame_bytes));
+    build_step_plans(e, v);
+    HIP_TRY(hipDeviceSynchronize());
+    v.built = true;
     return IRMV_OK;
 }
 
@@ -531,7 +596,7 @@ static int build_trunk(irmv_engine *e, Acts &act)
         op.bytes = 2.0 * (double)e->frame_bytes;
         e->ops.push_back(op);
     }
-    const size_t conv0_op = e->ops.size() + 1;   // (OP_PRE, then OP_CONV0)
+    e->front_ops[0] = (int)e->ops.size(); e->front_ops[1] = e->front_ops[0] + 1; e->front_ops[2] = e->front_ops[0] + 2;   // OP_PRE, OP_CONV0, model.1.conv
     { Op op; op.kind = OP_PRE; op.layer = "preprocess"; snprintf(op.kname, sizeof op.kname, "preprocess"); op.out_t = act.x0;
       op.bytes = (double)e->frame_bytes + (double)net_h * net_w * 8; e->ops.push_back(op); }
     {
@@ -562,16 +627,11 @@ static int build_trunk(irmv_engine *e, Acts &act)
     }
     TRY(add_conv(e, "model.1.conv", SegRef{act.a0, 0, 16, 0}, SegRef{}, act.h2, act.w2, act.a1, 0));
     {
-        const Op &m1 = e->ops.back();
-        if (!(m1.cfg.cin16 && m1.ksteps == 5 && m1.pair && m1.cout_pad == 32 && m1.out_coff == 0)) e->fused_front = false;
-        if (e->fused_front) {
-            Op op; op.kind = OP_FRONT; op.layer = "preprocess+model.0+model.1"; snprintf(op.kname, sizeof op.kname, "front_fused");
-            op.flops = e->ops[conv0_op].flops + m1.flops;
-            op.bytes = (double)e->frame_bytes + (double)act.h4 * act.w4 * 32 * 2;
-            op.w_packed = m1.w_packed; op.bias = m1.bias; op.out_t = m1.out_t;
+        View &v0 = e->views[IRMV_VIEW_WINDOW];
+        if (!front_takes_model1(e->ops.back())) v0.fused_front = false;
+        if (v0.fused_front) {
             for (Op &o : e->ops) o.fused_away = o.kind != OP_DEMOSAIC && o.kind != OP_CROP;   // preprocess, model.0.conv, model.1.conv
-            e->lazy_tensors.insert("input"); e->lazy_tensors.insert("0");
-            e->ops.push_back(op);
+            add_front_op(e, (double)e->frame_bytes);
         }
     }
     act.p3 = act.a4; act.p4 = act.a6; act.p5 = act.a8;   // the tensors the neck reads
@@ -731,7 +791,6 @@ static int build_post_stage(irmv_engine *e)
 {
     const irmv_engine_cfg &c = e->cfg;
     const int net_w = c.net_size, net_h = c.net_height, S = c.num_slots;
-    const int px = e->front.box[0], py = e->front.box[2], nw = e->front.box[1] - px, nh = e->front.box[3] - py;   // the letterbox box (front_plan)
     // ---- post-processing buffers ----
     TRY(dev_alloc(e, (void **)&e->boxes, (size_t)S * e->A * 16));
     TRY(dev_alloc(e, (void **)&e->keys, (size_t)S * e->A * e->nc * 8));
@@ -782,8 +841,7 @@ static int build_post_stage(irmv_engine *e)
     }
     // scratch of the classical extraction: per detection a padded label image (ROIs up to ~510 x 510) and contour points
     const size_t SL = e->classical ? (size_t)S : 1;   // keypoint mode keeps one slot's worth for irmv_engine_extract_armors
-    e->light_pool = std::max<size_t>((size_t)8 * c.src_width * c.src_height, (size_t)(c.src_width + 2) * (c.src_height + 2) + 16);
-    TRY(dev_alloc(e, (void **)&e->light_labels, SL * e->light_pool));
+    TRY(alloc_view_light(e, e->views[IRMV_VIEW_WINDOW]));
     TRY(dev_alloc(e, (void **)&e->light_points, SL * c.max_det * kLightPointsCap * 2 * sizeof(short)));
     TRY(dev_alloc(e, (void **)&e->light_hulls, SL * c.max_det * kLightPointsCap * 4 * sizeof(short)));
     TRY(dev_alloc(e, (void **)&e->light_boxes, (size_t)c.max_det * 16));
@@ -799,16 +857,6 @@ static int build_post_stage(irmv_engine *e)
     p.pre_nms_cap = c.pre_nms_cap;
     p.classwalk = e->sw.nms_classwalk ? 1 : 0;
     p.prefilter = e->sw.nms_prefilter;
-    if (c.resize_mode == IRMV_RESIZE_STRETCH) {
-        p.scale_x = (float)c.src_width / (float)net_w;   // src/yolo_engine.cpp:155-156
-        p.scale_y = (float)c.src_height / (float)net_h;
-        p.off_x = p.off_y = 0.f;
-    } else {
-        p.scale_x = (float)c.src_width / (float)nw;
-        p.scale_y = (float)c.src_height / (float)nh;
-        p.off_x = (float)px;
-        p.off_y = (float)py;
-    }
     p.armor_size = c.armor_size;
     PnpConst pc;
     pc.fx = c.camera_matrix[0]; pc.fy = c.camera_matrix[4];
@@ -841,7 +889,7 @@ int irmv::build_engine(irmv_engine *e)
     HIP_TRY(hipSetDevice(e->cfg.device));
     Acts act{};
     TRY(create_streams_and_frames(e));
-    TRY(build_front_geometry(e));
+    TRY(build_view_geometry(e, e->views[IRMV_VIEW_WINDOW], e->cfg.src_width, e->cfg.src_height));
     TRY(build_trunk(e, act));
     TRY(build_neck_and_head(e, act));
     TRY(build_post_stage(e));

@@ -50,9 +50,10 @@ extern "C" int irmv_engine_rotated_image(irmv_engine *e, int slot, uint8_t *dst)
     TRY(check_range(e, slot, 1));
     if (!dst) return fail(IRMV_ERR_ARG, "dst is null");
     HIP_TRY(hipSetDevice(e->cfg.device));
+    const View &v = view_of(e, slot);
     TRY(load_frame(e, slot, e->stream));
-    launch_rotate180(e->src_dev + (size_t)slot * e->frame_bytes, e->rot_dev, e->cfg.src_width, e->cfg.src_height, e->stream);
-    HIP_TRY(hipMemcpyAsync(dst, e->rot_dev, e->frame_bytes, hipMemcpyDeviceToHost, e->stream));
+    launch_rotate180(v.frames + (size_t)slot * v.frame_bytes, v.rot_dev, v.src_w, v.src_h, e->stream);
+    HIP_TRY(hipMemcpyAsync(dst, v.rot_dev, v.frame_bytes, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return IRMV_OK;
 }
@@ -75,10 +76,13 @@ static int extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, ir
     if (trace && !e->light_trace_dev) TRY(dev_alloc(e, (void **)&e->light_trace_dev, (size_t)e->cfg.max_det * sizeof(LightTrace)));
     if (trace) HIP_TRY(hipMemsetAsync(e->light_trace_dev, 0, (size_t)n * sizeof(LightTrace), st));
     TRY(load_frame(e, slot, st));
-    // a window engine takes the boxes in full result coordinates: window-local for the kernel, the corner back onto its points
-    const float ox = e->window ? (float)e->win_org[slot].x : 0.f, oy = e->window ? (float)e->win_org[slot].y : 0.f;
+    // a window engine takes the boxes in full result coordinates: in the window view window-local for the kernel, the corner
+    // back onto its points
+    const View &v = view_of(e, slot);
+    const bool shift = v.crop;
+    const float ox = shift ? (float)e->win_org[slot].x : 0.f, oy = shift ? (float)e->win_org[slot].y : 0.f;
     std::vector<float> local;
-    if (e->window) {
+    if (shift) {
         local.assign(xyxy, xyxy + (size_t)n * 4);
         for (size_t j = 0; j < local.size(); j++) local[j] -= (j & 1) ? oy : ox;
         HIP_TRY(hipMemcpyAsync(e->light_boxes, local.data(), (size_t)n * 16, hipMemcpyHostToDevice, st));
@@ -86,9 +90,9 @@ static int extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, ir
     } else {
         HIP_TRY(hipMemcpyAsync(e->light_boxes, xyxy, (size_t)n * 16, hipMemcpyHostToDevice, st));
     }
-    LightArgs a = light_args(e, slot);
+    LightArgs a = light_args(e, v, slot);
     a.dets = e->light_dets_dev;
-    a.labels = e->light_labels;
+    a.labels = v.light_labels;
     a.points = e->light_points;
     a.hulls = e->light_hulls;
     a.num_dets = nullptr;
@@ -106,7 +110,7 @@ static int extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, ir
         memset(&o, 0, sizeof o);
         memcpy(o.xyxy, xyxy + 4 * i, 16);
         o.class_id = IRMV_NUM_CLASSES;
-        det_pose(e, d, ox, oy, o);
+        det_pose(d, shift, ox, oy, o);
     }
     return IRMV_OK;
 }
@@ -544,7 +548,7 @@ extern "C" int irmv_engine_run_op(irmv_engine *e, int op, int first, int count, 
     if (flags & IRMV_RUN_POISON_ONLY) { HIP_TRY(hipStreamSynchronize(e->stream)); return IRMV_OK; }
     Launch l;   // (a plain launch of the op: no group, no fusion, no gate)
     l.op = op;
-    TRY(launch_op(e, l, first, count, post_args(e, first), 0u, false, e->stream));
+    TRY(launch_op(e, view_of(e, first), l, first, count, post_args(e, view_of(e, first), first), 0u, false, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return IRMV_OK;
 }
@@ -584,6 +588,8 @@ extern "C" int irmv_engine_profile(irmv_engine *e, int first, int count, irmv_ke
 {
     TRY(check_range(e, first, count));
     if (!n) return fail(IRMV_ERR_ARG, "n is null");
+    int view;
+    TRY(slots_view(e, first, count, &view));
     HIP_TRY(hipSetDevice(e->cfg.device));
     // Eager replay of the step's launches on the engine stream, every kernel bracketed by an event
     // pair.  The kernels are idempotent and are launched kProfileRepeat times inside their bracket: an event pair around ONE launch also times ~4 us of
@@ -592,7 +598,7 @@ extern "C" int irmv_engine_profile(irmv_engine *e, int first, int count, irmv_ke
     // ROCm 7.2: "invalid resource handle".)
     TRY(irmv_engine_wait(e));
     const StepKind kind = count == 1 ? STEP_ONE : STEP_BATCH;
-    const std::vector<Launch> &plan = e->plans[kind];
+    const std::vector<Launch> &plan = e->views[view].plans[kind];
     ProfileEvents pe;
     pe.ev.resize(2 * plan.size(), nullptr);
     for (hipEvent_t &x : pe.ev) HIP_TRY(hipEventCreate(&x));

@@ -163,7 +163,29 @@ struct GraphKey {
     int first, count;
     StepKind kind;
     bool upload;   // the frames' upload is the graph's first node
-    bool operator<(const GraphKey &o) const { return std::tie(first, count, kind, upload) < std::tie(o.first, o.count, o.kind, o.upload); }
+    int view;      // IRMV_VIEW_*: the view its slots were in when it was captured
+    bool operator<(const GraphKey &o) const { return std::tie(first, count, kind, upload, view) < std::tie(o.first, o.count, o.kind, o.upload, o.view); }
+};
+
+// What a step sees in front of model.1's output -- the source frame and everything that follows from its size.  views[0]
+// (IRMV_VIEW_WINDOW) is what e->cfg describes: the whole frame of an engine without a window, the window of one with it.
+// views[1] (IRMV_VIEW_FRAME) exists on window engines only, from the first irmv_engine_set_view(.., IRMV_VIEW_FRAME) on: the
+// full frame, read where the uploads or the demosaic put it, with no crop in front.
+struct View {
+    bool built = false;
+    bool crop = false;                 // a step cuts the slot's window out of its full frame first (OP_CROP)
+    int src_w = 0, src_h = 0;          // the source frame the front, the light extraction and the rotated image see
+    uint8_t *frames = nullptr;         // [S][frame_bytes]: src_dev, or full_dev for the frame view
+    size_t frame_bytes = 0;            // one such HWC frame (and the slot stride)
+    AxisTap *tap_x = nullptr, *tap_y = nullptr;
+    bool fused_front = false;          // OP_FRONT replaces preprocess + model.0.conv + model.1.conv in a step
+    irmv_front_plan_t front{};         // the front's geometry as front_plan decided it: tile grid, stage bytes, box = the valid (non-padding) net-input column / row ranges,
+                                       // fastx / fx_i0 / fx_step: every x tap is (i0 + 2 k, i0 + 2 k + 1; 1/2): the front kernel's 2 : 1 column path
+    float scale_x = 1.f, scale_y = 1.f, off_x = 0.f, off_y = 0.f;   // PostArgs: net-input pixels -> this source frame
+    signed char *light_labels = nullptr;   // label pool of the light extraction: light_pool bytes per slot
+    size_t light_pool = 0;
+    uint8_t *rot_dev = nullptr;        // [frame_bytes] irmv_engine_rotated_image
+    std::vector<Launch> plans[STEP_POST + 1];   // per StepKind: the launches of such a step, in order (build_step_plans)
 };
 
 // Events of one submitted slot group [first, first + count): h2d = its frames are in HBM (async upload only);
@@ -203,7 +225,7 @@ struct irmv_engine {
     bool sparse_branch = false;
     std::vector<char> branch_stale;
     int lvl_hw[3] = {0, 0, 0}, lvl_base[3] = {0, 0, 0};
-    size_t frame_bytes = 0;       // one HWC source frame (src_dev, rot_dev)
+    size_t frame_bytes = 0;       // one HWC source frame of src_dev (views[0])
     size_t src_bytes = 0;         // one source slot as the producer writes it (src_host, and raw_dev or src_dev): frame_bytes, or W*H for a Bayer engine
     hipStream_t stream = nullptr;                 // stream 0: single-slot detect(), read-backs, profile
     hipStream_t extra_streams[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // streams 1..num_streams-1
@@ -227,7 +249,6 @@ struct irmv_engine {
     bool bayer_table = false, bayer_mhc = false;
     uint16_t isp_gain[3] = {256, 256, 256};
     uint8_t isp_lut[kBayerTableBytes] = {0};
-    uint8_t *rot_dev = nullptr;   // [frame]
     // Tracking window (irmv_engine_cfg.win_width / win_height): cfg.src_width x cfg.src_height is then the WINDOW -- what every
     // kernel behind the crop sees as its source frame -- and full_w x full_h the frame the producer writes.  OP_CROP cuts the
     // window at win_dev[slot] out of the slot's full frame (full_dev, or the pinned slot itself) into its src_dev frame.
@@ -239,24 +260,23 @@ struct irmv_engine {
     int2 *win_dev = nullptr;          // [S] the windows' corners in buffer coordinates, read by window_crop_kernel when it runs
     std::vector<int2> win_org;        // [S] the corners as set, in result coordinates (the rotated frame under rotate180)
     std::vector<int2> sub_org;        // [S] ... as they were at the slot's last submit: what its results are shifted by
+    // Search view (irmv_engine_set_view): per slot, whether its next step runs on its window or on the whole frame.
+    View views[2];                    // [IRMV_VIEW_WINDOW], [IRMV_VIEW_FRAME]
+    std::vector<int> slot_view;       // [S] IRMV_VIEW_* of the slot's next submit (all IRMV_VIEW_WINDOW = 0 until set_view)
+    std::vector<int> sub_view;        // [S] ... as it was at the slot's last submit: whether its results carry the corner
+    int front_ops[3] = {-1, -1, -1};  // ops preprocess, model.0.conv, model.1.conv: what a view whose front is not fused launches
+    int front_op = -1;                // OP_FRONT: what a view whose front is fused launches in their place (-1: no view's is)
     PnpConst pnp_base{};              // the camera as configured; pnp_dev[slot] = pnp_base with the principal point moved by the slot's corner
-    AxisTap *tap_x = nullptr, *tap_y = nullptr;
     std::vector<Tensor> tensors;
     std::map<std::string, int> tensor_idx;
     std::vector<Op> ops;
-    std::vector<Launch> plans[STEP_POST + 1];   // per StepKind: the launches of such a step, in order (build_step_plans)
     std::vector<void *> dev_allocs;
     int head_t[3] = {-1, -1, -1};
     float *head_all = nullptr;
     PnpConst *pnp_dev = nullptr;
     long long *dbg_dev = nullptr;
     std::set<std::string> lazy_tensors;   // tensors a step does not write because a fused kernel keeps them on chip
-    bool fused_front = false;          // OP_FRONT replaces preprocess + model.0.conv + model.1.conv in a step
-    irmv_front_plan_t front{};         // the front's geometry as front_plan decided it: tile grid, stage bytes, box = the valid (non-padding) net-input column / row ranges,
-                                       // fastx / fx_i0 / fx_step: every x tap is (i0 + 2 k, i0 + 2 k + 1; 1/2): the front kernel's 2 : 1 column path
     bool classical = false;            // four points from the classical light extraction instead of a keypoint head
-    signed char *light_labels = nullptr;   // label pool: light_pool bytes per slot
-    size_t light_pool = 0;
     short *light_points = nullptr, *light_hulls = nullptr;
     float *light_boxes = nullptr;      // explicit boxes of irmv_engine_extract_armors
     DevDet *light_dets_dev = nullptr, *light_dets_host = nullptr;
@@ -268,7 +288,7 @@ struct irmv_engine {
     bool zero_copy_results = false;   // the NMS kernel writes its results straight into pinned host memory (no D2H copy)
     half_t *conv0_w = nullptr;
     float *conv0_b = nullptr;
-    PostArgs post{};
+    PostArgs post{};                  // (scale and offset: filled per step from the slots' view)
     std::map<GraphKey, hipGraphExec_t> graphs;
     double last_detect_ms = 0;
     std::vector<uint8_t> blob;
@@ -296,6 +316,8 @@ inline int stream_share(const irmv_engine *e, int count) { return (count + e->nu
 // the device memory an upload of the source slots writes: the raw slots of a Bayer engine, else the HWC frames themselves
 // (a window engine's full frames)
 inline uint8_t *upload_dev(const irmv_engine *e) { return e->raw_dev ? e->raw_dev : (e->window ? e->full_dev : e->src_dev); }
+// the view slot's next step runs in
+inline const View &view_of(const irmv_engine *e, int slot) { return e->views[e->slot_view[slot]]; }
 // profile / op name of a Bayer engine's demosaic as it runs now
 inline const char *demosaic_kname(const irmv_engine *e) { return e->bayer_mhc ? "bayer_demosaic_mhc" : (e->bayer_table ? "bayer_demosaic_lut" : "bayer_demosaic"); }
 inline ConvWeights conv_weights(const Op &op) { return {op.w_packed, {op.w_lds[0], op.w_lds[1], op.w_lds[2], op.w_lds[3]}, op.w_k16}; }
@@ -306,12 +328,15 @@ namespace irmv {
 void log_range(const irmv_engine *e, const char *what, const void *p, size_t bytes);
 bool upload_aligned(size_t src_bytes, int first, int count);
 void front_plan(const irmv_engine_cfg &c, const FrontSwitches &sw, irmv_front_plan_t *p, std::vector<AxisTap> &tx, std::vector<AxisTap> &ty);
+int check_letterbox(const irmv_engine_cfg &c);
 int write_window(irmv_engine *e, int slot);
 int write_isp_table(irmv_engine *e);
 // engine_graph.cpp
 int dev_alloc(irmv_engine *e, void **p, size_t bytes);
 int load_blob(irmv_engine *e);
 int build_engine(irmv_engine *e);
+int build_view_geometry(irmv_engine *e, View &v, int src_w, int src_h);
+int build_frame_view(irmv_engine *e);
 // engine_tune.cpp
 TuneEntry tune_entry(const ConvCfg &c);
 std::vector<TuneCand> tune_candidates(const Op &op, const ConvArgs &a, int count, bool want_fuse, bool lds_ok, const TuneSwitches &sw, int num_cus);
@@ -321,19 +346,20 @@ int build_head_groups(irmv_engine *e);
 int choose_sync_launch(irmv_engine *e);
 // engine_plan.cpp
 void finalize_head_fusion(irmv_engine *e);
-void build_step_plans(irmv_engine *e);
+void build_step_plans(irmv_engine *e, View &v);
 // engine_step.cpp
 void fill_conv_args(const irmv_engine *e, const Op &op, int first, int count, ConvArgs &a, bool fused = false);
-LightArgs light_args(const irmv_engine *e, int first);
-PostArgs post_args(const irmv_engine *e, int first);
+int slots_view(const irmv_engine *e, int first, int count, int *view = nullptr);
+LightArgs light_args(const irmv_engine *e, const View &v, int first);
+PostArgs post_args(const irmv_engine *e, const View &v, int first);
 bool launch_head_group(const irmv_engine *e, const irmv_engine::HeadGroup &g, int first, const PostArgs *pa, unsigned scan, hipStream_t s);
-int launch_op(irmv_engine *e, const Launch &l, int first, int count, const PostArgs &pa, unsigned scan, bool crop_pinned, hipStream_t s);
+int launch_op(irmv_engine *e, const View &v, const Launch &l, int first, int count, const PostArgs &pa, unsigned scan, bool crop_pinned, hipStream_t s);
 int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipStream_t s, int reps, const std::vector<hipEvent_t> *ev, bool crop_pinned = false);
 void mark_stepped(irmv_engine *e, int first, int count);
 int copy_out(irmv_engine *e, int first, int count, hipStream_t st = nullptr);
 int check_range(const irmv_engine *e, int first, int count);
 int load_frame(irmv_engine *e, int slot, hipStream_t st);
-void det_pose(const irmv_engine *e, const DevDet &d, float ox, float oy, irmv_det &o);
+void det_pose(const DevDet &d, bool shift, float ox, float oy, irmv_det &o);
 // engine_hooks.cpp
 int ensure_dense_head(irmv_engine *e, int slot);
 }

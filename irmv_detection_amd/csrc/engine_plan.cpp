@@ -102,14 +102,20 @@ static void sparse_head_plan(irmv_engine *e, std::vector<Launch> &plan)
     plan.swap(out);
 }
 
-// The one place that decides which ops of e->ops a step of each kind launches, and how.
-void irmv::build_step_plans(irmv_engine *e)
+// The one place that decides which ops of e->ops a step of each kind launches in view v, and how.  The views differ in front
+// of model.1's output only: whether the window is cut out first, and whether the front runs fused or as its three layers.
+void irmv::build_step_plans(irmv_engine *e, View &v)
 {
+    auto is_front_layer = [&](int i) { return i == e->front_ops[0] || i == e->front_ops[1] || i == e->front_ops[2]; };
     for (int k = STEP_BATCH; k <= STEP_POST; k++) {
+        v.plans[k].clear();
         const bool one = k == STEP_ONE, mat = k == STEP_MATERIALIZE, post = k == STEP_POST, step = !mat && !post;
         auto emits = [&](const Op &op) { return step && e->emit_scan && is_cls_final_carrier(op); };
         for (int i = 0; i < (int)e->ops.size(); i++) {
             const Op &op = e->ops[i];
+            if (op.kind == OP_FRONT) continue;   // (launched where model.1.conv stands, below)
+            if (op.kind == OP_CROP && !v.crop) continue;
+            const bool away = is_front_layer(i) ? v.fused_front : op.fused_away;   // the layers a fused kernel covers in this view
             if (post && op.kind != OP_NMS && op.kind != OP_LIGHT && op.kind != OP_SCAN) continue;
             if (op.kind == OP_SCAN && e->emit_scan && !post) continue;   // the class-branch convs have already filled the key lists
             const bool grouped = one && op.kind == OP_CONV && op.group >= 0;
@@ -122,7 +128,16 @@ void irmv::build_step_plans(irmv_engine *e)
             // a step skips the layers a fused kernel covers; a read-back runs only those (and the unfused form of a conv that
             // normally carries a 1x1 in its epilogue)
             // (... and a box branch's first conv that the steps -- their plans are built first -- run behind the tile gate)
-            if (mat ? !(op.fused_away || op.fuse_next >= 0 || op.gated_first || ((op.bneck >= 0 || op.kpt3 >= 0) && op.kind == OP_CONV)) : op.fused_away) continue;
+            const bool skip = mat ? !(away || op.fuse_next >= 0 || op.gated_first || ((op.bneck >= 0 || op.kpt3 >= 0) && op.kind == OP_CONV)) : away;
+            if (step && v.fused_front && i == e->front_ops[2]) {   // preprocess + model.0.conv + model.1.conv as the one front launch
+                const Op &fo = e->ops[e->front_op];
+                Launch f; f.op = e->front_op;
+                f.layer = fo.layer; f.name = fo.kname;
+                f.flops = fo.flops;
+                f.bytes = fo.bytes + ((double)v.frame_bytes - (double)e->frame_bytes);   // (the op counts view 0's frame)
+                v.plans[k].push_back(f);
+            }
+            if (skip) continue;
             Launch l; l.op = i;
             // every kernel is idempotent and can be repeated inside its profile bracket -- except the light extraction and, with
             // the split scan, the scan / NMS pair (the scan appends to the frame's candidate list, the NMS kernel consumes and resets it)
@@ -149,9 +164,10 @@ void irmv::build_step_plans(irmv_engine *e)
                 l.flops = op.flops + (nx ? nx->flops : 0.0);
                 l.launch_bytes = op.w_bytes + (nx ? nx->w_bytes : 0.0);
                 l.bytes = op.bytes + (nx ? nx->out_bytes - op.out_bytes + nx->w_bytes : 0.0) - l.launch_bytes;
+                if (op.kind == OP_PRE) l.bytes += (double)v.frame_bytes - (double)e->frame_bytes;   // (the op counts view 0's frame)
             }
-            e->plans[k].push_back(l);
+            v.plans[k].push_back(l);
         }
-        if (step && e->sparse_head) sparse_head_plan(e, e->plans[k]);
+        if (step && e->sparse_head) sparse_head_plan(e, v.plans[k]);
     }
 }

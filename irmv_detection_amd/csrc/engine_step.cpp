@@ -49,21 +49,31 @@ void irmv::fill_conv_args(const irmv_engine *e, const Op &op, int first, int cou
     if (op.w_k16) a.w2 = op.w_k16;   // a Cin = 16 final as its own launch (k_conv.hip conv1x1_k16_f32_kernel)
 }
 
-LightArgs irmv::light_args(const irmv_engine *e, int first)
+// All slots of a step are in one view: *view = that of [first, first + count), or IRMV_ERR_ARG naming the first two that differ.
+int irmv::slots_view(const irmv_engine *e, int first, int count, int *view)
+{
+    if (view) *view = e->slot_view[first];
+    for (int s = first + 1; s < first + count; s++)
+        if (e->slot_view[s] != e->slot_view[first])
+            return fail(IRMV_ERR_ARG, "slots " + std::to_string(first) + " and " + std::to_string(s) + " are in different views (irmv_engine_set_view): one step runs one view");
+    return IRMV_OK;
+}
+
+LightArgs irmv::light_args(const irmv_engine *e, const View &v, int first)
 {
     LightArgs a{};
     const irmv_engine_cfg &c = e->cfg;
-    a.frames = e->src_dev + (size_t)first * e->frame_bytes;
-    a.frame_bytes = e->frame_bytes;
-    a.cols = c.src_width; a.rows = c.src_height; a.rotate180 = c.rotate180;
+    a.frames = v.frames + (size_t)first * v.frame_bytes;
+    a.frame_bytes = v.frame_bytes;
+    a.cols = v.src_w; a.rows = v.src_h; a.rotate180 = c.rotate180;
     a.dets = e->dets_dev + (size_t)first * c.max_det;
     a.max_det = c.max_det;
     a.num_dets = reinterpret_cast<const int *>(e->fout_dev + first);
     a.num_dets_stride = (int)(sizeof(DevFrameOut) / sizeof(int));
     a.n_boxes = 0;
     a.boxes = nullptr;
-    a.labels = e->light_labels + (size_t)first * e->light_pool;
-    a.label_pool = e->light_pool;
+    a.labels = v.light_labels + (size_t)first * v.light_pool;
+    a.label_pool = v.light_pool;
     a.points = e->light_points + (size_t)first * c.max_det * kLightPointsCap * 2;
     a.points_cap = kLightPointsCap;
     a.hulls = e->light_hulls + (size_t)first * c.max_det * kLightPointsCap * 4;
@@ -90,9 +100,10 @@ static void launch_bayer(const irmv_engine *e, int first, int count, hipStream_t
     else launch_demosaic(bayer_args(e, first), count, s);
 }
 
-PostArgs irmv::post_args(const irmv_engine *e, int first)
+PostArgs irmv::post_args(const irmv_engine *e, const View &v, int first)
 {
     PostArgs p = e->post;
+    p.scale_x = v.scale_x; p.scale_y = v.scale_y; p.off_x = v.off_x; p.off_y = v.off_y;
     p.head_all = e->head_all;
     p.slots_total = e->cfg.num_slots;
     p.first = first;
@@ -121,32 +132,32 @@ static CropArgs crop_args(const irmv_engine *e, int first, bool pinned)
 
 static void launch_crop(const irmv_engine *e, int first, int count, bool pinned, hipStream_t s) { launch_window_crop(crop_args(e, first, pinned), count, s); }
 
-static PreArgs pre_args(const irmv_engine *e, const Op &op, int first)
+static PreArgs pre_args(const irmv_engine *e, const View &v, const Op &op, int first)
 {
     PreArgs a;
-    a.src = e->src_dev + (size_t)first * e->frame_bytes;
+    a.src = v.frames + (size_t)first * v.frame_bytes;
     a.dst = static_cast<half_t *>(e->tensors[op.out_t].slot(first));
-    a.tx = e->tap_x; a.ty = e->tap_y;
-    a.sw = e->cfg.src_width; a.sh = e->cfg.src_height; a.net_w = e->cfg.net_size; a.net_h = e->cfg.net_height; a.swap_rb = e->cfg.swap_rb;
-    a.src_slot_bytes = e->frame_bytes;
+    a.tx = v.tap_x; a.ty = v.tap_y;
+    a.sw = v.src_w; a.sh = v.src_h; a.net_w = e->cfg.net_size; a.net_h = e->cfg.net_height; a.swap_rb = e->cfg.swap_rb;
+    a.src_slot_bytes = v.frame_bytes;
     return a;
 }
 
-static FrontArgs front_args(const irmv_engine *e, const Op &op, int first)
+static FrontArgs front_args(const irmv_engine *e, const View &v, const Op &op, int first)
 {
     FrontArgs a;
-    a.src = e->src_dev + (size_t)first * e->frame_bytes;
-    a.src_slot_bytes = e->frame_bytes;
-    a.tx = e->tap_x; a.ty = e->tap_y;
-    a.vx0 = e->front.box[0]; a.vx1 = e->front.box[1]; a.vy0 = e->front.box[2]; a.vy1 = e->front.box[3];
-    a.sw = e->cfg.src_width; a.sh = e->cfg.src_height; a.net_w = e->cfg.net_size; a.net_h = e->cfg.net_height; a.swap_rb = e->cfg.swap_rb;
-    a.fastx = e->front.fastx; a.fx_i0 = e->front.fx_i0; a.fx_step = e->front.fx_step;
+    a.src = v.frames + (size_t)first * v.frame_bytes;
+    a.src_slot_bytes = v.frame_bytes;
+    a.tx = v.tap_x; a.ty = v.tap_y;
+    a.vx0 = v.front.box[0]; a.vx1 = v.front.box[1]; a.vy0 = v.front.box[2]; a.vy1 = v.front.box[3];
+    a.sw = v.src_w; a.sh = v.src_h; a.net_w = e->cfg.net_size; a.net_h = e->cfg.net_height; a.swap_rb = e->cfg.swap_rb;
+    a.fastx = v.front.fastx; a.fx_i0 = v.front.fx_i0; a.fx_step = v.front.fx_step;
     a.w0 = e->conv0_w; a.b0 = e->conv0_b;
     a.w1 = op.w_packed; a.b1 = op.bias;
     const Tensor &ot = e->tensors[op.out_t];
     a.out = static_cast<half_t *>(ot.slot(first));
     a.out_ld = ot.C;
-    a.tiles_x = e->front.tiles_x; a.tiles_y = e->front.tiles_y; a.tile_y = e->front.tile_y; a.stage_bytes = e->front.stage_bytes;
+    a.tiles_x = v.front.tiles_x; a.tiles_y = v.front.tiles_y; a.tile_y = v.front.tile_y; a.stage_bytes = v.front.stage_bytes;
     return a;
 }
 
@@ -285,16 +296,16 @@ bool irmv::launch_head_group(const irmv_engine *e, const irmv_engine::HeadGroup 
 
 // ---- step execution ------------------------------------------------------------
 // The one place an op reaches the GPU: the kernel of l.op's kind on slots [first, first + count), stream s, as launch l of a
-// plan says (irmv_engine_run_op: a plain Launch of the op).  scan: the members of l that append scan candidates to pa's key
+// plan of view v says (irmv_engine_run_op: a plain Launch of the op).  scan: the members of l that append scan candidates to pa's key
 // lists (bit k: member k of a group, bit 0: a lone conv); crop_pinned: OP_CROP reads the pinned slots.
-int irmv::launch_op(irmv_engine *e, const Launch &l, int first, int count, const PostArgs &pa, unsigned scan, bool crop_pinned, hipStream_t s)
+int irmv::launch_op(irmv_engine *e, const View &v, const Launch &l, int first, int count, const PostArgs &pa, unsigned scan, bool crop_pinned, hipStream_t s)
 {
     const Op &op = e->ops[l.op];
     switch (op.kind) {
     case OP_DEMOSAIC: launch_bayer(e, first, count, s); break;
     case OP_CROP: launch_crop(e, first, count, crop_pinned, s); break;
-    case OP_PRE: launch_preprocess(pre_args(e, op, first), count, s); break;
-    case OP_FRONT: if (!launch_front(front_args(e, op, first), count, s)) return fail(IRMV_ERR_HIP, "fused front kernel: LDS request refused"); break;
+    case OP_PRE: launch_preprocess(pre_args(e, v, op, first), count, s); break;
+    case OP_FRONT: if (!launch_front(front_args(e, v, op, first), count, s)) return fail(IRMV_ERR_HIP, "fused front kernel: LDS request refused"); break;
     case OP_C2F2: launch_c2f2(c2f2_args(e, op, first), count, s); break;
     case OP_C2F32: if (!launch_c2f32(op.mode, op.shortcut, c2f32_args(e, op, first, count), count, s)) return fail(IRMV_ERR_ARG, "no fused C2f kernel for " + op.layer); break;
     case OP_BNECK:   // (cv2's k-steps where the launch carries it)
@@ -319,19 +330,21 @@ int irmv::launch_op(irmv_engine *e, const Launch &l, int first, int count, const
     }
     case OP_SCAN: launch_scan_decode(pa, count, s); break;
     case OP_NMS: { PostArgs pn = pa; pn.keys_only = l.keys_only ? 1 : 0; launch_nms_pnp(pn, count, s); break; }
-    case OP_LIGHT: launch_light_extract(light_args(e, first), e->cfg.max_det, count, s); break;
+    case OP_LIGHT: launch_light_extract(light_args(e, v, first), e->cfg.max_det, count, s); break;
     }
     HIP_TRY(hipGetLastError());
     return IRMV_OK;
 }
 
-// Enqueue a step of kind `kind` on slots [first, first + count), stream s: the launches of e->plans[kind], in order.
+// Enqueue a step of kind `kind` on slots [first, first + count), stream s: the launches of that kind's plan in the slots' view
+// (the caller has made sure they share one), in order.
 // ev != nullptr (irmv_engine_profile's events): launch i of the plan is repeated `reps` times (once if it is `once`) between
 // (*ev)[2 i] and (*ev)[2 i + 1].
 int irmv::enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipStream_t s, int reps, const std::vector<hipEvent_t> *ev, bool crop_pinned)
 {
-    const std::vector<Launch> &plan = e->plans[kind];
-    const PostArgs pa = post_args(e, first);
+    const View &v = view_of(e, first);
+    const std::vector<Launch> &plan = v.plans[kind];
+    const PostArgs pa = post_args(e, v, first);
     PostArgs mute = pa;   // (a threshold no logit passes: no key, no bit)
     mute.logit_thr = INFINITY;
     for (size_t i = 0; i < plan.size(); i++) {
@@ -342,7 +355,7 @@ int irmv::enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipS
             // a profiled launch is repeated: only its last repetition appends candidates.  With the sparse head the other
             // repetitions still run the step's kernel -- no class store --, behind the mute threshold.
             const bool last = rep == n - 1, muted = !last && l.scan && e->sparse_head;
-            TRY(launch_op(e, l, first, count, muted ? mute : pa, last || muted ? l.scan : 0u, crop_pinned, s));
+            TRY(launch_op(e, v, l, first, count, muted ? mute : pa, last || muted ? l.scan : 0u, crop_pinned, s));
         }
         if (ev) HIP_TRY(hipEventRecord((*ev)[2 * i + 1], s));
     }
@@ -350,21 +363,26 @@ int irmv::enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipS
 }
 
 // Slots [first, first + count) have just been stepped: their heads hold the rows, and their gated tensors the tiles, of that
-// step's candidates only (sparse head / branch), and their results are shifted by the windows' corners as they are now.
+// step's candidates only (sparse head / branch), and their results are shifted by the windows' corners as they are now -- or,
+// stepped in the frame view, by nothing.
 void irmv::mark_stepped(irmv_engine *e, int first, int count)
 {
     if (e->sparse_head) std::fill(e->head_stale.begin() + first, e->head_stale.begin() + first + count, 1);
     if (e->sparse_branch) std::fill(e->branch_stale.begin() + first, e->branch_stale.begin() + first + count, 1);
-    if (e->window) std::copy(e->win_org.begin() + first, e->win_org.begin() + first + count, e->sub_org.begin() + first);
+    if (e->window) {
+        std::copy(e->win_org.begin() + first, e->win_org.begin() + first + count, e->sub_org.begin() + first);
+        std::copy(e->slot_view.begin() + first, e->slot_view.begin() + first + count, e->sub_view.begin() + first);
+    }
 }
 
 // Frame upload and result download: plain async copies, pinned memory both ways, on the streams submit_group() picks.
 // bands (never inside a stream capture, whose copy parameters are baked): an HWC window engine moves, for groups of up to 8
 // slots, only the band of full-width rows each slot's window covers -- one 1-D copy per slot, to the same offset of its device frame.
+// Slots in the frame view move whole frames.
 constexpr int kBandUploadMaxSlots = 8;
 static int copy_in(irmv_engine *e, int first, int count, hipStream_t st, bool bands = false)
 {
-    if (bands && e->window && !e->raw_dev && count <= kBandUploadMaxSlots) {
+    if (bands && view_of(e, first).crop && !e->raw_dev && count <= kBandUploadMaxSlots) {
         const size_t pitch = (size_t)e->full_w * 3, len = (size_t)e->cfg.src_height * pitch;
         for (int s = first; s < first + count; s++) {
             const int by0 = e->cfg.rotate180 ? e->full_h - e->win_org[s].y - e->cfg.src_height : e->win_org[s].y;
@@ -389,14 +407,14 @@ static bool upload_as_kernel(const irmv_engine *e, int first, int count)
 // section 9.)
 // An HWC window engine's synchronous step of one or two slots uploads nothing: its crop reads the window out of the pinned
 // slots (crop_from_pinned), so only the window crosses PCIe.  `captured`: the copy becomes a graph node (whole frames).
-static bool crop_from_pinned(const irmv_engine *e, int count)
+static bool crop_from_pinned(const irmv_engine *e, int first, int count)
 {
-    return e->window && !e->raw_dev && e->sw.window_upload && count <= 2 && e->sw.upload_kernel_blocks > 0 && e->src_host_dev;
+    return view_of(e, first).crop && !e->raw_dev && e->sw.window_upload && count <= 2 && e->sw.upload_kernel_blocks > 0 && e->src_host_dev;
 }
 
 static int upload_sync(irmv_engine *e, int first, int count, hipStream_t st, bool captured)
 {
-    if (crop_from_pinned(e, count)) return IRMV_OK;
+    if (crop_from_pinned(e, first, count)) return IRMV_OK;
     if (!upload_as_kernel(e, first, count)) return copy_in(e, first, count, st, !captured);
     const size_t off = (size_t)first * e->src_bytes;
     launch_upload_frames(e->src_host_dev + off, upload_dev(e) + off, e->src_bytes * count, e->sw.upload_kernel_blocks, st);
@@ -423,7 +441,7 @@ int irmv::check_range(const irmv_engine *e, int first, int count)
 
 static int get_graph(irmv_engine *e, StepKind kind, int first, int count, bool upload, hipGraphExec_t *out)
 {
-    const GraphKey key{first, count, kind, upload};
+    const GraphKey key{first, count, kind, upload, e->slot_view[first]};
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) { *out = it->second; return IRMV_OK; }
     hipGraph_t g = nullptr;
@@ -431,7 +449,7 @@ static int get_graph(irmv_engine *e, StepKind kind, int first, int count, bool u
     int rc = IRMV_OK;
     if (upload)   // the frames' upload as the graph's first node (synchronous single-stream submits): one or two frames as a kernel
         rc = upload_sync(e, first, count, e->stream, true);
-    if (!rc) rc = enqueue_step(e, kind, first, count, e->stream, 1, nullptr, upload && crop_from_pinned(e, count));
+    if (!rc) rc = enqueue_step(e, kind, first, count, e->stream, 1, nullptr, upload && crop_from_pinned(e, first, count));
     hipError_t ce = hipStreamEndCapture(e->stream, &g);
     if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
     if (ce != hipSuccess) return fail(IRMV_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
@@ -480,7 +498,7 @@ static int submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_
     // replay spends ~10 us of host work before its first packet reaches the GPU, a direct launch ~4; with the 70 us upload in
     // front the host stays far ahead of the GPU: 0.339 -> 0.331 ms per 1280 x 1024 frame).  Every other step is a graph replay.
     const bool eager = e->sync_launch == 1 && c == 1 && (flags & IRMV_SUBMIT_H2D) && !async_up;
-    const bool pinned = (flags & IRMV_SUBMIT_H2D) && !async_up && crop_from_pinned(e, c);   // (no upload at all: nothing to keep out of the graph)
+    const bool pinned = (flags & IRMV_SUBMIT_H2D) && !async_up && crop_from_pinned(e, f, c);   // (no upload at all: nothing to keep out of the graph)
     const bool graph_up = (flags & IRMV_SUBMIT_H2D) && !async_up && (e->sw.graph_upload || pinned) && !eager;
     const StepKind kind = c == 1 ? STEP_ONE : STEP_BATCH;
     hipGraphExec_t ge = nullptr;
@@ -524,6 +542,7 @@ static int submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_
 extern "C" int irmv_engine_submit(irmv_engine *e, int first, int count, uint32_t flags)
 {
     TRY(check_range(e, first, count));
+    TRY(slots_view(e, first, count));   // (before anything is enqueued)
     HIP_TRY(hipSetDevice(e->cfg.device));
     // A multi-slot step is cut into num_streams independent sub-batches, one captured graph each, on
     // separate streams: while one sub-batch sits in a launch gap or a kernel tail the other keeps the
@@ -548,6 +567,7 @@ extern "C" int irmv_engine_submit(irmv_engine *e, int first, int count, uint32_t
 extern "C" int irmv_engine_run_post(irmv_engine *e, int first, int count)
 {
     TRY(check_range(e, first, count));
+    TRY(slots_view(e, first, count));
     HIP_TRY(hipSetDevice(e->cfg.device));
     TRY(irmv_engine_wait(e));
     for (int s = first; s < first + count; s++) TRY(ensure_dense_head(e, s));   // (scan_decode_kernel reads every anchor's class logits)
@@ -597,13 +617,13 @@ extern "C" int irmv_engine_wait_upload(irmv_engine *e, int first, int count) { r
 // Other slots may stay in flight (the consumer side of the TripleBuffer: take the newest finished slot while the next one runs).
 extern "C" int irmv_engine_wait_slots(irmv_engine *e, int first, int count) { return wait_owners(e, first, count, false); }
 
-// The pose part of a result record: keypoints (a window engine's shifted by the corner ox, oy), PnP, and the classical
+// The pose part of a result record: keypoints (shift: a window's, moved by the corner ox, oy), PnP, and the classical
 // extraction's fields.
-void irmv::det_pose(const irmv_engine *e, const DevDet &d, float ox, float oy, irmv_det &o)
+void irmv::det_pose(const DevDet &d, bool shift, float ox, float oy, irmv_det &o)
 {
     o.pnp_ok = d.pnp_ok;
     memcpy(o.kpts, d.kpts, 32);
-    if (e->window)
+    if (shift)
         for (int j = 0; j < 8; j++) o.kpts[j] += (j & 1) ? oy : ox;
     memcpy(o.rvec, d.rvec, 24);
     memcpy(o.tvec, d.tvec, 24);
@@ -620,8 +640,10 @@ extern "C" int irmv_engine_results(irmv_engine *e, int slot, irmv_det *out, int 
     const DevFrameOut &fo = e->fout_host[slot];
     const int k = std::min(fo.num_dets, cap);
     const DevDet *d = e->dets_host + (size_t)slot * e->cfg.max_det;
-    // device records are window-local: the corner the slot was submitted with brings them to full-frame coordinates
-    const float ox = e->window ? (float)e->sub_org[slot].x : 0.f, oy = e->window ? (float)e->sub_org[slot].y : 0.f;
+    // device records of a step in the window view are window-local: the corner the slot was submitted with brings them to
+    // full-frame coordinates (a step in the frame view: nothing to add)
+    const bool shift = e->window && e->sub_view[slot] == IRMV_VIEW_WINDOW;
+    const float ox = shift ? (float)e->sub_org[slot].x : 0.f, oy = shift ? (float)e->sub_org[slot].y : 0.f;
     for (int i = 0; i < k; i++) {
         irmv_det &o = out[i];
         memcpy(o.xyxy, d[i].xyxy, 16);
@@ -629,9 +651,9 @@ extern "C" int irmv_engine_results(irmv_engine *e, int slot, irmv_det *out, int 
         // magic_enum::enum_cast<ArmorClass>(label).value_or(UNKNOWN), src/yolo_engine.cpp:216
         o.class_id = (d[i].cls >= 0 && d[i].cls < IRMV_NUM_CLASSES) ? d[i].cls : IRMV_NUM_CLASSES;
         o.anchor = d[i].anchor;
-        det_pose(e, d[i], ox, oy, o);
+        det_pose(d[i], shift, ox, oy, o);
         o.reserved = 0;
-        if (e->window)
+        if (shift)
             for (int j = 0; j < 4; j++) o.xyxy[j] += (j & 1) ? oy : ox;
     }
     *n = k;
@@ -651,8 +673,9 @@ extern "C" int irmv_engine_detect(irmv_engine *e, int slot, irmv_det *out, int c
 
 extern "C" double irmv_engine_last_detect_ms(const irmv_engine *e) { return e ? e->last_detect_ms : 0.0; }
 
-// The slot's pinned frame -> its HWC device frame (src_dev) on stream st, outside a step: an HWC engine copies it there, a
-// Bayer engine copies the raw frame to its device raw slot and demosaics it; a window engine then cuts the slot's window out.
+// The slot's pinned frame -> the HWC device frame of its view on stream st, outside a step: an HWC engine copies it there, a
+// Bayer engine copies the raw frame to its device raw slot and demosaics it; in the window view of a window engine the slot's
+// window is then cut out.
 int irmv::load_frame(irmv_engine *e, int slot, hipStream_t st)
 {
     TRY(copy_in(e, slot, 1, st, true));
@@ -660,7 +683,7 @@ int irmv::load_frame(irmv_engine *e, int slot, hipStream_t st)
         launch_bayer(e, slot, 1, st);
         HIP_TRY(hipGetLastError());
     }
-    if (e->window) {
+    if (view_of(e, slot).crop) {
         launch_crop(e, slot, 1, false, st);
         HIP_TRY(hipGetLastError());
     }

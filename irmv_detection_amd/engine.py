@@ -96,7 +96,9 @@ class YoloEngine:
     640 x 512 for a 1280 x 1024 camera); `net_width` / `net_height` hold the engine's dimensions.
     `window` = (w, h): a tracking window -- every step runs on a w x h crop of the frame at the sensor's resolution;
     `src_image_size` stays the full frame the producer writes, detections come back in full-frame coordinates, and
-    `set_window` / `set_window_center` move a slot's window between steps (irmv_detection_amd.window is the host reference).
+    `set_window` / `set_window_center` move a slot's window between steps (irmv_detection_amd.window is the host reference);
+    `set_view("frame")` runs a slot's next steps on the whole frame instead (the search after a lost target), `set_view("window")`
+    goes back -- one engine, nothing uploaded or tuned twice.
     """
 
     def __init__(self, onnx_file_path: Optional[str], src_image_size: Tuple[int, int] = (1280, 1024),
@@ -221,9 +223,10 @@ class YoloEngine:
 
     def get_rotated_image(self, slot: Optional[int] = None) -> np.ndarray:
         """The 180-degree rotated frame (yolo_engine.hpp:34); HWC in every source format (a Bayer engine's demosaiced frame).
-        A window engine returns the slot's rotated window, [win_h, win_w, 3]."""
+        A window engine returns the slot's rotated window, [win_h, win_w, 3] -- the whole rotated frame for a slot in the
+        frame view."""
         slot = self.slot if slot is None else slot
-        w, h = self.window_size or self.src_image_size
+        w, h = self.view(slot)[1] if self.window_size else self.src_image_size
         out = np.empty((h, w, 3), np.uint8)
         capi.check(self._L.irmv_engine_rotated_image(self._h, slot, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
@@ -251,6 +254,26 @@ class YoloEngine:
         v = [C.c_int(0) for _ in range(4)]
         capi.check(self._L.irmv_engine_get_window(self._h, slot, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+    def set_view(self, view: str, slot: Optional[int] = None) -> None:
+        """"frame": the slot's next steps run on the whole frame, as a plain engine of the full size would (no crop, no
+        offset, the configured camera); "window": on its window again.  Waits for the slot's last submitted step; the first
+        "frame" of an engine also builds that view (call it once at start-up).  All slots of one submit share a view."""
+        if view not in capi.VIEWS:
+            raise ValueError(f"view must be one of {sorted(capi.VIEWS)}, not {view!r}")
+        slot = self.slot if slot is None else slot
+        capi.check(self._L.irmv_engine_set_view(self._h, slot, capi.VIEWS[view]))
+
+    def view(self, slot: Optional[int] = None) -> Tuple[str, Tuple[int, int]]:
+        """(name, (w, h)): the slot's view and the source frame its steps see -- the window's size, or the full frame's."""
+        slot = self.slot if slot is None else slot
+        v, w, h = C.c_int(0), C.c_int(0), C.c_int(0)
+        capi.check(self._L.irmv_engine_get_view(self._h, slot, C.byref(v), C.byref(w), C.byref(h)))
+        return ("frame" if v.value == capi.VIEW_FRAME else "window"), (w.value, h.value)
+
+    def debug_graph_count(self) -> int:
+        """Test hook: the captured graphs the engine holds."""
+        return int(self._L.irmv_engine_debug_graph_count(self._h))
 
     def set_bayer_isp(self, gains: Sequence[int], lut=None) -> None:
         """Gains (R, G, B; Q8, 256 = 1.0) and tone LUT (uint8 [3][256], rows R, G, B, or [256] for all three; None = identity)
