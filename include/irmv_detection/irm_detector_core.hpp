@@ -88,6 +88,9 @@ public:
                                                          // height 0: square of the width (1280 x 1024 camera: 640 x 512)
     cv::Size window_size{0, 0};                          // tracking window of the three engines (YoloEngine's `window`); 0: none.  No policy here:
                                                          // the caller moves each engine's window (engine(id).set_window_center(...))
+    int enemy_color = -1;                                // the node's enemy_color (:154-160, "0 for blue, 1 for red"): 0 keeps B1..BS, 1 keeps R1..RS,
+                                                         // on the GPU where candidates are emitted; -1: no filter (what the reference's unused parameter amounts to)
+    std::vector<int> large_plate_classes;                // ArmorClass values whose detections PnP solves with the 225 mm plate; the rest: 135 mm
   };
 
   // What one frame produced, beyond the message: kept for debug publishers and tests.
@@ -109,6 +112,7 @@ public:
                                        IRMV_SRC_HWC8, std::array<uint16_t, 3>{256, 256, 256}, p.net_input_size.height > 0 ? p.net_input_size.height : -1,
                                        IRMV_DEMOSAIC_BILINEAR, p.window_size);
       push_params(*e);
+      if (p.enemy_color != -1 || !p.large_plate_classes.empty()) push_class_policy(*e);
     }
     yolo_engines_[0]->warm_up();   // the tile choices are shared by the three engines: one warm-up tunes for all
     for (size_t i = 1; i < yolo_engines_.size(); i++) yolo_engines_[i]->warm_up();
@@ -186,6 +190,13 @@ public:
     else if (name == "armor.max_small_center_distance") params_.armor_max_small_center_distance = value;
     else if (name == "armor.min_large_center_distance") params_.armor_min_large_center_distance = value;
     else if (name == "armor.max_large_center_distance") params_.armor_max_large_center_distance = value;
+    else if (name == "enemy_color") {                      // :384-385; live, and re-captures nothing
+      const int c = int(value);
+      if (c < -1 || c > 1) return false;
+      params_.enemy_color = c;
+      for (auto & e : yolo_engines_) e->set_enemy_color(c);   // (thresholds and plates set on an engine(id) stay)
+      return true;
+    }
     else return false;
     for (auto & e : yolo_engines_) push_params(*e);
     return true;
@@ -199,6 +210,16 @@ private:
     e.set_extract_params(params_.binary_threshold, float(params_.light_min_ratio), float(params_.light_max_ratio), float(params_.light_max_angle),
                          params_.armor_min_small_center_distance, params_.armor_max_small_center_distance,
                          params_.armor_min_large_center_distance, params_.armor_max_large_center_distance);
+  }
+
+  // enemy_color and large_plate_classes -> the engine's class policy, built once and uploaded once.  Nothing is sent while
+  // both are at their defaults.
+  void push_class_policy(YoloEngine & e) const
+  {
+    irmv_class_policy p = e.user_class_policy();
+    for (int c : params_.large_plate_classes)
+      if (c >= 0 && c < 16) p.plate[c] = IRMV_ARMOR_LARGE;
+    e.set_class_policy(p, params_.enemy_color);
   }
 
   Params params_;

@@ -106,6 +106,8 @@ public:
     src_image_buffer_ = irmv_engine_src_buffer(engine_, 0);
     rotated_ = has_window() ? cv::Mat(window.height, window.width, CV_8UC3) : cv::Mat(src_image_size.height, src_image_size.width, CV_8UC3);
     dets_.resize(static_cast<size_t>(irmv_engine_max_det(engine_)));
+    irmv_engine_get_class_policy(engine_, &base_policy_);   // the uniform policy of the engine's score threshold and plate
+    user_policy_ = base_policy_;
     if (warm_up_now) warm_up();
   }
 
@@ -143,6 +145,32 @@ public:
     if (irmv_engine_set_bayer_isp(engine_, gain_q8.data(), lut) != IRMV_OK)
       throw std::runtime_error(std::string("YoloEngine::set_bayer_isp: ") + irmv_last_error());
     rotated_valid_ = false;
+  }
+
+  // ---- class policy: per-class score thresholds, colour mask, plate size (include/irmv_hip.h, irmv_class_policy) ----
+  // Two things the caller sets independently, one table in the engine: the caller's policy (score_thr[c] >= 1 switches
+  // class c off where candidates are emitted; plate[c] is IRMV_ARMOR_SMALL / _LARGE, the object points PnP uses for a
+  // detection of class c) and the enemy colour, which switches the own colour's classes off on top of it.  Every call here
+  // waits for the steps in flight, uploads the table ONCE, holds from the next detect() on and re-captures nothing.  A
+  // refused argument throws and leaves both as they were.
+  void set_class_policy(const irmv_class_policy & p) { apply_class_policy(p, enemy_color_, "YoloEngine::set_class_policy: "); }
+  // ... and the colour in the same upload
+  void set_class_policy(const irmv_class_policy & p, int enemy_color) { apply_class_policy(p, enemy_color, "YoloEngine::set_class_policy: "); }
+  // The reference node's enemy_color ("0 for blue, 1 for red", src/irm_detector.cpp:154-160; declared there, never used):
+  // 0 = the enemy is blue, B1..BS stay on and R1..RS are off; 1 = the enemy is red; -1 = no filter.  The caller's thresholds
+  // and plates stay: a class with its own threshold keeps it whenever its colour is on.
+  void set_enemy_color(int enemy_color) { apply_class_policy(user_policy_, enemy_color, "YoloEngine::set_enemy_color: "); }
+  // Back to the engine's one score threshold and one plate model for every class, and no colour filter.
+  void reset_class_policy() { apply_class_policy(base_policy_, -1, "YoloEngine::reset_class_policy: "); }
+  // The caller's policy (without the colour mask) and the colour; class_policy() is what the engine holds: both combined.
+  const irmv_class_policy & user_class_policy() const { return user_policy_; }
+  int enemy_color() const { return enemy_color_; }
+  irmv_class_policy class_policy() const
+  {
+    irmv_class_policy p;
+    if (irmv_engine_get_class_policy(engine_, &p) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::class_policy: ") + irmv_last_error());
+    return p;
   }
 
   // ---- tracking window ----
@@ -336,6 +364,21 @@ private:
   }
 
   irmv_engine * engine_ = nullptr;
+  // caller's policy + colour -> one table upload; on a refusal nothing is stored
+  void apply_class_policy(const irmv_class_policy & p, int enemy_color, const char * who)
+  {
+    irmv_class_policy mask, eff = p;
+    if (irmv_class_policy_enemy(enemy_color, 0.5f, IRMV_ARMOR_SMALL, &mask) != IRMV_OK) throw std::runtime_error(std::string(who) + irmv_last_error());
+    for (int c = 0; c < 16; c++)
+      if (mask.score_thr[c] >= 1.f) eff.score_thr[c] = 1.f;   // the own colour's classes, as irmv_class_policy_enemy names them
+    if (irmv_engine_set_class_policy(engine_, &eff) != IRMV_OK) throw std::runtime_error(std::string(who) + irmv_last_error());
+    user_policy_ = p;
+    enemy_color_ = enemy_color;
+  }
+
+  irmv_class_policy base_policy_{};   // the uniform policy the engine was created with
+  irmv_class_policy user_policy_{};   // the caller's thresholds and plates, without the colour mask
+  int enemy_color_ = -1;
   cv::Size src_image_size_;
   cv::Size window_size_;
   bool enable_profiling_ = false;

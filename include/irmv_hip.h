@@ -183,7 +183,7 @@ typedef struct irmv_det {
  * src/yolo_engine.cpp:53-57,82-85).  Arrays hold max_det entries. */
 typedef struct irmv_raw_dets {
     int32_t num_dets;
-    int32_t n_candidates;  /* (anchor, class) pairs above score_thr before any cap */
+    int32_t n_candidates;  /* (anchor, class) pairs above their class's score threshold (irmv_class_policy; cfg.score_thr) before any cap */
     float *det_boxes;      /* [max_det][4] xyxy, net-input pixels */
     float *det_scores;     /* [max_det] */
     int32_t *det_classes;  /* [max_det] */
@@ -331,6 +331,42 @@ int irmv_engine_rotated_image(irmv_engine *e, int slot, uint8_t *dst_hwc);
 int irmv_engine_set_bayer_isp(irmv_engine *e, const uint16_t gain_q8[3], const uint8_t *lut);
 /* The current gains and LUT (either pointer may be NULL); the LUT of an engine that has none set is the identity. */
 int irmv_engine_get_bayer_isp(const irmv_engine *e, uint16_t gain_q8[3], uint8_t *lut);
+
+/* ---- class policy: per-class score thresholds, colour mask, plate size ------------------------------------------------
+ * One score threshold and one plate model per class, in a small table in device memory that every kernel deciding "is this
+ * (anchor, class) pair a candidate" reads when it runs, as does the place that picks PnP's object points.  A class that is
+ * off is off where candidates are emitted: it sets no candidate bit, appends no key and is not counted, so nothing behind
+ * the class carriers (head rows, the gated box and keypoint launches, the NMS walk) does any work for it.
+ * irmv_raw_dets.n_candidates counts the pairs that pass their own class's threshold; pre_nms_cap, max_det and NMS act on
+ * that list as they always did.  An engine on which irmv_engine_set_class_policy is never called runs the uniform policy of
+ * cfg.score_thr / cfg.armor_size: the same float compared with the same float, the same plate.
+ * irmv_detection_amd/class_policy.py is the host reference. */
+typedef struct irmv_class_policy {
+    uint32_t struct_size;    /* = sizeof(irmv_class_policy) */
+    float    score_thr[16];  /* class c < nc: in (0,1) -> (anchor, c) is a candidate iff logit > float32(log(t/(1-t))),
+                                evaluated in double on the float32 t -- the arithmetic cfg.score_thr gets;
+                                >= 1: the class is off (threshold +inf).  <= 0 or NaN: IRMV_ERR_ARG.  Entries >= nc ignored */
+    uint8_t  plate[16];      /* IRMV_ARMOR_SMALL / _LARGE: object points PnP uses for a detection of class c (keypoint head, and
+                                the classical extraction of a step's detections; irmv_engine_extract_armors on explicit
+                                boxes has no class and keeps cfg.armor_size).  irmv_det.armor_size of the keypoint path
+                                reports it; the classical path's stays the size the light gates classify */
+} irmv_class_policy;
+/* Waits for every step in flight on every stream of the engine, then writes the table with a small synchronous copy: the new
+ * policy holds from the next submit.  No captured graph changes: the graphs hold the table's address, never its contents.
+ * p == NULL: back to cfg.score_thr / cfg.armor_size for every class.  IRMV_ERR_ARG (null engine, wrong struct_size, a
+ * threshold <= 0 or NaN, a plate other than IRMV_ARMOR_SMALL / _LARGE) leaves policy and engine as they were. */
+int irmv_engine_set_class_policy(irmv_engine *e, const irmv_class_policy *p);
+int irmv_engine_get_class_policy(const irmv_engine *e, irmv_class_policy *out);
+/* Host only, no GPU touched.  _uniform: every class at score_thr (> 0; >= 1: off) with plate armor_size.
+ * _enemy: the reference node's enemy_color ("0 for blue, 1 for red", src/irm_detector.cpp:154-160), which it declares and
+ * never uses: 0 = the enemy is blue -> B1..BS (classes 0..6) on at score_thr, R1..RS (7..13) off; 1 = the enemy is red ->
+ * the reverse; -1 = both on (= _uniform).  Classes 14 and 15 stay on. */
+int irmv_class_policy_uniform(float score_thr, int armor_size, irmv_class_policy *out);
+int irmv_class_policy_enemy(int enemy_color, float score_thr, int armor_size, irmv_class_policy *out);
+/* The table the engine uploads for a model of nc classes (1..16), and every check irmv_engine_set_class_policy runs -- the
+ * function the engine itself builds from, as irmv_window_map / irmv_front_plan are.  logit_thr[c] for c >= nc is +inf;
+ * *min_logit_thr = the smallest entry (+inf: every class off), the kernels' wave-uniform pre-test. */
+int irmv_class_policy_table(const irmv_class_policy *p, int nc, float logit_thr[16], float *min_logit_thr);
 
 /* IrmDetector::extract_armors(get_rotated_image(), bboxes) (src/irm_detector.cpp:183,292-355) on the GPU:
  * for each of the n boxes (xyxy, rotated-frame pixels) on the slot's current frame -> out[i].kpts (LB, LT, RT,

@@ -72,6 +72,11 @@ class RawDets(C.Structure):
     ]
 
 
+class ClassPolicy(C.Structure):
+    """irmv_class_policy (include/irmv_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("score_thr", C.c_float * 16), ("plate", C.c_uint8 * 16)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("layer", C.c_char * 32), ("flops", C.c_double),
                 ("bytes", C.c_double), ("ms", C.c_float), ("reserved", C.c_int32)]
@@ -188,6 +193,11 @@ SYMBOLS = [
     ("irmv_engine_extract_armors", C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(Det)]),
     ("irmv_engine_set_bayer_isp", C.c_int, [_P, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]),
     ("irmv_engine_get_bayer_isp", C.c_int, [_P, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]),
+    ("irmv_engine_set_class_policy", C.c_int, [_P, C.POINTER(ClassPolicy)]),
+    ("irmv_engine_get_class_policy", C.c_int, [_P, C.POINTER(ClassPolicy)]),
+    ("irmv_class_policy_uniform", C.c_int, [C.c_float, C.c_int, C.POINTER(ClassPolicy)]),
+    ("irmv_class_policy_enemy", C.c_int, [C.c_int, C.c_float, C.c_int, C.POINTER(ClassPolicy)]),
+    ("irmv_class_policy_table", C.c_int, [C.POINTER(ClassPolicy), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("irmv_engine_light_trace", C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(LightTrace), C.POINTER(Det)]),
     ("irmv_light_limits", C.c_int, [C.POINTER(C.c_int32)]),
     ("irmv_engine_read_input", C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
@@ -288,6 +298,39 @@ def light_limits() -> dict:
     v = (C.c_int32 * 4)()
     check(load().irmv_light_limits(v))
     return dict(max_contours=v[0], points_cap=v[1], lds_image=v[2], lds_points=v[3])
+
+
+def class_policy_struct(score_thr, plate) -> ClassPolicy:
+    """An irmv_class_policy from 16 thresholds and 16 plates (no check: the library's are the ones under test)."""
+    p = ClassPolicy()
+    p.struct_size = C.sizeof(ClassPolicy)
+    for c in range(16):
+        p.score_thr[c] = float(score_thr[c])
+        p.plate[c] = int(plate[c])
+    return p
+
+
+def class_policy_uniform(score_thr: float, armor_size: int = ARMOR_SMALL) -> ClassPolicy:
+    p = ClassPolicy()
+    check(load().irmv_class_policy_uniform(score_thr, armor_size, C.byref(p)))
+    return p
+
+
+def class_policy_enemy(enemy_color: int, score_thr: float, armor_size: int = ARMOR_SMALL) -> ClassPolicy:
+    """irmv_class_policy_enemy: 0 = the enemy is blue (B1..BS on, R1..RS off), 1 = red, -1 = both on."""
+    p = ClassPolicy()
+    check(load().irmv_class_policy_enemy(enemy_color, score_thr, armor_size, C.byref(p)))
+    return p
+
+
+def class_policy_table(p: ClassPolicy, nc: int):
+    """irmv_class_policy_table (host only): -> (logit_thr float32[16], min_logit_thr float32), the table an engine of nc
+    classes uploads for p."""
+    import numpy as np
+    thr = np.zeros(16, np.float32)
+    mn = C.c_float(0)
+    check(load().irmv_class_policy_table(C.byref(p), nc, thr.ctypes.data_as(C.POINTER(C.c_float)), C.byref(mn)))
+    return thr, np.float32(mn.value)
 
 
 def _geometry_cfg(src_size, net_size, net_height, resize_mode, rotate180, src_format, window) -> EngineCfg:

@@ -654,6 +654,86 @@ extern "C" int irmv_engine_set_bayer_isp(irmv_engine *e, const uint16_t gain_q8[
     return IRMV_OK;
 }
 
+// ---- class policy ----------------------------------------------------------------------
+extern "C" int irmv_class_policy_uniform(float score_thr, int armor_size, irmv_class_policy *out)
+{
+    if (!out) return fail(IRMV_ERR_ARG, "out is null");
+    if (!(score_thr > 0.f)) return fail(IRMV_ERR_ARG, "score_thr must be above 0 (>= 1: off)");
+    if (armor_size != IRMV_ARMOR_SMALL && armor_size != IRMV_ARMOR_LARGE) return fail(IRMV_ERR_ARG, "bad armor_size");
+    memset(out, 0, sizeof *out);
+    out->struct_size = sizeof *out;
+    for (int c = 0; c < 16; c++) { out->score_thr[c] = score_thr; out->plate[c] = (uint8_t)armor_size; }
+    return IRMV_OK;
+}
+
+extern "C" int irmv_class_policy_enemy(int enemy_color, float score_thr, int armor_size, irmv_class_policy *out)
+{
+    if (enemy_color < -1 || enemy_color > 1) return fail(IRMV_ERR_ARG, "enemy_color must be 0 (blue), 1 (red) or -1 (both)");
+    TRY(irmv_class_policy_uniform(score_thr, armor_size, out));
+    // ArmorClass (armor.hpp): B1..BS = 0..6, R1..RS = 7..13.  The enemy's classes stay on, the own colour's are off.
+    if (enemy_color >= 0)
+        for (int c = 0; c < 7; c++) out->score_thr[(enemy_color == 0 ? 7 : 0) + c] = 1.0f;
+    return IRMV_OK;
+}
+
+extern "C" int irmv_class_policy_table(const irmv_class_policy *p, int nc, float logit_thr[16], float *min_logit_thr)
+{
+    if (!p || !logit_thr || !min_logit_thr) return fail(IRMV_ERR_ARG, "null argument");
+    if (p->struct_size != sizeof(irmv_class_policy)) return fail(IRMV_ERR_ARG, "irmv_class_policy.struct_size mismatch");
+    if (nc < 1 || nc > 16) return fail(IRMV_ERR_ARG, "nc must be 1..16");
+    for (int c = 0; c < nc; c++) {
+        if (!(p->score_thr[c] > 0.f)) return fail(IRMV_ERR_ARG, "score_thr[" + std::to_string(c) + "] must be above 0 (>= 1: the class is off)");
+        if (p->plate[c] != IRMV_ARMOR_SMALL && p->plate[c] != IRMV_ARMOR_LARGE) return fail(IRMV_ERR_ARG, "plate[" + std::to_string(c) + "] must be IRMV_ARMOR_SMALL or IRMV_ARMOR_LARGE");
+    }
+    float mn = INFINITY;
+    for (int c = 0; c < 16; c++) {
+        const float t = c < nc ? p->score_thr[c] : 1.0f;
+        // (the arithmetic cfg.score_thr has always had: double on the float32 t, rounded once)
+        logit_thr[c] = t >= 1.f ? INFINITY : (float)std::log((double)t / (1.0 - (double)t));
+        mn = std::min(mn, logit_thr[c]);
+    }
+    *min_logit_thr = mn;
+    return IRMV_OK;
+}
+
+// e->policy -> cls_dev[0] and its mute twin.  The caller has made sure that nothing of this engine is in flight.
+int irmv::write_class_table(irmv_engine *e)
+{
+    ClassTable t[2] = {};
+    TRY(irmv_class_policy_table(&e->policy, e->nc, t[0].thr, &t[0].min_thr));
+    t[1].min_thr = INFINITY;
+    for (int c = 0; c < kMaxClasses; c++) {
+        t[0].plate[c] = t[1].plate[c] = c < e->nc ? e->policy.plate[c] : e->cfg.armor_size;
+        t[1].thr[c] = INFINITY;
+    }
+    HIP_TRY(hipMemcpy(e->cls_dev, t, sizeof t, hipMemcpyHostToDevice));
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_set_class_policy(irmv_engine *e, const irmv_class_policy *p)
+{
+    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
+    irmv_class_policy np;
+    if (p) {
+        float thr[16], mn;
+        TRY(irmv_class_policy_table(p, e->nc, thr, &mn));   // every check, before anything changes
+        np = *p;
+    } else {
+        TRY(irmv_class_policy_uniform(e->cfg.score_thr, e->cfg.armor_size, &np));
+    }
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));   // every stream of the engine: no step in flight reads the table
+    e->policy = np;
+    return write_class_table(e);
+}
+
+extern "C" int irmv_engine_get_class_policy(const irmv_engine *e, irmv_class_policy *out)
+{
+    if (!e || !out) return fail(IRMV_ERR_ARG, "engine / out is null");
+    *out = e->policy;
+    return IRMV_OK;
+}
+
 extern "C" int irmv_engine_get_bayer_isp(const irmv_engine *e, uint16_t gain_q8[3], uint8_t *lut)
 {
     if (!e) return fail(IRMV_ERR_ARG, "engine is null");

@@ -851,13 +851,16 @@ static int build_post_stage(irmv_engine *e)
 
     PostArgs &p = e->post;
     p.net_w = net_w; p.net_h = net_h; p.A = e->A; p.nc = e->nc; p.nk = e->nk;
-    p.logit_thr = (float)std::log((double)c.score_thr / (1.0 - (double)c.score_thr));
+    // class policy: uniform from cfg.score_thr / cfg.armor_size until irmv_engine_set_class_policy says otherwise
+    TRY(dev_alloc(e, (void **)&e->cls_dev, 2 * sizeof(ClassTable)));
+    if (int rc = irmv_class_policy_uniform(c.score_thr, c.armor_size, &e->policy)) return rc;
+    TRY(write_class_table(e));
+    p.cls = e->cls_dev;
     p.iou_thr = c.iou_thr;
     p.max_det = c.max_det;
     p.pre_nms_cap = c.pre_nms_cap;
     p.classwalk = e->sw.nms_classwalk ? 1 : 0;
     p.prefilter = e->sw.nms_prefilter;
-    p.armor_size = c.armor_size;
     PnpConst pc;
     pc.fx = c.camera_matrix[0]; pc.fy = c.camera_matrix[4];
     pc.cx = c.camera_matrix[2]; pc.cy = c.camera_matrix[5];

@@ -274,6 +274,11 @@ struct irmv_engine {
     int head_t[3] = {-1, -1, -1};
     float *head_all = nullptr;
     PnpConst *pnp_dev = nullptr;
+    // Class policy (irmv_engine_set_class_policy): cls_dev[0] is the table every threshold site and plate pick reads, cls_dev[1]
+    // its mute twin -- all thresholds +inf, the same plates -- behind the muted repetitions of irmv_engine_profile.  The
+    // addresses are fixed for the engine's life; a policy change rewrites the contents and re-captures nothing.
+    ClassTable *cls_dev = nullptr;
+    irmv_class_policy policy{};       // the policy in force (the uniform one of cfg.score_thr / cfg.armor_size until set)
     long long *dbg_dev = nullptr;
     std::set<std::string> lazy_tensors;   // tensors a step does not write because a fused kernel keeps them on chip
     bool classical = false;            // four points from the classical light extraction instead of a keypoint head
@@ -331,6 +336,7 @@ void front_plan(const irmv_engine_cfg &c, const FrontSwitches &sw, irmv_front_pl
 int check_letterbox(const irmv_engine_cfg &c);
 int write_window(irmv_engine *e, int slot);
 int write_isp_table(irmv_engine *e);
+int write_class_table(irmv_engine *e);
 // engine_graph.cpp
 int dev_alloc(irmv_engine *e, void **p, size_t bytes);
 int load_blob(irmv_engine *e);

@@ -84,6 +84,7 @@ LightArgs irmv::light_args(const irmv_engine *e, const View &v, int first)
     a.pnp = e->pnp_dev;
     a.first = first; a.pnp_stride = e->post.pnp_stride;
     a.pnp_armor_size = c.armor_size;
+    a.cls = e->cls_dev;
     return a;
 }
 
@@ -273,7 +274,7 @@ static Conv0Args conv0_args(const irmv_engine *e, const Op &op, int first, int c
 
 static void scan_args_for(const irmv_engine *e, const Op &op, const PostArgs &pa, ConvArgs &a)
 {
-    a.scan_keys = pa.keys; a.scan_counts = pa.counts; a.scan_thr = pa.logit_thr; a.scan_nc = pa.nc;
+    a.scan_keys = pa.keys; a.scan_counts = pa.counts; a.scan_cls = pa.cls; a.scan_nc = pa.nc;
     a.scan_key_cap = pa.key_cap;
     a.scan_abase = e->lvl_base[op.level];
     a.cand_bits = pa.cand_bits; a.cand_words = pa.cand_words;   // (sparse head: the class channels stay on chip)
@@ -345,8 +346,8 @@ int irmv::enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipS
     const View &v = view_of(e, first);
     const std::vector<Launch> &plan = v.plans[kind];
     const PostArgs pa = post_args(e, v, first);
-    PostArgs mute = pa;   // (a threshold no logit passes: no key, no bit)
-    mute.logit_thr = INFINITY;
+    PostArgs mute = pa;   // (the table's twin with thresholds no logit passes: no key, no bit)
+    mute.cls = e->cls_dev + 1;
     for (size_t i = 0; i < plan.size(); i++) {
         const Launch &l = plan[i];
         if (ev) HIP_TRY(hipEventRecord((*ev)[2 * i], s));

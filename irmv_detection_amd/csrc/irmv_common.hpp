@@ -291,6 +291,18 @@ struct Kpt3Args {
 bool kpt3_eligible(int cin);
 bool launch_kpt3(const Kpt3Args &a, int cin, int batch, hipStream_t s);
 
+// Class policy (irmv_engine_set_class_policy): one logit threshold and one plate model per class, in device memory at an
+// address fixed for the engine's life -- kernels hold the pointer, a captured graph never the values.  (anchor, c) is a
+// candidate iff logit > thr[c]; min_thr = the smallest thr[c] over c < nc (+inf: every class off), the wave-uniform pre-test
+// in front of the per-class compare.  Entries at and above nc are +inf / the configured plate and never read by a compare.
+constexpr int kMaxClasses = 16;
+struct ClassTable {
+    float min_thr;
+    int32_t pad_[3];
+    float thr[kMaxClasses];
+    int32_t plate[kMaxClasses];   // IRMV_ARMOR_*: index into PnpConst::hy / hz for a detection of class c
+};
+
 struct ConvArgs {
     ConvSeg s0, s1;
     int Hin, Win;       // input size at the conv's own resolution
@@ -317,7 +329,7 @@ struct ConvArgs {
     // computed and appended to the frame's key list -- the separate scan over the head tensor then never runs.
     unsigned long long *scan_keys;   // [B][scan_key_cap], nullptr = off
     int *scan_counts;                // [B]
-    float scan_thr;
+    const ClassTable *scan_cls;      // per-class thresholds (never null where scan_keys is set)
     int scan_nc, scan_abase, scan_key_cap;   // classes; first anchor index of this level; list capacity (= A * nc)
     // Sparse head (LDS 3x3 kernel, N2 > 0): the frame's candidate-anchor bitmap, one bit per anchor.  nullptr = every head row
     // is stored.  With scan_keys (class carrier): a candidate's anchor bit is set next to its key and the class channels are
@@ -420,11 +432,11 @@ struct PostArgs {
     DevDet *dets;             // [B][max_det]
     DevFrameOut *fout;        // [B]
     int net_w, net_h, A, nc, nk;   // net input width x height; A = sum over s in {8, 16, 32} of (net_h / s) (net_w / s)
-    float logit_thr, iou_thr;
+    const ClassTable *cls;    // per-class logit thresholds and plates (ClassTable; the engine's, or its all-infinite mute twin)
+    float iou_thr;
     int max_det, pre_nms_cap;
     // parse_output mapping net -> source frame: x_src = (x - off_x) * scale_x
     float scale_x, scale_y, off_x, off_y;
-    int armor_size;
     const PnpConst *pnp;      // device copy (keeps the kernel-argument struct out of scratch)
     long long *dbg;           // optional [B][8] phase stamps of nms_pnp_kernel (diagnostic builds of the engine only)
     int keys_only;            // 1: the key list comes from the class-branch conv epilogues (ConvArgs::scan_keys): nms_pnp_kernel decodes
@@ -485,7 +497,8 @@ struct LightArgs {
     float light_min_ratio, light_max_ratio, light_max_angle;
     double min_small_cd, max_small_cd, min_large_cd, max_large_cd;
     const PnpConst *pnp;
-    int pnp_armor_size;
+    int pnp_armor_size;      // plate of explicit boxes (they have no class) ...
+    const ClassTable *cls;   // ... and, boxes == nullptr: the table whose plate[dets[i].cls] a step's detection solves with
     LightTrace *trace;       // [n_boxes] or nullptr (every launch of a step): see LightTrace
     int first, pnp_stride;   // frame b solves with pnp[(first + b) * pnp_stride] (PostArgs::pnp_stride)
 };

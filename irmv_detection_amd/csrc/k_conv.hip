@@ -958,6 +958,12 @@ __device__ __forceinline__ void conv3x3_lds_body(const ConvArgs &a, const half_t
     }
     const int chunks = a.Cin >> 5;
     const half8 zero8 = (half8){0, 0, 0, 0, 0, 0, 0, 0};
+    // class policy: the smallest per-class threshold, read here -- ahead of every store of the kernel -- through the uniform
+    // table pointer, so it is one scalar load into one SGPR
+    float scan_min = 0.f;
+    if constexpr (N2 == 1) {
+        if (a.scan_keys) scan_min = a.scan_cls->min_thr;
+    }
 
     // staging plan: element e -> (patch pixel, 16-byte quarter); weights: 9*NT*64 half8 per chunk
     constexpr int PMAX = lds_pmax(STRIDE, MT, TILE2D, WR, PF);   // patch 16-B pieces per thread and chunk plane (host guarantees the fit)
@@ -1144,19 +1150,26 @@ __device__ __forceinline__ void conv3x3_lds_body(const ConvArgs &a, const half_t
                             const f32x4 b2 = *reinterpret_cast<const f32x4 *>(s_bias2 + co);
                             const f32x4 v2 = (f32x4){c2[0] * kActUnscale + b2[0], c2[1] * kActUnscale + b2[1], c2[2] * kActUnscale + b2[2], c2[3] * kActUnscale + b2[3]};   // (the 1x1's inputs carry the activation scale)
                             if (st2) *reinterpret_cast<f32x4 *>(a.out2 + m * a.out2_ld + co) = v2;
-                            if (a.scan_keys) {
+                            if (N2 == 1 && a.scan_keys) {   // (compiled for the one-tile final only: a class final is one 16-channel tile, and the box carriers sit at the edge of the register file)
                                 // class logits: lane (g, r) holds classes co .. co + 3 of its pixel -- the values the head record just
                                 // received.  Candidates (rare) go to the frame's key list here, so no kernel re-reads the head for them
                                 // (key format and threshold test of k_post.hip: orderable(logit) << 32 | ~(anchor * nc + class)).
+                                // Two stages (class policy): the pre-test against the table's smallest threshold, one uniform value,
+                                // is the test a single threshold was; the lane's own four thresholds are loaded and compared only
+                                // behind it.  Bit, key and count all follow the per-class test: a class that is off leaves none.
                                 bool hit = false;
 #pragma unroll
-                                for (int i = 0; i < 4; i++) hit = hit || (mv[mt] && co + i < a.scan_nc && v2[i] > a.scan_thr);
+                                for (int i = 0; i < 4; i++) hit = hit || (mv[mt] && co + i < a.scan_nc && v2[i] > scan_min);
                                 if (hit) {
+                                    const f32x4 th = reinterpret_cast<const f32x4 *>(a.scan_cls->thr)[(unsigned int)(t2 * 4 + g)];   // (uniform base, 32-bit lane offset)
+                                    bool pass[4];
+#pragma unroll
+                                    for (int i = 0; i < 4; i++) pass[i] = co + i < a.scan_nc && v2[i] > th[i];
                                     const int an = a.scan_abase + mloc[mt];
-                                    if (a.cand_bits) atomicOr(&a.cand_bits[(size_t)im * a.cand_words + (an >> 5)], 1u << (an & 31));
+                                    if (a.cand_bits && (pass[0] || pass[1] || pass[2] || pass[3])) atomicOr(&a.cand_bits[(size_t)im * a.cand_words + (an >> 5)], 1u << (an & 31));
 #pragma unroll
                                     for (int i = 0; i < 4; i++) {
-                                        if (co + i < a.scan_nc && v2[i] > a.scan_thr) {
+                                        if (pass[i]) {
                                             const int idx = atomicAdd(&a.scan_counts[im], 1);
                                             const unsigned int u = __float_as_uint(v2[i]);
                                             const unsigned int ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -1600,6 +1613,7 @@ static ConvLauncher pick_lds(const ConvCfg &c, const ConvArgs &a, int ipw, LdsGe
     const int pf = c.pf4 ? 2 : (c.pf2 ? 1 : 0), nwv = c.w8 || c.wr ? 8 : 4;
     if (c.cm && c.cm != ipw) return nullptr;
     if (a.n2 > 0 && (a.cout_pad != 64 || !a.pair || a.res)) return nullptr;   // the fused 1x1 reads all 64 channels of a pixel
+    if (a.scan_keys && a.n2 != 1) return nullptr;                              // candidates are emitted by the one-tile final only
     g = c.wr ? wres_geom(a, c.stride, c.pp) : lds_geom(a, c.stride, c.mt, c.nt, nwv, 0, false, pf);
     if (!g.bytes) return nullptr;
     const LdsKey key{c.stride, c.mt, c.nt, a.n2, pf, c.cm, nwv, c.wr ? 2 : 0, c.pp};
@@ -1690,6 +1704,7 @@ bool launch_conv_lds_multi(int nt, const ConvArgs *a, const ConvWeights *w, int 
         const LdsGeom g = lds_geom(a[k], 1, 1, nt);
         const half_t *wl = lds_weights(w[k], nt);
         if (!wl || !g.bytes) return false;
+        if (a[k].scan_keys && a[k].n2 != 1) return false;   // candidates are emitted by the one-tile final only
         if (a[k].n2 > 0 && (nt != 4 || a[k].cout_pad != 64 || !a[k].pair || a[k].res || !(a[k].n2 == 1 || a[k].n2 == 4))) return false;
         LdsMember &l = m.m[k];
         l.a = a[k]; l.wl = wl;

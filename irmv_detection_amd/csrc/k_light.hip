@@ -504,7 +504,9 @@ __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
         d->quat[0] = d->quat[1] = d->quat[2] = 0.0; d->quat[3] = 1.0;
         d->pnp_ok = 0;
         // the reference always solves with the SMALL model (src/pnp_solver.cpp:47-48)
-        if (valid) d->pnp_ok = solve_pnp_ippe(a.pnp[(size_t)(a.first + b) * a.pnp_stride], d->kpts, a.pnp_armor_size, d->rvec, d->tvec, d->quat) ? 1 : 0;
+        // ... this project with the plate the class policy gives the detection's class (explicit boxes have no class)
+        const int plate = (a.cls && !a.boxes) ? a.cls->plate[d->cls & (kMaxClasses - 1)] : a.pnp_armor_size;
+        if (valid) d->pnp_ok = solve_pnp_ippe(a.pnp[(size_t)(a.first + b) * a.pnp_stride], d->kpts, plate, d->rvec, d->tvec, d->quat) ? 1 : 0;
     }
 }
 

@@ -108,14 +108,20 @@ __device__ __forceinline__ float dfl_side(const float *l)
 // read of the record's class logits).  Candidate keys go to the workgroup's LDS list (and to the frame's global list,
 // which only the > kCandCap path reads back); anchors with at least one candidate are appended to `alist`.  List
 // positions come from LDS counters: no global atomic, no counter that outlives the kernel.
-__device__ __forceinline__ void scan_quad(const PostArgs &a, int an, bool live, const f32x4 cl, unsigned long long *skeys, unsigned long long *gk,
+__device__ __forceinline__ void scan_quad(const PostArgs &a, float min_thr, int an, bool live, const f32x4 cl, unsigned long long *skeys, unsigned long long *gk,
                                           int *s_ncand, unsigned short *alist, int *s_nanch)
 {
     const int q = threadIdx.x & 3;
     bool hit = false;
 #pragma unroll
-    for (int i = 0; i < 4; i++) hit = hit || (live && 4 * q + i < a.nc && cl[i] > a.logit_thr);
+    for (int i = 0; i < 4; i++) hit = hit || (live && 4 * q + i < a.nc && cl[i] > min_thr);
     if (!__any(hit)) return;                      // the common case: nothing in these 16 anchors
+    // class policy: behind the pre-test against the smallest threshold, the lane's own four classes against their own
+    const f32x4 th = *reinterpret_cast<const f32x4 *>(a.cls->thr + 4 * q);
+    hit = false;
+#pragma unroll
+    for (int i = 0; i < 4; i++) hit = hit || (live && 4 * q + i < a.nc && cl[i] > th[i]);
+    if (!__any(hit)) return;
     const int lane = threadIdx.x & 63, base = lane & ~3;
     const bool quad_hit = ((__ballot(hit) >> base) & 0xfull) != 0ull;
     if (alist && quad_hit && q == 0) alist[atomicAdd(s_nanch, 1)] = (unsigned short)an;
@@ -124,7 +130,7 @@ __device__ __forceinline__ void scan_quad(const PostArgs &a, int an, bool live, 
     for (int i = 0; i < 4; i++) {
         const int c = 4 * q + i;
         const float logit = cl[i];
-        if (c < a.nc && logit > a.logit_thr) {
+        if (c < a.nc && logit > th[i]) {
             const int idx = atomicAdd(s_ncand, 1);   // LDS; <= A * nc = key_cap by construction
             const unsigned long long key = ((unsigned long long)orderable(logit) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)(an * a.nc + c));
             if (idx < kCandCap) skeys[idx] = key;
@@ -195,6 +201,7 @@ __global__ __launch_bounds__(256) void scan_decode_kernel(PostArgs a, int per)
     const int quads = a.A * 4;
     constexpr int U = kScanU;
     if (tid == 0) s_n = 0;
+    const float min_thr = a.cls->min_thr;   // class policy: the smallest per-class threshold (uniform: one scalar load)
     __syncthreads();
     const int w0 = a.net_w >> 3, h0 = a.net_h >> 3, A0 = w0 * h0, A1 = A0 + (w0 >> 1) * (h0 >> 1);   // level boundaries
     unsigned long long *gk = a.keys + (size_t)b * a.key_cap;
@@ -217,14 +224,20 @@ __global__ __launch_bounds__(256) void scan_decode_kernel(PostArgs a, int per)
             const int an = live ? (t >> 2) : 0;
             bool hit = false;
 #pragma unroll
-            for (int i = 0; i < 4; i++) hit = hit || (live && 4 * q + i < a.nc && cl[u][i] > a.logit_thr);
+            for (int i = 0; i < 4; i++) hit = hit || (live && 4 * q + i < a.nc && cl[u][i] > min_thr);
+            if (__ballot(hit) == 0ull) continue;                   // the common case: nothing in these 16 anchors
+            // ... behind that pre-test, rarely: the lane's own four classes against their own thresholds
+            const f32x4 th = reinterpret_cast<const f32x4 *>(a.cls->thr)[q];
+            hit = false;
+#pragma unroll
+            for (int i = 0; i < 4; i++) hit = hit || (live && 4 * q + i < a.nc && cl[u][i] > th[i]);
             const unsigned long long hits = __ballot(hit);
-            if (hits == 0ull) continue;                            // the common case: nothing in these 16 anchors
+            if (hits == 0ull) continue;
             if (hit) {
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
                     const int c = 4 * q + i;
-                    if (c < a.nc && cl[u][i] > a.logit_thr)
+                    if (c < a.nc && cl[u][i] > th[i])
                         s_keys[atomicAdd(&s_n, 1)] = ((unsigned long long)orderable(cl[u][i]) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)(an * a.nc + c));
                 }
             }
@@ -434,6 +447,7 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
     {
         constexpr int U = 8;
         int lbase = 0;
+        const float min_thr = a.cls->min_thr;   // class policy: the smallest per-class threshold (uniform: one scalar load)
 #pragma unroll 1
         for (int l = 0; l < 3; l++) {
             const int lhw = (a.net_w / (8 << l)) * (a.net_h / (8 << l));
@@ -451,7 +465,7 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
                 for (int u = 0; u < U; u++) {
                     if (q0 + u * 1024 >= quads) break;          // workgroup-uniform
                     const int t = q0 + u * 1024 + tid;
-                    scan_quad(a, lbase + (t >> 2), t < quads, cl[u], skeys, gk, &s_ncand, alist, &s_nanch);
+                    scan_quad(a, min_thr, lbase + (t >> 2), t < quads, cl[u], skeys, gk, &s_ncand, alist, &s_nanch);
                 }
             }
             lbase += lhw;
@@ -1293,7 +1307,8 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
             IRMV_STAMP(11);
             double rvec[3] = {0.0, 0.0, 0.0}, tvec[3] = {0.0, 0.0, 0.0}, quat[4] = {0.0, 0.0, 0.0, 1.0};
             int pnp_ok = 0;
-            if (a.nk >= 8) pnp_ok = solve_pnp_ippe_pair(a.pnp[(size_t)(a.first + b) * a.pnp_stride], px0, py0, px1, py1, a.armor_size, rvec, tvec, quat) ? 1 : 0;
+            const int plate = a.cls->plate[kept_cls[j] & (kMaxClasses - 1)];   // class policy: the object points of this detection's class
+            if (a.nk >= 8) pnp_ok = solve_pnp_ippe_pair(a.pnp[(size_t)(a.first + b) * a.pnp_stride], px0, py0, px1, py1, plate, rvec, tvec, quat) ? 1 : 0;
             IRMV_STAMP(12);
             if (w) {
 #pragma unroll
@@ -1302,7 +1317,7 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
                 for (int i = 0; i < 4; i++) d->quat[i] = quat[i];
                 d->pnp_ok = pnp_ok;
                 d->armor_valid = a.nk >= 8 ? 1 : 0;   // keypoint head: every detection carries its four points
-                d->armor_size = a.armor_size;
+                d->armor_size = plate;
                 d->n_lights = 0;
                 d->pad_ = 0;
             }

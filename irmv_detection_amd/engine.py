@@ -99,6 +99,8 @@ class YoloEngine:
     `set_window` / `set_window_center` move a slot's window between steps (irmv_detection_amd.window is the host reference);
     `set_view("frame")` runs a slot's next steps on the whole frame instead (the search after a lost target), `set_view("window")`
     goes back -- one engine, nothing uploaded or tuned twice.
+    `set_class_policy` / `set_enemy_color` change per-class score thresholds, the colour mask and the per-class plate model of
+    the living engine (irmv_detection_amd.class_policy is the host reference).
     """
 
     def __init__(self, onnx_file_path: Optional[str], src_image_size: Tuple[int, int] = (1280, 1024),
@@ -174,6 +176,9 @@ class YoloEngine:
         self.num_anchors = L.irmv_engine_num_anchors(self._h)
         self.head_channels = L.irmv_engine_head_channels(self._h)
         self._dets = (capi.Det * max_det)()
+        if hasattr(L, "irmv_engine_get_class_policy"):                # (absent only in an older build loaded through IRMV_LIB_PATH)
+            self._cfg_policy = self._get_policy()                     # the uniform policy of score_thr / armor_size
+            self._user_policy, self._enemy_color = (list(self._cfg_policy.score_thr), list(self._cfg_policy.plate)), -1
         # the reference warms up with 50 detect() calls in its constructor (:114-116)
         for _ in range(warmup):
             self.detect()
@@ -296,6 +301,59 @@ class YoloEngine:
         lut = np.empty((3, 256), np.uint8)
         capi.check(self._L.irmv_engine_get_bayer_isp(self._h, g, lut.ctypes.data_as(C.POINTER(C.c_uint8))))
         return tuple(g), lut
+
+    def set_class_policy(self, score_thr=None, plate=None) -> None:
+        """Per-class score thresholds and plate models, from the next submit on (irmv_engine_set_class_policy): each a
+        scalar or a per-class sequence; a threshold >= 1 switches the class off where candidates are emitted.  None keeps
+        the constructor's score_thr / armor_size; both None: back to them for every class, and no colour filter.  A dict from
+        irmv_detection_amd.class_policy (policy / uniform / enemy) may be passed as score_thr.  The colour set with
+        set_enemy_color stays in force on top of it.  Blocks until every step in flight has finished; uploads the table
+        once; re-captures nothing.  A refused argument raises and leaves everything as it was."""
+        if isinstance(score_thr, dict):
+            score_thr, plate = score_thr["score_thr"], score_thr["plate"] if plate is None else plate
+        if score_thr is None and plate is None:
+            capi.check(self._L.irmv_engine_set_class_policy(self._h, None))
+            self._user_policy, self._enemy_color = (list(self._cfg_policy.score_thr), list(self._cfg_policy.plate)), -1
+            return
+        self._apply_policy((self._per_class(score_thr, self._cfg_policy.score_thr), self._per_class(plate, self._cfg_policy.plate)), self._enemy_color)
+
+    def set_enemy_color(self, c: int) -> None:
+        """The reference node's enemy_color: 0 = the enemy is blue (B1..BS stay on, R1..RS are off), 1 = the enemy is red,
+        -1 = no filter.  The thresholds and plates set with set_class_policy stay: a class with its own threshold keeps it
+        whenever its colour is on."""
+        self._apply_policy(self._user_policy, int(c))
+
+    def _apply_policy(self, user, colour) -> None:
+        """The caller's (thresholds, plates) with the colour's mask on top -> one table upload; stored only if accepted."""
+        thr, pl = list(user[0]), list(user[1])
+        mask = capi.class_policy_enemy(colour, 0.5)            # (raises for a colour outside -1, 0, 1)
+        for k in range(16):
+            if mask.score_thr[k] >= 1:
+                thr[k] = 1.0
+        capi.check(self._L.irmv_engine_set_class_policy(self._h, C.byref(capi.class_policy_struct(thr, pl))))
+        self._user_policy, self._enemy_color = (list(user[0]), list(user[1])), colour
+
+    def get_class_policy(self) -> dict:
+        """The policy in force: dict(score_thr=float32[16], plate=uint8[16]) (entries at and above the model's class count
+        are not used)."""
+        p = self._get_policy()
+        return dict(score_thr=np.array(p.score_thr[:], np.float32), plate=np.array(p.plate[:], np.uint8))
+
+    def _get_policy(self) -> "capi.ClassPolicy":
+        p = capi.ClassPolicy()
+        capi.check(self._L.irmv_engine_get_class_policy(self._h, C.byref(p)))
+        return p
+
+    @staticmethod
+    def _per_class(v, default):
+        if v is None:
+            return list(default)
+        if np.ndim(v) == 0:
+            return [v] * 16
+        v = list(v)
+        if len(v) > 16:
+            raise ValueError("at most 16 per-class values")
+        return v + list(default)[len(v):]
 
     def extract_armors(self, bboxes, slot: Optional[int] = None) -> List[Armor]:
         """IrmDetector::extract_armors(get_rotated_image(), bboxes) (src/irm_detector.cpp:292-355) on the GPU,

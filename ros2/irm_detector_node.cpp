@@ -30,6 +30,8 @@ public:
     p.armor_min_large_center_distance = node_->declare_parameter("armor.min_large_center_distance", 3.2);
     p.armor_max_large_center_distance = node_->declare_parameter("armor.max_large_center_distance", 5.5);
     p.device = int(node_->declare_parameter("device", 0));
+    p.enemy_color = int(node_->declare_parameter("enemy_color", -1));   // 0 for blue, 1 for red (reference :154-160), -1: no filter; live through the callback below
+    for (int64_t c : node_->declare_parameter("large_plate_classes", std::vector<int64_t>{})) p.large_plate_classes.push_back(int(c));
     const auto ns = node_->declare_parameter("net_input_size", std::vector<int64_t>{0, 0});   // {width, height}; {0, 0}: square default
     if (ns.size() == 2) p.net_input_size = cv::Size(int(ns[0]), int(ns[1]));
     const std::string model = node_->declare_parameter("model_path", std::string("models/yolov7.onnx"));
