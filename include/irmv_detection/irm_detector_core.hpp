@@ -88,6 +88,8 @@ public:
                                                          // height 0: square of the width (1280 x 1024 camera: 640 x 512)
     cv::Size window_size{0, 0};                          // tracking window of the three engines (YoloEngine's `window`); 0: none.  No policy here:
                                                          // the caller moves each engine's window (engine(id).set_window_center(...))
+    cv::Size tile_overlap{-1, -1};                       // tiled search of the three engines (YoloEngine's `tile_overlap`; needs window_size): the least overlap
+                                                         // of neighbouring tiles; negative: off.  engine(id).detect_tiles() then searches the frame in its buffer
     int enemy_color = -1;                                // the node's enemy_color (:154-160, "0 for blue, 1 for red"): 0 keeps B1..BS, 1 keeps R1..RS,
                                                          // on the GPU where candidates are emitted; -1: no filter (what the reference's unused parameter amounts to)
     std::vector<int> large_plate_classes;                // ArmorClass values whose detections PnP solves with the 225 mm plate; the rest: 135 mm
@@ -110,7 +112,7 @@ public:
     for (auto & e : yolo_engines_) {
       e = std::make_unique<YoloEngine>(model_path, p.image_input_size, p.profiling, p.device, false, p.net_input_size.width > 0 ? p.net_input_size.width : -1,
                                        IRMV_SRC_HWC8, std::array<uint16_t, 3>{256, 256, 256}, p.net_input_size.height > 0 ? p.net_input_size.height : -1,
-                                       IRMV_DEMOSAIC_BILINEAR, p.window_size);
+                                       IRMV_DEMOSAIC_BILINEAR, p.window_size, p.tile_overlap);
       push_params(*e);
       if (p.enemy_color != -1 || !p.large_plate_classes.empty()) push_class_policy(*e);
     }

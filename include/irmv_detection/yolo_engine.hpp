@@ -77,10 +77,14 @@ public:
   // writes and bboxes come back in its coordinates; set_window() / set_window_center() move the window between detect()
   // calls; get_rotated_image() is then the rotated window.  set_view(View::Frame) runs detect() on the whole frame instead
   // (the search after a lost target), set_view(View::Window) goes back; get_rotated_image() follows the view.
+  // `tile_overlap` (a negative value = off; needs a window): the tiled search.  The engine gets 1 + nx * ny slots: slot 0 stays
+  // the tracking slot and owns the frame, slots 1.. hold the grid irmv_tile_grid gives for that least overlap of neighbouring
+  // windows, set once.  detect_tiles() then searches the frame already in get_src_image_buffer() at the sensor's resolution:
+  // every tile runs its window of that frame in ONE step and the step merges their lists (include/irmv_hip.h, "tiled search").
   YoloEngine(const std::string & onnx_file_path, cv::Size src_image_size, bool enable_profiling = false, int device = -1,
              bool warm_up_now = true, int net_size = -1, int src_format = IRMV_SRC_HWC8,
              std::array<uint16_t, 3> bayer_gain_q8 = {256, 256, 256}, int net_height = -1,
-             int bayer_demosaic = IRMV_DEMOSAIC_BILINEAR, cv::Size window = {})
+             int bayer_demosaic = IRMV_DEMOSAIC_BILINEAR, cv::Size window = {}, cv::Size tile_overlap = cv::Size(-1, -1))
   : src_image_size_(src_image_size), window_size_(window), enable_profiling_(enable_profiling)
   {
     irmv_engine_cfg cfg;
@@ -96,6 +100,15 @@ public:
     cfg.win_width = window.width;
     cfg.win_height = window.height;
     cfg.num_slots = 1;  // one engine per TripleBuffer slot, like the reference node
+    std::vector<int32_t> tile_xy;
+    if (tile_overlap.width >= 0 && tile_overlap.height >= 0) {
+      int nx = 0, ny = 0;
+      tile_xy.resize(2 * IRMV_MAX_TILES);
+      if (irmv_tile_grid(&cfg, tile_overlap.width, tile_overlap.height, tile_xy.data(), IRMV_MAX_TILES, &num_tiles_, &nx, &ny) != IRMV_OK)
+        throw std::runtime_error(std::string("YoloEngine: tile_overlap: ") + irmv_last_error());
+      cfg.num_slots = 1 + num_tiles_;
+      tile_grid_ = cv::Size(nx, ny);
+    }
     cfg.weights_path = onnx_file_path.c_str();
     const int rc = irmv_engine_create(&cfg, &engine_);
     if (rc == IRMV_ERR_MODEL) {
@@ -106,6 +119,10 @@ public:
     src_image_buffer_ = irmv_engine_src_buffer(engine_, 0);
     rotated_ = has_window() ? cv::Mat(window.height, window.width, CV_8UC3) : cv::Mat(src_image_size.height, src_image_size.width, CV_8UC3);
     dets_.resize(static_cast<size_t>(irmv_engine_max_det(engine_)));
+    for (int t = 0; t < num_tiles_; t++)
+      if (irmv_engine_set_window(engine_, 1 + t, tile_xy[static_cast<size_t>(2 * t)], tile_xy[static_cast<size_t>(2 * t + 1)]) != IRMV_OK)
+        throw std::runtime_error(std::string("YoloEngine: tile grid: ") + irmv_last_error());
+    tile_dets_.resize(num_tiles_ > 0 ? dets_.size() : 0);
     irmv_engine_get_class_policy(engine_, &base_policy_);   // the uniform policy of the engine's score threshold and plate
     user_policy_ = base_policy_;
     if (warm_up_now) warm_up();
@@ -238,6 +255,42 @@ public:
     }
     n_last_ = n;
     return out;
+  }
+
+  // ---- tiled search (constructor argument tile_overlap) ----
+  int num_tiles() const { return num_tiles_; }
+  cv::Size tile_grid() const { return tile_grid_; }   // tiles per row x per column
+  // The frame already in get_src_image_buffer(), searched at the sensor's resolution: one step of all tiles, merged on the GPU
+  // into one list in full-frame coordinates (at most max_det boxes: whole boxes first, by score).  The tracking slot's window,
+  // view and last results stay as they are.
+  std::vector<bbox> detect_tiles()
+  {
+    if (num_tiles_ < 1) throw std::runtime_error("YoloEngine::detect_tiles: the engine was built without tile_overlap");
+    int n = 0;
+    if (irmv_engine_submit_tiles(engine_, 0, 1, num_tiles_, IRMV_SUBMIT_H2D) != IRMV_OK || irmv_engine_wait_slots(engine_, 1, num_tiles_) != IRMV_OK ||
+        irmv_engine_tile_results(engine_, 1, tile_dets_.data(), static_cast<int>(tile_dets_.size()), &n, nullptr) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::detect_tiles: ") + irmv_last_error());
+    std::vector<bbox> out;
+    out.reserve(static_cast<size_t>(n));
+    for (int i = 0; i < n; i++) {
+      const irmv_det & d = tile_dets_[static_cast<size_t>(i)].det;
+      out.push_back(bbox{{d.xyxy[0], d.xyxy[1], d.xyxy[2], d.xyxy[3]}, d.score, static_cast<ArmorClass>(d.class_id)});
+    }
+    n_last_tiles_ = n;
+    return out;
+  }
+  // The records of the last detect_tiles(): each detection with its pose, the tile it came from and whether a seam cut it.
+  const irmv_tile_det * last_tile_detections(int * n) const
+  {
+    *n = n_last_tiles_;
+    return tile_dets_.data();
+  }
+  // The merge's two live parameters (irmv_engine_set_tile_merge): defaults 0.5 and 2 source pixels, neither validated on a
+  // trained model.
+  void set_tile_merge(float ios_thr, float edge_margin)
+  {
+    if (irmv_engine_set_tile_merge(engine_, ios_thr, edge_margin) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::set_tile_merge: ") + irmv_last_error());
   }
 
   // The full per-armor result of the last detect(): keypoints and pose, computed on the GPU.
@@ -387,5 +440,8 @@ private:
   mutable bool rotated_valid_ = false;
   std::vector<irmv_det> dets_;
   int n_last_ = 0;
+  std::vector<irmv_tile_det> tile_dets_;   // detect_tiles()
+  int num_tiles_ = 0, n_last_tiles_ = 0;
+  cv::Size tile_grid_{0, 0};
 };
 }  // namespace irmv_detection

@@ -286,6 +286,74 @@ size_t irmv_engine_src_bytes(const irmv_engine *e);    /* bytes of one source sl
 #define IRMV_SUBMIT_ASYNC_UPLOAD 2u /* ... on the engine's upload stream, event-chained to the compute stream: this
                                        group's frames cross PCIe while other groups' kernels run (one cross-stream hop) */
 
+/* ---- tiled search: one frame as overlapping windows in one step, merged ------------------------------------------------
+ * The frame view squeezes the frame into the net; a tiled step searches it at the sensor's resolution instead.  N slots of a
+ * window engine -- the tiles, each with its own corner (irmv_engine_set_window: data, moving a tile re-captures nothing) --
+ * run ONE step in which every slot's crop cuts its window out of the full frame of ONE slot, frame_slot.  Behind the crop each
+ * slot is what it always is: the same kernels and the same bits as a window engine's step of that slot on that frame, so
+ * irmv_engine_results(slot), the read-backs and the classical point source work per tile.  The step's last node merges the N
+ * result lists into one, in full-frame coordinates (k_tiles.hip; irmv_detection_amd/tiles.py is the bit-exact host reference).
+ * Tiling is a way of submitting, not a view: irmv_engine_set_view knows IRMV_VIEW_WINDOW and IRMV_VIEW_FRAME only.
+ *
+ * The merge.  Every coordinate is the fp32 value irmv_engine_results returns, float(local) + float(corner).  Tile t is slot
+ * first + t with corner (x0, y0), window ww x wh, frame FW x FH; m = edge_margin.
+ *   seam cut  a record is cut if  x0 > 0 && X1 < float(x0) + m,  or  y0 > 0 && Y1 < float(y0) + m,
+ *             or  x0 + ww < FW && X2 > float(x0 + ww) - m,  or  y0 + wh < FH && Y2 > float(y0 + wh) - m:
+ *             its box touches an edge of its tile that is not an edge of the frame, so the tile may have seen a part of it.
+ *   order     (cut ascending, score descending, tile ascending, index ascending): whole boxes first.
+ *   walk      in that order a record is kept unless an already kept record of a DIFFERENT tile and the SAME class_id has
+ *             inter > ios_thr * min(area_a, area_b) with it -- intersection over the smaller area, no division --, where
+ *             inter = max(0, min(X2) - max(X1)) * max(0, min(Y2) - max(Y1)) and area = (X2 - X1) * (Y2 - Y1), plain fp32.
+ *             Records of one tile never suppress each other (their own NMS has ruled).  It stops at max_det kept records.
+ * Capacity: IRMV_MAX_TILES x IRMV_MAX_DET_CAP = 4096 records, sorted and walked by one workgroup out of LDS.
+ * The merge's buffers are allocated by an engine's first tiled call; an engine on which none is made allocates, captures and
+ * runs what it always did, and the merge is no entry of irmv_engine_ops. */
+#define IRMV_MAX_TILES 16
+typedef struct irmv_tile_det {
+    irmv_det det;            /* byte-identical to record `index` of irmv_engine_results(first + tile) */
+    int32_t tile, index;     /* the slot (first + tile) and the place in its list the record comes from */
+    int32_t cut;             /* 1: the seam cut applies to it (it was kept all the same: nothing whole covered it) */
+    int32_t reserved;
+} irmv_tile_det;
+/* Host only, no GPU (like irmv_window_map / irmv_front_plan): the grid the engine documents.  cfg must have a window.  Per axis,
+ * with frame extent F, window extent w and least overlap 0 <= ov < w: n = 1 tiles if w == F, else ceil((F - ov) / (w - ov)),
+ * with corners c_i = (2 i (F - w) + (n - 1)) / (2 (n - 1)) in integers (0 when n == 1): the fewest tiles that cover the axis,
+ * spread evenly, neighbours overlapping by at least ov.  Tiles are row-major, t = iy * nx + ix; xy[t] = (x, y) in result
+ * coordinates, as irmv_engine_set_window takes them.  xy == NULL queries *n (and *nx, *ny; either may be NULL).
+ * 1280 x 1024, window 640 x 512, overlap 128: 3 x 3, x 0 320 640, y 0 256 512.
+ * IRMV_ERR_ARG: no window, an overlap out of range, more than IRMV_MAX_TILES tiles, cap smaller than the grid. */
+int irmv_tile_grid(const irmv_engine_cfg *cfg, int min_overlap_x, int min_overlap_y,
+                   int32_t *xy /* [cap][2] */, int cap, int *n, int *nx, int *ny);
+/* One tiled step of slots [first, first + count), 1 <= count <= IRMV_MAX_TILES, all in IRMV_VIEW_WINDOW, on the full frame of
+ * frame_slot (any slot of the engine, inside or outside the range).  With IRMV_SUBMIT_H2D only frame_slot's pinned frame
+ * crosses PCIe, once and whole -- never as bands, never cropped out of the pinned slot; IRMV_SUBMIT_ASYNC_UPLOAD moves that
+ * upload to the upload stream as it does for irmv_engine_submit; without IRMV_SUBMIT_H2D the device frame of frame_slot is read
+ * as it is.  A Bayer engine demosaics frame_slot's raw frame once.  The pinned and device frames of the other slots are
+ * neither read nor written.
+ * The step is ONE slot group: one captured graph -- [upload], [demosaic], crop, the slots' step, merge -- replayed on compute
+ * stream 0 of the engine (the stream of slot 0's single-slot steps), captured once per (frame_slot, first, count, upload
+ * form).  It is ordered against other groups like every submit; frame_slot counts as touched, so a later upload into it
+ * waits for this step.  irmv_engine_wait_slots(e, first, count) covers the merge.  A tiled step keeps the slots' result records
+ * in device memory (the merge reads them there) and copies them to the host behind the merge, also on engines whose ordinary
+ * steps write their records straight into pinned memory.
+ * IRMV_ERR_ARG, before anything is enqueued and leaving the engine usable: an engine without a window, a slot in the frame
+ * view, a bad range, count or frame_slot. */
+int irmv_engine_submit_tiles(irmv_engine *e, int frame_slot, int first, int count, uint32_t flags);
+/* Test hook, like irmv_engine_run_post: waits for everything in flight, runs the merge alone on the current results of slots
+ * [first, first + count) (e.g. of irmv_engine_write_head + irmv_engine_run_post) at the slots' current corners, and
+ * synchronizes.  From then on irmv_engine_results reads those slots' records in these corners. */
+int irmv_engine_merge_tiles(irmv_engine *e, int first, int count);
+/* The merged list of the last tiled step (after its wait) or irmv_engine_merge_tiles whose first slot was `first`: up to cap
+ * records in merge order, *n of them; *n_in (may be NULL) = the records that entered the merge.  The records are read out of the
+ * slots' result lists: they are valid until one of those slots is stepped again.  IRMV_ERR_ARG if no merge has run for `first`. */
+int irmv_engine_tile_results(irmv_engine *e, int first, irmv_tile_det *out, int cap, int *n, int *n_in);
+/* The merge's two parameters, two floats in device memory that the merge kernel reads when it runs: like
+ * irmv_engine_set_class_policy the call waits for every step in flight and re-captures nothing.  Defaults: ios_thr = 0.5 (the
+ * usual default of sliced inference), edge_margin = 2.0 source pixels.  Neither has been validated on a trained model -- none
+ * exists here --, which is why both are live.  IRMV_ERR_ARG: ios_thr outside (0, 1] or NaN, a negative or NaN margin. */
+int irmv_engine_set_tile_merge(irmv_engine *e, float ios_thr, float edge_margin);
+int irmv_engine_get_tile_merge(const irmv_engine *e, float *ios_thr, float *edge_margin);
+
 /* Enqueue one step for slots [first, first+count) and return immediately:
  *   [async H2D of the frames] -> ONE hipGraph {preprocess -> network -> decode -> NMS -> keypoints -> PnP} ->
  *   async D2H of the results.

@@ -26,6 +26,7 @@ SOURCES = [
     ("k_kpt.hip", []),
     ("k_conv.hip", []),
     ("k_post.hip", ["-ffp-contract=off"]),
+    ("k_tiles.hip", ["-ffp-contract=off"]),
     ("k_light.hip", ["-ffp-contract=off"]),
     ("k_shuffle.hip", []),
     ("k_debug.hip", []),
@@ -34,6 +35,7 @@ SOURCES = [
     ("engine_tune.cpp", ["-x", "hip"]),
     ("engine_plan.cpp", ["-x", "hip"]),
     ("engine_step.cpp", ["-x", "hip"]),
+    ("engine_tiles.cpp", ["-x", "hip"]),
     ("engine_hooks.cpp", ["-x", "hip"]),
 ]
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs.  Left to itself the compiler gives kernels without a waves_per_eu

@@ -25,6 +25,7 @@ VIEWS = {"window": VIEW_WINDOW, "frame": VIEW_FRAME}
 NUM_CLASSES = 14
 MAX_DET_CAP = 256
 CAND_CAP = 8192
+MAX_TILES = 16
 
 
 class IrmvError(RuntimeError):
@@ -61,6 +62,11 @@ class Det(C.Structure):
         ("rvec", C.c_double * 3), ("tvec", C.c_double * 3), ("quat", C.c_double * 4),
         ("armor_valid", C.c_int32), ("armor_size", C.c_int32), ("n_lights", C.c_int32), ("reserved", C.c_int32),
     ]
+
+
+class TileDet(C.Structure):
+    """irmv_tile_det (include/irmv_hip.h): a record of the merged list of a tiled step."""
+    _fields_ = [("det", Det), ("tile", C.c_int32), ("index", C.c_int32), ("cut", C.c_int32), ("reserved", C.c_int32)]
 
 
 class RawDets(C.Structure):
@@ -175,6 +181,12 @@ SYMBOLS = [
     ("irmv_engine_set_window", C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     ("irmv_engine_get_window", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("irmv_window_map", C.c_int, [C.POINTER(EngineCfg), C.c_int, C.c_int, C.POINTER(WindowMap)]),
+    ("irmv_tile_grid", C.c_int, [C.POINTER(EngineCfg), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("irmv_engine_submit_tiles", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint32]),
+    ("irmv_engine_merge_tiles", C.c_int, [_P, C.c_int, C.c_int]),
+    ("irmv_engine_tile_results", C.c_int, [_P, C.c_int, C.POINTER(TileDet), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("irmv_engine_set_tile_merge", C.c_int, [_P, C.c_float, C.c_float]),
+    ("irmv_engine_get_tile_merge", C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("irmv_engine_set_view", C.c_int, [_P, C.c_int, C.c_int]),
     ("irmv_engine_get_view", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("irmv_engine_debug_graph_count", C.c_int, [_P]),
@@ -355,6 +367,19 @@ def window_map(src_size, window, x0, y0, rotate180=True, camera_matrix=None, net
     m = WindowMap()
     check(load().irmv_window_map(C.byref(cfg), int(x0), int(y0), C.byref(m)))
     return dict(bx0=m.bx0, by0=m.by0, band_offset=m.band_offset, band_bytes=m.band_bytes, cx=m.cx, cy=m.cy)
+
+
+def tile_grid(src_size, window, overlap, rotate180=True, net_size=640, net_height=None):
+    """The tile grid of a tiled search (host only, irmv_tile_grid): -> (corners [(x, y)] row-major in result coordinates, nx, ny).
+    overlap: one number or (ox, oy), the least overlap of neighbouring tiles.  irmv_detection_amd.tiles.grid is its reference."""
+    import numpy as np
+    ox, oy = (overlap, overlap) if np.ndim(overlap) == 0 else overlap
+    cfg = _geometry_cfg(src_size, net_size, net_height, RESIZE_STRETCH, rotate180, SRC_HWC8, window)
+    n, nx, ny = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(load().irmv_tile_grid(C.byref(cfg), int(ox), int(oy), None, 0, C.byref(n), C.byref(nx), C.byref(ny)))
+    xy = (C.c_int32 * (2 * n.value))()
+    check(load().irmv_tile_grid(C.byref(cfg), int(ox), int(oy), xy, n.value, C.byref(n), C.byref(nx), C.byref(ny)))
+    return [(xy[2 * t], xy[2 * t + 1]) for t in range(n.value)], nx.value, ny.value
 
 
 def front_plan(src_size, net_size, net_height=None, resize_mode=RESIZE_STRETCH, rotate180=True, src_format=SRC_HWC8, window=None) -> dict:

@@ -89,6 +89,8 @@ irmv_engine::~irmv_engine()
     if (dets_host) (void)hipHostFree(dets_host);
     if (fout_host) (void)hipHostFree(fout_host);
     if (light_dets_host) (void)hipHostFree(light_dets_host);
+    for (auto &kv : tile_merges)
+        if (kv.second.out_host) (void)hipHostFree(kv.second.out_host);
     for (auto &kv : groups) {
         if (kv.second.h2d) (void)hipEventDestroy(kv.second.h2d);
         if (kv.second.out) (void)hipEventDestroy(kv.second.out);
@@ -501,6 +503,39 @@ extern "C" int irmv_window_map(const irmv_engine_cfg *cfg_in, int x0, int y0, ir
     if (int rc = resolve_cfg(cfg_in, &full)) return rc;
     if (full.win_width == 0) return fail(IRMV_ERR_ARG, "irmv_window_map: the configuration has no window (win_width, win_height)");
     return window_map(full.src_width, full.src_height, full.win_width, full.win_height, full.rotate180, full.camera_matrix, x0, y0, out);
+}
+
+// The tile grid of a tiled search, one axis: F the frame's extent, w the window's, ov the least overlap of neighbours.  The
+// fewest tiles that cover F with that overlap, spread evenly: corner i is i (F - w) / (n - 1) rounded to nearest.
+static int tile_axis(int F, int w, int ov, int *c, int cap)
+{
+    const int n = w == F ? 1 : (F - ov + (w - ov) - 1) / (w - ov);
+    if (n > cap) return n;
+    for (int i = 0; i < n; i++) c[i] = n == 1 ? 0 : (int)((2ll * i * (F - w) + (n - 1)) / (2ll * (n - 1)));
+    return n;
+}
+
+extern "C" int irmv_tile_grid(const irmv_engine_cfg *cfg_in, int min_overlap_x, int min_overlap_y, int32_t *xy, int cap, int *n, int *nx, int *ny)
+{
+    if (!cfg_in || !n) return fail(IRMV_ERR_ARG, "cfg/n is null");
+    irmv_engine_cfg full;
+    if (int rc = resolve_cfg(cfg_in, &full)) return rc;
+    if (full.win_width == 0) return fail(IRMV_ERR_ARG, "irmv_tile_grid: the configuration has no window (win_width, win_height)");
+    if (min_overlap_x < 0 || min_overlap_x >= full.win_width || min_overlap_y < 0 || min_overlap_y >= full.win_height)
+        return fail(IRMV_ERR_ARG, "irmv_tile_grid: the overlap must be in [0, window extent)");
+    int cx[IRMV_MAX_TILES], cy[IRMV_MAX_TILES];
+    const int gx = tile_axis(full.src_width, full.win_width, min_overlap_x, cx, IRMV_MAX_TILES);
+    const int gy = tile_axis(full.src_height, full.win_height, min_overlap_y, cy, IRMV_MAX_TILES);
+    if (gx > IRMV_MAX_TILES || gy > IRMV_MAX_TILES || gx * gy > IRMV_MAX_TILES)
+        return fail(IRMV_ERR_ARG, "irmv_tile_grid: the grid has more than IRMV_MAX_TILES tiles");
+    *n = gx * gy;
+    if (nx) *nx = gx;
+    if (ny) *ny = gy;
+    if (!xy) return IRMV_OK;
+    if (cap < gx * gy) return fail(IRMV_ERR_ARG, "irmv_tile_grid: cap is smaller than the grid");
+    for (int iy = 0; iy < gy; iy++)
+        for (int ix = 0; ix < gx; ix++) { xy[2 * (iy * gx + ix)] = cx[ix]; xy[2 * (iy * gx + ix) + 1] = cy[iy]; }
+    return IRMV_OK;
 }
 
 // The slot's entries of the two device tables from e->win_org[slot] and its view: the corner always, the camera with the

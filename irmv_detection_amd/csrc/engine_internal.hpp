@@ -6,6 +6,7 @@
 //   engine_tune.cpp   everything decided by timing at creation: conv tiles and their cache, head groups, the synchronous launch form
 //   engine_plan.cpp   head fusion, the sparse head's reordering, the launch list of each step kind
 //   engine_step.cpp   kernel arguments, the per-op launcher, steps, copies, graph capture, submit / wait / results
+//   engine_tiles.cpp  tiled search: the tile grid, tiled steps, the merge and its parameters
 //   engine_hooks.cpp  read-backs, debug_*, LDS fill / probe, conv and op test hooks, the profiler, the light trace
 #pragma once
 #include <hip/hip_runtime.h>
@@ -164,7 +165,8 @@ struct GraphKey {
     StepKind kind;
     bool upload;   // the frames' upload is the graph's first node
     int view;      // IRMV_VIEW_*: the view its slots were in when it was captured
-    bool operator<(const GraphKey &o) const { return std::tie(first, count, kind, upload, view) < std::tie(o.first, o.count, o.kind, o.upload, o.view); }
+    int frame_slot = -1;   // >= 0: a tiled step (irmv_engine_submit_tiles) whose slots all crop out of this slot's frame, merge node included
+    bool operator<(const GraphKey &o) const { return std::tie(first, count, kind, upload, view, frame_slot) < std::tie(o.first, o.count, o.kind, o.upload, o.view, o.frame_slot); }
 };
 
 // What a step sees in front of model.1's output -- the source frame and everything that follows from its size.  views[0]
@@ -266,6 +268,14 @@ struct irmv_engine {
     std::vector<int> sub_view;        // [S] ... as it was at the slot's last submit: whether its results carry the corner
     int front_ops[3] = {-1, -1, -1};  // ops preprocess, model.0.conv, model.1.conv: what a view whose front is not fused launches
     int front_op = -1;                // OP_FRONT: what a view whose front is fused launches in their place (-1: no view's is)
+    // Tiled search (irmv_engine_submit_tiles / irmv_engine_merge_tiles): nothing below exists until the first tiled call.
+    // tile_params_dev: the two floats the merge kernel reads when it runs (irmv_engine_set_tile_merge rewrites them, graphs hold
+    // the address).  tile_merges[first]: the merged list of the last tiled step or merge whose first slot was `first` -- device
+    // record, pinned copy, and whether one has run.
+    struct TileMerge { TileOut *out_dev = nullptr, *out_host = nullptr; int count = 0; bool valid = false; };
+    TileMergeParams *tile_params_dev = nullptr;
+    TileMergeParams tile_params{0.5f, 2.0f};
+    std::map<int, TileMerge> tile_merges;
     PnpConst pnp_base{};              // the camera as configured; pnp_dev[slot] = pnp_base with the principal point moved by the slot's corner
     std::vector<Tensor> tensors;
     std::map<std::string, int> tensor_idx;
@@ -357,15 +367,23 @@ void build_step_plans(irmv_engine *e, View &v);
 void fill_conv_args(const irmv_engine *e, const Op &op, int first, int count, ConvArgs &a, bool fused = false);
 int slots_view(const irmv_engine *e, int first, int count, int *view = nullptr);
 LightArgs light_args(const irmv_engine *e, const View &v, int first);
-PostArgs post_args(const irmv_engine *e, const View &v, int first);
+PostArgs post_args(const irmv_engine *e, const View &v, int first, bool dev_records = false);
 bool launch_head_group(const irmv_engine *e, const irmv_engine::HeadGroup &g, int first, const PostArgs *pa, unsigned scan, hipStream_t s);
-int launch_op(irmv_engine *e, const View &v, const Launch &l, int first, int count, const PostArgs &pa, unsigned scan, bool crop_pinned, hipStream_t s);
-int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipStream_t s, int reps, const std::vector<hipEvent_t> *ev, bool crop_pinned = false);
+int launch_op(irmv_engine *e, const View &v, const Launch &l, int first, int count, const PostArgs &pa, unsigned scan, bool crop_pinned, hipStream_t s, int tile_frame = -1);
+int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipStream_t s, int reps, const std::vector<hipEvent_t> *ev, bool crop_pinned = false, int tile_frame = -1);
 void mark_stepped(irmv_engine *e, int first, int count);
 int copy_out(irmv_engine *e, int first, int count, hipStream_t st = nullptr);
 int check_range(const irmv_engine *e, int first, int count);
 int load_frame(irmv_engine *e, int slot, hipStream_t st);
 void det_pose(const DevDet &d, bool shift, float ox, float oy, irmv_det &o);
+void slot_det(const irmv_engine *e, int slot, int i, irmv_det &o);
+int get_graph(irmv_engine *e, StepKind kind, int first, int count, bool upload, hipGraphExec_t *out, int tile_frame = -1);
+int group_of(irmv_engine *e, int first, int count, SlotGroup **out);
+bool upload_as_kernel(const irmv_engine *e, int first, int count);
+int copy_out_dev(irmv_engine *e, int first, int count, hipStream_t st);
+int upload_whole(irmv_engine *e, int slot, hipStream_t st, bool copy_engine = false);
+// engine_tiles.cpp
+TileArgs tile_args(const irmv_engine *e, int first, int count);
 // engine_hooks.cpp
 int ensure_dense_head(irmv_engine *e, int slot);
 }

@@ -101,8 +101,11 @@ static void launch_bayer(const irmv_engine *e, int first, int count, hipStream_t
     else launch_demosaic(bayer_args(e, first), count, s);
 }
 
-PostArgs irmv::post_args(const irmv_engine *e, const View &v, int first)
+// dev_records (tiled steps): the NMS writes device records also where the engine's ordinary steps write pinned host memory --
+// the merge kernel behind it reads them, and a D2H copy brings them to the host.
+PostArgs irmv::post_args(const irmv_engine *e, const View &v, int first, bool dev_records)
 {
+    const bool zero_copy = e->zero_copy_results && !dev_records;
     PostArgs p = e->post;
     p.scale_x = v.scale_x; p.scale_y = v.scale_y; p.off_x = v.off_x; p.off_y = v.off_y;
     p.head_all = e->head_all;
@@ -111,8 +114,8 @@ PostArgs irmv::post_args(const irmv_engine *e, const View &v, int first)
     p.boxes = e->boxes + (size_t)first * e->A * 4;
     p.keys = e->keys + (size_t)first * e->A * e->nc;
     p.key_cap = e->A * e->nc;
-    p.dets = (e->zero_copy_results ? e->dets_host_dev : e->dets_dev) + (size_t)first * e->cfg.max_det;
-    p.fout = (e->zero_copy_results ? e->fout_host_dev : e->fout_dev) + first;
+    p.dets = (zero_copy ? e->dets_host_dev : e->dets_dev) + (size_t)first * e->cfg.max_det;
+    p.fout = (zero_copy ? e->fout_host_dev : e->fout_dev) + first;
     if (p.dbg) p.dbg += (size_t)first * 16;
     p.counts = e->sw.split_scan ? e->cand_counts + first : nullptr;
     p.cand_bits = e->sparse_head ? e->cand_bits + (size_t)first * e->cand_words : nullptr;
@@ -121,17 +124,19 @@ PostArgs irmv::post_args(const irmv_engine *e, const View &v, int first)
 }
 
 // The crop of slots [first, first + count): out of their device frames, or (pinned) out of the pinned slots themselves.
-static CropArgs crop_args(const irmv_engine *e, int first, bool pinned)
+// tile_frame >= 0 (tiled steps): every slot's window is cut out of that slot's device frame.
+static CropArgs crop_args(const irmv_engine *e, int first, bool pinned, int tile_frame = -1)
 {
     CropArgs a{};
     a.src = pinned ? e->src_host_dev : e->full_dev; a.src_slot_bytes = e->full_bytes;
     a.dst = e->src_dev; a.dst_slot_bytes = e->frame_bytes;
     a.win = e->win_dev; a.first = first;
     a.full_w = e->full_w; a.full_h = e->full_h; a.win_w = e->cfg.src_width; a.win_h = e->cfg.src_height;
+    a.src_slot = tile_frame;
     return a;
 }
 
-static void launch_crop(const irmv_engine *e, int first, int count, bool pinned, hipStream_t s) { launch_window_crop(crop_args(e, first, pinned), count, s); }
+static void launch_crop(const irmv_engine *e, int first, int count, bool pinned, hipStream_t s, int tile_frame = -1) { launch_window_crop(crop_args(e, first, pinned, tile_frame), count, s); }
 
 static PreArgs pre_args(const irmv_engine *e, const View &v, const Op &op, int first)
 {
@@ -299,12 +304,14 @@ bool irmv::launch_head_group(const irmv_engine *e, const irmv_engine::HeadGroup 
 // The one place an op reaches the GPU: the kernel of l.op's kind on slots [first, first + count), stream s, as launch l of a
 // plan of view v says (irmv_engine_run_op: a plain Launch of the op).  scan: the members of l that append scan candidates to pa's key
 // lists (bit k: member k of a group, bit 0: a lone conv); crop_pinned: OP_CROP reads the pinned slots.
-int irmv::launch_op(irmv_engine *e, const View &v, const Launch &l, int first, int count, const PostArgs &pa, unsigned scan, bool crop_pinned, hipStream_t s)
+// tile_frame >= 0 (a tiled step): the demosaic runs ONCE, on that slot's raw frame, and the crop cuts every slot's window out of
+// that slot's device frame; every other op is the ordinary step's.
+int irmv::launch_op(irmv_engine *e, const View &v, const Launch &l, int first, int count, const PostArgs &pa, unsigned scan, bool crop_pinned, hipStream_t s, int tile_frame)
 {
     const Op &op = e->ops[l.op];
     switch (op.kind) {
-    case OP_DEMOSAIC: launch_bayer(e, first, count, s); break;
-    case OP_CROP: launch_crop(e, first, count, crop_pinned, s); break;
+    case OP_DEMOSAIC: if (tile_frame >= 0) launch_bayer(e, tile_frame, 1, s); else launch_bayer(e, first, count, s); break;
+    case OP_CROP: launch_crop(e, first, count, crop_pinned && tile_frame < 0, s, tile_frame); break;
     case OP_PRE: launch_preprocess(pre_args(e, v, op, first), count, s); break;
     case OP_FRONT: if (!launch_front(front_args(e, v, op, first), count, s)) return fail(IRMV_ERR_HIP, "fused front kernel: LDS request refused"); break;
     case OP_C2F2: launch_c2f2(c2f2_args(e, op, first), count, s); break;
@@ -341,11 +348,13 @@ int irmv::launch_op(irmv_engine *e, const View &v, const Launch &l, int first, i
 // (the caller has made sure they share one), in order.
 // ev != nullptr (irmv_engine_profile's events): launch i of the plan is repeated `reps` times (once if it is `once`) between
 // (*ev)[2 i] and (*ev)[2 i + 1].
-int irmv::enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipStream_t s, int reps, const std::vector<hipEvent_t> *ev, bool crop_pinned)
+// tile_frame >= 0: a tiled step of those slots on that slot's frame (launch_op), with device result records and the merge of
+// their lists (k_tiles.hip) as its last node.
+int irmv::enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipStream_t s, int reps, const std::vector<hipEvent_t> *ev, bool crop_pinned, int tile_frame)
 {
     const View &v = view_of(e, first);
     const std::vector<Launch> &plan = v.plans[kind];
-    const PostArgs pa = post_args(e, v, first);
+    const PostArgs pa = post_args(e, v, first, tile_frame >= 0);
     PostArgs mute = pa;   // (the table's twin with thresholds no logit passes: no key, no bit)
     mute.cls = e->cls_dev + 1;
     for (size_t i = 0; i < plan.size(); i++) {
@@ -356,9 +365,13 @@ int irmv::enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipS
             // a profiled launch is repeated: only its last repetition appends candidates.  With the sparse head the other
             // repetitions still run the step's kernel -- no class store --, behind the mute threshold.
             const bool last = rep == n - 1, muted = !last && l.scan && e->sparse_head;
-            TRY(launch_op(e, v, l, first, count, muted ? mute : pa, last || muted ? l.scan : 0u, crop_pinned, s));
+            TRY(launch_op(e, v, l, first, count, muted ? mute : pa, last || muted ? l.scan : 0u, crop_pinned, s, tile_frame));
         }
         if (ev) HIP_TRY(hipEventRecord((*ev)[2 * i + 1], s));
+    }
+    if (tile_frame >= 0) {
+        launch_tile_merge(tile_args(e, first, count), s);
+        HIP_TRY(hipGetLastError());
     }
     return IRMV_OK;
 }
@@ -398,7 +411,7 @@ static int copy_in(irmv_engine *e, int first, int count, hipStream_t st, bool ba
 }
 
 // One or two frames travel from the pinned slots as a KERNEL (k_pre.hip upload_frame_kernel), larger groups on the copy engine.
-static bool upload_as_kernel(const irmv_engine *e, int first, int count)
+bool irmv::upload_as_kernel(const irmv_engine *e, int first, int count)
 {
     return count <= 2 && e->sw.upload_kernel_blocks > 0 && e->src_host_dev && upload_aligned(e->src_bytes, first, count);
 }
@@ -422,10 +435,27 @@ static int upload_sync(irmv_engine *e, int first, int count, hipStream_t st, boo
     return IRMV_OK;
 }
 
+// One slot's pinned frame -> its device frame (raw slot of a Bayer engine), whole: never a band, never nothing (tiled steps).
+// copy_engine: not as the upload kernel (uploads on the side stream).
+int irmv::upload_whole(irmv_engine *e, int slot, hipStream_t st, bool copy_engine)
+{
+    const size_t off = (size_t)slot * e->src_bytes;
+    if (!copy_engine && upload_as_kernel(e, slot, 1)) launch_upload_frames(e->src_host_dev + off, upload_dev(e) + off, e->src_bytes, e->sw.upload_kernel_blocks, st);
+    else HIP_TRY(hipMemcpyAsync(upload_dev(e) + off, e->src_host + off, e->src_bytes, hipMemcpyHostToDevice, st));
+    return IRMV_OK;
+}
+
 int irmv::copy_out(irmv_engine *e, int first, int count, hipStream_t st)
 {
     if (!st) st = e->stream;
     if (e->zero_copy_results) return IRMV_OK;   // the kernel has already written the pinned records
+    return copy_out_dev(e, first, count, st);
+}
+
+// the device records of slots [first, first + count) -> their pinned twins (every step of an engine without zero-copy results;
+// tiled steps of any engine)
+int irmv::copy_out_dev(irmv_engine *e, int first, int count, hipStream_t st)
+{
     HIP_TRY(hipMemcpyAsync(e->dets_host + (size_t)first * e->cfg.max_det, e->dets_dev + (size_t)first * e->cfg.max_det,
                            (size_t)count * e->cfg.max_det * sizeof(DevDet), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(e->fout_host + first, e->fout_dev + first, (size_t)count * sizeof(DevFrameOut),
@@ -440,17 +470,20 @@ int irmv::check_range(const irmv_engine *e, int first, int count)
     return IRMV_OK;
 }
 
-static int get_graph(irmv_engine *e, StepKind kind, int first, int count, bool upload, hipGraphExec_t *out)
+// tile_frame >= 0: the graph of a tiled step on that slot's frame; its upload node moves that slot's whole frame.
+int irmv::get_graph(irmv_engine *e, StepKind kind, int first, int count, bool upload, hipGraphExec_t *out, int tile_frame)
 {
-    const GraphKey key{first, count, kind, upload, e->slot_view[first]};
+    const GraphKey key{first, count, kind, upload, e->slot_view[first], tile_frame};
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) { *out = it->second; return IRMV_OK; }
     hipGraph_t g = nullptr;
     HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     int rc = IRMV_OK;
-    if (upload)   // the frames' upload as the graph's first node (synchronous single-stream submits): one or two frames as a kernel
+    if (upload && tile_frame >= 0)
+        rc = upload_whole(e, tile_frame, e->stream);
+    else if (upload)   // the frames' upload as the graph's first node (synchronous single-stream submits): one or two frames as a kernel
         rc = upload_sync(e, first, count, e->stream, true);
-    if (!rc) rc = enqueue_step(e, kind, first, count, e->stream, 1, nullptr, upload && crop_from_pinned(e, first, count));
+    if (!rc) rc = enqueue_step(e, kind, first, count, e->stream, 1, nullptr, upload && tile_frame < 0 && crop_from_pinned(e, first, count), tile_frame);
     hipError_t ce = hipStreamEndCapture(e->stream, &g);
     if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
     if (ce != hipSuccess) return fail(IRMV_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
@@ -462,7 +495,7 @@ static int get_graph(irmv_engine *e, StepKind kind, int first, int count, bool u
     return IRMV_OK;
 }
 
-static int group_of(irmv_engine *e, int first, int count, SlotGroup **out)
+int irmv::group_of(irmv_engine *e, int first, int count, SlotGroup **out)
 {
     const auto key = std::make_pair(first, count);
     auto it = e->groups.find(key);
@@ -634,29 +667,32 @@ void irmv::det_pose(const DevDet &d, bool shift, float ox, float oy, irmv_det &o
     o.n_lights = d.n_lights;
 }
 
+// Record i of the slot's pinned result list as the ABI returns it (irmv_engine_results, irmv_engine_tile_results).
+void irmv::slot_det(const irmv_engine *e, int slot, int i, irmv_det &o)
+{
+    const DevDet &d = e->dets_host[(size_t)slot * e->cfg.max_det + i];
+    // device records of a step in the window view are window-local: the corner the slot was submitted with brings them to
+    // full-frame coordinates (a step in the frame view: nothing to add)
+    const bool shift = e->window && e->sub_view[slot] == IRMV_VIEW_WINDOW;
+    const float ox = shift ? (float)e->sub_org[slot].x : 0.f, oy = shift ? (float)e->sub_org[slot].y : 0.f;
+    memcpy(o.xyxy, d.xyxy, 16);
+    o.score = d.score;
+    // magic_enum::enum_cast<ArmorClass>(label).value_or(UNKNOWN), src/yolo_engine.cpp:216
+    o.class_id = (d.cls >= 0 && d.cls < IRMV_NUM_CLASSES) ? d.cls : IRMV_NUM_CLASSES;
+    o.anchor = d.anchor;
+    det_pose(d, shift, ox, oy, o);
+    o.reserved = 0;
+    if (shift)
+        for (int j = 0; j < 4; j++) o.xyxy[j] += (j & 1) ? oy : ox;
+}
+
 extern "C" int irmv_engine_results(irmv_engine *e, int slot, irmv_det *out, int cap, int *n)
 {
     TRY(check_range(e, slot, 1));
     if (!n || (cap > 0 && !out)) return fail(IRMV_ERR_ARG, "out/n is null");
     const DevFrameOut &fo = e->fout_host[slot];
     const int k = std::min(fo.num_dets, cap);
-    const DevDet *d = e->dets_host + (size_t)slot * e->cfg.max_det;
-    // device records of a step in the window view are window-local: the corner the slot was submitted with brings them to
-    // full-frame coordinates (a step in the frame view: nothing to add)
-    const bool shift = e->window && e->sub_view[slot] == IRMV_VIEW_WINDOW;
-    const float ox = shift ? (float)e->sub_org[slot].x : 0.f, oy = shift ? (float)e->sub_org[slot].y : 0.f;
-    for (int i = 0; i < k; i++) {
-        irmv_det &o = out[i];
-        memcpy(o.xyxy, d[i].xyxy, 16);
-        o.score = d[i].score;
-        // magic_enum::enum_cast<ArmorClass>(label).value_or(UNKNOWN), src/yolo_engine.cpp:216
-        o.class_id = (d[i].cls >= 0 && d[i].cls < IRMV_NUM_CLASSES) ? d[i].cls : IRMV_NUM_CLASSES;
-        o.anchor = d[i].anchor;
-        det_pose(d[i], shift, ox, oy, o);
-        o.reserved = 0;
-        if (shift)
-            for (int j = 0; j < 4; j++) o.xyxy[j] += (j & 1) ? oy : ox;
-    }
+    for (int i = 0; i < k; i++) slot_det(e, slot, i, out[i]);
     *n = k;
     return IRMV_OK;
 }

@@ -154,6 +154,7 @@ struct CropArgs {
     const int2 *win;          // [num_slots] top-left corner (x, y) in buffer coordinates; read when the kernel runs
     int first;
     int full_w, full_h, win_w, win_h;
+    int src_slot;             // -1: frame b is cut out of its own slot's frame; >= 0 (tiled steps): every frame out of this slot's
 };
 void launch_window_crop(const CropArgs &a, int batch, hipStream_t s);
 
@@ -454,6 +455,25 @@ void launch_nms_pnp(const PostArgs &a, int batch, hipStream_t s);
 constexpr int kScanBlocks = 16;   // workgroups per frame of scan_decode_kernel (more where a 16th of the keys would not fit kScanLdsMax)
 constexpr size_t kScanLdsMax = 159 * 1024;   // its dynamic LDS: 160 KiB per workgroup on gfx950, less its static variables
 void launch_scan_decode(const PostArgs &a, int batch, hipStream_t s);
+// tiled search (k_tiles.hip): the result lists of slots [first, first + count) -- windows of ONE frame -- merged into one
+constexpr int kMaxTiles = 16;     // == IRMV_MAX_TILES
+struct TileMergeParams { float ios_thr, edge_margin; };   // device memory, read when the kernel runs (irmv_engine_set_tile_merge)
+struct TileOut {
+    int32_t n_kept, n_in, pad_[2];
+    int32_t rec[256][4];          // [kMaxDetCap]: tile, index, cut, 0 of kept record i, in merge order
+};
+struct TileArgs {
+    const DevDet *dets;           // [num_slots][max_det] DEVICE records, window-local; tile t is slot first + t
+    const DevFrameOut *fout;      // [num_slots]
+    const int2 *win;              // [num_slots] corners in buffer coordinates (CropArgs::win)
+    const TileMergeParams *params;
+    TileOut *out;
+    int first, count, max_det;
+    int full_w, full_h, win_w, win_h, rotate180;
+};
+bool tile_merge_prepare();        // raises the kernel's LDS limit on the current device (outside any capture)
+void launch_tile_merge(const TileArgs &a, hipStream_t s);
+
 // ---- classical light extraction (k_light.hip) -------------
 constexpr int kLightLdsPoints = 256;         // contours up to this many points are sorted / hulled in LDS
 constexpr int kLightLdsImage = 40 * 1024;   // padded label images up to this many bytes live in LDS

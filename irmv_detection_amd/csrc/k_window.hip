@@ -18,8 +18,9 @@
 //
 // Bounds: an aligned source chunk may begin up to 15 bytes in front of the bytes a lane needs and end up to 15 behind them.
 // A chunk that would leave the slot's full frame [frame, frame + 3 full_w full_h) is not loaded: the destination chunk it
-// would have fed is copied byte by byte instead (this can only be the first and the last chunk of a frame).  Stores stay
-// inside the slot's window frame by construction: rows r < win_h, bytes < 3 win_w of each.
+// would have fed is copied byte by byte instead (this can only be the first and the last chunk of a frame).  A tiled step
+// (CropArgs::src_slot >= 0) cuts every slot's window out of ONE slot's frame: `frame` and `frame_end` are then that slot's.
+// Stores stay inside the slot's window frame by construction: rows r < win_h, bytes < 3 win_w of each.
 // Memory-bound: 3 win_w win_h bytes in, the same out.
 #include "irmv_common.hpp"
 
@@ -70,7 +71,8 @@ __global__ __launch_bounds__(256) void window_crop_kernel(CropArgs a)
     int2 org = a.win[slot];
     org.x = min(max(org.x, 0), a.full_w - a.win_w);   // (the host checks every origin it writes; a table entry cannot take the kernel out of its frame)
     org.y = min(max(org.y, 0), a.full_h - a.win_h);
-    const uint8_t *frame = a.src + (size_t)slot * a.src_slot_bytes;
+    // a tiled step cuts every slot's window out of ONE slot's frame; the bounds below follow that frame
+    const uint8_t *frame = a.src + (size_t)(a.src_slot >= 0 ? a.src_slot : slot) * a.src_slot_bytes;
     const uint8_t *frame_end = frame + (size_t)a.full_w * a.full_h * 3;
     uint8_t *out = a.dst + (size_t)slot * a.dst_slot_bytes;
     const int n = a.win_w * 3;                       // bytes of a window row

@@ -99,6 +99,8 @@ class YoloEngine:
     `set_window` / `set_window_center` move a slot's window between steps (irmv_detection_amd.window is the host reference);
     `set_view("frame")` runs a slot's next steps on the whole frame instead (the search after a lost target), `set_view("window")`
     goes back -- one engine, nothing uploaded or tuned twice.
+    `tile_grid` / `set_tiles` / `submit_tiles` / `tile_results`: the search at the sensor's resolution -- N slots run their
+    windows of ONE frame in one step, merged on the GPU into one list (irmv_detection_amd.tiles is the host reference).
     `set_class_policy` / `set_enemy_color` change per-class score thresholds, the colour mask and the per-class plate model of
     the living engine (irmv_detection_amd.class_policy is the host reference).
     """
@@ -156,6 +158,7 @@ class YoloEngine:
             capi.check(rc)
         self.src_image_size = (cfg.src_width, cfg.src_height)
         self.src_format = cfg.src_format
+        self._rotate180 = bool(cfg.rotate180)
         self.window_size = (cfg.win_width, cfg.win_height) if cfg.win_width else None
         self.bayer_demosaic = "mhc" if cfg.bayer_demosaic == capi.DEMOSAIC_MHC else "bilinear"
         self.net_size = net_size                 # the width (and, square, the height)
@@ -275,6 +278,55 @@ class YoloEngine:
         v, w, h = C.c_int(0), C.c_int(0), C.c_int(0)
         capi.check(self._L.irmv_engine_get_view(self._h, slot, C.byref(v), C.byref(w), C.byref(h)))
         return ("frame" if v.value == capi.VIEW_FRAME else "window"), (w.value, h.value)
+
+    # ---- tiled search ------------------------------------------------------------------
+    def tile_grid(self, overlap):
+        """The grid of a tiled search of this engine's frame with its window: -> (corners, nx, ny), corners row-major (x, y)
+        in result coordinates; overlap: one number or (ox, oy), the least overlap of neighbours (irmv_tile_grid)."""
+        if self.window_size is None:
+            raise IrmvError(capi.ERR_ARG, "the engine has no window")
+        return capi.tile_grid(self.src_image_size, self.window_size, overlap, rotate180=self._rotate180,
+                              net_size=self.net_width, net_height=self.net_height)
+
+    def set_tiles(self, corners, first: int = 0) -> None:
+        """Slots first, first + 1, ... become the tiles at `corners` (set_window per slot; moving one re-captures nothing)."""
+        for t, (x, y) in enumerate(corners):
+            self.set_window(x, y, first + t)
+
+    def submit_tiles(self, frame_slot: int = 0, first: int = 0, count: Optional[int] = None, h2d: bool = True, async_upload: bool = False) -> None:
+        """One tiled step: slots [first, first + count) each run their window of frame_slot's full frame, and the step's last
+        node merges their lists (irmv_engine_submit_tiles).  Collect with wait_slots(first, count) and tile_results(first)."""
+        count = self.num_slots - first if count is None else count
+        flags = (capi.SUBMIT_H2D if h2d else 0) | (capi.SUBMIT_ASYNC_UPLOAD if (h2d and async_upload) else 0)
+        capi.check(self._L.irmv_engine_submit_tiles(self._h, frame_slot, first, count, flags))
+
+    def merge_tiles(self, first: int = 0, count: Optional[int] = None) -> None:
+        """Test hook: the merge alone, on the slots' current results and corners (irmv_engine_merge_tiles)."""
+        count = self.num_slots - first if count is None else count
+        capi.check(self._L.irmv_engine_merge_tiles(self._h, first, count))
+
+    def tile_results_raw(self, first: int = 0):
+        """(records, n_in): the merged list as capi.TileDet records, and the number of records that entered the merge."""
+        out = (capi.TileDet * self.max_det)()
+        n, n_in = C.c_int(0), C.c_int(0)
+        capi.check(self._L.irmv_engine_tile_results(self._h, first, out, self.max_det, C.byref(n), C.byref(n_in)))
+        return [out[i] for i in range(n.value)], n_in.value
+
+    def tile_results(self, first: int = 0) -> List[Armor]:
+        """The merged list of the last tiled step (or merge_tiles) whose first slot was `first`, in full-frame coordinates."""
+        return [self._to_armor(r.det) for r in self.tile_results_raw(first)[0]]
+
+    def set_tile_merge(self, ios_thr: float = 0.5, edge_margin: float = 2.0) -> None:
+        """The merge's parameters, live: a record loses to a kept one of another tile and the same class when their
+        intersection exceeds ios_thr of the smaller box; a box within edge_margin source pixels of a tile edge inside the
+        frame ranks behind every whole box.  Neither default has been validated on a trained model."""
+        capi.check(self._L.irmv_engine_set_tile_merge(self._h, float(ios_thr), float(edge_margin)))
+
+    @property
+    def tile_merge(self) -> Tuple[float, float]:
+        a, b = C.c_float(0), C.c_float(0)
+        capi.check(self._L.irmv_engine_get_tile_merge(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def debug_graph_count(self) -> int:
         """Test hook: the captured graphs the engine holds."""
