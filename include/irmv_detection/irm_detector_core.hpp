@@ -93,6 +93,8 @@ public:
     int enemy_color = -1;                                // the node's enemy_color (:154-160, "0 for blue, 1 for red"): 0 keeps B1..BS, 1 keeps R1..RS,
                                                          // on the GPU where candidates are emitted; -1: no filter (what the reference's unused parameter amounts to)
     std::vector<int> large_plate_classes;                // ArmorClass values whose detections PnP solves with the 225 mm plate; the rest: 135 mm
+    int point_source = IRMV_POINTS_AUTO;                 // IRMV_POINTS_*; IRMV_POINTS_REFINED: a pose model's points snapped to the light bars, inside the step
+    double refine_snap = 0.5, refine_roi_margin = 4.0;   // its two live parameters (irmv_engine_set_refine; set_parameter "refine.snap" / "refine.roi_margin")
   };
 
   // What one frame produced, beyond the message: kept for debug publishers and tests.
@@ -112,8 +114,9 @@ public:
     for (auto & e : yolo_engines_) {
       e = std::make_unique<YoloEngine>(model_path, p.image_input_size, p.profiling, p.device, false, p.net_input_size.width > 0 ? p.net_input_size.width : -1,
                                        IRMV_SRC_HWC8, std::array<uint16_t, 3>{256, 256, 256}, p.net_input_size.height > 0 ? p.net_input_size.height : -1,
-                                       IRMV_DEMOSAIC_BILINEAR, p.window_size, p.tile_overlap);
+                                       IRMV_DEMOSAIC_BILINEAR, p.window_size, p.tile_overlap, p.point_source);
       push_params(*e);
+      if (p.refine_snap != 0.5 || p.refine_roi_margin != 4.0) e->set_refine(float(p.refine_snap), float(p.refine_roi_margin));
       if (p.enemy_color != -1 || !p.large_plate_classes.empty()) push_class_policy(*e);
     }
     yolo_engines_[0]->warm_up();   // the tile choices are shared by the three engines: one warm-up tunes for all
@@ -197,6 +200,13 @@ public:
       if (c < -1 || c > 1) return false;
       params_.enemy_color = c;
       for (auto & e : yolo_engines_) e->set_enemy_color(c);   // (thresholds and plates set on an engine(id) stay)
+      return true;
+    }
+    else if (name == "refine.snap" || name == "refine.roi_margin") {   // live, and re-captures nothing
+      const double snap = name == "refine.snap" ? value : params_.refine_snap, margin = name == "refine.roi_margin" ? value : params_.refine_roi_margin;
+      if (!(snap > 0.0 && snap <= 4.0) || !(margin >= 0.0 && margin <= 64.0)) return false;
+      params_.refine_snap = snap; params_.refine_roi_margin = margin;
+      for (auto & e : yolo_engines_) e->set_refine(float(snap), float(margin));
       return true;
     }
     else return false;

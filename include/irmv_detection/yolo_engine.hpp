@@ -81,10 +81,13 @@ public:
   // the tracking slot and owns the frame, slots 1.. hold the grid irmv_tile_grid gives for that least overlap of neighbouring
   // windows, set once.  detect_tiles() then searches the frame already in get_src_image_buffer() at the sensor's resolution:
   // every tile runs its window of that frame in ONE step and the step merges their lists (include/irmv_hip.h, "tiled search").
+  // `point_source` (IRMV_POINTS_*): IRMV_POINTS_REFINED snaps the keypoint head's points to the light bars found at them, inside
+  // the step (include/irmv_hip.h, "refined point source"); set_refine() changes its two parameters live.
   YoloEngine(const std::string & onnx_file_path, cv::Size src_image_size, bool enable_profiling = false, int device = -1,
              bool warm_up_now = true, int net_size = -1, int src_format = IRMV_SRC_HWC8,
              std::array<uint16_t, 3> bayer_gain_q8 = {256, 256, 256}, int net_height = -1,
-             int bayer_demosaic = IRMV_DEMOSAIC_BILINEAR, cv::Size window = {}, cv::Size tile_overlap = cv::Size(-1, -1))
+             int bayer_demosaic = IRMV_DEMOSAIC_BILINEAR, cv::Size window = {}, cv::Size tile_overlap = cv::Size(-1, -1),
+             int point_source = IRMV_POINTS_AUTO)
   : src_image_size_(src_image_size), window_size_(window), enable_profiling_(enable_profiling)
   {
     irmv_engine_cfg cfg;
@@ -100,6 +103,7 @@ public:
     cfg.win_width = window.width;
     cfg.win_height = window.height;
     cfg.num_slots = 1;  // one engine per TripleBuffer slot, like the reference node
+    cfg.point_source = point_source;
     std::vector<int32_t> tile_xy;
     if (tile_overlap.width >= 0 && tile_overlap.height >= 0) {
       int nx = 0, ny = 0;
@@ -143,7 +147,17 @@ public:
 
   // true: the model has a keypoint head and every detection carries its four armor points and pose (irmv_det);
   // false: a bbox-only model like the reference's -- the points come from extract_armors()
-  bool has_keypoint_head() const { return irmv_engine_point_source(engine_) == IRMV_POINTS_KEYPOINT_HEAD; }
+  // (a refined engine is a keypoint engine whose points were snapped to the light bars)
+  bool has_keypoint_head() const { return irmv_engine_point_source(engine_) == IRMV_POINTS_KEYPOINT_HEAD || refines_points(); }
+  bool refines_points() const { return irmv_engine_point_source(engine_) == IRMV_POINTS_REFINED; }
+
+  // The refined point source's two live parameters (irmv_engine_set_refine): defaults 0.5 and 4 source pixels, neither
+  // validated on a trained model.  Waits for the steps in flight; re-captures nothing.
+  void set_refine(float snap, float roi_margin)
+  {
+    if (irmv_engine_set_refine(engine_, snap, roi_margin) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::set_refine: ") + irmv_last_error());
+  }
 
   // The node's live parameters of the classical extraction (src/irm_detector.cpp:372-403)
   void set_extract_params(int binary_threshold, float light_min_ratio, float light_max_ratio, float light_max_angle, double min_small_cd,

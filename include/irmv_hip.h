@@ -40,6 +40,7 @@ extern "C" {
 #define IRMV_POINTS_AUTO 0
 #define IRMV_POINTS_KEYPOINT_HEAD 1
 #define IRMV_POINTS_CLASSICAL 2 /* gray -> threshold -> contours -> minAreaRect -> lights, on the GPU */
+#define IRMV_POINTS_REFINED 3   /* the keypoint head's points, snapped to the light bars found at them (irmv_engine_set_refine) */
 
 /* Format of the frames a producer writes into the source slots (irmv_engine_cfg.src_format).
  *   IRMV_SRC_HWC8: H x W x 3 bytes per slot, interleaved pixels in the model's channel order (swap_rb = 0) -- the reference's
@@ -111,7 +112,8 @@ typedef struct irmv_engine_cfg {
                                   flight: 6.1 k FPS against 2.7 k one at a time) */
     /* Source of the four armor points PnP consumes.  The reference obtains them by classical CV inside
      * each bbox (IrmDetector::extract_armors, src/irm_detector.cpp:292-355); a pose-style model carries them
-     * in a keypoint head.  IRMV_POINTS_AUTO picks the keypoint head when the model has one. */
+     * in a keypoint head.  IRMV_POINTS_AUTO picks the keypoint head when the model has one (never IRMV_POINTS_REFINED, which
+     * like IRMV_POINTS_KEYPOINT_HEAD is refused with IRMV_ERR_MODEL on a model without a keypoint head). */
     int32_t point_source;      /* IRMV_POINTS_* */
     int32_t binary_threshold;  /* 150 (src/irm_detector.cpp:152) */
     float light_min_ratio;     /* 0.1 */
@@ -174,8 +176,12 @@ typedef struct irmv_det {
                             bboxes cover more than 8 frame areas in total, or one bbox holds more than 1024 contours /
                             4096 contour points) -- reported, never replaced by a truncated result */
     int32_t armor_size;  /* IRMV_ARMOR_*: classical path derives it from the light-centre distance (src/irm_detector.cpp:340-341) */
-    int32_t n_lights;    /* classical path: lights that passed is_light() in this bbox */
-    int32_t reserved;
+    int32_t n_lights;    /* classical path: lights that passed is_light() in this bbox; refined path: in the guided ROI */
+    int32_t reserved;    /* IRMV_POINTS_REFINED engines and irmv_engine_refine_points: the refine flag --
+                            1: kpts and the pose are the light bars'; 0: the head's points kept (no admissible pair, one light for
+                            both sides, unusable keypoints, or PnP refused the new quad); -1: the head's points kept because the
+                            extraction had no answer (label pool, contour or point limit: where the classical source reports
+                            armor_valid = -1).  Every other engine: 0 */
 } irmv_det;
 
 /* EfficientNMS-layout view of one frame's result in net-input coordinates
@@ -447,8 +453,39 @@ int irmv_engine_extract_armors(irmv_engine *e, int slot, const float *xyxy, int 
  * Takes effect from the next submit / extract call. */
 int irmv_engine_set_extract_params(irmv_engine *e, int binary_threshold, float light_min_ratio, float light_max_ratio,
                                    float light_max_angle, const double center_distances[4]);
-/* IRMV_POINTS_KEYPOINT_HEAD or IRMV_POINTS_CLASSICAL: where this engine's four armor points come from (AUTO resolved). */
+/* IRMV_POINTS_KEYPOINT_HEAD, IRMV_POINTS_CLASSICAL or IRMV_POINTS_REFINED: where this engine's four armor points come from
+ * (AUTO resolved). */
 int irmv_engine_point_source(const irmv_engine *e);
+
+/* ---- refined point source (IRMV_POINTS_REFINED) ------------------------------------------
+ * A refined engine runs the keypoint engine's step; behind the NMS a guided light extraction (one more launch, profile name
+ * light_refine) takes each detection's four keypoints LB, LT, RT, RB as a prior and replaces them by the ends of the light
+ * bars found at them.  Where no bar is found the head's points and pose stay untouched.  Per detection, all in fp32 and in
+ * the written association order, in the pixels of the frame of the slot's view (a window engine: the window's):
+ *   1. All eight keypoint values are finite and below 2^24 in magnitude; else flag 0, n_lights 0, nothing is extracted.
+ *   2. Guided ROI: gx1 = min(x1, min kx) - roi_margin, gy1 = min(y1, min ky) - roi_margin, gx2 = max(x2, max kx) + roi_margin,
+ *      gy2 = max(y2, max ky) + roi_margin, then clamped to the frame and truncated like a bbox of the classical source.  The
+ *      label pool is handed out in detection order over these ROIs.  (A bar that ends at the bbox's edge would be cut by the
+ *      bbox's own ROI and measure a stump: hence the margin.)
+ *   3. Lights as the classical source finds them (threshold, external contours of >= 5 points, minimum-area rectangle,
+ *      is_light); n_lights counts those of the ROI.
+ *   4. Side L: (B, T) = (kpts[0..1], kpts[2..3]); side R: (B, T) = (kpts[6..7], kpts[4..5]).  A light with ends b (bottom),
+ *      t (top) has cost = ((b.x-B.x)^2 + (b.y-B.y)^2) + ((t.x-T.x)^2 + (t.y-T.y)^2) and, with len2 = (B.x-T.x)^2 + (B.y-T.y)^2,
+ *      is admissible for the side iff cost <= (snap * snap) * len2.
+ *   5. Per side the admissible light of least cost; on equal cost the contour found later (the classical source prefers the
+ *      same direction).
+ *   6. Refined iff both sides have a light, the two are different contours and PnP on {L.bottom, L.top, R.top, R.bottom}
+ *      succeeds -- with the plate the keypoint path uses (the class policy's plate[cls]; cfg.armor_size for explicit boxes) and
+ *      the slot's camera.  Then kpts, rvec, tvec, quat and pnp_ok are replaced; a quad PnP refuses changes nothing.
+ *   7. armor_valid stays 1, armor_size the policy's plate; irmv_raw_dets.det_kpts stay the net's output.
+ *   8. irmv_det.reserved carries the flag (see there).
+ * The two parameters are live like the tile merge's: the kernel reads them from device memory when it runs, the setter waits
+ * for every step in flight and re-captures nothing.  Defaults: snap = 0.5, allowed (0, 4]; roi_margin = 4.0 source pixels,
+ * allowed [0, 64].  Neither default has been validated on a trained model -- none exists here --, which is why both are live.
+ * IRMV_ERR_ARG (and nothing changes): a value outside its range or NaN.  Both calls work on an engine of any point source:
+ * irmv_engine_refine_points uses the parameters.  irmv_detection_amd/refine.py is the host reference of rules 1, 2, 4, 5, 8. */
+int irmv_engine_set_refine(irmv_engine *e, float snap, float roi_margin);
+int irmv_engine_get_refine(const irmv_engine *e, float *snap, float *roi_margin);
 
 /* ---- stage-wise read-backs used by the parity tests -------------------- */
 int irmv_engine_read_input(irmv_engine *e, int slot, float *chw);             /* [3][net_h][net_w], as the reference's input_buffer_ */
@@ -578,6 +615,11 @@ typedef struct irmv_light_trace {
 /* irmv_engine_extract_armors with a record of the kernel's stages: the same launch on the same scratch, plus trace[n].
  * out receives exactly what irmv_engine_extract_armors gives. */
 int irmv_engine_light_trace(irmv_engine *e, int slot, const float *xyxy, int n, irmv_light_trace *trace, irmv_det *out);
+/* The guided extraction on n explicit boxes (xyxy) and their keypoints (kpts[n][8]: LB, LT, RT, RB) on the slot's current
+ * frame, on an engine of any point source; coordinates, window and view as irmv_engine_extract_armors.  out[i]: kpts, the
+ * pose (plate cfg.armor_size), n_lights and reserved = the flag; where the flag is not 1, kpts are the inputs and the pose is
+ * theirs.  trace: NULL, or trace[n] as irmv_engine_light_trace fills it (rx..rh: the guided ROI). */
+int irmv_engine_refine_points(irmv_engine *e, int slot, const float *xyxy, const float *kpts, int n, irmv_light_trace *trace, irmv_det *out);
 /* Host only: out = {max_contours, points_cap, lds_image, lds_points} without an engine. */
 int irmv_light_limits(int32_t out[4]);
 

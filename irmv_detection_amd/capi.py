@@ -15,7 +15,7 @@ RESIZE_STRETCH, RESIZE_LETTERBOX = 0, 1
 ARMOR_SMALL, ARMOR_LARGE = 0, 1
 SUBMIT_H2D = 1
 SUBMIT_ASYNC_UPLOAD = 2
-POINTS_AUTO, POINTS_KEYPOINT_HEAD, POINTS_CLASSICAL = 0, 1, 2
+POINTS_AUTO, POINTS_KEYPOINT_HEAD, POINTS_CLASSICAL, POINTS_REFINED = 0, 1, 2, 3
 SRC_HWC8, SRC_BAYER_RGGB8, SRC_BAYER_BGGR8, SRC_BAYER_GRBG8, SRC_BAYER_GBRG8 = 0, 1, 2, 3, 4
 BAYER_FORMATS = {"RGGB": SRC_BAYER_RGGB8, "BGGR": SRC_BAYER_BGGR8, "GRBG": SRC_BAYER_GRBG8, "GBRG": SRC_BAYER_GBRG8}
 DEMOSAIC_BILINEAR, DEMOSAIC_MHC = 0, 1
@@ -198,6 +198,9 @@ SYMBOLS = [
     ("irmv_engine_wait_upload", C.c_int, [_P, C.c_int, C.c_int]),
     ("irmv_engine_set_extract_params", C.c_int, [_P, C.c_int, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double)]),
     ("irmv_engine_point_source", C.c_int, [_P]),
+    ("irmv_engine_set_refine", C.c_int, [_P, C.c_float, C.c_float]),
+    ("irmv_engine_get_refine", C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("irmv_engine_refine_points", C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.POINTER(LightTrace), C.POINTER(Det)]),
     ("irmv_engine_results", C.c_int, [_P, C.c_int, C.POINTER(Det), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_engine_detect", C.c_int, [_P, C.c_int, C.POINTER(Det), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_engine_last_detect_ms", C.c_double, [_P]),

@@ -6,7 +6,7 @@
 //   * frame slots are pinned host memory (hipHostMalloc) copied to HBM by an
 //     async copy on a dedicated upload stream, event-chained to the captured
 //     step (results need no download: the NMS kernel stores its records straight into mapped pinned host memory;
-//     only the classical-extraction mode keeps device records + one D2H copy) -- the dGPU
+//     only the classical and the refined point source keep device records + one D2H copy) -- the dGPU
 //     answer to the reference's cudaMallocManaged source buffer (:60-61) +
 //     TripleBuffer: slot n+1 uploads while slot n computes;
 //   * one set of weights per device shared by all slots (the reference builds
@@ -387,6 +387,33 @@ extern "C" int irmv_front_plan(const irmv_engine_cfg *cfg_in, irmv_front_plan_t 
     return IRMV_OK;
 }
 
+static int refined_needs_head() { return fail(IRMV_ERR_MODEL, "point_source = refined, but the model has no keypoint head"); }
+
+// nk of the blob's header without a GPU call: -1 where only the device holds the blob; an unreadable or short blob is left
+// to load_blob's own errors (-1 too).
+static int peek_blob_nk(const irmv_engine_cfg &c, int *nk)
+{
+    uint8_t h[32] = {0};   // engine_graph.cpp BlobHeader
+    *nk = -1;
+    size_t got = 0;
+    if (c.weights_path) {
+        std::string path = c.weights_path;
+        const size_t dot = path.find_last_of('.');
+        if (dot != std::string::npos && path.substr(dot) != ".irmw") path = path.substr(0, dot) + ".irmw";
+        std::ifstream f(path, std::ios::binary);
+        if (f) { f.read(reinterpret_cast<char *>(h), sizeof h); got = (size_t)f.gcount(); }
+    } else if (c.weights_blob && c.weights_bytes && !c.weights_on_device) {
+        got = std::min<size_t>(sizeof h, c.weights_bytes);
+        memcpy(h, c.weights_blob, got);
+    }
+    if (got == sizeof h && memcmp(h, "IRMW", 4) == 0) {   // char magic[4]; uint32_t version, nc, nk, ...
+        uint32_t v;
+        memcpy(&v, h + 12, 4);
+        *nk = (int)std::min<uint32_t>(v, 1u << 20);
+    }
+    return IRMV_OK;
+}
+
 extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **out)
 {
     if (!cfg_in || !out) return fail(IRMV_ERR_ARG, "cfg/out is null");
@@ -398,7 +425,14 @@ extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **o
     if (cfg->pre_nms_cap < 1 || cfg->pre_nms_cap > IRMV_CAND_CAP) return fail(IRMV_ERR_ARG, "pre_nms_cap must be 1..8192");
     if (!(cfg->score_thr > 0.f && cfg->score_thr < 1.f)) return fail(IRMV_ERR_ARG, "score_thr must be in (0, 1)");
     if (cfg->armor_size != IRMV_ARMOR_SMALL && cfg->armor_size != IRMV_ARMOR_LARGE) return fail(IRMV_ERR_ARG, "bad armor_size");
-    if (cfg->point_source < 0 || cfg->point_source > 2) return fail(IRMV_ERR_ARG, "bad point_source");
+    if (cfg->point_source < 0 || cfg->point_source > IRMV_POINTS_REFINED) return fail(IRMV_ERR_ARG, "bad point_source");
+    // The refined source needs the keypoint head: where the blob's header can be read without the GPU (a path, host memory)
+    // a model without one is refused here, before any HIP call; a blob in device memory right after it has been fetched.
+    if (cfg->point_source == IRMV_POINTS_REFINED) {
+        int nk = -1;
+        if (int rc = peek_blob_nk(*cfg, &nk)) return rc;
+        if (nk >= 0 && nk < 8) return refined_needs_head();
+    }
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (cfg->device < 0 || cfg->device >= ndev) return fail(IRMV_ERR_HIP, "no such HIP device");
@@ -419,6 +453,7 @@ extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **o
     e->cfg.weights_path = nullptr;  // caller-owned, not retained
     e->cfg.weights_blob = nullptr;
     if (rc) return rc;
+    if (cfg->point_source == IRMV_POINTS_REFINED && e->nk < 8) return refined_needs_head();   // (nothing is allocated yet)
     TRY(build_engine(e.get()));
     TRY(autotune_convs(e.get()));
     finalize_head_fusion(e.get());
@@ -628,7 +663,35 @@ int irmv::write_isp_table(irmv_engine *e)
 extern "C" int irmv_engine_point_source(const irmv_engine *e)
 {
     if (!e) return -1;
-    return e->classical ? IRMV_POINTS_CLASSICAL : IRMV_POINTS_KEYPOINT_HEAD;
+    return e->refined ? IRMV_POINTS_REFINED : e->classical ? IRMV_POINTS_CLASSICAL : IRMV_POINTS_KEYPOINT_HEAD;
+}
+
+// ---- refined point source: the two live parameters ------------------------------------
+// snap in (0, 4], roi_margin in [0, 64] source pixels; NaN fails both comparisons.  Host only.
+static int check_refine(float snap, float roi_margin)
+{
+    if (!(snap > 0.f && snap <= 4.f)) return fail(IRMV_ERR_ARG, "irmv_engine_set_refine: snap must be in (0, 4]");
+    if (!(roi_margin >= 0.f && roi_margin <= 64.f)) return fail(IRMV_ERR_ARG, "irmv_engine_set_refine: roi_margin must be in [0, 64]");
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_set_refine(irmv_engine *e, float snap, float roi_margin)
+{
+    TRY(check_refine(snap, roi_margin));   // (the values first: a refused one never reaches the engine)
+    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));   // every stream of the engine: no launch in flight reads the pair
+    e->refine = RefineParams{snap, roi_margin};
+    if (e->refine_dev) HIP_TRY(hipMemcpy(e->refine_dev, &e->refine, sizeof e->refine, hipMemcpyHostToDevice));
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_get_refine(const irmv_engine *e, float *snap, float *roi_margin)
+{
+    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
+    if (snap) *snap = e->refine.snap;
+    if (roi_margin) *roi_margin = e->refine.roi_margin;
+    return IRMV_OK;
 }
 
 extern "C" int irmv_engine_set_extract_params(irmv_engine *e, int binary_threshold, float light_min_ratio, float light_max_ratio,
@@ -648,8 +711,8 @@ extern "C" int irmv_engine_set_extract_params(irmv_engine *e, int binary_thresho
     c.light_min_ratio = light_min_ratio; c.light_max_ratio = light_max_ratio; c.light_max_angle = light_max_angle;
     c.armor_min_small_center_distance = cd[0]; c.armor_max_small_center_distance = cd[1];
     c.armor_min_large_center_distance = cd[2]; c.armor_max_large_center_distance = cd[3];
-    // captured steps of the classical mode carry these values as kernel arguments: re-capture on next use
-    if (e->classical) {
+    // captured steps of the classical and the refined mode carry these values as kernel arguments: re-capture on next use
+    if (e->classical || e->refined) {
         for (auto &g : e->graphs) (void)hipGraphExecDestroy(g.second);
         e->graphs.clear();
     }

@@ -545,7 +545,7 @@ static void add_front_op(irmv_engine *e, double frame_bytes)
 // scratch of the classical extraction that grows with the view's frame: per slot a padded label image
 static int alloc_view_light(irmv_engine *e, View &v)
 {
-    const size_t SL = e->classical ? (size_t)e->cfg.num_slots : 1;   // keypoint mode keeps one slot's worth for irmv_engine_extract_armors
+    const size_t SL = (e->classical || e->refined) ? (size_t)e->cfg.num_slots : 1;   // keypoint mode keeps one slot's worth for irmv_engine_extract_armors
     v.light_pool = std::max<size_t>((size_t)8 * v.src_w * v.src_h, (size_t)(v.src_w + 2) * (v.src_h + 2) + 16);
     return dev_alloc(e, (void **)&v.light_labels, SL * v.light_pool);
 }
@@ -834,13 +834,23 @@ static int build_post_stage(irmv_engine *e)
       op.bytes = (double)e->A * 64.0; e->ops.push_back(op); }
     if (c.point_source == IRMV_POINTS_KEYPOINT_HEAD && e->nk < 8) return fail(IRMV_ERR_MODEL, "point_source = keypoint head, but the model has none");
     e->classical = c.point_source == IRMV_POINTS_CLASSICAL || (c.point_source == IRMV_POINTS_AUTO && e->nk < 8);
-    e->zero_copy_results = !e->classical && e->sw.zero_copy_results;
+    e->refined = c.point_source == IRMV_POINTS_REFINED;   // (irmv_engine_create has refused a model without a keypoint head; AUTO never resolves to it)
+    // the light kernel reads and rewrites the records: not across PCIe
+    e->zero_copy_results = !e->classical && !e->refined && e->sw.zero_copy_results;
     if (e->classical) {
         Op op; op.kind = OP_LIGHT; op.layer = "extract_armors"; snprintf(op.kname, sizeof op.kname, "light_extract");
         e->ops.push_back(op);
     }
+    if (e->refined) {   // the guided instantiation behind the NMS: the keypoints it decoded are the prior
+        Op op; op.kind = OP_LIGHT; op.layer = "refine_points"; snprintf(op.kname, sizeof op.kname, "light_refine");
+        e->ops.push_back(op);
+        TRY(dev_alloc(e, (void **)&e->refine_dev, sizeof(RefineParams)));
+        HIP_TRY(hipMemcpy(e->refine_dev, &e->refine, sizeof e->refine, hipMemcpyHostToDevice));
+        TRY(dev_alloc(e, (void **)&e->refine_kpts, (size_t)S * c.max_det * 8 * sizeof(float)));
+        HIP_TRY(hipMemset(e->refine_kpts, 0, (size_t)S * c.max_det * 8 * sizeof(float)));
+    }
     // scratch of the classical extraction: per detection a padded label image (ROIs up to ~510 x 510) and contour points
-    const size_t SL = e->classical ? (size_t)S : 1;   // keypoint mode keeps one slot's worth for irmv_engine_extract_armors
+    const size_t SL = (e->classical || e->refined) ? (size_t)S : 1;   // keypoint mode keeps one slot's worth for irmv_engine_extract_armors
     TRY(alloc_view_light(e, e->views[IRMV_VIEW_WINDOW]));
     TRY(dev_alloc(e, (void **)&e->light_points, SL * c.max_det * kLightPointsCap * 2 * sizeof(short)));
     TRY(dev_alloc(e, (void **)&e->light_hulls, SL * c.max_det * kLightPointsCap * 4 * sizeof(short)));

@@ -64,8 +64,23 @@ static_assert(sizeof(irmv_light_rec) == sizeof(LightTraceRec) && sizeof(irmv_lig
                   IRMV_LIGHT_MAX_CONTOURS == kLightMaxContours && IRMV_LIGHT_POINTS_CAP == kLightPointsCap,
               "irmv_light_trace is LightTrace");
 
-// irmv_engine_extract_armors; trace != nullptr: irmv_engine_light_trace (the kernel also records its stages)
-static int extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, irmv_light_trace *trace, irmv_det *out)
+// The guided launch's device state on an engine that is not a refined one, made by its first irmv_engine_refine_points: the
+// parameter pair and one slot's worth of prior.
+static int ensure_refine(irmv_engine *e)
+{
+    if (!e->refine_dev) {
+        RefineParams *p = nullptr;
+        TRY(dev_alloc(e, (void **)&p, sizeof(RefineParams)));
+        HIP_TRY(hipMemcpy(p, &e->refine, sizeof e->refine, hipMemcpyHostToDevice));
+        e->refine_dev = p;
+    }
+    if (!e->refine_kpts) TRY(dev_alloc(e, (void **)&e->refine_kpts, (size_t)e->cfg.max_det * 8 * sizeof(float)));
+    return IRMV_OK;
+}
+
+// irmv_engine_extract_armors; trace != nullptr: irmv_engine_light_trace (the kernel also records its stages);
+// kpts != nullptr: irmv_engine_refine_points (the guided instantiation on explicit boxes and keypoints)
+static int extract_armors(irmv_engine *e, int slot, const float *xyxy, const float *kpts, int n, irmv_light_trace *trace, irmv_det *out)
 {
     TRY(check_range(e, slot, 1));
     if (n < 0 || n > e->cfg.max_det || (n > 0 && (!xyxy || !out))) return fail(IRMV_ERR_ARG, "n must be 0..max_det with xyxy/out set");
@@ -73,6 +88,7 @@ static int extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, ir
     HIP_TRY(hipSetDevice(e->cfg.device));
     TRY(irmv_engine_wait(e));
     hipStream_t st = e->stream;
+    if (kpts) TRY(ensure_refine(e));
     if (trace && !e->light_trace_dev) TRY(dev_alloc(e, (void **)&e->light_trace_dev, (size_t)e->cfg.max_det * sizeof(LightTrace)));
     if (trace) HIP_TRY(hipMemsetAsync(e->light_trace_dev, 0, (size_t)n * sizeof(LightTrace), st));
     TRY(load_frame(e, slot, st));
@@ -87,10 +103,21 @@ static int extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, ir
         for (size_t j = 0; j < local.size(); j++) local[j] -= (j & 1) ? oy : ox;
         HIP_TRY(hipMemcpyAsync(e->light_boxes, local.data(), (size_t)n * 16, hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));   // (`local` is pageable memory of this call)
+        if (kpts) {
+            local.assign(kpts, kpts + (size_t)n * 8);
+            for (size_t j = 0; j < local.size(); j++) local[j] -= (j & 1) ? oy : ox;
+            HIP_TRY(hipMemcpyAsync(e->refine_kpts, local.data(), (size_t)n * 32, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
     } else {
         HIP_TRY(hipMemcpyAsync(e->light_boxes, xyxy, (size_t)n * 16, hipMemcpyHostToDevice, st));
+        if (kpts) HIP_TRY(hipMemcpyAsync(e->refine_kpts, kpts, (size_t)n * 32, hipMemcpyHostToDevice, st));
     }
     LightArgs a = light_args(e, v, slot);
+    // the classical instantiation on a refined engine too; the guided one on any engine (slot 0's share of the prior buffer:
+    // nothing is in flight, and a step gathers its prior anew)
+    a.refine = kpts ? e->refine_dev : nullptr;
+    a.kpts = kpts ? e->refine_kpts : nullptr;
     a.dets = e->light_dets_dev;
     a.labels = v.light_labels;
     a.points = e->light_points;
@@ -111,19 +138,26 @@ static int extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, ir
         memcpy(o.xyxy, xyxy + 4 * i, 16);
         o.class_id = IRMV_NUM_CLASSES;
         det_pose(d, shift, ox, oy, o);
+        if (kpts) o.reserved = d.pad_;   // the refine flag
     }
     return IRMV_OK;
 }
 
 extern "C" int irmv_engine_extract_armors(irmv_engine *e, int slot, const float *xyxy, int n, irmv_det *out)
 {
-    return extract_armors(e, slot, xyxy, n, nullptr, out);
+    return extract_armors(e, slot, xyxy, nullptr, n, nullptr, out);
+}
+
+extern "C" int irmv_engine_refine_points(irmv_engine *e, int slot, const float *xyxy, const float *kpts, int n, irmv_light_trace *trace, irmv_det *out)
+{
+    if (n > 0 && !kpts) return fail(IRMV_ERR_ARG, "kpts is null");
+    return extract_armors(e, slot, xyxy, kpts, n, trace, out);
 }
 
 extern "C" int irmv_engine_light_trace(irmv_engine *e, int slot, const float *xyxy, int n, irmv_light_trace *trace, irmv_det *out)
 {
     if (n > 0 && !trace) return fail(IRMV_ERR_ARG, "trace is null");
-    return extract_armors(e, slot, xyxy, n, trace, out);
+    return extract_armors(e, slot, xyxy, nullptr, n, trace, out);
 }
 
 extern "C" int irmv_light_limits(int32_t out[4])

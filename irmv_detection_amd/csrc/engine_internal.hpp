@@ -292,6 +292,15 @@ struct irmv_engine {
     long long *dbg_dev = nullptr;
     std::set<std::string> lazy_tensors;   // tensors a step does not write because a fused kernel keeps them on chip
     bool classical = false;            // four points from the classical light extraction instead of a keypoint head
+    // Refined point source (IRMV_POINTS_REFINED): the keypoint engine's step plus the guided light extraction behind the NMS
+    // (k_light.hip, light_extract_kernel<true>).  `classical` stays false: the keypoint decode runs.  A refined engine has the
+    // classical engine's per-slot scratch and device records; refine_dev (the two live floats the kernel reads when it runs;
+    // graphs hold the address) and refine_kpts (the prior, [S][max_det][8]) exist from creation.  On any other engine both are
+    // made by the first irmv_engine_refine_points ([max_det][8]) and nothing else changes.
+    bool refined = false;
+    RefineParams refine{0.5f, 4.0f};
+    RefineParams *refine_dev = nullptr;
+    float *refine_kpts = nullptr;
     short *light_points = nullptr, *light_hulls = nullptr;
     float *light_boxes = nullptr;      // explicit boxes of irmv_engine_extract_armors
     DevDet *light_dets_dev = nullptr, *light_dets_host = nullptr;

@@ -85,6 +85,10 @@ LightArgs irmv::light_args(const irmv_engine *e, const View &v, int first)
     a.first = first; a.pnp_stride = e->post.pnp_stride;
     a.pnp_armor_size = c.armor_size;
     a.cls = e->cls_dev;
+    if (e->refined) {   // the guided instantiation: the two live parameters and the prior's buffer
+        a.refine = e->refine_dev;
+        a.kpts = e->refine_kpts + (size_t)first * c.max_det * 8;
+    }
     return a;
 }
 
@@ -681,7 +685,7 @@ void irmv::slot_det(const irmv_engine *e, int slot, int i, irmv_det &o)
     o.class_id = (d.cls >= 0 && d.cls < IRMV_NUM_CLASSES) ? d.cls : IRMV_NUM_CLASSES;
     o.anchor = d.anchor;
     det_pose(d, shift, ox, oy, o);
-    o.reserved = 0;
+    o.reserved = e->refined ? d.pad_ : 0;   // the refine flag (IRMV_POINTS_REFINED); every other engine: 0
     if (shift)
         for (int j = 0; j < 4; j++) o.xyxy[j] += (j & 1) ? oy : ox;
 }

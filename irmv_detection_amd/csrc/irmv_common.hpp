@@ -499,6 +499,9 @@ struct LightTrace {
     LightTraceRec recs[kLightMaxContours];   // per contour, discovery order; measured = 0: fewer than 5 points (or no answer)
 };
 
+// The guided instantiation's two live parameters: device memory, read when the kernel runs (irmv_engine_set_refine)
+struct RefineParams { float snap, roi_margin; };
+
 struct LightArgs {
     const uint8_t *frames;   // [B][rows][cols][3] device frames (un-rotated; rotation folded into the fetch)
     size_t frame_bytes;
@@ -521,6 +524,9 @@ struct LightArgs {
     const ClassTable *cls;   // ... and, boxes == nullptr: the table whose plate[dets[i].cls] a step's detection solves with
     LightTrace *trace;       // [n_boxes] or nullptr (every launch of a step): see LightTrace
     int first, pnp_stride;   // frame b solves with pnp[(first + b) * pnp_stride] (PostArgs::pnp_stride)
+    const RefineParams *refine;   // non-null: the guided instantiation (light_extract_kernel<true>): dets[i].kpts are the prior, refined in place
+    float *kpts;             // guided: the prior [B][max_det][8].  A step's launch fills it from the records first (refine_prior_kernel);
+                             // with explicit boxes the caller has (irmv_engine_refine_points), and the records are output only
 };
 void launch_light_extract(const LightArgs &a, int n_boxes_max, int batch, hipStream_t s);
 

@@ -17,6 +17,24 @@
 // itself on one lane.  Scratch is bounded (label pool per frame, 1024 contours and
 // points_cap contour points per detection); a detection that exhausts any of it gets
 // armor_valid = -1 -- "no answer" -- never a truncated, silently different result.
+//
+// The kernel has two instantiations.  kGuided = false is the reference's extraction as described above.  kGuided = true
+// (IRMV_POINTS_REFINED, irmv_engine_refine_points; profile name light_refine) takes each detection's four keypoints
+// LB, LT, RT, RB as a prior and replaces them by the ends of the light bars found at them:
+//   1. all eight keypoint values pass pixel_in_range, else: flag 0, n_lights 0, no extraction, nothing of the label pool;
+//   2. ROI: gx1 = min(x1, min kx) - roi_margin, gy1 = min(y1, min ky) - roi_margin, gx2 = max(x2, max kx) + roi_margin,
+//      gy2 = max(y2, max ky) + roi_margin (min(a, b) = a < b ? a : b, max(a, b) = a > b ? a : b, keypoints folded first),
+//      then roi_of unchanged; the label-pool prefix sums the guided ROIs of the detections in front by the same rule;
+//   3. lights exactly as above; n_lights counts the gated lights of the ROI;
+//   4. side L: (B, T) = (kpts[0..1], kpts[2..3]), side R: (B, T) = (kpts[6..7], kpts[4..5]); a gated light (b, t) has
+//      cost = ((b.x-B.x)^2 + (b.y-B.y)^2) + ((t.x-T.x)^2 + (t.y-T.y)^2), len2 = (B.x-T.x)^2 + (B.y-T.y)^2, and is
+//      admissible for the side iff cost <= (snap * snap) * len2 -- fp32, in this association order;
+//   5. per side the admissible light of least cost, on equal cost the one with the higher contour index;
+//   6. refined iff both sides have a light, the two are different contours and PnP on {L.bottom, L.top, R.top, R.bottom}
+//      succeeds (solved into temporaries, committed on success): kpts, rvec, tvec, quat, pnp_ok are replaced;
+//   7. armor_valid, armor_size, kpts_net stay; 8. DevDet::pad_ = 1 refined, 0 the head's points kept, -1 kept because the
+//      extraction had no answer (pool, contour or point limit).
+// snap and roi_margin are read from device memory when the kernel runs (RefineParams).
 #include "irmv_common.hpp"
 #include "pnp_device.hpp"
 
@@ -245,7 +263,9 @@ __device__ void contour_to_light(S *p, int n, S *scratch, const LightArgs &a, fl
 // in the row was not "positive".  So per 64-pixel block three ballots (start candidates, positive events, negative
 // events) and a few scalar bit operations reproduce every decision of the scan; only accepted starts are walked
 // (lane 0 follows the border), after which the labels to the right are re-read because they now carry marks.
-template <typename P>
+// kNoStack (the guided instantiation): a border that finds no room is given the points array itself with room 0 -- trace_border
+// writes nothing at room 0 -- instead of a two-short local, whose address costs the kernel a private segment.
+template <typename P, bool kNoStack = false>
 __device__ void scan_external(P *img, int step, int rw, int rh, int lane, short *pts, int points_cap, int *s_start, int *s_nfound, int *s_nfound_raw,
                               int *s_toolarge)
 {
@@ -287,8 +307,12 @@ __device__ void scan_external(P *img, int step, int rw, int rh, int lane, short 
                     const int room = keep ? points_cap - npts : 0;
                     int n = 0;
                     if (lane == 0) {
-                        short dummy[2];
-                        n = trace_border(img, step, xx, y, room > 0 ? pts + 2 * (size_t)npts : dummy, room > 0 ? room : 0, 4 * step * (rh + 2) + 16);
+                        if constexpr (kNoStack) {
+                            n = trace_border(img, step, xx, y, room > 0 ? pts + 2 * (size_t)npts : pts, room > 0 ? room : 0, 4 * step * (rh + 2) + 16);
+                        } else {
+                            short dummy[2];
+                            n = trace_border(img, step, xx, y, room > 0 ? pts + 2 * (size_t)npts : dummy, room > 0 ? room : 0, 4 * step * (rh + 2) + 16);
+                        }
                     }
                     n = __shfl(n, 0);
                     if (keep) {
@@ -335,22 +359,55 @@ __device__ __forceinline__ unsigned long long label_bytes(const Roi &r)
 {
     return ((unsigned long long)(r.rw + 2) * (r.rh + 2) + 15ull) & ~15ull;
 }
+// guided instantiation, rules 1 and 2: the ROI of a box and its eight keypoints; false: unusable keypoints or no ROI
+__device__ __forceinline__ bool guided_roi(const float *xyxy, const float *kp, float margin, int cols, int rows, Roi &r, bool &usable)
+{
+    usable = true;
+#pragma unroll
+    for (int i = 0; i < 8; i++) usable = usable && pixel_in_range(kp[i]);
+    r.min_x = r.min_y = 0.0f; r.rx = r.ry = r.rw = r.rh = 0;
+    if (!usable) return false;
+    float nx = kp[0], ny = kp[1], mx = kp[0], my = kp[1];
+#pragma unroll
+    for (int i = 1; i < 4; i++) {
+        nx = kp[2 * i] < nx ? kp[2 * i] : nx; mx = kp[2 * i] > mx ? kp[2 * i] : mx;
+        ny = kp[2 * i + 1] < ny ? kp[2 * i + 1] : ny; my = kp[2 * i + 1] > my ? kp[2 * i + 1] : my;
+    }
+    float g[4];
+    g[0] = (xyxy[0] < nx ? xyxy[0] : nx) - margin; g[1] = (xyxy[1] < ny ? xyxy[1] : ny) - margin;
+    g[2] = (xyxy[2] > mx ? xyxy[2] : mx) + margin; g[3] = (xyxy[3] > my ? xyxy[3] : my) + margin;
+    return roi_of(g, cols, rows, r);
+}
 
+template <bool kGuided>
 __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
 {
     __shared__ int s_nfound, s_toolarge, s_nfound_raw;
     __shared__ unsigned long long s_prefix;
     __shared__ int s_start[kLightMaxContours + 1];
     __shared__ short s_cpts[4][2 * kLightLdsPoints * 3 + 4];   // per wave: a contour's points + 2n points of sort / hull scratch
-    __shared__ LightRec s_top[4][2];   // per wave: the last two gated lights it measured
+    __shared__ LightRec s_top[4][2];   // per wave: the last two gated lights it measured (guided: its best light of side L, R)
     __shared__ int s_topc[4][2], s_nlights;
+    __shared__ float s_cost[4][2];     // guided: the cost of s_top[w][side]
     __shared__ __attribute__((aligned(16))) signed char s_img[kLightLdsImage];   // label image of ROIs up to ~200 x 200 (else: the HBM pool)
     const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int ndet = a.num_dets ? min(a.num_dets[b * a.num_dets_stride], a.max_det) : a.n_boxes;
     DevDet *d = a.dets + (size_t)b * a.max_det + j;
     if (j >= ndet) return;
     Roi R;
-    const bool empty = !roi_of(a.boxes ? a.boxes + 4 * j : d->xyxy, a.cols, a.rows, R);
+    bool empty, usable = true;
+    float kin[8] = {0, 0, 0, 0, 0, 0, 0, 0}, snap = 0.f, margin = 0.f;   // guided: the keypoint prior and the two live parameters
+    if constexpr (kGuided) {
+        snap = a.refine->snap; margin = a.refine->roi_margin;
+        // the prior comes from a copy of the records' keypoints (refine_prior_kernel), never from the records: other
+        // workgroups rewrite theirs while this one still sums the pool prefix over them
+        const float *kp = a.kpts + ((size_t)b * a.max_det + j) * 8;
+#pragma unroll
+        for (int i = 0; i < 8; i++) kin[i] = kp[i];
+        empty = !guided_roi(a.boxes ? a.boxes + 4 * j : d->xyxy, kin, margin, a.cols, a.rows, R, usable);
+    } else {
+        empty = !roi_of(a.boxes ? a.boxes + 4 * j : d->xyxy, a.cols, a.rows, R);
+    }
     const float min_x = R.min_x, min_y = R.min_y;
     const int rx = R.rx, ry = R.ry, rw = R.rw, rh = R.rh, step = rw + 2;
     // label image carved from the frame's pool in detection order (deterministic: a full pool drops the
@@ -360,7 +417,13 @@ __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
     unsigned long long mine = 0;
     for (int i = tid; i < j; i += blockDim.x) {
         Roi Q;
-        if (roi_of(a.boxes ? a.boxes + 4 * i : a.dets[(size_t)b * a.max_det + i].xyxy, a.cols, a.rows, Q)) mine += label_bytes(Q);
+        const DevDet &di = a.dets[(size_t)b * a.max_det + i];
+        if constexpr (kGuided) {
+            bool u;
+            if (guided_roi(a.boxes ? a.boxes + 4 * i : di.xyxy, a.kpts + ((size_t)b * a.max_det + i) * 8, margin, a.cols, a.rows, Q, u)) mine += label_bytes(Q);
+        } else {
+            if (roi_of(a.boxes ? a.boxes + 4 * i : di.xyxy, a.cols, a.rows, Q)) mine += label_bytes(Q);
+        }
     }
     if (mine) atomicAdd(&s_prefix, mine);
     __syncthreads();
@@ -407,7 +470,13 @@ __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
     // walks just the set bits with the sequential Suzuki-Abe state (lnbd_x); the walk, its loads and its decisions are
     // wave-uniform.  A border is followed by lane 0; its marks change labels to the right, so the rest of the chunk is
     // re-examined afterwards.  Same decisions in the same order as the one-pixel-at-a-time scan of oracle/orc_light.c.
-    if (!skip && tid < 64) {
+    if constexpr (kGuided) {
+        // (the same scan, inlined: out of line its entry saves a register to scratch, and this instantiation is to have none)
+        if (!skip && tid < 64) {
+            if (in_lds) [[clang::always_inline]] scan_external<lds_i8, true>((lds_i8 *)s_img, step, rw, rh, tid, pts, a.points_cap, s_start, &s_nfound, &s_nfound_raw, &s_toolarge);
+            else [[clang::always_inline]] scan_external<glb_i8, true>((glb_i8 *)img, step, rw, rh, tid, pts, a.points_cap, s_start, &s_nfound, &s_nfound_raw, &s_toolarge);
+        }
+    } else if (!skip && tid < 64) {
         if (in_lds) scan_external((lds_i8 *)s_img, step, rw, rh, tid, pts, a.points_cap, s_start, &s_nfound, &s_nfound_raw, &s_toolarge);
         else scan_external((glb_i8 *)img, step, rw, rh, tid, pts, a.points_cap, s_start, &s_nfound, &s_nfound_raw, &s_toolarge);
     }
@@ -435,9 +504,14 @@ __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
     {
         const int wave = tid >> 6, lane = tid & 63;
         short *hulls = a.hulls + ((size_t)b * a.max_det + j) * a.points_cap * 2 * 2;
-        LightRec r0, r1;
+        LightRec r0, r1;   // (guided: the wave's best light of side L, of side R)
         int c0 = -1, c1 = -1, cnt = 0;
+        float k0 = 0.f, k1 = 0.f;
         r0.ok = r1.ok = 0;
+        // guided, rule 4: the sides' (B, T) and their admission thresholds
+        const float s2 = snap * snap;
+        const float thrL = s2 * ((kin[0] - kin[2]) * (kin[0] - kin[2]) + (kin[1] - kin[3]) * (kin[1] - kin[3]));
+        const float thrR = s2 * ((kin[6] - kin[4]) * (kin[6] - kin[4]) + (kin[7] - kin[5]) * (kin[7] - kin[5]));
         for (int c = wave; c < nfound && pts_ok; c += 4) {
             const int n = s_start[c + 1] - s_start[c];
             if (n < 5) continue;
@@ -460,15 +534,70 @@ __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
                 tr->length = L.length;
                 tr->measured = 1; tr->ok = L.ok; tr->in_lds = n <= kLightLdsPoints ? 1 : 0;
             }
-            if (lane == 0 && L.ok) { r1 = r0; c1 = c0; r0 = L; c0 = c; cnt++; }
+            if constexpr (kGuided) {
+                if (lane == 0 && L.ok) {
+                    cnt++;
+                    const float bx = L.bottom[0], by = L.bottom[1], tx = L.top[0], ty = L.top[1];
+                    const float cl = ((bx - kin[0]) * (bx - kin[0]) + (by - kin[1]) * (by - kin[1])) + ((tx - kin[2]) * (tx - kin[2]) + (ty - kin[3]) * (ty - kin[3]));
+                    const float cr = ((bx - kin[6]) * (bx - kin[6]) + (by - kin[7]) * (by - kin[7])) + ((tx - kin[4]) * (tx - kin[4]) + (ty - kin[5]) * (ty - kin[5]));
+                    // contours come in ascending index: on equal cost the later one wins (rule 5)
+                    if (cl <= thrL && (c0 < 0 || cl <= k0)) { r0 = L; c0 = c; k0 = cl; }
+                    if (cr <= thrR && (c1 < 0 || cr <= k1)) { r1 = L; c1 = c; k1 = cr; }
+                }
+            } else {
+                if (lane == 0 && L.ok) { r1 = r0; c1 = c0; r0 = L; c0 = c; cnt++; }
+            }
         }
         if (lane == 0) {
             s_top[wave][0] = r0; s_top[wave][1] = r1;
             s_topc[wave][0] = c0; s_topc[wave][1] = c1;
+            if constexpr (kGuided) { s_cost[wave][0] = k0; s_cost[wave][1] = k1; }
             if (cnt) atomicAdd(&s_nlights, cnt);
         }
     }
     __syncthreads();
+    if constexpr (kGuided) {
+        // 4 (guided). per side the waves' candidates merged by (cost ascending, contour index descending), then rules 5 to 8
+        if (tid == 0) {
+            const int plate = (a.cls && !a.boxes) ? a.cls->plate[d->cls & (kMaxClasses - 1)] : a.pnp_armor_size;
+            const PnpConst &pc = a.pnp[(size_t)(a.first + b) * a.pnp_stride];
+            int flag = s_toolarge ? -1 : 0;
+            double rvec[3] = {0.0, 0.0, 0.0}, tvec[3] = {0.0, 0.0, 0.0}, quat[4] = {0.0, 0.0, 0.0, 1.0};
+            if (a.boxes) {
+                // explicit boxes and keypoints (irmv_engine_refine_points): the record is output only -- the inputs and their pose first
+                const int ok = solve_pnp_ippe(pc, kin, plate, rvec, tvec, quat) ? 1 : 0;
+                for (int i = 0; i < 8; i++) { d->kpts[i] = kin[i]; d->kpts_net[i] = 0.f; }
+                for (int i = 0; i < 3; i++) { d->rvec[i] = rvec[i]; d->tvec[i] = tvec[i]; }
+                for (int i = 0; i < 4; i++) d->quat[i] = quat[i];
+                d->pnp_ok = ok;
+                d->armor_valid = 1;
+                d->armor_size = plate;
+            }
+            if (usable && !s_toolarge) {
+                int wl = -1, wr = -1;
+                for (int w = 0; w < 4; w++) {
+                    if (s_topc[w][0] >= 0 && (wl < 0 || s_cost[w][0] < s_cost[wl][0] || (s_cost[w][0] == s_cost[wl][0] && s_topc[w][0] > s_topc[wl][0]))) wl = w;
+                    if (s_topc[w][1] >= 0 && (wr < 0 || s_cost[w][1] < s_cost[wr][1] || (s_cost[w][1] == s_cost[wr][1] && s_topc[w][1] > s_topc[wr][1]))) wr = w;
+                }
+                if (wl >= 0 && wr >= 0 && s_topc[wl][0] != s_topc[wr][1]) {
+                    const LightRec &l = s_top[wl][0], &r = s_top[wr][1];
+                    float kp[8];
+                    kp[0] = l.bottom[0]; kp[1] = l.bottom[1]; kp[2] = l.top[0]; kp[3] = l.top[1];
+                    kp[4] = r.top[0]; kp[5] = r.top[1]; kp[6] = r.bottom[0]; kp[7] = r.bottom[1];
+                    if (solve_pnp_ippe(pc, kp, plate, rvec, tvec, quat)) {
+                        for (int i = 0; i < 8; i++) d->kpts[i] = kp[i];
+                        for (int i = 0; i < 3; i++) { d->rvec[i] = rvec[i]; d->tvec[i] = tvec[i]; }
+                        for (int i = 0; i < 4; i++) d->quat[i] = quat[i];
+                        d->pnp_ok = 1;
+                        flag = 1;
+                    }
+                }
+            }
+            d->n_lights = usable ? s_nlights : 0;
+            d->pad_ = flag;
+        }
+        return;
+    }
     // 4. first two lights in OpenCV's contour order -> Armor -> PnP
     if (tid == 0) {
         const int total = s_nlights;
@@ -510,10 +639,22 @@ __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
     }
 }
 
+// the guided instantiation's prior of a step: the records' keypoints as the NMS kernel left them -> kpts [B][max_det][8]
+__global__ __launch_bounds__(256) void refine_prior_kernel(const DevDet *dets, float *kpts, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) kpts[i] = dets[i >> 3].kpts[i & 7];
+}
+
 void launch_light_extract(const LightArgs &a, int n_boxes_max, int batch, hipStream_t s)
 {
     if (n_boxes_max <= 0 || batch <= 0) return;
-    hipLaunchKernelGGL(light_extract_kernel, dim3(n_boxes_max, batch), dim3(256), 0, s, a);
+    if (a.refine && !a.boxes) {
+        const int n = batch * a.max_det * 8;
+        hipLaunchKernelGGL(refine_prior_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a.dets, a.kpts, n);
+    }
+    if (a.refine) hipLaunchKernelGGL(light_extract_kernel<true>, dim3(n_boxes_max, batch), dim3(256), 0, s, a);   // guided: profile name light_refine
+    else hipLaunchKernelGGL(light_extract_kernel<false>, dim3(n_boxes_max, batch), dim3(256), 0, s, a);
 }
 
 }  // namespace irmv

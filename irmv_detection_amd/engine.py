@@ -63,6 +63,7 @@ class Armor:
     valid: bool = True      # the four points exist (classical extraction found two gated lights / keypoint head)
     n_lights: int = 0
     no_answer: bool = False  # classical extraction ran out of scratch for this bbox (irmv_det.armor_valid == -1)
+    refined: int = 0         # refined point source: 1 = the points are the light bars' ends, 0 = the head's kept, -1 = kept, the extraction had no answer
     rvec: Optional[np.ndarray] = None
     tvec: Optional[np.ndarray] = None
     quat_xyzw: Optional[np.ndarray] = None
@@ -103,6 +104,9 @@ class YoloEngine:
     windows of ONE frame in one step, merged on the GPU into one list (irmv_detection_amd.tiles is the host reference).
     `set_class_policy` / `set_enemy_color` change per-class score thresholds, the colour mask and the per-class plate model of
     the living engine (irmv_detection_amd.class_policy is the host reference).
+    `point_source=capi.POINTS_REFINED`: the keypoint head's points snapped to the light bars found at them, inside the step
+    (`Armor.refined`); `set_refine` / `get_refine` change its two parameters live, `refine_points` runs it on explicit boxes
+    and keypoints on any engine (irmv_detection_amd.refine is the host reference).
     """
 
     def __init__(self, onnx_file_path: Optional[str], src_image_size: Tuple[int, int] = (1280, 1024),
@@ -327,6 +331,44 @@ class YoloEngine:
         a, b = C.c_float(0), C.c_float(0)
         capi.check(self._L.irmv_engine_get_tile_merge(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def set_refine(self, snap: float = 0.5, roi_margin: float = 4.0) -> None:
+        """The refined point source's parameters, live (irmv_engine_set_refine): a light is admissible for a side when its
+        cost is at most snap^2 times the squared length of the side's keypoint pair; the guided ROI is the hull of box and
+        keypoints grown by roi_margin source pixels.  Neither default has been validated on a trained model.  Waits for
+        every step in flight, re-captures nothing; a refused value raises and changes nothing."""
+        capi.check(self._L.irmv_engine_set_refine(self._h, float(snap), float(roi_margin)))
+
+    def get_refine(self) -> Tuple[float, float]:
+        a, b = C.c_float(0), C.c_float(0)
+        capi.check(self._L.irmv_engine_get_refine(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def refine_points(self, boxes, kpts, slot: int = 0, trace: bool = False):
+        """The guided extraction on explicit boxes (xyxy rows) and keypoints (rows of 8: LB, LT, RT, RB) on the slot's current
+        frame, on an engine of any point source (irmv_engine_refine_points): -> raw capi.Det records (`reserved` = the flag),
+        or (records, capi.LightTrace array) with trace=True."""
+        xy = np.ascontiguousarray(boxes, np.float32).reshape(-1, 4)
+        kp = np.ascontiguousarray(kpts, np.float32).reshape(-1, 8)
+        if len(xy) != len(kp):
+            raise ValueError("one row of keypoints per box")
+        out = (capi.Det * max(len(xy), 1))()
+        tr = (capi.LightTrace * max(len(xy), 1))() if trace else None
+        capi.check(self._L.irmv_engine_refine_points(self._h, slot, xy.ctypes.data_as(C.POINTER(C.c_float)),
+                                                     kp.ctypes.data_as(C.POINTER(C.c_float)), len(xy), tr, out))
+        return (out, tr) if trace else out
+
+    @property
+    def point_source(self) -> int:
+        """capi.POINTS_*: where the four points come from (AUTO resolved)."""
+        return int(self._L.irmv_engine_point_source(self._h))
+
+    def results_raw(self, slot: int = 0):
+        """The slot's result list as capi.Det records (copies), for byte comparisons."""
+        n = C.c_int(0)
+        out = (capi.Det * self.max_det)()
+        capi.check(self._L.irmv_engine_results(self._h, slot, out, self.max_det, C.byref(n)))
+        return [out[i] for i in range(n.value)]
 
     def debug_graph_count(self) -> int:
         """Test hook: the captured graphs the engine holds."""
@@ -608,7 +650,7 @@ class YoloEngine:
                   right_light=Light(top=(k[4], k[5]), bottom=(k[6], k[7])),
                   size=ArmorSize(d.armor_size) if d.armor_size in (0, 1) else ArmorSize.UNKNOWN,
                   armor_class=ArmorClass(d.class_id), confidence=d.score, valid=d.armor_valid == 1, n_lights=d.n_lights, no_answer=d.armor_valid < 0,
-                  bbox_xyxy=tuple(d.xyxy), pnp_ok=bool(d.pnp_ok),
+                  bbox_xyxy=tuple(d.xyxy), pnp_ok=bool(d.pnp_ok), refined=int(d.reserved),
                   rvec=np.array(d.rvec), tvec=np.array(d.tvec), quat_xyzw=np.array(d.quat))
         a.center = ((k[0] + k[2] + k[4] + k[6]) / 4.0, (k[1] + k[3] + k[5] + k[7]) / 4.0)
         return a

@@ -32,6 +32,9 @@ public:
     p.device = int(node_->declare_parameter("device", 0));
     p.enemy_color = int(node_->declare_parameter("enemy_color", -1));   // 0 for blue, 1 for red (reference :154-160), -1: no filter; live through the callback below
     for (int64_t c : node_->declare_parameter("large_plate_classes", std::vector<int64_t>{})) p.large_plate_classes.push_back(int(c));
+    p.point_source = int(node_->declare_parameter("point_source", 0));   // IRMV_POINTS_*: 0 auto, 3 refined (a pose model's points snapped to the light bars)
+    p.refine_snap = node_->declare_parameter("refine.snap", 0.5);         // live through the callback below, like refine.roi_margin
+    p.refine_roi_margin = node_->declare_parameter("refine.roi_margin", 4.0);
     const auto ns = node_->declare_parameter("net_input_size", std::vector<int64_t>{0, 0});   // {width, height}; {0, 0}: square default
     if (ns.size() == 2) p.net_input_size = cv::Size(int(ns[0]), int(ns[1]));
     const std::string model = node_->declare_parameter("model_path", std::string("models/yolov7.onnx"));
