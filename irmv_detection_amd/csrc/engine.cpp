@@ -58,6 +58,16 @@ void irmv::log_range(const irmv_engine *e, const char *what, const void *p, size
     if (log_alloc()) fprintf(stderr, "[irmv alloc] engine %p %-18s [%p, %p) %zu bytes\n", (const void *)e, what, p, (const void *)((const char *)p + bytes), bytes);
 }
 
+// Destroy the engine's captured graphs -- their steps are captured again on next use --; keep_post: all but run_post's.
+void irmv::drop_graphs(irmv_engine *e, bool keep_post)
+{
+    for (auto it = e->graphs.begin(); it != e->graphs.end();) {
+        if (keep_post && it->first.step.kind == STEP_POST) { ++it; continue; }
+        (void)hipGraphExecDestroy(it->second);
+        it = e->graphs.erase(it);
+    }
+}
+
 // Teardown order matters: nothing may be freed while any stream of this engine can still touch it.
 //   1. drain EVERY stream the engine ever enqueued work on (compute, upload, download, capture side lanes);
 //   2. destroy the graph executables (they hold kernel-argument copies pointing into the buffers);
@@ -80,8 +90,7 @@ irmv_engine::~irmv_engine()
                         t[7] - t[0], t[8] - t[7], t[9] - t[8], t[1] - t[9], t[10] - t[1], t[2] - t[10], t[3] - t[2], t[11] - t[3], t[12] - t[11], t[4] - t[12], t[4] - t[0], t[5], t[6]);
             }
     }
-    for (auto &g : graphs) (void)hipGraphExecDestroy(g.second);
-    graphs.clear();
+    drop_graphs(this, false);
     if (log_alloc()) fprintf(stderr, "[irmv alloc] engine %p destroy: freeing %zu device ranges\n", (const void *)this, dev_allocs.size());
     for (void *p : dev_allocs) (void)hipFree(p);
     dev_allocs.clear();
@@ -588,11 +597,18 @@ int irmv::write_window(irmv_engine *e, int slot)
     return IRMV_OK;
 }
 
-extern "C" int irmv_engine_set_window(irmv_engine *e, int slot, int x0, int y0)
+// What the window and view entry points (`who`) ask of their arguments first: an engine, with a window, and a slot of it.
+int irmv::check_window_slot(const irmv_engine *e, int slot, const char *who)
 {
     if (!e) return fail(IRMV_ERR_ARG, "engine is null");
-    if (!e->window) return fail(IRMV_ERR_ARG, "irmv_engine_set_window: the engine has no window (win_width, win_height)");
+    if (!e->window) return fail(IRMV_ERR_ARG, std::string(who) + ": the engine has no window (win_width, win_height)");
     if (slot < 0 || slot >= e->cfg.num_slots) return fail(IRMV_ERR_ARG, "slot out of range");
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_set_window(irmv_engine *e, int slot, int x0, int y0)
+{
+    TRY(check_window_slot(e, slot, "irmv_engine_set_window"));
     irmv_window_map_t m;
     TRY(window_map(e->full_w, e->full_h, e->cfg.src_width, e->cfg.src_height, e->cfg.rotate180, e->cfg.camera_matrix, x0, y0, &m));
     HIP_TRY(hipSetDevice(e->cfg.device));
@@ -603,9 +619,7 @@ extern "C" int irmv_engine_set_window(irmv_engine *e, int slot, int x0, int y0)
 
 extern "C" int irmv_engine_get_window(const irmv_engine *e, int slot, int *x0, int *y0, int *w, int *h)
 {
-    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
-    if (!e->window) return fail(IRMV_ERR_ARG, "irmv_engine_get_window: the engine has no window (win_width, win_height)");
-    if (slot < 0 || slot >= e->cfg.num_slots) return fail(IRMV_ERR_ARG, "slot out of range");
+    TRY(check_window_slot(e, slot, "irmv_engine_get_window"));
     if (x0) *x0 = e->win_org[slot].x;
     if (y0) *y0 = e->win_org[slot].y;
     if (w) *w = e->cfg.src_width;
@@ -616,9 +630,7 @@ extern "C" int irmv_engine_get_window(const irmv_engine *e, int slot, int *x0, i
 // ---- search view --------------------------------------------------------------------
 extern "C" int irmv_engine_set_view(irmv_engine *e, int slot, int view)
 {
-    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
-    if (!e->window) return fail(IRMV_ERR_ARG, "irmv_engine_set_view: the engine has no window (win_width, win_height)");
-    if (slot < 0 || slot >= e->cfg.num_slots) return fail(IRMV_ERR_ARG, "slot out of range");
+    TRY(check_window_slot(e, slot, "irmv_engine_set_view"));
     if (view != IRMV_VIEW_WINDOW && view != IRMV_VIEW_FRAME) return fail(IRMV_ERR_ARG, "unknown view (IRMV_VIEW_*)");
     HIP_TRY(hipSetDevice(e->cfg.device));
     if (view == IRMV_VIEW_FRAME && !e->views[IRMV_VIEW_FRAME].built) {
@@ -636,9 +648,7 @@ extern "C" int irmv_engine_set_view(irmv_engine *e, int slot, int view)
 
 extern "C" int irmv_engine_get_view(const irmv_engine *e, int slot, int *view, int *src_w, int *src_h)
 {
-    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
-    if (!e->window) return fail(IRMV_ERR_ARG, "irmv_engine_get_view: the engine has no window (win_width, win_height)");
-    if (slot < 0 || slot >= e->cfg.num_slots) return fail(IRMV_ERR_ARG, "slot out of range");
+    TRY(check_window_slot(e, slot, "irmv_engine_get_view"));
     const View &v = view_of(e, slot);
     if (view) *view = e->slot_view[slot];
     if (src_w) *src_w = v.src_w;
@@ -712,10 +722,7 @@ extern "C" int irmv_engine_set_extract_params(irmv_engine *e, int binary_thresho
     c.armor_min_small_center_distance = cd[0]; c.armor_max_small_center_distance = cd[1];
     c.armor_min_large_center_distance = cd[2]; c.armor_max_large_center_distance = cd[3];
     // captured steps of the classical and the refined mode carry these values as kernel arguments: re-capture on next use
-    if (e->classical || e->refined) {
-        for (auto &g : e->graphs) (void)hipGraphExecDestroy(g.second);
-        e->graphs.clear();
-    }
+    if (e->classical || e->refined) drop_graphs(e, false);
     return IRMV_OK;
 }
 
@@ -735,11 +742,7 @@ extern "C" int irmv_engine_set_bayer_isp(irmv_engine *e, const uint16_t gain_q8[
         // and captured again on their next use (run_post's graphs have no demosaic node and stay).  Later sets only rewrite
         // the table, which the kernels read from device memory when they run.
         e->bayer_table = true;
-        for (auto it = e->graphs.begin(); it != e->graphs.end();) {
-            if (it->first.kind == STEP_POST) { ++it; continue; }
-            (void)hipGraphExecDestroy(it->second);
-            it = e->graphs.erase(it);
-        }
+        drop_graphs(e, true);
         for (size_t i = 0; i < e->ops.size(); i++) {
             if (e->ops[i].kind != OP_DEMOSAIC) continue;
             snprintf(e->ops[i].kname, sizeof e->ops[i].kname, "%s", demosaic_kname(e));

@@ -240,7 +240,7 @@ static int materialize_fused(irmv_engine *e, int slot)
     if (e->lazy_tensors.empty()) return IRMV_OK;
     HIP_TRY(hipSetDevice(e->cfg.device));
     TRY(irmv_engine_wait(e));
-    TRY(enqueue_step(e, STEP_MATERIALIZE, slot, 1, e->stream, 1, nullptr));
+    TRY(enqueue_step(e, Step{STEP_MATERIALIZE, slot, 1}, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->head_stale[slot] = 0;   // (the finals and the keypoint layers have written every head row)
     e->branch_stale[slot] = 0; // (... and the box branches' gated first convs their whole tensors)
@@ -582,7 +582,8 @@ extern "C" int irmv_engine_run_op(irmv_engine *e, int op, int first, int count, 
     if (flags & IRMV_RUN_POISON_ONLY) { HIP_TRY(hipStreamSynchronize(e->stream)); return IRMV_OK; }
     Launch l;   // (a plain launch of the op: no group, no fusion, no gate)
     l.op = op;
-    TRY(launch_op(e, view_of(e, first), l, first, count, post_args(e, view_of(e, first), first), 0u, false, e->stream));
+    const Step step{count == 1 ? STEP_ONE : STEP_BATCH, first, count};
+    TRY(launch_op(e, view_of(e, first), l, step, post_args(e, view_of(e, first), step), 0u, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return IRMV_OK;
 }
@@ -636,7 +637,7 @@ extern "C" int irmv_engine_profile(irmv_engine *e, int first, int count, irmv_ke
     ProfileEvents pe;
     pe.ev.resize(2 * plan.size(), nullptr);
     for (hipEvent_t &x : pe.ev) HIP_TRY(hipEventCreate(&x));
-    TRY(enqueue_step(e, kind, first, count, e->stream, kProfileRepeat, &pe.ev));   // (a window engine crops out of its device frames, as a submit without IRMV_SUBMIT_H2D does)
+    TRY(enqueue_step(e, Step{kind, first, count}, e->stream, kProfileRepeat, &pe.ev));   // (a window engine crops out of its device frames, as a submit without IRMV_SUBMIT_H2D does)
     mark_stepped(e, first, count);
     TRY(copy_out(e, first, count));
     HIP_TRY(hipStreamSynchronize(e->stream));

@@ -5,8 +5,10 @@
 //   engine_graph.cpp  .irmw blob, tensors, weight packing, the op list (build_engine)
 //   engine_tune.cpp   everything decided by timing at creation: conv tiles and their cache, head groups, the synchronous launch form
 //   engine_plan.cpp   head fusion, the sparse head's reordering, the launch list of each step kind
-//   engine_step.cpp   kernel arguments, the per-op launcher, steps, copies, graph capture, submit / wait / results
-//   engine_tiles.cpp  tiled search: the tile grid, tiled steps, the merge and its parameters
+//   engine_step.cpp   kernel arguments, the per-op launcher, steps (Step), the upload decision (choose_upload / enqueue_upload),
+//                     result copies, graph capture, the one submit path of ordinary and tiled steps (submit_group), wait / results
+//   engine_tiles.cpp  tiled search: its checks, the merge's device state and arguments, the tiled submit's call of submit_group,
+//                     the merge hook, the merged results and the merge parameters
 //   engine_hooks.cpp  read-backs, debug_*, LDS fill / probe, conv and op test hooks, the profiler, the light trace
 #pragma once
 #include <hip/hip_runtime.h>
@@ -160,14 +162,40 @@ struct Launch {
     double flops = 0, bytes = 0, launch_bytes = 0;   // per frame; launch_bytes (the weights): once per launch
 };
 
-struct GraphKey {
-    int first, count;
+// What a step is: the plan of `kind` on slots [first, first + count).  Everything that follows from these fields is a member
+// here, so launch_op, enqueue_step and get_graph take a Step and nothing beside it describes the step.
+struct Step {
     StepKind kind;
-    bool upload;   // the frames' upload is the graph's first node
-    int view;      // IRMV_VIEW_*: the view its slots were in when it was captured
-    int frame_slot = -1;   // >= 0: a tiled step (irmv_engine_submit_tiles) whose slots all crop out of this slot's frame, merge node included
-    bool operator<(const GraphKey &o) const { return std::tie(first, count, kind, upload, view, frame_slot) < std::tie(o.first, o.count, o.kind, o.upload, o.view, o.frame_slot); }
+    int first, count;
+    int tile_frame = -1;        // >= 0: a tiled step (irmv_engine_submit_tiles): every slot crops its window out of this slot's frame, and the merge (k_tiles.hip) is its last node
+    bool crop_pinned = false;   // OP_CROP reads the window out of the pinned slots: nothing was uploaded (UP_PINNED_CROP)
+    bool tiled() const { return tile_frame >= 0; }
+    // a tiled step's NMS writes DEVICE records also where the engine's ordinary steps write pinned host memory: the merge kernel
+    // behind it reads them, and a D2H copy brings them to the host
+    bool dev_records() const { return tiled(); }
+    // the demosaic of a tiled step runs ONCE, on tile_frame's raw frame
+    int bayer_first() const { return tiled() ? tile_frame : first; }
+    int bayer_count() const { return tiled() ? 1 : count; }
+    bool operator<(const Step &o) const { return std::tie(first, count, kind, tile_frame, crop_pinned) < std::tie(o.first, o.count, o.kind, o.tile_frame, o.crop_pinned); }
 };
+
+// A captured step: the step, and the two facts that belong to a graph only.
+struct GraphKey {
+    Step step;
+    bool upload;   // the frames' upload is the graph's first node (UP_PINNED_CROP: there is none, and nothing in front of the graph either)
+    int view;      // IRMV_VIEW_*: the view its slots were in when it was captured
+    bool operator<(const GraphKey &o) const { return std::tie(upload, view, step) < std::tie(o.upload, o.view, o.step); }
+};
+
+// The form a submit's frame upload takes, decided in one place (choose_upload) and enqueued in one (enqueue_upload).
+enum UploadForm {
+    UP_NONE,          // no upload was asked for (a submit without IRMV_SUBMIT_H2D: the frames are on the device)
+    UP_PINNED_CROP,   // nothing: the step's crop reads the window out of the pinned slots, so only the window crosses PCIe
+    UP_KERNEL,        // whole frames, by k_pre.hip upload_frame_kernel
+    UP_COPY,          // whole frames, one copy
+    UP_BANDS,         // per slot the band of full-width rows its window covers
+};
+struct Upload { UploadForm form = UP_NONE; int first = 0, count = 0; };   // slots [first, first + count): a tiled step's frame_slot alone
 
 // What a step sees in front of model.1's output -- the source frame and everything that follows from its size.  views[0]
 // (IRMV_VIEW_WINDOW) is what e->cfg describes: the whole frame of an engine without a window, the window of one with it.
@@ -356,6 +384,8 @@ int check_letterbox(const irmv_engine_cfg &c);
 int write_window(irmv_engine *e, int slot);
 int write_isp_table(irmv_engine *e);
 int write_class_table(irmv_engine *e);
+void drop_graphs(irmv_engine *e, bool keep_post);
+int check_window_slot(const irmv_engine *e, int slot, const char *who);
 // engine_graph.cpp
 int dev_alloc(irmv_engine *e, void **p, size_t bytes);
 int load_blob(irmv_engine *e);
@@ -376,21 +406,21 @@ void build_step_plans(irmv_engine *e, View &v);
 void fill_conv_args(const irmv_engine *e, const Op &op, int first, int count, ConvArgs &a, bool fused = false);
 int slots_view(const irmv_engine *e, int first, int count, int *view = nullptr);
 LightArgs light_args(const irmv_engine *e, const View &v, int first);
-PostArgs post_args(const irmv_engine *e, const View &v, int first, bool dev_records = false);
+PostArgs post_args(const irmv_engine *e, const View &v, const Step &s);
 bool launch_head_group(const irmv_engine *e, const irmv_engine::HeadGroup &g, int first, const PostArgs *pa, unsigned scan, hipStream_t s);
-int launch_op(irmv_engine *e, const View &v, const Launch &l, int first, int count, const PostArgs &pa, unsigned scan, bool crop_pinned, hipStream_t s, int tile_frame = -1);
-int enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipStream_t s, int reps, const std::vector<hipEvent_t> *ev, bool crop_pinned = false, int tile_frame = -1);
+int launch_op(irmv_engine *e, const View &v, const Launch &l, const Step &s, const PostArgs &pa, unsigned scan, hipStream_t st);
+int enqueue_step(irmv_engine *e, const Step &s, hipStream_t st, int reps = 1, const std::vector<hipEvent_t> *ev = nullptr);
+void note_submit_windows(irmv_engine *e, int first, int count);
 void mark_stepped(irmv_engine *e, int first, int count);
 int copy_out(irmv_engine *e, int first, int count, hipStream_t st = nullptr);
 int check_range(const irmv_engine *e, int first, int count);
 int load_frame(irmv_engine *e, int slot, hipStream_t st);
 void det_pose(const DevDet &d, bool shift, float ox, float oy, irmv_det &o);
 void slot_det(const irmv_engine *e, int slot, int i, irmv_det &o);
-int get_graph(irmv_engine *e, StepKind kind, int first, int count, bool upload, hipGraphExec_t *out, int tile_frame = -1);
-int group_of(irmv_engine *e, int first, int count, SlotGroup **out);
-bool upload_as_kernel(const irmv_engine *e, int first, int count);
-int copy_out_dev(irmv_engine *e, int first, int count, hipStream_t st);
-int upload_whole(irmv_engine *e, int slot, hipStream_t st, bool copy_engine = false);
+Upload choose_upload(const irmv_engine *e, int first, int count, int tile_frame, bool copy_engine, bool captured);
+int enqueue_upload(irmv_engine *e, const Upload &u, hipStream_t st);
+int get_graph(irmv_engine *e, const Step &s, const Upload &upload, hipGraphExec_t *out);
+int submit_group(irmv_engine *e, int first, int count, uint32_t flags, hipStream_t st, int tile_frame = -1);
 // engine_tiles.cpp
 TileArgs tile_args(const irmv_engine *e, int first, int count);
 // engine_hooks.cpp

@@ -105,11 +105,10 @@ static void launch_bayer(const irmv_engine *e, int first, int count, hipStream_t
     else launch_demosaic(bayer_args(e, first), count, s);
 }
 
-// dev_records (tiled steps): the NMS writes device records also where the engine's ordinary steps write pinned host memory --
-// the merge kernel behind it reads them, and a D2H copy brings them to the host.
-PostArgs irmv::post_args(const irmv_engine *e, const View &v, int first, bool dev_records)
+PostArgs irmv::post_args(const irmv_engine *e, const View &v, const Step &s)
 {
-    const bool zero_copy = e->zero_copy_results && !dev_records;
+    const bool zero_copy = e->zero_copy_results && !s.dev_records();
+    const int first = s.first;
     PostArgs p = e->post;
     p.scale_x = v.scale_x; p.scale_y = v.scale_y; p.off_x = v.off_x; p.off_y = v.off_y;
     p.head_all = e->head_all;
@@ -127,20 +126,20 @@ PostArgs irmv::post_args(const irmv_engine *e, const View &v, int first, bool de
     return p;
 }
 
-// The crop of slots [first, first + count): out of their device frames, or (pinned) out of the pinned slots themselves.
-// tile_frame >= 0 (tiled steps): every slot's window is cut out of that slot's device frame.
-static CropArgs crop_args(const irmv_engine *e, int first, bool pinned, int tile_frame = -1)
+// The crop of the step's slots: out of their device frames, or (crop_pinned) out of the pinned slots themselves.
+// A tiled step: every slot's window is cut out of tile_frame's device frame.
+static CropArgs crop_args(const irmv_engine *e, const Step &s)
 {
     CropArgs a{};
-    a.src = pinned ? e->src_host_dev : e->full_dev; a.src_slot_bytes = e->full_bytes;
+    a.src = s.crop_pinned ? e->src_host_dev : e->full_dev; a.src_slot_bytes = e->full_bytes;
     a.dst = e->src_dev; a.dst_slot_bytes = e->frame_bytes;
-    a.win = e->win_dev; a.first = first;
+    a.win = e->win_dev; a.first = s.first;
     a.full_w = e->full_w; a.full_h = e->full_h; a.win_w = e->cfg.src_width; a.win_h = e->cfg.src_height;
-    a.src_slot = tile_frame;
+    a.src_slot = s.tile_frame;
     return a;
 }
 
-static void launch_crop(const irmv_engine *e, int first, int count, bool pinned, hipStream_t s, int tile_frame = -1) { launch_window_crop(crop_args(e, first, pinned, tile_frame), count, s); }
+static void launch_crop(const irmv_engine *e, const Step &s, hipStream_t st) { launch_window_crop(crop_args(e, s), s.count, st); }
 
 static PreArgs pre_args(const irmv_engine *e, const View &v, const Op &op, int first)
 {
@@ -305,17 +304,16 @@ bool irmv::launch_head_group(const irmv_engine *e, const irmv_engine::HeadGroup 
 }
 
 // ---- step execution ------------------------------------------------------------
-// The one place an op reaches the GPU: the kernel of l.op's kind on slots [first, first + count), stream s, as launch l of a
-// plan of view v says (irmv_engine_run_op: a plain Launch of the op).  scan: the members of l that append scan candidates to pa's key
-// lists (bit k: member k of a group, bit 0: a lone conv); crop_pinned: OP_CROP reads the pinned slots.
-// tile_frame >= 0 (a tiled step): the demosaic runs ONCE, on that slot's raw frame, and the crop cuts every slot's window out of
-// that slot's device frame; every other op is the ordinary step's.
-int irmv::launch_op(irmv_engine *e, const View &v, const Launch &l, int first, int count, const PostArgs &pa, unsigned scan, bool crop_pinned, hipStream_t s, int tile_frame)
+// The one place an op reaches the GPU: the kernel of l.op's kind on the slots of step t, stream s, as launch l of a plan of
+// view v says (irmv_engine_run_op: a plain Launch of the op).  scan: the members of l that append scan candidates to pa's key
+// lists (bit k: member k of a group, bit 0: a lone conv).  A tiled step differs in OP_DEMOSAIC and OP_CROP only (Step).
+int irmv::launch_op(irmv_engine *e, const View &v, const Launch &l, const Step &t, const PostArgs &pa, unsigned scan, hipStream_t s)
 {
     const Op &op = e->ops[l.op];
+    const int first = t.first, count = t.count;
     switch (op.kind) {
-    case OP_DEMOSAIC: if (tile_frame >= 0) launch_bayer(e, tile_frame, 1, s); else launch_bayer(e, first, count, s); break;
-    case OP_CROP: launch_crop(e, first, count, crop_pinned && tile_frame < 0, s, tile_frame); break;
+    case OP_DEMOSAIC: launch_bayer(e, t.bayer_first(), t.bayer_count(), s); break;
+    case OP_CROP: launch_crop(e, t, s); break;
     case OP_PRE: launch_preprocess(pre_args(e, v, op, first), count, s); break;
     case OP_FRONT: if (!launch_front(front_args(e, v, op, first), count, s)) return fail(IRMV_ERR_HIP, "fused front kernel: LDS request refused"); break;
     case OP_C2F2: launch_c2f2(c2f2_args(e, op, first), count, s); break;
@@ -348,17 +346,15 @@ int irmv::launch_op(irmv_engine *e, const View &v, const Launch &l, int first, i
     return IRMV_OK;
 }
 
-// Enqueue a step of kind `kind` on slots [first, first + count), stream s: the launches of that kind's plan in the slots' view
-// (the caller has made sure they share one), in order.
+// Enqueue step t on stream s: the launches of its kind's plan in its slots' view (the caller has made sure they share one),
+// in order; behind them, in a tiled step, the merge of the slots' lists (k_tiles.hip).
 // ev != nullptr (irmv_engine_profile's events): launch i of the plan is repeated `reps` times (once if it is `once`) between
 // (*ev)[2 i] and (*ev)[2 i + 1].
-// tile_frame >= 0: a tiled step of those slots on that slot's frame (launch_op), with device result records and the merge of
-// their lists (k_tiles.hip) as its last node.
-int irmv::enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipStream_t s, int reps, const std::vector<hipEvent_t> *ev, bool crop_pinned, int tile_frame)
+int irmv::enqueue_step(irmv_engine *e, const Step &t, hipStream_t s, int reps, const std::vector<hipEvent_t> *ev)
 {
-    const View &v = view_of(e, first);
-    const std::vector<Launch> &plan = v.plans[kind];
-    const PostArgs pa = post_args(e, v, first, tile_frame >= 0);
+    const View &v = view_of(e, t.first);
+    const std::vector<Launch> &plan = v.plans[t.kind];
+    const PostArgs pa = post_args(e, v, t);
     PostArgs mute = pa;   // (the table's twin with thresholds no logit passes: no key, no bit)
     mute.cls = e->cls_dev + 1;
     for (size_t i = 0; i < plan.size(); i++) {
@@ -369,102 +365,102 @@ int irmv::enqueue_step(irmv_engine *e, StepKind kind, int first, int count, hipS
             // a profiled launch is repeated: only its last repetition appends candidates.  With the sparse head the other
             // repetitions still run the step's kernel -- no class store --, behind the mute threshold.
             const bool last = rep == n - 1, muted = !last && l.scan && e->sparse_head;
-            TRY(launch_op(e, v, l, first, count, muted ? mute : pa, last || muted ? l.scan : 0u, crop_pinned, s, tile_frame));
+            TRY(launch_op(e, v, l, t, muted ? mute : pa, last || muted ? l.scan : 0u, s));
         }
         if (ev) HIP_TRY(hipEventRecord((*ev)[2 * i + 1], s));
     }
-    if (tile_frame >= 0) {
-        launch_tile_merge(tile_args(e, first, count), s);
+    if (t.tiled()) {
+        launch_tile_merge(tile_args(e, t.first, t.count), s);
         HIP_TRY(hipGetLastError());
     }
     return IRMV_OK;
 }
 
+// The corners and views of slots [first, first + count) as of this submit (or merge): what their results are shifted by from
+// here on -- the windows' corners as they are now, or, in the frame view, nothing.
+void irmv::note_submit_windows(irmv_engine *e, int first, int count)
+{
+    if (!e->window) return;
+    std::copy(e->win_org.begin() + first, e->win_org.begin() + first + count, e->sub_org.begin() + first);
+    std::copy(e->slot_view.begin() + first, e->slot_view.begin() + first + count, e->sub_view.begin() + first);
+}
+
 // Slots [first, first + count) have just been stepped: their heads hold the rows, and their gated tensors the tiles, of that
-// step's candidates only (sparse head / branch), and their results are shifted by the windows' corners as they are now -- or,
-// stepped in the frame view, by nothing.
+// step's candidates only (sparse head / branch).
 void irmv::mark_stepped(irmv_engine *e, int first, int count)
 {
     if (e->sparse_head) std::fill(e->head_stale.begin() + first, e->head_stale.begin() + first + count, 1);
     if (e->sparse_branch) std::fill(e->branch_stale.begin() + first, e->branch_stale.begin() + first + count, 1);
-    if (e->window) {
-        std::copy(e->win_org.begin() + first, e->win_org.begin() + first + count, e->sub_org.begin() + first);
-        std::copy(e->slot_view.begin() + first, e->slot_view.begin() + first + count, e->sub_view.begin() + first);
-    }
+    note_submit_windows(e, first, count);
 }
 
-// Frame upload and result download: plain async copies, pinned memory both ways, on the streams submit_group() picks.
-// bands (never inside a stream capture, whose copy parameters are baked): an HWC window engine moves, for groups of up to 8
-// slots, only the band of full-width rows each slot's window covers -- one 1-D copy per slot, to the same offset of its device frame.
-// Slots in the frame view move whole frames.
-constexpr int kBandUploadMaxSlots = 8;
-static int copy_in(irmv_engine *e, int first, int count, hipStream_t st, bool bands = false)
-{
-    if (bands && view_of(e, first).crop && !e->raw_dev && count <= kBandUploadMaxSlots) {
-        const size_t pitch = (size_t)e->full_w * 3, len = (size_t)e->cfg.src_height * pitch;
-        for (int s = first; s < first + count; s++) {
-            const int by0 = e->cfg.rotate180 ? e->full_h - e->win_org[s].y - e->cfg.src_height : e->win_org[s].y;
-            const size_t off = (size_t)s * e->src_bytes + (size_t)by0 * pitch;
-            HIP_TRY(hipMemcpyAsync(e->full_dev + off, e->src_host + off, len, hipMemcpyHostToDevice, st));
-        }
-        return IRMV_OK;
-    }
-    HIP_TRY(hipMemcpyAsync(upload_dev(e) + (size_t)first * e->src_bytes, e->src_host + (size_t)first * e->src_bytes,
-                           e->src_bytes * count, hipMemcpyHostToDevice, st));
-    return IRMV_OK;
-}
-
+// Frame upload and result download: pinned memory both ways, on the streams submit_group() picks.
 // One or two frames travel from the pinned slots as a KERNEL (k_pre.hip upload_frame_kernel), larger groups on the copy engine.
-bool irmv::upload_as_kernel(const irmv_engine *e, int first, int count)
+static bool upload_as_kernel(const irmv_engine *e, int first, int count)
 {
     return count <= 2 && e->sw.upload_kernel_blocks > 0 && e->src_host_dev && upload_aligned(e->src_bytes, first, count);
 }
 
-// The synchronous upload of slots [first, first + count) on stream st.  (A Bayer engine's single-frame upload stays a kernel
-// of its own in front of the demosaic: the demosaic reading the pinned slot itself was built and measured slower, DESIGN.md
-// section 9.)
-// An HWC window engine's synchronous step of one or two slots uploads nothing: its crop reads the window out of the pinned
-// slots (crop_from_pinned), so only the window crosses PCIe.  `captured`: the copy becomes a graph node (whole frames).
-static bool crop_from_pinned(const irmv_engine *e, int first, int count)
+// THE decision of how the pinned frames of slots [first, first + count) reach the device; whoever uploads asks once and hands
+// the answer on (enqueue_upload, get_graph, Step::crop_pinned).
+// copy_engine: the upload rides the side stream, or stands outside a step (load_frame): never a kernel, never nothing.
+// captured: the upload becomes a graph node, whose copy parameters are baked: never bands.
+// tile_frame >= 0 (a tiled step): that slot's frame, whole -- never bands, never the crop out of the pinned slot.
+// Otherwise, in order:
+//   - an HWC window engine's step of one or two slots in the window view uploads nothing: its crop reads the window out of the
+//     pinned slots, so only the window crosses PCIe (IRMV_WINDOW_UPLOAD=0: off);
+//   - the upload kernel.  (A Bayer engine's single-frame upload stays a kernel of its own in front of the demosaic: the demosaic
+//     reading the pinned slot itself was built and measured slower)
+//   - bands: an HWC window engine moves, for groups of up to 8 slots in the window view, only the band of full-width rows each
+//     slot's window covers;
+//   - one copy of the whole frames (every slot in the frame view, every Bayer engine).
+constexpr int kBandUploadMaxSlots = 8;
+Upload irmv::choose_upload(const irmv_engine *e, int first, int count, int tile_frame, bool copy_engine, bool captured)
 {
-    return view_of(e, first).crop && !e->raw_dev && e->sw.window_upload && count <= 2 && e->sw.upload_kernel_blocks > 0 && e->src_host_dev;
+    if (tile_frame >= 0) return {!copy_engine && upload_as_kernel(e, tile_frame, 1) ? UP_KERNEL : UP_COPY, tile_frame, 1};
+    const bool hwc_window = view_of(e, first).crop && !e->raw_dev;
+    if (!copy_engine) {
+        if (hwc_window && e->sw.window_upload && count <= 2 && e->sw.upload_kernel_blocks > 0 && e->src_host_dev) return {UP_PINNED_CROP, first, count};
+        if (upload_as_kernel(e, first, count)) return {UP_KERNEL, first, count};
+    }
+    return {hwc_window && count <= kBandUploadMaxSlots && !captured ? UP_BANDS : UP_COPY, first, count};
 }
 
-static int upload_sync(irmv_engine *e, int first, int count, hipStream_t st, bool captured)
+int irmv::enqueue_upload(irmv_engine *e, const Upload &u, hipStream_t st)
 {
-    if (crop_from_pinned(e, first, count)) return IRMV_OK;
-    if (!upload_as_kernel(e, first, count)) return copy_in(e, first, count, st, !captured);
-    const size_t off = (size_t)first * e->src_bytes;
-    launch_upload_frames(e->src_host_dev + off, upload_dev(e) + off, e->src_bytes * count, e->sw.upload_kernel_blocks, st);
+    const size_t off = (size_t)u.first * e->src_bytes, bytes = e->src_bytes * u.count;
+    switch (u.form) {
+    case UP_NONE: case UP_PINNED_CROP: break;
+    case UP_KERNEL: launch_upload_frames(e->src_host_dev + off, upload_dev(e) + off, bytes, e->sw.upload_kernel_blocks, st); break;
+    case UP_COPY: HIP_TRY(hipMemcpyAsync(upload_dev(e) + off, e->src_host + off, bytes, hipMemcpyHostToDevice, st)); break;
+    case UP_BANDS: {   // one 1-D copy per slot, to the same offset of its device frame
+        const size_t pitch = (size_t)e->full_w * 3, len = (size_t)e->cfg.src_height * pitch;
+        for (int s = u.first; s < u.first + u.count; s++) {
+            const int by0 = e->cfg.rotate180 ? e->full_h - e->win_org[s].y - e->cfg.src_height : e->win_org[s].y;
+            const size_t boff = (size_t)s * e->src_bytes + (size_t)by0 * pitch;
+            HIP_TRY(hipMemcpyAsync(e->full_dev + boff, e->src_host + boff, len, hipMemcpyHostToDevice, st));
+        }
+        break;
+    }
+    }
     return IRMV_OK;
-}
-
-// One slot's pinned frame -> its device frame (raw slot of a Bayer engine), whole: never a band, never nothing (tiled steps).
-// copy_engine: not as the upload kernel (uploads on the side stream).
-int irmv::upload_whole(irmv_engine *e, int slot, hipStream_t st, bool copy_engine)
-{
-    const size_t off = (size_t)slot * e->src_bytes;
-    if (!copy_engine && upload_as_kernel(e, slot, 1)) launch_upload_frames(e->src_host_dev + off, upload_dev(e) + off, e->src_bytes, e->sw.upload_kernel_blocks, st);
-    else HIP_TRY(hipMemcpyAsync(upload_dev(e) + off, e->src_host + off, e->src_bytes, hipMemcpyHostToDevice, st));
-    return IRMV_OK;
-}
-
-int irmv::copy_out(irmv_engine *e, int first, int count, hipStream_t st)
-{
-    if (!st) st = e->stream;
-    if (e->zero_copy_results) return IRMV_OK;   // the kernel has already written the pinned records
-    return copy_out_dev(e, first, count, st);
 }
 
 // the device records of slots [first, first + count) -> their pinned twins (every step of an engine without zero-copy results;
 // tiled steps of any engine)
-int irmv::copy_out_dev(irmv_engine *e, int first, int count, hipStream_t st)
+static int copy_out_dev(irmv_engine *e, int first, int count, hipStream_t st)
 {
     HIP_TRY(hipMemcpyAsync(e->dets_host + (size_t)first * e->cfg.max_det, e->dets_dev + (size_t)first * e->cfg.max_det,
                            (size_t)count * e->cfg.max_det * sizeof(DevDet), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(e->fout_host + first, e->fout_dev + first, (size_t)count * sizeof(DevFrameOut),
                            hipMemcpyDeviceToHost, st));
     return IRMV_OK;
+}
+
+int irmv::copy_out(irmv_engine *e, int first, int count, hipStream_t st)
+{
+    if (e->zero_copy_results) return IRMV_OK;   // the kernel has already written the pinned records
+    return copy_out_dev(e, first, count, st ? st : e->stream);
 }
 
 int irmv::check_range(const irmv_engine *e, int first, int count)
@@ -474,20 +470,17 @@ int irmv::check_range(const irmv_engine *e, int first, int count)
     return IRMV_OK;
 }
 
-// tile_frame >= 0: the graph of a tiled step on that slot's frame; its upload node moves that slot's whole frame.
-int irmv::get_graph(irmv_engine *e, StepKind kind, int first, int count, bool upload, hipGraphExec_t *out, int tile_frame)
+// The captured graph of step s in its slots' present view.  upload (choose_upload's answer with `captured`; UP_NONE: none): the
+// frames' upload as the graph's first node (synchronous single-stream submits).
+int irmv::get_graph(irmv_engine *e, const Step &s, const Upload &upload, hipGraphExec_t *out)
 {
-    const GraphKey key{first, count, kind, upload, e->slot_view[first], tile_frame};
+    const GraphKey key{s, upload.form != UP_NONE, e->slot_view[s.first]};
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) { *out = it->second; return IRMV_OK; }
     hipGraph_t g = nullptr;
     HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-    int rc = IRMV_OK;
-    if (upload && tile_frame >= 0)
-        rc = upload_whole(e, tile_frame, e->stream);
-    else if (upload)   // the frames' upload as the graph's first node (synchronous single-stream submits): one or two frames as a kernel
-        rc = upload_sync(e, first, count, e->stream, true);
-    if (!rc) rc = enqueue_step(e, kind, first, count, e->stream, 1, nullptr, upload && tile_frame < 0 && crop_from_pinned(e, first, count), tile_frame);
+    int rc = enqueue_upload(e, upload, e->stream);
+    if (!rc) rc = enqueue_step(e, s, e->stream);
     hipError_t ce = hipStreamEndCapture(e->stream, &g);
     if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
     if (ce != hipSuccess) return fail(IRMV_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
@@ -499,7 +492,7 @@ int irmv::get_graph(irmv_engine *e, StepKind kind, int first, int count, bool up
     return IRMV_OK;
 }
 
-int irmv::group_of(irmv_engine *e, int first, int count, SlotGroup **out)
+static int group_of(irmv_engine *e, int first, int count, SlotGroup **out)
 {
     const auto key = std::make_pair(first, count);
     auto it = e->groups.find(key);
@@ -525,9 +518,15 @@ int irmv::group_of(irmv_engine *e, int first, int count, SlotGroup **out)
 // so group B's frames cross PCIe while group A's kernels run.  The price is one cross-stream event hop per group
 // (measured on this stack: scripts/probes/stream_probe.cpp), which is why a lone synchronous detect() -- nothing to
 // overlap with -- keeps everything on one stream, and why the (tiny) download never leaves the compute stream.
-static int submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_t st)
+//
+// tile_frame >= 0: a tiled step (irmv_engine_submit_tiles) of the group on that slot's frame.  The same path with other data:
+// tile_frame counts as touched, so a later upload into it waits for this step and this step for whatever touched it last; the
+// caller passes compute stream 0; the step is never eager; its records are device records, copied out on every engine; and the
+// merged list's record (TileOut) follows them in front of event `out`.
+int irmv::submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_t st, int tile_frame)
 {
-    const bool async_up = (flags & IRMV_SUBMIT_H2D) && (flags & IRMV_SUBMIT_ASYNC_UPLOAD) && !e->sw.inline_copies;
+    const bool tiled = tile_frame >= 0, h2d = (flags & IRMV_SUBMIT_H2D) != 0;
+    const bool async_up = h2d && (flags & IRMV_SUBMIT_ASYNC_UPLOAD) && !e->sw.inline_copies;
     // An upload that rides the compute stream anyway (the synchronous detect()) is captured INTO the step's graph: one
     // submission instead of two, and the copy -> first kernel hand-over is the graph's own (IRMV_GRAPH_UPLOAD=0: a separate
     // hipMemcpyAsync in front of the graph, as before; same bits)
@@ -535,18 +534,21 @@ static int submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_
     // kernels and the same bits: ONE hipGraph replay, or its 41 launches issued one by one behind the upload (round 5: a graph
     // replay spends ~10 us of host work before its first packet reaches the GPU, a direct launch ~4; with the 70 us upload in
     // front the host stays far ahead of the GPU: 0.339 -> 0.331 ms per 1280 x 1024 frame).  Every other step is a graph replay.
-    const bool eager = e->sync_launch == 1 && c == 1 && (flags & IRMV_SUBMIT_H2D) && !async_up;
-    const bool pinned = (flags & IRMV_SUBMIT_H2D) && !async_up && crop_from_pinned(e, f, c);   // (no upload at all: nothing to keep out of the graph)
-    const bool graph_up = (flags & IRMV_SUBMIT_H2D) && !async_up && (e->sw.graph_upload || pinned) && !eager;
-    const StepKind kind = c == 1 ? STEP_ONE : STEP_BATCH;
+    const bool eager = !tiled && e->sync_launch == 1 && c == 1 && h2d && !async_up;
+    // The upload's form, asked once: every use below is this answer.  (`captured` is graph_up wherever the answer depends on it.)
+    const Upload upload = h2d ? choose_upload(e, f, c, tile_frame, async_up, !async_up && e->sw.graph_upload && !eager) : Upload{};
+    const bool pinned = upload.form == UP_PINNED_CROP;   // (no upload at all: nothing to keep out of the graph)
+    const bool graph_up = h2d && !async_up && (e->sw.graph_upload || pinned) && !eager;
+    const Step step{c == 1 ? STEP_ONE : STEP_BATCH, f, c, tile_frame, pinned};
     hipGraphExec_t ge = nullptr;
-    if (!eager) TRY(get_graph(e, kind, f, c, graph_up, &ge));
+    if (!eager) TRY(get_graph(e, step, graph_up ? upload : Upload{}, &ge));
     SlotGroup *g;
     TRY(group_of(e, f, c, &g));
     hipStream_t up = async_up ? e->h2d_stream : st;
-    // slots last used through a different grouping: order behind that group's completion
+    // slots last used through a different grouping (a tiled step: the frame's owner too): order behind that group's completion
     SlotGroup *seen[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int s = f; s < f + c; s++) {
+    for (int i = 0; i < c + (tiled ? 1 : 0); i++) {
+        const int s = i < c ? f + i : tile_frame;
         SlotGroup *o = e->slot_owner[s];
         e->slot_owner[s] = g;
         if (!o || o == g || !o->in_flight || o == seen[0] || o == seen[1] || o == seen[2] || o == seen[3]) continue;
@@ -555,21 +557,25 @@ static int submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_
         if (up != st) HIP_TRY(hipStreamWaitEvent(up, o->out, 0));
     }
     if (g->in_flight && g->compute != st) HIP_TRY(hipStreamWaitEvent(st, g->out, 0));   // the group moved to another compute stream
-    if (flags & IRMV_SUBMIT_H2D) {
-        if (async_up) {
-            if (g->in_flight) HIP_TRY(hipStreamWaitEvent(up, g->out, 0));   // previous step has consumed the device frames
-            TRY(copy_in(e, f, c, up, true));
-            HIP_TRY(hipEventRecord(g->h2d, up));
-            HIP_TRY(hipStreamWaitEvent(st, g->h2d, 0));
-        } else if (!graph_up) {
-            // (an eager step, or IRMV_GRAPH_UPLOAD=0)
-            TRY(upload_sync(e, f, c, st, false));
-        }
+    if (async_up) {
+        if (g->in_flight) HIP_TRY(hipStreamWaitEvent(up, g->out, 0));   // previous step has consumed the device frames
+        TRY(enqueue_upload(e, upload, up));
+        HIP_TRY(hipEventRecord(g->h2d, up));
+        HIP_TRY(hipStreamWaitEvent(st, g->h2d, 0));
+    } else if (!graph_up) {
+        // (an eager step, or IRMV_GRAPH_UPLOAD=0; a submit without IRMV_SUBMIT_H2D: UP_NONE)
+        TRY(enqueue_upload(e, upload, st));
     }
-    if (eager) TRY(enqueue_step(e, kind, f, c, st, 1, nullptr, pinned));
+    if (eager) TRY(enqueue_step(e, step, st));
     else HIP_TRY(hipGraphLaunch(ge, st));
     mark_stepped(e, f, c);
-    TRY(copy_out(e, f, c, st));
+    if (tiled) {
+        const irmv_engine::TileMerge &tm = e->tile_merges.at(f);
+        TRY(copy_out_dev(e, f, c, st));
+        HIP_TRY(hipMemcpyAsync(tm.out_host, tm.out_dev, sizeof(TileOut), hipMemcpyDeviceToHost, st));
+    } else {
+        TRY(copy_out(e, f, c, st));
+    }
     HIP_TRY(hipEventRecord(g->out, st));
     g->in_flight = true;
     g->async_up = async_up;
@@ -610,7 +616,7 @@ extern "C" int irmv_engine_run_post(irmv_engine *e, int first, int count)
     TRY(irmv_engine_wait(e));
     for (int s = first; s < first + count; s++) TRY(ensure_dense_head(e, s));   // (scan_decode_kernel reads every anchor's class logits)
     hipGraphExec_t ge;
-    TRY(get_graph(e, STEP_POST, first, count, false, &ge));
+    TRY(get_graph(e, Step{STEP_POST, first, count}, Upload{}, &ge));
     HIP_TRY(hipGraphLaunch(ge, e->stream));
     TRY(copy_out(e, first, count));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -719,13 +725,13 @@ extern "C" double irmv_engine_last_detect_ms(const irmv_engine *e) { return e ? 
 // window is then cut out.
 int irmv::load_frame(irmv_engine *e, int slot, hipStream_t st)
 {
-    TRY(copy_in(e, slot, 1, st, true));
+    TRY(enqueue_upload(e, choose_upload(e, slot, 1, -1, true, false), st));   // (the copy engine, uncaptured: a band or the whole frame)
     if (e->raw_dev) {
         launch_bayer(e, slot, 1, st);
         HIP_TRY(hipGetLastError());
     }
     if (view_of(e, slot).crop) {
-        launch_crop(e, slot, 1, false, st);
+        launch_crop(e, Step{STEP_ONE, slot, 1}, st);
         HIP_TRY(hipGetLastError());
     }
     return IRMV_OK;

@@ -54,7 +54,7 @@ TileArgs irmv::tile_args(const irmv_engine *e, int first, int count)
 
 // One tiled step: [upload of frame_slot's frame] -> ONE hipGraph {[demosaic of that frame] -> crop of every slot's window out
 // of it -> the slots' ordinary step -> merge} -> D2H of the slots' records and of the merged list, on compute stream 0.  It is
-// one slot group, ordered against other groups by the slot_owner rules of submit_group; frame_slot counts as touched.
+// the slot group (first, count), submitted by the path every step takes (engine_step.cpp submit_group).
 extern "C" int irmv_engine_submit_tiles(irmv_engine *e, int frame_slot, int first, int count, uint32_t flags)
 {
     TRY(check_tiles(e, first, count, "irmv_engine_submit_tiles"));
@@ -62,43 +62,7 @@ extern "C" int irmv_engine_submit_tiles(irmv_engine *e, int frame_slot, int firs
     HIP_TRY(hipSetDevice(e->cfg.device));
     irmv_engine::TileMerge *tm;
     TRY(ensure_tiles(e, first, &tm));
-    hipStream_t st = e->stream;
-    const bool h2d = (flags & IRMV_SUBMIT_H2D) != 0;
-    const bool async_up = h2d && (flags & IRMV_SUBMIT_ASYNC_UPLOAD) && !e->sw.inline_copies;
-    const bool graph_up = h2d && !async_up && e->sw.graph_upload;
-    hipGraphExec_t ge = nullptr;
-    TRY(get_graph(e, count == 1 ? STEP_ONE : STEP_BATCH, first, count, graph_up, &ge, frame_slot));
-    SlotGroup *g;
-    TRY(group_of(e, first, count, &g));
-    hipStream_t up = async_up ? e->h2d_stream : st;
-    // slots last used through a different grouping -- the tiles and the frame's owner -- : order behind that group's completion
-    SlotGroup *seen[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int i = 0; i <= count; i++) {
-        const int s = i < count ? first + i : frame_slot;
-        SlotGroup *o = e->slot_owner[s];
-        e->slot_owner[s] = g;
-        if (!o || o == g || !o->in_flight || o == seen[0] || o == seen[1] || o == seen[2] || o == seen[3]) continue;
-        seen[3] = seen[2]; seen[2] = seen[1]; seen[1] = seen[0]; seen[0] = o;
-        if (o->compute != st) HIP_TRY(hipStreamWaitEvent(st, o->out, 0));
-        if (up != st) HIP_TRY(hipStreamWaitEvent(up, o->out, 0));
-    }
-    if (g->in_flight && g->compute != st) HIP_TRY(hipStreamWaitEvent(st, g->out, 0));
-    if (async_up) {
-        if (g->in_flight) HIP_TRY(hipStreamWaitEvent(up, g->out, 0));   // the previous step has consumed the device frame
-        TRY(upload_whole(e, frame_slot, up, true));
-        HIP_TRY(hipEventRecord(g->h2d, up));
-        HIP_TRY(hipStreamWaitEvent(st, g->h2d, 0));
-    } else if (h2d && !graph_up) {
-        TRY(upload_whole(e, frame_slot, st, false));
-    }
-    HIP_TRY(hipGraphLaunch(ge, st));
-    mark_stepped(e, first, count);
-    TRY(copy_out_dev(e, first, count, st));
-    HIP_TRY(hipMemcpyAsync(tm->out_host, tm->out_dev, sizeof(TileOut), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(g->out, st));
-    g->in_flight = true;
-    g->async_up = async_up;
-    g->compute = st;
+    TRY(submit_group(e, first, count, flags, e->stream, frame_slot));
     tm->count = count;
     tm->valid = true;
     return IRMV_OK;
@@ -120,9 +84,7 @@ extern "C" int irmv_engine_merge_tiles(irmv_engine *e, int first, int count)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(tm->out_host, tm->out_dev, sizeof(TileOut), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    // the merge took the corners as they are now: the slots' records are read in them from here on
-    std::copy(e->win_org.begin() + first, e->win_org.begin() + first + count, e->sub_org.begin() + first);
-    std::copy(e->slot_view.begin() + first, e->slot_view.begin() + first + count, e->sub_view.begin() + first);
+    note_submit_windows(e, first, count);   // the merge took the corners as they are now: the slots' records are read in them from here on
     tm->count = count;
     tm->valid = true;
     return IRMV_OK;

@@ -270,6 +270,37 @@ def test_launch_forms_and_moving_tiles(wblob):
         check_merge(w, 1, CORNERS4, FULL, WIN)
 
 
+def test_tiled_and_single_slot_steps_order_across_compute_streams(wblob):
+    """Five slots give two compute streams: single-slot steps of slots 1 and 3 ride stream 1, tiled steps stream 0.  Submitted
+    back to back with no wait in between, the later step of a slot is ordered behind the earlier one on the other stream."""
+    a, b = frame_of(12), frame_of(61)
+    with weng(wblob, num_slots=5) as w:
+        w.get_src_image_buffer(0)[:] = a
+        for s in range(1, 5):
+            w.get_src_image_buffer(s)[:] = b
+        w.set_tiles(CORNERS4, first=1)
+        g0 = w.debug_graph_count()
+        # 1. the tiled step runs behind slot 1's ordinary step and overwrites it
+        w.submit(1, 1, async_upload=True)
+        w.submit_tiles(0, 1, 4)
+        w.wait_slots(1, 4)
+        solved = 0
+        for t, org in enumerate(CORNERS4):
+            solved += same_results(snapshot(w, 1 + t, False), reference(wblob, a, org, tag="f12"), org, ("tiles behind slot 1", t))
+        check_merge(w, 1, CORNERS4, FULL, WIN)
+        assert solved > 0
+        g1 = w.debug_graph_count()
+        assert g1 == g0 + 2                             # slot 1's step without an upload node, the tiled step with one
+        # 2. slot 3's ordinary step waits for the tiled one before its upload and crop replace the slot's frames
+        w.submit_tiles(0, 1, 4)
+        w.submit(3, 1, async_upload=True)
+        w.wait_slots(3, 1)
+        org = CORNERS4[2]
+        assert same_results(snapshot(w, 3, False), reference(wblob, b, org, tag="f61"), org, "slot 3 behind the tiles") > 0
+        w.wait_slots(1, 4)
+        assert w.debug_graph_count() == g1 + 1          # slot 3's step; the tiled step captured nothing again
+
+
 # ---- 5. Bayer ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("algo", ["bilinear", "mhc"])
 def test_bayer_tiles_are_bayer_windows(wblob, algo):
