@@ -164,7 +164,8 @@ typedef struct irmv_engine_cfg {
 typedef struct irmv_det {
     float xyxy[4];
     float score;
-    int32_t class_id;  /* 0..13, 14 = UNKNOWN */
+    int32_t class_id;  /* 0..13, 14 = UNKNOWN.  A model with nc > 14 reports its classes >= 14 as UNKNOWN here;
+                        * irmv_raw_dets.det_classes keeps them. */
     int32_t anchor;    /* index of the originating anchor (debug / parity) */
     int32_t pnp_ok;    /* 1 if rvec/tvec are valid */
     float kpts[8];     /* left-bottom, left-top, right-top, right-bottom; source-frame pixels */
