@@ -95,6 +95,9 @@ public:
     std::vector<int> large_plate_classes;                // ArmorClass values whose detections PnP solves with the 225 mm plate; the rest: 135 mm
     int point_source = IRMV_POINTS_AUTO;                 // IRMV_POINTS_*; IRMV_POINTS_REFINED: a pose model's points snapped to the light bars, inside the step
     double refine_snap = 0.5, refine_roi_margin = 4.0;   // its two live parameters (irmv_engine_set_refine; set_parameter "refine.snap" / "refine.roi_margin")
+    bool debug = false;                                  // the node's debug (:90-95, :259-280): every frame also yields FrameResult::visualized_image / binary_image,
+                                                         // rendered on the GPU (YoloEngine::render); live through set_bool_parameter("debug", v) like the reference (:380-381)
+    int debug_scale = 1;                                 // 1, 2 or 4: the debug images at full, half or quarter size (set_parameter "debug_scale")
   };
 
   // What one frame produced, beyond the message: kept for debug publishers and tests.
@@ -105,6 +108,9 @@ public:
     std::vector<Armor> armors;          // one per message entry, same order
     std::vector<irmv_det> poses;        // rvec / tvec / quaternion of each, as computed on the GPU
     double inference_latency_ms = 0;    // YoloEngine::get_profiling_time() (:251)
+    // Params::debug only (else empty): the frame with this frame's armors, boxes and labels drawn on it (:261-263; the latency
+    // text lines are not drawn), and gray -> threshold(binary_threshold) -> three channels with the boxes and labels (:273-277)
+    cv::Mat visualized_image, binary_image;
   };
 
   // Three engines, one per TripleBuffer slot, like the node (:33-38); K, D from camera_info (:52).
@@ -181,6 +187,30 @@ public:
       out.poses.push_back(d);
     }
     out.inference_latency_ms = eng.get_profiling_time();
+    if (params_.debug) {
+      // the marks: every bbox (:263, :277) and every extracted armor (:262) -- of a pose model both live in the detection
+      // records; of a bbox-only model the armors are records of their own whose box is no number, so it draws none
+      std::vector<irmv_det> marks;
+      if (eng.has_keypoint_head()) {
+        int n = 0;
+        const irmv_det * dets = eng.last_detections(&n);
+        marks.assign(dets, dets + n);
+      } else {
+        for (const auto & b : out.bboxes) {
+          irmv_det m{};
+          std::copy(b.xyxy.begin(), b.xyxy.end(), m.xyxy);
+          m.class_id = static_cast<int32_t>(b.class_id);
+          marks.push_back(m);
+        }
+        for (irmv_det m : poses) {
+          std::fill(m.xyxy, m.xyxy + 4, std::nanf(""));
+          marks.push_back(m);
+        }
+        if (marks.size() > eng.max_det()) marks.resize(eng.max_det());   // (boxes first: the armors' marks are what is dropped)
+      }
+      out.visualized_image = eng.render(IRMV_RENDER_COLOR, params_.debug_scale, IRMV_MARK_BOXES | IRMV_MARK_LABELS | IRMV_MARK_ARMORS, &marks);
+      out.binary_image = eng.render(IRMV_RENDER_BINARY, params_.debug_scale, IRMV_MARK_BOXES | IRMV_MARK_LABELS, &marks);
+    }
     return out;
   }
 
@@ -195,6 +225,12 @@ public:
     else if (name == "armor.max_small_center_distance") params_.armor_max_small_center_distance = value;
     else if (name == "armor.min_large_center_distance") params_.armor_min_large_center_distance = value;
     else if (name == "armor.max_large_center_distance") params_.armor_max_large_center_distance = value;
+    else if (name == "debug_scale") {                      // live: the next frame's debug images have that size
+      const int sc = int(value);
+      if (sc != 1 && sc != 2 && sc != 4) return false;
+      params_.debug_scale = sc;
+      return true;
+    }
     else if (name == "enemy_color") {                      // :384-385; live, and re-captures nothing
       const int c = int(value);
       if (c < -1 || c > 1) return false;
@@ -211,6 +247,15 @@ public:
     }
     else return false;
     for (auto & e : yolo_engines_) push_params(*e);
+    return true;
+  }
+
+  // The node's bool parameters (parameter.as_bool(), :380-381): "debug" is live -- the next frame carries, or drops, the two
+  // debug images.  (A NUMBER sent to "debug" through set_parameter stays refused, as it is not a number.)
+  bool set_bool_parameter(const std::string & name, bool value)
+  {
+    if (name != "debug") return false;
+    params_.debug = value;
     return true;
   }
 

@@ -375,6 +375,32 @@ public:
     return rotated_;
   }
 
+  // The node's debug images (src/irm_detector.cpp:259-280), rendered on the GPU from the frame of the last detect() -- a Bayer
+  // engine's demosaiced frame, a window engine's window (View::Frame: the whole frame): kind IRMV_RENDER_COLOR is the frame,
+  // IRMV_RENDER_BINARY gray > binary_threshold on three channels (-1: the threshold set with set_extract_params); scale 1, 2
+  // or 4 shrinks it for a radio link; marks (IRMV_MARK_BOXES | _LABELS | _ARMORS) of `dets` are drawn on it, nullptr = the
+  // last detect()'s own records.  Only the finished CV_8UC3 picture crosses PCIe (include/irmv_hip.h, "debug images").  The
+  // drawing is this project's own rasteriser and 5 x 7 font, not OpenCV's: at scale 1 boxes and labels are the pixels
+  // visualize_bboxes draws without OpenCV.
+  cv::Mat render(int kind = IRMV_RENDER_COLOR, int scale = 1, uint32_t marks = IRMV_MARK_BOXES | IRMV_MARK_LABELS | IRMV_MARK_ARMORS,
+                 const std::vector<irmv_det> * dets = nullptr, int binary_threshold = -1)
+  {
+    irmv_render_opts o{};
+    o.struct_size = sizeof o;
+    o.kind = kind;
+    o.scale = scale;
+    o.marks = marks;
+    o.binary_threshold = binary_threshold;
+    int w = 0, h = 0;
+    if (irmv_engine_render_dims(engine_, 0, scale, &w, &h) != IRMV_OK) throw std::runtime_error(std::string("YoloEngine::render: ") + irmv_last_error());
+    cv::Mat out(h, w, CV_8UC3);
+    if (irmv_engine_render(engine_, 0, &o, dets ? dets->data() : nullptr, dets ? static_cast<int>(dets->size()) : -1, out.data) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::render: ") + irmv_last_error());
+    return out;
+  }
+
+  size_t max_det() const { return dets_.size(); }
+
   uint8_t * get_src_image_buffer() const { return src_image_buffer_; }
   // bytes a producer writes into get_src_image_buffer() per frame: width * height * 3 (HWC8) or width * height (Bayer)
   size_t src_image_bytes() const { return irmv_engine_src_bytes(engine_); }
@@ -396,26 +422,13 @@ private:
   // Class label without OpenCV: the ArmorClass names (B1..B5, BO, BS, R1..R5, RO, RS, UNKNOWN) in a 5 x 7 bitmap font at
   // scale 3 (glyphs 15 x 21 px, 18 px advance: the size of FONT_HERSHEY_SIMPLEX at scale 1), text origin = bottom-left
   // corner at (x, y) like cv::putText (src/yolo_engine.cpp:238-241).
-  static const uint8_t * glyph(char c)
-  {
-    static const uint8_t font[][8] = {
-      {'B', 0x1e, 0x11, 0x11, 0x1e, 0x11, 0x11, 0x1e}, {'R', 0x1e, 0x11, 0x11, 0x1e, 0x14, 0x12, 0x11},
-      {'O', 0x0e, 0x11, 0x11, 0x11, 0x11, 0x11, 0x0e}, {'S', 0x0f, 0x10, 0x10, 0x0e, 0x01, 0x01, 0x1e},
-      {'U', 0x11, 0x11, 0x11, 0x11, 0x11, 0x11, 0x0e}, {'N', 0x11, 0x19, 0x15, 0x13, 0x11, 0x11, 0x11},
-      {'K', 0x11, 0x12, 0x14, 0x18, 0x14, 0x12, 0x11}, {'W', 0x11, 0x11, 0x11, 0x15, 0x15, 0x1b, 0x11},
-      {'1', 0x04, 0x0c, 0x04, 0x04, 0x04, 0x04, 0x0e}, {'2', 0x0e, 0x11, 0x01, 0x02, 0x04, 0x08, 0x1f},
-      {'3', 0x1e, 0x01, 0x01, 0x0e, 0x01, 0x01, 0x1e}, {'4', 0x02, 0x06, 0x0a, 0x12, 0x1f, 0x02, 0x02},
-      {'5', 0x1f, 0x10, 0x1e, 0x01, 0x01, 0x11, 0x0e}};
-    for (const auto & g : font)
-      if (g[0] == uint8_t(c)) return g + 1;
-    return nullptr;
-  }
+  // The glyphs are the library's (irmv_render_glyph): the table the GPU's debug images are drawn from.
   static void draw_label(cv::Mat & img, const std::string & text, int x, int y, int c0, int c1, int c2)
   {
     constexpr int S = 3;
     for (size_t k = 0; k < text.size(); k++) {
-      const uint8_t * g = glyph(text[k]);
-      if (!g) continue;
+      uint8_t g[7];
+      if (irmv_render_glyph(text[k], g) != IRMV_OK) continue;
       for (int r = 0; r < 7; r++)
         for (int c = 0; c < 5; c++) {
           if (!((g[r] >> (4 - c)) & 1)) continue;

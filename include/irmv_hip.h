@@ -394,6 +394,54 @@ double irmv_engine_last_detect_ms(const irmv_engine *e);
  * IRMV_VIEW_FRAME, the rotated full frame: src_height*src_width*3 bytes. */
 int irmv_engine_rotated_image(irmv_engine *e, int slot, uint8_t *dst_hwc);
 
+/* ---- debug images: the node's visualized and binary frames, rendered on the GPU -----------------------------------------
+ * What the reference node publishes in debug mode (src/irm_detector.cpp:259-280): the frame with the armors and boxes drawn on
+ * it, and gray -> threshold -> three channels with the boxes.  One kernel (k_render.hip render_view) produces either from the
+ * slot's device frame, optionally at 1/2 or 1/4 size, and only the finished picture crosses PCIe.  On demand, like
+ * irmv_engine_rotated_image, and no part of a captured step: the call waits for what is in flight, loads the slot's current
+ * frame (a Bayer engine's demosaiced, a window slot's cropped; IRMV_VIEW_FRAME: the full frame), copies the marks to a device
+ * scratch, launches once, copies the picture back and synchronizes.  Its scratch is allocated by the first call; it captures
+ * and drops no graph.  irmv_detection_amd/render.py is the host reference, bit for bit:
+ *   R        the W x H frame of the slot's view in the coordinates detections come back in (rotated under cfg.rotate180: what
+ *            irmv_engine_rotated_image returns), channels as stored;  output ow = W / s, oh = H / s, trailing source columns and
+ *            rows dropped
+ *   colour   per channel (sum of the s x s block of R + s*s/2) / (s*s)
+ *   binary   255 on all three channels where any pixel of the block has gray > T,
+ *            gray = (p0*3735 + p1*19235 + p2*9798 + (1<<14)) >> 15 (the light extraction's), else 0
+ *   marks    every float truncated toward zero, a window slot's corner subtracted, floor-divided by s.  A record with a
+ *            non-finite xyxy value or one of magnitude >= 2^24 gets no box and no label; one with such a kpts value or
+ *            armor_valid != 1 no armor mark.  First the armor marks of every record, then per record its box and its label;
+ *            later marks overwrite earlier ones.
+ *   box      2-px lines, (0,0,255) for classes 0..6, (255,0,0) otherwise; label: the ArmorClass name (class_id outside 0..13:
+ *            UNKNOWN) in the 5 x 7 font of irmv_render_glyph, cell 3, 2, 1 px for s = 1, 2, 4, bottom-left corner at the box's
+ *            first corner -- at s = 1 exactly YoloEngine::visualize_bboxes without OpenCV
+ *   armor    green (0,255,0): a ring of radius r = 5, 3, 2 at LB, LT, RT, RB (|dx^2 + dy^2 - r^2| <= 2r) and the segments
+ *            LT-LB, RT-RB, LT-RT, LB-RB: every pixel within distance 1 of the segment, in 64-bit integers */
+#define IRMV_RENDER_COLOR  0
+#define IRMV_RENDER_BINARY 1
+#define IRMV_MARK_BOXES  1u
+#define IRMV_MARK_LABELS 2u
+#define IRMV_MARK_ARMORS 4u
+typedef struct irmv_render_opts {
+    uint32_t struct_size;      /* = sizeof(irmv_render_opts) */
+    int32_t kind;              /* IRMV_RENDER_* */
+    int32_t scale;             /* 1, 2 or 4 */
+    uint32_t marks;            /* IRMV_MARK_* bits */
+    int32_t binary_threshold;  /* 0..255, or -1 = the engine's current one (irmv_engine_set_extract_params) */
+    int32_t reserved[3];       /* must be 0 */
+} irmv_render_opts;
+/* The picture's size at `scale` for the slot's current view. */
+int irmv_engine_render_dims(const irmv_engine *e, int slot, int scale, int *w, int *h);
+/* dets == NULL with n == -1: the slot's last results, as irmv_engine_results returns them (a slot never stepped has none;
+ * creation may have stepped slot 0 on its empty frame to time detect()'s launch form);
+ * otherwise 0 <= n <= max_det explicit records, of which xyxy, class_id, kpts and armor_valid are read.  dst_hwc receives
+ * h * w * 3 bytes.  IRMV_ERR_ARG (a null engine, opts or dst, a wrong struct_size, an unknown kind, a scale other than 1, 2, 4,
+ * unknown mark bits, non-zero reserved fields, a threshold outside -1..255, a bad slot or n) leaves the engine as it was. */
+int irmv_engine_render(irmv_engine *e, int slot, const irmv_render_opts *o, const irmv_det *dets, int n, uint8_t *dst_hwc);
+/* Host only: the 5 x 7 glyph the kernel draws for ch, row 0 on top, bit 4 the leftmost column; IRMV_ERR_ARG if there is none.
+ * The device table is uploaded from this one. */
+int irmv_render_glyph(int ch, uint8_t rows[7]);
+
 /* The gains and tone curve of a Bayer engine, changeable while it lives (the camera SDK's ISP retuned per venue):
  *   out = lut[c][min(255, (v * gain_q8[c] + 128) >> 8)]   per channel c = R, G, B,
  * v the interpolated value.  gain_q8: Q8 in [0, 1023]; lut: [3][256] bytes, rows R, G, B, NULL = identity (then exactly the

@@ -29,6 +29,7 @@ SOURCES = [
     ("k_tiles.hip", ["-ffp-contract=off"]),
     ("k_light.hip", ["-ffp-contract=off"]),
     ("k_shuffle.hip", []),
+    ("k_render.hip", []),
     ("k_debug.hip", []),
     ("engine.cpp", ["-x", "hip"]),
     ("engine_graph.cpp", ["-x", "hip"]),

@@ -83,6 +83,18 @@ class ClassPolicy(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("score_thr", C.c_float * 16), ("plate", C.c_uint8 * 16)]
 
 
+RENDER_COLOR, RENDER_BINARY = 0, 1
+RENDER_KINDS = {"color": RENDER_COLOR, "binary": RENDER_BINARY}
+MARK_BOXES, MARK_LABELS, MARK_ARMORS = 1, 2, 4
+MARK_ALL = MARK_BOXES | MARK_LABELS | MARK_ARMORS
+
+
+class RenderOpts(C.Structure):
+    """irmv_render_opts (include/irmv_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("scale", C.c_int32), ("marks", C.c_uint32),
+                ("binary_threshold", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("layer", C.c_char * 32), ("flops", C.c_double),
                 ("bytes", C.c_double), ("ms", C.c_float), ("reserved", C.c_int32)]
@@ -205,6 +217,9 @@ SYMBOLS = [
     ("irmv_engine_detect", C.c_int, [_P, C.c_int, C.POINTER(Det), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_engine_last_detect_ms", C.c_double, [_P]),
     ("irmv_engine_rotated_image", C.c_int, [_P, C.c_int, C.POINTER(C.c_uint8)]),
+    ("irmv_engine_render_dims", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("irmv_engine_render", C.c_int, [_P, C.c_int, C.POINTER(RenderOpts), C.POINTER(Det), C.c_int, C.POINTER(C.c_uint8)]),
+    ("irmv_render_glyph", C.c_int, [C.c_int, C.POINTER(C.c_uint8)]),
     ("irmv_engine_extract_armors", C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(Det)]),
     ("irmv_engine_set_bayer_isp", C.c_int, [_P, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]),
     ("irmv_engine_get_bayer_isp", C.c_int, [_P, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]),
@@ -313,6 +328,20 @@ def light_limits() -> dict:
     v = (C.c_int32 * 4)()
     check(load().irmv_light_limits(v))
     return dict(max_contours=v[0], points_cap=v[1], lds_image=v[2], lds_points=v[3])
+
+
+def render_opts(kind=RENDER_COLOR, scale=1, marks=MARK_ALL, binary_threshold=-1) -> RenderOpts:
+    """An irmv_render_opts (no check: the library's are the ones under test)."""
+    o = RenderOpts()
+    o.struct_size = C.sizeof(RenderOpts)
+    o.kind, o.scale, o.marks, o.binary_threshold = int(kind), int(scale), int(marks), int(binary_threshold)
+    return o
+
+
+def render_glyph(ch: str):
+    """irmv_render_glyph (host only): the seven rows of the 5 x 7 glyph drawn for ch, or None where there is none."""
+    rows = (C.c_uint8 * 7)()
+    return tuple(rows) if load().irmv_render_glyph(ord(ch), rows) == OK else None
 
 
 def class_policy_struct(score_thr, plate) -> ClassPolicy:

@@ -58,6 +58,138 @@ extern "C" int irmv_engine_rotated_image(irmv_engine *e, int slot, uint8_t *dst)
     return IRMV_OK;
 }
 
+// ---- debug images (include/irmv_hip.h, "debug images"; k_render.hip) -----------------------------------------------------
+// THE glyph table: irmv_render_glyph reads it, and the device font is built from it.
+static const struct { char ch; uint8_t rows[7]; } kRenderGlyphs[] = {
+    {'B', {0x1e, 0x11, 0x11, 0x1e, 0x11, 0x11, 0x1e}}, {'R', {0x1e, 0x11, 0x11, 0x1e, 0x14, 0x12, 0x11}},
+    {'O', {0x0e, 0x11, 0x11, 0x11, 0x11, 0x11, 0x0e}}, {'S', {0x0f, 0x10, 0x10, 0x0e, 0x01, 0x01, 0x1e}},
+    {'U', {0x11, 0x11, 0x11, 0x11, 0x11, 0x11, 0x0e}}, {'N', {0x11, 0x19, 0x15, 0x13, 0x11, 0x11, 0x11}},
+    {'K', {0x11, 0x12, 0x14, 0x18, 0x14, 0x12, 0x11}}, {'W', {0x11, 0x11, 0x11, 0x15, 0x15, 0x1b, 0x11}},
+    {'1', {0x04, 0x0c, 0x04, 0x04, 0x04, 0x04, 0x0e}}, {'2', {0x0e, 0x11, 0x01, 0x02, 0x04, 0x08, 0x1f}},
+    {'3', {0x1e, 0x01, 0x01, 0x0e, 0x01, 0x01, 0x1e}}, {'4', {0x02, 0x06, 0x0a, 0x12, 0x1f, 0x02, 0x02}},
+    {'5', {0x1f, 0x10, 0x1e, 0x01, 0x01, 0x11, 0x0e}}};
+constexpr int kRenderGlyphCount = (int)(sizeof kRenderGlyphs / sizeof *kRenderGlyphs);
+static_assert(kRenderGlyphCount <= 16, "RenderFont::glyph");
+// ArmorClass names (reference include/irmv_detection/armor.hpp:7), UNKNOWN last
+static const char *const kRenderNames[IRMV_NUM_CLASSES + 1] = {"B1", "B2", "B3", "B4", "B5", "BO", "BS", "R1", "R2", "R3", "R4", "R5", "RO", "RS", "UNKNOWN"};
+
+static int render_glyph_index(int ch)
+{
+    for (int i = 0; i < kRenderGlyphCount; i++)
+        if (kRenderGlyphs[i].ch == ch) return i;
+    return -1;
+}
+
+extern "C" int irmv_render_glyph(int ch, uint8_t rows[7])
+{
+    const int i = render_glyph_index(ch);
+    if (i < 0 || !rows) return fail(IRMV_ERR_ARG, "render_glyph: no such glyph, or rows is null");
+    memcpy(rows, kRenderGlyphs[i].rows, 7);
+    return IRMV_OK;
+}
+
+static int check_render_scale(int scale)
+{
+    if (scale != 1 && scale != 2 && scale != 4) return fail(IRMV_ERR_ARG, "render: scale must be 1, 2 or 4");
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_render_dims(const irmv_engine *e, int slot, int scale, int *w, int *h)
+{
+    TRY(check_range(e, slot, 1));
+    TRY(check_render_scale(scale));
+    if (!w || !h) return fail(IRMV_ERR_ARG, "render_dims: w / h is null");
+    const View &v = view_of(e, slot);
+    *w = v.src_w / scale;
+    *h = v.src_h / scale;
+    return IRMV_OK;
+}
+
+// The scratch of irmv_engine_render, made by its first call: mark records, the font, the picture.
+static int ensure_render(irmv_engine *e)
+{
+    if (e->render_out) return IRMV_OK;
+    RenderFont f;
+    memset(&f, 0, sizeof f);
+    for (int i = 0; i < kRenderGlyphCount; i++) memcpy(f.glyph[i], kRenderGlyphs[i].rows, 7);
+    for (int c = 0; c <= IRMV_NUM_CLASSES; c++) {
+        f.len[c] = (uint8_t)strlen(kRenderNames[c]);
+        for (int k = 0; k < f.len[c]; k++) f.name[c][k] = (uint8_t)render_glyph_index(kRenderNames[c][k]);
+    }
+    if (!e->render_marks) TRY(dev_alloc(e, (void **)&e->render_marks, (size_t)e->cfg.max_det * sizeof(RenderMark)));
+    if (!e->render_font) TRY(dev_alloc(e, (void **)&e->render_font, sizeof(RenderFont)));
+    HIP_TRY(hipMemcpy(e->render_font, &f, sizeof f, hipMemcpyHostToDevice));
+    e->render_marks_host.resize((size_t)e->cfg.max_det);
+    TRY(dev_alloc(e, (void **)&e->render_out, std::max(e->frame_bytes, e->full_bytes)));
+    return IRMV_OK;
+}
+
+// A mark coordinate: v truncated toward zero, the corner subtracted, floor-divided by the scale; false where v has none
+static bool render_coord(float v, int org, int scale, int32_t *out)
+{
+    if (!std::isfinite(v) || std::fabs(v) >= 16777216.f) return false;
+    const int t = (int)v - org;
+    *out = t >= 0 ? t / scale : -((-t + scale - 1) / scale);
+    return true;
+}
+
+extern "C" int irmv_engine_render(irmv_engine *e, int slot, const irmv_render_opts *o, const irmv_det *dets, int n, uint8_t *dst)
+{
+    TRY(check_range(e, slot, 1));
+    if (!o || !dst) return fail(IRMV_ERR_ARG, "render: opts / dst is null");
+    if (o->struct_size != sizeof(irmv_render_opts)) return fail(IRMV_ERR_ARG, "render: opts.struct_size is not sizeof(irmv_render_opts)");
+    if (o->kind != IRMV_RENDER_COLOR && o->kind != IRMV_RENDER_BINARY) return fail(IRMV_ERR_ARG, "render: unknown kind");
+    TRY(check_render_scale(o->scale));
+    if (o->marks & ~(IRMV_MARK_BOXES | IRMV_MARK_LABELS | IRMV_MARK_ARMORS)) return fail(IRMV_ERR_ARG, "render: unknown mark bits");
+    if (o->reserved[0] || o->reserved[1] || o->reserved[2]) return fail(IRMV_ERR_ARG, "render: reserved fields must be 0");
+    if (o->binary_threshold < -1 || o->binary_threshold > 255) return fail(IRMV_ERR_ARG, "render: binary_threshold must be -1..255");
+    const bool last = !dets && n == -1;
+    if (!last && (n < 0 || n > e->cfg.max_det || (n > 0 && !dets))) return fail(IRMV_ERR_ARG, "render: n must be 0..max_det with dets set, or -1 with dets null");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));
+    TRY(ensure_render(e));
+    std::vector<irmv_det> own;
+    if (last) {
+        own.resize((size_t)e->cfg.max_det);
+        TRY(irmv_engine_results(e, slot, own.data(), e->cfg.max_det, &n));
+        dets = own.data();
+    }
+    hipStream_t st = e->stream;
+    const View &v = view_of(e, slot);
+    const int s = o->scale, ox = v.crop ? e->win_org[slot].x : 0, oy = v.crop ? e->win_org[slot].y : 0;
+    for (int i = 0; i < n; i++) {
+        const irmv_det &d = dets[i];
+        RenderMark &m = e->render_marks_host[(size_t)i];
+        memset(&m, 0, sizeof m);
+        m.cls = d.class_id >= 0 && d.class_id < IRMV_NUM_CLASSES ? d.class_id : IRMV_NUM_CLASSES;
+        if (render_coord(d.xyxy[0], ox, s, &m.x1) && render_coord(d.xyxy[1], oy, s, &m.y1) && render_coord(d.xyxy[2], ox, s, &m.x2) && render_coord(d.xyxy[3], oy, s, &m.y2))
+            m.flags |= (o->marks & IRMV_MARK_BOXES ? kRenderBox : 0) | (o->marks & IRMV_MARK_LABELS ? kRenderLabel : 0);
+        bool pts = d.armor_valid == 1 && (o->marks & IRMV_MARK_ARMORS);
+        for (int k = 0; k < 4 && pts; k++) pts = render_coord(d.kpts[2 * k], ox, s, &m.px[k]) && render_coord(d.kpts[2 * k + 1], oy, s, &m.py[k]);
+        if (pts) m.flags |= kRenderArmor;
+    }
+    TRY(load_frame(e, slot, st));
+    if (n > 0) HIP_TRY(hipMemcpyAsync(e->render_marks, e->render_marks_host.data(), (size_t)n * sizeof(RenderMark), hipMemcpyHostToDevice, st));
+    RenderArgs a{};
+    a.frame = v.frames + (size_t)slot * v.frame_bytes;
+    a.dst = e->render_out;
+    a.marks = e->render_marks;
+    a.font = e->render_font;
+    a.W = v.src_w; a.H = v.src_h; a.ow = v.src_w / s; a.oh = v.src_h / s;
+    a.rotate180 = e->cfg.rotate180 ? 1 : 0;
+    a.scale = s;
+    a.binary = o->kind == IRMV_RENDER_BINARY;
+    a.threshold = o->binary_threshold >= 0 ? o->binary_threshold : e->cfg.binary_threshold;
+    a.n = n;
+    if (a.ow > 0 && a.oh > 0) {
+        launch_render_view(a, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(dst, e->render_out, (size_t)a.ow * a.oh * 3, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return IRMV_OK;
+}
+
 static_assert(sizeof(irmv_light_rec) == sizeof(LightTraceRec) && sizeof(irmv_light_trace) == sizeof(LightTrace) &&
                   offsetof(irmv_light_trace, starts) == offsetof(LightTrace, starts) && offsetof(irmv_light_trace, points) == offsetof(LightTrace, points) &&
                   offsetof(irmv_light_trace, recs) == offsetof(LightTrace, recs) && offsetof(irmv_light_rec, length) == offsetof(LightTraceRec, length) &&

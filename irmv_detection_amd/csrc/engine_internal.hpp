@@ -9,7 +9,7 @@
 //                     result copies, graph capture, the one submit path of ordinary and tiled steps (submit_group), wait / results
 //   engine_tiles.cpp  tiled search: its checks, the merge's device state and arguments, the tiled submit's call of submit_group,
 //                     the merge hook, the merged results and the merge parameters
-//   engine_hooks.cpp  read-backs, debug_*, LDS fill / probe, conv and op test hooks, the profiler, the light trace
+//   engine_hooks.cpp  read-backs, debug images, debug_*, LDS fill / probe, conv and op test hooks, the profiler, the light trace
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -333,6 +333,12 @@ struct irmv_engine {
     float *light_boxes = nullptr;      // explicit boxes of irmv_engine_extract_armors
     DevDet *light_dets_dev = nullptr, *light_dets_host = nullptr;
     LightTrace *light_trace_dev = nullptr;   // [max_det], allocated by the first irmv_engine_light_trace
+    // Debug images (irmv_engine_render): nothing below exists until the first call.  render_out holds the largest picture any
+    // view of the engine gives (scale 1); render_marks_host is what the mark upload reads (it outlives the call).
+    RenderMark *render_marks = nullptr;      // [max_det]
+    RenderFont *render_font = nullptr;
+    uint8_t *render_out = nullptr;
+    std::vector<RenderMark> render_marks_host;
     float *boxes = nullptr;
     unsigned long long *keys = nullptr;
     DevDet *dets_dev = nullptr, *dets_host = nullptr, *dets_host_dev = nullptr;       // *_host_dev: device view of the pinned buffer

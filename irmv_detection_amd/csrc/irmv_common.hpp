@@ -530,6 +530,32 @@ struct LightArgs {
 };
 void launch_light_extract(const LightArgs &a, int n_boxes_max, int batch, hipStream_t s);
 
+// ---- debug images (k_render.hip; irmv_engine_render) -----------------------------------------------------------------
+// One mark record as the host hands it to the kernel: every coordinate already an integer in OUTPUT pixels (truncated, the
+// window's corner subtracted, floor-divided by the scale -- include/irmv_hip.h, "debug images").
+constexpr int kRenderBox = 1, kRenderLabel = 2, kRenderArmor = 4;   // RenderMark::flags: what the record draws
+struct RenderMark {
+    int32_t x1, y1, x2, y2;   // box
+    int32_t flags, cls;       // kRender* bits; name / colour index 0..14 (14 = UNKNOWN)
+    int32_t px[4], py[4];     // LB, LT, RT, RB
+    int32_t pad_[2];
+};
+// glyph rows and class names, built on the host from the table irmv_render_glyph exposes
+struct RenderFont {
+    uint8_t glyph[16][8];     // [glyph index][row]
+    uint8_t name[16][8];      // [class 0..14][k] -> glyph index
+    uint8_t len[16];
+};
+struct RenderArgs {
+    const uint8_t *frame;     // [H][W][3] device frame, un-rotated (rotation folded into the fetch)
+    uint8_t *dst;             // [oh][ow][3]
+    const RenderMark *marks;  // [n]
+    const RenderFont *font;
+    int W, H, ow, oh, rotate180, scale, binary, threshold, n;
+};
+constexpr int kRenderTileW = 64, kRenderTileH = 16;   // output pixels per workgroup (256 threads, 4 pixels of a row each)
+void launch_render_view(const RenderArgs &a, hipStream_t s);
+
 // ---- LDS fill / probe (k_debug.hip; test hooks irmv_debug_lds_fill / irmv_debug_lds_probe) ----------------------------
 constexpr int kDebugLdsWords = 160 * 1024 / 4;   // the largest LDS allocation of one workgroup on gfx950
 int debug_lds_workgroups(int cus);               // several per CU

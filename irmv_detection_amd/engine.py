@@ -107,6 +107,8 @@ class YoloEngine:
     `point_source=capi.POINTS_REFINED`: the keypoint head's points snapped to the light bars found at them, inside the step
     (`Armor.refined`); `set_refine` / `get_refine` change its two parameters live, `refine_points` runs it on explicit boxes
     and keypoints on any engine (irmv_detection_amd.refine is the host reference).
+    `render`: the node's debug images -- the frame or its thresholded gray with boxes, labels and armors drawn on it, at full,
+    half or quarter size -- made on the GPU from the slot's device frame (irmv_detection_amd.render is the host reference).
     """
 
     def __init__(self, onnx_file_path: Optional[str], src_image_size: Tuple[int, int] = (1280, 1024),
@@ -242,6 +244,52 @@ class YoloEngine:
         out = np.empty((h, w, 3), np.uint8)
         capi.check(self._L.irmv_engine_rotated_image(self._h, slot, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
+
+    def render_dims(self, scale: int = 1, slot: Optional[int] = None) -> Tuple[int, int]:
+        """(w, h) of the slot's debug picture at `scale` (irmv_engine_render_dims)."""
+        slot = self.slot if slot is None else slot
+        w, h = C.c_int(0), C.c_int(0)
+        capi.check(self._L.irmv_engine_render_dims(self._h, slot, int(scale), C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def render(self, kind: str = "color", scale: int = 1, marks: int = capi.MARK_ALL, dets=None, slot: Optional[int] = None,
+               binary_threshold: Optional[int] = None) -> np.ndarray:
+        """The node's debug image of the slot's current frame, rendered on the GPU (irmv_engine_render): "color" = the frame,
+        "binary" = gray > binary_threshold on three channels (None: the engine's current threshold), at 1/scale size (1, 2, 4),
+        with the marks capi.MARK_BOXES | MARK_LABELS | MARK_ARMORS of `dets` drawn on it -> uint8 [h, w, 3].  dets: None = the
+        slot's last results; else capi.Det records (results_raw), or bbox / Armor objects.  A Bayer engine renders its
+        demosaiced frame, a window slot its window (the whole frame in the frame view); only the picture crosses PCIe.
+        irmv_detection_amd.render is the host reference."""
+        if kind not in capi.RENDER_KINDS:
+            raise ValueError(f"kind must be one of {sorted(capi.RENDER_KINDS)}, not {kind!r}")
+        slot = self.slot if slot is None else slot
+        o = capi.render_opts(capi.RENDER_KINDS[kind], scale, marks, -1 if binary_threshold is None else binary_threshold)
+        w, h = self.render_dims(scale, slot)
+        recs, n = None, -1
+        if dets is not None:
+            n = len(dets)
+            recs = (capi.Det * max(n, 1))()
+            for i, d in enumerate(dets):
+                recs[i] = self._to_det(d)
+        out = np.empty((h, w, 3), np.uint8)
+        capi.check(self._L.irmv_engine_render(self._h, slot, C.byref(o), recs, n, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    @staticmethod
+    def _to_det(d) -> "capi.Det":
+        """A record irmv_engine_render reads: a capi.Det as it is, a bbox (no armor), or an Armor (box, class and points)."""
+        if isinstance(d, capi.Det):
+            return d
+        r = capi.Det()
+        if isinstance(d, bbox):
+            r.xyxy, r.class_id, r.score = (C.c_float * 4)(*d.xyxy), int(d.class_id), d.score
+        elif isinstance(d, Armor):
+            r.xyxy, r.class_id, r.score = (C.c_float * 4)(*d.bbox_xyxy), int(d.armor_class), d.confidence
+            r.kpts = (C.c_float * 8)(*d.image_points().reshape(8))
+            r.armor_valid = 1 if d.valid else (-1 if d.no_answer else 0)
+        else:
+            raise TypeError("dets holds capi.Det, bbox or Armor objects")
+        return r
 
     def set_window(self, x0: int, y0: int, slot: Optional[int] = None) -> None:
         """Move the slot's window: (x0, y0) is its top-left corner in the coordinates detections come back in (the rotated

@@ -6,6 +6,7 @@
 #include <auto_aim_interfaces/msg/armors.hpp>
 #include <rclcpp/rclcpp.hpp>
 #include <rclcpp_components/register_node_macro.hpp>
+#include <sensor_msgs/msg/image.hpp>
 
 #include "irmv_detection/irm_detector_core.hpp"
 
@@ -35,6 +36,8 @@ public:
     p.point_source = int(node_->declare_parameter("point_source", 0));   // IRMV_POINTS_*: 0 auto, 3 refined (a pose model's points snapped to the light bars)
     p.refine_snap = node_->declare_parameter("refine.snap", 0.5);         // live through the callback below, like refine.roi_margin
     p.refine_roi_margin = node_->declare_parameter("refine.roi_margin", 4.0);
+    p.debug = node_->declare_parameter("debug", false);                   // reference :90-95; live through the callback below (:380-381)
+    p.debug_scale = int(node_->declare_parameter("debug_scale", 1));      // 1, 2 or 4: the debug images at full, half or quarter size
     const auto ns = node_->declare_parameter("net_input_size", std::vector<int64_t>{0, 0});   // {width, height}; {0, 0}: square default
     if (ns.size() == 2) p.net_input_size = cv::Size(int(ns[0]), int(ns[1]));
     const std::string model = node_->declare_parameter("model_path", std::string("models/yolov7.onnx"));
@@ -44,12 +47,17 @@ public:
     for (size_t i = 0; i < 9 && i < k.size(); i++) K[i] = k[i];
     core_ = std::make_unique<IrmDetectorCore>(model, K, d, p);
     armors_pub_ = node_->create_publisher<auto_aim_interfaces::msg::Armors>("/detector/armors", rclcpp::SensorDataQoS());
+    // the reference's two debug topics (:90-95), as plain rgb8 sensor_msgs/Image: the pictures come finished from the GPU
+    // (IrmDetectorCore::FrameResult), so neither cv_bridge nor image_transport is needed.  Created always: `debug` is live.
+    visualized_img_pub_ = node_->create_publisher<sensor_msgs::msg::Image>("/image/visualized_image", rclcpp::SensorDataQoS());
+    binary_img_pub_ = node_->create_publisher<sensor_msgs::msg::Image>("/image/binary_image", rclcpp::SensorDataQoS());
     param_handle_ = node_->add_on_set_parameters_callback([this](const std::vector<rclcpp::Parameter> & ps) {
       rcl_interfaces::msg::SetParametersResult r;
       r.successful = true;
       r.reason = "success";
       for (const auto & q : ps)
-        if (q.get_type() == rclcpp::ParameterType::PARAMETER_INTEGER) core_->set_parameter(q.get_name(), double(q.as_int()));
+        if (q.get_type() == rclcpp::ParameterType::PARAMETER_BOOL) core_->set_bool_parameter(q.get_name(), q.as_bool());
+        else if (q.get_type() == rclcpp::ParameterType::PARAMETER_INTEGER) core_->set_parameter(q.get_name(), double(q.as_int()));
         else if (q.get_type() == rclcpp::ParameterType::PARAMETER_DOUBLE) core_->set_parameter(q.get_name(), q.as_double());
       return r;
     });
@@ -74,9 +82,27 @@ public:
       msg.armors.emplace_back(m);
     }
     armors_pub_->publish(msg);
+    if (!r.visualized_image.empty()) {   // debug is on (:259-280)
+      visualized_img_pub_->publish(image_msg(r.visualized_image, msg.header));
+      binary_img_pub_->publish(image_msg(r.binary_image, msg.header));
+    }
   }
 
 private:
+  static sensor_msgs::msg::Image image_msg(const cv::Mat & m, const std_msgs::msg::Header & header)
+  {
+    sensor_msgs::msg::Image img;
+    img.header = header;
+    img.height = uint32_t(m.rows);
+    img.width = uint32_t(m.cols);
+    img.encoding = "rgb8";   // as the reference publishes them (:271, :279)
+    img.is_bigendian = 0;
+    img.step = uint32_t(m.cols) * 3;
+    img.data.assign(m.data, m.data + size_t(m.rows) * m.cols * 3);
+    return img;
+  }
+
+  rclcpp::Publisher<sensor_msgs::msg::Image>::SharedPtr visualized_img_pub_, binary_img_pub_;
   rclcpp::Node::SharedPtr node_;
   std::unique_ptr<IrmDetectorCore> core_;
   rclcpp::Publisher<auto_aim_interfaces::msg::Armors>::SharedPtr armors_pub_;
