@@ -671,6 +671,15 @@ int irmv_engine_light_trace(irmv_engine *e, int slot, const float *xyxy, int n, 
 int irmv_engine_refine_points(irmv_engine *e, int slot, const float *xyxy, const float *kpts, int n, irmv_light_trace *trace, irmv_det *out);
 /* Host only: out = {max_contours, points_cap, lds_image, lds_points} without an engine. */
 int irmv_light_limits(int32_t out[4]);
+/* Host only: the candidate counts at which the post stage (decode + NMS, k_post.hip) changes its code path, and the tile
+ * merge's capacities, as the library is compiled.  out = {rank_use (rank sort / class-walk / full suppression matrix up to
+ * here, bitonic sort above), rank_max (the prefilter's compaction buffer), lazy_n (lazy suppression matrix up to here),
+ * sup_cap (precomputed block masks), cand_cap (LDS sort up to here, exact radix select above), pre_hi, pre_lo (the
+ * prefilter's window: it runs above pre_hi candidates), max_tiles, max_det_cap (tile merge: tiles, records per tile),
+ * scan_blocks, scan_step, scan_lds_max (scan_decode_kernel: workgroups per frame, quads per round, LDS bytes that bound
+ * a workgroup's range), inscan_chunk (quads per round of the scan inside nms_pnp_kernel), mat_n (rows of the full
+ * suppression matrix), 0, 0}.  The count ladders of tests/post_ladder.py are computed from it. */
+int irmv_post_limits(int32_t out[16]);
 
 /* ---- the front's plan (tests/test_input_geometry.py) -----------------------------------------------------------------
  * Host only: every geometry decision between a source frame and model.1's output that irmv_engine_create derives from the

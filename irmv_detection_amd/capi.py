@@ -230,6 +230,7 @@ SYMBOLS = [
     ("irmv_class_policy_table", C.c_int, [C.POINTER(ClassPolicy), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("irmv_engine_light_trace", C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(LightTrace), C.POINTER(Det)]),
     ("irmv_light_limits", C.c_int, [C.POINTER(C.c_int32)]),
+    ("irmv_post_limits", C.c_int, [C.POINTER(C.c_int32)]),
     ("irmv_engine_read_input", C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
     ("irmv_engine_read_head", C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
     ("irmv_engine_write_head", C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
@@ -328,6 +329,18 @@ def light_limits() -> dict:
     v = (C.c_int32 * 4)()
     check(load().irmv_light_limits(v))
     return dict(max_contours=v[0], points_cap=v[1], lds_image=v[2], lds_points=v[3])
+
+
+POST_LIMIT_NAMES = ("rank_use", "rank_max", "lazy_n", "sup_cap", "cand_cap", "pre_hi", "pre_lo", "max_tiles", "max_det_cap",
+                    "scan_blocks", "scan_step", "scan_lds_max", "inscan_chunk", "mat_n")
+
+
+def post_limits() -> dict:
+    """The candidate counts at which decode + NMS (k_post.hip) changes its code path and the tile merge's capacities, as the
+    kernels are compiled (host only; irmv_post_limits in include/irmv_hip.h names each)."""
+    v = (C.c_int32 * 16)()
+    check(load().irmv_post_limits(v))
+    return {k: int(v[i]) for i, k in enumerate(POST_LIMIT_NAMES)}
 
 
 def render_opts(kind=RENDER_COLOR, scale=1, marks=MARK_ALL, binary_threshold=-1) -> RenderOpts:

@@ -299,6 +299,13 @@ extern "C" int irmv_light_limits(int32_t out[4])
     return IRMV_OK;
 }
 
+extern "C" int irmv_post_limits(int32_t out[16])
+{
+    if (!out) return fail(IRMV_ERR_ARG, "out is null");
+    post_limits(out);
+    return IRMV_OK;
+}
+
 static int debug_lds_geometry(int *workgroups)
 {
     int dev = 0, cus = 0;

@@ -455,6 +455,7 @@ void launch_nms_pnp(const PostArgs &a, int batch, hipStream_t s);
 constexpr int kScanBlocks = 16;   // workgroups per frame of scan_decode_kernel (more where a 16th of the keys would not fit kScanLdsMax)
 constexpr size_t kScanLdsMax = 159 * 1024;   // its dynamic LDS: 160 KiB per workgroup on gfx950, less its static variables
 void launch_scan_decode(const PostArgs &a, int batch, hipStream_t s);
+void post_limits(int32_t out[16]);   // the candidate counts k_post.hip branches on and the merge kernel's capacities (irmv_post_limits)
 // tiled search (k_tiles.hip): the result lists of slots [first, first + count) -- windows of ONE frame -- merged into one
 constexpr int kMaxTiles = 16;     // == IRMV_MAX_TILES
 struct TileMergeParams { float ios_thr, edge_margin; };   // device memory, read when the kernel runs (irmv_engine_set_tile_merge)

@@ -365,6 +365,7 @@ constexpr int kLazyN_ = 1024;   // most candidates of the lazy-matrix walk
 constexpr int kPreHi = 512, kPreLo = 320;
 constexpr int kMatW_ = 8;       // 64-bit words of a suppression-matrix row (512 candidates)
 constexpr int kKptLds = 6144;   // class-walk path: the candidates' keypoint logits live in skeys[kKptLds ..) (16 KiB)
+constexpr int kInScanU = 8;     // the in-kernel scan (no scan_decode_kernel in front): rounds of 1024 quads whose loads are issued together
 
 __device__ __forceinline__ void wave_lds_sync()
 {
@@ -445,7 +446,7 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
     // ---- 0. decode.  Scan: class logits of every anchor -> candidate keys + the list of anchors that have one.  Level
     // by level (records of a level are contiguous), four lanes per anchor; the loads of U rounds are issued together.
     {
-        constexpr int U = 8;
+        constexpr int U = kInScanU;
         int lbase = 0;
         const float min_thr = a.cls->min_thr;   // class policy: the smallest per-class threshold (uniform: one scalar load)
 #pragma unroll 1
@@ -1343,6 +1344,15 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
 void launch_nms_pnp(const PostArgs &a, int batch, hipStream_t s)
 {
     hipLaunchKernelGGL(nms_pnp_kernel, dim3(batch), dim3(1024), 0, s, a);
+}
+
+// The candidate counts the kernels above branch on, as compiled (irmv_post_limits: tests/post_ladder.py builds its count
+// ladders from them, so a threshold that moves takes its tests along).
+void post_limits(int32_t out[16])
+{
+    const int32_t v[16] = {kRankSortUse, kRankSortMax, kLazyN_, kSupCap, kCandCap, kPreHi, kPreLo, kMaxTiles, kMaxDetCap,
+                           kScanBlocks, 256 * kScanU, (int32_t)kScanLdsMax, 1024 * kInScanU, kMatW_ * 64, 0, 0};
+    for (int i = 0; i < 16; i++) out[i] = v[i];
 }
 
 }  // namespace irmv

@@ -214,11 +214,15 @@ def test_head_error_over_unchosen_frames(blob, onet, rm_test_image, capsys):
 
 # ---------------------------------------------------------------- decode / NMS / keypoints
 def _assert_post_exact(eng, head, slot=0, **kw):
+    """net: the engine's (square) net size; exp: the oracle's answer where the caller already holds it (one reference shared
+    by several engines)."""
     eng.write_head(head, slot)
     eng.run_post(slot, 1)
     raw = eng.read_raw(slot)
-    exp = oracle.decode_nms(head, 640, 14, 8, kw.get("score_thr", 0.25), kw.get("iou_thr", 0.45),
-                            kw.get("max_det", 100), kw.get("pre_nms_cap", 4096))
+    exp = kw.get("exp")
+    if exp is None:
+        exp = oracle.decode_nms(head, kw.get("net", 640), 14, 8, kw.get("score_thr", 0.25), kw.get("iou_thr", 0.45),
+                                kw.get("max_det", 100), kw.get("pre_nms_cap", 4096))
     assert raw["n_candidates"] == exp["n_candidates"]
     assert raw["num_dets"] == exp["num_dets"]
     assert np.array_equal(raw["anchors"], exp["anchors"]) and np.array_equal(raw["classes"], exp["classes"])

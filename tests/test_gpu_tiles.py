@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import detect_craft as dc
+import tile_ladder as tl
 from irmv_detection_amd import bayer, capi, tiles
 from test_gpu_window import FULL, WIN, _hip_memcpy_h2d, frame_of, peng, reference, same_results, same_tensors, snapshot, weng
 
@@ -221,6 +222,83 @@ def test_merge_at_capacity(blob):
         assert n_in == 4096 and len(recs) == 256
         trace = check_merge(w, 0, corners, FULL2, WIN2)
         assert cross_tile_suppressions(trace) > 0 and sum(t["rule"] == "cap" for t in trace) > 0
+
+
+# ---- 3a. the merge ladder (tests/tile_ladder.py) ---------------------------------------------------------------------------------
+# Which part of tile_merge_kernel each case reaches, and why, is stated in tests/tile_ladder.py; tests/test_tile_ladder.py
+# asserts the same reach conditions on the host alone.  Wall time per test on the MI355X (two runs; most of it is the host
+# reference's walk): suppressors 0.65 - 0.76 s per max_det, ties on the boundary 0.06 - 0.16 s, input counts 0.23 s (one tile),
+# 0.32 - 0.40 s (two), 0.34 - 0.45 s for each of the four sixteen-tile tests.  (Tried once on a build whose walk ignored
+# register 3 of the kept list: the three suppressor tests fail, test_merge_at_capacity passes.)
+
+
+def ladder_merge(w, tile_recs, corners, ios_thr=0.5, edge_margin=0.0):
+    """Crafted tiles through decode + NMS + merge; -> (lists, kept, trace) of the reference on the GPU's own tile lists, after
+    check_merge has compared the kernel's list with it."""
+    run_crafted(w, [crafted_head(w, WIN2, r) for r in tile_recs])
+    lists, _ = slot_lists(w, 0, len(corners))
+    assert [len(L["scores"]) for L in lists] == [min(len(r), w.max_det) for r in tile_recs]   # every crafted record came out of its tile's NMS, up to its max_det
+    kept, trace = tiles.merge(lists, corners, WIN2, FULL2, ios_thr, edge_margin, w.max_det)
+    return lists, kept, trace
+
+
+@pytest.mark.parametrize("max_det", [256, 255, 250])
+def test_merge_suppressors_in_every_register_and_lane(blob, max_det):
+    """240 records of tile 0 kept first, each the twin of one of tile 1's: the suppressors sit at kept positions 0 .. 239, in
+    all four registers of the walk and every lane (asserted from the reference's trace, then the kernel is compared); then
+    the same tiles with the scores swapped: tile 1 alone fills the list."""
+    with weng(blob, full=FULL2, win=WIN2, net=WIN2, num_slots=2, max_det=max_det) as w:
+        w.set_tiles(tl.SUP_CORNERS)
+        w.set_tile_merge(0.5, 0.0)
+        lists, kept, trace = ladder_merge(w, tl.suppressor_tiles(), tl.SUP_CORNERS)
+        blocks, residues = tl.suppressor_reach(kept, trace)
+        assert len(kept) == max_det and blocks == [0, 1, 2, 3] and residues == list(range(64))
+        assert sum(t["cut"] for t in trace) == 0
+        assert check_merge(w, 0, tl.SUP_CORNERS, FULL2, WIN2, 0.5, 0.0) == trace
+        lists, kept, trace = ladder_merge(w, tl.suppressor_tiles(swap=True), tl.SUP_CORNERS)
+        assert len(kept) == max_det and all(k[0] == 1 for k in kept)
+        check_merge(w, 0, tl.SUP_CORNERS, FULL2, WIN2, 0.5, 0.0)
+
+
+def test_merge_tied_scores_on_the_register_boundary(blob):
+    """Equal scores inside a tile and across the two, on kept positions 62 .. 65: the order is (tile, index), the 64th kept
+    record (last lane of register 0) and the 65th (first lane of register 1) each suppress a twin."""
+    with weng(blob, full=FULL2, win=WIN2, net=WIN2, num_slots=2, max_det=256) as w:
+        w.set_tiles(tl.SUP_CORNERS)
+        w.set_tile_merge(0.5, 0.0)
+        lists, kept, trace = ladder_merge(w, tl.tied_boundary_tiles(), tl.SUP_CORNERS)
+        score = lambda k: lists[k[0]]["scores"][k[1]]
+        assert len(kept) == 66 and [k[0] for k in kept[62:66]] == [0, 0, 1, 1]
+        assert score(kept[61]) > score(kept[62]) == score(kept[63]) == score(kept[64]) == score(kept[65])
+        pos = {(t, i): j for j, (t, i, _) in enumerate(kept)}
+        assert sorted(pos[tuple(t["by"])] for t in trace if t["rule"] == "suppressed") == [63, 64]
+        check_merge(w, 0, tl.SUP_CORNERS, FULL2, WIN2, 0.5, 0.0)
+
+
+@pytest.mark.parametrize("count,lo,hi", [(1, 0, 256), (2, 0, 512), (16, 0, 257), (16, 1023, 1025), (16, 2047, 2049), (16, 4095, 4096)])
+def test_merge_input_counts(blob, count, lo, hi):
+    """n_in = 0 .. 5 and one rung either side of every size of the sort (P = 64 .. 4096), the records spread over 1, 2 and 16
+    tiles with empty tiles first, in the middle and last; ios_thr 1.0: nobody suppresses anybody, min(n_in, max_det) are kept.
+    (Sixteen tiles in four tests: none walks more than three large lists through the host reference.)"""
+    corners, nx, ny = capi.tile_grid(FULL2, WIN2, (64, 18), net_size=WIN2[0], net_height=WIN2[1])
+    assert (nx, ny) == (4, 4)
+    corners = corners[:count]
+    ladder = [n for n in tl.input_counts(count) if lo <= n <= hi]
+    assert len(ladder) >= 2
+    with weng(blob, full=FULL2, win=WIN2, net=WIN2, num_slots=count, max_det=256) as w:
+        w.set_tiles(corners)
+        w.set_tile_merge(1.0, 0.0)
+        seen_empty = set()
+        for n_in in ladder:
+            per = tl.spread(n_in, count)
+            seen_empty |= {t for t in range(count) if per[t] == 0 and n_in > 0}
+            run_crafted(w, [crafted_head(w, WIN2, tl.isolated(k, 100 * count + t)) for t, k in enumerate(per)])
+            recs, got_in = w.tile_results_raw(0)
+            assert got_in == n_in and len(recs) == min(n_in, 256), (count, n_in)
+            trace = check_merge(w, 0, corners, FULL2, WIN2, 1.0, 0.0)
+            assert len(trace) == n_in and cross_tile_suppressions(trace) == 0
+        want = {0, 8, 15} if count == 16 and lo <= 13 * 256 else ({0, 1} if count == 2 else set())
+        assert want <= seen_empty, (count, lo, seen_empty)      # (small n_in leave further tiles empty)
 
 
 # ---- 4. launch forms -------------------------------------------------------------------------------------------------------------
