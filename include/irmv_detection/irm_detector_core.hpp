@@ -95,6 +95,11 @@ public:
     std::vector<int> large_plate_classes;                // ArmorClass values whose detections PnP solves with the 225 mm plate; the rest: 135 mm
     int point_source = IRMV_POINTS_AUTO;                 // IRMV_POINTS_*; IRMV_POINTS_REFINED: a pose model's points snapped to the light bars, inside the step
     double refine_snap = 0.5, refine_roi_margin = 4.0;   // its two live parameters (irmv_engine_set_refine; set_parameter "refine.snap" / "refine.roi_margin")
+    // Pose ambiguity (include/irmv_hip.h): struct_size != 0 enables it on the three engines at creation -- FrameResult::alts is
+    // then filled, and mode IRMV_POSE_PRIOR lets the tilt prior choose.  Live: set_parameter "pose_prior" (the mode; enables),
+    // "pose_prior.ratio", "pose_prior.normal_up" (every class), and "up.x" / "up.y" / "up.z" or set_up() for the gimbal's up vector.
+    irmv_pose_prior pose_prior{};
+    std::array<double, 3> up{0.0, -1.0, 0.0};
     bool debug = false;                                  // the node's debug (:90-95, :259-280): every frame also yields FrameResult::visualized_image / binary_image,
                                                          // rendered on the GPU (YoloEngine::render); live through set_bool_parameter("debug", v) like the reference (:380-381)
     int debug_scale = 1;                                 // 1, 2 or 4: the debug images at full, half or quarter size (set_parameter "debug_scale")
@@ -107,6 +112,10 @@ public:
     std::vector<YoloEngine::bbox> bboxes;
     std::vector<Armor> armors;          // one per message entry, same order
     std::vector<irmv_det> poses;        // rvec / tvec / quaternion of each, as computed on the GPU
+    // Pose ambiguity enabled and a pose-style model: per entry of `poses` the IPPE solution it does NOT report, with
+    // err / err_alt, the rms normalised residuals of the reported pose and of this one (else empty).  A tracker keeps both
+    // while err_alt / err is small and lets its motion model decide; a large ratio means the reported pose stands alone.
+    std::vector<irmv_pose_alt> alts;
     double inference_latency_ms = 0;    // YoloEngine::get_profiling_time() (:251)
     // Params::debug only (else empty): the frame with this frame's armors, boxes and labels drawn on it (:261-263; the latency
     // text lines are not drawn), and gray -> threshold(binary_threshold) -> three channels with the boxes and labels (:273-277)
@@ -124,6 +133,7 @@ public:
       push_params(*e);
       if (p.refine_snap != 0.5 || p.refine_roi_margin != 4.0) e->set_refine(float(p.refine_snap), float(p.refine_roi_margin));
       if (p.enemy_color != -1 || !p.large_plate_classes.empty()) push_class_policy(*e);
+      if (p.pose_prior.struct_size != 0) { e->set_pose_prior(&p.pose_prior); e->set_up(p.up); }
     }
     yolo_engines_[0]->warm_up();   // the tile choices are shared by the three engines: one warm-up tunes for all
     for (size_t i = 1; i < yolo_engines_.size(); i++) yolo_engines_[i]->warm_up();
@@ -149,13 +159,16 @@ public:
 
     std::vector<Armor> armors;
     std::vector<irmv_det> poses;
+    std::vector<irmv_pose_alt> alts;
     if (eng.has_keypoint_head()) {
       // pose-style model: each detection carries its four points and, already, its pose
       int n = 0;
       const irmv_det * dets = eng.last_detections(&n);
+      const std::vector<irmv_pose_alt> all = eng.pose_alts();   // parallel to dets (empty: not enabled)
       for (int i = 0; i < n; i++) {
         const irmv_det & d = dets[i];
         if (d.armor_valid != 1) continue;
+        if (size_t(i) < all.size()) alts.push_back(all[size_t(i)]);
         Armor a(Light(cv::Point2f(d.kpts[2], d.kpts[3]), cv::Point2f(d.kpts[0], d.kpts[1])),
                 Light(cv::Point2f(d.kpts[4], d.kpts[5]), cv::Point2f(d.kpts[6], d.kpts[7])));
         a.armor_class = static_cast<ArmorClass>(d.class_id);
@@ -185,6 +198,7 @@ public:
       out.armors_msg.armors.push_back(m);
       out.armors.push_back(armors[i]);
       out.poses.push_back(d);
+      if (alts.size() == armors.size()) out.alts.push_back(alts[i]);
     }
     out.inference_latency_ms = eng.get_profiling_time();
     if (params_.debug) {
@@ -245,8 +259,41 @@ public:
       for (auto & e : yolo_engines_) e->set_refine(float(snap), float(margin));
       return true;
     }
+    else if (name == "pose_prior" || name == "pose_prior.ratio" || name == "pose_prior.normal_up") {
+      // live; the first one enables the alt records (one re-capture per engine), later ones re-capture nothing
+      irmv_pose_prior p = params_.pose_prior.struct_size ? params_.pose_prior : yolo_engines_[0]->pose_prior();
+      if (name == "pose_prior") {
+        if (value != double(IRMV_POSE_MIN_ERR) && value != double(IRMV_POSE_PRIOR)) return false;
+        p.mode = int(value);
+      } else if (name == "pose_prior.ratio") {
+        if (!(value >= 1.0)) return false;
+        p.ambiguity_ratio = value;
+      } else {
+        if (!(std::fabs(value) <= 1.0)) return false;
+        for (double & s : p.normal_up) s = value;
+        p.normal_up_default = value;
+      }
+      params_.pose_prior = p;
+      for (auto & e : yolo_engines_) e->set_pose_prior(&p);
+      return true;
+    }
+    else if (name == "up.x" || name == "up.y" || name == "up.z") {   // one component; set_up() takes the whole vector
+      std::array<double, 3> u = params_.up;
+      u[size_t(name[3] - 'x')] = value;
+      return set_up(u);
+    }
     else return false;
     for (auto & e : yolo_engines_) push_params(*e);
+    return true;
+  }
+
+  // The gimbal's up vector in the camera frame (any length), for the frames to come: false for a zero or non-finite vector
+  bool set_up(const std::array<double, 3> & up)
+  {
+    const double n2 = (up[0] * up[0] + up[1] * up[1]) + up[2] * up[2];
+    if (!(n2 > 0.0 && std::isfinite(n2))) return false;
+    params_.up = up;
+    for (auto & e : yolo_engines_) e->set_up(up);
     return true;
   }
 

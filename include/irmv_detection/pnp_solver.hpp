@@ -57,6 +57,29 @@ public:
     return ok != 0;
   }
 
+  // cv::solvePnPGeneric(..., SOLVEPNP_IPPE): both solutions, solvePnP's answer first (bit for bit), then the mirror pose it
+  // throws away, with their rms normalised residuals (irmv_pnp_solve2).  Returns the number of usable solutions: 0, 1 or 2.
+  int solvePnPGeneric(const Armor & armor, std::vector<cv::Mat> & rvecs, std::vector<cv::Mat> & tvecs, std::vector<double> & errs) const
+  {
+    const float pts[8] = {armor.left_light.bottom.x, armor.left_light.bottom.y, armor.left_light.top.x, armor.left_light.top.y,
+                          armor.right_light.top.x, armor.right_light.top.y, armor.right_light.bottom.x, armor.right_light.bottom.y};
+    double r[6], t[6], e[2];
+    int32_t ok = 0;
+    if (irmv_pnp_solve2(pnp_, pts, 1, IRMV_ARMOR_SMALL, r, t, e, &ok) != IRMV_OK)
+      throw std::runtime_error(std::string("PnPSolver::solvePnPGeneric: ") + irmv_last_error());
+    rvecs.clear(); tvecs.clear(); errs.clear();
+    const int n = (ok & 1) ? ((ok & 2) ? 2 : 1) : 0;
+    for (int s = 0; s < n; s++) {
+      cv::Mat rv(3, 1, CV_64F), tv(3, 1, CV_64F);
+      for (int i = 0; i < 3; i++) {
+        rv.at<double>(i) = r[3 * s + i];
+        tv.at<double>(i) = t[3 * s + i];
+      }
+      rvecs.push_back(rv); tvecs.push_back(tv); errs.push_back(e[s]);
+    }
+    return n;
+  }
+
   // |p - (cx, cy)| with the true principal point.  (The reference reads K with
   // at<float>() from a CV_64F matrix, src/pnp_solver.cpp:56-57, and therefore uses
   // (0.0, 7.6e12) with the shipped YAML -- SURVEY.md Appendix E.1.)

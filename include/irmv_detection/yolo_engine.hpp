@@ -204,6 +204,58 @@ public:
     return p;
   }
 
+  // ---- pose ambiguity: both IPPE solutions per armor, and a gravity prior (include/irmv_hip.h, "pose ambiguity") ----
+  // From the first set_pose_prior on every detect() also delivers the solution its records do not report (pose_alts()); mode
+  // IRMV_POSE_PRIOR lets the per-class tilt prior choose between the two.  nullptr: IRMV_POSE_MIN_ERR with the defaults.  The
+  // first call re-captures the steps once; later calls and set_up re-capture nothing.  A refused value throws, nothing changes.
+  void set_pose_prior(const irmv_pose_prior * p)
+  {
+    if (irmv_engine_set_pose_prior(engine_, p) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::set_pose_prior: ") + irmv_last_error());
+    pose_alts_on_ = true;
+  }
+  void set_pose_prior(int mode, double ambiguity_ratio = 8.0, double normal_up = -0.25881904510252074)
+  {
+    irmv_pose_prior p{};
+    p.struct_size = sizeof p; p.mode = mode; p.ambiguity_ratio = ambiguity_ratio;
+    for (double & s : p.normal_up) s = normal_up;
+    p.normal_up_default = normal_up;
+    set_pose_prior(&p);
+  }
+  irmv_pose_prior pose_prior() const
+  {
+    irmv_pose_prior p;
+    if (irmv_engine_get_pose_prior(engine_, &p) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::pose_prior: ") + irmv_last_error());
+    return p;
+  }
+  bool delivers_pose_alts() const { return pose_alts_on_; }
+  // The gimbal's up vector in the camera frame PnP sees (any length; default (0, -1, 0)): per frame, before detect()
+  void set_up(const std::array<double, 3> & up)
+  {
+    if (irmv_engine_set_up(engine_, 0, up.data()) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::set_up: ") + irmv_last_error());
+  }
+  std::array<double, 3> up() const
+  {
+    std::array<double, 3> u{};
+    if (irmv_engine_get_up(engine_, 0, u.data()) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::up: ") + irmv_last_error());
+    return u;
+  }
+  // Parallel to last_detections(): entry i is the other solution of record i (empty before the first set_pose_prior)
+  std::vector<irmv_pose_alt> pose_alts() const
+  {
+    std::vector<irmv_pose_alt> a;
+    if (!pose_alts_on_) return a;
+    a.resize(dets_.size());
+    int n = 0;
+    if (irmv_engine_pose_alts(engine_, 0, a.data(), static_cast<int>(a.size()), &n) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::pose_alts: ") + irmv_last_error());
+    a.resize(static_cast<size_t>(n));
+    return a;
+  }
+
   // ---- tracking window ----
   bool has_window() const { return window_size_.width > 0 && window_size_.height > 0; }
   // The window's top-left corner in the coordinates bboxes come back in (the rotated frame); from the next detect() on.
@@ -459,6 +511,7 @@ private:
   irmv_class_policy base_policy_{};   // the uniform policy the engine was created with
   irmv_class_policy user_policy_{};   // the caller's thresholds and plates, without the colour mask
   int enemy_color_ = -1;
+  bool pose_alts_on_ = false;         // set_pose_prior has been called: the engine delivers alt records
   cv::Size src_image_size_;
   cv::Size window_size_;
   bool enable_profiling_ = false;

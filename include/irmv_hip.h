@@ -536,6 +536,67 @@ int irmv_engine_point_source(const irmv_engine *e);
 int irmv_engine_set_refine(irmv_engine *e, float snap, float roi_margin);
 int irmv_engine_get_refine(const irmv_engine *e, float *snap, float *roi_margin);
 
+/* ---- pose ambiguity: both IPPE solutions per armor, and a gravity prior ------------------------------------------------
+ * IPPE has two solutions per plate, mirror images about the line of sight.  A is the one cv::solvePnP(SOLVEPNP_IPPE) reports
+ * -- solution 0 unless !(err0 <= err1) --, B the other.  For a 135 x 55 mm plate a few metres away the two residuals differ
+ * by less than the keypoint noise, and the reported yaw flips between the mirror poses from frame to frame.  From the first
+ * irmv_engine_set_pose_prior on, a step delivers BOTH (irmv_engine_pose_alts, as cv::solvePnPGeneric does) and, in mode
+ * IRMV_POSE_PRIOR, chooses between them by what the scene knows and IPPE does not use: a plate is mounted at a known tilt
+ * against gravity, and the gimbal knows where "up" is.
+ * The rule, fp64 in the written order (no fused multiply-add), per detection of class c in slot k:
+ *   n_X    = column 0 of R_X (R_X[0], R_X[3], R_X[6] row-major): the model x axis in camera coordinates, the plate normal
+ *            pointing AWAY from the camera
+ *   u      = the slot's unit up vector (irmv_engine_set_up), s = normal_up[c]: the class's expected n . u
+ *   cost_X = fabs(((R_X[0]*u.x + R_X[3]*u.y) + R_X[6]*u.z) - s)
+ *   report B  iff  mode == IRMV_POSE_PRIOR  &&  errB <= ambiguity_ratio * errA  &&  costB < costA
+ * Any NaN makes a comparison false: A stays.  rvec and quat of either pose are converted as always; pnp_ok keeps its meaning
+ * (a failed translation of either solution fails the call, then the reported pose's finiteness).  A robot plate whose outward
+ * normal points 15 degrees upward has s = -sin 15 deg = -0.25881904510252074 (the outpost's: +); the library takes s, not
+ * an angle, so neither side does trigonometry.  irmv_detection_amd/pose_prior.py is the bit-exact host reference.
+ * An engine on which irmv_engine_set_pose_prior is never called allocates nothing for this, launches the kernels it always
+ * launched and returns the bits it always returned.  The first call allocates the side records, the prior table and the up
+ * table and drops the captured graphs once (as the first irmv_engine_set_bayer_isp does); later calls and every
+ * irmv_engine_set_up rewrite device memory the kernels read when they run and re-capture nothing.  In mode IRMV_POSE_MIN_ERR
+ * an enabled engine's irmv_det records stay byte-identical to a never-enabled engine's.
+ * Window engines: the crop only moves the principal point, so u is the same in the window and the frame view and for any
+ * corner.  rotate180: u is in the frame PnP sees, the rotated one.  Explicit boxes (irmv_engine_extract_armors,
+ * irmv_engine_refine_points) have no class: the rule runs with normal_up_default and no alt record is exposed -- the rule the
+ * plate follows there.  Classical and refined engines: the record is the alt of the quad whose pose irmv_det finally reports.
+ * Tiled steps: the alt of merged record r is irmv_engine_pose_alts(first + r.tile)[r.index].
+ * The default ambiguity_ratio = 8 rests on a CPU experiment alone (the project's fp64 reference on synthetic corner noise: at
+ * 0.3 px the min-error rule reports the mirror pose in 25 - 27 % of the poses of a plate leaning back 15 degrees, this rule in
+ * 7 - 12 %; ratios 2, 8 and +inf within that range).  No trained keypoint head exists here, which is why every parameter is live. */
+#define IRMV_POSE_MIN_ERR 0   /* cv::solvePnP's choice (default) */
+#define IRMV_POSE_PRIOR   1
+typedef struct irmv_pose_prior {
+    uint32_t struct_size;        /* = sizeof(irmv_pose_prior) */
+    int32_t  mode;               /* IRMV_POSE_* */
+    double   ambiguity_ratio;    /* >= 1, +inf allowed (the cost alone decides); default 8 */
+    double   normal_up[16];      /* per class, in [-1, 1]; default -0.25881904510252074 (a robot's plate) */
+    double   normal_up_default;  /* detections without a class (explicit boxes) */
+} irmv_pose_prior;
+typedef struct irmv_pose_alt {
+    double  rvec[3], tvec[3], quat[4];   /* the solution irmv_det does NOT report */
+    double  err, err_alt;                /* the solver's rms normalised residual of irmv_det's pose / of this one */
+    int32_t state;                       /* 0: pnp_ok == 0, nothing here (all zero); 1: irmv_det holds A; 2: the prior reported B */
+    int32_t alt_ok;                      /* this pose's own finiteness check */
+} irmv_pose_alt;
+/* Waits for every step in flight on every stream of the engine, as irmv_engine_set_class_policy does.  p == NULL: mode
+ * IRMV_POSE_MIN_ERR with the defaults; the records are still delivered.  IRMV_ERR_ARG, before the GPU is touched and leaving
+ * everything as it was: a null engine, a wrong struct_size, an unknown mode, a ratio < 1 or NaN, |normal_up| > 1 or NaN
+ * (all 16 entries and the default). */
+int irmv_engine_set_pose_prior(irmv_engine *e, const irmv_pose_prior *p);
+int irmv_engine_get_pose_prior(const irmv_engine *e, irmv_pose_prior *out);   /* before the first set: the defaults */
+/* The slot's up vector, normalised on the host: v / sqrt((x*x + y*y) + z*z).  Default (0, -1, 0): a level camera (image y
+ * points down).  Waits for the slot's last step, as irmv_engine_set_window does; works before the first
+ * irmv_engine_set_pose_prior (the value is kept and uploaded then).  IRMV_ERR_ARG: a slot out of range, a zero, non-finite
+ * or NaN vector (also one whose squared length overflows). */
+int irmv_engine_set_up(irmv_engine *e, int slot, const double up[3]);
+int irmv_engine_get_up(const irmv_engine *e, int slot, double up[3]);   /* the unit vector in force */
+/* Parallel to irmv_engine_results: out[i] belongs to record i of the slot's last step; *n = min(num_dets, cap).  The records
+ * reach the host the way the slot's irmv_det records do.  IRMV_ERR_ARG before the first irmv_engine_set_pose_prior. */
+int irmv_engine_pose_alts(irmv_engine *e, int slot, irmv_pose_alt *out, int cap, int *n);
+
 /* ---- stage-wise read-backs used by the parity tests -------------------- */
 int irmv_engine_read_input(irmv_engine *e, int slot, float *chw);             /* [3][net_h][net_w], as the reference's input_buffer_ */
 int irmv_engine_read_head(irmv_engine *e, int slot, float *head);             /* [A][64+nc+nk], A = irmv_engine_num_anchors(): levels
@@ -745,6 +806,11 @@ void irmv_pnp_destroy(irmv_pnp *p);
 /* img_pts [n][8] (LB, LT, RT, RB; pixels) -> rvec [n][3], tvec [n][3], ok [n];
  * IPPE on the GPU, one lane per armor (cv::solvePnP(..., SOLVEPNP_IPPE), src/pnp_solver.cpp:49-51). */
 int irmv_pnp_solve(irmv_pnp *p, const float *img_pts, int n, int armor_size, double *rvec, double *tvec, int32_t *ok);
+/* Both IPPE solutions (cv::solvePnPGeneric): rvec [n][2][3], tvec [n][2][3], err [n][2] (rms normalised residual), A first --
+ * entry 0 is bit-identical to irmv_pnp_solve's answer, entry 1 the solution it throws away ("pose ambiguity" above).
+ * ok [n]: bit 0 = irmv_pnp_solve's ok; bit 1 = entry 1 passed its own finiteness check.  Where bit 0 is clear, entry 1 and
+ * both errors are zero. */
+int irmv_pnp_solve2(irmv_pnp *p, const float *img_pts, int n, int armor_size, double *rvec, double *tvec, double *err, int32_t *ok);
 
 #ifdef __cplusplus
 }

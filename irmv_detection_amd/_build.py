@@ -28,6 +28,9 @@ SOURCES = [
     ("k_post.hip", ["-ffp-contract=off"]),
     ("k_tiles.hip", ["-ffp-contract=off"]),
     ("k_light.hip", ["-ffp-contract=off"]),
+    # the pose-ambiguity instantiations of the two files above, each in a module of its own (k_post.hip's header)
+    ("k_post_alt.hip", ["-ffp-contract=off"]),
+    ("k_light_alt.hip", ["-ffp-contract=off"]),
     ("k_shuffle.hip", []),
     ("k_render.hip", []),
     ("k_debug.hip", []),
@@ -105,7 +108,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     for src, extra in SOURCES:
         sp = os.path.join(CSRC, src)
         obj = os.path.join(LIB_DIR, os.path.splitext(src)[0] + ".o")
-        if force or _stale(obj, [sp] + headers):
+        included = [os.path.join(CSRC, src.replace("_alt.hip", ".hip"))] if src.endswith("_alt.hip") else []   # k_*_alt.hip #include their twin
+        if force or _stale(obj, [sp] + included + headers):
             cmd = [cc] + COMMON + extra + os.environ.get("IRMV_EXTRA_HIPCC_FLAGS", "").split() + ["-c", sp, "-o", obj]
             if verbose:
                 print(" ".join(cmd))

@@ -83,6 +83,23 @@ class ClassPolicy(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("score_thr", C.c_float * 16), ("plate", C.c_uint8 * 16)]
 
 
+POSE_MIN_ERR, POSE_PRIOR = 0, 1
+POSE_MODES = {"min_err": POSE_MIN_ERR, "prior": POSE_PRIOR}
+NORMAL_UP_ROBOT = -0.25881904510252074   # -sin 15 deg: a plate whose outward normal points 15 degrees upward
+
+
+class PosePrior(C.Structure):
+    """irmv_pose_prior (include/irmv_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("ambiguity_ratio", C.c_double),
+                ("normal_up", C.c_double * 16), ("normal_up_default", C.c_double)]
+
+
+class PoseAlt(C.Structure):
+    """irmv_pose_alt (include/irmv_hip.h): the IPPE solution a result record does not report."""
+    _fields_ = [("rvec", C.c_double * 3), ("tvec", C.c_double * 3), ("quat", C.c_double * 4),
+                ("err", C.c_double), ("err_alt", C.c_double), ("state", C.c_int32), ("alt_ok", C.c_int32)]
+
+
 RENDER_COLOR, RENDER_BINARY = 0, 1
 RENDER_KINDS = {"color": RENDER_COLOR, "binary": RENDER_BINARY}
 MARK_BOXES, MARK_LABELS, MARK_ARMORS = 1, 2, 4
@@ -259,6 +276,13 @@ SYMBOLS = [
     ("irmv_pnp_destroy", None, [_P]),
     ("irmv_pnp_solve", C.c_int, [_P, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_double),
                                  C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    ("irmv_pnp_solve2", C.c_int, [_P, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_double),
+                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    ("irmv_engine_set_pose_prior", C.c_int, [_P, C.POINTER(PosePrior)]),
+    ("irmv_engine_get_pose_prior", C.c_int, [_P, C.POINTER(PosePrior)]),
+    ("irmv_engine_set_up", C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
+    ("irmv_engine_get_up", C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
+    ("irmv_engine_pose_alts", C.c_int, [_P, C.c_int, C.POINTER(PoseAlt), C.c_int, C.POINTER(C.c_int)]),
 ]
 
 _lib = None
@@ -364,6 +388,20 @@ def class_policy_struct(score_thr, plate) -> ClassPolicy:
     for c in range(16):
         p.score_thr[c] = float(score_thr[c])
         p.plate[c] = int(plate[c])
+    return p
+
+
+def pose_prior_struct(mode=POSE_MIN_ERR, ratio=8.0, normal_up=NORMAL_UP_ROBOT, normal_up_default=None) -> PosePrior:
+    """An irmv_pose_prior (no check: the library's are the ones under test).  normal_up: one number for every class, or 16."""
+    import numpy as np
+    p = PosePrior()
+    p.struct_size = C.sizeof(PosePrior)
+    p.mode = POSE_MODES[mode] if isinstance(mode, str) else int(mode)
+    p.ambiguity_ratio = float(ratio)
+    nu = np.broadcast_to(np.asarray(normal_up, np.float64), (16,))
+    for c in range(16):
+        p.normal_up[c] = float(nu[c])
+    p.normal_up_default = float(nu[0] if normal_up_default is None else normal_up_default)
     return p
 
 

@@ -97,6 +97,7 @@ irmv_engine::~irmv_engine()
     if (src_host) (void)hipHostFree(src_host);
     if (dets_host) (void)hipHostFree(dets_host);
     if (fout_host) (void)hipHostFree(fout_host);
+    if (alts_host) (void)hipHostFree(alts_host);
     if (light_dets_host) (void)hipHostFree(light_dets_host);
     for (auto &kv : tile_merges)
         if (kv.second.out_host) (void)hipHostFree(kv.second.out_host);
@@ -423,6 +424,8 @@ static int peek_blob_nk(const irmv_engine_cfg &c, int *nk)
     return IRMV_OK;
 }
 
+static void pose_prior_defaults(irmv_pose_prior *p);   // (pose ambiguity, below)
+
 extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **out)
 {
     if (!cfg_in || !out) return fail(IRMV_ERR_ARG, "cfg/out is null");
@@ -458,6 +461,9 @@ extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **o
         else (void)hipGetLastError();   // an older runtime serving the library (torch's bundled ROCm 7.0) does not know the attribute: no node, and no sticky error for the checks behind the tuning launches
     }
     e->sw = read_switches();
+    pose_prior_defaults(&e->pose_prior);
+    e->up.assign((size_t)cfg->num_slots * 3, 0.0);
+    for (int s = 0; s < cfg->num_slots; s++) e->up[3 * s + 1] = -1.0;   // a level camera: image y points down
     int rc = load_blob(e.get());
     e->cfg.weights_path = nullptr;  // caller-owned, not retained
     e->cfg.weights_blob = nullptr;
@@ -835,6 +841,120 @@ extern "C" int irmv_engine_get_class_policy(const irmv_engine *e, irmv_class_pol
     return IRMV_OK;
 }
 
+// ---- pose ambiguity ---------------------------------------------------------------------
+static void pose_prior_defaults(irmv_pose_prior *p)
+{
+    memset(p, 0, sizeof *p);
+    p->struct_size = sizeof *p;
+    p->mode = IRMV_POSE_MIN_ERR;
+    p->ambiguity_ratio = 8.0;
+    for (int c = 0; c < 16; c++) p->normal_up[c] = -0.25881904510252074;   // -sin 15 deg: a robot's plate
+    p->normal_up_default = -0.25881904510252074;
+}
+
+// Host only; NaN fails every comparison
+static int check_pose_prior(const irmv_pose_prior *p)
+{
+    if (p->struct_size != sizeof(irmv_pose_prior)) return fail(IRMV_ERR_ARG, "irmv_pose_prior.struct_size mismatch");
+    if (p->mode != IRMV_POSE_MIN_ERR && p->mode != IRMV_POSE_PRIOR) return fail(IRMV_ERR_ARG, "irmv_pose_prior.mode: unknown mode (IRMV_POSE_*)");
+    if (!(p->ambiguity_ratio >= 1.0)) return fail(IRMV_ERR_ARG, "irmv_pose_prior.ambiguity_ratio must be >= 1 (+inf allowed)");
+    for (int c = 0; c < 16; c++)
+        if (!(std::fabs(p->normal_up[c]) <= 1.0)) return fail(IRMV_ERR_ARG, "irmv_pose_prior.normal_up[" + std::to_string(c) + "] must be in [-1, 1]");
+    if (!(std::fabs(p->normal_up_default) <= 1.0)) return fail(IRMV_ERR_ARG, "irmv_pose_prior.normal_up_default must be in [-1, 1]");
+    return IRMV_OK;
+}
+
+// e->pose_prior -> prior_dev.  The caller has made sure that nothing of this engine is in flight.
+static int write_pose_prior(irmv_engine *e)
+{
+    PosePrior t{};
+    t.mode = e->pose_prior.mode;
+    t.ratio = e->pose_prior.ambiguity_ratio;
+    for (int c = 0; c < kMaxClasses; c++) t.s[c] = e->pose_prior.normal_up[c];
+    t.s_default = e->pose_prior.normal_up_default;
+    HIP_TRY(hipMemcpy(e->prior_dev, &t, sizeof t, hipMemcpyHostToDevice));
+    return IRMV_OK;
+}
+
+// The first irmv_engine_set_pose_prior: the alt records (device and pinned, zeroed), the two tables, and the one re-capture --
+// the captured steps hold the kAlt = false kernel nodes.  Nothing of the engine is in flight.
+static int enable_pose_alt(irmv_engine *e)
+{
+    const size_t n = (size_t)e->cfg.num_slots * e->cfg.max_det;
+    TRY(dev_alloc(e, (void **)&e->alts_dev, n * sizeof(DevAlt)));
+    HIP_TRY(hipMemset(e->alts_dev, 0, n * sizeof(DevAlt)));
+    HIP_TRY(hipHostMalloc((void **)&e->alts_host, n * sizeof(DevAlt), hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(hipHostGetDevicePointer((void **)&e->alts_host_dev, e->alts_host, 0));
+    memset(e->alts_host, 0, n * sizeof(DevAlt));
+    log_range(e, "pinned alts_host", e->alts_host, n * sizeof(DevAlt));
+    TRY(dev_alloc(e, (void **)&e->prior_dev, sizeof(PosePrior)));
+    TRY(dev_alloc(e, (void **)&e->up_dev, e->up.size() * sizeof(double)));
+    HIP_TRY(hipMemcpy(e->up_dev, e->up.data(), e->up.size() * sizeof(double), hipMemcpyHostToDevice));
+    e->pose_alt = true;
+    drop_graphs(e, false);
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_set_pose_prior(irmv_engine *e, const irmv_pose_prior *p)
+{
+    irmv_pose_prior np;
+    if (p) {
+        TRY(check_pose_prior(p));   // (the values first: a refused one never reaches the engine)
+        np = *p;
+    } else {
+        pose_prior_defaults(&np);
+    }
+    if (!e) return fail(IRMV_ERR_ARG, "engine is null");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));   // every stream of the engine: no step in flight reads the table, no graph is running
+    if (!e->pose_alt) TRY(enable_pose_alt(e));
+    e->pose_prior = np;
+    return write_pose_prior(e);
+}
+
+extern "C" int irmv_engine_get_pose_prior(const irmv_engine *e, irmv_pose_prior *out)
+{
+    if (!e || !out) return fail(IRMV_ERR_ARG, "engine / out is null");
+    *out = e->pose_prior;
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_set_up(irmv_engine *e, int slot, const double up[3])
+{
+    if (!up) return fail(IRMV_ERR_ARG, "up is null");
+    const double len = std::sqrt((up[0] * up[0] + up[1] * up[1]) + up[2] * up[2]);
+    if (!(len > 0.0 && len < INFINITY)) return fail(IRMV_ERR_ARG, "irmv_engine_set_up: the vector must be finite and non-zero");
+    TRY(check_range(e, slot, 1));
+    const double u[3] = {up[0] / len, up[1] / len, up[2] / len};
+    if (e->pose_alt) {
+        HIP_TRY(hipSetDevice(e->cfg.device));
+        TRY(irmv_engine_wait_slots(e, slot, 1));   // the slot's last step has read the table
+        HIP_TRY(hipMemcpy(e->up_dev + 3 * slot, u, sizeof u, hipMemcpyHostToDevice));
+    }
+    std::copy(u, u + 3, e->up.begin() + 3 * slot);
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_get_up(const irmv_engine *e, int slot, double up[3])
+{
+    TRY(check_range(e, slot, 1));
+    if (!up) return fail(IRMV_ERR_ARG, "up is null");
+    std::copy(e->up.begin() + 3 * slot, e->up.begin() + 3 * slot + 3, up);
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_pose_alts(irmv_engine *e, int slot, irmv_pose_alt *out, int cap, int *n)
+{
+    TRY(check_range(e, slot, 1));
+    if (!n || (cap > 0 && !out)) return fail(IRMV_ERR_ARG, "out/n is null");
+    if (!e->pose_alt) return fail(IRMV_ERR_ARG, "irmv_engine_pose_alts: irmv_engine_set_pose_prior has not been called on this engine");
+    static_assert(sizeof(DevAlt) == sizeof(irmv_pose_alt), "DevAlt is irmv_pose_alt");
+    const int k = std::max(0, std::min(std::min(e->fout_host[slot].num_dets, e->cfg.max_det), cap));
+    if (k) memcpy(out, e->alts_host + (size_t)slot * e->cfg.max_det, (size_t)k * sizeof(irmv_pose_alt));
+    *n = k;
+    return IRMV_OK;
+}
+
 extern "C" int irmv_engine_get_bayer_isp(const irmv_engine *e, uint16_t gain_q8[3], uint8_t *lut)
 {
     if (!e) return fail(IRMV_ERR_ARG, "engine is null");
@@ -850,7 +970,8 @@ struct irmv_pnp {
     PnpConst c{};
     hipStream_t stream = nullptr;
     float *pts = nullptr;
-    double *rvec = nullptr, *tvec = nullptr;
+    double *rvec = nullptr, *tvec = nullptr;   // [cap][2][3]: irmv_pnp_solve uses the first half
+    double *err = nullptr;                     // [cap][2]
     int32_t *ok = nullptr;
     int cap = 0;
 };
@@ -860,8 +981,23 @@ static void pnp_free(irmv_pnp *p)
     if (p->pts) (void)hipFree(p->pts);
     if (p->rvec) (void)hipFree(p->rvec);
     if (p->tvec) (void)hipFree(p->tvec);
+    if (p->err) (void)hipFree(p->err);
     if (p->ok) (void)hipFree(p->ok);
-    p->pts = nullptr; p->rvec = p->tvec = nullptr; p->ok = nullptr; p->cap = 0;
+    p->pts = nullptr; p->rvec = p->tvec = p->err = nullptr; p->ok = nullptr; p->cap = 0;
+}
+
+static int pnp_reserve(irmv_pnp *p, int n)
+{
+    if (n <= p->cap) return IRMV_OK;
+    pnp_free(p);
+    const int cap = std::max(n, 64);
+    HIP_TRY(hipMalloc((void **)&p->pts, (size_t)cap * 32));
+    HIP_TRY(hipMalloc((void **)&p->rvec, (size_t)cap * 48));
+    HIP_TRY(hipMalloc((void **)&p->tvec, (size_t)cap * 48));
+    HIP_TRY(hipMalloc((void **)&p->err, (size_t)cap * 16));
+    HIP_TRY(hipMalloc((void **)&p->ok, (size_t)cap * 4));
+    p->cap = cap;
+    return IRMV_OK;
 }
 
 extern "C" int irmv_pnp_create(int device, const double K[9], const double D[5], irmv_pnp **out)
@@ -897,20 +1033,30 @@ extern "C" int irmv_pnp_solve(irmv_pnp *p, const float *img_pts, int n, int armo
     if (armor_size != IRMV_ARMOR_SMALL && armor_size != IRMV_ARMOR_LARGE) return fail(IRMV_ERR_ARG, "bad armor_size");
     if (n == 0) return IRMV_OK;
     HIP_TRY(hipSetDevice(p->device));
-    if (n > p->cap) {
-        pnp_free(p);
-        const int cap = std::max(n, 64);
-        HIP_TRY(hipMalloc((void **)&p->pts, (size_t)cap * 32));
-        HIP_TRY(hipMalloc((void **)&p->rvec, (size_t)cap * 24));
-        HIP_TRY(hipMalloc((void **)&p->tvec, (size_t)cap * 24));
-        HIP_TRY(hipMalloc((void **)&p->ok, (size_t)cap * 4));
-        p->cap = cap;
-    }
+    TRY(pnp_reserve(p, n));
     HIP_TRY(hipMemcpyAsync(p->pts, img_pts, (size_t)n * 32, hipMemcpyHostToDevice, p->stream));
     launch_pnp_only(p->c, p->pts, n, armor_size, p->rvec, p->tvec, p->ok, p->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(rvec, p->rvec, (size_t)n * 24, hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipMemcpyAsync(tvec, p->tvec, (size_t)n * 24, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(ok, p->ok, (size_t)n * 4, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return IRMV_OK;
+}
+
+extern "C" int irmv_pnp_solve2(irmv_pnp *p, const float *img_pts, int n, int armor_size, double *rvec, double *tvec, double *err, int32_t *ok)
+{
+    if (!p || !img_pts || !rvec || !tvec || !err || !ok || n < 0) return fail(IRMV_ERR_ARG, "null argument");
+    if (armor_size != IRMV_ARMOR_SMALL && armor_size != IRMV_ARMOR_LARGE) return fail(IRMV_ERR_ARG, "bad armor_size");
+    if (n == 0) return IRMV_OK;
+    HIP_TRY(hipSetDevice(p->device));
+    TRY(pnp_reserve(p, n));
+    HIP_TRY(hipMemcpyAsync(p->pts, img_pts, (size_t)n * 32, hipMemcpyHostToDevice, p->stream));
+    launch_pnp_both(p->c, p->pts, n, armor_size, p->rvec, p->tvec, p->err, p->ok, p->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(rvec, p->rvec, (size_t)n * 48, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(tvec, p->tvec, (size_t)n * 48, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(err, p->err, (size_t)n * 16, hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipMemcpyAsync(ok, p->ok, (size_t)n * 4, hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
     return IRMV_OK;

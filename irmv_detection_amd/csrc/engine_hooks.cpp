@@ -257,6 +257,7 @@ static int extract_armors(irmv_engine *e, int slot, const float *xyxy, const flo
     a.num_dets = nullptr;
     a.n_boxes = n;
     a.boxes = e->light_boxes;
+    a.alts = nullptr;   // explicit boxes have no class: normal_up_default, and no alt record
     a.trace = trace ? e->light_trace_dev : nullptr;
     launch_light_extract(a, n, 1, st);
     HIP_TRY(hipGetLastError());

@@ -317,6 +317,16 @@ struct irmv_engine {
     // addresses are fixed for the engine's life; a policy change rewrites the contents and re-captures nothing.
     ClassTable *cls_dev = nullptr;
     irmv_class_policy policy{};       // the policy in force (the uniform one of cfg.score_thr / cfg.armor_size until set)
+    // Pose ambiguity (irmv_engine_set_pose_prior).  Until the first call nothing but `up` and `pose_prior` (host values) exists
+    // and every step launches what it always has.  The first call allocates the alt records -- [S][max_det] on the device and
+    // pinned, travelling exactly as the DevDet records do (post_args, copy_out) --, the prior table and the per-slot up vectors,
+    // and drops the captured graphs once: from then on the steps launch the kAlt kernels, which read both tables when they run.
+    bool pose_alt = false;
+    DevAlt *alts_dev = nullptr, *alts_host = nullptr, *alts_host_dev = nullptr;
+    PosePrior *prior_dev = nullptr;
+    double *up_dev = nullptr;             // [S][3]
+    std::vector<double> up;               // [S][3] unit vectors as set (default (0, -1, 0)), in the frame PnP sees
+    irmv_pose_prior pose_prior{};         // the prior in force (MIN_ERR, ratio 8, every normal_up 0 until set)
     long long *dbg_dev = nullptr;
     std::set<std::string> lazy_tensors;   // tensors a step does not write because a fused kernel keeps them on chip
     bool classical = false;            // four points from the classical light extraction instead of a keypoint head

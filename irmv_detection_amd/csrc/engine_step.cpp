@@ -89,6 +89,10 @@ LightArgs irmv::light_args(const irmv_engine *e, const View &v, int first)
         a.refine = e->refine_dev;
         a.kpts = e->refine_kpts + (size_t)first * c.max_det * 8;
     }
+    if (e->pose_alt) {   // the kAlt instantiations: the records beside the step's device records
+        a.alts = e->alts_dev + (size_t)first * c.max_det;
+        a.prior = e->prior_dev; a.up = e->up_dev;
+    }
     return a;
 }
 
@@ -123,6 +127,10 @@ PostArgs irmv::post_args(const irmv_engine *e, const View &v, const Step &s)
     p.counts = e->sw.split_scan ? e->cand_counts + first : nullptr;
     p.cand_bits = e->sparse_head ? e->cand_bits + (size_t)first * e->cand_words : nullptr;
     p.cand_words = e->cand_words;
+    if (e->pose_alt) {   // nms_pnp_kernel<true>: the alt records go where the DevDet records go
+        p.alts = (zero_copy ? e->alts_host_dev : e->alts_dev) + (size_t)first * e->cfg.max_det;
+        p.prior = e->prior_dev; p.up = e->up_dev;
+    }
     return p;
 }
 
@@ -454,6 +462,9 @@ static int copy_out_dev(irmv_engine *e, int first, int count, hipStream_t st)
                            (size_t)count * e->cfg.max_det * sizeof(DevDet), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(e->fout_host + first, e->fout_dev + first, (size_t)count * sizeof(DevFrameOut),
                            hipMemcpyDeviceToHost, st));
+    if (e->pose_alt)
+        HIP_TRY(hipMemcpyAsync(e->alts_host + (size_t)first * e->cfg.max_det, e->alts_dev + (size_t)first * e->cfg.max_det,
+                               (size_t)count * e->cfg.max_det * sizeof(DevAlt), hipMemcpyDeviceToHost, st));
     return IRMV_OK;
 }
 

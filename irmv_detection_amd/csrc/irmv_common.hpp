@@ -423,6 +423,30 @@ struct PnpConst {
     double hy[2], hz[2];   // half extents of the small / large armor (metres)
 };
 
+// Pose ambiguity (irmv_engine_set_pose_prior): IPPE's two solutions per armor.  A = the one the min-error rule reports (solution
+// 0 unless !(err0 <= err1)), B = the other.  DevAlt is the side record of one detection (the layout of irmv_pose_alt): the
+// solution its DevDet does NOT carry.  PosePrior and the per-slot up vectors ([num_slots][3] doubles) live in device memory at
+// addresses fixed from the first set_pose_prior on and are read when the kernel runs, like ClassTable and PnpConst.
+struct DevAlt {
+    double rvec[3], tvec[3], quat[4];
+    double err, err_alt;      // rms normalised residual of the reported pose / of this one
+    int32_t state;            // 0: pnp_ok == 0, the record is all zero; 1: the DevDet holds A; 2: the prior reported B
+    int32_t alt_ok;           // this pose's own finiteness check
+};
+constexpr int kPoseMinErr = 0, kPosePrior = 1;   // == IRMV_POSE_*
+struct PosePrior {
+    int32_t mode, pad_;
+    double ratio;             // B is eligible iff errB <= ratio * errA
+    double s[kMaxClasses];    // per class: the expected n . u (n = column 0 of R: the plate normal pointing away from the camera)
+    double s_default;         // ... of a detection without a class (explicit boxes)
+};
+// What one solve needs of the two tables: the rule's operands as values
+struct PoseRule { int mode; double ratio, s, ux, uy, uz; };
+__device__ inline PoseRule pose_rule(const PosePrior *p, const double *up, int cls)   // cls < 0: s_default
+{
+    return PoseRule{p->mode, p->ratio, cls >= 0 ? p->s[cls & (kMaxClasses - 1)] : p->s_default, up[0], up[1], up[2]};
+}
+
 struct PostArgs {
     const float *head_all;    // one allocation: [level][slot (all num_slots)][H*W][kHeadRec]
     int slots_total, first;   // level block offset = lvl_base * slots_total records; this step starts at slot `first`
@@ -450,8 +474,14 @@ struct PostArgs {
     unsigned int *cand_bits;  // [B][cand_words] candidate-anchor bitmap of the sparse head (ConvArgs::cand_bits), or nullptr: nms_pnp_kernel
     int cand_words;           // clears its frame's words where it resets the count
     int pnp_stride;           // frame b solves with pnp[(first + b) * pnp_stride]: 0 = one record for every slot, 1 = one per slot (window engines)
+    // Pose ambiguity: all three null until the first irmv_engine_set_pose_prior (nms_pnp_kernel<false>, today's code and bits);
+    // set, nms_pnp_kernel<true> runs: survivor j's other solution goes to alts[b * max_det + j], the prior may pick B
+    DevAlt *alts;             // [B][max_det], device or pinned like dets
+    const PosePrior *prior;
+    const double *up;         // [num_slots][3]: frame b's unit up vector at up[3 * (first + b)]
 };
 void launch_nms_pnp(const PostArgs &a, int batch, hipStream_t s);
+void launch_nms_pnp_alt(const PostArgs &a, int batch, hipStream_t s);   // k_post_alt.hip: a.alts != nullptr (launch_nms_pnp calls it)
 constexpr int kScanBlocks = 16;   // workgroups per frame of scan_decode_kernel (more where a 16th of the keys would not fit kScanLdsMax)
 constexpr size_t kScanLdsMax = 159 * 1024;   // its dynamic LDS: 160 KiB per workgroup on gfx950, less its static variables
 void launch_scan_decode(const PostArgs &a, int batch, hipStream_t s);
@@ -528,8 +558,14 @@ struct LightArgs {
     const RefineParams *refine;   // non-null: the guided instantiation (light_extract_kernel<true>): dets[i].kpts are the prior, refined in place
     float *kpts;             // guided: the prior [B][max_det][8].  A step's launch fills it from the records first (refine_prior_kernel);
                              // with explicit boxes the caller has (irmv_engine_refine_points), and the records are output only
+    // Pose ambiguity (PostArgs): prior == nullptr launches today's instantiations.  alts may be null with prior set (explicit
+    // boxes: the rule runs with s_default, no record leaves)
+    DevAlt *alts;            // [B][max_det]
+    const PosePrior *prior;
+    const double *up;        // [num_slots][3], frame b's at up[3 * (first + b)]
 };
 void launch_light_extract(const LightArgs &a, int n_boxes_max, int batch, hipStream_t s);
+void launch_light_extract_alt(const LightArgs &a, int n_boxes_max, int batch, hipStream_t s);   // k_light_alt.hip: a.prior != nullptr (launch_light_extract calls it)
 
 // ---- debug images (k_render.hip; irmv_engine_render) -----------------------------------------------------------------
 // One mark record as the host hands it to the kernel: every coordinate already an integer in OUTPUT pixels (truncated, the
@@ -564,6 +600,9 @@ hipError_t launch_lds_fill(uint32_t pattern, uint32_t *check, int workgroups, hi
 hipError_t launch_lds_probe(uint32_t pattern, uint32_t word, uint32_t *out, int workgroups, hipStream_t s);   // out: [workgroups][4], zeroed
 
 void launch_pnp_only(const PnpConst &c, const float *pts, int n, int armor_size, double *rvec, double *tvec,
+                     int32_t *ok, hipStream_t s);
+// both solutions, A first: rvec / tvec [n][2][3], err [n][2], ok bit 0 = launch_pnp_only's ok, bit 1 = B passed its own finiteness check
+void launch_pnp_both(const PnpConst &c, const float *pts, int n, int armor_size, double *rvec, double *tvec, double *err,
                      int32_t *ok, hipStream_t s);
 
 }  // namespace irmv

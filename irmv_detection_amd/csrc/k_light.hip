@@ -35,6 +35,11 @@
 //   7. armor_valid, armor_size, kpts_net stay; 8. DevDet::pad_ = 1 refined, 0 the head's points kept, -1 kept because the
 //      extraction had no answer (pool, contour or point limit).
 // snap and roi_margin are read from device memory when the kernel runs (RefineParams).
+//
+// This file is compiled TWICE: on its own (the two instantiations above, kAlt = false, and their launcher), and through
+// k_light_alt.hip with IRMV_ALT_TU defined, which takes the templates only and instantiates kAlt = true (pose ambiguity) in a
+// module of its own.  Both sets in one module moved scan_external out of line in the kAlt = false kernels; alone they are the
+// kernels from before the parameter.
 #include "irmv_common.hpp"
 #include "pnp_device.hpp"
 
@@ -379,7 +384,9 @@ __device__ __forceinline__ bool guided_roi(const float *xyxy, const float *kp, f
     return roi_of(g, cols, rows, r);
 }
 
-template <bool kGuided>
+// kAlt (LightArgs::prior set: engines after their first irmv_engine_set_pose_prior): every solve is solve_pnp_ippe_both -- the
+// prior may report B -- and, where a.alts is set, the other solution of the pose the record finally carries goes to its DevAlt.
+template <bool kGuided, bool kAlt = false>
 __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
 {
     __shared__ int s_nfound, s_toolarge, s_nfound_raw;
@@ -565,7 +572,13 @@ __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
             double rvec[3] = {0.0, 0.0, 0.0}, tvec[3] = {0.0, 0.0, 0.0}, quat[4] = {0.0, 0.0, 0.0, 1.0};
             if (a.boxes) {
                 // explicit boxes and keypoints (irmv_engine_refine_points): the record is output only -- the inputs and their pose first
-                const int ok = solve_pnp_ippe(pc, kin, plate, rvec, tvec, quat) ? 1 : 0;
+                int ok;
+                if constexpr (kAlt) {   // (no class: s_default; no record)
+                    DevAlt alt;
+                    ok = solve_pnp_ippe_both(pc, kin, plate, rvec, tvec, quat, pose_rule(a.prior, a.up + 3 * (size_t)(a.first + b), -1), &alt) ? 1 : 0;
+                } else {
+                    ok = solve_pnp_ippe(pc, kin, plate, rvec, tvec, quat) ? 1 : 0;
+                }
                 for (int i = 0; i < 8; i++) { d->kpts[i] = kin[i]; d->kpts_net[i] = 0.f; }
                 for (int i = 0; i < 3; i++) { d->rvec[i] = rvec[i]; d->tvec[i] = tvec[i]; }
                 for (int i = 0; i < 4; i++) d->quat[i] = quat[i];
@@ -584,7 +597,12 @@ __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
                     float kp[8];
                     kp[0] = l.bottom[0]; kp[1] = l.bottom[1]; kp[2] = l.top[0]; kp[3] = l.top[1];
                     kp[4] = r.top[0]; kp[5] = r.top[1]; kp[6] = r.bottom[0]; kp[7] = r.bottom[1];
-                    if (solve_pnp_ippe(pc, kp, plate, rvec, tvec, quat)) {
+                    bool solved;
+                    DevAlt alt;
+                    if constexpr (kAlt) solved = solve_pnp_ippe_both(pc, kp, plate, rvec, tvec, quat, pose_rule(a.prior, a.up + 3 * (size_t)(a.first + b), a.boxes ? -1 : d->cls), &alt);
+                    else solved = solve_pnp_ippe(pc, kp, plate, rvec, tvec, quat);
+                    if (solved) {
+                        if constexpr (kAlt) { if (a.alts) a.alts[(size_t)b * a.max_det + j] = alt; }   // the alt of the quad whose pose is reported
                         for (int i = 0; i < 8; i++) d->kpts[i] = kp[i];
                         for (int i = 0; i < 3; i++) { d->rvec[i] = rvec[i]; d->tvec[i] = tvec[i]; }
                         for (int i = 0; i < 4; i++) d->quat[i] = quat[i];
@@ -635,10 +653,24 @@ __global__ __launch_bounds__(256) void light_extract_kernel(LightArgs a)
         // the reference always solves with the SMALL model (src/pnp_solver.cpp:47-48)
         // ... this project with the plate the class policy gives the detection's class (explicit boxes have no class)
         const int plate = (a.cls && !a.boxes) ? a.cls->plate[d->cls & (kMaxClasses - 1)] : a.pnp_armor_size;
-        if (valid) d->pnp_ok = solve_pnp_ippe(a.pnp[(size_t)(a.first + b) * a.pnp_stride], d->kpts, plate, d->rvec, d->tvec, d->quat) ? 1 : 0;
+        if constexpr (kAlt) {
+            DevAlt alt{};
+            if (valid) d->pnp_ok = solve_pnp_ippe_both(a.pnp[(size_t)(a.first + b) * a.pnp_stride], d->kpts, plate, d->rvec, d->tvec, d->quat,
+                                                       pose_rule(a.prior, a.up + 3 * (size_t)(a.first + b), a.boxes ? -1 : d->cls), &alt) ? 1 : 0;
+            if (a.alts) a.alts[(size_t)b * a.max_det + j] = alt;
+        } else {
+            if (valid) d->pnp_ok = solve_pnp_ippe(a.pnp[(size_t)(a.first + b) * a.pnp_stride], d->kpts, plate, d->rvec, d->tvec, d->quat) ? 1 : 0;
+        }
     }
 }
 
+#ifdef IRMV_ALT_TU
+void launch_light_extract_alt(const LightArgs &a, int n_boxes_max, int batch, hipStream_t s)
+{
+    if (a.refine) hipLaunchKernelGGL((light_extract_kernel<true, true>), dim3(n_boxes_max, batch), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((light_extract_kernel<false, true>), dim3(n_boxes_max, batch), dim3(256), 0, s, a);
+}
+#else
 // the guided instantiation's prior of a step: the records' keypoints as the NMS kernel left them -> kpts [B][max_det][8]
 __global__ __launch_bounds__(256) void refine_prior_kernel(const DevDet *dets, float *kpts, int n)
 {
@@ -653,8 +685,10 @@ void launch_light_extract(const LightArgs &a, int n_boxes_max, int batch, hipStr
         const int n = batch * a.max_det * 8;
         hipLaunchKernelGGL(refine_prior_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a.dets, a.kpts, n);
     }
+    if (a.prior) { launch_light_extract_alt(a, n_boxes_max, batch, s); return; }
     if (a.refine) hipLaunchKernelGGL(light_extract_kernel<true>, dim3(n_boxes_max, batch), dim3(256), 0, s, a);   // guided: profile name light_refine
     else hipLaunchKernelGGL(light_extract_kernel<false>, dim3(n_boxes_max, batch), dim3(256), 0, s, a);
 }
+#endif   // IRMV_ALT_TU
 
 }  // namespace irmv

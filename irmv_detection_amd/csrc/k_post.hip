@@ -14,6 +14,12 @@
 // Latency-bound integer/compare work: one lane per anchor for the decode, one
 // workgroup per frame for sort + NMS, the IoU test of a 64-candidate block
 // against the kept set and against itself done wave-wide with ballots.
+//
+// This file is compiled TWICE.  On its own it holds every kernel and launcher an engine has always run.  k_post_alt.hip includes
+// it with IRMV_ALT_TU defined and takes only the templates and device functions, to instantiate nms_pnp_kernel<true> and the
+// two-solution PnP kernel in a module of their own: with both instantiations in one module the inliner's choices for
+// nms_pnp_kernel<false> changed (13 333 -> 13 494 instructions) -- alone in its module it is, instruction for instruction, the
+// kernel from before the template parameter.
 #include "irmv_common.hpp"
 #include "pnp_device.hpp"
 
@@ -180,6 +186,7 @@ __device__ __forceinline__ void decode_boxes(const PostArgs &a, int b, const uns
 // decoded here, four lanes per anchor, exactly as decode_boxes does.
 // ---------------------------------------------------------------------------
 constexpr int kScanU = 2;   // loads in flight per lane: one memory round trip per U * 64 anchors
+#ifndef IRMV_ALT_TU
 // A workgroup's range of (anchor, side) quads: a kScanBlocks-th of the frame, unless its keys would not fit in LDS (nets of more
 // than 22 528 anchors, beyond 1024 x 1024, whose launch was refused): then ranges that do, and as many more workgroups.
 static int scan_quads_per_block(int A, int nc)
@@ -295,6 +302,7 @@ void launch_scan_decode(const PostArgs &a, int batch, hipStream_t s)
     }
     hipLaunchKernelGGL(scan_decode_kernel, dim3(blocks, batch), dim3(256), lds, s, a, per);
 }
+#endif   // IRMV_ALT_TU
 
 // "IoU(a, b) > thr" as inter > thr * union (same expression as the oracle's iou_gt)
 __device__ __forceinline__ bool iou_gt(const f32x4 a, const f32x4 b, float thr)
@@ -328,6 +336,7 @@ __device__ __forceinline__ bool iou_gt_area(const f32x4 a, float aa, const f32x4
     return inter > thr * uni;
 }
 
+#ifndef IRMV_ALT_TU
 __global__ void pnp_only_kernel(PnpConst c, const float *pts, int n, int armor_size, double *rvec, double *tvec, int32_t *ok)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -342,6 +351,29 @@ void launch_pnp_only(const PnpConst &c, const float *pts, int n, int armor_size,
 {
     hipLaunchKernelGGL(pnp_only_kernel, dim3((n + 63) / 64), dim3(64), 0, s, c, pts, n, armor_size, rvec, tvec, ok);
 }
+#else
+// irmv_pnp_solve2: both solutions of every quad, A first (mode MIN_ERR: nothing is picked)
+__global__ void pnp_both_kernel(PnpConst c, const float *pts, int n, int armor_size, double *rvec, double *tvec, double *err, int32_t *ok)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double r[3] = {0, 0, 0}, t[3] = {0, 0, 0}, q[4];
+    DevAlt alt;
+    const PoseRule rule{kPoseMinErr, 1.0, 0.0, 0.0, 0.0, 0.0};
+    const bool good = solve_pnp_ippe_both(c, pts + 8 * i, armor_size, r, t, q, rule, &alt);
+    for (int k = 0; k < 3; k++) {
+        rvec[6 * i + k] = r[k]; tvec[6 * i + k] = t[k];
+        rvec[6 * i + 3 + k] = alt.rvec[k]; tvec[6 * i + 3 + k] = alt.tvec[k];
+    }
+    err[2 * i] = alt.err; err[2 * i + 1] = alt.err_alt;
+    ok[i] = (good ? 1 : 0) | (alt.alt_ok ? 2 : 0);
+}
+
+void launch_pnp_both(const PnpConst &c, const float *pts, int n, int armor_size, double *rvec, double *tvec, double *err, int32_t *ok, hipStream_t s)
+{
+    hipLaunchKernelGGL(pnp_both_kernel, dim3((n + 63) / 64), dim3(64), 0, s, c, pts, n, armor_size, rvec, tvec, err, ok);
+}
+#endif   // IRMV_ALT_TU
 
 // ---------------------------------------------------------------------------
 // One workgroup (1024 lanes = 16 waves) per frame:
@@ -392,6 +424,9 @@ __device__ __forceinline__ unsigned long long block_sup_mask(f32x4 box, int cls,
     return sup;
 }
 
+// kAlt (engines after their first irmv_engine_set_pose_prior): phase 4 solves with solve_pnp_ippe_pair_both -- the prior may
+// report B -- and the pair's odd lane stores the survivor's DevAlt.  kAlt = false is the kernel as it has always been.
+template <bool kAlt>
 __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
 {
     __shared__ __attribute__((aligned(16))) unsigned long long skeys[kCandCap];   // 64 KiB: candidate keys (bitonic sorts in place)
@@ -1309,7 +1344,16 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
             double rvec[3] = {0.0, 0.0, 0.0}, tvec[3] = {0.0, 0.0, 0.0}, quat[4] = {0.0, 0.0, 0.0, 1.0};
             int pnp_ok = 0;
             const int plate = a.cls->plate[kept_cls[j] & (kMaxClasses - 1)];   // class policy: the object points of this detection's class
-            if (a.nk >= 8) pnp_ok = solve_pnp_ippe_pair(a.pnp[(size_t)(a.first + b) * a.pnp_stride], px0, py0, px1, py1, plate, rvec, tvec, quat) ? 1 : 0;
+            if constexpr (kAlt) {
+                DevAlt alt{};
+                if (a.nk >= 8) {
+                    const PoseRule rule = pose_rule(a.prior, a.up + 3 * (size_t)(a.first + b), kept_cls[j]);
+                    pnp_ok = solve_pnp_ippe_pair_both(a.pnp[(size_t)(a.first + b) * a.pnp_stride], px0, py0, px1, py1, plate, rvec, tvec, quat, rule, &alt) ? 1 : 0;
+                }
+                if (!w) a.alts[(size_t)b * a.max_det + j] = alt;   // (the pair's other lane stages the record)
+            } else {
+                if (a.nk >= 8) pnp_ok = solve_pnp_ippe_pair(a.pnp[(size_t)(a.first + b) * a.pnp_stride], px0, py0, px1, py1, plate, rvec, tvec, quat) ? 1 : 0;
+            }
             IRMV_STAMP(12);
             if (w) {
 #pragma unroll
@@ -1341,9 +1385,16 @@ __global__ __launch_bounds__(1024) void nms_pnp_kernel(PostArgs a)
 #undef IRMV_STAMP
 }
 
+#ifdef IRMV_ALT_TU
+void launch_nms_pnp_alt(const PostArgs &a, int batch, hipStream_t s)
+{
+    hipLaunchKernelGGL(nms_pnp_kernel<true>, dim3(batch), dim3(1024), 0, s, a);
+}
+#else
 void launch_nms_pnp(const PostArgs &a, int batch, hipStream_t s)
 {
-    hipLaunchKernelGGL(nms_pnp_kernel, dim3(batch), dim3(1024), 0, s, a);
+    if (a.alts) launch_nms_pnp_alt(a, batch, s);
+    else hipLaunchKernelGGL(nms_pnp_kernel<false>, dim3(batch), dim3(1024), 0, s, a);
 }
 
 // The candidate counts the kernels above branch on, as compiled (irmv_post_limits: tests/post_ladder.py builds its count
@@ -1354,5 +1405,6 @@ void post_limits(int32_t out[16])
                            kScanBlocks, 256 * kScanU, (int32_t)kScanLdsMax, 1024 * kInScanU, kMatW_ * 64, 0, 0};
     for (int i = 0; i < 16; i++) out[i] = v[i];
 }
+#endif   // IRMV_ALT_TU
 
 }  // namespace irmv

@@ -111,9 +111,34 @@ __device__ inline void rot_to_quat(const double *R, double *q)
     }
 }
 
-// pts: LB, LT, RT, RB in source-frame pixels (src/pnp_solver.cpp:41-44)
-__device__ inline bool solve_pnp_ippe(const PnpConst &c, const float *pts, int armor_size, double *rvec, double *tvec, double *quat)
+// The prior's cost of a solution: |n . u - s|, n = column 0 of R (the model x axis in camera coordinates: the plate normal
+// pointing away from the camera), in the written order (irmv_detection_amd/pose_prior.py is the bit-exact host reference)
+__device__ inline double pose_cost(const double *R, const PoseRule &r)
 {
+    return fabs(((R[0] * r.ux + R[3] * r.uy) + R[6] * r.uz) - r.s);
+}
+
+// report B  iff  mode == PRIOR && errB <= ratio * errA && costB < costA   (any NaN: false, A stays)
+__device__ inline bool pose_pick_b(const PoseRule &r, double errA, double costA, double errB, double costB)
+{
+    return r.mode == kPosePrior && errB <= r.ratio * errA && costB < costA;
+}
+
+__device__ inline bool pose_finite(const double *rvec, const double *tvec)
+{
+    const double chk = rvec[0] + rvec[1] + rvec[2] + tvec[0] + tvec[1] + tvec[2];
+    return chk == chk && fabs(chk) < 1e300;
+}
+
+// pts: LB, LT, RT, RB in source-frame pixels (src/pnp_solver.cpp:41-44)
+// kBoth = false: cv::solvePnP(SOLVEPNP_IPPE)'s answer -- rule and alt are not read.  kBoth = true (quat non-null): *alt receives
+// the solution that is not reported, both residuals and the choice (DevAlt; all zero where the call fails), and `rule` may
+// report B.  Up to the choice the operation sequence is the same, so with mode MIN_ERR the reported bits are kBoth = false's.
+template <bool kBoth>
+__device__ inline bool solve_pnp_ippe_t(const PnpConst &c, const float *pts, int armor_size, double *rvec, double *tvec, double *quat,
+                                        const PoseRule *rule, DevAlt *alt)
+{
+    if constexpr (kBoth) *alt = DevAlt{};
     const double hy = c.hy[armor_size], hz = c.hz[armor_size];
     for (int i = 0; i < 8; i++)
         if (!pixel_in_range(pts[i])) return false;
@@ -194,12 +219,41 @@ __device__ inline bool solve_pnp_ippe(const PnpConst &c, const float *pts, int a
         }
         if (sol == 0) best = ps; else other = ps;
     }
-    if (!(best.err <= other.err)) best = other;
-    rot_to_rvec(best.R, rvec);
-    tvec[0] = best.t[0]; tvec[1] = best.t[1]; tvec[2] = best.t[2];
-    if (quat) rot_to_quat(best.R, quat);
-    const double chk = rvec[0] + rvec[1] + rvec[2] + tvec[0] + tvec[1] + tvec[2];
-    return chk == chk && fabs(chk) < 1e300;
+    if constexpr (kBoth) {
+        // A = solution 0 unless !(err0 <= err1); then the rule
+        if (!(best.err <= other.err)) { const Pose t = best; best = other; other = t; }
+        const bool pick = pose_pick_b(*rule, best.err, pose_cost(best.R, *rule), other.err, pose_cost(other.R, *rule));
+        if (pick) { const Pose t = best; best = other; other = t; }
+        rot_to_rvec(best.R, rvec);
+        tvec[0] = best.t[0]; tvec[1] = best.t[1]; tvec[2] = best.t[2];
+        rot_to_quat(best.R, quat);
+        if (!pose_finite(rvec, tvec)) return false;
+        rot_to_rvec(other.R, alt->rvec);
+        alt->tvec[0] = other.t[0]; alt->tvec[1] = other.t[1]; alt->tvec[2] = other.t[2];
+        rot_to_quat(other.R, alt->quat);
+        alt->err = best.err; alt->err_alt = other.err;
+        alt->state = pick ? 2 : 1;
+        alt->alt_ok = pose_finite(alt->rvec, alt->tvec) ? 1 : 0;
+        return true;
+    } else {
+        if (!(best.err <= other.err)) best = other;
+        rot_to_rvec(best.R, rvec);
+        tvec[0] = best.t[0]; tvec[1] = best.t[1]; tvec[2] = best.t[2];
+        if (quat) rot_to_quat(best.R, quat);
+        const double chk = rvec[0] + rvec[1] + rvec[2] + tvec[0] + tvec[1] + tvec[2];
+        return chk == chk && fabs(chk) < 1e300;
+    }
+}
+
+__device__ inline bool solve_pnp_ippe(const PnpConst &c, const float *pts, int armor_size, double *rvec, double *tvec, double *quat)
+{
+    return solve_pnp_ippe_t<false>(c, pts, armor_size, rvec, tvec, quat, nullptr, nullptr);
+}
+
+__device__ inline bool solve_pnp_ippe_both(const PnpConst &c, const float *pts, int armor_size, double *rvec, double *tvec, double *quat,
+                                           const PoseRule &rule, DevAlt *alt)
+{
+    return solve_pnp_ippe_t<true>(c, pts, armor_size, rvec, tvec, quat, &rule, alt);
 }
 
 // The same solver spread over a PAIR of lanes (2 consecutive lanes, both active, same arguments; the result is valid on both).
@@ -214,7 +268,12 @@ __device__ inline double quad_bcast(double v, int src_lane) { return __shfl(v, s
 
 // (px[h], py[h]): point q + 2 h of the armor (LB, LT, RT, RB) in source-frame pixels -- BY VALUE: a pointer indexed by the lane
 // parity had put the caller's array (and with it the whole record) into scratch memory
-__device__ inline bool solve_pnp_ippe_pair(const PnpConst &c, float px0, float py0, float px1, float py1, int armor_size, double *rvec, double *tvec, double *quat)
+// kBoth (quat non-null; rule and alt as in solve_pnp_ippe_t, *alt valid on both lanes): B is the losing lane's `ps`.  Each lane
+// converts ITS solution to rvec / quat -- the work both lanes do redundantly on the winner's in the kBoth = false form -- and the
+// reported and the other pose are then broadcast from their lanes: B costs shuffles and stores, no arithmetic.
+template <bool kBoth>
+__device__ inline bool solve_pnp_ippe_pair_t(const PnpConst &c, float px0, float py0, float px1, float py1, int armor_size, double *rvec, double *tvec, double *quat,
+                                             const PoseRule *rule, DevAlt *alt)
 {
     const int lane = threadIdx.x & 63, base = lane & ~1, q = lane & 1;
     const double hy = c.hy[armor_size], hz = c.hz[armor_size];
@@ -320,17 +379,63 @@ __device__ inline bool solve_pnp_ippe_pair(const PnpConst &c, float px0, float p
     const int ok0 = __shfl((int)sol_ok, base), ok1 = __shfl((int)sol_ok, base + 1);
     const double e0 = quad_bcast(ps.err, base), e1 = quad_bcast(ps.err, base + 1);
     ok = ok && ok0 && ok1;
-    const int win = base + ((e0 <= e1) ? 0 : 1);
-    Pose best;
+    if constexpr (kBoth) {
+        const int qa = (e0 <= e1) ? 0 : 1;                 // A's lane of the pair
+        const double errA = qa ? e1 : e0, errB = qa ? e0 : e1;
+        const double cost = pose_cost(ps.R, *rule);
+        const double costA = quad_bcast(cost, base + qa), costB = quad_bcast(cost, base + (qa ^ 1));
+        const bool pick = pose_pick_b(*rule, errA, costA, errB, costB);
+        const int rep = base + (qa ^ (pick ? 1 : 0)), oth = rep ^ 1;
+        double own[10];                                     // this lane's solution: rvec, tvec, quat
+        rot_to_rvec(ps.R, own);
+        own[3] = ps.t[0]; own[4] = ps.t[1]; own[5] = ps.t[2];
+        rot_to_quat(ps.R, own + 6);
+        const int fin = pose_finite(own, own + 3) ? 1 : 0;
+        double other[10];
 #pragma unroll
-    for (int i = 0; i < 9; i++) best.R[i] = quad_bcast(ps.R[i], win);
+        for (int i = 0; i < 10; i++) {
+            const double v = quad_bcast(own[i], rep);
+            other[i] = quad_bcast(own[i], oth);
+            if (i < 3) rvec[i] = v; else if (i < 6) tvec[i - 3] = v; else quat[i - 6] = v;
+        }
+        const int fin_rep = __shfl(fin, rep), fin_oth = __shfl(fin, oth);
+        const bool good = ok && fin_rep;
+        DevAlt r{};
+        if (good) {
 #pragma unroll
-    for (int i = 0; i < 3; i++) best.t[i] = quad_bcast(ps.t[i], win);
-    rot_to_rvec(best.R, rvec);
-    tvec[0] = best.t[0]; tvec[1] = best.t[1]; tvec[2] = best.t[2];
-    if (quat) rot_to_quat(best.R, quat);
-    const double chk = rvec[0] + rvec[1] + rvec[2] + tvec[0] + tvec[1] + tvec[2];
-    return ok && chk == chk && fabs(chk) < 1e300;
+            for (int i = 0; i < 3; i++) { r.rvec[i] = other[i]; r.tvec[i] = other[3 + i]; }
+#pragma unroll
+            for (int i = 0; i < 4; i++) r.quat[i] = other[6 + i];
+            r.err = pick ? errB : errA; r.err_alt = pick ? errA : errB;
+            r.state = pick ? 2 : 1;
+            r.alt_ok = fin_oth;
+        }
+        *alt = r;
+        return good;
+    } else {
+        const int win = base + ((e0 <= e1) ? 0 : 1);
+        Pose best;
+#pragma unroll
+        for (int i = 0; i < 9; i++) best.R[i] = quad_bcast(ps.R[i], win);
+#pragma unroll
+        for (int i = 0; i < 3; i++) best.t[i] = quad_bcast(ps.t[i], win);
+        rot_to_rvec(best.R, rvec);
+        tvec[0] = best.t[0]; tvec[1] = best.t[1]; tvec[2] = best.t[2];
+        if (quat) rot_to_quat(best.R, quat);
+        const double chk = rvec[0] + rvec[1] + rvec[2] + tvec[0] + tvec[1] + tvec[2];
+        return ok && chk == chk && fabs(chk) < 1e300;
+    }
+}
+
+__device__ inline bool solve_pnp_ippe_pair(const PnpConst &c, float px0, float py0, float px1, float py1, int armor_size, double *rvec, double *tvec, double *quat)
+{
+    return solve_pnp_ippe_pair_t<false>(c, px0, py0, px1, py1, armor_size, rvec, tvec, quat, nullptr, nullptr);
+}
+
+__device__ inline bool solve_pnp_ippe_pair_both(const PnpConst &c, float px0, float py0, float px1, float py1, int armor_size, double *rvec, double *tvec, double *quat,
+                                                const PoseRule &rule, DevAlt *alt)
+{
+    return solve_pnp_ippe_pair_t<true>(c, px0, py0, px1, py1, armor_size, rvec, tvec, quat, &rule, alt);
 }
 
 }  // namespace irmv

@@ -418,6 +418,43 @@ class YoloEngine:
         capi.check(self._L.irmv_engine_results(self._h, slot, out, self.max_det, C.byref(n)))
         return [out[i] for i in range(n.value)]
 
+    # ---- pose ambiguity (include/irmv_hip.h; host reference: pose_prior.py) ----
+    def set_pose_prior(self, mode="min_err", ratio: float = 8.0, normal_up=capi.NORMAL_UP_ROBOT, normal_up_default=None) -> None:
+        """irmv_engine_set_pose_prior: from the first call on every step also delivers the IPPE solution its records do not
+        report (pose_alts); mode "prior" lets the per-class tilt prior choose between the two.  normal_up: the expected
+        n . up per class (one number or 16; -sin 15 deg for a robot's plate), ratio: B is eligible while errB <= ratio * errA.
+        mode None: back to the defaults (MIN_ERR), records still delivered.  The first call re-captures the steps once; a
+        refused value raises and changes nothing."""
+        if mode is None:
+            capi.check(self._L.irmv_engine_set_pose_prior(self._h, None))
+            return
+        p = capi.pose_prior_struct(mode, ratio, normal_up, normal_up_default)
+        capi.check(self._L.irmv_engine_set_pose_prior(self._h, C.byref(p)))
+
+    def pose_prior(self) -> dict:
+        p = capi.PosePrior()
+        capi.check(self._L.irmv_engine_get_pose_prior(self._h, C.byref(p)))
+        return dict(mode=int(p.mode), ratio=float(p.ambiguity_ratio), normal_up=np.array(p.normal_up[:], np.float64),
+                    normal_up_default=float(p.normal_up_default))
+
+    def set_up(self, up, slot: int = 0) -> None:
+        """The slot's up vector in the camera frame PnP sees (normalised by the library; default (0, -1, 0)), live: waits for
+        the slot's last step, re-captures nothing."""
+        u = np.ascontiguousarray(up, np.float64).reshape(3)
+        capi.check(self._L.irmv_engine_set_up(self._h, slot, u.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def up(self, slot: int = 0) -> np.ndarray:
+        u = np.zeros(3)
+        capi.check(self._L.irmv_engine_get_up(self._h, slot, u.ctypes.data_as(C.POINTER(C.c_double))))
+        return u
+
+    def pose_alts(self, slot: int = 0):
+        """capi.PoseAlt records (copies) parallel to results(slot) / results_raw(slot)."""
+        n = C.c_int(0)
+        out = (capi.PoseAlt * self.max_det)()
+        capi.check(self._L.irmv_engine_pose_alts(self._h, slot, out, self.max_det, C.byref(n)))
+        return [out[i] for i in range(n.value)]
+
     def debug_graph_count(self) -> int:
         """Test hook: the captured graphs the engine holds."""
         return int(self._L.irmv_engine_debug_graph_count(self._h))
@@ -740,6 +777,18 @@ class PnPSolver:
                                           tvec.ctypes.data_as(C.POINTER(C.c_double)),
                                           ok.ctypes.data_as(C.POINTER(C.c_int32))))
         return ok, rvec, tvec
+
+    def solve_generic(self, img_pts: np.ndarray, armor_size: int = capi.ARMOR_SMALL):
+        """Both IPPE solutions per quad (irmv_pnp_solve2, cv::solvePnPGeneric): -> (ok [n] bool, alt_ok [n] bool,
+        rvec [n, 2, 3], tvec [n, 2, 3], err [n, 2]); entry 0 is solve_batch's answer, bit for bit."""
+        pts = np.ascontiguousarray(img_pts, np.float32).reshape(-1, 8)
+        n = len(pts)
+        rvec = np.zeros((n, 2, 3)); tvec = np.zeros((n, 2, 3)); err = np.zeros((n, 2)); ok = np.zeros(n, np.int32)
+        dp = C.POINTER(C.c_double)
+        capi.check(self._L.irmv_pnp_solve2(self._h, pts.ctypes.data_as(C.POINTER(C.c_float)), n, armor_size,
+                                           rvec.ctypes.data_as(dp), tvec.ctypes.data_as(dp), err.ctypes.data_as(dp),
+                                           ok.ctypes.data_as(C.POINTER(C.c_int32))))
+        return (ok & 1).astype(bool), (ok & 2).astype(bool), rvec, tvec, err
 
     def calculateDistanceToCenter(self, image_point: Tuple[float, float]) -> float:
         """|p - (cx, cy)|.  The reference reads cx, cy with at<float>() from a
