@@ -3,36 +3,36 @@ count at which nms_pnp_kernel (csrc/k_post.hip) changes its code path.  No GPU h
 builders on the CPU oracle, tests/test_gpu_post_ladder.py runs them through write_head + run_post.
 
 The counts are computed from `capi.post_limits()` (irmv_post_limits), never written down: a pull request that moves a
-threshold moves the ladder with it.  Which branch a count family is meant to reach (lines of k_post.hip at the time of
-writing; the constants are the ones irmv_post_limits returns):
+threshold moves the ladder with it.  Which branch a count family is meant to reach (by the phase or helper of k_post.hip
+that holds it; the constants are the ones irmv_post_limits returns):
 
-  0, 1, 2            the empty frame (rank sort skipped: `if (n_stored > 0)`, :697 / :918), a lone key, a pair
-  7, 8, 9            the rank sort's padding `n8 = (n + 7) & ~7` (:691 / :913): seven pad keys, none, seven
-  63, 64, 65         a 64-candidate block exactly full (`(n + 63) >> 6`, :776 / :985), and P = min(16, 1024 / n) lanes per
-  127, 128, 129      key (:698 / :919) going from 16 to 15; two blocks
-  pre_lo +- 1        the lower bound of the prefilter's radix window (`before >= lo`, :641) -- reached through plateaus()
-  340, 341, 342      1024 // 3: P goes from 3 to 2 (the last stretch `j_lo < j_hi`, :702 / :923, runs empty at some n)
-  rank_use +- 1      rank sort | bitonic (:908), class-walk path (:664), full suppression matrix (`n <= kMatN`, :968),
-                     and the prefilter starting to run (`n_total > pre_hi`, :537)
-  lazy_n +- 1        lazy matrix | per-class-list walk (:1075); sixteen blocks = sixteen waves (:1096)
-  rank_max +- 1      the bitonic network's size 2048 -> 4096 (:943) and, in attempt 0, the compaction buffer
-                     `pos < kRankSortMax` (:653)
-  sup_cap +- 1       precomputed block masks | masks on the fly in the walk (`start < n_pre`, :1194); pre_nms_cap's default
-  cand_cap +- 1      keys in LDS | exact radix select from the global list (:436, :548, :552)
+  0, 1, 2            the empty frame (rank_sort skips its count: `if (n > 0)`), a lone key, a pair
+  7, 8, 9            rank_sort's padding `n8 = (n + 7) & ~7`: seven pad keys, none, seven
+  63, 64, 65         a 64-candidate block exactly full (`(n + 63) >> 6` in the walks and gather_sorted), and rank_sort's
+  127, 128, 129      P = min(16, 1024 / n) lanes per key going from 16 to 15; two blocks
+  pre_lo +- 1        the lower bound of the prefilter's radix window (`before >= lo` in select_window) -- reached through plateaus()
+  340, 341, 342      1024 // 3: P goes from 3 to 2 (rank_sort's last stretch `j_lo < j_hi` runs empty at some n)
+  rank_use +- 1      rank sort | bitonic (sort_keys), class-walk path (`kp_lds` in the kernel body), full suppression matrix
+                     (`n <= kMatN`, kernel body), and the prefilter starting to run (`n_total > pre_hi`, kernel body)
+  lazy_n +- 1        nms_lazy_matrix | nms_class_lists (kernel body); sixteen blocks = sixteen waves (class_word_masks)
+  rank_max +- 1      the bitonic network's size 2048 -> 4096 (sort_keys) and, in attempt 0, select_window's compaction buffer
+                     `pos < kRankSortMax`
+  sup_cap +- 1       precomputed block masks | masks on the fly in the walk (`start < n_pre`, nms_class_lists); pre_nms_cap's default
+  cand_cap +- 1      keys in LDS | exact radix select from the global list (take_keys, the kernel body's start-over, select_top_k)
 
 Builders (each returns a complete (A, 64 + nc + nk) fp32 head with exactly n (anchor, class) pairs above the 0.25 score
 threshold, every other class logit at -20):
 
   chain(n)           one class, neighbouring anchors, wide overlapping boxes, distinct scores: few survivors, so above
                      rank_use the prefilter's first walk neither fills max_det nor sees everything and the kernel starts
-                     over (:1227); from ~4095 up the cluster is large enough to fill 100
+                     over (the restart rule of the attempt loop); from ~4095 up the cluster is large enough to fill 100
   iso(n)             point boxes, random pairs, random scores: nobody suppresses anybody, the first walk fills
   tied(n)            the first n pairs in (anchor, class) order at ONE logit: keys differ only in their lower 32 bits, both
-                     radix searches run to their last pass (:559, :600); several classes per anchor
+                     radix searches (select_top_k, select_window) run to their last pass; several classes per anchor
   plateaus(m, n, ..) m pairs at logit 2.0, n - m at 1.0: the first radix bucket holds m keys, so the window search ends
-                     above it, in it or below it as m passes pre_lo and pre_hi (:630 - :644)
+                     above it, in it or below it as m passes pre_lo and pre_hi (select_window's wave-0 scan)
   dense(a0, a1)      every class lit on anchors [a0, a1): placed by dense_ranges() on the partition edges of both scans
-                     (scan_decode_kernel's per-workgroup range :185, the in-kernel scan's rounds :457) and on the level edges
+                     (scan_decode_kernel's per-workgroup range, the rounds of take_keys' in-kernel scan) and on the level edges
 """
 import functools
 

@@ -1,26 +1,26 @@
 """decode + NMS (csrc/k_post.hip) at every candidate count a branch switches on: the heads of tests/post_ladder.py through
 write_head + run_post, each against the CPU oracle bit for bit (test_gpu_engine._assert_post_exact), one engine per test.
 
-Which kernel branch each count family reaches is listed, with the line of its condition, in tests/post_ladder.py; the
-configurations choose WHO gets there:
+Which kernel branch each count family reaches is listed, with the phase or helper that holds its condition, in
+tests/post_ladder.py; the configurations choose WHO gets there:
 
   scan            run_post as it is: scan_decode_kernel finds the candidates and decodes their boxes, nms_pnp_kernel takes the
-                  keys from the global list (`if (a.counts)`, :421) and the rank-sort / bitonic paths of :908
+                  keys from the global list (`if (a.counts)` in take_keys) and the rank-sort / bitonic paths of sort_keys
   keys            IRMV_POST_KEYS_ONLY=1: nms_pnp_kernel decodes its own boxes as a whole step's does -- the class-major path
-                  up to rank_use candidates (`kp_lds`, :664), decode_keys above
+                  up to rank_use candidates (`kp_lds` in the kernel body: nms_class_walk), decode_keys above
   keys-r3         ... with IRMV_NMS_CLASSWALK=0: decode_keys + the full-matrix walk at every count
-  inkernel        IRMV_SPLIT_SCAN=0: the scan inside nms_pnp_kernel (:445), keys mirrored to the global list the start-over
-                  and the radix select read back (:548, :564)
+  inkernel        IRMV_SPLIT_SCAN=0: the scan inside nms_pnp_kernel (take_keys' other branch), keys mirrored to the global list
+                  the start-over (the kernel body's attempt loop) and the radix select (select_top_k) read back
   nopre           IRMV_NMS_PREFILTER=0: no first walk on the head of the list; every count runs the full algorithm
   pre64           IRMV_NMS_PRE=64,32: the prefilter's window moved to 32 .. 64, so its searches run at counts from 65 up and
                   the compaction / start-over logic meets the small-count paths
-  wide            pre_nms_cap = cand_cap, max_det 256: survivors reach the LDS staging past record 236 (:1246)
+  wide            pre_nms_cap = cand_cap, max_det 256: survivors reach the LDS staging past record 236 (NmsLds::det_staging)
   narrow          max_det 1 with pre_nms_cap = rank_use and rank_use + 1: the first block's cap (`__popcll(K) > room`)
-  cap-at-m        pre_nms_cap = m - 1, m, m + 1 around the 400 keys the first walk selects: the `n >= n_full` clause of :1227
+  cap-at-m        pre_nms_cap = m - 1, m, m + 1 around the 400 keys the first walk selects: the `n >= n_full` clause of the restart rule
   cap-at-n        pre_nms_cap = n - 1, n, n + 1 at n = rank_use, lazy_n candidates, max_det 256
   small           net 64 (84 anchors, up to 1176 pairs): several classes per anchor, one busy scan workgroup and fifteen idle
   no-anchor-list  net 1024 with IRMV_SPLIT_SCAN=0: 21 504 anchors > 4 * sup_cap, the in-kernel scan keeps no anchor list
-                  (`alist` null, :417) and decodes every anchor's box
+                  (NmsLds::anchor_list returns null) and decodes every anchor's box
 
 Beyond the oracle equality: the raw tuples of scan, keys, keys-r3, inkernel and nopre are compared with each other as the
 tests run (each against the first configuration that ran in this process), pre64's against a default engine's, and after
