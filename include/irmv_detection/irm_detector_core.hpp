@@ -103,6 +103,15 @@ public:
     bool debug = false;                                  // the node's debug (:90-95, :259-280): every frame also yields FrameResult::visualized_image / binary_image,
                                                          // rendered on the GPU (YoloEngine::render); live through set_bool_parameter("debug", v) like the reference (:380-381)
     int debug_scale = 1;                                 // 1, 2 or 4: the debug images at full, half or quarter size (set_parameter "debug_scale")
+    int src_format = IRMV_SRC_HWC8;                      // IRMV_SRC_*: a Bayer format makes image_buffers() raw CFA frames, demosaiced on the GPU
+    // Frame metering (include/irmv_hip.h): struct_size != 0 enables it on the three engines at creation (YoloEngine::meter_opts
+    // fills one) -- FrameResult::stats is then each frame's record.
+    irmv_meter_opts metering{};
+    // Automatic white balance: every awb_period-th frame the gains irmv_stats_gray_world(lo = 8, hi = 247) reads from that
+    // frame's record go to all three engines (set_bayer_isp, the tone LUT kept); a record the helper refuses leaves the gains
+    // alone.  0: off.  Needs Bayer engines and IRMV_METER_RAW metering -- white balance must look in front of its own gains --,
+    // else the constructor throws and set_parameter("awb_period", v) refuses.  Live: set_parameter "awb_period".
+    int awb_period = 0;
   };
 
   // What one frame produced, beyond the message: kept for debug publishers and tests.
@@ -120,16 +129,24 @@ public:
     // Params::debug only (else empty): the frame with this frame's armors, boxes and labels drawn on it (:261-263; the latency
     // text lines are not drawn), and gray -> threshold(binary_threshold) -> three channels with the boxes and labels (:273-277)
     cv::Mat visualized_image, binary_image;
+    // Params::metering only (else stats_valid = false): this frame's metering record; awb_applied: this frame's record set new
+    // white-balance gains, awb_gains, which hold from the next frame on
+    irmv_frame_stats stats{};
+    bool stats_valid = false, awb_applied = false;
+    std::array<uint16_t, 3> awb_gains{256, 256, 256};
   };
 
   // Three engines, one per TripleBuffer slot, like the node (:33-38); K, D from camera_info (:52).
   IrmDetectorCore(const std::string & model_path, const std::array<double, 9> & k, const std::vector<double> & d, const Params & p)
   : params_(p)
   {
+    if (p.awb_period < 0 || (p.awb_period > 0 && !awb_possible(p)))
+      throw std::invalid_argument("IrmDetectorCore: awb_period needs a Bayer src_format and IRMV_METER_RAW metering");
     for (auto & e : yolo_engines_) {
       e = std::make_unique<YoloEngine>(model_path, p.image_input_size, p.profiling, p.device, false, p.net_input_size.width > 0 ? p.net_input_size.width : -1,
-                                       IRMV_SRC_HWC8, std::array<uint16_t, 3>{256, 256, 256}, p.net_input_size.height > 0 ? p.net_input_size.height : -1,
+                                       p.src_format, std::array<uint16_t, 3>{256, 256, 256}, p.net_input_size.height > 0 ? p.net_input_size.height : -1,
                                        IRMV_DEMOSAIC_BILINEAR, p.window_size, p.tile_overlap, p.point_source);
+      if (p.metering.struct_size != 0) e->set_metering(&p.metering);
       push_params(*e);
       if (p.refine_snap != 0.5 || p.refine_roi_margin != 4.0) e->set_refine(float(p.refine_snap), float(p.refine_roi_margin));
       if (p.enemy_color != -1 || !p.large_plate_classes.empty()) push_class_policy(*e);
@@ -201,6 +218,19 @@ public:
       if (alts.size() == armors.size()) out.alts.push_back(alts[i]);
     }
     out.inference_latency_ms = eng.get_profiling_time();
+    if (params_.metering.struct_size != 0) {
+      out.stats = eng.frame_stats();
+      out.stats_valid = true;
+      if (params_.awb_period > 0 && ++awb_frames_ % uint64_t(params_.awb_period) == 0) {
+        std::vector<uint8_t> lut;
+        std::array<uint16_t, 3> g = eng.bayer_gains(&lut);
+        if (irmv_stats_gray_world(&out.stats, 8, 247, g.data()) == IRMV_OK) {   // (refused: g is untouched, and nothing is set)
+          for (auto & e : yolo_engines_) e->set_bayer_isp(g, lut.data());
+          out.awb_applied = true;
+          out.awb_gains = g;
+        }
+      }
+    }
     if (params_.debug) {
       // the marks: every bbox (:263, :277) and every extracted armor (:262) -- of a pose model both live in the detection
       // records; of a bbox-only model the armors are records of their own whose box is no number, so it draws none
@@ -243,6 +273,12 @@ public:
       const int sc = int(value);
       if (sc != 1 && sc != 2 && sc != 4) return false;
       params_.debug_scale = sc;
+      return true;
+    }
+    else if (name == "awb_period") {                       // live; refused without Bayer engines and IRMV_METER_RAW metering
+      const int n = int(value);
+      if (n < 0 || double(n) != value || (n > 0 && !awb_possible(params_))) return false;
+      params_.awb_period = n;
       return true;
     }
     else if (name == "enemy_color") {                      // :384-385; live, and re-captures nothing
@@ -309,6 +345,11 @@ public:
   const Params & params() const { return params_; }
 
 private:
+  static bool awb_possible(const Params & p)
+  {
+    return p.src_format != IRMV_SRC_HWC8 && p.metering.struct_size != 0 && p.metering.domain == IRMV_METER_RAW;
+  }
+
   void push_params(YoloEngine & e) const
   {
     e.set_extract_params(params_.binary_threshold, float(params_.light_min_ratio), float(params_.light_max_ratio), float(params_.light_max_angle),
@@ -327,6 +368,7 @@ private:
   }
 
   Params params_;
+  uint64_t awb_frames_ = 0;   // frames since creation, counted while awb_period is on
   std::array<std::unique_ptr<YoloEngine>, 3> yolo_engines_;
   std::unique_ptr<PnPSolver> pnp_solver_;
 };

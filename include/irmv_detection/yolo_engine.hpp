@@ -177,6 +177,62 @@ public:
       throw std::runtime_error(std::string("YoloEngine::set_bayer_isp: ") + irmv_last_error());
     rotated_valid_ = false;
   }
+  bool is_bayer() const { return irmv_engine_src_format(engine_) != IRMV_SRC_HWC8; }
+  // the gains in force, and (lut != nullptr) the [3][256] tone LUT behind them
+  std::array<uint16_t, 3> bayer_gains(std::vector<uint8_t> * lut = nullptr) const
+  {
+    std::array<uint16_t, 3> g{256, 256, 256};
+    if (lut) lut->resize(3 * 256);
+    if (irmv_engine_get_bayer_isp(engine_, g.data(), lut ? lut->data() : nullptr) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::bayer_gains: ") + irmv_last_error());
+    return g;
+  }
+
+  // ---- frame metering (include/irmv_hip.h, "frame metering") ----
+  // set_metering: from the next detect() on every step also computes four 256-bin histograms of the rectangle (view-local
+  // result coordinates; w == h == 0: the whole view), sampled every `step` pixels: IRMV_METER_VIEW = the frame the network
+  // sees (three channels and gray), IRMV_METER_RAW = a Bayer engine's raw frame in front of gains and LUT (R, G, B sites and
+  // all).  nullptr: off.  The first enabling call re-captures the steps once; later ones, nullptr included, none.
+  // frame_stats(): the record of the last detect().  meter(): the frame in the buffer now, on demand, on any engine.
+  // irmv_stats_mean_q8 / _percentile / _gray_world / _exposure_q8 read a record.
+  static irmv_meter_opts meter_opts(int domain = IRMV_METER_VIEW, cv::Point corner = {}, cv::Size size = {}, int step = 1)
+  {
+    irmv_meter_opts o{};
+    o.struct_size = sizeof o;
+    o.domain = domain;
+    o.x0 = corner.x; o.y0 = corner.y; o.w = size.width; o.h = size.height;
+    o.step = step;
+    return o;
+  }
+  void set_metering(const irmv_meter_opts * o)
+  {
+    if (irmv_engine_set_metering(engine_, o) != IRMV_OK) throw std::runtime_error(std::string("YoloEngine::set_metering: ") + irmv_last_error());
+  }
+  void set_metering(int domain, cv::Point corner = {}, cv::Size size = {}, int step = 1)
+  {
+    const irmv_meter_opts o = meter_opts(domain, corner, size, step);
+    set_metering(&o);
+  }
+  // the options in force; false: off (or never set)
+  bool metering(irmv_meter_opts * o = nullptr) const
+  {
+    int on = 0;
+    irmv_engine_get_metering(engine_, o, &on);
+    return on != 0;
+  }
+  irmv_frame_stats frame_stats() const
+  {
+    irmv_frame_stats s;
+    if (irmv_engine_frame_stats(engine_, 0, &s) != IRMV_OK) throw std::runtime_error(std::string("YoloEngine::frame_stats: ") + irmv_last_error());
+    return s;
+  }
+  irmv_frame_stats meter(int domain = IRMV_METER_VIEW, cv::Point corner = {}, cv::Size size = {}, int step = 1)
+  {
+    const irmv_meter_opts o = meter_opts(domain, corner, size, step);
+    irmv_frame_stats s;
+    if (irmv_engine_meter(engine_, 0, &o, &s) != IRMV_OK) throw std::runtime_error(std::string("YoloEngine::meter: ") + irmv_last_error());
+    return s;
+  }
 
   // ---- class policy: per-class score thresholds, colour mask, plate size (include/irmv_hip.h, irmv_class_policy) ----
   // Two things the caller sets independently, one table in the engine: the caller's policy (score_thr[c] >= 1 switches

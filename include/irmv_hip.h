@@ -679,7 +679,7 @@ int irmv_engine_read_tensor(irmv_engine *e, const char *name, int first_slot, in
  * Every op of the engine's graph, of any kind; the non-conv layer ops run one at a time on a slot range. */
 typedef struct irmv_graph_op {
     int32_t op;                 /* the engine's op index (the `op` of irmv_engine_run_op and of the conv hooks above) */
-    char kind[16];              /* conv conv0 pool dw shuffle front c2f2 c2f32 bneck kpt3 pre demosaic crop scan nms light */
+    char kind[16];              /* conv conv0 pool dw shuffle front c2f2 c2f32 bneck kpt3 pre demosaic crop scan nms light meter */
     char layer[48];             /* weight layer, or the op's own name (model.9.m, model.N.shuffle, preprocess, ...) */
     char kname[48];             /* kernel, as irmv_engine_profile names it */
     irmv_conv_seg s0, s1;       /* inputs (tensor "" = none; the pool's: channels [0, C) of its own tensor) */
@@ -798,6 +798,97 @@ int irmv_debug_lds_fill(uint32_t pattern32);
  * out[4 w + 2], out[4 w + 3] = the HW_ID and XCC_ID registers of the CU it ran on.  *n = workgroups launched; out holds
  * 4 * cap words (IRMV_ERR_ARG if cap is smaller than that number; out NULL queries *n alone). */
 int irmv_debug_lds_probe(uint32_t pattern32, uint32_t word, uint32_t *out, int cap, int *n);
+
+/* ---- frame metering: histograms inside the step, white balance from them ------------------------------------------------
+ * The measuring half of the ISP.  A Bayer producer has bypassed the camera SDK's auto white balance and exposure, and the frame
+ * it would meter exists only in device memory.  Metering is a per-frame record of four 256-bin integer histograms, computed on
+ * the GPU (k_meter.hip) as one op of the captured step and delivered beside the slot's detections, or on demand for any
+ * rectangle; small host functions turn a record into white-balance gains, a percentile and an exposure ratio.  Everything is an
+ * integer count; irmv_detection_amd/metering.py is the host reference, bit for bit.
+ *   rectangle   x0, y0, w, h in VIEW-LOCAL result coordinates: the frame of the slot's current view as detections see it
+ *               (rotated under cfg.rotate180); a window slot's corner is NOT added.  w == h == 0: the whole view; otherwise
+ *               w, h >= 1.  The rectangle is clipped to the view; an empty intersection is legal: all-zero histograms, n and rect
+ *   VIEW        the samples are the pixels (x, y) of the clipped rectangle with (x - rx0) % step == 0 and (y - ry0) % step == 0,
+ *               (rx0, ry0) the clipped corner, step 1, 2 or 4.  hist rows 0, 1, 2: the three channels as stored; row 3:
+ *               gray = (p0*3735 + p1*19235 + p2*9798 + (1<<14)) >> 15, the light extraction's
+ *   RAW         Bayer engines only: the raw CFA frame in front of gains and tone LUT -- what white balance must look at, or the
+ *               loop chases its own gains.  The clipped rectangle is mapped to buffer coordinates (flipped under rotate180; a
+ *               window slot in the window view: plus the buffer corner irmv_window_map gives) and shrunk inward to even bounds:
+ *               a grid of 2 x 2 CFA cells.  Cell (i, j), counted from the shrunk region's corner in BUFFER coordinates, is
+ *               sampled iff i % step == 0 and j % step == 0; all four sites of a sampled cell count.  Rows 0, 1, 2: the R, G, B
+ *               sites by the engine's pattern in buffer coordinates; row 3: every sampled site
+ *   record      n[r] = the samples of row r (= the sum of hist[r]); rect = the clipped rectangle (RAW: after shrinking) back in
+ *               view-local result coordinates */
+#define IRMV_METER_VIEW 0
+#define IRMV_METER_RAW  1
+typedef struct irmv_meter_opts {
+    uint32_t struct_size;      /* = sizeof(irmv_meter_opts) */
+    int32_t domain;            /* IRMV_METER_* */
+    int32_t x0, y0, w, h;
+    int32_t step;              /* 1, 2 or 4 */
+    int32_t reserved[2];       /* must be 0 */
+} irmv_meter_opts;
+typedef struct irmv_frame_stats {
+    uint32_t hist[4][256];
+    uint32_t n[4];
+    int32_t rect[4];           /* x, y, w, h */
+    int32_t domain, step;      /* as metered; both 0 in the record of a step that ran with metering off */
+    int32_t reserved[2];       /* 0 (the record is a multiple of 16 bytes) */
+} irmv_frame_stats;
+/* Host only, no GPU: where a rectangle lies in `view` (IRMV_VIEW_*) of an engine of this configuration, with the window (if
+ * there is one) at (win_x0, win_y0) in result coordinates -- the function the engine and its kernels build from, like
+ * irmv_window_map and irmv_front_plan -- and every argument check: IRMV_ERR_ARG for a wrong struct_size, an unknown domain,
+ * IRMV_METER_RAW on IRMV_SRC_HWC8, a step other than 1, 2, 4, a negative size, exactly one of w, h zero, non-zero reserved
+ * fields; also for IRMV_VIEW_FRAME without a window in cfg and for a window not inside the frame. */
+typedef struct irmv_meter_map_t {
+    int32_t rect[4];           /* the record's rect */
+    int32_t region[4];         /* the same region x, y, w, h in the buffer that is read: the view's HWC frame as stored (pixels), or the
+                                  raw frame (CFA sites, all four even) */
+    int32_t phase[2];          /* VIEW: the first sampled column / row of the region, counted from its corner (non-zero under
+                                  rotate180 only: the sample grid hangs at the rectangle's corner in result coordinates); RAW: 0 */
+    int32_t grid[2];           /* sampled columns and rows: pixels, or 2 x 2 cells */
+    uint32_t n[4];             /* the record's n */
+    int32_t reserved[4];
+} irmv_meter_map_t;
+int irmv_meter_map(const irmv_engine_cfg *cfg, const irmv_meter_opts *opts, int view, int win_x0, int win_y0, irmv_meter_map_t *out);
+/* Host only: out = {rows of the view's frame per partial workgroup, the most partial workgroups per frame, LDS bytes of the
+ * histogram kernel, its threads, batch, the most per frame in a launch of more than `batch` frames, 0, 0}: a launch takes
+ * min(out[1] or out[5], ceil(view rows / out[0])) workgroups per frame. */
+int irmv_meter_limits(int32_t out[8]);
+/* On demand, like irmv_engine_render, on any engine whether metering is enabled or not: waits for what is in flight, loads the
+ * slot's current frame, launches once with THESE options, copies the record back and synchronizes.  Its scratch is made by the
+ * first metering call of the engine; it captures and drops no graph and leaves the slot's step record alone. */
+int irmv_engine_meter(irmv_engine *e, int slot, const irmv_meter_opts *opts, irmv_frame_stats *out);
+/* Metering inside the step.  The first call with opts != NULL waits for everything in flight, allocates the per-slot records
+ * (device, and pinned the way the irmv_det records are), the partials scratch and the device parameter record, and drops the
+ * captured graphs once: from then on every ordinary step carries one more op (kind "meter" in irmv_engine_ops, appended to its
+ * records; "frame_meter" in irmv_engine_profile) behind whatever produces the view's frame -- the demosaic, the crop -- or
+ * first.  Later calls wait for the steps in flight and rewrite the parameter record, which the kernels read when they run: a
+ * new rectangle, step or domain re-captures nothing, and neither does NULL, which sets "off" -- the kernel returns at once and
+ * the step's record is all zero.  Options are per engine; clipping is per slot view when the step runs.  Tiled steps
+ * (irmv_engine_submit_tiles) do not meter and leave the slots' records as they were; irmv_engine_run_post and the read-backs
+ * do not meter either.  An engine on which this is never called allocates, captures, launches and returns what it always did.
+ * IRMV_ERR_ARG (the checks of irmv_meter_map, before the GPU is touched) leaves the engine as it was.
+ * irmv_engine_get_metering: *on = 0 and opts untouched while off or never set. */
+int irmv_engine_set_metering(irmv_engine *e, const irmv_meter_opts *opts);
+int irmv_engine_get_metering(const irmv_engine *e, irmv_meter_opts *opts, int *on);
+/* The record of the slot's last ordinary step, valid after its wait; it reaches the host the way the slot's detections do.
+ * IRMV_ERR_ARG before the first irmv_engine_set_metering with opts != NULL. */
+int irmv_engine_frame_stats(irmv_engine *e, int slot, irmv_frame_stats *out);
+/* Host only: what a record says.  Sums that can pass 2^64 are taken in 128 bits.
+ * mean_q8: with S = sum v * hist[row][v] and N = sum hist[row][v] over lo <= v <= hi: *mean_q8 = (256 S + N / 2) / N, *count =
+ *   N; N == 0 (an empty range too): both 0.  IRMV_ERR_ARG: a row outside 0..3, lo or hi outside 0..255.
+ * percentile: the smallest v with cum(v) * den >= num * n[row], cum(v) = hist[row][0] + ... + hist[row][v].  IRMV_ERR_ARG:
+ *   n[row] == 0, den == 0, num > den.
+ * gray_world: IRMV_METER_RAW records only.  With S_c, N_c the sums of mean_q8 over [lo, hi] for c = R, G, B: gain_q8[1] = 256
+ *   and for c = R, B gain_q8[c] = min(1023, (256 S_G N_c + S_c N_G / 2) / (S_c N_G)).  IRMV_ERR_ARG where S_c N_G == 0 for
+ *   either, and gain_q8 is left alone.
+ * exposure_q8: with p that percentile, *ratio_q8 = clamp((256 target + p / 2) / max(p, 1), 16, 4096): the factor (Q8) by which
+ *   the exposure time should change.  The camera is the caller's.  IRMV_ERR_ARG: the percentile's, a target outside 0..255. */
+int irmv_stats_mean_q8(const irmv_frame_stats *s, int row, int lo, int hi, uint64_t *mean_q8, uint64_t *count);
+int irmv_stats_percentile(const irmv_frame_stats *s, int row, uint64_t num, uint64_t den, int *value);
+int irmv_stats_gray_world(const irmv_frame_stats *s, int lo, int hi, uint16_t gain_q8[3]);
+int irmv_stats_exposure_q8(const irmv_frame_stats *s, int row, uint64_t num, uint64_t den, int target, int *ratio_q8);
 
 /* ---- PnPSolver (include/irmv_detection/pnp_solver.hpp:15-23) ------------ */
 typedef struct irmv_pnp irmv_pnp;

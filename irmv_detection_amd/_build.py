@@ -33,6 +33,7 @@ SOURCES = [
     ("k_light_alt.hip", ["-ffp-contract=off"]),
     ("k_shuffle.hip", []),
     ("k_render.hip", []),
+    ("k_meter.hip", []),
     ("k_debug.hip", []),
     ("engine.cpp", ["-x", "hip"]),
     ("engine_graph.cpp", ["-x", "hip"]),
@@ -41,6 +42,7 @@ SOURCES = [
     ("engine_step.cpp", ["-x", "hip"]),
     ("engine_tiles.cpp", ["-x", "hip"]),
     ("engine_hooks.cpp", ["-x", "hip"]),
+    ("engine_meter.cpp", ["-x", "hip"]),
 ]
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs.  Left to itself the compiler gives kernels without a waves_per_eu
 # bound (fused C2f blocks, direct convs) AGPR accumulators and copies every one of them out with a v_accvgpr_read before the

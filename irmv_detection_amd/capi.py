@@ -181,6 +181,28 @@ class LightTrace(C.Structure):
                 ("recs", LightRec * LIGHT_MAX_CONTOURS)]
 
 
+METER_VIEW, METER_RAW = 0, 1
+METER_DOMAINS = {"view": METER_VIEW, "raw": METER_RAW}
+
+
+class MeterOpts(C.Structure):
+    """irmv_meter_opts (include/irmv_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("domain", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32),
+                ("h", C.c_int32), ("step", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class FrameStats(C.Structure):
+    """irmv_frame_stats (include/irmv_hip.h)."""
+    _fields_ = [("hist", C.c_uint32 * 256 * 4), ("n", C.c_uint32 * 4), ("rect", C.c_int32 * 4), ("domain", C.c_int32),
+                ("step", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class MeterMap(C.Structure):
+    """irmv_meter_map_t (include/irmv_hip.h)."""
+    _fields_ = [("rect", C.c_int32 * 4), ("region", C.c_int32 * 4), ("phase", C.c_int32 * 2), ("grid", C.c_int32 * 2),
+                ("n", C.c_uint32 * 4), ("reserved", C.c_int32 * 4)]
+
+
 DECLINED = 1    # irmv_engine_run_conv_candidate: no kernel runs that candidate
 RUN_POISON, RUN_POISON_ONLY = 1, 2   # ... its flags: NaN over the output it must write first (and launch nothing)
 
@@ -283,6 +305,16 @@ SYMBOLS = [
     ("irmv_engine_set_up", C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     ("irmv_engine_get_up", C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     ("irmv_engine_pose_alts", C.c_int, [_P, C.c_int, C.POINTER(PoseAlt), C.c_int, C.POINTER(C.c_int)]),
+    ("irmv_meter_map", C.c_int, [C.POINTER(EngineCfg), C.POINTER(MeterOpts), C.c_int, C.c_int, C.c_int, C.POINTER(MeterMap)]),
+    ("irmv_meter_limits", C.c_int, [C.POINTER(C.c_int32)]),
+    ("irmv_engine_meter", C.c_int, [_P, C.c_int, C.POINTER(MeterOpts), C.POINTER(FrameStats)]),
+    ("irmv_engine_set_metering", C.c_int, [_P, C.POINTER(MeterOpts)]),
+    ("irmv_engine_get_metering", C.c_int, [_P, C.POINTER(MeterOpts), C.POINTER(C.c_int)]),
+    ("irmv_engine_frame_stats", C.c_int, [_P, C.c_int, C.POINTER(FrameStats)]),
+    ("irmv_stats_mean_q8", C.c_int, [C.POINTER(FrameStats), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("irmv_stats_percentile", C.c_int, [C.POINTER(FrameStats), C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_int)]),
+    ("irmv_stats_gray_world", C.c_int, [C.POINTER(FrameStats), C.c_int, C.c_int, C.POINTER(C.c_uint16)]),
+    ("irmv_stats_exposure_q8", C.c_int, [C.POINTER(FrameStats), C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_int)]),
 ]
 
 _lib = None
@@ -438,6 +470,83 @@ def _geometry_cfg(src_size, net_size, net_height, resize_mode, rotate180, src_fo
     if window is not None:
         cfg.win_width, cfg.win_height = int(window[0]), int(window[1])
     return cfg
+
+
+def meter_opts(domain=METER_VIEW, rect=None, step=1) -> MeterOpts:
+    """An irmv_meter_opts (no check: the library's are the ones under test).  domain: "view" / "raw" or IRMV_METER_*;
+    rect: (x0, y0, w, h) in view-local result coordinates, None = the whole view."""
+    o = MeterOpts()
+    o.struct_size = C.sizeof(MeterOpts)
+    o.domain = METER_DOMAINS[domain] if isinstance(domain, str) else int(domain)
+    if rect is not None:
+        o.x0, o.y0, o.w, o.h = (int(v) for v in rect)
+    o.step = int(step)
+    return o
+
+
+def stats_dict(s: FrameStats) -> dict:
+    """An irmv_frame_stats as metering.meter returns it: hist uint32 [4][256], n uint32 [4], rect, domain, step."""
+    import numpy as np
+    return dict(hist=np.ctypeslib.as_array(s.hist).astype(np.uint32).reshape(4, 256).copy(), n=np.array(list(s.n), np.uint32),
+                rect=tuple(s.rect), domain=int(s.domain), step=int(s.step))
+
+
+def stats_struct(stats) -> FrameStats:
+    """The irmv_frame_stats of a record dict (metering.meter, stats_dict)."""
+    import numpy as np
+    s = FrameStats()
+    h = np.ascontiguousarray(np.asarray(stats["hist"], np.uint32).reshape(4, 256))
+    C.memmove(s.hist, h.ctypes.data, h.nbytes)
+    for i in range(4):
+        s.n[i] = int(stats["n"][i])
+        s.rect[i] = int(stats.get("rect", (0, 0, 0, 0))[i])
+    s.domain, s.step = int(stats.get("domain", 0)), int(stats.get("step", 1))
+    return s
+
+
+def meter_map(src_size, opts: MeterOpts, view=0, window=None, win_xy=(0, 0), rotate180=True, src_format=SRC_HWC8, net_size=640, net_height=None) -> dict:
+    """Where a metering rectangle lies (host only, irmv_meter_map): the record's rect, the region in the buffer that is read,
+    the sample grid and n[4], as the engine's kernels compute them; raises IrmvError where an argument is refused."""
+    cfg = _geometry_cfg(src_size, net_size, net_height, RESIZE_STRETCH, rotate180, src_format, window)
+    m = MeterMap()
+    check(load().irmv_meter_map(C.byref(cfg), C.byref(opts), int(view), int(win_xy[0]), int(win_xy[1]), C.byref(m)))
+    return dict(rect=tuple(m.rect), region=tuple(m.region), phase=tuple(m.phase), grid=tuple(m.grid), n=tuple(m.n))
+
+
+METER_LIMIT_NAMES = ("rows_per_block", "blocks_max", "lds_bytes", "threads", "batch_frames", "blocks_batch")
+
+
+def meter_limits() -> dict:
+    """The metering kernel's launch shape as compiled (host only, irmv_meter_limits)."""
+    v = (C.c_int32 * 8)()
+    check(load().irmv_meter_limits(v))
+    return {k: int(v[i]) for i, k in enumerate(METER_LIMIT_NAMES)}
+
+
+def stats_mean_q8(stats, row, lo=0, hi=255):
+    """irmv_stats_mean_q8 -> (mean_q8, count)."""
+    m, n = C.c_uint64(0), C.c_uint64(0)
+    check(load().irmv_stats_mean_q8(C.byref(stats_struct(stats)), int(row), int(lo), int(hi), C.byref(m), C.byref(n)))
+    return m.value, n.value
+
+
+def stats_percentile(stats, row, num, den) -> int:
+    v = C.c_int(0)
+    check(load().irmv_stats_percentile(C.byref(stats_struct(stats)), int(row), int(num), int(den), C.byref(v)))
+    return v.value
+
+
+def stats_gray_world(stats, lo=8, hi=247):
+    """irmv_stats_gray_world -> (gain_R, 256, gain_B), Q8."""
+    g = (C.c_uint16 * 3)()
+    check(load().irmv_stats_gray_world(C.byref(stats_struct(stats)), int(lo), int(hi), g))
+    return tuple(g)
+
+
+def stats_exposure_q8(stats, row, num, den, target) -> int:
+    v = C.c_int(0)
+    check(load().irmv_stats_exposure_q8(C.byref(stats_struct(stats)), int(row), int(num), int(den), int(target), C.byref(v)))
+    return v.value
 
 
 def window_map(src_size, window, x0, y0, rotate180=True, camera_matrix=None, net_size=640, net_height=None) -> dict:

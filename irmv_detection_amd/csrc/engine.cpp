@@ -98,6 +98,7 @@ irmv_engine::~irmv_engine()
     if (dets_host) (void)hipHostFree(dets_host);
     if (fout_host) (void)hipHostFree(fout_host);
     if (alts_host) (void)hipHostFree(alts_host);
+    if (meter_stats_host) (void)hipHostFree(meter_stats_host);
     if (light_dets_host) (void)hipHostFree(light_dets_host);
     for (auto &kv : tile_merges)
         if (kv.second.out_host) (void)hipHostFree(kv.second.out_host);
@@ -311,6 +312,7 @@ static EngineSwitches read_switches()
     s.sparse_head = !off("IRMV_SPARSE_HEAD"); s.sparse_branch = !off("IRMV_SPARSE_BRANCH");
     s.zero_copy_results = !off("IRMV_ZERO_COPY_RESULTS"); s.post_keys_only = is1("IRMV_POST_KEYS_ONLY");
     s.nms_classwalk = !off("IRMV_NMS_CLASSWALK");
+    s.meter_merge = !off("IRMV_METER_MERGE");
     s.nms_prefilter = off("IRMV_NMS_PREFILTER") ? 0 : 1;
     if (const char *pe = getenv("IRMV_NMS_PRE")) { int hi = 0, lo = 0; if (sscanf(pe, "%d,%d", &hi, &lo) == 2 && hi >= 64 && hi <= 512 && lo >= 32 && lo < hi) s.nms_prefilter = hi | (lo << 16); }
     if (const char *st = getenv("IRMV_NMS_STAMPS")) { s.nms_stamps = true; s.nms_stamps_slots = atoi(st); }
@@ -346,7 +348,7 @@ int irmv::check_letterbox(const irmv_engine_cfg &c)
 
 // The caller's configuration at this library's size (an older caller's prefix, the appended fields at their defaults),
 // and the checks of everything the front's geometry follows from.  No GPU call.
-static int resolve_cfg(const irmv_engine_cfg *cfg_in, irmv_engine_cfg *full)
+int irmv::resolve_cfg(const irmv_engine_cfg *cfg_in, irmv_engine_cfg *full)
 {
     const size_t sz = cfg_in->struct_size;
     if (sz != sizeof(irmv_engine_cfg) && sz != kCfgSizeV1 && sz != kCfgSizeV2) return fail(IRMV_ERR_ARG, "irmv_engine_cfg size mismatch");
@@ -533,7 +535,7 @@ extern "C" size_t irmv_engine_src_bytes(const irmv_engine *e) { return e ? e->sr
 // ---- tracking window ----------------------------------------------------------------
 // A window at (x0, y0) in result coordinates: where it lies in the buffer, the band of full-width rows it covers, and the
 // principal point its pixels are seen with.  The one place this arithmetic lives (irmv_window_map exports it).
-static int window_map(int full_w, int full_h, int win_w, int win_h, int rotate180, const double K[9], int x0, int y0, irmv_window_map_t *m)
+int irmv::window_map(int full_w, int full_h, int win_w, int win_h, int rotate180, const double K[9], int x0, int y0, irmv_window_map_t *m)
 {
     if (x0 < 0 || y0 < 0 || x0 > full_w - win_w || y0 > full_h - win_h) return fail(IRMV_ERR_ARG, "the window does not lie inside the frame");
     memset(m, 0, sizeof *m);

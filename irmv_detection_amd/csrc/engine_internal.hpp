@@ -10,6 +10,7 @@
 //   engine_tiles.cpp  tiled search: its checks, the merge's device state and arguments, the tiled submit's call of submit_group,
 //                     the merge hook, the merged results and the merge parameters
 //   engine_hooks.cpp  read-backs, debug images, debug_*, LDS fill / probe, conv and op test hooks, the profiler, the light trace
+//   engine_meter.cpp  frame metering: its checks and map, the record's host helpers, the on-demand call, the step's op
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -109,10 +110,11 @@ struct EngineSwitches {
     bool nms_classwalk = true;     // IRMV_NMS_CLASSWALK=0
     int nms_prefilter = 1;         // PostArgs::prefilter.  IRMV_NMS_PREFILTER=0: crowded frames sort and mask every candidate (round-3 behaviour; bit-identical);
                                    // IRMV_NMS_PRE=<hi>,<lo> (experiment: size of the head of the list): hi | lo << 16
+    bool meter_merge = true;       // frame_meter_kernel adds a lane-group of equal pixels once with its sample count (IRMV_METER_MERGE=0: one LDS add per sample; same bits)
     bool nms_stamps = false; int nms_stamps_slots = 0;   // IRMV_NMS_STAMPS=<n>: the NMS kernel stamps its phases, the destructor prints the first n slots' (at least four)
 };
 
-enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_DEMOSAIC, OP_CROP };
+enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_DEMOSAIC, OP_CROP, OP_METER };
 
 struct Op {
     OpKind kind;
@@ -349,6 +351,18 @@ struct irmv_engine {
     RenderFont *render_font = nullptr;
     uint8_t *render_out = nullptr;
     std::vector<RenderMark> render_marks_host;
+    // Frame metering (irmv_engine_meter / irmv_engine_set_metering): nothing below exists until the first metering call.  That
+    // call makes the scratch: the partials slab, the two parameter records -- [0] the step's, [1] the on-demand call's -- and the
+    // device records, [num_slots] the steps' and one more for the on-demand call.  The first set_metering with options adds the
+    // pinned records (travelling exactly as the DevDet records do: meter_args, copy_out), the op (meter_op, the last of `ops`)
+    // and its launch in every built view's step plans, and drops the captured graphs once.
+    uint32_t *meter_slab = nullptr;          // [S][kMeterBlocksMax][4][256]
+    MeterParams *meter_params_dev = nullptr; // [2]
+    MeterStats *meter_stats_dev = nullptr;   // [S + 1]
+    MeterStats *meter_stats_host = nullptr, *meter_stats_host_dev = nullptr;   // [S] pinned, and its device view
+    int meter_op = -1;                       // >= 0: the steps meter
+    bool meter_on = false;                   // the options in force are not "off"
+    irmv_meter_opts meter_opts{};
     float *boxes = nullptr;
     unsigned long long *keys = nullptr;
     DevDet *dets_dev = nullptr, *dets_host = nullptr, *dets_host_dev = nullptr;       // *_host_dev: device view of the pinned buffer
@@ -402,6 +416,8 @@ int write_isp_table(irmv_engine *e);
 int write_class_table(irmv_engine *e);
 void drop_graphs(irmv_engine *e, bool keep_post);
 int check_window_slot(const irmv_engine *e, int slot, const char *who);
+int resolve_cfg(const irmv_engine_cfg *cfg_in, irmv_engine_cfg *full);
+int window_map(int full_w, int full_h, int win_w, int win_h, int rotate180, const double K[9], int x0, int y0, irmv_window_map_t *m);
 // engine_graph.cpp
 int dev_alloc(irmv_engine *e, void **p, size_t bytes);
 int load_blob(irmv_engine *e);
@@ -418,6 +434,7 @@ int choose_sync_launch(irmv_engine *e);
 // engine_plan.cpp
 void finalize_head_fusion(irmv_engine *e);
 void build_step_plans(irmv_engine *e, View &v);
+void add_meter_op(irmv_engine *e);
 // engine_step.cpp
 void fill_conv_args(const irmv_engine *e, const Op &op, int first, int count, ConvArgs &a, bool fused = false);
 int slots_view(const irmv_engine *e, int first, int count, int *view = nullptr);
@@ -429,6 +446,7 @@ int enqueue_step(irmv_engine *e, const Step &s, hipStream_t st, int reps = 1, co
 void note_submit_windows(irmv_engine *e, int first, int count);
 void mark_stepped(irmv_engine *e, int first, int count);
 int copy_out(irmv_engine *e, int first, int count, hipStream_t st = nullptr);
+MeterArgs meter_args(const irmv_engine *e, const View &v, int first, const MeterParams *params, MeterStats *out);
 int check_range(const irmv_engine *e, int first, int count);
 int load_frame(irmv_engine *e, int slot, hipStream_t st);
 void det_pose(const DevDet &d, bool shift, float ox, float oy, irmv_det &o);

@@ -102,6 +102,34 @@ static void sparse_head_plan(irmv_engine *e, std::vector<Launch> &plan)
     plan.swap(out);
 }
 
+// Frame metering (e->meter_op >= 0): the steps of view v launch the meter op behind whatever produces the view's frame -- the
+// demosaic, the crop, both at the head of the plan -- or first.
+static void add_meter_launch(const irmv_engine *e, View &v)
+{
+    for (int k : {(int)STEP_BATCH, (int)STEP_ONE}) {
+        std::vector<Launch> &plan = v.plans[k];
+        size_t at = 0;
+        for (size_t i = 0; i < plan.size(); i++)
+            if (e->ops[plan[i].op].kind == OP_DEMOSAIC || e->ops[plan[i].op].kind == OP_CROP) at = i + 1;
+        const Op &op = e->ops[e->meter_op];
+        Launch l; l.op = e->meter_op;
+        l.name = op.kname; l.layer = op.layer;
+        l.bytes = (double)v.frame_bytes;   // (the VIEW domain at step 1 on the whole view: the most it reads)
+        plan.insert(plan.begin() + at, l);
+    }
+}
+
+// The first irmv_engine_set_metering with options: the op, appended to e->ops, and its launch in the step plans of every view
+// built so far (a view built later gets it from build_step_plans).  Nothing of the engine is in flight.
+void irmv::add_meter_op(irmv_engine *e)
+{
+    Op op; op.kind = OP_METER; op.layer = "frame_meter"; snprintf(op.kname, sizeof op.kname, "frame_meter");
+    e->ops.push_back(op);
+    e->meter_op = (int)e->ops.size() - 1;
+    for (View &v : e->views)
+        if (v.built) add_meter_launch(e, v);
+}
+
 // The one place that decides which ops of e->ops a step of each kind launches in view v, and how.  The views differ in front
 // of model.1's output only: whether the window is cut out first, and whether the front runs fused or as its three layers.
 void irmv::build_step_plans(irmv_engine *e, View &v)
@@ -114,6 +142,7 @@ void irmv::build_step_plans(irmv_engine *e, View &v)
         for (int i = 0; i < (int)e->ops.size(); i++) {
             const Op &op = e->ops[i];
             if (op.kind == OP_FRONT) continue;   // (launched where model.1.conv stands, below)
+            if (op.kind == OP_METER) continue;   // (added behind the loop)
             if (op.kind == OP_CROP && !v.crop) continue;
             const bool away = is_front_layer(i) ? v.fused_front : op.fused_away;   // the layers a fused kernel covers in this view
             if (post && op.kind != OP_NMS && op.kind != OP_LIGHT && op.kind != OP_SCAN) continue;
@@ -170,4 +199,5 @@ void irmv::build_step_plans(irmv_engine *e, View &v)
         }
         if (step && e->sparse_head) sparse_head_plan(e, v.plans[k]);
     }
+    if (e->meter_op >= 0) add_meter_launch(e, v);
 }

@@ -149,6 +149,31 @@ static CropArgs crop_args(const irmv_engine *e, const Step &s)
 
 static void launch_crop(const irmv_engine *e, const Step &s, hipStream_t st) { launch_window_crop(crop_args(e, s), s.count, st); }
 
+// Frame metering of slots from `first` on in view v: the options at `params`, frame b's record to out[b].
+MeterArgs irmv::meter_args(const irmv_engine *e, const View &v, int first, const MeterParams *params, MeterStats *out)
+{
+    MeterArgs a{};
+    a.frames = v.frames; a.frame_bytes = v.frame_bytes;
+    a.raw = e->raw_dev; a.raw_bytes = e->src_bytes;
+    a.params = params;
+    a.win = v.crop ? e->win_dev : nullptr;
+    a.slab = e->meter_slab;
+    a.out = out;
+    a.first = first;
+    a.vw = v.src_w; a.vh = v.src_h; a.raw_w = e->full_w; a.raw_h = e->full_h;
+    a.rotate180 = e->cfg.rotate180 ? 1 : 0;
+    a.ry = e->bayer.ry; a.rx = e->bayer.rx;
+    return a;
+}
+
+// A step's metering: the records go where its DevDet records go (post_args).  A tiled step does not meter.
+static void launch_meter(const irmv_engine *e, const View &v, const Step &s, hipStream_t st)
+{
+    if (s.tiled()) return;
+    MeterStats *out = (e->zero_copy_results ? e->meter_stats_host_dev : e->meter_stats_dev) + s.first;
+    launch_frame_meter(meter_args(e, v, s.first, e->meter_params_dev, out), s.count, e->sw.meter_merge, st);
+}
+
 static PreArgs pre_args(const irmv_engine *e, const View &v, const Op &op, int first)
 {
     PreArgs a;
@@ -322,6 +347,7 @@ int irmv::launch_op(irmv_engine *e, const View &v, const Launch &l, const Step &
     switch (op.kind) {
     case OP_DEMOSAIC: launch_bayer(e, t.bayer_first(), t.bayer_count(), s); break;
     case OP_CROP: launch_crop(e, t, s); break;
+    case OP_METER: launch_meter(e, v, t, s); break;
     case OP_PRE: launch_preprocess(pre_args(e, v, op, first), count, s); break;
     case OP_FRONT: if (!launch_front(front_args(e, v, op, first), count, s)) return fail(IRMV_ERR_HIP, "fused front kernel: LDS request refused"); break;
     case OP_C2F2: launch_c2f2(c2f2_args(e, op, first), count, s); break;
@@ -455,9 +481,11 @@ int irmv::enqueue_upload(irmv_engine *e, const Upload &u, hipStream_t st)
 }
 
 // the device records of slots [first, first + count) -> their pinned twins (every step of an engine without zero-copy results;
-// tiled steps of any engine)
-static int copy_out_dev(irmv_engine *e, int first, int count, hipStream_t st)
+// tiled steps of any engine -- which do not meter: stats = false)
+static int copy_out_dev(irmv_engine *e, int first, int count, hipStream_t st, bool stats)
 {
+    if (stats && e->meter_op >= 0)
+        HIP_TRY(hipMemcpyAsync(e->meter_stats_host + first, e->meter_stats_dev + first, (size_t)count * sizeof(MeterStats), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(e->dets_host + (size_t)first * e->cfg.max_det, e->dets_dev + (size_t)first * e->cfg.max_det,
                            (size_t)count * e->cfg.max_det * sizeof(DevDet), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(e->fout_host + first, e->fout_dev + first, (size_t)count * sizeof(DevFrameOut),
@@ -471,7 +499,7 @@ static int copy_out_dev(irmv_engine *e, int first, int count, hipStream_t st)
 int irmv::copy_out(irmv_engine *e, int first, int count, hipStream_t st)
 {
     if (e->zero_copy_results) return IRMV_OK;   // the kernel has already written the pinned records
-    return copy_out_dev(e, first, count, st ? st : e->stream);
+    return copy_out_dev(e, first, count, st ? st : e->stream, true);
 }
 
 int irmv::check_range(const irmv_engine *e, int first, int count)
@@ -582,7 +610,7 @@ int irmv::submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_t
     mark_stepped(e, f, c);
     if (tiled) {
         const irmv_engine::TileMerge &tm = e->tile_merges.at(f);
-        TRY(copy_out_dev(e, f, c, st));
+        TRY(copy_out_dev(e, f, c, st, false));
         HIP_TRY(hipMemcpyAsync(tm.out_host, tm.out_dev, sizeof(TileOut), hipMemcpyDeviceToHost, st));
     } else {
         TRY(copy_out(e, f, c, st));

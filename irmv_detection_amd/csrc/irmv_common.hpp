@@ -593,6 +593,77 @@ struct RenderArgs {
 constexpr int kRenderTileW = 64, kRenderTileH = 16;   // output pixels per workgroup (256 threads, 4 pixels of a row each)
 void launch_render_view(const RenderArgs &a, hipStream_t s);
 
+// ---- frame metering (k_meter.hip; include/irmv_hip.h, "frame metering") -------------------------------------------------
+constexpr int kMeterView = 0, kMeterRaw = 1;   // == IRMV_METER_*
+// The options as the kernels read them from device memory when they run (a captured graph holds the address): on = 0 is
+// "off" -- the histogram kernel returns at once and the record is all zero.
+struct MeterParams { int32_t on, domain, x0, y0, w, h, step, pad_; };
+struct MeterStats {           // == irmv_frame_stats
+    uint32_t hist[4][256];
+    uint32_t n[4];
+    int32_t rect[4];
+    int32_t domain, step, pad_[2];
+};
+// Where a rectangle lies.  rect: the clipped (RAW: shrunk) rectangle x, y, w, h in view-local result coordinates; bx, by,
+// bw, bh: the same region in the coordinates of the buffer that is read -- the view's HWC frame (pixels), or the raw frame
+// (CFA sites; all four even); px, py: VIEW: offset in the region of its first sampled column / row (the sample grid hangs at
+// the rectangle's corner in RESULT coordinates, which under rotate180 is the region's far corner); nx, ny: sampled columns
+// and rows (RAW: 2 x 2 cells).  Everything 0 where nothing is left.
+struct MeterGeom { int32_t rect[4], bx, by, bw, bh, px, py, nx, ny; };
+__host__ __device__ inline int meter_step(int step) { return step == 2 || step == 4 ? step : 1; }
+// THE geometry: irmv_meter_map returns it, both kernels compute it per frame.  vw x vh: the view's frame; (cx, cy): the
+// view's corner inside the raw frame, buffer coordinates (a window slot in the window view; else 0, 0).
+__host__ __device__ inline MeterGeom meter_geometry(const MeterParams &p, int vw, int vh, int rot, int cx, int cy)
+{
+    MeterGeom g{};
+    long long x0 = p.x0, y0 = p.y0, x1 = x0 + p.w, y1 = y0 + p.h;
+    if (p.w == 0 && p.h == 0) { x0 = 0; y0 = 0; x1 = vw; y1 = vh; }
+    x0 = x0 > 0 ? x0 : 0; y0 = y0 > 0 ? y0 : 0;
+    x1 = x1 < vw ? x1 : vw; y1 = y1 < vh ? y1 : vh;
+    if (x1 <= x0 || y1 <= y0) return g;
+    const int st = meter_step(p.step);
+    const int rw = (int)(x1 - x0), rh = (int)(y1 - y0);
+    const int bx = rot ? vw - (int)x1 : (int)x0, by = rot ? vh - (int)y1 : (int)y0;   // in the view's frame as stored
+    if (p.domain != kMeterRaw) {
+        g.rect[0] = (int)x0; g.rect[1] = (int)y0; g.rect[2] = rw; g.rect[3] = rh;
+        g.bx = bx; g.by = by; g.bw = rw; g.bh = rh;
+        g.px = rot ? (rw - 1) % st : 0; g.py = rot ? (rh - 1) % st : 0;
+        g.nx = (rw + st - 1) / st; g.ny = (rh + st - 1) / st;
+        return g;
+    }
+    const int ex0 = (bx + cx + 1) & ~1, ex1 = (bx + cx + rw) & ~1, ey0 = (by + cy + 1) & ~1, ey1 = (by + cy + rh) & ~1;
+    if (ex1 <= ex0 || ey1 <= ey0) return g;
+    g.bx = ex0; g.by = ey0; g.bw = ex1 - ex0; g.bh = ey1 - ey0;
+    g.nx = (g.bw / 2 + st - 1) / st; g.ny = (g.bh / 2 + st - 1) / st;
+    const int lx = ex0 - cx, ly = ey0 - cy;   // back into the view's frame, then into result coordinates
+    g.rect[0] = rot ? vw - (lx + g.bw) : lx; g.rect[1] = rot ? vh - (ly + g.bh) : ly; g.rect[2] = g.bw; g.rect[3] = g.bh;
+    return g;
+}
+constexpr int kMeterWaves = 8, kMeterThreads = 64 * kMeterWaves;
+constexpr int kMeterRowsPerBlock = 8;    // a launch takes one partial workgroup per this many rows of the view's frame ...
+constexpr int kMeterBlocksMax = 128;     // ... up to this many per frame (one frame alone is latency-bound: it wants every CU) ...
+constexpr int kMeterBatchFrames = 4, kMeterBlocksBatch = 32;   // ... and, in a launch of more than 4 frames, up to 32 (the slab's traffic)
+constexpr int kMeterLdsBytes = kMeterWaves * 4 * 256 * 4;   // the waves' private [4][256] histograms
+inline int meter_blocks(int view_rows, int batch)
+{
+    const int b = (view_rows + kMeterRowsPerBlock - 1) / kMeterRowsPerBlock, cap = batch > kMeterBatchFrames ? kMeterBlocksBatch : kMeterBlocksMax;
+    return b < 1 ? 1 : (b > cap ? cap : b);
+}
+struct MeterArgs {
+    const uint8_t *frames;    // [num_slots][vh][vw][3]: the view's device frames, un-rotated
+    size_t frame_bytes;
+    const uint8_t *raw;       // [num_slots][raw_h][raw_w] raw CFA frames; nullptr: not a Bayer engine (RAW then meters nothing)
+    size_t raw_bytes;
+    const MeterParams *params;
+    const int2 *win;          // [num_slots] the view's corner in the raw frame (CropArgs::win), read when the kernel runs; nullptr: (0, 0)
+    uint32_t *slab;           // [num_slots][kMeterBlocksMax][4][256] partial histograms, rewritten by every launch
+    MeterStats *out;          // [batch]: frame b's record, device or pinned
+    int first;                // frame b is slot first + b
+    int vw, vh, raw_w, raw_h, rotate180, ry, rx;   // ry, rx: parities of the R sites (BayerArgs)
+};
+// histogram kernel, then the sum of its partials; fast: a lane-group of equal pixels is added once with its sample count
+void launch_frame_meter(const MeterArgs &a, int batch, bool fast, hipStream_t s);
+
 // ---- LDS fill / probe (k_debug.hip; test hooks irmv_debug_lds_fill / irmv_debug_lds_probe) ----------------------------
 constexpr int kDebugLdsWords = 160 * 1024 / 4;   // the largest LDS allocation of one workgroup on gfx950
 int debug_lds_workgroups(int cus);               // several per CU

@@ -481,6 +481,37 @@ class YoloEngine:
         capi.check(self._L.irmv_engine_get_bayer_isp(self._h, g, lut.ctypes.data_as(C.POINTER(C.c_uint8))))
         return tuple(g), lut
 
+    def set_metering(self, domain="view", rect=None, step: int = 1) -> None:
+        """Frame metering inside the step (irmv_engine_set_metering): from the next submit on every ordinary step also computes
+        four 256-bin histograms of `rect` -- (x0, y0, w, h) in view-local result coordinates, None = the whole view -- sampled
+        every `step` (1, 2, 4) pixels: domain "view" = the view's frame (three channels and gray), "raw" = a Bayer engine's CFA
+        frame in front of gains and LUT (R, G, B sites and all).  set_metering(None) switches it off again (records all zero).
+        The first enabling call re-captures the steps once; every later one, None included, only rewrites device data.
+        irmv_detection_amd.metering is the host reference."""
+        if domain is None:
+            capi.check(self._L.irmv_engine_set_metering(self._h, None))
+            return
+        if domain not in capi.METER_DOMAINS:
+            raise ValueError(f"domain must be None or one of {sorted(capi.METER_DOMAINS)}, not {domain!r}")
+        o = capi.meter_opts(domain, rect, step)
+        capi.check(self._L.irmv_engine_set_metering(self._h, C.byref(o)))
+
+    def frame_stats(self, slot: Optional[int] = None) -> dict:
+        """The metering record of the slot's last ordinary step (after its wait): hist uint32 [4][256], n uint32 [4], rect
+        (x, y, w, h: the clipped rectangle), domain, step (irmv_engine_frame_stats)."""
+        s = capi.FrameStats()
+        capi.check(self._L.irmv_engine_frame_stats(self._h, self.slot if slot is None else slot, C.byref(s)))
+        return capi.stats_dict(s)
+
+    def meter(self, domain="view", rect=None, step: int = 1, slot: Optional[int] = None) -> dict:
+        """Meter the slot's current frame on demand (irmv_engine_meter), on any engine: the record as frame_stats returns it."""
+        if domain not in capi.METER_DOMAINS:
+            raise ValueError(f"domain must be one of {sorted(capi.METER_DOMAINS)}, not {domain!r}")
+        o = capi.meter_opts(domain, rect, step)
+        s = capi.FrameStats()
+        capi.check(self._L.irmv_engine_meter(self._h, self.slot if slot is None else slot, C.byref(o), C.byref(s)))
+        return capi.stats_dict(s)
+
     def set_class_policy(self, score_thr=None, plate=None) -> None:
         """Per-class score thresholds and plate models, from the next submit on (irmv_engine_set_class_policy): each a
         scalar or a per-class sequence; a threshold >= 1 switches the class off where candidates are emitted.  None keeps

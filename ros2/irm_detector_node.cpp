@@ -38,6 +38,16 @@ public:
     p.refine_roi_margin = node_->declare_parameter("refine.roi_margin", 4.0);
     p.debug = node_->declare_parameter("debug", false);                   // reference :90-95; live through the callback below (:380-381)
     p.debug_scale = int(node_->declare_parameter("debug_scale", 1));      // 1, 2 or 4: the debug images at full, half or quarter size
+    // frame metering (IrmDetectorCore::Params::metering): "" off, "view" or "raw" on the rectangle {x0, y0, w, h} ({0, 0, 0, 0}: the
+    // whole view) every metering_step pixels; awb_period (live through the callback below): gray-world white balance every n-th
+    // frame, for a Bayer src_format with "raw" metering
+    p.src_format = int(node_->declare_parameter("src_format", 0));        // IRMV_SRC_*: 0 HWC, 1..4 the Bayer patterns
+    const std::string metering = node_->declare_parameter("metering", std::string(""));
+    const auto mr = node_->declare_parameter("metering_rect", std::vector<int64_t>{0, 0, 0, 0});
+    const int metering_step = int(node_->declare_parameter("metering_step", 1));
+    if (!metering.empty() && mr.size() == 4)
+      p.metering = YoloEngine::meter_opts(metering == "raw" ? IRMV_METER_RAW : IRMV_METER_VIEW, cv::Point(int(mr[0]), int(mr[1])), cv::Size(int(mr[2]), int(mr[3])), metering_step);
+    p.awb_period = int(node_->declare_parameter("awb_period", 0));
     const auto ns = node_->declare_parameter("net_input_size", std::vector<int64_t>{0, 0});   // {width, height}; {0, 0}: square default
     if (ns.size() == 2) p.net_input_size = cv::Size(int(ns[0]), int(ns[1]));
     const std::string model = node_->declare_parameter("model_path", std::string("models/yolov7.onnx"));
