@@ -674,6 +674,14 @@ int irmv_engine_run_conv_candidate(irmv_engine *e, int op, int tune_count, int c
 /* The raw storage (fp16 bits at the activation scale, or fp32) of a tensor's slots [first, first + count); bytes must
  * equal its size.  Unlike irmv_engine_read_tap it never recomputes a tensor a step keeps on chip. */
 int irmv_engine_read_tensor(irmv_engine *e, const char *name, int first_slot, int count, void *dst, size_t bytes);
+/* The mirror of irmv_engine_read_tensor (tests/test_gpu_act_craft.py): copy raw storage (fp16 bits at the activation scale, or
+ * fp32) over a tensor's slots [first, first + count); bytes must equal their size (IRMV_ERR_ARG otherwise).  It waits for the
+ * engine and first brings the slots to the dense state a read-back leaves (the head rows a sparse step did not store, the
+ * gated box branches); the slots stay marked as not stale, so a later irmv_engine_read_tensor, read_head or run_post never
+ * recomputes over what was written.  irmv_engine_read_tap and irmv_engine_read_input of a tensor a step keeps on chip STILL
+ * recompute it (and every other such tensor of the slot) from the slot's frame: read what was written with
+ * irmv_engine_read_tensor only. */
+int irmv_engine_write_tensor(irmv_engine *e, const char *name, int first_slot, int count, const void *src, size_t bytes);
 
 /* ---- per-op test hooks (tests/test_gpu_graph_ops.py) ------------------------
  * Every op of the engine's graph, of any kind; the non-conv layer ops run one at a time on a slot range. */
@@ -691,10 +699,25 @@ typedef struct irmv_graph_op {
 
 /* One record per op of the graph, in step order; *n = their number (records beyond cap are not written). */
 int irmv_engine_ops(irmv_engine *e, irmv_graph_op *ops, int cap, int *n);
-/* Run the engine's own kernel of a conv0, pool, dw or shuffle op on slots [first, first + count), as a step of that
- * count launches it, and synchronize.  flags: IRMV_RUN_POISON / IRMV_RUN_POISON_ONLY over the op's output channels on
- * those slots (the pool: channels [C, 4C) of its tensor; [0, C) is its input).  IRMV_ERR_ARG for any other kind. */
+/* Run the engine's own kernel of a conv0, pool, dw or shuffle op, or of a fused c2f2, c2f32, bneck or kpt3 op, on slots
+ * [first, first + count), as a step of that count launches it, and synchronize.  A fused op runs as a plain launch: kpt3
+ * without the sparse head's gate, every head row written.  flags: IRMV_RUN_POISON / IRMV_RUN_POISON_ONLY over the op's
+ * output channels on those slots (the pool: channels [C, 4C) of its tensor; [0, C) is its input; a fused op: every range
+ * irmv_engine_op_io lists as written).  IRMV_ERR_ARG for any other kind. */
 int irmv_engine_run_op(irmv_engine *e, int op, int first_slot, int count, uint32_t flags);
+/* What a fused op (c2f2, c2f32, bneck, kpt3) stands for: the conv ops whose layers it computes, in the order a step without
+ * it runs them, every channel range its launch writes, and every channel range it reads (a residual included; a segment
+ * with shift 1 is read as its nearest 2x upsample).  Nothing else of any activation tensor reaches its output.  No conv or
+ * fused kernel reads channels beyond a segment's C: K positions past Cin are clamped onto the segment's own last channels.
+ * IRMV_ERR_ARG for an op of any other kind. */
+typedef struct irmv_op_io {
+    int32_t op;
+    int32_t n_sub, sub[4];      /* engine op indices of its conv ops (records of irmv_engine_conv_ops) */
+    int32_t n_writes, n_reads;
+    irmv_conv_seg writes[2], reads[2];
+    int32_t reserved;
+} irmv_op_io;
+int irmv_engine_op_io(irmv_engine *e, int op, irmv_op_io *io);
 /* ---- light-extraction test hook (tests/test_gpu_light_shapes.py) ----------------
  * What light_extract_kernel saw in one box, stage by stage. */
 #define IRMV_LIGHT_MAX_CONTOURS 1024   /* contours per box; more: armor_valid = -1 */

@@ -145,6 +145,12 @@ class GraphOp(C.Structure):
                 ("fused_away", C.c_int32), ("reserved", C.c_int32)]
 
 
+class OpIo(C.Structure):
+    """irmv_op_io (irmv_engine_op_io): the conv ops a fused op stands for, what its launch writes and reads."""
+    _fields_ = [("op", C.c_int32), ("n_sub", C.c_int32), ("sub", C.c_int32 * 4), ("n_writes", C.c_int32), ("n_reads", C.c_int32),
+                ("writes", ConvSeg * 2), ("reads", ConvSeg * 2), ("reserved", C.c_int32)]
+
+
 LIGHT_MAX_CONTOURS, LIGHT_POINTS_CAP = 1024, 4096   # array bounds of irmv_light_trace (the kernel's limits: light_limits())
 
 
@@ -287,7 +293,9 @@ SYMBOLS = [
     ("irmv_engine_conv_candidates", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(ConvCand), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_engine_run_conv_candidate", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]),
     ("irmv_engine_read_tensor", C.c_int, [_P, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    ("irmv_engine_write_tensor", C.c_int, [_P, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     ("irmv_engine_ops", C.c_int, [_P, C.POINTER(GraphOp), C.c_int, C.POINTER(C.c_int)]),
+    ("irmv_engine_op_io", C.c_int, [_P, C.c_int, C.POINTER(OpIo)]),
     ("irmv_engine_run_op", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint32]),
     ("irmv_sppf_slab", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     ("irmv_front_plan", C.c_int, [C.POINTER(EngineCfg), C.POINTER(FrontPlan)]),

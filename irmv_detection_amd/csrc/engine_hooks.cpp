@@ -503,6 +503,28 @@ extern "C" int irmv_engine_read_tensor(irmv_engine *e, const char *name, int fir
     return IRMV_OK;
 }
 
+extern "C" int irmv_engine_write_tensor(irmv_engine *e, const char *name, int first, int count, const void *src, size_t bytes)
+{
+    TRY(check_range(e, first, count));
+    if (!name) return fail(IRMV_ERR_ARG, "name is null");
+    auto it = e->tensor_idx.find(name);
+    if (it == e->tensor_idx.end()) return fail(IRMV_ERR_ARG, std::string("no tensor named ") + name);
+    const Tensor &t = e->tensors[it->second];
+    const size_t need = t.slot_elems * t.esize() * count;
+    if (!src || bytes != need) return fail(IRMV_ERR_ARG, "write_tensor: buffer size does not match the slot range");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));
+    // the dense state first (what ensure_dense_head and read_tensor's branch_stale path run), whatever tensor is written: the
+    // read-back step would otherwise run later, over the written values
+    for (int s = first; s < first + count; s++) {
+        if (e->head_stale[s] || e->branch_stale[s]) TRY(materialize_fused(e, s));
+        e->head_stale[s] = 0;
+        e->branch_stale[s] = 0;
+    }
+    HIP_TRY(hipMemcpy(t.slot(first), src, need, hipMemcpyHostToDevice));
+    return IRMV_OK;
+}
+
 extern "C" int irmv_engine_debug_read_head_rows(irmv_engine *e, int slot, float *rec, size_t bytes)
 {
     TRY(check_range(e, slot, 1));
@@ -705,16 +727,77 @@ extern "C" int irmv_engine_ops(irmv_engine *e, irmv_graph_op *ops, int cap, int 
     return IRMV_OK;
 }
 
+// What a fused op's launch writes and reads, from the argument builders of engine_step.cpp (c2f2_args, c2f32_args, bneck_args,
+// kpt3_args) and the kernels behind them; false: op is no fused op.
+struct FusedIo { std::vector<int> sub; std::vector<SegRef> writes, reads; };
+static bool fused_io(const irmv_engine *e, const Op &op, FusedIo &io)
+{
+    io = FusedIo{};
+    for (int k = 0; k < 4; k++) if (op.sub[k] >= 0) io.sub.push_back(op.sub[k]);
+    auto seg = [&](const SegRef &s) { if (s.t >= 0 && s.C > 0) io.reads.push_back(s); };
+    switch (op.kind) {
+    case OP_C2F2:    // the block input -> the block output; cat and tmp stay on chip
+        seg(op.s0);
+        io.writes.push_back(SegRef{op.out_t, 0, e->ops[op.sub[3]].cout, 0});
+        return true;
+    case OP_C2F32:   // mode 0: input -> output; 1: input -> y0 | y1 | y2 of the concat buffer; 2: y0 | y1 | y2 -> output
+        if (op.mode != 2) { seg(e->ops[op.sub[0]].s0); seg(e->ops[op.sub[0]].s1); }
+        else seg(SegRef{op.res_t, 0, 96, 0});
+        if (op.mode == 1) io.writes.push_back(SegRef{op.res_t, 0, 96, 0});
+        else io.writes.push_back(SegRef{op.out_t, 0, e->ops[op.sub[3]].cout, 0});
+        return true;
+    case OP_BNECK: { // A: slice y_in of the concat buffer -> the next slice; B: the slices up to and including y_in -> the block output
+        const Op &m1 = e->ops[op.sub[0]], &m2 = e->ops[op.sub[1]];
+        if (op.sub[2] < 0) {
+            seg(m1.s0);
+            io.writes.push_back(SegRef{m2.out_t, m2.out_coff, m2.cout, 0});
+        } else {
+            const Op &c2 = e->ops[op.sub[2]];
+            seg(SegRef{op.res_t, 0, m1.s0.coff + m1.s0.C, 0});
+            io.writes.push_back(SegRef{c2.out_t, c2.out_coff, c2.cout, 0});
+        }
+        return true;
+    }
+    case OP_KPT3: {  // the level's input -> the keypoint channels of its head records
+        const Op &o2 = e->ops[op.sub[2]];
+        seg(e->ops[op.sub[0]].s0);
+        io.writes.push_back(SegRef{o2.out_t, o2.out_coff, o2.cout_pad, 0});   // (the final's padding rows too: 16 floats of a record)
+        return true;
+    }
+    default: return false;
+    }
+}
+
+extern "C" int irmv_engine_op_io(irmv_engine *e, int op, irmv_op_io *out)
+{
+    if (!e || !out) return fail(IRMV_ERR_ARG, "engine / io is null");
+    if (op < 0 || op >= (int)e->ops.size()) return fail(IRMV_ERR_ARG, "no such op");
+    FusedIo io;
+    if (!fused_io(e, e->ops[op], io)) return fail(IRMV_ERR_ARG, std::string("op_io describes c2f2, c2f32, bneck and kpt3 ops, not ") + op_kind_name(e->ops[op].kind));
+    memset(out, 0, sizeof *out);
+    out->op = op;
+    out->n_sub = (int32_t)io.sub.size(); out->n_writes = (int32_t)io.writes.size(); out->n_reads = (int32_t)io.reads.size();
+    for (size_t i = 0; i < io.sub.size(); i++) out->sub[i] = io.sub[i];
+    for (size_t i = 0; i < io.writes.size(); i++) put_seg(e, out->writes[i], io.writes[i], false);
+    for (size_t i = 0; i < io.reads.size(); i++) put_seg(e, out->reads[i], io.reads[i], false);
+    return IRMV_OK;
+}
+
 extern "C" int irmv_engine_run_op(irmv_engine *e, int op, int first, int count, uint32_t flags)
 {
     TRY(check_range(e, first, count));
     if (op < 0 || op >= (int)e->ops.size()) return fail(IRMV_ERR_ARG, "no such op");
     const Op &o = e->ops[op];
-    if (o.kind != OP_CONV0 && o.kind != OP_POOL && o.kind != OP_DW && o.kind != OP_SHUF)
-        return fail(IRMV_ERR_ARG, std::string("run_op runs conv0, pool, dw and shuffle ops, not ") + op_kind_name(o.kind));
+    FusedIo io;
+    const bool fused = fused_io(e, o, io);
+    if (!fused && o.kind != OP_CONV0 && o.kind != OP_POOL && o.kind != OP_DW && o.kind != OP_SHUF)
+        return fail(IRMV_ERR_ARG, std::string("run_op runs conv0, pool, dw, shuffle, c2f2, c2f32, bneck and kpt3 ops, not ") + op_kind_name(o.kind));
     HIP_TRY(hipSetDevice(e->cfg.device));
     TRY(irmv_engine_wait(e));
-    if (flags & kRunPoisons) {
+    if (fused) TRY(slots_view(e, first, count, nullptr));
+    if ((flags & kRunPoisons) && fused) {
+        for (const SegRef &w : io.writes) TRY(poison_output(e, e->tensors[w.t], w.coff, w.C, first, count));
+    } else if (flags & kRunPoisons) {
         int t, coff, C;
         op_output(e, o, &t, &coff, &C);
         TRY(poison_output(e, e->tensors[t], coff, C, first, count));

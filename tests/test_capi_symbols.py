@@ -60,6 +60,18 @@ def test_graph_op_record_matches_the_header(tmp_path):
     assert got == [C.sizeof(capi.GraphOp)] + [getattr(capi.GraphOp, f).offset for f in fields]
 
 
+def test_op_io_record_matches_the_header(tmp_path):
+    """irmv_op_io (irmv_engine_op_io) against its ctypes mirror, field by field."""
+    fields = [f for f, _ in capi.OpIo._fields_]
+    src = tmp_path / "io.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "irmv_hip.h"\nint main(void){printf("%zu", sizeof(irmv_op_io));' +
+                   "".join(f'printf(" %zu", offsetof(irmv_op_io, {f}));' for f in fields) + "return 0;}\n")
+    exe = tmp_path / "io"
+    subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+    assert got == [C.sizeof(capi.OpIo)] + [getattr(capi.OpIo, f).offset for f in fields]
+
+
 def test_light_trace_record_matches_the_header(tmp_path, lib):
     """irmv_light_trace / irmv_light_rec (irmv_engine_light_trace) against their ctypes mirrors, field by field, and the
     limits the library was compiled with against the header's array bounds."""

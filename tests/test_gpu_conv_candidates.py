@@ -31,7 +31,8 @@ accumulation term bounds them, and there it is a handful of fp32 roundings that 
 when the output barely cancels: the MFMA sum, the ln 2 unscale of the accumulator, the bias add, and the reference's
 own fp32 read-back of its fp16 inputs.  The keypoint final model.22.cv4.0.2 (K = 16: one MFMA step, few terms, little
 cancellation) comes closest: 0.876 on the 1024 engine, i.e. C_ACC ~ 3.5 -- four such roundings is what C_ACC = 4
-allows.  M_REL = 0.25 leaves a quarter of an fp16 step for the read-back and the pre-rounding error.  Both are far
+allows.  (On written inputs of a wide range these finals pass 4: the MFMA rounds more often than once.  The count is in
+tests/test_gpu_act_craft.py, "Finding".)  M_REL = 0.25 leaves a quarter of an fp16 step for the read-back and the pre-rounding error.  Both are far
 below the ~K / 32 accumulator roundings a K loop makes at worst (144 for model.9.cv2).  A mis-staged chunk or a wrong
 border tap moves outputs by a sizable fraction of sum |w||x| and lands far outside this bound; so does a bias error
 wherever it is large against 2^-11 |y| (an error of one fp16 step of the bias passes where |y| >> |b|).  The end to

@@ -53,7 +53,7 @@ COVERED = {   # the other kinds that write activation tensors, and where they ar
     "conv": "the sweep of tests/test_gpu_conv_candidates.py",
     "front": "bitwise against its layers in the sweep, and on the zoo of tests/test_gpu_input_geometry.py", "c2f2": "bitwise against its layers in the sweep",
     "c2f32": "bitwise against its layers in the sweep", "bneck": "bitwise against its layers in the sweep",
-    "kpt3": "bitwise against its layers in the sweep",
+    "kpt3": "bitwise against its layers in the sweep",   # (all four also alone, on written inputs: tests/test_gpu_act_craft.py)
     "pre": "the preprocess bit-exact tests of tests/test_gpu_engine.py and tests/test_gpu_rect.py, and bitwise against the oracle "
            "on the zoo of tests/test_gpu_input_geometry.py",
 }
