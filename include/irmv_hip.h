@@ -289,6 +289,13 @@ int irmv_engine_debug_graph_count(const irmv_engine *e);
 int irmv_engine_src_format(const irmv_engine *e);      /* IRMV_SRC_* of this engine; -1 for a null engine */
 size_t irmv_engine_src_bytes(const irmv_engine *e);    /* bytes of one source slot (host and device); 0 for a null engine */
 
+/* Without IRMV_SUBMIT_H2D a step reads the slot's device frame as it is: what a producer wrote through
+ * irmv_engine_src_device_buffer, what the last WHOLE upload of the slot left there (a step with IRMV_SUBMIT_H2D in the frame
+ * view, of a Bayer engine or of an engine without a window; a tiled step's frame_slot), or what an on-demand entry loaded
+ * (irmv_engine_rotated_image, _render, _meter, _extract_armors, _refine_points, _light_trace: the pinned frame as it was at
+ * that call -- on an HWC window engine in the window view only the rows under the window of that call).  A window-view step
+ * with IRMV_SUBMIT_H2D of an HWC window engine leaves the device frame UNSPECIFIED: it uploads the window's band, or crops
+ * out of the pinned slot and uploads nothing, as the launch form decides. */
 #define IRMV_SUBMIT_H2D 1u          /* copy the pinned slots -> HBM first */
 #define IRMV_SUBMIT_ASYNC_UPLOAD 2u /* ... on the engine's upload stream, event-chained to the compute stream: this
                                        group's frames cross PCIe while other groups' kernels run (one cross-stream hop) */
@@ -391,7 +398,12 @@ double irmv_engine_last_detect_ms(const irmv_engine *e);
  * receives src_height*src_width*3 bytes in every format: a Bayer engine uploads the
  * raw slot, demosaics it and returns the rotated R, G, B frame.  A window engine
  * returns the rotated window: win_height*win_width*3 bytes -- or, for a slot in
- * IRMV_VIEW_FRAME, the rotated full frame: src_height*src_width*3 bytes. */
+ * IRMV_VIEW_FRAME, the rotated full frame: src_height*src_width*3 bytes.
+ * On demand, callable at any time: the call waits for the slot's own step in flight (as irmv_engine_wait_slots(slot, 1) does;
+ * other slots stay in flight), then loads the slot's pinned frame AS IT IS NOW into the device frame -- in the window view of
+ * an HWC window engine the band of rows under the window -- and returns its rotation.  A step of the slot that was in flight
+ * keeps the frame it was submitted with, also where the producer has overwritten the pinned slot since
+ * irmv_engine_wait_upload. */
 int irmv_engine_rotated_image(irmv_engine *e, int slot, uint8_t *dst_hwc);
 
 /* ---- debug images: the node's visualized and binary frames, rendered on the GPU -----------------------------------------

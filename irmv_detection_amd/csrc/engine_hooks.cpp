@@ -51,6 +51,9 @@ extern "C" int irmv_engine_rotated_image(irmv_engine *e, int slot, uint8_t *dst)
     if (!dst) return fail(IRMV_ERR_ARG, "dst is null");
     HIP_TRY(hipSetDevice(e->cfg.device));
     const View &v = view_of(e, slot);
+    // the slot's step in flight may run on another compute stream and still read the device frame load_frame rewrites (its
+    // pinned slot may be the producer's again since irmv_engine_wait_upload); other slots stay in flight
+    TRY(irmv_engine_wait_slots(e, slot, 1));
     TRY(load_frame(e, slot, e->stream));
     launch_rotate180(v.frames + (size_t)slot * v.frame_bytes, v.rot_dev, v.src_w, v.src_h, e->stream);
     HIP_TRY(hipMemcpyAsync(dst, v.rot_dev, v.frame_bytes, hipMemcpyDeviceToHost, e->stream));
