@@ -834,6 +834,43 @@ int irmv_debug_lds_fill(uint32_t pattern32);
  * 4 * cap words (IRMV_ERR_ARG if cap is smaller than that number; out NULL queries *n alone). */
 int irmv_debug_lds_probe(uint32_t pattern32, uint32_t word, uint32_t *out, int cap, int *n);
 
+/* ---- device-memory residue test hooks (tests/test_gpu_mem_residue.py) ------
+ * Global memory keeps its contents from one step to the next too.  Every device range of an engine carries a class -- what
+ * a step may rely on in it -- and a kind -- how its words are used ("device memory a step may rely on"); these
+ * two list the ranges and choose the residue a step finds.  No production path uses them. */
+#define IRMV_MEM_CONST   0   /* uploaded by the host, written by no step; a fill never touches it */
+#define IRMV_MEM_ACT     1   /* activation tensor / head: a fill covers the channels some op of the step declares as written */
+#define IRMV_MEM_CARRIED 2   /* a documented step-boundary invariant; a fill never touches it */
+#define IRMV_MEM_SCRATCH 3   /* a step writes it before it reads it; a fill covers all of it */
+#define IRMV_MEM_U8    0     /* plain data by width ... */
+#define IRMV_MEM_F16   1
+#define IRMV_MEM_F32   2
+#define IRMV_MEM_F64   3
+#define IRMV_MEM_INDEX 4     /* some kernel uses a word as an index, count, offset or label: index_max is the largest value valid there */
+typedef struct irmv_mem_range {
+    char name[48];
+    int32_t mem_class, kind;     /* IRMV_MEM_* */
+    uint32_t index_max;          /* IRMV_MEM_INDEX only */
+    int32_t reserved;
+    uint64_t bytes;
+    uint64_t base;               /* the device address (tests read a CARRIED range through it; nothing else may) */
+} irmv_mem_range;
+/* The engine's device ranges in allocation order.  *n = their number; recs NULL queries *n alone, else IRMV_ERR_ARG if cap
+ * is smaller. */
+int irmv_engine_debug_allocs(irmv_engine *e, irmv_mem_range *recs, int cap, int *n);
+/* Waits for the engine, then writes pattern32 over every SCRATCH range and over the written channel ranges of every ACT tensor
+ * -- the union of what irmv_engine_ops and irmv_engine_op_io declare as written -- on all slots.  A range of kind INDEX gets
+ * pattern32 == 0 ? 0 : index_max in every word instead, so no fill puts an out-of-range value where a kernel would use it as
+ * an address.  The two halfwords of pattern32 must be equal (a fill has no phase).  *filled = the bytes written.  Touches no
+ * CONST or CARRIED byte, no stale flag and no host memory. */
+int irmv_engine_debug_fill_mem(irmv_engine *e, uint32_t pattern32, uint64_t *filled);
+/* (tests) `bytes` of range `range` (its index in irmv_engine_debug_allocs' list) from `offset` on, as they lie in memory: waits
+ * for the engine, runs no kernel and no read-back step, changes no flag.  IRMV_ERR_ARG outside the range. */
+int irmv_engine_debug_read_mem(irmv_engine *e, int range, uint64_t offset, void *dst, uint64_t bytes);
+/* (tests) the per-slot candidate counters as they lie in memory, one of the two CARRIED ranges (the other:
+ * irmv_engine_debug_read_cand_bits).  *n = num_slots, or 0 on an engine that keeps none. */
+int irmv_engine_debug_read_cand_counts(irmv_engine *e, int32_t *counts, int cap, int *n);
+
 /* ---- frame metering: histograms inside the step, white balance from them ------------------------------------------------
  * The measuring half of the ISP.  A Bayer producer has bypassed the camera SDK's auto white balance and exposure, and the frame
  * it would meter exists only in device memory.  Metering is a per-frame record of four 256-bin integer histograms, computed on

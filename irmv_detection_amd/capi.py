@@ -212,6 +212,15 @@ class MeterMap(C.Structure):
 DECLINED = 1    # irmv_engine_run_conv_candidate: no kernel runs that candidate
 RUN_POISON, RUN_POISON_ONLY = 1, 2   # ... its flags: NaN over the output it must write first (and launch nothing)
 
+MEM_CLASSES = ("CONST", "ACT", "CARRIED", "SCRATCH")   # IRMV_MEM_CONST .. IRMV_MEM_SCRATCH
+MEM_KINDS = ("U8", "F16", "F32", "F64", "INDEX")       # IRMV_MEM_U8 .. IRMV_MEM_INDEX
+
+
+class MemRange(C.Structure):
+    """irmv_mem_range (irmv_engine_debug_allocs): one device range of an engine with its class and kind."""
+    _fields_ = [("name", C.c_char * 48), ("mem_class", C.c_int32), ("kind", C.c_int32), ("index_max", C.c_uint32),
+                ("reserved", C.c_int32), ("bytes", C.c_uint64), ("base", C.c_uint64)]
+
 
 # every symbol include/irmv_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
@@ -302,6 +311,10 @@ SYMBOLS = [
     ("irmv_engine_profile", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_debug_lds_fill", C.c_int, [C.c_uint32]),
     ("irmv_debug_lds_probe", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int)]),
+    ("irmv_engine_debug_allocs", C.c_int, [_P, C.POINTER(MemRange), C.c_int, C.POINTER(C.c_int)]),
+    ("irmv_engine_debug_fill_mem", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint64)]),
+    ("irmv_engine_debug_read_mem", C.c_int, [_P, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64]),
+    ("irmv_engine_debug_read_cand_counts", C.c_int, [_P, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_pnp_create", C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_P)]),
     ("irmv_pnp_destroy", None, [_P]),
     ("irmv_pnp_solve", C.c_int, [_P, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_double),

@@ -92,7 +92,7 @@ irmv_engine::~irmv_engine()
     }
     drop_graphs(this, false);
     if (log_alloc()) fprintf(stderr, "[irmv alloc] engine %p destroy: freeing %zu device ranges\n", (const void *)this, dev_allocs.size());
-    for (void *p : dev_allocs) (void)hipFree(p);
+    for (const DevRange &r : dev_allocs) (void)hipFree(r.base);
     dev_allocs.clear();
     if (src_host) (void)hipHostFree(src_host);
     if (dets_host) (void)hipHostFree(dets_host);
@@ -883,14 +883,16 @@ static int write_pose_prior(irmv_engine *e)
 static int enable_pose_alt(irmv_engine *e)
 {
     const size_t n = (size_t)e->cfg.num_slots * e->cfg.max_det;
-    TRY(dev_alloc(e, (void **)&e->alts_dev, n * sizeof(DevAlt)));
+    // DevAlt: doubles, and two int32 flags (state, alt_ok) that only the host reads; nms_pnp_kernel<true> / light_extract write
+    // the records of [0, num_dets), no kernel reads one
+    TRY(dev_alloc(e, (void **)&e->alts_dev, n * sizeof(DevAlt), "alts_dev", mem_scratch(MEM_F64)));
     HIP_TRY(hipMemset(e->alts_dev, 0, n * sizeof(DevAlt)));
     HIP_TRY(hipHostMalloc((void **)&e->alts_host, n * sizeof(DevAlt), hipHostMallocMapped | hipHostMallocCoherent));
     HIP_TRY(hipHostGetDevicePointer((void **)&e->alts_host_dev, e->alts_host, 0));
     memset(e->alts_host, 0, n * sizeof(DevAlt));
     log_range(e, "pinned alts_host", e->alts_host, n * sizeof(DevAlt));
-    TRY(dev_alloc(e, (void **)&e->prior_dev, sizeof(PosePrior)));
-    TRY(dev_alloc(e, (void **)&e->up_dev, e->up.size() * sizeof(double)));
+    TRY(dev_alloc(e, (void **)&e->prior_dev, sizeof(PosePrior), "prior_dev", mem_const(MEM_F64)));   // host-written tables, read when the kernel runs
+    TRY(dev_alloc(e, (void **)&e->up_dev, e->up.size() * sizeof(double), "up_dev", mem_const(MEM_F64)));
     HIP_TRY(hipMemcpy(e->up_dev, e->up.data(), e->up.size() * sizeof(double), hipMemcpyHostToDevice));
     e->pose_alt = true;
     drop_graphs(e, false);

@@ -32,11 +32,14 @@ static uint16_t float_to_half_bits(float f)
 }
 
 // ---- tensors, weight packing and the layer ops -----------------------------------------
-int irmv::dev_alloc(irmv_engine *e, void **p, size_t bytes)
+// THE device allocation of an engine: every range is recorded with its name and its tag (engine_internal.hpp, MemTag), which
+// the call site chooses from what the range's consumers do with its words and says so in a comment.
+int irmv::dev_alloc(irmv_engine *e, void **p, size_t bytes, const std::string &name, MemTag tag)
 {
+    static const char *const cls[] = {"CONST", "ACT", "CARRIED", "SCRATCH"};
     HIP_TRY(hipMalloc(p, bytes ? bytes : 16));
-    e->dev_allocs.push_back(*p);
-    log_range(e, "device", *p, bytes ? bytes : 16);
+    e->dev_allocs.push_back(DevRange{name, tag, *p, bytes ? bytes : 16});
+    log_range(e, (std::string(cls[tag.cls]) + " " + name).c_str(), *p, bytes ? bytes : 16);
     return IRMV_OK;
 }
 
@@ -46,7 +49,8 @@ static int new_tensor(irmv_engine *e, const std::string &name, int H, int W, int
     t.name = name;
     t.H = H; t.W = W; t.C = C; t.f32 = f32;
     t.slot_elems = (size_t)H * W * C;
-    TRY(dev_alloc(e, &t.base, t.slot_elems * t.esize() * e->cfg.num_slots));
+    // an activation tensor: convs, pools and fused kernels read its halfwords as fp16 values only
+    TRY(dev_alloc(e, &t.base, t.slot_elems * t.esize() * e->cfg.num_slots, name, mem_act(f32 ? MEM_F32 : MEM_F16)));
     // activations start at zero so that never-written pad channels are finite
     HIP_TRY(hipMemset(t.base, 0, t.slot_elems * t.esize() * e->cfg.num_slots));
     *idx = (int)e->tensors.size();
@@ -97,8 +101,9 @@ static int pack_conv(irmv_engine *e, const LayerW &l, Op &op)
     // scaled once here; layers without activation (the Detect finals) undo the scale in their epilogue and keep their bias
     std::vector<float> bias(op.cout_pad, 0.f);
     for (int i = 0; i < l.cout; i++) bias[i] = l.act == 1 ? (float)((double)l.b[i] * (double)kActScale) : l.b[i];
-    TRY(dev_alloc(e, (void **)&op.w_packed, packed.size() * 2));
-    TRY(dev_alloc(e, (void **)&op.bias, bias.size() * 4));
+    // weights and biases: uploaded below, read as MFMA operands (names "w." / "b." + l.name)
+    TRY(dev_alloc(e, (void **)&op.w_packed, packed.size() * 2, "w." + l.name, mem_const(MEM_F16)));
+    TRY(dev_alloc(e, (void **)&op.bias, bias.size() * 4, "b." + l.name, mem_const(MEM_F32)));
     HIP_TRY(hipMemcpy(op.w_packed, packed.data(), packed.size() * 2, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(op.bias, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
     if (l.k == 1 && l.cin == 16 && op.cfg.out_f32 && l.act == 0 && op.cout_pad == 16) {   // lane (g, r): output channel r, input channels 4 g .. 4 g + 3
@@ -106,7 +111,7 @@ static int pack_conv(irmv_engine *e, const LayerW &l, Op &op)
         for (int lane = 0; lane < 64; lane++)
             for (int j = 0; j < 4; j++)
                 if ((lane & 15) < l.cout) pk[lane * 4 + j] = l.w[(size_t)(lane & 15) * l.cin + 4 * (lane >> 4) + j];
-        TRY(dev_alloc(e, (void **)&op.w_k16, pk.size() * 2));
+        TRY(dev_alloc(e, (void **)&op.w_k16, pk.size() * 2, "w." + l.name + ".k16", mem_const(MEM_F16)));
         HIP_TRY(hipMemcpy(op.w_k16, pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
     }
     // LDS-kernel layout: [n-block][chunk of 32 ch][tap][tile in block][lane][8]
@@ -130,7 +135,7 @@ static int pack_conv(irmv_engine *e, const LayerW &l, Op &op)
                                 if (co < l.cout) pl[base + j] = l.w[((size_t)co * 9 + tap) * l.cin + c];
                             }
                         }
-            TRY(dev_alloc(e, (void **)&op.w_lds[v], pl.size() * 2));
+            TRY(dev_alloc(e, (void **)&op.w_lds[v], pl.size() * 2, "w." + l.name + ".lds" + std::to_string(v), mem_const(MEM_F16)));
             HIP_TRY(hipMemcpy(op.w_lds[v], pl.data(), pl.size() * 2, hipMemcpyHostToDevice));
         }
     }
@@ -200,8 +205,8 @@ static int add_dw(irmv_engine *e, const std::string &layer, SegRef in, int Hin, 
     std::vector<uint16_t> w((size_t)9 * l->cout);
     for (int c = 0; c < l->cout; c++)
         for (int t = 0; t < 9; t++) w[(size_t)t * l->cout + c] = l->w[(size_t)c * 9 + t];
-    TRY(dev_alloc(e, (void **)&op.w_packed, w.size() * 2));
-    TRY(dev_alloc(e, (void **)&op.bias, (size_t)l->cout * 4));
+    TRY(dev_alloc(e, (void **)&op.w_packed, w.size() * 2, "w." + layer, mem_const(MEM_F16)));
+    TRY(dev_alloc(e, (void **)&op.bias, (size_t)l->cout * 4, "b." + layer, mem_const(MEM_F32)));
     HIP_TRY(hipMemcpy(op.w_packed, w.data(), w.size() * 2, hipMemcpyHostToDevice));
     {   // no activation, but the output feeds further layers: it stays at the activation scale, so the bias is scaled too
         std::vector<float> bs((size_t)l->cout);
@@ -461,22 +466,27 @@ static int create_streams_and_frames(irmv_engine *e)
         if (hipHostGetDevicePointer((void **)&e->src_host_dev, e->src_host, 0) != hipSuccess) { e->src_host_dev = nullptr; (void)hipGetLastError(); }
         e->numa_placed = user && scope.bound();
     }
-    TRY(dev_alloc(e, (void **)&e->src_dev, e->frame_bytes * S));
+    // Device frames: pixel bytes.  Every consumer (preprocess / front taps, crop, demosaic and its [3][256] ISP table, light
+    // extraction's threshold, metering's 256-bin histograms, render) uses a byte as a value or as an index into a table of 256
+    // entries, so every byte value is valid everywhere.  SCRATCH: the upload, the crop or the demosaic writes a frame first.
+    TRY(dev_alloc(e, (void **)&e->src_dev, e->frame_bytes * S, "src_dev", mem_scratch(MEM_U8)));
     HIP_TRY(hipMemset(e->src_dev, 0, e->frame_bytes * S));
     View &v0 = e->views[IRMV_VIEW_WINDOW];
     v0.built = true; v0.crop = e->window;
     v0.src_w = c.src_width; v0.src_h = c.src_height;
     v0.frames = e->src_dev; v0.frame_bytes = e->frame_bytes;
-    TRY(dev_alloc(e, (void **)&v0.rot_dev, e->frame_bytes));
+    TRY(dev_alloc(e, (void **)&v0.rot_dev, e->frame_bytes, "rot_dev", mem_scratch(MEM_U8)));   // rotate180 writes it, a D2H copy reads it
     e->slot_view.assign(S, IRMV_VIEW_WINDOW);
     e->sub_view = e->slot_view;
     if (e->window) {
-        TRY(dev_alloc(e, (void **)&e->full_dev, e->full_bytes * S));
+        TRY(dev_alloc(e, (void **)&e->full_dev, e->full_bytes * S, "full_dev", mem_scratch(MEM_U8)));
         HIP_TRY(hipMemset(e->full_dev, 0, e->full_bytes * S));
-        TRY(dev_alloc(e, (void **)&e->win_dev, sizeof(int2) * S));
+        // the windows' corners: written by the host alone (write_window); window_crop_kernel, tile_merge_kernel and the meter
+        // clamp what they read
+        TRY(dev_alloc(e, (void **)&e->win_dev, sizeof(int2) * S, "win_dev", mem_const(MEM_INDEX)));
     }
     if (bayer) {
-        TRY(dev_alloc(e, (void **)&e->raw_dev, e->src_bytes * S));
+        TRY(dev_alloc(e, (void **)&e->raw_dev, e->src_bytes * S, "raw_dev", mem_scratch(MEM_U8)));
         HIP_TRY(hipMemset(e->raw_dev, 0, e->src_bytes * S));
         // phase of the R sites: IRMV_SRC_BAYER_{RGGB, BGGR, GRBG, GBRG}8 -> R at (0,0), (1,1), (0,1), (1,0)
         static const int ry[4] = {0, 1, 0, 1}, rx[4] = {0, 1, 1, 0};
@@ -487,7 +497,7 @@ static int create_streams_and_frames(irmv_engine *e)
         for (int i = 0; i < 3; i++) b.gain[i] = c.bayer_gain_q8[i];
         for (int i = 0; i < 3; i++) e->isp_gain[i] = c.bayer_gain_q8[i];
         for (int i = 0; i < kBayerTableBytes; i++) e->isp_lut[i] = (uint8_t)(i & 255);
-        TRY(dev_alloc(e, (void **)&e->isp_table_dev, kBayerTableBytes));
+        TRY(dev_alloc(e, (void **)&e->isp_table_dev, kBayerTableBytes, "isp_table", mem_const(MEM_U8)));
         e->bayer_mhc = c.bayer_demosaic == IRMV_DEMOSAIC_MHC;
         if (e->bayer_mhc) { e->bayer_table = true; TRY(write_isp_table(e)); }
     }
@@ -504,8 +514,10 @@ int irmv::build_view_geometry(irmv_engine *e, View &v, int src_w, int src_h)
     std::vector<AxisTap> tx, ty;
     irmv_front_plan_t &plan = v.front;
     front_plan(c, e->sw.front, &plan, tx, ty);
-    TRY(dev_alloc(e, (void **)&v.tap_x, net_w * sizeof(AxisTap)));
-    TRY(dev_alloc(e, (void **)&v.tap_y, net_h * sizeof(AxisTap)));
+    // tap tables: source columns / rows and weights of the resize, uploaded below
+    const char *vn = &v == &e->views[IRMV_VIEW_FRAME] ? ".frame" : "";
+    TRY(dev_alloc(e, (void **)&v.tap_x, net_w * sizeof(AxisTap), std::string("tap_x") + vn, mem_const(MEM_INDEX)));
+    TRY(dev_alloc(e, (void **)&v.tap_y, net_h * sizeof(AxisTap), std::string("tap_y") + vn, mem_const(MEM_INDEX)));
     HIP_TRY(hipMemcpy(v.tap_x, tx.data(), net_w * sizeof(AxisTap), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(v.tap_y, ty.data(), net_h * sizeof(AxisTap), hipMemcpyHostToDevice));
     v.fused_front = plan.fused != 0;
@@ -547,7 +559,9 @@ static int alloc_view_light(irmv_engine *e, View &v)
 {
     const size_t SL = (e->classical || e->refined) ? (size_t)e->cfg.num_slots : 1;   // keypoint mode keeps one slot's worth for irmv_engine_extract_armors
     v.light_pool = std::max<size_t>((size_t)8 * v.src_w * v.src_h, (size_t)(v.src_w + 2) * (v.src_h + 2) + 16);
-    return dev_alloc(e, (void **)&v.light_labels, SL * v.light_pool);
+    // light_extract_kernel thresholds every byte of an ROI's padded label image before its scan reads it; the scan and the
+    // border following compare labels (0, 1, the two border marks) and never index by one
+    return dev_alloc(e, (void **)&v.light_labels, SL * v.light_pool, &v == &e->views[IRMV_VIEW_FRAME] ? "light_labels.frame" : "light_labels", mem_scratch(MEM_U8));
 }
 
 // The frame view of a window engine (irmv_engine_set_view): the full frame's geometry and tap tables, the larger label pool
@@ -563,7 +577,7 @@ int irmv::build_frame_view(irmv_engine *e)
     if (!front_takes_model1(e->ops[e->front_ops[2]])) v.fused_front = false;
     if (v.fused_front && e->front_op < 0) add_front_op(e, (double)e->frame_bytes);   // (its bytes count view 0's frame; build_step_plans adds the difference)
     TRY(alloc_view_light(e, v));
-    TRY(dev_alloc(e, (void **)&v.rot_dev, v.frame_bytes));
+    TRY(dev_alloc(e, (void **)&v.rot_dev, v.frame_bytes, "rot_dev.frame", mem_scratch(MEM_U8)));
     build_step_plans(e, v);
     HIP_TRY(hipDeviceSynchronize());
     v.built = true;
@@ -615,8 +629,8 @@ static int build_trunk(irmv_engine *e, Acts &act)
                     const int kh = 2 * ks + (g >> 1), kw = 2 * (g & 1) + (j >> 2), ci = j & 3;
                     if (kh < 3 && kw < 3 && ci < 3) w[((size_t)ks * 64 + lane) * 8 + j] = l->w[(o * 9 + kh * 3 + kw) * 3 + ci];
                 }
-        TRY(dev_alloc(e, (void **)&e->conv0_w, w.size() * 2));
-        TRY(dev_alloc(e, (void **)&e->conv0_b, b.size() * 4));
+        TRY(dev_alloc(e, (void **)&e->conv0_w, w.size() * 2, "w.conv0", mem_const(MEM_F16)));
+        TRY(dev_alloc(e, (void **)&e->conv0_b, b.size() * 4, "b.conv0", mem_const(MEM_F32)));
         HIP_TRY(hipMemcpy(e->conv0_w, w.data(), w.size() * 2, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(e->conv0_b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
         Op op; op.kind = OP_CONV0; op.layer = "model.0.conv"; snprintf(op.kname, sizeof op.kname, "conv0_mfma");
@@ -700,7 +714,8 @@ static int build_neck_and_head(irmv_engine *e, const Acts &act)
         base += e->lvl_hw[i];
     }
     e->A = base;
-    TRY(dev_alloc(e, (void **)&e->head_all, (size_t)S * e->A * kHeadRec * 4));
+    // the head records: fp32 logits, read as values by the scan, the DFL decode and the keypoint decode
+    TRY(dev_alloc(e, (void **)&e->head_all, (size_t)S * e->A * kHeadRec * 4, "head_all", mem_act(MEM_F32)));
     HIP_TRY(hipMemset(e->head_all, 0, (size_t)S * e->A * kHeadRec * 4));
     for (int i = 0; i < 3; i++) {   // per-level views [slot][H*W][kHeadRec] into the one head allocation
         Tensor t;
@@ -792,23 +807,39 @@ static int build_post_stage(irmv_engine *e)
     const irmv_engine_cfg &c = e->cfg;
     const int net_w = c.net_size, net_h = c.net_height, S = c.num_slots;
     // ---- post-processing buffers ----
-    TRY(dev_alloc(e, (void **)&e->boxes, (size_t)S * e->A * 16));
-    TRY(dev_alloc(e, (void **)&e->keys, (size_t)S * e->A * e->nc * 8));
+    // boxes: xyxy floats of the candidate anchors, written by the decode (scan_decode_kernel / decode_keys), read as values by
+    // the NMS walks at the anchors of the frame's own keys.
+    TRY(dev_alloc(e, (void **)&e->boxes, (size_t)S * e->A * 16, "boxes", mem_scratch(MEM_F32)));
+    // keys: (orderable logit) << 32 | (0xffffffff - id), id = anchor * nc + class.  The low word is an INDEX: unpack_key
+    // (k_post.hip) turns it into the anchor that addresses boxes and head records, clamped by anchor_of to A - 1 whatever the
+    // word holds; take_keys clamps the count it reads the list to.  Valid low words are [0xffffffff - (A nc - 1), 0xffffffff],
+    // so the largest valid word is 0xffffffff (id 0); the high word is a score, any value.
+    TRY(dev_alloc(e, (void **)&e->keys, (size_t)S * e->A * e->nc * 8, "keys", mem_scratch_index(0xffffffffu)));
     // per-slot candidate counters of the split scan (k_post.hip scan_decode_kernel): zeroed HERE, once, with a synchronous
     // memset -- afterwards each nms_pnp launch reads its frames' counters and resets them itself (no memset node in a
     // captured step, nothing left non-zero between steps)
     if (e->sw.split_scan) {
-        TRY(dev_alloc(e, (void **)&e->cand_counts, (size_t)S * sizeof(int)));
+        // CARRIED, invariant: zero between steps.  A count: the emitting epilogues and scan_decode_kernel refuse an index at or
+        // above key_cap = A nc, take_keys clamps what it reads to [0, key_cap]
+        TRY(dev_alloc(e, (void **)&e->cand_counts, (size_t)S * sizeof(int), "cand_counts", mem_carried_index((uint32_t)(e->A * e->nc))));
         HIP_TRY(hipMemset(e->cand_counts, 0, (size_t)S * sizeof(int)));
         // ... and the candidate-anchor bitmap of the sparse head, kept the same way
         e->cand_words = (e->A + 31) / 32;
-        TRY(dev_alloc(e, (void **)&e->cand_bits, (size_t)S * e->cand_words * sizeof(unsigned int)));
+        // CARRIED, invariant: zero between steps.  Bit masks (any word is in range; a set bit stores or computes a head row)
+        TRY(dev_alloc(e, (void **)&e->cand_bits, (size_t)S * e->cand_words * sizeof(unsigned int), "cand_bits", mem_carried_index(0xffffffffu)));
         HIP_TRY(hipMemset(e->cand_bits, 0, (size_t)S * e->cand_words * sizeof(unsigned int)));
     }
     e->head_stale.assign((size_t)S, 0);
     e->branch_stale.assign((size_t)S, 0);
-    TRY(dev_alloc(e, (void **)&e->dets_dev, (size_t)S * c.max_det * sizeof(DevDet)));
-    TRY(dev_alloc(e, (void **)&e->fout_dev, (size_t)S * sizeof(DevFrameOut)));
+    // DevDet mixes floats, doubles and int32 fields; the most dangerous use decides.  cls: light_extract_kernel and pose_rule
+    // index the class tables with cls & 15 and tile_merge_kernel maps anything outside [0, 14) to 14; anchor and pnp_ok are
+    // read by the host alone; armor_size (0 / 1) is the host's index into the plate sizes.  The largest word valid in every one
+    // of them is 1 (0 for a model of one class).  Records at and above num_dets are read by no kernel.
+    const uint32_t det_max = e->nc > 1 ? 1u : 0u;
+    TRY(dev_alloc(e, (void **)&e->dets_dev, (size_t)S * c.max_det * sizeof(DevDet), "dets_dev", mem_scratch_index(det_max)));
+    // num_dets is the record count of light_extract_kernel (min(n, max_det), a negative count runs nothing), refine_prior_kernel
+    // and tile_merge_kernel (clamped to [0, max_det]); n_candidates (<= A nc) and the rest go to the host
+    TRY(dev_alloc(e, (void **)&e->fout_dev, (size_t)S * sizeof(DevFrameOut), "fout_dev", mem_scratch_index((uint32_t)c.max_det)));
     HIP_TRY(hipMemset(e->dets_dev, 0, (size_t)S * c.max_det * sizeof(DevDet)));
     HIP_TRY(hipMemset(e->fout_dev, 0, (size_t)S * sizeof(DevFrameOut)));
     // Result records live in mapped, coherent pinned memory: in keypoint mode the NMS kernel stores them there directly
@@ -844,25 +875,29 @@ static int build_post_stage(irmv_engine *e)
     if (e->refined) {   // the guided instantiation behind the NMS: the keypoints it decoded are the prior
         Op op; op.kind = OP_LIGHT; op.layer = "refine_points"; snprintf(op.kname, sizeof op.kname, "light_refine");
         e->ops.push_back(op);
-        TRY(dev_alloc(e, (void **)&e->refine_dev, sizeof(RefineParams)));
+        TRY(dev_alloc(e, (void **)&e->refine_dev, sizeof(RefineParams), "refine_params", mem_const(MEM_F32)));
         HIP_TRY(hipMemcpy(e->refine_dev, &e->refine, sizeof e->refine, hipMemcpyHostToDevice));
-        TRY(dev_alloc(e, (void **)&e->refine_kpts, (size_t)S * c.max_det * 8 * sizeof(float)));
+        // the prior: refine_prior_kernel copies the records' keypoints here, guided_roi range-checks all eight before use
+        TRY(dev_alloc(e, (void **)&e->refine_kpts, (size_t)S * c.max_det * 8 * sizeof(float), "refine_kpts", mem_scratch(MEM_F32)));
         HIP_TRY(hipMemset(e->refine_kpts, 0, (size_t)S * c.max_det * 8 * sizeof(float)));
     }
     // scratch of the classical extraction: per detection a padded label image (ROIs up to ~510 x 510) and contour points
     const size_t SL = (e->classical || e->refined) ? (size_t)S : 1;   // keypoint mode keeps one slot's worth for irmv_engine_extract_armors
     TRY(alloc_view_light(e, e->views[IRMV_VIEW_WINDOW]));
-    TRY(dev_alloc(e, (void **)&e->light_points, SL * c.max_det * kLightPointsCap * 2 * sizeof(short)));
-    TRY(dev_alloc(e, (void **)&e->light_hulls, SL * c.max_det * kLightPointsCap * 4 * sizeof(short)));
-    TRY(dev_alloc(e, (void **)&e->light_boxes, (size_t)c.max_det * 16));
-    TRY(dev_alloc(e, (void **)&e->light_dets_dev, (size_t)c.max_det * sizeof(DevDet)));
+    // contour points and hull scratch: 16-bit ROI coordinates that trace_border writes and contour_to_light sorts, hulls and
+    // measures -- arithmetic only (ranks and hull indices are counted, never read from memory); s_start bounds every read
+    TRY(dev_alloc(e, (void **)&e->light_points, SL * c.max_det * kLightPointsCap * 2 * sizeof(short), "light_points", mem_scratch(MEM_F16)));
+    TRY(dev_alloc(e, (void **)&e->light_hulls, SL * c.max_det * kLightPointsCap * 4 * sizeof(short), "light_hulls", mem_scratch(MEM_F16)));
+    // explicit boxes of irmv_engine_extract_armors, uploaded before the launch; roi_of clips them to the frame
+    TRY(dev_alloc(e, (void **)&e->light_boxes, (size_t)c.max_det * 16, "light_boxes", mem_scratch(MEM_F32)));
+    TRY(dev_alloc(e, (void **)&e->light_dets_dev, (size_t)c.max_det * sizeof(DevDet), "light_dets_dev", mem_scratch_index(det_max)));   // (DevDet: as dets_dev)
     HIP_TRY(hipHostMalloc((void **)&e->light_dets_host, (size_t)c.max_det * sizeof(DevDet), hipHostMallocDefault));
     log_range(e, "pinned light_dets", e->light_dets_host, (size_t)c.max_det * sizeof(DevDet));
 
     PostArgs &p = e->post;
     p.net_w = net_w; p.net_h = net_h; p.A = e->A; p.nc = e->nc; p.nk = e->nk;
     // class policy: uniform from cfg.score_thr / cfg.armor_size until irmv_engine_set_class_policy says otherwise
-    TRY(dev_alloc(e, (void **)&e->cls_dev, 2 * sizeof(ClassTable)));
+    TRY(dev_alloc(e, (void **)&e->cls_dev, 2 * sizeof(ClassTable), "cls_dev", mem_const(MEM_INDEX)));   // thresholds and plate indices, written by write_class_table
     if (int rc = irmv_class_policy_uniform(c.score_thr, c.armor_size, &e->policy)) return rc;
     TRY(write_class_table(e));
     p.cls = e->cls_dev;
@@ -879,7 +914,7 @@ static int build_post_stage(irmv_engine *e)
     pc.hy[0] = 135.0 / 2.0 / 1000.0; pc.hy[1] = 225.0 / 2.0 / 1000.0;   // src/pnp_solver.cpp:18-21
     pc.hz[0] = pc.hz[1] = 55.0 / 2.0 / 1000.0;
     e->pnp_base = pc;
-    TRY(dev_alloc(e, (void **)&e->pnp_dev, sizeof(PnpConst) * (e->window ? S : 1)));
+    TRY(dev_alloc(e, (void **)&e->pnp_dev, sizeof(PnpConst) * (e->window ? S : 1), "pnp_dev", mem_const(MEM_F64)));
     HIP_TRY(hipMemcpy(e->pnp_dev, &pc, sizeof pc, hipMemcpyHostToDevice));
     p.pnp = e->pnp_dev;
     p.pnp_stride = e->window ? 1 : 0;
@@ -890,7 +925,7 @@ static int build_post_stage(irmv_engine *e)
     }
     p.dbg = nullptr;
     if (e->sw.nms_stamps) {
-        TRY(dev_alloc(e, (void **)&e->dbg_dev, (size_t)S * 16 * sizeof(long long)));
+        TRY(dev_alloc(e, (void **)&e->dbg_dev, (size_t)S * 16 * sizeof(long long), "dbg_dev", mem_scratch(MEM_F64)));   // phase stamps: written by nms_pnp_kernel, printed by the host
         HIP_TRY(hipMemset(e->dbg_dev, 0, (size_t)S * 16 * sizeof(long long)));
         p.dbg = e->dbg_dev;
     }

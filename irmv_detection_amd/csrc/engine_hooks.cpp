@@ -119,11 +119,11 @@ static int ensure_render(irmv_engine *e)
         f.len[c] = (uint8_t)strlen(kRenderNames[c]);
         for (int k = 0; k < f.len[c]; k++) f.name[c][k] = (uint8_t)render_glyph_index(kRenderNames[c][k]);
     }
-    if (!e->render_marks) TRY(dev_alloc(e, (void **)&e->render_marks, (size_t)e->cfg.max_det * sizeof(RenderMark)));
-    if (!e->render_font) TRY(dev_alloc(e, (void **)&e->render_font, sizeof(RenderFont)));
+    if (!e->render_marks) TRY(dev_alloc(e, (void **)&e->render_marks, (size_t)e->cfg.max_det * sizeof(RenderMark), "render_marks", mem_const(MEM_INDEX)));   // the host uploads the n marks a call draws (cls indexes the font)
+    if (!e->render_font) TRY(dev_alloc(e, (void **)&e->render_font, sizeof(RenderFont), "render_font", mem_const(MEM_INDEX)));
     HIP_TRY(hipMemcpy(e->render_font, &f, sizeof f, hipMemcpyHostToDevice));
     e->render_marks_host.resize((size_t)e->cfg.max_det);
-    TRY(dev_alloc(e, (void **)&e->render_out, std::max(e->frame_bytes, e->full_bytes)));
+    TRY(dev_alloc(e, (void **)&e->render_out, std::max(e->frame_bytes, e->full_bytes), "render_out", mem_scratch(MEM_U8)));   // the picture: written by the kernel, copied to the host
     return IRMV_OK;
 }
 
@@ -205,11 +205,11 @@ static int ensure_refine(irmv_engine *e)
 {
     if (!e->refine_dev) {
         RefineParams *p = nullptr;
-        TRY(dev_alloc(e, (void **)&p, sizeof(RefineParams)));
+        TRY(dev_alloc(e, (void **)&p, sizeof(RefineParams), "refine_params", mem_const(MEM_F32)));
         HIP_TRY(hipMemcpy(p, &e->refine, sizeof e->refine, hipMemcpyHostToDevice));
         e->refine_dev = p;
     }
-    if (!e->refine_kpts) TRY(dev_alloc(e, (void **)&e->refine_kpts, (size_t)e->cfg.max_det * 8 * sizeof(float)));
+    if (!e->refine_kpts) TRY(dev_alloc(e, (void **)&e->refine_kpts, (size_t)e->cfg.max_det * 8 * sizeof(float), "refine_kpts", mem_scratch(MEM_F32)));   // (as build_post_stage's)
     return IRMV_OK;
 }
 
@@ -224,7 +224,9 @@ static int extract_armors(irmv_engine *e, int slot, const float *xyxy, const flo
     TRY(irmv_engine_wait(e));
     hipStream_t st = e->stream;
     if (kpts) TRY(ensure_refine(e));
-    if (trace && !e->light_trace_dev) TRY(dev_alloc(e, (void **)&e->light_trace_dev, (size_t)e->cfg.max_det * sizeof(LightTrace)));
+    // the trace of a hook call: zeroed in front of every launch, written by the kernel, read by the host, which indexes by its
+    // counts and starts -- so nothing but zero is valid in every word
+    if (trace && !e->light_trace_dev) TRY(dev_alloc(e, (void **)&e->light_trace_dev, (size_t)e->cfg.max_det * sizeof(LightTrace), "light_trace", mem_scratch_index(0u)));
     if (trace) HIP_TRY(hipMemsetAsync(e->light_trace_dev, 0, (size_t)n * sizeof(LightTrace), st));
     TRY(load_frame(e, slot, st));
     // a window engine takes the boxes in full result coordinates: in the window view window-local for the kernel, the corner
@@ -811,6 +813,120 @@ extern "C" int irmv_engine_run_op(irmv_engine *e, int op, int first, int count, 
     const Step step{count == 1 ? STEP_ONE : STEP_BATCH, first, count};
     TRY(launch_op(e, view_of(e, first), l, step, post_args(e, view_of(e, first), step), 0u, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return IRMV_OK;
+}
+
+// ---- device-memory residue hooks (tests/test_gpu_mem_residue.py) ------------------------
+extern "C" int irmv_engine_debug_allocs(irmv_engine *e, irmv_mem_range *recs, int cap, int *n)
+{
+    if (!e || !n) return fail(IRMV_ERR_ARG, "engine / n is null");
+    *n = (int)e->dev_allocs.size();
+    if (!recs) return IRMV_OK;
+    if (cap < *n) return fail(IRMV_ERR_ARG, "debug_allocs: buffer too small");
+    for (size_t i = 0; i < e->dev_allocs.size(); i++) {
+        const DevRange &r = e->dev_allocs[i];
+        irmv_mem_range &o = recs[i];
+        memset(&o, 0, sizeof o);
+        put_name(o.name, r.name);
+        o.mem_class = r.tag.cls; o.kind = r.tag.kind; o.index_max = r.tag.index_max;
+        o.bytes = r.bytes; o.base = (uint64_t)(uintptr_t)r.base;
+    }
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_debug_read_cand_counts(irmv_engine *e, int32_t *counts, int cap, int *n)
+{
+    if (!e || !n) return fail(IRMV_ERR_ARG, "engine / n is null");
+    *n = e->cand_counts ? e->cfg.num_slots : 0;
+    if (!counts || *n == 0) return IRMV_OK;
+    if (cap < *n) return fail(IRMV_ERR_ARG, "read_cand_counts: buffer too small");
+    TRY(irmv_engine_wait(e));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(hipMemcpy(counts, e->cand_counts, (size_t)*n * sizeof(int), hipMemcpyDeviceToHost));
+    return IRMV_OK;
+}
+
+extern "C" int irmv_engine_debug_read_mem(irmv_engine *e, int range, uint64_t offset, void *dst, uint64_t bytes)
+{
+    if (!e || !dst) return fail(IRMV_ERR_ARG, "engine / dst is null");
+    if (range < 0 || range >= (int)e->dev_allocs.size()) return fail(IRMV_ERR_ARG, "debug_read_mem: no such range");
+    const DevRange &r = e->dev_allocs[(size_t)range];
+    if (offset > r.bytes || bytes > r.bytes - offset) return fail(IRMV_ERR_ARG, "debug_read_mem: outside range " + r.name);
+    TRY(irmv_engine_wait(e));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(hipMemcpy(dst, static_cast<const char *>(r.base) + offset, bytes, hipMemcpyDeviceToHost));
+    return IRMV_OK;
+}
+
+// `bytes` at p (2-byte aligned) <- the 32-bit word v, whose halfwords are equal: words, then a halfword, then a byte
+static int fill_range(void *p, size_t bytes, uint32_t v, hipStream_t st)
+{
+    char *c = static_cast<char *>(p);
+    if (((uintptr_t)c & 2) && bytes >= 2) { HIP_TRY(hipMemsetD16Async((hipDeviceptr_t)c, (unsigned short)v, 1, st)); c += 2; bytes -= 2; }
+    if (bytes / 4) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)c, (int)v, bytes / 4, st));
+    c += bytes / 4 * 4;
+    if (bytes & 2) { HIP_TRY(hipMemsetD16Async((hipDeviceptr_t)c, (unsigned short)v, 1, st)); c += 2; }
+    if (bytes & 1) HIP_TRY(hipMemsetD8Async((hipDeviceptr_t)c, (unsigned char)v, 1, st));
+    return IRMV_OK;
+}
+
+// The channels of every tensor that some op declares as written: op_output of every op and the writes of the fused ones --
+// what irmv_engine_ops and irmv_engine_op_io report.
+static std::vector<std::vector<char>> written_channels(const irmv_engine *e)
+{
+    std::vector<std::vector<char>> w(e->tensors.size());
+    for (size_t t = 0; t < w.size(); t++) w[t].assign((size_t)e->tensors[t].C, 0);
+    auto mark = [&](int t, int coff, int C) { for (int c = std::max(coff, 0); t >= 0 && c < coff + C && c < e->tensors[t].C; c++) w[t][c] = 1; };
+    for (const Op &op : e->ops) {
+        int t, coff, C;
+        op_output(e, op, &t, &coff, &C);
+        mark(t, coff, C);
+        FusedIo io;
+        if (fused_io(e, op, io)) for (const SegRef &s : io.writes) mark(s.t, s.coff, s.C);
+    }
+    return w;
+}
+
+extern "C" int irmv_engine_debug_fill_mem(irmv_engine *e, uint32_t pattern32, uint64_t *filled)
+{
+    if (!e || !filled) return fail(IRMV_ERR_ARG, "engine / filled is null");
+    if ((pattern32 >> 16) != (pattern32 & 0xffffu)) return fail(IRMV_ERR_ARG, "debug_fill_mem: the two halfwords of the pattern must be equal");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(irmv_engine_wait(e));
+    hipStream_t st = e->stream;
+    const int S = e->cfg.num_slots;
+    uint64_t total = 0;
+    for (const DevRange &r : e->dev_allocs) {
+        if (r.tag.cls != MEM_SCRATCH) continue;
+        if (r.tag.kind == MEM_INDEX) {   // whole words of the largest value valid in every indexing use
+            if (r.bytes & 3) return fail(IRMV_ERR_ARG, "debug_fill_mem: INDEX range " + r.name + " is no whole number of words");
+            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)r.base, (int)(pattern32 == 0 ? 0u : r.tag.index_max), r.bytes / 4, st));
+        } else TRY(fill_range(r.base, r.bytes, pattern32, st));
+        total += r.bytes;
+    }
+    // The written channels of every tensor.  A tensor written whole is one fill.  Any other is read back, patterned on the
+    // written channels in a buffer of this call and written again, so its pad channels keep exactly what they held.  (The
+    // path of IRMV_RUN_POISON, hipMemset2DAsync, takes a byte value, and these patterns are halfwords.)
+    const auto w = written_channels(e);
+    std::vector<uint16_t> host;
+    for (size_t ti = 0; ti < w.size(); ti++) {
+        const Tensor &t = e->tensors[ti];
+        const size_t n_written = (size_t)std::count(w[ti].begin(), w[ti].end(), (char)1), rows = (size_t)S * t.H * t.W;
+        const size_t hw = t.esize() / 2;   // halfwords per element
+        if (n_written == 0) continue;
+        if (n_written == (size_t)t.C) TRY(fill_range(t.base, rows * t.C * t.esize(), pattern32, st));
+        else {
+            host.resize(rows * t.C * hw);
+            HIP_TRY(hipMemcpy(host.data(), t.base, host.size() * 2, hipMemcpyDeviceToHost));
+            for (size_t r = 0; r < rows; r++)
+                for (int c = 0; c < t.C; c++)
+                    if (w[ti][c]) for (size_t k = 0; k < hw; k++) host[(r * t.C + c) * hw + k] = (uint16_t)pattern32;
+            HIP_TRY(hipMemcpy(t.base, host.data(), host.size() * 2, hipMemcpyHostToDevice));
+        }
+        total += n_written * t.esize() * rows;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    *filled = total;
     return IRMV_OK;
 }
 

@@ -67,6 +67,24 @@ struct Tensor {
 
 struct SegRef { int t = -1, coff = 0, C = 0, shift = 0; };
 
+// Every device allocation of an engine says what a step may rely on in it ("device memory a step may rely on");
+// dev_alloc takes the tag as a required argument, and irmv_engine_debug_fill_mem chooses the residue by it.
+//   MEM_CONST    the host uploads it, no step writes it
+//   MEM_ACT      an activation tensor (or the head): a step writes the channels its ops declare, pad channels stay +0
+//   MEM_CARRIED  a step relies on what the last one left: a documented step-boundary invariant
+//   MEM_SCRATCH  a step writes every word before it reads it
+// The kind is how the words are used.  MEM_INDEX: some kernel uses a word as an index, count, offset or label; index_max is
+// the largest value valid in every such use (a fill never puts anything else there).  The others are plain data by width.
+enum MemClass { MEM_CONST = IRMV_MEM_CONST, MEM_ACT = IRMV_MEM_ACT, MEM_CARRIED = IRMV_MEM_CARRIED, MEM_SCRATCH = IRMV_MEM_SCRATCH };
+enum MemKind { MEM_U8 = IRMV_MEM_U8, MEM_F16 = IRMV_MEM_F16, MEM_F32 = IRMV_MEM_F32, MEM_F64 = IRMV_MEM_F64, MEM_INDEX = IRMV_MEM_INDEX };
+struct MemTag { MemClass cls; MemKind kind; uint32_t index_max; };
+constexpr MemTag mem_const(MemKind k) { return {MEM_CONST, k, 0u}; }
+constexpr MemTag mem_act(MemKind k) { return {MEM_ACT, k, 0u}; }
+constexpr MemTag mem_scratch(MemKind k) { return {MEM_SCRATCH, k, 0u}; }
+constexpr MemTag mem_scratch_index(uint32_t max) { return {MEM_SCRATCH, MEM_INDEX, max}; }
+constexpr MemTag mem_carried_index(uint32_t max) { return {MEM_CARRIED, MEM_INDEX, max}; }
+struct DevRange { std::string name; MemTag tag; void *base; size_t bytes; };
+
 // The front's switches (front_plan): IRMV_FRONT_FASTX / _DIRECT / _TILE8 =0 clear them (the last keeps the 4-row tile); all
 // on for the plan irmv_front_plan exports.
 struct FrontSwitches { bool fastx = true, direct = true, tall = true; };
@@ -310,7 +328,7 @@ struct irmv_engine {
     std::vector<Tensor> tensors;
     std::map<std::string, int> tensor_idx;
     std::vector<Op> ops;
-    std::vector<void *> dev_allocs;
+    std::vector<DevRange> dev_allocs;     // every device range of the engine, classified (dev_alloc)
     int head_t[3] = {-1, -1, -1};
     float *head_all = nullptr;
     PnpConst *pnp_dev = nullptr;
@@ -419,7 +437,7 @@ int check_window_slot(const irmv_engine *e, int slot, const char *who);
 int resolve_cfg(const irmv_engine_cfg *cfg_in, irmv_engine_cfg *full);
 int window_map(int full_w, int full_h, int win_w, int win_h, int rotate180, const double K[9], int x0, int y0, irmv_window_map_t *m);
 // engine_graph.cpp
-int dev_alloc(irmv_engine *e, void **p, size_t bytes);
+int dev_alloc(irmv_engine *e, void **p, size_t bytes, const std::string &name, MemTag tag);
 int load_blob(irmv_engine *e);
 int build_engine(irmv_engine *e);
 int build_view_geometry(irmv_engine *e, View &v, int src_w, int src_h);

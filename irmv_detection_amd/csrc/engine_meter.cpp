@@ -148,11 +148,14 @@ static int ensure_meter(irmv_engine *e)
 {
     if (e->meter_stats_dev) return IRMV_OK;
     const size_t S = (size_t)e->cfg.num_slots;
-    if (!e->meter_slab) TRY(dev_alloc(e, (void **)&e->meter_slab, S * kMeterBlocksMax * 1024 * sizeof(uint32_t)));
-    if (!e->meter_params_dev) TRY(dev_alloc(e, (void **)&e->meter_params_dev, 2 * sizeof(MeterParams)));
+    // partial histograms: 32-bit counts that the second kernel of a launch sums -- values, never indices
+    if (!e->meter_slab) TRY(dev_alloc(e, (void **)&e->meter_slab, S * kMeterBlocksMax * 1024 * sizeof(uint32_t), "meter_slab", mem_scratch(MEM_F32)));
+    // the options, written by the host alone (a rectangle: meter_geometry clips it to the view)
+    if (!e->meter_params_dev) TRY(dev_alloc(e, (void **)&e->meter_params_dev, 2 * sizeof(MeterParams), "meter_params", mem_const(MEM_INDEX)));
     HIP_TRY(hipMemset(e->meter_params_dev, 0, 2 * sizeof(MeterParams)));
     MeterStats *st = nullptr;
-    TRY(dev_alloc(e, (void **)&st, (S + 1) * sizeof(MeterStats)));
+    // the records: counts, the clipped rectangle and the echo of the options, written by the summing kernel, read by the host
+    TRY(dev_alloc(e, (void **)&st, (S + 1) * sizeof(MeterStats), "meter_stats", mem_scratch(MEM_F32)));
     HIP_TRY(hipMemset(st, 0, (S + 1) * sizeof(MeterStats)));
     e->meter_stats_dev = st;
     return IRMV_OK;

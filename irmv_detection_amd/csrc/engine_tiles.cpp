@@ -22,14 +22,17 @@ static int ensure_tiles(irmv_engine *e, int first, irmv_engine::TileMerge **out)
     if (!e->tile_params_dev) {
         if (!tile_merge_prepare()) return fail(IRMV_ERR_HIP, "tile merge kernel: LDS request refused");
         TileMergeParams *p = nullptr;
-        TRY(dev_alloc(e, (void **)&p, sizeof(TileMergeParams)));
+        TRY(dev_alloc(e, (void **)&p, sizeof(TileMergeParams), "tile_params", mem_const(MEM_F32)));   // two floats, written by the host alone
         HIP_TRY(hipMemcpy(p, &e->tile_params, sizeof e->tile_params, hipMemcpyHostToDevice));
         e->tile_params_dev = p;
     }
     irmv_engine::TileMerge &tm = e->tile_merges[first];
     if (!tm.out_dev) {
         TileOut *d = nullptr;
-        TRY(dev_alloc(e, (void **)&d, sizeof(TileOut)));
+        // TileOut: tile_merge_kernel writes n_kept, n_in and rec[0 .. n_kept) and reads none of it; the host indexes the slots'
+        // records by rec (tile < count, index < max_det) up to n_kept.  The smallest tiled step has one tile, so zero is the
+        // only word valid in every one of these uses.
+        TRY(dev_alloc(e, (void **)&d, sizeof(TileOut), "tile_out." + std::to_string(first), mem_scratch_index(0u)));
         HIP_TRY(hipMemset(d, 0, sizeof(TileOut)));
         if (!tm.out_host) {
             HIP_TRY(hipHostMalloc((void **)&tm.out_host, sizeof(TileOut), hipHostMallocDefault));

@@ -730,6 +730,39 @@ class YoloEngine:
                                                                  C.byref(n), C.byref(sparse)))
         return bool(sparse.value), words
 
+    def debug_cand_counts(self) -> np.ndarray:
+        """The per-slot candidate counters as they lie in memory (int32, empty where the engine keeps none)."""
+        n = C.c_int(0)
+        capi.check(self._L.irmv_engine_debug_read_cand_counts(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.int32)
+        if n.value:
+            capi.check(self._L.irmv_engine_debug_read_cand_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), n.value, C.byref(n)))
+        return out
+
+    def debug_allocs(self) -> list:
+        """The engine's device ranges in allocation order: dicts of name, class and kind (capi.MEM_CLASSES / MEM_KINDS),
+        index_max, bytes, base."""
+        n = C.c_int(0)
+        capi.check(self._L.irmv_engine_debug_allocs(self._h, None, 0, C.byref(n)))
+        recs = (capi.MemRange * max(n.value, 1))()
+        capi.check(self._L.irmv_engine_debug_allocs(self._h, recs, n.value, C.byref(n)))
+        return [dict(name=r.name.decode(), cls=capi.MEM_CLASSES[r.mem_class], kind=capi.MEM_KINDS[r.kind], index_max=int(r.index_max),
+                     bytes=int(r.bytes), base=int(r.base)) for r in recs[:n.value]]
+
+    def debug_read_mem(self, index: int, offset: int, nbytes: int) -> np.ndarray:
+        """Test hook: nbytes of device range `index` of debug_allocs() from `offset` on, as they lie in memory (uint8); no
+        kernel and no read-back step runs."""
+        out = np.empty(nbytes, np.uint8)
+        capi.check(self._L.irmv_engine_debug_read_mem(self._h, index, offset, out.ctypes.data_as(C.c_void_p), nbytes))
+        return out
+
+    def debug_fill_mem(self, pattern32: int) -> int:
+        """Test hook: pattern32 over every SCRATCH range and the written channels of every activation tensor, on all slots
+        (INDEX ranges: 0, or their largest valid value); -> bytes filled.  CONST and CARRIED ranges are left alone."""
+        filled = C.c_uint64(0)
+        capi.check(self._L.irmv_engine_debug_fill_mem(self._h, int(pattern32), C.byref(filled)))
+        return int(filled.value)
+
     def debug_head_rows(self, slot: int = 0) -> np.ndarray:
         """The slot's head records as they lie in memory, no read-back step in front: [num_anchors, 96] float32, box 64 |
         classes at 64 | keypoints at 80 (after a step of a sparse engine only the candidate anchors' rows are the step's)."""

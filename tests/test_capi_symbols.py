@@ -173,3 +173,19 @@ def test_numa_cpulist_parser_and_thread_binding(lib):
             "print('ok', rc, sorted(after)[:4], n)\n") % (ROOT, node0)
     out = subprocess.check_output([os.sys.executable, "-c", code], text=True)
     assert out.startswith("ok")
+
+
+def test_mem_range_record_matches_the_header(tmp_path):
+    """irmv_mem_range (irmv_engine_debug_allocs) against its ctypes mirror, field by field, and the class / kind numbers."""
+    fields = [f for f, _ in capi.MemRange._fields_]
+    src = tmp_path / "mr.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "irmv_hip.h"\nint main(void){printf("%zu", sizeof(irmv_mem_range));' +
+                   "".join(f'printf(" %zu", offsetof(irmv_mem_range, {f}));' for f in fields) +
+                   'printf(" %d %d %d %d %d %d %d %d %d", IRMV_MEM_CONST, IRMV_MEM_ACT, IRMV_MEM_CARRIED, IRMV_MEM_SCRATCH,'
+                   ' IRMV_MEM_U8, IRMV_MEM_F16, IRMV_MEM_F32, IRMV_MEM_F64, IRMV_MEM_INDEX);return 0;}\n')
+    exe = tmp_path / "mr"
+    subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+    assert got == ([C.sizeof(capi.MemRange)] + [getattr(capi.MemRange, f).offset for f in fields] +
+                   [capi.MEM_CLASSES.index(c) for c in ("CONST", "ACT", "CARRIED", "SCRATCH")] +
+                   [capi.MEM_KINDS.index(k) for k in ("U8", "F16", "F32", "F64", "INDEX")])
