@@ -100,6 +100,14 @@ public:
     // "pose_prior.ratio", "pose_prior.normal_up" (every class), and "up.x" / "up.y" / "up.z" or set_up() for the gimbal's up vector.
     irmv_pose_prior pose_prior{};
     std::array<double, 3> up{0.0, -1.0, 0.0};
+    // Constrained pose (include/irmv_hip.h): struct_size != 0 enables it on the three engines at creation (YoloEngine::yaw_opts())
+    // -- FrameResult::yaw is then filled.  yaw_publish: the message carries the constrained pose in place of IPPE's wherever
+    // its state is 1.  Live: set_parameter "yaw_solve" (0 | 1; the first 1 enables), "yaw_publish" (0 | 1).
+    // Models with a keypoint head only (a refined engine is one), like FrameResult::alts: a bbox-only detector takes its armors
+    // from extract_armors() -- explicit boxes, which have no side records --, so FrameResult::yaw stays empty there and
+    // yaw_publish changes nothing.
+    irmv_yaw_opts yaw_solve{};
+    bool yaw_publish = false;
     bool debug = false;                                  // the node's debug (:90-95, :259-280): every frame also yields FrameResult::visualized_image / binary_image,
                                                          // rendered on the GPU (YoloEngine::render); live through set_bool_parameter("debug", v) like the reference (:380-381)
     int debug_scale = 1;                                 // 1, 2 or 4: the debug images at full, half or quarter size (set_parameter "debug_scale")
@@ -125,6 +133,9 @@ public:
     // err / err_alt, the rms normalised residuals of the reported pose and of this one (else empty).  A tracker keeps both
     // while err_alt / err is small and lets its motion model decide; a large ratio means the reported pose stands alone.
     std::vector<irmv_pose_alt> alts;
+    // Params::yaw_solve only (else empty): parallel to `poses`, the plate's pose with its yaw solved at the class's known tilt
+    // and the up vector (state 1; -1: refused, 0: nothing)
+    std::vector<irmv_yaw_pose> yaw;
     double inference_latency_ms = 0;    // YoloEngine::get_profiling_time() (:251)
     // Params::debug only (else empty): the frame with this frame's armors, boxes and labels drawn on it (:261-263; the latency
     // text lines are not drawn), and gray -> threshold(binary_threshold) -> three channels with the boxes and labels (:273-277)
@@ -151,6 +162,7 @@ public:
       if (p.refine_snap != 0.5 || p.refine_roi_margin != 4.0) e->set_refine(float(p.refine_snap), float(p.refine_roi_margin));
       if (p.enemy_color != -1 || !p.large_plate_classes.empty()) push_class_policy(*e);
       if (p.pose_prior.struct_size != 0) { e->set_pose_prior(&p.pose_prior); e->set_up(p.up); }
+      if (p.yaw_solve.struct_size != 0) { e->set_yaw_solve(p.yaw_solve); e->set_up(p.up); }
     }
     yolo_engines_[0]->warm_up();   // the tile choices are shared by the three engines: one warm-up tunes for all
     for (size_t i = 1; i < yolo_engines_.size(); i++) yolo_engines_[i]->warm_up();
@@ -177,15 +189,18 @@ public:
     std::vector<Armor> armors;
     std::vector<irmv_det> poses;
     std::vector<irmv_pose_alt> alts;
+    std::vector<irmv_yaw_pose> yaws;
     if (eng.has_keypoint_head()) {
       // pose-style model: each detection carries its four points and, already, its pose
       int n = 0;
       const irmv_det * dets = eng.last_detections(&n);
       const std::vector<irmv_pose_alt> all = eng.pose_alts();   // parallel to dets (empty: not enabled)
+      const std::vector<irmv_yaw_pose> all_yaw = eng.yaw_poses();
       for (int i = 0; i < n; i++) {
         const irmv_det & d = dets[i];
         if (d.armor_valid != 1) continue;
         if (size_t(i) < all.size()) alts.push_back(all[size_t(i)]);
+        if (size_t(i) < all_yaw.size()) yaws.push_back(all_yaw[size_t(i)]);
         Armor a(Light(cv::Point2f(d.kpts[2], d.kpts[3]), cv::Point2f(d.kpts[0], d.kpts[1])),
                 Light(cv::Point2f(d.kpts[4], d.kpts[5]), cv::Point2f(d.kpts[6], d.kpts[7])));
         a.armor_class = static_cast<ArmorClass>(d.class_id);
@@ -216,6 +231,15 @@ public:
       out.armors.push_back(armors[i]);
       out.poses.push_back(d);
       if (alts.size() == armors.size()) out.alts.push_back(alts[i]);
+      if (yaws.size() == armors.size()) {
+        out.yaw.push_back(yaws[i]);
+        if (params_.yaw_publish && yaws[i].state == 1) {     // the constrained pose in place of IPPE's
+          ArmorMsg & pm = out.armors_msg.armors.back();
+          pm.pose.position.x = yaws[i].tvec[0]; pm.pose.position.y = yaws[i].tvec[1]; pm.pose.position.z = yaws[i].tvec[2];
+          pm.pose.orientation.x = yaws[i].quat[0]; pm.pose.orientation.y = yaws[i].quat[1];
+          pm.pose.orientation.z = yaws[i].quat[2]; pm.pose.orientation.w = yaws[i].quat[3];
+        }
+      }
     }
     out.inference_latency_ms = eng.get_profiling_time();
     if (params_.metering.struct_size != 0) {
@@ -293,6 +317,21 @@ public:
       if (!(snap > 0.0 && snap <= 4.0) || !(margin >= 0.0 && margin <= 64.0)) return false;
       params_.refine_snap = snap; params_.refine_roi_margin = margin;
       for (auto & e : yolo_engines_) e->set_refine(float(snap), float(margin));
+      return true;
+    }
+    else if (name == "yaw_solve") {
+      // live; the first 1 enables the records (one re-capture per engine), later ones re-capture nothing
+      if (value != 0.0 && value != 1.0) return false;
+      if (value == 0.0 && params_.yaw_solve.struct_size == 0) return true;
+      irmv_yaw_opts o = params_.yaw_solve.struct_size ? params_.yaw_solve : YoloEngine::yaw_opts();
+      o.enable = int(value);
+      params_.yaw_solve = o;
+      for (auto & e : yolo_engines_) { e->set_yaw_solve(o); e->set_up(params_.up); }
+      return true;
+    }
+    else if (name == "yaw_publish") {
+      if (value != 0.0 && value != 1.0) return false;
+      params_.yaw_publish = value == 1.0;
       return true;
     }
     else if (name == "pose_prior" || name == "pose_prior.ratio" || name == "pose_prior.normal_up") {

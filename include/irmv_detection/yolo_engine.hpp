@@ -312,6 +312,42 @@ public:
     return a;
   }
 
+  // ---- constrained pose (include/irmv_hip.h, "constrained pose") ----
+  // From the first set_yaw_solve on every detect() also solves, per solved record, the plate's yaw at the class's known tilt
+  // (set_pose_prior's normal_up) and the up vector (set_up): yaw_poses().  The first call re-captures the steps once; later
+  // calls, set_up and set_pose_prior re-capture nothing.  A refused value throws, nothing changes.
+  static irmv_yaw_opts yaw_opts(bool enable = true, int rounds = 4, double tau_max = 1.0, double horizon_min = 1e-4)
+  {
+    irmv_yaw_opts o{};
+    o.struct_size = sizeof o; o.enable = enable ? 1 : 0; o.rounds = rounds; o.tau_max = tau_max; o.horizon_min = horizon_min;
+    return o;
+  }
+  void set_yaw_solve(const irmv_yaw_opts & o = yaw_opts())
+  {
+    if (irmv_engine_set_yaw_solve(engine_, &o) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::set_yaw_solve: ") + irmv_last_error());
+    yaw_on_ = true;
+  }
+  irmv_yaw_opts yaw_solve() const
+  {
+    irmv_yaw_opts o;
+    if (irmv_engine_get_yaw_solve(engine_, &o) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::yaw_solve: ") + irmv_last_error());
+    return o;
+  }
+  // Parallel to last_detections(): entry i is the constrained pose of record i (empty before the first set_yaw_solve)
+  std::vector<irmv_yaw_pose> yaw_poses() const
+  {
+    std::vector<irmv_yaw_pose> a;
+    if (!yaw_on_) return a;
+    a.resize(dets_.size());
+    int n = 0;
+    if (irmv_engine_yaw_poses(engine_, 0, a.data(), static_cast<int>(a.size()), &n) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::yaw_poses: ") + irmv_last_error());
+    a.resize(static_cast<size_t>(n));
+    return a;
+  }
+
   // ---- tracking window ----
   bool has_window() const { return window_size_.width > 0 && window_size_.height > 0; }
   // The window's top-left corner in the coordinates bboxes come back in (the rotated frame); from the next detect() on.
@@ -568,6 +604,7 @@ private:
   irmv_class_policy user_policy_{};   // the caller's thresholds and plates, without the colour mask
   int enemy_color_ = -1;
   bool pose_alts_on_ = false;         // set_pose_prior has been called: the engine delivers alt records
+  bool yaw_on_ = false;               // set_yaw_solve has been called: the engine delivers constrained poses
   cv::Size src_image_size_;
   cv::Size window_size_;
   bool enable_profiling_ = false;

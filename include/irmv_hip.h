@@ -609,6 +609,59 @@ int irmv_engine_get_up(const irmv_engine *e, int slot, double up[3]);   /* the u
  * reach the host the way the slot's irmv_det records do.  IRMV_ERR_ARG before the first irmv_engine_set_pose_prior. */
 int irmv_engine_pose_alts(irmv_engine *e, int slot, irmv_pose_alt *out, int cap, int *n);
 
+/* ---- constrained pose: the plate's yaw at its known tilt ---------------------------------------------------------------
+ * The prior above only chooses between two noisy IPPE poses.  A plate has ONE free rotational degree of freedom once the
+ * slot's up vector u (irmv_engine_set_up), the class's tilt s = n . u (irmv_pose_prior.normal_up) and the fact that a plate's
+ * long edge is horizontal are used: four corners then determine one angle and a translation.  From the first
+ * irmv_engine_set_yaw_solve on, a step solves that angle for every record with pnp_ok == 1 and armor_valid == 1 in a kernel of
+ * its own behind the NMS (behind the light extraction on classical and refined engines) and delivers one side record per
+ * detection (irmv_engine_yaw_poses).  irmv_det, irmv_pose_alt and irmv_tile_det stay byte-identical whether or not it is on.
+ * The model, fp64 in the written order (no fused multiply-add); irmv_detection_amd/yaw_solve.py states it operation for
+ * operation:
+ *   per slot, on the host:   g = e_z - (e_z . u) u,  h1 = g / |g|  (the optical axis in the horizontal plane),  h2 = u x h1;
+ *                            |g|^2 < horizon_min: the slot has no basis (the camera looks along gravity)
+ *   per class, on the host:  c = sqrt(1 - s s);  c == 0: the class has no basis
+ *   for tau = tan(psi / 2):  d = 1 + tau tau,  cs = (1 - tau tau) / d,  sn = (2 tau) / d
+ *                            n = s u + c (cs h1 + sn h2)   (model x: the normal, away from the camera)
+ *                            y = cs h2 - sn h1             (model y: left)
+ *                            z = n x y,   R = [n y z]
+ *   translation:             the least-squares translation of the IPPE solver for that R, on the same undistorted points
+ *   cost q(tau):             the sum of the eight squared normalised residuals; +inf where a corner has depth <= 0, where
+ *                            !(n . t > 0) (a plate seen from behind) and where anything is NaN
+ * The search: one 64-lane wavefront per detection; lane k evaluates tau_k = lo + ((hi - lo) k) / 63, first on
+ * [-tau_max, tau_max]; the lane of least q wins (ties: the lower lane); the next round is [max(tau* - step, -tau_max),
+ * min(tau* + step, tau_max)] with step = (hi - lo) / 63; `rounds` rounds.  err = sqrt(q / 8) of the last winner.
+ * A record is refused (state -1) where the slot or the class has no basis, where every lane of the first round is +inf, and
+ * where the last winner's q is +inf.
+ * Nothing is allocated and nothing new is launched until the first irmv_engine_set_yaw_solve.  That call waits for everything
+ * in flight, allocates the records and the two tables and drops the captured graphs once; later calls, irmv_engine_set_up
+ * and irmv_engine_set_pose_prior rewrite the tables the kernel reads when it runs and re-capture nothing.  enable = 0: the
+ * kernel returns at once and irmv_engine_yaw_poses delivers all-zero records.  Before irmv_engine_set_up /
+ * irmv_engine_set_pose_prior their documented defaults apply.  Explicit boxes have no such record.  Tiled steps: the record of
+ * merged record r is irmv_engine_yaw_poses(first + r.tile)[r.index].
+ * Measured on the CPU alone (the reference on synthetic corner noise); no trained keypoint head exists. */
+typedef struct irmv_yaw_opts {
+    uint32_t struct_size;        /* = sizeof(irmv_yaw_opts) */
+    int32_t  enable;             /* 0 | 1 */
+    int32_t  rounds;             /* 1 .. 6; default 4 */
+    int32_t  reserved;           /* 0 */
+    double   tau_max;            /* in (0, 4]; default 1 = +-90 degrees */
+    double   horizon_min;        /* in (0, 1); default 1e-4 */
+} irmv_yaw_opts;
+typedef struct irmv_yaw_pose {
+    double  rvec[3], tvec[3], quat[4];
+    double  tau, cs, sn, err;            /* the winner's parameter, cos psi, sin psi, rms normalised residual */
+    int32_t state;                       /* 0: nothing here (pnp_ok == 0 or armor_valid != 1; all zero); 1: solved; -1: refused */
+    int32_t lane[6];                     /* the winning lane of each round; -1: the round did not run */
+    int32_t reserved;
+} irmv_yaw_pose;
+/* IRMV_ERR_ARG before the GPU is touched, leaving everything as it was: a null engine or opts, a wrong struct_size, enable
+ * outside {0, 1}, rounds outside 1 .. 6, tau_max outside (0, 4] or NaN, horizon_min outside (0, 1) or NaN, reserved != 0. */
+int irmv_engine_set_yaw_solve(irmv_engine *e, const irmv_yaw_opts *opts);
+int irmv_engine_get_yaw_solve(const irmv_engine *e, irmv_yaw_opts *opts);   /* before the first set: the defaults with enable = 0 */
+/* Parallel to irmv_engine_results, as irmv_engine_pose_alts is.  IRMV_ERR_ARG before the first irmv_engine_set_yaw_solve. */
+int irmv_engine_yaw_poses(irmv_engine *e, int slot, irmv_yaw_pose *out, int cap, int *n);
+
 /* ---- stage-wise read-backs used by the parity tests -------------------- */
 int irmv_engine_read_input(irmv_engine *e, int slot, float *chw);             /* [3][net_h][net_w], as the reference's input_buffer_ */
 int irmv_engine_read_head(irmv_engine *e, int slot, float *head);             /* [A][64+nc+nk], A = irmv_engine_num_anchors(): levels
@@ -974,6 +1027,11 @@ int irmv_pnp_solve(irmv_pnp *p, const float *img_pts, int n, int armor_size, dou
  * ok [n]: bit 0 = irmv_pnp_solve's ok; bit 1 = entry 1 passed its own finiteness check.  Where bit 0 is clear, entry 1 and
  * both errors are zero. */
 int irmv_pnp_solve2(irmv_pnp *p, const float *img_pts, int n, int armor_size, double *rvec, double *tvec, double *err, int32_t *ok);
+/* The constrained pose ("constrained pose" above) of n quads with one up vector (normalised as irmv_engine_set_up does) and
+ * one tilt normal_up in [-1, 1]: out [n].  Every quad is taken as solved input: state is 1 or -1, or 0 for a quad with a
+ * non-finite or >= 2^24 coordinate.  opts->enable is not read.  IRMV_ERR_ARG: what the engine calls refuse. */
+int irmv_pnp_solve_yaw(irmv_pnp *p, const float *img_pts, int n, int armor_size, const double up[3], double normal_up,
+                       const irmv_yaw_opts *opts, irmv_yaw_pose *out);
 
 #ifdef __cplusplus
 }

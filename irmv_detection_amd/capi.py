@@ -191,6 +191,28 @@ METER_VIEW, METER_RAW = 0, 1
 METER_DOMAINS = {"view": METER_VIEW, "raw": METER_RAW}
 
 
+class YawOpts(C.Structure):
+    """irmv_yaw_opts (include/irmv_hip.h, "constrained pose")."""
+    _fields_ = [("struct_size", C.c_uint32), ("enable", C.c_int32), ("rounds", C.c_int32), ("reserved", C.c_int32),
+                ("tau_max", C.c_double), ("horizon_min", C.c_double)]
+
+
+class YawPose(C.Structure):
+    """irmv_yaw_pose (include/irmv_hip.h): the constrained pose of one detection."""
+    _fields_ = [("rvec", C.c_double * 3), ("tvec", C.c_double * 3), ("quat", C.c_double * 4),
+                ("tau", C.c_double), ("cs", C.c_double), ("sn", C.c_double), ("err", C.c_double),
+                ("state", C.c_int32), ("lane", C.c_int32 * 6), ("reserved", C.c_int32)]
+
+
+def yaw_opts_struct(enable=1, rounds=4, tau_max=1.0, horizon_min=1e-4) -> YawOpts:
+    """An irmv_yaw_opts (no check: the library's are the ones under test)."""
+    o = YawOpts()
+    o.struct_size = C.sizeof(YawOpts)
+    o.enable, o.rounds, o.reserved = int(enable), int(rounds), 0
+    o.tau_max, o.horizon_min = float(tau_max), float(horizon_min)
+    return o
+
+
 class MeterOpts(C.Structure):
     """irmv_meter_opts (include/irmv_hip.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("domain", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32),
@@ -326,6 +348,11 @@ SYMBOLS = [
     ("irmv_engine_set_up", C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     ("irmv_engine_get_up", C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     ("irmv_engine_pose_alts", C.c_int, [_P, C.c_int, C.POINTER(PoseAlt), C.c_int, C.POINTER(C.c_int)]),
+    ("irmv_engine_set_yaw_solve", C.c_int, [_P, C.POINTER(YawOpts)]),
+    ("irmv_engine_get_yaw_solve", C.c_int, [_P, C.POINTER(YawOpts)]),
+    ("irmv_engine_yaw_poses", C.c_int, [_P, C.c_int, C.POINTER(YawPose), C.c_int, C.POINTER(C.c_int)]),
+    ("irmv_pnp_solve_yaw", C.c_int, [_P, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double,
+                                     C.POINTER(YawOpts), C.POINTER(YawPose)]),
     ("irmv_meter_map", C.c_int, [C.POINTER(EngineCfg), C.POINTER(MeterOpts), C.c_int, C.c_int, C.c_int, C.POINTER(MeterMap)]),
     ("irmv_meter_limits", C.c_int, [C.POINTER(C.c_int32)]),
     ("irmv_engine_meter", C.c_int, [_P, C.c_int, C.POINTER(MeterOpts), C.POINTER(FrameStats)]),

@@ -98,6 +98,7 @@ irmv_engine::~irmv_engine()
     if (dets_host) (void)hipHostFree(dets_host);
     if (fout_host) (void)hipHostFree(fout_host);
     if (alts_host) (void)hipHostFree(alts_host);
+    if (yaw_host) (void)hipHostFree(yaw_host);
     if (meter_stats_host) (void)hipHostFree(meter_stats_host);
     if (light_dets_host) (void)hipHostFree(light_dets_host);
     for (auto &kv : tile_merges)
@@ -464,6 +465,7 @@ extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **o
     }
     e->sw = read_switches();
     pose_prior_defaults(&e->pose_prior);
+    yaw_opts_defaults(&e->yaw_opts);
     e->up.assign((size_t)cfg->num_slots * 3, 0.0);
     for (int s = 0; s < cfg->num_slots; s++) e->up[3 * s + 1] = -1.0;   // a level camera: image y points down
     int rc = load_blob(e.get());
@@ -913,7 +915,8 @@ extern "C" int irmv_engine_set_pose_prior(irmv_engine *e, const irmv_pose_prior 
     TRY(irmv_engine_wait(e));   // every stream of the engine: no step in flight reads the table, no graph is running
     if (!e->pose_alt) TRY(enable_pose_alt(e));
     e->pose_prior = np;
-    return write_pose_prior(e);
+    TRY(write_pose_prior(e));
+    return write_yaw_tables(e);   // (the constrained pose reads the classes' tilts)
 }
 
 extern "C" int irmv_engine_get_pose_prior(const irmv_engine *e, irmv_pose_prior *out)
@@ -936,6 +939,10 @@ extern "C" int irmv_engine_set_up(irmv_engine *e, int slot, const double up[3])
         HIP_TRY(hipMemcpy(e->up_dev + 3 * slot, u, sizeof u, hipMemcpyHostToDevice));
     }
     std::copy(u, u + 3, e->up.begin() + 3 * slot);
+    if (e->yaw_op >= 0) {   // the constrained pose's basis of the slot
+        if (!e->pose_alt) { HIP_TRY(hipSetDevice(e->cfg.device)); TRY(irmv_engine_wait_slots(e, slot, 1)); }
+        TRY(write_yaw_tables(e, slot));
+    }
     return IRMV_OK;
 }
 
@@ -969,17 +976,6 @@ extern "C" int irmv_engine_get_bayer_isp(const irmv_engine *e, uint16_t gain_q8[
 }
 
 // ---- PnPSolver -------------------------------------------------------------------------
-struct irmv_pnp {
-    int device = 0;
-    PnpConst c{};
-    hipStream_t stream = nullptr;
-    float *pts = nullptr;
-    double *rvec = nullptr, *tvec = nullptr;   // [cap][2][3]: irmv_pnp_solve uses the first half
-    double *err = nullptr;                     // [cap][2]
-    int32_t *ok = nullptr;
-    int cap = 0;
-};
-
 static void pnp_free(irmv_pnp *p)
 {
     if (p->pts) (void)hipFree(p->pts);
@@ -987,10 +983,12 @@ static void pnp_free(irmv_pnp *p)
     if (p->tvec) (void)hipFree(p->tvec);
     if (p->err) (void)hipFree(p->err);
     if (p->ok) (void)hipFree(p->ok);
+    if (p->yaw) (void)hipFree(p->yaw);
+    p->yaw = nullptr;
     p->pts = nullptr; p->rvec = p->tvec = p->err = nullptr; p->ok = nullptr; p->cap = 0;
 }
 
-static int pnp_reserve(irmv_pnp *p, int n)
+int pnp_reserve(irmv_pnp *p, int n)   // (engine_yaw.cpp's stand-alone call reserves here too)
 {
     if (n <= p->cap) return IRMV_OK;
     pnp_free(p);
@@ -1000,6 +998,7 @@ static int pnp_reserve(irmv_pnp *p, int n)
     HIP_TRY(hipMalloc((void **)&p->tvec, (size_t)cap * 48));
     HIP_TRY(hipMalloc((void **)&p->err, (size_t)cap * 16));
     HIP_TRY(hipMalloc((void **)&p->ok, (size_t)cap * 4));
+    HIP_TRY(hipMalloc((void **)&p->yaw, (size_t)cap * sizeof(DevYaw)));
     p->cap = cap;
     return IRMV_OK;
 }

@@ -11,6 +11,7 @@
 //                     the merge hook, the merged results and the merge parameters
 //   engine_hooks.cpp  read-backs, debug images, debug_*, LDS fill / probe, conv and op test hooks, the profiler, the light trace
 //   engine_meter.cpp  frame metering: its checks and map, the record's host helpers, the on-demand call, the step's op
+//   engine_yaw.cpp    constrained pose: its checks, the two tables and who rewrites them, the step's op, the stand-alone call
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -132,7 +133,7 @@ struct EngineSwitches {
     bool nms_stamps = false; int nms_stamps_slots = 0;   // IRMV_NMS_STAMPS=<n>: the NMS kernel stamps its phases, the destructor prints the first n slots' (at least four)
 };
 
-enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_DEMOSAIC, OP_CROP, OP_METER };
+enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_DEMOSAIC, OP_CROP, OP_METER, OP_YAW };
 
 struct Op {
     OpKind kind;
@@ -247,6 +248,20 @@ struct SlotGroup {
     bool in_flight = false;          // submitted and not yet known complete
     bool async_up = false;           // the last submit uploaded on the side stream (event h2d is valid)
 };
+
+// The PnP object (engine.cpp; engine_yaw.cpp's stand-alone call)
+struct irmv_pnp {
+    int device = 0;
+    PnpConst c{};
+    hipStream_t stream = nullptr;
+    float *pts = nullptr;
+    double *rvec = nullptr, *tvec = nullptr;   // [cap][2][3]: irmv_pnp_solve uses the first half
+    double *err = nullptr;                     // [cap][2]
+    int32_t *ok = nullptr;
+    DevYaw *yaw = nullptr;                     // [cap]: irmv_pnp_solve_yaw's records
+    int cap = 0;
+};
+int pnp_reserve(irmv_pnp *p, int n);           // engine.cpp: the object's buffers for n quads
 
 struct irmv_engine {
     irmv_engine_cfg cfg{};
@@ -398,6 +413,16 @@ struct irmv_engine {
     std::vector<std::vector<float>> merged_b;
     bool merge_head0 = false;
     EngineSwitches sw{};       // the environment as irmv_engine_create found it
+    // (last, so that every member above lies where it lay before the feature)
+    // Constrained pose (irmv_engine_set_yaw_solve): nothing below but yaw_opts (a host value) exists until the first call.  It
+    // allocates the records -- [S][max_det] on the device and pinned, travelling exactly as the DevAlt records do --, the table
+    // and the per-slot bases, appends the op (yaw_op, behind the NMS / the light extraction in every step plan and run_post's)
+    // and drops the captured graphs once.  set_up, set_pose_prior and later calls rewrite the two tables (write_yaw_tables).
+    int yaw_op = -1;
+    irmv_yaw_opts yaw_opts{};
+    DevYaw *yaw_dev = nullptr, *yaw_host = nullptr, *yaw_host_dev = nullptr;
+    YawTable *yaw_table_dev = nullptr;
+    YawBasis *yaw_basis_dev = nullptr;        // [S]
 
     ~irmv_engine();
 };
@@ -453,6 +478,7 @@ int choose_sync_launch(irmv_engine *e);
 void finalize_head_fusion(irmv_engine *e);
 void build_step_plans(irmv_engine *e, View &v);
 void add_meter_op(irmv_engine *e);
+void add_yaw_op(irmv_engine *e);
 // engine_step.cpp
 void fill_conv_args(const irmv_engine *e, const Op &op, int first, int count, ConvArgs &a, bool fused = false);
 int slots_view(const irmv_engine *e, int first, int count, int *view = nullptr);
@@ -477,4 +503,8 @@ int submit_group(irmv_engine *e, int first, int count, uint32_t flags, hipStream
 TileArgs tile_args(const irmv_engine *e, int first, int count);
 // engine_hooks.cpp
 int ensure_dense_head(irmv_engine *e, int slot);
+// engine_yaw.cpp
+void yaw_opts_defaults(irmv_yaw_opts *o);
+int write_yaw_tables(irmv_engine *e, int slot = -1);   // no-op before the first set_yaw_solve; slot >= 0: that slot's basis alone
+void launch_yaw(const irmv_engine *e, const Step &s, const PostArgs &pa, hipStream_t st);
 }

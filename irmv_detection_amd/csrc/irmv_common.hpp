@@ -672,6 +672,41 @@ hipError_t launch_lds_probe(uint32_t pattern, uint32_t word, uint32_t *out, int 
 
 void launch_pnp_only(const PnpConst &c, const float *pts, int n, int armor_size, double *rvec, double *tvec,
                      int32_t *ok, hipStream_t s);
+
+// ---- constrained pose (k_yaw.hip; irmv_engine_set_yaw_solve) ----------------------------------------------------------
+// DevYaw is the side record of one detection (the layout of irmv_yaw_pose).  YawTable and the per-slot YawBasis records live in
+// device memory at addresses fixed from the first set_yaw_solve on; the host writes them (engine_yaw.cpp: every unit vector
+// and every square root is the host's), the kernel reads them when it runs.
+constexpr int kYawRoundsMax = 6, kYawThreads = 256, kYawPerBlock = kYawThreads / 64;
+struct DevYaw {
+    double rvec[3], tvec[3], quat[4];
+    double tau, cs, sn, err;
+    int32_t state;            // 0: nothing here (all zero); 1: solved; -1: refused
+    int32_t lane[kYawRoundsMax];
+    int32_t pad_;
+};
+struct YawTable {
+    int32_t enable, rounds;
+    double tau_max;
+    double s[kMaxClasses], c[kMaxClasses];   // per class: the tilt n . u and sqrt(1 - s s); c == 0: no basis
+};
+struct YawBasis { double u[3], h1[3], h2[3]; int32_t ok, pad_; };   // ok == 0: the camera looks along gravity
+// What one solve needs of the two tables, as values (the stand-alone form passes it as a kernel argument)
+struct YawRule { double u[3], h1[3], h2[3], s, c, tau_max; int32_t rounds, ok; };
+struct YawArgs {
+    const DevDet *dets;       // [B][max_det]: the records the post stage wrote
+    int max_det;
+    const int *num_dets;      // frame b: num_dets[b * num_dets_stride]
+    int num_dets_stride;
+    const PnpConst *pnp;      // frame b solves with pnp[(first + b) * pnp_stride]
+    int first, pnp_stride;
+    const YawTable *table;
+    const YawBasis *basis;    // [num_slots]: frame b's is basis[first + b]
+    DevYaw *out;              // [B][max_det]
+};
+void launch_yaw_solve(const YawArgs &a, int batch, hipStream_t s);
+// stand-alone: quad i of pts [n][8] -> out[i], every quad under the one rule
+void launch_yaw_points(const PnpConst &c, const float *pts, int n, int armor_size, const YawRule &rule, DevYaw *out, hipStream_t s);
 // both solutions, A first: rvec / tvec [n][2][3], err [n][2], ok bit 0 = launch_pnp_only's ok, bit 1 = B passed its own finiteness check
 void launch_pnp_both(const PnpConst &c, const float *pts, int n, int armor_size, double *rvec, double *tvec, double *err,
                      int32_t *ok, hipStream_t s);

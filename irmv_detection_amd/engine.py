@@ -455,6 +455,27 @@ class YoloEngine:
         capi.check(self._L.irmv_engine_pose_alts(self._h, slot, out, self.max_det, C.byref(n)))
         return [out[i] for i in range(n.value)]
 
+    # ---- constrained pose (include/irmv_hip.h; host reference: yaw_solve.py) ----
+    def set_yaw_solve(self, enable: bool = True, rounds: int = 4, tau_max: float = 1.0, horizon_min: float = 1e-4) -> None:
+        """irmv_engine_set_yaw_solve: from the first call on every step also solves, per solved record, the plate's yaw at
+        the class's known tilt (set_pose_prior's normal_up) and the slot's up vector (set_up) and delivers it beside the
+        record (yaw_poses).  The first call re-captures the steps once; later calls, set_up and set_pose_prior are live.  A
+        refused value raises and changes nothing."""
+        o = capi.yaw_opts_struct(1 if enable else 0, rounds, tau_max, horizon_min)
+        capi.check(self._L.irmv_engine_set_yaw_solve(self._h, C.byref(o)))
+
+    def yaw_solve(self) -> dict:
+        o = capi.YawOpts()
+        capi.check(self._L.irmv_engine_get_yaw_solve(self._h, C.byref(o)))
+        return dict(enable=bool(o.enable), rounds=int(o.rounds), tau_max=float(o.tau_max), horizon_min=float(o.horizon_min))
+
+    def yaw_poses(self, slot: int = 0):
+        """capi.YawPose records (copies) parallel to results(slot) / results_raw(slot)."""
+        n = C.c_int(0)
+        out = (capi.YawPose * self.max_det)()
+        capi.check(self._L.irmv_engine_yaw_poses(self._h, slot, out, self.max_det, C.byref(n)))
+        return [out[i] for i in range(n.value)]
+
     def debug_graph_count(self) -> int:
         """Test hook: the captured graphs the engine holds."""
         return int(self._L.irmv_engine_debug_graph_count(self._h))
@@ -853,6 +874,19 @@ class PnPSolver:
                                            rvec.ctypes.data_as(dp), tvec.ctypes.data_as(dp), err.ctypes.data_as(dp),
                                            ok.ctypes.data_as(C.POINTER(C.c_int32))))
         return (ok & 1).astype(bool), (ok & 2).astype(bool), rvec, tvec, err
+
+    def solve_yaw(self, img_pts: np.ndarray, up, normal_up: float, armor_size: int = capi.ARMOR_SMALL, *, rounds: int = 4,
+                  tau_max: float = 1.0, horizon_min: float = 1e-4):
+        """The constrained pose of every quad (irmv_pnp_solve_yaw) under one up vector and one tilt normal_up = n . up:
+        -> list of capi.YawPose."""
+        pts = np.ascontiguousarray(img_pts, np.float32).reshape(-1, 8)
+        n = len(pts)
+        u = np.ascontiguousarray(up, np.float64).reshape(3)
+        o = capi.yaw_opts_struct(1, rounds, tau_max, horizon_min)
+        out = (capi.YawPose * max(n, 1))()
+        capi.check(self._L.irmv_pnp_solve_yaw(self._h, pts.ctypes.data_as(C.POINTER(C.c_float)), n, armor_size,
+                                              u.ctypes.data_as(C.POINTER(C.c_double)), float(normal_up), C.byref(o), out))
+        return [out[i] for i in range(n)]
 
     def calculateDistanceToCenter(self, image_point: Tuple[float, float]) -> float:
         """|p - (cx, cy)|.  The reference reads cx, cy with at<float>() from a

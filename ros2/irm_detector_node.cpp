@@ -48,6 +48,10 @@ public:
     if (!metering.empty() && mr.size() == 4)
       p.metering = YoloEngine::meter_opts(metering == "raw" ? IRMV_METER_RAW : IRMV_METER_VIEW, cv::Point(int(mr[0]), int(mr[1])), cv::Size(int(mr[2]), int(mr[3])), metering_step);
     p.awb_period = int(node_->declare_parameter("awb_period", 0));
+    // constrained pose (IrmDetectorCore::Params::yaw_solve): the plate's yaw solved at its known tilt beside every pose;
+    // yaw_publish: the message carries that pose where it was solved
+    if (node_->declare_parameter("yaw_solve", false)) p.yaw_solve = YoloEngine::yaw_opts();
+    p.yaw_publish = node_->declare_parameter("yaw_publish", false);
     const auto ns = node_->declare_parameter("net_input_size", std::vector<int64_t>{0, 0});   // {width, height}; {0, 0}: square default
     if (ns.size() == 2) p.net_input_size = cv::Size(int(ns[0]), int(ns[1]));
     const std::string model = node_->declare_parameter("model_path", std::string("models/yolov7.onnx"));
