@@ -108,6 +108,10 @@ public:
     // yaw_publish changes nothing.
     irmv_yaw_opts yaw_solve{};
     bool yaw_publish = false;
+    // Plate patches (include/irmv_hip.h): struct_size != 0 enables them on the three engines at creation
+    // (YoloEngine::patch_opts()) -- FrameResult::patches is then filled.  Live: set_parameter "patches" (0 | 1; the first 1
+    // enables).  Models with a keypoint head only, like FrameResult::yaw.
+    irmv_patch_opts patches{};
     bool debug = false;                                  // the node's debug (:90-95, :259-280): every frame also yields FrameResult::visualized_image / binary_image,
                                                          // rendered on the GPU (YoloEngine::render); live through set_bool_parameter("debug", v) like the reference (:380-381)
     int debug_scale = 1;                                 // 1, 2 or 4: the debug images at full, half or quarter size (set_parameter "debug_scale")
@@ -136,6 +140,9 @@ public:
     // Params::yaw_solve only (else empty): parallel to `poses`, the plate's pose with its yaw solved at the class's known tilt
     // and the up vector (state 1; -1: refused, 0: nothing)
     std::vector<irmv_yaw_pose> yaw;
+    // Params::patches only (else empty): parallel to `poses`, each armor's rectified 20 x 28 gray number image, its Otsu
+    // threshold and the colour vote of its two light bars (state 1; 0: no patch)
+    std::vector<irmv_plate_patch> patches;
     double inference_latency_ms = 0;    // YoloEngine::get_profiling_time() (:251)
     // Params::debug only (else empty): the frame with this frame's armors, boxes and labels drawn on it (:261-263; the latency
     // text lines are not drawn), and gray -> threshold(binary_threshold) -> three channels with the boxes and labels (:273-277)
@@ -163,6 +170,7 @@ public:
       if (p.enemy_color != -1 || !p.large_plate_classes.empty()) push_class_policy(*e);
       if (p.pose_prior.struct_size != 0) { e->set_pose_prior(&p.pose_prior); e->set_up(p.up); }
       if (p.yaw_solve.struct_size != 0) { e->set_yaw_solve(p.yaw_solve); e->set_up(p.up); }
+      if (p.patches.struct_size != 0) e->set_patches(p.patches);
     }
     yolo_engines_[0]->warm_up();   // the tile choices are shared by the three engines: one warm-up tunes for all
     for (size_t i = 1; i < yolo_engines_.size(); i++) yolo_engines_[i]->warm_up();
@@ -190,17 +198,20 @@ public:
     std::vector<irmv_det> poses;
     std::vector<irmv_pose_alt> alts;
     std::vector<irmv_yaw_pose> yaws;
+    std::vector<irmv_plate_patch> plates;
     if (eng.has_keypoint_head()) {
       // pose-style model: each detection carries its four points and, already, its pose
       int n = 0;
       const irmv_det * dets = eng.last_detections(&n);
       const std::vector<irmv_pose_alt> all = eng.pose_alts();   // parallel to dets (empty: not enabled)
       const std::vector<irmv_yaw_pose> all_yaw = eng.yaw_poses();
+      const std::vector<irmv_plate_patch> all_plates = eng.plate_patches();
       for (int i = 0; i < n; i++) {
         const irmv_det & d = dets[i];
         if (d.armor_valid != 1) continue;
         if (size_t(i) < all.size()) alts.push_back(all[size_t(i)]);
         if (size_t(i) < all_yaw.size()) yaws.push_back(all_yaw[size_t(i)]);
+        if (size_t(i) < all_plates.size()) plates.push_back(all_plates[size_t(i)]);
         Armor a(Light(cv::Point2f(d.kpts[2], d.kpts[3]), cv::Point2f(d.kpts[0], d.kpts[1])),
                 Light(cv::Point2f(d.kpts[4], d.kpts[5]), cv::Point2f(d.kpts[6], d.kpts[7])));
         a.armor_class = static_cast<ArmorClass>(d.class_id);
@@ -231,6 +242,7 @@ public:
       out.armors.push_back(armors[i]);
       out.poses.push_back(d);
       if (alts.size() == armors.size()) out.alts.push_back(alts[i]);
+      if (plates.size() == armors.size()) out.patches.push_back(plates[i]);
       if (yaws.size() == armors.size()) {
         out.yaw.push_back(yaws[i]);
         if (params_.yaw_publish && yaws[i].state == 1) {     // the constrained pose in place of IPPE's
@@ -327,6 +339,16 @@ public:
       o.enable = int(value);
       params_.yaw_solve = o;
       for (auto & e : yolo_engines_) { e->set_yaw_solve(o); e->set_up(params_.up); }
+      return true;
+    }
+    else if (name == "patches") {
+      // live; the first 1 enables the records (one re-capture per engine), later ones re-capture nothing
+      if (value != 0.0 && value != 1.0) return false;
+      if (value == 0.0 && params_.patches.struct_size == 0) return true;
+      irmv_patch_opts o = params_.patches.struct_size ? params_.patches : YoloEngine::patch_opts();
+      o.enable = int(value);
+      params_.patches = o;
+      for (auto & e : yolo_engines_) e->set_patches(o);
       return true;
     }
     else if (name == "yaw_publish") {

@@ -348,6 +348,42 @@ public:
     return a;
   }
 
+  // ---- plate patches (include/irmv_hip.h, "plate patches") ----
+  // From the first set_patches on every detect() also rectifies, per record with armor_valid == 1, the 20 x 28 gray number
+  // image between the light bars out of the slot's frame: plate_patches().  The first call re-captures the steps once; later
+  // calls re-capture nothing.  A refused value throws, nothing changes.
+  static irmv_patch_opts patch_opts(bool enable = true, int span_small = 32, int span_large = 54, int light_rows = 12, int top = 7)
+  {
+    irmv_patch_opts o{};
+    o.struct_size = sizeof o; o.enable = enable ? 1 : 0; o.span[0] = span_small; o.span[1] = span_large; o.light_rows = light_rows; o.top = top;
+    return o;
+  }
+  void set_patches(const irmv_patch_opts & o = patch_opts())
+  {
+    if (irmv_engine_set_patches(engine_, &o) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::set_patches: ") + irmv_last_error());
+    patches_on_ = true;
+  }
+  irmv_patch_opts patches() const
+  {
+    irmv_patch_opts o;
+    if (irmv_engine_get_patches(engine_, &o) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::patches: ") + irmv_last_error());
+    return o;
+  }
+  // Parallel to last_detections(): entry i is the patch of record i (empty before the first set_patches)
+  std::vector<irmv_plate_patch> plate_patches() const
+  {
+    std::vector<irmv_plate_patch> a;
+    if (!patches_on_) return a;
+    a.resize(dets_.size());
+    int n = 0;
+    if (irmv_engine_plate_patches(engine_, 0, a.data(), static_cast<int>(a.size()), &n) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::plate_patches: ") + irmv_last_error());
+    a.resize(static_cast<size_t>(n));
+    return a;
+  }
+
   // ---- tracking window ----
   bool has_window() const { return window_size_.width > 0 && window_size_.height > 0; }
   // The window's top-left corner in the coordinates bboxes come back in (the rotated frame); from the next detect() on.
@@ -605,6 +641,7 @@ private:
   int enemy_color_ = -1;
   bool pose_alts_on_ = false;         // set_pose_prior has been called: the engine delivers alt records
   bool yaw_on_ = false;               // set_yaw_solve has been called: the engine delivers constrained poses
+  bool patches_on_ = false;           // set_patches has been called: the engine delivers plate patches
   cv::Size src_image_size_;
   cv::Size window_size_;
   bool enable_profiling_ = false;

@@ -662,6 +662,80 @@ int irmv_engine_get_yaw_solve(const irmv_engine *e, irmv_yaw_opts *opts);   /* b
 /* Parallel to irmv_engine_results, as irmv_engine_pose_alts is.  IRMV_ERR_ARG before the first irmv_engine_set_yaw_solve. */
 int irmv_engine_yaw_poses(irmv_engine *e, int slot, irmv_yaw_pose *out, int cap, int *n);
 
+/* ---- plate patches: each armor's rectified number image ---------------------------------------------------------------
+ * A consumer of such a detector cuts the number plate out of the frame between the two light bars, rectifies it with the
+ * four points and hands the small gray image to a number classifier.  From the first irmv_engine_set_patches on, a step does
+ * that for every record with armor_valid == 1 in a kernel of its own behind the NMS (behind the light extraction on classical
+ * and refined engines), on the slot's frame at the sensor's resolution, and delivers one side record per detection
+ * (irmv_engine_plate_patches): the patch, its Otsu threshold and a colour vote of its two light bars.  irmv_det,
+ * irmv_pose_alt, irmv_yaw_pose and irmv_tile_det stay byte-identical whether or not it is on.
+ * irmv_detection_amd/patches.py states the model operation for operation; fp64 in the written order (no fused
+ * multiply-add), divisions are divisions.
+ *   Layout.  The patch is IRMV_PATCH_W = 20 columns by IRMV_PATCH_H = 28 rows.  A rectified image of `span` columns has the
+ *     light bars' centre lines in columns 0 and span - 1 (span[IRMV_ARMOR_SMALL] = 32, span[IRMV_ARMOR_LARGE] = 54), the
+ *     bars' top ends in row `top` = 7 and their bottom ends in row top + light_rows = 19.  The patch is that image's middle
+ *     20 columns: with off = (span - 20) / 2, patch pixel (i, j) -- column i, row j -- has plate coordinates
+ *     s = (i + off) / (span - 1), t = (j - top) / light_rows; t runs past [0, 1] on purpose.
+ *   Mapping (Heckbert's square-to-quad).  The record's eight float keypoints (LB, LT, RT, RB) widened to double;
+ *     p0 = LT, p1 = RT, p2 = RB, p3 = LB:
+ *       dx1 = x1 - x2   dx2 = x3 - x2   sx = ((x0 - x1) + x2) - x3        (the same for y)
+ *       den = dx1 dy2 - dx2 dy1
+ *       g = (sx dy2 - dx2 sy) / den        h = (dx1 sy - sx dy1) / den
+ *       a = (x1 - x0) + g x1   b = (x3 - x0) + h x3   c = x0
+ *       d = (y1 - y0) + g y1   e = (y3 - y0) + h y3   f = y0
+ *       w = (g s + h t) + 1     x = ((a s + b t) + c) / w     y = ((d s + e t) + f) / w
+ *     (x, y) is in the pixels of the frame the slot's step saw, in the coordinates its results come in (W x H): with
+ *     rotate180 the one irmv_engine_rotated_image returns -- the rotation is folded into the fetch --, without it the slot's
+ *     frame as it lies in the buffer.  The records' keypoints are in that frame already; a window slot's result keypoints
+ *     are those plus the window's corner.
+ *   Sampling (integers).  A sample for which 0 <= x <= W - 1 && 0 <= y <= H - 1 is false (NaN fails it) counts in n_outside.
+ *     One for which -1 <= x <= W && -1 <= y <= H is false has value 0.  Every other one: X = floor(32 x + 0.5), ix = X >> 5,
+ *     fx = X & 31, likewise y; texel gray (p0 3735 + p1 19235 + p2 9798 + 2^14) >> 15 (the light extraction's), 0 outside
+ *     the frame; v = (g00 (32 - fx)(32 - fy) + g10 fx (32 - fy) + g01 (32 - fx) fy + g11 fx fy + 512) >> 10.
+ *   Otsu.  N = 560, S = sum v; for k in 0 .. 255: w0 = #(v <= k), w1 = N - w0, m0 = sum(v <= k), A = m0 N - S w0,
+ *     q_k = (double)(A A) / (double)(w0 w1) where w0 > 0 && w1 > 0, else -1.  otsu is the smallest k of maximal q; a patch of
+ *     one gray level reports that level.
+ *   Bar colour vote.  The 2 x (light_rows + 1) points s in {0, 1}, t = r / light_rows; the nearest texel
+ *     ((X + 16) >> 5, (Y + 16) >> 5) under the second guard above; bar_sum[0] sums channel 0, bar_sum[1] channel 2 of the
+ *     texels inside the frame.
+ *   No patch (state 0, the record all zero): armor_valid != 1, a non-finite keypoint, den == 0 or a non-finite coefficient,
+ *     !(w > 0) at any of the 560 samples.  Otherwise state 1.
+ * Nothing is allocated and nothing new is launched until the first irmv_engine_set_patches.  That call waits for everything
+ * in flight, allocates the records and the option table and drops the captured graphs once; later calls rewrite the table
+ * the kernel reads when it runs and re-capture nothing.  enable = 0: the kernel returns at once, and the call zeroes the
+ * records.  The kernel reads the slot's frame where and when the light extraction of a refined engine reads it: the frame the
+ * step was submitted with, under every upload path.  Tiled steps: the patch of merged record r is
+ * irmv_engine_plate_patches(first + r.tile)[r.index]. */
+#define IRMV_PATCH_W 20
+#define IRMV_PATCH_H 28
+typedef struct irmv_patch_opts {
+    uint32_t struct_size;        /* = sizeof(irmv_patch_opts) */
+    int32_t  enable;             /* 0 | 1 */
+    int32_t  span[2];            /* per plate size: 20 .. 128, span - 20 even; default 32, 54 */
+    int32_t  light_rows;         /* 1 .. 28; default 12 */
+    int32_t  top;                /* 0 .. 27; default 7 */
+    int32_t  reserved[2];        /* 0 */
+} irmv_patch_opts;
+typedef struct irmv_plate_patch {
+    uint8_t  gray[IRMV_PATCH_H][IRMV_PATCH_W];
+    int32_t  state, otsu, n_outside, armor_size;   /* armor_size: the record's, whose span the patch used */
+    uint32_t bar_sum[2], sum;                       /* sum: S, the 560 values' */
+    int32_t  reserved;
+} irmv_plate_patch;   /* 592 bytes */
+/* IRMV_ERR_ARG before the engine is looked at, leaving everything as it was: null opts, a wrong struct_size, enable outside
+ * {0, 1}, a value outside its range above, reserved != 0.  Then: a null engine. */
+int irmv_engine_set_patches(irmv_engine *e, const irmv_patch_opts *opts);
+int irmv_engine_get_patches(const irmv_engine *e, irmv_patch_opts *opts);   /* before the first set: the defaults with enable = 0 */
+/* Parallel to irmv_engine_results, as irmv_engine_yaw_poses is.  IRMV_ERR_ARG before the first irmv_engine_set_patches. */
+int irmv_engine_plate_patches(irmv_engine *e, int slot, irmv_plate_patch *out, int cap, int *n);
+/* On demand, on any engine, enabled or not: the patches of n explicit quads (kpts [n][8] in result coordinates, LB LT RT RB;
+ * armor_size [n], IRMV_ARMOR_SMALL / _LARGE) on the slot's current frame in its current view, as irmv_engine_refine_points
+ * acts, under the engine's present options (enable is not read): out [n], 0 <= n <= IRMV_MAX_DET_CAP.  Every quad is taken as
+ * an armor (state is 0 only for the geometric reasons above).  Waits for the engine's steps in flight. */
+int irmv_engine_patches_at(irmv_engine *e, int slot, const float *kpts, const int32_t *armor_size, int n, irmv_plate_patch *out);
+/* out: IRMV_PATCH_W, IRMV_PATCH_H, span min, span max, light_rows max, top max, sizeof(irmv_plate_patch), 0 */
+int irmv_patch_limits(int32_t out[8]);
+
 /* ---- stage-wise read-backs used by the parity tests -------------------- */
 int irmv_engine_read_input(irmv_engine *e, int slot, float *chw);             /* [3][net_h][net_w], as the reference's input_buffer_ */
 int irmv_engine_read_head(irmv_engine *e, int slot, float *head);             /* [A][64+nc+nk], A = irmv_engine_num_anchors(): levels

@@ -213,6 +213,30 @@ def yaw_opts_struct(enable=1, rounds=4, tau_max=1.0, horizon_min=1e-4) -> YawOpt
     return o
 
 
+PATCH_W, PATCH_H = 20, 28
+
+
+class PatchOpts(C.Structure):
+    """irmv_patch_opts (include/irmv_hip.h, "plate patches")."""
+    _fields_ = [("struct_size", C.c_uint32), ("enable", C.c_int32), ("span", C.c_int32 * 2), ("light_rows", C.c_int32),
+                ("top", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class PlatePatch(C.Structure):
+    """irmv_plate_patch (include/irmv_hip.h): the rectified number image of one detection."""
+    _fields_ = [("gray", (C.c_uint8 * PATCH_W) * PATCH_H), ("state", C.c_int32), ("otsu", C.c_int32), ("n_outside", C.c_int32),
+                ("armor_size", C.c_int32), ("bar_sum", C.c_uint32 * 2), ("sum", C.c_uint32), ("reserved", C.c_int32)]
+
+
+def patch_opts_struct(enable=1, span=(32, 54), light_rows=12, top=7) -> PatchOpts:
+    """An irmv_patch_opts (no check: the library's are the ones under test)."""
+    o = PatchOpts()
+    o.struct_size = C.sizeof(PatchOpts)
+    o.enable, o.light_rows, o.top = int(enable), int(light_rows), int(top)
+    o.span[0], o.span[1] = int(span[0]), int(span[1])
+    return o
+
+
 class MeterOpts(C.Structure):
     """irmv_meter_opts (include/irmv_hip.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("domain", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32),
@@ -353,6 +377,11 @@ SYMBOLS = [
     ("irmv_engine_yaw_poses", C.c_int, [_P, C.c_int, C.POINTER(YawPose), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_pnp_solve_yaw", C.c_int, [_P, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double,
                                      C.POINTER(YawOpts), C.POINTER(YawPose)]),
+    ("irmv_engine_set_patches", C.c_int, [_P, C.POINTER(PatchOpts)]),
+    ("irmv_engine_get_patches", C.c_int, [_P, C.POINTER(PatchOpts)]),
+    ("irmv_engine_plate_patches", C.c_int, [_P, C.c_int, C.POINTER(PlatePatch), C.c_int, C.POINTER(C.c_int)]),
+    ("irmv_engine_patches_at", C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int, C.POINTER(PlatePatch)]),
+    ("irmv_patch_limits", C.c_int, [C.POINTER(C.c_int32)]),
     ("irmv_meter_map", C.c_int, [C.POINTER(EngineCfg), C.POINTER(MeterOpts), C.c_int, C.c_int, C.c_int, C.POINTER(MeterMap)]),
     ("irmv_meter_limits", C.c_int, [C.POINTER(C.c_int32)]),
     ("irmv_engine_meter", C.c_int, [_P, C.c_int, C.POINTER(MeterOpts), C.POINTER(FrameStats)]),

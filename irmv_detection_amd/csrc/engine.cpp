@@ -99,6 +99,7 @@ irmv_engine::~irmv_engine()
     if (fout_host) (void)hipHostFree(fout_host);
     if (alts_host) (void)hipHostFree(alts_host);
     if (yaw_host) (void)hipHostFree(yaw_host);
+    if (patch_host) (void)hipHostFree(patch_host);
     if (meter_stats_host) (void)hipHostFree(meter_stats_host);
     if (light_dets_host) (void)hipHostFree(light_dets_host);
     for (auto &kv : tile_merges)
@@ -466,6 +467,7 @@ extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **o
     e->sw = read_switches();
     pose_prior_defaults(&e->pose_prior);
     yaw_opts_defaults(&e->yaw_opts);
+    patch_opts_defaults(&e->patch_opts);
     e->up.assign((size_t)cfg->num_slots * 3, 0.0);
     for (int s = 0; s < cfg->num_slots; s++) e->up[3 * s + 1] = -1.0;   // a level camera: image y points down
     int rc = load_blob(e.get());

@@ -12,6 +12,7 @@
 //   engine_hooks.cpp  read-backs, debug images, debug_*, LDS fill / probe, conv and op test hooks, the profiler, the light trace
 //   engine_meter.cpp  frame metering: its checks and map, the record's host helpers, the on-demand call, the step's op
 //   engine_yaw.cpp    constrained pose: its checks, the two tables and who rewrites them, the step's op, the stand-alone call
+//   engine_patch.cpp  plate patches: their checks, the option table, the step's op, the records' way out, the on-demand call
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -133,7 +134,7 @@ struct EngineSwitches {
     bool nms_stamps = false; int nms_stamps_slots = 0;   // IRMV_NMS_STAMPS=<n>: the NMS kernel stamps its phases, the destructor prints the first n slots' (at least four)
 };
 
-enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_DEMOSAIC, OP_CROP, OP_METER, OP_YAW };
+enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_DEMOSAIC, OP_CROP, OP_METER, OP_YAW, OP_PATCH };
 
 struct Op {
     OpKind kind;
@@ -423,6 +424,17 @@ struct irmv_engine {
     DevYaw *yaw_dev = nullptr, *yaw_host = nullptr, *yaw_host_dev = nullptr;
     YawTable *yaw_table_dev = nullptr;
     YawBasis *yaw_basis_dev = nullptr;        // [S]
+    // Plate patches (irmv_engine_set_patches), behind everything above for the same reason.  Nothing below but patch_opts (a
+    // host value) exists until the first set_patches -- the records ([S][max_det], device and pinned, travelling as the DevYaw
+    // records do), the table, the op (patch_op, behind the NMS / the light extraction in every step plan and run_post's), one
+    // drop of the captured graphs -- or the first irmv_engine_patches_at: the table and the call's three buffers.
+    int patch_op = -1;
+    irmv_patch_opts patch_opts{};
+    DevPatch *patch_dev = nullptr, *patch_host = nullptr, *patch_host_dev = nullptr;
+    PatchTable *patch_table_dev = nullptr;
+    float *patch_at_kpts = nullptr;           // [kMaxDetCap][8]
+    int32_t *patch_at_sizes = nullptr;        // [kMaxDetCap]
+    DevPatch *patch_at_out = nullptr;         // [kMaxDetCap]
 
     ~irmv_engine();
 };
@@ -479,6 +491,7 @@ void finalize_head_fusion(irmv_engine *e);
 void build_step_plans(irmv_engine *e, View &v);
 void add_meter_op(irmv_engine *e);
 void add_yaw_op(irmv_engine *e);
+void add_patch_op(irmv_engine *e);
 // engine_step.cpp
 void fill_conv_args(const irmv_engine *e, const Op &op, int first, int count, ConvArgs &a, bool fused = false);
 int slots_view(const irmv_engine *e, int first, int count, int *view = nullptr);
@@ -507,4 +520,7 @@ int ensure_dense_head(irmv_engine *e, int slot);
 void yaw_opts_defaults(irmv_yaw_opts *o);
 int write_yaw_tables(irmv_engine *e, int slot = -1);   // no-op before the first set_yaw_solve; slot >= 0: that slot's basis alone
 void launch_yaw(const irmv_engine *e, const Step &s, const PostArgs &pa, hipStream_t st);
+// engine_patch.cpp
+void patch_opts_defaults(irmv_patch_opts *o);
+void launch_patch(const irmv_engine *e, const View &v, const Step &s, const PostArgs &pa, hipStream_t st);
 }

@@ -130,21 +130,31 @@ void irmv::add_meter_op(irmv_engine *e)
         if (v.built) add_meter_launch(e, v);
 }
 
-// Constrained pose (e->yaw_op >= 0): the steps of view v and run_post launch the yaw op behind the last kernel that writes the
-// DevDet records -- the NMS, or the light extraction of a classical or refined engine.
-static void add_yaw_launch(const irmv_engine *e, View &v)
+// A side-record op (the constrained pose, the plate patches): the steps of view v and run_post launch it behind the last kernel
+// that writes the DevDet records -- the NMS, or the light extraction of a classical or refined engine.
+static void add_side_launch(const irmv_engine *e, View &v, int op_index, double bytes)
 {
     for (int k : {(int)STEP_BATCH, (int)STEP_ONE, (int)STEP_POST}) {
         std::vector<Launch> &plan = v.plans[k];
         size_t at = plan.size();
         for (size_t i = 0; i < plan.size(); i++)
             if (e->ops[plan[i].op].kind == OP_NMS || e->ops[plan[i].op].kind == OP_LIGHT) at = i + 1;
-        const Op &op = e->ops[e->yaw_op];
-        Launch l; l.op = e->yaw_op;
+        const Op &op = e->ops[op_index];
+        Launch l; l.op = op_index;
         l.name = op.kname; l.layer = op.layer;
-        l.bytes = (double)e->cfg.max_det * (sizeof(DevDet) + sizeof(DevYaw));
+        l.bytes = bytes;
         plan.insert(plan.begin() + at, l);
     }
+}
+
+static void add_yaw_launch(const irmv_engine *e, View &v)
+{
+    add_side_launch(e, v, e->yaw_op, (double)e->cfg.max_det * (sizeof(DevDet) + sizeof(DevYaw)));
+}
+
+static void add_patch_launch(const irmv_engine *e, View &v)
+{
+    add_side_launch(e, v, e->patch_op, (double)e->cfg.max_det * (sizeof(DevDet) + sizeof(DevPatch)));
 }
 
 // The first irmv_engine_set_yaw_solve: the op, appended to e->ops, and its launch in the plans of every view built so far (a
@@ -156,6 +166,16 @@ void irmv::add_yaw_op(irmv_engine *e)
     e->yaw_op = (int)e->ops.size() - 1;
     for (View &v : e->views)
         if (v.built) add_yaw_launch(e, v);
+}
+
+// The first irmv_engine_set_patches, likewise
+void irmv::add_patch_op(irmv_engine *e)
+{
+    Op op; op.kind = OP_PATCH; op.layer = "plate_patch"; snprintf(op.kname, sizeof op.kname, "plate_patch");
+    e->ops.push_back(op);
+    e->patch_op = (int)e->ops.size() - 1;
+    for (View &v : e->views)
+        if (v.built) add_patch_launch(e, v);
 }
 
 // The one place that decides which ops of e->ops a step of each kind launches in view v, and how.  The views differ in front
@@ -170,7 +190,7 @@ void irmv::build_step_plans(irmv_engine *e, View &v)
         for (int i = 0; i < (int)e->ops.size(); i++) {
             const Op &op = e->ops[i];
             if (op.kind == OP_FRONT) continue;   // (launched where model.1.conv stands, below)
-            if (op.kind == OP_METER || op.kind == OP_YAW) continue;   // (added behind the loop)
+            if (op.kind == OP_METER || op.kind == OP_YAW || op.kind == OP_PATCH) continue;   // (added behind the loop)
             if (op.kind == OP_CROP && !v.crop) continue;
             const bool away = is_front_layer(i) ? v.fused_front : op.fused_away;   // the layers a fused kernel covers in this view
             if (post && op.kind != OP_NMS && op.kind != OP_LIGHT && op.kind != OP_SCAN) continue;
@@ -229,4 +249,5 @@ void irmv::build_step_plans(irmv_engine *e, View &v)
     }
     if (e->meter_op >= 0) add_meter_launch(e, v);
     if (e->yaw_op >= 0) add_yaw_launch(e, v);
+    if (e->patch_op >= 0) add_patch_launch(e, v);
 }

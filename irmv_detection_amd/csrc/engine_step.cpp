@@ -349,6 +349,7 @@ int irmv::launch_op(irmv_engine *e, const View &v, const Launch &l, const Step &
     case OP_CROP: launch_crop(e, t, s); break;
     case OP_METER: launch_meter(e, v, t, s); break;
     case OP_YAW: launch_yaw(e, t, pa, s); break;
+    case OP_PATCH: launch_patch(e, v, t, pa, s); break;
     case OP_PRE: launch_preprocess(pre_args(e, v, op, first), count, s); break;
     case OP_FRONT: if (!launch_front(front_args(e, v, op, first), count, s)) return fail(IRMV_ERR_HIP, "fused front kernel: LDS request refused"); break;
     case OP_C2F2: launch_c2f2(c2f2_args(e, op, first), count, s); break;
@@ -497,6 +498,10 @@ static int copy_out_dev(irmv_engine *e, int first, int count, hipStream_t st, bo
     if (e->yaw_op >= 0)
         HIP_TRY(hipMemcpyAsync(e->yaw_host + (size_t)first * e->cfg.max_det, e->yaw_dev + (size_t)first * e->cfg.max_det,
                                (size_t)count * e->cfg.max_det * sizeof(DevYaw), hipMemcpyDeviceToHost, st));
+    // (disabled: the kernel returns at once and set_patches has zeroed both copies -- max_det records of 592 bytes stay where they are)
+    if (e->patch_op >= 0 && e->patch_opts.enable)
+        HIP_TRY(hipMemcpyAsync(e->patch_host + (size_t)first * e->cfg.max_det, e->patch_dev + (size_t)first * e->cfg.max_det,
+                               (size_t)count * e->cfg.max_det * sizeof(DevPatch), hipMemcpyDeviceToHost, st));
     return IRMV_OK;
 }
 

@@ -707,6 +707,35 @@ struct YawArgs {
 void launch_yaw_solve(const YawArgs &a, int batch, hipStream_t s);
 // stand-alone: quad i of pts [n][8] -> out[i], every quad under the one rule
 void launch_yaw_points(const PnpConst &c, const float *pts, int n, int armor_size, const YawRule &rule, DevYaw *out, hipStream_t s);
+
+// ---- plate patches (k_patch.hip; irmv_engine_set_patches) ---------------------------------------------------------------
+// DevPatch is the side record of one detection (the layout of irmv_plate_patch).  PatchTable lives in device memory at an
+// address fixed from the first set_patches (or patches_at) on; the host writes it, the kernel reads it when it runs.
+constexpr int kPatchW = 20, kPatchH = 28, kPatchN = kPatchW * kPatchH, kPatchWords = kPatchN / 4;
+constexpr int kPatchThreads = 256, kPatchPerBlock = kPatchThreads / 64;
+constexpr int kPatchSpanMin = 20, kPatchSpanMax = 128, kPatchRowsMax = 28, kPatchTopMax = 27;
+struct DevPatch {
+    uint32_t gray[kPatchWords];   // [28][20] bytes, row-major: a word is four neighbouring samples of a row
+    int32_t state, otsu, n_outside, armor_size;
+    uint32_t bar_sum[2], sum;
+    int32_t pad_;
+};
+struct PatchTable { int32_t enable, span[2], light_rows, top, pad_[3]; };
+struct PatchArgs {
+    const uint8_t *frames;    // [B][H][W][3] device frames, un-rotated (rotation folded into the fetch): LightArgs::frames
+    size_t frame_bytes;
+    int W, H, rotate180;
+    const DevDet *dets;       // [B][max_det]: the records the post stage wrote
+    int max_det;
+    const int *num_dets;      // frame b: num_dets[b * num_dets_stride]
+    int num_dets_stride;
+    const PatchTable *table;
+    DevPatch *out;            // [B][max_det]
+};
+void launch_patch_step(const PatchArgs &a, int batch, hipStream_t s);
+// on demand: quad i of kpts [n][8] (frame coordinates) with plate sizes[i] on the one frame a.frames -> a.out[i]; a.dets,
+// a.num_dets and the table's enable are not read
+void launch_patch_points(const PatchArgs &a, const float *kpts, const int32_t *sizes, int n, hipStream_t s);
 // both solutions, A first: rvec / tvec [n][2][3], err [n][2], ok bit 0 = launch_pnp_only's ok, bit 1 = B passed its own finiteness check
 void launch_pnp_both(const PnpConst &c, const float *pts, int n, int armor_size, double *rvec, double *tvec, double *err,
                      int32_t *ok, hipStream_t s);

@@ -476,6 +476,38 @@ class YoloEngine:
         capi.check(self._L.irmv_engine_yaw_poses(self._h, slot, out, self.max_det, C.byref(n)))
         return [out[i] for i in range(n.value)]
 
+    # ---- plate patches (include/irmv_hip.h; host reference: patches.py) ----
+    def set_patches(self, enable: bool = True, span=(32, 54), light_rows: int = 12, top: int = 7) -> None:
+        """irmv_engine_set_patches: from the first call on every step also rectifies, per record with armor_valid == 1, the
+        20 x 28 gray number image between the light bars out of the slot's frame and delivers it, its Otsu threshold and the
+        bars' colour vote beside the record (plate_patches).  The first call re-captures the steps once; later calls are live.
+        A refused value raises and changes nothing."""
+        o = capi.patch_opts_struct(1 if enable else 0, span, light_rows, top)
+        capi.check(self._L.irmv_engine_set_patches(self._h, C.byref(o)))
+
+    def patches(self) -> dict:
+        o = capi.PatchOpts()
+        capi.check(self._L.irmv_engine_get_patches(self._h, C.byref(o)))
+        return dict(enable=bool(o.enable), span=(int(o.span[0]), int(o.span[1])), light_rows=int(o.light_rows), top=int(o.top))
+
+    def plate_patches(self, slot: int = 0):
+        """capi.PlatePatch records (copies) parallel to results(slot) / results_raw(slot)."""
+        n = C.c_int(0)
+        out = (capi.PlatePatch * self.max_det)()
+        capi.check(self._L.irmv_engine_plate_patches(self._h, slot, out, self.max_det, C.byref(n)))
+        return [out[i] for i in range(n.value)]
+
+    def patches_at(self, kpts: np.ndarray, armor_size, slot: int = 0):
+        """irmv_engine_patches_at: the patches of explicit quads ([n, 8] LB LT RT RB in result coordinates; armor_size one
+        value or [n]) on the slot's current frame, on any engine, under the present options -> list of capi.PlatePatch."""
+        pts = np.ascontiguousarray(kpts, np.float32).reshape(-1, 8)
+        n = len(pts)
+        sizes = np.ascontiguousarray(np.broadcast_to(np.asarray(armor_size, np.int32), (n,)))
+        out = (capi.PlatePatch * max(n, 1))()
+        capi.check(self._L.irmv_engine_patches_at(self._h, slot, pts.ctypes.data_as(C.POINTER(C.c_float)),
+                                                  sizes.ctypes.data_as(C.POINTER(C.c_int32)), n, out))
+        return [out[i] for i in range(n)]
+
     def debug_graph_count(self) -> int:
         """Test hook: the captured graphs the engine holds."""
         return int(self._L.irmv_engine_debug_graph_count(self._h))

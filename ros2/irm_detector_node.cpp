@@ -52,6 +52,9 @@ public:
     // yaw_publish: the message carries that pose where it was solved
     if (node_->declare_parameter("yaw_solve", false)) p.yaw_solve = YoloEngine::yaw_opts();
     p.yaw_publish = node_->declare_parameter("yaw_publish", false);
+    // plate patches (IrmDetectorCore::Params::patches): each armor's rectified number image beside its pose (FrameResult::patches;
+    // not published)
+    if (node_->declare_parameter("patches", false)) p.patches = YoloEngine::patch_opts();
     const auto ns = node_->declare_parameter("net_input_size", std::vector<int64_t>{0, 0});   // {width, height}; {0, 0}: square default
     if (ns.size() == 2) p.net_input_size = cv::Size(int(ns[0]), int(ns[1]));
     const std::string model = node_->declare_parameter("model_path", std::string("models/yolov7.onnx"));
