@@ -300,17 +300,7 @@ public:
     return u;
   }
   // Parallel to last_detections(): entry i is the other solution of record i (empty before the first set_pose_prior)
-  std::vector<irmv_pose_alt> pose_alts() const
-  {
-    std::vector<irmv_pose_alt> a;
-    if (!pose_alts_on_) return a;
-    a.resize(dets_.size());
-    int n = 0;
-    if (irmv_engine_pose_alts(engine_, 0, a.data(), static_cast<int>(a.size()), &n) != IRMV_OK)
-      throw std::runtime_error(std::string("YoloEngine::pose_alts: ") + irmv_last_error());
-    a.resize(static_cast<size_t>(n));
-    return a;
-  }
+  std::vector<irmv_pose_alt> pose_alts() const { return side_records<irmv_pose_alt>(pose_alts_on_, irmv_engine_pose_alts, "pose_alts"); }
 
   // ---- constrained pose (include/irmv_hip.h, "constrained pose") ----
   // From the first set_yaw_solve on every detect() also solves, per solved record, the plate's yaw at the class's known tilt
@@ -336,17 +326,7 @@ public:
     return o;
   }
   // Parallel to last_detections(): entry i is the constrained pose of record i (empty before the first set_yaw_solve)
-  std::vector<irmv_yaw_pose> yaw_poses() const
-  {
-    std::vector<irmv_yaw_pose> a;
-    if (!yaw_on_) return a;
-    a.resize(dets_.size());
-    int n = 0;
-    if (irmv_engine_yaw_poses(engine_, 0, a.data(), static_cast<int>(a.size()), &n) != IRMV_OK)
-      throw std::runtime_error(std::string("YoloEngine::yaw_poses: ") + irmv_last_error());
-    a.resize(static_cast<size_t>(n));
-    return a;
-  }
+  std::vector<irmv_yaw_pose> yaw_poses() const { return side_records<irmv_yaw_pose>(yaw_on_, irmv_engine_yaw_poses, "yaw_poses"); }
 
   // ---- plate patches (include/irmv_hip.h, "plate patches") ----
   // From the first set_patches on every detect() also rectifies, per record with armor_valid == 1, the 20 x 28 gray number
@@ -372,17 +352,7 @@ public:
     return o;
   }
   // Parallel to last_detections(): entry i is the patch of record i (empty before the first set_patches)
-  std::vector<irmv_plate_patch> plate_patches() const
-  {
-    std::vector<irmv_plate_patch> a;
-    if (!patches_on_) return a;
-    a.resize(dets_.size());
-    int n = 0;
-    if (irmv_engine_plate_patches(engine_, 0, a.data(), static_cast<int>(a.size()), &n) != IRMV_OK)
-      throw std::runtime_error(std::string("YoloEngine::plate_patches: ") + irmv_last_error());
-    a.resize(static_cast<size_t>(n));
-    return a;
-  }
+  std::vector<irmv_plate_patch> plate_patches() const { return side_records<irmv_plate_patch>(patches_on_, irmv_engine_plate_patches, "plate_patches"); }
 
   // ---- tracking window ----
   bool has_window() const { return window_size_.width > 0 && window_size_.height > 0; }
@@ -624,6 +594,20 @@ private:
   }
 
   irmv_engine * engine_ = nullptr;
+  // Slot 0's side records of one kind, parallel to last_detections(): empty until the feature's first set (`on`), then what
+  // the library's call `get` delivers; `who` names the caller in a thrown error.
+  template <typename R>
+  std::vector<R> side_records(bool on, int (*get)(irmv_engine *, int, R *, int, int *), const char * who) const
+  {
+    std::vector<R> a;
+    if (!on) return a;
+    a.resize(dets_.size());
+    int n = 0;
+    if (get(engine_, 0, a.data(), static_cast<int>(a.size()), &n) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::") + who + ": " + irmv_last_error());
+    a.resize(static_cast<size_t>(n));
+    return a;
+  }
   // caller's policy + colour -> one table upload; on a refusal nothing is stored
   void apply_class_policy(const irmv_class_policy & p, int enemy_color, const char * who)
   {

@@ -95,12 +95,7 @@ irmv_engine::~irmv_engine()
     for (const DevRange &r : dev_allocs) (void)hipFree(r.base);
     dev_allocs.clear();
     if (src_host) (void)hipHostFree(src_host);
-    if (dets_host) (void)hipHostFree(dets_host);
-    if (fout_host) (void)hipHostFree(fout_host);
-    if (alts_host) (void)hipHostFree(alts_host);
-    if (yaw_host) (void)hipHostFree(yaw_host);
-    if (patch_host) (void)hipHostFree(patch_host);
-    if (meter_stats_host) (void)hipHostFree(meter_stats_host);
+    dets.free_host(); fout.free_host(); alts.free_host(); yaw.free_host(); patch.free_host(); meter.free_host();   // the record channels
     if (light_dets_host) (void)hipHostFree(light_dets_host);
     for (auto &kv : tile_merges)
         if (kv.second.out_host) (void)hipHostFree(kv.second.out_host);
@@ -889,12 +884,8 @@ static int enable_pose_alt(irmv_engine *e)
     const size_t n = (size_t)e->cfg.num_slots * e->cfg.max_det;
     // DevAlt: doubles, and two int32 flags (state, alt_ok) that only the host reads; nms_pnp_kernel<true> / light_extract write
     // the records of [0, num_dets), no kernel reads one
-    TRY(dev_alloc(e, (void **)&e->alts_dev, n * sizeof(DevAlt), "alts_dev", mem_scratch(MEM_F64)));
-    HIP_TRY(hipMemset(e->alts_dev, 0, n * sizeof(DevAlt)));
-    HIP_TRY(hipHostMalloc((void **)&e->alts_host, n * sizeof(DevAlt), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(hipHostGetDevicePointer((void **)&e->alts_host_dev, e->alts_host, 0));
-    memset(e->alts_host, 0, n * sizeof(DevAlt));
-    log_range(e, "pinned alts_host", e->alts_host, n * sizeof(DevAlt));
+    TRY(dev_alloc(e, (void **)&e->alts.dev, n * sizeof(DevAlt), "alts_dev", mem_scratch(MEM_F64)));
+    TRY(e->alts.pin(e, e->cfg.num_slots, e->cfg.max_det, "pinned alts_host"));
     TRY(dev_alloc(e, (void **)&e->prior_dev, sizeof(PosePrior), "prior_dev", mem_const(MEM_F64)));   // host-written tables, read when the kernel runs
     TRY(dev_alloc(e, (void **)&e->up_dev, e->up.size() * sizeof(double), "up_dev", mem_const(MEM_F64)));
     HIP_TRY(hipMemcpy(e->up_dev, e->up.data(), e->up.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -962,10 +953,7 @@ extern "C" int irmv_engine_pose_alts(irmv_engine *e, int slot, irmv_pose_alt *ou
     if (!n || (cap > 0 && !out)) return fail(IRMV_ERR_ARG, "out/n is null");
     if (!e->pose_alt) return fail(IRMV_ERR_ARG, "irmv_engine_pose_alts: irmv_engine_set_pose_prior has not been called on this engine");
     static_assert(sizeof(DevAlt) == sizeof(irmv_pose_alt), "DevAlt is irmv_pose_alt");
-    const int k = std::max(0, std::min(std::min(e->fout_host[slot].num_dets, e->cfg.max_det), cap));
-    if (k) memcpy(out, e->alts_host + (size_t)slot * e->cfg.max_det, (size_t)k * sizeof(irmv_pose_alt));
-    *n = k;
-    return IRMV_OK;
+    return e->alts.deliver(e, slot, out, cap, n);
 }
 
 extern "C" int irmv_engine_get_bayer_isp(const irmv_engine *e, uint16_t gain_q8[3], uint8_t *lut)

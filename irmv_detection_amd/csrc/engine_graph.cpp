@@ -836,25 +836,17 @@ static int build_post_stage(irmv_engine *e)
     // read by the host alone; armor_size (0 / 1) is the host's index into the plate sizes.  The largest word valid in every one
     // of them is 1 (0 for a model of one class).  Records at and above num_dets are read by no kernel.
     const uint32_t det_max = e->nc > 1 ? 1u : 0u;
-    TRY(dev_alloc(e, (void **)&e->dets_dev, (size_t)S * c.max_det * sizeof(DevDet), "dets_dev", mem_scratch_index(det_max)));
+    TRY(dev_alloc(e, (void **)&e->dets.dev, (size_t)S * c.max_det * sizeof(DevDet), "dets_dev", mem_scratch_index(det_max)));
     // num_dets is the record count of light_extract_kernel (min(n, max_det), a negative count runs nothing), refine_prior_kernel
     // and tile_merge_kernel (clamped to [0, max_det]); n_candidates (<= A nc) and the rest go to the host
-    TRY(dev_alloc(e, (void **)&e->fout_dev, (size_t)S * sizeof(DevFrameOut), "fout_dev", mem_scratch_index((uint32_t)c.max_det)));
-    HIP_TRY(hipMemset(e->dets_dev, 0, (size_t)S * c.max_det * sizeof(DevDet)));
-    HIP_TRY(hipMemset(e->fout_dev, 0, (size_t)S * sizeof(DevFrameOut)));
+    TRY(dev_alloc(e, (void **)&e->fout.dev, (size_t)S * sizeof(DevFrameOut), "fout_dev", mem_scratch_index((uint32_t)c.max_det)));
     // Result records live in mapped, coherent pinned memory: in keypoint mode the NMS kernel stores them there directly
     // (~20 KB per frame over PCIe, visible to the host once the stream is synchronised), which removes the D2H copies of
     // a step -- measured 9.6 us per synchronous call on this stack (scripts/probes/stream_probe.cpp), and copies issued
     // from the compute streams also halve the upload stream's H2D rate.  The classical mode (light_extract_kernel
     // reads and rewrites the records on the device) keeps device records + a copy.
-    HIP_TRY(hipHostMalloc((void **)&e->dets_host, (size_t)S * c.max_det * sizeof(DevDet), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(hipHostMalloc((void **)&e->fout_host, (size_t)S * sizeof(DevFrameOut), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(hipHostGetDevicePointer((void **)&e->dets_host_dev, e->dets_host, 0));
-    HIP_TRY(hipHostGetDevicePointer((void **)&e->fout_host_dev, e->fout_host, 0));
-    log_range(e, "pinned dets_host", e->dets_host, (size_t)S * c.max_det * sizeof(DevDet));
-    log_range(e, "pinned fout_host", e->fout_host, (size_t)S * sizeof(DevFrameOut));
-    memset(e->dets_host, 0, (size_t)S * c.max_det * sizeof(DevDet));
-    memset(e->fout_host, 0, (size_t)S * sizeof(DevFrameOut));
+    TRY(e->dets.pin(e, S, c.max_det, "pinned dets_host"));
+    TRY(e->fout.pin(e, S, 1, "pinned fout_host"));
     // class-logit scan + box decode of the candidate anchors: kScanBlocks workgroups per frame (k_post.hip)
     if (e->sw.split_scan) {
         Op op; op.kind = OP_SCAN; op.layer = "scan_decode"; snprintf(op.kname, sizeof op.kname, "scan_decode");

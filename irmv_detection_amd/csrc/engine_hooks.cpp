@@ -940,8 +940,8 @@ extern "C" int irmv_engine_read_raw(irmv_engine *e, int slot, irmv_raw_dets *out
 {
     TRY(check_range(e, slot, 1));
     if (!out) return fail(IRMV_ERR_ARG, "out is null");
-    const DevFrameOut &fo = e->fout_host[slot];
-    const DevDet *d = e->dets_host + (size_t)slot * e->cfg.max_det;
+    const DevFrameOut &fo = *e->fout.host_at(slot);
+    const DevDet *d = e->dets.host_at(slot);
     out->num_dets = fo.num_dets;
     out->n_candidates = fo.n_candidates;
     for (int i = 0; i < e->cfg.max_det; i++) {

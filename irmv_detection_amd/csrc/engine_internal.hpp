@@ -4,15 +4,17 @@
 //                     window ABI, extract-parameter and Bayer-ISP setters, the PnP object
 //   engine_graph.cpp  .irmw blob, tensors, weight packing, the op list (build_engine)
 //   engine_tune.cpp   everything decided by timing at creation: conv tiles and their cache, head groups, the synchronous launch form
-//   engine_plan.cpp   head fusion, the sparse head's reordering, the launch list of each step kind
+//   engine_plan.cpp   head fusion, the sparse head's reordering, the launch list of each step kind, the ops a feature appends
+//                     to the steps and where their launches stand (append_op)
 //   engine_step.cpp   kernel arguments, the per-op launcher, steps (Step), the upload decision (choose_upload / enqueue_upload),
-//                     result copies, graph capture, the one submit path of ordinary and tiled steps (submit_group), wait / results
+//                     the record channels (Records<T>: pinning, where a step writes, result copies, delivery), graph capture,
+//                     the one submit path of ordinary and tiled steps (submit_group), wait / results
 //   engine_tiles.cpp  tiled search: its checks, the merge's device state and arguments, the tiled submit's call of submit_group,
 //                     the merge hook, the merged results and the merge parameters
 //   engine_hooks.cpp  read-backs, debug images, debug_*, LDS fill / probe, conv and op test hooks, the profiler, the light trace
-//   engine_meter.cpp  frame metering: its checks and map, the record's host helpers, the on-demand call, the step's op
-//   engine_yaw.cpp    constrained pose: its checks, the two tables and who rewrites them, the step's op, the stand-alone call
-//   engine_patch.cpp  plate patches: their checks, the option table, the step's op, the records' way out, the on-demand call
+//   engine_meter.cpp  frame metering: its checks and map, the record's host helpers, the on-demand call, the step's launch
+//   engine_yaw.cpp    constrained pose: its checks, the two tables and who rewrites them, the step's launch, the stand-alone call
+//   engine_patch.cpp  plate patches: their checks, the option table, the step's launch, the on-demand call
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -264,6 +266,29 @@ struct irmv_pnp {
 };
 int pnp_reserve(irmv_pnp *p, int n);           // engine.cpp: the object's buffers for n quads
 
+// A record channel: the records a step writes per slot -- its result list, or a feature's side records beside it -- and their
+// way to the host.  `dev` is a dev_alloc range of the feature's own site (which says who writes and who reads it); pin() gives
+// it the twin `host` in mapped, coherent pinned memory and that memory's device view `host_dev`.  A step writes ONE of the two
+// -- step_at() decides which, and nothing else does --, copy() moves slots between them, the host reads `host` alone.
+// per_slot: max_det, or 1 for a per-frame record.  One implementation for every channel (engine_step.cpp).
+struct irmv_engine;
+template <typename T> struct Records {
+    T *dev = nullptr, *host = nullptr, *host_dev = nullptr;
+    int per_slot = 0;
+    T *dev_at(int slot) const { return dev + (size_t)slot * per_slot; }
+    const T *host_at(int slot) const { return host + (size_t)slot * per_slot; }
+    // the pinned twin of dev's first slots * per_slot records, both zeroed; `what`: log_range's text
+    int pin(const irmv_engine *e, int slots, int per_slot, const char *what);
+    // where step s writes its first slot's records: the pinned memory (zero-copy results) or the device records
+    T *step_at(const irmv_engine *e, const Step &s) const;
+    // slots [first, first + count) from one copy to the other on stream st
+    int copy(int first, int count, hipMemcpyKind dir, hipStream_t st) const;
+    int zero(int slots) const;   // both copies
+    // the first min(num_dets, max_det, cap) records of the slot's pinned list -> out, their number -> *n
+    int deliver(const irmv_engine *e, int slot, void *out, int cap, int *n) const;
+    void free_host();
+};
+
 struct irmv_engine {
     irmv_engine_cfg cfg{};
     int nc = 0, nk = 0, A = 0, no = 0;
@@ -354,11 +379,10 @@ struct irmv_engine {
     ClassTable *cls_dev = nullptr;
     irmv_class_policy policy{};       // the policy in force (the uniform one of cfg.score_thr / cfg.armor_size until set)
     // Pose ambiguity (irmv_engine_set_pose_prior).  Until the first call nothing but `up` and `pose_prior` (host values) exists
-    // and every step launches what it always has.  The first call allocates the alt records -- [S][max_det] on the device and
-    // pinned, travelling exactly as the DevDet records do (post_args, copy_out) --, the prior table and the per-slot up vectors,
-    // and drops the captured graphs once: from then on the steps launch the kAlt kernels, which read both tables when they run.
+    // and every step launches what it always has.  The first call allocates the alt records (`alts` below), the prior table and
+    // the per-slot up vectors, and drops the captured graphs once: from then on the steps launch the kAlt kernels, which read
+    // both tables when they run.
     bool pose_alt = false;
-    DevAlt *alts_dev = nullptr, *alts_host = nullptr, *alts_host_dev = nullptr;
     PosePrior *prior_dev = nullptr;
     double *up_dev = nullptr;             // [S][3]
     std::vector<double> up;               // [S][3] unit vectors as set (default (0, -1, 0)), in the frame PnP sees
@@ -387,20 +411,24 @@ struct irmv_engine {
     std::vector<RenderMark> render_marks_host;
     // Frame metering (irmv_engine_meter / irmv_engine_set_metering): nothing below exists until the first metering call.  That
     // call makes the scratch: the partials slab, the two parameter records -- [0] the step's, [1] the on-demand call's -- and the
-    // device records, [num_slots] the steps' and one more for the on-demand call.  The first set_metering with options adds the
-    // pinned records (travelling exactly as the DevDet records do: meter_args, copy_out), the op (meter_op, the last of `ops`)
-    // and its launch in every built view's step plans, and drops the captured graphs once.
+    // device records (`meter` below), [num_slots] the steps' and one more for the on-demand call.  The first set_metering with
+    // options pins the steps' records, appends the op (meter_op: its launch stands in every view's step plans) and drops the
+    // captured graphs once.
     uint32_t *meter_slab = nullptr;          // [S][kMeterBlocksMax][4][256]
     MeterParams *meter_params_dev = nullptr; // [2]
-    MeterStats *meter_stats_dev = nullptr;   // [S + 1]
-    MeterStats *meter_stats_host = nullptr, *meter_stats_host_dev = nullptr;   // [S] pinned, and its device view
     int meter_op = -1;                       // >= 0: the steps meter
     bool meter_on = false;                   // the options in force are not "off"
     irmv_meter_opts meter_opts{};
     float *boxes = nullptr;
     unsigned long long *keys = nullptr;
-    DevDet *dets_dev = nullptr, *dets_host = nullptr, *dets_host_dev = nullptr;       // *_host_dev: device view of the pinned buffer
-    DevFrameOut *fout_dev = nullptr, *fout_host = nullptr, *fout_host_dev = nullptr;
+    // The record channels, in copy-out order.  dets and fout exist from creation; each of the others from its feature's first
+    // enable (the comments above), with [S][max_det] records -- meter: [S + 1] device records, of which the first S are pinned.
+    Records<MeterStats> meter;
+    Records<DevDet> dets;
+    Records<DevFrameOut> fout;
+    Records<DevAlt> alts;
+    Records<DevYaw> yaw;
+    Records<DevPatch> patch;
     bool zero_copy_results = false;   // the NMS kernel writes its results straight into pinned host memory (no D2H copy)
     half_t *conv0_w = nullptr;
     float *conv0_b = nullptr;
@@ -414,23 +442,19 @@ struct irmv_engine {
     std::vector<std::vector<float>> merged_b;
     bool merge_head0 = false;
     EngineSwitches sw{};       // the environment as irmv_engine_create found it
-    // (last, so that every member above lies where it lay before the feature)
     // Constrained pose (irmv_engine_set_yaw_solve): nothing below but yaw_opts (a host value) exists until the first call.  It
-    // allocates the records -- [S][max_det] on the device and pinned, travelling exactly as the DevAlt records do --, the table
-    // and the per-slot bases, appends the op (yaw_op, behind the NMS / the light extraction in every step plan and run_post's)
-    // and drops the captured graphs once.  set_up, set_pose_prior and later calls rewrite the two tables (write_yaw_tables).
+    // allocates the records (`yaw` above), the table and the per-slot bases, appends the op (yaw_op, behind the NMS / the light
+    // extraction in every step plan and run_post's) and drops the captured graphs once.  set_up, set_pose_prior and later calls
+    // rewrite the two tables (write_yaw_tables).
     int yaw_op = -1;
     irmv_yaw_opts yaw_opts{};
-    DevYaw *yaw_dev = nullptr, *yaw_host = nullptr, *yaw_host_dev = nullptr;
     YawTable *yaw_table_dev = nullptr;
     YawBasis *yaw_basis_dev = nullptr;        // [S]
-    // Plate patches (irmv_engine_set_patches), behind everything above for the same reason.  Nothing below but patch_opts (a
-    // host value) exists until the first set_patches -- the records ([S][max_det], device and pinned, travelling as the DevYaw
-    // records do), the table, the op (patch_op, behind the NMS / the light extraction in every step plan and run_post's), one
-    // drop of the captured graphs -- or the first irmv_engine_patches_at: the table and the call's three buffers.
+    // Plate patches (irmv_engine_set_patches).  Nothing below but patch_opts (a host value) exists until the first set_patches
+    // -- the records (`patch` above), the table, the op (patch_op, placed as yaw_op is), one drop of the captured graphs -- or
+    // the first irmv_engine_patches_at: the table and the call's three buffers.
     int patch_op = -1;
     irmv_patch_opts patch_opts{};
-    DevPatch *patch_dev = nullptr, *patch_host = nullptr, *patch_host_dev = nullptr;
     PatchTable *patch_table_dev = nullptr;
     float *patch_at_kpts = nullptr;           // [kMaxDetCap][8]
     int32_t *patch_at_sizes = nullptr;        // [kMaxDetCap]
@@ -489,9 +513,7 @@ int choose_sync_launch(irmv_engine *e);
 // engine_plan.cpp
 void finalize_head_fusion(irmv_engine *e);
 void build_step_plans(irmv_engine *e, View &v);
-void add_meter_op(irmv_engine *e);
-void add_yaw_op(irmv_engine *e);
-void add_patch_op(irmv_engine *e);
+void append_op(irmv_engine *e, OpKind kind);   // OP_METER, OP_YAW or OP_PATCH, at its feature's first enable
 // engine_step.cpp
 void fill_conv_args(const irmv_engine *e, const Op &op, int first, int count, ConvArgs &a, bool fused = false);
 int slots_view(const irmv_engine *e, int first, int count, int *view = nullptr);

@@ -146,7 +146,7 @@ extern "C" int irmv_stats_exposure_q8(const irmv_frame_stats *s, int row, uint64
 // parameter records (off), the device records (zero).
 static int ensure_meter(irmv_engine *e)
 {
-    if (e->meter_stats_dev) return IRMV_OK;
+    if (e->meter.dev) return IRMV_OK;
     const size_t S = (size_t)e->cfg.num_slots;
     // partial histograms: 32-bit counts that the second kernel of a launch sums -- values, never indices
     if (!e->meter_slab) TRY(dev_alloc(e, (void **)&e->meter_slab, S * kMeterBlocksMax * 1024 * sizeof(uint32_t), "meter_slab", mem_scratch(MEM_F32)));
@@ -157,7 +157,7 @@ static int ensure_meter(irmv_engine *e)
     // the records: counts, the clipped rectangle and the echo of the options, written by the summing kernel, read by the host
     TRY(dev_alloc(e, (void **)&st, (S + 1) * sizeof(MeterStats), "meter_stats", mem_scratch(MEM_F32)));
     HIP_TRY(hipMemset(st, 0, (S + 1) * sizeof(MeterStats)));
-    e->meter_stats_dev = st;
+    e->meter.dev = st;
     return IRMV_OK;
 }
 
@@ -174,7 +174,7 @@ extern "C" int irmv_engine_meter(irmv_engine *e, int slot, const irmv_meter_opts
     const MeterParams p = meter_params(*o);
     HIP_TRY(hipMemcpy(e->meter_params_dev + 1, &p, sizeof p, hipMemcpyHostToDevice));
     TRY(load_frame(e, slot, st));
-    MeterStats *rec = e->meter_stats_dev + e->cfg.num_slots;
+    MeterStats *rec = e->meter.dev + e->cfg.num_slots;   // (the record behind the steps')
     launch_frame_meter(meter_args(e, v, slot, e->meter_params_dev + 1, rec), 1, e->sw.meter_merge, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, rec, sizeof(MeterStats), hipMemcpyDeviceToHost, st));
@@ -186,12 +186,8 @@ extern "C" int irmv_engine_meter(irmv_engine *e, int slot, const irmv_meter_opts
 // not hold the meter's nodes.  Nothing of the engine is in flight.
 static int enable_metering(irmv_engine *e)
 {
-    const size_t bytes = (size_t)e->cfg.num_slots * sizeof(MeterStats);
-    HIP_TRY(hipHostMalloc((void **)&e->meter_stats_host, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(hipHostGetDevicePointer((void **)&e->meter_stats_host_dev, e->meter_stats_host, 0));
-    memset(e->meter_stats_host, 0, bytes);
-    log_range(e, "pinned meter_stats_host", e->meter_stats_host, bytes);
-    add_meter_op(e);
+    TRY(e->meter.pin(e, e->cfg.num_slots, 1, "pinned meter_stats_host"));   // (the steps' records: still zero, as ensure_meter left them)
+    append_op(e, OP_METER);
     drop_graphs(e, true);   // (run_post's graphs have no meter node and stay)
     return IRMV_OK;
 }
@@ -225,6 +221,6 @@ extern "C" int irmv_engine_frame_stats(irmv_engine *e, int slot, irmv_frame_stat
     TRY(check_range(e, slot, 1));
     if (!out) return fail(IRMV_ERR_ARG, "out is null");
     if (e->meter_op < 0) return fail(IRMV_ERR_ARG, "irmv_engine_frame_stats: irmv_engine_set_metering has not been called on this engine");
-    memcpy(out, e->meter_stats_host + slot, sizeof *out);
+    memcpy(out, e->meter.host_at(slot), sizeof *out);
     return IRMV_OK;
 }

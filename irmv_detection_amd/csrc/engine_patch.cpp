@@ -54,13 +54,9 @@ static int enable_patches(irmv_engine *e)
     const size_t n = (size_t)e->cfg.num_slots * e->cfg.max_det;
     // DevPatch: bytes and counts that only the host reads; patch_step_kernel writes every word of the records of [0, num_dets)
     // where it is enabled, no kernel reads one
-    TRY(dev_alloc(e, (void **)&e->patch_dev, n * sizeof(DevPatch), "patch_dev", mem_scratch(MEM_U8)));
-    HIP_TRY(hipMemset(e->patch_dev, 0, n * sizeof(DevPatch)));
-    HIP_TRY(hipHostMalloc((void **)&e->patch_host, n * sizeof(DevPatch), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(hipHostGetDevicePointer((void **)&e->patch_host_dev, e->patch_host, 0));
-    memset(e->patch_host, 0, n * sizeof(DevPatch));
-    log_range(e, "pinned patch_host", e->patch_host, n * sizeof(DevPatch));
-    add_patch_op(e);
+    TRY(dev_alloc(e, (void **)&e->patch.dev, n * sizeof(DevPatch), "patch_dev", mem_scratch(MEM_U8)));
+    TRY(e->patch.pin(e, e->cfg.num_slots, e->cfg.max_det, "pinned patch_host"));
+    append_op(e, OP_PATCH);
     drop_graphs(e, false);   // (run_post's graphs too: the op stands behind their NMS)
     return IRMV_OK;
 }
@@ -72,11 +68,7 @@ extern "C" int irmv_engine_set_patches(irmv_engine *e, const irmv_patch_opts *o)
     HIP_TRY(hipSetDevice(e->cfg.device));
     TRY(irmv_engine_wait(e));   // every stream of the engine: no step in flight reads the table, no graph is running
     if (e->patch_op < 0) TRY(enable_patches(e));
-    if (!o->enable) {   // nothing writes the records from here on: none of an earlier step is left for a later enable to show
-        const size_t bytes = (size_t)e->cfg.num_slots * e->cfg.max_det * sizeof(DevPatch);
-        HIP_TRY(hipMemset(e->patch_dev, 0, bytes));
-        memset(e->patch_host, 0, bytes);
-    }
+    if (!o->enable) TRY(e->patch.zero(e->cfg.num_slots));   // nothing writes the records from here on: none of an earlier step is left for a later enable to show
     e->patch_opts = *o;
     return write_patch_table(e);
 }
@@ -90,10 +82,9 @@ extern "C" int irmv_engine_get_patches(const irmv_engine *e, irmv_patch_opts *o)
 
 // A step's patches: they read the records of pa (where the step's NMS or light extraction wrote them) and the slots' frames
 // exactly where light_args points the light extraction -- the view's device frames, which the step's upload (and crop, and
-// demosaic) filled in front of its first layer on the same stream --, and go where the DevYaw records go.
+// demosaic) filled in front of its first layer on the same stream --, and go where the DevDet records go (Records::step_at).
 void irmv::launch_patch(const irmv_engine *e, const View &v, const Step &s, const PostArgs &pa, hipStream_t st)
 {
-    const bool zero_copy = e->zero_copy_results && !s.dev_records();
     PatchArgs a{};
     a.frames = v.frames + (size_t)s.first * v.frame_bytes;
     a.frame_bytes = v.frame_bytes;
@@ -102,7 +93,7 @@ void irmv::launch_patch(const irmv_engine *e, const View &v, const Step &s, cons
     a.num_dets = reinterpret_cast<const int *>(pa.fout);
     a.num_dets_stride = (int)(sizeof(DevFrameOut) / sizeof(int));
     a.table = e->patch_table_dev;
-    a.out = (zero_copy ? e->patch_host_dev : e->patch_dev) + (size_t)s.first * e->cfg.max_det;
+    a.out = e->patch.step_at(e, s);
     launch_patch_step(a, s.count, st);
 }
 
@@ -111,12 +102,9 @@ extern "C" int irmv_engine_plate_patches(irmv_engine *e, int slot, irmv_plate_pa
     TRY(check_range(e, slot, 1));
     if (!n || (cap > 0 && !out)) return fail(IRMV_ERR_ARG, "out/n is null");
     if (e->patch_op < 0) return fail(IRMV_ERR_ARG, "irmv_engine_plate_patches: irmv_engine_set_patches has not been called on this engine");
-    const int k = std::max(0, std::min(std::min(e->fout_host[slot].num_dets, e->cfg.max_det), cap));
     // (disabled: the kernel returns at once and set_patches has zeroed the records, so they stay all zero until the first step
     // after the next enable)
-    if (k) memcpy(out, e->patch_host + (size_t)slot * e->cfg.max_det, (size_t)k * sizeof(irmv_plate_patch));
-    *n = k;
-    return IRMV_OK;
+    return e->patch.deliver(e, slot, out, cap, n);
 }
 
 extern "C" int irmv_engine_patches_at(irmv_engine *e, int slot, const float *kpts, const int32_t *armor_size, int n, irmv_plate_patch *out)

@@ -1,5 +1,5 @@
-// What a step launches: the Detect finals' fusion as the tuner left it, the sparse head's reordering, and the launch list of
-// each step kind.
+// What a step launches: the Detect finals' fusion as the tuner left it, the sparse head's reordering, the launch list of
+// each step kind, and the ops a feature appends to it.
 #include "engine_internal.hpp"
 
 // a class-branch conv that carries its final 1x1: with emit_scan, its epilogue appends the level's scan candidates
@@ -102,80 +102,62 @@ static void sparse_head_plan(irmv_engine *e, std::vector<Launch> &plan)
     plan.swap(out);
 }
 
-// Frame metering (e->meter_op >= 0): the steps of view v launch the meter op behind whatever produces the view's frame -- the
-// demosaic, the crop, both at the head of the plan -- or first.
-static void add_meter_launch(const irmv_engine *e, View &v)
+// ---- ops a feature appends to the steps ---------------------------------------------------
+// The op kinds that are not part of the network's op list: a feature appends one to e->ops at its first enable (append_op).
+// build_step_plans skips them in its loop and places their launches behind it, in this order.
+static constexpr OpKind kAppendedOps[] = {OP_METER, OP_YAW, OP_PATCH};
+static bool is_appended(OpKind k) { return std::find(std::begin(kAppendedOps), std::end(kAppendedOps), k) != std::end(kAppendedOps); }
+
+// Everything that differs between them, decided here and nowhere else:
+//   index    where the engine keeps the op's index in e->ops (-1: never enabled)
+//   anchor   the launch stands directly behind the plan's last op of one of these two kinds
+//   records  a side-record op: run_post's plan launches it too (the meter: BATCH and ONE steps only)
+//   bytes    irmv_engine_profile's per-frame figure of the launch in view v
+struct AppendedOp { int *index; const char *name; OpKind anchor[2]; bool records; double bytes; };
+static AppendedOp appended_op(irmv_engine *e, const View &v, OpKind kind)
 {
-    for (int k : {(int)STEP_BATCH, (int)STEP_ONE}) {
-        std::vector<Launch> &plan = v.plans[k];
-        size_t at = 0;
-        for (size_t i = 0; i < plan.size(); i++)
-            if (e->ops[plan[i].op].kind == OP_DEMOSAIC || e->ops[plan[i].op].kind == OP_CROP) at = i + 1;
-        const Op &op = e->ops[e->meter_op];
-        Launch l; l.op = e->meter_op;
-        l.name = op.kname; l.layer = op.layer;
-        l.bytes = (double)v.frame_bytes;   // (the VIEW domain at step 1 on the whole view: the most it reads)
-        plan.insert(plan.begin() + at, l);
+    const double md = (double)e->cfg.max_det;
+    switch (kind) {
+    // behind whatever produces the view's frame -- the demosaic, the crop, both at the head of the plan -- or first; it reads at
+    // most the VIEW domain at step 1 on the whole view
+    case OP_METER: return {&e->meter_op, "frame_meter", {OP_DEMOSAIC, OP_CROP}, false, (double)v.frame_bytes};
+    // the constrained pose and the plate patches: behind the last kernel that writes the DevDet records -- the NMS, or the light
+    // extraction of a classical or refined engine
+    case OP_YAW: return {&e->yaw_op, "yaw_solve", {OP_NMS, OP_LIGHT}, true, md * (sizeof(DevDet) + sizeof(DevYaw))};
+    case OP_PATCH: return {&e->patch_op, "plate_patch", {OP_NMS, OP_LIGHT}, true, md * (sizeof(DevDet) + sizeof(DevPatch))};
+    default: return {nullptr, "", {kind, kind}, false, 0.0};
     }
 }
 
-// The first irmv_engine_set_metering with options: the op, appended to e->ops, and its launch in the step plans of every view
-// built so far (a view built later gets it from build_step_plans).  Nothing of the engine is in flight.
-void irmv::add_meter_op(irmv_engine *e)
+// The launch of appended op `kind` in the plans of view v, if the engine has the op.  It goes DIRECTLY behind its anchor: in
+// front of the launches placed there before it.
+static void place_appended(irmv_engine *e, View &v, OpKind kind)
 {
-    Op op; op.kind = OP_METER; op.layer = "frame_meter"; snprintf(op.kname, sizeof op.kname, "frame_meter");
-    e->ops.push_back(op);
-    e->meter_op = (int)e->ops.size() - 1;
-    for (View &v : e->views)
-        if (v.built) add_meter_launch(e, v);
-}
-
-// A side-record op (the constrained pose, the plate patches): the steps of view v and run_post launch it behind the last kernel
-// that writes the DevDet records -- the NMS, or the light extraction of a classical or refined engine.
-static void add_side_launch(const irmv_engine *e, View &v, int op_index, double bytes)
-{
+    const AppendedOp a = appended_op(e, v, kind);
+    if (!a.index || *a.index < 0) return;
     for (int k : {(int)STEP_BATCH, (int)STEP_ONE, (int)STEP_POST}) {
+        if (k == STEP_POST && !a.records) continue;
         std::vector<Launch> &plan = v.plans[k];
-        size_t at = plan.size();
+        size_t at = a.records ? plan.size() : 0;
         for (size_t i = 0; i < plan.size(); i++)
-            if (e->ops[plan[i].op].kind == OP_NMS || e->ops[plan[i].op].kind == OP_LIGHT) at = i + 1;
-        const Op &op = e->ops[op_index];
-        Launch l; l.op = op_index;
-        l.name = op.kname; l.layer = op.layer;
-        l.bytes = bytes;
+            if (e->ops[plan[i].op].kind == a.anchor[0] || e->ops[plan[i].op].kind == a.anchor[1]) at = i + 1;
+        Launch l; l.op = *a.index;
+        l.name = l.layer = a.name;
+        l.bytes = a.bytes;
         plan.insert(plan.begin() + at, l);
     }
 }
 
-static void add_yaw_launch(const irmv_engine *e, View &v)
+// A feature's first enable (set_metering with options, set_yaw_solve, set_patches): the op, appended to e->ops, and its launch
+// in the plans of every view built so far (a view built later gets it from build_step_plans).  Nothing of the engine is in flight.
+void irmv::append_op(irmv_engine *e, OpKind kind)
 {
-    add_side_launch(e, v, e->yaw_op, (double)e->cfg.max_det * (sizeof(DevDet) + sizeof(DevYaw)));
-}
-
-static void add_patch_launch(const irmv_engine *e, View &v)
-{
-    add_side_launch(e, v, e->patch_op, (double)e->cfg.max_det * (sizeof(DevDet) + sizeof(DevPatch)));
-}
-
-// The first irmv_engine_set_yaw_solve: the op, appended to e->ops, and its launch in the plans of every view built so far (a
-// view built later gets it from build_step_plans).  Nothing of the engine is in flight.
-void irmv::add_yaw_op(irmv_engine *e)
-{
-    Op op; op.kind = OP_YAW; op.layer = "yaw_solve"; snprintf(op.kname, sizeof op.kname, "yaw_solve");
+    const AppendedOp a = appended_op(e, e->views[0], kind);
+    Op op; op.kind = kind; op.layer = a.name; snprintf(op.kname, sizeof op.kname, "%s", a.name);
     e->ops.push_back(op);
-    e->yaw_op = (int)e->ops.size() - 1;
+    *a.index = (int)e->ops.size() - 1;
     for (View &v : e->views)
-        if (v.built) add_yaw_launch(e, v);
-}
-
-// The first irmv_engine_set_patches, likewise
-void irmv::add_patch_op(irmv_engine *e)
-{
-    Op op; op.kind = OP_PATCH; op.layer = "plate_patch"; snprintf(op.kname, sizeof op.kname, "plate_patch");
-    e->ops.push_back(op);
-    e->patch_op = (int)e->ops.size() - 1;
-    for (View &v : e->views)
-        if (v.built) add_patch_launch(e, v);
+        if (v.built) place_appended(e, v, kind);
 }
 
 // The one place that decides which ops of e->ops a step of each kind launches in view v, and how.  The views differ in front
@@ -190,7 +172,7 @@ void irmv::build_step_plans(irmv_engine *e, View &v)
         for (int i = 0; i < (int)e->ops.size(); i++) {
             const Op &op = e->ops[i];
             if (op.kind == OP_FRONT) continue;   // (launched where model.1.conv stands, below)
-            if (op.kind == OP_METER || op.kind == OP_YAW || op.kind == OP_PATCH) continue;   // (added behind the loop)
+            if (is_appended(op.kind)) continue;   // (placed behind the loop)
             if (op.kind == OP_CROP && !v.crop) continue;
             const bool away = is_front_layer(i) ? v.fused_front : op.fused_away;   // the layers a fused kernel covers in this view
             if (post && op.kind != OP_NMS && op.kind != OP_LIGHT && op.kind != OP_SCAN) continue;
@@ -247,7 +229,5 @@ void irmv::build_step_plans(irmv_engine *e, View &v)
         }
         if (step && e->sparse_head) sparse_head_plan(e, v.plans[k]);
     }
-    if (e->meter_op >= 0) add_meter_launch(e, v);
-    if (e->yaw_op >= 0) add_yaw_launch(e, v);
-    if (e->patch_op >= 0) add_patch_launch(e, v);
+    for (OpKind kind : kAppendedOps) place_appended(e, v, kind);
 }

@@ -1,5 +1,5 @@
-// Running a step: the kernel arguments of every op kind, the one launcher, frame and result copies, graph capture, and the
-// submit / wait / results ABI.
+// Running a step: the kernel arguments of every op kind, the one launcher, frame copies, the record channels (where a step's
+// records go and how they reach the host), graph capture, and the submit / wait / results ABI.
 #include "engine_internal.hpp"
 
 // ---- kernel arguments: one builder per op kind, on slots [first, first + count) -----------
@@ -66,9 +66,9 @@ LightArgs irmv::light_args(const irmv_engine *e, const View &v, int first)
     a.frames = v.frames + (size_t)first * v.frame_bytes;
     a.frame_bytes = v.frame_bytes;
     a.cols = v.src_w; a.rows = v.src_h; a.rotate180 = c.rotate180;
-    a.dets = e->dets_dev + (size_t)first * c.max_det;
+    a.dets = e->dets.dev_at(first);
     a.max_det = c.max_det;
-    a.num_dets = reinterpret_cast<const int *>(e->fout_dev + first);
+    a.num_dets = reinterpret_cast<const int *>(e->fout.dev_at(first));
     a.num_dets_stride = (int)(sizeof(DevFrameOut) / sizeof(int));
     a.n_boxes = 0;
     a.boxes = nullptr;
@@ -90,7 +90,7 @@ LightArgs irmv::light_args(const irmv_engine *e, const View &v, int first)
         a.kpts = e->refine_kpts + (size_t)first * c.max_det * 8;
     }
     if (e->pose_alt) {   // the kAlt instantiations: the records beside the step's device records
-        a.alts = e->alts_dev + (size_t)first * c.max_det;
+        a.alts = e->alts.dev_at(first);
         a.prior = e->prior_dev; a.up = e->up_dev;
     }
     return a;
@@ -111,7 +111,6 @@ static void launch_bayer(const irmv_engine *e, int first, int count, hipStream_t
 
 PostArgs irmv::post_args(const irmv_engine *e, const View &v, const Step &s)
 {
-    const bool zero_copy = e->zero_copy_results && !s.dev_records();
     const int first = s.first;
     PostArgs p = e->post;
     p.scale_x = v.scale_x; p.scale_y = v.scale_y; p.off_x = v.off_x; p.off_y = v.off_y;
@@ -121,14 +120,14 @@ PostArgs irmv::post_args(const irmv_engine *e, const View &v, const Step &s)
     p.boxes = e->boxes + (size_t)first * e->A * 4;
     p.keys = e->keys + (size_t)first * e->A * e->nc;
     p.key_cap = e->A * e->nc;
-    p.dets = (zero_copy ? e->dets_host_dev : e->dets_dev) + (size_t)first * e->cfg.max_det;
-    p.fout = (zero_copy ? e->fout_host_dev : e->fout_dev) + first;
+    p.dets = e->dets.step_at(e, s);
+    p.fout = e->fout.step_at(e, s);
     if (p.dbg) p.dbg += (size_t)first * 16;
     p.counts = e->sw.split_scan ? e->cand_counts + first : nullptr;
     p.cand_bits = e->sparse_head ? e->cand_bits + (size_t)first * e->cand_words : nullptr;
     p.cand_words = e->cand_words;
     if (e->pose_alt) {   // nms_pnp_kernel<true>: the alt records go where the DevDet records go
-        p.alts = (zero_copy ? e->alts_host_dev : e->alts_dev) + (size_t)first * e->cfg.max_det;
+        p.alts = e->alts.step_at(e, s);
         p.prior = e->prior_dev; p.up = e->up_dev;
     }
     return p;
@@ -170,8 +169,7 @@ MeterArgs irmv::meter_args(const irmv_engine *e, const View &v, int first, const
 static void launch_meter(const irmv_engine *e, const View &v, const Step &s, hipStream_t st)
 {
     if (s.tiled()) return;
-    MeterStats *out = (e->zero_copy_results ? e->meter_stats_host_dev : e->meter_stats_dev) + s.first;
-    launch_frame_meter(meter_args(e, v, s.first, e->meter_params_dev, out), s.count, e->sw.meter_merge, st);
+    launch_frame_meter(meter_args(e, v, s.first, e->meter_params_dev, e->meter.step_at(e, s)), s.count, e->sw.meter_merge, st);
 }
 
 static PreArgs pre_args(const irmv_engine *e, const View &v, const Op &op, int first)
@@ -482,26 +480,77 @@ int irmv::enqueue_upload(irmv_engine *e, const Upload &u, hipStream_t st)
     return IRMV_OK;
 }
 
+// ---- record channels (Records<T>, engine_internal.hpp) ---------------------------------------
+// Pin: in this order the device range is zeroed, the pinned twin made, its device view fetched, the twin zeroed and logged.
+template <typename T> int Records<T>::pin(const irmv_engine *e, int slots, int n_per_slot, const char *what)
+{
+    per_slot = n_per_slot;
+    const size_t bytes = (size_t)slots * per_slot * sizeof(T);
+    HIP_TRY(hipMemset(dev, 0, bytes));
+    HIP_TRY(hipHostMalloc((void **)&host, bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(hipHostGetDevicePointer((void **)&host_dev, host, 0));
+    memset(host, 0, bytes);
+    log_range(e, what, host, bytes);
+    return IRMV_OK;
+}
+
+// THE decision of where a step's records go: into pinned host memory where the engine's results are zero-copy, unless a kernel
+// behind the writer reads them on the device (Step::dev_records) -- then, and on every other engine, into the device records,
+// and copy_out_dev brings them to the host.
+template <typename T> T *Records<T>::step_at(const irmv_engine *e, const Step &s) const
+{
+    return (e->zero_copy_results && !s.dev_records() ? host_dev : dev) + (size_t)s.first * per_slot;
+}
+
+template <typename T> int Records<T>::copy(int first, int count, hipMemcpyKind dir, hipStream_t st) const
+{
+    const size_t at = (size_t)first * per_slot, bytes = (size_t)count * per_slot * sizeof(T);
+    if (dir == hipMemcpyDeviceToHost) HIP_TRY(hipMemcpyAsync(host + at, dev + at, bytes, dir, st));
+    else HIP_TRY(hipMemcpyAsync(dev + at, host + at, bytes, dir, st));
+    return IRMV_OK;
+}
+
+template <typename T> int Records<T>::zero(int slots) const
+{
+    const size_t bytes = (size_t)slots * per_slot * sizeof(T);
+    HIP_TRY(hipMemset(dev, 0, bytes));
+    memset(host, 0, bytes);
+    return IRMV_OK;
+}
+
+template <typename T> int Records<T>::deliver(const irmv_engine *e, int slot, void *out, int cap, int *n) const
+{
+    const int k = std::max(0, std::min(std::min(e->fout.host_at(slot)->num_dets, e->cfg.max_det), cap));
+    if (k) memcpy(out, host_at(slot), (size_t)k * sizeof(T));
+    *n = k;
+    return IRMV_OK;
+}
+
+template <typename T> void Records<T>::free_host()
+{
+    if (host) (void)hipHostFree(host);
+    host = host_dev = nullptr;
+}
+
+template struct Records<MeterStats>;
+template struct Records<DevDet>;
+template struct Records<DevFrameOut>;
+template struct Records<DevAlt>;
+template struct Records<DevYaw>;
+template struct Records<DevPatch>;
+
 // the device records of slots [first, first + count) -> their pinned twins (every step of an engine without zero-copy results;
 // tiled steps of any engine -- which do not meter: stats = false)
 static int copy_out_dev(irmv_engine *e, int first, int count, hipStream_t st, bool stats)
 {
-    if (stats && e->meter_op >= 0)
-        HIP_TRY(hipMemcpyAsync(e->meter_stats_host + first, e->meter_stats_dev + first, (size_t)count * sizeof(MeterStats), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(e->dets_host + (size_t)first * e->cfg.max_det, e->dets_dev + (size_t)first * e->cfg.max_det,
-                           (size_t)count * e->cfg.max_det * sizeof(DevDet), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(e->fout_host + first, e->fout_dev + first, (size_t)count * sizeof(DevFrameOut),
-                           hipMemcpyDeviceToHost, st));
-    if (e->pose_alt)
-        HIP_TRY(hipMemcpyAsync(e->alts_host + (size_t)first * e->cfg.max_det, e->alts_dev + (size_t)first * e->cfg.max_det,
-                               (size_t)count * e->cfg.max_det * sizeof(DevAlt), hipMemcpyDeviceToHost, st));
-    if (e->yaw_op >= 0)
-        HIP_TRY(hipMemcpyAsync(e->yaw_host + (size_t)first * e->cfg.max_det, e->yaw_dev + (size_t)first * e->cfg.max_det,
-                               (size_t)count * e->cfg.max_det * sizeof(DevYaw), hipMemcpyDeviceToHost, st));
+    const hipMemcpyKind d2h = hipMemcpyDeviceToHost;
+    if (stats && e->meter_op >= 0) TRY(e->meter.copy(first, count, d2h, st));
+    TRY(e->dets.copy(first, count, d2h, st));
+    TRY(e->fout.copy(first, count, d2h, st));
+    if (e->pose_alt) TRY(e->alts.copy(first, count, d2h, st));
+    if (e->yaw_op >= 0) TRY(e->yaw.copy(first, count, d2h, st));
     // (disabled: the kernel returns at once and set_patches has zeroed both copies -- max_det records of 592 bytes stay where they are)
-    if (e->patch_op >= 0 && e->patch_opts.enable)
-        HIP_TRY(hipMemcpyAsync(e->patch_host + (size_t)first * e->cfg.max_det, e->patch_dev + (size_t)first * e->cfg.max_det,
-                               (size_t)count * e->cfg.max_det * sizeof(DevPatch), hipMemcpyDeviceToHost, st));
+    if (e->patch_op >= 0 && e->patch_opts.enable) TRY(e->patch.copy(first, count, d2h, st));
     return IRMV_OK;
 }
 
@@ -728,7 +777,7 @@ void irmv::det_pose(const DevDet &d, bool shift, float ox, float oy, irmv_det &o
 // Record i of the slot's pinned result list as the ABI returns it (irmv_engine_results, irmv_engine_tile_results).
 void irmv::slot_det(const irmv_engine *e, int slot, int i, irmv_det &o)
 {
-    const DevDet &d = e->dets_host[(size_t)slot * e->cfg.max_det + i];
+    const DevDet &d = e->dets.host_at(slot)[i];
     // device records of a step in the window view are window-local: the corner the slot was submitted with brings them to
     // full-frame coordinates (a step in the frame view: nothing to add)
     const bool shift = e->window && e->sub_view[slot] == IRMV_VIEW_WINDOW;
@@ -748,7 +797,7 @@ extern "C" int irmv_engine_results(irmv_engine *e, int slot, irmv_det *out, int 
 {
     TRY(check_range(e, slot, 1));
     if (!n || (cap > 0 && !out)) return fail(IRMV_ERR_ARG, "out/n is null");
-    const DevFrameOut &fo = e->fout_host[slot];
+    const DevFrameOut &fo = *e->fout.host_at(slot);
     const int k = std::min(fo.num_dets, cap);
     for (int i = 0; i < k; i++) slot_det(e, slot, i, out[i]);
     *n = k;

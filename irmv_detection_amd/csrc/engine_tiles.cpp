@@ -47,7 +47,7 @@ static int ensure_tiles(irmv_engine *e, int first, irmv_engine::TileMerge **out)
 TileArgs irmv::tile_args(const irmv_engine *e, int first, int count)
 {
     TileArgs a{};
-    a.dets = e->dets_dev; a.fout = e->fout_dev; a.win = e->win_dev;
+    a.dets = e->dets.dev; a.fout = e->fout.dev; a.win = e->win_dev;
     a.params = e->tile_params_dev;
     a.out = e->tile_merges.at(first).out_dev;
     a.first = first; a.count = count; a.max_det = e->cfg.max_det;
@@ -78,10 +78,9 @@ extern "C" int irmv_engine_merge_tiles(irmv_engine *e, int first, int count)
     TRY(irmv_engine_wait(e));
     irmv_engine::TileMerge *tm;
     TRY(ensure_tiles(e, first, &tm));
-    const size_t md = (size_t)e->cfg.max_det;
     if (e->zero_copy_results) {   // the slots' current records are the pinned ones: bring them to the device records the kernel reads
-        HIP_TRY(hipMemcpyAsync(e->dets_dev + first * md, e->dets_host + first * md, count * md * sizeof(DevDet), hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(e->fout_dev + first, e->fout_host + first, (size_t)count * sizeof(DevFrameOut), hipMemcpyHostToDevice, e->stream));
+        TRY(e->dets.copy(first, count, hipMemcpyHostToDevice, e->stream));
+        TRY(e->fout.copy(first, count, hipMemcpyHostToDevice, e->stream));
     }
     launch_tile_merge(tile_args(e, first, count), e->stream);
     HIP_TRY(hipGetLastError());

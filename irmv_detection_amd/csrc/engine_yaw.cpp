@@ -80,16 +80,12 @@ static int enable_yaw(irmv_engine *e)
     const size_t n = (size_t)e->cfg.num_slots * e->cfg.max_det;
     // DevYaw: doubles and int32 flags that only the host reads; yaw_solve_kernel writes the records of [0, num_dets) where it
     // is enabled, no kernel reads one
-    TRY(dev_alloc(e, (void **)&e->yaw_dev, n * sizeof(DevYaw), "yaw_dev", mem_scratch(MEM_F64)));
-    HIP_TRY(hipMemset(e->yaw_dev, 0, n * sizeof(DevYaw)));
-    HIP_TRY(hipHostMalloc((void **)&e->yaw_host, n * sizeof(DevYaw), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(hipHostGetDevicePointer((void **)&e->yaw_host_dev, e->yaw_host, 0));
-    memset(e->yaw_host, 0, n * sizeof(DevYaw));
-    log_range(e, "pinned yaw_host", e->yaw_host, n * sizeof(DevYaw));
+    TRY(dev_alloc(e, (void **)&e->yaw.dev, n * sizeof(DevYaw), "yaw_dev", mem_scratch(MEM_F64)));
+    TRY(e->yaw.pin(e, e->cfg.num_slots, e->cfg.max_det, "pinned yaw_host"));
     // host-written tables, read when the kernel runs
     TRY(dev_alloc(e, (void **)&e->yaw_table_dev, sizeof(YawTable), "yaw_table", mem_const(MEM_F64)));
     TRY(dev_alloc(e, (void **)&e->yaw_basis_dev, (size_t)e->cfg.num_slots * sizeof(YawBasis), "yaw_basis", mem_const(MEM_F64)));
-    add_yaw_op(e);
+    append_op(e, OP_YAW);
     drop_graphs(e, false);   // (run_post's graphs too: the op stands behind their NMS)
     return IRMV_OK;
 }
@@ -101,11 +97,7 @@ extern "C" int irmv_engine_set_yaw_solve(irmv_engine *e, const irmv_yaw_opts *o)
     HIP_TRY(hipSetDevice(e->cfg.device));
     TRY(irmv_engine_wait(e));   // every stream of the engine: no step in flight reads the tables, no graph is running
     if (e->yaw_op < 0) TRY(enable_yaw(e));
-    if (!o->enable) {   // nothing writes the records from here on: none of an earlier step is left for a later enable to show
-        const size_t bytes = (size_t)e->cfg.num_slots * e->cfg.max_det * sizeof(DevYaw);
-        HIP_TRY(hipMemset(e->yaw_dev, 0, bytes));
-        memset(e->yaw_host, 0, bytes);
-    }
+    if (!o->enable) TRY(e->yaw.zero(e->cfg.num_slots));   // nothing writes the records from here on: none of an earlier step is left for a later enable to show
     e->yaw_opts = *o;
     return write_yaw_tables(e);
 }
@@ -118,17 +110,16 @@ extern "C" int irmv_engine_get_yaw_solve(const irmv_engine *e, irmv_yaw_opts *o)
 }
 
 // A step's constrained poses: they read the records of pa (where the step's NMS or light extraction wrote them) and go where
-// the DevAlt records go.
+// the DevDet records go (Records::step_at).
 void irmv::launch_yaw(const irmv_engine *e, const Step &s, const PostArgs &pa, hipStream_t st)
 {
-    const bool zero_copy = e->zero_copy_results && !s.dev_records();
     YawArgs a{};
     a.dets = pa.dets; a.max_det = e->cfg.max_det;
     a.num_dets = reinterpret_cast<const int *>(pa.fout);
     a.num_dets_stride = (int)(sizeof(DevFrameOut) / sizeof(int));
     a.pnp = pa.pnp; a.first = s.first; a.pnp_stride = pa.pnp_stride;
     a.table = e->yaw_table_dev; a.basis = e->yaw_basis_dev;
-    a.out = (zero_copy ? e->yaw_host_dev : e->yaw_dev) + (size_t)s.first * e->cfg.max_det;
+    a.out = e->yaw.step_at(e, s);
     launch_yaw_solve(a, s.count, st);
 }
 
@@ -137,12 +128,9 @@ extern "C" int irmv_engine_yaw_poses(irmv_engine *e, int slot, irmv_yaw_pose *ou
     TRY(check_range(e, slot, 1));
     if (!n || (cap > 0 && !out)) return fail(IRMV_ERR_ARG, "out/n is null");
     if (e->yaw_op < 0) return fail(IRMV_ERR_ARG, "irmv_engine_yaw_poses: irmv_engine_set_yaw_solve has not been called on this engine");
-    const int k = std::max(0, std::min(std::min(e->fout_host[slot].num_dets, e->cfg.max_det), cap));
     // (disabled: the kernel returns at once and set_yaw_solve has zeroed the records, so they stay all zero until the first
     // step after the next enable)
-    if (k) memcpy(out, e->yaw_host + (size_t)slot * e->cfg.max_det, (size_t)k * sizeof(irmv_yaw_pose));
-    *n = k;
-    return IRMV_OK;
+    return e->yaw.deliver(e, slot, out, cap, n);
 }
 
 extern "C" int irmv_pnp_solve_yaw(irmv_pnp *p, const float *img_pts, int n, int armor_size, const double up[3], double normal_up,

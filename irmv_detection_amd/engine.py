@@ -448,12 +448,16 @@ class YoloEngine:
         capi.check(self._L.irmv_engine_get_up(self._h, slot, u.ctypes.data_as(C.POINTER(C.c_double))))
         return u
 
+    def _side_records(self, getter, record, slot: int):
+        """The slot's side records of one kind -- `getter` is the library's call, `record` its ctypes type -- as copies."""
+        n = C.c_int(0)
+        out = (record * self.max_det)()
+        capi.check(getter(self._h, slot, out, self.max_det, C.byref(n)))
+        return [out[i] for i in range(n.value)]
+
     def pose_alts(self, slot: int = 0):
         """capi.PoseAlt records (copies) parallel to results(slot) / results_raw(slot)."""
-        n = C.c_int(0)
-        out = (capi.PoseAlt * self.max_det)()
-        capi.check(self._L.irmv_engine_pose_alts(self._h, slot, out, self.max_det, C.byref(n)))
-        return [out[i] for i in range(n.value)]
+        return self._side_records(self._L.irmv_engine_pose_alts, capi.PoseAlt, slot)
 
     # ---- constrained pose (include/irmv_hip.h; host reference: yaw_solve.py) ----
     def set_yaw_solve(self, enable: bool = True, rounds: int = 4, tau_max: float = 1.0, horizon_min: float = 1e-4) -> None:
@@ -471,10 +475,7 @@ class YoloEngine:
 
     def yaw_poses(self, slot: int = 0):
         """capi.YawPose records (copies) parallel to results(slot) / results_raw(slot)."""
-        n = C.c_int(0)
-        out = (capi.YawPose * self.max_det)()
-        capi.check(self._L.irmv_engine_yaw_poses(self._h, slot, out, self.max_det, C.byref(n)))
-        return [out[i] for i in range(n.value)]
+        return self._side_records(self._L.irmv_engine_yaw_poses, capi.YawPose, slot)
 
     # ---- plate patches (include/irmv_hip.h; host reference: patches.py) ----
     def set_patches(self, enable: bool = True, span=(32, 54), light_rows: int = 12, top: int = 7) -> None:
@@ -492,10 +493,7 @@ class YoloEngine:
 
     def plate_patches(self, slot: int = 0):
         """capi.PlatePatch records (copies) parallel to results(slot) / results_raw(slot)."""
-        n = C.c_int(0)
-        out = (capi.PlatePatch * self.max_det)()
-        capi.check(self._L.irmv_engine_plate_patches(self._h, slot, out, self.max_det, C.byref(n)))
-        return [out[i] for i in range(n.value)]
+        return self._side_records(self._L.irmv_engine_plate_patches, capi.PlatePatch, slot)
 
     def patches_at(self, kpts: np.ndarray, armor_size, slot: int = 0):
         """irmv_engine_patches_at: the patches of explicit quads ([n, 8] LB LT RT RB in result coordinates; armor_size one
