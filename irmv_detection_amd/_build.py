@@ -24,6 +24,7 @@ SOURCES = [
     ("k_c2f.hip", []),
     ("k_bneck.hip", []),
     ("k_kpt.hip", []),
+    ("k_boxg.hip", []),
     ("k_conv.hip", []),
     ("k_post.hip", ["-ffp-contract=off"]),
     ("k_tiles.hip", ["-ffp-contract=off"]),

@@ -307,6 +307,8 @@ static EngineSwitches read_switches()
     s.sync_launch = starts("IRMV_SYNC_LAUNCH", 'e') ? 1 : (starts("IRMV_SYNC_LAUNCH", 'g') ? 0 : -1);
     s.split_scan = !off("IRMV_SPLIT_SCAN"); s.emit_scan = !off("IRMV_EMIT_SCAN");
     s.sparse_head = !off("IRMV_SPARSE_HEAD"); s.sparse_branch = !off("IRMV_SPARSE_BRANCH");
+    s.sparse_gather = !off("IRMV_SPARSE_GATHER");
+    if (const char *gg = getenv("IRMV_SPARSE_GATHER_GRID")) s.gather_grid = atoi(gg);
     s.zero_copy_results = !off("IRMV_ZERO_COPY_RESULTS"); s.post_keys_only = is1("IRMV_POST_KEYS_ONLY");
     s.nms_classwalk = !off("IRMV_NMS_CLASSWALK");
     s.meter_merge = !off("IRMV_METER_MERGE");

@@ -402,6 +402,40 @@ static int fuse_kpt3(irmv_engine *e, int level)
     return IRMV_OK;
 }
 
+// The box branch of a Detect level -- the last three ops: 3x3 (Cin -> 64), 3x3 (64 -> 64) carrying the final 1x1 -- at the
+// candidate anchors only, as one launch from a list (k_boxg.hip).  The OP_BOXG op stands behind the layer ops; whether a step
+// runs it in their place is the plan's decision (engine_plan.cpp box_gathers: the sparse branch, IRMV_SPARSE_GATHER), read-backs
+// run the layers.
+static int fuse_boxg(irmv_engine *e, int level)
+{
+    if (e->ops.size() < 3 || e->cfg.num_slots > 1024) return IRMV_OK;
+    const int i2 = (int)e->ops.size() - 1, i1 = i2 - 1, i0 = i2 - 2;
+    const Op &o0 = e->ops[i0], &o1 = e->ops[i1], &o2 = e->ops[i2];
+    const bool ok = o0.kind == OP_CONV && o1.kind == OP_CONV && o2.kind == OP_CONV && o1.fuse_next == i2 && o2.cout_pad == 64 && o2.w_packed &&
+                    o0.cfg.ks == 3 && o0.cfg.stride == 1 && o0.cfg.act == 1 && !o0.cfg.out_f32 && o0.cout == 64 && o0.pair && o0.res_t < 0 &&
+                    o0.s1.C == 0 && o0.s0.shift == 0 && o0.w_lds[2] != nullptr && box_gather_eligible(o0.cin) &&
+                    o1.cfg.ks == 3 && o1.cfg.act == 1 && o1.cin == 64 && o1.s0.t == o0.out_t && o1.s0.coff == o0.out_coff && o1.s1.C == 0 && o1.s0.shift == 0 && o1.w_lds[2] != nullptr &&
+                    o0.Hin == o1.Hin && o0.Win == o1.Win && o0.Hout == o0.Hin && o0.Wout == o0.Win;
+    if (!ok) return IRMV_OK;
+    {   // the kernel addresses the level's input through a buffer descriptor with 32-bit byte offsets
+        const Tensor &xt = e->tensors[o0.s0.t];
+        if ((double)e->cfg.num_slots * xt.H * xt.W * xt.C * 2.0 >= 2147483648.0) return IRMV_OK;
+    }
+    Op op;
+    op.kind = OP_BOXG;
+    op.layer = "model.22.cv2." + std::to_string(level) + ".g";
+    snprintf(op.kname, sizeof op.kname, "box_gather_c%d", o0.cin);
+    op.sub[0] = i0; op.sub[1] = i1; op.sub[2] = i2;
+    op.Hin = op.Hout = o0.Hin; op.Win = op.Wout = o0.Win;
+    op.cin = o0.cin;
+    op.level = level;
+    op.boxg = 1;   // (flops and bytes stay 0: both depend on the frames)
+    e->ops.push_back(op);
+    const int me = (int)e->ops.size() - 1;
+    e->ops[i0].boxg = e->ops[i1].boxg = e->ops[i2].boxg = me;
+    return IRMV_OK;
+}
+
 static int add_c2f(irmv_engine *e, const std::string &prefix, SegRef s0, SegRef s1, int H, int W, int c2, int n,
                    bool shortcut, int out_t)
 {
@@ -798,6 +832,7 @@ static int build_neck_and_head(irmv_engine *e, const Acts &act)
                     e->ops[i1].fuse_next = i2;
             }
             if (b == 2 && !e->merge_head0) TRY(fuse_kpt3(e, i));
+            if (b == 0 && !e->merge_head0) TRY(fuse_boxg(e, i));
         }
     return IRMV_OK;
 }
@@ -828,6 +863,15 @@ static int build_post_stage(irmv_engine *e)
         // CARRIED, invariant: zero between steps.  Bit masks (any word is in range; a set bit stores or computes a head row)
         TRY(dev_alloc(e, (void **)&e->cand_bits, (size_t)S * e->cand_words * sizeof(unsigned int), "cand_bits", mem_carried_index(0xffffffffu)));
         HIP_TRY(hipMemset(e->cand_bits, 0, (size_t)S * e->cand_words * sizeof(unsigned int)));
+        // ... and, where a level has an OP_BOXG op, the candidate lists cand_list_kernel derives from the bitmap inside a step.
+        // Indices: an entry is a pixel of its level, a count at most the level's pixels; both kernels of k_boxg.hip clamp what
+        // they read to their own level, the values below are the smallest level's
+        bool gathers = false;
+        for (const Op &op : e->ops) gathers = gathers || op.kind == OP_BOXG;
+        if (gathers) {
+            TRY(dev_alloc(e, (void **)&e->boxg_list, (size_t)S * e->A * sizeof(int), "boxg_list", mem_scratch_index((uint32_t)(e->lvl_hw[2] - 1))));
+            TRY(dev_alloc(e, (void **)&e->boxg_count, (size_t)3 * S * sizeof(int), "boxg_count", mem_scratch_index((uint32_t)e->lvl_hw[2])));
+        }
     }
     e->head_stale.assign((size_t)S, 0);
     e->branch_stale.assign((size_t)S, 0);

@@ -689,7 +689,7 @@ extern "C" int irmv_engine_run_conv_candidate(irmv_engine *e, int op, int tune_c
 // ---- per-op test hooks (tests/test_gpu_graph_ops.py) ---------------------------------
 static const char *op_kind_name(OpKind k)   // (in OpKind's order)
 {
-    static const char *const names[] = {"pre", "conv0", "conv", "pool", "nms", "light", "front", "c2f2", "c2f32", "dw", "shuffle", "scan", "bneck", "kpt3", "demosaic", "crop", "meter", "yaw", "patch"};
+    static const char *const names[] = {"pre", "conv0", "conv", "pool", "nms", "light", "front", "c2f2", "c2f32", "dw", "shuffle", "scan", "bneck", "kpt3", "boxg", "demosaic", "crop", "meter", "yaw", "patch"};
     static_assert(sizeof names / sizeof *names == OP_PATCH + 1, "a name per OpKind");
     return (unsigned)k <= OP_PATCH ? names[k] : "?";
 }

@@ -127,6 +127,8 @@ struct EngineSwitches {
     bool split_scan = true;        // scan + box decode as a multi-workgroup kernel in front of nms_pnp (IRMV_SPLIT_SCAN=0: inside it)
     bool emit_scan = true, sparse_head = true, sparse_branch = true;   // IRMV_EMIT_SCAN=0: the class-branch conv epilogues emit no candidates; IRMV_SPARSE_HEAD=0: every head row is stored;
                                    // IRMV_SPARSE_BRANCH=0: no tile gate behind the class carriers
+    bool sparse_gather = true;     // IRMV_SPARSE_GATHER=0: the box branch stays the tile-gated layer launches (no OP_BOXG launch in a step)
+    int gather_grid = 0;           // IRMV_SPARSE_GATHER_GRID=<n> (tests): workgroups of a box_gather launch; 0: one per CU
     bool zero_copy_results = true; // IRMV_ZERO_COPY_RESULTS=0: device records + a D2H copy in keypoint mode too
     bool post_keys_only = false;   // IRMV_POST_KEYS_ONLY=1 (tests): run_post's NMS ignores scan_decode_kernel's boxes and decodes its own, as a whole step's does
     bool nms_classwalk = true;     // IRMV_NMS_CLASSWALK=0
@@ -136,7 +138,7 @@ struct EngineSwitches {
     bool nms_stamps = false; int nms_stamps_slots = 0;   // IRMV_NMS_STAMPS=<n>: the NMS kernel stamps its phases, the destructor prints the first n slots' (at least four)
 };
 
-enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_DEMOSAIC, OP_CROP, OP_METER, OP_YAW, OP_PATCH };
+enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_BOXG, OP_DEMOSAIC, OP_CROP, OP_METER, OP_YAW, OP_PATCH };
 
 struct Op {
     OpKind kind;
@@ -165,7 +167,9 @@ struct Op {
     int group = -1;            // single-frame steps: index into irmv_engine::head_groups of the one launch this conv rides in
     int bneck = -1;            // single-frame steps: index of the OP_BNECK launch (k_bneck.hip) that computes this conv; OP_BNECK itself: 1 = kept
     int kpt3 = -1;             // a keypoint-branch conv: index of the OP_KPT3 launch (k_kpt.hip) that computes its level's branch in every step; OP_KPT3 itself: 1
-    bool gated_first = false;  // a Detect box branch's first conv that some step runs behind the tile gate (sparse branch): its tensor is lazy, the read-back step runs it densely
+    int boxg = -1;             // a box-branch conv: index of the OP_BOXG launch (k_boxg.hip) that computes its level's branch at the candidate anchors in the steps that
+                               // gather (box_gathers); OP_BOXG itself: 1
+    bool gated_first = false;  // a Detect box branch's first conv that some step runs behind the tile gate (sparse branch) or not at all (OP_BOXG): its tensor is lazy, the read-back step runs it densely
     int tune_fuse[2] = {-1, -1};   // OP_CONV: fuse_next as the autotuner's two passes (stream share, one slot) found it (test hooks rebuild their candidate lists)
 };
 
@@ -181,6 +185,7 @@ struct Launch {
     bool keys_only = false;   // OP_NMS: decodes the boxes of its key lists itself
     bool sparse = false;      // a Detect box carrier or OP_KPT3 behind its level's class carrier: stores the candidate anchors' head rows only
     int gate = 0;             // sparse branch, ConvArgs::tile_gate / Kpt3Args::tile_gate: 0 = off, 1 = halo 0 (writes head rows), 2 = halo 1 (box branch's first conv)
+    bool cand_list = false;   // OP_BOXG: the plan's first -- cand_list_kernel runs in front of it, for every level's launch
     bool once = false;        // not repeated under irmv_engine_profile (appends to, consumes or rewrites per-frame lists)
     std::string name, layer;  // irmv_engine_profile's row
     double flops = 0, bytes = 0, launch_bytes = 0;   // per frame; launch_bytes (the weights): once per launch
@@ -315,6 +320,10 @@ struct irmv_engine {
     // tensor stale outside active tiles: branch_stale[slot], until the read-back step has run it densely.
     bool sparse_branch = false;
     std::vector<char> branch_stale;
+    // Candidate lists of the OP_BOXG launches (k_boxg.hip): per level and slot the candidate pixels cand_list_kernel found in
+    // the bitmap, and their number.  Scratch: a step writes every count, and every entry below it, before a gather launch reads.
+    int *boxg_list = nullptr;    // level l, slot s: lvl_base[l] * S + s * lvl_hw[l] + [0, lvl_hw[l])
+    int *boxg_count = nullptr;   // [3][S]
     int lvl_hw[3] = {0, 0, 0}, lvl_base[3] = {0, 0, 0};
     size_t frame_bytes = 0;       // one HWC source frame of src_dev (views[0])
     size_t src_bytes = 0;         // one source slot as the producer writes it (src_host, and raw_dev or src_dev): frame_bytes, or W*H for a Bayer engine

@@ -45,6 +45,9 @@ static bool is_box_final_carrier(const Op &op) { return op.fuse_next >= 0 && op.
 // first conv feeds nothing but its carrier's 3x3: where it runs a resident-weight kernel it moves behind the last class carrier
 // too (it reads the level input only) and is gated with a halo of one pixel; its tensor becomes a lazy one (Op::gated_first).
 // flops / bytes stay the dense figures: upper bounds for a gated launch.
+//
+// Candidate gather (box_gathers): a level's OP_BOXG launch stands for its first conv and its carrier; it moves behind the last
+// class carrier like the carriers it replaces, and the plan's first one runs cand_list_kernel in front of itself.
 static void sparse_head_plan(irmv_engine *e, std::vector<Launch> &plan)
 {
     int last_cls = -1;
@@ -75,9 +78,16 @@ static void sparse_head_plan(irmv_engine *e, std::vector<Launch> &plan)
             first_conv[i] = carrier >= 0 && !other;
         }
     std::vector<Launch> out, moved;
+    bool listed = false;
     for (size_t i = 0; i < plan.size(); i++) {
         Launch &l = plan[i];
         Op &op = e->ops[l.op];
+        const bool boxg = op.kind == OP_BOXG;
+        if (boxg) {
+            l.sparse = true;
+            l.cand_list = !listed;
+            listed = true;
+        }
         if (l.scan) {   // class carrier(s): the 1x1's output stays on chip
             if (l.group < 0) l.bytes -= e->ops[op.fuse_next].out_bytes;
             else for (size_t m = 0; m < e->head_groups[l.group].members.size(); m++)
@@ -96,10 +106,25 @@ static void sparse_head_plan(irmv_engine *e, std::vector<Launch> &plan)
             op.gated_first = true;
             e->lazy_tensors.insert(e->tensors[op.out_t].name);
         }
-        if ((box || first_conv[i]) && (int)i < last_cls) moved.push_back(l); else out.push_back(l);
+        if ((box || first_conv[i] || boxg) && (int)i < last_cls) moved.push_back(l); else out.push_back(l);
         if ((int)i == last_cls) { out.insert(out.end(), moved.begin(), moved.end()); moved.clear(); }
     }
     plan.swap(out);
+}
+
+// Does a step (of one slot: `one`) run the box branch of OP_BOXG op g as that launch, in place of the layers it covers?  Wherever
+// the sparse branch holds and the level's convs are launches of their own behind a class carrier of their own: not in a grouped
+// head launch.  IRMV_SPARSE_GATHER=0 keeps the tile-gated layer launches, and so does IRMV_FORCE_WRES, which asks for the
+// resident-weight kernels on every eligible layer by name.
+static bool box_gathers(const irmv_engine *e, const Op &g, bool one)
+{
+    if (!e->sparse_branch || !e->sw.sparse_gather || e->sw.tune.has_wres || !e->boxg_list) return false;
+    const Op &o0 = e->ops[g.sub[0]], &o1 = e->ops[g.sub[1]];
+    if (o1.fuse_next != g.sub[2]) return false;   // (the carrier's tile choice dropped the final: the branch runs as layers)
+    bool grouped = o0.group >= 0 || o1.group >= 0;
+    for (const Op &op : e->ops)
+        if (is_cls_final_carrier(op) && op.level == g.level) grouped = grouped || op.group >= 0;
+    return !(one && grouped);
 }
 
 // ---- ops a feature appends to the steps ---------------------------------------------------
@@ -184,6 +209,14 @@ void irmv::build_step_plans(irmv_engine *e, View &v)
             if (op.kind == OP_BNECK ? !bneck : (op.bneck >= 0 && bneck)) continue;
             // every step runs a level's keypoint branch as its OP_KPT3 launch (where the engine has one)
             if (op.kind == OP_KPT3 ? !step : (op.kpt3 >= 0 && step)) continue;
+            // ... and a level's box branch as its OP_BOXG launch where the step gathers (box_gathers); the first conv's tensor is
+            // then one no step writes: lazy, and dense again after the read-back step (Op::gated_first)
+            if (op.kind == OP_BOXG ? !(step && box_gathers(e, op, one)) : (op.boxg >= 0 && step && box_gathers(e, e->ops[op.boxg], one))) continue;
+            if (op.kind == OP_BOXG) {
+                Op &o0 = e->ops[op.sub[0]];
+                o0.gated_first = true;
+                e->lazy_tensors.insert(e->tensors[o0.out_t].name);
+            }
             // a step skips the layers a fused kernel covers; a read-back runs only those (and the unfused form of a conv that
             // normally carries a 1x1 in its epilogue)
             // (... and a box branch's first conv that the steps -- their plans are built first -- run behind the tile gate)

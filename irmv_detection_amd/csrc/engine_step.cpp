@@ -277,6 +277,38 @@ static Kpt3Args kpt3_args(const irmv_engine *e, const Op &op, const Launch &l, i
     return a;
 }
 
+// the candidate lists of slots [first, first + count): every level that has an OP_BOXG op
+static CandListArgs cand_list_args(const irmv_engine *e, int first, const PostArgs &pa)
+{
+    CandListArgs a{};
+    a.cand_bits = pa.cand_bits; a.cand_words = pa.cand_words;
+    const size_t S = (size_t)e->cfg.num_slots;
+    for (int l = 0; l < 3; l++) { a.abase[l] = e->lvl_base[l]; a.hw[l] = e->lvl_hw[l]; }
+    for (const Op &op : e->ops)
+        if (op.kind == OP_BOXG) {
+            const int l = op.level;
+            a.list[l] = e->boxg_list + (size_t)e->lvl_base[l] * S + (size_t)first * e->lvl_hw[l];
+            a.count[l] = e->boxg_count + (size_t)l * S + first;
+        }
+    return a;
+}
+
+static BoxGatherArgs boxg_args(const irmv_engine *e, const Op &op, int first, const PostArgs &pa)
+{
+    const Op &o0 = e->ops[op.sub[0]], &o1 = e->ops[op.sub[1]], &o2 = e->ops[op.sub[2]];
+    const Tensor &xt = e->tensors[o0.s0.t], &ht = e->tensors[o2.out_t];
+    const CandListArgs c = cand_list_args(e, first, pa);
+    BoxGatherArgs a{};
+    a.x = static_cast<const half_t *>(xt.slot(first)) + o0.s0.coff; a.x_ld = xt.C;
+    a.H = op.Hin; a.W = op.Win;
+    a.w0 = o0.w_lds[2]; a.b0 = o0.bias;
+    a.w1 = o1.w_lds[2]; a.b1 = o1.bias;
+    a.w2 = o2.w_packed; a.b2 = o2.bias;
+    a.out = static_cast<float *>(ht.slot(first)) + o2.out_coff; a.out_ld = ht.C;
+    a.list = c.list[op.level]; a.count = c.count[op.level];
+    return a;
+}
+
 static DwArgs dw_args(const irmv_engine *e, const Op &op, int first)
 {
     DwArgs a;
@@ -356,6 +388,11 @@ int irmv::launch_op(irmv_engine *e, const View &v, const Launch &l, const Step &
         if (!launch_bneck64(op.mode, op.sub[2] >= 0 ? e->ops[op.sub[2]].ksteps : 6, op.shortcut, bneck_args(e, op, first), count, s)) return fail(IRMV_ERR_ARG, "no fused bottleneck kernel for " + op.layer);
         break;
     case OP_KPT3: if (!launch_kpt3(kpt3_args(e, op, l, first, pa), op.cin, count, s)) return fail(IRMV_ERR_ARG, "no fused keypoint-branch kernel for " + op.layer); break;
+    case OP_BOXG:
+        if (!pa.cand_bits) return fail(IRMV_ERR_ARG, "a box gather launch needs the sparse head's bitmap: " + op.layer);
+        if (l.cand_list) launch_cand_list(cand_list_args(e, first, pa), count, s);
+        if (!launch_box_gather(boxg_args(e, op, first, pa), op.cin, count, e->sw.gather_grid > 0 ? e->sw.gather_grid : e->num_cus, s)) return fail(IRMV_ERR_ARG, "no box gather kernel for " + op.layer);
+        break;
     case OP_DW: launch_dwconv3x3(dw_args(e, op, first), count, s); break;
     case OP_SHUF: launch_shuffle_cat(shuf_args(e, op, first, count), s); break;
     case OP_CONV0: launch_conv0(conv0_args(e, op, first, count), s); break;

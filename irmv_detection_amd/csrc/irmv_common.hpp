@@ -292,6 +292,35 @@ struct Kpt3Args {
 bool kpt3_eligible(int cin);
 bool launch_kpt3(const Kpt3Args &a, int cin, int batch, hipStream_t s);
 
+// The box branch of one Detect level (3x3 Cin -> 64, 3x3 64 -> 64, 1x1 64 -> 64) at the step's candidate anchors only, from a
+// compact list (k_boxg.hip).  cand_list_kernel writes the lists of all levels: per image of the launch its candidate pixels
+// of the level, in any order, and their number.
+struct CandListArgs {
+    const unsigned int *cand_bits;   // [B][cand_words] candidate-anchor bitmap
+    int cand_words;
+    int abase[3], hw[3];             // first anchor and pixel count of each level
+    int *list[3];                    // [B][hw] pixel y * W + x; nullptr: the level keeps no list
+    int *count[3];                   // [B]
+};
+void launch_cand_list(const CandListArgs &a, int batch, hipStream_t s);
+struct BoxGatherArgs {
+    const half_t *x;      // the level's input [B][H][W][x_ld], offset to the first of its Cin channels
+    int x_ld;
+    int H, W;
+    const half_t *w0;     // first conv: LDS-family nt = 4 packing [chunk of 32][tap][4 tiles][64 lanes][8]
+    const float *b0;
+    const half_t *w1;     // second conv: the same packing, two chunks
+    const float *b1;
+    const half_t *w2;     // final 1x1: [4 tiles][2 k-steps][64 lanes][8]
+    const float *b2;      // (not scaled: the final has no activation)
+    float *out;           // head records [B][H * W][out_ld], offset to the box channels
+    int out_ld;
+    const int *list;      // [B][H * W], const int *count: [B] (CandListArgs)
+    const int *count;
+};
+bool box_gather_eligible(int cin);
+bool launch_box_gather(const BoxGatherArgs &a, int cin, int batch, int grid, hipStream_t s);   // grid: the persistent workgroups (captured with the step)
+
 // Class policy (irmv_engine_set_class_policy): one logit threshold and one plate model per class, in device memory at an
 // address fixed for the engine's life -- kernels hold the pointer, a captured graph never the values.  (anchor, c) is a
 // candidate iff logit > thr[c]; min_thr = the smallest thr[c] over c < nc (+inf: every class off), the wave-uniform pre-test
