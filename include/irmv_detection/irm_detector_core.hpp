@@ -112,6 +112,10 @@ public:
     // (YoloEngine::patch_opts()) -- FrameResult::patches is then filled.  Live: set_parameter "patches" (0 | 1; the first 1
     // enables).  Models with a keypoint head only, like FrameResult::yaw.
     irmv_patch_opts patches{};
+    // Plate numbers (include/irmv_hip.h): the path of an .irmn model file, empty = off.  The three engines load it at creation
+    // and read every plate patch with it (the patches are turned on with their defaults where `patches` did not) --
+    // FrameResult::numbers is then filled.  Live: set_parameter("number_model", path); an empty path switches the records off.
+    std::string number_model;
     bool debug = false;                                  // the node's debug (:90-95, :259-280): every frame also yields FrameResult::visualized_image / binary_image,
                                                          // rendered on the GPU (YoloEngine::render); live through set_bool_parameter("debug", v) like the reference (:380-381)
     int debug_scale = 1;                                 // 1, 2 or 4: the debug images at full, half or quarter size (set_parameter "debug_scale")
@@ -143,6 +147,9 @@ public:
     // Params::patches only (else empty): parallel to `poses`, each armor's rectified 20 x 28 gray number image, its Otsu
     // threshold and the colour vote of its two light bars (state 1; 0: no patch)
     std::vector<irmv_plate_patch> patches;
+    // Params::number_model only (else empty): parallel to `poses`, the MLP's reading of each armor's patch -- label, runner-up,
+    // margin, logits (state 1; 0: no answer, exactly where the patch has none)
+    std::vector<irmv_plate_number> numbers;
     double inference_latency_ms = 0;    // YoloEngine::get_profiling_time() (:251)
     // Params::debug only (else empty): the frame with this frame's armors, boxes and labels drawn on it (:261-263; the latency
     // text lines are not drawn), and gray -> threshold(binary_threshold) -> three channels with the boxes and labels (:273-277)
@@ -171,6 +178,7 @@ public:
       if (p.pose_prior.struct_size != 0) { e->set_pose_prior(&p.pose_prior); e->set_up(p.up); }
       if (p.yaw_solve.struct_size != 0) { e->set_yaw_solve(p.yaw_solve); e->set_up(p.up); }
       if (p.patches.struct_size != 0) e->set_patches(p.patches);
+      if (!p.number_model.empty()) { e->set_number_model(p.number_model); e->set_numbers(true); }
     }
     yolo_engines_[0]->warm_up();   // the tile choices are shared by the three engines: one warm-up tunes for all
     for (size_t i = 1; i < yolo_engines_.size(); i++) yolo_engines_[i]->warm_up();
@@ -199,6 +207,7 @@ public:
     std::vector<irmv_pose_alt> alts;
     std::vector<irmv_yaw_pose> yaws;
     std::vector<irmv_plate_patch> plates;
+    std::vector<irmv_plate_number> numbers;
     if (eng.has_keypoint_head()) {
       // pose-style model: each detection carries its four points and, already, its pose
       int n = 0;
@@ -206,12 +215,14 @@ public:
       const std::vector<irmv_pose_alt> all = eng.pose_alts();   // parallel to dets (empty: not enabled)
       const std::vector<irmv_yaw_pose> all_yaw = eng.yaw_poses();
       const std::vector<irmv_plate_patch> all_plates = eng.plate_patches();
+      const std::vector<irmv_plate_number> all_numbers = eng.plate_numbers();
       for (int i = 0; i < n; i++) {
         const irmv_det & d = dets[i];
         if (d.armor_valid != 1) continue;
         if (size_t(i) < all.size()) alts.push_back(all[size_t(i)]);
         if (size_t(i) < all_yaw.size()) yaws.push_back(all_yaw[size_t(i)]);
         if (size_t(i) < all_plates.size()) plates.push_back(all_plates[size_t(i)]);
+        if (size_t(i) < all_numbers.size()) numbers.push_back(all_numbers[size_t(i)]);
         Armor a(Light(cv::Point2f(d.kpts[2], d.kpts[3]), cv::Point2f(d.kpts[0], d.kpts[1])),
                 Light(cv::Point2f(d.kpts[4], d.kpts[5]), cv::Point2f(d.kpts[6], d.kpts[7])));
         a.armor_class = static_cast<ArmorClass>(d.class_id);
@@ -243,6 +254,7 @@ public:
       out.poses.push_back(d);
       if (alts.size() == armors.size()) out.alts.push_back(alts[i]);
       if (plates.size() == armors.size()) out.patches.push_back(plates[i]);
+      if (numbers.size() == armors.size()) out.numbers.push_back(numbers[i]);
       if (yaws.size() == armors.size()) {
         out.yaw.push_back(yaws[i]);
         if (params_.yaw_publish && yaws[i].state == 1) {     // the constrained pose in place of IPPE's
@@ -381,6 +393,24 @@ public:
     }
     else return false;
     for (auto & e : yolo_engines_) push_params(*e);
+    return true;
+  }
+
+  // The node's string parameters: "number_model" is live -- a path loads that .irmn file into the three engines and switches
+  // the number records on (the first time: one re-capture per engine), an empty path switches them off.  false, and nothing
+  // changed on the engines that refused, for a file that cannot be read or a model that is refused.
+  bool set_parameter(const std::string & name, const std::string & value)
+  {
+    if (name != "number_model") return false;
+    try {
+      for (auto & e : yolo_engines_) {
+        if (!value.empty()) e->set_number_model(value);
+        if (!value.empty() || !params_.number_model.empty()) e->set_numbers(!value.empty());
+      }
+    } catch (const std::exception &) {
+      return false;
+    }
+    params_.number_model = value;
     return true;
   }
 

@@ -354,6 +354,56 @@ public:
   // Parallel to last_detections(): entry i is the patch of record i (empty before the first set_patches)
   std::vector<irmv_plate_patch> plate_patches() const { return side_records<irmv_plate_patch>(patches_on_, irmv_engine_plate_patches, "plate_patches"); }
 
+  // ---- plate numbers (include/irmv_hip.h, "plate numbers") ----
+  // A small MLP reads each plate patch: set_number_model (an .irmn file, as irmv_detection_amd/number_net.py writes one, or a
+  // model in memory), then set_numbers -- from then on every detect() also delivers label, runner-up, margin and logits beside
+  // each record: plate_numbers().  set_numbers(true) needs a model and turns the patches on, with their defaults, where they
+  // were never set.  The first enabling call re-captures the steps once; later calls and a new model re-capture nothing.  A
+  // refused model or call throws, nothing changes.
+  void set_number_model(const std::string & irmn_path)
+  {
+    if (irmv_engine_load_number_model(engine_, irmn_path.c_str()) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::set_number_model: ") + irmv_last_error());
+  }
+  void set_number_model(const irmv_number_model & m)
+  {
+    if (irmv_engine_set_number_model(engine_, &m) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::set_number_model: ") + irmv_last_error());
+  }
+  void set_numbers(bool enable = true)
+  {
+    irmv_number_opts o{};
+    o.struct_size = sizeof o; o.enable = enable ? 1 : 0;
+    if (irmv_engine_set_numbers(engine_, &o) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::set_numbers: ") + irmv_last_error());
+    if (enable) numbers_on_ = patches_on_ = true;   // (a first call with enable = false changes nothing)
+  }
+  bool numbers() const
+  {
+    irmv_number_opts o;
+    if (irmv_engine_get_numbers(engine_, &o) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::numbers: ") + irmv_last_error());
+    return o.enable != 0;
+  }
+  // Parallel to last_detections(): entry i is the number of record i (empty before the first set_numbers(true))
+  std::vector<irmv_plate_number> plate_numbers() const { return side_records<irmv_plate_number>(numbers_on_, irmv_engine_plate_numbers, "plate_numbers"); }
+  // On demand, enabled or not: the numbers of explicit patch records under the engine's model
+  std::vector<irmv_plate_number> numbers_at(const std::vector<irmv_plate_patch> & patches) const
+  {
+    std::vector<irmv_plate_number> out(patches.size());
+    if (irmv_engine_numbers_at(engine_, patches.data(), static_cast<int>(patches.size()), out.data()) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::numbers_at: ") + irmv_last_error());
+    return out;
+  }
+  // The softmax of a record's first n_classes logits (host, in double); all zero for a "no answer" record
+  static std::array<float, 16> number_softmax(const irmv_plate_number & r, int n_classes)
+  {
+    std::array<float, 16> p{};
+    if (irmv_number_softmax(&r, n_classes, p.data()) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::number_softmax: ") + irmv_last_error());
+    return p;
+  }
+
   // ---- tracking window ----
   bool has_window() const { return window_size_.width > 0 && window_size_.height > 0; }
   // The window's top-left corner in the coordinates bboxes come back in (the rotated frame); from the next detect() on.
@@ -626,6 +676,7 @@ private:
   bool pose_alts_on_ = false;         // set_pose_prior has been called: the engine delivers alt records
   bool yaw_on_ = false;               // set_yaw_solve has been called: the engine delivers constrained poses
   bool patches_on_ = false;           // set_patches has been called: the engine delivers plate patches
+  bool numbers_on_ = false;           // set_numbers(true) has been called: the engine delivers plate numbers
   cv::Size src_image_size_;
   cv::Size window_size_;
   bool enable_profiling_ = false;

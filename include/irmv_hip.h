@@ -736,6 +736,88 @@ int irmv_engine_patches_at(irmv_engine *e, int slot, const float *kpts, const in
 /* out: IRMV_PATCH_W, IRMV_PATCH_H, span min, span max, light_rows max, top max, sizeof(irmv_plate_patch), 0 */
 int irmv_patch_limits(int32_t out[8]);
 
+/* ---- plate numbers: each plate patch read by a small MLP ----------------------------------------------------------------
+ * The classic second opinion of an armor detector: a small multi-layer perceptron on the 560 values of the plate patch above,
+ * giving a label and the logits a confidence follows from.  From the first irmv_engine_set_numbers on, a step runs it in a
+ * kernel of its own directly behind the patch kernel, on the patch records where that kernel wrote them, and delivers one side
+ * record per detection (irmv_engine_plate_numbers).  irmv_det, irmv_pose_alt, irmv_yaw_pose, irmv_plate_patch and irmv_tile_det
+ * stay byte-identical whether or not it is on.  irmv_detection_amd/number_net.py (NumberModel.reference) states the model
+ * operation for operation; the results are equal in bytes.
+ *   Network.  n_layers = 1 .. 3 dense layers of widths dims[0] = 560 -> dims[1] -> .. -> dims[n_layers]: hidden widths
+ *     1 .. 128, the last width C = 1 .. 16.  The input is the patch in row-major order, k = j * 20 + i for column i, row j.
+ *     ReLU, r = a > 0 ? a : +0, behind every layer but the last.  No softmax on the device.
+ *   Weights.  fp32, row-major [out][in] (a torch.nn.Linear weight, an ONNX Gemm with transB = 1), biases fp32 [out].  At set
+ *     time every weight is rounded to fp16 (nearest even) and kept as fp16; biases stay fp32.  A non-finite weight or bias, or
+ *     one of magnitude above 65504, is refused.  With that bound no logit can overflow --
+ *     560 * 65504 * 128 * 65504 * 128 * 65504 ~ 2.6e21 < 3.4e38 --: logits are always finite.
+ *   Input.  IRMV_NUM_IN_BINARY: x_k = gray_k > otsu ? 1.0f : 0.0f with the patch record's own otsu (Otsu binarisation and a
+ *     scale by 1/255).  IRMV_NUM_IN_GRAY: x_k = (float)gray_k / 255.0f, one correctly rounded fp32 division.
+ *   Arithmetic.  fp32, no fused multiply-add, denormals kept: every product w * x is rounded, then every sum.  The summation
+ *     order is part of the model: a unit has FOUR chains, chain q takes the inputs k = q (mod 4) in ascending k,
+ *       a_0 = bias, a_1 = a_2 = a_3 = +0;   a_q = a_q + (float)w[k] * x_k   for k = q, q + 4, q + 8, ...
+ *       a = (a_0 + a_1) + (a_2 + a_3)
+ *     (the same for every layer: k runs over the layer's inputs, x is the previous layer's ReLU output).
+ *   Result.  label: the index of the largest logit, ties to the smaller index.  second: the same among the others, -1 where
+ *     C = 1.  margin = logit[label] - logit[second] in fp32, 0 where C = 1.  ones: the number of inputs equal to 1 (binary),
+ *     the integer sum of the 560 gray values (gray).  logits behind C are +0.  state 1: classified.  state 0, "no answer": all
+ *     96 bytes zero, exactly where the patch record has state == 0.
+ * Nothing is allocated and nothing new is launched until the first call below.  irmv_engine_set_number_model checks everything
+ * first, waits for the engine and uploads the rounded weights to device ranges sized for the largest model, whose addresses
+ * never move: a later model is live for the next step and re-captures nothing.  The first irmv_engine_set_numbers allocates
+ * the records, appends the kernel to the steps and drops the captured graphs once; later calls rewrite the table the kernel
+ * reads when it runs.  enable = 1 without a model: IRMV_ERR_ARG.  enable = 1 on an engine whose patches were never set turns
+ * them on in the same call, with the patch defaults and enable = 1.  enable = 0: the kernel returns at once, and the call
+ * zeroes the records.  Patches disabled while numbers stay enabled: the patch records are zero and every number record is "no
+ * answer".  Tiled steps: the number of merged record r is irmv_engine_plate_numbers(first + r.tile)[r.index]. */
+#define IRMV_NUM_IN_BINARY 0
+#define IRMV_NUM_IN_GRAY 1
+#define IRMV_NUM_CLASSES_MAX 16
+typedef struct irmv_number_model {
+    uint32_t struct_size;        /* = sizeof(irmv_number_model) */
+    int32_t  n_layers;           /* 1 .. 3 */
+    int32_t  dims[4];            /* dims[0] = 560, hidden 1 .. 128, dims[n_layers] = C = 1 .. 16; the rest 0 */
+    int32_t  input;              /* IRMV_NUM_IN_* */
+    const float *weight[3];      /* layer l: [dims[l + 1]][dims[l]] */
+    const float *bias[3];        /* layer l: [dims[l + 1]] */
+} irmv_number_model;
+typedef struct irmv_number_opts {
+    uint32_t struct_size;        /* = sizeof(irmv_number_opts) */
+    int32_t  enable;             /* 0 | 1 */
+    int32_t  reserved[3];        /* 0 */
+} irmv_number_opts;
+typedef struct irmv_plate_number {
+    int32_t  state, label, second, ones;
+    float    margin;
+    int32_t  reserved[3];
+    float    logits[IRMV_NUM_CLASSES_MAX];
+} irmv_plate_number;   /* 96 bytes */
+/* IRMV_ERR_ARG before the engine is looked at, leaving everything as it was: a null model, a wrong struct_size, n_layers,
+ * dims or input outside the ranges above, a null weight or bias of a layer in use, a value refused above.  Then: a null engine. */
+int irmv_engine_set_number_model(irmv_engine *e, const irmv_number_model *model);
+/* A model file (.irmn; NumberModel.save writes one), little endian: "IRMN", uint32 version = 1, int32 n_layers, int32 dims[4],
+ * int32 input -- 32 bytes --, then per layer its fp32 weights [out][in] and its fp32 biases [out].  Every length is checked
+ * against the file's size before it is used; the file must end where the last bias does.  irmv_number_model_read fills
+ * *model with pointers into buf (buf_floats floats; *need_floats, if not null: how many the file's model takes, at most
+ * 90384); the values themselves are checked by irmv_engine_set_number_model. */
+int irmv_number_model_read(const char *path, irmv_number_model *model, float *buf, int64_t buf_floats, int64_t *need_floats);
+int irmv_engine_load_number_model(irmv_engine *e, const char *path);
+/* IRMV_ERR_ARG before the engine is looked at: null opts, a wrong struct_size, enable outside {0, 1}, reserved != 0.  enable = 0
+ * on an engine that never enabled them changes nothing and makes nothing. */
+int irmv_engine_set_numbers(irmv_engine *e, const irmv_number_opts *opts);
+int irmv_engine_get_numbers(const irmv_engine *e, irmv_number_opts *opts);   /* before the first set: enable = 0 */
+/* Parallel to irmv_engine_results, as irmv_engine_plate_patches is.  IRMV_ERR_ARG before the first irmv_engine_set_numbers
+ * with enable = 1. */
+int irmv_engine_plate_numbers(irmv_engine *e, int slot, irmv_plate_number *out, int cap, int *n);
+/* On demand, on any engine that has a model, enabled or not: the numbers of n explicit patch records, out [n],
+ * 0 <= n <= IRMV_MAX_DET_CAP.  Reads no frame and no slot.  A patch whose state is not 0 or 1, or whose otsu is outside
+ * 0 .. 255, is refused.  Waits for the engine's steps in flight. */
+int irmv_engine_numbers_at(irmv_engine *e, const irmv_plate_patch *patches, int n, irmv_plate_number *out);
+/* out: 560, hidden max, C max, layers max, sizeof(irmv_plate_number), weight halves kept on the device, 65504, 0 */
+int irmv_number_limits(int32_t out[8]);
+/* Host only: the softmax of the record's first C logits, computed in double (exp(l - max) / sum), out[C .. 15] = 0.  A "no
+ * answer" record gives all zero.  (A device exp would end the byte parity of the records.) */
+int irmv_number_softmax(const irmv_plate_number *rec, int C, float out[16]);
+
 /* ---- stage-wise read-backs used by the parity tests -------------------- */
 int irmv_engine_read_input(irmv_engine *e, int slot, float *chw);             /* [3][net_h][net_w], as the reference's input_buffer_ */
 int irmv_engine_read_head(irmv_engine *e, int slot, float *head);             /* [A][64+nc+nk], A = irmv_engine_num_anchors(): levels

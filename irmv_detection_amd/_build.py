@@ -37,6 +37,7 @@ SOURCES = [
     ("k_meter.hip", []),
     ("k_yaw.hip", ["-ffp-contract=off"]),   # the constrained pose: a module of its own (its header)
     ("k_patch.hip", ["-ffp-contract=off"]),   # plate patches: a module of its own, fp64 in the written order (its header)
+    ("k_number.hip", ["-ffp-contract=off"]),   # plate numbers: a module of its own, fp32 in the written order (its header)
     ("k_debug.hip", []),
     ("engine.cpp", ["-x", "hip"]),
     ("engine_graph.cpp", ["-x", "hip"]),
@@ -48,6 +49,7 @@ SOURCES = [
     ("engine_meter.cpp", ["-x", "hip"]),
     ("engine_yaw.cpp", ["-x", "hip", "-ffp-contract=off"]),   # (its host arithmetic is the reference's, operation for operation)
     ("engine_patch.cpp", ["-x", "hip", "-ffp-contract=off"]),
+    ("engine_number.cpp", ["-x", "hip", "-ffp-contract=off"]),
 ]
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs.  Left to itself the compiler gives kernels without a waves_per_eu
 # bound (fused C2f blocks, direct convs) AGPR accumulators and copies every one of them out with a v_accvgpr_read before the

@@ -228,6 +228,26 @@ class PlatePatch(C.Structure):
                 ("armor_size", C.c_int32), ("bar_sum", C.c_uint32 * 2), ("sum", C.c_uint32), ("reserved", C.c_int32)]
 
 
+NUM_IN_BINARY, NUM_IN_GRAY, NUM_CLASSES_MAX = 0, 1, 16
+
+
+class NumberModel(C.Structure):
+    """irmv_number_model (include/irmv_hip.h, "plate numbers"); number_net.NumberModel.c_struct fills one."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_layers", C.c_int32), ("dims", C.c_int32 * 4), ("input", C.c_int32),
+                ("weight", C.POINTER(C.c_float) * 3), ("bias", C.POINTER(C.c_float) * 3)]
+
+
+class NumberOpts(C.Structure):
+    """irmv_number_opts (include/irmv_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("enable", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class PlateNumber(C.Structure):
+    """irmv_plate_number (include/irmv_hip.h): the MLP's reading of one detection's plate patch."""
+    _fields_ = [("state", C.c_int32), ("label", C.c_int32), ("second", C.c_int32), ("ones", C.c_int32), ("margin", C.c_float),
+                ("reserved", C.c_int32 * 3), ("logits", C.c_float * NUM_CLASSES_MAX)]
+
+
 def patch_opts_struct(enable=1, span=(32, 54), light_rows=12, top=7) -> PatchOpts:
     """An irmv_patch_opts (no check: the library's are the ones under test)."""
     o = PatchOpts()
@@ -382,6 +402,15 @@ SYMBOLS = [
     ("irmv_engine_plate_patches", C.c_int, [_P, C.c_int, C.POINTER(PlatePatch), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_engine_patches_at", C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int, C.POINTER(PlatePatch)]),
     ("irmv_patch_limits", C.c_int, [C.POINTER(C.c_int32)]),
+    ("irmv_engine_set_number_model", C.c_int, [_P, C.POINTER(NumberModel)]),
+    ("irmv_number_model_read", C.c_int, [C.c_char_p, C.POINTER(NumberModel), C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]),
+    ("irmv_engine_load_number_model", C.c_int, [_P, C.c_char_p]),
+    ("irmv_engine_set_numbers", C.c_int, [_P, C.POINTER(NumberOpts)]),
+    ("irmv_engine_get_numbers", C.c_int, [_P, C.POINTER(NumberOpts)]),
+    ("irmv_engine_plate_numbers", C.c_int, [_P, C.c_int, C.POINTER(PlateNumber), C.c_int, C.POINTER(C.c_int)]),
+    ("irmv_engine_numbers_at", C.c_int, [_P, C.POINTER(PlatePatch), C.c_int, C.POINTER(PlateNumber)]),
+    ("irmv_number_limits", C.c_int, [C.POINTER(C.c_int32)]),
+    ("irmv_number_softmax", C.c_int, [C.POINTER(PlateNumber), C.c_int, C.POINTER(C.c_float)]),
     ("irmv_meter_map", C.c_int, [C.POINTER(EngineCfg), C.POINTER(MeterOpts), C.c_int, C.c_int, C.c_int, C.POINTER(MeterMap)]),
     ("irmv_meter_limits", C.c_int, [C.POINTER(C.c_int32)]),
     ("irmv_engine_meter", C.c_int, [_P, C.c_int, C.POINTER(MeterOpts), C.POINTER(FrameStats)]),

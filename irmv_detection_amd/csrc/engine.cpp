@@ -95,7 +95,7 @@ irmv_engine::~irmv_engine()
     for (const DevRange &r : dev_allocs) (void)hipFree(r.base);
     dev_allocs.clear();
     if (src_host) (void)hipHostFree(src_host);
-    dets.free_host(); fout.free_host(); alts.free_host(); yaw.free_host(); patch.free_host(); meter.free_host();   // the record channels
+    dets.free_host(); fout.free_host(); alts.free_host(); yaw.free_host(); patch.free_host(); number.free_host(); meter.free_host();   // the record channels
     if (light_dets_host) (void)hipHostFree(light_dets_host);
     for (auto &kv : tile_merges)
         if (kv.second.out_host) (void)hipHostFree(kv.second.out_host);

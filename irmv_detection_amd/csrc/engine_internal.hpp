@@ -15,6 +15,7 @@
 //   engine_meter.cpp  frame metering: its checks and map, the record's host helpers, the on-demand call, the step's launch
 //   engine_yaw.cpp    constrained pose: its checks, the two tables and who rewrites them, the step's launch, the stand-alone call
 //   engine_patch.cpp  plate patches: their checks, the option table, the step's launch, the on-demand call
+//   engine_number.cpp plate numbers: the model's checks, its .irmn file and upload, the switch, the step's launch, the on-demand call
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -138,7 +139,7 @@ struct EngineSwitches {
     bool nms_stamps = false; int nms_stamps_slots = 0;   // IRMV_NMS_STAMPS=<n>: the NMS kernel stamps its phases, the destructor prints the first n slots' (at least four)
 };
 
-enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_BOXG, OP_DEMOSAIC, OP_CROP, OP_METER, OP_YAW, OP_PATCH };
+enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_BOXG, OP_DEMOSAIC, OP_CROP, OP_METER, OP_YAW, OP_PATCH, OP_NUMBER };
 
 struct Op {
     OpKind kind;
@@ -438,6 +439,7 @@ struct irmv_engine {
     Records<DevAlt> alts;
     Records<DevYaw> yaw;
     Records<DevPatch> patch;
+    Records<DevNumber> number;
     bool zero_copy_results = false;   // the NMS kernel writes its results straight into pinned host memory (no D2H copy)
     half_t *conv0_w = nullptr;
     float *conv0_b = nullptr;
@@ -468,6 +470,20 @@ struct irmv_engine {
     float *patch_at_kpts = nullptr;           // [kMaxDetCap][8]
     int32_t *patch_at_sizes = nullptr;        // [kMaxDetCap]
     DevPatch *patch_at_out = nullptr;         // [kMaxDetCap]
+    // Plate numbers (irmv_engine_set_number_model / irmv_engine_set_numbers).  Nothing below but number_opts (a host value)
+    // exists until the first set_number_model: the table, the weights and the biases, each sized for the largest model, at
+    // addresses that never move -- a later model rewrites their contents and re-captures nothing.  The first set_numbers makes
+    // the records (`number` above) and the op (number_op, directly behind the patch op's launch) and drops the captured graphs
+    // once; the first irmv_engine_numbers_at the call's two buffers.
+    int number_op = -1;
+    bool number_model = false;                // a model has been set
+    irmv_number_opts number_opts{};
+    NumberTable number_table{};               // the table as uploaded last (enable: number_opts.enable)
+    NumberTable *number_table_dev = nullptr;
+    half_t *number_weights = nullptr;         // [kNumWeightHalves]
+    float *number_bias = nullptr;             // [kNumBiasFloats]
+    DevPatch *number_at_in = nullptr;         // [kMaxDetCap]
+    DevNumber *number_at_out = nullptr;       // [kMaxDetCap]
 
     ~irmv_engine();
 };
@@ -522,7 +538,7 @@ int choose_sync_launch(irmv_engine *e);
 // engine_plan.cpp
 void finalize_head_fusion(irmv_engine *e);
 void build_step_plans(irmv_engine *e, View &v);
-void append_op(irmv_engine *e, OpKind kind);   // OP_METER, OP_YAW or OP_PATCH, at its feature's first enable
+void append_op(irmv_engine *e, OpKind kind);   // OP_METER, OP_YAW, OP_PATCH or OP_NUMBER, at its feature's first enable
 // engine_step.cpp
 void fill_conv_args(const irmv_engine *e, const Op &op, int first, int count, ConvArgs &a, bool fused = false);
 int slots_view(const irmv_engine *e, int first, int count, int *view = nullptr);
@@ -554,4 +570,8 @@ void launch_yaw(const irmv_engine *e, const Step &s, const PostArgs &pa, hipStre
 // engine_patch.cpp
 void patch_opts_defaults(irmv_patch_opts *o);
 void launch_patch(const irmv_engine *e, const View &v, const Step &s, const PostArgs &pa, hipStream_t st);
+int enable_patches(irmv_engine *e);   // the first set_patches' part, for a caller that has waited for the engine
+int write_patch_table(irmv_engine *e);
+// engine_number.cpp
+void launch_number(const irmv_engine *e, const Step &s, const PostArgs &pa, hipStream_t st);
 }

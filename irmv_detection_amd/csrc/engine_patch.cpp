@@ -36,7 +36,7 @@ static int check_patch_opts(const irmv_patch_opts *o)
 }
 
 // e->patch_opts -> the table (made by the first call that needs one).  The caller has made sure that no step in flight reads it.
-static int write_patch_table(irmv_engine *e)
+int irmv::write_patch_table(irmv_engine *e)
 {
     // host-written, read when the kernel runs
     if (!e->patch_table_dev) TRY(dev_alloc(e, (void **)&e->patch_table_dev, sizeof(PatchTable), "patch_table", mem_const(MEM_INDEX)));
@@ -49,7 +49,7 @@ static int write_patch_table(irmv_engine *e)
 
 // The first irmv_engine_set_patches: the records (device and pinned, zeroed), the op and the one re-capture -- no captured
 // step holds the patch node.  Nothing of the engine is in flight.
-static int enable_patches(irmv_engine *e)
+int irmv::enable_patches(irmv_engine *e)
 {
     const size_t n = (size_t)e->cfg.num_slots * e->cfg.max_det;
     // DevPatch: bytes and counts that only the host reads; patch_step_kernel writes every word of the records of [0, num_dets)

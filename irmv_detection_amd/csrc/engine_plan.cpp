@@ -130,7 +130,7 @@ static bool box_gathers(const irmv_engine *e, const Op &g, bool one)
 // ---- ops a feature appends to the steps ---------------------------------------------------
 // The op kinds that are not part of the network's op list: a feature appends one to e->ops at its first enable (append_op).
 // build_step_plans skips them in its loop and places their launches behind it, in this order.
-static constexpr OpKind kAppendedOps[] = {OP_METER, OP_YAW, OP_PATCH};
+static constexpr OpKind kAppendedOps[] = {OP_METER, OP_YAW, OP_PATCH, OP_NUMBER};
 static bool is_appended(OpKind k) { return std::find(std::begin(kAppendedOps), std::end(kAppendedOps), k) != std::end(kAppendedOps); }
 
 // Everything that differs between them, decided here and nowhere else:
@@ -150,6 +150,9 @@ static AppendedOp appended_op(irmv_engine *e, const View &v, OpKind kind)
     // extraction of a classical or refined engine
     case OP_YAW: return {&e->yaw_op, "yaw_solve", {OP_NMS, OP_LIGHT}, true, md * (sizeof(DevDet) + sizeof(DevYaw))};
     case OP_PATCH: return {&e->patch_op, "plate_patch", {OP_NMS, OP_LIGHT}, true, md * (sizeof(DevDet) + sizeof(DevPatch))};
+    // the plate numbers: directly behind the patch launch whose records they read (a plan reads nms, patch, number, yaw); the
+    // weights are read once per launch's detection and stay in L2
+    case OP_NUMBER: return {&e->number_op, "plate_number", {OP_PATCH, OP_PATCH}, true, md * (sizeof(DevPatch) + sizeof(DevNumber)) + (double)kNumWeightHalves * sizeof(half_t)};
     default: return {nullptr, "", {kind, kind}, false, 0.0};
     }
 }

@@ -380,6 +380,7 @@ int irmv::launch_op(irmv_engine *e, const View &v, const Launch &l, const Step &
     case OP_METER: launch_meter(e, v, t, s); break;
     case OP_YAW: launch_yaw(e, t, pa, s); break;
     case OP_PATCH: launch_patch(e, v, t, pa, s); break;
+    case OP_NUMBER: launch_number(e, t, pa, s); break;
     case OP_PRE: launch_preprocess(pre_args(e, v, op, first), count, s); break;
     case OP_FRONT: if (!launch_front(front_args(e, v, op, first), count, s)) return fail(IRMV_ERR_HIP, "fused front kernel: LDS request refused"); break;
     case OP_C2F2: launch_c2f2(c2f2_args(e, op, first), count, s); break;
@@ -575,6 +576,7 @@ template struct Records<DevFrameOut>;
 template struct Records<DevAlt>;
 template struct Records<DevYaw>;
 template struct Records<DevPatch>;
+template struct Records<DevNumber>;
 
 // the device records of slots [first, first + count) -> their pinned twins (every step of an engine without zero-copy results;
 // tiled steps of any engine -- which do not meter: stats = false)
@@ -588,6 +590,7 @@ static int copy_out_dev(irmv_engine *e, int first, int count, hipStream_t st, bo
     if (e->yaw_op >= 0) TRY(e->yaw.copy(first, count, d2h, st));
     // (disabled: the kernel returns at once and set_patches has zeroed both copies -- max_det records of 592 bytes stay where they are)
     if (e->patch_op >= 0 && e->patch_opts.enable) TRY(e->patch.copy(first, count, d2h, st));
+    if (e->number_op >= 0 && e->number_opts.enable) TRY(e->number.copy(first, count, d2h, st));   // (disabled: as the patches)
     return IRMV_OK;
 }
 

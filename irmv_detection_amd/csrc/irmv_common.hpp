@@ -765,6 +765,40 @@ void launch_patch_step(const PatchArgs &a, int batch, hipStream_t s);
 // on demand: quad i of kpts [n][8] (frame coordinates) with plate sizes[i] on the one frame a.frames -> a.out[i]; a.dets,
 // a.num_dets and the table's enable are not read
 void launch_patch_points(const PatchArgs &a, const float *kpts, const int32_t *sizes, int n, hipStream_t s);
+
+// ---- plate numbers (k_number.hip; irmv_engine_set_numbers) ----------------------------------------------------------------
+// DevNumber is the side record of one detection (the layout of irmv_plate_number).  NumberTable, the fp16 weights and the
+// fp32 biases live in device memory at addresses fixed from the first set_number_model on; the host writes them (every value
+// checked first), the kernel reads them when it runs.  Layer l: weights k-major [dims[l]][pad[l]] halves at w_off[l], zero
+// behind dims[l + 1]; biases [pad[l]] floats at b_off[l].
+constexpr int kNumIn = kPatchN, kNumHiddenMax = 128, kNumClassMax = 16, kNumLayersMax = 3, kNumPadUnit = 16;
+constexpr int kNumWeightHalves = kNumIn * kNumHiddenMax + kNumHiddenMax * kNumHiddenMax + kNumHiddenMax * kNumClassMax;
+constexpr int kNumBiasFloats = 2 * kNumHiddenMax + kNumClassMax;
+constexpr int kNumRecWords = 24;
+struct DevNumber {
+    int32_t state, label, second, ones;
+    float margin;
+    int32_t pad_[3];
+    float logits[kNumClassMax];
+};
+struct NumberTable {
+    int32_t enable, n_layers, input, pad_;
+    int32_t dims[4];                       // dims[0] = 560
+    int32_t pad[kNumLayersMax], w_off[kNumLayersMax], b_off[kNumLayersMax], pad2_[3];
+};
+struct NumberArgs {
+    const DevPatch *patches;  // [B][max_det]: where the step's patch op wrote them
+    int max_det;
+    const int *num_dets;      // frame b: num_dets[b * num_dets_stride]
+    int num_dets_stride;
+    const NumberTable *table;
+    const half_t *weights;
+    const float *bias;
+    DevNumber *out;           // [B][max_det]
+};
+void launch_number_step(const NumberArgs &a, int batch, hipStream_t s);
+// on demand: patch i of a.patches [n] -> a.out[i]; a.num_dets and the table's enable are not read
+void launch_number_points(const NumberArgs &a, int n, hipStream_t s);
 // both solutions, A first: rvec / tvec [n][2][3], err [n][2], ok bit 0 = launch_pnp_only's ok, bit 1 = B passed its own finiteness check
 void launch_pnp_both(const PnpConst &c, const float *pts, int n, int armor_size, double *rvec, double *tvec, double *err,
                      int32_t *ok, hipStream_t s);

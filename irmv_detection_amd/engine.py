@@ -506,6 +506,43 @@ class YoloEngine:
                                                   sizes.ctypes.data_as(C.POINTER(C.c_int32)), n, out))
         return [out[i] for i in range(n)]
 
+    # ---- plate numbers (include/irmv_hip.h; host reference: number_net.py) ----
+    def set_number_model(self, model) -> None:
+        """irmv_engine_set_number_model: a number_net.NumberModel, or the path of an .irmn file (irmv_engine_load_number_model).
+        Live for the next step; re-captures nothing.  A refused model raises and changes nothing."""
+        if isinstance(model, (str, bytes, os.PathLike)):
+            capi.check(self._L.irmv_engine_load_number_model(self._h, os.fsencode(model)))
+            return
+        m, keep = model.c_struct()
+        capi.check(self._L.irmv_engine_set_number_model(self._h, C.byref(m)))
+        del keep
+
+    def set_numbers(self, enable: bool = True) -> None:
+        """irmv_engine_set_numbers: from the first call on every step also reads each plate patch with the model and delivers
+        label, runner-up, margin and logits beside the record (plate_numbers).  Needs a model; turns the patches on (with
+        their defaults) where they were never set.  The first call re-captures the steps once; later calls are live."""
+        o = capi.NumberOpts()
+        o.struct_size, o.enable = C.sizeof(capi.NumberOpts), 1 if enable else 0
+        capi.check(self._L.irmv_engine_set_numbers(self._h, C.byref(o)))
+
+    def numbers(self) -> dict:
+        o = capi.NumberOpts()
+        capi.check(self._L.irmv_engine_get_numbers(self._h, C.byref(o)))
+        return dict(enable=bool(o.enable))
+
+    def plate_numbers(self, slot: int = 0):
+        """capi.PlateNumber records (copies) parallel to results(slot) / results_raw(slot)."""
+        return self._side_records(self._L.irmv_engine_plate_numbers, capi.PlateNumber, slot)
+
+    def numbers_at(self, patches):
+        """irmv_engine_numbers_at: the numbers of explicit patch records (capi.PlatePatch structures, e.g. plate_patches() or
+        patches_at()) under the engine's model, enabled or not -> list of capi.PlateNumber."""
+        n = len(patches)
+        src = (capi.PlatePatch * max(n, 1))(*patches)
+        out = (capi.PlateNumber * max(n, 1))()
+        capi.check(self._L.irmv_engine_numbers_at(self._h, src, n, out))
+        return [out[i] for i in range(n)]
+
     def debug_graph_count(self) -> int:
         """Test hook: the captured graphs the engine holds."""
         return int(self._L.irmv_engine_debug_graph_count(self._h))

@@ -7,7 +7,7 @@ file.  No `onnx` package exists in the image, so the few protobuf fields needed
 are decoded by hand (ModelProto.graph = 7; GraphProto.node = 1, initializer = 5;
 TensorProto: dims = 1, data_type = 2, float_data = 4, int32_data = 5, name = 8, raw_data = 9,
 double_data = 10, external_data = 13, data_location = 14; NodeProto: input = 1, output = 2,
-name = 3, op_type = 4, attribute = 5; AttributeProto: name = 1, i = 3, ints = 8).
+name = 3, op_type = 4, attribute = 5; AttributeProto: name = 1, f = 2, i = 3, ints = 8).
 
 Expected input: an Ultralytics YOLOv8n / YOLOv8n-pose export (BatchNorm already
 folded into the convs, so every conv initializer pair is `<layer>.weight`,
@@ -169,6 +169,8 @@ class _Node:
                         an = v2.decode()
                     elif f2 == 3 and w2 == 0:
                         ai = v2
+                    elif f2 == 2 and w2 == 5 and ai is None:      # f: a Gemm's alpha / beta (number_net.py)
+                        ai = struct.unpack("<f", v2)[0]
                     elif f2 == 8:
                         ais += [v2] if w2 == 0 else [int(d) for d in _varints(v2)]
                 self.attrs[an] = ais if ais else ai

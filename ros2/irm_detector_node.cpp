@@ -55,6 +55,9 @@ public:
     // plate patches (IrmDetectorCore::Params::patches): each armor's rectified number image beside its pose (FrameResult::patches;
     // not published)
     if (node_->declare_parameter("patches", false)) p.patches = YoloEngine::patch_opts();
+    // plate numbers (IrmDetectorCore::Params::number_model): the path of an .irmn model, "" = off; each armor's patch read by that
+    // MLP beside its pose (FrameResult::numbers; not published).  Live through the callback below.
+    p.number_model = node_->declare_parameter("number_model", std::string(""));
     const auto ns = node_->declare_parameter("net_input_size", std::vector<int64_t>{0, 0});   // {width, height}; {0, 0}: square default
     if (ns.size() == 2) p.net_input_size = cv::Size(int(ns[0]), int(ns[1]));
     const std::string model = node_->declare_parameter("model_path", std::string("models/yolov7.onnx"));
@@ -76,6 +79,7 @@ public:
         if (q.get_type() == rclcpp::ParameterType::PARAMETER_BOOL) core_->set_bool_parameter(q.get_name(), q.as_bool());
         else if (q.get_type() == rclcpp::ParameterType::PARAMETER_INTEGER) core_->set_parameter(q.get_name(), double(q.as_int()));
         else if (q.get_type() == rclcpp::ParameterType::PARAMETER_DOUBLE) core_->set_parameter(q.get_name(), q.as_double());
+        else if (q.get_type() == rclcpp::ParameterType::PARAMETER_STRING) core_->set_parameter(q.get_name(), q.as_string());
       return r;
     });
   }
