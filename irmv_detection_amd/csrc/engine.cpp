@@ -308,6 +308,7 @@ static EngineSwitches read_switches()
     s.split_scan = !off("IRMV_SPLIT_SCAN"); s.emit_scan = !off("IRMV_EMIT_SCAN");
     s.sparse_head = !off("IRMV_SPARSE_HEAD"); s.sparse_branch = !off("IRMV_SPARSE_BRANCH");
     s.sparse_gather = !off("IRMV_SPARSE_GATHER");
+    s.gather_kpt = !off("IRMV_GATHER_KPT"); s.kpt3_named = is1("IRMV_KPT3");
     if (const char *gg = getenv("IRMV_SPARSE_GATHER_GRID")) s.gather_grid = atoi(gg);
     s.zero_copy_results = !off("IRMV_ZERO_COPY_RESULTS"); s.post_keys_only = is1("IRMV_POST_KEYS_ONLY");
     s.nms_classwalk = !off("IRMV_NMS_CLASSWALK");

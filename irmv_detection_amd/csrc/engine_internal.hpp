@@ -129,6 +129,8 @@ struct EngineSwitches {
     bool emit_scan = true, sparse_head = true, sparse_branch = true;   // IRMV_EMIT_SCAN=0: the class-branch conv epilogues emit no candidates; IRMV_SPARSE_HEAD=0: every head row is stored;
                                    // IRMV_SPARSE_BRANCH=0: no tile gate behind the class carriers
     bool sparse_gather = true;     // IRMV_SPARSE_GATHER=0: the box branch stays the tile-gated layer launches (no OP_BOXG launch in a step)
+    bool gather_kpt = true;        // a gather launch computes its level's keypoint branch too and the step drops the OP_KPT3 launch (IRMV_GATHER_KPT=0: off)
+    bool kpt3_named = false;       // IRMV_KPT3=1 set explicitly asks for kpt3_kernel by name: its launches stay (the rule IRMV_FORCE_WRES has)
     int gather_grid = 0;           // IRMV_SPARSE_GATHER_GRID=<n> (tests): workgroups of a box_gather launch; 0: one per CU
     bool zero_copy_results = true; // IRMV_ZERO_COPY_RESULTS=0: device records + a D2H copy in keypoint mode too
     bool post_keys_only = false;   // IRMV_POST_KEYS_ONLY=1 (tests): run_post's NMS ignores scan_decode_kernel's boxes and decodes its own, as a whole step's does
@@ -187,6 +189,7 @@ struct Launch {
     bool sparse = false;      // a Detect box carrier or OP_KPT3 behind its level's class carrier: stores the candidate anchors' head rows only
     int gate = 0;             // sparse branch, ConvArgs::tile_gate / Kpt3Args::tile_gate: 0 = off, 1 = halo 0 (writes head rows), 2 = halo 1 (box branch's first conv)
     bool cand_list = false;   // OP_BOXG: the plan's first -- cand_list_kernel runs in front of it, for every level's launch
+    int kpt = -1;             // OP_BOXG: the level's OP_KPT3 op whose branch the launch computes too (the plan has dropped that launch); -1: box only
     bool once = false;        // not repeated under irmv_engine_profile (appends to, consumes or rewrites per-frame lists)
     std::string name, layer;  // irmv_engine_profile's row
     double flops = 0, bytes = 0, launch_bytes = 0;   // per frame; launch_bytes (the weights): once per launch

@@ -77,9 +77,28 @@ static void sparse_head_plan(irmv_engine *e, std::vector<Launch> &plan)
             }
             first_conv[i] = carrier >= 0 && !other;
         }
+    // Keypoint branch in the gather: a level's gather launch visits exactly the anchors whose keypoint rows the sparse OP_KPT3
+    // launch would store, with the first conv's B fragments in its hands, so it computes that branch too (a fourth wave per
+    // group, k_boxg.hip) and the step drops the OP_KPT3 launch.  IRMV_GATHER_KPT=0 keeps both launches; so does IRMV_KPT3=1 set
+    // explicitly, which asks for kpt3_kernel by name.
+    std::vector<char> rides(plan.size(), 0);
+    if (e->sw.gather_kpt && !e->sw.kpt3_named)
+        for (size_t i = 0; i < plan.size(); i++) {
+            const Op &ko = e->ops[plan[i].op];
+            if (ko.kind != OP_KPT3 || ko.level < 0 || ko.level >= 3 || !lvl_cls[ko.level] || (int)i <= last_cls) continue;
+            for (size_t j = 0; j < plan.size() && !rides[i]; j++) {
+                const Op &go = e->ops[plan[j].op];
+                if (go.kind != OP_BOXG || go.level != ko.level) continue;
+                const Op &k0 = e->ops[ko.sub[0]], &g0 = e->ops[go.sub[0]];
+                if (k0.s0.t != g0.s0.t || k0.s0.coff != g0.s0.coff || k0.cin != g0.cin || ko.Hin != go.Hin || ko.Win != go.Win) continue;
+                plan[j].kpt = plan[i].op;
+                rides[i] = 1;
+            }
+        }
     std::vector<Launch> out, moved;
     bool listed = false;
     for (size_t i = 0; i < plan.size(); i++) {
+        if (rides[i]) continue;   // (behind the last class carrier: nothing below is due at this index)
         Launch &l = plan[i];
         Op &op = e->ops[l.op];
         const bool boxg = op.kind == OP_BOXG;

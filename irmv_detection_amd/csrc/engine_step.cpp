@@ -293,7 +293,7 @@ static CandListArgs cand_list_args(const irmv_engine *e, int first, const PostAr
     return a;
 }
 
-static BoxGatherArgs boxg_args(const irmv_engine *e, const Op &op, int first, const PostArgs &pa)
+static BoxGatherArgs boxg_args(const irmv_engine *e, const Op &op, const Launch &l, int first, const PostArgs &pa)
 {
     const Op &o0 = e->ops[op.sub[0]], &o1 = e->ops[op.sub[1]], &o2 = e->ops[op.sub[2]];
     const Tensor &xt = e->tensors[o0.s0.t], &ht = e->tensors[o2.out_t];
@@ -306,6 +306,15 @@ static BoxGatherArgs boxg_args(const irmv_engine *e, const Op &op, int first, co
     a.w2 = o2.w_packed; a.b2 = o2.bias;
     a.out = static_cast<float *>(ht.slot(first)) + o2.out_coff; a.out_ld = ht.C;
     a.list = c.list[op.level]; a.count = c.count[op.level];
+    if (l.kpt >= 0) {   // the keypoint branch rides along: kpt3_args' operands
+        const Op &k = e->ops[l.kpt];
+        const Op &k0 = e->ops[k.sub[0]], &k1 = e->ops[k.sub[1]], &k2 = e->ops[k.sub[2]];
+        const Tensor &kt = e->tensors[k2.out_t];
+        a.kw0 = k0.w_lds[0]; a.kb0 = k0.bias;
+        a.kw1 = k1.w_packed; a.kb1 = k1.bias;
+        a.kw2 = k2.w_k16; a.kb2 = k2.bias;
+        a.kout = static_cast<float *>(kt.slot(first)) + k2.out_coff; a.kout_ld = kt.C;
+    }
     return a;
 }
 
@@ -392,7 +401,7 @@ int irmv::launch_op(irmv_engine *e, const View &v, const Launch &l, const Step &
     case OP_BOXG:
         if (!pa.cand_bits) return fail(IRMV_ERR_ARG, "a box gather launch needs the sparse head's bitmap: " + op.layer);
         if (l.cand_list) launch_cand_list(cand_list_args(e, first, pa), count, s);
-        if (!launch_box_gather(boxg_args(e, op, first, pa), op.cin, count, e->sw.gather_grid > 0 ? e->sw.gather_grid : e->num_cus, s)) return fail(IRMV_ERR_ARG, "no box gather kernel for " + op.layer);
+        if (!launch_box_gather(boxg_args(e, op, l, first, pa), op.cin, count, e->sw.gather_grid > 0 ? e->sw.gather_grid : e->num_cus, s)) return fail(IRMV_ERR_ARG, "no box gather kernel for " + op.layer);
         break;
     case OP_DW: launch_dwconv3x3(dw_args(e, op, first), count, s); break;
     case OP_SHUF: launch_shuffle_cat(shuf_args(e, op, first, count), s); break;

@@ -317,6 +317,15 @@ struct BoxGatherArgs {
     int out_ld;
     const int *list;      // [B][H * W], const int *count: [B] (CandListArgs)
     const int *count;
+    // the level's keypoint branch in the same launch (Kpt3Args' operands w1 .. b3 and out); kw0 == nullptr: box only
+    const half_t *kw0;    // first conv: LDS-family nt = 1 packing [chunk of 32][tap][64 lanes][8]
+    const float *kb0;
+    const half_t *kw1;    // second conv: Cin = 16 direct packing [5 k-steps][64 lanes][8]
+    const float *kb1;
+    const half_t *kw2;    // final 1x1: A layout of v_mfma_f32_16x16x16_f16 [64 lanes][4]
+    const float *kb2;
+    float *kout;          // head records, offset to the keypoint channels
+    int kout_ld;
 };
 bool box_gather_eligible(int cin);
 bool launch_box_gather(const BoxGatherArgs &a, int cin, int batch, int grid, hipStream_t s);   // grid: the persistent workgroups (captured with the step)

@@ -29,8 +29,8 @@ def internal_name(sym):
     m = re.search(r"kpt3_kernel<(\d)>", sym) or re.search(r"kpt3_kernelILi(\d)E", sym)
     if m:   # the keypoint branch of a Detect level in one launch (round 5): <Cin / 64>
         return f"kpt3_c{64 * int(m.group(1))}"
-    m = re.search(r"box_gather_kernel<(\d)>", sym) or re.search(r"box_gather_kernelILi(\d)E", sym)
-    if m:   # the box branch of a Detect level at the candidate anchors (k_boxg.hip): <Cin / 64>
+    m = re.search(r"box_gather_kernel<(\d)(?:, (?:true|false))?>", sym) or re.search(r"box_gather_kernelILi(\d)E", sym)
+    if m:   # the box branch of a Detect level at the candidate anchors (k_boxg.hip): <Cin / 64, with the keypoint branch>
         return f"box_gather_c{64 * int(m.group(1))}"
     if "cand_list_kernel" in sym:   # (no row of the profile: it runs inside the first box_gather launch's bracket)
         return "cand_list"
