@@ -108,6 +108,11 @@ public:
     // yaw_publish changes nothing.
     irmv_yaw_opts yaw_solve{};
     bool yaw_publish = false;
+    // Pose uncertainty (include/irmv_hip.h): pose_cov enables it on the three engines at creation with corner noise sigma_px
+    // (pixels, in (0, 64]) -- FrameResult::covs is then filled.  Live: set_parameter "pose_cov" (0 | 1; the first 1 enables),
+    // "sigma_px".  Models with a keypoint head only, like FrameResult::yaw.
+    bool pose_cov = false;
+    double sigma_px = 1.0;
     // Plate patches (include/irmv_hip.h): struct_size != 0 enables them on the three engines at creation
     // (YoloEngine::patch_opts()) -- FrameResult::patches is then filled.  Live: set_parameter "patches" (0 | 1; the first 1
     // enables).  Models with a keypoint head only, like FrameResult::yaw.
@@ -144,6 +149,9 @@ public:
     // Params::yaw_solve only (else empty): parallel to `poses`, the plate's pose with its yaw solved at the class's known tilt
     // and the up vector (state 1; -1: refused, 0: nothing)
     std::vector<irmv_yaw_pose> yaw;
+    // Params::pose_cov only (else empty): parallel to `poses`, the first-order covariance of each armor's pose -- and, where
+    // `yaw` is filled, of its constrained pose -- under Params::sigma_px of corner noise (state 1; -1: refused, 0: nothing)
+    std::vector<irmv_pose_cov> covs;
     // Params::patches only (else empty): parallel to `poses`, each armor's rectified 20 x 28 gray number image, its Otsu
     // threshold and the colour vote of its two light bars (state 1; 0: no patch)
     std::vector<irmv_plate_patch> patches;
@@ -177,6 +185,7 @@ public:
       if (p.enemy_color != -1 || !p.large_plate_classes.empty()) push_class_policy(*e);
       if (p.pose_prior.struct_size != 0) { e->set_pose_prior(&p.pose_prior); e->set_up(p.up); }
       if (p.yaw_solve.struct_size != 0) { e->set_yaw_solve(p.yaw_solve); e->set_up(p.up); }
+      if (p.pose_cov) e->set_pose_cov(YoloEngine::pose_cov_opts(true, p.sigma_px));
       if (p.patches.struct_size != 0) e->set_patches(p.patches);
       if (!p.number_model.empty()) { e->set_number_model(p.number_model); e->set_numbers(true); }
     }
@@ -206,6 +215,7 @@ public:
     std::vector<irmv_det> poses;
     std::vector<irmv_pose_alt> alts;
     std::vector<irmv_yaw_pose> yaws;
+    std::vector<irmv_pose_cov> covs;
     std::vector<irmv_plate_patch> plates;
     std::vector<irmv_plate_number> numbers;
     if (eng.has_keypoint_head()) {
@@ -214,6 +224,7 @@ public:
       const irmv_det * dets = eng.last_detections(&n);
       const std::vector<irmv_pose_alt> all = eng.pose_alts();   // parallel to dets (empty: not enabled)
       const std::vector<irmv_yaw_pose> all_yaw = eng.yaw_poses();
+      const std::vector<irmv_pose_cov> all_covs = eng.pose_covs();
       const std::vector<irmv_plate_patch> all_plates = eng.plate_patches();
       const std::vector<irmv_plate_number> all_numbers = eng.plate_numbers();
       for (int i = 0; i < n; i++) {
@@ -221,6 +232,7 @@ public:
         if (d.armor_valid != 1) continue;
         if (size_t(i) < all.size()) alts.push_back(all[size_t(i)]);
         if (size_t(i) < all_yaw.size()) yaws.push_back(all_yaw[size_t(i)]);
+        if (size_t(i) < all_covs.size()) covs.push_back(all_covs[size_t(i)]);
         if (size_t(i) < all_plates.size()) plates.push_back(all_plates[size_t(i)]);
         if (size_t(i) < all_numbers.size()) numbers.push_back(all_numbers[size_t(i)]);
         Armor a(Light(cv::Point2f(d.kpts[2], d.kpts[3]), cv::Point2f(d.kpts[0], d.kpts[1])),
@@ -253,6 +265,7 @@ public:
       out.armors.push_back(armors[i]);
       out.poses.push_back(d);
       if (alts.size() == armors.size()) out.alts.push_back(alts[i]);
+      if (covs.size() == armors.size()) out.covs.push_back(covs[i]);
       if (plates.size() == armors.size()) out.patches.push_back(plates[i]);
       if (numbers.size() == armors.size()) out.numbers.push_back(numbers[i]);
       if (yaws.size() == armors.size()) {
@@ -351,6 +364,18 @@ public:
       o.enable = int(value);
       params_.yaw_solve = o;
       for (auto & e : yolo_engines_) { e->set_yaw_solve(o); e->set_up(params_.up); }
+      return true;
+    }
+    else if (name == "pose_cov" || name == "sigma_px") {
+      // live; the first pose_cov = 1 enables the records (one re-capture per engine), later calls re-capture nothing
+      const bool on = name == "pose_cov" ? value == 1.0 : params_.pose_cov;
+      const double sigma = name == "sigma_px" ? value : params_.sigma_px;
+      if (name == "pose_cov" && value != 0.0 && value != 1.0) return false;
+      if (!(sigma > 0.0 && sigma <= 64.0)) return false;
+      if (on || params_.pose_cov)
+        for (auto & e : yolo_engines_) e->set_pose_cov(YoloEngine::pose_cov_opts(on, sigma));
+      params_.pose_cov = on;
+      params_.sigma_px = sigma;
       return true;
     }
     else if (name == "patches") {

@@ -80,6 +80,25 @@ public:
     return n;
   }
 
+  // The first-order covariance of a pose of the armor under corner noise of sigma_px pixels (irmv_pnp_pose_cov; include/irmv_hip.h,
+  // "pose uncertainty"): rvec / tvec as solvePnP or solvePnPGeneric returned them -- the second solution's is how the alt
+  // pose gets one.  up != nullptr: the pose is a constrained pose about that vector and the yaw block is filled too.
+  irmv_pose_cov pose_cov(const Armor & armor, const cv::Mat & rvec, const cv::Mat & tvec, double sigma_px = 1.0,
+                         const std::array<double, 3> * up = nullptr, int armor_size = IRMV_ARMOR_SMALL) const
+  {
+    const float pts[8] = {armor.left_light.bottom.x, armor.left_light.bottom.y, armor.left_light.top.x, armor.left_light.top.y,
+                          armor.right_light.top.x, armor.right_light.top.y, armor.right_light.bottom.x, armor.right_light.bottom.y};
+    double r[3], t[3];
+    for (int i = 0; i < 3; i++) {
+      r[i] = rvec.at<double>(i);
+      t[i] = tvec.at<double>(i);
+    }
+    irmv_pose_cov out{};
+    if (irmv_pnp_pose_cov(pnp_, pts, 1, armor_size, r, t, up ? up->data() : nullptr, sigma_px, &out) != IRMV_OK)
+      throw std::runtime_error(std::string("PnPSolver::pose_cov: ") + irmv_last_error());
+    return out;
+  }
+
   // |p - (cx, cy)| with the true principal point.  (The reference reads K with
   // at<float>() from a CV_64F matrix, src/pnp_solver.cpp:56-57, and therefore uses
   // (0.0, 7.6e12) with the shipped YAML -- SURVEY.md Appendix E.1.)

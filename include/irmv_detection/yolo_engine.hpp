@@ -328,6 +328,32 @@ public:
   // Parallel to last_detections(): entry i is the constrained pose of record i (empty before the first set_yaw_solve)
   std::vector<irmv_yaw_pose> yaw_poses() const { return side_records<irmv_yaw_pose>(yaw_on_, irmv_engine_yaw_poses, "yaw_poses"); }
 
+  // ---- pose uncertainty (include/irmv_hip.h, "pose uncertainty") ----
+  // From the first set_pose_cov on every detect() also computes, per solved record, the first-order covariance of its IPPE
+  // pose and -- where yaws are solved -- of its constrained pose under corner noise of sigma_px pixels: pose_covs().  The
+  // first call re-captures the steps once; later calls re-capture nothing.  A refused value throws, nothing changes.
+  static irmv_pose_cov_opts pose_cov_opts(bool enable = true, double sigma_px = 1.0)
+  {
+    irmv_pose_cov_opts o{};
+    o.struct_size = sizeof o; o.enable = enable ? 1 : 0; o.sigma_px = sigma_px;
+    return o;
+  }
+  void set_pose_cov(const irmv_pose_cov_opts & o = pose_cov_opts())
+  {
+    if (irmv_engine_set_pose_cov(engine_, &o) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::set_pose_cov: ") + irmv_last_error());
+    pose_cov_on_ = true;
+  }
+  irmv_pose_cov_opts pose_cov() const
+  {
+    irmv_pose_cov_opts o;
+    if (irmv_engine_get_pose_cov(engine_, &o) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::pose_cov: ") + irmv_last_error());
+    return o;
+  }
+  // Parallel to last_detections(): entry i is the covariance of record i (empty before the first set_pose_cov)
+  std::vector<irmv_pose_cov> pose_covs() const { return side_records<irmv_pose_cov>(pose_cov_on_, irmv_engine_pose_covs, "pose_covs"); }
+
   // ---- plate patches (include/irmv_hip.h, "plate patches") ----
   // From the first set_patches on every detect() also rectifies, per record with armor_valid == 1, the 20 x 28 gray number
   // image between the light bars out of the slot's frame: plate_patches().  The first call re-captures the steps once; later
@@ -675,6 +701,7 @@ private:
   int enemy_color_ = -1;
   bool pose_alts_on_ = false;         // set_pose_prior has been called: the engine delivers alt records
   bool yaw_on_ = false;               // set_yaw_solve has been called: the engine delivers constrained poses
+  bool pose_cov_on_ = false;          // set_pose_cov has been called: the engine delivers pose covariances
   bool patches_on_ = false;           // set_patches has been called: the engine delivers plate patches
   bool numbers_on_ = false;           // set_numbers(true) has been called: the engine delivers plate numbers
   cv::Size src_image_size_;

@@ -662,6 +662,56 @@ int irmv_engine_get_yaw_solve(const irmv_engine *e, irmv_yaw_opts *opts);   /* b
 /* Parallel to irmv_engine_results, as irmv_engine_pose_alts is.  IRMV_ERR_ARG before the first irmv_engine_set_yaw_solve. */
 int irmv_engine_yaw_poses(irmv_engine *e, int slot, irmv_yaw_pose *out, int cap, int *n);
 
+/* ---- pose uncertainty: the first-order covariance of the IPPE and the constrained pose ---------------------------------
+ * A tracker behind these records needs a measurement noise per measurement.  From the first irmv_engine_set_pose_cov on, a
+ * step computes, for every record with pnp_ok == 1 and armor_valid == 1, the Gauss-Newton covariance of its pose under
+ * independent corner noise of sigma_px pixels, in a kernel of its own behind the constrained pose's (behind the NMS / the
+ * light extraction where there is none), and delivers one side record per detection (irmv_engine_pose_covs).  irmv_det,
+ * irmv_pose_alt, irmv_yaw_pose, irmv_plate_patch, irmv_plate_number and irmv_tile_det stay byte-identical whether or not it is
+ * on.  The model, fp64 in the written order (no fused multiply-add, every division a division);
+ * irmv_detection_amd/pose_cov.py states it operation for operation:
+ *   corners      (nx_i, ny_i): the four undistorted normalised corners the IPPE solver sees for the record's kpts
+ *   object       P_i: the corners of the plate the pose was solved with (the record's armor_size)
+ *   pose         R from rvec by Rodrigues' formula, sin and cos from two stated series (the device has no libm the host could
+ *                follow bit for bit; the series are exact to ~ 1e-15 on the reduced angle); t = tvec
+ *   projection   X_i = R P_i + t,  x_i = X_i.x / X_i.z,  y_i = X_i.y / X_i.z
+ *   residuals    r_2i = ((x_i - nx_i) fx) / sigma_px,  r_2i+1 = ((y_i - ny_i) fy) / sigma_px -- a PIXEL residual that ignores
+ *                the distortion's own Jacobian
+ *   parameters   R <- exp([w]x) R, t <- t + tau, ordered (w_x, w_y, w_z, tau_x, tau_y, tau_z) in the CAMERA frame;
+ *                dX_i/dw = -[R P_i]x, dX_i/dtau = I; J is the analytic 8 x 6 Jacobian of r
+ *   covariance   A = J^T J (each entry summed over the rows in ascending order), Cholesky A = L L^T, Sigma = A^-1 by two
+ *                triangular solves per column; cov[21] is Sigma's upper triangle, row-major
+ *   chi2         the sum of the eight r^2;  sigma_range = sqrt(d^T Sigma_tautau d), d = t / |t|
+ *   yaw block    where the engine solves constrained poses and the record's irmv_yaw_pose.state == 1: the parameters are
+ *                (psi, tau) at THAT pose, dX_i/dpsi = u x (R_yaw P_i) with the slot's up vector u; yaw_cov[10] is the upper
+ *                triangle of the 4 x 4 inverse, sigma_yaw = sqrt(yaw_cov[0]) (radians)
+ * A record is refused (state -1, everything else zero) where a corner has depth <= 0, an input is not finite (a coordinate
+ * >= 2^24 counts, as for the solver), a pivot p has !(p > 0) or an output is not finite; yaw_state likewise for its block.
+ * sigma_px is the only modelling parameter: a caller who prefers the a-posteriori scale multiplies cov by chi2 / 2 (yaw_cov by
+ * yaw_chi2 / 4) itself.
+ * Nothing is allocated and nothing new is launched until the first irmv_engine_set_pose_cov.  That call waits for everything
+ * in flight, allocates the records and the option table and drops the captured graphs once; later calls rewrite the table the
+ * kernel reads when it runs and re-capture nothing.  enable = 0: the kernel returns at once and irmv_engine_pose_covs delivers
+ * all-zero records.  Explicit boxes have no such record.  Tiled steps: the record of merged record r is
+ * irmv_engine_pose_covs(first + r.tile)[r.index].  Window slots: the crop only moves the principal point, so a window engine's
+ * record equals a plain engine's on the cropped frame. */
+typedef struct irmv_pose_cov_opts {
+    uint32_t struct_size;        /* = sizeof(irmv_pose_cov_opts) */
+    int32_t  enable;             /* 0 | 1 */
+    double   sigma_px;           /* in (0, 64]; default 1 */
+} irmv_pose_cov_opts;
+typedef struct irmv_pose_cov {
+    double  cov[21], chi2, sigma_range;          /* upper triangle of the 6 x 6, row-major; sum of r^2; metres along the ray */
+    double  yaw_cov[10], yaw_chi2, sigma_yaw;    /* upper triangle of the 4 x 4 of (psi, tau); sum of r^2; radians */
+    int32_t state, yaw_state;                    /* 0: nothing here (all zero); 1: computed; -1: refused */
+} irmv_pose_cov;                                 /* 288 bytes */
+/* IRMV_ERR_ARG before the GPU is touched, leaving everything as it was: a null engine or opts, a wrong struct_size, enable
+ * outside {0, 1}, sigma_px outside (0, 64] or NaN. */
+int irmv_engine_set_pose_cov(irmv_engine *e, const irmv_pose_cov_opts *opts);
+int irmv_engine_get_pose_cov(const irmv_engine *e, irmv_pose_cov_opts *opts);   /* before the first set: the defaults with enable = 0 */
+/* Parallel to irmv_engine_results, as irmv_engine_pose_alts is.  IRMV_ERR_ARG before the first irmv_engine_set_pose_cov. */
+int irmv_engine_pose_covs(irmv_engine *e, int slot, irmv_pose_cov *out, int cap, int *n);
+
 /* ---- plate patches: each armor's rectified number image ---------------------------------------------------------------
  * A consumer of such a detector cuts the number plate out of the frame between the two light bars, rectifies it with the
  * four points and hands the small gray image to a number classifier.  From the first irmv_engine_set_patches on, a step does
@@ -1188,6 +1238,13 @@ int irmv_pnp_solve2(irmv_pnp *p, const float *img_pts, int n, int armor_size, do
  * non-finite or >= 2^24 coordinate.  opts->enable is not read.  IRMV_ERR_ARG: what the engine calls refuse. */
 int irmv_pnp_solve_yaw(irmv_pnp *p, const float *img_pts, int n, int armor_size, const double up[3], double normal_up,
                        const irmv_yaw_opts *opts, irmv_yaw_pose *out);
+/* The pose uncertainty ("pose uncertainty" above) of n quads at explicit poses rvec [n][3], tvec [n][3]: out [n].  This is also
+ * how a caller gets the covariance of the alt pose.  up != NULL (normalised as irmv_engine_set_up does): the poses are taken
+ * as constrained poses about it and the yaw block is computed too; NULL: yaw_state = 0.  Every quad is taken as solved
+ * input: state is 1 or -1.  IRMV_ERR_ARG before the GPU is touched: a null argument, n < 0, a bad armor_size, sigma_px outside
+ * (0, 64] or NaN, an up vector that is zero or not finite. */
+int irmv_pnp_pose_cov(irmv_pnp *p, const float *img_pts, int n, int armor_size, const double *rvec, const double *tvec,
+                      const double up[3], double sigma_px, irmv_pose_cov *out);
 
 #ifdef __cplusplus
 }

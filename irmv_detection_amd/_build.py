@@ -36,6 +36,7 @@ SOURCES = [
     ("k_render.hip", []),
     ("k_meter.hip", []),
     ("k_yaw.hip", ["-ffp-contract=off"]),   # the constrained pose: a module of its own (its header)
+    ("k_posecov.hip", ["-ffp-contract=off"]),   # the pose uncertainty: a module of its own, fp64 in the written order (its header)
     ("k_patch.hip", ["-ffp-contract=off"]),   # plate patches: a module of its own, fp64 in the written order (its header)
     ("k_number.hip", ["-ffp-contract=off"]),   # plate numbers: a module of its own, fp32 in the written order (its header)
     ("k_debug.hip", []),
@@ -48,6 +49,7 @@ SOURCES = [
     ("engine_hooks.cpp", ["-x", "hip"]),
     ("engine_meter.cpp", ["-x", "hip"]),
     ("engine_yaw.cpp", ["-x", "hip", "-ffp-contract=off"]),   # (its host arithmetic is the reference's, operation for operation)
+    ("engine_posecov.cpp", ["-x", "hip", "-ffp-contract=off"]),
     ("engine_patch.cpp", ["-x", "hip", "-ffp-contract=off"]),
     ("engine_number.cpp", ["-x", "hip", "-ffp-contract=off"]),
 ]

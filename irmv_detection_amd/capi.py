@@ -204,6 +204,26 @@ class YawPose(C.Structure):
                 ("state", C.c_int32), ("lane", C.c_int32 * 6), ("reserved", C.c_int32)]
 
 
+class PoseCovOpts(C.Structure):
+    """irmv_pose_cov_opts (include/irmv_hip.h, "pose uncertainty")."""
+    _fields_ = [("struct_size", C.c_uint32), ("enable", C.c_int32), ("sigma_px", C.c_double)]
+
+
+class PoseCov(C.Structure):
+    """irmv_pose_cov (include/irmv_hip.h): the covariance of one detection's IPPE pose and of its constrained pose."""
+    _fields_ = [("cov", C.c_double * 21), ("chi2", C.c_double), ("sigma_range", C.c_double),
+                ("yaw_cov", C.c_double * 10), ("yaw_chi2", C.c_double), ("sigma_yaw", C.c_double),
+                ("state", C.c_int32), ("yaw_state", C.c_int32)]
+
+
+def pose_cov_opts_struct(enable=1, sigma_px=1.0) -> PoseCovOpts:
+    """An irmv_pose_cov_opts (no check: the library's are the ones under test)."""
+    o = PoseCovOpts()
+    o.struct_size = C.sizeof(PoseCovOpts)
+    o.enable, o.sigma_px = int(enable), float(sigma_px)
+    return o
+
+
 def yaw_opts_struct(enable=1, rounds=4, tau_max=1.0, horizon_min=1e-4) -> YawOpts:
     """An irmv_yaw_opts (no check: the library's are the ones under test)."""
     o = YawOpts()
@@ -397,6 +417,11 @@ SYMBOLS = [
     ("irmv_engine_yaw_poses", C.c_int, [_P, C.c_int, C.POINTER(YawPose), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_pnp_solve_yaw", C.c_int, [_P, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double,
                                      C.POINTER(YawOpts), C.POINTER(YawPose)]),
+    ("irmv_engine_set_pose_cov", C.c_int, [_P, C.POINTER(PoseCovOpts)]),
+    ("irmv_engine_get_pose_cov", C.c_int, [_P, C.POINTER(PoseCovOpts)]),
+    ("irmv_engine_pose_covs", C.c_int, [_P, C.c_int, C.POINTER(PoseCov), C.c_int, C.POINTER(C.c_int)]),
+    ("irmv_pnp_pose_cov", C.c_int, [_P, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), C.c_double, C.POINTER(PoseCov)]),
     ("irmv_engine_set_patches", C.c_int, [_P, C.POINTER(PatchOpts)]),
     ("irmv_engine_get_patches", C.c_int, [_P, C.POINTER(PatchOpts)]),
     ("irmv_engine_plate_patches", C.c_int, [_P, C.c_int, C.POINTER(PlatePatch), C.c_int, C.POINTER(C.c_int)]),

@@ -95,7 +95,7 @@ irmv_engine::~irmv_engine()
     for (const DevRange &r : dev_allocs) (void)hipFree(r.base);
     dev_allocs.clear();
     if (src_host) (void)hipHostFree(src_host);
-    dets.free_host(); fout.free_host(); alts.free_host(); yaw.free_host(); patch.free_host(); number.free_host(); meter.free_host();   // the record channels
+    dets.free_host(); fout.free_host(); alts.free_host(); yaw.free_host(); posecov.free_host(); patch.free_host(); number.free_host(); meter.free_host();   // the record channels
     if (light_dets_host) (void)hipHostFree(light_dets_host);
     for (auto &kv : tile_merges)
         if (kv.second.out_host) (void)hipHostFree(kv.second.out_host);
@@ -465,6 +465,7 @@ extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **o
     e->sw = read_switches();
     pose_prior_defaults(&e->pose_prior);
     yaw_opts_defaults(&e->yaw_opts);
+    pose_cov_opts_defaults(&e->posecov_opts);
     patch_opts_defaults(&e->patch_opts);
     e->up.assign((size_t)cfg->num_slots * 3, 0.0);
     for (int s = 0; s < cfg->num_slots; s++) e->up[3 * s + 1] = -1.0;   // a level camera: image y points down
@@ -977,11 +978,14 @@ static void pnp_free(irmv_pnp *p)
     if (p->err) (void)hipFree(p->err);
     if (p->ok) (void)hipFree(p->ok);
     if (p->yaw) (void)hipFree(p->yaw);
+    if (p->cov_poses) (void)hipFree(p->cov_poses);
+    if (p->cov) (void)hipFree(p->cov);
+    p->cov_poses = nullptr; p->cov = nullptr;
     p->yaw = nullptr;
     p->pts = nullptr; p->rvec = p->tvec = p->err = nullptr; p->ok = nullptr; p->cap = 0;
 }
 
-int pnp_reserve(irmv_pnp *p, int n)   // (engine_yaw.cpp's stand-alone call reserves here too)
+int pnp_reserve(irmv_pnp *p, int n)   // (engine_yaw.cpp's and engine_posecov.cpp's stand-alone calls reserve here too)
 {
     if (n <= p->cap) return IRMV_OK;
     pnp_free(p);
@@ -992,6 +996,8 @@ int pnp_reserve(irmv_pnp *p, int n)   // (engine_yaw.cpp's stand-alone call rese
     HIP_TRY(hipMalloc((void **)&p->err, (size_t)cap * 16));
     HIP_TRY(hipMalloc((void **)&p->ok, (size_t)cap * 4));
     HIP_TRY(hipMalloc((void **)&p->yaw, (size_t)cap * sizeof(DevYaw)));
+    HIP_TRY(hipMalloc((void **)&p->cov_poses, (size_t)cap * 6 * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&p->cov, (size_t)cap * sizeof(DevPoseCov)));
     p->cap = cap;
     return IRMV_OK;
 }

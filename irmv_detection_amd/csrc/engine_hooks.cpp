@@ -689,9 +689,9 @@ extern "C" int irmv_engine_run_conv_candidate(irmv_engine *e, int op, int tune_c
 // ---- per-op test hooks (tests/test_gpu_graph_ops.py) ---------------------------------
 static const char *op_kind_name(OpKind k)   // (in OpKind's order)
 {
-    static const char *const names[] = {"pre", "conv0", "conv", "pool", "nms", "light", "front", "c2f2", "c2f32", "dw", "shuffle", "scan", "bneck", "kpt3", "boxg", "demosaic", "crop", "meter", "yaw", "patch", "number"};
-    static_assert(sizeof names / sizeof *names == OP_NUMBER + 1, "a name per OpKind");
-    return (unsigned)k <= OP_NUMBER ? names[k] : "?";
+    static const char *const names[] = {"pre", "conv0", "conv", "pool", "nms", "light", "front", "c2f2", "c2f32", "dw", "shuffle", "scan", "bneck", "kpt3", "boxg", "demosaic", "crop", "meter", "yaw", "patch", "number", "pose_cov"};
+    static_assert(sizeof names / sizeof *names == OP_POSECOV + 1, "a name per OpKind (OP_POSECOV is the last)");
+    return (unsigned)k <= OP_POSECOV ? names[k] : "?";
 }
 
 // The activation channels op writes: [*coff, *coff + *C) of tensor *t (-1: none).  The pool writes slices 1..3 of its

@@ -14,6 +14,7 @@
 //   engine_hooks.cpp  read-backs, debug images, debug_*, LDS fill / probe, conv and op test hooks, the profiler, the light trace
 //   engine_meter.cpp  frame metering: its checks and map, the record's host helpers, the on-demand call, the step's launch
 //   engine_yaw.cpp    constrained pose: its checks, the two tables and who rewrites them, the step's launch, the stand-alone call
+//   engine_posecov.cpp pose uncertainty: its checks, the option table, the step's launch, the stand-alone call
 //   engine_patch.cpp  plate patches: their checks, the option table, the step's launch, the on-demand call
 //   engine_number.cpp plate numbers: the model's checks, its .irmn file and upload, the switch, the step's launch, the on-demand call
 #pragma once
@@ -141,7 +142,7 @@ struct EngineSwitches {
     bool nms_stamps = false; int nms_stamps_slots = 0;   // IRMV_NMS_STAMPS=<n>: the NMS kernel stamps its phases, the destructor prints the first n slots' (at least four)
 };
 
-enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_BOXG, OP_DEMOSAIC, OP_CROP, OP_METER, OP_YAW, OP_PATCH, OP_NUMBER };
+enum OpKind { OP_PRE, OP_CONV0, OP_CONV, OP_POOL, OP_NMS, OP_LIGHT, OP_FRONT, OP_C2F2, OP_C2F32, OP_DW, OP_SHUF, OP_SCAN, OP_BNECK, OP_KPT3, OP_BOXG, OP_DEMOSAIC, OP_CROP, OP_METER, OP_YAW, OP_PATCH, OP_NUMBER, OP_POSECOV };
 
 struct Op {
     OpKind kind;
@@ -272,6 +273,8 @@ struct irmv_pnp {
     int32_t *ok = nullptr;
     DevYaw *yaw = nullptr;                     // [cap]: irmv_pnp_solve_yaw's records
     int cap = 0;
+    double *cov_poses = nullptr;               // [cap][6]: irmv_pnp_pose_cov's poses (rvec, tvec) ...
+    DevPoseCov *cov = nullptr;                 // [cap]: ... and its records
 };
 int pnp_reserve(irmv_pnp *p, int n);           // engine.cpp: the object's buffers for n quads
 
@@ -441,6 +444,7 @@ struct irmv_engine {
     Records<DevFrameOut> fout;
     Records<DevAlt> alts;
     Records<DevYaw> yaw;
+    Records<DevPoseCov> posecov;
     Records<DevPatch> patch;
     Records<DevNumber> number;
     bool zero_copy_results = false;   // the NMS kernel writes its results straight into pinned host memory (no D2H copy)
@@ -464,6 +468,13 @@ struct irmv_engine {
     irmv_yaw_opts yaw_opts{};
     YawTable *yaw_table_dev = nullptr;
     YawBasis *yaw_basis_dev = nullptr;        // [S]
+    // Pose uncertainty (irmv_engine_set_pose_cov): nothing below but posecov_opts (a host value) exists until the first call.  It
+    // allocates the records (`posecov` above) and the option table, appends the op (posecov_op: behind the yaw op's launch
+    // where there is one, else behind the NMS / the light extraction) and drops the captured graphs once.  Later calls rewrite
+    // the table.
+    int posecov_op = -1;
+    irmv_pose_cov_opts posecov_opts{};
+    PoseCovTable *posecov_table_dev = nullptr;
     // Plate patches (irmv_engine_set_patches).  Nothing below but patch_opts (a host value) exists until the first set_patches
     // -- the records (`patch` above), the table, the op (patch_op, placed as yaw_op is), one drop of the captured graphs -- or
     // the first irmv_engine_patches_at: the table and the call's three buffers.
@@ -541,7 +552,7 @@ int choose_sync_launch(irmv_engine *e);
 // engine_plan.cpp
 void finalize_head_fusion(irmv_engine *e);
 void build_step_plans(irmv_engine *e, View &v);
-void append_op(irmv_engine *e, OpKind kind);   // OP_METER, OP_YAW, OP_PATCH or OP_NUMBER, at its feature's first enable
+void append_op(irmv_engine *e, OpKind kind);   // OP_METER, OP_YAW, OP_POSECOV, OP_PATCH or OP_NUMBER, at its feature's first enable
 // engine_step.cpp
 void fill_conv_args(const irmv_engine *e, const Op &op, int first, int count, ConvArgs &a, bool fused = false);
 int slots_view(const irmv_engine *e, int first, int count, int *view = nullptr);
@@ -570,6 +581,9 @@ int ensure_dense_head(irmv_engine *e, int slot);
 void yaw_opts_defaults(irmv_yaw_opts *o);
 int write_yaw_tables(irmv_engine *e, int slot = -1);   // no-op before the first set_yaw_solve; slot >= 0: that slot's basis alone
 void launch_yaw(const irmv_engine *e, const Step &s, const PostArgs &pa, hipStream_t st);
+// engine_posecov.cpp
+void pose_cov_opts_defaults(irmv_pose_cov_opts *o);
+void launch_posecov(const irmv_engine *e, const Step &s, const PostArgs &pa, hipStream_t st);
 // engine_patch.cpp
 void patch_opts_defaults(irmv_patch_opts *o);
 void launch_patch(const irmv_engine *e, const View &v, const Step &s, const PostArgs &pa, hipStream_t st);

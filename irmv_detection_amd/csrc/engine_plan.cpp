@@ -149,15 +149,15 @@ static bool box_gathers(const irmv_engine *e, const Op &g, bool one)
 // ---- ops a feature appends to the steps ---------------------------------------------------
 // The op kinds that are not part of the network's op list: a feature appends one to e->ops at its first enable (append_op).
 // build_step_plans skips them in its loop and places their launches behind it, in this order.
-static constexpr OpKind kAppendedOps[] = {OP_METER, OP_YAW, OP_PATCH, OP_NUMBER};
+static constexpr OpKind kAppendedOps[] = {OP_METER, OP_YAW, OP_POSECOV, OP_PATCH, OP_NUMBER};
 static bool is_appended(OpKind k) { return std::find(std::begin(kAppendedOps), std::end(kAppendedOps), k) != std::end(kAppendedOps); }
 
 // Everything that differs between them, decided here and nowhere else:
 //   index    where the engine keeps the op's index in e->ops (-1: never enabled)
-//   anchor   the launch stands directly behind the plan's last op of one of these two kinds
+//   anchor   the launch stands directly behind the plan's last op of one of these kinds
 //   records  a side-record op: run_post's plan launches it too (the meter: BATCH and ONE steps only)
 //   bytes    irmv_engine_profile's per-frame figure of the launch in view v
-struct AppendedOp { int *index; const char *name; OpKind anchor[2]; bool records; double bytes; };
+struct AppendedOp { int *index; const char *name; std::vector<OpKind> anchor; bool records; double bytes; };
 static AppendedOp appended_op(irmv_engine *e, const View &v, OpKind kind)
 {
     const double md = (double)e->cfg.max_det;
@@ -168,11 +168,17 @@ static AppendedOp appended_op(irmv_engine *e, const View &v, OpKind kind)
     // the constrained pose and the plate patches: behind the last kernel that writes the DevDet records -- the NMS, or the light
     // extraction of a classical or refined engine
     case OP_YAW: return {&e->yaw_op, "yaw_solve", {OP_NMS, OP_LIGHT}, true, md * (sizeof(DevDet) + sizeof(DevYaw))};
-    case OP_PATCH: return {&e->patch_op, "plate_patch", {OP_NMS, OP_LIGHT}, true, md * (sizeof(DevDet) + sizeof(DevPatch))};
+    // the pose uncertainty reads the yaw launch's records: behind it where the plan has one (a yaw op enabled later goes
+    // directly behind the NMS, in front of it), else where the yaw launch would stand.  The patches go behind it where there is
+    // one; an engine without it has no OP_POSECOV launch and the patches stand where they always did.  One order is left in
+    // which the patches come first: yaw enabled, then the patches (nms, patch, yaw), then this op behind the yaw launch --
+    // what it reads decides, and nothing reads across the patches.
+    case OP_POSECOV: return {&e->posecov_op, "pose_cov", {OP_NMS, OP_LIGHT, OP_YAW}, true, md * (sizeof(DevDet) + sizeof(DevYaw) + sizeof(DevPoseCov))};
+    case OP_PATCH: return {&e->patch_op, "plate_patch", {OP_NMS, OP_LIGHT, OP_POSECOV}, true, md * (sizeof(DevDet) + sizeof(DevPatch))};
     // the plate numbers: directly behind the patch launch whose records they read (a plan reads nms, patch, number, yaw); the
     // weights are read once per launch's detection and stay in L2
-    case OP_NUMBER: return {&e->number_op, "plate_number", {OP_PATCH, OP_PATCH}, true, md * (sizeof(DevPatch) + sizeof(DevNumber)) + (double)kNumWeightHalves * sizeof(half_t)};
-    default: return {nullptr, "", {kind, kind}, false, 0.0};
+    case OP_NUMBER: return {&e->number_op, "plate_number", {OP_PATCH}, true, md * (sizeof(DevPatch) + sizeof(DevNumber)) + (double)kNumWeightHalves * sizeof(half_t)};
+    default: return {nullptr, "", {}, false, 0.0};
     }
 }
 
@@ -187,7 +193,7 @@ static void place_appended(irmv_engine *e, View &v, OpKind kind)
         std::vector<Launch> &plan = v.plans[k];
         size_t at = a.records ? plan.size() : 0;
         for (size_t i = 0; i < plan.size(); i++)
-            if (e->ops[plan[i].op].kind == a.anchor[0] || e->ops[plan[i].op].kind == a.anchor[1]) at = i + 1;
+            if (std::find(a.anchor.begin(), a.anchor.end(), e->ops[plan[i].op].kind) != a.anchor.end()) at = i + 1;
         Launch l; l.op = *a.index;
         l.name = l.layer = a.name;
         l.bytes = a.bytes;

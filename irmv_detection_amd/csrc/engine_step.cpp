@@ -388,6 +388,7 @@ int irmv::launch_op(irmv_engine *e, const View &v, const Launch &l, const Step &
     case OP_CROP: launch_crop(e, t, s); break;
     case OP_METER: launch_meter(e, v, t, s); break;
     case OP_YAW: launch_yaw(e, t, pa, s); break;
+    case OP_POSECOV: launch_posecov(e, t, pa, s); break;
     case OP_PATCH: launch_patch(e, v, t, pa, s); break;
     case OP_NUMBER: launch_number(e, t, pa, s); break;
     case OP_PRE: launch_preprocess(pre_args(e, v, op, first), count, s); break;
@@ -584,6 +585,7 @@ template struct Records<DevDet>;
 template struct Records<DevFrameOut>;
 template struct Records<DevAlt>;
 template struct Records<DevYaw>;
+template struct Records<DevPoseCov>;
 template struct Records<DevPatch>;
 template struct Records<DevNumber>;
 
@@ -597,6 +599,7 @@ static int copy_out_dev(irmv_engine *e, int first, int count, hipStream_t st, bo
     TRY(e->fout.copy(first, count, d2h, st));
     if (e->pose_alt) TRY(e->alts.copy(first, count, d2h, st));
     if (e->yaw_op >= 0) TRY(e->yaw.copy(first, count, d2h, st));
+    if (e->posecov_op >= 0 && e->posecov_opts.enable) TRY(e->posecov.copy(first, count, d2h, st));   // (disabled: as the patches)
     // (disabled: the kernel returns at once and set_patches has zeroed both copies -- max_det records of 592 bytes stay where they are)
     if (e->patch_op >= 0 && e->patch_opts.enable) TRY(e->patch.copy(first, count, d2h, st));
     if (e->number_op >= 0 && e->number_opts.enable) TRY(e->number.copy(first, count, d2h, st));   // (disabled: as the patches)

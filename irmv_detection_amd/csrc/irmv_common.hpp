@@ -746,6 +746,35 @@ void launch_yaw_solve(const YawArgs &a, int batch, hipStream_t s);
 // stand-alone: quad i of pts [n][8] -> out[i], every quad under the one rule
 void launch_yaw_points(const PnpConst &c, const float *pts, int n, int armor_size, const YawRule &rule, DevYaw *out, hipStream_t s);
 
+// ---- pose uncertainty (k_posecov.hip; irmv_engine_set_pose_cov) -----------------------------------------------------------
+// DevPoseCov is the side record of one detection (the layout of irmv_pose_cov).  PoseCovTable lives in device memory at an
+// address fixed from the first set_pose_cov on; the host writes it, the kernel reads it when it runs.
+constexpr int kPoseCovN = 21, kPoseCovYawN = 10, kPoseCovSeriesTerms = 16;
+struct DevPoseCov {
+    double cov[kPoseCovN], chi2, sigma_range;
+    double yaw_cov[kPoseCovYawN], yaw_chi2, sigma_yaw;
+    int32_t state, yaw_state;   // 0: nothing here (all zero); 1: computed; -1: refused
+};
+struct PoseCovTable { int32_t enable, pad_; double sigma_px; };
+// What the stand-alone form needs beside the camera, as values
+struct PoseCovRule { double sigma_px, u[3]; int32_t has_up, pad_; };
+struct PoseCovArgs {
+    const DevDet *dets;       // [B][max_det]: the records the post stage wrote
+    int max_det;
+    const int *num_dets;      // frame b: num_dets[b * num_dets_stride]
+    int num_dets_stride;
+    const PnpConst *pnp;      // frame b's camera is pnp[(first + b) * pnp_stride]
+    int first, pnp_stride;
+    const PoseCovTable *table;
+    const DevYaw *yaw;        // [B][max_det]: where the step's yaw launch wrote its records; nullptr: the engine solves no yaws
+    const YawBasis *basis;    // [num_slots]: frame b's up vector is basis[first + b].u (read where yaw is not null)
+    DevPoseCov *out;          // [B][max_det]
+};
+void launch_pose_cov(const PoseCovArgs &a, int batch, hipStream_t s);
+// stand-alone: quad i of pts [n][8] with pose poses[i] (rvec, tvec: six doubles) -> out[i]; rule.has_up: the yaw block too
+void launch_pose_cov_points(const PnpConst &c, const float *pts, const double *poses, int n, int armor_size, const PoseCovRule &rule,
+                            DevPoseCov *out, hipStream_t s);
+
 // ---- plate patches (k_patch.hip; irmv_engine_set_patches) ---------------------------------------------------------------
 // DevPatch is the side record of one detection (the layout of irmv_plate_patch).  PatchTable lives in device memory at an
 // address fixed from the first set_patches (or patches_at) on; the host writes it, the kernel reads it when it runs.

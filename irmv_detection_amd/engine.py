@@ -477,6 +477,24 @@ class YoloEngine:
         """capi.YawPose records (copies) parallel to results(slot) / results_raw(slot)."""
         return self._side_records(self._L.irmv_engine_yaw_poses, capi.YawPose, slot)
 
+    # ---- pose uncertainty (include/irmv_hip.h; host reference: pose_cov.py) ----
+    def set_pose_cov(self, enable: bool = True, sigma_px: float = 1.0) -> None:
+        """irmv_engine_set_pose_cov: from the first call on every step also computes, per solved record, the first-order
+        covariance of its IPPE pose and -- where yaws are solved -- of its constrained pose under corner noise of sigma_px
+        pixels, and delivers it beside the record (pose_covs).  The first call re-captures the steps once; later calls
+        are live.  A refused value raises and changes nothing."""
+        o = capi.pose_cov_opts_struct(1 if enable else 0, sigma_px)
+        capi.check(self._L.irmv_engine_set_pose_cov(self._h, C.byref(o)))
+
+    def pose_cov(self) -> dict:
+        o = capi.PoseCovOpts()
+        capi.check(self._L.irmv_engine_get_pose_cov(self._h, C.byref(o)))
+        return dict(enable=bool(o.enable), sigma_px=float(o.sigma_px))
+
+    def pose_covs(self, slot: int = 0):
+        """capi.PoseCov records (copies) parallel to results(slot) / results_raw(slot)."""
+        return self._side_records(self._L.irmv_engine_pose_covs, capi.PoseCov, slot)
+
     # ---- plate patches (include/irmv_hip.h; host reference: patches.py) ----
     def set_patches(self, enable: bool = True, span=(32, 54), light_rows: int = 12, top: int = 7) -> None:
         """irmv_engine_set_patches: from the first call on every step also rectifies, per record with armor_valid == 1, the
@@ -961,3 +979,20 @@ class PnPSolver:
         the true principal point (documented deviation)."""
         cx, cy = float(self.camera_matrix[2]), float(self.camera_matrix[5])
         return float(np.hypot(np.float32(image_point[0]) - np.float32(cx), np.float32(image_point[1]) - np.float32(cy)))
+
+    def pose_cov(self, img_pts: np.ndarray, rvec, tvec, armor_size: int = capi.ARMOR_SMALL, *, up=None, sigma_px: float = 1.0):
+        """The pose uncertainty of every quad at its explicit pose (irmv_pnp_pose_cov); up: the poses are constrained poses
+        about it and the yaw block is computed too -> list of capi.PoseCov."""
+        pts = np.ascontiguousarray(img_pts, np.float32).reshape(-1, 8)
+        n = len(pts)
+        r = np.ascontiguousarray(rvec, np.float64).reshape(-1, 3)
+        t = np.ascontiguousarray(tvec, np.float64).reshape(-1, 3)
+        if len(r) != n or len(t) != n:
+            raise ValueError("pose_cov: one rvec and one tvec per quad")
+        u = None if up is None else np.ascontiguousarray(up, np.float64).reshape(3)
+        dp = C.POINTER(C.c_double)
+        out = (capi.PoseCov * max(n, 1))()
+        capi.check(self._L.irmv_pnp_pose_cov(self._h, pts.ctypes.data_as(C.POINTER(C.c_float)), n, armor_size,
+                                             r.ctypes.data_as(dp), t.ctypes.data_as(dp),
+                                             None if u is None else u.ctypes.data_as(dp), float(sigma_px), out))
+        return [out[i] for i in range(n)]

@@ -52,6 +52,11 @@ public:
     // yaw_publish: the message carries that pose where it was solved
     if (node_->declare_parameter("yaw_solve", false)) p.yaw_solve = YoloEngine::yaw_opts();
     p.yaw_publish = node_->declare_parameter("yaw_publish", false);
+    // pose uncertainty (IrmDetectorCore::Params::pose_cov): the first-order covariance of every pose under sigma_px of corner
+    // noise (FrameResult::covs; not published: auto_aim_interfaces has no field for it, INTEGRATION.md shows the layout of a
+    // geometry_msgs/PoseWithCovariance)
+    p.pose_cov = node_->declare_parameter("pose_cov", false);
+    p.sigma_px = node_->declare_parameter("sigma_px", 1.0);
     // plate patches (IrmDetectorCore::Params::patches): each armor's rectified number image beside its pose (FrameResult::patches;
     // not published)
     if (node_->declare_parameter("patches", false)) p.patches = YoloEngine::patch_opts();
