@@ -28,6 +28,7 @@
 
 #include "irmv_detection/armor.hpp"
 #include "irmv_detection/pnp_solver.hpp"
+#include "irmv_detection/tracker.hpp"
 #include "irmv_detection/yolo_engine.hpp"
 
 namespace irmv_detection
@@ -113,6 +114,14 @@ public:
     // "sigma_px".  Models with a keypoint head only, like FrameResult::yaw.
     bool pose_cov = false;
     double sigma_px = 1.0;
+    // Armor tracks (include/irmv_hip.h): struct_size != 0 (ArmorTracker::default_opts()) gives the detector ONE tracker, fed with
+    // every frame's poses in frame order -- the three engines each see every third frame, so none of them could keep the
+    // table -- and with their covariances where `pose_cov` is on; FrameResult::det_tracks / tracks are then filled, stamped
+    // from the frame's time stamp.  The camera pose in the world comes from set_camera_pose() (default identity).  The
+    // tracker's measurement is always the IPPE translation of FrameResult::poses, also where `yaw_publish` puts the constrained
+    // pose into the message: the covariance it takes from `pose_cov` is that pose's.  Live:
+    // set_parameter "tracking" (0 | 1: 0 drops the tracker and its table, 1 starts an empty one).
+    irmv_track_opts tracking{};
     // Plate patches (include/irmv_hip.h): struct_size != 0 enables them on the three engines at creation
     // (YoloEngine::patch_opts()) -- FrameResult::patches is then filled.  Live: set_parameter "patches" (0 | 1; the first 1
     // enables).  Models with a keypoint head only, like FrameResult::yaw.
@@ -158,6 +167,12 @@ public:
     // Params::number_model only (else empty): parallel to `poses`, the MLP's reading of each armor's patch -- label, runner-up,
     // margin, logits (state 1; 0: no answer, exactly where the patch has none)
     std::vector<irmv_plate_number> numbers;
+    // Params::tracking only (else empty / state 0): parallel to `poses`, what the tracker made of each armor -- id, hits, filtered
+    // position and velocity in the world frame --, the frame's header and the whole table (IRMV_TRACK_CAP entries, coasting
+    // tracks included; irmv_track_predict extrapolates one)
+    std::vector<irmv_det_track> det_tracks;
+    irmv_track_frame track_frame{};
+    std::vector<irmv_track> tracks;
     double inference_latency_ms = 0;    // YoloEngine::get_profiling_time() (:251)
     // Params::debug only (else empty): the frame with this frame's armors, boxes and labels drawn on it (:261-263; the latency
     // text lines are not drawn), and gray -> threshold(binary_threshold) -> three channels with the boxes and labels (:273-277)
@@ -192,6 +207,7 @@ public:
     yolo_engines_[0]->warm_up();   // the tile choices are shared by the three engines: one warm-up tunes for all
     for (size_t i = 1; i < yolo_engines_.size(); i++) yolo_engines_[i]->warm_up();
     pnp_solver_ = std::make_unique<PnPSolver>(k, d, p.device);
+    if (p.tracking.struct_size != 0 && p.tracking.enable) tracker_ = std::make_unique<ArmorTracker>(p.tracking, p.device);
   }
 
   // Camera::Config::image_buffers (:68-72): where the producer deposits frames
@@ -277,6 +293,19 @@ public:
           pm.pose.orientation.z = yaws[i].quat[2]; pm.pose.orientation.w = yaws[i].quat[3];
         }
       }
+    }
+    if (tracker_) {
+      // one frame of the tracker: the armors of the message, in its order, at the frame's stamp relative to the first frame's
+      // (seconds since the epoch would leave a double 2e-7 s of resolution)
+      const int64_t ns = out.armors_msg.header.stamp_ns;
+      if (!track_epoch_set_) { track_epoch_ns_ = ns; track_epoch_set_ = true; }
+      std::vector<irmv_track_obs> obs;
+      for (size_t i = 0; i < out.poses.size(); i++)
+        obs.push_back(ArmorTracker::observation(out.poses[i], out.covs.size() == out.poses.size() ? &out.covs[i] : nullptr));
+      ArmorTracker::Result r = tracker_->update(double(ns - track_epoch_ns_) * 1e-9, obs, &cam_R_, &cam_t_);
+      out.det_tracks = std::move(r.det_tracks);
+      out.track_frame = r.frame;
+      out.tracks = std::move(r.tracks);
     }
     out.inference_latency_ms = eng.get_profiling_time();
     if (params_.metering.struct_size != 0) {
@@ -388,6 +417,21 @@ public:
       for (auto & e : yolo_engines_) e->set_patches(o);
       return true;
     }
+    else if (name == "tracking") {
+      // live; 1 starts a tracker with an empty table (ids from 1), 0 drops it
+      if (value != 0.0 && value != 1.0) return false;
+      if (value == 1.0 && !tracker_) {
+        irmv_track_opts o = params_.tracking.struct_size ? params_.tracking : ArmorTracker::default_opts();
+        o.enable = 1;
+        tracker_ = std::make_unique<ArmorTracker>(o, params_.device);
+        params_.tracking = o;
+      } else if (value == 0.0) {
+        tracker_.reset();
+        track_epoch_set_ = false;
+        if (params_.tracking.struct_size) params_.tracking.enable = 0;
+      }
+      return true;
+    }
     else if (name == "yaw_publish") {
       if (value != 0.0 && value != 1.0) return false;
       params_.yaw_publish = value == 1.0;
@@ -449,6 +493,17 @@ public:
     return true;
   }
 
+  // The camera's pose in the world (R_wc row-major, t_wc) for the frames to come: what the tracker turns each armor's tvec
+  // into a world position with.  false for a value that is not finite.
+  bool set_camera_pose(const std::array<double, 9> & R_wc, const std::array<double, 3> & t_wc)
+  {
+    for (double v : R_wc) if (!std::isfinite(v)) return false;
+    for (double v : t_wc) if (!std::isfinite(v)) return false;
+    cam_R_ = R_wc;
+    cam_t_ = t_wc;
+    return true;
+  }
+
   // The node's bool parameters (parameter.as_bool(), :380-381): "debug" is live -- the next frame carries, or drops, the two
   // debug images.  (A NUMBER sent to "debug" through set_parameter stays refused, as it is not a number.)
   bool set_bool_parameter(const std::string & name, bool value)
@@ -487,5 +542,10 @@ private:
   uint64_t awb_frames_ = 0;   // frames since creation, counted while awb_period is on
   std::array<std::unique_ptr<YoloEngine>, 3> yolo_engines_;
   std::unique_ptr<PnPSolver> pnp_solver_;
+  std::unique_ptr<ArmorTracker> tracker_;      // Params::tracking: the one tracker behind the three engines
+  std::array<double, 9> cam_R_{1, 0, 0, 0, 1, 0, 0, 0, 1};
+  std::array<double, 3> cam_t_{0, 0, 0};
+  int64_t track_epoch_ns_ = 0;                 // the first tracked frame's stamp: the tracker's time zero
+  bool track_epoch_set_ = false;
 };
 }  // namespace irmv_detection

@@ -354,6 +354,58 @@ public:
   // Parallel to last_detections(): entry i is the covariance of record i (empty before the first set_pose_cov)
   std::vector<irmv_pose_cov> pose_covs() const { return side_records<irmv_pose_cov>(pose_cov_on_, irmv_engine_pose_covs, "pose_covs"); }
 
+  // ---- armor tracks (include/irmv_hip.h, "armor tracks") ----
+  // From the first set_tracking on every detect() also advances the engine's track table over its detections, in submit
+  // order: det_tracks() and tracks().  Nothing is re-captured.  A refused value throws, nothing changes.
+  static irmv_track_opts track_opts(bool enable = true)
+  {
+    irmv_track_opts o{};
+    irmv_track_default_opts(&o);   // the library's defaults
+    o.enable = enable ? 1 : 0;
+    return o;
+  }
+  void set_tracking(const irmv_track_opts & o = track_opts())
+  {
+    if (irmv_engine_set_tracking(engine_, &o) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::set_tracking: ") + irmv_last_error());
+    tracking_on_ = true;
+  }
+  irmv_track_opts tracking() const
+  {
+    irmv_track_opts o;
+    if (irmv_engine_get_tracking(engine_, &o) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::tracking: ") + irmv_last_error());
+    return o;
+  }
+  // The stamp (seconds) and the camera pose in the world of the frames to come, live as set_up is
+  void set_stamp(double t)
+  {
+    if (irmv_engine_set_stamp(engine_, 0, t) != IRMV_OK) throw std::runtime_error(std::string("YoloEngine::set_stamp: ") + irmv_last_error());
+  }
+  void set_camera_pose(const std::array<double, 9> & R_wc, const std::array<double, 3> & t_wc)
+  {
+    if (irmv_engine_set_camera_pose(engine_, 0, R_wc.data(), t_wc.data()) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::set_camera_pose: ") + irmv_last_error());
+  }
+  // Parallel to last_detections(): entry i is what the tracker made of record i (empty before the first set_tracking)
+  std::vector<irmv_det_track> det_tracks() const { return side_records<irmv_det_track>(tracking_on_, irmv_engine_det_tracks, "det_tracks"); }
+  // The table as the last detect() left it: IRMV_TRACK_CAP entries, free ones included (empty before the first set_tracking)
+  std::vector<irmv_track> tracks(irmv_track_frame * frame = nullptr) const
+  {
+    std::vector<irmv_track> a;
+    if (!tracking_on_) return a;
+    a.resize(IRMV_TRACK_CAP);
+    int n = 0;
+    if (irmv_engine_tracks(engine_, 0, frame, a.data(), IRMV_TRACK_CAP, &n) != IRMV_OK)
+      throw std::runtime_error(std::string("YoloEngine::tracks: ") + irmv_last_error());
+    a.resize(static_cast<size_t>(n));
+    return a;
+  }
+  void reset_tracks()
+  {
+    if (irmv_engine_reset_tracks(engine_) != IRMV_OK) throw std::runtime_error(std::string("YoloEngine::reset_tracks: ") + irmv_last_error());
+  }
+
   // ---- plate patches (include/irmv_hip.h, "plate patches") ----
   // From the first set_patches on every detect() also rectifies, per record with armor_valid == 1, the 20 x 28 gray number
   // image between the light bars out of the slot's frame: plate_patches().  The first call re-captures the steps once; later
@@ -702,6 +754,7 @@ private:
   bool pose_alts_on_ = false;         // set_pose_prior has been called: the engine delivers alt records
   bool yaw_on_ = false;               // set_yaw_solve has been called: the engine delivers constrained poses
   bool pose_cov_on_ = false;          // set_pose_cov has been called: the engine delivers pose covariances
+  bool tracking_on_ = false;          // set_tracking has been called: the engine delivers track records
   bool patches_on_ = false;           // set_patches has been called: the engine delivers plate patches
   bool numbers_on_ = false;           // set_numbers(true) has been called: the engine delivers plate numbers
   cv::Size src_image_size_;

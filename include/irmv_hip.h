@@ -712,6 +712,135 @@ int irmv_engine_get_pose_cov(const irmv_engine *e, irmv_pose_cov_opts *opts);   
 /* Parallel to irmv_engine_results, as irmv_engine_pose_alts is.  IRMV_ERR_ARG before the first irmv_engine_set_pose_cov. */
 int irmv_engine_pose_covs(irmv_engine *e, int slot, irmv_pose_cov *out, int cap, int *n);
 
+/* ---- armor tracks: frame-to-frame ids and a constant-velocity filter ---------------------------------------------------
+ * Every record above belongs to one frame.  From the first irmv_engine_set_tracking on, an engine keeps ONE table of
+ * IRMV_TRACK_CAP tracks in device memory and advances it behind every ordinary step, in a kernel of its own (k_track.hip), and a
+ * slot delivers two more records: one irmv_det_track per detection (irmv_engine_det_tracks) and the table as that step left it
+ * (irmv_engine_tracks).  irmv_det and every other record stay byte-identical whether or not it is on.  The arithmetic, fp64 in
+ * the written order (no fused multiply-add; +, -, *, / and comparisons only); irmv_detection_amd/tracks.py states it operation
+ * for operation:
+ *   frame        the slot's stamp t (irmv_engine_set_stamp, seconds), its camera pose in the world (R_wc row-major, t_wc:
+ *                irmv_engine_set_camera_pose) and the n = min(num_dets, max_det) records of the step
+ *   eligible     pnp_ok == 1, armor_valid == 1, tvec finite with z > 0, and a measurement and noise that are finite (noise
+ *                diagonal > 0)
+ *   measurement  z = R_wc tvec + t_wc;  noise R = R_wc C R_wc^T with C the translation block (rows, columns 3 .. 5) of the
+ *                record's irmv_pose_cov where that feature is enabled and its state is 1, else
+ *                C = diag((sigma_lat z)^2, (sigma_lat z)^2, (sigma_rng z^2)^2) with z = tvec.z
+ *   stamps       t not greater than the stamp of the last processed frame (or not finite): the frame is refused ON THE DEVICE --
+ *                frame state -2, the table and its stamp untouched, the frame's detection records all zero
+ *   1 predict    every live track to t: x = [p, v], p += dt v; P = F P F^T + Q, per axis Q = accel_sigma^2 [dt^4/4 dt^3/2; . dt^2]
+ *   2 gate       for every live track and eligible record of the same class (match_class = 0: of any): y = z - p,
+ *                S = P_pp + R, inverted by cofactors, d2 = y^T S^-1 y; kept where det S > 0 and 0 <= d2 <= gate
+ *   3 assign     greedily: the least d2 left; ties to the lower track index, then the lower record index
+ *   4 update     x += K y, P -= K H P with K = P H^T S^-1 (upper triangle, mirrored); hits++, misses = 0, last_hit = t;
+ *                confirmed from confirm_hits hits on
+ *   5 misses     every other live track: misses++; deleted (entry zeroed) when misses > max_misses or t - last_hit > max_coast_s
+ *   6 births     every other eligible record, in index order: a tentative track in the lowest free entry with p = z, v = 0,
+ *                P = blockdiag(R, init_vel_sigma^2 I) and the next id; no free entry: state -1 ("no room")
+ * Ids start at 1 and are never reused in the life of the engine (of the stand-alone tracker).
+ * `det` is a word of the snapshots: the table carries whatever the last launch left in it (a refused frame writes -1 into its
+ * snapshot, and a launch that advances behind it writes that back) and nothing ever reads it from there.
+ * Ordering (rule 7): tracks advance in SUBMIT order, and within a multi-slot submit in slot order, however
+ * the steps' graphs overlap on their streams.  A slot's two track records are those of its last ordinary step and describe the
+ * table as that step left it.  Stamp and camera pose are seen as of the submit.
+ * Fed: every ordinary step (irmv_engine_detect, irmv_engine_submit of one or more slots), in the window and the frame view, of
+ * every point source.  NOT fed: tiled steps, irmv_engine_run_post and the on-demand entries; they leave the table alone, and a
+ * tiled step's and run_post's two channels read as zero for their slots.
+ * Nothing is allocated and nothing new is launched until the first irmv_engine_set_tracking.  That call waits for everything in
+ * flight; it re-captures NOTHING (the launch is no graph node: it follows the step's graph on the step's stream, chained to the
+ * previous track launch by one event).  enable = 0 zeroes both channels and clears the table; the id counter goes on.
+ * Sizes: irmv_track_opts 72, irmv_det_track 72, irmv_track_frame 40, irmv_track 384 bytes. */
+#define IRMV_TRACK_CAP 32
+#define IRMV_TRACK_FREE      0
+#define IRMV_TRACK_TENTATIVE 1
+#define IRMV_TRACK_CONFIRMED 2
+typedef struct irmv_track_opts {
+    uint32_t struct_size;        /* = sizeof(irmv_track_opts) */
+    int32_t  enable;             /* 0 | 1 */
+    int32_t  confirm_hits;       /* 1 .. 2^20; default 3 */
+    int32_t  max_misses;         /* 1 .. 2^20; default 5 */
+    int32_t  match_class;        /* 0 | 1; default 1 */
+    int32_t  reserved;           /* 0 */
+    double   gate;               /* default 16.27: the 0.999 quantile of chi-square with three degrees of freedom */
+    double   max_coast_s;        /* default 0.5 */
+    double   accel_sigma;        /* m/s^2; default 8 */
+    double   init_vel_sigma;     /* m/s; default 3 */
+    double   sigma_lat;          /* default 0.002 */
+    double   sigma_rng;          /* default 0.01 */
+} irmv_track_opts;               /* 72 bytes; every double finite and > 0 */
+typedef struct irmv_det_track {
+    int32_t  state;              /* 0: not eligible (all zero); 1: matched; 2: started a track; -1: no room */
+    int32_t  track;              /* table index; -1: no room */
+    uint32_t id;
+    int32_t  hits;
+    double   d2;                 /* matched: the gated distance */
+    double   pos[3], vel[3];     /* filtered, world frame */
+} irmv_det_track;                /* 72 bytes */
+typedef struct irmv_track_frame {
+    double   stamp;              /* the frame's stamp */
+    int32_t  state;              /* 1: processed; -2: stamp refused; 0: tracking off / no ordinary step yet */
+    int32_t  n_live, n_confirmed, n_started, n_deleted, n_no_room;
+    uint32_t next_id;
+    int32_t  reserved;
+} irmv_track_frame;              /* 40 bytes */
+typedef struct irmv_track {
+    uint32_t id;                 /* from 1; 0: free entry (all zero but det) */
+    int32_t  class_id;
+    int32_t  state;              /* IRMV_TRACK_* */
+    int32_t  hits, misses;
+    int32_t  det;                /* snapshots: the frame's record matched to (or starting) the track; -1: none */
+    double   first_stamp, last_hit, stamp;   /* stamp: the time x and P are valid at */
+    double   x[6];               /* p, v in the world frame */
+    double   P[36];              /* row-major, exactly symmetric */
+} irmv_track;                    /* 384 bytes */
+/* IRMV_ERR_ARG before the GPU is touched, leaving everything as it was (the values first): null opts, a wrong struct_size,
+ * enable or match_class outside {0, 1}, confirm_hits or max_misses outside 1 .. 2^20, reserved != 0, a double that is not
+ * finite and positive; then a null engine. */
+int irmv_engine_set_tracking(irmv_engine *e, const irmv_track_opts *opts);
+/* Host only: the defaults above with struct_size filled in and enable = 0 -- the one place the values are written down for
+ * the facades. */
+int irmv_track_default_opts(irmv_track_opts *opts);
+int irmv_engine_get_tracking(const irmv_engine *e, irmv_track_opts *opts);   /* before the first set: the defaults with enable = 0 */
+/* The slot's stamp (default 0) and camera pose (default identity, zero): live per-slot state as irmv_engine_set_up is -- the
+ * call waits for the slot's last step, then writes the slot's entry of a device table; works before the first
+ * irmv_engine_set_tracking.  IRMV_ERR_ARG: a slot out of range, a value that is not finite. */
+int irmv_engine_set_stamp(irmv_engine *e, int slot, double t);
+int irmv_engine_get_stamp(const irmv_engine *e, int slot, double *t);
+int irmv_engine_set_camera_pose(irmv_engine *e, int slot, const double R_wc[9], const double t_wc[3]);
+int irmv_engine_get_camera_pose(const irmv_engine *e, int slot, double R_wc[9], double t_wc[3]);
+/* Parallel to irmv_engine_results, as irmv_engine_pose_covs is.  IRMV_ERR_ARG before the first irmv_engine_set_tracking. */
+int irmv_engine_det_tracks(irmv_engine *e, int slot, irmv_det_track *out, int cap, int *n);
+/* The slot's frame header and the first min(cap, IRMV_TRACK_CAP) entries of its snapshot (free entries included); *n = that
+ * number.  frame or out may be NULL (out with cap = 0).  IRMV_ERR_ARG before the first irmv_engine_set_tracking. */
+int irmv_engine_tracks(irmv_engine *e, int slot, irmv_track_frame *frame, irmv_track *out, int cap, int *n);
+/* Waits for everything in flight, then clears the table and its stamp; the id counter goes on, the slots' records stay. */
+int irmv_engine_reset_tracks(irmv_engine *e);
+/* out[0] = IRMV_TRACK_CAP, [1] = sizeof(irmv_track), [2] = sizeof(irmv_det_track), [3] = sizeof(irmv_track_frame),
+ * [4] = sizeof(irmv_track_opts), [5] = the most observations of one irmv_tracker_update, [6], [7] = 0 */
+int irmv_track_limits(int32_t out[8]);
+/* Host only, the bits of tracks.py predict_position: a live track's position and its 3 x 3 covariance (row-major) at stamp
+ * t >= track->stamp under white acceleration accel_sigma (the filter's own prediction step).  IRMV_ERR_ARG: a null argument, a
+ * free track, t before the track's stamp or not finite, accel_sigma not finite and positive. */
+int irmv_track_predict(const irmv_track *track, double t, double accel_sigma, double pos[3], double cov[9]);
+
+/* The same tracker stand-alone on explicit observations, as irmv_pnp offers the pose kernels: one table per object. */
+typedef struct irmv_tracker irmv_tracker;
+typedef struct irmv_track_obs {
+    int32_t class_id;
+    int32_t valid;               /* 1: what pnp_ok == 1 and armor_valid == 1 say of a record */
+    int32_t has_cov;             /* 1: cov is the noise C in the camera frame; 0: the default from sigma_lat / sigma_rng */
+    int32_t reserved;
+    double  tvec[3];
+    double  cov[9];              /* row-major 3 x 3 */
+} irmv_track_obs;                /* 112 bytes */
+int irmv_tracker_create(int device, const irmv_track_opts *opts, irmv_tracker **out);   /* opts NULL: the defaults, enabled */
+void irmv_tracker_destroy(irmv_tracker *tr);
+/* One frame of n <= 256 observations at stamp t under the camera pose (NULL: identity / zero): det_out [n], *frame, tracks_out
+ * [IRMV_TRACK_CAP]; each may be NULL.  A refused stamp is a result (frame->state == -2), not an error. */
+int irmv_tracker_update(irmv_tracker *tr, double t, const double R_wc[9], const double t_wc[3], const irmv_track_obs *obs, int n,
+                        irmv_det_track *det_out, irmv_track_frame *frame, irmv_track *tracks_out);
+int irmv_tracker_reset(irmv_tracker *tr);   /* the table and its stamp; the id counter goes on */
+
 /* ---- plate patches: each armor's rectified number image ---------------------------------------------------------------
  * A consumer of such a detector cuts the number plate out of the frame between the two light bars, rectifies it with the
  * four points and hands the small gray image to a number classifier.  From the first irmv_engine_set_patches on, a step does

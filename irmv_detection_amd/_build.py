@@ -39,6 +39,7 @@ SOURCES = [
     ("k_posecov.hip", ["-ffp-contract=off"]),   # the pose uncertainty: a module of its own, fp64 in the written order (its header)
     ("k_patch.hip", ["-ffp-contract=off"]),   # plate patches: a module of its own, fp64 in the written order (its header)
     ("k_number.hip", ["-ffp-contract=off"]),   # plate numbers: a module of its own, fp32 in the written order (its header)
+    ("k_track.hip", ["-ffp-contract=off"]),   # armor tracks: a module of its own, fp64 in the written order (its header)
     ("k_debug.hip", []),
     ("engine.cpp", ["-x", "hip"]),
     ("engine_graph.cpp", ["-x", "hip"]),
@@ -52,6 +53,7 @@ SOURCES = [
     ("engine_posecov.cpp", ["-x", "hip", "-ffp-contract=off"]),
     ("engine_patch.cpp", ["-x", "hip", "-ffp-contract=off"]),
     ("engine_number.cpp", ["-x", "hip", "-ffp-contract=off"]),
+    ("engine_track.cpp", ["-x", "hip", "-ffp-contract=off"]),
 ]
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs.  Left to itself the compiler gives kernels without a waves_per_eu
 # bound (fused C2f blocks, direct convs) AGPR accumulators and copies every one of them out with a v_accvgpr_read before the
@@ -66,7 +68,7 @@ def source_hash() -> str:
     their numbers when it differs from the tree it runs in -- a hash of the BINARY would not survive a rebuild elsewhere."""
     import hashlib
     h = hashlib.sha256()
-    names = sorted(set([s for s, _ in SOURCES] + ["irmv_common.hpp", "pnp_device.hpp", "numa.hpp", "engine_internal.hpp"]))
+    names = sorted(set([s for s, _ in SOURCES] + ["irmv_common.hpp", "pnp_device.hpp", "numa.hpp", "engine_internal.hpp", "track_math.hpp"]))
     for n in names:
         pth = os.path.join(CSRC, n)
         if os.path.exists(pth):
@@ -113,7 +115,7 @@ def build_comm(force: bool = False, verbose: bool = False) -> str:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(LIB_DIR, exist_ok=True)
-    headers = [os.path.join(CSRC, "irmv_common.hpp"), os.path.join(CSRC, "pnp_device.hpp"), os.path.join(CSRC, "numa.hpp"), os.path.join(CSRC, "engine_internal.hpp"), os.path.join(INCLUDE, "irmv_hip.h"), __file__]
+    headers = [os.path.join(CSRC, "irmv_common.hpp"), os.path.join(CSRC, "pnp_device.hpp"), os.path.join(CSRC, "numa.hpp"), os.path.join(CSRC, "engine_internal.hpp"), os.path.join(CSRC, "track_math.hpp"), os.path.join(INCLUDE, "irmv_hip.h"), __file__]
     objs = []
     cc = hipcc()
     for src, extra in SOURCES:

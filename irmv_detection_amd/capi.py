@@ -216,6 +216,54 @@ class PoseCov(C.Structure):
                 ("state", C.c_int32), ("yaw_state", C.c_int32)]
 
 
+class TrackOpts(C.Structure):
+    """irmv_track_opts (include/irmv_hip.h, "armor tracks")."""
+    _fields_ = [("struct_size", C.c_uint32), ("enable", C.c_int32), ("confirm_hits", C.c_int32), ("max_misses", C.c_int32),
+                ("match_class", C.c_int32), ("reserved", C.c_int32), ("gate", C.c_double), ("max_coast_s", C.c_double),
+                ("accel_sigma", C.c_double), ("init_vel_sigma", C.c_double), ("sigma_lat", C.c_double), ("sigma_rng", C.c_double)]
+
+
+class DetTrack(C.Structure):
+    """irmv_det_track: what the tracker made of one detection."""
+    _fields_ = [("state", C.c_int32), ("track", C.c_int32), ("id", C.c_uint32), ("hits", C.c_int32), ("d2", C.c_double),
+                ("pos", C.c_double * 3), ("vel", C.c_double * 3)]
+
+
+class TrackFrame(C.Structure):
+    """irmv_track_frame: the header of a slot's track snapshot."""
+    _fields_ = [("stamp", C.c_double), ("state", C.c_int32), ("n_live", C.c_int32), ("n_confirmed", C.c_int32), ("n_started", C.c_int32),
+                ("n_deleted", C.c_int32), ("n_no_room", C.c_int32), ("next_id", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class Track(C.Structure):
+    """irmv_track: one entry of the track table."""
+    _fields_ = [("id", C.c_uint32), ("class_id", C.c_int32), ("state", C.c_int32), ("hits", C.c_int32), ("misses", C.c_int32),
+                ("det", C.c_int32), ("first_stamp", C.c_double), ("last_hit", C.c_double), ("stamp", C.c_double),
+                ("x", C.c_double * 6), ("P", C.c_double * 36)]
+
+
+class TrackObs(C.Structure):
+    """irmv_track_obs: one observation of the stand-alone tracker."""
+    _fields_ = [("class_id", C.c_int32), ("valid", C.c_int32), ("has_cov", C.c_int32), ("reserved", C.c_int32),
+                ("tvec", C.c_double * 3), ("cov", C.c_double * 9)]
+
+
+TRACK_CAP = 32
+
+
+def track_opts_struct(enable=1, **fields) -> TrackOpts:
+    """An irmv_track_opts: the library's defaults (irmv_track_default_opts), then `fields` (no check: the library's are the
+    ones under test)."""
+    o = TrackOpts()
+    check(load().irmv_track_default_opts(C.byref(o)))
+    o.enable = int(enable)
+    for name, v in fields.items():
+        if name not in dict(TrackOpts._fields_) or name in ("struct_size", "reserved"):
+            raise TypeError(f"irmv_track_opts has no option {name!r}")
+        setattr(o, name, v)
+    return o
+
+
 def pose_cov_opts_struct(enable=1, sigma_px=1.0) -> PoseCovOpts:
     """An irmv_pose_cov_opts (no check: the library's are the ones under test)."""
     o = PoseCovOpts()
@@ -435,6 +483,23 @@ SYMBOLS = [
     ("irmv_engine_plate_numbers", C.c_int, [_P, C.c_int, C.POINTER(PlateNumber), C.c_int, C.POINTER(C.c_int)]),
     ("irmv_engine_numbers_at", C.c_int, [_P, C.POINTER(PlatePatch), C.c_int, C.POINTER(PlateNumber)]),
     ("irmv_number_limits", C.c_int, [C.POINTER(C.c_int32)]),
+    ("irmv_engine_set_tracking", C.c_int, [_P, C.POINTER(TrackOpts)]),
+    ("irmv_engine_get_tracking", C.c_int, [_P, C.POINTER(TrackOpts)]),
+    ("irmv_track_default_opts", C.c_int, [C.POINTER(TrackOpts)]),
+    ("irmv_engine_set_stamp", C.c_int, [_P, C.c_int, C.c_double]),
+    ("irmv_engine_get_stamp", C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
+    ("irmv_engine_set_camera_pose", C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("irmv_engine_get_camera_pose", C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("irmv_engine_det_tracks", C.c_int, [_P, C.c_int, C.POINTER(DetTrack), C.c_int, C.POINTER(C.c_int)]),
+    ("irmv_engine_tracks", C.c_int, [_P, C.c_int, C.POINTER(TrackFrame), C.POINTER(Track), C.c_int, C.POINTER(C.c_int)]),
+    ("irmv_engine_reset_tracks", C.c_int, [_P]),
+    ("irmv_track_limits", C.c_int, [C.POINTER(C.c_int32)]),
+    ("irmv_track_predict", C.c_int, [C.POINTER(Track), C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("irmv_tracker_create", C.c_int, [C.c_int, C.POINTER(TrackOpts), C.POINTER(C.c_void_p)]),
+    ("irmv_tracker_destroy", None, [_P]),
+    ("irmv_tracker_update", C.c_int, [_P, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(TrackObs), C.c_int,
+                                      C.POINTER(DetTrack), C.POINTER(TrackFrame), C.POINTER(Track)]),
+    ("irmv_tracker_reset", C.c_int, [_P]),
     ("irmv_number_softmax", C.c_int, [C.POINTER(PlateNumber), C.c_int, C.POINTER(C.c_float)]),
     ("irmv_meter_map", C.c_int, [C.POINTER(EngineCfg), C.POINTER(MeterOpts), C.c_int, C.c_int, C.c_int, C.POINTER(MeterMap)]),
     ("irmv_meter_limits", C.c_int, [C.POINTER(C.c_int32)]),

@@ -95,10 +95,11 @@ irmv_engine::~irmv_engine()
     for (const DevRange &r : dev_allocs) (void)hipFree(r.base);
     dev_allocs.clear();
     if (src_host) (void)hipHostFree(src_host);
-    dets.free_host(); fout.free_host(); alts.free_host(); yaw.free_host(); posecov.free_host(); patch.free_host(); number.free_host(); meter.free_host();   // the record channels
+    dets.free_host(); fout.free_host(); alts.free_host(); yaw.free_host(); posecov.free_host(); dettrack.free_host(); tracks.free_host(); patch.free_host(); number.free_host(); meter.free_host();   // the record channels
     if (light_dets_host) (void)hipHostFree(light_dets_host);
     for (auto &kv : tile_merges)
         if (kv.second.out_host) (void)hipHostFree(kv.second.out_host);
+    if (track_event) (void)hipEventDestroy(track_event);
     for (auto &kv : groups) {
         if (kv.second.h2d) (void)hipEventDestroy(kv.second.h2d);
         if (kv.second.out) (void)hipEventDestroy(kv.second.out);
@@ -467,6 +468,12 @@ extern "C" int irmv_engine_create(const irmv_engine_cfg *cfg_in, irmv_engine **o
     yaw_opts_defaults(&e->yaw_opts);
     pose_cov_opts_defaults(&e->posecov_opts);
     patch_opts_defaults(&e->patch_opts);
+    track_opts_defaults(&e->track_opts);
+    {
+        TrackSlot ts{};   // stamp 0, camera pose identity
+        ts.R[0] = ts.R[4] = ts.R[8] = 1.0;
+        e->track_slots.assign((size_t)cfg->num_slots, ts);
+    }
     e->up.assign((size_t)cfg->num_slots * 3, 0.0);
     for (int s = 0; s < cfg->num_slots; s++) e->up[3 * s + 1] = -1.0;   // a level camera: image y points down
     int rc = load_blob(e.get());

@@ -15,6 +15,7 @@
 //   engine_meter.cpp  frame metering: its checks and map, the record's host helpers, the on-demand call, the step's launch
 //   engine_yaw.cpp    constrained pose: its checks, the two tables and who rewrites them, the step's launch, the stand-alone call
 //   engine_posecov.cpp pose uncertainty: its checks, the option table, the step's launch, the stand-alone call
+//   engine_track.cpp  armor tracks: the checks, the switch, stamps and camera poses, the launch behind a step, the stand-alone tracker
 //   engine_patch.cpp  plate patches: their checks, the option table, the step's launch, the on-demand call
 //   engine_number.cpp plate numbers: the model's checks, its .irmn file and upload, the switch, the step's launch, the on-demand call
 #pragma once
@@ -447,6 +448,8 @@ struct irmv_engine {
     Records<DevPoseCov> posecov;
     Records<DevPatch> patch;
     Records<DevNumber> number;
+    Records<DevDetTrack> dettrack;
+    Records<DevTrackSnap> tracks;
     bool zero_copy_results = false;   // the NMS kernel writes its results straight into pinned host memory (no D2H copy)
     half_t *conv0_w = nullptr;
     float *conv0_b = nullptr;
@@ -498,6 +501,18 @@ struct irmv_engine {
     float *number_bias = nullptr;             // [kNumBiasFloats]
     DevPatch *number_at_in = nullptr;         // [kMaxDetCap]
     DevNumber *number_at_out = nullptr;       // [kMaxDetCap]
+    // Armor tracks (irmv_engine_set_tracking).  Nothing below but track_opts and track_slots (host values) exists until the first
+    // set_tracking: the two channels (`dettrack`, `tracks` above), the carried table, the option table, the per-slot stamps and
+    // camera poses, the event.  There is no op and no graph node: track_step launches behind an ordinary step on the step's
+    // stream and chains the launches of different streams by track_event, in submit order.
+    bool track_made = false;
+    irmv_track_opts track_opts{};
+    std::vector<TrackSlot> track_slots;       // [S] stamp and camera pose as set (0, identity, 0)
+    DevTrackTable *track_table_dev = nullptr;
+    TrackOpts *track_opts_dev = nullptr;
+    TrackSlot *track_slots_dev = nullptr;     // [S]
+    hipEvent_t track_event = nullptr;         // recorded behind the last track launch ...
+    hipStream_t track_event_stream = nullptr; // ... on this stream (nullptr: none since the last irmv_engine_wait of set_tracking)
 
     ~irmv_engine();
 };
@@ -584,6 +599,10 @@ void launch_yaw(const irmv_engine *e, const Step &s, const PostArgs &pa, hipStre
 // engine_posecov.cpp
 void pose_cov_opts_defaults(irmv_pose_cov_opts *o);
 void launch_posecov(const irmv_engine *e, const Step &s, const PostArgs &pa, hipStream_t st);
+// engine_track.cpp
+void track_opts_defaults(irmv_track_opts *o);
+int track_step(irmv_engine *e, const Step &s, hipStream_t st);                 // behind an ordinary step: the table advances over its slots
+int track_skip(irmv_engine *e, int first, int count, hipStream_t st, bool copied);   // a step that does not feed the tracker: its slots' channels read as zero
 // engine_patch.cpp
 void patch_opts_defaults(irmv_patch_opts *o);
 void launch_patch(const irmv_engine *e, const View &v, const Step &s, const PostArgs &pa, hipStream_t st);

@@ -588,6 +588,8 @@ template struct Records<DevYaw>;
 template struct Records<DevPoseCov>;
 template struct Records<DevPatch>;
 template struct Records<DevNumber>;
+template struct Records<DevDetTrack>;
+template struct Records<DevTrackSnap>;
 
 // the device records of slots [first, first + count) -> their pinned twins (every step of an engine without zero-copy results;
 // tiled steps of any engine -- which do not meter: stats = false)
@@ -603,6 +605,11 @@ static int copy_out_dev(irmv_engine *e, int first, int count, hipStream_t st, bo
     // (disabled: the kernel returns at once and set_patches has zeroed both copies -- max_det records of 592 bytes stay where they are)
     if (e->patch_op >= 0 && e->patch_opts.enable) TRY(e->patch.copy(first, count, d2h, st));
     if (e->number_op >= 0 && e->number_opts.enable) TRY(e->number.copy(first, count, d2h, st));   // (disabled: as the patches)
+    // (disabled: nothing is launched and set_tracking has zeroed both copies)
+    if (e->track_made && e->track_opts.enable) {
+        TRY(e->dettrack.copy(first, count, d2h, st));
+        TRY(e->tracks.copy(first, count, d2h, st));
+    }
     return IRMV_OK;
 }
 
@@ -718,6 +725,9 @@ int irmv::submit_group(irmv_engine *e, int f, int c, uint32_t flags, hipStream_t
     if (eager) TRY(enqueue_step(e, step, st));
     else HIP_TRY(hipGraphLaunch(ge, st));
     mark_stepped(e, f, c);
+    // the track table advances behind the step, in submit order (rule 7); a tiled step does not feed it
+    if (tiled) TRY(track_skip(e, f, c, st, true));   // (copy_out_dev below carries the zeros)
+    else TRY(track_step(e, step, st));
     if (tiled) {
         const irmv_engine::TileMerge &tm = e->tile_merges.at(f);
         TRY(copy_out_dev(e, f, c, st, false));
@@ -767,6 +777,7 @@ extern "C" int irmv_engine_run_post(irmv_engine *e, int first, int count)
     hipGraphExec_t ge;
     TRY(get_graph(e, Step{STEP_POST, first, count}, Upload{}, &ge));
     HIP_TRY(hipGraphLaunch(ge, e->stream));
+    TRY(track_skip(e, first, count, e->stream, !e->zero_copy_results));   // (run_post does not feed the tracker; copy_out below copies iff the results are not zero-copy)
     TRY(copy_out(e, first, count));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return IRMV_OK;

@@ -775,6 +775,47 @@ void launch_pose_cov(const PoseCovArgs &a, int batch, hipStream_t s);
 void launch_pose_cov_points(const PnpConst &c, const float *pts, const double *poses, int n, int armor_size, const PoseCovRule &rule,
                             DevPoseCov *out, hipStream_t s);
 
+// ---- armor tracks (k_track.hip; irmv_engine_set_tracking, irmv_tracker) ----------------------------------------------------
+// DevDetTrack, DevTrackFrame, DevTrack and TrackObs have the layouts of irmv_det_track, irmv_track_frame, irmv_track and
+// irmv_track_obs.  DevTrackTable is the state that outlives a step: one per engine (per stand-alone tracker), read and written
+// by track_kernel alone, cleared by the host between steps only.  DevTrackSnap is a slot's record: the header and the table as
+// the slot's step left it.  TrackOpts and TrackSlot live in device memory at fixed addresses; the host writes them, the kernel
+// reads them when it runs.
+constexpr int kTrackCap = 32, kTrackThreads = 256;
+constexpr int kTrackClasses = 14;   // IRMV_NUM_CLASSES: a record's class as irmv_det reports it (slot_det)
+struct DevDetTrack { int32_t state, track; uint32_t id; int32_t hits; double d2, pos[3], vel[3]; };
+struct DevTrackFrame { double stamp; int32_t state, n_live, n_confirmed, n_started, n_deleted, n_no_room; uint32_t next_id; int32_t pad_; };
+struct DevTrack {
+    uint32_t id;
+    int32_t cls, state, hits, misses, det;
+    double first, last_hit, stamp;
+    double x[6], P[36];
+};
+struct DevTrackTable { double stamp; int32_t stamped; uint32_t next_id; DevTrack tracks[kTrackCap]; };
+struct DevTrackSnap { DevTrackFrame frame; DevTrack tracks[kTrackCap]; };
+struct TrackObs { int32_t cls, valid, has_cov, pad_; double tvec[3], cov[9]; };
+struct TrackOpts { int32_t enable, confirm_hits, max_misses, match_class; double gate, max_coast_s, accel_sigma, init_vel_sigma, sigma_lat, sigma_rng; };
+struct TrackSlot { double stamp, R[9], t[3]; };
+struct TrackArgs {
+    DevTrackTable *table;
+    const TrackOpts *opts;
+    const TrackSlot *slots;   // frame b's stamp and camera pose: slots[first + b]
+    int first;
+    // the engine's form: frame b's records are dets[b * max_det + i], i < min(num_dets[b * num_dets_stride], max_det) ...
+    const DevDet *dets;
+    int max_det;
+    const int *num_dets;
+    int num_dets_stride;
+    const DevPoseCov *cov;    // ... with their covariances where the step computed them ([B][max_det]); nullptr: the default noise
+    // the stand-alone form (dets == nullptr): n_obs <= kMaxDetCap observations of the one frame
+    const TrackObs *obs;
+    int n_obs;
+    DevDetTrack *out_det;     // [B][max_det]: the frame's [0, n) records are written
+    DevTrackSnap *out_snap;   // [B]
+};
+// `batch` frames, one after the other in index order, by ONE workgroup
+void launch_track_update(const TrackArgs &a, int batch, hipStream_t s);
+
 // ---- plate patches (k_patch.hip; irmv_engine_set_patches) ---------------------------------------------------------------
 // DevPatch is the side record of one detection (the layout of irmv_plate_patch).  PatchTable lives in device memory at an
 // address fixed from the first set_patches (or patches_at) on; the host writes it, the kernel reads it when it runs.

@@ -495,6 +495,54 @@ class YoloEngine:
         """capi.PoseCov records (copies) parallel to results(slot) / results_raw(slot)."""
         return self._side_records(self._L.irmv_engine_pose_covs, capi.PoseCov, slot)
 
+    # ---- armor tracks (include/irmv_hip.h; host reference: tracks.py) ----
+    def set_tracking(self, enable: bool = True, **opts) -> None:
+        """irmv_engine_set_tracking: from the first call on every ordinary step also advances the engine's track table over
+        its detections, in submit order, and delivers det_tracks / tracks per slot.  opts: the fields of
+        capi.track_opts_struct.  Re-captures nothing.  A refused value raises and changes nothing."""
+        o = capi.track_opts_struct(1 if enable else 0, **opts)
+        capi.check(self._L.irmv_engine_set_tracking(self._h, C.byref(o)))
+
+    def tracking(self) -> dict:
+        o = capi.TrackOpts()
+        capi.check(self._L.irmv_engine_get_tracking(self._h, C.byref(o)))
+        return {name: getattr(o, name) for name, _ in capi.TrackOpts._fields_ if name not in ("struct_size", "reserved")}
+
+    def set_stamp(self, t: float, slot: int = 0) -> None:
+        """The stamp (seconds) of the slot's next frames, live as set_up is."""
+        capi.check(self._L.irmv_engine_set_stamp(self._h, slot, float(t)))
+
+    def stamp(self, slot: int = 0) -> float:
+        t = C.c_double(0.0)
+        capi.check(self._L.irmv_engine_get_stamp(self._h, slot, C.byref(t)))
+        return t.value
+
+    def set_camera_pose(self, R_wc, t_wc, slot: int = 0) -> None:
+        """The slot's camera pose in the world (R_wc row-major 3 x 3, t_wc), live as set_up is."""
+        R = np.ascontiguousarray(R_wc, np.float64).reshape(9)
+        t = np.ascontiguousarray(t_wc, np.float64).reshape(3)
+        capi.check(self._L.irmv_engine_set_camera_pose(self._h, slot, R.ctypes.data_as(C.POINTER(C.c_double)), t.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def camera_pose(self, slot: int = 0):
+        R, t = np.zeros(9), np.zeros(3)
+        capi.check(self._L.irmv_engine_get_camera_pose(self._h, slot, R.ctypes.data_as(C.POINTER(C.c_double)), t.ctypes.data_as(C.POINTER(C.c_double))))
+        return R.reshape(3, 3), t
+
+    def det_tracks(self, slot: int = 0):
+        """capi.DetTrack records (copies) parallel to results(slot) / results_raw(slot)."""
+        return self._side_records(self._L.irmv_engine_det_tracks, capi.DetTrack, slot)
+
+    def tracks(self, slot: int = 0):
+        """(capi.TrackFrame, [capi.Track] * 32): the table as the slot's last ordinary step left it, free entries included."""
+        n = C.c_int(0)
+        frame = capi.TrackFrame()
+        out = (capi.Track * capi.TRACK_CAP)()
+        capi.check(self._L.irmv_engine_tracks(self._h, slot, C.byref(frame), out, capi.TRACK_CAP, C.byref(n)))
+        return frame, [out[i] for i in range(n.value)]
+
+    def reset_tracks(self) -> None:
+        capi.check(self._L.irmv_engine_reset_tracks(self._h))
+
     # ---- plate patches (include/irmv_hip.h; host reference: patches.py) ----
     def set_patches(self, enable: bool = True, span=(32, 54), light_rows: int = 12, top: int = 7) -> None:
         """irmv_engine_set_patches: from the first call on every step also rectifies, per record with armor_valid == 1, the
@@ -909,6 +957,59 @@ class YoloEngine:
                   rvec=np.array(d.rvec), tvec=np.array(d.tvec), quat_xyzw=np.array(d.quat))
         a.center = ((k[0] + k[2] + k[4] + k[6]) / 4.0, (k[1] + k[3] + k[5] + k[7]) / 4.0)
         return a
+
+
+class Tracker:
+    """The armor tracker stand-alone on explicit observations (irmv_tracker_*; host reference: tracks.py)."""
+
+    def __init__(self, *, device: int = 0, **opts):
+        self._L = capi.load()
+        self._h = C.c_void_p()
+        o = capi.track_opts_struct(1, **opts)
+        capi.check(self._L.irmv_tracker_create(device, C.byref(o), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.irmv_tracker_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def update(self, t: float, obs, R_wc=None, t_wc=None):
+        """One frame of observations -- capi.TrackObs, or (class_id, tvec[3], valid, cov[9] | None) tuples -- at stamp t ->
+        ([capi.DetTrack] * n, capi.TrackFrame, [capi.Track] * 32)."""
+        n = len(obs)
+        arr = (capi.TrackObs * max(n, 1))()
+        for i, o in enumerate(obs):
+            if isinstance(o, capi.TrackObs):
+                arr[i] = o
+                continue
+            cls, tvec, valid, cov = o
+            arr[i].class_id, arr[i].valid, arr[i].has_cov = int(cls), int(valid), 0 if cov is None else 1
+            arr[i].tvec[:] = [float(v) for v in tvec]
+            if cov is not None:
+                arr[i].cov[:] = [float(v) for v in np.asarray(cov, np.float64).reshape(9)]
+        R = None if R_wc is None else np.ascontiguousarray(R_wc, np.float64).reshape(9)
+        tw = None if t_wc is None else np.ascontiguousarray(t_wc, np.float64).reshape(3)
+        dets = (capi.DetTrack * max(n, 1))()
+        frame = capi.TrackFrame()
+        tracks = (capi.Track * capi.TRACK_CAP)()
+        capi.check(self._L.irmv_tracker_update(self._h, float(t), None if R is None else R.ctypes.data_as(C.POINTER(C.c_double)),
+                                               None if tw is None else tw.ctypes.data_as(C.POINTER(C.c_double)), arr, n, dets,
+                                               C.byref(frame), tracks))
+        return [dets[i] for i in range(n)], frame, list(tracks)
+
+    def reset(self) -> None:
+        capi.check(self._L.irmv_tracker_reset(self._h))
+
+
+def track_predict(track, t: float, accel_sigma: float):
+    """irmv_track_predict: (pos[3], cov[3][3]) of a capi.Track at stamp t."""
+    pos, cov = np.zeros(3), np.zeros(9)
+    capi.check(capi.load().irmv_track_predict(C.byref(track), float(t), float(accel_sigma), pos.ctypes.data_as(C.POINTER(C.c_double)),
+                                              cov.ctypes.data_as(C.POINTER(C.c_double))))
+    return pos, cov.reshape(3, 3)
 
 
 class PnPSolver:

@@ -57,6 +57,9 @@ public:
     // geometry_msgs/PoseWithCovariance)
     p.pose_cov = node_->declare_parameter("pose_cov", false);
     p.sigma_px = node_->declare_parameter("sigma_px", 1.0);
+    // armor tracks (IrmDetectorCore::Params::tracking): frame-to-frame ids and a velocity filter over the published armors
+    // (FrameResult::det_tracks / tracks; not published: auto_aim_interfaces has no field for them)
+    if (node_->declare_parameter("tracking", false)) p.tracking = ArmorTracker::default_opts();
     // plate patches (IrmDetectorCore::Params::patches): each armor's rectified number image beside its pose (FrameResult::patches;
     // not published)
     if (node_->declare_parameter("patches", false)) p.patches = YoloEngine::patch_opts();
