@@ -21,6 +21,25 @@ records wherever the window lies and were left out):
             mask enemy(0) (R1 .. RS off) | plates alternating SMALL / LARGE by class
   corners   (0, 0), the far corner, (31, 40 | 41), (5, 37)
 test_palettes_move_the_results asserts on R alone that every policy and every corner changes an observed result.
+
+Families T and D (rule 7 and the newer side records): T is W's engine on 3 streams with pose prior, metering, yaw solve, pose
+covariance, patches, the seeded number model of tests/test_gpu_numbers.py and the tracker on, W's frames; D is C's engine and
+cuts with yaw solve, covariance, patches and the tracker on (device records copied out).  A read also returns yaw_poses,
+pose_covs, plate_patches, plate_numbers (bit for bit against R at the attribution) and the three track records: det_tracks, the
+frame header and the 32-entry snapshot, bit for bit against irmv_detection_amd/tracks.py, which replays the model's fed log
+(step_programs.Replay) on the observations R's step of each attributed (frame, state) reports (test_gpu_tracks.step_obs).  The
+engine under test never supplies an expectation.
+  palettes  sigma_px off | 0.7 | 1.5;  yaw rounds 4, tau_max 1 | rounds 2, tau_max 0.5;  patch spans 32, 54, 12 light rows |
+            30, 50, 10 light rows;  numbers off | on;  tracking off | max_misses 1, match_class 1 | max_misses 2, match_class 0,
+            confirm_hits 2;  camera poses identity and the translations (2, 0, 0) mm and (0, -1, 3) mm;  stamps 1 s + 10 ms a
+            clock tick.
+  measured  on the GPU, on R's and the host reference's answers: every T program has 22 .. 59 observations with a
+            DET_MATCHED record, 18 .. 50 with a DET_STARTED one, 5 .. 8 refused, 7 .. 23 zero, 26 .. 59 distinct byte triples and
+            49 .. 395 deletions over its log; over T's eight programs 5 524 matches with 0 < d2 < gate (the millimetre
+            translations, and W's frames re-seen at another corner) and 448 fed frames with n_no_room >= 1 (100 records, of
+            which more are solved than the table's 32 entries hold).  D: 14 .. 24 observations with a match per program,
+            110 .. 216 matches with 0 < d2 < gate, never a full table (one armor a cut).  So 10 ms a tick keeps every re-seen
+            armor inside the gate and max_misses of 1 and 2 delete within a phrase; no palette value had to be changed.
 """
 import ctypes as C
 import time
@@ -31,14 +50,33 @@ import pytest
 import detect_craft as dc
 import step_programs as sp
 from irmv_detection_amd import bayer, capi, tiles, weights
+from irmv_detection_amd import tracks as T
 from irmv_detection_amd import class_policy as cp
 from irmv_detection_amd.engine import YoloEngine
 from conftest import golden_path
+from test_gpu_numbers import model as number_model
+from test_gpu_tracks import step_obs
 from test_gpu_window import K, frame_of, same_results, snapshot, wblob, weng  # noqa: F401  (wblob: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
-FRAME_SEEDS = {"W": (10, 11, 14, 16, 21, 41), "B": (12, 13, 15, 16, 20, 21), "P": (70, 71, 72, 73, 74, 75)}
+FRAME_SEEDS = {"W": (10, 11, 14, 16, 21, 41), "B": (12, 13, 15, 16, 20, 21), "P": (70, 71, 72, 73, 74, 75), "T": (10, 11, 14, 16, 21, 41)}
+# the palettes of the newer setters (families T and D); index 0 of COVS and TRACKING is "off"
+COVS = [None, 0.7, 1.5]                                                           # sigma_px
+YAWS = [dict(rounds=4, tau_max=1.0), dict(rounds=2, tau_max=0.5)]
+PATCHES = [dict(span=(32, 54), light_rows=12, top=7), dict(span=(30, 50), light_rows=10, top=7)]
+TRACKING = [None, dict(max_misses=1, match_class=1), dict(max_misses=2, match_class=0, confirm_hits=2)]
+TRACK_OPTIONS = [None] + [T.Options(**o) for o in TRACKING[1:]]
+POSES = [(T.IDENTITY, t) for t in ((0.0, 0.0, 0.0), (0.002, 0.0, 0.0), (0.0, -0.001, 0.003))]     # camera poses: translations, metres
+STAMP0, TICK = 1.0, 0.01                                                          # the clock: seconds at tick 0, seconds a tick
+
+
+def stamp_of(k):
+    """Seconds of clock tick k (a refused_feeds model's half ticks too); a slot whose stamp was never set carries 0."""
+    return 0.0 if k < 0 else STAMP0 + TICK * k
+
+
+TRACKED = "TD"
 # family C: 322 x 201 cuts of tests/golden/rm_test.jpg, each with the armor (lights inside x 630 .. 785, y 360 .. 420) somewhere else
 C_CUTS = ((540, 280), (560, 300), (500, 260), (600, 310), (520, 330), (580, 250))
 EXTRACTS = [(150, 0.1, 0.4, 40.0, (0.8, 3.2, 3.2, 5.5)), (120, 0.05, 0.5, 45.0, (0.5, 4.0, 3.0, 6.0))]
@@ -63,7 +101,7 @@ _frames = {}
 
 def frame(fam, i):
     if (fam, i) not in _frames:
-        if fam == "C":
+        if fam in "CD":
             if "rm" not in _frames:
                 from PIL import Image
                 _frames["rm"] = np.asarray(Image.open(golden_path("rm_test.jpg")).convert("RGB"))
@@ -80,6 +118,12 @@ def engine(fam, blob, slots=None, streams=None):
     slots, streams = slots or f["slots"], f["streams"] if streams is None else streams
     if fam == "W":
         return weng(blob, num_slots=slots, num_streams=streams)
+    if fam == "T":
+        e = weng(blob, num_slots=slots, num_streams=streams)
+        e.set_number_model(number_model())          # (no operation of a program: the model is there before set_numbers)
+        return e
+    if fam == "D":
+        fam = "C"
     if fam == "B":
         return weng(blob, full=f["full"], src_format="GRBG", bayer_demosaic="mhc", point_source=capi.POINTS_REFINED, num_slots=slots, num_streams=streams)
     if fam == "C":
@@ -117,15 +161,28 @@ def set_global(e, key, v):
     elif key == "extract":
         thr, lo, hi, ang, cd = EXTRACTS[v]
         capi.check(e._L.irmv_engine_set_extract_params(e._h, thr, lo, hi, ang, (C.c_double * 4)(*cd)))
+    elif key == "yaw" and v is not None:
+        e.set_yaw_solve(**YAWS[v])
+    elif key == "cov" and v is not None:
+        e.set_pose_cov(False) if v == 0 else e.set_pose_cov(sigma_px=COVS[v])
+    elif key == "patches" and v is not None:
+        e.set_patches(**PATCHES[v])
+    elif key == "numbers" and v is not None:
+        e.set_numbers(bool(v))
+    elif key == "tracking" and v is not None:
+        e.set_tracking(False) if v == 0 else e.set_tracking(**TRACKING[v])
 
 
 GLOBAL_KEY = {"set_class_policy": "policy", "set_enemy_color": "colour", "set_pose_prior": "prior", "set_refine": "refine", "set_metering": "metering",
-              "set_bayer_isp": "isp", "set_tile_merge": "merge", "set_extract_params": "extract"}
+              "set_bayer_isp": "isp", "set_tile_merge": "merge", "set_extract_params": "extract", **sp.NEW_GLOBAL}
 
 
 def set_state(e, slot, state, fam):
-    """Everything a state tuple of the model holds, onto slot `slot` of an idle engine."""
-    view, corner, policy, colour, prior, up, refine, metering, isp, extract = state
+    """Everything a state tuple of the model holds, onto slot `slot` of an idle engine -- but for the tracking options: R never
+    tracks (no per-frame record depends on them), and a fresh twin sets them itself."""
+    view, corner, policy, colour, prior, up, refine, metering, isp, extract = state[:10]
+    for key, v in zip(("yaw", "cov", "patches", "numbers"), state[10:14]):
+        set_global(e, key, v)
     if e.window_size:
         e.set_view(view, slot)
         e.set_window(corner[0], corner[1], slot)
@@ -133,17 +190,21 @@ def set_state(e, slot, state, fam):
         set_global(e, key, v)
     if fam == "B":
         set_global(e, "refine", refine)
-    if fam == "C":
+    if fam in "CD":
         set_global(e, "extract", extract)
     if prior is not None:
         e.set_up(UPS[up], slot)
 
 
 def switch_on(e, fam):
-    """What a W program's first operations switch on (the records exist from then on, whatever is set later)."""
-    if fam == "W":
+    """What a program's first operations switch on (the records exist from then on, whatever is set later) -- but for the
+    tracker, which only the engines under test and their fresh twins run."""
+    if fam in "WT":
         set_global(e, "prior", 0)
         set_global(e, "metering", 0)
+    for op in sp.FAMILIES[fam]["preamble"]:
+        if op[0] in sp.NEW_GLOBAL and op[0] != "set_tracking":
+            set_global(e, sp.NEW_GLOBAL[op[0]], op[1])
 
 
 def entry(e, fam, kind, slot, variant=None):
@@ -161,10 +222,18 @@ def entry(e, fam, kind, slot, variant=None):
     return e.read_head(slot)
 
 
-def read(e, fam, slot):
+def read(e, fam, slot, tracks=False):
     g = dict(snap=snapshot(e, slot, False), raw=[bytes(d) for d in e.results_raw(slot)])
-    if fam == "W":
+    if fam in "WT":
         g["alts"], g["stats"] = [bytes(a) for a in e.pose_alts(slot)], e.frame_stats(slot)
+    if fam in TRACKED:
+        g["side"] = dict(yaws=[bytes(r) for r in e.yaw_poses(slot)], covs=[bytes(r) for r in e.pose_covs(slot)],
+                         patches=[bytes(r) for r in e.plate_patches(slot)])
+        if fam == "T":
+            g["side"]["numbers"] = [bytes(r) for r in e.plate_numbers(slot)]
+        if tracks:
+            frame, snap = e.tracks(slot)
+            g["tracks"] = (b"".join(bytes(d) for d in e.det_tracks(slot)), bytes(frame), b"".join(bytes(t) for t in snap))
     return g
 
 
@@ -188,6 +257,12 @@ def execute(e, fam, program):
             e.set_tiles(op[2], op[1])
         elif k in GLOBAL_KEY:
             set_global(e, GLOBAL_KEY[k], op[1])
+        elif k == "set_stamp":
+            e.set_stamp(stamp_of(op[2]), op[1])
+        elif k == "set_camera_pose":
+            e.set_camera_pose(POSES[op[2]][0], POSES[op[2]][1], op[1])
+        elif k == "reset_tracks":
+            e.reset_tracks()
         elif k == "detect":
             e.detect(op[1])
         elif k == "submit":
@@ -212,7 +287,7 @@ def execute(e, fam, program):
             assert rc == capi.ERR_ARG, op
             got.append(dict(windows=[e.window(s)[:2] for s in range(e.num_slots)], views=[e.view(s)[0] for s in range(e.num_slots)]))
         elif k == "read":
-            got.append(read(e, fam, op[1]))
+            got.append(read(e, fam, op[1], fam in TRACKED))
         elif k == "read_tiles":
             recs, n_in = e.tile_results_raw(op[1])
             got.append(dict(kept=[(r.tile, r.index, r.cut) for r in recs], dets=[bytes(r.det) for r in recs], n_in=n_in))
@@ -231,6 +306,8 @@ class Ref:
         switch_on(self.e, fam)
 
     def step(self, attr, post=None):
+        attr = (attr[0], attr[1][:14] + (None,))        # (the tracking options: no per-frame record depends on them)
+        post = post and (post[0], post[1][:14] + (None,))
         key = ("step", attr, post)
         if key not in self.cache:
             e = self.e
@@ -242,15 +319,22 @@ class Ref:
                 set_state(e, 0, after, self.fam)
                 e.run_post(0, 1)
             self.cache[key] = read(e, self.fam, 0)
+            if self.fam in TRACKED and post is None:
+                self.cache[key]["obs"] = step_obs(e, 0)             # what the host tracker is fed for a step of this attribution
             self.evals += 1
         return self.cache[key]
 
+    def obs_of(self, frame, state):
+        return self.step((frame, state))["obs"]
+
     def entry(self, kind, attr, variant):
+        attr = (attr[0], attr[1][:14] + (None,))
         key = (kind, attr, variant % 2)
         if key not in self.cache:
             if kind == "read_head":
-                self.cache.pop(("step", attr, None), None)
+                obs = self.cache.pop(("step", attr, None), {}).get("obs")
                 self.step(attr)
+                assert obs is None or obs == self.cache["step", attr, None]["obs"]
             else:
                 set_state(self.e, 0, attr[1], self.fam)
                 self.e.get_src_image_buffer(0)[:] = frame(self.fam, attr[0])
@@ -263,12 +347,12 @@ def blobs(blob, wblob):  # noqa: F811
     """Per family: the crafted blob of test_gpu_window.py; C: a bbox-only blob (nk = 0) with the same class shift and every
     box 3 bins wide on each side, so that the coarse levels' boxes hold the armor of the cut."""
     c = dc.craft(weights.synthetic_blob(0, nk=0), cls=("shift", 3.0), box=("bias", dc.dfl_bias(3)))
-    return {"W": wblob, "B": wblob, "P": wblob, "C": c}
+    return {"W": wblob, "B": wblob, "P": wblob, "C": c, "T": wblob, "D": c}
 
 
 @pytest.fixture(scope="module")
 def refs(blobs):
-    r = {fam: Ref(fam, blobs[fam]) for fam in "WBCP"}
+    r = {fam: Ref(fam, blobs[fam]) for fam in "WBCPTD"}
     yield r
     for x in r.values():
         x.e.close()
@@ -288,8 +372,14 @@ def same_out(a, b, where):
         assert a.shape == b.shape and np.array_equal(a, b), where
 
 
-def check(fam, R, obs, got, where=""):
-    """Every observation of the program against R at the model's attribution -> R's answers of the step observations."""
+def replay_of(R, log, options=TRACK_OPTIONS, poses=POSES):
+    """The host reference of the tracks (irmv_detection_amd/tracks.py) on a model's log, fed what R's steps report."""
+    return sp.Replay(log, R.obs_of, options, stamp_of, poses)
+
+
+def check(fam, R, obs, got, where="", replay=None):
+    """Every observation of the program against R at the model's attribution -> R's answers of the step observations.
+    replay: the host reference on the log of the model that made `obs` (the tracked families)."""
     assert len(obs) == len(got)
     f = sp.FAMILIES[fam]
     answers = []
@@ -298,10 +388,17 @@ def check(fam, R, obs, got, where=""):
         if o["kind"] == "read":
             ref = R.step(o["res"], o["post"])
             same_results(g["snap"], ref["snap"], o["shift"], w)
-            if fam == "W":
+            if fam in "WT":
                 assert g["alts"] == ref["alts"], w
                 if o["stats"] is not None:
                     same_stats(g["stats"], R.step(o["stats"])["stats"], w)
+            if fam in TRACKED:
+                for name, recs in ref["side"].items():          # (a channel its setter disabled since the step: zeroed at once)
+                    assert g["side"][name] == ([bytes(len(r)) for r in recs] if name in o["wiped"] else recs), (w, name)
+                if o["track"] is not None:
+                    want = sp.expected_tracks(replay, o["track"], len(g["raw"]))
+                    for part, a, b in zip(("det_tracks", "frame", "snapshot"), g["tracks"], want):
+                        assert a == b, (w, o["track"], part)
             answers.append(ref)
         elif o["kind"] == "read_tiles":
             parts = [R.step(a) for a in o["parts"]]
@@ -323,10 +420,44 @@ def result_key(a):
     return (tuple(a["raw"]), a["snap"]["counts"])
 
 
-def fresh_engine_agrees(fam, blob, S, program):
-    """F: a fresh engine in the program's final state, stepped once per slot, against S's last results."""
+def fresh_tracker_agrees(fam, blob, S, m, replay):
+    """F1: a fresh one-slot engine stepped synchronously through the last epoch of the log, each step under its own tracking
+    options (the last one's are the program's final ones).  Its table is the one S's last fed slot shows, every byte but
+    the ids, which lie apart by exactly what S's earlier epochs issued; so do the two id counters."""
+    e = len(m.epochs) - 1
+    log = m.resolve(e)
+    last = max(i for i, r in enumerate(log) if not r[4])
+    slot = m.epochs[e][last]["slot"]
+    assert m.trk[slot][1] is m.epochs[e][last], "the program's close feeds every slot: the last one still shows its step"
+    earlier = replay.first_id(e) - 1
+    with engine(fam, blob, 1, 1) as F:
+        switch_on(F, fam)
+        opts = None
+        for frame_i, state, k, pose, _ in log[:last + 1]:
+            set_state(F, 0, state, fam)
+            if state[14] != opts:
+                opts = state[14]
+                set_global(F, "tracking", opts)
+            F.set_stamp(stamp_of(k))
+            F.set_camera_pose(POSES[pose][0], POSES[pose][1])
+            F.get_src_image_buffer(0)[:] = frame(fam, frame_i)
+            F.detect(0)
+        (ff, fs), (sf, ss) = F.tracks(0), S.tracks(slot)
+    assert sf.state == 1 and sf.next_id - ff.next_id == earlier and ff.next_id - 1 == replay.result(e, last)[1].next_id - 1 - earlier, (sf.next_id, ff.next_id, earlier)
+    for a, b in zip(fs, ss):
+        if b.id:
+            b.id -= earlier
+        assert bytes(a) == bytes(b), ("fresh tracker", a.id, b.id)
+    return earlier
+
+
+def fresh_engine_agrees(fam, blob, S, program, replay=None):
+    """F: a fresh engine in the program's final state, stepped once per slot, against S's last results.  (The tracked
+    families: but for the track records, which fresh_tracker_agrees holds.)"""
     m = sp.Model(fam)
     m.run(program)
+    if fam in TRACKED:
+        fresh_tracker_agrees(fam, blob, S, m, replay)
     with engine(fam, blob) as F:
         switch_on(F, fam)
         for s in range(m.n):
@@ -339,22 +470,67 @@ def fresh_engine_agrees(fam, blob, S, program):
             a, b = read(S, fam, s), read(F, fam, s)
             same_results(a["snap"], b["snap"], (0, 0), ("fresh", s))
             assert a["raw"] == b["raw"], ("fresh", s)
-            if fam == "W":
+            if fam in "WT":
                 assert a["alts"] == b["alts"], ("fresh", s)
                 same_stats(a["stats"], b["stats"], ("fresh", s))
+            if fam in TRACKED:
+                assert a["side"] == b["side"], ("fresh", s)
 
 
-def run_case(fam, blob, R, program, where, want_launch=None):
+_facts = {}
+
+
+def track_facts(fam, R, program, key):
+    """What the host reference, fed R's records, says of a tracked program: the observations the model expects and the whole
+    log replayed.  Nothing here comes from an engine under test.  Memoised per (family, seed): the launch forms share it."""
+    if key in _facts:
+        return _facts[key]
+    m = sp.Model(fam)
+    obs = [o for _, o in m.run(program) if o["kind"] == "read"]
+    log = m.log()
+    replay = replay_of(R, log)
+    f = dict(replay=replay, matched=0, started=0, moved=0, no_room=0, deleted=0, triples=set(),
+             refused=sum(o["track"][0] == "refused" for o in obs), zero=sum(o["track"][0] == "zero" for o in obs))
+    for o in obs:
+        if o["track"][0] == "fed":
+            dets, frame, _ = res = replay.result(o["track"][1], o["track"][2])
+            f["matched"] += any(d.state == T.DET_MATCHED for d in dets)
+            f["started"] += any(d.state == T.DET_STARTED for d in dets)
+            f["triples"].add(sp.pack_tracks(res))
+    for e, epoch in enumerate(log):
+        seen = set()
+        for k, entry in enumerate(epoch):
+            dets, frame, snap = replay.result(e, k)
+            gate = TRACK_OPTIONS[entry[1][14]].gate
+            f["moved"] += sum(d.state == T.DET_MATCHED and 0.0 < d.d2 < gate for d in dets)
+            f["no_room"] += frame.n_no_room >= 1
+            ids = {t.id for t in snap if t.state != T.FREE}
+            f["deleted"] += len(seen - ids)
+            seen = ids
+    _facts[key] = f
+    return f
+
+
+def run_case(fam, blob, R, program, where, want_launch=None, key=None):
     t0 = time.time()
     obs = sp.Model(fam).run(program)
+    facts = track_facts(fam, R, program, key or where) if fam in TRACKED else None
+    tf = time.time() - t0
     with engine(fam, blob) as S:
         t1 = time.time()
         got = execute(S, fam, program)
         t2 = time.time()
-        answers = check(fam, R, obs, got, where)
-        fresh_engine_agrees(fam, blob, S, program)
+        answers = check(fam, R, obs, got, where, facts and facts["replay"])
+        fresh_engine_agrees(fam, blob, S, program, facts and facts["replay"])
         launch = S.sync_launch
         assert want_launch is None or launch == want_launch, where
+    if facts:
+        print(f"step program {where}: tracks -- fed log {[len(e) for e in facts['replay'].log]}, observations with a match {facts['matched']}, with a start "
+              f"{facts['started']}, refused {facts['refused']}, zero {facts['zero']}, distinct triples {len(facts['triples'])}; over the log: matches with "
+              f"0 < d2 < gate {facts['moved']}, frames without room {facts['no_room']}, deletions {facts['deleted']}; host reference {tf:.2f} s")
+        # not vacuous, on the host reference's answers alone
+        assert facts["matched"] >= 1 and facts["refused"] >= 1 and len(facts["triples"]) >= 6, where
+        assert fam == "D" or (facts["started"] >= 1 and facts["deleted"] >= 1 and facts["zero"] >= 1), where
     steps = answers
     solved = sum(any(d["ints"][2] == 1 for d in a["snap"]["dets"]) for a in steps)
     distinct = len({result_key(a) for a in steps})
@@ -370,6 +546,26 @@ def test_program_matches_the_reference(blobs, refs, monkeypatch, fam, form, seed
     for k, v in FORMS[form].items():
         monkeypatch.setenv(k, v)
     run_case(fam, blobs[fam], refs[fam], sp.generate(fam, seed, LENGTH), f"{fam}/{form}/{seed}", form if form in ("eager", "graph") else None)
+
+
+@pytest.mark.parametrize("fam,form,seed", sp.TRACK_CASES, ids=[f"{f}-{form}-{s}" for f, form, s in sp.TRACK_CASES])
+def test_tracked_program_matches_the_references(blobs, refs, monkeypatch, fam, form, seed):
+    """Families T and D: the per-frame records (the four newer side records among them) against R, the three track records
+    against irmv_detection_amd/tracks.py replaying the model's fed log on R's records, and the closing checks."""
+    for k, v in FORMS[form].items():
+        monkeypatch.setenv(k, v)
+    run_case(fam, blobs[fam], refs[fam], sp.generate(fam, seed, LENGTH), f"{fam}/{form}/{seed}", form if form in ("eager", "graph") else None, (fam, seed))
+
+
+def test_the_tracked_set_is_not_vacuous(refs):
+    """Over T's cases, on the host reference fed R's records alone: a match of a moved armor (0 < d2 < gate) and a frame
+    that found no room in the table."""
+    moved = no_room = 0
+    for seed in sorted({s for f, _, s in sp.TRACK_CASES if f == "T"}):
+        f = track_facts("T", refs["T"], sp.generate("T", seed, LENGTH), ("T", seed))
+        moved, no_room = moved + f["moved"], no_room + f["no_room"]
+    print(f"tracked set: matches with 0 < d2 < gate {moved}, frames without room {no_room}")
+    assert moved >= 1 and no_room >= 1
 
 
 @pytest.mark.parametrize("with_rotated", [False, True], ids=["plain", "rotated_image_in_flight"])
@@ -401,6 +597,37 @@ def test_palettes_move_the_results(refs):
                 if result_key(R.step((frame_i, st[:1] + (corners[(corners.index(st[1]) + 1) % 4],) + st[2:]))) != here:
                     moved_c.add(st[1])
         assert moved_p == set(range(sp.N_POLICY)) and moved_c == set(corners), (fam, moved_p, moved_c)
+    # the newer setters, on family T: every palette entry changes the record it governs at an observed attribution ...
+    R = refs["T"]
+    programs = {seed: sp.generate("T", seed, LENGTH) for seed in sorted({s for f, _, s in sp.TRACK_CASES if f == "T"})}
+    attrs = set()
+    for p in programs.values():
+        attrs.update(o["res"] for _, o in sp.Model("T").run(p) if o["kind"] == "read" and not o["post"])
+    moved = set()
+    for idx, name, count in ((10, "yaws", sp.N_YAW), (11, "covs", sp.N_COV), (12, "patches", sp.N_PATCHES), (13, "numbers", sp.N_NUMBERS)):
+        for v in range(count):
+            for frame_i, st in sorted((a for a in attrs if a[1][idx] == v), key=repr)[:8]:
+                here = R.step((frame_i, st))["side"][name]
+                if any(R.step((frame_i, st[:idx] + (q,) + st[idx + 1:]))["side"][name] != here for q in range(count) if q != v):
+                    moved.add((name, v))
+                    break
+    assert moved == {("yaws", 0), ("yaws", 1), ("covs", 0), ("covs", 1), ("covs", 2), ("patches", 0), ("patches", 1), ("numbers", 0), ("numbers", 1)}, moved
+    # ... and every tracking option set, every camera pose and every sigma_px (through the tracker's noise) the track records
+    # of program 0: the host reference on the same log with the entry exchanged gives other bytes
+    base = track_facts("T", R, programs[0], ("T", 0))["replay"]
+    log = base.log
+
+    def moves(log, **kw):
+        """Does the host reference give other bytes somewhere?  (It stops at the first entry that differs.)"""
+        r = replay_of(R, log, **kw)
+        return any(sp.pack_tracks(r.result(e, k)) != sp.pack_tracks(base.result(e, k)) for e in range(len(log)) for k in range(len(log[e])))
+
+    for i in (1, 2):
+        assert moves(log, options=[None, TRACK_OPTIONS[3 - i], TRACK_OPTIONS[3 - i]]), ("tracking options", i)
+        assert moves(log, poses=[POSES[0] if j == i else q for j, q in enumerate(POSES)]), ("camera pose", i)
+    for v in range(sp.N_COV):
+        other = [[(fr, st[:11] + ((v + 1) % sp.N_COV,) + st[12:], k, pose, ref) if st[11] == v else (fr, st, k, pose, ref) for fr, st, k, pose, ref in ep] for ep in log]
+        assert moves(other), ("sigma_px", v)
 
 
 # ---- controls: a model that breaks one rule must be caught -----------------------------------------------------------------------
@@ -415,3 +642,15 @@ def test_a_wrong_model_is_caught(wblob, refs):  # noqa: F811
         wrong = sp.Model("W", **{flag: True}).run(program)
         with pytest.raises(AssertionError):
             check("W", refs["W"], wrong, got, flag)
+    # the T control: the contract passes; the three wrong models of rule 7 and, again, the four above are each caught
+    program = sp.generate("T", sp.CONTROL_SEED, sp.CONTROL_LENGTH)
+    with engine("T", wblob) as S:
+        got = execute(S, "T", program)
+    m = sp.Model("T")
+    obs = m.run(program)
+    check("T", refs["T"], obs, got, "control T", replay_of(refs["T"], m.log()))
+    for flag in ("tracks_by_slot", "skips_feed", "refused_feeds", "late_setters", "late_frames", "sticky_groups", "current_corner"):
+        m = sp.Model("T", **{flag: True})
+        wrong = m.run(program)
+        with pytest.raises(AssertionError):
+            check("T", refs["T"], wrong, got, flag, replay_of(refs["T"], m.log()))
