@@ -1011,6 +1011,17 @@ int irmv_engine_debug_poke_candidate_counts(irmv_engine *e, int value);
    (all zero between steps).  *sparse = 1 if this engine's steps store candidate head rows only (IRMV_SPARSE_HEAD=0, or a
    configuration without candidate emission: 0, and no words are kept: *n = 0).  words may be NULL to query *n. */
 int irmv_engine_debug_read_cand_bits(irmv_engine *e, int slot, uint32_t *words, int cap, int *n, int *sparse);
+/* Its counterpart (tests/test_gpu_gather_craft.py): waits, then copies n words over the slot's bitmap.  IRMV_ERR_ARG on an
+   engine without a sparse head, for n other than the engine's word count, and for any set bit at or past num_anchors.  A
+   step expects the bitmap all zero: write zeros back before the next one. */
+int irmv_engine_debug_write_cand_bits(irmv_engine *e, int slot, const uint32_t *words, int n);
+/* The candidate lists of Detect level `level` (0 .. 2, one with a boxg op) on slots [first, first + count), as
+   cand_list_kernel leaves them: counts[count], and entries[count][H * W] of which image i's first counts[i] are its list
+   (pixel = y * W + x).  Waits, then copies; irmv_engine_run_op with IRMV_RUN_WRITTEN_LISTS gathers from them.
+   IRMV_ERR_ARG for a count outside [0, H * W] or ANY entry outside [0, H * W).  Reading: the ranges "boxg_list" (level l,
+   slot s at int index lvl_base[l] * num_slots + s * H * W) and "boxg_count" ([3][num_slots]) of irmv_engine_debug_allocs,
+   through irmv_engine_debug_read_mem. */
+int irmv_engine_debug_write_cand_lists(irmv_engine *e, int level, int first_slot, int count, const int32_t *counts, const int32_t *entries);
 /* Read-only (tests): the slot's head records as they lie in memory, with NO read-back step in front (read_head, read_tap and
    read_tensor first bring a sparse head to the dense state): [num_anchors][96] floats, box 64 | classes at 64 | keypoints at
    80; `bytes` must be num_anchors * 96 * 4.  After a step of a sparse engine only the rows the step stored are the step's. */
@@ -1087,7 +1098,7 @@ int irmv_engine_write_tensor(irmv_engine *e, const char *name, int first_slot, i
  * Every op of the engine's graph, of any kind; the non-conv layer ops run one at a time on a slot range. */
 typedef struct irmv_graph_op {
     int32_t op;                 /* the engine's op index (the `op` of irmv_engine_run_op and of the conv hooks above) */
-    char kind[16];              /* conv conv0 pool dw shuffle front c2f2 c2f32 bneck kpt3 pre demosaic crop scan nms light meter */
+    char kind[16];              /* conv conv0 pool dw shuffle front c2f2 c2f32 bneck kpt3 boxg pre demosaic crop scan nms light meter */
     char layer[48];             /* weight layer, or the op's own name (model.9.m, model.N.shuffle, preprocess, ...) */
     char kname[48];             /* kernel, as irmv_engine_profile names it */
     irmv_conv_seg s0, s1;       /* inputs (tensor "" = none; the pool's: channels [0, C) of its own tensor) */
@@ -1099,16 +1110,28 @@ typedef struct irmv_graph_op {
 
 /* One record per op of the graph, in step order; *n = their number (records beyond cap are not written). */
 int irmv_engine_ops(irmv_engine *e, irmv_graph_op *ops, int cap, int *n);
-/* Run the engine's own kernel of a conv0, pool, dw or shuffle op, or of a fused c2f2, c2f32, bneck or kpt3 op, on slots
+/* Run the engine's own kernel of a conv0, pool, dw or shuffle op, or of a fused c2f2, c2f32, bneck, kpt3 or boxg op, on slots
  * [first, first + count), as a step of that count launches it, and synchronize.  A fused op runs as a plain launch: kpt3
  * without the sparse head's gate, every head row written.  flags: IRMV_RUN_POISON / IRMV_RUN_POISON_ONLY over the op's
  * output channels on those slots (the pool: channels [C, 4C) of its tensor; [0, C) is its input; a fused op: every range
- * irmv_engine_op_io lists as written).  IRMV_ERR_ARG for any other kind. */
+ * irmv_engine_op_io lists as written).  IRMV_ERR_ARG for any other kind, and for a flag below on an op that is no boxg op.
+ *
+ * A boxg op (the candidate gather of a Detect level, on an engine with the sparse head): cand_list_kernel turns the
+ * candidate bitmap of the slots (irmv_engine_debug_write_cand_bits) into every level's lists, then the level's gather
+ * stores the box channels of the head rows at its candidate anchors -- and the keypoint channels (the final's padding
+ * included) where a batched step's launch of the op carries the level's keypoint branch.  count: 1 .. num_slots, whatever
+ * the step plans launch.  The poison flags cover the box channels of EVERY row of the range, and the keypoint channels
+ * when that branch rides. */
+#define IRMV_RUN_BOX_ONLY 4u        /* boxg: the box-only instantiation also where the keypoint branch would ride */
+#define IRMV_RUN_WRITTEN_LISTS 8u   /* boxg: no cand_list_kernel; the gather runs on what irmv_engine_debug_write_cand_lists wrote */
+#define IRMV_RUN_GRID(n) ((uint32_t)(n) << 16)   /* boxg: n = 1 .. 65535 persistent workgroups; 0: the engine's own grid (one per CU) */
 int irmv_engine_run_op(irmv_engine *e, int op, int first_slot, int count, uint32_t flags);
-/* What a fused op (c2f2, c2f32, bneck, kpt3) stands for: the conv ops whose layers it computes, in the order a step without
- * it runs them, every channel range its launch writes, and every channel range it reads (a residual included; a segment
- * with shift 1 is read as its nearest 2x upsample).  Nothing else of any activation tensor reaches its output.  No conv or
- * fused kernel reads channels beyond a segment's C: K positions past Cin are clamped onto the segment's own last channels.
+/* What a fused op (c2f2, c2f32, bneck, kpt3, boxg) stands for: the conv ops whose layers it computes, in the order a step
+ * without it runs them, every channel range its launch writes, and every channel range it reads (a residual included; a
+ * segment with shift 1 is read as its nearest 2x upsample).  Nothing else of any activation tensor reaches its output.  No conv
+ * or fused kernel reads channels beyond a segment's C: K positions past Cin are clamped onto the segment's own last channels.
+ * boxg: sub = the three box convs; writes = the head's box channels, then the keypoint final's cout_pad channels where the
+ * branch rides (its three convs: the sub-ops of the level's kpt3 op); it writes them at the candidate anchors only.
  * IRMV_ERR_ARG for an op of any other kind. */
 typedef struct irmv_op_io {
     int32_t op;

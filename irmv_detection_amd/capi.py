@@ -345,6 +345,14 @@ class MeterMap(C.Structure):
 
 DECLINED = 1    # irmv_engine_run_conv_candidate: no kernel runs that candidate
 RUN_POISON, RUN_POISON_ONLY = 1, 2   # ... its flags: NaN over the output it must write first (and launch nothing)
+RUN_BOX_ONLY, RUN_WRITTEN_LISTS = 4, 8   # a boxg op: without the keypoint branch that rides; on written lists (no cand_list_kernel)
+
+
+def RUN_GRID(n):
+    """IRMV_RUN_GRID: a boxg op's launch on n persistent workgroups (0: the engine's own grid)."""
+    assert 0 <= n < 65536
+    return n << 16
+
 
 MEM_CLASSES = ("CONST", "ACT", "CARRIED", "SCRATCH")   # IRMV_MEM_CONST .. IRMV_MEM_SCRATCH
 MEM_KINDS = ("U8", "F16", "F32", "F64", "INDEX")       # IRMV_MEM_U8 .. IRMV_MEM_INDEX
@@ -425,6 +433,8 @@ SYMBOLS = [
     ("irmv_engine_run_post", C.c_int, [_P, C.c_int, C.c_int]),
     ("irmv_engine_debug_poke_candidate_counts", C.c_int, [_P, C.c_int]),
     ("irmv_engine_debug_read_cand_bits", C.c_int, [_P, C.c_int, C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("irmv_engine_debug_write_cand_bits", C.c_int, [_P, C.c_int, C.POINTER(C.c_uint32), C.c_int]),
+    ("irmv_engine_debug_write_cand_lists", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("irmv_engine_debug_read_head_rows", C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.c_size_t]),
     ("irmv_engine_debug_read_head_raw", C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
     ("irmv_engine_read_tap", C.c_int, [_P, C.c_int, C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]),

@@ -45,6 +45,48 @@ extern "C" int irmv_engine_debug_read_cand_bits(irmv_engine *e, int slot, uint32
     return IRMV_OK;
 }
 
+extern "C" int irmv_engine_debug_write_cand_bits(irmv_engine *e, int slot, const uint32_t *words, int n)
+{
+    TRY(check_range(e, slot, 1));
+    if (!e->sparse_head) return fail(IRMV_ERR_ARG, "write_cand_bits: this engine has no sparse head");
+    if (!words || n != e->cand_words) return fail(IRMV_ERR_ARG, "write_cand_bits: the word count is not the engine's");
+    for (int wd = 0; wd < n; wd++) {   // (cand_list_kernel guards `an < A` itself: that guard is not for a test to lean on)
+        const int lo = wd * 32;
+        const uint32_t past = lo >= e->A ? 0xffffffffu : (e->A - lo >= 32 ? 0u : 0xffffffffu << (e->A - lo));
+        if (words[wd] & past) return fail(IRMV_ERR_ARG, "write_cand_bits: a bit at or past the last anchor is set");
+    }
+    TRY(irmv_engine_wait(e));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(hipMemcpy(e->cand_bits + (size_t)slot * e->cand_words, words, (size_t)n * sizeof(unsigned int), hipMemcpyHostToDevice));
+    return IRMV_OK;
+}
+
+// the level's OP_BOXG op; -1: none
+static int boxg_of_level(const irmv_engine *e, int level)
+{
+    for (size_t i = 0; i < e->ops.size(); i++)
+        if (e->ops[i].kind == OP_BOXG && e->ops[i].level == level) return (int)i;
+    return -1;
+}
+
+extern "C" int irmv_engine_debug_write_cand_lists(irmv_engine *e, int level, int first, int count, const int32_t *counts, const int32_t *entries)
+{
+    TRY(check_range(e, first, count));
+    if (level < 0 || level > 2 || !e->boxg_list || boxg_of_level(e, level) < 0) return fail(IRMV_ERR_ARG, "write_cand_lists: the level has no box gather op");
+    if (!counts || !entries) return fail(IRMV_ERR_ARG, "write_cand_lists: counts / entries is null");
+    const int hw = e->lvl_hw[level];
+    for (int i = 0; i < count; i++)   // (box_gather_kernel clamps both itself: those clamps are not for a test to lean on)
+        if (counts[i] < 0 || counts[i] > hw) return fail(IRMV_ERR_ARG, "write_cand_lists: a count outside [0, H * W]");
+    for (size_t i = 0; i < (size_t)count * hw; i++)
+        if (entries[i] < 0 || entries[i] >= hw) return fail(IRMV_ERR_ARG, "write_cand_lists: an entry outside [0, H * W)");
+    TRY(irmv_engine_wait(e));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    const size_t S = (size_t)e->cfg.num_slots;   // (cand_list_args' addresses)
+    HIP_TRY(hipMemcpy(e->boxg_list + (size_t)e->lvl_base[level] * S + (size_t)first * hw, entries, (size_t)count * hw * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->boxg_count + (size_t)level * S + first, counts, (size_t)count * sizeof(int), hipMemcpyHostToDevice));
+    return IRMV_OK;
+}
+
 extern "C" int irmv_engine_rotated_image(irmv_engine *e, int slot, uint8_t *dst)
 {
     TRY(check_range(e, slot, 1));
@@ -732,8 +774,17 @@ extern "C" int irmv_engine_ops(irmv_engine *e, irmv_graph_op *ops, int cap, int 
     return IRMV_OK;
 }
 
+// The OP_KPT3 op whose branch a batched step's launch of OP_BOXG op `op` computes too (Launch::kpt, the same in every view);
+// -1: the launch is box only, or no batched step gathers.
+static int boxg_kpt(const irmv_engine *e, int op)
+{
+    for (const Launch &l : e->views[0].plans[STEP_BATCH])
+        if (l.op == op && l.group < 0) return l.kpt;
+    return -1;
+}
+
 // What a fused op's launch writes and reads, from the argument builders of engine_step.cpp (c2f2_args, c2f32_args, bneck_args,
-// kpt3_args) and the kernels behind them; false: op is no fused op.
+// kpt3_args, boxg_args) and the kernels behind them; false: op is no fused op.
 struct FusedIo { std::vector<int> sub; std::vector<SegRef> writes, reads; };
 static bool fused_io(const irmv_engine *e, const Op &op, FusedIo &io)
 {
@@ -769,6 +820,17 @@ static bool fused_io(const irmv_engine *e, const Op &op, FusedIo &io)
         io.writes.push_back(SegRef{o2.out_t, o2.out_coff, o2.cout_pad, 0});   // (the final's padding rows too: 16 floats of a record)
         return true;
     }
+    case OP_BOXG: {  // the level's input -> the box channels of its head records at the candidate anchors, and the keypoint channels where the branch rides
+        const Op &o2 = e->ops[op.sub[2]];
+        seg(e->ops[op.sub[0]].s0);
+        io.writes.push_back(SegRef{o2.out_t, o2.out_coff, o2.cout, 0});
+        const int k = boxg_kpt(e, (int)(&op - e->ops.data()));
+        if (k >= 0) {
+            const Op &k2 = e->ops[e->ops[k].sub[2]];
+            io.writes.push_back(SegRef{k2.out_t, k2.out_coff, k2.cout_pad, 0});   // (kpt3's: the final's padding rows too)
+        }
+        return true;
+    }
     default: return false;
     }
 }
@@ -778,7 +840,7 @@ extern "C" int irmv_engine_op_io(irmv_engine *e, int op, irmv_op_io *out)
     if (!e || !out) return fail(IRMV_ERR_ARG, "engine / io is null");
     if (op < 0 || op >= (int)e->ops.size()) return fail(IRMV_ERR_ARG, "no such op");
     FusedIo io;
-    if (!fused_io(e, e->ops[op], io)) return fail(IRMV_ERR_ARG, std::string("op_io describes c2f2, c2f32, bneck and kpt3 ops, not ") + op_kind_name(e->ops[op].kind));
+    if (!fused_io(e, e->ops[op], io)) return fail(IRMV_ERR_ARG, std::string("op_io describes c2f2, c2f32, bneck, kpt3 and boxg ops, not ") + op_kind_name(e->ops[op].kind));
     memset(out, 0, sizeof *out);
     out->op = op;
     out->n_sub = (int32_t)io.sub.size(); out->n_writes = (int32_t)io.writes.size(); out->n_reads = (int32_t)io.reads.size();
@@ -796,7 +858,12 @@ extern "C" int irmv_engine_run_op(irmv_engine *e, int op, int first, int count, 
     FusedIo io;
     const bool fused = fused_io(e, o, io);
     if (!fused && o.kind != OP_CONV0 && o.kind != OP_POOL && o.kind != OP_DW && o.kind != OP_SHUF)
-        return fail(IRMV_ERR_ARG, std::string("run_op runs conv0, pool, dw, shuffle, c2f2, c2f32, bneck and kpt3 ops, not ") + op_kind_name(o.kind));
+        return fail(IRMV_ERR_ARG, std::string("run_op runs conv0, pool, dw, shuffle, c2f2, c2f32, bneck, kpt3 and boxg ops, not ") + op_kind_name(o.kind));
+    const bool boxg = o.kind == OP_BOXG;
+    if (!boxg && (flags & ~kRunPoisons)) return fail(IRMV_ERR_ARG, "run_op: flags other than the poison flags are a boxg op's");
+    if (boxg && (flags & ~(kRunPoisons | IRMV_RUN_BOX_ONLY | IRMV_RUN_WRITTEN_LISTS | 0xffff0000u))) return fail(IRMV_ERR_ARG, "run_op: unknown flag bits");
+    if (boxg && (!e->sparse_head || !e->boxg_list)) return fail(IRMV_ERR_ARG, "run_op: a boxg op needs the sparse head's bitmap and the candidate lists");
+    if (boxg && ((flags & IRMV_RUN_BOX_ONLY) || boxg_kpt(e, op) < 0) && io.writes.size() > 1) io.writes.resize(1);   // (box only: the keypoint channels are not this run's)
     HIP_TRY(hipSetDevice(e->cfg.device));
     TRY(irmv_engine_wait(e));
     if (fused) TRY(slots_view(e, first, count, nullptr));
@@ -810,6 +877,12 @@ extern "C" int irmv_engine_run_op(irmv_engine *e, int op, int first, int count, 
     if (flags & IRMV_RUN_POISON_ONLY) { HIP_TRY(hipStreamSynchronize(e->stream)); return IRMV_OK; }
     Launch l;   // (a plain launch of the op: no group, no fusion, no gate)
     l.op = op;
+    if (boxg) {   // cand_list_kernel in front unless the lists are the caller's; the keypoint branch where a batched step links it
+        l.sparse = true;
+        l.cand_list = !(flags & IRMV_RUN_WRITTEN_LISTS);
+        l.kpt = (flags & IRMV_RUN_BOX_ONLY) ? -1 : boxg_kpt(e, op);
+        l.grid = (int)(flags >> 16);
+    }
     const Step step{count == 1 ? STEP_ONE : STEP_BATCH, first, count};
     TRY(launch_op(e, view_of(e, first), l, step, post_args(e, view_of(e, first), step), 0u, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));

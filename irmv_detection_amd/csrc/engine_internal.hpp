@@ -192,6 +192,7 @@ struct Launch {
     int gate = 0;             // sparse branch, ConvArgs::tile_gate / Kpt3Args::tile_gate: 0 = off, 1 = halo 0 (writes head rows), 2 = halo 1 (box branch's first conv)
     bool cand_list = false;   // OP_BOXG: the plan's first -- cand_list_kernel runs in front of it, for every level's launch
     int kpt = -1;             // OP_BOXG: the level's OP_KPT3 op whose branch the launch computes too (the plan has dropped that launch); -1: box only
+    int grid = 0;             // OP_BOXG: workgroups of the launch (irmv_engine_run_op's IRMV_RUN_GRID); 0: the engine's (IRMV_SPARSE_GATHER_GRID, else one per CU)
     bool once = false;        // not repeated under irmv_engine_profile (appends to, consumes or rewrites per-frame lists)
     std::string name, layer;  // irmv_engine_profile's row
     double flops = 0, bytes = 0, launch_bytes = 0;   // per frame; launch_bytes (the weights): once per launch

@@ -402,7 +402,7 @@ int irmv::launch_op(irmv_engine *e, const View &v, const Launch &l, const Step &
     case OP_BOXG:
         if (!pa.cand_bits) return fail(IRMV_ERR_ARG, "a box gather launch needs the sparse head's bitmap: " + op.layer);
         if (l.cand_list) launch_cand_list(cand_list_args(e, first, pa), count, s);
-        if (!launch_box_gather(boxg_args(e, op, l, first, pa), op.cin, count, e->sw.gather_grid > 0 ? e->sw.gather_grid : e->num_cus, s)) return fail(IRMV_ERR_ARG, "no box gather kernel for " + op.layer);
+        if (!launch_box_gather(boxg_args(e, op, l, first, pa), op.cin, count, l.grid > 0 ? l.grid : (e->sw.gather_grid > 0 ? e->sw.gather_grid : e->num_cus), s)) return fail(IRMV_ERR_ARG, "no box gather kernel for " + op.layer);
         break;
     case OP_DW: launch_dwconv3x3(dw_args(e, op, first), count, s); break;
     case OP_SHUF: launch_shuffle_cat(shuf_args(e, op, first, count), s); break;

@@ -54,6 +54,7 @@ COVERED = {   # the other kinds that write activation tensors, and where they ar
     "front": "bitwise against its layers in the sweep, and on the zoo of tests/test_gpu_input_geometry.py", "c2f2": "bitwise against its layers in the sweep",
     "c2f32": "bitwise against its layers in the sweep", "bneck": "bitwise against its layers in the sweep",
     "kpt3": "bitwise against its layers in the sweep",   # (all four also alone, on written inputs: tests/test_gpu_act_craft.py)
+    "boxg": "alone, on written candidates and activations: tests/test_gpu_gather_craft.py (here: check_boxg)",
     "pre": "the preprocess bit-exact tests of tests/test_gpu_engine.py and tests/test_gpu_rect.py, and bitwise against the oracle "
            "on the zoo of tests/test_gpu_input_geometry.py",
 }
@@ -119,6 +120,32 @@ def check_runs(e, op, ranges):
             assert np.array_equal(read(e, n, 0, N), v), (op.layer.decode(), first, count, f"input {n} changed")
 
 
+def check_boxg(e, op, ranges):
+    """A candidate gather op (it names no output tensor of its own: it writes head rows at candidate anchors).
+    irmv_engine_op_io describes it -- its level's three box convs, the level input, the head's box channels (and the keypoint
+    channels where that branch rides) -- and on the bitmap a step leaves behind, all zero, its run on every range builds empty
+    lists and writes nothing: the dense head is what it was.  An engine without the sparse head refuses the run."""
+    N = e.num_slots
+    io = capi.OpIo()
+    capi.check(e._L.irmv_engine_op_io(e._h, op.op, C.byref(io)))
+    lv = int(op.layer.decode().split(".")[3])
+    assert op.layer.decode() == f"model.22.cv2.{lv}.g" and op.kname.decode().startswith("box_gather_c") and not op.out_tensor
+    assert io.n_sub == 3 and io.n_reads == 1 and io.n_writes in (1, 2)
+    head = io.writes[0].tensor.decode()
+    assert (head, io.writes[0].coff, io.writes[0].C) == (f"head.{lv}", 0, 64)
+    if io.n_writes == 2:
+        assert (io.writes[1].tensor.decode(), io.writes[1].coff, io.writes[1].C) == (head, 80, 16)
+    sparse, _ = e.debug_cand_bits(0)
+    if not sparse:
+        assert e._L.irmv_engine_run_op(e._h, op.op, 0, 1, 0) == capi.ERR_ARG
+        return
+    base = read(e, head, 0, N)
+    for first, count in ranges:
+        assert not any(e.debug_cand_bits(s)[1].any() for s in range(first, first + count))
+        run_op(e, op.op, first, count, 0)
+    assert np.array_equal(read(e, head, 0, N).view(np.uint32), base.view(np.uint32)), (op.layer, "a run without a candidate wrote head rows")
+
+
 def ref_ratio(e, op, table, specs, slot):
     """conv0, dw: worst err / bound of the op's output on one slot.  shuffle, pool: the number of mismatches (must be 0)."""
     out_name = op.out_tensor.decode()
@@ -173,6 +200,9 @@ def check_graph(e, blob, log, tag, ranges, ref_slots, slabs, shuffle):
     for op in mine:
         check_runs(e, op, ranges)
         worst[op.layer.decode()] = max(ref_ratio(e, op, table, specs, s) for s in ref_slots)
+    for op in ops:
+        if op.kind == b"boxg":
+            check_boxg(e, op, ranges)
     parts = []
     for k in CHECKED:
         w = [(v, n) for n, v in worst.items() if kind_of[n] == k]
