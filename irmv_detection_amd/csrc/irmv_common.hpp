@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <cstdlib>
+#include <mutex>
 
 namespace irmv {
 
@@ -12,6 +13,56 @@ typedef _Float16 half_t;
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+// 16 bytes as the memory instructions move them: eight fp16 of a fragment, loaded, selected and stored without a type
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x4 ld16(const half_t *p) { return *reinterpret_cast<const u32x4 *>(p); }
+__device__ __forceinline__ u32x4 keep_if(bool c, u32x4 v) { return c ? v : (u32x4){0u, 0u, 0u, 0u}; }   // zero padding by select (the load itself is unconditional)
+__device__ __forceinline__ half8 as_h8(u32x4 v) { return __builtin_bit_cast(half8, v); }
+
+// ---- dynamic LDS above the default 64 KiB (host) ------------------------------------------------------------------------
+// A kernel may only be launched with more once hipFuncSetAttribute has raised its limit, per device.  Engines are created
+// and run from several threads (one per GPU): the check, the attribute call and the update are one critical section, so no
+// thread launches before the limit is raised.  (Taken on every launch CALL -- engine creation, tuning, graph capture, eager
+// profiling; a captured step is replayed without any of this code.)
+inline std::mutex g_lds_limit_mu;
+// The memory of one kernel, per device: the largest byte count granted, and the one value its launcher derives from the
+// raised limit (0 where it derives none)
+struct LdsGrant { size_t bytes; int derived; };
+template <auto Kernel>
+inline LdsGrant g_lds_grant[64] = {};
+// The limit of `Kernel` on the current device is at least `bytes` afterwards; false: the runtime refused (no sticky error is
+// left).  A request at or below the largest count granted does nothing.  derive(dev) runs behind every attribute call,
+// inside the critical section (so once per device, unless the runtime refuses); every call hands its value back in `derived`.
+template <auto Kernel, class F>
+bool raise_lds_limit(size_t bytes, int &derived, F derive)
+{
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    LdsGrant &g = g_lds_grant<Kernel>[dev & 63];
+    bool ok = true;
+    std::lock_guard<std::mutex> lk(g_lds_limit_mu);
+    if (bytes > g.bytes) {
+        ok = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+        if (ok) g.bytes = bytes;
+        else (void)hipGetLastError();
+        g.derived = derive(dev);
+    }
+    derived = g.derived;
+    return ok;
+}
+template <auto Kernel>
+bool raise_lds_limit(size_t bytes)
+{
+    int none;
+    return raise_lds_limit<Kernel>(bytes, none, [](int) { return 0; });
+}
+// ... and the launch behind it (a refusal shows as the launch's own error)
+template <auto Kernel, class... A>
+void launch_lds(dim3 grid, dim3 block, size_t lds, size_t limit, hipStream_t s, A... args)
+{
+    (void)raise_lds_limit<Kernel>(limit);
+    hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+}
 
 // ---- activation scale (round 4) ---------------------------------------------------
 // Every fp16 activation tensor between the layers holds a' = log2(e) * a.  With biases pre-multiplied by log2(e) at load
@@ -35,7 +86,6 @@ constexpr float kActUnscale = 0.693147180559945309f; // ln 2
 // output of 70 000.  Every SiLU output is therefore produced by v_fma_mix*_f16 explicitly: exp, add, rcp, fma_mix -- four
 // vector instructions per output value, no separate multiply or convert -- and the shortcut variants (activation + residual,
 // rounded after the add) pin their fp32 intermediates with empty asm statements.
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float silu_rcp(float y) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-y)); }
 // two activated outputs as one packed half2: lo = half(y0 * sigma(y0)), hi = half(y1 * sigma(y1)), each rounded once
 __device__ __forceinline__ unsigned int silu_pack2(float y0, float y1)
@@ -48,7 +98,7 @@ __device__ __forceinline__ unsigned int silu_pack2(float y0, float y1)
 }
 __device__ __forceinline__ half8 silu_pack8(float y0, float y1, float y2, float y3, float y4, float y5, float y6, float y7)
 {
-    return __builtin_bit_cast(half8, (u32x4_t){silu_pack2(y0, y1), silu_pack2(y2, y3), silu_pack2(y4, y5), silu_pack2(y6, y7)});
+    return as_h8((u32x4){silu_pack2(y0, y1), silu_pack2(y2, y3), silu_pack2(y4, y5), silu_pack2(y6, y7)});
 }
 __device__ __forceinline__ half4 silu_pack4(float y0, float y1, float y2, float y3)
 {

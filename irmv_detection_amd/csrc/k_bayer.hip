@@ -45,16 +45,16 @@ __device__ __forceinline__ void demosaic_band(const BayerArgs &a, const uint8_t 
     const int tail0 = head + (n16 << 4);
     for (int k = threadIdx.x; k < head; k += blockDim.x) lds[mis + k] = src[k];
     for (int i0 = threadIdx.x; i0 < n16; i0 += 4 * blockDim.x) {   // four loads in flight per lane before the LDS writes
-        u32x4_t v[4];
+        u32x4 v[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int i = i0 + u * (int)blockDim.x;
-            if (i < n16) v[u] = *reinterpret_cast<const u32x4_t *>(src + head + 16 * i);
+            if (i < n16) v[u] = *reinterpret_cast<const u32x4 *>(src + head + 16 * i);
         }
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int i = i0 + u * (int)blockDim.x;
-            if (i < n16) *reinterpret_cast<u32x4_t *>(lds + mis + head + 16 * i) = v[u];
+            if (i < n16) *reinterpret_cast<u32x4 *>(lds + mis + head + 16 * i) = v[u];
         }
     }
     for (int k = tail0 + (int)threadIdx.x; k < nbytes; k += blockDim.x) lds[mis + k] = src[k];
@@ -76,7 +76,7 @@ __device__ __forceinline__ void demosaic_band(const BayerArgs &a, const uint8_t 
             const int xl = x0 == 0 ? 1 : x0 - 1;
             p[k][0] = r[xl];
             if (aligned && x0 + kRun <= W) {
-                const u32x4_t v = *reinterpret_cast<const u32x4_t *>(r + x0);
+                const u32x4 v = *reinterpret_cast<const u32x4 *>(r + x0);
 #pragma unroll
                 for (int j = 0; j < kRun; j++) p[k][j + 1] = (v[j >> 2] >> (8 * (j & 3))) & 0xffu;
             } else {
@@ -117,13 +117,13 @@ __device__ __forceinline__ void demosaic_band(const BayerArgs &a, const uint8_t 
         if (x0 + kRun <= W && ((uintptr_t)d & 15) == 0) {
 #pragma unroll
             for (int q = 0; q < 3; q++) {
-                u32x4_t v;
+                u32x4 v;
 #pragma unroll
                 for (int w = 0; w < 4; w++) {
                     const int b = 16 * q + 4 * w;
                     v[w] = out[b] | (out[b + 1] << 8) | (out[b + 2] << 16) | (out[b + 3] << 24);
                 }
-                reinterpret_cast<u32x4_t *>(d)[q] = v;
+                reinterpret_cast<u32x4 *>(d)[q] = v;
             }
         } else {
             const int n = min(kRun, W - x0) * 3;
@@ -153,16 +153,16 @@ __device__ __forceinline__ int stage_rows(const uint8_t *src, int nbytes, uint8_
     const int tail0 = head + (n16 << 4);
     for (int k = threadIdx.x; k < head; k += blockDim.x) lds[mis + k] = src[k];
     for (int i0 = threadIdx.x; i0 < n16; i0 += 4 * blockDim.x) {   // four loads in flight per lane before the LDS writes
-        u32x4_t v[4];
+        u32x4 v[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int i = i0 + u * (int)blockDim.x;
-            if (i < n16) v[u] = *reinterpret_cast<const u32x4_t *>(src + head + 16 * i);
+            if (i < n16) v[u] = *reinterpret_cast<const u32x4 *>(src + head + 16 * i);
         }
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int i = i0 + u * (int)blockDim.x;
-            if (i < n16) *reinterpret_cast<u32x4_t *>(lds + mis + head + 16 * i) = v[u];
+            if (i < n16) *reinterpret_cast<u32x4 *>(lds + mis + head + 16 * i) = v[u];
         }
     }
     for (int k = tail0 + (int)threadIdx.x; k < nbytes; k += blockDim.x) lds[mis + k] = src[k];
@@ -175,13 +175,13 @@ __device__ __forceinline__ void store_run(uint8_t *d, const uint32_t (&out)[3 * 
     if (x0 + kRun <= W && ((uintptr_t)d & 15) == 0) {
 #pragma unroll
         for (int q = 0; q < 3; q++) {
-            u32x4_t v;
+            u32x4 v;
 #pragma unroll
             for (int w = 0; w < 4; w++) {
                 const int b = 16 * q + 4 * w;
                 v[w] = out[b] | (out[b + 1] << 8) | (out[b + 2] << 16) | (out[b + 3] << 24);
             }
-            reinterpret_cast<u32x4_t *>(d)[q] = v;
+            reinterpret_cast<u32x4 *>(d)[q] = v;
         }
     } else {
         const int n = min(kRun, W - x0) * 3;
@@ -198,7 +198,7 @@ __device__ __forceinline__ void demosaic_band_table(const BayerArgs &a, const ui
     constexpr int R = MHC ? 2 : 1, NR = 2 * R + 1;
     const uint8_t *tab = lds;
     uint8_t *staged = lds + kBayerTableBytes;
-    if (threadIdx.x < kBayerTableBytes / 16) reinterpret_cast<u32x4_t *>(lds)[threadIdx.x] = reinterpret_cast<const u32x4_t *>(table)[threadIdx.x];
+    if (threadIdx.x < kBayerTableBytes / 16) reinterpret_cast<u32x4 *>(lds)[threadIdx.x] = reinterpret_cast<const u32x4 *>(table)[threadIdx.x];
     const int W = a.W, H = a.H;
     const int y0 = band * kBayerBandRows, y1 = min(y0 + kBayerBandRows, H);
     const int ylo = max(y0 - R, 0), yhi = min(y1 + R, H);   // staged rows [ylo, yhi): reflect-101 maps rows -R .. -1 and H .. H + R - 1 into them
@@ -223,7 +223,7 @@ __device__ __forceinline__ void demosaic_band_table(const BayerArgs &a, const ui
                 p[k][j] = r[x < 0 ? -x : x];
             }
             if (aligned && x0 + kRun <= W) {
-                const u32x4_t v = *reinterpret_cast<const u32x4_t *>(r + x0);
+                const u32x4 v = *reinterpret_cast<const u32x4 *>(r + x0);
 #pragma unroll
                 for (int j = 0; j < kRun; j++) p[k][j + R] = (v[j >> 2] >> (8 * (j & 3))) & 0xffu;
             } else {

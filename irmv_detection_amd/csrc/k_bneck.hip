@@ -25,8 +25,6 @@
 // (tests/test_gpu_engine.py::test_single_frame_bottleneck_kernels_are_bitwise_the_layers).
 #include "irmv_common.hpp"
 
-#include <mutex>
-
 namespace irmv {
 
 namespace {
@@ -36,9 +34,6 @@ constexpr int B2W = BT + 2, B2N = B2W * B2W;   // m.cv1 output region (halo 1): 
 constexpr int B3N = BT * BT;                   // the tile: 64 pixels = 4 MFMA tiles
 constexpr int BPS = 160;                       // bytes per pixel of a 64-channel plane: 128 + 32 of padding (16 consecutive pixels
                                                // x 2 lane groups of a ds_read_b128 hit 16 distinct 16-byte slots of the 256-byte bank window)
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4 ld16g(const half_t *p) { return *reinterpret_cast<const u32x4 *>(p); }
-__device__ __forceinline__ u32x4 keep16(bool c, u32x4 v) { return c ? v : (u32x4){0u, 0u, 0u, 0u}; }
 }  // namespace
 
 // MODE 0 = A, 1 = B.  KS2 = k-steps of cv2 (mode B: 6 for an n = 1 block, 8 for n = 2; mode A: unused).
@@ -75,7 +70,7 @@ __global__ __launch_bounds__(512) void bneck64_kernel(BneckArgs a)
         const int ly = px / B1W, lx = px - ly * B1W;
         const int gy = oy0 - 2 + ly, gx = ox0 - 2 + lx;
         const bool in = e < B1N * 8 && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-        v[i] = ld16g(a.yin + ((size_t)(b * H + (in ? gy : 0)) * W + (in ? gx : 0)) * a.yin_ld + q * 8);
+        v[i] = ld16(a.yin + ((size_t)(b * H + (in ? gy : 0)) * W + (in ? gx : 0)) * a.yin_ld + q * 8);
     }
     const int tpx = tid >> 3, tq = tid & 7;                  // (512 pieces per tile plane: one per thread)
     const int tgy = oy0 + (tpx >> 3), tgx = ox0 + (tpx & 7);
@@ -83,7 +78,7 @@ __global__ __launch_bounds__(512) void bneck64_kernel(BneckArgs a)
     if constexpr (NEXTRA > 0) {
 #pragma unroll
         for (int j = 0; j < NEXTRA; j++)
-            x[j] = ld16g(a.cat + ((size_t)(b * H + (tin ? tgy : 0)) * W + (tin ? tgx : 0)) * a.cat_ld + j * 64 + tq * 8);
+            x[j] = ld16(a.cat + ((size_t)(b * H + (tin ? tgy : 0)) * W + (tin ? tgx : 0)) * a.cat_ld + j * 64 + tq * 8);
     }
     __builtin_amdgcn_sched_barrier(0);
     half8 W1[18], W2[18], W3[MODE == 1 ? KS2 : 1];
@@ -117,11 +112,11 @@ __global__ __launch_bounds__(512) void bneck64_kernel(BneckArgs a)
             const int e = tid + i * 512, px = e >> 3, q = e & 7;
             const int ly = px / B1W, lx = px - ly * B1W;
             const int gy = oy0 - 2 + ly, gx = ox0 - 2 + lx;
-            if (e < B1N * 8) *reinterpret_cast<u32x4 *>(s_in + px * BPS + q * 16) = keep16((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W, v[i]);
+            if (e < B1N * 8) *reinterpret_cast<u32x4 *>(s_in + px * BPS + q * 16) = keep_if((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W, v[i]);
         }
         if constexpr (NEXTRA > 0) {
 #pragma unroll
-            for (int j = 0; j < NEXTRA; j++) *reinterpret_cast<u32x4 *>(s_y0 + j * (B3N * BPS) + tpx * BPS + tq * 16) = keep16(tin, x[j]);
+            for (int j = 0; j < NEXTRA; j++) *reinterpret_cast<u32x4 *>(s_y0 + j * (B3N * BPS) + tpx * BPS + tq * 16) = keep_if(tin, x[j]);
         }
     }
     __syncthreads();
@@ -256,25 +251,14 @@ __global__ __launch_bounds__(512) void bneck64_kernel(BneckArgs a)
 
 size_t bneck64_lds_bytes(int mode, int ks2) { return (size_t)(B1N + B2N + B3N) * BPS + (mode == 1 ? (size_t)(ks2 / 2 - 2) * B3N * BPS : 0); }
 
-static std::mutex g_bneck_attr_mu;
-
 bool launch_bneck64(int mode, int ks2, bool shortcut, const BneckArgs &a, int batch, hipStream_t s)
 {
     const dim3 grid(a.tiles_x * a.tiles_y * batch), block(512);
     const size_t lds = bneck64_lds_bytes(mode, ks2);
-#define IRMV_BNECK(MODE_, KS_, SC_)                                                                                 \
-    if (mode == MODE_ && (MODE_ == 0 || ks2 == KS_) && shortcut == SC_) {                                            \
-        static unsigned long long attr_done = 0;                                                                     \
-        int dev = 0; (void)hipGetDevice(&dev);                                                                       \
-        {   /* per device, once, and nobody launches before the limit is raised */                                   \
-            std::lock_guard<std::mutex> lk(g_bneck_attr_mu);                                                         \
-            if (!(attr_done & (1ull << (dev & 63)))) {                                                               \
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(bneck64_kernel<MODE_, KS_, SC_>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); \
-                attr_done |= 1ull << (dev & 63);                                                                     \
-            }                                                                                                        \
-        }                                                                                                            \
-        hipLaunchKernelGGL((bneck64_kernel<MODE_, KS_, SC_>), grid, block, lds, s, a);                               \
-        return true;                                                                                                 \
+#define IRMV_BNECK(MODE_, KS_, SC_)                                                    \
+    if (mode == MODE_ && (MODE_ == 0 || ks2 == KS_) && shortcut == SC_) {               \
+        launch_lds<bneck64_kernel<MODE_, KS_, SC_>>(grid, block, lds, 96 * 1024, s, a); \
+        return true;                                                                    \
     }
     IRMV_BNECK(0, 6, true) IRMV_BNECK(0, 6, false)
     IRMV_BNECK(1, 6, true) IRMV_BNECK(1, 6, false) IRMV_BNECK(1, 8, true) IRMV_BNECK(1, 8, false)

@@ -39,8 +39,6 @@
 // arithmetic for the final.  A column of an MFMA does not depend on its neighbours, so which pixels share a tile is free.
 #include "irmv_common.hpp"
 
-#include <mutex>
-
 namespace irmv {
 
 namespace {
@@ -176,7 +174,7 @@ __global__ __launch_bounds__(KPT ? GNTK : GNT) void box_gather_kernel(BoxGatherA
     auto to_mfma_lanes = [&](half8 (&row)[5]) {
 #pragma unroll
         for (int j = 0; j < 5; j++) {
-            u32x4_t v = __builtin_bit_cast(u32x4_t, row[j]);
+            u32x4 v = __builtin_bit_cast(u32x4, row[j]);
 #pragma unroll
             for (int d = 0; d < 4; d++) v[d] = (unsigned int)__builtin_amdgcn_ds_bpermute(from, (int)v[d]);
             row[j] = __builtin_bit_cast(half8, v);
@@ -425,29 +423,20 @@ __global__ __launch_bounds__(KPT ? GNTK : GNT) void box_gather_kernel(BoxGatherA
 
 bool box_gather_eligible(int cin) { return cin == 64 || cin == 128 || cin == 256; }
 
+template <int KC>
+static void launch_box_gather_inst(const BoxGatherArgs &a, int batch, int grid, hipStream_t s)
+{
+    if (a.kw0 != nullptr) launch_lds<box_gather_kernel<KC, true>>(dim3(grid), dim3(GNTK), GLDSK, GLDSK, s, a, batch);   // the keypoint branch rides along: a fourth wave per group and its planes
+    else launch_lds<box_gather_kernel<KC, false>>(dim3(grid), dim3(GNT), GLDS, GLDS, s, a, batch);
+}
+
 bool launch_box_gather(const BoxGatherArgs &a, int cin, int batch, int grid, hipStream_t s)
 {
     if (batch < 1 || batch > GMAXB || grid < 1) return false;
-    static std::mutex mu;
-    static unsigned long long done[6] = {0, 0, 0, 0, 0, 0};   // per instantiation: the devices whose dynamic-LDS limit has been raised
-    const bool kpt = a.kw0 != nullptr;   // the keypoint branch rides along: a fourth wave per group and its planes
-    const size_t lds = kpt ? GLDSK : GLDS;
-    auto go = [&](auto kernel, unsigned long long &mask) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            if (!(mask >> (dev & 63) & 1ull)) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                mask |= 1ull << (dev & 63);
-            }
-        }
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kpt ? GNTK : GNT), lds, s, a, batch);
-    };
     switch (cin) {
-    case 64: if (kpt) go(box_gather_kernel<1, true>, done[3]); else go(box_gather_kernel<1, false>, done[0]); return true;
-    case 128: if (kpt) go(box_gather_kernel<2, true>, done[4]); else go(box_gather_kernel<2, false>, done[1]); return true;
-    case 256: if (kpt) go(box_gather_kernel<4, true>, done[5]); else go(box_gather_kernel<4, false>, done[2]); return true;
+    case 64: launch_box_gather_inst<1>(a, batch, grid, s); return true;
+    case 128: launch_box_gather_inst<2>(a, batch, grid, s); return true;
+    case 256: launch_box_gather_inst<4>(a, batch, grid, s); return true;
     default: return false;
     }
 }

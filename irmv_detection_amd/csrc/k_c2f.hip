@@ -14,7 +14,6 @@
 #include "irmv_common.hpp"
 
 #include <cstdlib>
-#include <mutex>
 
 namespace irmv {
 
@@ -29,13 +28,9 @@ constexpr int HP = 32;                    // bytes per pixel of the 16-channel p
 __device__ __forceinline__ f32x4 bias4(const float *b) { return (f32x4){b[0], b[1], b[2], b[3]}; }
 
 // Global-memory B fragments are loaded UNCONDITIONALLY from a clamped (always valid) address and zeroed by a select
-// afterwards, as four dwords: behind `if (inside) B = load` the compiler builds the zero / loaded merge per 16-bit
-// element and waits for every load where it is issued (vmcnt(0) after each pair), which serialises the round trips the
-// prefetch below is there to overlap.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4 ld16(const half_t *p) { return *reinterpret_cast<const u32x4 *>(p); }
-__device__ __forceinline__ u32x4 keep_if(bool c, u32x4 v) { return c ? v : (u32x4){0u, 0u, 0u, 0u}; }
-__device__ __forceinline__ half8 as_h8(u32x4 v) { return __builtin_bit_cast(half8, v); }
+// afterwards, as four dwords (ld16 / keep_if, irmv_common.hpp): behind `if (inside) B = load` the compiler builds the zero /
+// loaded merge per 16-bit element and waits for every load where it is issued (vmcnt(0) after each pair), which serialises
+// the round trips the prefetch below is there to overlap.
 
 // MFMA tiles of an RH x RW pixel region (RW = 16 + 2 or 16 + 4): tile t < RH is columns 0 .. 15 of row t, the tiles after
 // those walk the remaining RW - 16 columns top to bottom, 16 pixels each.  Same tile count as a flat walk in runs of 16, but
@@ -246,11 +241,9 @@ __global__ __launch_bounds__(256) void c2f2_kernel(C2fArgs a, int batch, int xcd
     }
 }
 
-static int c2f_xcd_order() { return xcd_image_order(); }
-
 void launch_c2f2(const C2fArgs &a, int batch, hipStream_t s)
 {
-    hipLaunchKernelGGL(c2f2_kernel, dim3(a.tiles_x * a.tiles_y * batch), dim3(256), 0, s, a, batch, c2f_xcd_order());
+    hipLaunchKernelGGL(c2f2_kernel, dim3(a.tiles_x * a.tiles_y * batch), dim3(256), 0, s, a, batch, xcd_image_order());
 }
 
 
@@ -595,29 +588,18 @@ __global__ __launch_bounds__(256) void c2f32_kernel(C2f32Args a, int batch, int 
     }
 }
 
-static std::mutex g_c2f_attr_mu;
-
 size_t c2f32_lds_bytes(int mode) { return (size_t)(R1N + R2N + (mode == 1 ? 0 : R3N) + (mode == 0 ? R3N : 0)) * PS; }
 
 bool launch_c2f32(int mode, bool shortcut, const C2f32Args &a, int batch, hipStream_t s)
 {
     const int ks1 = a.cin1 / 32;
     const dim3 grid(a.tiles_x * a.tiles_y * batch), block(256);
-    const int xcd = c2f_xcd_order();
+    const int xcd = xcd_image_order();
     const size_t lds = c2f32_lds_bytes(mode);
-#define IRMV_C2F32(MODE_, KS_, SC_)                                                                               \
-    if (mode == MODE_ && (MODE_ == 2 || ks1 == KS_) && shortcut == SC_) {                                          \
-        static unsigned long long attr_done = 0;                                                                   \
-        int dev = 0; (void)hipGetDevice(&dev);                                                                     \
-        {   /* per device, once, and nobody launches before the limit is raised */                                 \
-            std::lock_guard<std::mutex> lk(g_c2f_attr_mu);                                                         \
-            if (!(attr_done & (1ull << (dev & 63)))) {                                                             \
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(c2f32_kernel<MODE_, KS_, SC_>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); \
-                attr_done |= 1ull << (dev & 63);                                                                   \
-            }                                                                                                      \
-        }                                                                                                          \
-        hipLaunchKernelGGL((c2f32_kernel<MODE_, KS_, SC_>), grid, block, lds, s, a, batch, xcd);                   \
-        return true;                                                                                               \
+#define IRMV_C2F32(MODE_, KS_, SC_)                                                              \
+    if (mode == MODE_ && (MODE_ == 2 || ks1 == KS_) && shortcut == SC_) {                         \
+        launch_lds<c2f32_kernel<MODE_, KS_, SC_>>(grid, block, lds, 96 * 1024, s, a, batch, xcd); \
+        return true;                                                                              \
     }
     IRMV_C2F32(0, 2, true) IRMV_C2F32(0, 2, false) IRMV_C2F32(0, 4, false) IRMV_C2F32(0, 6, false) IRMV_C2F32(0, 6, true) IRMV_C2F32(0, 4, true)
     IRMV_C2F32(1, 2, true) IRMV_C2F32(1, 2, false) IRMV_C2F32(1, 4, true) IRMV_C2F32(1, 6, true)

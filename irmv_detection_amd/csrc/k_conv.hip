@@ -19,7 +19,6 @@
 #include <cstdio>
 #include <cstring>
 #include <iterator>
-#include <mutex>
 #include <type_traits>
 
 namespace irmv {
@@ -122,7 +121,6 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a, int wg_x, int 
     // k-step, for the loads it has just issued -- one exposed memory round trip per k-step.
     // 1x1 convs need no select at all: there is no padding, a row past M fills a B column whose results are never stored,
     // and K positions past Cin meet zero weights (pack_conv) with finite activations.
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     half8 Ab[PF][NT];
     u32x4 Bb[PF][MT];
     bool Bz[PF][MT];   // fragment must read as zero
@@ -432,68 +430,64 @@ bool launch_conv_direct_multi(const ConvCfg &c, const ConvArgs *a, int n, hipStr
 // profiles/r02_mfma.json of the round-1 layout), whereas 2 x 80 B = 40 dwords has period 8 again.
 constexpr int pix_stride(int stride) { return stride == 2 ? 80 : 96; }
 
-// hipFuncSetAttribute is per device: remember, per kernel, on which devices it has been applied.  Engines may be created
-// and run from several threads (one per GPU): the check, the attribute call and the flag update are one critical section,
-// so no thread launches before the limit is raised.  (The mutex is taken on every launch CALL -- engine creation, tuning,
-// graph capture, eager profiling; a captured step is replayed without any of this code.)
-static std::mutex g_attr_mu;
-template <class F>
-static void once_per_device(unsigned long long &mask, F set_attribute)
-{
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    std::lock_guard<std::mutex> lk(g_attr_mu);
-    if (mask & bit) return;
-    set_attribute();
-    mask |= bit;
-}
-
 // ---------------------------------------------------------------------------
 // Pointwise (1x1) convolution as a persistent, software-pipelined GEMM.
 //
 // The direct kernel above gives a wave ONE pixel tile per lifetime: index arithmetic, a cold first load, 4..16 k-steps,
 // a SiLU epilogue as long as the matrix work (K <= 512), exit -- its waves sit in waits 40 % and issue stalls 40 % of
 // their cycles (profiles/r02_mfma.json) and it reaches 0.26-0.34 of the HBM line its arithmetic intensity puts it under.
-// Here a workgroup keeps the weights of its 64 output channels in LDS (NT x KS KiB, fragment order: conflict-free
-// ds_read_b128) and its four waves walk pixel tiles of 32 pixels with a stride of the whole grid.  Activations go
-// straight from memory into B fragments, and every fragment register is re-loaded for the wave's NEXT tile right after
-// the MFMAs that consumed it: a tile's loads are in flight for a whole tile time, under the MFMAs and the SiLU epilogue
-// of the tile before.  Same operands, same k order as the direct kernel -> bit-identical, so the autotuner may pick either.
+// Here a workgroup keeps the weights of NBW blocks of 64 output channels in LDS (NBW x NT x KS KiB, fragment order:
+// conflict-free ds_read_b128) and its waves walk pixel tiles of 32 pixels.  Activations go straight from memory into B
+// fragments, and every fragment register is re-loaded for the wave's NEXT tile right after the last MFMAs that consume
+// it: a tile's loads are in flight for a whole tile time, under the MFMAs and the SiLU epilogue of the tile before.
+//   NBW = 1: four waves; every 64-channel block has workgroups of its own, so a layer with 128 / 256 output channels reads
+//   its input two / four times (from L2 the second time on, but every read is a request the CU's vector-memory path has to
+//   carry).  The bias of the block stays in registers.
+//   NBW = 2, 4: ONE 8-wave workgroup keeps the weights of NBW blocks (up to 128 KiB, one workgroup per CU) and a wave runs
+//   the B fragments of its pixel tile -- loaded ONCE -- against all of them, block after block; the fragments of the wave's
+//   next tile are requested during the last block's pass.  The biases live in LDS behind the weights.
+// Same operands, same k order per output channel as the direct kernel -> bit-identical, so the autotuner may pick any.
 // ---------------------------------------------------------------------------
-template <int KS>
-__global__ __launch_bounds__(256) void conv1x1_pw_kernel(ConvArgs a, int tiles_total, int wg_per_nblock)
+template <int KS, int NBW>
+__global__ __launch_bounds__(NBW > 1 ? 512 : 256) void conv1x1_pw_kernel(ConvArgs a, int wg_per_group)
 {
-    constexpr int MT = 2, NT = 4;
+    constexpr int MT = 2, NT = 4, NWV = NBW > 1 ? 8 : 4, NTH = 64 * NWV;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    half8 *s_w = reinterpret_cast<half8 *>(smem);   // [NT][KS][64 lanes]
+    half8 *s_w = reinterpret_cast<half8 *>(smem);                                   // [NBW][NT][KS][64 lanes]
+    float *s_bias = reinterpret_cast<float *>(smem + (size_t)NBW * NT * KS * 1024); // NBW > 1: [NBW][64]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, r = lane & 15;
-    const int nblk = blockIdx.y;
-    // weights -> LDS: every piece of a thread is loaded before the first is stored (NT * KS * 64 / 256 = KS pieces; a
-    // load -> store loop serialises KS memory round trips at the head of every workgroup)
-    half8 wreg[KS];
+    const int nblk0 = blockIdx.y * NBW;
+    // weights -> LDS: every piece of a thread is loaded before the first is stored (a load -> store loop serialises WPT
+    // memory round trips at the head of every workgroup)
+    constexpr int WALL = NBW * NT * KS * 64, WPT = WALL / NTH;                      // half8 pieces, per thread (<= 16)
+    static_assert(WALL % NTH == 0, "every thread stages the same number of pieces");
+    half8 wreg[WPT];
     {
-        const half8 *wsrc = reinterpret_cast<const half8 *>(a.w) + (size_t)nblk * NT * KS * 64;
+        const half8 *wsrc = reinterpret_cast<const half8 *>(a.w) + (size_t)nblk0 * NT * KS * 64;
 #pragma unroll
-        for (int i = 0; i < KS; i++) wreg[i] = wsrc[tid + i * 256];
+        for (int i = 0; i < WPT; i++) wreg[i] = wsrc[tid + i * NTH];
+    }
+    // the two bias placements are measured choices: one block's 16 values per lane fit the registers of the 4-wave form
+    float bias[2][8];
+    if constexpr (NBW == 1) {
+#pragma unroll
+        for (int u = 0; u < 2; u++)
+#pragma unroll
+            for (int i = 0; i < 8; i++) bias[u][i] = a.bias[(nblk0 * 2 + u) * 32 + g * 8 + i];
+    } else {
+        if (tid < NBW * 64) s_bias[tid] = a.bias[nblk0 * 64 + tid];
     }
     const int HWo = a.Hout * a.Wout;
     const int H0 = a.Hin >> a.s0.shift, W0 = a.Win >> a.s0.shift, H1 = a.Hin >> a.s1.shift, W1 = a.Win >> a.s1.shift;
     const bool flat = a.s0.shift == 0 && a.s1.shift == 0;
-    float bias[2][8];
-#pragma unroll
-    for (int u = 0; u < 2; u++)
-#pragma unroll
-        for (int i = 0; i < 8; i++) bias[u][i] = a.bias[(nblk * 2 + u) * 32 + g * 8 + i];
 
     // This wave's share of the image: a CONTIGUOUS range of 16-pixel units, the same number for every wave of the launch
     // give or take one (a fixed stride of 32-pixel tiles left a quarter of the waves with a fourth tile where the others
     // had three: the launch lasted as long as they did).  The range is walked in 32-pixel tiles; an odd unit at its end
     // is a half tile with its own copy of the tile body (MT = 1: no loads, MFMAs or epilogue for the missing half).
-    const int units = (a.M + 15) >> 4, nw = wg_per_nblock * 4, wv = blockIdx.x * 4 + wave;
+    const int units = (a.M + 15) >> 4, nw = wg_per_group * NWV, wv = blockIdx.x * NWV + wave;
     const int u0 = (int)((long long)wv * units / nw), u1 = (int)((long long)(wv + 1) * units / nw);
-    (void)tiles_total;
     // unit ub .. ub + MT - 1: source pointers of both K segments (a unit past this wave's range reads pixel 0: never stored)
     const half_t *p0[MT], *p1[MT];
     bool mv[MT];
@@ -531,133 +525,10 @@ __global__ __launch_bounds__(256) void conv1x1_pw_kernel(ConvArgs a, int tiles_t
 #pragma unroll
         for (int mt = 0; mt < MT; mt++) B[mt][ks] = load_b(mt, ks);
 #pragma unroll
-    for (int i = 0; i < KS; i++) s_w[tid + i * 256] = wreg[i];
-    __syncthreads();                                             // weights staged
+    for (int i = 0; i < WPT; i++) s_w[tid + i * NTH] = wreg[i];
+    __syncthreads();                                             // weights (and the LDS biases) staged
     half_t *out = static_cast<half_t *>(a.out);
     // one tile: MTA active 16-pixel units; PRE: re-load every consumed fragment for the tile that follows
-    auto run_tile = [&](auto mta_c, auto pre_c, int ub) {
-        constexpr int MTA = decltype(mta_c)::value;
-        constexpr bool PRE = decltype(pre_c)::value;
-        size_t m_cur[MTA];
-        bool mv_cur[MTA];
-#pragma unroll
-        for (int mt = 0; mt < MTA; mt++) { m_cur[mt] = (size_t)(ub + mt) * 16 + r; mv_cur[mt] = mv[mt]; }
-        if constexpr (PRE) tile_ptrs(ub + MT);                   // from here p0 / p1 / mv describe the NEXT tile
-        f32x4 acc[MTA][NT];   // start at the bias: tile 2 u + h, register i <-> channel u * 32 + g * 8 + 4 h + i
-#pragma unroll
-        for (int mt = 0; mt < MTA; mt++)
-#pragma unroll
-            for (int nt = 0; nt < NT; nt++) acc[mt][nt] = (f32x4){bias[nt >> 1][(nt & 1) * 4 + 0], bias[nt >> 1][(nt & 1) * 4 + 1], bias[nt >> 1][(nt & 1) * 4 + 2], bias[nt >> 1][(nt & 1) * 4 + 3]};
-        // A fragments from LDS, double-buffered one k-step ahead; the scheduling barrier keeps the compiler from hoisting
-        // all KS x NT fragment reads to the top of the unrolled loop (256 VGPRs and spills without it)
-        half8 A[2][NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; nt++) A[0][nt] = s_w[(nt * KS) * 64 + lane];
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++) {
-            if (ks + 1 < KS) {
-#pragma unroll
-                for (int nt = 0; nt < NT; nt++) A[(ks + 1) & 1][nt] = s_w[(nt * KS + ks + 1) * 64 + lane];
-            }
-#pragma unroll
-            for (int mt = 0; mt < MTA; mt++) {
-#pragma unroll
-                for (int nt = 0; nt < NT; nt++) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[ks & 1][nt], B[mt][ks], acc[mt][nt], 0, 0, 0);
-                if constexpr (PRE) B[mt][ks] = load_b(mt, ks);   // consumed: fetch the next tile's fragment into the same registers
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // epilogue of the direct kernel's paired-tile path: lane g holds channels u * 32 + g * 8 + [0, 8) of its pixel
-#pragma unroll
-        for (int mt = 0; mt < MTA; mt++) {
-            if (!mv_cur[mt]) continue;
-#pragma unroll
-            for (int u = 0; u < 2; u++) {
-                float vals[8];
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    vals[i] = acc[mt][2 * u][i];
-                    vals[4 + i] = acc[mt][2 * u + 1][i];
-                }
-                const half8 o = silu_pack8(vals[0], vals[1], vals[2], vals[3], vals[4], vals[5], vals[6], vals[7]);
-                *reinterpret_cast<half8 *>(out + m_cur[mt] * a.out_ld + (nblk * 2 + u) * 32 + g * 8) = o;
-            }
-        }
-    };
-    int ub = u0;
-    for (; ub + MT <= u1; ub += MT) run_tile(std::integral_constant<int, MT>{}, std::true_type{}, ub);
-    if (ub < u1) run_tile(std::integral_constant<int, 1>{}, std::false_type{}, ub);
-}
-
-// Pointwise kernel, several output-channel blocks per workgroup (NBW blocks of 64 channels): the kernel above gives every
-// 64-channel block its own workgroups, so a layer with 128 / 256 output channels reads its input two / four times (from L2
-// the second time on, but every read is a request the CU's vector-memory path has to carry).  Here ONE 8-wave workgroup
-// keeps the weights of NBW blocks in LDS (NBW x KS x 4 KiB: up to 128 KiB, one workgroup per CU) and a wave runs the B
-// fragments of its pixel tile -- loaded ONCE -- against all of them, block after block; the fragments of the wave's next
-// tile are requested during the last block's pass.  Per output channel the k order is the kernel's above -> bit-identical.
-template <int KS, int NBW>
-__global__ __launch_bounds__(512) void conv1x1_pwn_kernel(ConvArgs a, int wg_per_group)
-{
-    constexpr int MT = 2, NT = 4, NTH = 512;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    half8 *s_w = reinterpret_cast<half8 *>(smem);                                   // [NBW][NT][KS][64 lanes]
-    float *s_bias = reinterpret_cast<float *>(smem + (size_t)NBW * NT * KS * 1024); // [NBW][64]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int g = lane >> 4, r = lane & 15;
-    const int nblk0 = blockIdx.y * NBW;
-    constexpr int WALL = NBW * NT * KS * 64, WPT = (WALL + NTH - 1) / NTH;          // half8 pieces, per thread (<= 16)
-    half8 wreg[WPT];
-    {
-        const half8 *wsrc = reinterpret_cast<const half8 *>(a.w) + (size_t)nblk0 * NT * KS * 64;
-#pragma unroll
-        for (int i = 0; i < WPT; i++) {
-            const int e = tid + i * NTH;
-            wreg[i] = wsrc[e < WALL ? e : WALL - 1];
-        }
-    }
-    if (tid < NBW * 64) s_bias[tid] = a.bias[nblk0 * 64 + tid];
-    const int HWo = a.Hout * a.Wout;
-    const int H0 = a.Hin >> a.s0.shift, W0 = a.Win >> a.s0.shift, H1 = a.Hin >> a.s1.shift, W1 = a.Win >> a.s1.shift;
-    const bool flat = a.s0.shift == 0 && a.s1.shift == 0;
-    const int units = (a.M + 15) >> 4, nw = wg_per_group * 8, wv = blockIdx.x * 8 + wave;
-    const int u0 = (int)((long long)wv * units / nw), u1 = (int)((long long)(wv + 1) * units / nw);
-    const half_t *p0[MT], *p1[MT];
-    bool mv[MT];
-    auto tile_ptrs = [&](int ub) {
-#pragma unroll
-        for (int mt = 0; mt < MT; mt++) {
-            const int m = (ub + mt) * 16 + r;
-            mv[mt] = ub + mt < u1 && m < a.M;
-            const int mm = mv[mt] ? m : 0;
-            if (flat) {   // no half-resolution segment (every layer but the neck's upsample + concat readers): pixel m of the output
-                          // is pixel m of both segments -- no (image, row, column) split: two integer divisions per unit less
-                p0[mt] = a.s0.p + (size_t)mm * a.s0.ld + 8 * g;
-                p1[mt] = a.s1.p + (size_t)mm * a.s1.ld + 8 * g - a.s0.C;
-            } else {
-                const int b = mm / HWo, rem = mm - b * HWo;
-                const int oy = rem / a.Wout, ox = rem - oy * a.Wout;
-                p0[mt] = a.s0.p + ((size_t)(b * H0 + (oy >> a.s0.shift)) * W0 + (ox >> a.s0.shift)) * a.s0.ld + 8 * g;
-                p1[mt] = a.s1.p + ((size_t)(b * H1 + (oy >> a.s1.shift)) * W1 + (ox >> a.s1.shift)) * a.s1.ld + 8 * g - a.s0.C;
-            }
-        }
-    };
-    auto load_b = [&](int mt, int ks) -> half8 {   // unconditional (see conv1x1_pw_kernel)
-        const int c = ks * 32;
-        return *reinterpret_cast<const half8 *>((c < a.s0.C ? p0[mt] : p1[mt]) + c);
-    };
-    half8 B[MT][KS];
-    tile_ptrs(u0);
-#pragma unroll
-    for (int ks = 0; ks < KS; ks++)
-#pragma unroll
-        for (int mt = 0; mt < MT; mt++) B[mt][ks] = load_b(mt, ks);
-#pragma unroll
-    for (int i = 0; i < WPT; i++) {
-        const int e = tid + i * NTH;
-        if (e < WALL) s_w[e] = wreg[i];
-    }
-    __syncthreads();                                             // weights and biases staged
-    half_t *out = static_cast<half_t *>(a.out);
     auto run_tile = [&](auto mta_c, auto pre_c, int ub) {
         constexpr int MTA = decltype(mta_c)::value;
         constexpr bool PRE = decltype(pre_c)::value;
@@ -669,13 +540,17 @@ __global__ __launch_bounds__(512) void conv1x1_pwn_kernel(ConvArgs a, int wg_per
 #pragma unroll
         for (int nb = 0; nb < NBW; nb++) {
             const half8 *s_wb = s_w + nb * (NT * KS * 64) + lane;
-            f32x4 acc[MTA][NT];   // start at the block's bias (LDS): tile 2 u + h, register i <-> channel u * 32 + g * 8 + 4 h + i
+            f32x4 acc[MTA][NT];   // start at the block's bias: tile 2 u + h, register i <-> channel u * 32 + g * 8 + 4 h + i
 #pragma unroll
             for (int nt = 0; nt < NT; nt++) {
-                const f32x4 b = *reinterpret_cast<const f32x4 *>(s_bias + nb * 64 + (nt >> 1) * 32 + g * 8 + (nt & 1) * 4);
+                f32x4 b;
+                if constexpr (NBW == 1) b = (f32x4){bias[nt >> 1][(nt & 1) * 4 + 0], bias[nt >> 1][(nt & 1) * 4 + 1], bias[nt >> 1][(nt & 1) * 4 + 2], bias[nt >> 1][(nt & 1) * 4 + 3]};
+                else b = *reinterpret_cast<const f32x4 *>(s_bias + nb * 64 + (nt >> 1) * 32 + g * 8 + (nt & 1) * 4);
 #pragma unroll
                 for (int mt = 0; mt < MTA; mt++) acc[mt][nt] = b;
             }
+            // A fragments from LDS, double-buffered one k-step ahead; the scheduling barrier keeps the compiler from hoisting
+            // all KS x NT fragment reads to the top of the unrolled loop (256 VGPRs and spills without it)
             half8 A[2][NT];
 #pragma unroll
             for (int nt = 0; nt < NT; nt++) A[0][nt] = s_wb[(nt * KS) * 64];
@@ -689,10 +564,11 @@ __global__ __launch_bounds__(512) void conv1x1_pwn_kernel(ConvArgs a, int wg_per
                 for (int mt = 0; mt < MTA; mt++) {
 #pragma unroll
                     for (int nt = 0; nt < NT; nt++) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[ks & 1][nt], B[mt][ks], acc[mt][nt], 0, 0, 0);
-                    if constexpr (PRE) if (nb == NBW - 1) B[mt][ks] = load_b(mt, ks);   // last pass over this tile's fragments: fetch the next tile's
+                    if constexpr (PRE) if (nb == NBW - 1) B[mt][ks] = load_b(mt, ks);   // last pass over this tile's fragments: fetch the next tile's into the same registers
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
+            // epilogue of the direct kernel's paired-tile path: lane g holds channels u * 32 + g * 8 + [0, 8) of its pixel
 #pragma unroll
             for (int mt = 0; mt < MTA; mt++) {
                 if (!mv_cur[mt]) continue;
@@ -723,59 +599,49 @@ bool conv_pw_eligible(const ConvCfg &c, const ConvArgs &a)
            a.res == nullptr && a.n2 == 0;
 }
 
-template <int KS>
+template <int KS, int NBW>
 static void launch_pw_inst(const ConvLaunch &l, hipStream_t s)
 {
-    static unsigned long long attr_done = 0;
-    once_per_device(attr_done, [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_pw_kernel<KS>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    });
-    const ConvArgs &a = l.a;
-    const int tiles_total = (a.M + 31) / 32, nblocks = a.cout_pad / 64;
-    // ~2 workgroups per CU in total, never more workgroups than there are 4-tile rounds
-    int wg = (tiles_total + 3) / 4;
-    const int cap = (512 + nblocks - 1) / nblocks;
-    if (wg > cap) wg = cap;
-    if (wg < 1) wg = 1;
-    hipLaunchKernelGGL((conv1x1_pw_kernel<KS>), dim3(wg, nblocks), dim3(256), l.g.bytes, s, a, tiles_total, wg);
-}
-
-// several output-channel blocks per workgroup (NBW): the input is read nblocks / NBW times
-template <int KS, int NBW>
-static void launch_pwn_inst(const ConvLaunch &l, hipStream_t s)
-{
-    static unsigned long long attr_done = 0;
-    // per DEVICE (engines on several GPUs are created from concurrent threads): workgroups a CU holds (registers and LDS)
-    // and the device's CU count size the grid to one round.  Element `dev` is written once, inside the critical section of
-    // once_per_device, before any launch on that device leaves it.
-    static int per_cu[64], cus[64];
+    constexpr auto kernel = conv1x1_pw_kernel<KS, NBW>;
     const ConvArgs &a = l.a;
     const size_t lds = l.g.bytes;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev &= 63;
-    once_per_device(attr_done, [lds, dev] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_pwn_kernel<KS, NBW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        int nb = 0, nc = 0;
-        per_cu[dev] = 1; cus[dev] = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(conv1x1_pwn_kernel<KS, NBW>), 512, lds) == hipSuccess && nb >= 1) per_cu[dev] = nb > 2 ? 2 : nb;
-        if (hipDeviceGetAttribute(&nc, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && nc > 0) cus[dev] = nc;
-    });
-    const int groups = a.cout_pad / 64 / NBW;
-    const int units = (a.M + 15) / 16;
-    int wg = (cus[dev] * per_cu[dev] + groups - 1) / groups;     // the chip in one round ...
-    if (wg > (units + 7) / 8) wg = (units + 7) / 8;              // ... but a 16-pixel unit per wave at least (20 x 20 maps: more
-                                                                 // workgroups beat longer pipelines: 2 / 3 units per wave +7 / +25 %)
+    const int groups = a.cout_pad / 64 / NBW;   // workgroups side by side on the output channels
+    int wg;
+    if constexpr (NBW == 1) {
+        (void)raise_lds_limit<kernel>(96 * 1024);
+        // ~2 workgroups per CU in total, never more workgroups than there are 4-tile rounds
+        const int tiles_total = (a.M + 31) / 32;
+        wg = (tiles_total + 3) / 4;
+        const int cap = (512 + groups - 1) / groups;
+        if (wg > cap) wg = cap;
+    } else {
+        // per DEVICE (engines on several GPUs are created from concurrent threads): the workgroups the chip holds in one round
+        // -- those of a CU (registers and LDS; the query wants the raised limit) times the CUs -- kept with the grant
+        int round_wgs = 0;
+        (void)raise_lds_limit<kernel>(160 * 1024, round_wgs, [lds](int dev) {
+            int nb = 0, nc = 0, per_cu = 1, cus = 256;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(kernel), 512, lds) == hipSuccess && nb >= 1) per_cu = nb > 2 ? 2 : nb;
+            if (hipDeviceGetAttribute(&nc, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && nc > 0) cus = nc;
+            return cus * per_cu;
+        });
+        const int units = (a.M + 15) / 16;
+        wg = (round_wgs + groups - 1) / groups;                      // the chip in one round ...
+        if (wg > (units + 7) / 8) wg = (units + 7) / 8;              // ... but a 16-pixel unit per wave at least (20 x 20 maps: more
+                                                                     // workgroups beat longer pipelines: 2 / 3 units per wave +7 / +25 %)
+    }
     if (wg < 1) wg = 1;
-    hipLaunchKernelGGL((conv1x1_pwn_kernel<KS, NBW>), dim3(wg, groups), dim3(512), lds, s, a, wg);
+    hipLaunchKernelGGL(kernel, dim3(wg, groups), dim3(NBW > 1 ? 512 : 256), lds, s, a, wg);
 }
 
-// The pointwise family's variants: (k-steps, output-channel blocks per workgroup; 1 = the single-block kernel).  The
-// multi-block form keeps NBW x KS <= 32: <= 128 KiB of weights, <= 16 staging pieces per thread.
-static constexpr struct { int ksteps, nbw; ConvLauncher launch; } k_pw[] = {
-    {4, 1, launch_pw_inst<4>}, {6, 1, launch_pw_inst<6>}, {8, 1, launch_pw_inst<8>}, {12, 1, launch_pw_inst<12>}, {16, 1, launch_pw_inst<16>},
-    {4, 2, launch_pwn_inst<4, 2>}, {6, 2, launch_pwn_inst<6, 2>}, {8, 2, launch_pwn_inst<8, 2>}, {12, 2, launch_pwn_inst<12, 2>}, {16, 2, launch_pwn_inst<16, 2>},
-    {4, 4, launch_pwn_inst<4, 4>}, {6, 4, launch_pwn_inst<6, 4>}, {8, 4, launch_pwn_inst<8, 4>},
+// The pointwise family's variants: (k-steps, output-channel blocks per workgroup).  The multi-block forms keep
+// NBW x KS <= 32: <= 128 KiB of weights, <= 16 staging pieces per thread.
+struct PwVariant { int ksteps, nbw; ConvLauncher launch; };
+template <int KS, int NBW>
+constexpr PwVariant pw_variant() { return {KS, NBW, launch_pw_inst<KS, NBW>}; }
+static constexpr PwVariant k_pw[] = {
+    pw_variant<4, 1>(), pw_variant<6, 1>(), pw_variant<8, 1>(), pw_variant<12, 1>(), pw_variant<16, 1>(),
+    pw_variant<4, 2>(), pw_variant<6, 2>(), pw_variant<8, 2>(), pw_variant<12, 2>(), pw_variant<16, 2>(),
+    pw_variant<4, 4>(), pw_variant<6, 4>(), pw_variant<8, 4>(),
 };
 
 // cfg.ipw = NBW; g.bytes = the weight slabs (+ the multi-block form's NBW x 64 biases)
@@ -1530,16 +1396,12 @@ bool conv_lds_fits(const ConvArgs &a, const ConvWeights &w, int stride, int mt, 
 template <int STRIDE, int MT, int NT, bool TILE2D, int N2, int PF = 0, int CM = 0, int NWV = 4, int WR = 0, bool PP = false>
 static void launch_lds_inst(const ConvLaunch &l, hipStream_t s)
 {
-    static unsigned long long attr_done = 0;   // per instantiation: devices whose dynamic-LDS limit has been raised
-    once_per_device(attr_done, [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_lds_kernel<STRIDE, MT, NT, TILE2D, N2, PF, CM, NWV, WR, PP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
     const LdsGeom &g = l.g;
     const int groups = (l.batch + l.ipw - 1) / l.ipw;
     const int wg_tiles = PP ? (g.tiles_x * g.tiles_y + 1) / 2 : g.tiles_x * g.tiles_y;   // ping-pong: two tile positions per workgroup
     const int nblocks = l.a.cout_pad / (16 * NT);
-    hipLaunchKernelGGL((conv3x3_lds_kernel<STRIDE, MT, NT, TILE2D, N2, PF, CM, NWV, WR, PP>), dim3(wg_tiles * groups * nblocks), dim3(64 * NWV), g.bytes, s, l.a,
-                       l.w, g.tiles_x, g.tiles_y, g.twc_log2, g.patch_bytes, l.ipw, l.batch, nblocks, xcd_image_order() | (wres_stagger() << 1));
+    launch_lds<conv3x3_lds_kernel<STRIDE, MT, NT, TILE2D, N2, PF, CM, NWV, WR, PP>>(dim3(wg_tiles * groups * nblocks), dim3(64 * NWV), g.bytes, 160 * 1024, s, l.a,
+        l.w, g.tiles_x, g.tiles_y, g.twc_log2, g.patch_bytes, l.ipw, l.batch, nblocks, xcd_image_order() | (wres_stagger() << 1));
 }
 
 // Weights-resident variant: Cin = 64 -> 64 channels, stride 1.  ONE 8-wave workgroup per CU keeps the
@@ -1680,11 +1542,7 @@ const char *conv_cfg_name(const ConvCfg &c, char *buf, int n)
 template <int NT>
 static void launch_lds_multi_inst(const LdsMultiArgs &m, int total, size_t bytes, hipStream_t s)
 {
-    static unsigned long long attr_done = 0;
-    once_per_device(attr_done, [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_lds_multi<1, 1, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    hipLaunchKernelGGL((conv3x3_lds_multi<1, 1, NT>), dim3(total), dim3(256), bytes, s, m);
+    launch_lds<conv3x3_lds_multi<1, 1, NT>>(dim3(total), dim3(256), bytes, 160 * 1024, s, m);
 }
 static constexpr struct { int nt; void (*launch)(const LdsMultiArgs &, int, size_t, hipStream_t); } k_lds_multi[] = {
     {1, launch_lds_multi_inst<1>}, {2, launch_lds_multi_inst<2>}, {4, launch_lds_multi_inst<4>},
@@ -1735,8 +1593,8 @@ bool launch_conv_lds_multi(int nt, const ConvArgs *a, const ConvWeights *w, int 
 // are never NaN; of two zeros of different sign either may come out, which no later layer can tell apart.)
 __device__ __forceinline__ half8 hmax8(half8 a, half8 b)
 {
-    u32x4_t x = __builtin_bit_cast(u32x4_t, a);
-    const u32x4_t y = __builtin_bit_cast(u32x4_t, b);
+    u32x4 x = __builtin_bit_cast(u32x4, a);
+    const u32x4 y = __builtin_bit_cast(u32x4, b);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         unsigned int r;
@@ -1875,13 +1733,9 @@ void launch_sppf_pool(half_t *buf, int batch, int H, int W, int C, hipStream_t s
     const int cw = sppf_slab(batch, H, W, C);
     if (cw) {
         const size_t lds = (size_t)4 * H * W * cw * 2;
-        static unsigned long long attr_done = 0;
-        once_per_device(attr_done, [] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sppf_pool_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        });
         // 512 lanes: a slab's H * W * cw / 8 items (400 .. 1600 at a 640 net) take half the rounds of each of the three
         // barrier-separated passes, and the one workgroup a CU holds (LDS) puts two waves on every SIMD instead of one
-        hipLaunchKernelGGL(sppf_pool_lds_kernel, dim3(batch * (C / cw)), dim3(512), lds, s, buf, H, W, C, cw);
+        launch_lds<sppf_pool_lds_kernel>(dim3(batch * (C / cw)), dim3(512), lds, 160 * 1024, s, buf, H, W, C, cw);
         return;
     }
     const int total = batch * H * W * (C >> 3);

@@ -521,8 +521,7 @@ int front_min_stage_bytes(int tile_y) { return (2 * tile_y + 1) * 2 * C0HALF * 3
 // Raises the kernels' dynamic-LDS limit (default 64 KiB); call once per process before the first launch / capture.
 bool front_prepare()
 {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(front_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, kFrontStageMax) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void *>(front_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, kFrontStageMax) == hipSuccess;
+    return raise_lds_limit<front_kernel<4>>(kFrontStageMax) && raise_lds_limit<front_kernel<8>>(kFrontStageMax);
 }
 
 bool launch_front(const FrontArgs &a, int batch, hipStream_t s)

@@ -42,7 +42,6 @@ constexpr int KQS = 32;                        // bytes per pixel of the 16-chan
 constexpr int KNT = 192;                       // three waves
 constexpr int KNP = (K1N * 8 + KNT - 1) / KNT; // 16-byte pieces of a slab per thread: 9
 static_assert(K2N == 9 * 16, "the halo region is nine MFMA tiles");
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 }  // namespace
 
 // STEPS = Cin / 64 (1, 2, 4).  A workgroup keeps its tile for `ipw` consecutive images: the slab of the next (image, slab) step

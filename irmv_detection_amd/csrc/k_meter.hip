@@ -84,8 +84,8 @@ template <bool kFast> __device__ __forceinline__ void meter_view_rows(const Mete
         const int c = seg * 64 + lane;
         if (c >= nbody) continue;
         const int q0 = head + 16 * c;
-        const u32x4_t *gp = reinterpret_cast<const u32x4_t *>(s + 3 * (size_t)q0);
-        const u32x4_t v0 = gp[0], v1 = gp[1], v2 = gp[2];
+        const u32x4 *gp = reinterpret_cast<const u32x4 *>(s + 3 * (size_t)q0);
+        const u32x4 v0 = gp[0], v1 = gp[1], v2 = gp[2];
         const uint32_t w[12] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3], v2[0], v2[1], v2[2], v2[3]};
         if (kFast) {   // sixteen times one pixel: its three dwords repeat, and they are that pixel's bytes in rotation
             const uint32_t p0 = w[0] & 255u, p1 = (w[0] >> 8) & 255u, p2 = (w[0] >> 16) & 255u;
@@ -136,7 +136,7 @@ template <bool kFast> __device__ __forceinline__ void meter_raw_rows(const Meter
         const int c = seg * 64 + lane;
         if (c >= nbody) continue;
         const int q0 = head + 16 * c;
-        const u32x4_t v = *reinterpret_cast<const u32x4_t *>(s + q0);
+        const u32x4 v = *reinterpret_cast<const u32x4 *>(s + q0);
         const uint32_t w[4] = {v[0], v[1], v[2], v[3]};
         const int odd = (g.bx + q0) & 1;              // x parity of the group's first site; alternates from there
         const uint32_t row_e = odd ? row_at[1] : row_at[0], row_o = odd ? row_at[0] : row_at[1];

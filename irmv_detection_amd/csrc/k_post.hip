@@ -24,8 +24,6 @@
 #include "irmv_common.hpp"
 #include "pnp_device.hpp"
 
-#include <mutex>
-
 namespace irmv {
 
 // exp(x) as a fixed sequence of fp32 operations (same sequence in oracle/orc_post.c)
@@ -310,18 +308,7 @@ void launch_scan_decode(const PostArgs &a, int batch, hipStream_t s)
     const int per = scan_quads_per_block(a.A, a.nc);
     const size_t lds = (size_t)(per / 4) * a.nc * sizeof(unsigned long long);
     const int blocks = std::max(kScanBlocks, (a.A * 4 + per - 1) / per);
-    static std::mutex mu;
-    static size_t raised[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (raised[dev & 63] < lds) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(scan_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            raised[dev & 63] = lds;
-        }
-    }
-    hipLaunchKernelGGL(scan_decode_kernel, dim3(blocks, batch), dim3(256), lds, s, a, per);
+    launch_lds<scan_decode_kernel>(dim3(blocks, batch), dim3(256), lds, lds, s, a, per);
 }
 #endif   // IRMV_ALT_TU
 
@@ -1287,9 +1274,9 @@ __device__ __forceinline__ void emit_records(const PostArgs &a, const NmsLds &L,
 __device__ __forceinline__ void store_records(const PostArgs &a, const NmsLds &L, int b, int kept, int tid)
 {
     constexpr int kVec = sizeof(DevDet) / 16;
-    const u32x4_t *src = reinterpret_cast<const u32x4_t *>(L.det_staging());
-    u32x4_t *dst = reinterpret_cast<u32x4_t *>(a.dets + (size_t)b * a.max_det);
-    const u32x4_t zero = {0u, 0u, 0u, 0u};
+    const u32x4 *src = reinterpret_cast<const u32x4 *>(L.det_staging());
+    u32x4 *dst = reinterpret_cast<u32x4 *>(a.dets + (size_t)b * a.max_det);
+    const u32x4 zero = {0u, 0u, 0u, 0u};
     for (int i = tid; i < a.max_det * kVec; i += blockDim.x) dst[i] = i < kept * kVec ? src[i] : zero;
 }
 

@@ -21,8 +21,6 @@
 // lives in lane j % 64, register j / 64; max_det <= 256 = 4 registers), so it needs neither LDS hand-over nor barriers.
 #include "irmv_common.hpp"
 
-#include <mutex>
-
 namespace irmv {
 
 constexpr int kTileThreads = 1024;
@@ -142,17 +140,7 @@ __global__ __launch_bounds__(kTileThreads) void tile_merge_kernel(TileArgs a, in
 
 bool tile_merge_prepare()
 {
-    static std::mutex mu;
-    static bool raised[64] = {false};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    if (!raised[dev & 63]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(tile_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)tile_lds_bytes(kMaxTiles, kMaxDetCap)) != hipSuccess) { (void)hipGetLastError(); return false; }
-        raised[dev & 63] = true;
-    }
-    return true;
+    return raise_lds_limit<tile_merge_kernel>(tile_lds_bytes(kMaxTiles, kMaxDetCap));
 }
 
 void launch_tile_merge(const TileArgs &a, hipStream_t s)

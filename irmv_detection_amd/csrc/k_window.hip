@@ -28,20 +28,20 @@ namespace irmv {
 
 constexpr int kCropBlocksMax = 256;   // workgroups per frame: one frame alone still reaches every CU
 
-__device__ __forceinline__ u32x4_t shfl_down1(const u32x4_t v)
+__device__ __forceinline__ u32x4 shfl_down1(const u32x4 v)
 {
-    u32x4_t r;
+    u32x4 r;
 #pragma unroll
     for (int i = 0; i < 4; i++) r[i] = (unsigned int)__shfl_down((int)v[i], 1);
     return r;
 }
 
 // bytes [m, m + 16) of the 32 bytes lo : hi, m in [1, 15] and the same for every lane of the wave
-__device__ __forceinline__ u32x4_t funnel(const u32x4_t lo, const u32x4_t hi, int m)
+__device__ __forceinline__ u32x4 funnel(const u32x4 lo, const u32x4 hi, int m)
 {
     const unsigned int x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     const unsigned int sh = (unsigned int)m & 3u;
-    u32x4_t o;
+    u32x4 o;
     switch (m >> 2) {   // (static register indices in every arm: a runtime index would put x in scratch)
     case 0:
 #pragma unroll
@@ -99,18 +99,18 @@ __global__ __launch_bounds__(256) void window_crop_kernel(CropArgs a)
         const uint8_t *al = sp - m;
         // the aligned source chunk of this lane's first byte; chunk nbody is loaded too (its left neighbour's second half)
         const bool have = c <= nbody && al >= frame && al + 16 <= frame_end;
-        u32x4_t lo = (u32x4_t){0u, 0u, 0u, 0u};
-        if (have) lo = *reinterpret_cast<const u32x4_t *>(al);
-        u32x4_t hi = shfl_down1(lo);
+        u32x4 lo = (u32x4){0u, 0u, 0u, 0u};
+        if (have) lo = *reinterpret_cast<const u32x4 *>(al);
+        u32x4 hi = shfl_down1(lo);
         bool have_hi = __shfl_down((int)have, 1) != 0;
         if (lane == 63 && valid && m != 0) {         // no lane to its right
             have_hi = al + 32 <= frame_end;
-            if (have_hi) hi = *reinterpret_cast<const u32x4_t *>(al + 16);
+            if (have_hi) hi = *reinterpret_cast<const u32x4 *>(al + 16);
         }
         if (!valid) continue;
         uint8_t *dp = d + head + 16 * (size_t)c;
-        if (m == 0 && have) *reinterpret_cast<u32x4_t *>(dp) = lo;
-        else if (m != 0 && have && have_hi) *reinterpret_cast<u32x4_t *>(dp) = funnel(lo, hi, m);
+        if (m == 0 && have) *reinterpret_cast<u32x4 *>(dp) = lo;
+        else if (m != 0 && have && have_hi) *reinterpret_cast<u32x4 *>(dp) = funnel(lo, hi, m);
         else {
 #pragma unroll
             for (int k = 0; k < 16; k++) dp[k] = sp[k];
